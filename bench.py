@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X NNPOps hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--atoms 10000] [--no-cpu-baseline] [--no-side]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--atoms 10000] [--no-cpu-baseline] [--no-side] [--dump-outputs DIR]
 
 Workload (BASELINE.json metric: "AEV+forces (energy+grad evals/sec) per GPU, 10k-atom box"):
 one *step* = one full ANI-2x symmetry-function evaluation of a 10 000-atom periodic box --
@@ -431,6 +431,30 @@ class Ranks:
 
 
 # =============================================================================================
+# --dump-outputs: what the timed path computed, for comparing two builds output for output
+# =============================================================================================
+DUMP_LIMIT_BYTES = 60 << 20    # data of all files together; the .npy headers stay far inside a 64 MB budget
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """Write {name: [rows, ...] tensor} as <out_dir>/<name>.npy in float32.  The arrays share their first (atom) dimension;
+    when together they hold more than DUMP_LIMIT_BYTES, every file gets the same sorted sample of rows, drawn with `seed`
+    from the row count alone, so that two runs with the same arguments write the same rows."""
+    import numpy as np
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    rows = {a.shape[0] for a in host.values()}
+    assert len(rows) == 1, {k: a.shape for k, a in host.items()}
+    rows = rows.pop()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(seed).choice(rows, rows * DUMP_LIMIT_BYTES // total, replace=False))
+        host = {k: a[keep] for k, a in host.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(a))
+
+
+# =============================================================================================
 # headline: ANI-2x AEV forward+backward, 10 000-atom periodic box
 # =============================================================================================
 def run_aev(args, R):
@@ -554,6 +578,8 @@ def run_aev(args, R):
     assert bool(torch.isfinite(grad).all())
     if dist:
         assert bool(torch.equal(gathered[last][rank * n:(rank + 1) * n], grad))
+    if args.dump_outputs and rank == 0:                       # the last timed step's results (rank 0's own frame)
+        dump_outputs(args.dump_outputs, {"radial": radial, "angular": angular, "position_grad": grad})
     elapsed = R.max_over_ranks(elapsed)
     if rank != 0:
         return None
@@ -1568,7 +1594,14 @@ def main():
     ap.add_argument("--workload", default="aev", choices=sorted(WORKLOADS),
                     help="aev: the headline metric (default, with the others attached under 'side'); the rest run one BASELINE "
                          "configuration alone: latency = config 1, torchani = 2, cfconv = 3, conformers = 4, neighbors = 5")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (radial and angular AEV, dE/dpositions) as "
+                         "DIR/<name>.npy in float32; above 60 MiB in all, the same seeded sample of atom rows from each")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "aev":
+        ap.error("--dump-outputs writes the outputs of the headline workload (--workload aev)")
     spawn_ranks_if_needed(args)
     R = Ranks()
     if args.workload != "aev":

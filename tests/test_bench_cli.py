@@ -60,3 +60,37 @@ def test_cpu_worker_mode_times_one_frame():
     """The 'all cores' CPU figure starts one `bench.py --cpu-worker` per core; the worker must not need torch or a GPU."""
     out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--cpu-worker", "300", "5"], cwd=ROOT)
     assert float(out.decode().strip()) > 0
+
+
+def test_dump_outputs_writes_float32_files_and_a_seeded_row_sample(tmp_path, monkeypatch):
+    """--dump-outputs: every array as <name>.npy in float32, whole while it fits the budget; above it, the same sorted rows of
+    every array, the same rows from run to run."""
+    import numpy as np
+    import torch
+    bench = _bench()
+    g = torch.Generator().manual_seed(0)
+    arrays = {"radial": torch.randn(500, 112, generator=g), "angular": torch.randn(500, 896, generator=g),
+              "position_grad": torch.randn(500, 3, generator=g)}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    for k, v in arrays.items():
+        a = np.load(tmp_path / "whole" / f"{k}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, v.numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 100 * (112 + 896 + 3) * 4)       # room for 100 of the 500 rows
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    total = sum(os.path.getsize(tmp_path / "a" / f"{k}.npy") for k in arrays)
+    assert total <= bench.DUMP_LIMIT_BYTES + 3 * 128                                 # (+ one .npy header per file)
+    rows = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in arrays}
+    assert all(a.shape[0] == 100 for a in rows.values())
+    keep = [int(np.flatnonzero((arrays["position_grad"].numpy() == r).all(1))[0]) for r in rows["position_grad"]]
+    assert keep == sorted(keep) and len(set(keep)) == 100
+    for k, v in arrays.items():
+        assert np.array_equal(rows[k], v.numpy()[keep])
+        assert np.array_equal(np.load(tmp_path / "b" / f"{k}.npy"), rows[k])
+
+
+@pytest.mark.parametrize("argv, message", [(["--steps", "0"], "--steps must be at least 1"),
+                                           (["--dump-outputs", "d", "--workload", "cfconv"], "--dump-outputs writes")])
+def test_command_line_refuses_what_it_cannot_time_or_dump(argv, message):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv], cwd=ROOT, capture_output=True, text=True)
+    assert out.returncode == 2 and message in out.stderr, out.stderr

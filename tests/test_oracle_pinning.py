@@ -1,6 +1,10 @@
 """Pin the oracle (CPU, no GPU needed): against the golden vectors the reference's own tests hold,
-against the reference's own sources compiled in place (oracle/_ref, when present), and against
-fixtures produced by the reference CPU torch op (tests/golden/neighbors_ref.npz)."""
+against what the reference's own sources compute (tests/golden/oracle_pinning_ref.json, and the sources
+compiled in place under oracle/_ref when present), and against fixtures produced by the reference CPU
+torch op (tests/golden/neighbors_ref.npz)."""
+import hashlib
+import json
+
 import numpy as np
 import pytest
 
@@ -9,7 +13,22 @@ from nnpops_amd import workloads
 from oracle import (AniOracle, CFConvNeighborsOracle, CFConvOracle, neighbor_pairs_backward_oracle,
                     neighbor_pairs_oracle)
 
-needs_ref = pytest.mark.skipif(not oracle.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
+REF_OUTPUTS = "oracle_pinning_ref.json"     # what oracle/_ref computes on the cases below (make_golden_oracle_pinning.py)
+
+
+def digest(arr):
+    """dtype, shape and SHA-256 of the bytes: equal digests <=> bitwise equal arrays."""
+    arr = np.ascontiguousarray(arr)
+    return {"dtype": arr.dtype.str, "shape": list(arr.shape), "sha256": hashlib.sha256(arr.tobytes()).hexdigest()}
+
+
+def _ref_outputs(golden_dir):
+    with open(f"{golden_dir}/{REF_OUTPUTS}") as f:
+        return json.load(f)
+
+
+def _assert_bitwise(got, want):
+    assert got.dtype == want.dtype and got.shape == want.shape and np.array_equal(got, want)
 
 
 # ---------------------------------------------------------------- ANI
@@ -54,10 +73,11 @@ def test_ani_oracle_gradient_is_consistent(golden_dir, torchani):
     _fd_check(energy, grad, g["positions"].astype(np.float64))
 
 
-@needs_ref
-@pytest.mark.parametrize("kind", ["vacuum", "cubic", "triclinic"])
-@pytest.mark.parametrize("torchani", [True, False])
-def test_ani_oracle_bitwise_equals_reference(kind, torchani):
+ANI_KINDS = ["vacuum", "cubic", "triclinic"]
+
+
+def ani_outputs(cls, kind, torchani):
+    """{radial, angular, grad} of AniOracle or RefAni on one seeded case."""
     rf, af = workloads.ani2x_functions()
     if kind == "vacuum":
         pos, species = workloads.conformer(50, 0)
@@ -66,14 +86,23 @@ def test_ani_oracle_bitwise_equals_reference(kind, torchani):
         pos, species, box = workloads.random_box(200, seed=1)
     else:
         pos, species, box = workloads.triclinic_box(180, seed=2)
-    a = AniOracle(7, 5.1, 3.5, species, rf, af, periodic=box is not None, torchani=torchani)
-    b = oracle.RefAni(7, 5.1, 3.5, species, rf, af, periodic=box is not None, torchani=torchani)
-    ra, aa = a.forward(pos, box)
-    rb, ab = b.forward(pos, box)
-    assert np.array_equal(ra, rb) and np.array_equal(aa, ab)
+    o = cls(7, 5.1, 3.5, species, rf, af, periodic=box is not None, torchani=torchani)
+    r, a = o.forward(pos, box)
     rng = np.random.default_rng(3)
-    wr, wa = rng.standard_normal(ra.shape).astype(np.float32), rng.standard_normal(aa.shape).astype(np.float32)
-    assert np.array_equal(a.backward(wr, wa), b.backward(wr, wa))
+    wr, wa = rng.standard_normal(r.shape).astype(np.float32), rng.standard_normal(a.shape).astype(np.float32)
+    return {"radial": r, "angular": a, "grad": o.backward(wr, wa)}
+
+
+@pytest.mark.parametrize("kind", ANI_KINDS)
+@pytest.mark.parametrize("torchani", [True, False])
+def test_ani_oracle_bitwise_equals_reference(golden_dir, kind, torchani):
+    got = ani_outputs(AniOracle, kind, torchani)
+    ref = _ref_outputs(golden_dir)
+    for name, arr in got.items():
+        assert digest(arr) == ref[f"ani_{kind}_torchani{int(torchani)}_{name}"], name
+    if oracle.have_ref():
+        for name, arr in ani_outputs(oracle.RefAni, kind, torchani).items():
+            _assert_bitwise(got[name], arr)
 
 
 # ---------------------------------------------------------------- CFConv
@@ -89,10 +118,8 @@ def test_cfconv_oracle_vs_schnetpack_golden(golden_dir, tag):
     np.testing.assert_allclose(y, g[f"{tag}_output"], rtol=2e-6, atol=1e-6 * np.abs(y).max())
 
 
-@needs_ref
-@pytest.mark.parametrize("periodic", [False, True])
-@pytest.mark.parametrize("act", ["ssp", "tanh"])
-def test_cfconv_oracle_bitwise_equals_reference(periodic, act):
+def cfconv_outputs(NB, CF, periodic, act):
+    """[forward, input grad, position grad, *neighbour export] of the oracle's or the reference's classes on one seeded case."""
     pos, _, box = workloads.random_box(150, seed=5)
     box = box if periodic else None
     rng = np.random.default_rng(6)
@@ -100,14 +127,24 @@ def test_cfconv_oracle_bitwise_equals_reference(periodic, act):
     w1, w2 = rng.standard_normal((W, G)).astype(np.float32) * 0.3, rng.standard_normal((W, W)).astype(np.float32) * 0.2
     b1, b2 = rng.standard_normal(W).astype(np.float32), rng.standard_normal(W).astype(np.float32)
     x, gy = rng.standard_normal((150, W)).astype(np.float32), rng.standard_normal((150, W)).astype(np.float32)
-    res = []
-    for NB, CF in ((CFConvNeighborsOracle, CFConvOracle), (oracle.RefCFConvNeighbors, oracle.RefCFConv)):
-        nb = NB(150, 4.0, periodic)
-        nb.build(pos, box)
-        cf = CF(150, W, G, 4.0, 0.3, act, w1, b1, w2, b2, periodic=periodic)
-        res.append((cf.forward(nb, pos, x, box),) + cf.backward(nb, pos, x, gy, box) + nb.export())
-    for a, b in zip(*res):
-        assert np.array_equal(a, b)
+    nb = NB(150, 4.0, periodic)
+    nb.build(pos, box)
+    cf = CF(150, W, G, 4.0, 0.3, act, w1, b1, w2, b2, periodic=periodic)
+    return [cf.forward(nb, pos, x, box), *cf.backward(nb, pos, x, gy, box), *nb.export()]
+
+
+@pytest.mark.parametrize("periodic", [False, True])
+@pytest.mark.parametrize("act", ["ssp", "tanh"])
+def test_cfconv_oracle_bitwise_equals_reference(golden_dir, periodic, act):
+    got = cfconv_outputs(CFConvNeighborsOracle, CFConvOracle, periodic, act)
+    ref = _ref_outputs(golden_dir)
+    prefix = f"cfconv_periodic{int(periodic)}_{act}_"
+    assert len(got) == sum(k.startswith(prefix) for k in ref)
+    for k, arr in enumerate(got):
+        assert digest(arr) == ref[f"{prefix}{k}"], k
+    if oracle.have_ref():
+        for a, b in zip(got, cfconv_outputs(oracle.RefCFConvNeighbors, oracle.RefCFConv, periodic, act)):
+            _assert_bitwise(a, b)
 
 
 # ---------------------------------------------------------------- getNeighborPairs
