@@ -250,7 +250,10 @@ int nnpops_neighbor_pairs_backward_ws(int dtype, int num_atoms, int64_t num_slot
 /* Backward WITHOUT atomics for a list the forward op emitted (round 6; replaces the atomicAdd scatter of getNeighborPairsCUDA.cu:80-101
  * by an owner-computes gather).  Such a list is grouped by neighbors[0] (rows ascending, see above); nnpops_neighbor_pairs_build_index
  * adds the TRANSPOSED view -- the slots sorted by neighbors[1], ascending slot inside an atom's group -- plus the first / last slot of
- * every atom's group on either side:
+ * every atom's group on either side.  The list must be COMPACTED, as the forward op emits it when max_num_pairs > 0: the used slots
+ * first, grouped by neighbors[0], and -1 only behind them (a tile whose first slot is -1 is skipped whole).  A max_num_pairs == -1
+ * list, whose -1 slots are interleaved with the pairs, must go through nnpops_neighbor_pairs_backward_ws.  A slot whose neighbors[1]
+ * lies outside [0, num_atoms) is dropped from the transposed view like an unused slot (it stays in its row's run of slots).
  *   index: device int32 [nnpops_neighbor_pairs_index_ints(num_atoms, num_slots)], 8-byte aligned; a function of `neighbors` alone, so
  *          the torch op builds it once in forward() when the positions require a gradient and saves it with the list;
  *   workspace: device scratch, 256-byte aligned, nnpops_neighbor_pairs_index_workspace_bytes(...) bytes (free after the call).

@@ -357,7 +357,12 @@ def neighbor_pairs_backward(num_atoms, neighbors, deltas, distances, grad_deltas
 
 
 def neighbor_pairs_build_index(num_atoms, neighbors):
-    """Transposed index of a list the forward op emitted (grouped by neighbors[0]): int32 tensor for neighbor_pairs_backward_indexed."""
+    """Transposed index of a list the forward op emitted: int32 tensor for neighbor_pairs_backward_indexed and pme_direct(index=).
+
+    The list must be compacted (max_num_pairs > 0): used slots first, grouped by neighbors[0], -1 only behind them.  A
+    max_num_pairs == -1 list interleaves -1 slots with the pairs and must take neighbor_pairs_backward instead.  Slots whose
+    neighbors[1] lies outside [0, num_atoms) are dropped from the transposed view like unused slots.  Up to 262 144 atoms
+    (NNPOPS_PAIRS_INDEX_MAX_ATOMS); beyond, NNPOpsHipError with NNPOPS_ERR_UNSUPPORTED."""
     dev = neighbors.device
     L = lib()
     slots = neighbors.size(1)
@@ -369,7 +374,8 @@ def neighbor_pairs_build_index(num_atoms, neighbors):
 
 
 def neighbor_pairs_backward_indexed(num_atoms, neighbors, deltas, distances, grad_deltas, grad_distances, index):
-    """The backward pass without atomics (owner-computes gather over the transposed index)."""
+    """The backward pass without atomics (owner-computes gather over the transposed index).  `index` must have been built by
+    neighbor_pairs_build_index from exactly this `neighbors`, a compacted list (see there); any other list takes neighbor_pairs_backward."""
     dev, dt = deltas.device, deltas.dtype
     grad_positions = torch.empty((num_atoms, 3), dtype=dt, device=dev)
     L = lib()
@@ -386,7 +392,8 @@ def neighbor_pairs_backward_indexed(num_atoms, neighbors, deltas, distances, gra
 def pme_direct(positions, charges, neighbors, deltas, distances, exclusions, alpha, coulomb, index=None):
     """Direct-space PME on a pair list (reference src/pytorch/pme/pmeCUDA.cu:30-100) through the C ABI.
     -> (energy float32[1], dE/dpositions [N, 3], dE/dcharges [N]); `exclusions` int32 [N, max], rows sorted descending.
-    index: the list's transposed index (neighbor_pairs_build_index) -- the list must then be one the forward op emitted: no atomics."""
+    index: the list's transposed index (neighbor_pairs_build_index) -- the list must then be a compacted one the forward op emitted
+    (used slots first, grouped by neighbors[0], -1 only behind them): no atomics."""
     _dev_f32(positions, "positions")
     _dev_f32(charges, "charges")
     n, pairs = positions.size(0), neighbors.size(1)

@@ -43,6 +43,9 @@ constexpr int kBucketWaves = 16;
 
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// tiles of the first level: at least one, so that an empty list still has its row of the histogram (the workspace is sized by this too)
+int64_t index_tiles(int64_t num_slots) { return std::max<int64_t>(1, (num_slots + kTile - 1) / kTile); }
+
 // workgroup b runs on XCD b % 8: give every XCD a contiguous eighth of the tiles (device_common.h: xcd_contiguous_wave_id)
 __device__ __forceinline__ int xcd_contiguous_tile() {
     const int g = blockIdx.x, n = gridDim.x, xcd = g & 7;
@@ -312,7 +315,7 @@ int64_t nnpops_neighbor_pairs_index_ints(int num_atoms, int64_t num_slots) {
 
 int64_t nnpops_neighbor_pairs_index_workspace_bytes(int num_atoms, int64_t num_slots) {
     if (num_atoms <= 0 || num_slots < 0) return 0;
-    const size_t ntiles = (size_t)((num_slots + kTile - 1) / kTile) + 8;
+    const size_t ntiles = (size_t)index_tiles(num_slots) + 8;
     // the {column, slot} records by bucket | histogram [buckets][tiles] | bucket totals
     return (int64_t)(align256(sizeof(int2) * (size_t)num_slots) + align256(sizeof(int) * kMaxBuckets * ntiles) + align256(sizeof(int) * kMaxBuckets) + 512);
 }
@@ -332,7 +335,7 @@ int nnpops_neighbor_pairs_build_index(int num_atoms, int64_t num_slots, const in
     int* order = index;
     int2* row_seg = (int2*)(index + ((num_slots + 1) & ~1ll));      // (int2: 8-byte aligned behind an odd number of slots)
     int2* col_seg = row_seg + num_atoms;
-    const int ntiles = std::max(1, (int)((num_slots + kTile - 1) / kTile));
+    const int ntiles = (int)index_tiles(num_slots);      // (num_slots < 2^31: checked above)
     char* ws = (char*)workspace;
     auto take = [&](size_t bytes) { char* p = ws; ws += align256(bytes); return p; };
     int2* records = (int2*)take(sizeof(int2) * (size_t)num_slots);
