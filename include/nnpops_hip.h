@@ -274,7 +274,8 @@ int nnpops_neighbor_pairs_backward_indexed(int dtype, int num_atoms, int64_t num
 
 /* ------------------------------------------------------------------------------------------
  * PME, direct-space part (replaces computeDirect: src/pytorch/pme/pmeCUDA.cu:30-100, pmeCPU.cpp:75-163) -- the immediate
- * consumer of the pair list above (src/pytorch/pme/pme.py:163-165).  The reciprocal-space part is not built.
+ * consumer of the pair list above (src/pytorch/pme/pme.py:163-165).  The reciprocal-space part follows below
+ * (nnpops_pme_reciprocal_*).
  * ------------------------------------------------------------------------------------------ */
 /* positions: device [num_atoms][3]; charges: device [num_atoms]; neighbors int32 [2][num_pairs], deltas [num_pairs][3],
  * distances [num_pairs]: the outputs of nnpops_neighbor_pairs_forward (float32), slots holding -1 are skipped;
@@ -301,6 +302,34 @@ int nnpops_pme_direct_indexed(int num_atoms, int64_t num_pairs, int max_exclusio
                               const int32_t* neighbors, const float* deltas, const float* distances, const int32_t* exclusions,
                               const int32_t* index, float alpha, float coulomb, float* energy, float* position_deriv,
                               float* charge_deriv, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * PME, reciprocal-space part (replaces computeReciprocal: src/pytorch/pme/pmeCUDA.cu:102-430, pmeCPU.cpp:174-364).  Three passes
+ * around two FFTs that are the CALLER's (torch.fft / hipFFT; this library links no FFT):
+ *   1. nnpops_pme_reciprocal_spread: positions, charges -> real grid float32 [gridx][gridy][gridz] (fully overwritten):
+ *      sum over atoms of q sqrt(coulomb) thx thy thz at (base + i) mod grid, B-splines of `order` (4 or 5);
+ *   2. the caller: complex grid = rfftn(real grid) with the DEFAULT norm (unscaled forward transform), complex64
+ *      [gridx][gridy][gridz / 2 + 1], contiguous;
+ *   3. nnpops_pme_reciprocal_convolve: multiplies the complex grid IN PLACE by exp(-pi^2 m^2 / alpha^2) / (pi V m^2 bx by bz)
+ *      (0 at m = 0; bx, by, bz the B-spline moduli, device float32 [gridx], [gridy], [gridz]) and writes energy (device float[1])
+ *      = 0.5 sum_k w |S(k)|^2 eterm, w = 2 for 0 < kz <= (gridz - 1) / 2, else 1.  The self energy is NOT included.
+ *   4. the caller: real grid = irfftn(scaled complex grid, s = (gridx, gridy, gridz), norm = "forward") (unscaled inverse);
+ *   5. nnpops_pme_reciprocal_interpolate: dE/dpositions [num_atoms][3] and dE/dcharges [num_atoms] (fully overwritten) from
+ *      the weights spread stored in the workspace.
+ * box_vectors: device float32 [3][3], reduced triclinic (a = (a0, 0, 0), b = (b0, b1, 0), c = (c0, c1, c2)), read on the device by
+ * every pass (never copied to the host).  workspace: device scratch of nnpops_pme_reciprocal_workspace_bytes(...) bytes, the SAME
+ * buffer with the same sizes for all three calls of one evaluation (spread stores the splines in it for interpolate).  No float
+ * atomics: the grid, the energy and the derivatives are bitwise reproducible.  Orders other than 4 and 5: NNPOPS_ERR_INVALID_ARGUMENT.
+ * Graph-capturable.  Additive. */
+int64_t nnpops_pme_reciprocal_workspace_bytes(int num_atoms, int gridx, int gridy, int gridz, int order);
+int nnpops_pme_reciprocal_spread(int num_atoms, int gridx, int gridy, int gridz, int order, const float* positions, const float* charges,
+                                 const float* box_vectors, float coulomb, float* real_grid, void* workspace, void* stream);
+int nnpops_pme_reciprocal_convolve(int num_atoms, int gridx, int gridy, int gridz, int order, const float* box_vectors, float alpha,
+                                   const float* xmoduli, const float* ymoduli, const float* zmoduli, void* recip_grid, float* energy,
+                                   void* workspace, void* stream);
+int nnpops_pme_reciprocal_interpolate(int num_atoms, int gridx, int gridy, int gridz, int order, const float* charges,
+                                      const float* box_vectors, float coulomb, const float* real_grid, float* position_deriv,
+                                      float* charge_deriv, void* workspace, void* stream);
 
 /* ---- dense layers of the ANI atomic networks (reference src/pytorch/BatchedNN.cpp:30-50, BatchedNN.py:37-122) ----
  * C[M x N] = A[M x K] B with fp32 in and out; the products run on the half-precision matrix instruction with every

@@ -85,6 +85,13 @@ SIGNATURES = {
     "nnpops_pme_direct_indexed_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int]),
     "nnpops_pme_direct_indexed": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nnpops_pme_reciprocal_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nnpops_pme_reciprocal_spread": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nnpops_pme_reciprocal_convolve": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nnpops_pme_reciprocal_interpolate": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_neighbor_pairs_backward": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_neighbor_pairs_backward_workspace_bytes": (C.c_int64, [C.c_int]),
@@ -418,6 +425,35 @@ def pme_direct(positions, charges, neighbors, deltas, distances, exclusions, alp
                                    _ptr(deltas.contiguous()), _ptr(distances.contiguous()), _ptr(exclusions) if max_excl else None,
                                    float(alpha), float(coulomb), _ptr(energy), _ptr(pos_deriv), _ptr(charge_deriv), _ptr(ws),
                                    _stream_ptr(dev)))
+    return energy, pos_deriv, charge_deriv
+
+
+def pme_reciprocal(positions, charges, box_vectors, gridx, gridy, gridz, order, alpha, coulomb, xmoduli, ymoduli, zmoduli):
+    """Reciprocal-space PME (reference src/pytorch/pme/pmeCUDA.cu:102-430) through the C ABI: spread -> torch.fft.rfftn ->
+    convolve -> torch.fft.irfftn(norm="forward") -> interpolate.  -> (energy float32[1] without the self energy, dE/dpositions
+    [N, 3], dE/dcharges [N]).  Orders 4 and 5."""
+    _dev_f32(positions, "positions")
+    _dev_f32(charges, "charges")
+    _dev_f32(box_vectors, "box_vectors", (3, 3))
+    dev = positions.device
+    n = positions.size(0)
+    mods = [_dev_f32(m.to(device=dev, dtype=torch.float32).contiguous(), name, (k,))
+            for m, name, k in ((xmoduli, "xmoduli", gridx), (ymoduli, "ymoduli", gridy), (zmoduli, "zmoduli", gridz))]
+    L = lib()
+    ws = torch.empty((int(L.nnpops_pme_reciprocal_workspace_bytes(n, gridx, gridy, gridz, order)),), dtype=torch.uint8, device=dev)
+    real = torch.empty((gridx, gridy, gridz), dtype=torch.float32, device=dev)
+    energy = torch.empty((1,), dtype=torch.float32, device=dev)
+    pos_deriv = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    charge_deriv = torch.empty((n,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _check(L.nnpops_pme_reciprocal_spread(n, gridx, gridy, gridz, order, _ptr(positions), _ptr(charges), _ptr(box_vectors),
+                                              float(coulomb), _ptr(real), _ptr(ws), _stream_ptr(dev)))
+        recip = torch.fft.rfftn(real).contiguous()
+        _check(L.nnpops_pme_reciprocal_convolve(n, gridx, gridy, gridz, order, _ptr(box_vectors), float(alpha), _ptr(mods[0]),
+                                                _ptr(mods[1]), _ptr(mods[2]), _ptr(recip), _ptr(energy), _ptr(ws), _stream_ptr(dev)))
+        grid = torch.fft.irfftn(recip, s=(gridx, gridy, gridz), norm="forward").contiguous()
+        _check(L.nnpops_pme_reciprocal_interpolate(n, gridx, gridy, gridz, order, _ptr(charges), _ptr(box_vectors), float(coulomb),
+                                                   _ptr(grid), _ptr(pos_deriv), _ptr(charge_deriv), _ptr(ws), _stream_ptr(dev)))
     return energy, pos_deriv, charge_deriv
 
 

@@ -7,7 +7,7 @@
 //     dE/dr / r = -k q1 q2 (erfc(alpha r) + 2 alpha r exp(-(alpha r)^2) / sqrt(pi)) / r^3      (force along delta)
 // and for every excluded pair (taken WITHOUT periodic wrap, each once) the erf() part is subtracted again, because the
 // reciprocal-space sum cannot leave it out.  Outputs: the energy and dE/dpositions, dE/dcharges (the autograd backward
-// only scales them).  The reciprocal-space part (charge spreading + 3-D FFT) is outside this build's scope.
+// only scales them).  The reciprocal-space part (charge spreading + 3-D FFT) is pme_recip.hip.
 //
 // Layout for MI355X: OWNER COMPUTES, no float atomics (the first version issued ~12 M device-scope float
 // atomics at 100 000 atoms and was bound by them: 0.6 ms).  Two launches:

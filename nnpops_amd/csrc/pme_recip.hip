@@ -1,0 +1,525 @@
+// pme_recip.hip -- reciprocal-space part of Particle Mesh Ewald (smooth PME, Essmann et al. 1995).
+//
+// Replaces the reference's computeReciprocal (reference src/pytorch/pme/pmeCUDA.cu:102-430, CPU form
+// src/pytorch/pme/pmeCPU.cpp:174-364).  The caller runs the two FFTs (torch.fft / hipFFT); this file holds the passes around
+// them:
+//   spread       positions, charges -> real grid Q[Kx][Ky][Kz] = sum_atoms q sqrt(coulomb) thx thy thz at (base + i) mod K
+//   convolve     complex grid [Kx][Ky][Kz/2+1] (rfftn of Q, default norm) *= eterm in place; energy = 0.5 sum w eterm |S|^2
+//   interpolate  real grid (irfftn of the scaled complex grid, norm="forward") -> dE/dpositions, dE/dcharges
+//
+// Layout for MI355X: NO float atomics, everything bitwise reproducible (the reference scatters order^3 float atomics per atom).
+//   pme_recip_spline     one lane per atom: wraps the atom into the box (z -> y -> x), stores the base grid index and the order x 3
+//                        B-spline weights and derivative weights in the workspace (the backward reuses them), and counts the atom
+//                        into the BRICK (4 x 4 x 16 grid points) of its base index with one integer atomic.
+//   pme_recip_scan       one workgroup: exclusive prefix of the brick counts.
+//   pme_recip_scatter    one lane per atom: a slot inside its brick's range (integer atomic: the order inside a brick is arbitrary)
+//   pme_recip_order      one wave per brick: the brick's atoms re-placed in ascending atom index (rank sort) -- the order the
+//                        spread adds them in no longer depends on the atomics.
+//   pme_recip_gather     one workgroup per brick of grid points, one lane per point (OWNER COMPUTES): the atoms whose base lies in
+//                        the brick or in its (order - 1) halo below are staged in LDS, brick after brick in a fixed order and in
+//                        ascending atom index inside a brick; every lane adds what reaches its point.  Every point is written
+//                        exactly once, so the grid needs no clearing.
+//   pme_recip_convolve   one lane per complex point; energy in double per workgroup, the partials summed in a fixed order.
+//   pme_recip_interp     one lane per atom: order^3 gather with the stored weights, owner computes.
+// The box is read on the device by every pass (never copied to the host): a captured graph follows new box values written in place.
+#include <cmath>
+
+#include "device_common.h"
+#include "host_common.h"
+
+using namespace nnpops;
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kBX = 4, kBY = 4, kBZ = 16;              // brick of grid points = one gather workgroup (kBX * kBY * kBZ == kBlock)
+constexpr int kMaxBinsPerAxis = 4;                     // bricks a cyclic window of (brick + order - 1) cells can touch
+constexpr int kConvBlocksMax = 1024;
+static_assert(kBX * kBY * kBZ == kBlock, "one lane per grid point of a brick");
+
+struct RecipBox { float r00, r10, r11, r20, r21, r22; };
+
+// the reciprocal box of a reduced triclinic box (lower triangular), the same float expressions as the reference's invertBoxVectors
+__device__ __forceinline__ RecipBox recip_box(const float* __restrict__ b) {
+    const float det = b[0] * b[4] * b[8];
+    const float s = 1.0f / det;
+    RecipBox r;
+    r.r00 = b[4] * b[8] * s;
+    r.r10 = -b[3] * b[8] * s;
+    r.r11 = b[0] * b[8] * s;
+    r.r20 = (b[3] * b[7] - b[4] * b[6]) * s;
+    r.r21 = -b[0] * b[7] * s;
+    r.r22 = b[0] * b[4] * s;
+    return r;
+}
+
+struct Dims {
+    int kx, ky, kz;          // grid
+    int nbx, nby, nbz;       // bricks per axis
+    long long nbins;
+};
+
+Dims make_dims(int gx, int gy, int gz) {
+    Dims d{gx, gy, gz, div_up(gx, kBX), div_up(gy, kBY), div_up(gz, kBZ), 0};
+    d.nbins = (long long)d.nbx * d.nby * d.nbz;
+    return d;
+}
+
+int conv_blocks(int gx, int gy, int gz) {
+    const long long points = (long long)gx * gy * (gz / 2 + 1);
+    return (int)std::min<long long>(std::max<long long>(1, (points + kBlock - 1) / kBlock), kConvBlocksMax);
+}
+
+// ---- workspace: ONE carve, used by the size query and by every entry point (they must agree) ----
+struct RecipWorkspace {
+    double* partial;      // [conv_blocks]
+    int* bin_count;       // [nbins]        integer histogram (zeroed by spread)
+    int* bin_start;       // [nbins + 1]    exclusive prefix
+    int* cursor;          // [nbins]        scatter cursors
+    int* unsorted;        // [N]            atoms by brick, arbitrary order inside a brick
+    int* sorted;          // [N]            atoms by brick, ascending inside a brick
+    int4* base;           // [N]            base grid index (x, y, z, brick)
+    float* theta;         // [N][3][order]  B-spline weights
+    float* dtheta;        // [N][3][order]  their derivatives
+    size_t bytes;
+};
+
+RecipWorkspace carve(void* workspace, int num_atoms, int gx, int gy, int gz, int order) {
+    const Dims d = make_dims(gx, gy, gz);
+    RecipWorkspace w{};
+    uintptr_t p = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
+    auto take = [&](size_t bytes) { const uintptr_t at = p; p += (bytes + 255) & ~(size_t)255; return at; };
+    const size_t n = (size_t)num_atoms;
+    w.partial = (double*)take(sizeof(double) * conv_blocks(gx, gy, gz));
+    w.bin_count = (int*)take(sizeof(int) * (size_t)d.nbins);
+    w.bin_start = (int*)take(sizeof(int) * ((size_t)d.nbins + 1));
+    w.cursor = (int*)take(sizeof(int) * (size_t)d.nbins);
+    w.unsorted = (int*)take(sizeof(int) * n);
+    w.sorted = (int*)take(sizeof(int) * n);
+    w.base = (int4*)take(sizeof(int4) * n);
+    w.theta = (float*)take(sizeof(float) * 3 * (size_t)order * n);
+    w.dtheta = (float*)take(sizeof(float) * 3 * (size_t)order * n);
+    w.bytes = (size_t)(p - (uintptr_t)workspace) + 256;
+    return w;
+}
+
+// ---- pass 1: wrap, base index, B-spline weights (the reference's computeSpline, pmeCPU.cpp:26-70, restated) ----
+template <int ORDER>
+__global__ __launch_bounds__(kBlock) void pme_recip_spline(int num_atoms, const float* __restrict__ pos, const float* __restrict__ box,
+                                                           Dims d, int4* __restrict__ base, float* __restrict__ theta,
+                                                           float* __restrict__ dtheta, int* __restrict__ bin_count) {
+    const int atom = blockIdx.x * kBlock + threadIdx.x;
+    if (atom >= num_atoms) return;
+    float b[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) b[i] = box[i];
+    const RecipBox r = recip_box(b);
+    float p[3] = {pos[3 * atom], pos[3 * atom + 1], pos[3 * atom + 2]};
+    // into the reduced box, c then b then a
+    const float rdiag[3] = {r.r00, r.r11, r.r22};
+#pragma unroll
+    for (int i = 2; i >= 0; i--) {
+        const float s = floorf(p[i] * rdiag[i]);
+#pragma unroll
+        for (int j = 0; j < 3; j++) p[j] -= s * b[3 * i + j];
+    }
+    const float t3[3] = {p[0] * r.r00 + p[1] * r.r10 + p[2] * r.r20,
+                         p[0] * 0.0f + p[1] * r.r11 + p[2] * r.r21,
+                         p[0] * 0.0f + p[1] * 0.0f + p[2] * r.r22};
+    const int K[3] = {d.kx, d.ky, d.kz};
+    int gi[3];
+    float* th = theta + (size_t)atom * 3 * ORDER;
+    float* dth = dtheta + (size_t)atom * 3 * ORDER;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const float t = (t3[i] - floorf(t3[i])) * K[i];
+        const int ti = (int)t;
+        const float dr = t - ti;
+        gi[i] = min(max(ti % K[i], 0), K[i] - 1);          // (t can round up to exactly K; a NaN position must not index outside)
+        // weights of order 2 .. ORDER-1, then the derivatives from order ORDER-1, then order ORDER
+        float w[ORDER];
+        w[ORDER - 1] = 0.f;
+        w[1] = dr;
+        w[0] = 1.f - dr;
+#pragma unroll
+        for (int j = 3; j < ORDER; j++) {
+            const float div = 1.0f / (j - 1);
+            w[j - 1] = div * dr * w[j - 2];
+#pragma unroll
+            for (int k = 1; k < j - 1; k++) w[j - k - 1] = div * ((dr + k) * w[j - k - 2] + (j - k - dr) * w[j - k - 1]);
+            w[0] = div * (1.f - dr) * w[0];
+        }
+        dth[i * ORDER] = -w[0];
+#pragma unroll
+        for (int j = 1; j < ORDER; j++) dth[i * ORDER + j] = w[j - 1] - w[j];
+        const float scale = 1.0f / (ORDER - 1);
+        w[ORDER - 1] = scale * dr * w[ORDER - 2];
+#pragma unroll
+        for (int j = 1; j < ORDER - 1; j++) w[ORDER - j - 1] = scale * ((dr + j) * w[ORDER - j - 2] + (ORDER - j - dr) * w[ORDER - j - 1]);
+        w[0] = scale * (1.f - dr) * w[0];
+#pragma unroll
+        for (int j = 0; j < ORDER; j++) th[i * ORDER + j] = w[j];
+    }
+    const int bin = (int)(((long long)(gi[0] / kBX) * d.nby + gi[1] / kBY) * d.nbz + gi[2] / kBZ);
+    base[atom] = make_int4(gi[0], gi[1], gi[2], bin);
+    atomicAdd(&bin_count[bin], 1);                        // integer: the counts are exact whatever the order
+}
+
+// ---- pass 2: exclusive prefix of the brick counts (one workgroup of 1 024 lanes walking the counts 1 024 at a time, coalesced) ----
+__global__ __launch_bounds__(1024) void pme_recip_scan(long long nbins, const int* __restrict__ count, int* __restrict__ start,
+                                                       int* __restrict__ cursor) {
+    __shared__ int wave_sums[1024 / 64];
+    int carry = 0;
+    for (long long c0 = 0; c0 < nbins; c0 += 1024) {
+        const long long i = c0 + threadIdx.x;
+        const int v = i < nbins ? count[i] : 0;
+        int incl = v;                                     // inclusive scan inside the wave
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int u = __shfl_up(incl, off, 64);
+            if (lane_id() >= off) incl += u;
+        }
+        if (lane_id() == 63) wave_sums[threadIdx.x >> 6] = incl;
+        __syncthreads();
+        int before = carry, all = 0;                      // (16 wave sums: every lane adds them up itself)
+        for (int w = 0; w < 1024 / 64; w++) {
+            const int ws = wave_sums[w];
+            before += w < (int)(threadIdx.x >> 6) ? ws : 0;
+            all += ws;
+        }
+        if (i < nbins) {
+            start[i] = before + incl - v;
+            cursor[i] = before + incl - v;
+        }
+        carry += all;
+        __syncthreads();                                  // (wave_sums is rewritten by the next chunk)
+    }
+    if (threadIdx.x == 0) start[nbins] = carry;
+}
+
+// ---- pass 3: every atom into its brick's range (arbitrary order inside the brick) ----
+__global__ __launch_bounds__(kBlock) void pme_recip_scatter(int num_atoms, const int4* __restrict__ base, int* __restrict__ cursor,
+                                                            int* __restrict__ unsorted) {
+    const int atom = blockIdx.x * kBlock + threadIdx.x;
+    if (atom >= num_atoms) return;
+    unsorted[atomicAdd(&cursor[base[atom].w], 1)] = atom;
+}
+
+// ---- pass 4: inside every brick, ascending atom index (rank sort, one wave per brick; atom indices are distinct) ----
+__global__ __launch_bounds__(kBlock) void pme_recip_order(long long nbins, const int* __restrict__ start, const int* __restrict__ unsorted,
+                                                          int* __restrict__ sorted) {
+    const long long waves = (long long)gridDim.x * (kBlock / 64);
+    for (long long bin = (long long)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); bin < nbins; bin += waves) {
+        const int s = start[bin], e = start[bin + 1];
+        for (int k = s + lane_id(); k < e; k += 64) {
+            const int a = unsorted[k];
+            int rank = 0;
+            for (int j = s; j < e; j++) rank += unsorted[j] < a;
+            sorted[s + rank] = a;
+        }
+    }
+}
+
+// bricks along one axis whose cells hold the base index of an atom that reaches a point of brick `b`: the cyclic window
+// [b*B - (order-1), b*B + B - 1] mod K, in window order (a fixed order: the gather's sum order follows it)
+__device__ int window_bins(int b, int B, int K, int nb, int order, int* out) {
+    const int len = B + order - 1;
+    if (len >= K) {                                       // the window covers the whole axis
+        for (int i = 0; i < nb; i++) out[i] = i;
+        return nb;
+    }
+    int n = 0;
+    const int first = ((b * B - (order - 1)) % K + K) % K;
+    for (int j = 0; j < len; j++) {
+        const int bin = ((first + j) % K) / B;
+        bool seen = false;
+        for (int i = 0; i < n; i++) seen |= out[i] == bin;
+        if (!seen && n < kMaxBinsPerAxis) out[n++] = bin;       // (never more than kMaxBinsPerAxis: see kMaxBinsPerAxis)
+    }
+    return n;
+}
+
+// weight of the atom with base `g0` at point `g` along one axis: every stencil slot i with (g0 + i) mod K == g (a grid smaller
+// than the order folds the stencil onto itself)
+template <int ORDER>
+__device__ __forceinline__ float axis_weight(int g, int g0, int K, const float* th) {
+    int dd = g - g0;
+    dd += dd < 0 ? K : 0;
+    float w = 0.f;
+    for (int i = dd; i < ORDER; i += K) w += th[i];
+    return w;
+}
+
+// ---- pass 5: the spread as a gather, one workgroup per brick of grid points ----
+template <int ORDER>
+__global__ __launch_bounds__(kBlock) void pme_recip_gather(Dims d, const int* __restrict__ start, const int* __restrict__ sorted,
+                                                           const int4* __restrict__ base, const float* __restrict__ theta,
+                                                           const float* __restrict__ charge, float sqrt_coulomb,
+                                                           float* __restrict__ grid) {
+    __shared__ int s_bx[kMaxBinsPerAxis], s_by[kMaxBinsPerAxis], s_bz[kMaxBinsPerAxis];
+    __shared__ int s_first[kMaxBinsPerAxis * kMaxBinsPerAxis * kMaxBinsPerAxis];
+    __shared__ int s_prefix[kMaxBinsPerAxis * kMaxBinsPerAxis * kMaxBinsPerAxis + 1];
+    __shared__ int s_ntrip;
+    __shared__ int s_base[3][kBlock];
+    __shared__ float s_th[3 * ORDER][kBlock];              // [axis * ORDER + i][slot]: x weights carry q sqrt(coulomb)
+
+    const int brick = blockIdx.x;
+    const int bz = brick % d.nbz, by = (brick / d.nbz) % d.nby, bx = brick / (d.nbz * d.nby);
+    __shared__ int s_n[3], s_count[kMaxBinsPerAxis * kMaxBinsPerAxis * kMaxBinsPerAxis];
+    // three lanes find the windows along x, y, z; one lane per brick of the window reads its range; one lane adds them up
+    if (threadIdx.x == 0) s_n[0] = window_bins(bx, kBX, d.kx, d.nbx, ORDER, s_bx);
+    if (threadIdx.x == 64) s_n[1] = window_bins(by, kBY, d.ky, d.nby, ORDER, s_by);
+    if (threadIdx.x == 128) s_n[2] = window_bins(bz, kBZ, d.kz, d.nbz, ORDER, s_bz);
+    __syncthreads();
+    const int nx = s_n[0], ny = s_n[1], nz = s_n[2];
+    if ((int)threadIdx.x < nx * ny * nz) {                // window order: x outermost, z innermost
+        const int i = threadIdx.x / (ny * nz), j = (threadIdx.x / nz) % ny, k = threadIdx.x % nz;
+        const long long bin = ((long long)s_bx[i] * d.nby + s_by[j]) * d.nbz + s_bz[k];
+        const int first = start[bin];
+        s_first[threadIdx.x] = first;
+        s_count[threadIdx.x] = start[bin + 1] - first;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int total = 0;
+        const int t = nx * ny * nz;
+        for (int u = 0; u < t; u++) { s_prefix[u] = total; total += s_count[u]; }
+        s_prefix[t] = total;
+        s_ntrip = t;
+    }
+    __syncthreads();
+    const int ntrip = s_ntrip, total = s_prefix[ntrip];
+    const int gx = bx * kBX + (threadIdx.x / (kBY * kBZ)), gy = by * kBY + (threadIdx.x / kBZ) % kBY, gz = bz * kBZ + threadIdx.x % kBZ;
+    const bool live = gx < d.kx && gy < d.ky && gz < d.kz;
+    float acc = 0.f;
+    for (int c0 = 0; c0 < total; c0 += kBlock) {
+        const int f = c0 + threadIdx.x;
+        if (f < total) {
+            int t = 0;
+            while (s_prefix[t + 1] <= f) t++;
+            const int atom = sorted[s_first[t] + (f - s_prefix[t])];
+            const int4 b0 = base[atom];
+            s_base[0][threadIdx.x] = b0.x; s_base[1][threadIdx.x] = b0.y; s_base[2][threadIdx.x] = b0.z;
+            const float qs = charge[atom] * sqrt_coulomb;
+            const float* th = theta + (size_t)atom * 3 * ORDER;
+#pragma unroll
+            for (int i = 0; i < ORDER; i++) s_th[i][threadIdx.x] = qs * th[i];
+#pragma unroll
+            for (int i = ORDER; i < 3 * ORDER; i++) s_th[i][threadIdx.x] = th[i];
+        }
+        __syncthreads();
+        const int m = min(kBlock, total - c0);
+        if (live) {
+            for (int k = 0; k < m; k++) {
+                float tx[ORDER], ty[ORDER], tz[ORDER];
+#pragma unroll
+                for (int i = 0; i < ORDER; i++) { tx[i] = s_th[i][k]; ty[i] = s_th[ORDER + i][k]; tz[i] = s_th[2 * ORDER + i][k]; }
+                const float wx = axis_weight<ORDER>(gx, s_base[0][k], d.kx, tx);
+                const float wy = axis_weight<ORDER>(gy, s_base[1][k], d.ky, ty);
+                const float wz = axis_weight<ORDER>(gz, s_base[2][k], d.kz, tz);
+                acc += wx * wy * wz;
+            }
+        }
+        __syncthreads();
+    }
+    if (live) grid[((size_t)gx * d.ky + gy) * d.kz + gz] = acc;
+}
+
+// ---- convolution with the Ewald kernel (pmeCPU.cpp:229-262 semantics), energy in double ----
+__global__ __launch_bounds__(kBlock) void pme_recip_convolve(int gx, int gy, int gz, const float* __restrict__ box, float recip_exp_factor,
+                                                            const float* __restrict__ xmod, const float* __restrict__ ymod,
+                                                            const float* __restrict__ zmod, float2* __restrict__ cgrid,
+                                                            double* __restrict__ partial) {
+    __shared__ double red[kBlock / 64];
+    float b[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) b[i] = box[i];
+    const RecipBox r = recip_box(b);
+    const float scale_factor = (float)M_PI * b[0] * b[4] * b[8];
+    const int zsize = gz / 2 + 1;
+    const long long points = (long long)gx * gy * zsize;
+    double energy = 0.0;
+    for (long long idx = (long long)blockIdx.x * kBlock + threadIdx.x; idx < points; idx += (long long)gridDim.x * kBlock) {
+        const int kx = (int)(idx / ((long long)gy * zsize));
+        const int rem = (int)(idx - (long long)kx * gy * zsize);
+        const int ky = rem / zsize, kz = rem - ky * zsize;
+        const int mx = kx < (gx + 1) / 2 ? kx : kx - gx;
+        const int my = ky < (gy + 1) / 2 ? ky : ky - gy;
+        const int mz = kz < (gz + 1) / 2 ? kz : kz - gz;
+        const float mhx = mx * r.r00;
+        const float mhy = mx * r.r10 + my * r.r11;
+        const float mhz = mx * r.r20 + my * r.r21 + mz * r.r22;
+        const float m2 = mhx * mhx + mhy * mhy + mhz * mhz;
+        const float denom = m2 * (scale_factor * xmod[kx]) * ymod[ky] * zmod[kz];
+        const float eterm = idx == 0 ? 0.f : expf(-recip_exp_factor * m2) / denom;
+        const float w = (kz > 0 && kz <= (gz - 1) / 2) ? 2.f : 1.f;
+        float2 g = cgrid[idx];
+        energy += (double)(w * eterm * (g.x * g.x + g.y * g.y));
+        g.x *= eterm; g.y *= eterm;
+        cgrid[idx] = g;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) energy += __shfl_xor(energy, off, 64);
+    if (lane_id() == 0) red[threadIdx.x >> 6] = energy;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double e = 0.0;
+        for (int w = 0; w < kBlock / 64; w++) e += red[w];
+        partial[blockIdx.x] = e;
+    }
+}
+
+// workgroup partials -> 0.5 x their sum, always in the same order
+__global__ __launch_bounds__(kConvBlocksMax) void pme_recip_energy(const double* __restrict__ partial, int count, float* __restrict__ energy) {
+    __shared__ double red[kConvBlocksMax];
+    red[threadIdx.x] = (int)threadIdx.x < count ? partial[threadIdx.x] : 0.0;
+    __syncthreads();
+    for (int off = kConvBlocksMax / 2; off >= 1; off >>= 1) {
+        if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *energy = (float)(0.5 * red[0]);
+}
+
+// ---- interpolation: dE/dpositions, dE/dcharges from the irfftn of the scaled complex grid ----
+template <int ORDER>
+__global__ __launch_bounds__(kBlock) void pme_recip_interp(int num_atoms, Dims d, const float* __restrict__ box,
+                                                           const float* __restrict__ charge, float sqrt_coulomb,
+                                                           const int4* __restrict__ base, const float* __restrict__ theta,
+                                                           const float* __restrict__ dtheta, const float* __restrict__ grid,
+                                                           float* __restrict__ pos_deriv, float* __restrict__ charge_deriv) {
+    const int atom = blockIdx.x * kBlock + threadIdx.x;
+    if (atom >= num_atoms) return;
+    float b[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) b[i] = box[i];
+    const RecipBox r = recip_box(b);
+    const int4 b0 = base[atom];
+    const float* th = theta + (size_t)atom * 3 * ORDER;
+    const float* dth = dtheta + (size_t)atom * 3 * ORDER;
+    float tx[ORDER], ty[ORDER], tz[ORDER], dx[ORDER], dy[ORDER], dz[ORDER];
+    int ix[ORDER], iy[ORDER], iz[ORDER];
+#pragma unroll
+    for (int i = 0; i < ORDER; i++) {
+        tx[i] = th[i]; ty[i] = th[ORDER + i]; tz[i] = th[2 * ORDER + i];
+        dx[i] = dth[i]; dy[i] = dth[ORDER + i]; dz[i] = dth[2 * ORDER + i];
+        ix[i] = (b0.x + i) % d.kx; iy[i] = (b0.y + i) % d.ky; iz[i] = (b0.z + i) % d.kz;
+    }
+    float gx = 0.f, gy = 0.f, gz = 0.f, dq = 0.f;
+#pragma unroll
+    for (int a = 0; a < ORDER; a++) {
+#pragma unroll
+        for (int c = 0; c < ORDER; c++) {
+            const float* row = grid + ((size_t)ix[a] * d.ky + iy[c]) * d.kz;
+#pragma unroll
+            for (int e = 0; e < ORDER; e++) {
+                const float g = row[iz[e]];
+                gx += dx[a] * ty[c] * tz[e] * g;
+                gy += tx[a] * dy[c] * tz[e] * g;
+                gz += tx[a] * ty[c] * dz[e] * g;
+                dq += tx[a] * ty[c] * tz[e] * g;
+            }
+        }
+    }
+    const float s = charge[atom] * sqrt_coulomb;
+    const float fx = gx * d.kx, fy = gy * d.ky, fz = gz * d.kz;
+    pos_deriv[3 * atom] = s * (fx * r.r00);
+    pos_deriv[3 * atom + 1] = s * (fx * r.r10 + fy * r.r11);
+    pos_deriv[3 * atom + 2] = s * (fx * r.r20 + fy * r.r21 + fz * r.r22);
+    charge_deriv[atom] = dq * sqrt_coulomb;
+}
+
+int check_common(int num_atoms, int gx, int gy, int gz, int order) {
+    NNPOPS_REQUIRE(num_atoms >= 0, "bad number of atoms %d", num_atoms);
+    NNPOPS_REQUIRE(gx >= 1 && gy >= 1 && gz >= 1, "the grid dimensions must be positive (%d, %d, %d)", gx, gy, gz);
+    NNPOPS_REQUIRE((long long)gx * gy * gz <= 0x7fffffffll, "grid of %lld points is too large", (long long)gx * gy * gz);
+    NNPOPS_REQUIRE(order == 4 || order == 5, "Only pmeOrder 4 or 5 is supported (got %d)", order);
+    return NNPOPS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t nnpops_pme_reciprocal_workspace_bytes(int num_atoms, int gridx, int gridy, int gridz, int order) {
+    if (check_common(num_atoms, gridx, gridy, gridz, order) != NNPOPS_OK) return 0;
+    return (int64_t)carve(nullptr, num_atoms, gridx, gridy, gridz, order).bytes;
+}
+
+int nnpops_pme_reciprocal_spread(int num_atoms, int gridx, int gridy, int gridz, int order, const float* positions, const float* charges,
+                                 const float* box_vectors, float coulomb, float* real_grid, void* workspace, void* stream) {
+    if (int rc = check_common(num_atoms, gridx, gridy, gridz, order)) return rc;
+    NNPOPS_REQUIRE(coulomb > 0, "coulomb must be positive");
+    NNPOPS_REQUIRE(box_vectors && real_grid && workspace, "NULL device pointer");
+    NNPOPS_REQUIRE(num_atoms == 0 || (positions && charges), "NULL positions / charges pointer");
+    hipStream_t s = (hipStream_t)stream;
+    const Dims d = make_dims(gridx, gridy, gridz);
+    const RecipWorkspace w = carve(workspace, num_atoms, gridx, gridy, gridz, order);
+    const float sqrt_coulomb = (float)std::sqrt((double)coulomb);
+    const int ab = div_up(num_atoms, kBlock);
+    NNPOPS_HIP_TRY(hipMemsetAsync(w.bin_count, 0, sizeof(int) * (size_t)d.nbins, s));
+    if (num_atoms > 0) {
+        if (order == 4)
+            hipLaunchKernelGGL(pme_recip_spline<4>, dim3(ab), dim3(kBlock), 0, s, num_atoms, positions, box_vectors, d, w.base, w.theta,
+                               w.dtheta, w.bin_count);
+        else
+            hipLaunchKernelGGL(pme_recip_spline<5>, dim3(ab), dim3(kBlock), 0, s, num_atoms, positions, box_vectors, d, w.base, w.theta,
+                               w.dtheta, w.bin_count);
+    }
+    hipLaunchKernelGGL(pme_recip_scan, dim3(1), dim3(1024), 0, s, d.nbins, (const int*)w.bin_count, w.bin_start, w.cursor);
+    if (num_atoms > 0) {
+        hipLaunchKernelGGL(pme_recip_scatter, dim3(ab), dim3(kBlock), 0, s, num_atoms, (const int4*)w.base, w.cursor, w.unsorted);
+        const int ob = (int)std::min<long long>((d.nbins + kBlock / 64 - 1) / (kBlock / 64), 16384);
+        hipLaunchKernelGGL(pme_recip_order, dim3(ob), dim3(kBlock), 0, s, d.nbins, (const int*)w.bin_start, (const int*)w.unsorted, w.sorted);
+    }
+    if (order == 4)
+        hipLaunchKernelGGL(pme_recip_gather<4>, dim3((unsigned)d.nbins), dim3(kBlock), 0, s, d, (const int*)w.bin_start, (const int*)w.sorted,
+                           (const int4*)w.base, (const float*)w.theta, charges, sqrt_coulomb, real_grid);
+    else
+        hipLaunchKernelGGL(pme_recip_gather<5>, dim3((unsigned)d.nbins), dim3(kBlock), 0, s, d, (const int*)w.bin_start, (const int*)w.sorted,
+                           (const int4*)w.base, (const float*)w.theta, charges, sqrt_coulomb, real_grid);
+    NNPOPS_HIP_TRY(hipGetLastError());
+    return NNPOPS_OK;
+}
+
+int nnpops_pme_reciprocal_convolve(int num_atoms, int gridx, int gridy, int gridz, int order, const float* box_vectors, float alpha,
+                                   const float* xmoduli, const float* ymoduli, const float* zmoduli, void* recip_grid, float* energy,
+                                   void* workspace, void* stream) {
+    if (int rc = check_common(num_atoms, gridx, gridy, gridz, order)) return rc;
+    NNPOPS_REQUIRE(alpha > 0, "alpha must be positive");
+    NNPOPS_REQUIRE(box_vectors && xmoduli && ymoduli && zmoduli && recip_grid && energy && workspace, "NULL device pointer");
+    hipStream_t s = (hipStream_t)stream;
+    const RecipWorkspace w = carve(workspace, num_atoms, gridx, gridy, gridz, order);
+    const int cb = conv_blocks(gridx, gridy, gridz);
+    const float recip_exp_factor = (float)(M_PI * M_PI / ((double)alpha * (double)alpha));
+    hipLaunchKernelGGL(pme_recip_convolve, dim3(cb), dim3(kBlock), 0, s, gridx, gridy, gridz, box_vectors, recip_exp_factor, xmoduli,
+                       ymoduli, zmoduli, (float2*)recip_grid, w.partial);
+    hipLaunchKernelGGL(pme_recip_energy, dim3(1), dim3(kConvBlocksMax), 0, s, (const double*)w.partial, cb, energy);
+    NNPOPS_HIP_TRY(hipGetLastError());
+    return NNPOPS_OK;
+}
+
+int nnpops_pme_reciprocal_interpolate(int num_atoms, int gridx, int gridy, int gridz, int order, const float* charges,
+                                      const float* box_vectors, float coulomb, const float* real_grid, float* position_deriv,
+                                      float* charge_deriv, void* workspace, void* stream) {
+    if (int rc = check_common(num_atoms, gridx, gridy, gridz, order)) return rc;
+    NNPOPS_REQUIRE(coulomb > 0, "coulomb must be positive");
+    NNPOPS_REQUIRE(box_vectors && real_grid && workspace, "NULL device pointer");
+    NNPOPS_REQUIRE(num_atoms == 0 || (charges && position_deriv && charge_deriv), "NULL charges / derivative pointer");
+    if (num_atoms == 0) return NNPOPS_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const Dims d = make_dims(gridx, gridy, gridz);
+    const RecipWorkspace w = carve(workspace, num_atoms, gridx, gridy, gridz, order);
+    const float sqrt_coulomb = (float)std::sqrt((double)coulomb);
+    const int ab = div_up(num_atoms, kBlock);
+    if (order == 4)
+        hipLaunchKernelGGL(pme_recip_interp<4>, dim3(ab), dim3(kBlock), 0, s, num_atoms, d, box_vectors, charges, sqrt_coulomb,
+                           (const int4*)w.base, (const float*)w.theta, (const float*)w.dtheta, real_grid, position_deriv, charge_deriv);
+    else
+        hipLaunchKernelGGL(pme_recip_interp<5>, dim3(ab), dim3(kBlock), 0, s, num_atoms, d, box_vectors, charges, sqrt_coulomb,
+                           (const int4*)w.base, (const float*)w.theta, (const float*)w.dtheta, real_grid, position_deriv, charge_deriv);
+    NNPOPS_HIP_TRY(hipGetLastError());
+    return NNPOPS_OK;
+}
+
+}  // extern "C"

@@ -14,15 +14,16 @@
 //
 // Differences that are deliberate:
 //   * the AEV / CFConv / BatchedNN ops have no CPU implementation: a CPU tensor raises (the reference's CPU path is the
-//     oracle of this repository, not part of the product).  The two ops for which the reference itself registers a CPU
-//     kernel at the dispatcher -- neighbors::getNeighborPairs and pme::pme_direct -- do have a CPU key here (plain C++
-//     loops pinned to the reference's CPU ops by fixtures, tests/test_neighbors_cpu_key.py, tests/test_pme_cpu.py);
+//     oracle of this repository, not part of the product).  The three ops for which the reference itself registers a CPU
+//     kernel at the dispatcher -- neighbors::getNeighborPairs, pme::pme_direct and pme::pme_reciprocal -- do have a CPU key here (plain C++
+//     loops pinned to the reference's CPU ops by fixtures, tests/test_neighbors_cpu_key.py, tests/test_pme_cpu.py, tests/test_pme_reciprocal_cpu.py);
 //   * outputs are fresh tensors on every call (the reference re-returns the same storage,
 //     SymmetryFunctions.cpp:136-138,157) -- no caller can observe the difference except by aliasing bugs;
 //   * CFConv honours the current stream (the reference leaves that commented out, CFConv.cpp:167-170).
 #include <c10/hip/HIPGuard.h>
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime_api.h>
+#include <torch/fft.h>
 #include <torch/script.h>
 #include <torch/serialize/archive.h>
 
@@ -1188,7 +1189,7 @@ TORCH_LIBRARY_IMPL(neighbors, CPU, m) { m.impl("getNeighborPairs", neighbor_pair
 // =============================================================================================
 // PME, direct-space part (reference src/pytorch/pme/pme.cpp:4, pmeCUDA.cu:30-100,236-290, pmeCPU.cpp:75-175): same op
 // name and schema; the energy's autograd backward scales the derivatives computed in the forward pass, exactly as the
-// reference does.  The reciprocal-space op (pme_reciprocal) is not built.
+// reference does.  The reciprocal-space op (pme_reciprocal) follows it below.
 // =============================================================================================
 class PmeDirectFunction : public torch::autograd::Function<PmeDirectFunction> {
 public:
@@ -1288,9 +1289,239 @@ public:
     }
 };
 
+// =============================================================================================
+// PME, reciprocal-space part (reference src/pytorch/pme/pme.cpp:5, pmeCUDA.cu:102-430, pmeCPU.cpp:174-364): same op name and
+// schema.  Device: spread -> torch::fft::rfftn -> convolve (in place) -> [backward] irfftn(norm "forward") -> interpolate, the
+// splines kept in the workspace between forward and backward, the box read on the device.  Host: plain loops + torch::fft on CPU.
+// The energy is 0.5 sum_k; the self energy is the Python class's (as in the reference).
+// =============================================================================================
+namespace pme_recip_host {
+
+struct Recip { float m[3][3]; };
+
+Recip invert_box(const float* b) {
+    Recip r{};
+    const float scale = 1.0f / (b[0] * b[4] * b[8]);
+    r.m[0][0] = b[4] * b[8] * scale;
+    r.m[1][0] = -b[3] * b[8] * scale;
+    r.m[1][1] = b[0] * b[8] * scale;
+    r.m[2][0] = (b[3] * b[7] - b[4] * b[6]) * scale;
+    r.m[2][1] = -b[0] * b[7] * scale;
+    r.m[2][2] = b[0] * b[4] * scale;
+    return r;
+}
+
+// base grid index, B-spline weights th[i][axis] and derivatives dth[i][axis] of one atom (order >= 2)
+void spline(const float* p_in, const float* b, const Recip& r, const int K[3], int order, int base[3], std::vector<float>& th,
+            std::vector<float>& dth) {
+    float p[3] = {p_in[0], p_in[1], p_in[2]};
+    for (int i = 2; i >= 0; i--) {
+        const float s = std::floor(p[i] * r.m[i][i]);
+        for (int j = 0; j < 3; j++) p[j] -= s * b[3 * i + j];
+    }
+    for (int i = 0; i < 3; i++) {
+        float t = p[0] * r.m[0][i] + p[1] * r.m[1][i] + p[2] * r.m[2][i];
+        t = (t - std::floor(t)) * K[i];
+        const int ti = (int)t;
+        const float dr = t - ti;
+        base[i] = std::min(std::max(ti % K[i], 0), K[i] - 1);
+        auto w = [&](int j) -> float& { return th[3 * j + i]; };
+        w(order - 1) = 0;
+        w(1) = dr;
+        w(0) = 1 - dr;
+        for (int j = 3; j < order; j++) {
+            const float div = 1.0f / (j - 1);
+            w(j - 1) = div * dr * w(j - 2);
+            for (int k = 1; k < j - 1; k++) w(j - k - 1) = div * ((dr + k) * w(j - k - 2) + (j - k - dr) * w(j - k - 1));
+            w(0) = div * (1 - dr) * w(0);
+        }
+        dth[i] = -w(0);
+        for (int j = 1; j < order; j++) dth[3 * j + i] = w(j - 1) - w(j);
+        const float scale = 1.0f / (order - 1);
+        w(order - 1) = scale * dr * w(order - 2);
+        for (int j = 1; j < order - 1; j++) w(order - j - 1) = scale * ((dr + j) * w(order - j - 2) + (order - j - dr) * w(order - j - 1));
+        w(0) = scale * (1 - dr) * w(0);
+    }
+}
+
+}  // namespace pme_recip_host
+
+class PmeReciprocalFunction : public torch::autograd::Function<PmeReciprocalFunction> {
+public:
+    static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& box_vectors,
+                          const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz, const torch::Scalar& order,
+                          const torch::Scalar& alpha, const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli,
+                          const Tensor& zmoduli) {
+        TORCH_CHECK(positions.dim() == 2 && positions.size(1) == 3, "positions must have shape (atoms, 3)");
+        TORCH_CHECK(charges.dim() == 1 && charges.size(0) == positions.size(0), "charges must be 1D, one per atom");
+        TORCH_CHECK(box_vectors.dim() == 2 && box_vectors.size(0) == 3 && box_vectors.size(1) == 3, "box_vectors must have shape (3, 3)");
+        TORCH_CHECK(positions.scalar_type() == torch::kFloat32 && charges.scalar_type() == torch::kFloat32 &&
+                    box_vectors.scalar_type() == torch::kFloat32, "pme_reciprocal computes in float32");
+        const int64_t K[3] = {gridx.toLong(), gridy.toLong(), gridz.toLong()};
+        TORCH_CHECK(K[0] >= 1 && K[1] >= 1 && K[2] >= 1, "pme_reciprocal: the grid dimensions must be positive");
+        TORCH_CHECK(K[0] * K[1] * K[2] <= std::numeric_limits<int32_t>::max(), "pme_reciprocal: the grid is too large");
+        const int64_t pme_order = order.toLong();
+        TORCH_CHECK(pme_order >= 2, "pme_reciprocal: order must be at least 2");
+        const double a = alpha.toDouble(), k = coulomb.toDouble();
+        TORCH_CHECK(a > 0 && k > 0, "pme_reciprocal: alpha and coulomb must be positive");
+        const Tensor* mods[3] = {&xmoduli, &ymoduli, &zmoduli};
+        for (int i = 0; i < 3; i++)
+            TORCH_CHECK(mods[i]->dim() == 1 && mods[i]->size(0) == K[i] && mods[i]->scalar_type() == torch::kFloat32,
+                        "pme_reciprocal: the moduli must be float32 tensors of the grid's sizes");
+        for (const Tensor* t : {&charges, &box_vectors, &xmoduli, &ymoduli, &zmoduli})
+            TORCH_CHECK(t->device() == positions.device(), "pme_reciprocal: every tensor must be on the device of positions (",
+                        positions.device(), "), got ", t->device());
+        const Tensor pos = positions.contiguous(), q = charges.contiguous(), box = box_vectors.contiguous();
+        const Tensor xm = xmoduli.contiguous(), ym = ymoduli.contiguous(), zm = zmoduli.contiguous();
+        const int64_t n = positions.size(0);
+        const auto opts = positions.options();
+        Tensor energy, recip, workspace;
+        if (positions.is_cuda()) {
+            TORCH_CHECK(pme_order == 4 || pme_order == 5, "pme_reciprocal: Only pmeOrder 4 or 5 is supported on the device (got ", pme_order, ")");
+            c10::hip::HIPGuard guard(positions.device().index());
+            void* stream = current_stream(positions.device());
+            const int gx = (int)K[0], gy = (int)K[1], gz = (int)K[2], o = (int)pme_order;
+            workspace = torch::empty({nnpops_pme_reciprocal_workspace_bytes((int)n, gx, gy, gz, o)}, opts.dtype(torch::kUInt8));
+            Tensor real = torch::empty({K[0], K[1], K[2]}, opts);
+            if (nnpops_pme_reciprocal_spread((int)n, gx, gy, gz, o, pos.data_ptr<float>(), q.data_ptr<float>(), box.data_ptr<float>(), (float)k,
+                                             real.data_ptr<float>(), workspace.data_ptr(), stream) != NNPOPS_OK)
+                raise_last("pme::pme_reciprocal");
+            recip = torch::fft::rfftn(real).contiguous();
+            energy = torch::empty({}, opts);
+            if (nnpops_pme_reciprocal_convolve((int)n, gx, gy, gz, o, box.data_ptr<float>(), (float)a, xm.data_ptr<float>(), ym.data_ptr<float>(),
+                                               zm.data_ptr<float>(), recip.data_ptr(), energy.data_ptr<float>(), workspace.data_ptr(),
+                                               stream) != NNPOPS_OK)
+                raise_last("pme::pme_reciprocal");
+        } else {
+            // host tensors: the reference registers a CPU kernel (pmeCPU.cpp:174-364); plain loops, double energy
+            using namespace pme_recip_host;
+            const float* B = box.data_ptr<float>();
+            const Recip r = invert_box(B);
+            const int Ki[3] = {(int)K[0], (int)K[1], (int)K[2]};
+            const float sqrt_k = (float)std::sqrt(k);
+            Tensor real = torch::zeros({K[0], K[1], K[2]}, opts);
+            float* G = real.data_ptr<float>();
+            const float* P = pos.data_ptr<float>(); const float* Q = q.data_ptr<float>();
+            std::vector<float> th(3 * pme_order), dth(3 * pme_order);
+            for (int64_t atom = 0; atom < n; atom++) {
+                int b0[3];
+                spline(P + 3 * atom, B, r, Ki, (int)pme_order, b0, th, dth);
+                for (int ix = 0; ix < pme_order; ix++) {
+                    const int64_t xi = (b0[0] + ix) % Ki[0];
+                    const float dx = Q[atom] * sqrt_k * th[3 * ix];
+                    for (int iy = 0; iy < pme_order; iy++) {
+                        const int64_t yi = (b0[1] + iy) % Ki[1];
+                        const float dxdy = dx * th[3 * iy + 1];
+                        for (int iz = 0; iz < pme_order; iz++) G[(xi * K[1] + yi) * K[2] + (b0[2] + iz) % Ki[2]] += dxdy * th[3 * iz + 2];
+                    }
+                }
+            }
+            recip = torch::fft::rfftn(real).contiguous();
+            auto* C = reinterpret_cast<c10::complex<float>*>(recip.data_ptr());
+            const int64_t zsize = K[2] / 2 + 1;
+            const float scale_factor = (float)(M_PI * B[0] * B[4] * B[8]);
+            const float exp_factor = (float)(M_PI * M_PI / (a * a));
+            const float* XM = xm.data_ptr<float>(); const float* YM = ym.data_ptr<float>(); const float* ZM = zm.data_ptr<float>();
+            double e = 0.0;
+            for (int64_t kx = 0; kx < K[0]; kx++) {
+                const int64_t mx = kx < (K[0] + 1) / 2 ? kx : kx - K[0];
+                for (int64_t ky = 0; ky < K[1]; ky++) {
+                    const int64_t my = ky < (K[1] + 1) / 2 ? ky : ky - K[1];
+                    for (int64_t kz = 0; kz < zsize; kz++) {
+                        const int64_t mz = kz < (K[2] + 1) / 2 ? kz : kz - K[2];
+                        const int64_t idx = (kx * K[1] + ky) * zsize + kz;
+                        const float mhx = mx * r.m[0][0], mhy = mx * r.m[1][0] + my * r.m[1][1];
+                        const float mhz = mx * r.m[2][0] + my * r.m[2][1] + mz * r.m[2][2];
+                        const float m2 = mhx * mhx + mhy * mhy + mhz * mhz;
+                        const float denom = m2 * (scale_factor * XM[kx]) * YM[ky] * ZM[kz];
+                        const float eterm = idx == 0 ? 0.f : std::exp(-exp_factor * m2) / denom;
+                        const float w = (kz > 0 && kz <= (K[2] - 1) / 2) ? 2.f : 1.f;
+                        e += w * eterm * std::norm(C[idx]);
+                        C[idx] *= eterm;
+                    }
+                }
+            }
+            energy = torch::full({}, (float)(0.5 * e), opts);
+        }
+        // (the device path keeps the splines in the workspace and does not need the positions again)
+        const Tensor none = torch::empty({0}, opts);
+        ctx->save_for_backward({q, box, recip, workspace.defined() ? workspace : none, positions.is_cuda() ? none : pos});
+        ctx->saved_data["grid"] = std::vector<int64_t>{K[0], K[1], K[2]};
+        ctx->saved_data["order"] = pme_order;
+        ctx->saved_data["coulomb"] = k;
+        return energy;
+    }
+
+    static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) {
+        TORCH_CHECK(!torch::GradMode::is_enabled(),
+                    "pme_reciprocal: second derivatives are not implemented (backward was called with create_graph=True)");
+        const auto saved = ctx->get_saved_variables();
+        const Tensor q = saved[0], box = saved[1], recip = saved[2], workspace = saved[3], pos = saved[4];
+        const std::vector<int64_t> K = ctx->saved_data["grid"].toIntVector();
+        const int64_t pme_order = ctx->saved_data["order"].toInt();
+        const double k = ctx->saved_data["coulomb"].toDouble();
+        const int64_t n = q.size(0);
+        const Tensor grid = torch::fft::irfftn(recip, torch::IntArrayRef(K), c10::nullopt, "forward").contiguous();
+        const auto opts = q.options();
+        Tensor pos_deriv = torch::empty({n, 3}, opts), charge_deriv = torch::empty({n}, opts);
+        if (q.is_cuda()) {
+            c10::hip::HIPGuard guard(q.device().index());
+            if (nnpops_pme_reciprocal_interpolate((int)n, (int)K[0], (int)K[1], (int)K[2], (int)pme_order, q.data_ptr<float>(),
+                                                  box.data_ptr<float>(), (float)k, grid.data_ptr<float>(), pos_deriv.data_ptr<float>(),
+                                                  charge_deriv.data_ptr<float>(), workspace.data_ptr(), current_stream(q.device())) != NNPOPS_OK)
+                raise_last("pme::pme_reciprocal");
+        } else {
+            using namespace pme_recip_host;
+            const float* B = box.data_ptr<float>();
+            const Recip r = invert_box(B);
+            const int Ki[3] = {(int)K[0], (int)K[1], (int)K[2]};
+            const float sqrt_k = (float)std::sqrt(k);
+            const float* G = grid.data_ptr<float>(); const float* P = pos.data_ptr<float>(); const float* Q = q.data_ptr<float>();
+            float* PD = pos_deriv.data_ptr<float>(); float* CD = charge_deriv.data_ptr<float>();
+            std::vector<float> th(3 * pme_order), dth(3 * pme_order);
+            for (int64_t atom = 0; atom < n; atom++) {
+                int b0[3];
+                spline(P + 3 * atom, B, r, Ki, (int)pme_order, b0, th, dth);
+                float d[3] = {0, 0, 0}, dq = 0;
+                for (int ix = 0; ix < pme_order; ix++) {
+                    const int64_t xi = (b0[0] + ix) % Ki[0];
+                    for (int iy = 0; iy < pme_order; iy++) {
+                        const int64_t yi = (b0[1] + iy) % Ki[1];
+                        for (int iz = 0; iz < pme_order; iz++) {
+                            const float g = G[(xi * K[1] + yi) * K[2] + (b0[2] + iz) % Ki[2]];
+                            const float tx = th[3 * ix], ty = th[3 * iy + 1], tz = th[3 * iz + 2];
+                            d[0] += dth[3 * ix] * ty * tz * g;
+                            d[1] += tx * dth[3 * iy + 1] * tz * g;
+                            d[2] += tx * ty * dth[3 * iz + 2] * g;
+                            dq += tx * ty * tz * g;
+                        }
+                    }
+                }
+                const float s = Q[atom] * sqrt_k;
+                const float fx = d[0] * Ki[0], fy = d[1] * Ki[1], fz = d[2] * Ki[2];
+                PD[3 * atom] = s * (fx * r.m[0][0]);
+                PD[3 * atom + 1] = s * (fx * r.m[1][0] + fy * r.m[1][1]);
+                PD[3 * atom + 2] = s * (fx * r.m[2][0] + fy * r.m[2][1] + fz * r.m[2][2]);
+                CD[atom] = dq * sqrt_k;
+            }
+        }
+        return {pos_deriv * grad_outputs[0], charge_deriv * grad_outputs[0], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(),
+                Tensor(), Tensor(), Tensor(), Tensor()};
+    }
+};
+
 TORCH_LIBRARY(pme, m) {
     m.def("pme_direct(Tensor positions, Tensor charges, Tensor neighbors, Tensor deltas, Tensor distances, Tensor exclusions, "
           "Scalar alpha, Scalar coulomb) -> Tensor");
+    m.def("pme_reciprocal(Tensor positions, Tensor charges, Tensor box_vectors, Scalar gridx, Scalar gridy, Scalar gridz, "
+          "Scalar order, Scalar alpha, Scalar coulomb, Tensor xmoduli, Tensor ymoduli, Tensor zmoduli) -> Tensor");
+}
+
+Tensor pme_reciprocal_entry(const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const torch::Scalar& gridx,
+                            const torch::Scalar& gridy, const torch::Scalar& gridz, const torch::Scalar& order, const torch::Scalar& alpha,
+                            const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli, const Tensor& zmoduli) {
+    return PmeReciprocalFunction::apply(positions, charges, box_vectors, gridx, gridy, gridz, order, alpha, coulomb, xmoduli, ymoduli,
+                                        zmoduli);
 }
 
 Tensor pme_direct_entry(const Tensor& positions, const Tensor& charges, const Tensor& neighbors, const Tensor& deltas,
@@ -1298,12 +1529,24 @@ Tensor pme_direct_entry(const Tensor& positions, const Tensor& charges, const Te
     return PmeDirectFunction::apply(positions, charges, neighbors, deltas, distances, exclusions, alpha, coulomb);
 }
 
-TORCH_LIBRARY_IMPL(pme, AutogradCUDA, m) { m.impl("pme_direct", pme_direct_entry); }
-TORCH_LIBRARY_IMPL(pme, AutogradCPU, m) { m.impl("pme_direct", pme_direct_entry); }
+TORCH_LIBRARY_IMPL(pme, AutogradCUDA, m) {
+    m.impl("pme_direct", pme_direct_entry);
+    m.impl("pme_reciprocal", pme_reciprocal_entry);
+}
+TORCH_LIBRARY_IMPL(pme, AutogradCPU, m) {
+    m.impl("pme_direct", pme_direct_entry);
+    m.impl("pme_reciprocal", pme_reciprocal_entry);
+}
 // ... and the backend keys themselves (the reference registers its autograd Function under CPU, pmeCPU.cpp:381): below
 // autograd -- torch.inference_mode(), AutoDispatchBelowAutograd -- the same entry runs without recording a graph
-TORCH_LIBRARY_IMPL(pme, CUDA, m) { m.impl("pme_direct", pme_direct_entry); }
-TORCH_LIBRARY_IMPL(pme, CPU, m) { m.impl("pme_direct", pme_direct_entry); }
+TORCH_LIBRARY_IMPL(pme, CUDA, m) {
+    m.impl("pme_direct", pme_direct_entry);
+    m.impl("pme_reciprocal", pme_reciprocal_entry);
+}
+TORCH_LIBRARY_IMPL(pme, CPU, m) {
+    m.impl("pme_direct", pme_direct_entry);
+    m.impl("pme_reciprocal", pme_reciprocal_entry);
+}
 
 // =============================================================================================
 // BatchedLinear (reference src/pytorch/BatchedNN.cpp:30-50): y = W v + b broadcast over
