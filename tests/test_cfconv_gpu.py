@@ -118,15 +118,16 @@ def test_triclinic_box():
     _case(pos, box, 128, 50, 5.0, 0.1, "ssp", seed=3)
 
 
-def test_half_and_full_list_paths_agree(monkeypatch):
-    """The matrix-core widths evaluate the filter network once per pair (filters + owner-computes gather);
-    $NNPOPS_CFCONV_HALF=0 (read at handle creation) keeps the kernels that evaluate every pair from both ends.
-    Both meet the oracle, and each other far inside the parity bar."""
+def test_split_and_fp32_filters_kernels_agree(monkeypatch):
+    """The matrix-core widths evaluate the filter network once per pair (filters + owner-computes gather); at W = 128 the
+    default filters kernels run split-fp16 products, $NNPOPS_CFCONV_SPLIT=0 (read at handle creation) keeps the fp32 matrix
+    kernel.  Both meet the oracle, and each other far inside the parity bar."""
     pos, _, box = workloads.random_box(1500, seed=51)
-    y_half = _case(pos, box, 128, 50, 5.0, 0.1, "ssp", seed=11)
-    monkeypatch.setenv("NNPOPS_CFCONV_HALF", "0")
-    y_full = _case(pos, box, 128, 50, 5.0, 0.1, "ssp", seed=11)
-    assert np.abs(y_half - y_full).max() <= 2e-6 * np.abs(y_full).max()
+    y_split = _case(pos, box, 128, 50, 5.0, 0.1, "ssp", seed=11)
+    monkeypatch.setenv("NNPOPS_CFCONV_SPLIT", "0")
+    y_fp32 = _case(pos, box, 128, 50, 5.0, 0.1, "ssp", seed=11)
+    assert np.abs(y_split - y_fp32).max() <= 2e-6 * np.abs(y_fp32).max()
+    monkeypatch.delenv("NNPOPS_CFCONV_SPLIT")
     pos, _ = workloads.conformer(120, seed=52)              # all-pairs neighbour search, odd number of column blocks
     _case(pos, None, 48, 20, 5.0, 0.1, "tanh", seed=12)
 
@@ -244,32 +245,33 @@ def test_split_fp16_second_layer_is_as_accurate_as_fp32(monkeypatch):
 def test_register_fed_filters_kernels_agree_with_the_plane_kernels(monkeypatch, W, G, act):
     """Round 6: where both layers run as split products the forward filters kernel takes 32 pairs per wave and feeds layer 2 from registers
     (cfconv_filters_h2x2), the backward one runs one matrix pass per layer on register-fed operands (cfconv_filters_h2b, one wave per
-    SIMD at widths 96 / 128, two below); $NNPOPS_CFCONV_FWD32=0 / $NNPOPS_CFCONV_BWD1=0 keep the kernels that go through LDS planes
-    (still the ones for more than 63 Gaussians).  Same arithmetic, the 32 products of a matrix step added in another order: both
-    meet the oracle, and each other far inside the parity bar -- also with the backward kernel's two wave counts swapped."""
+    SIMD at widths 96 / 128, two below); $NNPOPS_CFCONV_SPLIT=1 keeps the kernel that splits layer 2 only and goes through LDS planes
+    (cfconv_filters_h2, forward and backward: the ones for more than 63 Gaussians).  Both meet the oracle, and each other far inside the parity bar."""
     pos, _, box = workloads.random_box(1400, seed=91)
-    new, old, swapped = {}, {}, {}
+    new, old = {}, {}
     _case(pos, box, W, G, 5.0, 0.1, act, seed=31, keep=new)
-    monkeypatch.setenv("NNPOPS_CFCONV_BWD_WAVES", "8" if W >= 96 else "4")
-    _case(pos, box, W, G, 5.0, 0.1, act, seed=31, keep=swapped)
-    monkeypatch.delenv("NNPOPS_CFCONV_BWD_WAVES")
-    monkeypatch.setenv("NNPOPS_CFCONV_FWD32", "0")
-    monkeypatch.setenv("NNPOPS_CFCONV_BWD1", "0")
+    monkeypatch.setenv("NNPOPS_CFCONV_SPLIT", "1")
     _case(pos, box, W, G, 5.0, 0.1, act, seed=31, keep=old)
     for key in ("y", "xg", "pg"):
         scale = np.abs(old[key]).max()
         assert np.abs(new[key] - old[key]).max() <= 3e-6 * scale, key
-        assert np.abs(swapped[key] - new[key]).max() <= 3e-6 * scale, key
     # Round 6: dY1 goes into its fp16 planes scaled to the top of the fp16 range (ConvParams::dy_scale).  Unscaled, the forces under tanh --
     # whose saturated neurons leave most of dY1 orders of magnitude below its largest entries -- sat 2e-5 ... 7e-5 of the largest force from
     # the oracle, in every split-fp16 kernel since round 3; now they sit where the fp32 matrix kernel sits (tools/cfconv_split_error.py).
     for keep in (new, old):
         assert np.abs(keep["pg"] - keep["pg_ref"]).max() <= 8e-6 * np.abs(keep["pg_ref"]).max()
     # a ragged last pass (pairs not a multiple of 32) and a molecule (all-pairs list)
-    monkeypatch.delenv("NNPOPS_CFCONV_FWD32")
-    monkeypatch.delenv("NNPOPS_CFCONV_BWD1")
+    monkeypatch.delenv("NNPOPS_CFCONV_SPLIT")
     mol, _ = workloads.conformer(61, seed=92)
     _case(mol, None, W, G, 5.0, 0.2, act, seed=32)
+
+
+@pytest.mark.parametrize("W,G,act", [(128, 100, "ssp"), (64, 80, "tanh")])
+def test_plane_kernel_serves_many_gaussians(W, G, act):
+    """A split width with G + 1 > 64: layer 1 does not fit two split K steps, so without any switch the filters kernel is the one that
+    splits layer 2 only and goes through LDS planes (cfconv_filters_h2; at W = 128, G = 100 five waves per workgroup)."""
+    pos, _, box = workloads.random_box(1400, seed=93)
+    _case(pos, box, W, G, 5.0, 0.1, act, seed=33)
 
 
 def test_weights_outside_the_fp16_range_keep_the_fp32_layer():

@@ -25,9 +25,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 PATCHES = {
-    "cfconv.hip": [
+    "cfconv_fallback_kernels.h": [
         ("                float* frow = filt + (size_t)p * W + col;\n",
          "                float* frow = filt + (size_t)(p & 15) * W + col;\n", 2),
+    ],
+    "cfconv_filters.h": [
         ("            const size_t fo = (size_t)__builtin_amdgcn_readlane(my_p, q) * W, vo = (size_t)__builtin_amdgcn_readlane(my_j, q) * W;\n",
          "            const size_t fo = (size_t)(__builtin_amdgcn_readlane(my_p, q) & 15) * W, vo = (size_t)__builtin_amdgcn_readlane(my_j, q) * W;\n", 1),
     ],
