@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X NNPOps hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--atoms 10000] [--no-cpu-baseline] [--no-side] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--atoms 10000] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-side] [--no-pmc]]
 
 Workload (BASELINE.json metric: "AEV+forces (energy+grad evals/sec) per GPU, 10k-atom box"):
 one *step* = one full ANI-2x symmetry-function evaluation of a 10 000-atom periodic box --
@@ -16,12 +16,15 @@ itself as `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --maste
 one rank per GPU over RCCL.  The path shards over independent frames: every rank
 evaluates its own 10k-atom frame (different seed) and the per-atom forces of all frames are assembled
 with ONE all_gather per step (the only collective; "scaling": "weak");
-value = total evaluations of all ranks / max-over-ranks time.  BASELINE config 4 (1024 conformers, strong
-scaling over the same ranks) is run right after and reported under "side".
+value = total evaluations of all ranks / max-over-ranks time.  With `--full`, BASELINE config 4 (1024
+conformers, strong scaling over the same ranks) is run right after and reported under "side".
 
-Rank 0 prints ONE JSON line.  At N = 1 the line also carries, under "side", short runs of the other
-BASELINE configurations (each with its own roofline and CPU baseline); `--workload X` runs one of them
-alone and prints its line instead.
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline figure needs: set-up, the
+settle and warm-up steps, the K timed steps, `--dump-outputs`, the line.  Its kernel durations and roofline
+come from event brackets of those same steps.  `--full` adds everything that takes runs of its own: the CPU
+baselines, the rocprofv3 counter and trace passes, and at N = 1 short runs of the other BASELINE
+configurations under "side" (each with its own roofline and CPU baseline).  `--workload X` runs one of them
+alone and prints its line instead (its CPU baseline and counter passes again with `--full` only).
 """
 import argparse
 import json
@@ -1571,19 +1574,20 @@ WORKLOADS = {"aev": run_aev, "cfconv": run_cfconv, "cfconv_reference": run_cfcon
              "torchani": run_torchani, "latency": run_latency}
 
 
-def main():
-    if len(sys.argv) > 1 and sys.argv[1] == "--cpu-worker":
-        return cpu_worker_main(sys.argv[2:])
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=500)     # 0.06 s of GPU time: long enough for clocks and caches to settle
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--atoms", type=int, default=10000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-side", action="store_true", help="skip the short runs of the other BASELINE configurations")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 counter passes (HBM traffic, instruction counts) of the headline kernels")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU baselines, the rocprofv3 counter and trace passes and the "
+                         "other BASELINE configurations under 'side' (without it a run times its workload and prints its line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-side", action="store_true", help="with --full: skip the short runs of the other BASELINE configurations")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the rocprofv3 counter passes (HBM traffic, instruction counts)")
     ap.add_argument("--settle", type=int, default=-1, help="untimed settling steps before the warm-up (-1: 2500 for frames up to 20 000 atoms)")
-    ap.add_argument("--strict-side", action="store_true", help="exit with status 3 when a side workload failed (the line is still printed)")
+    ap.add_argument("--strict-side", action="store_true", help="with --full: exit with status 3 when a side workload failed (the line is still printed)")
     ap.add_argument("--graph", action="store_true", help="torchani / cfconv workloads: replay the step as one captured HIP graph")
     ap.add_argument("--no-shard8", action="store_true", help="conformers workload: skip the eight per-shard timings (profiles of the full batch alone)")
     ap.add_argument("--nn-layout", default="fused", choices=["fused", "gemm", "grouped", "reference"],
@@ -1592,16 +1596,25 @@ def main():
     ap.add_argument("--no-fused-step", action="store_true", help="torchani workload: the four-module composition instead of one autograd node")
     ap.add_argument("--neighbor-algorithm", type=int, default=0)
     ap.add_argument("--workload", default="aev", choices=sorted(WORKLOADS),
-                    help="aev: the headline metric (default, with the others attached under 'side'); the rest run one BASELINE "
+                    help="aev: the headline metric (default; with --full the others attached under 'side'); the rest run one BASELINE "
                          "configuration alone: latency = config 1, torchani = 2, cfconv = 3, conformers = 4, neighbors = 5")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (radial and angular AEV, dE/dpositions) as "
                          "DIR/<name>.npy in float32; above 60 MiB in all, the same seeded sample of atom rows from each")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
     if args.dump_outputs and args.workload != "aev":
         ap.error("--dump-outputs writes the outputs of the headline workload (--workload aev)")
+    if not args.full:                                         # a plain run: no extra run of any kind
+        args.no_cpu_baseline = args.no_side = args.no_pmc = True
+    return args
+
+
+def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--cpu-worker":
+        return cpu_worker_main(sys.argv[2:])
+    args = parse_args()
     spawn_ranks_if_needed(args)
     R = Ranks()
     if args.workload != "aev":

@@ -89,6 +89,47 @@ def test_dump_outputs_writes_float32_files_and_a_seeded_row_sample(tmp_path, mon
         assert np.array_equal(np.load(tmp_path / "b" / f"{k}.npy"), rows[k])
 
 
+def test_plain_run_leaves_the_extra_runs_to_full():
+    """Without --full a run has no CPU baseline, no rocprofv3 pass and no side line; --full brings them all back, and the --no-*
+    switches still take single ones out of a full run."""
+    bench = _bench()
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not plain.full and plain.no_cpu_baseline and plain.no_side and plain.no_pmc
+    assert (plain.steps, plain.warmup, plain.settle, plain.workload) == (20, 5, -1, "aev")
+    full = bench.parse_args(["--steps", "20", "--warmup", "5", "--full"])
+    assert full.full and not (full.no_cpu_baseline or full.no_side or full.no_pmc)
+    part = bench.parse_args(["--full", "--no-side", "--no-pmc"])
+    assert part.no_side and part.no_pmc and not part.no_cpu_baseline
+    assert bench.parse_args(["--workload", "cfconv"]).no_cpu_baseline
+
+
+@pytest.mark.parametrize("full", [False, True])
+def test_side_lines_run_with_full_only(monkeypatch, capsys, full):
+    """main() at N = 1: a plain run prints the headline alone (with an empty side_errors); --full runs and attaches every side line."""
+    import json
+    bench = _bench()
+    ran = []
+
+    class OneRank:
+        rank, world = 0, 1
+
+        def close(self):
+            pass
+    monkeypatch.setattr(bench, "Ranks", OneRank)
+    monkeypatch.setattr(bench, "run_aev", lambda args, R: ran.append(("aev", args.no_cpu_baseline, args.no_pmc)) or {"value": 1.0})
+    for name in ("latency", "torchani", "cfconv", "cfconv_reference", "conformers", "neighbors"):
+        monkeypatch.setitem(bench.WORKLOADS, name, lambda args, R, name=name: ran.append(name) or {"value": 2.0})
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"] + (["--full"] if full else []))
+    bench.main()
+    line = json.loads(capsys.readouterr().out.strip())
+    assert line["side_errors"] == {}
+    if full:
+        assert ran == [("aev", False, False), "latency", "torchani", "cfconv", "cfconv_reference", "conformers", "neighbors"]
+        assert set(line["side"]) == set(ran[1:])
+    else:
+        assert ran == [("aev", True, True)] and "side" not in line
+
+
 @pytest.mark.parametrize("argv, message", [(["--steps", "0"], "--steps must be at least 1"),
                                            (["--dump-outputs", "d", "--workload", "cfconv"], "--dump-outputs writes")])
 def test_command_line_refuses_what_it_cannot_time_or_dump(argv, message):

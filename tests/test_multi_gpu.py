@@ -202,8 +202,33 @@ def test_four_rank_conformer_rehearsal_on_one_device():
     assert line["config"]["conformers"] == 1024 and 14000 < line["config"]["atoms_this_rank"] < 16800
 
 
-def test_default_bench_line_carries_measured_counters():
-    """`python bench.py` (shortened): ONE JSON line whose roofline carries the HBM traffic and the vector-issue floor of every
+def test_plain_bench_line_is_the_headline_alone():
+    """`python bench.py --gpus 1 --steps 20 --warmup 5`: ONE JSON line with the headline and the figures its own steps give (event
+    brackets), and nothing that takes runs of its own -- no CPU baseline, no rocprofv3 pass, no side line."""
+    import json
+    import subprocess
+    import sys
+    import time
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    t0 = time.perf_counter()
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"], cwd=root,
+                         capture_output=True, text=True, timeout=300)
+    wall = time.perf_counter() - t0
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["n_gpus"] == 1 and line["steps"] == 20 and line["warmup"] == 5 and line["dtype"] == "f32"
+    assert line["unit"] == "evals/s" and line["higher_is_better"] is True
+    assert abs(line["value"] * line["ms_per_step"] - 1e3) <= 2e-3 * 1e3
+    assert line["side_errors"] == {} and "side" not in line and "cpu_baseline" not in line
+    assert line["kernels_us_rocprofv3"] is None and line["roofline"]["traffic"] is None
+    assert 0 < line["roofline"]["frac"] < 1 and all(k["us"] > 0 for k in line["roofline"]["per_kernel"].values())
+    assert wall < 90, wall                                   # (the full line took over 90 s beyond its steps)
+
+
+def test_full_bench_line_carries_measured_counters():
+    """`python bench.py --full` (shortened): ONE JSON line whose roofline carries the HBM traffic and the vector-issue floor of every
     headline kernel, both measured in the run by the rocprofv3 counter passes bench.py starts on itself, and a step that adds up."""
     import json
     import shutil
@@ -212,8 +237,8 @@ def test_default_bench_line_carries_measured_counters():
     if not (shutil.which("rocprofv3") or os.path.exists("/opt/rocm/bin/rocprofv3")):
         pytest.skip("rocprofv3 not installed")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "40", "--warmup", "8", "--settle", "50", "--no-side",
-                          "--no-cpu-baseline"], cwd=root, capture_output=True, text=True, timeout=600)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "40", "--warmup", "8", "--settle", "50",
+                          "--no-side", "--no-cpu-baseline"], cwd=root, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
