@@ -15,6 +15,8 @@
  *   nnpops_cfconv_create / compute / backprop   CFConv ctor / compute / backprop   src/schnet/CFConv.h:109-217
  *   nnpops_neighbor_pairs_forward / _backward   neighbors::getNeighborPairs forward/backward kernels
  *                                               src/pytorch/neighbors/getNeighborPairsCUDA.cu:31-101
+ *   nnpops_neighbor_pairs_box_backward / _double_backward   box gradient and second derivatives of that op
+ *                                               (the reference's CPU op differentiates both: getNeighborPairsCPU.cpp:56-98)
  *   nnpops_pme_direct                           pme::pme_direct (computeDirect)   src/pytorch/pme/pmeCUDA.cu:30-100
  *
  * Conventions
@@ -271,6 +273,33 @@ int64_t nnpops_neighbor_pairs_backward_indexed_workspace_bytes(int dtype, int64_
 int nnpops_neighbor_pairs_backward_indexed(int dtype, int num_atoms, int64_t num_slots, const int32_t* neighbors, const void* deltas,
                                            const void* distances, const void* grad_deltas, const void* grad_distances,
                                            const int32_t* index, void* grad_positions, void* workspace, void* stream);
+
+/* Box gradient and second derivatives of the backward pass above (additive).  For a used slot k (i = neighbors[0][k],
+ * j = neighbors[1][k], both in [0, num_atoms); any other slot is unused and contributes nothing), delta_k = x_i - x_j - sum_a n_ka B[a,:]
+ * with n_k the integer minimum-image shift, recovered from positions, box and delta_k (the wrap's rounds have zero derivative);
+ * G_k = grad_deltas[k] + deltas[k] / distances[k] * grad_distances[k] as in the backward pass.  box, gg_box, grad_box: [3][3], rows =
+ * box vectors (lower triangular, as the forward op takes them), same dtype as positions.  Neither entry needs the transposed index:
+ * both work on any list, compacted or max_num_pairs == -1, in any order.  No atomics, no host synchronisation (graph-capturable);
+ * bitwise reproducible.  A used slot with distance 0 divides by zero, as the backward pass does.
+ *
+ * nnpops_neighbor_pairs_box_backward: grad_box[a][:] = - sum_k n_ka G_k (all nine entries, as the reference's CPU composition
+ *   differentiates whole rows), added up in float64 per block in a fixed order and then over the blocks in a fixed order.
+ *   workspace: device, 8-byte aligned, nnpops_neighbor_pairs_box_backward_workspace_bytes(num_slots) bytes.
+ * nnpops_neighbor_pairs_double_backward: vector-Jacobian product of the backward pass, (grad_deltas, grad_distances, deltas, distances)
+ *   -> (grad_positions, grad_box), with the incoming gg_positions [num_atoms][3] and gg_box [3][3] (either may be NULL: zero).  Per slot,
+ *   w_k = gg_positions[i] - gg_positions[j] - sum_a n_ka gg_box[a][:] and u_k = deltas[k] / distances[k]:
+ *     d_grad_deltas[k] = w_k,  d_grad_distances[k] = u_k . w_k,  d_deltas[k] = grad_distances[k] / distances[k] w_k,
+ *     d_distances[k] = - grad_distances[k] (deltas[k] . w_k) / distances[k]^2
+ *   ([num_slots][3], [num_slots], [num_slots][3], [num_slots]: every slot written, zeros for unused ones).  positions and box are read
+ *   only when gg_box is given (then both are required); grad_deltas does not enter. */
+int64_t nnpops_neighbor_pairs_box_backward_workspace_bytes(int64_t num_slots);
+int nnpops_neighbor_pairs_box_backward(int dtype, int num_atoms, int64_t num_slots, const int32_t* neighbors, const void* positions,
+                                       const void* box, const void* deltas, const void* distances, const void* grad_deltas,
+                                       const void* grad_distances, void* grad_box, void* workspace, void* stream);
+int nnpops_neighbor_pairs_double_backward(int dtype, int num_atoms, int64_t num_slots, const int32_t* neighbors, const void* positions,
+                                          const void* box, const void* deltas, const void* distances, const void* grad_distances,
+                                          const void* gg_positions, const void* gg_box, void* d_grad_deltas, void* d_grad_distances,
+                                          void* d_deltas, void* d_distances, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * PME, direct-space part (replaces computeDirect: src/pytorch/pme/pmeCUDA.cu:30-100, pmeCPU.cpp:75-163) -- the immediate

@@ -101,6 +101,12 @@ SIGNATURES = {
     "nnpops_neighbor_pairs_backward_indexed_workspace_bytes": (C.c_int64, [C.c_int, C.c_int64]),
     "nnpops_neighbor_pairs_backward_indexed": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nnpops_neighbor_pairs_box_backward_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "nnpops_neighbor_pairs_box_backward": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nnpops_neighbor_pairs_double_backward": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_neighbor_pairs_backward_ws": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
@@ -394,6 +400,37 @@ def neighbor_pairs_backward_indexed(num_atoms, neighbors, deltas, distances, gra
                                                         _ptr(grad_deltas.contiguous()), _ptr(grad_distances.contiguous()),
                                                         _ptr(index), _ptr(grad_positions), _ptr(ws), _stream_ptr(dev)))
     return grad_positions
+
+
+def neighbor_pairs_box_backward(num_atoms, neighbors, positions, box, deltas, distances, grad_deltas, grad_distances):
+    """grad_box [3,3] = - sum_k n_k (x) G_k of the backward pass (n_k: the slot's minimum-image shift, recovered from positions, box and
+    deltas).  Any list, compacted or not, in any order; float64 sums in a fixed order (bitwise reproducible).  box in deltas' dtype."""
+    dev, dt = deltas.device, deltas.dtype
+    grad_box = torch.empty((3, 3), dtype=dt, device=dev)
+    L = lib()
+    slots = distances.numel()
+    with torch.cuda.device(dev):
+        ws = torch.empty((int(L.nnpops_neighbor_pairs_box_backward_workspace_bytes(slots)) // 8,), dtype=torch.float64, device=dev)
+        _check(L.nnpops_neighbor_pairs_box_backward(_DTYPE_CODE[dt], num_atoms, slots, _ptr(neighbors), _ptr(positions.contiguous()),
+                                                    _ptr(box.contiguous()), _ptr(deltas.contiguous()), _ptr(distances.contiguous()),
+                                                    _ptr(grad_deltas.contiguous()), _ptr(grad_distances.contiguous()), _ptr(grad_box),
+                                                    _ptr(ws), _stream_ptr(dev)))
+    return grad_box
+
+
+def neighbor_pairs_double_backward(num_atoms, neighbors, deltas, distances, grad_distances, gg_positions=None, gg_box=None,
+                                   positions=None, box=None):
+    """Vector-Jacobian product of the backward pass with (gg_positions [N,3], gg_box [3,3]), either may be None.
+    -> (d_grad_deltas [P,3], d_grad_distances [P], d_deltas [P,3], d_distances [P]).  positions and box are needed with gg_box only."""
+    dev, dt = deltas.device, deltas.dtype
+    slots = distances.numel()
+    outs = (torch.empty((slots, 3), dtype=dt, device=dev), torch.empty((slots,), dtype=dt, device=dev),
+            torch.empty((slots, 3), dtype=dt, device=dev), torch.empty((slots,), dtype=dt, device=dev))
+    ins = [None if t is None else t.contiguous() for t in (positions, box, deltas, distances, grad_distances, gg_positions, gg_box)]
+    with torch.cuda.device(dev):
+        _check(lib().nnpops_neighbor_pairs_double_backward(_DTYPE_CODE[dt], num_atoms, slots, _ptr(neighbors), *(_ptr(t) for t in ins),
+                                                           *(_ptr(t) for t in outs), _stream_ptr(dev)))
+    return outs
 
 
 def pme_direct(positions, charges, neighbors, deltas, distances, exclusions, alpha, coulomb, index=None):

@@ -903,6 +903,245 @@ PairIndexCache& pair_index_cache(int device) {
     return (*slots)[(size_t)std::max(0, std::min(device, 63))];
 }
 
+// ---------------------------------------------------------------------------------------------
+// Second order and the box.  The backward pass of getNeighborPairs is itself a differentiable function (both keys):
+//     NeighborPairsBackwardFunction        Bwd(grad_deltas, grad_distances, deltas, distances) -> (grad_positions, grad_box)
+// Its forward runs the first-order kernels of round 6 unchanged for grad_positions (the indexed gather when the forward op built an
+// index, the fixed-point sums otherwise; plain loops on the host key) and adds the box reduction only when the box needs a gradient.
+// deltas and distances reach it as the forward op's saved OUTPUTS, so autograd chains its own backward -- the per-slot
+//     NeighborPairsDoubleBackwardFunction  (gg_positions, gg_box) -> d(grad_deltas, grad_distances, deltas, distances)
+// (pairs_second_order.hip: derivation) -- back through the forward op's backward, which is Bwd again: Hessian-vector products with
+// respect to positions and box.  A third derivative raises instead of dropping terms.  Without create_graph and without a box
+// gradient nothing of this is recorded: the same kernels as before run, and nothing more is saved.
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+void neighbor_pairs_host_backward(const Tensor& neighbors, const Tensor& deltas, const Tensor& distances, const Tensor& gd,
+                                  const Tensor& gr, Tensor& gpos);      // (host key, below)
+
+// the slot's minimum-image shift n_k, recovered from positions, box and its delta (pairs_second_order.hip: image_shift)
+template <typename T>
+void host_image_shift(const T* pos, const T* box, int64_t i, int64_t j, const T* d, T (&n)[3]) {
+    T D[3];
+    for (int c = 0; c < 3; c++) D[c] = (pos[3 * i + c] - pos[3 * j + c]) - d[c];
+    n[2] = std::round(D[2] / box[8]);
+    n[1] = std::round((D[1] - n[2] * box[7]) / box[4]);
+    n[0] = std::round((D[0] - n[2] * box[6] - n[1] * box[3]) / box[0]);
+}
+
+// grad_box[a][:] = - sum_k n_ka G_k, G_k as neighbor_pairs_host_backward forms it (float64 sums in slot order)
+template <typename T>
+void neighbor_pairs_host_box_backward(const Tensor& neighbors, const Tensor& positions, const Tensor& box, const Tensor& deltas,
+                                      const Tensor& distances, const Tensor& gd, const Tensor& gr, Tensor& gbox) {
+    const int64_t slots = distances.size(0), n_atoms = positions.size(0);
+    const int32_t* nb = neighbors.data_ptr<int32_t>();
+    const T* pos = positions.data_ptr<T>();
+    const T* b = box.data_ptr<T>();
+    const T* dl = deltas.data_ptr<T>();
+    const T* ds = distances.data_ptr<T>();
+    const T* pgd = gd.data_ptr<T>();
+    const T* pgr = gr.data_ptr<T>();
+    double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int64_t k = 0; k < slots; k++) {
+        const int32_t row = nb[k], col = nb[slots + k];
+        if (row < 0 || col < 0 || row >= n_atoms || col >= n_atoms) continue;
+        T G[3], n[3];
+        for (int c = 0; c < 3; c++) G[c] = pgd[3 * k + c] + (ds[k] > 0 ? dl[3 * k + c] / ds[k] * pgr[k] : (T)0);
+        host_image_shift<T>(pos, b, row, col, dl + 3 * k, n);
+        for (int a = 0; a < 3; a++)
+            for (int c = 0; c < 3; c++) acc[3 * a + c] -= (double)n[a] * (double)G[c];
+    }
+    T* out = gbox.data_ptr<T>();
+    for (int q = 0; q < 9; q++) out[q] = (T)acc[q];
+}
+
+// the vector-Jacobian product of the backward pass (pairs_second_order.hip), r = 0 guarded as in neighbor_pairs_host_backward
+template <typename T>
+void neighbor_pairs_host_double_backward(const Tensor& neighbors, const Tensor& positions, const Tensor& box, const Tensor& deltas,
+                                         const Tensor& distances, const Tensor& gr, const Tensor& hx, const Tensor& hb, tensor_list& out,
+                                         int64_t n_atoms) {
+    const int64_t slots = distances.size(0);
+    const int32_t* nb = neighbors.data_ptr<int32_t>();
+    const T* dl = deltas.data_ptr<T>();
+    const T* ds = distances.data_ptr<T>();
+    const T* pgr = gr.data_ptr<T>();
+    const T* phx = hx.defined() ? hx.data_ptr<T>() : nullptr;
+    const T* phb = hb.defined() ? hb.data_ptr<T>() : nullptr;
+    const T* pos = phb ? positions.data_ptr<T>() : nullptr;
+    const T* b = phb ? box.data_ptr<T>() : nullptr;
+    T* o_gd = out[0].data_ptr<T>();
+    T* o_gr = out[1].data_ptr<T>();
+    T* o_dl = out[2].data_ptr<T>();
+    T* o_ds = out[3].data_ptr<T>();
+    for (int64_t k = 0; k < slots; k++) {
+        const int32_t row = nb[k], col = nb[slots + k];
+        T w[3] = {0, 0, 0};
+        T a = 0, s = 0, c = 0;
+        if (row >= 0 && col >= 0 && row < n_atoms && col < n_atoms) {
+            if (phx)
+                for (int q = 0; q < 3; q++) w[q] = phx[3 * row + q] - phx[3 * col + q];
+            if (phb) {
+                T n[3];
+                host_image_shift<T>(pos, b, row, col, dl + 3 * k, n);
+                for (int q = 0; q < 3; q++) w[q] -= n[0] * phb[q] + n[1] * phb[3 + q] + n[2] * phb[6 + q];
+            }
+            const T r = ds[k];
+            if (r > 0) {
+                const T dw = dl[3 * k] * w[0] + dl[3 * k + 1] * w[1] + dl[3 * k + 2] * w[2];
+                a = dw / r;
+                s = pgr[k] / r;
+                c = -s * dw / r;
+            }
+        }
+        for (int q = 0; q < 3; q++) { o_gd[3 * k + q] = w[q]; o_dl[3 * k + q] = s * w[q]; }
+        o_gr[k] = a;
+        o_ds[k] = c;
+    }
+}
+
+// grad_positions of the first-order pass: exactly the kernels (host loops) that ran before the box and second order existed
+Tensor pairs_grad_positions(const Tensor& neighbors, const Tensor& index, const Tensor& deltas, const Tensor& distances,
+                            const Tensor& grad_deltas, const Tensor& grad_distances, int64_t num_atoms) {
+    if (!deltas.is_cuda()) {
+        Tensor gpos = torch::zeros({num_atoms, 3}, deltas.options());
+        if (deltas.scalar_type() == torch::kFloat64) neighbor_pairs_host_backward<double>(neighbors, deltas, distances, grad_deltas, grad_distances, gpos);
+        else neighbor_pairs_host_backward<float>(neighbors, deltas, distances, grad_deltas, grad_distances, gpos);
+        return gpos;
+    }
+    Tensor grad_positions = torch::empty({num_atoms, 3}, deltas.options());
+    const int dtype = deltas.scalar_type() == torch::kFloat64 ? 1 : 0;
+    c10::hip::HIPGuard guard(deltas.device().index());
+    if (index.defined()) {
+        Tensor terms = torch::empty({nnpops_neighbor_pairs_backward_indexed_workspace_bytes(dtype, distances.size(0)) / 8 + 1},
+                                    deltas.options().dtype(torch::kInt64));
+        if (nnpops_neighbor_pairs_backward_indexed(dtype, (int)num_atoms, distances.size(0), neighbors.data_ptr<int32_t>(), deltas.data_ptr(),
+                                                   distances.data_ptr(), grad_deltas.data_ptr(), grad_distances.data_ptr(),
+                                                   index.data_ptr<int32_t>(), grad_positions.data_ptr(), terms.data_ptr(),
+                                                   current_stream(deltas.device())) != NNPOPS_OK)
+            raise_last("neighbors::getNeighborPairs backward");
+        return grad_positions;
+    }
+    // (scratch for the order-independent fixed-point sums of the backward pass: no float atomics, nnpops_hip.h)
+    Tensor workspace = torch::empty({nnpops_neighbor_pairs_backward_workspace_bytes((int)num_atoms) / 8}, deltas.options().dtype(torch::kInt64));
+    if (nnpops_neighbor_pairs_backward_ws(dtype, (int)num_atoms, distances.size(0), neighbors.data_ptr<int32_t>(), deltas.data_ptr(),
+                                          distances.data_ptr(), grad_deltas.data_ptr(), grad_distances.data_ptr(),
+                                          grad_positions.data_ptr(), workspace.data_ptr(), current_stream(deltas.device())) != NNPOPS_OK)
+        raise_last("neighbors::getNeighborPairs backward");
+    return grad_positions;
+}
+
+// grad_box [3, 3] in deltas' dtype; positions and box as the forward op used them (box cast to the positions' dtype)
+Tensor pairs_grad_box(const Tensor& neighbors, const Tensor& positions, const Tensor& box, const Tensor& deltas, const Tensor& distances,
+                      const Tensor& grad_deltas, const Tensor& grad_distances) {
+    Tensor gbox = torch::empty({3, 3}, deltas.options());
+    if (!deltas.is_cuda()) {
+        if (deltas.scalar_type() == torch::kFloat64)
+            neighbor_pairs_host_box_backward<double>(neighbors, positions, box, deltas, distances, grad_deltas, grad_distances, gbox);
+        else
+            neighbor_pairs_host_box_backward<float>(neighbors, positions, box, deltas, distances, grad_deltas, grad_distances, gbox);
+        return gbox;
+    }
+    const int dtype = deltas.scalar_type() == torch::kFloat64 ? 1 : 0;
+    const int64_t slots = distances.size(0);
+    c10::hip::HIPGuard guard(deltas.device().index());
+    Tensor workspace = torch::empty({nnpops_neighbor_pairs_box_backward_workspace_bytes(slots) / 8}, deltas.options().dtype(torch::kFloat64));
+    if (nnpops_neighbor_pairs_box_backward(dtype, (int)positions.size(0), slots, neighbors.data_ptr<int32_t>(), positions.data_ptr(), box.data_ptr(),
+                                           deltas.data_ptr(), distances.data_ptr(), grad_deltas.data_ptr(), grad_distances.data_ptr(),
+                                           gbox.data_ptr(), workspace.data_ptr(), current_stream(deltas.device())) != NNPOPS_OK)
+        raise_last("neighbors::getNeighborPairs backward (box)");
+    return gbox;
+}
+
+std::optional<Tensor> opt(const Tensor& t) { return t.defined() ? std::optional<Tensor>(t) : std::nullopt; }
+
+class NeighborPairsDoubleBackwardFunction : public torch::autograd::Function<NeighborPairsDoubleBackwardFunction> {
+public:
+    // (optional tensors: autograd records no input for an absent one)
+    static tensor_list forward(AutogradContext* ctx, const std::optional<Tensor>& gg_positions_opt, const std::optional<Tensor>& gg_box_opt,
+                               const Tensor& deltas, const Tensor& distances, const Tensor& grad_distances, const Tensor& neighbors,
+                               const std::optional<Tensor>& positions_opt, const std::optional<Tensor>& box_opt, int64_t num_atoms) {
+        const Tensor gg_positions = gg_positions_opt.value_or(Tensor()), gg_box = gg_box_opt.value_or(Tensor());
+        const Tensor positions = positions_opt.value_or(Tensor()), box = box_opt.value_or(Tensor());
+        const int64_t slots = distances.size(0);
+        tensor_list out = {torch::empty({slots, 3}, deltas.options()), torch::empty({slots}, deltas.options()),
+                           torch::empty({slots, 3}, deltas.options()), torch::empty({slots}, deltas.options())};
+        const Tensor hb = box.defined() ? gg_box : Tensor();
+        if (!deltas.is_cuda()) {
+            if (deltas.scalar_type() == torch::kFloat64)
+                neighbor_pairs_host_double_backward<double>(neighbors, positions, box, deltas, distances, grad_distances, gg_positions, hb, out, num_atoms);
+            else
+                neighbor_pairs_host_double_backward<float>(neighbors, positions, box, deltas, distances, grad_distances, gg_positions, hb, out, num_atoms);
+            return out;
+        }
+        auto ptr = [](const Tensor& t) -> const void* { return t.defined() ? t.data_ptr() : nullptr; };
+        c10::hip::HIPGuard guard(deltas.device().index());
+        if (nnpops_neighbor_pairs_double_backward(deltas.scalar_type() == torch::kFloat64 ? 1 : 0, (int)num_atoms, slots, neighbors.data_ptr<int32_t>(),
+                                                  hb.defined() ? positions.data_ptr() : nullptr, hb.defined() ? box.data_ptr() : nullptr,
+                                                  deltas.data_ptr(), distances.data_ptr(), grad_distances.data_ptr(), ptr(gg_positions), ptr(hb),
+                                                  out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(),
+                                                  current_stream(deltas.device())) != NNPOPS_OK)
+            raise_last("neighbors::getNeighborPairs double backward");
+        return out;
+    }
+
+    static tensor_list backward(AutogradContext*, tensor_list) {
+        TORCH_CHECK(false, "neighbors::getNeighborPairs: third derivatives are not implemented");
+        return {};
+    }
+};
+
+class NeighborPairsBackwardFunction : public torch::autograd::Function<NeighborPairsBackwardFunction> {
+public:
+    // positions / box: defined (detached, box in the positions' dtype) only when want_box
+    static tensor_list forward(AutogradContext* ctx, const Tensor& grad_deltas, const Tensor& grad_distances, const Tensor& deltas,
+                               const Tensor& distances, const Tensor& neighbors, const std::optional<Tensor>& index_opt,
+                               const std::optional<Tensor>& positions_opt, const std::optional<Tensor>& box_opt, int64_t num_atoms,
+                               bool want_positions, bool want_box) {
+        const Tensor index = index_opt.value_or(Tensor()), positions = positions_opt.value_or(Tensor()), box = box_opt.value_or(Tensor());
+        // -> {grad_positions if want_positions, grad_box if want_box} (no undefined outputs: autograd cannot describe them)
+        ctx->set_materialize_grads(false);
+        tensor_list out;
+        if (want_positions) out.push_back(pairs_grad_positions(neighbors, index, deltas, distances, grad_deltas, grad_distances, num_atoms));
+        if (want_box) out.push_back(pairs_grad_box(neighbors, positions, box, deltas, distances, grad_deltas, grad_distances));
+        ctx->save_for_backward({deltas, distances, grad_distances, neighbors, positions, box});
+        ctx->saved_data["num_atoms"] = num_atoms;
+        ctx->saved_data["want_positions"] = want_positions;
+        return out;
+    }
+
+    static tensor_list backward(AutogradContext* ctx, tensor_list grads) {
+        const auto saved = ctx->get_saved_variables();
+        const Tensor deltas = saved[0], distances = saved[1], grad_distances = saved[2], neighbors = saved[3], positions = saved[4], box = saved[5];
+        const bool want_positions = ctx->saved_data["want_positions"].toBool();
+        const Tensor gx = want_positions ? grads[0] : Tensor();
+        const Tensor gb = box.defined() ? grads[want_positions ? 1 : 0] : Tensor();
+        const Tensor hx = gx.defined() ? gx.contiguous() : Tensor();
+        const Tensor hb = gb.defined() ? gb.contiguous() : Tensor();
+        tensor_list out(11);
+        if (!hx.defined() && !hb.defined()) return out;
+        const tensor_list d = NeighborPairsDoubleBackwardFunction::apply(opt(hx), opt(hb), deltas, distances, grad_distances, neighbors, opt(positions),
+                                                                         opt(box), ctx->saved_data["num_atoms"].toInt());
+        for (int q = 0; q < 4; q++) out[q] = d[q];
+        return out;
+    }
+};
+
+// the forward ops' backward: Bwd, and the box gradient back in box_vectors' own dtype
+tensor_list neighbor_pairs_backward_entry(AutogradContext* ctx, const tensor_list& grad_outputs) {
+    const auto saved = ctx->get_saved_variables();
+    const Tensor neighbors = saved[0], deltas = saved[1], distances = saved[2], index = saved[3], positions = saved[4], box = saved[5];
+    const int64_t num_atoms = ctx->saved_data["num_atoms"].toInt();
+    const Tensor grad_deltas = grad_outputs[1].defined() ? grad_outputs[1].contiguous() : torch::zeros_like(deltas);
+    const Tensor grad_distances = grad_outputs[2].defined() ? grad_outputs[2].contiguous() : torch::zeros_like(distances);
+    const bool want_box = ctx->needs_input_grad(1) && box.defined();
+    const tensor_list g = NeighborPairsBackwardFunction::apply(grad_deltas, grad_distances, deltas, distances, neighbors, opt(index),
+                                                               opt(want_box ? positions : Tensor()), opt(want_box ? box : Tensor()), num_atoms,
+                                                               ctx->needs_input_grad(0), want_box);
+    const bool want_positions = ctx->needs_input_grad(0);
+    const Tensor grad_positions = want_positions ? g[0] : Tensor();
+    const Tensor grad_box = want_box ? g[want_positions ? 1 : 0].to((torch::ScalarType)ctx->saved_data["box_dtype"].toInt()) : Tensor();
+    return {grad_positions, Tensor(), Tensor(), grad_box, Tensor()};
+}
+
 class NeighborPairsFunction : public torch::autograd::Function<NeighborPairsFunction> {
 public:
     static tensor_list forward(AutogradContext* ctx, const Tensor& positions, const torch::Scalar& cutoff,
@@ -965,38 +1204,15 @@ public:
             PairIndexCache& cache = pair_index_cache(positions.device().index());
             cache.neighbors = neighbors; cache.index = index; cache.version = neighbors._version();
         }
-        ctx->save_for_backward({neighbors, deltas, distances, index});
+        // (positions and the cast box only when the box needs a gradient: its n_k are recovered from them, pairs_second_order.hip)
+        const bool box_grad = use_periodic && box_vectors.requires_grad();
+        ctx->save_for_backward({neighbors, deltas, distances, index, box_grad ? positions.detach() : Tensor(), box_grad ? box.detach() : Tensor()});
         ctx->saved_data["num_atoms"] = num_atoms;
+        ctx->saved_data["box_dtype"] = (int64_t)box_vectors.scalar_type();
         return {neighbors, deltas, distances, num_pairs};
     }
 
-    static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) {
-        const auto saved = ctx->get_saved_variables();
-        const Tensor neighbors = saved[0], deltas = saved[1], distances = saved[2], index = saved[3];
-        const int64_t num_atoms = ctx->saved_data["num_atoms"].toInt();
-        const Tensor grad_deltas = grad_outputs[1].defined() ? grad_outputs[1].contiguous() : torch::zeros_like(deltas);
-        const Tensor grad_distances = grad_outputs[2].defined() ? grad_outputs[2].contiguous() : torch::zeros_like(distances);
-        Tensor grad_positions = torch::empty({num_atoms, 3}, deltas.options());
-        const int dtype = deltas.scalar_type() == torch::kFloat64 ? 1 : 0;
-        c10::hip::HIPGuard guard(deltas.device().index());
-        if (index.defined()) {
-            Tensor terms = torch::empty({nnpops_neighbor_pairs_backward_indexed_workspace_bytes(dtype, distances.size(0)) / 8 + 1},
-                                        deltas.options().dtype(torch::kInt64));
-            if (nnpops_neighbor_pairs_backward_indexed(dtype, (int)num_atoms, distances.size(0), neighbors.data_ptr<int32_t>(), deltas.data_ptr(),
-                                                       distances.data_ptr(), grad_deltas.data_ptr(), grad_distances.data_ptr(),
-                                                       index.data_ptr<int32_t>(), grad_positions.data_ptr(), terms.data_ptr(),
-                                                       current_stream(deltas.device())) != NNPOPS_OK)
-                raise_last("neighbors::getNeighborPairs backward");
-            return {grad_positions, Tensor(), Tensor(), Tensor(), Tensor()};
-        }
-        // (scratch for the order-independent fixed-point sums of the backward pass: no float atomics, nnpops_hip.h)
-        Tensor workspace = torch::empty({nnpops_neighbor_pairs_backward_workspace_bytes((int)num_atoms) / 8}, deltas.options().dtype(torch::kInt64));
-        if (nnpops_neighbor_pairs_backward_ws(dtype, (int)num_atoms, distances.size(0), neighbors.data_ptr<int32_t>(), deltas.data_ptr(),
-                                              distances.data_ptr(), grad_deltas.data_ptr(), grad_distances.data_ptr(),
-                                              grad_positions.data_ptr(), workspace.data_ptr(), current_stream(deltas.device())) != NNPOPS_OK)
-            raise_last("neighbors::getNeighborPairs backward");
-        return {grad_positions, Tensor(), Tensor(), Tensor(), Tensor()};
-    }
+    static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) { return neighbor_pairs_backward_entry(ctx, grad_outputs); }
 };
 
 TORCH_LIBRARY(neighbors, m) {
@@ -1158,22 +1374,15 @@ public:
             neighbor_pairs_host<float>(positions, box, c, max_pairs, checkErrors, neighbors, deltas, distances);
         Tensor num_pairs = torch::empty({1}, positions.options().dtype(torch::kInt32));
         num_pairs.data_ptr<int32_t>()[0] = (int32_t)distances.size(0);
-        ctx->save_for_backward({neighbors, deltas, distances});
+        const bool box_grad = box.defined() && box_vectors.requires_grad();
+        ctx->save_for_backward({neighbors, deltas, distances, Tensor(), box_grad ? positions.detach() : Tensor(),
+                                box_grad ? box_vectors.detach().to(positions.scalar_type()).contiguous() : Tensor()});
         ctx->saved_data["num_atoms"] = positions.size(0);
+        ctx->saved_data["box_dtype"] = (int64_t)box_vectors.scalar_type();
         return {neighbors, deltas, distances, num_pairs};
     }
 
-    static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) {
-        const auto saved = ctx->get_saved_variables();
-        const Tensor neighbors = saved[0], deltas = saved[1], distances = saved[2];
-        const int64_t num_atoms = ctx->saved_data["num_atoms"].toInt();
-        const Tensor gd = grad_outputs[1].defined() ? grad_outputs[1].contiguous() : torch::zeros_like(deltas);
-        const Tensor gr = grad_outputs[2].defined() ? grad_outputs[2].contiguous() : torch::zeros_like(distances);
-        Tensor gpos = torch::zeros({num_atoms, 3}, deltas.options());
-        if (deltas.scalar_type() == torch::kFloat64) neighbor_pairs_host_backward<double>(neighbors, deltas, distances, gd, gr, gpos);
-        else neighbor_pairs_host_backward<float>(neighbors, deltas, distances, gd, gr, gpos);
-        return {gpos, Tensor(), Tensor(), Tensor(), Tensor()};
-    }
+    static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) { return neighbor_pairs_backward_entry(ctx, grad_outputs); }
 };
 
 std::tuple<Tensor, Tensor, Tensor, Tensor> neighbor_pairs_host_entry(const Tensor& positions, const torch::Scalar& cutoff,

@@ -22,6 +22,14 @@ def getNeighborPairs(positions: Tensor, cutoff: float, max_num_pairs: int = -1, 
 
     Unlike the reference's GPU path the compacted list comes out in a deterministic order (grouped by
     ``neighbors[0]``, ascending).
+
+    Differentiable, on the GPU and on host tensors alike, with respect to ``positions`` and ``box_vectors``
+    (the minimum-image rounds count as constants, as in the reference's CPU op), and twice: the backward pass
+    is itself differentiable, so ``torch.autograd.grad(E, positions, create_graph=True)`` gives forces that a
+    loss can be differentiated through (force matching), Hessian-vector products, and dE/dbox (the virial)
+    with its derivatives.  The gradient of ``box_vectors`` has their dtype and covers all nine entries, as the
+    reference's composition differentiates whole rows.  Third derivatives raise a RuntimeError.
+    ``pme_direct`` does not pass gradients into ``deltas``, so box gradients through PME remain unavailable.
     """
     if box_vectors is None:
         box_vectors = empty((0, 0), device=positions.device, dtype=positions.dtype)
