@@ -18,6 +18,8 @@
  *   nnpops_neighbor_pairs_box_backward / _double_backward   box gradient and second derivatives of that op
  *                                               (the reference's CPU op differentiates both: getNeighborPairsCPU.cpp:56-98)
  *   nnpops_pme_direct                           pme::pme_direct (computeDirect)   src/pytorch/pme/pmeCUDA.cu:30-100
+ *   nnpops_pme_direct_box, nnpops_pme_reciprocal_convolve_box / _box_gradient   box gradients of both PME terms (no reference
+ *                                               counterpart: pme::pme_direct_box and the box gradient of pme::pme_reciprocal)
  *
  * Conventions
  *   - plain C: opaque handles, raw pointers, sizes.  No torch / C++ types cross this boundary.
@@ -331,6 +333,18 @@ int nnpops_pme_direct_indexed(int num_atoms, int64_t num_pairs, int max_exclusio
                               const int32_t* neighbors, const float* deltas, const float* distances, const int32_t* exclusions,
                               const int32_t* index, float alpha, float coulomb, float* energy, float* position_deriv,
                               float* charge_deriv, void* workspace, void* stream);
+/* Box gradient of the direct-space energy above (additive): grad_box [3][3] (device float32, rows = box vectors, all nine entries)
+ * = dE/dB = - sum_k n_k (x) G_k over the included pairs (both atoms in [0, num_atoms), not excluded), G_k = dE/ddelta_k =
+ * -dedr_k deltas[k] with the direct kernels' dedr, n_k the slot's integer minimum-image shift recovered from positions, box_vectors
+ * and deltas[k] (box_vectors: device float32 [3][3], reduced triclinic, the box the list was built with).  Excluded pairs are taken
+ * un-wrapped and add nothing.  Any list order, -1 slots anywhere; it only reads the list, so it serves lists with and without a
+ * transposed index.  Float64 sums per block in a fixed order, then over the blocks in a fixed order: bitwise reproducible, no
+ * atomics, no host synchronisation (graph-capturable).  workspace: device, 8-byte aligned,
+ * nnpops_pme_direct_box_workspace_bytes(num_pairs) bytes. */
+int64_t nnpops_pme_direct_box_workspace_bytes(int64_t num_pairs);
+int nnpops_pme_direct_box(int num_atoms, int64_t num_pairs, int max_exclusions, const float* positions, const float* charges,
+                          const int32_t* neighbors, const float* deltas, const float* distances, const int32_t* exclusions,
+                          const float* box_vectors, float alpha, float coulomb, float* grad_box, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * PME, reciprocal-space part (replaces computeReciprocal: src/pytorch/pme/pmeCUDA.cu:102-430, pmeCPU.cpp:174-364).  Three passes
@@ -359,6 +373,23 @@ int nnpops_pme_reciprocal_convolve(int num_atoms, int gridx, int gridy, int grid
 int nnpops_pme_reciprocal_interpolate(int num_atoms, int gridx, int gridy, int gridz, int order, const float* charges,
                                       const float* box_vectors, float coulomb, const float* real_grid, float* position_deriv,
                                       float* charge_deriv, void* workspace, void* stream);
+/* Box gradient of the reciprocal-space energy (additive).  With E = 0.5 sum_k w E'_k (E'_k = eterm |S(k)|^2, the sum of step 3),
+ * b = pi^2 / alpha^2, m_k = B^-1 k and g_j = dE/dx_j (step 5):
+ *     grad_box = dE/dB = - B^-T (Pi + X),  Pi = 0.5 sum_{k != 0} w E'_k [I - 2 (b + 1/|m_k|^2) m_k m_k^T],  X = sum_j x_j (x) g_j
+ * (positions held fixed as passed, not wrapped; all nine entries).  Two entries take the place of / follow the steps above:
+ *   3'. nnpops_pme_reciprocal_convolve_box: step 3 -- the same scaled grid and energy, bit for bit -- that also leaves the per-workgroup
+ *       float64 sums of Pi in box_workspace;
+ *   6.  nnpops_pme_reciprocal_box_gradient: after step 5, X from positions and position_deriv (the unscaled dE/dpositions of step 5),
+ *       then grad_box (device float32 [3][3]) = - B^-T (Pi + X), B^-1 the general 3 x 3 inverse in float64.
+ * box_workspace: device scratch of nnpops_pme_reciprocal_box_workspace_bytes(...) bytes, the same buffer for 3' and 6 (the step-3
+ * workspace keeps its size).  Fixed-order float64 sums, no atomics: bitwise reproducible.  Graph-capturable. */
+int64_t nnpops_pme_reciprocal_box_workspace_bytes(int num_atoms, int gridx, int gridy, int gridz, int order);
+int nnpops_pme_reciprocal_convolve_box(int num_atoms, int gridx, int gridy, int gridz, int order, const float* box_vectors, float alpha,
+                                       const float* xmoduli, const float* ymoduli, const float* zmoduli, void* recip_grid, float* energy,
+                                       void* workspace, void* box_workspace, void* stream);
+int nnpops_pme_reciprocal_box_gradient(int num_atoms, int gridx, int gridy, int gridz, int order, const float* positions,
+                                       const float* box_vectors, const float* position_deriv, float* grad_box, void* box_workspace,
+                                       void* stream);
 
 /* ---- dense layers of the ANI atomic networks (reference src/pytorch/BatchedNN.cpp:30-50, BatchedNN.py:37-122) ----
  * C[M x N] = A[M x K] B with fp32 in and out; the products run on the half-precision matrix instruction with every

@@ -92,6 +92,14 @@ SIGNATURES = {
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_pme_reciprocal_interpolate": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nnpops_pme_direct_box_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "nnpops_pme_direct_box": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nnpops_pme_reciprocal_box_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nnpops_pme_reciprocal_convolve_box": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nnpops_pme_reciprocal_box_gradient": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_neighbor_pairs_backward": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_neighbor_pairs_backward_workspace_bytes": (C.c_int64, [C.c_int]),
@@ -492,6 +500,62 @@ def pme_reciprocal(positions, charges, box_vectors, gridx, gridy, gridz, order, 
         _check(L.nnpops_pme_reciprocal_interpolate(n, gridx, gridy, gridz, order, _ptr(charges), _ptr(box_vectors), float(coulomb),
                                                    _ptr(grid), _ptr(pos_deriv), _ptr(charge_deriv), _ptr(ws), _stream_ptr(dev)))
     return energy, pos_deriv, charge_deriv
+
+
+def pme_direct_box(positions, charges, neighbors, deltas, distances, exclusions, box_vectors, alpha, coulomb):
+    """dE/dbox [3, 3] float32 of the direct-space PME energy: - sum_k n_k (x) G_k over the included pairs (n_k: the slot's
+    minimum-image shift, recovered from positions, box and deltas).  Any list order; float64 sums in a fixed order."""
+    _dev_f32(positions, "positions")
+    _dev_f32(charges, "charges")
+    _dev_f32(box_vectors, "box_vectors", (3, 3))
+    n, pairs = positions.size(0), neighbors.size(1)
+    dev = positions.device
+    exclusions = exclusions.to(device=dev, dtype=torch.int32).contiguous()
+    max_excl = exclusions.size(1)
+    grad_box = torch.empty((3, 3), dtype=torch.float32, device=dev)
+    L = lib()
+    with torch.cuda.device(dev):
+        ws = torch.empty((int(L.nnpops_pme_direct_box_workspace_bytes(pairs)) // 8,), dtype=torch.float64, device=dev)
+        _check(L.nnpops_pme_direct_box(n, pairs, max_excl, _ptr(positions.contiguous()), _ptr(charges.contiguous()),
+                                       _ptr(neighbors.to(torch.int32).contiguous()), _ptr(deltas.contiguous()),
+                                       _ptr(distances.contiguous()), _ptr(exclusions) if max_excl else None,
+                                       _ptr(box_vectors.contiguous()), float(alpha), float(coulomb), _ptr(grad_box), _ptr(ws),
+                                       _stream_ptr(dev)))
+    return grad_box
+
+
+def pme_reciprocal_box(positions, charges, box_vectors, gridx, gridy, gridz, order, alpha, coulomb, xmoduli, ymoduli, zmoduli):
+    """pme_reciprocal with the box gradient: spread -> rfftn -> convolve_box -> irfftn -> interpolate -> box_gradient.
+    -> (energy float32[1], dE/dpositions [N, 3], dE/dcharges [N], dE/dbox [3, 3])."""
+    _dev_f32(positions, "positions")
+    _dev_f32(charges, "charges")
+    _dev_f32(box_vectors, "box_vectors", (3, 3))
+    dev = positions.device
+    n = positions.size(0)
+    mods = [_dev_f32(m.to(device=dev, dtype=torch.float32).contiguous(), name, (k,))
+            for m, name, k in ((xmoduli, "xmoduli", gridx), (ymoduli, "ymoduli", gridy), (zmoduli, "zmoduli", gridz))]
+    L = lib()
+    ws = torch.empty((int(L.nnpops_pme_reciprocal_workspace_bytes(n, gridx, gridy, gridz, order)),), dtype=torch.uint8, device=dev)
+    box_ws = torch.empty((int(L.nnpops_pme_reciprocal_box_workspace_bytes(n, gridx, gridy, gridz, order)),), dtype=torch.uint8,
+                         device=dev)
+    real = torch.empty((gridx, gridy, gridz), dtype=torch.float32, device=dev)
+    energy = torch.empty((1,), dtype=torch.float32, device=dev)
+    pos_deriv = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    charge_deriv = torch.empty((n,), dtype=torch.float32, device=dev)
+    grad_box = torch.empty((3, 3), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _check(L.nnpops_pme_reciprocal_spread(n, gridx, gridy, gridz, order, _ptr(positions), _ptr(charges), _ptr(box_vectors),
+                                              float(coulomb), _ptr(real), _ptr(ws), _stream_ptr(dev)))
+        recip = torch.fft.rfftn(real).contiguous()
+        _check(L.nnpops_pme_reciprocal_convolve_box(n, gridx, gridy, gridz, order, _ptr(box_vectors), float(alpha), _ptr(mods[0]),
+                                                    _ptr(mods[1]), _ptr(mods[2]), _ptr(recip), _ptr(energy), _ptr(ws), _ptr(box_ws),
+                                                    _stream_ptr(dev)))
+        grid = torch.fft.irfftn(recip, s=(gridx, gridy, gridz), norm="forward").contiguous()
+        _check(L.nnpops_pme_reciprocal_interpolate(n, gridx, gridy, gridz, order, _ptr(charges), _ptr(box_vectors), float(coulomb),
+                                                   _ptr(grid), _ptr(pos_deriv), _ptr(charge_deriv), _ptr(ws), _stream_ptr(dev)))
+        _check(L.nnpops_pme_reciprocal_box_gradient(n, gridx, gridy, gridz, order, _ptr(positions), _ptr(box_vectors), _ptr(pos_deriv),
+                                                    _ptr(grad_box), _ptr(box_ws), _stream_ptr(dev)))
+    return energy, pos_deriv, charge_deriv, grad_box
 
 
 # ---------------------------------------------------------------------------------------------

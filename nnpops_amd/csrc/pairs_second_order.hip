@@ -11,14 +11,14 @@
 //     d/dg_delta = w,   d/dg_r = u.w,   d/ddelta = (g_r / r) w,   d/dr = -g_r (delta.w) / r^2    (pairs_double_backward)
 // The last two are the (g_r / r)(I - u u^T) w of the Hessian once they have gone back through the forward op's own backward.
 //
-// n_k is RECOVERED from what the list stores, not replayed: D = x_i - x_j - delta_k is an integer combination of the rows of the
-// lower-triangular box, so n_z = round(D_z / B_zz), n_y = round((D_y - n_z B_zy) / B_yy), n_x = round((D_x - n_z B_zx - n_y B_yx) / B_xx)
-// -- exact whatever rounding choices (ties, reciprocal multiplies) the forward made.  Only the box terms need it.
+// n_k is RECOVERED from what the list stores, not replayed (box_grad.h: image_shift, shared with PME's direct term).  Only the box
+// terms need it.
 //
 // A slot is used when both of its atoms lie in [0, num_atoms) (-1: unused); an unused slot contributes nothing to any output.  A used
 // slot with r = 0 divides by zero, as the first-order kernels do: its NaN stays in its own outputs (and in grad_B, which sums them all).
 // No atomics: the double backward writes every output of its slot; the box gradient is a fixed-order float64 sum over fixed blocks,
 // then one workgroup over the blocks in a fixed order -- bitwise reproducible, no host synchronisation, capturable.
+#include "box_grad.h"
 #include "device_common.h"
 #include "host_common.h"
 
@@ -26,21 +26,7 @@ using namespace nnpops;
 
 namespace {
 
-constexpr int kBoxThreads = 256;
-constexpr int kBoxMaxBlocks = 1024;      // partial sums per call: a function of num_slots alone (the order of the sums is fixed)
-
-int box_blocks(long long num_slots) { return (int)std::max<long long>(1, std::min<long long>(div_up(num_slots, kBoxThreads), kBoxMaxBlocks)); }
-
 __device__ __forceinline__ bool used_slot(int i, int j, int num_atoms) { return (unsigned)i < (unsigned)num_atoms && (unsigned)j < (unsigned)num_atoms; }
-
-// n_k of the slot: box rows a = (B00, 0, 0), b = (B10, B11, 0), c = (B20, B21, B22) as the forward op uses them
-template <typename T>
-__device__ __forceinline__ void image_shift(const T* __restrict__ pos, int i, int j, T dx, T dy, T dz, const T* __restrict__ box, T (&n)[3]) {
-    const T Dx = (pos[3 * i] - pos[3 * j]) - dx, Dy = (pos[3 * i + 1] - pos[3 * j + 1]) - dy, Dz = (pos[3 * i + 2] - pos[3 * j + 2]) - dz;
-    n[2] = round(Dz / box[8]);
-    n[1] = round((Dy - n[2] * box[7]) / box[4]);
-    n[0] = round((Dx - n[2] * box[6] - n[1] * box[3]) / box[0]);
-}
 
 // one lane per slot; BOX: h_B is given (then positions and box are read for n_k)
 template <typename T, bool BOX>
@@ -81,15 +67,14 @@ __global__ __launch_bounds__(256) void pairs_double_backward(long long num_slots
     d_distances[k] = c;
 }
 
-// grad_B = - sum_k n_k (x) G_k: block b adds up slots b*256 + t, then strides of gridDim*256 (float64, a fixed xor tree over the
-// wave, the four waves in order) and writes its 9 partial sums
+// grad_B = - sum_k n_k (x) G_k: block b adds up slots b*256 + t, then strides of gridDim*256 (float64) and writes its 9 partial sums
+// (box_grad.h: box_block_sum9)
 template <typename T>
 __global__ __launch_bounds__(kBoxThreads) void pairs_box_partials(long long num_slots, int num_atoms, const int32_t* __restrict__ neighbors,
                                                                   const T* __restrict__ pos, const T* __restrict__ box,
                                                                   const T* __restrict__ deltas, const T* __restrict__ distances,
                                                                   const T* __restrict__ grad_deltas, const T* __restrict__ grad_distances,
                                                                   double* __restrict__ partials) {
-    __shared__ double red[kBoxThreads / 64][9];
     double acc[9];
 #pragma unroll
     for (int q = 0; q < 9; q++) acc[q] = 0.0;
@@ -106,50 +91,10 @@ __global__ __launch_bounds__(kBoxThreads) void pairs_box_partials(long long num_
 #pragma unroll
             for (int q = 0; q < 3; q++) acc[3 * a + q] -= (double)n[a] * (double)G[q];
     }
-#pragma unroll
-    for (int q = 0; q < 9; q++)
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) acc[q] += __shfl_xor(acc[q], off, 64);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int q = 0; q < 9; q++) red[wave][q] = acc[q];
-    }
-    __syncthreads();
-    if (threadIdx.x < 9) {
-        double s = red[0][threadIdx.x];
-        for (int w = 1; w < kBoxThreads / 64; w++) s += red[w][threadIdx.x];
-        partials[(size_t)blockIdx.x * 9 + threadIdx.x] = s;
-    }
+    box_block_sum9(acc, partials + (size_t)blockIdx.x * 9);
 }
 
-// one workgroup: lane t adds up partials t, t + 256, ... of each of the 9 sums, then the same tree as above
-template <typename T>
-__global__ __launch_bounds__(kBoxThreads) void pairs_box_finish(int nblocks, const double* __restrict__ partials, T* __restrict__ grad_box) {
-    __shared__ double red[kBoxThreads / 64][9];
-    double acc[9];
-#pragma unroll
-    for (int q = 0; q < 9; q++) acc[q] = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += kBoxThreads) {
-#pragma unroll
-        for (int q = 0; q < 9; q++) acc[q] += partials[(size_t)b * 9 + q];
-    }
-#pragma unroll
-    for (int q = 0; q < 9; q++)
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) acc[q] += __shfl_xor(acc[q], off, 64);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int q = 0; q < 9; q++) red[wave][q] = acc[q];
-    }
-    __syncthreads();
-    if (threadIdx.x < 9) {
-        double s = red[0][threadIdx.x];
-        for (int w = 1; w < kBoxThreads / 64; w++) s += red[w][threadIdx.x];
-        grad_box[threadIdx.x] = (T)s;
-    }
-}
+// (the blocks are added up by box_grad.h: pairs_box_finish)
 
 template <typename T>
 void launch_double_backward(long long num_slots, int num_atoms, const int32_t* neighbors, const void* positions, const void* box,

@@ -26,8 +26,14 @@
 // Energy: double per lane, per workgroup, partials summed in a fixed order.  Everything is bitwise reproducible -- the
 // reference scatters eight float atomics per pair (pmeCUDA.cu:62-69) -- unless an atom receives more entries than its
 // row holds (4 x the average pairs per atom + 32); such entries fall back to float atomics on a side array.
+//
+// Box gradient (nnpops_pme_direct_box): the included pairs depend on the box through delta_k = x_i - x_j - n_k B only (the excluded
+// pairs are taken un-wrapped), so with G_k = dE/ddelta_k = -dedr_k delta_k, dE/dB = - sum_k n_k (x) G_k.  pme_direct_box_partials
+// is one lane per slot, the same inclusion test and the same float expressions for dedr as the kernels above, n_k recovered as the
+// pair list's box gradient does (box_grad.h), float64 sums per block; pairs_box_finish adds the blocks up in a fixed order.
 #include <cmath>
 
+#include "box_grad.h"
 #include "device_common.h"
 #include "host_common.h"
 
@@ -336,6 +342,48 @@ __global__ __launch_bounds__(kPmeBlock) void pme_direct_gather_indexed(int num_a
     }
 }
 
+// dE/dB = - sum_k n_k (x) G_k = sum_k n_k (x) (dedr_k delta_k): block b adds up slots b*256 + t, then strides of gridDim*256 (float64)
+// and writes its 9 partial sums in the pair list's order (box_grad.h: box_block_sum9).  Any list order; -1 slots add nothing.  The
+// shift comes first: most slots of a list have n_k = 0 and add exactly nothing, so they skip the exclusion scan, the charges and the
+// erfc (a slot with n_k = 0 and r = 0 therefore leaves the sum finite).
+__global__ __launch_bounds__(kBoxThreads) void pme_direct_box_partials(long long num_pairs, int num_atoms, int max_excl,
+                                                                      const int* __restrict__ nb0, const int* __restrict__ nb1,
+                                                                      const float* __restrict__ pos, const float* __restrict__ box,
+                                                                      const float* __restrict__ deltas, const float* __restrict__ distances,
+                                                                      const float* __restrict__ charge, const int* __restrict__ excl,
+                                                                      float alpha, float coulomb, double* __restrict__ partials) {
+    double acc[9];
+#pragma unroll
+    for (int q = 0; q < 9; q++) acc[q] = 0.0;
+    for (long long i = (long long)blockIdx.x * kBoxThreads + threadIdx.x; i < num_pairs; i += (long long)gridDim.x * kBoxThreads) {
+        const int atom1 = nb0[i], atom2 = nb1[i];
+        if ((unsigned)atom1 >= (unsigned)num_atoms || (unsigned)atom2 >= (unsigned)num_atoms) continue;
+        const float dx = deltas[3 * i], dy = deltas[3 * i + 1], dz = deltas[3 * i + 2];
+        float n[3];
+        image_shift(pos, atom1, atom2, dx, dy, dz, box, n);
+        if (n[0] == 0.f && n[1] == 0.f && n[2] == 0.f) continue;
+        bool include = true;
+        for (int j = 0; j < max_excl; j++) {                   // exclusion rows are sorted in descending order (as pme_direct_pairs)
+            const int e = excl[(long long)atom1 * max_excl + j];
+            if (e < atom2) break;
+            if (e == atom2) { include = false; break; }
+        }
+        if (!include) continue;
+        const float r = distances[i];
+        const float inv_r = 1.0f / r, ar = alpha * r;
+        const float ex = expf(-ar * ar), erfc_ar = erfcf(ar);
+        const float pre = coulomb * inv_r;
+        const float c1 = charge[atom1], c2 = charge[atom2];
+        const float dedr = pre * c1 * c2 * (erfc_ar + ar * ex * kTwoOverSqrtPi) * inv_r * inv_r;
+        const float f[3] = {dedr * dx, dedr * dy, dedr * dz};          // -G_k, the direct kernels' force on the second atom
+#pragma unroll
+        for (int a = 0; a < 3; a++)
+#pragma unroll
+            for (int q = 0; q < 3; q++) acc[3 * a + q] += (double)n[a] * (double)f[q];
+    }
+    box_block_sum9(acc, partials + (size_t)blockIdx.x * 9);
+}
+
 int pair_blocks(long long num_pairs) { return (int)std::min<long long>(std::max<long long>(1, (num_pairs + kPmeBlock - 1) / kPmeBlock), 256 * 16); }
 int gather_blocks_full(int num_atoms) { return (int)std::max<long long>(1, ((long long)num_atoms * 16 + kPmeBlock - 1) / kPmeBlock); }
 int gather_blocks(int num_atoms) { return (int)std::min<long long>(std::max<long long>(1, ((long long)num_atoms * 16 + kPmeBlock - 1) / kPmeBlock), 256 * 16); }
@@ -431,6 +479,31 @@ int nnpops_pme_direct_indexed(int num_atoms, int64_t num_pairs, int max_exclusio
                        alpha, coulomb, row_seg, col_seg, order, (const float4*)terms, (const float4*)second, position_deriv, charge_deriv,
                        partial + pb);
     hipLaunchKernelGGL(pme_sum_partials, dim3(1), dim3(1024), 0, s, partial, pb + gb, energy);
+    NNPOPS_HIP_TRY(hipGetLastError());
+    return NNPOPS_OK;
+}
+
+int64_t nnpops_pme_direct_box_workspace_bytes(int64_t num_pairs) {
+    if (num_pairs < 0) return 0;
+    return (int64_t)sizeof(double) * 9 * box_blocks(num_pairs);
+}
+
+int nnpops_pme_direct_box(int num_atoms, int64_t num_pairs, int max_exclusions, const float* positions, const float* charges,
+                          const int32_t* neighbors, const float* deltas, const float* distances, const int32_t* exclusions,
+                          const float* box_vectors, float alpha, float coulomb, float* grad_box, void* workspace, void* stream) {
+    NNPOPS_REQUIRE(num_atoms > 0 && num_pairs >= 0 && max_exclusions >= 0, "bad sizes (atoms %d, pairs %lld, exclusions %d)", num_atoms,
+                   (long long)num_pairs, max_exclusions);
+    NNPOPS_REQUIRE(alpha > 0 && coulomb > 0, "alpha and coulomb must be positive");
+    NNPOPS_REQUIRE(positions && charges && box_vectors && grad_box && workspace, "NULL device pointer");
+    NNPOPS_REQUIRE(((uintptr_t)workspace & 7) == 0, "the workspace must be 8-byte aligned");
+    NNPOPS_REQUIRE(num_pairs == 0 || (neighbors && deltas && distances), "NULL pair-list pointer");
+    NNPOPS_REQUIRE(max_exclusions == 0 || exclusions, "NULL exclusions pointer");
+    hipStream_t s = (hipStream_t)stream;
+    const int nblocks = box_blocks(num_pairs);
+    hipLaunchKernelGGL(pme_direct_box_partials, dim3(nblocks), dim3(kBoxThreads), 0, s, (long long)num_pairs, num_atoms, max_exclusions,
+                       neighbors, neighbors + num_pairs, positions, box_vectors, deltas, distances, charges, exclusions, alpha, coulomb,
+                       (double*)workspace);
+    hipLaunchKernelGGL(pairs_box_finish<float>, dim3(1), dim3(kBoxThreads), 0, s, nblocks, (const double*)workspace, grad_box);
     NNPOPS_HIP_TRY(hipGetLastError());
     return NNPOPS_OK;
 }

@@ -21,6 +21,11 @@
 //                        exactly once, so the grid needs no clearing.
 //   pme_recip_convolve   one lane per complex point; energy in double per workgroup, the partials summed in a fixed order.
 //   pme_recip_interp     one lane per atom: order^3 gather with the stored weights, owner computes.
+// The box gradient: with E = 0.5 sum_k w E'_k, b = pi^2 / alpha^2, g_j = dE/dx_j,
+//     dE/dB = - B^-T (Pi + X),   Pi = 0.5 sum_k w E'_k [I - 2 (b + 1/|m|^2) m m^T],   X = sum_j x_j (x) g_j
+//   pme_recip_box_pi          after the convolution, one lane per complex point: Pi in double per workgroup from the scaled grid;
+//   pme_recip_box_atoms       one lane per atom: X in double per workgroup from the positions and the interpolated g;
+//   pme_recip_box_finish      one workgroup: both sums in a fixed order, then - B^-T (Pi + X).
 // The box is read on the device by every pass (never copied to the host): a captured graph follows new box values written in place.
 #include <cmath>
 
@@ -99,6 +104,23 @@ RecipWorkspace carve(void* workspace, int num_atoms, int gx, int gy, int gz, int
     w.base = (int4*)take(sizeof(int4) * n);
     w.theta = (float*)take(sizeof(float) * 3 * (size_t)order * n);
     w.dtheta = (float*)take(sizeof(float) * 3 * (size_t)order * n);
+    w.bytes = (size_t)(p - (uintptr_t)workspace) + 256;
+    return w;
+}
+
+// ---- the box gradient's own workspace (the one above keeps its size): Pi from the convolution, X from the atoms ----
+struct BoxWorkspace {
+    double* pi_partial;   // [conv_blocks][6]
+    double* x_partial;    // [ceil(N / kBlock)][9]
+    size_t bytes;
+};
+
+BoxWorkspace box_carve(void* workspace, int num_atoms, int gx, int gy, int gz) {
+    BoxWorkspace w{};
+    uintptr_t p = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
+    auto take = [&](size_t bytes) { const uintptr_t at = p; p += (bytes + 255) & ~(size_t)255; return at; };
+    w.pi_partial = (double*)take(sizeof(double) * 6 * conv_blocks(gx, gy, gz));
+    w.x_partial = (double*)take(sizeof(double) * 9 * (size_t)std::max(1, div_up(num_atoms, kBlock)));
     w.bytes = (size_t)(p - (uintptr_t)workspace) + 256;
     return w;
 }
@@ -369,6 +391,140 @@ __global__ __launch_bounds__(kBlock) void pme_recip_convolve(int gx, int gy, int
     }
 }
 
+// ---- box gradient: Pi = 0.5 sum_{k != 0} w E'_k [I - 2 (b + 1/|m|^2) m m^T] (E'_k = eterm |S|^2, b = pi^2 / alpha^2) ----
+// A pass of its own over the grid pme_recip_convolve has scaled (g' = eterm S, so w E'_k = w |g'|^2 / eterm), leaving that kernel and
+// its bits exactly as they are: a variant that also formed Pi from the same float values was compiled with other contractions of |m|^2
+// (the extra uses change how the vectoriser packs them), so its eterm, and the grid, could differ in the last bit.  Per workgroup, in
+// double, into pi_partial [gridDim][6] (xx, yy, zz, xy, xz, yz; without the 1/2).  Points whose eterm underflows add nothing.
+__global__ __launch_bounds__(kBlock) void pme_recip_box_pi(int gx, int gy, int gz, const float* __restrict__ box, float recip_exp_factor,
+                                                          const float* __restrict__ xmod, const float* __restrict__ ymod,
+                                                          const float* __restrict__ zmod, const float2* __restrict__ cgrid,
+                                                          double* __restrict__ pi_partial) {
+    __shared__ double red[kBlock / 64][6];
+    float b[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) b[i] = box[i];
+    const RecipBox r = recip_box(b);
+    const float scale_factor = (float)M_PI * b[0] * b[4] * b[8];
+    const int zsize = gz / 2 + 1;
+    const long long points = (long long)gx * gy * zsize;
+    double pi[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (long long idx = (long long)blockIdx.x * kBlock + threadIdx.x; idx < points; idx += (long long)gridDim.x * kBlock) {
+        if (idx == 0) continue;
+        const int kx = (int)(idx / ((long long)gy * zsize));
+        const int rem = (int)(idx - (long long)kx * gy * zsize);
+        const int ky = rem / zsize, kz = rem - ky * zsize;
+        const int mx = kx < (gx + 1) / 2 ? kx : kx - gx;
+        const int my = ky < (gy + 1) / 2 ? ky : ky - gy;
+        const int mz = kz < (gz + 1) / 2 ? kz : kz - gz;
+        const float mhx = mx * r.r00;
+        const float mhy = mx * r.r10 + my * r.r11;
+        const float mhz = mx * r.r20 + my * r.r21 + mz * r.r22;
+        const float m2 = mhx * mhx + mhy * mhy + mhz * mhz;
+        const float denom = m2 * (scale_factor * xmod[kx]) * ymod[ky] * zmod[kz];
+        const float eterm = expf(-recip_exp_factor * m2) / denom;
+        if (!(eterm > 0.f)) continue;
+        const float w = (kz > 0 && kz <= (gz - 1) / 2) ? 2.f : 1.f;
+        const float2 g = cgrid[idx];
+        const double t = (double)w * ((double)g.x * g.x + (double)g.y * g.y) / (double)eterm;
+        const double c = 2.0 * ((double)recip_exp_factor + 1.0 / (double)m2);
+        const double hx = mhx, hy = mhy, hz = mhz;
+        pi[0] += t * (1.0 - c * hx * hx); pi[1] += t * (1.0 - c * hy * hy); pi[2] += t * (1.0 - c * hz * hz);
+        pi[3] -= t * c * hx * hy;         pi[4] -= t * c * hx * hz;         pi[5] -= t * c * hy * hz;
+    }
+#pragma unroll
+    for (int q = 0; q < 6; q++)
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) pi[q] += __shfl_xor(pi[q], off, 64);
+    if (lane_id() == 0) {
+#pragma unroll
+        for (int q = 0; q < 6; q++) red[threadIdx.x >> 6][q] = pi[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        double s = red[0][threadIdx.x];
+        for (int w = 1; w < kBlock / 64; w++) s += red[w][threadIdx.x];
+        pi_partial[(size_t)blockIdx.x * 6 + threadIdx.x] = s;
+    }
+}
+
+// ---- box gradient: X = sum_j x_j (x) g_j from the positions and the interpolated dE/dpositions, float64 per workgroup ----
+__global__ __launch_bounds__(kBlock) void pme_recip_box_atoms(int num_atoms, const float* __restrict__ pos, const float* __restrict__ pos_deriv,
+                                                             double* __restrict__ x_partial) {
+    __shared__ double red[kBlock / 64][9];
+    double acc[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const int atom = blockIdx.x * kBlock + threadIdx.x;
+    if (atom < num_atoms) {
+#pragma unroll
+        for (int a = 0; a < 3; a++)
+#pragma unroll
+            for (int b = 0; b < 3; b++) acc[3 * a + b] = (double)pos[3 * atom + a] * (double)pos_deriv[3 * atom + b];
+    }
+#pragma unroll
+    for (int q = 0; q < 9; q++)
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) acc[q] += __shfl_xor(acc[q], off, 64);
+    if (lane_id() == 0) {
+#pragma unroll
+        for (int q = 0; q < 9; q++) red[threadIdx.x >> 6][q] = acc[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < 9) {
+        double s = red[0][threadIdx.x];
+        for (int w = 1; w < kBlock / 64; w++) s += red[w][threadIdx.x];
+        x_partial[(size_t)blockIdx.x * 9 + threadIdx.x] = s;
+    }
+}
+
+// one workgroup: Pi (1/2 x the convolution's partials) and X (the atom partials), each added up in a fixed order, then
+// dE/dB = - B^-T (Pi + X) with B^-1 the general 3 x 3 inverse of the box in double (for the reduced box the kernels take it equals
+// the lower-triangular one of recip_box)
+__global__ __launch_bounds__(kBlock) void pme_recip_box_finish(int pi_blocks, const double* __restrict__ pi_partial, int x_blocks,
+                                                              const double* __restrict__ x_partial, const float* __restrict__ box,
+                                                              float* __restrict__ grad_box) {
+    __shared__ double red[kBlock / 64][15];
+    double acc[15];
+#pragma unroll
+    for (int q = 0; q < 15; q++) acc[q] = 0.0;
+    for (int b = threadIdx.x; b < pi_blocks; b += kBlock) {
+#pragma unroll
+        for (int q = 0; q < 6; q++) acc[q] += pi_partial[(size_t)b * 6 + q];
+    }
+    for (int b = threadIdx.x; b < x_blocks; b += kBlock) {
+#pragma unroll
+        for (int q = 0; q < 9; q++) acc[6 + q] += x_partial[(size_t)b * 9 + q];
+    }
+#pragma unroll
+    for (int q = 0; q < 15; q++)
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) acc[q] += __shfl_xor(acc[q], off, 64);
+    if (lane_id() == 0) {
+#pragma unroll
+        for (int q = 0; q < 15; q++) red[threadIdx.x >> 6][q] = acc[q];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s[15];
+        for (int q = 0; q < 15; q++) {
+            s[q] = red[0][q];
+            for (int w = 1; w < kBlock / 64; w++) s[q] += red[w][q];
+        }
+        const double pxx = 0.5 * s[0], pyy = 0.5 * s[1], pzz = 0.5 * s[2], pxy = 0.5 * s[3], pxz = 0.5 * s[4], pyz = 0.5 * s[5];
+        const double M[9] = {pxx + s[6], pxy + s[7], pxz + s[8], pxy + s[9], pyy + s[10], pyz + s[11], pxz + s[12], pyz + s[13], pzz + s[14]};
+        double B[9];
+        for (int q = 0; q < 9; q++) B[q] = (double)box[q];
+        // B^-1 = adj(B) / det(B)
+        const double c00 = B[4] * B[8] - B[5] * B[7], c01 = B[5] * B[6] - B[3] * B[8], c02 = B[3] * B[7] - B[4] * B[6];
+        const double det = B[0] * c00 + B[1] * c01 + B[2] * c02;
+        const double inv[9] = {c00 / det, (B[2] * B[7] - B[1] * B[8]) / det, (B[1] * B[5] - B[2] * B[4]) / det,
+                               c01 / det, (B[0] * B[8] - B[2] * B[6]) / det, (B[2] * B[3] - B[0] * B[5]) / det,
+                               c02 / det, (B[1] * B[6] - B[0] * B[7]) / det, (B[0] * B[4] - B[1] * B[3]) / det};
+        for (int a = 0; a < 3; a++)
+            for (int b = 0; b < 3; b++)       // (B^-T M)[a][b] = sum_c B^-1[c][a] M[c][b]
+                grad_box[3 * a + b] = (float)-(inv[a] * M[b] + inv[3 + a] * M[3 + b] + inv[6 + a] * M[6 + b]);
+    }
+}
+
 // workgroup partials -> 0.5 x their sum, always in the same order
 __global__ __launch_bounds__(kConvBlocksMax) void pme_recip_energy(const double* __restrict__ partial, int count, float* __restrict__ energy) {
     __shared__ double red[kConvBlocksMax];
@@ -495,6 +651,48 @@ int nnpops_pme_reciprocal_convolve(int num_atoms, int gridx, int gridy, int grid
     hipLaunchKernelGGL(pme_recip_convolve, dim3(cb), dim3(kBlock), 0, s, gridx, gridy, gridz, box_vectors, recip_exp_factor, xmoduli,
                        ymoduli, zmoduli, (float2*)recip_grid, w.partial);
     hipLaunchKernelGGL(pme_recip_energy, dim3(1), dim3(kConvBlocksMax), 0, s, (const double*)w.partial, cb, energy);
+    NNPOPS_HIP_TRY(hipGetLastError());
+    return NNPOPS_OK;
+}
+
+int64_t nnpops_pme_reciprocal_box_workspace_bytes(int num_atoms, int gridx, int gridy, int gridz, int order) {
+    if (check_common(num_atoms, gridx, gridy, gridz, order) != NNPOPS_OK) return 0;
+    return (int64_t)box_carve(nullptr, num_atoms, gridx, gridy, gridz).bytes;
+}
+
+int nnpops_pme_reciprocal_convolve_box(int num_atoms, int gridx, int gridy, int gridz, int order, const float* box_vectors, float alpha,
+                                       const float* xmoduli, const float* ymoduli, const float* zmoduli, void* recip_grid, float* energy,
+                                       void* workspace, void* box_workspace, void* stream) {
+    if (int rc = check_common(num_atoms, gridx, gridy, gridz, order)) return rc;
+    NNPOPS_REQUIRE(alpha > 0, "alpha must be positive");
+    NNPOPS_REQUIRE(box_vectors && xmoduli && ymoduli && zmoduli && recip_grid && energy && workspace && box_workspace, "NULL device pointer");
+    hipStream_t s = (hipStream_t)stream;
+    const RecipWorkspace w = carve(workspace, num_atoms, gridx, gridy, gridz, order);
+    const BoxWorkspace bw = box_carve(box_workspace, num_atoms, gridx, gridy, gridz);
+    const int cb = conv_blocks(gridx, gridy, gridz);
+    const float recip_exp_factor = (float)(M_PI * M_PI / ((double)alpha * (double)alpha));
+    hipLaunchKernelGGL(pme_recip_convolve, dim3(cb), dim3(kBlock), 0, s, gridx, gridy, gridz, box_vectors, recip_exp_factor, xmoduli,
+                       ymoduli, zmoduli, (float2*)recip_grid, w.partial);
+    hipLaunchKernelGGL(pme_recip_energy, dim3(1), dim3(kConvBlocksMax), 0, s, (const double*)w.partial, cb, energy);
+    hipLaunchKernelGGL(pme_recip_box_pi, dim3(cb), dim3(kBlock), 0, s, gridx, gridy, gridz, box_vectors, recip_exp_factor, xmoduli, ymoduli,
+                       zmoduli, (const float2*)recip_grid, bw.pi_partial);
+    NNPOPS_HIP_TRY(hipGetLastError());
+    return NNPOPS_OK;
+}
+
+int nnpops_pme_reciprocal_box_gradient(int num_atoms, int gridx, int gridy, int gridz, int order, const float* positions,
+                                       const float* box_vectors, const float* position_deriv, float* grad_box, void* box_workspace,
+                                       void* stream) {
+    if (int rc = check_common(num_atoms, gridx, gridy, gridz, order)) return rc;
+    NNPOPS_REQUIRE(box_vectors && grad_box && box_workspace, "NULL device pointer");
+    NNPOPS_REQUIRE(num_atoms == 0 || (positions && position_deriv), "NULL positions / derivative pointer");
+    hipStream_t s = (hipStream_t)stream;
+    const BoxWorkspace bw = box_carve(box_workspace, num_atoms, gridx, gridy, gridz);
+    const int ab = div_up(num_atoms, kBlock);
+    if (num_atoms > 0)
+        hipLaunchKernelGGL(pme_recip_box_atoms, dim3(ab), dim3(kBlock), 0, s, num_atoms, positions, position_deriv, bw.x_partial);
+    hipLaunchKernelGGL(pme_recip_box_finish, dim3(1), dim3(kBlock), 0, s, conv_blocks(gridx, gridy, gridz), (const double*)bw.pi_partial, ab,
+                       (const double*)bw.x_partial, box_vectors, grad_box);
     NNPOPS_HIP_TRY(hipGetLastError());
     return NNPOPS_OK;
 }

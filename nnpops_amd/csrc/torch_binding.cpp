@@ -1400,11 +1400,17 @@ TORCH_LIBRARY_IMPL(neighbors, CPU, m) { m.impl("getNeighborPairs", neighbor_pair
 // name and schema; the energy's autograd backward scales the derivatives computed in the forward pass, exactly as the
 // reference does.  The reciprocal-space op (pme_reciprocal) follows it below.
 // =============================================================================================
+// the energy and its derivatives, and the inputs as the kernels read them
+struct PmeDirectForward {
+    Tensor energy, pos_deriv, charge_deriv;
+    Tensor pos, q, nb, dl, ds, ex;
+};
+
 class PmeDirectFunction : public torch::autograd::Function<PmeDirectFunction> {
 public:
-    static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& neighbors,
-                          const Tensor& deltas, const Tensor& distances, const Tensor& exclusions, const torch::Scalar& alpha,
-                          const torch::Scalar& coulomb) {
+    // the forward pass on either key, shared with pme_direct_box
+    static PmeDirectForward run(const Tensor& positions, const Tensor& charges, const Tensor& neighbors, const Tensor& deltas,
+                                const Tensor& distances, const Tensor& exclusions, const torch::Scalar& alpha, const torch::Scalar& coulomb) {
         TORCH_CHECK(positions.dim() == 2 && positions.size(1) == 3, "positions must have shape (atoms, 3)");
         TORCH_CHECK(charges.dim() == 1 && charges.size(0) == positions.size(0), "charges must be 1D, one per atom");
         TORCH_CHECK(neighbors.dim() == 2 && neighbors.size(0) == 2, "neighbors must have shape (2, pairs)");
@@ -1484,8 +1490,15 @@ public:
                 }
             energy.fill_((float)e);
         }
-        ctx->save_for_backward({pos_deriv, charge_deriv});
-        return energy;
+        return {energy, pos_deriv, charge_deriv, pos, q, nb, dl, ds, ex};
+    }
+
+    static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& neighbors,
+                          const Tensor& deltas, const Tensor& distances, const Tensor& exclusions, const torch::Scalar& alpha,
+                          const torch::Scalar& coulomb) {
+        const PmeDirectForward f = run(positions, charges, neighbors, deltas, distances, exclusions, alpha, coulomb);
+        ctx->save_for_backward({f.pos_deriv, f.charge_deriv});
+        return f.energy;
     }
 
     static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) {
@@ -1495,6 +1508,76 @@ public:
                     "pme_direct: second derivatives are not implemented (backward was called with create_graph=True)");
         const auto saved = ctx->get_saved_variables();
         return {saved[0] * grad_outputs[0], saved[1] * grad_outputs[0], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+    }
+};
+
+// pme_direct_box: pme_direct's forward (same kernels, same bits, the indexed path included) and, when box_vectors needs a gradient,
+// dE/dB = - sum_k n_k (x) G_k over the included pairs (nnpops_pme_direct_box / the host loop below), computed in the forward pass
+// like the other derivatives.  No gradient flows into deltas or distances, as with pme_direct: a list whose deltas depend on the box
+// is not counted twice.
+class PmeDirectBoxFunction : public torch::autograd::Function<PmeDirectBoxFunction> {
+public:
+    static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& neighbors,
+                          const Tensor& deltas, const Tensor& distances, const Tensor& exclusions, const Tensor& box_vectors,
+                          const torch::Scalar& alpha, const torch::Scalar& coulomb, bool box_grad) {
+        TORCH_CHECK(box_vectors.dim() == 2 && box_vectors.size(0) == 3 && box_vectors.size(1) == 3, "box_vectors must have shape (3, 3)");
+        TORCH_CHECK(box_vectors.scalar_type() == torch::kFloat32, "pme_direct_box computes in float32");
+        TORCH_CHECK(box_vectors.device() == positions.device(), "pme_direct_box: every tensor must be on the device of positions (",
+                    positions.device(), "), got ", box_vectors.device());
+        const PmeDirectForward f = PmeDirectFunction::run(positions, charges, neighbors, deltas, distances, exclusions, alpha, coulomb);
+        Tensor grad_box;
+        if (box_grad) {
+            const Tensor box = box_vectors.contiguous();
+            const int64_t n = f.pos.size(0), pairs = f.nb.size(1), max_excl = f.ex.size(1);
+            const float a = (float)alpha.toDouble(), k = (float)coulomb.toDouble();
+            grad_box = torch::empty({3, 3}, f.pos.options());
+            if (positions.is_cuda()) {
+                c10::hip::HIPGuard guard(positions.device().index());
+                Tensor workspace = torch::empty({nnpops_pme_direct_box_workspace_bytes(pairs) / 8}, f.pos.options().dtype(torch::kFloat64));
+                if (nnpops_pme_direct_box((int)n, pairs, (int)max_excl, f.pos.data_ptr<float>(), f.q.data_ptr<float>(), f.nb.data_ptr<int32_t>(),
+                                          f.dl.data_ptr<float>(), f.ds.data_ptr<float>(), max_excl ? f.ex.data_ptr<int32_t>() : nullptr,
+                                          box.data_ptr<float>(), a, k, grad_box.data_ptr<float>(), workspace.data_ptr(),
+                                          current_stream(positions.device())) != NNPOPS_OK)
+                    raise_last("pme::pme_direct_box");
+            } else {
+                // the same inclusion test, dedr and shift recovery as the device pass; double sums
+                const float* P = f.pos.data_ptr<float>(); const float* Q = f.q.data_ptr<float>(); const float* B = box.data_ptr<float>();
+                const int32_t* N0 = f.nb.data_ptr<int32_t>(); const int32_t* N1 = N0 + pairs; const int32_t* E = f.ex.data_ptr<int32_t>();
+                const float* DL = f.dl.data_ptr<float>(); const float* DS = f.ds.data_ptr<float>();
+                const float two_over_sqrt_pi = 1.12837916709551257390f;
+                double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+                for (int64_t i = 0; i < pairs; i++) {
+                    const int a1 = N0[i], a2 = N1[i];
+                    if (a1 < 0) continue;
+                    float D[3], sh[3];
+                    for (int c = 0; c < 3; c++) D[c] = (P[3 * a1 + c] - P[3 * a2 + c]) - DL[3 * i + c];
+                    sh[2] = std::round(D[2] / B[8]);
+                    sh[1] = std::round((D[1] - sh[2] * B[7]) / B[4]);
+                    sh[0] = std::round((D[0] - sh[2] * B[6] - sh[1] * B[3]) / B[0]);
+                    if (sh[0] == 0 && sh[1] == 0 && sh[2] == 0) continue;         // (adds exactly nothing)
+                    bool include = true;
+                    for (int64_t j = 0; include && j < max_excl && E[a1 * max_excl + j] >= a2; j++)
+                        if (E[a1 * max_excl + j] == a2) include = false;
+                    if (!include) continue;
+                    const float r = DS[i], inv_r = 1 / r, ar = a * r, pre = k * inv_r, er = std::erfc(ar);
+                    const float dedr = pre * Q[a1] * Q[a2] * (er + ar * std::exp(-ar * ar) * two_over_sqrt_pi) * inv_r * inv_r;
+                    for (int c = 0; c < 3; c++)
+                        for (int d = 0; d < 3; d++) acc[3 * c + d] += (double)sh[c] * (double)(dedr * DL[3 * i + d]);
+                }
+                float* GB = grad_box.data_ptr<float>();
+                for (int c = 0; c < 9; c++) GB[c] = (float)acc[c];
+            }
+        }
+        ctx->save_for_backward({f.pos_deriv, f.charge_deriv, grad_box});
+        return f.energy;
+    }
+
+    static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) {
+        TORCH_CHECK(!torch::GradMode::is_enabled(),
+                    "pme_direct_box: second derivatives are not implemented (backward was called with create_graph=True)");
+        const auto saved = ctx->get_saved_variables();
+        return {saved[0] * grad_outputs[0], saved[1] * grad_outputs[0], Tensor(), Tensor(), Tensor(), Tensor(),
+                saved[2].defined() ? saved[2] * grad_outputs[0] : Tensor(), Tensor(), Tensor(), Tensor()};
     }
 };
 
@@ -1553,6 +1636,26 @@ void spline(const float* p_in, const float* b, const Recip& r, const int K[3], i
     }
 }
 
+// dE/dB = - B^-T (Pi + X): pi = the six sums of the convolution loop (without their 1/2), X = sum_j x_j (x) g_j; as
+// pme_recip_box_finish, in double with the general 3 x 3 inverse
+void box_gradient(int64_t n, const float* pos, const float* pos_deriv, const double* pi, const float* box, float* grad_box) {
+    double X[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int64_t j = 0; j < n; j++)
+        for (int a = 0; a < 3; a++)
+            for (int b = 0; b < 3; b++) X[3 * a + b] += (double)pos[3 * j + a] * (double)pos_deriv[3 * j + b];
+    const double M[9] = {0.5 * pi[0] + X[0], 0.5 * pi[3] + X[1], 0.5 * pi[4] + X[2], 0.5 * pi[3] + X[3], 0.5 * pi[1] + X[4],
+                         0.5 * pi[5] + X[5], 0.5 * pi[4] + X[6], 0.5 * pi[5] + X[7], 0.5 * pi[2] + X[8]};
+    double B[9];
+    for (int c = 0; c < 9; c++) B[c] = box[c];
+    const double c00 = B[4] * B[8] - B[5] * B[7], c01 = B[5] * B[6] - B[3] * B[8], c02 = B[3] * B[7] - B[4] * B[6];
+    const double det = B[0] * c00 + B[1] * c01 + B[2] * c02;
+    const double inv[9] = {c00 / det, (B[2] * B[7] - B[1] * B[8]) / det, (B[1] * B[5] - B[2] * B[4]) / det,
+                           c01 / det, (B[0] * B[8] - B[2] * B[6]) / det, (B[2] * B[3] - B[0] * B[5]) / det,
+                           c02 / det, (B[1] * B[6] - B[0] * B[7]) / det, (B[0] * B[4] - B[1] * B[3]) / det};
+    for (int a = 0; a < 3; a++)
+        for (int b = 0; b < 3; b++) grad_box[3 * a + b] = (float)-(inv[a] * M[b] + inv[3 + a] * M[3 + b] + inv[6 + a] * M[6 + b]);
+}
+
 }  // namespace pme_recip_host
 
 class PmeReciprocalFunction : public torch::autograd::Function<PmeReciprocalFunction> {
@@ -1560,7 +1663,7 @@ public:
     static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& box_vectors,
                           const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz, const torch::Scalar& order,
                           const torch::Scalar& alpha, const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli,
-                          const Tensor& zmoduli) {
+                          const Tensor& zmoduli, bool box_grad) {
         TORCH_CHECK(positions.dim() == 2 && positions.size(1) == 3, "positions must have shape (atoms, 3)");
         TORCH_CHECK(charges.dim() == 1 && charges.size(0) == positions.size(0), "charges must be 1D, one per atom");
         TORCH_CHECK(box_vectors.dim() == 2 && box_vectors.size(0) == 3 && box_vectors.size(1) == 3, "box_vectors must have shape (3, 3)");
@@ -1584,7 +1687,8 @@ public:
         const Tensor xm = xmoduli.contiguous(), ym = ymoduli.contiguous(), zm = zmoduli.contiguous();
         const int64_t n = positions.size(0);
         const auto opts = positions.options();
-        Tensor energy, recip, workspace;
+        // box_grad: the box gradient -B^-T (Pi + X) (pme_recip.hip): Pi is summed here, X in the backward from the position derivatives
+        Tensor energy, recip, workspace, pi;
         if (positions.is_cuda()) {
             TORCH_CHECK(pme_order == 4 || pme_order == 5, "pme_reciprocal: Only pmeOrder 4 or 5 is supported on the device (got ", pme_order, ")");
             c10::hip::HIPGuard guard(positions.device().index());
@@ -1597,7 +1701,13 @@ public:
                 raise_last("pme::pme_reciprocal");
             recip = torch::fft::rfftn(real).contiguous();
             energy = torch::empty({}, opts);
-            if (nnpops_pme_reciprocal_convolve((int)n, gx, gy, gz, o, box.data_ptr<float>(), (float)a, xm.data_ptr<float>(), ym.data_ptr<float>(),
+            if (box_grad) {
+                pi = torch::empty({nnpops_pme_reciprocal_box_workspace_bytes((int)n, gx, gy, gz, o)}, opts.dtype(torch::kUInt8));
+                if (nnpops_pme_reciprocal_convolve_box((int)n, gx, gy, gz, o, box.data_ptr<float>(), (float)a, xm.data_ptr<float>(),
+                                                       ym.data_ptr<float>(), zm.data_ptr<float>(), recip.data_ptr(), energy.data_ptr<float>(),
+                                                       workspace.data_ptr(), pi.data_ptr(), stream) != NNPOPS_OK)
+                    raise_last("pme::pme_reciprocal");
+            } else if (nnpops_pme_reciprocal_convolve((int)n, gx, gy, gz, o, box.data_ptr<float>(), (float)a, xm.data_ptr<float>(), ym.data_ptr<float>(),
                                                zm.data_ptr<float>(), recip.data_ptr(), energy.data_ptr<float>(), workspace.data_ptr(),
                                                stream) != NNPOPS_OK)
                 raise_last("pme::pme_reciprocal");
@@ -1631,7 +1741,7 @@ public:
             const float scale_factor = (float)(M_PI * B[0] * B[4] * B[8]);
             const float exp_factor = (float)(M_PI * M_PI / (a * a));
             const float* XM = xm.data_ptr<float>(); const float* YM = ym.data_ptr<float>(); const float* ZM = zm.data_ptr<float>();
-            double e = 0.0;
+            double e = 0.0, PS[6] = {0, 0, 0, 0, 0, 0};    // (Pi without its 1/2: xx, yy, zz, xy, xz, yz)
             for (int64_t kx = 0; kx < K[0]; kx++) {
                 const int64_t mx = kx < (K[0] + 1) / 2 ? kx : kx - K[0];
                 for (int64_t ky = 0; ky < K[1]; ky++) {
@@ -1645,16 +1755,27 @@ public:
                         const float denom = m2 * (scale_factor * XM[kx]) * YM[ky] * ZM[kz];
                         const float eterm = idx == 0 ? 0.f : std::exp(-exp_factor * m2) / denom;
                         const float w = (kz > 0 && kz <= (K[2] - 1) / 2) ? 2.f : 1.f;
-                        e += w * eterm * std::norm(C[idx]);
+                        const float term = w * eterm * std::norm(C[idx]);
+                        e += term;
+                        if (box_grad && idx != 0) {
+                            const double t = term, c = 2.0 * ((double)exp_factor + 1.0 / (double)m2);
+                            const double hx = mhx, hy = mhy, hz = mhz;
+                            PS[0] += t * (1.0 - c * hx * hx); PS[1] += t * (1.0 - c * hy * hy); PS[2] += t * (1.0 - c * hz * hz);
+                            PS[3] -= t * c * hx * hy;         PS[4] -= t * c * hx * hz;         PS[5] -= t * c * hy * hz;
+                        }
                         C[idx] *= eterm;
                     }
                 }
             }
             energy = torch::full({}, (float)(0.5 * e), opts);
+            if (box_grad) pi = torch::tensor(std::vector<double>(PS, PS + 6), opts.dtype(torch::kFloat64));
         }
-        // (the device path keeps the splines in the workspace and does not need the positions again)
+        // (the device path keeps the splines in the workspace and does not need the positions again, unless for the box gradient)
         const Tensor none = torch::empty({0}, opts);
-        ctx->save_for_backward({q, box, recip, workspace.defined() ? workspace : none, positions.is_cuda() ? none : pos});
+        if (box_grad)
+            ctx->save_for_backward({q, box, recip, workspace.defined() ? workspace : none, pos, pi});
+        else
+            ctx->save_for_backward({q, box, recip, workspace.defined() ? workspace : none, positions.is_cuda() ? none : pos});
         ctx->saved_data["grid"] = std::vector<int64_t>{K[0], K[1], K[2]};
         ctx->saved_data["order"] = pme_order;
         ctx->saved_data["coulomb"] = k;
@@ -1714,8 +1835,24 @@ public:
                 CD[atom] = dq * sqrt_k;
             }
         }
-        return {pos_deriv * grad_outputs[0], charge_deriv * grad_outputs[0], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(),
-                Tensor(), Tensor(), Tensor(), Tensor()};
+        Tensor grad_box;
+        if (saved.size() > 5) {
+            const Tensor pi = saved[5];
+            grad_box = torch::empty({3, 3}, opts);
+            if (q.is_cuda()) {
+                c10::hip::HIPGuard guard(q.device().index());
+                if (nnpops_pme_reciprocal_box_gradient((int)n, (int)K[0], (int)K[1], (int)K[2], (int)pme_order, pos.data_ptr<float>(),
+                                                       box.data_ptr<float>(), pos_deriv.data_ptr<float>(), grad_box.data_ptr<float>(),
+                                                       pi.data_ptr(), current_stream(q.device())) != NNPOPS_OK)
+                    raise_last("pme::pme_reciprocal");
+            } else {
+                pme_recip_host::box_gradient(n, pos.data_ptr<float>(), pos_deriv.data_ptr<float>(), pi.data_ptr<double>(),
+                                             box.data_ptr<float>(), grad_box.data_ptr<float>());
+            }
+            grad_box = grad_box * grad_outputs[0];
+        }
+        return {pos_deriv * grad_outputs[0], charge_deriv * grad_outputs[0], grad_box, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(),
+                Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
     }
 };
 
@@ -1724,13 +1861,24 @@ TORCH_LIBRARY(pme, m) {
           "Scalar alpha, Scalar coulomb) -> Tensor");
     m.def("pme_reciprocal(Tensor positions, Tensor charges, Tensor box_vectors, Scalar gridx, Scalar gridy, Scalar gridz, "
           "Scalar order, Scalar alpha, Scalar coulomb, Tensor xmoduli, Tensor ymoduli, Tensor zmoduli) -> Tensor");
+    m.def("pme_direct_box(Tensor positions, Tensor charges, Tensor neighbors, Tensor deltas, Tensor distances, Tensor exclusions, "
+          "Tensor box_vectors, Scalar alpha, Scalar coulomb) -> Tensor");
+}
+
+Tensor pme_direct_box_entry(const Tensor& positions, const Tensor& charges, const Tensor& neighbors, const Tensor& deltas,
+                            const Tensor& distances, const Tensor& exclusions, const Tensor& box_vectors, const torch::Scalar& alpha,
+                            const torch::Scalar& coulomb) {
+    const bool box_grad = torch::GradMode::is_enabled() && box_vectors.requires_grad();
+    return PmeDirectBoxFunction::apply(positions, charges, neighbors, deltas, distances, exclusions, box_vectors, alpha, coulomb, box_grad);
 }
 
 Tensor pme_reciprocal_entry(const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const torch::Scalar& gridx,
                             const torch::Scalar& gridy, const torch::Scalar& gridz, const torch::Scalar& order, const torch::Scalar& alpha,
                             const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli, const Tensor& zmoduli) {
+    // (decided here: inside forward() grad mode is off, and nothing is recorded under inference mode or no_grad)
+    const bool box_grad = torch::GradMode::is_enabled() && box_vectors.requires_grad();
     return PmeReciprocalFunction::apply(positions, charges, box_vectors, gridx, gridy, gridz, order, alpha, coulomb, xmoduli, ymoduli,
-                                        zmoduli);
+                                        zmoduli, box_grad);
 }
 
 Tensor pme_direct_entry(const Tensor& positions, const Tensor& charges, const Tensor& neighbors, const Tensor& deltas,
@@ -1741,20 +1889,24 @@ Tensor pme_direct_entry(const Tensor& positions, const Tensor& charges, const Te
 TORCH_LIBRARY_IMPL(pme, AutogradCUDA, m) {
     m.impl("pme_direct", pme_direct_entry);
     m.impl("pme_reciprocal", pme_reciprocal_entry);
+    m.impl("pme_direct_box", pme_direct_box_entry);
 }
 TORCH_LIBRARY_IMPL(pme, AutogradCPU, m) {
     m.impl("pme_direct", pme_direct_entry);
     m.impl("pme_reciprocal", pme_reciprocal_entry);
+    m.impl("pme_direct_box", pme_direct_box_entry);
 }
 // ... and the backend keys themselves (the reference registers its autograd Function under CPU, pmeCPU.cpp:381): below
 // autograd -- torch.inference_mode(), AutoDispatchBelowAutograd -- the same entry runs without recording a graph
 TORCH_LIBRARY_IMPL(pme, CUDA, m) {
     m.impl("pme_direct", pme_direct_entry);
     m.impl("pme_reciprocal", pme_reciprocal_entry);
+    m.impl("pme_direct_box", pme_direct_box_entry);
 }
 TORCH_LIBRARY_IMPL(pme, CPU, m) {
     m.impl("pme_direct", pme_direct_entry);
     m.impl("pme_reciprocal", pme_reciprocal_entry);
+    m.impl("pme_direct_box", pme_direct_box_entry);
 }
 
 // =============================================================================================

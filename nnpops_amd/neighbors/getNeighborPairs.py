@@ -29,7 +29,8 @@ def getNeighborPairs(positions: Tensor, cutoff: float, max_num_pairs: int = -1, 
     loss can be differentiated through (force matching), Hessian-vector products, and dE/dbox (the virial)
     with its derivatives.  The gradient of ``box_vectors`` has their dtype and covers all nine entries, as the
     reference's composition differentiates whole rows.  Third derivatives raise a RuntimeError.
-    ``pme_direct`` does not pass gradients into ``deltas``, so box gradients through PME remain unavailable.
+    ``pme_direct`` does not pass gradients into ``deltas``; PME's box gradient comes from ``pme_direct_box`` and
+    ``pme_reciprocal`` themselves (``PME.compute_direct`` picks the former when the box requires a gradient).
     """
     if box_vectors is None:
         box_vectors = empty((0, 0), device=positions.device, dtype=positions.dtype)

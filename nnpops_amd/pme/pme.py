@@ -4,7 +4,9 @@ Mirrors the reference class (src/pytorch/pme/pme.py:5-165): same constructor arg
 ``compute_direct(positions, charges, cutoff, box_vectors, max_num_pairs)`` contract, same unit convention (the value of
 Coulomb's constant sets the units), same exclusion semantics (only the un-wrapped copy of an excluded pair is left out, and
 the erf() part that reciprocal space cannot leave out is subtracted here).  ``compute_direct`` = getNeighborPairs +
-``torch.ops.pme.pme_direct``, differentiable w.r.t. positions and charges (first derivatives only).
+``torch.ops.pme.pme_direct``, differentiable w.r.t. positions and charges (first derivatives only).  When ``box_vectors``
+requires a gradient (and grad mode is on) it calls ``torch.ops.pme.pme_direct_box`` instead: the same forward pass, bit for
+bit, and dE/dbox as well.
 
 The reciprocal-space term (charge spreading onto a grid + 3-D FFTs, src/pytorch/pme/pmeCUDA.cu:102-430) is
 ``torch.ops.pme.pme_reciprocal``: deterministic HIP passes around torch's FFTs (nnpops_amd/csrc/pme_recip.hip) and a CPU key.
@@ -48,6 +50,10 @@ class PME:
     """Particle Mesh Ewald (the reference's class, src/pytorch/pme/pme.py).  The direct- and reciprocal-space terms are not
     physically meaningful on their own, only their sum.
 
+    Both terms are differentiable with respect to positions, charges and box vectors (first derivatives only; the reference
+    offers no box derivative).  The box gradient is that of the physical energy with the positions held fixed as passed: all
+    nine entries, in the box's dtype, so stress and virial losses see both PME terms.
+
     ``reciprocal`` (keyword only, default False): with True the constructor computes the B-spline moduli and
     ``compute_reciprocal`` works as the reference's; with False ``compute_reciprocal`` raises, as this class always did.  The
     default will become True in a later change."""
@@ -90,7 +96,9 @@ class PME:
 
     def compute_direct(self, positions: torch.Tensor, charges: torch.Tensor, cutoff: float, box_vectors: torch.Tensor,
                        max_num_pairs: int = -1):
-        """Energy of the direct-space term (a 0-dim tensor)."""
+        """Energy of the direct-space term (a 0-dim tensor).  Differentiable with respect to positions, charges and, when it
+        requires a gradient, box_vectors (``pme_direct_box``; the pair list's deltas pass no gradient, so the box is not counted
+        twice)."""
         if positions.dim() != 2 or positions.shape[1] != 3:
             raise ValueError('positions must have shape (atoms, 3)')
         if charges.dim() != 1:
@@ -103,10 +111,14 @@ class PME:
             raise ValueError('cutoff must be positive')
         neighbors, deltas, distances, _ = getNeighborPairs(positions, cutoff, max_num_pairs, box_vectors)
         self.exclusions = self.exclusions.to(positions.device)
+        if box_vectors.requires_grad and torch.is_grad_enabled():
+            return torch.ops.pme.pme_direct_box(positions, charges, neighbors, deltas, distances, self.exclusions, box_vectors,
+                                                self.alpha, self.coulomb)
         return torch.ops.pme.pme_direct(positions, charges, neighbors, deltas, distances, self.exclusions, self.alpha, self.coulomb)
 
     def compute_reciprocal(self, positions: torch.Tensor, charges: torch.Tensor, box_vectors: torch.Tensor):
-        """Energy of the reciprocal-space term including the self energy (a 0-dim tensor); needs ``PME(..., reciprocal=True)``."""
+        """Energy of the reciprocal-space term including the self energy (a 0-dim tensor); needs ``PME(..., reciprocal=True)``.
+        Differentiable with respect to positions, charges and box_vectors (the self energy does not depend on the box)."""
         if not self.reciprocal:
             raise RuntimeError("the reciprocal-space term of PME is not enabled on this object: construct it with "
                                "PME(..., reciprocal=True) (the default stays False for now, see DESIGN.md, scope)")
