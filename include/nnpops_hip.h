@@ -18,6 +18,8 @@
  *   nnpops_neighbor_pairs_box_backward / _double_backward   box gradient and second derivatives of that op
  *                                               (the reference's CPU op differentiates both: getNeighborPairsCPU.cpp:56-98)
  *   nnpops_pme_direct                           pme::pme_direct (computeDirect)   src/pytorch/pme/pmeCUDA.cu:30-100
+ *   nnpops_pme_direct_double_backward, nnpops_pme_reciprocal_spread_directional / _interpolate_second   second derivatives of both PME
+ *                                               terms w.r.t. positions and charges (the reference refuses them)
  *   nnpops_pme_direct_box, nnpops_pme_reciprocal_convolve_box / _box_gradient   box gradients of both PME terms (no reference
  *                                               counterpart: pme::pme_direct_box and the box gradient of pme::pme_reciprocal)
  *
@@ -345,6 +347,25 @@ int64_t nnpops_pme_direct_box_workspace_bytes(int64_t num_pairs);
 int nnpops_pme_direct_box(int num_atoms, int64_t num_pairs, int max_exclusions, const float* positions, const float* charges,
                           const int32_t* neighbors, const float* deltas, const float* distances, const int32_t* exclusions,
                           const float* box_vectors, float alpha, float coulomb, float* grad_box, void* workspace, void* stream);
+/* Double backward of the direct-space energy with respect to positions and charges (additive; force matching).  With P = dE/dpositions
+ * and C = dE/dcharges of the entries above and the cotangents v (device float32 [num_atoms][3]) and w (device [num_atoms]):
+ *     grad_positions [num_atoms][3] = d/dpositions,  grad_charges [num_atoms] = d/dcharges  of  L = sum_i v_i . P_i + sum_i w_i C_i
+ * (both fully overwritten; the caller scales them by the energy's grad_output).  deltas / distances enter as data: the image shifts
+ * are held fixed, as in the first-order entries.  Excluded pairs un-wrapped, every atom from its own row (symmetric table).
+ * Owner computes over the list's transposed index, no atomics of any kind, float64 sums in a fixed order: bitwise reproducible; no
+ * host synchronisation (graph-capturable).
+ *   index: nnpops_neighbor_pairs_build_index of `neighbors` -- required;
+ *   first_index: NULL for a list grouped by neighbors[0] (what the forward op of getNeighborPairs emits: `index`'s row segments are
+ *     used); for any other list the index built from the list with its two rows swapped ([neighbors[1]; neighbors[0]]), whose column
+ *     segments then serve the first side.  build_index drops slots whose column is outside [0, num_atoms) and skips a tile that
+ *     STARTS with a negative column, so for a list with -1 slots among the pairs build both indices from a copy in which the
+ *     negative entries are replaced by num_atoms (the torch op does exactly that).
+ *   workspace: nnpops_pme_direct_double_backward_workspace_bytes(num_pairs, num_atoms) bytes (32 bytes per slot). */
+int64_t nnpops_pme_direct_double_backward_workspace_bytes(int64_t num_pairs, int num_atoms);
+int nnpops_pme_direct_double_backward(int num_atoms, int64_t num_pairs, int max_exclusions, const float* positions, const float* charges,
+                                      const int32_t* neighbors, const float* deltas, const float* distances, const int32_t* exclusions,
+                                      const int32_t* index, const int32_t* first_index, const float* v, const float* w, float alpha,
+                                      float coulomb, float* grad_positions, float* grad_charges, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * PME, reciprocal-space part (replaces computeReciprocal: src/pytorch/pme/pmeCUDA.cu:102-430, pmeCPU.cpp:174-364).  Three passes
@@ -390,6 +411,28 @@ int nnpops_pme_reciprocal_convolve_box(int num_atoms, int gridx, int gridy, int 
 int nnpops_pme_reciprocal_box_gradient(int num_atoms, int gridx, int gridy, int gridz, int order, const float* positions,
                                        const float* box_vectors, const float* position_deriv, float* grad_box, void* box_workspace,
                                        void* stream);
+/* Double backward of the reciprocal-space energy with respect to positions and charges (additive; force matching).  W_i(m): atom i's
+ * separable B-spline weight at grid point m; phi: the real grid of step 4 (the potential).  With the cotangents v (device float32
+ * [num_atoms][3], of dE/dpositions) and w (device [num_atoms], of dE/dcharges), L = sum_i v_i . dE/dx_i + sum_i w_i dE/dq_i:
+ *   7. nnpops_pme_reciprocal_spread_directional: real grid (fully overwritten) Q' = sqrt(coulomb) sum_i [w_i W_i + q_i (v_i . grad) W_i],
+ *      over the bricks and sorted atoms step 1 left in `workspace` (same positions: no second sort); also fills second_workspace;
+ *   8. the caller: rfftn(Q') -> nnpops_pme_reciprocal_convolve (its energy output is not needed) -> irfftn(norm = "forward") = phi';
+ *   9. nnpops_pme_reciprocal_interpolate_second: from phi (potential_grid) and phi' (directional_grid)
+ *        grad_charges[j]   = sqrt(coulomb) [W_j . phi' + ((v_j . grad) W_j) . phi]
+ *        grad_positions[j] = sqrt(coulomb) [q_j grad W_j . phi' + q_j grad((v_j . grad) W_j) . phi + w_j grad W_j . phi]
+ *      (both fully overwritten; the caller scales them by the energy's grad_output).
+ * workspace: the buffer of steps 1-5 of the SAME evaluation, unchanged since (steps 7-9 only read its splines and bricks; step 8
+ * overwrites its energy partials).  second_workspace: nnpops_pme_reciprocal_second_workspace_bytes(...) bytes, the same buffer for 7 and 9
+ * (second-derivative weights and the fractional directions).  positions, charges, box_vectors: as passed to step 1.  Orders 4 and 5.
+ * No atomics: bitwise reproducible.  No host synchronisation (graph-capturable). */
+int64_t nnpops_pme_reciprocal_second_workspace_bytes(int num_atoms, int gridx, int gridy, int gridz, int order);
+int nnpops_pme_reciprocal_spread_directional(int num_atoms, int gridx, int gridy, int gridz, int order, const float* positions,
+                                             const float* charges, const float* box_vectors, float coulomb, const float* v, const float* w,
+                                             float* real_grid, void* workspace, void* second_workspace, void* stream);
+int nnpops_pme_reciprocal_interpolate_second(int num_atoms, int gridx, int gridy, int gridz, int order, const float* charges,
+                                             const float* box_vectors, float coulomb, const float* w, const float* potential_grid,
+                                             const float* directional_grid, float* grad_positions, float* grad_charges, void* workspace,
+                                             void* second_workspace, void* stream);
 
 /* ---- dense layers of the ANI atomic networks (reference src/pytorch/BatchedNN.cpp:30-50, BatchedNN.py:37-122) ----
  * C[M x N] = A[M x K] B with fp32 in and out; the products run on the half-precision matrix instruction with every

@@ -100,6 +100,16 @@ SIGNATURES = {
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_pme_reciprocal_box_gradient": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nnpops_pme_direct_double_backward_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int]),
+    "nnpops_pme_direct_double_backward": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nnpops_pme_reciprocal_second_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nnpops_pme_reciprocal_spread_directional": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                           C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nnpops_pme_reciprocal_interpolate_second": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
+                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                           C.c_void_p]),
     "nnpops_neighbor_pairs_backward": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_neighbor_pairs_backward_workspace_bytes": (C.c_int64, [C.c_int]),
@@ -556,6 +566,81 @@ def pme_reciprocal_box(positions, charges, box_vectors, gridx, gridy, gridz, ord
         _check(L.nnpops_pme_reciprocal_box_gradient(n, gridx, gridy, gridz, order, _ptr(positions), _ptr(box_vectors), _ptr(pos_deriv),
                                                     _ptr(grad_box), _ptr(box_ws), _stream_ptr(dev)))
     return energy, pos_deriv, charge_deriv, grad_box
+
+
+def pme_direct_double_backward(positions, charges, neighbors, deltas, distances, exclusions, v, w, alpha, coulomb, index=None):
+    """Double backward of direct-space PME through the C ABI: with P = dE/dpositions, C = dE/dcharges of pme_direct and the
+    cotangents v [N, 3], w [N] -> (d/dpositions [N, 3], d/dcharges [N]) of sum v . P + sum w C (deltas and distances as data).
+    index: the transposed index of a list grouped by neighbors[0] (as for pme_direct).  None: any list -- any order, -1 slots
+    anywhere; both sides' indices are built here from a copy with the unused entries replaced by N.  No atomics."""
+    _dev_f32(positions, "positions")
+    _dev_f32(charges, "charges")
+    n, pairs = positions.size(0), neighbors.size(1)
+    dev = positions.device
+    _dev_f32(v, "v", (n, 3))
+    _dev_f32(w, "w", (n,))
+    exclusions = exclusions.to(device=dev, dtype=torch.int32).contiguous()
+    max_excl = exclusions.size(1)
+    neighbors = neighbors.to(torch.int32).contiguous()
+    first_index = None
+    if index is None:
+        clean = torch.where(neighbors < 0, torch.full_like(neighbors, n), neighbors).contiguous()
+        index = neighbor_pairs_build_index(n, clean)
+        first_index = neighbor_pairs_build_index(n, clean.flip(0).contiguous())
+    grad_positions = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    grad_charges = torch.empty((n,), dtype=torch.float32, device=dev)
+    L = lib()
+    ws = torch.empty((int(L.nnpops_pme_direct_double_backward_workspace_bytes(pairs, n)),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(L.nnpops_pme_direct_double_backward(n, pairs, max_excl, _ptr(positions), _ptr(charges), _ptr(neighbors),
+                                                   _ptr(deltas.contiguous()), _ptr(distances.contiguous()),
+                                                   _ptr(exclusions) if max_excl else None, _ptr(index),
+                                                   None if first_index is None else _ptr(first_index), _ptr(v), _ptr(w), float(alpha),
+                                                   float(coulomb), _ptr(grad_positions), _ptr(grad_charges), _ptr(ws), _stream_ptr(dev)))
+    return grad_positions, grad_charges
+
+
+def pme_reciprocal_double_backward(positions, charges, box_vectors, gridx, gridy, gridz, order, alpha, coulomb, xmoduli, ymoduli, zmoduli,
+                                   v, w):
+    """Double backward of reciprocal-space PME through the C ABI (steps 1-4 of pme_reciprocal, then spread_directional -> rfftn ->
+    convolve -> irfftn -> interpolate_second): with the cotangents v [N, 3] of dE/dpositions and w [N] of dE/dcharges
+    -> (d/dpositions [N, 3], d/dcharges [N]) of sum v . dE/dpositions + sum w dE/dcharges.  Orders 4 and 5."""
+    _dev_f32(positions, "positions")
+    _dev_f32(charges, "charges")
+    _dev_f32(box_vectors, "box_vectors", (3, 3))
+    dev = positions.device
+    n = positions.size(0)
+    _dev_f32(v, "v", (n, 3))
+    _dev_f32(w, "w", (n,))
+    mods = [_dev_f32(m.to(device=dev, dtype=torch.float32).contiguous(), name, (k,))
+            for m, name, k in ((xmoduli, "xmoduli", gridx), (ymoduli, "ymoduli", gridy), (zmoduli, "zmoduli", gridz))]
+    L = lib()
+    dims = (gridx, gridy, gridz, order)
+    ws = torch.empty((int(L.nnpops_pme_reciprocal_workspace_bytes(n, *dims)),), dtype=torch.uint8, device=dev)
+    ws2 = torch.empty((int(L.nnpops_pme_reciprocal_second_workspace_bytes(n, *dims)),), dtype=torch.uint8, device=dev)
+    real = torch.empty((gridx, gridy, gridz), dtype=torch.float32, device=dev)
+    real2 = torch.empty_like(real)
+    energy = torch.empty((1,), dtype=torch.float32, device=dev)
+    grad_positions = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    grad_charges = torch.empty((n,), dtype=torch.float32, device=dev)
+
+    def convolved(grid):
+        recip = torch.fft.rfftn(grid).contiguous()
+        _check(L.nnpops_pme_reciprocal_convolve(n, *dims, _ptr(box_vectors), float(alpha), _ptr(mods[0]), _ptr(mods[1]), _ptr(mods[2]),
+                                                _ptr(recip), _ptr(energy), _ptr(ws), _stream_ptr(dev)))
+        return torch.fft.irfftn(recip, s=(gridx, gridy, gridz), norm="forward").contiguous()
+
+    with torch.cuda.device(dev):
+        _check(L.nnpops_pme_reciprocal_spread(n, *dims, _ptr(positions), _ptr(charges), _ptr(box_vectors), float(coulomb), _ptr(real),
+                                              _ptr(ws), _stream_ptr(dev)))
+        phi = convolved(real)
+        _check(L.nnpops_pme_reciprocal_spread_directional(n, *dims, _ptr(positions), _ptr(charges), _ptr(box_vectors), float(coulomb),
+                                                          _ptr(v), _ptr(w), _ptr(real2), _ptr(ws), _ptr(ws2), _stream_ptr(dev)))
+        phi2 = convolved(real2)
+        _check(L.nnpops_pme_reciprocal_interpolate_second(n, *dims, _ptr(charges), _ptr(box_vectors), float(coulomb), _ptr(w), _ptr(phi),
+                                                          _ptr(phi2), _ptr(grad_positions), _ptr(grad_charges), _ptr(ws), _ptr(ws2),
+                                                          _stream_ptr(dev)))
+    return grad_positions, grad_charges
 
 
 # ---------------------------------------------------------------------------------------------

@@ -26,6 +26,8 @@
 //   pme_recip_box_pi          after the convolution, one lane per complex point: Pi in double per workgroup from the scaled grid;
 //   pme_recip_box_atoms       one lane per atom: X in double per workgroup from the positions and the interpolated g;
 //   pme_recip_box_finish      one workgroup: both sums in a fixed order, then - B^-T (Pi + X).
+// Second derivatives with respect to positions and charges: pme_recip_spline2, pme_recip_gather_dir and pme_recip_interp2,
+// described where they stand below; they read what the passes above left in the workspace and leave those passes as they are.
 // The box is read on the device by every pass (never copied to the host): a captured graph follows new box values written in place.
 #include <cmath>
 
@@ -585,6 +587,255 @@ __global__ __launch_bounds__(kBlock) void pme_recip_interp(int num_atoms, Dims d
     charge_deriv[atom] = dq * sqrt_coulomb;
 }
 
+// =====================================================================================================================================
+// Second order: the double backward with respect to positions and charges.  W_i(m) = atom i's separable weight at grid
+// point m, Q = sum_i q_i W_i the charge grid, phi = G * Q the potential grid (the irfftn the interpolation reads).  With cotangents
+// v [N][3] of the position gradient and w [N] of the charge gradient, L = sum_i v_i . dE/dx_i + sum_i w_i dE/dq_i = Q' . phi with
+//     Q'  = sum_i [w_i W_i + q_i (v_i . grad) W_i]        pme_recip_gather_dir: the forward's bricks and sorted atoms, no second sort
+//     phi' = G * Q'                                        the caller: rfftn -> nnpops_pme_reciprocal_convolve -> irfftn
+//     dL/dq_j = W_j . phi' + ((v_j . grad) W_j) . phi
+//     dL/dx_j = q_j grad W_j . phi' + q_j grad((v_j . grad) W_j) . phi + w_j grad W_j . phi      pme_recip_interp2
+// (v . grad) W along axis a is s_a dtheta_a times the other two axes' theta, s_a = K_a (v . B^-1 column a); its gradient needs
+// d2theta (the order-(n-2) weights differenced twice) and the mixed products dtheta_a dtheta_b theta_c.  pme_recip_spline2 recomputes
+// the fractional offset from the positions exactly as pme_recip_spline does and stores d2theta and s in a workspace of its own.
+// The first-order kernels above are not touched.
+struct SecondWorkspace {
+    float* d2theta;       // [N][3][order]
+    float* dir;           // [N][3]        s_a = K_a (v . B^-1 column a)
+    size_t bytes;
+};
+
+SecondWorkspace second_carve(void* workspace, int num_atoms, int order) {
+    SecondWorkspace w{};
+    uintptr_t p = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
+    auto take = [&](size_t bytes) { const uintptr_t at = p; p += (bytes + 255) & ~(size_t)255; return at; };
+    w.d2theta = (float*)take(sizeof(float) * 3 * (size_t)order * (size_t)num_atoms);
+    w.dir = (float*)take(sizeof(float) * 3 * (size_t)num_atoms);
+    w.bytes = (size_t)(p - (uintptr_t)workspace) + 256;
+    return w;
+}
+
+template <int ORDER>
+__global__ __launch_bounds__(kBlock) void pme_recip_spline2(int num_atoms, const float* __restrict__ pos, const float* __restrict__ box,
+                                                            Dims d, const int4* __restrict__ base, const float* __restrict__ v,
+                                                            float* __restrict__ d2theta, float* __restrict__ dir) {
+    const int atom = blockIdx.x * kBlock + threadIdx.x;
+    if (atom >= num_atoms) return;
+    float b[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) b[i] = box[i];
+    const RecipBox r = recip_box(b);
+    float p[3] = {pos[3 * atom], pos[3 * atom + 1], pos[3 * atom + 2]};
+    const float rdiag[3] = {r.r00, r.r11, r.r22};
+#pragma unroll
+    for (int i = 2; i >= 0; i--) {                        // into the reduced box, c then b then a (as pme_recip_spline)
+        const float s = floorf(p[i] * rdiag[i]);
+#pragma unroll
+        for (int j = 0; j < 3; j++) p[j] -= s * b[3 * i + j];
+    }
+    const float t3[3] = {p[0] * r.r00 + p[1] * r.r10 + p[2] * r.r20,
+                         p[0] * 0.0f + p[1] * r.r11 + p[2] * r.r21,
+                         p[0] * 0.0f + p[1] * 0.0f + p[2] * r.r22};
+    const int K[3] = {d.kx, d.ky, d.kz};
+    const int4 b0 = base[atom];
+    const int g0[3] = {b0.x, b0.y, b0.z};
+    float* d2 = d2theta + (size_t)atom * 3 * ORDER;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const float t = (t3[i] - floorf(t3[i])) * K[i];
+        const int ti = (int)t;
+        float dr = t - ti;
+        // the base index is the forward pass's: should this pass round the offset to the other side of a grid line, take the end of
+        // the forward's cell (the weights are continuous there)
+        const int gi = min(max(ti % K[i], 0), K[i] - 1);
+        if (gi != g0[i]) dr = ((gi - g0[i] + K[i]) % K[i] == 1) ? 1.0f : 0.0f;
+        // weights of order ORDER - 2 by the recursion of pme_recip_spline, then differenced twice
+        float w[ORDER];
+#pragma unroll
+        for (int j = 0; j < ORDER; j++) w[j] = 0.f;
+        w[1] = dr;
+        w[0] = 1.f - dr;
+#pragma unroll
+        for (int j = 3; j <= ORDER - 2; j++) {
+            const float div = 1.0f / (j - 1);
+            w[j - 1] = div * dr * w[j - 2];
+#pragma unroll
+            for (int k = 1; k < j - 1; k++) w[j - k - 1] = div * ((dr + k) * w[j - k - 2] + (j - k - dr) * w[j - k - 1]);
+            w[0] = div * (1.f - dr) * w[0];
+        }
+#pragma unroll
+        for (int j = 0; j < ORDER; j++) {
+            const float lo = j >= 2 ? w[j - 2] : 0.f, mid = j >= 1 ? w[j - 1] : 0.f;      // (w[ORDER-2], w[ORDER-1] are zero)
+            d2[i * ORDER + j] = lo - 2.0f * mid + w[j];
+        }
+    }
+    const float vx = v[3 * atom], vy = v[3 * atom + 1], vz = v[3 * atom + 2];
+    dir[3 * atom] = K[0] * (vx * r.r00 + vy * r.r10 + vz * r.r20);
+    dir[3 * atom + 1] = K[1] * (vy * r.r11 + vz * r.r21);
+    dir[3 * atom + 2] = K[2] * (vz * r.r22);
+}
+
+// the two weights of one axis of a staged atom at point `g` (row: ORDER values of the first array, then ORDER of the second): every
+// stencil slot i with (g0 + i) mod K == g, as axis_weight
+template <int ORDER>
+__device__ __forceinline__ void axis_weights2(int g, int g0, int K, const float* row, float& a, float& b) {
+    int dd = g - g0;
+    dd += dd < 0 ? K : 0;
+    a = 0.f;
+    b = 0.f;
+    for (int i = dd; i < ORDER; i += K) { a += row[i]; b += row[ORDER + i]; }
+}
+
+// the spread of Q' as a gather: pme_recip_gather's walk over the bricks and sorted atoms the forward pass left in the workspace; per
+// staged atom six axis arrays -- x: A = w theta + q s_x dtheta and q theta; y: theta and s_y dtheta; z: theta and s_z dtheta -- and
+//     Q'(m) += A_x ty tz + (q tx) (Dy tz + ty Dz)
+// The staged weights lie atom-major in LDS with an odd stride: a lane reads the one slot its point needs per array (lanes of a wave
+// ask for at most ORDER neighbouring words: no bank conflict) instead of all ORDER slots and a select.  A wave's 64 points share
+// their x: an atom whose x stencil misses it is skipped by the whole wave.
+template <int ORDER>
+__global__ __launch_bounds__(kBlock) void pme_recip_gather_dir(Dims d, const int* __restrict__ start, const int* __restrict__ sorted,
+                                                               const int4* __restrict__ base, const float* __restrict__ theta,
+                                                               const float* __restrict__ dtheta, const float* __restrict__ dir,
+                                                               const float* __restrict__ charge, const float* __restrict__ wq,
+                                                               float sqrt_coulomb, float* __restrict__ grid) {
+    __shared__ int s_bx[kMaxBinsPerAxis], s_by[kMaxBinsPerAxis], s_bz[kMaxBinsPerAxis];
+    __shared__ int s_first[kMaxBinsPerAxis * kMaxBinsPerAxis * kMaxBinsPerAxis];
+    __shared__ int s_prefix[kMaxBinsPerAxis * kMaxBinsPerAxis * kMaxBinsPerAxis + 1];
+    __shared__ int s_ntrip;
+    __shared__ int s_base[3][kBlock];
+    __shared__ float s_w[kBlock][6 * ORDER + 1];           // [slot][array * ORDER + i]: Ax, Qx, Ty, Dy, Tz, Dz (odd stride)
+    __shared__ int s_n[3], s_count[kMaxBinsPerAxis * kMaxBinsPerAxis * kMaxBinsPerAxis];
+
+    const int brick = blockIdx.x;
+    const int bz = brick % d.nbz, by = (brick / d.nbz) % d.nby, bx = brick / (d.nbz * d.nby);
+    if (threadIdx.x == 0) s_n[0] = window_bins(bx, kBX, d.kx, d.nbx, ORDER, s_bx);
+    if (threadIdx.x == 64) s_n[1] = window_bins(by, kBY, d.ky, d.nby, ORDER, s_by);
+    if (threadIdx.x == 128) s_n[2] = window_bins(bz, kBZ, d.kz, d.nbz, ORDER, s_bz);
+    __syncthreads();
+    const int nx = s_n[0], ny = s_n[1], nz = s_n[2];
+    if ((int)threadIdx.x < nx * ny * nz) {                // window order: x outermost, z innermost
+        const int i = threadIdx.x / (ny * nz), j = (threadIdx.x / nz) % ny, k = threadIdx.x % nz;
+        const long long bin = ((long long)s_bx[i] * d.nby + s_by[j]) * d.nbz + s_bz[k];
+        const int first = start[bin];
+        s_first[threadIdx.x] = first;
+        s_count[threadIdx.x] = start[bin + 1] - first;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int total = 0;
+        const int t = nx * ny * nz;
+        for (int u = 0; u < t; u++) { s_prefix[u] = total; total += s_count[u]; }
+        s_prefix[t] = total;
+        s_ntrip = t;
+    }
+    __syncthreads();
+    const int ntrip = s_ntrip, total = s_prefix[ntrip];
+    const int gx = bx * kBX + (threadIdx.x / (kBY * kBZ)), gy = by * kBY + (threadIdx.x / kBZ) % kBY, gz = bz * kBZ + threadIdx.x % kBZ;
+    const bool live = gx < d.kx && gy < d.ky && gz < d.kz;
+    float acc = 0.f;
+    for (int c0 = 0; c0 < total; c0 += kBlock) {
+        const int f = c0 + threadIdx.x;
+        if (f < total) {
+            int t = 0;
+            while (s_prefix[t + 1] <= f) t++;
+            const int atom = sorted[s_first[t] + (f - s_prefix[t])];
+            const int4 b0 = base[atom];
+            s_base[0][threadIdx.x] = b0.x; s_base[1][threadIdx.x] = b0.y; s_base[2][threadIdx.x] = b0.z;
+            const float qs = charge[atom] * sqrt_coulomb, ws = wq[atom] * sqrt_coulomb;
+            const float sx = dir[3 * atom], sy = dir[3 * atom + 1], sz = dir[3 * atom + 2];
+            const float* th = theta + (size_t)atom * 3 * ORDER;
+            const float* dth = dtheta + (size_t)atom * 3 * ORDER;
+#pragma unroll
+            for (int i = 0; i < ORDER; i++) {
+                s_w[threadIdx.x][i] = ws * th[i] + qs * sx * dth[i];
+                s_w[threadIdx.x][ORDER + i] = qs * th[i];
+                s_w[threadIdx.x][2 * ORDER + i] = th[ORDER + i];
+                s_w[threadIdx.x][3 * ORDER + i] = sy * dth[ORDER + i];
+                s_w[threadIdx.x][4 * ORDER + i] = th[2 * ORDER + i];
+                s_w[threadIdx.x][5 * ORDER + i] = sz * dth[2 * ORDER + i];
+            }
+        }
+        __syncthreads();
+        const int m = min(kBlock, total - c0);
+        if (live) {
+            for (int k = 0; k < m; k++) {
+                int ddx = gx - s_base[0][k];
+                ddx += ddx < 0 ? d.kx : 0;
+                if (ddx >= ORDER) continue;                // (the x stencil misses this wave's points: adds exactly nothing)
+                float ax, qx, ty, dy, tz, dz;
+                axis_weights2<ORDER>(gx, s_base[0][k], d.kx, &s_w[k][0], ax, qx);
+                axis_weights2<ORDER>(gy, s_base[1][k], d.ky, &s_w[k][2 * ORDER], ty, dy);
+                axis_weights2<ORDER>(gz, s_base[2][k], d.kz, &s_w[k][4 * ORDER], tz, dz);
+                acc += ax * ty * tz + qx * (dy * tz + ty * dz);
+            }
+        }
+        __syncthreads();
+    }
+    if (live) grid[((size_t)gx * d.ky + gy) * d.kz + gz] = acc;
+}
+
+// one lane per atom over its order^3 stencil, both grids: the sums along z first, then the x / y weights
+template <int ORDER>
+__global__ __launch_bounds__(kBlock) void pme_recip_interp2(int num_atoms, Dims d, const float* __restrict__ box,
+                                                            const float* __restrict__ charge, const float* __restrict__ wq,
+                                                            float sqrt_coulomb, const int4* __restrict__ base,
+                                                            const float* __restrict__ theta, const float* __restrict__ dtheta,
+                                                            const float* __restrict__ d2theta, const float* __restrict__ dir,
+                                                            const float* __restrict__ phi, const float* __restrict__ phi2,
+                                                            float* __restrict__ grad_pos, float* __restrict__ grad_charge) {
+    const int atom = blockIdx.x * kBlock + threadIdx.x;
+    if (atom >= num_atoms) return;
+    float b[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) b[i] = box[i];
+    const RecipBox r = recip_box(b);
+    const int4 b0 = base[atom];
+    const float* th = theta + (size_t)atom * 3 * ORDER;
+    const float* dth = dtheta + (size_t)atom * 3 * ORDER;
+    const float* d2 = d2theta + (size_t)atom * 3 * ORDER;
+    float tz[ORDER], dz[ORDER], cz[ORDER];
+    int iz[ORDER];
+#pragma unroll
+    for (int i = 0; i < ORDER; i++) {
+        tz[i] = th[2 * ORDER + i]; dz[i] = dth[2 * ORDER + i]; cz[i] = d2[2 * ORDER + i];
+        iz[i] = (b0.z + i) % d.kz;
+    }
+    float hx = 0.f, hy = 0.f, hz = 0.f;                                       // d_a W . phi
+    float hxx = 0.f, hyy = 0.f, hzz = 0.f, hxy = 0.f, hxz = 0.f, hyz = 0.f;   // d_a d_b W . phi
+    float a2 = 0.f, g2x = 0.f, g2y = 0.f, g2z = 0.f;                          // W . phi', d_a W . phi'
+#pragma unroll
+    for (int a = 0; a < ORDER; a++) {
+        const int xi = (b0.x + a) % d.kx;
+        const float tx = th[a], dx = dth[a], cx = d2[a];
+#pragma unroll
+        for (int c = 0; c < ORDER; c++) {
+            const size_t row = ((size_t)xi * d.ky + (b0.y + c) % d.ky) * d.kz;
+            const float ty = th[ORDER + c], dy = dth[ORDER + c], cy = d2[ORDER + c];
+            float z0 = 0.f, z1 = 0.f, z2 = 0.f, p0 = 0.f, p1 = 0.f;
+#pragma unroll
+            for (int e = 0; e < ORDER; e++) {
+                const float g = phi[row + iz[e]], g2 = phi2[row + iz[e]];
+                z0 += tz[e] * g; z1 += dz[e] * g; z2 += cz[e] * g;
+                p0 += tz[e] * g2; p1 += dz[e] * g2;
+            }
+            const float txy = tx * ty, dxy = dx * ty, xdy = tx * dy;
+            hx += dxy * z0; hy += xdy * z0; hz += txy * z1;
+            hxx += cx * ty * z0; hyy += tx * cy * z0; hzz += txy * z2;
+            hxy += dx * dy * z0; hxz += dxy * z1; hyz += xdy * z1;
+            a2 += txy * p0; g2x += dxy * p0; g2y += xdy * p0; g2z += txy * p1;
+        }
+    }
+    const float sx = dir[3 * atom], sy = dir[3 * atom + 1], sz = dir[3 * atom + 2];
+    const float qs = charge[atom] * sqrt_coulomb, ws = wq[atom] * sqrt_coulomb;
+    grad_charge[atom] = sqrt_coulomb * (a2 + sx * hx + sy * hy + sz * hz);
+    const float fx = (qs * (g2x + sx * hxx + sy * hxy + sz * hxz) + ws * hx) * d.kx;
+    const float fy = (qs * (g2y + sx * hxy + sy * hyy + sz * hyz) + ws * hy) * d.ky;
+    const float fz = (qs * (g2z + sx * hxz + sy * hyz + sz * hzz) + ws * hz) * d.kz;
+    grad_pos[3 * atom] = fx * r.r00;
+    grad_pos[3 * atom + 1] = fx * r.r10 + fy * r.r11;
+    grad_pos[3 * atom + 2] = fx * r.r20 + fy * r.r21 + fz * r.r22;
+}
+
 int check_common(int num_atoms, int gx, int gy, int gz, int order) {
     NNPOPS_REQUIRE(num_atoms >= 0, "bad number of atoms %d", num_atoms);
     NNPOPS_REQUIRE(gx >= 1 && gy >= 1 && gz >= 1, "the grid dimensions must be positive (%d, %d, %d)", gx, gy, gz);
@@ -716,6 +967,70 @@ int nnpops_pme_reciprocal_interpolate(int num_atoms, int gridx, int gridy, int g
     else
         hipLaunchKernelGGL(pme_recip_interp<5>, dim3(ab), dim3(kBlock), 0, s, num_atoms, d, box_vectors, charges, sqrt_coulomb,
                            (const int4*)w.base, (const float*)w.theta, (const float*)w.dtheta, real_grid, position_deriv, charge_deriv);
+    NNPOPS_HIP_TRY(hipGetLastError());
+    return NNPOPS_OK;
+}
+
+int64_t nnpops_pme_reciprocal_second_workspace_bytes(int num_atoms, int gridx, int gridy, int gridz, int order) {
+    if (check_common(num_atoms, gridx, gridy, gridz, order) != NNPOPS_OK) return 0;
+    return (int64_t)second_carve(nullptr, num_atoms, order).bytes;
+}
+
+int nnpops_pme_reciprocal_spread_directional(int num_atoms, int gridx, int gridy, int gridz, int order, const float* positions,
+                                             const float* charges, const float* box_vectors, float coulomb, const float* v, const float* w,
+                                             float* real_grid, void* workspace, void* second_workspace, void* stream) {
+    if (int rc = check_common(num_atoms, gridx, gridy, gridz, order)) return rc;
+    NNPOPS_REQUIRE(coulomb > 0, "coulomb must be positive");
+    NNPOPS_REQUIRE(box_vectors && real_grid && workspace && second_workspace, "NULL device pointer");
+    NNPOPS_REQUIRE(num_atoms == 0 || (positions && charges && v && w), "NULL positions / charges / cotangent pointer");
+    hipStream_t s = (hipStream_t)stream;
+    const Dims d = make_dims(gridx, gridy, gridz);
+    const RecipWorkspace ws = carve(workspace, num_atoms, gridx, gridy, gridz, order);
+    const SecondWorkspace w2 = second_carve(second_workspace, num_atoms, order);
+    const float sqrt_coulomb = (float)std::sqrt((double)coulomb);
+    const int ab = div_up(num_atoms, kBlock);
+    if (order == 4) {
+        if (num_atoms > 0)
+            hipLaunchKernelGGL(pme_recip_spline2<4>, dim3(ab), dim3(kBlock), 0, s, num_atoms, positions, box_vectors, d, (const int4*)ws.base, v,
+                               w2.d2theta, w2.dir);
+        hipLaunchKernelGGL(pme_recip_gather_dir<4>, dim3((unsigned)d.nbins), dim3(kBlock), 0, s, d, (const int*)ws.bin_start,
+                           (const int*)ws.sorted, (const int4*)ws.base, (const float*)ws.theta, (const float*)ws.dtheta,
+                           (const float*)w2.dir, charges, w, sqrt_coulomb, real_grid);
+    } else {
+        if (num_atoms > 0)
+            hipLaunchKernelGGL(pme_recip_spline2<5>, dim3(ab), dim3(kBlock), 0, s, num_atoms, positions, box_vectors, d, (const int4*)ws.base, v,
+                               w2.d2theta, w2.dir);
+        hipLaunchKernelGGL(pme_recip_gather_dir<5>, dim3((unsigned)d.nbins), dim3(kBlock), 0, s, d, (const int*)ws.bin_start,
+                           (const int*)ws.sorted, (const int4*)ws.base, (const float*)ws.theta, (const float*)ws.dtheta,
+                           (const float*)w2.dir, charges, w, sqrt_coulomb, real_grid);
+    }
+    NNPOPS_HIP_TRY(hipGetLastError());
+    return NNPOPS_OK;
+}
+
+int nnpops_pme_reciprocal_interpolate_second(int num_atoms, int gridx, int gridy, int gridz, int order, const float* charges,
+                                             const float* box_vectors, float coulomb, const float* w, const float* potential_grid,
+                                             const float* directional_grid, float* grad_positions, float* grad_charges, void* workspace,
+                                             void* second_workspace, void* stream) {
+    if (int rc = check_common(num_atoms, gridx, gridy, gridz, order)) return rc;
+    NNPOPS_REQUIRE(coulomb > 0, "coulomb must be positive");
+    NNPOPS_REQUIRE(box_vectors && potential_grid && directional_grid && workspace && second_workspace, "NULL device pointer");
+    NNPOPS_REQUIRE(num_atoms == 0 || (charges && w && grad_positions && grad_charges), "NULL charges / cotangent / gradient pointer");
+    if (num_atoms == 0) return NNPOPS_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const Dims d = make_dims(gridx, gridy, gridz);
+    const RecipWorkspace ws = carve(workspace, num_atoms, gridx, gridy, gridz, order);
+    const SecondWorkspace w2 = second_carve(second_workspace, num_atoms, order);
+    const float sqrt_coulomb = (float)std::sqrt((double)coulomb);
+    const int ab = div_up(num_atoms, kBlock);
+    if (order == 4)
+        hipLaunchKernelGGL(pme_recip_interp2<4>, dim3(ab), dim3(kBlock), 0, s, num_atoms, d, box_vectors, charges, w, sqrt_coulomb,
+                           (const int4*)ws.base, (const float*)ws.theta, (const float*)ws.dtheta, (const float*)w2.d2theta,
+                           (const float*)w2.dir, potential_grid, directional_grid, grad_positions, grad_charges);
+    else
+        hipLaunchKernelGGL(pme_recip_interp2<5>, dim3(ab), dim3(kBlock), 0, s, num_atoms, d, box_vectors, charges, w, sqrt_coulomb,
+                           (const int4*)ws.base, (const float*)ws.theta, (const float*)ws.dtheta, (const float*)w2.d2theta,
+                           (const float*)w2.dir, potential_grid, directional_grid, grad_positions, grad_charges);
     NNPOPS_HIP_TRY(hipGetLastError());
     return NNPOPS_OK;
 }

@@ -1404,6 +1404,7 @@ TORCH_LIBRARY_IMPL(neighbors, CPU, m) { m.impl("getNeighborPairs", neighbor_pair
 struct PmeDirectForward {
     Tensor energy, pos_deriv, charge_deriv;
     Tensor pos, q, nb, dl, ds, ex;
+    Tensor index;      // the list's cached transposed index when the indexed kernels ran (pme_direct_twice keeps it)
 };
 
 class PmeDirectFunction : public torch::autograd::Function<PmeDirectFunction> {
@@ -1430,6 +1431,7 @@ public:
         const auto opts = positions.options();
         Tensor energy = torch::empty({}, opts), pos_deriv = torch::empty({n, 3}, opts), charge_deriv = torch::empty({n}, opts);
         const float a = (float)alpha.toDouble(), k = (float)coulomb.toDouble();
+        Tensor used_index;
         if (positions.is_cuda()) {
             c10::hip::HIPGuard guard(positions.device().index());
             const PairIndexCache& cache = pair_index_cache(positions.device().index());
@@ -1437,6 +1439,7 @@ public:
                                  nb.sizes() == cache.neighbors.sizes() && nb._version() == cache.version &&
                                  cache.index.numel() == nnpops_neighbor_pairs_index_ints((int)n, pairs);
             if (indexed) {
+                used_index = cache.index;
                 Tensor workspace = torch::empty({nnpops_pme_direct_indexed_workspace_bytes(pairs, (int)n)}, opts.dtype(torch::kUInt8));
                 if (nnpops_pme_direct_indexed((int)n, pairs, (int)max_excl, pos.data_ptr<float>(), q.data_ptr<float>(), nb.data_ptr<int32_t>(),
                                               dl.data_ptr<float>(), ds.data_ptr<float>(), max_excl ? ex.data_ptr<int32_t>() : nullptr,
@@ -1490,7 +1493,7 @@ public:
                 }
             energy.fill_((float)e);
         }
-        return {energy, pos_deriv, charge_deriv, pos, q, nb, dl, ds, ex};
+        return {energy, pos_deriv, charge_deriv, pos, q, nb, dl, ds, ex, used_index};
     }
 
     static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& neighbors,
@@ -1581,6 +1584,144 @@ public:
     }
 };
 
+// ---------------------------------------------------------------------------------------------
+// pme_direct_twice: pme_direct's forward and first-order backward (PmeDirectFunction::run, the same kernels and bits), recorded so that
+// the backward pass is itself differentiable with respect to positions and charges (force matching).  As with the
+// pair list: the backward is a Function (PmeDirectBackwardFunction: g -> g P, g C) whose own backward is the double backward
+// (PmeDirectDoubleBackwardFunction: pme_second_order.hip on the device, plain loops on the host); a third derivative raises.
+// pme_direct and pme_direct_box keep their refusal of create_graph=True: this op is the opt-in.
+// ---------------------------------------------------------------------------------------------
+// transposed index (pairs_index.hip) of a [2, pairs] int32 list whose unused entries have been replaced by num_atoms
+Tensor pme_build_pair_index(const Tensor& nb, int64_t n) {
+    const int64_t pairs = nb.size(1);
+    Tensor index = torch::empty({nnpops_neighbor_pairs_index_ints((int)n, pairs)}, nb.options());
+    Tensor iws = torch::empty({nnpops_neighbor_pairs_index_workspace_bytes((int)n, pairs) / 8 + 1}, nb.options().dtype(torch::kInt64));
+    if (nnpops_neighbor_pairs_build_index((int)n, pairs, nb.data_ptr<int32_t>(), index.data_ptr<int32_t>(), iws.data_ptr(),
+                                          current_stream(nb.device())) != NNPOPS_OK)
+        raise_last("pme::pme_direct_twice (double backward: the owner-computes gather needs the pair list's transposed index)");
+    return index;
+}
+
+class PmeDirectDoubleBackwardFunction : public torch::autograd::Function<PmeDirectDoubleBackwardFunction> {
+public:
+    // (v, w: cotangents of g P and g C) -> d/dpositions, d/dcharges, d/dg of g (sum v . P + sum w C)
+    static tensor_list forward(AutogradContext*, const Tensor& v_in, const Tensor& w_in, const Tensor& g, const Tensor& positions,
+                               const Tensor& charges, const Tensor& pos_deriv, const Tensor& charge_deriv, const Tensor& nb, const Tensor& dl,
+                               const Tensor& ds, const Tensor& ex, const std::optional<Tensor>& index_opt, double alpha, double coulomb) {
+        const Tensor v = v_in.contiguous(), w = w_in.contiguous(), pos = positions.contiguous(), q = charges.contiguous();
+        const int64_t n = pos.size(0), pairs = nb.size(1), max_excl = ex.size(1);
+        const auto opts = pos.options();
+        Tensor gx = torch::empty({n, 3}, opts), gq = torch::empty({n}, opts);
+        const float a = (float)alpha, k = (float)coulomb;
+        if (pos.is_cuda()) {
+            c10::hip::HIPGuard guard(pos.device().index());
+            Tensor index = index_opt.value_or(Tensor()), first_index;
+            if (!index.defined()) {
+                // a list of unknown origin: any order, -1 slots anywhere -- both sides through column segments (nnpops_hip.h)
+                const Tensor clean = torch::where(nb < 0, torch::full({}, n, nb.options()), nb).contiguous();
+                index = pme_build_pair_index(clean, n);
+                first_index = pme_build_pair_index(clean.flip(0).contiguous(), n);
+            }
+            Tensor workspace = torch::empty({nnpops_pme_direct_double_backward_workspace_bytes(pairs, (int)n)}, opts.dtype(torch::kUInt8));
+            if (nnpops_pme_direct_double_backward((int)n, pairs, (int)max_excl, pos.data_ptr<float>(), q.data_ptr<float>(), nb.data_ptr<int32_t>(),
+                                                  dl.data_ptr<float>(), ds.data_ptr<float>(), max_excl ? ex.data_ptr<int32_t>() : nullptr,
+                                                  index.data_ptr<int32_t>(), first_index.defined() ? first_index.data_ptr<int32_t>() : nullptr,
+                                                  v.data_ptr<float>(), w.data_ptr<float>(), a, k, gx.data_ptr<float>(), gq.data_ptr<float>(),
+                                                  workspace.data_ptr(), current_stream(pos.device())) != NNPOPS_OK)
+                raise_last("pme::pme_direct_twice (double backward)");
+        } else {
+            // the device pass's expressions per pair, double sums per atom
+            const float* P = pos.data_ptr<float>(); const float* Q = q.data_ptr<float>();
+            const float* V = v.data_ptr<float>(); const float* W = w.data_ptr<float>();
+            const int32_t* N0 = nb.data_ptr<int32_t>(); const int32_t* N1 = N0 + pairs; const int32_t* E = ex.data_ptr<int32_t>();
+            const float* DL = dl.data_ptr<float>(); const float* DS = ds.data_ptr<float>();
+            const float two_over_sqrt_pi = 1.12837916709551257390f;
+            std::vector<double> ax(3 * n, 0.0), aq(n, 0.0);
+            // one pair (i, j) with delta d, distance r and f, f', f'' of its kind
+            auto pair = [&](int64_t i, int64_t j, const float* d, float r, float f, float fp, float fpp) {
+                const float inv_r = 1 / r;
+                float u[3], dv[3], s = 0;
+                for (int c = 0; c < 3; c++) { u[c] = d[c] * inv_r; dv[c] = V[3 * i + c] - V[3 * j + c]; s += u[c] * dv[c]; }
+                const float qq = Q[i] * Q[j], cw = W[i] * Q[j] + W[j] * Q[i];
+                const float A = qq * (fpp - fp * inv_r) * s + cw * fp, Bv = qq * fp * inv_r;
+                for (int c = 0; c < 3; c++) {
+                    const float t = A * u[c] + Bv * dv[c];
+                    ax[3 * i + c] += t; ax[3 * j + c] -= t;
+                }
+                aq[i] += Q[j] * fp * s + W[j] * f;
+                aq[j] += Q[i] * fp * s + W[i] * f;
+            };
+            for (int64_t i = 0; i < pairs; i++) {
+                const int a1 = N0[i], a2 = N1[i];
+                bool include = a1 > -1 && a2 > -1;
+                for (int64_t j = 0; include && j < max_excl && E[a1 * max_excl + j] >= a2; j++)
+                    if (E[a1 * max_excl + j] == a2) include = false;
+                if (!include) continue;
+                const float r = DS[i], inv_r = 1 / r, ar = a * r, pre = k * inv_r, er = std::erfc(ar), ex_ = std::exp(-ar * ar) * two_over_sqrt_pi;
+                pair(a1, a2, DL + 3 * i, r, pre * er, -pre * (er + ar * ex_) * inv_r, 2 * pre * (er + ar * ex_ + ar * ar * ar * ex_) * inv_r * inv_r);
+            }
+            for (int64_t a1 = 0; a1 < n; a1++)
+                for (int64_t j = 0; j < max_excl && E[a1 * max_excl + j] > a1; j++) {
+                    const int a2 = E[a1 * max_excl + j];
+                    float d[3];
+                    for (int c = 0; c < 3; c++) d[c] = P[3 * a1 + c] - P[3 * a2 + c];
+                    const float r = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]), inv_r = 1 / r, ar = a * r, pre = k * inv_r;
+                    const float er = std::erf(ar), ex_ = std::exp(-ar * ar) * two_over_sqrt_pi;
+                    pair(a1, a2, d, r, -pre * er, pre * (er - ar * ex_) * inv_r, 2 * pre * (ar * ex_ + ar * ar * ar * ex_ - er) * inv_r * inv_r);
+                }
+            float* GX = gx.data_ptr<float>(); float* GQ = gq.data_ptr<float>();
+            for (int64_t i = 0; i < 3 * n; i++) GX[i] = (float)ax[i];
+            for (int64_t i = 0; i < n; i++) GQ[i] = (float)aq[i];
+        }
+        return {gx * g, gq * g, ((v * pos_deriv).sum() + (w * charge_deriv).sum()).reshape(g.sizes())};
+    }
+
+    static tensor_list backward(AutogradContext*, tensor_list) {
+        TORCH_CHECK(false, "pme_direct_twice: third derivatives are not implemented");
+        return {};
+    }
+};
+
+class PmeDirectBackwardFunction : public torch::autograd::Function<PmeDirectBackwardFunction> {
+public:
+    static tensor_list forward(AutogradContext* ctx, const Tensor& g, const Tensor& positions, const Tensor& charges, const Tensor& pos_deriv,
+                               const Tensor& charge_deriv, const Tensor& nb, const Tensor& dl, const Tensor& ds, const Tensor& ex,
+                               const std::optional<Tensor>& index_opt, double alpha, double coulomb) {
+        ctx->save_for_backward({g, positions, charges, pos_deriv, charge_deriv, nb, dl, ds, ex, index_opt.value_or(Tensor())});
+        ctx->saved_data["alpha"] = alpha;
+        ctx->saved_data["coulomb"] = coulomb;
+        return {pos_deriv * g, charge_deriv * g};
+    }
+
+    static tensor_list backward(AutogradContext* ctx, tensor_list grads) {
+        const auto s = ctx->get_saved_variables();
+        const tensor_list d = PmeDirectDoubleBackwardFunction::apply(grads[0], grads[1], s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], s[8], opt(s[9]),
+                                                                     ctx->saved_data["alpha"].toDouble(), ctx->saved_data["coulomb"].toDouble());
+        return {d[2], d[0], d[1], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+    }
+};
+
+class PmeDirectTwiceFunction : public torch::autograd::Function<PmeDirectTwiceFunction> {
+public:
+    static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& neighbors,
+                          const Tensor& deltas, const Tensor& distances, const Tensor& exclusions, const torch::Scalar& alpha,
+                          const torch::Scalar& coulomb) {
+        const PmeDirectForward f = PmeDirectFunction::run(positions, charges, neighbors, deltas, distances, exclusions, alpha, coulomb);
+        // (the index the forward pass found in the cache travels with the saved tensors: a later getNeighborPairs call replaces the cache)
+        ctx->save_for_backward({positions, charges, f.pos_deriv, f.charge_deriv, f.nb, f.dl, f.ds, f.ex, f.index});
+        ctx->saved_data["alpha"] = alpha.toDouble();
+        ctx->saved_data["coulomb"] = coulomb.toDouble();
+        return f.energy;
+    }
+
+    static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) {
+        const auto s = ctx->get_saved_variables();
+        const tensor_list d = PmeDirectBackwardFunction::apply(grad_outputs[0], s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], opt(s[8]),
+                                                               ctx->saved_data["alpha"].toDouble(), ctx->saved_data["coulomb"].toDouble());
+        return {d[0], d[1], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+    }
+};
+
 // =============================================================================================
 // PME, reciprocal-space part (reference src/pytorch/pme/pme.cpp:5, pmeCUDA.cu:102-430, pmeCPU.cpp:174-364): same op name and
 // schema.  Device: spread -> torch::fft::rfftn -> convolve (in place) -> [backward] irfftn(norm "forward") -> interpolate, the
@@ -1604,8 +1745,9 @@ Recip invert_box(const float* b) {
 }
 
 // base grid index, B-spline weights th[i][axis] and derivatives dth[i][axis] of one atom (order >= 2)
+// (d2th, optional: the second derivatives d2th[i][axis] -- the order-(n-2) weights differenced twice, order >= 4)
 void spline(const float* p_in, const float* b, const Recip& r, const int K[3], int order, int base[3], std::vector<float>& th,
-            std::vector<float>& dth) {
+            std::vector<float>& dth, std::vector<float>* d2th = nullptr) {
     float p[3] = {p_in[0], p_in[1], p_in[2]};
     for (int i = 2; i >= 0; i--) {
         const float s = std::floor(p[i] * r.m[i][i]);
@@ -1633,6 +1775,41 @@ void spline(const float* p_in, const float* b, const Recip& r, const int K[3], i
         w(order - 1) = scale * dr * w(order - 2);
         for (int j = 1; j < order - 1; j++) w(order - j - 1) = scale * ((dr + j) * w(order - j - 2) + (order - j - dr) * w(order - j - 1));
         w(0) = scale * (1 - dr) * w(0);
+        if (d2th) {
+            std::vector<float> u(order + 2, 0.0f);       // order-(n-2) weights in u[0 .. n-3], zeros behind
+            u[1] = dr;
+            u[0] = 1 - dr;
+            for (int j = 3; j <= order - 2; j++) {
+                const float div = 1.0f / (j - 1);
+                u[j - 1] = div * dr * u[j - 2];
+                for (int k = 1; k < j - 1; k++) u[j - k - 1] = div * ((dr + k) * u[j - k - 2] + (j - k - dr) * u[j - k - 1]);
+                u[0] = div * (1 - dr) * u[0];
+            }
+            for (int j = 0; j < order; j++) (*d2th)[3 * j + i] = (j >= 2 ? u[j - 2] : 0.0f) - 2.0f * (j >= 1 ? u[j - 1] : 0.0f) + u[j];
+        }
+    }
+}
+
+// the complex grid times the Ewald kernel, in place: the float expressions of pme_reciprocal's host loop, without its sums
+void convolve(c10::complex<float>* C, const int64_t K[3], const float* B, const Recip& r, double alpha, const float* XM, const float* YM,
+              const float* ZM) {
+    const int64_t zsize = K[2] / 2 + 1;
+    const float scale_factor = (float)(M_PI * B[0] * B[4] * B[8]);
+    const float exp_factor = (float)(M_PI * M_PI / (alpha * alpha));
+    for (int64_t kx = 0; kx < K[0]; kx++) {
+        const int64_t mx = kx < (K[0] + 1) / 2 ? kx : kx - K[0];
+        for (int64_t ky = 0; ky < K[1]; ky++) {
+            const int64_t my = ky < (K[1] + 1) / 2 ? ky : ky - K[1];
+            for (int64_t kz = 0; kz < zsize; kz++) {
+                const int64_t mz = kz < (K[2] + 1) / 2 ? kz : kz - K[2];
+                const int64_t idx = (kx * K[1] + ky) * zsize + kz;
+                const float mhx = mx * r.m[0][0], mhy = mx * r.m[1][0] + my * r.m[1][1];
+                const float mhz = mx * r.m[2][0] + my * r.m[2][1] + mz * r.m[2][2];
+                const float m2 = mhx * mhx + mhy * mhy + mhz * mhz;
+                const float denom = m2 * (scale_factor * XM[kx]) * YM[ky] * ZM[kz];
+                C[idx] *= idx == 0 ? 0.f : std::exp(-exp_factor * m2) / denom;
+            }
+        }
     }
 }
 
@@ -1658,9 +1835,18 @@ void box_gradient(int64_t n, const float* pos, const float* pos_deriv, const dou
 
 }  // namespace pme_recip_host
 
+// the energy, what the backward passes need, and the inputs as the kernels read them
+struct PmeRecipForward {
+    Tensor energy, q, box, recip, workspace, pos, pi, xm, ym, zm;
+    std::vector<int64_t> grid;
+    int64_t order;
+    double alpha, coulomb;
+};
+
 class PmeReciprocalFunction : public torch::autograd::Function<PmeReciprocalFunction> {
 public:
-    static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& box_vectors,
+    // the forward pass on either key, shared with pme_reciprocal_twice
+    static PmeRecipForward run(const Tensor& positions, const Tensor& charges, const Tensor& box_vectors,
                           const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz, const torch::Scalar& order,
                           const torch::Scalar& alpha, const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli,
                           const Tensor& zmoduli, bool box_grad) {
@@ -1770,30 +1956,30 @@ public:
             energy = torch::full({}, (float)(0.5 * e), opts);
             if (box_grad) pi = torch::tensor(std::vector<double>(PS, PS + 6), opts.dtype(torch::kFloat64));
         }
-        // (the device path keeps the splines in the workspace and does not need the positions again, unless for the box gradient)
-        const Tensor none = torch::empty({0}, opts);
-        if (box_grad)
-            ctx->save_for_backward({q, box, recip, workspace.defined() ? workspace : none, pos, pi});
-        else
-            ctx->save_for_backward({q, box, recip, workspace.defined() ? workspace : none, positions.is_cuda() ? none : pos});
-        ctx->saved_data["grid"] = std::vector<int64_t>{K[0], K[1], K[2]};
-        ctx->saved_data["order"] = pme_order;
-        ctx->saved_data["coulomb"] = k;
-        return energy;
+        return {energy, q, box, recip, workspace, pos, pi, xm, ym, zm, std::vector<int64_t>{K[0], K[1], K[2]}, pme_order, a, k};
     }
 
-    static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) {
-        TORCH_CHECK(!torch::GradMode::is_enabled(),
-                    "pme_reciprocal: second derivatives are not implemented (backward was called with create_graph=True)");
-        const auto saved = ctx->get_saved_variables();
-        const Tensor q = saved[0], box = saved[1], recip = saved[2], workspace = saved[3], pos = saved[4];
-        const std::vector<int64_t> K = ctx->saved_data["grid"].toIntVector();
-        const int64_t pme_order = ctx->saved_data["order"].toInt();
-        const double k = ctx->saved_data["coulomb"].toDouble();
+    static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& box_vectors,
+                          const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz, const torch::Scalar& order,
+                          const torch::Scalar& alpha, const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli,
+                          const Tensor& zmoduli, bool box_grad) {
+        const PmeRecipForward f = run(positions, charges, box_vectors, gridx, gridy, gridz, order, alpha, coulomb, xmoduli, ymoduli, zmoduli, box_grad);
+        // (the device path keeps the splines in the workspace and does not need the positions again, unless for the box gradient)
+        const Tensor none = torch::empty({0}, positions.options());
+        if (box_grad)
+            ctx->save_for_backward({f.q, f.box, f.recip, f.workspace.defined() ? f.workspace : none, f.pos, f.pi});
+        else
+            ctx->save_for_backward({f.q, f.box, f.recip, f.workspace.defined() ? f.workspace : none, positions.is_cuda() ? none : f.pos});
+        ctx->saved_data["grid"] = f.grid;
+        ctx->saved_data["order"] = f.order;
+        ctx->saved_data["coulomb"] = f.coulomb;
+        return f.energy;
+    }
+
+    // dE/dpositions, dE/dcharges (unscaled) from the potential grid: the first-order backward on either key
+    static void interpolate(const Tensor& grid, const Tensor& q, const Tensor& box, const Tensor& workspace, const Tensor& pos,
+                            const std::vector<int64_t>& K, int64_t pme_order, double k, Tensor& pos_deriv, Tensor& charge_deriv) {
         const int64_t n = q.size(0);
-        const Tensor grid = torch::fft::irfftn(recip, torch::IntArrayRef(K), c10::nullopt, "forward").contiguous();
-        const auto opts = q.options();
-        Tensor pos_deriv = torch::empty({n, 3}, opts), charge_deriv = torch::empty({n}, opts);
         if (q.is_cuda()) {
             c10::hip::HIPGuard guard(q.device().index());
             if (nnpops_pme_reciprocal_interpolate((int)n, (int)K[0], (int)K[1], (int)K[2], (int)pme_order, q.data_ptr<float>(),
@@ -1835,6 +2021,21 @@ public:
                 CD[atom] = dq * sqrt_k;
             }
         }
+    }
+
+    static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) {
+        TORCH_CHECK(!torch::GradMode::is_enabled(),
+                    "pme_reciprocal: second derivatives are not implemented (backward was called with create_graph=True)");
+        const auto saved = ctx->get_saved_variables();
+        const Tensor q = saved[0], box = saved[1], recip = saved[2], workspace = saved[3], pos = saved[4];
+        const std::vector<int64_t> K = ctx->saved_data["grid"].toIntVector();
+        const int64_t pme_order = ctx->saved_data["order"].toInt();
+        const double k = ctx->saved_data["coulomb"].toDouble();
+        const int64_t n = q.size(0);
+        const Tensor grid = torch::fft::irfftn(recip, torch::IntArrayRef(K), c10::nullopt, "forward").contiguous();
+        const auto opts = q.options();
+        Tensor pos_deriv = torch::empty({n, 3}, opts), charge_deriv = torch::empty({n}, opts);
+        interpolate(grid, q, box, workspace, pos, K, pme_order, k, pos_deriv, charge_deriv);
         Tensor grad_box;
         if (saved.size() > 5) {
             const Tensor pi = saved[5];
@@ -1856,6 +2057,185 @@ public:
     }
 };
 
+// ---------------------------------------------------------------------------------------------
+// pme_reciprocal_twice: pme_reciprocal's forward and first-order backward (PmeReciprocalFunction::run / ::interpolate, the same kernels
+// and bits), recorded so that the backward pass is itself differentiable with respect to positions and charges.
+//     PmeRecipBackwardFunction        g -> g P, g C; keeps the potential grid phi (the irfftn it needed anyway) for the next pass
+//     PmeRecipDoubleBackwardFunction  (v, w) -> spread of Q' -> rfftn -> the existing convolution -> irfftn = phi' -> two-grid
+//                                     interpolation (pme_recip.hip); plain loops on the host
+// No box gradient (the default ops have it) and no third derivative: both raise.
+// ---------------------------------------------------------------------------------------------
+class PmeRecipDoubleBackwardFunction : public torch::autograd::Function<PmeRecipDoubleBackwardFunction> {
+public:
+    static tensor_list forward(AutogradContext*, const Tensor& v_in, const Tensor& w_in, const Tensor& g, const Tensor& positions,
+                               const Tensor& charges, const Tensor& box, const Tensor& workspace, const Tensor& xm, const Tensor& ym,
+                               const Tensor& zm, const Tensor& phi, const Tensor& pos_deriv, const Tensor& charge_deriv,
+                               std::vector<int64_t> K, int64_t pme_order, double alpha, double k) {
+        const Tensor v = v_in.contiguous(), w = w_in.contiguous(), pos = positions.contiguous(), q = charges.contiguous();
+        const int64_t n = q.size(0);
+        const auto opts = q.options();
+        Tensor gx = torch::empty({n, 3}, opts), gq = torch::empty({n}, opts);
+        if (q.is_cuda()) {
+            c10::hip::HIPGuard guard(q.device().index());
+            void* stream = current_stream(q.device());
+            const int kx = (int)K[0], ky = (int)K[1], kz = (int)K[2], o = (int)pme_order;
+            Tensor second = torch::empty({nnpops_pme_reciprocal_second_workspace_bytes((int)n, kx, ky, kz, o)}, opts.dtype(torch::kUInt8));
+            Tensor real = torch::empty({K[0], K[1], K[2]}, opts);
+            if (nnpops_pme_reciprocal_spread_directional((int)n, kx, ky, kz, o, pos.data_ptr<float>(), q.data_ptr<float>(), box.data_ptr<float>(),
+                                                         (float)k, v.data_ptr<float>(), w.data_ptr<float>(), real.data_ptr<float>(),
+                                                         workspace.data_ptr(), second.data_ptr(), stream) != NNPOPS_OK)
+                raise_last("pme::pme_reciprocal_twice (double backward)");
+            Tensor recip = torch::fft::rfftn(real).contiguous();
+            Tensor unused = torch::empty({}, opts);
+            if (nnpops_pme_reciprocal_convolve((int)n, kx, ky, kz, o, box.data_ptr<float>(), (float)alpha, xm.data_ptr<float>(), ym.data_ptr<float>(),
+                                               zm.data_ptr<float>(), recip.data_ptr(), unused.data_ptr<float>(), workspace.data_ptr(),
+                                               stream) != NNPOPS_OK)
+                raise_last("pme::pme_reciprocal_twice (double backward)");
+            const Tensor phi2 = torch::fft::irfftn(recip, torch::IntArrayRef(K), c10::nullopt, "forward").contiguous();
+            if (nnpops_pme_reciprocal_interpolate_second((int)n, kx, ky, kz, o, q.data_ptr<float>(), box.data_ptr<float>(), (float)k,
+                                                         w.data_ptr<float>(), phi.data_ptr<float>(), phi2.data_ptr<float>(), gx.data_ptr<float>(),
+                                                         gq.data_ptr<float>(), workspace.data_ptr(), second.data_ptr(), stream) != NNPOPS_OK)
+                raise_last("pme::pme_reciprocal_twice (double backward)");
+        } else {
+            using namespace pme_recip_host;
+            const float* B = box.data_ptr<float>();
+            const Recip r = invert_box(B);
+            const int Ki[3] = {(int)K[0], (int)K[1], (int)K[2]};
+            const int64_t Kl[3] = {K[0], K[1], K[2]};
+            const int od = (int)pme_order;
+            const float sqrt_k = (float)std::sqrt(k);
+            const float* P = pos.data_ptr<float>(); const float* Q = q.data_ptr<float>();
+            const float* V = v.data_ptr<float>(); const float* W = w.data_ptr<float>();
+            std::vector<float> th(3 * od), dth(3 * od), d2th(3 * od);
+            // s_a = K_a (v . B^-1 column a): the direction in grid units
+            auto direction = [&](int64_t atom, float (&s)[3]) {
+                for (int a = 0; a < 3; a++) s[a] = Ki[a] * (V[3 * atom] * r.m[0][a] + V[3 * atom + 1] * r.m[1][a] + V[3 * atom + 2] * r.m[2][a]);
+            };
+            Tensor real = torch::zeros({K[0], K[1], K[2]}, opts);
+            float* G2 = real.data_ptr<float>();
+            for (int64_t atom = 0; atom < n; atom++) {
+                int b0[3];
+                float s[3];
+                spline(P + 3 * atom, B, r, Ki, od, b0, th, dth);
+                direction(atom, s);
+                const float qs = Q[atom] * sqrt_k, ws = W[atom] * sqrt_k;
+                for (int ix = 0; ix < od; ix++) {
+                    const int64_t xi = (b0[0] + ix) % Ki[0];
+                    const float ax = ws * th[3 * ix] + qs * s[0] * dth[3 * ix], qx = qs * th[3 * ix];
+                    for (int iy = 0; iy < od; iy++) {
+                        const int64_t yi = (b0[1] + iy) % Ki[1];
+                        const float ty = th[3 * iy + 1], dy = s[1] * dth[3 * iy + 1];
+                        for (int iz = 0; iz < od; iz++) {
+                            const float tz = th[3 * iz + 2], dz = s[2] * dth[3 * iz + 2];
+                            G2[(xi * K[1] + yi) * K[2] + (b0[2] + iz) % Ki[2]] += ax * ty * tz + qx * (dy * tz + ty * dz);
+                        }
+                    }
+                }
+            }
+            Tensor recip = torch::fft::rfftn(real).contiguous();
+            convolve(reinterpret_cast<c10::complex<float>*>(recip.data_ptr()), Kl, B, r, alpha, xm.data_ptr<float>(), ym.data_ptr<float>(),
+                     zm.data_ptr<float>());
+            const Tensor phi2 = torch::fft::irfftn(recip, torch::IntArrayRef(K), c10::nullopt, "forward").contiguous();
+            const float* G = phi.data_ptr<float>(); const float* H = phi2.data_ptr<float>();
+            float* GX = gx.data_ptr<float>(); float* GQ = gq.data_ptr<float>();
+            for (int64_t atom = 0; atom < n; atom++) {
+                int b0[3];
+                float s[3];
+                spline(P + 3 * atom, B, r, Ki, od, b0, th, dth, &d2th);
+                direction(atom, s);
+                double h[3] = {0, 0, 0}, hh[6] = {0, 0, 0, 0, 0, 0}, a2 = 0, g2[3] = {0, 0, 0};      // hh: xx, yy, zz, xy, xz, yz
+                for (int ix = 0; ix < od; ix++) {
+                    const int64_t xi = (b0[0] + ix) % Ki[0];
+                    const double tx = th[3 * ix], dx = dth[3 * ix], cx = d2th[3 * ix];
+                    for (int iy = 0; iy < od; iy++) {
+                        const int64_t yi = (b0[1] + iy) % Ki[1];
+                        const double ty = th[3 * iy + 1], dy = dth[3 * iy + 1], cy = d2th[3 * iy + 1];
+                        for (int iz = 0; iz < od; iz++) {
+                            const int64_t at = (xi * K[1] + yi) * K[2] + (b0[2] + iz) % Ki[2];
+                            const double tz = th[3 * iz + 2], dz = dth[3 * iz + 2], cz = d2th[3 * iz + 2];
+                            const double f = G[at], f2 = H[at];
+                            h[0] += dx * ty * tz * f; h[1] += tx * dy * tz * f; h[2] += tx * ty * dz * f;
+                            hh[0] += cx * ty * tz * f; hh[1] += tx * cy * tz * f; hh[2] += tx * ty * cz * f;
+                            hh[3] += dx * dy * tz * f; hh[4] += dx * ty * dz * f; hh[5] += tx * dy * dz * f;
+                            a2 += tx * ty * tz * f2;
+                            g2[0] += dx * ty * tz * f2; g2[1] += tx * dy * tz * f2; g2[2] += tx * ty * dz * f2;
+                        }
+                    }
+                }
+                const double qs = (double)Q[atom] * sqrt_k, ws = (double)W[atom] * sqrt_k;
+                GQ[atom] = (float)(sqrt_k * (a2 + s[0] * h[0] + s[1] * h[1] + s[2] * h[2]));
+                const double fx = (qs * (g2[0] + s[0] * hh[0] + s[1] * hh[3] + s[2] * hh[4]) + ws * h[0]) * Ki[0];
+                const double fy = (qs * (g2[1] + s[0] * hh[3] + s[1] * hh[1] + s[2] * hh[5]) + ws * h[1]) * Ki[1];
+                const double fz = (qs * (g2[2] + s[0] * hh[4] + s[1] * hh[5] + s[2] * hh[2]) + ws * h[2]) * Ki[2];
+                GX[3 * atom] = (float)(fx * r.m[0][0]);
+                GX[3 * atom + 1] = (float)(fx * r.m[1][0] + fy * r.m[1][1]);
+                GX[3 * atom + 2] = (float)(fx * r.m[2][0] + fy * r.m[2][1] + fz * r.m[2][2]);
+            }
+        }
+        return {gx * g, gq * g, ((v * pos_deriv).sum() + (w * charge_deriv).sum()).reshape(g.sizes())};
+    }
+
+    static tensor_list backward(AutogradContext*, tensor_list) {
+        TORCH_CHECK(false, "pme_reciprocal_twice: third derivatives are not implemented");
+        return {};
+    }
+};
+
+class PmeRecipBackwardFunction : public torch::autograd::Function<PmeRecipBackwardFunction> {
+public:
+    static tensor_list forward(AutogradContext* ctx, const Tensor& g, const Tensor& positions, const Tensor& charges, const Tensor& box,
+                               const Tensor& recip, const Tensor& workspace, const Tensor& xm, const Tensor& ym, const Tensor& zm,
+                               std::vector<int64_t> K, int64_t pme_order, double alpha, double k) {
+        const Tensor pos = positions.contiguous(), q = charges.contiguous();
+        const int64_t n = q.size(0);
+        const Tensor phi = torch::fft::irfftn(recip, torch::IntArrayRef(K), c10::nullopt, "forward").contiguous();
+        Tensor pos_deriv = torch::empty({n, 3}, q.options()), charge_deriv = torch::empty({n}, q.options());
+        PmeReciprocalFunction::interpolate(phi, q, box, workspace, pos, K, pme_order, k, pos_deriv, charge_deriv);
+        ctx->save_for_backward({g, positions, charges, box, workspace, xm, ym, zm, phi, pos_deriv, charge_deriv});
+        ctx->saved_data["grid"] = K;
+        ctx->saved_data["order"] = pme_order;
+        ctx->saved_data["alpha"] = alpha;
+        ctx->saved_data["coulomb"] = k;
+        return {pos_deriv * g, charge_deriv * g};
+    }
+
+    static tensor_list backward(AutogradContext* ctx, tensor_list grads) {
+        const auto s = ctx->get_saved_variables();
+        const tensor_list d = PmeRecipDoubleBackwardFunction::apply(grads[0], grads[1], s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], s[8], s[9], s[10],
+                                                                    ctx->saved_data["grid"].toIntVector(), ctx->saved_data["order"].toInt(),
+                                                                    ctx->saved_data["alpha"].toDouble(), ctx->saved_data["coulomb"].toDouble());
+        return {d[2], d[0], d[1], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+    }
+};
+
+class PmeReciprocalTwiceFunction : public torch::autograd::Function<PmeReciprocalTwiceFunction> {
+public:
+    static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& box_vectors,
+                          const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz, const torch::Scalar& order,
+                          const torch::Scalar& alpha, const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli,
+                          const Tensor& zmoduli) {
+        TORCH_CHECK(order.toLong() >= 4, "pme_reciprocal_twice: order must be at least 4 (below that the second derivatives of the B-spline "
+                    "weights are not continuous), got ", order.toLong());
+        const PmeRecipForward f = PmeReciprocalFunction::run(positions, charges, box_vectors, gridx, gridy, gridz, order, alpha, coulomb, xmoduli,
+                                                             ymoduli, zmoduli, false);
+        const Tensor none = torch::empty({0}, positions.options());
+        ctx->save_for_backward({positions, charges, f.box, f.recip, f.workspace.defined() ? f.workspace : none, f.xm, f.ym, f.zm});
+        ctx->saved_data["grid"] = f.grid;
+        ctx->saved_data["order"] = f.order;
+        ctx->saved_data["alpha"] = f.alpha;
+        ctx->saved_data["coulomb"] = f.coulomb;
+        return f.energy;
+    }
+
+    static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) {
+        const auto s = ctx->get_saved_variables();
+        const tensor_list d = PmeRecipBackwardFunction::apply(grad_outputs[0], s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7],
+                                                              ctx->saved_data["grid"].toIntVector(), ctx->saved_data["order"].toInt(),
+                                                              ctx->saved_data["alpha"].toDouble(), ctx->saved_data["coulomb"].toDouble());
+        return {d[0], d[1], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+    }
+};
+
 TORCH_LIBRARY(pme, m) {
     m.def("pme_direct(Tensor positions, Tensor charges, Tensor neighbors, Tensor deltas, Tensor distances, Tensor exclusions, "
           "Scalar alpha, Scalar coulomb) -> Tensor");
@@ -1863,6 +2243,11 @@ TORCH_LIBRARY(pme, m) {
           "Scalar order, Scalar alpha, Scalar coulomb, Tensor xmoduli, Tensor ymoduli, Tensor zmoduli) -> Tensor");
     m.def("pme_direct_box(Tensor positions, Tensor charges, Tensor neighbors, Tensor deltas, Tensor distances, Tensor exclusions, "
           "Tensor box_vectors, Scalar alpha, Scalar coulomb) -> Tensor");
+    // the twice-differentiable variants (force matching): the schemas of pme_direct and pme_reciprocal
+    m.def("pme_direct_twice(Tensor positions, Tensor charges, Tensor neighbors, Tensor deltas, Tensor distances, Tensor exclusions, "
+          "Scalar alpha, Scalar coulomb) -> Tensor");
+    m.def("pme_reciprocal_twice(Tensor positions, Tensor charges, Tensor box_vectors, Scalar gridx, Scalar gridy, Scalar gridz, "
+          "Scalar order, Scalar alpha, Scalar coulomb, Tensor xmoduli, Tensor ymoduli, Tensor zmoduli) -> Tensor");
 }
 
 Tensor pme_direct_box_entry(const Tensor& positions, const Tensor& charges, const Tensor& neighbors, const Tensor& deltas,
@@ -1881,6 +2266,22 @@ Tensor pme_reciprocal_entry(const Tensor& positions, const Tensor& charges, cons
                                         zmoduli, box_grad);
 }
 
+Tensor pme_direct_twice_entry(const Tensor& positions, const Tensor& charges, const Tensor& neighbors, const Tensor& deltas,
+                              const Tensor& distances, const Tensor& exclusions, const torch::Scalar& alpha, const torch::Scalar& coulomb) {
+    return PmeDirectTwiceFunction::apply(positions, charges, neighbors, deltas, distances, exclusions, alpha, coulomb);
+}
+
+Tensor pme_reciprocal_twice_entry(const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const torch::Scalar& gridx,
+                                  const torch::Scalar& gridy, const torch::Scalar& gridz, const torch::Scalar& order,
+                                  const torch::Scalar& alpha, const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli,
+                                  const Tensor& zmoduli) {
+    TORCH_CHECK(!(torch::GradMode::is_enabled() && box_vectors.requires_grad()),
+                "pme_reciprocal_twice: box gradients need the default ops (pme_reciprocal; PME without twice_differentiable=True): the "
+                "twice-differentiable ops return no box gradient");
+    return PmeReciprocalTwiceFunction::apply(positions, charges, box_vectors, gridx, gridy, gridz, order, alpha, coulomb, xmoduli, ymoduli,
+                                             zmoduli);
+}
+
 Tensor pme_direct_entry(const Tensor& positions, const Tensor& charges, const Tensor& neighbors, const Tensor& deltas,
                         const Tensor& distances, const Tensor& exclusions, const torch::Scalar& alpha, const torch::Scalar& coulomb) {
     return PmeDirectFunction::apply(positions, charges, neighbors, deltas, distances, exclusions, alpha, coulomb);
@@ -1890,11 +2291,15 @@ TORCH_LIBRARY_IMPL(pme, AutogradCUDA, m) {
     m.impl("pme_direct", pme_direct_entry);
     m.impl("pme_reciprocal", pme_reciprocal_entry);
     m.impl("pme_direct_box", pme_direct_box_entry);
+    m.impl("pme_direct_twice", pme_direct_twice_entry);
+    m.impl("pme_reciprocal_twice", pme_reciprocal_twice_entry);
 }
 TORCH_LIBRARY_IMPL(pme, AutogradCPU, m) {
     m.impl("pme_direct", pme_direct_entry);
     m.impl("pme_reciprocal", pme_reciprocal_entry);
     m.impl("pme_direct_box", pme_direct_box_entry);
+    m.impl("pme_direct_twice", pme_direct_twice_entry);
+    m.impl("pme_reciprocal_twice", pme_reciprocal_twice_entry);
 }
 // ... and the backend keys themselves (the reference registers its autograd Function under CPU, pmeCPU.cpp:381): below
 // autograd -- torch.inference_mode(), AutoDispatchBelowAutograd -- the same entry runs without recording a graph
@@ -1902,11 +2307,15 @@ TORCH_LIBRARY_IMPL(pme, CUDA, m) {
     m.impl("pme_direct", pme_direct_entry);
     m.impl("pme_reciprocal", pme_reciprocal_entry);
     m.impl("pme_direct_box", pme_direct_box_entry);
+    m.impl("pme_direct_twice", pme_direct_twice_entry);
+    m.impl("pme_reciprocal_twice", pme_reciprocal_twice_entry);
 }
 TORCH_LIBRARY_IMPL(pme, CPU, m) {
     m.impl("pme_direct", pme_direct_entry);
     m.impl("pme_reciprocal", pme_reciprocal_entry);
     m.impl("pme_direct_box", pme_direct_box_entry);
+    m.impl("pme_direct_twice", pme_direct_twice_entry);
+    m.impl("pme_reciprocal_twice", pme_reciprocal_twice_entry);
 }
 
 // =============================================================================================

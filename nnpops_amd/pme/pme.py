@@ -6,7 +6,8 @@ Coulomb's constant sets the units), same exclusion semantics (only the un-wrappe
 the erf() part that reciprocal space cannot leave out is subtracted here).  ``compute_direct`` = getNeighborPairs +
 ``torch.ops.pme.pme_direct``, differentiable w.r.t. positions and charges (first derivatives only).  When ``box_vectors``
 requires a gradient (and grad mode is on) it calls ``torch.ops.pme.pme_direct_box`` instead: the same forward pass, bit for
-bit, and dE/dbox as well.
+bit, and dE/dbox as well.  Second derivatives with respect to positions and charges are an opt-in,
+``PME(..., twice_differentiable=True)``.
 
 The reciprocal-space term (charge spreading onto a grid + 3-D FFTs, src/pytorch/pme/pmeCUDA.cu:102-430) is
 ``torch.ops.pme.pme_reciprocal``: deterministic HIP passes around torch's FFTs (nnpops_amd/csrc/pme_recip.hip) and a CPU key.
@@ -46,6 +47,10 @@ def bspline_moduli(size: int, order: int) -> torch.Tensor:
     return torch.tensor(mod, dtype=torch.float32)
 
 
+_TWICE_BOX_MESSAGE = ("PME(..., twice_differentiable=True): box gradients need the default ops (PME without twice_differentiable); the "
+                      "twice-differentiable ops return no box gradient")
+
+
 class PME:
     """Particle Mesh Ewald (the reference's class, src/pytorch/pme/pme.py).  The direct- and reciprocal-space terms are not
     physically meaningful on their own, only their sum.
@@ -56,10 +61,16 @@ class PME:
 
     ``reciprocal`` (keyword only, default False): with True the constructor computes the B-spline moduli and
     ``compute_reciprocal`` works as the reference's; with False ``compute_reciprocal`` raises, as this class always did.  The
-    default will become True in a later change."""
+    default will become True in a later change.
+
+    ``twice_differentiable`` (keyword only, default False): with True ``compute_direct`` and ``compute_reciprocal`` call
+    ``torch.ops.pme.pme_direct_twice`` / ``pme_reciprocal_twice``: the same forward and first-order passes, bit for bit, whose
+    backward can itself be differentiated with respect to positions and charges (``create_graph=True``: force matching, Hessian-
+    vector products).  These ops return no box gradient -- a box that requires a gradient raises -- and the
+    reciprocal term then needs ``order >= 4``.  With the default False second derivatives are refused, as before."""
 
     def __init__(self, gridx: int, gridy: int, gridz: int, order: int, alpha: float, coulomb: float, exclusions: torch.Tensor, *,
-                 reciprocal: bool = False):
+                 reciprocal: bool = False, twice_differentiable: bool = False):
         # the reference's argument checks (pme.py:75-85)
         if gridx < 1 or gridy < 1 or gridz < 1:
             raise ValueError('The grid dimensions must be positive')
@@ -91,6 +102,7 @@ class PME:
         # rows sorted in descending order: the kernels stop scanning a row at the first entry below the partner (pme.py:93)
         self.exclusions, _ = torch.sort(exclusions.to(torch.int32), descending=True)
         self.reciprocal = bool(reciprocal)
+        self.twice_differentiable = bool(twice_differentiable)
         if self.reciprocal:
             self.moduli = [bspline_moduli(k, order) for k in (gridx, gridy, gridz)]
 
@@ -111,6 +123,11 @@ class PME:
             raise ValueError('cutoff must be positive')
         neighbors, deltas, distances, _ = getNeighborPairs(positions, cutoff, max_num_pairs, box_vectors)
         self.exclusions = self.exclusions.to(positions.device)
+        if self.twice_differentiable:
+            if box_vectors.requires_grad and torch.is_grad_enabled():
+                raise RuntimeError(_TWICE_BOX_MESSAGE)
+            return torch.ops.pme.pme_direct_twice(positions, charges, neighbors, deltas, distances, self.exclusions, self.alpha,
+                                                  self.coulomb)
         if box_vectors.requires_grad and torch.is_grad_enabled():
             return torch.ops.pme.pme_direct_box(positions, charges, neighbors, deltas, distances, self.exclusions, box_vectors,
                                                 self.alpha, self.coulomb)
@@ -133,6 +150,12 @@ class PME:
         for i in range(3):
             self.moduli[i] = self.moduli[i].to(positions.device)
         self_energy = -torch.sum(charges ** 2) * (self.coulomb * self.alpha / math.sqrt(math.pi))
+        if self.twice_differentiable:
+            if box_vectors.requires_grad and torch.is_grad_enabled():
+                raise RuntimeError(_TWICE_BOX_MESSAGE)
+            return self_energy + torch.ops.pme.pme_reciprocal_twice(positions, charges, box_vectors, self.gridx, self.gridy, self.gridz,
+                                                                    self.order, self.alpha, self.coulomb, self.moduli[0],
+                                                                    self.moduli[1], self.moduli[2])
         return self_energy + torch.ops.pme.pme_reciprocal(positions, charges, box_vectors, self.gridx, self.gridy, self.gridz,
                                                           self.order, self.alpha, self.coulomb, self.moduli[0], self.moduli[1],
                                                           self.moduli[2])
