@@ -121,7 +121,13 @@ int nnpops_ani_read_overflow(nnpops_ani_t h, int32_t* value);
  * chunked | mfma; backward= kernel number; generic= the function list does not factor; uniform= one eta and one zeta; grid= eight
  * radial factors on equally spaced shifts (taken by recurrence); literal= the constants are the published ANI-2x set and the
  * forward kernels carry them as literals; dynamic_quads, fused_build, cap, cap_angular, chunk, classes, cells: state after the last
- * compute() / check().  Writes at most `capacity` bytes including the terminator.  Additive. */
+ * compute() / check().  What the last backprop() launched (host-side records, no device work): bwd_mode= 0 the first-generation
+ * angular backward (what runs when the pair matrix of the records does not fit the LDS, or on request), 1-4 the pair-matrix
+ * kernels (1 / 3 one / two waves per atom with 16-byte gradient loads, 2 / 4 the same with the gradient row staged in LDS; where
+ * the launch ran by class, the top class's mode); radial_bwd= lanes | rows (a lane per neighbour, or the first-generation row
+ * kernel); tile= and compact= the pair-matrix edge and the compact-layout flag mode 0 was launched with (-1 when it did not run).
+ * Before any backprop(): bwd_mode=-1 radial_bwd=none tile=-1 compact=-1.  The line stays below 512 bytes.
+ * Writes at most `capacity` bytes including the terminator.  Additive. */
 int nnpops_ani_describe(nnpops_ani_t h, char* text, int capacity);
 /* The same check in two halves for callers that have more work to queue behind compute(): _begin (right after compute) queues
  * one single-thread launch that publishes the overflow word and a stamp into pinned host memory and returns 1 -- or 0 when the check cannot be deferred (first calls, while

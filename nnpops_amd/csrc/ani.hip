@@ -68,6 +68,11 @@ struct nnpops_ani {
                                     // -1 where every backward launch runs two waves per atom (dense systems), 0 / 1 forced ($NNPOPS_ANI_SCATTER)
     bool scatter_now = false;       // ... decided by backprop() for the call in progress
     bool last_fused_build = false;  // the last compute() ran the one-launch build + forward (what describe() reports)
+    // what the last backprop() launched (host-side records for describe(); -1: no backprop() yet / that kernel did not run)
+    int last_bwd_mode = -1;         // 0: the round-1 ani_angular_backward, 1-4: the pair kernels (with classes: the top class's mode)
+    int last_radial_lanes = -1;     // 1: a lane per neighbour (ani_radial_bwd.h), 0: the round-1 ani_radial_backward (rows)
+    int last_tile = -1;             // pair-matrix tile and compact_bwd flag the round-1 angular backward was launched with
+    int last_compact = -1;
     bool fine_grid = true;          // cell grid of half-cutoff cells where it fits (celllist.h: decide_grid)
     bool fwd_row_via_lds = true;    // the angular row leaves as whole-wave stores from an LDS copy
     int fwd_occ = 7;                // A/B: register budget of the forward kernel (waves per SIMD)
@@ -360,6 +365,7 @@ int launch_angular(nnpops_ani* h, bool forward, const float* grad_or_null, float
         //  with two waves everywhere; the 153-triple atoms of a liquid stay with one wave, 15.8 against 25 us)
         if (mode == 1 && !h->backward_forced && (cl.two_waves || h->scatter_now || ang_bwd_pair_lds_bytes<NFRP, NFZP>(tile, h->hp.NB, false) > 16 * 1024)) mode = 3;
         if (!vec_ok && (mode == 1 || mode == 3)) mode++;
+        if (c == 0) h->last_bwd_mode = mode;                   // (describe(): the whole launch, or the top class)
         const bool glds = mode == 2 || mode == 4;
         const size_t lb = (ang_bwd_pair_lds_bytes<NFRP, NFZP>(tile, h->hp.NB, glds) + 15) & ~(size_t)15;
         void (*k)(const AniParams*, const AngularConsts, int, int, int, const float4*, const float4*, const int*, const int*, const int*, const float*, int,
@@ -410,6 +416,9 @@ int launch_angular(nnpops_ani* h, bool forward, const float* grad_or_null, float
         }
     } else {
         auto k = ani_angular_backward<TA, NFRP, NFZP>;
+        h->last_bwd_mode = 0;
+        h->last_tile = h->tile;
+        h->last_compact = (int)h->compact_bwd;
         if (lds_group > 64 * 1024) NNPOPS_HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_group));
         hipLaunchKernelGGL(k, grid, block, lds_group, h->stream, h->d_params, h->cap, h->cap_angular, h->tile, h->d_recA,
                            h->d_recB, h->d_tri, h->d_cnt_a, h->d_cnt_ro, grad_or_null, h->ld_angular, h->d_leg_force, h->d_centre_force,
@@ -448,6 +457,7 @@ int launch_generic(nnpops_ani* h, bool forward, const float* g, float* out, cons
         const size_t lb = (ang_bwd_pair_lds_bytes<4, 4>(h->cap_angular, h->hp.NB, false) + 15) & ~(size_t)15;
         if (lb > 160 * 1024) return fail(NNPOPS_ERR_UNSUPPORTED, "generic angular backward needs %zu bytes of LDS (cap_angular %d)", lb, h->cap_angular);
         auto k = ani_angular_backward_pair<TA, 4, 4, 4, 1, false, true>;
+        h->last_bwd_mode = 1;                                  // (the pair kernel, one wave per atom, gradients through the L1)
         if (lb > 64 * 1024) NNPOPS_HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
         hipLaunchKernelGGL(k, dim3(N), dim3(64), lb, sp.stream, h->d_params, h->ac, h->cap, h->cap_angular, h->cap_angular, h->d_recA, h->d_recB, h->d_tri,
                            h->d_cnt_a, h->d_cnt_ro, g, h->ld_angular, h->d_leg_force, h->d_centre_force, h->d_ids, nullptr, 0, h->hp.NB, (int)lb, nullptr, 0, N, 0);
@@ -963,6 +973,7 @@ int nnpops_ani_backprop_strided(nnpops_ani_t h, const float* radial_deriv, int r
     int rc = fork_streams(h, spans, nspans);
     if (rc != NNPOPS_OK) return rc;
     h->backprop_stamp = h->backprop_stamp >= 0x3fffffff ? 1 : h->backprop_stamp + 1;      // (as a float's bits: never a NaN pattern, never 0)
+    h->last_bwd_mode = h->last_tile = h->last_compact = -1;   // (set again where the launches are made)
     {   // Leg forces straight into the receiving atoms' rows?  Only where EVERY launch of the angular backward runs two waves per atom
         // (the second wave does the look-up under the first one's row sums) and the radial backward is the kernel that reads such rows:
         // dense systems (the atoms average 200 triples or more, check()), the pair-matrix kernels with 16-byte gradient loads.
@@ -987,6 +998,7 @@ int nnpops_ani_backprop_strided(nnpops_ani_t h, const float* radial_deriv, int r
         KernelTimer timer(h, NNPOPS_ANI_K_RADIAL_BWD, sp.stream);
         const int nr4 = h->hp.nR / 4;
         const bool lanes = radial_lanes(h, radial_deriv);
+        h->last_radial_lanes = lanes ? 1 : 0;
         if (lanes) {
             // a lane per neighbour: only this atom's own gradient row is staged in LDS
             const int lw = (int)(((size_t)h->hp.S * h->hp.nR * sizeof(float) + 15) & ~(size_t)15);
@@ -1122,11 +1134,20 @@ int nnpops_ani_check(nnpops_ani_t h, int* max_radial_neighbors, int* max_angular
     // atoms): angular forward 70 -> 46 us, backward 48 -> 38; 10 000-atom liquid: 19.2 -> 17.6 and 17.6 -> 15.7 us.
     std::vector<int> counts;
     const bool want_order = (!h->last_used_cells || h->lpt == 2) && h->hp.N >= 256 && h->lpt;
-    if (want_order) {
+    // (the counts also decide kernels -- two waves per atom, scattered leg forces, the forward's chunk: that must not depend on the
+    //  schedule switch, so $NNPOPS_ANI_LPT=0 / 1 fetch them as well and only skip the order)
+    const bool want_counts = want_order || h->hp.N >= 256;
+    if (want_counts) {
         counts.resize((size_t)h->hp.N);
         NNPOPS_HIP_TRY(hipMemcpyAsync(counts.data(), h->d_cnt_a, sizeof(int) * counts.size(), hipMemcpyDeviceToHost, h->stream));
     }
     NNPOPS_HIP_TRY(hipStreamSynchronize(h->stream));
+    if (want_counts) {
+        double triples = 0;
+        for (int cnt : counts) triples += 0.5 * cnt * (cnt - 1);
+        h->mean_triples = triples / std::max<size_t>(counts.size(), 1);
+        h->bwd_two_waves = h->mean_triples >= 200.0;
+    }
     if (want_order) {
         std::vector<int> perm(counts.size());
         for (size_t a = 0; a < perm.size(); a++) perm[a] = (int)a;
@@ -1138,12 +1159,6 @@ int nnpops_ani_check(nnpops_ani_t h, int* max_radial_neighbors, int* max_angular
         // the classes are rebuilt here.  Records of 32 slots: one class.
         std::vector<unsigned char> tile_of(perm.size(), 255);
         h->bwd_classes.clear();
-        {
-            double triples = 0;
-            for (int cnt : counts) triples += 0.5 * cnt * (cnt - 1);
-            h->mean_triples = triples / std::max<size_t>(counts.size(), 1);
-            h->bwd_two_waves = h->mean_triples >= 200.0;
-        }
         // (classes pay when every launch can fill the chip: the 61 199-atom conformer batch 304 -> 246 us; on a 7 600-atom block of
         //  it three launches are 3 us slower than one)
         if (h->cap_angular > 48 && h->bwd_by_class && h->hp.N >= h->bwd_class_atoms) {          // (record capacities are 32, 64, 128, ...)
@@ -1276,14 +1291,16 @@ int nnpops_ani_describe(nnpops_ani_t h, char* text, int capacity) {
     const bool shape2x = h->nfrp == 8 && h->nfzp == 4;
     std::snprintf(text, (size_t)capacity,
                   "forward=%s backward=%d generic=%d uniform=%d grid=%d literal=%d dynamic_quads=%d fused_build=%d cap=%d cap_angular=%d "
-                  "chunk=%d classes=%d cells=%d scatter=%d row_major_walk=%d",
+                  "chunk=%d classes=%d cells=%d scatter=%d row_major_walk=%d bwd_mode=%d radial_bwd=%s tile=%d compact=%d",
                   h->forward_kernel == 2 ? "mfma" : h->forward_kernel == 1 ? "chunked" : "merge", h->backward_kernel, (int)h->generic,
                   (int)uni, (int)(uni && h->fwd_grid), (int)(uni && h->fwd_grid && shape2x && h->fwd_literal), (int)h->fwd_dynamic,
                   (int)(h->computed ? h->last_fused_build : (h->fuse_forward < 0 ? h->hp.N <= kFuseAtoms : h->fuse_forward != 0)), h->cap, h->cap_angular,
                   // (the chunk the forward kernel is launched with, not the configured floor: ADVICE r04)
                   h->generic ? h->fwd_chunk : forward_chunk(h, (size_t)h->cap_angular * 2 * sizeof(float4), (size_t)(h->nfrp + h->nfzp) * sizeof(float)),
                   (int)h->bwd_classes.size(), (int)h->last_used_cells,
-                  (int)h->scatter_now, h->hp.tri_row_major);      // (scatter: the last backprop() stored the leg forces in the receivers' rows)
+                  (int)h->scatter_now, h->hp.tri_row_major,       // (scatter: the last backprop() stored the leg forces in the receivers' rows)
+                  // what the last backprop() launched: mode 0 = the round-1 angular backward (with its tile and layout), 1-4 = the pair kernels
+                  h->last_bwd_mode, h->last_radial_lanes < 0 ? "none" : h->last_radial_lanes ? "lanes" : "rows", h->last_tile, h->last_compact);
     return NNPOPS_OK;
 }
 
