@@ -95,6 +95,16 @@ int nnpops_ani_compute_strided(nnpops_ani_t h, const float* positions, const flo
                                float* angular, int angular_ld);
 int nnpops_ani_backprop_strided(nnpops_ani_t h, const float* radial_deriv, int radial_ld, const float* angular_deriv,
                                 int angular_ld, float* position_deriv);
+/* backprop_strided followed by the box-vector gradient (virial) of the same scalar L = sum radial_deriv * radial + sum angular_deriv *
+ * angular.  Every displacement of the AEV is d = x_j - x_i + n B with B = box (rows = vectors) and n the integer minimum-image shift
+ * compute() chose, held fixed: box_deriv[k][c] = sum over every use of a displacement of n_k (dL/dd)_c -- all nine entries, the same
+ * formal derivative as nnpops_neighbor_pairs_box_backward.  box_deriv: device [3][3], fully overwritten (float32, accumulated in
+ * float64 in a fixed order: two calls agree bit for bit); position_deriv is exactly what backprop_strided writes.
+ * CONTRACT: positions and box are the arrays of the preceding compute(), unchanged -- the shifts are recovered from them and from
+ * the displacements the handle kept, not stored.  Periodic handles only, and not with nnpops_ani_set_molecules (NNPOPS_ERR_INVALID_ARGUMENT).
+ * Allocates nothing: graph-capturable like backprop.  Additive. */
+int nnpops_ani_backprop_box_strided(nnpops_ani_t h, const float* positions, const float* box, const float* radial_deriv, int radial_ld,
+                                    const float* angular_deriv, int angular_ld, float* position_deriv, float* box_deriv);
 /* Blocks on the handle's stream and reports whether the last compute() overflowed a neighbour
  * buffer (NNPOPS_ERR_CAPACITY; the handle has then already grown its buffers, so simply call
  * compute() again).  max_radial_neighbors / max_angular_neighbors (host, may be NULL) receive the

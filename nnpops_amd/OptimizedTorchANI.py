@@ -43,7 +43,12 @@ class FusedOptimizedTorchANI(OptimizedTorchANI):
     layers of every atomic network (+, when the positions require a gradient, the networks' input gradient and the AEV
     backward) issued back to back from one C++ call -- 7 kernel launches (the capacity check rides in the first network launch), one autograd node whose backward is a single
     multiplication -- instead of the ~45 launches the composition records.  Not constructed directly: ``OptimizedTorchANI(...)``
-    turns into it.  Second derivatives are refused (use ``fused_step=False``)."""
+    turns into it.  Second derivatives are refused (use ``fused_step=False``).
+
+    A ``cell`` that requires a gradient gets one (extension): the step then also runs the box-gradient pass of the AEV backward and
+    keeps dE/dcell [3, 3] next to dE/dpositions -- the formal derivative with the minimum-image shifts held fixed, all nine entries
+    -- so ``energy.backward()`` fills ``cell.grad`` and a stress / NPT driver needs nothing else.  Without it the step launches
+    exactly what it always did.  ``energy_and_forces`` returns no virial."""
 
     @torch.jit.export
     def set_check_interval(self, interval: int) -> None:

@@ -116,7 +116,13 @@ class TorchANISymmetryFunctions(torch.nn.Module):
 
     def forward(self, species_positions: Tuple[Tensor, Tensor], cell: Optional[Tensor] = None,
                 pbc: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
-        """(species, positions[1, N, 3]) -> (species, aev[1, N, S*nR + S(S+1)/2*nA])"""
+        """(species, positions[1, N, 3]) -> (species, aev[1, N, S*nR + S(S+1)/2*nA])
+
+        Extension: differentiable with respect to ``cell`` as well (first derivatives).  When ``cell`` requires a gradient the
+        backward also returns dL/dcell [3, 3] -- the derivative with the minimum-image shifts of the forward held fixed, all nine
+        entries, the convention of ``getNeighborPairs`` and ``PME`` -- from which a stress follows as
+        ``(positions.T @ positions.grad + cell.T @ cell.grad) / volume``.  A cell that does not require a gradient costs nothing
+        and gets none; ``create_graph=True`` with a cell gradient is refused."""
         species, positions = species_positions
         self.check_arguments(species, cell, pbc)
         # the reference concatenates the two outputs of `operation` (SymmetryFunctions.py:120-122); `aev` has the kernels

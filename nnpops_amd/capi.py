@@ -35,6 +35,8 @@ SIGNATURES = {
     "nnpops_ani_backprop": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_ani_compute_strided": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "nnpops_ani_backprop_strided": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "nnpops_ani_backprop_box_strided": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                  C.c_void_p]),
     "nnpops_ani_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "nnpops_ani_check_begin": (C.c_int, [C.c_void_p]),
     "nnpops_ani_check_end": (C.c_int, [C.c_void_p]),
@@ -268,6 +270,25 @@ class AniSymmetryFunctions:
         _check(self._lib.nnpops_ani_set_stream(self._h, _stream_ptr(radial_grad.device)))
         _check(self._lib.nnpops_ani_backprop(self._h, _ptr(radial_grad), _ptr(angular_grad), _ptr(position_grad)))
         return position_grad
+
+    def backprop_box(self, positions, box, radial_grad, angular_grad, position_grad=None, box_grad=None):
+        """``backprop`` plus the box-vector gradient (virial) of the same scalar -> (position_grad [N,3], box_grad [3,3]).
+
+        ``box_grad[k][c] = sum n_k (dL/dd)_c`` over every displacement ``d = x_j - x_i + n @ box`` the AEV used, the integer
+        minimum-image shifts ``n`` held fixed; all nine entries.  ``positions`` and ``box`` must be the tensors of the preceding
+        ``compute`` (the shifts are recovered from them).  Periodic evaluators only."""
+        _dev_f32(positions, "positions", (self.num_atoms, 3))
+        _dev_f32(box, "box", (3, 3))
+        _dev_f32(radial_grad, "radial_grad", (self.num_atoms, self.radial_width))
+        _dev_f32(angular_grad, "angular_grad", (self.num_atoms, self.angular_width))
+        if position_grad is None:
+            position_grad = torch.empty((self.num_atoms, 3), dtype=torch.float32, device=radial_grad.device)
+        if box_grad is None:
+            box_grad = torch.empty((3, 3), dtype=torch.float32, device=radial_grad.device)
+        _check(self._lib.nnpops_ani_set_stream(self._h, _stream_ptr(radial_grad.device)))
+        _check(self._lib.nnpops_ani_backprop_box_strided(self._h, _ptr(positions), _ptr(box), _ptr(radial_grad), 0, _ptr(angular_grad), 0,
+                                                         _ptr(position_grad), _ptr(box_grad)))
+        return position_grad, box_grad
 
     KERNELS = ("neighbors", "radial_forward", "angular_forward", "radial_backward", "angular_backward", "cell_grid")
 

@@ -16,6 +16,7 @@
 #include "ani_angular_generic.h"
 #include "ani_radial_bwd.h"
 #include "ani_build_forward.h"
+#include "ani_box_grad.h"
 #include "host_common.h"
 
 using namespace nnpops;
@@ -89,6 +90,7 @@ struct nnpops_ani {
     int fwd_atoms_per_group = 1;    // > 1: every wave / workgroup walks that many atoms (amortises its prologue)
     int* d_cnt_a = nullptr;         // [N]
     int* d_cnt_ro = nullptr;        // [N]
+    double* d_box_partials = nullptr; // [ani_box_blocks(N)][9] partial sums of the box-gradient pass (ani_box_grad.h): sized by N alone
     int* d_status = nullptr;        // [kStatAlloc]: check()'s kStatWords words, then the class launches' flag (ani_kernels.h)
     int* h_status = nullptr;        // pinned, device-visible host words {stamp, overflow} (nnpops_ani_check_begin / _end)
     int* h_status_dev = nullptr;    // the device's address of the same words
@@ -712,6 +714,7 @@ int nnpops_ani_create(nnpops_ani_t* out, int num_atoms, int num_species, float r
     if ((rc = dev_alloc(&h->d_centre_force, (size_t)num_atoms + 1))) return cleanup(rc);      // (+ the class launches' flag word, ani_angular_bwd.h)
     if (hipMemset(h->d_centre_force + num_atoms, 0, sizeof(float4)) != hipSuccess) return cleanup(fail(NNPOPS_ERR_HIP, "memset failed"));
     if ((rc = dev_alloc(&h->d_status, (size_t)kStatAlloc))) return cleanup(rc);
+    if (periodic && (rc = dev_alloc(&h->d_box_partials, (size_t)9 * ani_box_blocks(num_atoms)))) return cleanup(rc);
     if ((rc = alloc_rows(h))) return cleanup(rc);
     h->max_cells = num_atoms + 4096;
     if ((rc = dev_alloc(&h->d_grid, 1))) return cleanup(rc);
@@ -792,7 +795,7 @@ int nnpops_ani_destroy(nnpops_ani_t h) {
     if (!h) return NNPOPS_OK;
     DeviceGuard guard(h->device);
     dev_free(h->d_params); dev_free(h->d_species); dev_free(h->d_segment);
-    dev_free(h->d_nbr); dev_free(h->d_recA); dev_free(h->d_recB); dev_free(h->d_tri); dev_free(h->d_cnt_a); dev_free(h->d_cnt_ro); dev_free(h->d_cnt_pos); dev_free(h->d_status);
+    dev_free(h->d_nbr); dev_free(h->d_recA); dev_free(h->d_recB); dev_free(h->d_tri); dev_free(h->d_cnt_a); dev_free(h->d_cnt_ro); dev_free(h->d_cnt_pos); dev_free(h->d_status); dev_free(h->d_box_partials);
     dev_free(h->d_ids); dev_free(h->d_leg_force); dev_free(h->d_centre_force); dev_free(h->d_bucket_offsets);
     dev_free(h->d_hist); dev_free(h->d_bins);
     dev_free(h->d_grid); dev_free(h->d_cell_count); dev_free(h->d_cell_start); dev_free(h->d_atom_cell);
@@ -1030,6 +1033,27 @@ int nnpops_ani_backprop_strided(nnpops_ani_t h, const float* radial_deriv, int r
     }
     rc = join_streams(h, spans, nspans);
     if (rc != NNPOPS_OK) return rc;
+    NNPOPS_HIP_TRY(hipGetLastError());
+    return NNPOPS_OK;
+}
+
+int nnpops_ani_backprop_box_strided(nnpops_ani_t h, const float* positions, const float* box, const float* radial_deriv, int radial_ld,
+                                    const float* angular_deriv, int angular_ld, float* position_deriv, float* box_deriv) {
+    NNPOPS_REQUIRE(h != nullptr, "NULL handle");
+    NNPOPS_REQUIRE(h->hp.periodic, "the box gradient needs a periodic handle (this one was created without box vectors)");
+    NNPOPS_REQUIRE(!h->d_segment, "the box gradient is not defined for a handle of batched molecules (nnpops_ani_set_molecules)");
+    NNPOPS_REQUIRE(positions && box && box_deriv, "NULL device pointer");
+    int rc = nnpops_ani_backprop_strided(h, radial_deriv, radial_ld, angular_deriv, angular_ld, position_deriv);
+    if (rc != NNPOPS_OK) return rc;
+    // ... and behind the joined streams, with every leg force in place (the classes' clean-up launch included): one pass over the
+    // rows, the records and the leg forces, then the sum of its workgroups (ani_box_grad.h)
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(NNPOPS_ERR_HIP, "cannot select device %d", h->device);
+    const int nblocks = ani_box_blocks(h->hp.N);
+    hipLaunchKernelGGL(ani_box_partials, dim3(nblocks), dim3(kBoxThreads), 0, h->stream, h->d_params, positions, box, h->d_nbr, h->cap,
+                       h->cap_angular, h->d_cnt_pos, radial_deriv, h->ld_radial, h->d_recA, h->d_ids, h->d_leg_force,
+                       h->last_used_cells ? h->d_sorted_atom : nullptr, h->scatter_now ? 1 : 0, h->d_box_partials);
+    hipLaunchKernelGGL(pairs_box_finish<float>, dim3(1), dim3(kBoxThreads), 0, h->stream, nblocks, (const double*)h->d_box_partials, box_deriv);
     NNPOPS_HIP_TRY(hipGetLastError());
     return NNPOPS_OK;
 }

@@ -345,6 +345,19 @@ public:
         return {Tensor(), positionsGrad, Tensor()};          // no gradient for the holder and the box (:174)
     }
 
+    // The two backward forms WITH the gradient of the box vectors (nnpops_ani_backprop_box_strided): `positions` and `cell` are the
+    // tensors of the forward this backward belongs to -- the minimum-image shifts are recovered from them.  -> {none, dL/dpositions,
+    // dL/dcell [3, 3]}; the position gradient is the one backward() / backwardFused() return, bit for bit.
+    tensor_list backwardFusedCell(const Tensor& aevGrad, const Tensor& positions, const Tensor& cell) {
+        const Tensor g = aevGrad.contiguous();
+        const int64_t wr = numSpecies * numRadial, w = g.size(1);
+        return backpropCell(g.data_ptr<float>(), (int)w, g.data_ptr<float>() + wr, (int)w, positions, cell);
+    }
+    tensor_list backwardCell(const tensor_list& grads, const Tensor& positions, const Tensor& cell) {
+        const Tensor radialGrad = grads[0].contiguous(), angularGrad = grads[1].contiguous();
+        return backpropCell(radialGrad.data_ptr<float>(), 0, angularGrad.data_ptr<float>(), 0, positions, cell);
+    }
+
     static std::string serialize(const HolderPtr& self) {
         torch::serialize::OutputArchive archive;
         archive.write("numSpecies", self->numSpecies);
@@ -394,6 +407,19 @@ public:
     }
 
 private:
+    tensor_list backpropCell(const float* radialGrad, int ldRadial, const float* angularGrad, int ldAngular, const Tensor& positions,
+                             const Tensor& cell) {
+        if (!impl) throw std::runtime_error("backward() called before forward()");
+        const Tensor pos = positions.contiguous(), box = cell.contiguous();
+        const auto opts = torch::TensorOptions().device(device).dtype(torch::kFloat32);
+        Tensor positionsGrad = torch::empty({(int64_t)atomSpecies.size(), 3}, opts), cellGrad = torch::empty({3, 3}, opts);
+        nnpops_ani_set_stream(impl, current_stream(device));
+        if (nnpops_ani_backprop_box_strided(impl, pos.data_ptr<float>(), box.data_ptr<float>(), radialGrad, ldRadial, angularGrad, ldAngular,
+                                            positionsGrad.data_ptr<float>(), cellGrad.data_ptr<float>()) != NNPOPS_OK)
+            raise_last("NNPOpsANISymmetryFunctions::backward");
+        return {Tensor(), positionsGrad, cellGrad};
+    }
+
     void applyMolecules() {
         std::vector<int32_t> off(moleculeOffsets.begin(), moleculeOffsets.end());
         if (nnpops_ani_set_molecules(impl, off.empty() ? 0 : (int)off.size() - 1, off.empty() ? nullptr : off.data()) != NNPOPS_OK)
@@ -429,42 +455,75 @@ public:
 private:
 };
 
+// Both nodes: `cellGrad` (decided by the caller, where grad mode is what the user set) = the box vectors require a gradient.  The node
+// then saves positions and cell, its backward runs the box-gradient pass behind the usual launches and fills the cell's slot; otherwise
+// it does exactly what it always did -- nothing saved, no extra launch, no gradient for the box (reference :174).
+bool wants_cell_gradient(const c10::optional<Tensor>& periodicBoxVectors) {
+    return torch::GradMode::is_enabled() && periodicBoxVectors.has_value() && periodicBoxVectors->requires_grad();
+}
+void refuse_second_derivatives(const char* op) {
+    TORCH_CHECK(!torch::GradMode::is_enabled(), "NNPOpsANISymmetryFunctions::", op,
+                ": second derivatives are not implemented (backward was called with create_graph=True and the cell requires a gradient)");
+}
+
 class AutogradFunctions : public torch::autograd::Function<AutogradFunctions> {
 public:
     static tensor_list forward(AutogradContext* ctx, const HolderPtr& holder, const Tensor& positions,
-                               const c10::optional<Tensor>& periodicBoxVectors) {
+                               const c10::optional<Tensor>& periodicBoxVectors, bool cellGrad) {
         ctx->saved_data["holder"] = holder;
+        ctx->saved_data["cell_grad"] = cellGrad;
+        if (cellGrad) ctx->save_for_backward({positions, *periodicBoxVectors});
         return holder->forward(positions, periodicBoxVectors);
     }
     static tensor_list backward(AutogradContext* ctx, const tensor_list& grads) {
         const auto holder = ctx->saved_data["holder"].toCustomClass<Holder>();
         ctx->saved_data.erase("holder");
-        return holder->backward(grads);
+        tensor_list out;
+        if (ctx->saved_data["cell_grad"].toBool()) {
+            refuse_second_derivatives("operation");
+            const auto saved = ctx->get_saved_variables();
+            out = holder->backwardCell(grads, saved[0], saved[1]);
+        } else {
+            out = holder->backward(grads);
+        }
+        out.push_back(Tensor());
+        return out;
     }
 };
 
 tensor_list operation(const c10::optional<HolderPtr>& holder, const Tensor& positions,
                       const c10::optional<Tensor>& periodicBoxVectors) {
-    return AutogradFunctions::apply(*holder, positions, periodicBoxVectors);
+    return AutogradFunctions::apply(*holder, positions, periodicBoxVectors, wants_cell_gradient(periodicBoxVectors));
 }
 
 class FusedAutogradFunction : public torch::autograd::Function<FusedAutogradFunction> {
 public:
     static Tensor forward(AutogradContext* ctx, const HolderPtr& holder, const Tensor& positions,
-                          const c10::optional<Tensor>& periodicBoxVectors) {
+                          const c10::optional<Tensor>& periodicBoxVectors, bool cellGrad) {
         ctx->saved_data["holder"] = holder;
+        ctx->saved_data["cell_grad"] = cellGrad;
+        if (cellGrad) ctx->save_for_backward({positions, *periodicBoxVectors});
         return holder->forwardImpl(positions, periodicBoxVectors, true)[0];
     }
     static tensor_list backward(AutogradContext* ctx, const tensor_list& grads) {
         const auto holder = ctx->saved_data["holder"].toCustomClass<Holder>();
         ctx->saved_data.erase("holder");
-        return holder->backwardFused(grads[0]);
+        tensor_list out;
+        if (ctx->saved_data["cell_grad"].toBool()) {
+            refuse_second_derivatives("aev");
+            const auto saved = ctx->get_saved_variables();
+            out = holder->backwardFusedCell(grads[0], saved[0], saved[1]);
+        } else {
+            out = holder->backwardFused(grads[0]);
+        }
+        out.push_back(Tensor());
+        return out;
     }
 };
 
 // Additive: the whole AEV as one tensor (see Holder::forwardImpl).  operation() keeps the reference's two-tensor form.
 Tensor aev(const c10::optional<HolderPtr>& holder, const Tensor& positions, const c10::optional<Tensor>& periodicBoxVectors) {
-    return FusedAutogradFunction::apply(*holder, positions, periodicBoxVectors);
+    return FusedAutogradFunction::apply(*holder, positions, periodicBoxVectors, wants_cell_gradient(periodicBoxVectors));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -485,7 +544,8 @@ std::pair<Tensor, Tensor> energy_step(const HolderPtr& holder, const Tensor& fra
                                       const std::vector<int64_t>& kind_atoms, const std::vector<int64_t>& widths, int64_t members,
                                       const Tensor& planes, const Tensor& floats, const c10::optional<Tensor>& shift,
                                       const c10::optional<Tensor>& x_blocks, const c10::optional<Tensor>& dead_blocks, bool need_gradient,
-                                      float gradient_sign, int64_t act_scale_log2) {
+                                      float gradient_sign, int64_t act_scale_log2, Tensor* kept_cell = nullptr) {
+    // (kept_cell != NULL, with need_gradient: the AEV backward also runs its box-gradient pass and dE/dcell * gradient_sign [3, 3] is kept there)
     TORCH_CHECK(frame.dim() == 2 || (frame.dim() == 3 && frame.size(0) == 1), "energy(): positions must be [atoms, 3] or [1, atoms, 3]");
     const Tensor positions = frame.dim() == 3 ? frame[0] : frame;
     Tensor energy, kept;
@@ -541,7 +601,14 @@ std::pair<Tensor, Tensor> energy_step(const HolderPtr& holder, const Tensor& fra
             }
             call.frame.dx = daev.data_ptr<float>(); call.frame.lddx = (int)daev.size(1); call.frame.dx_scale = gradient_sign / (float)members;
             if (nnpops_mlp_input_grad(stream, &call.frame) != NNPOPS_OK) raise_last("NNPOpsANISymmetryFunctions::energy");
-            kept = holder->backwardFused(daev)[1];
+            if (kept_cell != nullptr) {
+                TORCH_CHECK(cell.has_value(), "energy(): a gradient of the cell was requested without a cell");
+                const tensor_list both = holder->backwardFusedCell(daev, positions, *cell);
+                kept = both[1];
+                *kept_cell = both[2];
+            } else {
+                kept = holder->backwardFused(daev)[1];
+            }
         }
         if (!holder->finishDeferredCheck()) break;
     }
@@ -557,12 +624,13 @@ public:
                           const Tensor& rows, std::vector<int64_t> kind_atoms, std::vector<int64_t> widths, int64_t members,
                           const Tensor& planes, const Tensor& floats, const c10::optional<Tensor>& shift,
                           const c10::optional<Tensor>& x_blocks, const c10::optional<Tensor>& dead_blocks, bool need_gradient,
-                          int64_t act_scale_log2) {
-        Tensor energy, kept;
+                          int64_t act_scale_log2, bool need_cell) {
+        Tensor energy, kept, kept_cell;
         std::tie(energy, kept) = energy_step(holder, frame, cell, rows, kind_atoms, widths, members, planes, floats, shift, x_blocks, dead_blocks,
-                                             need_gradient, 1.0f, act_scale_log2);
+                                             need_gradient, 1.0f, act_scale_log2, need_cell ? &kept_cell : nullptr);
         if (need_gradient) {
-            ctx->save_for_backward({kept});
+            if (need_cell) ctx->save_for_backward({kept, kept_cell});      // dE/dcell next to dE/dpositions: backward scales both
+            else ctx->save_for_backward({kept});
             ctx->saved_data["lead"] = frame.dim() == 3;
         }
         return energy;
@@ -583,7 +651,15 @@ public:
                                    g.scalar_type() == torch::kFloat64 ? 1 : 0, out.data_ptr<float>()) != NNPOPS_OK)
             raise_last("NNPOpsANISymmetryFunctions::energy (backward)");
         if (ctx->saved_data["lead"].toBool()) out = out.unsqueeze(0);
-        return {Tensor(), out, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+        Tensor cell_out;
+        if (saved.size() > 1) {                                              // dE/dcell, [3, 3] float32
+            cell_out = torch::empty_like(saved[1]);
+            if (nnpops_scale_by_scalar(current_stream(kept.device()), saved[1].data_ptr<float>(), saved[1].numel(), g.data_ptr(),
+                                       g.scalar_type() == torch::kFloat64 ? 1 : 0, cell_out.data_ptr<float>()) != NNPOPS_OK)
+                raise_last("NNPOpsANISymmetryFunctions::energy (backward)");
+        }
+        return {Tensor(), out, cell_out, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(),
+                Tensor()};
     }
 };
 
@@ -591,9 +667,10 @@ Tensor energy(const c10::optional<HolderPtr>& holder, const Tensor& positions, c
               std::vector<int64_t> kind_atoms, std::vector<int64_t> widths, int64_t members, const Tensor& planes, const Tensor& floats,
               const c10::optional<Tensor>& shift, const c10::optional<Tensor>& x_blocks, const c10::optional<Tensor>& dead_blocks,
               int64_t act_scale_log2) {
-    const bool need = torch::GradMode::is_enabled() && positions.requires_grad();
+    const bool need_cell = torch::GradMode::is_enabled() && cell.has_value() && cell->requires_grad();
+    const bool need = (torch::GradMode::is_enabled() && positions.requires_grad()) || need_cell;
     return EnergyFunction::apply(*holder, positions, cell, rows, kind_atoms, widths, members, planes, floats, shift, x_blocks, dead_blocks, need,
-                                 act_scale_log2);
+                                 act_scale_log2, need_cell);
 }
 
 // Additive: energy AND forces (-dE/dpositions) of the frame from one call, outside autograd -- what an MD driver asks a model for
