@@ -127,6 +127,12 @@ int nnpops_ani_overflow_word(nnpops_ani_t h, const int32_t** word);
  * layer that opens a HIP runtime of its own to copy from the address above may get a second runtime that does not know the
  * pointer) and leaves the word as it is -- only nnpops_ani_check() clears it.  Additive. */
 int nnpops_ani_read_overflow(nnpops_ani_t h, int32_t* value);
+/* The cell grid the last compute() decided on the device, for diagnostics and tests: waits for the handle's stream and copies it
+ * with this library's runtime as out = {nx, ny, nz, ncells, m, ok, bin_overflow, periodic} (m: stencil half-width in cells, 1 for
+ * cells at least a cutoff wide, 2 for half-width cells; ok = 0: the box was refused, or a bin overflowed, and check() falls back
+ * or grows).  What it returns before any compute() went through the grid is unspecified; after a fall-back to the all-pairs search
+ * it stays what the refused build left.  Blocks, runs no kernel, not capturable into a graph.  Additive. */
+int nnpops_ani_read_grid(nnpops_ani_t h, int32_t* out);
 /* Which kernels this handle runs, as one line of `key=value` words (for logs and tests; the words may grow): forward= merge |
  * chunked | mfma; backward= kernel number; generic= the function list does not factor; uniform= one eta and one zeta; grid= eight
  * radial factors on equally spaced shifts (taken by recurrence); literal= the constants are the published ANI-2x set and the
@@ -211,6 +217,9 @@ int nnpops_cfconv_neighbors_check(nnpops_cfconv_neighbors_t h, int* num_pairs);
 /* Blocks; copies the half list of the last build to host arrays (test/diagnostic use):
  * pair_atoms [2][capacity] (row 0 = i, row 1 = j), distances [capacity]. */
 int nnpops_cfconv_neighbors_export(nnpops_cfconv_neighbors_t h, int capacity, int32_t* pair_atoms, float* distances);
+/* The cell grid of the last build() that went through one (1 024 atoms and more), as nnpops_ani_read_grid:
+ * out = {nx, ny, nz, ncells, m, ok, bin_overflow, periodic}.  Blocks, runs no kernel, not capturable; diagnostics only. */
+int nnpops_cfconv_neighbors_read_grid(nnpops_cfconv_neighbors_t h, int32_t* out);
 
 /* activation: 0 = shifted softplus, 1 = tanh (CFConv.h:114-117).
  * w1: host [width][num_gaussians] (the layout the reference core indexes, CpuCFConv.cpp:163);
@@ -253,6 +262,10 @@ int64_t nnpops_neighbor_pairs_workspace_bytes(int num_atoms);
 int nnpops_neighbor_pairs_forward(int dtype, int num_atoms, const void* positions, const void* box, double cutoff,
                                   int64_t max_num_pairs, int32_t* neighbors, void* deltas, void* distances,
                                   int32_t* num_pairs, void* workspace, void* stream);
+/* The cell grid that the last nnpops_neighbor_pairs_forward() with this workspace and this num_atoms left in it (compacted lists of
+ * 8 192 atoms and more; anything else builds no grid and the words are whatever the workspace held), as nnpops_ani_read_grid:
+ * out = {nx, ny, nz, ncells, m, ok, bin_overflow, periodic}.  Waits for `stream`, runs no kernel, not capturable; diagnostics only. */
+int nnpops_neighbor_pairs_read_grid(const void* workspace, int num_atoms, void* stream, int32_t* out);
 /* grad_positions: device [num_atoms][3], fully overwritten
  * (getNeighborPairsCUDA.cu:80-101: +g on neighbors[0], -g on neighbors[1], g = grad_deltas + deltas/distance*grad_distances). */
 int nnpops_neighbor_pairs_backward(int dtype, int num_atoms, int64_t num_slots, const int32_t* neighbors,

@@ -48,6 +48,7 @@ SIGNATURES = {
     "nnpops_ani_timing_overhead": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "nnpops_ani_overflow_word": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "nnpops_ani_read_overflow": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "nnpops_ani_read_grid": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "nnpops_ani_describe": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "nnpops_ani_check_begin_with": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]),
     "nnpops_ani_set_timing_merge": (C.c_int, [C.c_void_p, C.c_int]),
@@ -57,6 +58,7 @@ SIGNATURES = {
     "nnpops_cfconv_neighbors_build": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_cfconv_neighbors_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "nnpops_cfconv_neighbors_export": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "nnpops_cfconv_neighbors_read_grid": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "nnpops_cfconv_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float,
                                        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "nnpops_cfconv_destroy": (C.c_int, [C.c_void_p]),
@@ -81,6 +83,7 @@ SIGNATURES = {
     "nnpops_neighbor_pairs_workspace_bytes": (C.c_int64, [C.c_int]),
     "nnpops_neighbor_pairs_forward": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int64,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nnpops_neighbor_pairs_read_grid": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int32)]),
     "nnpops_pme_direct_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
     "nnpops_pme_direct": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -185,6 +188,13 @@ def _dev_f32(t, name, shape=None):
     if shape is not None and tuple(t.shape) != tuple(shape):
         raise ValueError(f'"{name}" has shape {tuple(t.shape)}, expected {tuple(shape)}')
     return t
+
+
+GRID_FIELDS = ("nx", "ny", "nz", "ncells", "m", "ok", "bin_overflow", "periodic")
+
+
+def _grid_dict(words):
+    return dict(zip(GRID_FIELDS, (int(v) for v in words)))
 
 
 def _stream_ptr(device):
@@ -316,6 +326,13 @@ class AniSymmetryFunctions:
         _check(self._lib.nnpops_ani_read_overflow(self._h, C.byref(word)))     # (copied by the library's own runtime: ADVICE r05)
         return word.value
 
+    def read_grid(self):
+        """The cell grid the last compute() decided, {nx, ny, nz, ncells, m, ok, bin_overflow, periodic} (blocks; diagnostics only,
+        meaningful once a compute() has gone through the grid: describe()["cells"])."""
+        words = (C.c_int32 * 8)()
+        _check(self._lib.nnpops_ani_read_grid(self._h, words))
+        return _grid_dict(words)
+
     def set_timing_merge(self, merge):
         """True: one bracket around build + angular forward (reported as "neighbors") and one around the two backward kernels (reported as
         "angular_backward") instead of the four single ones: single + single - merged = what a bracket costs, measured in place."""
@@ -361,10 +378,12 @@ class AniSymmetryFunctions:
 _DTYPE_CODE = {torch.float32: 0, torch.float64: 1}
 
 
-def neighbor_pairs_forward(positions, cutoff, max_num_pairs=-1, box=None):
+def neighbor_pairs_forward(positions, cutoff, max_num_pairs=-1, box=None, return_grid=False):
     """-> (neighbors int32[2,P], deltas[P,3], distances[P], num_pairs int32[1]) on positions' device.
 
-    P = N(N-1)/2 when max_num_pairs == -1, else max_num_pairs.  No host synchronisation."""
+    P = N(N-1)/2 when max_num_pairs == -1, else max_num_pairs.  No host synchronisation.
+    return_grid=True (diagnostics: blocks) appends the cell grid the call left in its workspace, as AniSymmetryFunctions.read_grid,
+    or None when the call built none (max_num_pairs == -1, or fewer than 8 192 atoms)."""
     if not positions.is_cuda:
         raise ValueError('"positions" must live on the HIP device (nnpops_amd has no CPU path)')
     if positions.dtype not in _DTYPE_CODE:
@@ -393,6 +412,13 @@ def neighbor_pairs_forward(positions, cutoff, max_num_pairs=-1, box=None):
         _check(L.nnpops_neighbor_pairs_forward(_DTYPE_CODE[dt], n, _ptr(positions), _ptr(box), float(cutoff), max_num_pairs,
                                                _ptr(neighbors), _ptr(deltas), _ptr(distances), _ptr(num_pairs), _ptr(ws),
                                                _stream_ptr(dev)))
+        if return_grid:
+            grid = None
+            if max_num_pairs != -1 and n >= 8192:
+                words = (C.c_int32 * 8)()
+                _check(L.nnpops_neighbor_pairs_read_grid(_ptr(ws), n, _stream_ptr(dev), words))
+                grid = _grid_dict(words)
+            return neighbors, deltas, distances, num_pairs, grid
     return neighbors, deltas, distances, num_pairs
 
 
@@ -706,6 +732,12 @@ class CFConvNeighbors:
         n = C.c_int(0)
         _check(self._lib.nnpops_cfconv_neighbors_check(self._h, C.byref(n)))
         return n.value
+
+    def read_grid(self):
+        """The cell grid of the last build() that went through one, as AniSymmetryFunctions.read_grid (blocks; diagnostics only)."""
+        words = (C.c_int32 * 8)()
+        _check(self._lib.nnpops_cfconv_neighbors_read_grid(self._h, words))
+        return _grid_dict(words)
 
     def export(self):
         """-> (pair_atoms int32[2,P], distances f32[P]) of the half list {(i, j>i)}, i ascending, j ascending (host arrays)."""

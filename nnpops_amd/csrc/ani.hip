@@ -1309,6 +1309,17 @@ int nnpops_ani_read_overflow(nnpops_ani_t h, int32_t* value) {
     return NNPOPS_OK;
 }
 
+int nnpops_ani_read_grid(nnpops_ani_t h, int32_t* out) {
+    NNPOPS_REQUIRE(h != nullptr && out != nullptr, "NULL argument");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(NNPOPS_ERR_HIP, "cannot select device %d", h->device);
+    CellGrid g;
+    NNPOPS_HIP_TRY(hipMemcpyAsync(&g, h->d_grid, sizeof(CellGrid), hipMemcpyDeviceToHost, h->stream));
+    NNPOPS_HIP_TRY(hipStreamSynchronize(h->stream));
+    grid_words(g, out);
+    return NNPOPS_OK;
+}
+
 int nnpops_ani_describe(nnpops_ani_t h, char* text, int capacity) {
     NNPOPS_REQUIRE(h != nullptr && text != nullptr && capacity > 0, "NULL argument");
     const bool uni = h->fwd_uniform && h->hp.nFR == h->nfrp && h->hp.nFZ == h->nfzp;

@@ -650,6 +650,12 @@ struct CellBuffers {
     int* tile_total = nullptr;             // [max_cells / 8192 + 1] optional: lets grids of more than 8192 cells scan in parallel
 };
 
+// What the read_grid entry points of the consumers report (include/nnpops_hip.h): a host copy of the grid, as eight ints.
+static inline void grid_words(const CellGrid& g, int32_t* out) {
+    out[0] = g.nx; out[1] = g.ny; out[2] = g.nz; out[3] = g.ncells;
+    out[4] = g.m; out[5] = g.ok; out[6] = g.bin_overflow; out[7] = g.periodic;
+}
+
 static inline bool cell_build_is_binned(int N, bool periodic, const CellBuffers& b) {
     // (callers hand over hist / bins only for systems their bins are sized for: the stateful handles up to kBinnedAtoms atoms, with
     //  bins that grow in check(); getNeighborPairs up to kPairsBinnedAtoms with a fixed bin of 128 ids per cell)

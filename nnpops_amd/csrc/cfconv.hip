@@ -292,6 +292,16 @@ int nnpops_cfconv_neighbors_check(nnpops_cfconv_neighbors_t h, int* num_pairs) {
     return NNPOPS_OK;
 }
 
+int nnpops_cfconv_neighbors_read_grid(nnpops_cfconv_neighbors_t h, int32_t* out) {
+    NNPOPS_REQUIRE(h != nullptr && out != nullptr, "NULL argument");
+    DeviceGuard guard(h->device);
+    CellGrid g;
+    NNPOPS_HIP_TRY(hipMemcpyAsync(&g, h->d_grid, sizeof(CellGrid), hipMemcpyDeviceToHost, h->stream));
+    NNPOPS_HIP_TRY(hipStreamSynchronize(h->stream));
+    grid_words(g, out);
+    return NNPOPS_OK;
+}
+
 int nnpops_cfconv_neighbors_export(nnpops_cfconv_neighbors_t h, int capacity, int32_t* pair_atoms, float* distances) {
     NNPOPS_REQUIRE(h != nullptr && pair_atoms && distances, "NULL argument");
     NNPOPS_REQUIRE(h->built, "export() must follow build()");

@@ -712,6 +712,18 @@ int nnpops_neighbor_pairs_forward(int dtype, int num_atoms, const void* position
                                 (double*)deltas, (double*)distances, num_pairs, workspace, s);
 }
 
+int nnpops_neighbor_pairs_read_grid(const void* workspace, int num_atoms, void* stream, int32_t* out) {
+    NNPOPS_REQUIRE(workspace != nullptr && out != nullptr, "NULL argument");
+    NNPOPS_REQUIRE(num_atoms > 0, "num_atoms must be positive");
+    Workspace w;
+    carve(&w, (char*)const_cast<void*>(workspace), num_atoms);      // (the layout the forward call used)
+    CellGrid g;
+    NNPOPS_HIP_TRY(hipMemcpyAsync(&g, w.grid, sizeof(CellGrid), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    NNPOPS_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    grid_words(g, out);
+    return NNPOPS_OK;
+}
+
 int64_t nnpops_neighbor_pairs_backward_workspace_bytes(int num_atoms) {
     return num_atoms < 0 ? 0 : (int64_t)sizeof(unsigned long long) * (2 + 7 * (int64_t)num_atoms);
 }

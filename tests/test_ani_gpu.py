@@ -111,14 +111,26 @@ def test_neighbor_algorithms_agree_with_oracle(algorithm, kind):
 
 
 def test_cell_grid_falls_back_when_box_too_small(monkeypatch):
-    """A system large enough for the cell grid (the threshold is lowered to this one's size), but a 14.6 A box has < 3 cells
-    per axis at Rcr 5.1: the handle must notice on the device, switch to the all-pairs search and still be right (also grows
-    the rows)."""
+    """A system large enough for the cell grid (the threshold is lowered to this one's size), but a 14.6 A box has < 3 full-width
+    cells per axis at Rcr 5.1: the handle must notice on the device, switch to the all-pairs search and still be right (also
+    grows the rows).  The box does hold 5 half-width cells per axis (14.6 / 2.55), and since the half-width grid became the
+    default the handle walks that 5 x 5 x 5 grid instead of falling back, so the full-width grid is pinned here
+    (NNPOPS_ANI_FINE_GRID=0) and the grid of the first build is read back: 2 x 2 x 2, refused (ok = 0), bit 1 of the overflow
+    word set before check() consumes it, and the evaluation that is compared ran on the all-pairs search."""
+    from nnpops_amd import capi
     monkeypatch.setenv("NNPOPS_ANI_CELL_ATOMS", "1024")
+    monkeypatch.setenv("NNPOPS_ANI_FINE_GRID", "0")
+    import cell_geometry
+    seen = []
+    monkeypatch.setattr(capi, "AniSymmetryFunctions", cell_geometry.recording_ani(capi, seen))      # keeps the first build's state
     rf, af = workloads.ani2x_functions()
     pos, species, box = workloads.random_box(1100, density=0.35, seed=12, min_dist=0.5)
     assert box[0, 0] < 3 * 5.1
     _run_case(7, 5.1, 3.5, species, rf, af, pos, box)
+    sym, = seen
+    grid = sym.first["grid"]
+    assert sym.first["cells"] == "1" and (grid["nx"], grid["ny"], grid["nz"], grid["m"], grid["ok"]) == (2, 2, 2, 1, 0)
+    assert sym.first["word"] & 2 and sym.describe()["cells"] == "0"
 
 
 def test_cell_bins_grow_on_overflow(monkeypatch):
