@@ -13,6 +13,7 @@
  *   nnpops_ani_backprop              backprop                              src/ani/ANISymmetryFunctions.h:92
  *   nnpops_cfconv_neighbors_*        CFConvNeighbors ctor / build          src/schnet/CFConv.h:37-85
  *   nnpops_cfconv_create / compute / backprop   CFConv ctor / compute / backprop   src/schnet/CFConv.h:109-217
+ *   nnpops_cfconv_backprop_box       (additive) backprop and the box-vector gradient of a periodic list
  *   nnpops_neighbor_pairs_forward / _backward   neighbors::getNeighborPairs forward/backward kernels
  *                                               src/pytorch/neighbors/getNeighborPairsCUDA.cu:31-101
  *   nnpops_neighbor_pairs_box_backward / _double_backward   box gradient and second derivatives of that op
@@ -244,6 +245,18 @@ int nnpops_cfconv_compute(nnpops_cfconv_t h, nnpops_cfconv_neighbors_t neighbors
 int nnpops_cfconv_backprop(nnpops_cfconv_t h, nnpops_cfconv_neighbors_t neighbors, const float* positions,
                            const float* box, const float* input, const float* output_deriv, float* input_deriv,
                            float* position_deriv);
+/* As nnpops_cfconv_backprop, and the box-vector gradient (virial) of a periodic list behind it:
+ *     box_deriv[k][c] = sum over the half pairs i < j of  n_ij,k * (dL/dd_ij)_c ,   d_ij = x_j - x_i + n_ij * box
+ * with the minimum-image shifts n_ij the neighbour build chose held fixed; all nine entries, upper triangle included.
+ * box_deriv: device float32 [3][3], fully overwritten (products and sums in float64, no atomics: two calls agree bit for bit).
+ * positions and box are REQUIRED here and must be those of the neighbour list's last build(): the shifts are recovered from them
+ * and the stored displacements.  A non-periodic list or a NULL pointer is an error.  input_deriv and position_deriv are what
+ * nnpops_cfconv_backprop gives in the same place, bit for bit.  Runs on the convolution's stream; its scratch (partial sums; for
+ * the vector kernels one float per neighbour-row entry) is allocated by the first call with a given list, so run one step before
+ * capturing a HIP graph.  The stress follows as (sum_i x_i (x) dL/dx_i + box^T box_deriv) / V. */
+int nnpops_cfconv_backprop_box(nnpops_cfconv_t h, nnpops_cfconv_neighbors_t neighbors, const float* positions,
+                               const float* box, const float* input, const float* output_deriv, float* input_deriv,
+                               float* position_deriv, float* box_deriv);
 
 /* ------------------------------------------------------------------------------------------
  * getNeighborPairs (replaces the neighbors::getNeighborPairs CUDA kernels)

@@ -66,6 +66,8 @@ SIGNATURES = {
     "nnpops_cfconv_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_cfconv_backprop": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),
+    "nnpops_cfconv_backprop_box": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_split_planes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p, C.c_long]),
     "nnpops_rows_dot": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "nnpops_gemm_split": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_long, C.c_void_p,
@@ -798,6 +800,22 @@ class CFConv:
         _check(self._lib.nnpops_cfconv_backprop(self._h, neighbors._h, _ptr(positions), _ptr(box), _ptr(x), _ptr(out_grad),
                                                 _ptr(x_grad), _ptr(pos_grad)))
         return x_grad, pos_grad
+
+    def backprop_box(self, neighbors, positions, x, out_grad, box):
+        """backprop() and the box-vector gradient of a periodic list -> (input_grad, position_grad, box_grad float32 (3, 3)).
+        ``positions`` and ``box`` must be those of the list's last build()."""
+        _dev_f32(positions, "positions", (self.num_atoms, 3))
+        _dev_f32(x, "input", (self.num_atoms, self.width))
+        _dev_f32(out_grad, "output_grad", (self.num_atoms, self.width))
+        if box is not None:
+            _dev_f32(box, "box", (3, 3))
+        x_grad = torch.empty_like(x)
+        pos_grad = torch.empty((self.num_atoms, 3), dtype=torch.float32, device=x.device)
+        box_grad = torch.empty((3, 3), dtype=torch.float32, device=x.device)
+        _check(self._lib.nnpops_cfconv_set_stream(self._h, _stream_ptr(x.device)))
+        _check(self._lib.nnpops_cfconv_backprop_box(self._h, neighbors._h, _ptr(positions), _ptr(box), _ptr(x), _ptr(out_grad),
+                                                    _ptr(x_grad), _ptr(pos_grad), _ptr(box_grad)))
+        return x_grad, pos_grad, box_grad
 
 
 # ---- dense layers (batched_nn.hip) ----

@@ -28,6 +28,8 @@
 // The kernels live in cfconv_build.h (neighbour rows, half list), cfconv_filters.h (the default filters kernels, the gather)
 // and cfconv_fallback_kernels.h (the vector kernel, the fp32 matrix and LDS-plane filters kernels); this file holds the
 // handles, the weight preparation, the choice of kernels and the C ABI.
+// nnpops_cfconv_backprop_box adds dL/dbox of a periodic list behind the backward pass: one reduction over the wrapped pairs of what
+// that pass leaves on the device (cfconv_box_grad.h).
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -35,6 +37,7 @@
 #include <cstring>
 #include <vector>
 
+#include "cfconv_box_grad.h"
 #include "cfconv_build.h"
 #include "cfconv_fallback_kernels.h"
 #include "cfconv_filters.h"
@@ -147,6 +150,11 @@ struct nnpops_cfconv {
     unsigned long long filt_epoch = 0;
     bool graph_seen = false;      // a filters launch of this convolution has been captured into a graph: replays write d_filt unseen
     bool reuse_filters = true;                     // $NNPOPS_CFCONV_REUSE_FILTERS=0: always store
+    // box-gradient calls only (nnpops_cfconv_backprop_box), sized on first use like d_filt: the partial sums of the pass
+    // [cfconv_box_blocks(N)][9] and, on the vector path, the pair scalar of every row entry [N][cap]
+    double* d_box_partials = nullptr;
+    float* d_row_s = nullptr;
+    size_t row_s_len = 0;
 };
 
 extern "C" {
@@ -476,7 +484,7 @@ int nnpops_cfconv_destroy(nnpops_cfconv_t h) {
     DeviceGuard guard(h->device);
     dev_free(h->d_w1t); dev_free(h->d_w2t); dev_free(h->d_b1); dev_free(h->d_b2);
     dev_free(h->d_w1t_s); dev_free(h->d_w2t_s); dev_free(h->d_b1_s);
-    dev_free(h->d_filt); dev_free(h->d_pair_s);
+    dev_free(h->d_filt); dev_free(h->d_pair_s); dev_free(h->d_box_partials); dev_free(h->d_row_s);
     dev_free(h->d_w1b); dev_free(h->d_w2h); dev_free(h->d_w2l); dev_free(h->d_w1h); dev_free(h->d_w1l);
     delete h;
     return NNPOPS_OK;
@@ -492,7 +500,8 @@ int nnpops_cfconv_set_stream(nnpops_cfconv_t h, void* stream) {
 
 namespace {
 
-template <int ACT, int CPL, bool BWD, bool WLDS = true>
+// (ROW_S: the pair scalar of every row entry to h->d_row_s and nothing else, for a box-gradient call)
+template <int ACT, int CPL, bool BWD, bool WLDS = true, bool ROW_S = false>
 int launch_conv(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, const float* x, const float* gout, float* out, float* pos_grad) {
     // as many waves per workgroup as fit next to the shared weights in 160 KiB of LDS
     const size_t budget = 156 * 1024 / sizeof(float);
@@ -501,36 +510,36 @@ int launch_conv(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, const float* x, c
         return fail(NNPOPS_ERR_UNSUPPORTED, "CFConv tiles (%zu floats) do not fit in LDS", wfl + per_wave);
     const int wpb = (int)std::min<size_t>(kMaxWavesPerBlock, (budget - wfl) / per_wave);
     const size_t lds = (wfl + (size_t)wpb * per_wave) * sizeof(float);
-    auto k = cfconv_kernel<ACT, CPL, BWD, WLDS>;
+    auto k = cfconv_kernel<ACT, CPL, BWD, WLDS, ROW_S>;
     if (lds > 64 * 1024)
         NNPOPS_HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const int blocks = std::max(1, std::min(h->blocks, div_up(h->p.N, wpb)));
     hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * wpb), lds, h->stream, h->p, h->d_w1t, h->d_b1, h->d_w2t, h->d_b2,
-                       nb->d_rows, nb->d_cnt, nb->cap, x, gout, out, pos_grad);
+                       nb->d_rows, nb->d_cnt, nb->cap, x, gout, out, pos_grad, ROW_S ? h->d_row_s : (float*)nullptr);
     NNPOPS_HIP_TRY(hipGetLastError());
     return NNPOPS_OK;
 }
 
 // the vector kernels: weights in LDS when they fit beside one wave's tiles, else streamed through the caches
-template <bool BWD>
+template <bool BWD, bool ROW_S = false>
 int launch_vector(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, const float* x, const float* gout, float* out, float* pos_grad) {
     const size_t budget = 156 * 1024 / sizeof(float);
     const bool fits = conv_weight_floats(h->p.W, h->p.G) + conv_wave_floats(h->p.W, h->p.G, BWD) <= budget && h->p.W <= 128;
     if (fits) {
         const bool two = h->p.W > 64;
         if (h->p.activation == 0)
-            return two ? launch_conv<0, 2, BWD>(h, nb, x, gout, out, pos_grad) : launch_conv<0, 1, BWD>(h, nb, x, gout, out, pos_grad);
-        return two ? launch_conv<1, 2, BWD>(h, nb, x, gout, out, pos_grad) : launch_conv<1, 1, BWD>(h, nb, x, gout, out, pos_grad);
+            return two ? launch_conv<0, 2, BWD, true, ROW_S>(h, nb, x, gout, out, pos_grad) : launch_conv<0, 1, BWD, true, ROW_S>(h, nb, x, gout, out, pos_grad);
+        return two ? launch_conv<1, 2, BWD, true, ROW_S>(h, nb, x, gout, out, pos_grad) : launch_conv<1, 1, BWD, true, ROW_S>(h, nb, x, gout, out, pos_grad);
     }
     const int cpl = div_up(h->p.W, 64);
     if (h->p.activation == 0) {
-        if (cpl <= 2) return launch_conv<0, 2, BWD, false>(h, nb, x, gout, out, pos_grad);
-        if (cpl <= 4) return launch_conv<0, 4, BWD, false>(h, nb, x, gout, out, pos_grad);
-        return launch_conv<0, 8, BWD, false>(h, nb, x, gout, out, pos_grad);
+        if (cpl <= 2) return launch_conv<0, 2, BWD, false, ROW_S>(h, nb, x, gout, out, pos_grad);
+        if (cpl <= 4) return launch_conv<0, 4, BWD, false, ROW_S>(h, nb, x, gout, out, pos_grad);
+        return launch_conv<0, 8, BWD, false, ROW_S>(h, nb, x, gout, out, pos_grad);
     }
-    if (cpl <= 2) return launch_conv<1, 2, BWD, false>(h, nb, x, gout, out, pos_grad);
-    if (cpl <= 4) return launch_conv<1, 4, BWD, false>(h, nb, x, gout, out, pos_grad);
-    return launch_conv<1, 8, BWD, false>(h, nb, x, gout, out, pos_grad);
+    if (cpl <= 2) return launch_conv<1, 2, BWD, false, ROW_S>(h, nb, x, gout, out, pos_grad);
+    if (cpl <= 4) return launch_conv<1, 4, BWD, false, ROW_S>(h, nb, x, gout, out, pos_grad);
+    return launch_conv<1, 8, BWD, false, ROW_S>(h, nb, x, gout, out, pos_grad);
 }
 
 // the pair slots behind the neighbour rows and the convolution's filter-row buffers
@@ -682,6 +691,20 @@ int dispatch_conv(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, const float* x,
                                 : dispatch_half<1, BWD>(h, nb, x, gout, out, pos_grad);
 }
 
+// what a box-gradient call keeps beside the backward pass's own buffers (first use, or the neighbour rows have grown: not capturable)
+int ensure_box_buffers(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, bool row_s) {
+    int rc;
+    if (!h->d_box_partials && (rc = dev_alloc(&h->d_box_partials, (size_t)9 * cfconv_box_blocks(h->p.N)))) return rc;
+    const size_t need = (size_t)nb->N * nb->cap;
+    if (row_s && h->row_s_len < need) {
+        dev_free(h->d_row_s);
+        h->d_row_s = nullptr; h->row_s_len = 0;
+        if ((rc = dev_alloc(&h->d_row_s, need))) return rc;
+        h->row_s_len = need;
+    }
+    return NNPOPS_OK;
+}
+
 int check_pair(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb) {
     NNPOPS_REQUIRE(h != nullptr && nb != nullptr, "NULL handle");
     NNPOPS_REQUIRE(nb->built, "the neighbour list has not been built");
@@ -713,6 +736,37 @@ int nnpops_cfconv_backprop(nnpops_cfconv_t h, nnpops_cfconv_neighbors_t neighbor
     NNPOPS_REQUIRE(input && output_deriv && input_deriv && position_deriv, "NULL device pointer");
     DeviceGuard guard(h->device);
     return dispatch_conv<true>(h, neighbors, input, output_deriv, input_deriv, position_deriv);
+}
+
+int nnpops_cfconv_backprop_box(nnpops_cfconv_t h, nnpops_cfconv_neighbors_t neighbors, const float* positions, const float* box,
+                               const float* input, const float* output_deriv, float* input_deriv, float* position_deriv,
+                               float* box_deriv) {
+    int rc = check_pair(h, neighbors);
+    if (rc != NNPOPS_OK) return rc;
+    NNPOPS_REQUIRE(neighbors->periodic, "the box gradient needs a periodic neighbour list (this one was created without box vectors)");
+    NNPOPS_REQUIRE(positions && box && box_deriv, "NULL device pointer (the box gradient needs positions, box and box_deriv)");
+    NNPOPS_REQUIRE(input && output_deriv && input_deriv && position_deriv, "NULL device pointer");
+    DeviceGuard guard(h->device);
+    const bool row_s = h->path == ConvPath::kVector;
+    if ((rc = ensure_box_buffers(h, neighbors, row_s)) != NNPOPS_OK) return rc;
+    // the backward pass exactly as nnpops_cfconv_backprop launches it (the same kernels: the same bits); the vector path, which has no
+    // pair slots, then walks the rows once more for the pair scalar of every entry (cfconv_kernel<..., ROW_S>: a second evaluation of
+    // the filter network, on the path that is functional rather than tuned) ...
+    if ((rc = dispatch_conv<true>(h, neighbors, input, output_deriv, input_deriv, position_deriv)) != NNPOPS_OK) return rc;
+    if (row_s && (rc = launch_vector<true, true>(h, neighbors, input, output_deriv, nullptr, nullptr)) != NNPOPS_OK) return rc;
+    // ... then one pass over the rows and the pair scalars it left behind, and the sum of its workgroups (cfconv_box_grad.h)
+    const int N = h->p.N, nblocks = cfconv_box_blocks(N);
+    const float4* order = neighbors->cell_ordered ? neighbors->d_sorted_pos : nullptr;
+    if (row_s)
+        hipLaunchKernelGGL(cfconv_box_partials<true>, dim3(nblocks), dim3(kBoxThreads), 0, h->stream, N, positions, box, neighbors->d_rows,
+                           neighbors->d_cnt, neighbors->cap, (const int*)nullptr, 0, (const float*)h->d_row_s, order, h->d_box_partials);
+    else
+        hipLaunchKernelGGL(cfconv_box_partials<false>, dim3(nblocks), dim3(kBoxThreads), 0, h->stream, N, positions, box, neighbors->d_rows,
+                           neighbors->d_cnt, neighbors->cap, (const int*)neighbors->d_pid, neighbors->pair_cap(), (const float*)h->d_pair_s,
+                           order, h->d_box_partials);
+    hipLaunchKernelGGL(pairs_box_finish<float>, dim3(1), dim3(kBoxThreads), 0, h->stream, nblocks, (const double*)h->d_box_partials, box_deriv);
+    NNPOPS_HIP_TRY(hipGetLastError());
+    return NNPOPS_OK;
 }
 
 }  // extern "C"

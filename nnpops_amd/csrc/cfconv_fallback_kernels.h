@@ -2,6 +2,7 @@
 //
 //   cfconv_kernel         vector kernel, one wave per atom: widths that are not a multiple of 16, widths above 128 (weights streamed
 //                         through the caches), weights of the matrix-core kernels that do not fit in LDS, or $NNPOPS_CFCONV_VALU=1
+//                         (its ROW_S instantiations, launched by box-gradient calls only, store the pair scalar of every row entry)
 //   cfconv_filters_mfma   filters on the fp32 matrix instruction: widths 16, 48, 80, 112, weights outside the fp16 range, or
 //                         $NNPOPS_CFCONV_SPLIT=0
 //   cfconv_filters_h2     filters with layer 2 as split-fp16 products through LDS planes: widths 32, 64, 96, 128 with more than
@@ -46,13 +47,21 @@ __host__ __device__ inline size_t conv_wave_floats(int W, int G, bool backward) 
 // CPL = channels per lane (1: W <= 64, 2: W <= 128).  BACKWARD adds the d/dr path and the two gradients.
 // WLDS = false: the weights do not fit in LDS next to one wave's tiles (W > 128): they are read through the
 // caches instead.  Same arithmetic, a functional path for unusually wide layers, not a tuned one.
-template <int ACT, int CPL, bool BACKWARD, bool WLDS = true>
+// ROW_S (box-gradient calls only, behind the backward pass proper): the same walk stores the pair scalar sc of every row entry to
+// row_s[i][entry] for the box-gradient pass (cfconv_box_grad.h) and NOTHING else -- `out` and `pos_grad` are not written.  It is a
+// second launch and not a flag on the backward pass itself because the gradients of a box-gradient call have to be those of a plain
+// one to the bit: one more use of sc in the loop below makes the compiler pack and contract the force update differently (measured
+// on the ISA: 8 of its 24 updates per tile change between v_pk_mul + v_sub and v_fma), so an instantiation that did both would give
+// other last bits.  Every other instantiation ignores row_s (the host passes NULL) and is, instruction for instruction, what it was
+// without the argument.
+template <int ACT, int CPL, bool BACKWARD, bool WLDS = true, bool ROW_S = false>
 __global__ __launch_bounds__(64 * kMaxWavesPerBlock) void cfconv_kernel(
     ConvParams P, const float* __restrict__ w1t, const float* __restrict__ b1, const float* __restrict__ w2t,
     const float* __restrict__ b2, const float4* __restrict__ rows, const int* __restrict__ cnt, int cap,
     const float* __restrict__ x, const float* __restrict__ gout,   // gout: upstream gradient (backward only)
     float* __restrict__ out,                                       // forward: output ; backward: input gradient
-    float* __restrict__ pos_grad) {
+    float* __restrict__ pos_grad, float* __restrict__ row_s) {
+    static_assert(BACKWARD || !ROW_S, "the pair scalars belong to the backward pass");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int W = P.W, G = P.G;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -204,14 +213,15 @@ __global__ __launch_bounds__(64 * kMaxWavesPerBlock) void cfconv_kernel(
                     const float sc = wave_sum(scale_p[p]) * ps[4 * 8 + p];                    // * 1/r
                     // position_deriv[i] -= sc * delta  (owner side of ref :287-291; delta = pos_j - pos_i)
                     fx -= sc * ps[5 * 8 + p]; fy -= sc * ps[6 * 8 + p]; fz -= sc * ps[7 * 8 + p];
+                    if (ROW_S && lane == p && p < np) row_s[(size_t)i * cap + t0 + p] = sc;
                 }
             }
             __builtin_amdgcn_wave_barrier();
         }
 #pragma unroll
         for (int c = 0; c < CPL; c++)
-            if (live[c]) out[(size_t)i * W + ch[c]] = acc[c];
-        if (BACKWARD && lane == 0) {
+            if (live[c] && !ROW_S) out[(size_t)i * W + ch[c]] = acc[c];
+        if (BACKWARD && !ROW_S && lane == 0) {
             pos_grad[3 * i] = fx; pos_grad[3 * i + 1] = fy; pos_grad[3 * i + 2] = fz;
         }
     }

@@ -7,7 +7,7 @@
 //   torch.classes.NNPOpsANISymmetryFunctions.Holder / torch.ops.NNPOpsANISymmetryFunctions.operation
 //                                                         (reference src/pytorch/SymmetryFunctions.cpp:265-284)
 //   torch.classes.NNPOpsCFConvNeighbors.Holder            (reference src/pytorch/CFConvNeighbors.cpp:77-85)
-//   torch.classes.NNPOpsCFConv.Holder / torch.ops.NNPOpsCFConv.operation
+//   torch.classes.NNPOpsCFConv.Holder / torch.ops.NNPOpsCFConv.operation / operation_periodic (additive: dL/dbox)
 //                                                         (reference src/pytorch/CFConv.cpp:276-291)
 //   torch.ops.neighbors.getNeighborPairs                  (reference src/pytorch/neighbors/neighbors.cpp:4)
 //   torch.ops.NNPOpsBatchedNN.BatchedLinear               (reference src/pytorch/BatchedNN.cpp:48-50)
@@ -767,6 +767,7 @@ public:
         }
     }
     double getCutoff() const { return cutoff; }
+    bool isPeriodic() const { return periodic; }
     nnpops_cfconv_neighbors_t getImpl() const { return impl; }
 
 private:
@@ -873,6 +874,37 @@ public:
         return output;
     }
 
+    // Additive (operation_periodic): the same forward, to the bit, on a list built with box vectors; the box is kept next to the positions
+    // for a backward pass that returns dL/dbox (the box vectors must be those of the list's last build).
+    Tensor forwardPeriodic(const c10::IValue& neighbors_, const Tensor& positions_, const Tensor& box_, const Tensor& input_) {
+        if (box_.scalar_type() != torch::kFloat32) throw std::runtime_error("The type of \"box\" has to be float32");
+        if (box_.dim() != 2 || box_.size(0) != 3 || box_.size(1) != 3) throw std::runtime_error("The shape of \"box\" has to be (3, 3)");
+        require_device_tensor(box_, "box");
+        if (box_.device() != positions_.device()) throw std::runtime_error("The device of \"box\" and \"positions\" has to be the same");
+        const NeighborsPtr nb = neighbors_.toCustomClass<Neighbors>();
+        if (!nb->getImpl()) throw std::runtime_error("\"neighbors\" has not been built");
+        if (!nb->isPeriodic()) throw std::runtime_error("\"neighbors\" has been built without a box: a \"box\" needs a periodic neighbour list");
+        Tensor output = forward(neighbors_, positions_, input_);
+        box = box_.detach().contiguous();
+        return output;
+    }
+
+    // backward() and dL/dbox behind it (nnpops_cfconv_backprop_box): {holder, neighbours, positions, box, input}
+    tensor_list backwardBox(const tensor_list& grads) {
+        if (!impl || !box.defined()) throw std::runtime_error("backwardBox() called before forwardPeriodic()");
+        const Tensor outputGrad = grads[0].contiguous();
+        const auto opts = torch::TensorOptions().device(device).dtype(torch::kFloat32);
+        Tensor inputGrad = torch::empty({numAtoms, numFilters}, opts);
+        Tensor positionsGrad = torch::empty({numAtoms, 3}, opts);
+        Tensor boxGrad = torch::empty({3, 3}, opts);
+        nnpops_cfconv_set_stream(impl, current_stream(device));
+        if (nnpops_cfconv_backprop_box(impl, neighbors->getImpl(), positions.data_ptr<float>(), box.data_ptr<float>(), input.data_ptr<float>(),
+                                       outputGrad.data_ptr<float>(), inputGrad.data_ptr<float>(), positionsGrad.data_ptr<float>(),
+                                       boxGrad.data_ptr<float>()) != NNPOPS_OK)
+            raise_last("NNPOpsCFConv::backward");
+        return {Tensor(), Tensor(), positionsGrad, boxGrad, inputGrad};
+    }
+
     tensor_list backward(const tensor_list& grads) {
         if (!impl) throw std::runtime_error("backward() called before forward()");
         const Tensor outputGrad = grads[0].contiguous();
@@ -922,7 +954,7 @@ private:
     int64_t numAtoms = 0, numFilters = 0;
     double cutoff = 0;
     NeighborsPtr neighbors;
-    Tensor positions, input;
+    Tensor positions, input, box;
     nnpops_cfconv_t impl = nullptr;
 };
 
@@ -940,9 +972,39 @@ public:
     }
 };
 
+// `boxGrad` (decided by the caller, where grad mode is what the user set) = the box vectors require a gradient: the node's backward then
+// runs the box-gradient pass behind the usual launches and fills the box's slot; otherwise it is the plain backward and the slot stays empty.
+class PeriodicAutogradFunctions : public torch::autograd::Function<PeriodicAutogradFunctions> {
+public:
+    static Tensor forward(AutogradContext* ctx, const HolderPtr& holder, const c10::IValue& neighbors, const Tensor& positions,
+                          const Tensor& box, const Tensor& input, bool boxGrad) {
+        ctx->saved_data["holder"] = holder;
+        ctx->saved_data["box_grad"] = boxGrad;
+        return holder->forwardPeriodic(neighbors, positions, box, input);
+    }
+    static tensor_list backward(AutogradContext* ctx, const tensor_list& grads) {
+        const HolderPtr holder = ctx->saved_data["holder"].toCustomClass<Holder>();
+        ctx->saved_data.erase("holder");
+        tensor_list out;
+        if (ctx->saved_data["box_grad"].toBool()) {
+            out = holder->backwardBox(grads);
+        } else {
+            out = holder->backward(grads);                   // {holder, neighbours, positions, input}
+            out.insert(out.begin() + 3, Tensor());           // (no gradient for the box)
+        }
+        out.push_back(Tensor());
+        return out;
+    }
+};
+
 Tensor operation(const c10::optional<HolderPtr>& holder, const c10::IValue& neighbors, const Tensor& positions,
                  const Tensor& input) {
     return AutogradFunctions::apply(*holder, neighbors, positions, input);
+}
+
+Tensor operation_periodic(const c10::optional<HolderPtr>& holder, const c10::IValue& neighbors, const Tensor& positions,
+                          const Tensor& box, const Tensor& input) {
+    return PeriodicAutogradFunctions::apply(*holder, neighbors, positions, box, input, torch::GradMode::is_enabled() && box.requires_grad());
 }
 
 TORCH_LIBRARY(NNPOpsCFConv, m) {
@@ -953,6 +1015,7 @@ TORCH_LIBRARY(NNPOpsCFConv, m) {
         .def_pickle([](const HolderPtr& self) -> std::string { return Holder::serialize(self); },
                     [](const std::string& state) -> HolderPtr { return Holder::deserialize(state); });
     m.def("operation", operation);
+    m.def("operation_periodic", operation_periodic);
 }
 
 }  // namespace CFConv
