@@ -14,6 +14,7 @@
  *   nnpops_cfconv_neighbors_*        CFConvNeighbors ctor / build          src/schnet/CFConv.h:37-85
  *   nnpops_cfconv_create / compute / backprop   CFConv ctor / compute / backprop   src/schnet/CFConv.h:109-217
  *   nnpops_cfconv_backprop_box       (additive) backprop and the box-vector gradient of a periodic list
+ *   nnpops_cfconv_double_backward    (additive) the backward of backprop: second derivatives w.r.t. positions and input
  *   nnpops_neighbor_pairs_forward / _backward   neighbors::getNeighborPairs forward/backward kernels
  *                                               src/pytorch/neighbors/getNeighborPairsCUDA.cu:31-101
  *   nnpops_neighbor_pairs_box_backward / _double_backward   box gradient and second derivatives of that op
@@ -257,6 +258,21 @@ int nnpops_cfconv_backprop(nnpops_cfconv_t h, nnpops_cfconv_neighbors_t neighbor
 int nnpops_cfconv_backprop_box(nnpops_cfconv_t h, nnpops_cfconv_neighbors_t neighbors, const float* positions,
                                const float* box, const float* input, const float* output_deriv, float* input_deriv,
                                float* position_deriv, float* box_deriv);
+/* The backward of nnpops_cfconv_backprop (second derivatives for training on forces and Hessian-vector products).  backprop maps
+ * (output_deriv g, input x, positions) to input_deriv gx and position_deriv gp; with cotangents gg_input_deriv V [N][W] of gx and
+ * gg_position_deriv Q [N][3] of gp this returns the gradients of M = <V, gx> + <Q, gp>:
+ *     out_output_deriv [N][W] = dM/dg,   out_input [N][W] = dM/dx,   out_positions [N][3] = dM/dpositions
+ * with the pair set and the minimum-image shifts of the list's last build() held fixed (no gradient flows into the list, none into
+ * the box; the filter network's weights are constants).  Either cotangent may be NULL, meaning zero, but not both.  The three outputs
+ * are fully overwritten.  One owner-computes kernel over the neighbour rows: no atomics (two calls agree bit for bit), no scratch, no
+ * allocation and no host synchronisation, so it can be captured into a HIP graph; it runs on the convolution's stream and leaves what
+ * compute / backprop keep between calls untouched.  positions is not read (the list stores the displacements of its build). */
+int nnpops_cfconv_double_backward(nnpops_cfconv_t h, nnpops_cfconv_neighbors_t neighbors, const float* positions, const float* input,
+                                  const float* output_deriv, const float* gg_input_deriv, const float* gg_position_deriv,
+                                  float* out_output_deriv, float* out_input, float* out_positions);
+/* The number of the list's last build (a process-wide counter, never 0 for a built list; 0 before the first build): what was
+ * computed for one build of a list may be told apart from a later one. */
+int nnpops_cfconv_neighbors_build_count(nnpops_cfconv_neighbors_t h, unsigned long long* count);
 
 /* ------------------------------------------------------------------------------------------
  * getNeighborPairs (replaces the neighbors::getNeighborPairs CUDA kernels)

@@ -68,6 +68,9 @@ SIGNATURES = {
                                          C.c_void_p, C.c_void_p]),
     "nnpops_cfconv_backprop_box": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nnpops_cfconv_double_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nnpops_cfconv_neighbors_build_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "nnpops_split_planes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p, C.c_long]),
     "nnpops_rows_dot": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "nnpops_gemm_split": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_long, C.c_void_p,
@@ -735,6 +738,12 @@ class CFConvNeighbors:
         _check(self._lib.nnpops_cfconv_neighbors_check(self._h, C.byref(n)))
         return n.value
 
+    def build_count(self):
+        """The number of the last build (a process-wide counter; 0 before the first build)."""
+        n = C.c_ulonglong(0)
+        _check(self._lib.nnpops_cfconv_neighbors_build_count(self._h, C.byref(n)))
+        return n.value
+
     def read_grid(self):
         """The cell grid of the last build() that went through one, as AniSymmetryFunctions.read_grid (blocks; diagnostics only)."""
         words = (C.c_int32 * 8)()
@@ -816,6 +825,24 @@ class CFConv:
         _check(self._lib.nnpops_cfconv_backprop_box(self._h, neighbors._h, _ptr(positions), _ptr(box), _ptr(x), _ptr(out_grad),
                                                     _ptr(x_grad), _ptr(pos_grad), _ptr(box_grad)))
         return x_grad, pos_grad, box_grad
+
+    def double_backward(self, neighbors, positions, x, out_grad, gg_x=None, gg_pos=None):
+        """The backward of backprop(): with cotangents ``gg_x`` (N, W) of its input gradient and ``gg_pos`` (N, 3) of its position
+        gradient (either may be None = zero, not both) -> the gradients of <gg_x, x_grad> + <gg_pos, pos_grad> with respect to
+        (out_grad, x, positions), the pair list of the last build() held fixed."""
+        _dev_f32(positions, "positions", (self.num_atoms, 3))
+        _dev_f32(x, "input", (self.num_atoms, self.width))
+        _dev_f32(out_grad, "output_grad", (self.num_atoms, self.width))
+        if gg_x is not None:
+            _dev_f32(gg_x, "gg_input_grad", (self.num_atoms, self.width))
+        if gg_pos is not None:
+            _dev_f32(gg_pos, "gg_position_grad", (self.num_atoms, 3))
+        d_out_grad, d_x = torch.empty_like(x), torch.empty_like(x)
+        d_pos = torch.empty((self.num_atoms, 3), dtype=torch.float32, device=x.device)
+        _check(self._lib.nnpops_cfconv_set_stream(self._h, _stream_ptr(x.device)))
+        _check(self._lib.nnpops_cfconv_double_backward(self._h, neighbors._h, _ptr(positions), _ptr(x), _ptr(out_grad), _ptr(gg_x),
+                                                       _ptr(gg_pos), _ptr(d_out_grad), _ptr(d_x), _ptr(d_pos)))
+        return d_out_grad, d_x, d_pos
 
 
 # ---- dense layers (batched_nn.hip) ----

@@ -30,6 +30,8 @@
 // handles, the weight preparation, the choice of kernels and the C ABI.
 // nnpops_cfconv_backprop_box adds dL/dbox of a periodic list behind the backward pass: one reduction over the wrapped pairs of what
 // that pass leaves on the device (cfconv_box_grad.h).
+// nnpops_cfconv_double_backward is the backward of the backward pass with respect to output_deriv, input and positions: one
+// owner-computes pass over the full rows that keeps nothing between calls (cfconv_second_order.h).
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -41,6 +43,7 @@
 #include "cfconv_build.h"
 #include "cfconv_fallback_kernels.h"
 #include "cfconv_filters.h"
+#include "cfconv_second_order.h"
 #include "host_common.h"
 
 using namespace nnpops;
@@ -253,6 +256,12 @@ int nnpops_cfconv_neighbors_build(nnpops_cfconv_neighbors_t h, const float* posi
     h->epoch = ++build_counter;
     h->cell_ordered = use_cells;
     if (h->want_half) return launch_half_build(h, h->stream);
+    return NNPOPS_OK;
+}
+
+int nnpops_cfconv_neighbors_build_count(nnpops_cfconv_neighbors_t h, unsigned long long* count) {
+    NNPOPS_REQUIRE(h != nullptr && count != nullptr, "NULL argument");
+    *count = h->built ? h->epoch : 0;       // 0: never built, or the last build was rejected by check()
     return NNPOPS_OK;
 }
 
@@ -705,6 +714,71 @@ int ensure_box_buffers(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, bool row_s
     return NNPOPS_OK;
 }
 
+// The double backward (cfconv_second_order.h).  The family is a matter of the width and of LDS alone: the fp32 matrix instruction where
+// W is a multiple of 16 up to 128 and both weight matrices fit in LDS beside one wave's tile, else the vector kernel.
+template <int ACT, int NCB>
+int launch_second_mfma(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, const float* x, const float* g, const float* V, const float* Q,
+                       float* out_g, float* out_x, float* out_pos) {
+    const size_t budget = 160 * 1024 / sizeof(float);
+    const size_t wfl = mfma_weight_floats(h->p.W, h->p.G), per_wave = second_mfma_wave_floats(h->p.W);
+    constexpr int waves = NCB > 4 ? 4 : kMaxWavesPerBlock;
+    const int wpb = (int)std::min<size_t>(waves, (budget - wfl) / per_wave);
+    const size_t lds = (wfl + (size_t)wpb * per_wave) * sizeof(float);
+    auto k = cfconv_second_mfma<ACT, NCB, waves>;
+    if (lds > 64 * 1024)
+        NNPOPS_HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int blocks = std::max(1, std::min(h->blocks, div_up(h->p.N, wpb)));
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * wpb), lds, h->stream, h->p, h->d_w1t, h->d_b1, h->d_w2t, h->d_b2, nb->d_rows, nb->d_cnt,
+                       nb->cap, nb->cell_ordered ? nb->d_sorted_pos : (const float4*)nullptr, x, g, V, Q, out_g, out_x, out_pos);
+    NNPOPS_HIP_TRY(hipGetLastError());
+    return NNPOPS_OK;
+}
+
+template <int ACT, int CPL, bool WLDS>
+int launch_second_vector(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, const float* x, const float* g, const float* V, const float* Q,
+                         float* out_g, float* out_x, float* out_pos) {
+    const size_t budget = 156 * 1024 / sizeof(float);
+    const size_t wfl = WLDS ? conv_weight_floats(h->p.W, h->p.G) : 0, per_wave = second_wave_floats(h->p.W, h->p.G);
+    if (wfl + per_wave > budget)
+        return fail(NNPOPS_ERR_UNSUPPORTED, "CFConv tiles (%zu floats) do not fit in LDS", wfl + per_wave);
+    const int wpb = (int)std::min<size_t>(kMaxWavesPerBlock, (budget - wfl) / per_wave);
+    const size_t lds = (wfl + (size_t)wpb * per_wave) * sizeof(float);
+    auto k = cfconv_second_vector<ACT, CPL, WLDS>;
+    if (lds > 64 * 1024)
+        NNPOPS_HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int blocks = std::max(1, std::min(h->blocks, div_up(h->p.N, wpb)));
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * wpb), lds, h->stream, h->p, h->d_w1t, h->d_b1, h->d_w2t, h->d_b2, nb->d_rows, nb->d_cnt,
+                       nb->cap, nb->cell_ordered ? nb->d_sorted_pos : (const float4*)nullptr, x, g, V, Q, out_g, out_x, out_pos);
+    NNPOPS_HIP_TRY(hipGetLastError());
+    return NNPOPS_OK;
+}
+
+template <int ACT>
+int dispatch_second(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, const float* x, const float* g, const float* V, const float* Q,
+                    float* out_g, float* out_x, float* out_pos) {
+    const int W = h->p.W, G = h->p.G;
+    if (W % 16 == 0 && W <= 128 && mfma_weight_floats(W, G) + second_mfma_wave_floats(W) <= (size_t)160 * 1024 / sizeof(float)) {
+        switch (W) {
+            case 16:  return launch_second_mfma<ACT, 1>(h, nb, x, g, V, Q, out_g, out_x, out_pos);
+            case 32:  return launch_second_mfma<ACT, 2>(h, nb, x, g, V, Q, out_g, out_x, out_pos);
+            case 48:  return launch_second_mfma<ACT, 3>(h, nb, x, g, V, Q, out_g, out_x, out_pos);
+            case 64:  return launch_second_mfma<ACT, 4>(h, nb, x, g, V, Q, out_g, out_x, out_pos);
+            case 80:  return launch_second_mfma<ACT, 5>(h, nb, x, g, V, Q, out_g, out_x, out_pos);
+            case 96:  return launch_second_mfma<ACT, 6>(h, nb, x, g, V, Q, out_g, out_x, out_pos);
+            case 112: return launch_second_mfma<ACT, 7>(h, nb, x, g, V, Q, out_g, out_x, out_pos);
+            default:  return launch_second_mfma<ACT, 8>(h, nb, x, g, V, Q, out_g, out_x, out_pos);
+        }
+    }
+    const size_t budget = 156 * 1024 / sizeof(float);
+    if (W <= 128 && conv_weight_floats(W, G) + second_wave_floats(W, G) <= budget)
+        return W > 64 ? launch_second_vector<ACT, 2, true>(h, nb, x, g, V, Q, out_g, out_x, out_pos)
+                      : launch_second_vector<ACT, 1, true>(h, nb, x, g, V, Q, out_g, out_x, out_pos);
+    const int cpl = div_up(W, 64);
+    if (cpl <= 2) return launch_second_vector<ACT, 2, false>(h, nb, x, g, V, Q, out_g, out_x, out_pos);
+    if (cpl <= 4) return launch_second_vector<ACT, 4, false>(h, nb, x, g, V, Q, out_g, out_x, out_pos);
+    return launch_second_vector<ACT, 8, false>(h, nb, x, g, V, Q, out_g, out_x, out_pos);
+}
+
 int check_pair(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb) {
     NNPOPS_REQUIRE(h != nullptr && nb != nullptr, "NULL handle");
     NNPOPS_REQUIRE(nb->built, "the neighbour list has not been built");
@@ -767,6 +841,20 @@ int nnpops_cfconv_backprop_box(nnpops_cfconv_t h, nnpops_cfconv_neighbors_t neig
     hipLaunchKernelGGL(pairs_box_finish<float>, dim3(1), dim3(kBoxThreads), 0, h->stream, nblocks, (const double*)h->d_box_partials, box_deriv);
     NNPOPS_HIP_TRY(hipGetLastError());
     return NNPOPS_OK;
+}
+
+int nnpops_cfconv_double_backward(nnpops_cfconv_t h, nnpops_cfconv_neighbors_t neighbors, const float* positions, const float* input,
+                                  const float* output_deriv, const float* gg_input_deriv, const float* gg_position_deriv,
+                                  float* out_output_deriv, float* out_input, float* out_positions) {
+    (void)positions;                // displacements were stored by build() from the same positions
+    int rc = check_pair(h, neighbors);
+    if (rc != NNPOPS_OK) return rc;
+    NNPOPS_REQUIRE(input && output_deriv && out_output_deriv && out_input && out_positions, "NULL device pointer");
+    NNPOPS_REQUIRE(gg_input_deriv || gg_position_deriv, "gg_input_deriv and gg_position_deriv are both NULL: nothing to differentiate");
+    DeviceGuard guard(h->device);
+    return h->p.activation == 0
+               ? dispatch_second<0>(h, neighbors, input, output_deriv, gg_input_deriv, gg_position_deriv, out_output_deriv, out_input, out_positions)
+               : dispatch_second<1>(h, neighbors, input, output_deriv, gg_input_deriv, gg_position_deriv, out_output_deriv, out_input, out_positions);
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 //                                                         (reference src/pytorch/SymmetryFunctions.cpp:265-284)
 //   torch.classes.NNPOpsCFConvNeighbors.Holder            (reference src/pytorch/CFConvNeighbors.cpp:77-85)
 //   torch.classes.NNPOpsCFConv.Holder / torch.ops.NNPOpsCFConv.operation / operation_periodic (additive: dL/dbox)
+//   torch.ops.NNPOpsCFConv.operation_twice / operation_periodic_twice (additive: the same ops, twice differentiable)
 //                                                         (reference src/pytorch/CFConv.cpp:276-291)
 //   torch.ops.neighbors.getNeighborPairs                  (reference src/pytorch/neighbors/neighbors.cpp:4)
 //   torch.ops.NNPOpsBatchedNN.BatchedLinear               (reference src/pytorch/BatchedNN.cpp:48-50)
@@ -769,6 +770,12 @@ public:
     double getCutoff() const { return cutoff; }
     bool isPeriodic() const { return periodic; }
     nnpops_cfconv_neighbors_t getImpl() const { return impl; }
+    // the number of the last build (0: never built): the twice-differentiable ops record it and refuse to differentiate on a later one
+    int64_t getBuildCount() const {
+        unsigned long long count = 0;
+        if (impl && nnpops_cfconv_neighbors_build_count(impl, &count) != NNPOPS_OK) raise_last("NNPOpsCFConvNeighbors");
+        return (int64_t)count;
+    }
 
 private:
     double cutoff;
@@ -784,6 +791,7 @@ TORCH_LIBRARY(NNPOpsCFConvNeighbors, m) {
         .def(torch::init<double>())
         .def("build", &Holder::build)
         .def("build_periodic", &Holder::buildPeriodic)
+        .def("build_count", &Holder::getBuildCount)
         .def_pickle([](const HolderPtr& self) -> double { return self->getCutoff(); },
                     [](double cutoff) -> HolderPtr { return HolderPtr::make(cutoff); });
 }
@@ -918,6 +926,42 @@ public:
         return {Tensor(), Tensor(), positionsGrad, inputGrad};    // nothing for the holder and the neighbours (:189)
     }
 
+    // The twice-differentiable ops (operation_twice / operation_periodic_twice) keep their tensors in their own autograd contexts, not in
+    // the slot above: the backward pass on what the caller hands over (the routine and the bits of backward()) ...
+    tensor_list backwardOf(const NeighborsPtr& nb, const Tensor& positions_, const Tensor& input_, const Tensor& outputGrad_) {
+        if (!impl) throw std::runtime_error("backward() called before forward()");
+        const Tensor pos = positions_.detach().contiguous(), in = input_.detach().contiguous(), outputGrad = outputGrad_.detach().contiguous();
+        const auto opts = torch::TensorOptions().device(device).dtype(torch::kFloat32);
+        Tensor inputGrad = torch::empty({numAtoms, numFilters}, opts);
+        Tensor positionsGrad = torch::empty({numAtoms, 3}, opts);
+        nnpops_cfconv_set_stream(impl, current_stream(device));
+        if (nnpops_cfconv_backprop(impl, nb->getImpl(), pos.data_ptr<float>(), nullptr, in.data_ptr<float>(), outputGrad.data_ptr<float>(),
+                                   inputGrad.data_ptr<float>(), positionsGrad.data_ptr<float>()) != NNPOPS_OK)
+            raise_last("NNPOpsCFConv::backward");
+        return {inputGrad, positionsGrad};
+    }
+
+    // ... and its backward (nnpops_cfconv_double_backward): cotangents of the two gradients (either may be undefined = zero) to the
+    // gradients with respect to {outputGrad, input, positions}
+    tensor_list doubleBackward(const NeighborsPtr& nb, const Tensor& positions_, const Tensor& input_, const Tensor& outputGrad_,
+                               const Tensor& ggInput_, const Tensor& ggPositions_) {
+        if (!impl) throw std::runtime_error("backward() called before forward()");
+        const Tensor pos = positions_.detach().contiguous(), in = input_.detach().contiguous(), outputGrad = outputGrad_.detach().contiguous();
+        Tensor ggInput, ggPositions;
+        if (ggInput_.defined()) ggInput = ggInput_.detach().to(torch::kFloat32).contiguous();
+        if (ggPositions_.defined()) ggPositions = ggPositions_.detach().to(torch::kFloat32).contiguous();
+        const auto opts = torch::TensorOptions().device(device).dtype(torch::kFloat32);
+        Tensor dOutputGrad = torch::empty({numAtoms, numFilters}, opts), dInput = torch::empty({numAtoms, numFilters}, opts);
+        Tensor dPositions = torch::empty({numAtoms, 3}, opts);
+        nnpops_cfconv_set_stream(impl, current_stream(device));
+        if (nnpops_cfconv_double_backward(impl, nb->getImpl(), pos.data_ptr<float>(), in.data_ptr<float>(), outputGrad.data_ptr<float>(),
+                                          ggInput.defined() ? ggInput.data_ptr<float>() : nullptr,
+                                          ggPositions.defined() ? ggPositions.data_ptr<float>() : nullptr, dOutputGrad.data_ptr<float>(),
+                                          dInput.data_ptr<float>(), dPositions.data_ptr<float>()) != NNPOPS_OK)
+            raise_last("NNPOpsCFConv::operation_twice (double backward)");
+        return {dOutputGrad, dInput, dPositions};
+    }
+
     static std::string serialize(const HolderPtr& self) {
         torch::serialize::OutputArchive archive;
         archive.write("gaussianWidth", self->gaussianWidth);
@@ -1007,6 +1051,93 @@ Tensor operation_periodic(const c10::optional<HolderPtr>& holder, const c10::IVa
     return PeriodicAutogradFunctions::apply(*holder, neighbors, positions, box, input, torch::GradMode::is_enabled() && box.requires_grad());
 }
 
+// ---------------------------------------------------------------------------------------------
+// operation_twice / operation_periodic_twice: the forward and the first backward of operation / operation_periodic (Holder::forward,
+// nnpops_cfconv_backprop: the same kernels and bits), recorded so that the backward pass is itself differentiable with respect to
+// the output gradient, the positions and the input.
+//     CFConvBackwardFunction         (g, positions, input) -> (gx, gp); keeps its tensors in its own context
+//     CFConvDoubleBackwardFunction   (V, Q, g, positions, input) -> (dM/dg, dM/dx, dM/dpositions), nnpops_cfconv_double_backward
+// Every node records the number of the list's build in the forward pass and raises on another: the rows it would walk belong to
+// other positions.  No box gradient (operation_periodic has it) and no third derivative: both raise.
+// ---------------------------------------------------------------------------------------------
+inline void check_same_build(const NeighborsPtr& nb, int64_t build) {
+    TORCH_CHECK(nb->getBuildCount() == build, "NNPOpsCFConv::operation_twice: \"neighbors\" has been rebuilt since the forward pass; its rows "
+                "no longer belong to the positions this gradient is taken at (build the list, run the forward pass and differentiate "
+                "before building it again)");
+}
+
+class CFConvDoubleBackwardFunction : public torch::autograd::Function<CFConvDoubleBackwardFunction> {
+public:
+    // (a cotangent nobody asked for arrives undefined -- CFConvBackwardFunction does not materialise zeros -- and travels as nullopt)
+    static tensor_list forward(AutogradContext*, const c10::optional<Tensor>& ggInput, const c10::optional<Tensor>& ggPositions, const Tensor& g,
+                               const Tensor& positions, const Tensor& input, const HolderPtr& holder, const c10::IValue& neighbors,
+                               int64_t build) {
+        const NeighborsPtr nb = neighbors.toCustomClass<Neighbors>();
+        check_same_build(nb, build);
+        return holder->doubleBackward(nb, positions, input, g, ggInput ? *ggInput : Tensor(), ggPositions ? *ggPositions : Tensor());
+    }
+    static tensor_list backward(AutogradContext*, tensor_list) {
+        TORCH_CHECK(false, "NNPOpsCFConv::operation_twice: third derivatives are not implemented");
+        return {};
+    }
+};
+
+class CFConvBackwardFunction : public torch::autograd::Function<CFConvBackwardFunction> {
+public:
+    static tensor_list forward(AutogradContext* ctx, const Tensor& g, const Tensor& positions, const Tensor& input, const HolderPtr& holder,
+                               const c10::IValue& neighbors, int64_t build) {
+        const NeighborsPtr nb = neighbors.toCustomClass<Neighbors>();
+        check_same_build(nb, build);
+        ctx->set_materialize_grads(false);
+        ctx->save_for_backward({g, positions, input});
+        ctx->saved_data["holder"] = holder;
+        ctx->saved_data["neighbors"] = neighbors;
+        ctx->saved_data["build"] = build;
+        return holder->backwardOf(nb, positions, input, g);
+    }
+    static tensor_list backward(AutogradContext* ctx, tensor_list grads) {
+        if (!grads[0].defined() && !grads[1].defined()) return {Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+        const auto s = ctx->get_saved_variables();
+        const auto given = [](const Tensor& t) { return t.defined() ? c10::optional<Tensor>(t) : c10::optional<Tensor>(); };
+        const tensor_list d = CFConvDoubleBackwardFunction::apply(given(grads[0]), given(grads[1]), s[0], s[1], s[2],
+                                                                  ctx->saved_data["holder"].toCustomClass<Holder>(),
+                                                                  ctx->saved_data["neighbors"], ctx->saved_data["build"].toInt());
+        return {d[0], d[2], d[1], Tensor(), Tensor(), Tensor()};
+    }
+};
+
+// (periodic: the box is an input only so that the op has operation_periodic's schema; its slot stays empty)
+class CFConvTwiceFunction : public torch::autograd::Function<CFConvTwiceFunction> {
+public:
+    static Tensor forward(AutogradContext* ctx, const HolderPtr& holder, const c10::IValue& neighbors, const Tensor& positions,
+                          const c10::optional<Tensor>& box, const Tensor& input) {
+        const Tensor output = box ? holder->forwardPeriodic(neighbors, positions, *box, input) : holder->forward(neighbors, positions, input);
+        ctx->save_for_backward({positions, input});
+        ctx->saved_data["holder"] = holder;
+        ctx->saved_data["neighbors"] = neighbors;
+        ctx->saved_data["build"] = neighbors.toCustomClass<Neighbors>()->getBuildCount();
+        return output;
+    }
+    static tensor_list backward(AutogradContext* ctx, tensor_list grads) {
+        const auto s = ctx->get_saved_variables();
+        const tensor_list d = CFConvBackwardFunction::apply(grads[0], s[0], s[1], ctx->saved_data["holder"].toCustomClass<Holder>(),
+                                                            ctx->saved_data["neighbors"], ctx->saved_data["build"].toInt());
+        return {Tensor(), Tensor(), d[1], Tensor(), d[0]};
+    }
+};
+
+Tensor operation_twice(const c10::optional<HolderPtr>& holder, const c10::IValue& neighbors, const Tensor& positions, const Tensor& input) {
+    return CFConvTwiceFunction::apply(*holder, neighbors, positions, c10::optional<Tensor>(), input);
+}
+
+Tensor operation_periodic_twice(const c10::optional<HolderPtr>& holder, const c10::IValue& neighbors, const Tensor& positions,
+                                const Tensor& box, const Tensor& input) {
+    TORCH_CHECK(!(torch::GradMode::is_enabled() && box.requires_grad()),
+                "NNPOpsCFConv::operation_periodic_twice: box gradients need the default op (operation_periodic; CFConv without "
+                "twice_differentiable=True): the twice-differentiable ops return no box gradient");
+    return CFConvTwiceFunction::apply(*holder, neighbors, positions, c10::optional<Tensor>(box), input);
+}
+
 TORCH_LIBRARY(NNPOpsCFConv, m) {
     m.class_<Holder>("Holder")
         .def(torch::init<double, const std::string&, const Tensor&, const Tensor&, const Tensor&, const Tensor&>())
@@ -1016,6 +1147,8 @@ TORCH_LIBRARY(NNPOpsCFConv, m) {
                     [](const std::string& state) -> HolderPtr { return Holder::deserialize(state); });
     m.def("operation", operation);
     m.def("operation_periodic", operation_periodic);
+    m.def("operation_twice", operation_twice);
+    m.def("operation_periodic_twice", operation_periodic_twice);
 }
 
 }  // namespace CFConv
