@@ -481,7 +481,7 @@ int nnpops_pme_reciprocal_box_gradient(int num_atoms, int gridx, int gridy, int 
  *      (both fully overwritten; the caller scales them by the energy's grad_output).
  * workspace: the buffer of steps 1-5 of the SAME evaluation, unchanged since (steps 7-9 only read its splines and bricks; step 8
  * overwrites its energy partials).  second_workspace: nnpops_pme_reciprocal_second_workspace_bytes(...) bytes, the same buffer for 7 and 9
- * (second-derivative weights and the fractional directions).  positions, charges, box_vectors: as passed to step 1.  Orders 4 and 5.
+ * (the spline weights and their first and second differences in double, and the fractional directions).  positions, charges, box_vectors: as passed to step 1.  Orders 4 and 5.
  * No atomics: bitwise reproducible.  No host synchronisation (graph-capturable). */
 int64_t nnpops_pme_reciprocal_second_workspace_bytes(int num_atoms, int gridx, int gridy, int gridz, int order);
 int nnpops_pme_reciprocal_spread_directional(int num_atoms, int gridx, int gridy, int gridz, int order, const float* positions,

@@ -535,10 +535,14 @@ def pme_direct(positions, charges, neighbors, deltas, distances, exclusions, alp
     return energy, pos_deriv, charge_deriv
 
 
-def pme_reciprocal(positions, charges, box_vectors, gridx, gridy, gridz, order, alpha, coulomb, xmoduli, ymoduli, zmoduli):
-    """Reciprocal-space PME (reference src/pytorch/pme/pmeCUDA.cu:102-430) through the C ABI: spread -> torch.fft.rfftn ->
-    convolve -> torch.fft.irfftn(norm="forward") -> interpolate.  -> (energy float32[1] without the self energy, dE/dpositions
-    [N, 3], dE/dcharges [N]).  Orders 4 and 5."""
+_PASSES_GUARD, _PASSES_PATTERN = 4096, 0xA5
+
+
+def pme_reciprocal_passes(positions, charges, box_vectors, gridx, gridy, gridz, order, alpha, coulomb, xmoduli, ymoduli, zmoduli):
+    """pme_reciprocal with every pass's output kept: -> (real grid [Kx, Ky, Kz] of the spread, complex grid [Kx, Ky, Kz/2 + 1] before
+    scaling, scaled complex grid, potential grid (irfftn, norm="forward"), energy float32[1], dE/dpositions [N, 3], dE/dcharges [N]).
+    The real grid starts as NaN (the spread writes every point exactly once and needs no clearing), and the workspace is exactly
+    nnpops_pme_reciprocal_workspace_bytes long, 256-byte aligned and followed by a guard pattern: a pass that writes past it raises."""
     _dev_f32(positions, "positions")
     _dev_f32(charges, "charges")
     _dev_f32(box_vectors, "box_vectors", (3, 3))
@@ -547,21 +551,35 @@ def pme_reciprocal(positions, charges, box_vectors, gridx, gridy, gridz, order, 
     mods = [_dev_f32(m.to(device=dev, dtype=torch.float32).contiguous(), name, (k,))
             for m, name, k in ((xmoduli, "xmoduli", gridx), (ymoduli, "ymoduli", gridy), (zmoduli, "zmoduli", gridz))]
     L = lib()
-    ws = torch.empty((int(L.nnpops_pme_reciprocal_workspace_bytes(n, gridx, gridy, gridz, order)),), dtype=torch.uint8, device=dev)
-    real = torch.empty((gridx, gridy, gridz), dtype=torch.float32, device=dev)
+    nbytes = int(L.nnpops_pme_reciprocal_workspace_bytes(n, gridx, gridy, gridz, order))
+    buf = torch.full((nbytes + _PASSES_GUARD + 256,), _PASSES_PATTERN, dtype=torch.uint8, device=dev)
+    off = (-buf.data_ptr()) % 256
+    ws = C.c_void_p(buf.data_ptr() + off)
+    real = torch.full((gridx, gridy, gridz), float("nan"), dtype=torch.float32, device=dev)
     energy = torch.empty((1,), dtype=torch.float32, device=dev)
     pos_deriv = torch.empty((n, 3), dtype=torch.float32, device=dev)
     charge_deriv = torch.empty((n,), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         _check(L.nnpops_pme_reciprocal_spread(n, gridx, gridy, gridz, order, _ptr(positions), _ptr(charges), _ptr(box_vectors),
-                                              float(coulomb), _ptr(real), _ptr(ws), _stream_ptr(dev)))
-        recip = torch.fft.rfftn(real).contiguous()
+                                              float(coulomb), _ptr(real), ws, _stream_ptr(dev)))
+        before = torch.fft.rfftn(real).contiguous()
+        recip = before.clone()
         _check(L.nnpops_pme_reciprocal_convolve(n, gridx, gridy, gridz, order, _ptr(box_vectors), float(alpha), _ptr(mods[0]),
-                                                _ptr(mods[1]), _ptr(mods[2]), _ptr(recip), _ptr(energy), _ptr(ws), _stream_ptr(dev)))
+                                                _ptr(mods[1]), _ptr(mods[2]), _ptr(recip), _ptr(energy), ws, _stream_ptr(dev)))
         grid = torch.fft.irfftn(recip, s=(gridx, gridy, gridz), norm="forward").contiguous()
         _check(L.nnpops_pme_reciprocal_interpolate(n, gridx, gridy, gridz, order, _ptr(charges), _ptr(box_vectors), float(coulomb),
-                                                   _ptr(grid), _ptr(pos_deriv), _ptr(charge_deriv), _ptr(ws), _stream_ptr(dev)))
-    return energy, pos_deriv, charge_deriv
+                                                   _ptr(grid), _ptr(pos_deriv), _ptr(charge_deriv), ws, _stream_ptr(dev)))
+    if not bool((buf[:off] == _PASSES_PATTERN).all()) or not bool((buf[off + nbytes:] == _PASSES_PATTERN).all()):
+        raise RuntimeError(f"pme_reciprocal wrote outside its workspace of {nbytes} bytes")
+    return real, before, recip, grid, energy, pos_deriv, charge_deriv
+
+
+def pme_reciprocal(positions, charges, box_vectors, gridx, gridy, gridz, order, alpha, coulomb, xmoduli, ymoduli, zmoduli):
+    """Reciprocal-space PME (reference src/pytorch/pme/pmeCUDA.cu:102-430) through the C ABI: spread -> torch.fft.rfftn ->
+    convolve -> torch.fft.irfftn(norm="forward") -> interpolate.  -> (energy float32[1] without the self energy, dE/dpositions
+    [N, 3], dE/dcharges [N]).  Orders 4 and 5."""
+    return pme_reciprocal_passes(positions, charges, box_vectors, gridx, gridy, gridz, order, alpha, coulomb, xmoduli, ymoduli,
+                                 zmoduli)[4:]
 
 
 def pme_direct_box(positions, charges, neighbors, deltas, distances, exclusions, box_vectors, alpha, coulomb):
@@ -680,7 +698,9 @@ def pme_reciprocal_double_backward(positions, charges, box_vectors, gridx, gridy
         recip = torch.fft.rfftn(grid).contiguous()
         _check(L.nnpops_pme_reciprocal_convolve(n, *dims, _ptr(box_vectors), float(alpha), _ptr(mods[0]), _ptr(mods[1]), _ptr(mods[2]),
                                                 _ptr(recip), _ptr(energy), _ptr(ws), _stream_ptr(dev)))
-        return torch.fft.irfftn(recip, s=(gridx, gridy, gridz), norm="forward").contiguous()
+        # the inverse transform in double, rounded once (as the torch op does on the device): interpolate_second differences the grid twice, and the float transform's
+        # error, white across the grid, grew there with the square of the grid size
+        return torch.fft.irfftn(recip.to(torch.complex128), s=(gridx, gridy, gridz), norm="forward").float().contiguous()
 
     with torch.cuda.device(dev):
         _check(L.nnpops_pme_reciprocal_spread(n, *dims, _ptr(positions), _ptr(charges), _ptr(box_vectors), float(coulomb), _ptr(real),

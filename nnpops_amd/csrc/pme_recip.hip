@@ -597,10 +597,11 @@ __global__ __launch_bounds__(kBlock) void pme_recip_interp(int num_atoms, Dims d
 //     dL/dx_j = q_j grad W_j . phi' + q_j grad((v_j . grad) W_j) . phi + w_j grad W_j . phi      pme_recip_interp2
 // (v . grad) W along axis a is s_a dtheta_a times the other two axes' theta, s_a = K_a (v . B^-1 column a); its gradient needs
 // d2theta (the order-(n-2) weights differenced twice) and the mixed products dtheta_a dtheta_b theta_c.  pme_recip_spline2 recomputes
-// the fractional offset from the positions exactly as pme_recip_spline does and stores d2theta and s in a workspace of its own.
+// the fractional offset from the positions exactly as pme_recip_spline does and stores theta, dtheta, d2theta (in double) and s in a
+// workspace of its own.
 // The first-order kernels above are not touched.
 struct SecondWorkspace {
-    float* d2theta;       // [N][3][order]
+    double* wide;         // [N][3][3][order]  theta, dtheta, d2theta of the three axes, in double (see pme_recip_spline2)
     float* dir;           // [N][3]        s_a = K_a (v . B^-1 column a)
     size_t bytes;
 };
@@ -609,7 +610,7 @@ SecondWorkspace second_carve(void* workspace, int num_atoms, int order) {
     SecondWorkspace w{};
     uintptr_t p = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
     auto take = [&](size_t bytes) { const uintptr_t at = p; p += (bytes + 255) & ~(size_t)255; return at; };
-    w.d2theta = (float*)take(sizeof(float) * 3 * (size_t)order * (size_t)num_atoms);
+    w.wide = (double*)take(sizeof(double) * 9 * (size_t)order * (size_t)num_atoms);
     w.dir = (float*)take(sizeof(float) * 3 * (size_t)num_atoms);
     w.bytes = (size_t)(p - (uintptr_t)workspace) + 256;
     return w;
@@ -618,7 +619,7 @@ SecondWorkspace second_carve(void* workspace, int num_atoms, int order) {
 template <int ORDER>
 __global__ __launch_bounds__(kBlock) void pme_recip_spline2(int num_atoms, const float* __restrict__ pos, const float* __restrict__ box,
                                                             Dims d, const int4* __restrict__ base, const float* __restrict__ v,
-                                                            float* __restrict__ d2theta, float* __restrict__ dir) {
+                                                            double* __restrict__ wide, float* __restrict__ dir) {
     const int atom = blockIdx.x * kBlock + threadIdx.x;
     if (atom >= num_atoms) return;
     float b[9];
@@ -639,7 +640,7 @@ __global__ __launch_bounds__(kBlock) void pme_recip_spline2(int num_atoms, const
     const int K[3] = {d.kx, d.ky, d.kz};
     const int4 b0 = base[atom];
     const int g0[3] = {b0.x, b0.y, b0.z};
-    float* d2 = d2theta + (size_t)atom * 3 * ORDER;
+    double* wd = wide + (size_t)atom * 9 * ORDER;
 #pragma unroll
     for (int i = 0; i < 3; i++) {
         const float t = (t3[i] - floorf(t3[i])) * K[i];
@@ -649,25 +650,36 @@ __global__ __launch_bounds__(kBlock) void pme_recip_spline2(int num_atoms, const
         // the forward's cell (the weights are continuous there)
         const int gi = min(max(ti % K[i], 0), K[i] - 1);
         if (gi != g0[i]) dr = ((gi - g0[i] + K[i]) % K[i] == 1) ? 1.0f : 0.0f;
-        // weights of order ORDER - 2 by the recursion of pme_recip_spline, then differenced twice
-        float w[ORDER];
+        // The recursion of pme_recip_spline in double from the float offset, kept at orders ORDER - 2 (differenced twice: d2theta),
+        // ORDER - 1 (differenced: dtheta) and ORDER (theta).  pme_recip_interp2 takes all three from here: d2theta sums to zero
+        // over the stencil, and float weights, which do so only to rounding, left an error of that rounding times phi itself.
+        const double x = dr;
+        double w[ORDER];
 #pragma unroll
-        for (int j = 0; j < ORDER; j++) w[j] = 0.f;
-        w[1] = dr;
-        w[0] = 1.f - dr;
+        for (int j = 0; j < ORDER; j++) w[j] = 0.0;
+        w[1] = x;
+        w[0] = 1.0 - x;
+        auto raise = [&](int j) {
+            const double div = 1.0 / (j - 1);
+            w[j - 1] = div * x * w[j - 2];
 #pragma unroll
-        for (int j = 3; j <= ORDER - 2; j++) {
-            const float div = 1.0f / (j - 1);
-            w[j - 1] = div * dr * w[j - 2];
+            for (int k = 1; k < j - 1; k++) w[j - k - 1] = div * ((x + k) * w[j - k - 2] + (j - k - x) * w[j - k - 1]);
+            w[0] = div * (1.0 - x) * w[0];
+        };
 #pragma unroll
-            for (int k = 1; k < j - 1; k++) w[j - k - 1] = div * ((dr + k) * w[j - k - 2] + (j - k - dr) * w[j - k - 1]);
-            w[0] = div * (1.f - dr) * w[0];
-        }
+        for (int j = 3; j <= ORDER - 2; j++) raise(j);
 #pragma unroll
         for (int j = 0; j < ORDER; j++) {
-            const float lo = j >= 2 ? w[j - 2] : 0.f, mid = j >= 1 ? w[j - 1] : 0.f;      // (w[ORDER-2], w[ORDER-1] are zero)
-            d2[i * ORDER + j] = lo - 2.0f * mid + w[j];
+            const double lo = j >= 2 ? w[j - 2] : 0.0, mid = j >= 1 ? w[j - 1] : 0.0;      // (w[ORDER-2], w[ORDER-1] are zero)
+            wd[(6 + i) * ORDER + j] = lo - 2.0 * mid + w[j];
         }
+        raise(ORDER - 1);
+        wd[(3 + i) * ORDER] = -w[0];
+#pragma unroll
+        for (int j = 1; j < ORDER; j++) wd[(3 + i) * ORDER + j] = w[j - 1] - w[j];
+        raise(ORDER);
+#pragma unroll
+        for (int j = 0; j < ORDER; j++) wd[i * ORDER + j] = w[j];
     }
     const float vx = v[3 * atom], vy = v[3 * atom + 1], vz = v[3 * atom + 2];
     dir[3 * atom] = K[0] * (vx * r.r00 + vy * r.r10 + vz * r.r20);
@@ -779,8 +791,7 @@ template <int ORDER>
 __global__ __launch_bounds__(kBlock) void pme_recip_interp2(int num_atoms, Dims d, const float* __restrict__ box,
                                                             const float* __restrict__ charge, const float* __restrict__ wq,
                                                             float sqrt_coulomb, const int4* __restrict__ base,
-                                                            const float* __restrict__ theta, const float* __restrict__ dtheta,
-                                                            const float* __restrict__ d2theta, const float* __restrict__ dir,
+                                                            const double* __restrict__ wide, const float* __restrict__ dir,
                                                             const float* __restrict__ phi, const float* __restrict__ phi2,
                                                             float* __restrict__ grad_pos, float* __restrict__ grad_charge) {
     const int atom = blockIdx.x * kBlock + threadIdx.x;
@@ -790,50 +801,52 @@ __global__ __launch_bounds__(kBlock) void pme_recip_interp2(int num_atoms, Dims 
     for (int i = 0; i < 9; i++) b[i] = box[i];
     const RecipBox r = recip_box(b);
     const int4 b0 = base[atom];
-    const float* th = theta + (size_t)atom * 3 * ORDER;
-    const float* dth = dtheta + (size_t)atom * 3 * ORDER;
-    const float* d2 = d2theta + (size_t)atom * 3 * ORDER;
-    float tz[ORDER], dz[ORDER], cz[ORDER];
+    const double* th = wide + (size_t)atom * 9 * ORDER;
+    const double* dth = th + 3 * ORDER;
+    const double* d2 = th + 6 * ORDER;
+    double tz[ORDER], dz[ORDER], cz[ORDER];
     int iz[ORDER];
 #pragma unroll
     for (int i = 0; i < ORDER; i++) {
         tz[i] = th[2 * ORDER + i]; dz[i] = dth[2 * ORDER + i]; cz[i] = d2[2 * ORDER + i];
         iz[i] = (b0.z + i) % d.kz;
     }
-    float hx = 0.f, hy = 0.f, hz = 0.f;                                       // d_a W . phi
-    float hxx = 0.f, hyy = 0.f, hzz = 0.f, hxy = 0.f, hxz = 0.f, hyz = 0.f;   // d_a d_b W . phi
-    float a2 = 0.f, g2x = 0.f, g2y = 0.f, g2z = 0.f;                          // W . phi', d_a W . phi'
+    // The sums run in double: d_a d_b W . phi differences the potential grid twice, and on a fine grid neighbouring values of phi nearly
+    // cancel -- float sums left an error that grew with the square of the grid size.
+    double hx = 0.0, hy = 0.0, hz = 0.0;                                      // d_a W . phi
+    double hxx = 0.0, hyy = 0.0, hzz = 0.0, hxy = 0.0, hxz = 0.0, hyz = 0.0;  // d_a d_b W . phi
+    double a2 = 0.0, g2x = 0.0, g2y = 0.0, g2z = 0.0;                         // W . phi', d_a W . phi'
 #pragma unroll
     for (int a = 0; a < ORDER; a++) {
         const int xi = (b0.x + a) % d.kx;
-        const float tx = th[a], dx = dth[a], cx = d2[a];
+        const double tx = th[a], dx = dth[a], cx = d2[a];
 #pragma unroll
         for (int c = 0; c < ORDER; c++) {
             const size_t row = ((size_t)xi * d.ky + (b0.y + c) % d.ky) * d.kz;
-            const float ty = th[ORDER + c], dy = dth[ORDER + c], cy = d2[ORDER + c];
-            float z0 = 0.f, z1 = 0.f, z2 = 0.f, p0 = 0.f, p1 = 0.f;
+            const double ty = th[ORDER + c], dy = dth[ORDER + c], cy = d2[ORDER + c];
+            double z0 = 0.0, z1 = 0.0, z2 = 0.0, p0 = 0.0, p1 = 0.0;
 #pragma unroll
             for (int e = 0; e < ORDER; e++) {
-                const float g = phi[row + iz[e]], g2 = phi2[row + iz[e]];
+                const double g = phi[row + iz[e]], g2 = phi2[row + iz[e]];
                 z0 += tz[e] * g; z1 += dz[e] * g; z2 += cz[e] * g;
                 p0 += tz[e] * g2; p1 += dz[e] * g2;
             }
-            const float txy = tx * ty, dxy = dx * ty, xdy = tx * dy;
+            const double txy = tx * ty, dxy = dx * ty, xdy = tx * dy;
             hx += dxy * z0; hy += xdy * z0; hz += txy * z1;
             hxx += cx * ty * z0; hyy += tx * cy * z0; hzz += txy * z2;
             hxy += dx * dy * z0; hxz += dxy * z1; hyz += xdy * z1;
             a2 += txy * p0; g2x += dxy * p0; g2y += xdy * p0; g2z += txy * p1;
         }
     }
-    const float sx = dir[3 * atom], sy = dir[3 * atom + 1], sz = dir[3 * atom + 2];
-    const float qs = charge[atom] * sqrt_coulomb, ws = wq[atom] * sqrt_coulomb;
-    grad_charge[atom] = sqrt_coulomb * (a2 + sx * hx + sy * hy + sz * hz);
-    const float fx = (qs * (g2x + sx * hxx + sy * hxy + sz * hxz) + ws * hx) * d.kx;
-    const float fy = (qs * (g2y + sx * hxy + sy * hyy + sz * hyz) + ws * hy) * d.ky;
-    const float fz = (qs * (g2z + sx * hxz + sy * hyz + sz * hzz) + ws * hz) * d.kz;
-    grad_pos[3 * atom] = fx * r.r00;
-    grad_pos[3 * atom + 1] = fx * r.r10 + fy * r.r11;
-    grad_pos[3 * atom + 2] = fx * r.r20 + fy * r.r21 + fz * r.r22;
+    const double sx = dir[3 * atom], sy = dir[3 * atom + 1], sz = dir[3 * atom + 2];
+    const double qs = (double)charge[atom] * sqrt_coulomb, ws = (double)wq[atom] * sqrt_coulomb;
+    grad_charge[atom] = (float)(sqrt_coulomb * (a2 + sx * hx + sy * hy + sz * hz));
+    const double fx = (qs * (g2x + sx * hxx + sy * hxy + sz * hxz) + ws * hx) * d.kx;
+    const double fy = (qs * (g2y + sx * hxy + sy * hyy + sz * hyz) + ws * hy) * d.ky;
+    const double fz = (qs * (g2z + sx * hxz + sy * hyz + sz * hzz) + ws * hz) * d.kz;
+    grad_pos[3 * atom] = (float)(fx * r.r00);
+    grad_pos[3 * atom + 1] = (float)(fx * r.r10 + fy * r.r11);
+    grad_pos[3 * atom + 2] = (float)(fx * r.r20 + fy * r.r21 + fz * r.r22);
 }
 
 int check_common(int num_atoms, int gx, int gy, int gz, int order) {
@@ -992,14 +1005,14 @@ int nnpops_pme_reciprocal_spread_directional(int num_atoms, int gridx, int gridy
     if (order == 4) {
         if (num_atoms > 0)
             hipLaunchKernelGGL(pme_recip_spline2<4>, dim3(ab), dim3(kBlock), 0, s, num_atoms, positions, box_vectors, d, (const int4*)ws.base, v,
-                               w2.d2theta, w2.dir);
+                               w2.wide, w2.dir);
         hipLaunchKernelGGL(pme_recip_gather_dir<4>, dim3((unsigned)d.nbins), dim3(kBlock), 0, s, d, (const int*)ws.bin_start,
                            (const int*)ws.sorted, (const int4*)ws.base, (const float*)ws.theta, (const float*)ws.dtheta,
                            (const float*)w2.dir, charges, w, sqrt_coulomb, real_grid);
     } else {
         if (num_atoms > 0)
             hipLaunchKernelGGL(pme_recip_spline2<5>, dim3(ab), dim3(kBlock), 0, s, num_atoms, positions, box_vectors, d, (const int4*)ws.base, v,
-                               w2.d2theta, w2.dir);
+                               w2.wide, w2.dir);
         hipLaunchKernelGGL(pme_recip_gather_dir<5>, dim3((unsigned)d.nbins), dim3(kBlock), 0, s, d, (const int*)ws.bin_start,
                            (const int*)ws.sorted, (const int4*)ws.base, (const float*)ws.theta, (const float*)ws.dtheta,
                            (const float*)w2.dir, charges, w, sqrt_coulomb, real_grid);
@@ -1025,11 +1038,11 @@ int nnpops_pme_reciprocal_interpolate_second(int num_atoms, int gridx, int gridy
     const int ab = div_up(num_atoms, kBlock);
     if (order == 4)
         hipLaunchKernelGGL(pme_recip_interp2<4>, dim3(ab), dim3(kBlock), 0, s, num_atoms, d, box_vectors, charges, w, sqrt_coulomb,
-                           (const int4*)ws.base, (const float*)ws.theta, (const float*)ws.dtheta, (const float*)w2.d2theta,
+                           (const int4*)ws.base, (const double*)w2.wide,
                            (const float*)w2.dir, potential_grid, directional_grid, grad_positions, grad_charges);
     else
         hipLaunchKernelGGL(pme_recip_interp2<5>, dim3(ab), dim3(kBlock), 0, s, num_atoms, d, box_vectors, charges, w, sqrt_coulomb,
-                           (const int4*)ws.base, (const float*)ws.theta, (const float*)ws.dtheta, (const float*)w2.d2theta,
+                           (const int4*)ws.base, (const double*)w2.wide,
                            (const float*)w2.dir, potential_grid, directional_grid, grad_positions, grad_charges);
     NNPOPS_HIP_TRY(hipGetLastError());
     return NNPOPS_OK;

@@ -2364,7 +2364,9 @@ public:
                                                zm.data_ptr<float>(), recip.data_ptr(), unused.data_ptr<float>(), workspace.data_ptr(),
                                                stream) != NNPOPS_OK)
                 raise_last("pme::pme_reciprocal_twice (double backward)");
-            const Tensor phi2 = torch::fft::irfftn(recip, torch::IntArrayRef(K), c10::nullopt, "forward").contiguous();
+            // (the inverse transform in double, as for phi: PmeRecipBackwardFunction::backward)
+            const Tensor phi2 = torch::fft::irfftn(recip.to(torch::kComplexDouble), torch::IntArrayRef(K), c10::nullopt, "forward")
+                                    .to(torch::kFloat).contiguous();
             if (nnpops_pme_reciprocal_interpolate_second((int)n, kx, ky, kz, o, q.data_ptr<float>(), box.data_ptr<float>(), (float)k,
                                                          w.data_ptr<float>(), phi.data_ptr<float>(), phi2.data_ptr<float>(), gx.data_ptr<float>(),
                                                          gq.data_ptr<float>(), workspace.data_ptr(), second.data_ptr(), stream) != NNPOPS_OK)
@@ -2464,7 +2466,7 @@ public:
         const Tensor phi = torch::fft::irfftn(recip, torch::IntArrayRef(K), c10::nullopt, "forward").contiguous();
         Tensor pos_deriv = torch::empty({n, 3}, q.options()), charge_deriv = torch::empty({n}, q.options());
         PmeReciprocalFunction::interpolate(phi, q, box, workspace, pos, K, pme_order, k, pos_deriv, charge_deriv);
-        ctx->save_for_backward({g, positions, charges, box, workspace, xm, ym, zm, phi, pos_deriv, charge_deriv});
+        ctx->save_for_backward({g, positions, charges, box, workspace, xm, ym, zm, phi, pos_deriv, charge_deriv, recip});
         ctx->saved_data["grid"] = K;
         ctx->saved_data["order"] = pme_order;
         ctx->saved_data["alpha"] = alpha;
@@ -2474,8 +2476,15 @@ public:
 
     static tensor_list backward(AutogradContext* ctx, tensor_list grads) {
         const auto s = ctx->get_saved_variables();
-        const tensor_list d = PmeRecipDoubleBackwardFunction::apply(grads[0], grads[1], s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], s[8], s[9], s[10],
-                                                                    ctx->saved_data["grid"].toIntVector(), ctx->saved_data["order"].toInt(),
+        // On the device the second-order interpolation reads a potential grid transformed back in double and rounded once: it
+        // differences phi twice, and the float transform's error, white across the grid, grew there with the square of the grid size
+        // (DESIGN.md s8b).  The first-order outputs keep the float transform and their bits.
+        const std::vector<int64_t> K = ctx->saved_data["grid"].toIntVector();
+        const Tensor phi = s[1].is_cuda() ? torch::fft::irfftn(s[11].to(torch::kComplexDouble), torch::IntArrayRef(K), c10::nullopt, "forward")
+                                                .to(torch::kFloat).contiguous()
+                                          : s[8];
+        const tensor_list d = PmeRecipDoubleBackwardFunction::apply(grads[0], grads[1], s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], phi, s[9], s[10],
+                                                                    K, ctx->saved_data["order"].toInt(),
                                                                     ctx->saved_data["alpha"].toDouble(), ctx->saved_data["coulomb"].toDouble());
         return {d[2], d[0], d[1], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
     }
