@@ -578,6 +578,10 @@ typedef struct {
      * the smallest activations' last bits (below 6e-5 * 2^act_scale_log2 the high plane is a denormal; the low plane still carries
      * the remainder): callers derive it from a bound on the activations (nnpops_amd/BatchedNN.py: _refresh_planes). */
     int act_scale_log2;
+    /* Optional, with mean_out / mean_out_shifted: the rows are num_segments molecules and the mean is taken per molecule
+     * (nnpops_mlp_energy_mean_segments below) -- mean_out / mean_out_shifted then hold num_segments values.  segment_offsets
+     * [num_segments + 1] and segment_positions [sum of num_atoms] are device arrays; NULL / 0: one mean over everything. */
+    const int32_t* segment_offsets; const int32_t* segment_positions; int num_segments;
 } nnpops_mlp_frame;
 int64_t nnpops_mlp_packed_halves(int rows, int cols);
 int64_t nnpops_mlp_d1_halves(int num_atoms, int num_members, int h1);
@@ -595,6 +599,25 @@ int nnpops_mlp_energy_mean_shifted(void* stream, const float* energies, int64_t 
  * otherwise.  The backward of the one-node OptimizedTorchANI step (pytorch/OptimizedTorchANI.py:49-52): forces kept by the forward
  * pass times the gradient autograd hands in, in one launch. */
 int nnpops_scale_by_scalar(void* stream, const float* in, int64_t count, const void* factor, int factor_is_double, float* out);
+/* The energy mean of nnpops_mlp_energy_mean for a BATCH of molecules: out[b] = scale * sum over the atoms a of molecule b and the
+ * members m of energies[positions[a]][m].  `energies` is [num_atoms][num_members] in the grouped order nnpops_mlp_forward writes;
+ * molecule b is the rows molecule_offsets[b] .. molecule_offsets[b + 1] - 1 (the convention of nnpops_ani_set_molecules; the
+ * offsets start at 0 and end at num_atoms) and positions[row] is the place of that row in the grouped order (the inverse of the
+ * frame's rows[]).  All device pointers; 1 <= num_molecules.  One wave per molecule: lane l adds the atoms l, l + 64, ... of the
+ * molecule, each atom's members in order, in double precision, and the 64 lane sums meet in a fixed butterfly -- the value of a
+ * molecule depends on its own atoms only: not on the number of molecules, on its place among them or on the atoms of other
+ * molecules, and no atomic is involved.  Molecules of any size (also empty ones: 0). */
+int nnpops_mlp_energy_mean_segments(void* stream, const float* energies, int num_atoms, int num_members, const int32_t* molecule_offsets,
+                                    int num_molecules, const int32_t* positions, float scale, float* out);
+/* ... promoted and shifted like nnpops_mlp_energy_mean_shifted: out[b] = (double)(float)mean_b + shift[0], device doubles. */
+int nnpops_mlp_energy_mean_segments_shifted(void* stream, const float* energies, int num_atoms, int num_members,
+                                            const int32_t* molecule_offsets, int num_molecules, const int32_t* positions, float scale,
+                                            const double* shift, double* out);
+/* out[row][0..2] = in[row][0..2] * (float)factors[molecule of row] for the num_atoms rows of a batch of molecules (offsets as above);
+ * `factors` is a DEVICE array of num_molecules doubles when factor_is_double != 0, floats otherwise.  The backward of the batched
+ * one-node step: every molecule's kept forces times its own upstream gradient, in one launch. */
+int nnpops_scale_by_segment(void* stream, const float* in, int num_atoms, const int32_t* molecule_offsets, int num_molecules,
+                            const void* factors, int factor_is_double, float* out);
 
 #ifdef __cplusplus
 }

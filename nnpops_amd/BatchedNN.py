@@ -192,8 +192,11 @@ class _FusedSpeciesNN(_SpeciesGroupedNN):
     live_blocks: List[int]
     act_scale_log2: int
 
+    __jit_ignored_attributes__ = ["_batch_plans"]      # host-side state of the batched step
+
     def __init__(self, converter, ensemble, atomicNumbers: Tensor):
         super().__init__(converter, ensemble, atomicNumbers)
+        self._batch_plans = {}
         self.num_models = int(self.layer0_weights.shape[1])
         self.widths = []
         self.live_blocks = []
@@ -303,6 +306,8 @@ class _FusedSpeciesNN(_SpeciesGroupedNN):
         holder = getattr(self, 'holder', None)         # (the one-node step keeps dE/dAEV between the steps, cleared once for ONE list of
         if holder is not None:                         #  live blocks: torch_binding.cpp, Holder::gradCache)
             holder.reset_gradient_cache()
+        for plan in self._batch_plans.values():        # (... and so does every batched holder)
+            plan[0].reset_gradient_cache()
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
         super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
@@ -346,6 +351,55 @@ class _FusedSpeciesNN(_SpeciesGroupedNN):
                                                                       self.x_blocks, self.dead_blocks, self.act_scale_log2)
         return torch.ops.NNPOpsANISymmetryFunctions.energy_forces(self.holder, positions, cell, self.atom_order32, self.group_sizes, self.widths,
                                                                   self.num_models, self.mlp_planes, self.mlp_floats, shift, None, None, self.act_scale_log2)
+
+    @torch.jit.unused
+    def _batch_plan(self, holder, batch: int, device: torch.device):
+        """What the batched step needs for ``batch`` conformers, made once per batch size (and device): the batched AEV holder (the
+        one of TorchANISymmetryFunctions.batch_holder: no second holder for the same size), the rows of the batch * N atoms grouped by
+        species -- conformer after conformer inside a species --, the group sizes, the place of every row in that order and the
+        molecule offsets.  The packed planes, live blocks and activation scale are the ones of the single-molecule step."""
+        key = (batch, str(device))
+        plan = self._batch_plans.get(key)
+        if plan is None or plan[0] is not holder:
+            n = self.num_atoms
+            order = self.atom_order.to(device=device, dtype=torch.int64)
+            base = torch.arange(batch, dtype=torch.int64, device=device).unsqueeze(1) * n
+            parts, first = [], 0
+            for size in self.group_sizes:
+                parts.append((base + order[first:first + size].unsqueeze(0)).reshape(-1))
+                first += size
+            rows = torch.cat(parts)
+            places = torch.empty_like(rows)
+            places[rows] = torch.arange(batch * n, dtype=torch.int64, device=device)
+            offsets = torch.arange(batch + 1, dtype=torch.int32, device=device) * n
+            plan = (holder, rows.to(torch.int32).contiguous(), [size * batch for size in self.group_sizes], places.to(torch.int32).contiguous(),
+                    offsets.contiguous())
+            self._batch_plans[key] = plan
+        return plan
+
+    @torch.jit.unused
+    def _batch_call(self, op, holder, positions: Tensor, shift: Optional[Tensor]):
+        if not self.fused_ok:        # (a state dict loaded since construction: the weights no longer bound the fp16 operands)
+            raise RuntimeError("the loaded weights exceed the activation bound of the fused network kernels (BatchedNN.py: fused_ok); "
+                               "build the model with OptimizedTorchANI(..., fused_step=False) or nn_layout='grouped'")
+        holder, rows, sizes, places, offsets = self._batch_plan(holder, int(positions.shape[0]), positions.device)
+        if self.x_blocks.numel() > 0:
+            return op(holder, positions, None, rows, sizes, self.widths, self.num_models, self.live_planes, self.mlp_floats, offsets, places, shift,
+                      self.x_blocks, self.dead_blocks, self.act_scale_log2)
+        return op(holder, positions, None, rows, sizes, self.widths, self.num_models, self.mlp_planes, self.mlp_floats, offsets, places, shift,
+                  None, None, self.act_scale_log2)
+
+    @torch.jit.unused
+    def fused_energy_batch(self, holder, positions: Tensor, shift: Optional[Tensor] = None) -> Tensor:
+        """fused_energy() for B conformers (only inside OptimizedTorchANI, which hands over the batched AEV holder): positions [B, N, 3]
+        -> ensemble-mean energies [B] as one autograd node (``torch.ops.NNPOpsANISymmetryFunctions.energy_batch``); float64 and shifted
+        with ``shift``."""
+        return self._batch_call(torch.ops.NNPOpsANISymmetryFunctions.energy_batch, holder, positions, shift)
+
+    @torch.jit.unused
+    def fused_energy_forces_batch(self, holder, positions: Tensor, shift: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+        """The same step outside autograd: (energies [B], forces [B, N, 3] = -dE_b/dpositions)."""
+        return self._batch_call(torch.ops.NNPOpsANISymmetryFunctions.energy_forces_batch, holder, positions, shift)
 
 
 class _SplitGemmSpeciesNN(_SpeciesGroupedNN):
@@ -446,3 +500,11 @@ class TorchANIBatchedNN(nn.ModuleList):
 
     def set_check_interval(self, interval: int) -> None:
         self[0].set_check_interval(interval)
+
+    @torch.jit.unused
+    def fused_energy_batch(self, holder, positions: Tensor, shift: Optional[Tensor] = None) -> Tensor:
+        return self[0].fused_energy_batch(holder, positions, shift)
+
+    @torch.jit.unused
+    def fused_energy_forces_batch(self, holder, positions: Tensor, shift: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+        return self[0].fused_energy_forces_batch(holder, positions, shift)

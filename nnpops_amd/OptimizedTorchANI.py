@@ -37,6 +37,29 @@ class OptimizedTorchANI(torch.nn.Module):
         species_energies = self.neural_networks(species_aevs)
         return self.energy_shifter(species_energies)
 
+    @torch.jit.unused
+    def _batch_arguments(self, species_coordinates: Tuple[Tensor, Tensor], cell: Optional[Tensor], pbc: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+        """The argument errors of the batched methods; -> (species [B, N] of the module's molecule, coordinates [B, N, 3])."""
+        if cell is not None or pbc is not None:
+            raise ValueError('Batches of conformers are non-periodic: "cell" and "pbc" are not supported')
+        coordinates = species_coordinates[1]
+        batch = self.aev_computer.check_batch_arguments(coordinates)
+        if batch < 1:
+            raise ValueError('"positions" has to hold at least one conformer')
+        return self.species_converter.species.expand(batch, -1), coordinates
+
+    @torch.jit.unused
+    def forward_batch(self, species_coordinates: Tuple[Tensor, Tensor], cell: Optional[Tensor] = None,
+                      pbc: Optional[Tensor] = None) -> SpeciesEnergies:
+        """Extension (the reference scores one molecule per call): B conformers of THE molecule this module was built for, non-periodic.
+        (species[B, N], coordinates[B, N, 3]) -> SpeciesEnergies(species, energies[B]), one float64 energy per conformer, shifted by the
+        molecule's self energy as ``forward`` returns it, differentiable with respect to the coordinates.  Here: the composition of
+        ``aev_computer.forward_batch``, the networks and the shifter."""
+        species, coordinates = self._batch_arguments(species_coordinates, cell, pbc)
+        species_aevs = self.aev_computer.forward_batch((species, coordinates))
+        species_energies = self.neural_networks(species_aevs)
+        return self.energy_shifter(species_energies)
+
 
 class FusedOptimizedTorchANI(OptimizedTorchANI):
     """OptimizedTorchANI whose forward is ``torch.ops.NNPOpsANISymmetryFunctions.energy``: neighbour search + AEV + the four
@@ -85,3 +108,31 @@ class FusedOptimizedTorchANI(OptimizedTorchANI):
         if shift.dtype == torch.float64 and shift.numel() == 1 and shift.device == positions.device:
             return SpeciesEnergies(species, self.neural_networks.fused_energy(positions, cell, shift))
         return self.energy_shifter((species, self.neural_networks.fused_energy(positions, cell)))
+
+    @torch.jit.unused
+    def forward_batch(self, species_coordinates: Tuple[Tensor, Tensor], cell: Optional[Tensor] = None,
+                      pbc: Optional[Tensor] = None) -> SpeciesEnergies:
+        """``OptimizedTorchANI.forward_batch`` as ONE autograd node (``torch.ops.NNPOpsANISymmetryFunctions.energy_batch``): the AEV
+        kernels and the networks run once over all B x N atoms behind the batched holder of ``aev_computer`` -- the launches of a
+        single-molecule step, not B times as many --, a mean per conformer, and a backward that scales every conformer's kept forces
+        by its own upstream gradient.  An energy is the same bits wherever its conformer stands in whatever batch.  Second
+        derivatives are refused, as in ``forward``."""
+        species, coordinates = self._batch_arguments(species_coordinates, cell, pbc)
+        holder = self.aev_computer.batch_holder(int(coordinates.shape[0]))
+        shift = self.energy_shifter.self_energies
+        if shift.dtype == torch.float64 and shift.numel() == 1 and shift.device == coordinates.device:
+            return SpeciesEnergies(species, self.neural_networks.fused_energy_batch(holder, coordinates, shift))
+        return self.energy_shifter((species, self.neural_networks.fused_energy_batch(holder, coordinates)))
+
+    @torch.jit.unused
+    def energy_and_forces_batch(self, species_coordinates: Tuple[Tensor, Tensor], cell: Optional[Tensor] = None,
+                                pbc: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+        """Extension: (energies [B], forces [B, N, 3] = -dE_b/dcoordinates) of B conformers from ONE call, outside autograd -- the
+        counterpart of ``energy_and_forces``; the energies of ``forward_batch`` and the negated gradients, bit for bit."""
+        _, coordinates = self._batch_arguments(species_coordinates, cell, pbc)
+        holder = self.aev_computer.batch_holder(int(coordinates.shape[0]))
+        shift = self.energy_shifter.self_energies
+        if shift.dtype == torch.float64 and shift.numel() == 1 and shift.device == coordinates.device:
+            return self.neural_networks.fused_energy_forces_batch(holder, coordinates, shift)
+        energies, forces = self.neural_networks.fused_energy_forces_batch(holder, coordinates)
+        return energies + self.energy_shifter.self_energies, forces

@@ -84,20 +84,32 @@ class TorchANISymmetryFunctions(torch.nn.Module):
         return self.holder.overflow_flag()
 
     @torch.jit.unused
+    def batch_holder(self, batch: int):
+        """The holder that evaluates ``batch`` conformers of this module's molecule at once (molecule offsets 0, N, 2N, ...), made
+        on first use and kept: forward_batch and the batched step of :class:`OptimizedTorchANI` share it."""
+        holder = self._batch_holders.get(batch)
+        if holder is None:
+            holder = torch.classes.NNPOpsANISymmetryFunctions.Holder(*self._ctor, self._species * batch)
+            holder.set_molecules([k * len(self._species) for k in range(batch + 1)])
+            self._batch_holders[batch] = holder
+        return holder
+
+    @torch.jit.unused
+    def check_batch_arguments(self, positions: Tensor) -> int:
+        """The argument error of forward_batch; -> the number of conformers."""
+        if positions.dim() != 3 or positions.shape[1] != len(self._species) or positions.shape[2] != 3:
+            raise ValueError(f'"positions" has to have the shape [batch, {len(self._species)}, 3]')
+        return int(positions.shape[0])
+
+    @torch.jit.unused
     def forward_batch(self, species_positions: Tuple[Tensor, Tensor]) -> Tuple[Tensor, Tensor]:
         """Extension (the reference rejects batches, SymmetryFunctions.py:110): B conformers of THE molecule this module was
         built for, non-periodic.  (species[B, N], positions[B, N, 3]) -> (species, aev[B, N, W]), differentiable w.r.t.
         positions.  All B x N atoms are evaluated by ONE batched holder (molecule offsets 0, N, 2N, ...; atoms of different
         conformers never interact) in one launch sequence -- not B launches of a one-molecule holder."""
         species, positions = species_positions
-        if positions.dim() != 3 or positions.shape[1] != len(self._species) or positions.shape[2] != 3:
-            raise ValueError(f'"positions" has to have the shape [batch, {len(self._species)}, 3]')
-        batch = int(positions.shape[0])
-        holder = self._batch_holders.get(batch)
-        if holder is None:
-            holder = torch.classes.NNPOpsANISymmetryFunctions.Holder(*self._ctor, self._species * batch)
-            holder.set_molecules([k * len(self._species) for k in range(batch + 1)])
-            self._batch_holders[batch] = holder
+        batch = self.check_batch_arguments(positions)
+        holder = self.batch_holder(batch)
         flat = positions.reshape(batch * len(self._species), 3)
         features = torch.ops.NNPOpsANISymmetryFunctions.aev(holder, flat, None)
         return species, features.reshape(batch, len(self._species), -1)

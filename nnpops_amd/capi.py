@@ -85,6 +85,11 @@ SIGNATURES = {
     "nnpops_mlp_energy_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
     "nnpops_mlp_energy_mean_shifted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
     "nnpops_scale_by_scalar": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]),
+    "nnpops_mlp_energy_mean_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float,
+                                                  C.c_void_p]),
+    "nnpops_mlp_energy_mean_segments_shifted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float,
+                                                          C.c_void_p, C.c_void_p]),
+    "nnpops_scale_by_segment": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "nnpops_neighbor_pairs_workspace_bytes": (C.c_int64, [C.c_int]),
     "nnpops_neighbor_pairs_forward": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int64,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -916,7 +921,8 @@ class _MlpFrame(C.Structure):
                 ("upstream", C.c_void_p), ("dx_scale", C.c_float), ("kinds", _MlpKind * MLP_MAX_KINDS),
                 ("x_groups", C.c_void_p), ("dead_groups", C.c_void_p), ("num_dead_groups", C.c_int), ("dx_partial", C.c_void_p),
                 ("mean_scale", C.c_float), ("mean_out", C.c_void_p), ("mean_shift", C.c_void_p), ("mean_out_shifted", C.c_void_p),
-                ("publish_word", C.c_void_p), ("publish_to", C.c_void_p), ("publish_stamp", C.c_int32), ("act_scale_log2", C.c_int)]
+                ("publish_word", C.c_void_p), ("publish_to", C.c_void_p), ("publish_stamp", C.c_int32), ("act_scale_log2", C.c_int),
+                ("segment_offsets", C.c_void_p), ("segment_positions", C.c_void_p), ("num_segments", C.c_int)]
 
 
 def mlp_pack(w, rows, cols, transpose=False, permute=False):
@@ -1050,4 +1056,46 @@ def scale_by_scalar(values, factor):
     out = torch.empty_like(values)
     _check(lib().nnpops_scale_by_scalar(_stream_ptr(values.device), _ptr(values), values.numel(), _ptr(factor),
                                         int(factor.dtype == torch.float64), _ptr(out)))
+    return out
+
+
+def _segment_tables(molecule_offsets, positions, num_atoms):
+    for name, t in (("molecule_offsets", molecule_offsets), ("positions", positions)):
+        if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+            raise ValueError(f'"{name}" must be a contiguous int32 device tensor')
+    if molecule_offsets.numel() < 2 or positions.numel() != num_atoms:
+        raise ValueError("molecule_offsets holds one entry more than there are molecules, positions one per atom")
+    return molecule_offsets.numel() - 1
+
+
+def mlp_energy_mean_segments(energies, molecule_offsets, positions, scale=1.0, shift=None):
+    """Per-molecule means of ``energies`` [grouped atoms][members] (nnpops_mlp_energy_mean_segments): molecule b is the rows
+    molecule_offsets[b] .. molecule_offsets[b + 1] - 1, ``positions[row]`` the place of a row in the grouped order.  -> float32 [B], or
+    -- with ``shift``, a float64 device scalar -- float64 [B] = (double)(float)mean + shift."""
+    energies = _dev_f32(energies, "energies")
+    n, members = energies.shape
+    count = _segment_tables(molecule_offsets, positions, n)
+    if shift is None:
+        out = torch.empty((count,), dtype=torch.float32, device=energies.device)
+        _check(lib().nnpops_mlp_energy_mean_segments(_stream_ptr(out.device), _ptr(energies), n, members, _ptr(molecule_offsets), count,
+                                                     _ptr(positions), float(scale), _ptr(out)))
+        return out
+    assert shift.dtype == torch.float64 and shift.is_cuda and shift.numel() >= 1
+    out = torch.empty((count,), dtype=torch.float64, device=energies.device)
+    _check(lib().nnpops_mlp_energy_mean_segments_shifted(_stream_ptr(out.device), _ptr(energies), n, members, _ptr(molecule_offsets), count,
+                                                         _ptr(positions), float(scale), _ptr(shift), _ptr(out)))
+    return out
+
+
+def scale_by_segment(values, molecule_offsets, factors):
+    """values [atoms][3] (float32 device tensor) times the factor of the molecule each row belongs to; ``factors`` a float32 or
+    float64 device tensor, one per molecule (nnpops_scale_by_segment -- the backward of the batched one-node step)."""
+    values = _dev_f32(values, "values")
+    assert values.dim() == 2 and values.shape[1] == 3
+    assert factors.is_cuda and factors.dtype in (torch.float32, torch.float64) and factors.is_contiguous()
+    count = molecule_offsets.numel() - 1
+    assert molecule_offsets.is_cuda and molecule_offsets.dtype == torch.int32 and molecule_offsets.is_contiguous() and factors.numel() == count >= 1
+    out = torch.empty_like(values)
+    _check(lib().nnpops_scale_by_segment(_stream_ptr(values.device), _ptr(values), values.shape[0], _ptr(molecule_offsets), count,
+                                         _ptr(factors), int(factors.dtype == torch.float64), _ptr(out)))
     return out

@@ -80,6 +80,7 @@ struct MlpArgs {
     float mean_scale; float* mean_out; const double* mean_shift; double* mean_out_shifted;   // optional: the energy mean rides along (mlp_sum_members)
     const int* publish_word; int* publish_to; int publish_stamp;                             // optional: an ANI handle's deferred capacity check rides along (mlp_forward)
     float scale, unscale;                   // 2^-act_scale_log2 and its inverse: the operand scale of the fp16 planes (nnpops_hip.h; 1/16 by default)
+    const int* seg_offsets; const int* seg_positions; int num_segments;                      // optional: the mean is taken molecule by molecule (energy_mean_segment)
     KindDesc kinds[NNPOPS_MLP_MAX_KINDS];
 };
 
@@ -540,11 +541,39 @@ __device__ __forceinline__ void energy_mean_block(const float* __restrict__ v, l
     }
 }
 
+// The mean of ONE molecule of a batch, by one wave: v is [grouped atoms][M], the molecule is the rows offsets[b] .. offsets[b + 1] - 1
+// and position[row] the place of a row in the grouped order.  Lane l adds the atoms l, l + 64, ... of the molecule (counted inside the
+// molecule), the members of an atom in order, and the 64 lane sums meet in a fixed butterfly: the order of the additions is a function
+// of the molecule's own atoms -- not of the number of molecules, of the molecule's place among them, or of which wave of which
+// workgroup of which kernel takes it.  Offsets and positions are clamped to the arrays: a bad table gives wrong numbers, not a fault.
+__device__ __forceinline__ void energy_mean_segment(const float* __restrict__ v, int n, int M, const int* __restrict__ offsets,
+                                                    const int* __restrict__ position, int b, float scale, float* __restrict__ out,
+                                                    const double* __restrict__ shift, double* __restrict__ out_shifted) {
+    const int lane = threadIdx.x & 63;
+    const int begin = min(max(offsets[b], 0), n), end = min(max(offsets[b + 1], begin), n);
+    double acc = 0.0;
+    for (int a = begin + lane; a < end; a += 64) {
+        const float* e = v + (size_t)min(max(position[a], 0), n - 1) * M;
+        for (int m = 0; m < M; m++) acc += (double)e[m];
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    if (lane == 0) {
+        const float mean = (float)(acc * (double)scale);
+        if (shift) out_shifted[b] = (double)mean + shift[0];
+        else out[b] = mean;
+    }
+}
+
 // dx = scale * sum over the members of dx_partial (what mlp_forward left when the frame carries dx_partial), written to the
 // columns the feature blocks live in; dead column blocks are set to zero.  One thread per (grouped atom, four columns).
 __global__ __launch_bounds__(256) void mlp_sum_members(const MlpArgs g) {
     __shared__ double red[1024 / 64];
-    if (blockIdx.x == 0 && (g.mean_out || g.mean_out_shifted))                  // (the energy mean rides along: one launch fewer)
+    if (g.seg_offsets) {                                                        // (a batch of molecules: one wave per molecule)
+        for (int b = blockIdx.x * 4 + (threadIdx.x >> 6); b < g.num_segments; b += gridDim.x * 4)
+            energy_mean_segment(g.energies, g.n_grouped, g.M, g.seg_offsets, g.seg_positions, b, g.mean_scale, g.mean_out, g.mean_shift,
+                                g.mean_out_shifted);
+    } else if (blockIdx.x == 0 && (g.mean_out || g.mean_out_shifted))           // (the energy mean rides along: one launch fewer)
         energy_mean_block<256>(g.energies, (long)g.n_grouped * g.M, g.mean_scale, g.mean_out, g.mean_shift, g.mean_out_shifted, red);
     const int quads = g.F >> 2, per_row = quads + g.num_dead * 4;
     const long total = (long)g.n_grouped * per_row;
@@ -610,6 +639,27 @@ __global__ __launch_bounds__(256) void scale_by_scalar(const float* __restrict__
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) out[i] = in[i] * f;
 }
 
+// the means of a batch of molecules (energy_mean_segment), four molecules per workgroup
+__global__ __launch_bounds__(256) void mlp_energy_mean_segments(const float* __restrict__ v, int n, int M, const int* __restrict__ offsets,
+                                                                int num_segments, const int* __restrict__ position, float scale,
+                                                                float* __restrict__ out, const double* __restrict__ shift,
+                                                                double* __restrict__ out_shifted) {
+    for (int b = blockIdx.x * 4 + (threadIdx.x >> 6); b < num_segments; b += gridDim.x * 4)
+        energy_mean_segment(v, n, M, offsets, position, b, scale, out, shift, out_shifted);
+}
+
+// out[row][0..2] = in[row][0..2] * (float)factor[molecule of row]: one wave per molecule (the backward of the batched energy node)
+template <typename F>
+__global__ __launch_bounds__(256) void scale_by_segment(const float* __restrict__ in, int n, const int* __restrict__ offsets, int num_segments,
+                                                        const F* __restrict__ factor, float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    for (int b = blockIdx.x * 4 + (threadIdx.x >> 6); b < num_segments; b += gridDim.x * 4) {
+        const int begin = min(max(offsets[b], 0), n), end = min(max(offsets[b + 1], begin), n);
+        const float f = (float)factor[b];
+        for (long i = 3L * begin + lane; i < 3L * end; i += 64) out[i] = in[i] * f;
+    }
+}
+
 int check_and_fill(const nnpops_mlp_frame* fr, MlpArgs& g, bool grad, int blocks_per_tile_grad, int* total_blocks) {
     NNPOPS_REQUIRE(fr != nullptr, "NULL frame descriptor");
     NNPOPS_REQUIRE(fr->num_kinds >= 1 && fr->num_kinds <= NNPOPS_MLP_MAX_KINDS, "1..%d kinds per launch (got %d)", NNPOPS_MLP_MAX_KINDS, fr->num_kinds);
@@ -635,6 +685,13 @@ int check_and_fill(const nnpops_mlp_frame* fr, MlpArgs& g, bool grad, int blocks
     }
     NNPOPS_REQUIRE(!fr->publish_word || fr->publish_to, "publish_word without publish_to");
     NNPOPS_REQUIRE(!(fr->mean_out && fr->mean_out_shifted) && (!fr->mean_out_shifted || fr->mean_shift), "one energy mean: float, or shifted double with its shift");
+    g.seg_offsets = nullptr; g.seg_positions = nullptr; g.num_segments = 0;
+    if (fr->segment_offsets || fr->segment_positions || fr->num_segments != 0) {
+        NNPOPS_REQUIRE(fr->segment_offsets && fr->segment_positions && fr->num_segments >= 1,
+                       "a mean per molecule needs segment_offsets, segment_positions and at least one molecule (got %d)", fr->num_segments);
+        NNPOPS_REQUIRE(fr->mean_out || fr->mean_out_shifted, "segment_offsets without mean_out / mean_out_shifted");
+        g.seg_offsets = fr->segment_offsets; g.seg_positions = fr->segment_positions; g.num_segments = fr->num_segments;
+    }
     NNPOPS_REQUIRE(!fr->x_groups || fr->num_features % 16 == 0, "x_groups maps blocks of 16 features: the feature count must be a multiple of 16 (got %d)",
                    fr->num_features);
     NNPOPS_REQUIRE(fr->num_dead_groups >= 0 && (fr->num_dead_groups == 0 || fr->dead_groups), "dead_groups is NULL");
@@ -724,6 +781,44 @@ int nnpops_mlp_energy_mean_shifted(void* stream, const float* energies, int64_t 
     NNPOPS_REQUIRE(energies && out && shift && count > 0, "NULL device pointer or empty sum");
     hipLaunchKernelGGL(mlp_energy_mean, dim3(1), dim3(1024), 0, (hipStream_t)stream, energies, (long)count, scale, (float*)nullptr, shift,
                        out);
+    NNPOPS_HIP_TRY(hipGetLastError());
+    return NNPOPS_OK;
+}
+
+int nnpops_mlp_energy_mean_segments(void* stream, const float* energies, int num_atoms, int num_members, const int32_t* molecule_offsets,
+                                    int num_molecules, const int32_t* positions, float scale, float* out) {
+    NNPOPS_REQUIRE(energies && molecule_offsets && positions && out, "NULL device pointer");
+    NNPOPS_REQUIRE(num_molecules >= 1 && num_atoms >= 1 && num_members >= 1, "empty batch (%d molecules, %d atoms, %d members)", num_molecules,
+                   num_atoms, num_members);
+    hipLaunchKernelGGL(mlp_energy_mean_segments, dim3(std::min((num_molecules + 3) / 4, 4096)), dim3(256), 0, (hipStream_t)stream, energies,
+                       num_atoms, num_members, molecule_offsets, num_molecules, positions, scale, out, (const double*)nullptr, (double*)nullptr);
+    NNPOPS_HIP_TRY(hipGetLastError());
+    return NNPOPS_OK;
+}
+
+int nnpops_mlp_energy_mean_segments_shifted(void* stream, const float* energies, int num_atoms, int num_members,
+                                            const int32_t* molecule_offsets, int num_molecules, const int32_t* positions, float scale,
+                                            const double* shift, double* out) {
+    NNPOPS_REQUIRE(energies && molecule_offsets && positions && shift && out, "NULL device pointer");
+    NNPOPS_REQUIRE(num_molecules >= 1 && num_atoms >= 1 && num_members >= 1, "empty batch (%d molecules, %d atoms, %d members)", num_molecules,
+                   num_atoms, num_members);
+    hipLaunchKernelGGL(mlp_energy_mean_segments, dim3(std::min((num_molecules + 3) / 4, 4096)), dim3(256), 0, (hipStream_t)stream, energies,
+                       num_atoms, num_members, molecule_offsets, num_molecules, positions, scale, (float*)nullptr, shift, out);
+    NNPOPS_HIP_TRY(hipGetLastError());
+    return NNPOPS_OK;
+}
+
+int nnpops_scale_by_segment(void* stream, const float* in, int num_atoms, const int32_t* molecule_offsets, int num_molecules,
+                            const void* factors, int factor_is_double, float* out) {
+    NNPOPS_REQUIRE(in && molecule_offsets && factors && out, "NULL device pointer");
+    NNPOPS_REQUIRE(num_molecules >= 1 && num_atoms >= 1, "empty batch (%d molecules, %d atoms)", num_molecules, num_atoms);
+    const int blocks = std::min((num_molecules + 3) / 4, 4096);
+    if (factor_is_double)
+        hipLaunchKernelGGL(scale_by_segment<double>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, in, num_atoms, molecule_offsets,
+                           num_molecules, (const double*)factors, out);
+    else
+        hipLaunchKernelGGL(scale_by_segment<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, in, num_atoms, molecule_offsets,
+                           num_molecules, (const float*)factors, out);
     NNPOPS_HIP_TRY(hipGetLastError());
     return NNPOPS_OK;
 }

@@ -453,7 +453,29 @@ public:
     uint32_t gradCacheVersion = 0;    //   another list, and an in-place edit of the list shows in its version counter
     MlpScratch mlpScratch;            // ... and the networks' workspaces of a step (per-member gradient shares, per-atom energies)
     void resetGradientCache() { gradCache = Tensor(); gradCacheBlocks = nullptr; gradCacheKey = Tensor(); }      // (the networks' live blocks have changed: BatchedNN.py)
+    // energy_step over a batch: the device tables the per-molecule mean and the per-molecule backward walk (molecule offsets, place of
+    // every row in the species-grouped order) are compared ONCE with what this holder was told (setMolecules) and with `rows` -- one
+    // host round trip for a given triple of tensors, held here so that their addresses cannot be handed to other tensors meanwhile.
+    int64_t moleculeCount() const { return moleculeOffsets.empty() ? 0 : (int64_t)moleculeOffsets.size() - 1; }
+    int64_t atomCount() const { return (int64_t)atomSpecies.size(); }
+    void verifyBatchTables(const Tensor& offsets, const Tensor& places, const Tensor& rows, bool capturing) {
+        const Tensor* given[3] = {&offsets, &places, &rows};
+        bool known = true;
+        for (int i = 0; i < 3; i++)
+            known = known && batchTables[i].defined() && batchTables[i].is_same(*given[i]) && batchTableVersions[i] == given[i]->_version();
+        if (known) return;
+        TORCH_CHECK(!capturing, "energy_batch(): the molecule tables of a batch are verified on their first use, which cannot happen inside a graph "
+                                "capture: evaluate the batch once before capturing");
+        const Tensor want = torch::tensor(moleculeOffsets, torch::TensorOptions().dtype(torch::kInt32));
+        TORCH_CHECK(torch::equal(offsets.cpu(), want), "energy_batch(): the molecule offsets are not the ones of the holder (Holder.set_molecules)");
+        const Tensor back = places.index_select(0, rows.to(torch::kLong));
+        TORCH_CHECK(torch::equal(back.cpu(), torch::arange(rows.numel(), torch::TensorOptions().dtype(torch::kInt32))),
+                    "energy_batch(): row_positions is not the inverse of rows");
+        for (int i = 0; i < 3; i++) { batchTables[i] = *given[i]; batchTableVersions[i] = given[i]->_version(); }
+    }
 private:
+    Tensor batchTables[3];
+    uint32_t batchTableVersions[3] = {0, 0, 0};
 };
 
 // Both nodes: `cellGrad` (decided by the caller, where grad mode is what the user set) = the box vectors require a gradient.  The node
@@ -541,14 +563,24 @@ Tensor aev(const c10::optional<HolderPtr>& holder, const Tensor& positions, cons
 // right behind the AEV forward, read after everything else has been launched.  A buffer that did overflow is grown there and the
 // step issued again.  Before: the host waited for the AEV forward, then launched the networks into an idle device; waiting at the
 // END of the step for the whole stream was worse still, 0.22 -> 0.28 ms.)
+// A batch of molecules behind one step (energy_batch): the tables of nnpops_mlp_energy_mean_segments.  The step differs from the one of a
+// single molecule in how the mean is taken -- one per molecule -- and in the shape of what comes back: energy [B], kept [B * N, 3].
+struct BatchTables {
+    Tensor offsets, places;           // int32 [B + 1], int32 [B * N]
+    int64_t molecules;
+};
+
 std::pair<Tensor, Tensor> energy_step(const HolderPtr& holder, const Tensor& frame, const c10::optional<Tensor>& cell, const Tensor& rows,
                                       const std::vector<int64_t>& kind_atoms, const std::vector<int64_t>& widths, int64_t members,
                                       const Tensor& planes, const Tensor& floats, const c10::optional<Tensor>& shift,
                                       const c10::optional<Tensor>& x_blocks, const c10::optional<Tensor>& dead_blocks, bool need_gradient,
-                                      float gradient_sign, int64_t act_scale_log2, Tensor* kept_cell = nullptr) {
+                                      float gradient_sign, int64_t act_scale_log2, Tensor* kept_cell = nullptr,
+                                      const BatchTables* batch = nullptr) {
     // (kept_cell != NULL, with need_gradient: the AEV backward also runs its box-gradient pass and dE/dcell * gradient_sign [3, 3] is kept there)
-    TORCH_CHECK(frame.dim() == 2 || (frame.dim() == 3 && frame.size(0) == 1), "energy(): positions must be [atoms, 3] or [1, atoms, 3]");
-    const Tensor positions = frame.dim() == 3 ? frame[0] : frame;
+    TORCH_CHECK(batch != nullptr || frame.dim() == 2 || (frame.dim() == 3 && frame.size(0) == 1),
+                "energy(): positions must be [atoms, 3] or [1, atoms, 3]");
+    const Tensor positions = batch ? frame.reshape({-1, 3}) : frame.dim() == 3 ? frame[0] : frame;
+    const int64_t count = batch ? batch->molecules : 1;
     Tensor energy, kept;
     for (int attempt = 0;; attempt++) {
         TORCH_CHECK(attempt <= 8, "NNPOpsANISymmetryFunctions::energy: neighbour buffers kept overflowing");
@@ -569,15 +601,28 @@ std::pair<Tensor, Tensor> energy_step(const HolderPtr& holder, const Tensor& fra
         if (shift.has_value()) {
             TORCH_CHECK(shift->scalar_type() == torch::kFloat64 && shift->device() == aev.device() && shift->numel() == 1 && shift->is_contiguous(),
                         "energy(): the self-energy shift must be one float64 on the device of the positions");
-            energy = torch::empty({1}, aev.options().dtype(torch::kFloat64));
+            energy = torch::empty({count}, aev.options().dtype(torch::kFloat64));
         } else {
-            energy = torch::empty({1}, aev.options());
+            energy = torch::empty({count}, aev.options());
         }
         const float mean_scale = 1.0f / (float)members;
         if (mean_rides) {
             call.frame.mean_scale = mean_scale;
             if (shift.has_value()) { call.frame.mean_shift = shift->data_ptr<double>(); call.frame.mean_out_shifted = energy.data_ptr<double>(); }
             else call.frame.mean_out = energy.data_ptr<float>();
+            if (batch) {
+                call.frame.segment_offsets = batch->offsets.data_ptr<int32_t>(); call.frame.segment_positions = batch->places.data_ptr<int32_t>();
+                call.frame.num_segments = (int)count;
+            }
+        } else if (batch) {
+            const int rc = shift.has_value()
+                ? nnpops_mlp_energy_mean_segments_shifted(stream, call.energies.data_ptr<float>(), (int)call.energies.size(0), (int)members,
+                                                          batch->offsets.data_ptr<int32_t>(), (int)count, batch->places.data_ptr<int32_t>(),
+                                                          mean_scale, shift->data_ptr<double>(), energy.data_ptr<double>())
+                : nnpops_mlp_energy_mean_segments(stream, call.energies.data_ptr<float>(), (int)call.energies.size(0), (int)members,
+                                                  batch->offsets.data_ptr<int32_t>(), (int)count, batch->places.data_ptr<int32_t>(), mean_scale,
+                                                  energy.data_ptr<float>());
+            if (rc != NNPOPS_OK) raise_last("NNPOpsANISymmetryFunctions::energy_batch");
         } else {
             const int rc = shift.has_value()
                 ? nnpops_mlp_energy_mean_shifted(stream, call.energies.data_ptr<float>(), call.energies.numel(), mean_scale,
@@ -690,6 +735,93 @@ std::tuple<Tensor, Tensor> energy_forces(const c10::optional<HolderPtr>& holder,
     return std::make_tuple(energy, forces);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Additive: the same step for a BATCH of molecules -- B conformers behind one holder with molecule offsets (Holder.set_molecules).
+// positions [B, N, 3] -> energies [B]: one AEV launch sequence and one launch of the networks over all B * N atoms, one mean per
+// molecule (nnpops_mlp_energy_mean_segments), dE_b/dpositions of every molecule kept from the forward [B * N, 3]; the backward scales
+// each molecule's rows by its own upstream gradient (nnpops_scale_by_segment) and hands them back as [B, N, 3].
+// ---------------------------------------------------------------------------------------------
+BatchTables batch_tables(const HolderPtr& holder, const Tensor& positions, const c10::optional<Tensor>& cell, const Tensor& rows,
+                         const Tensor& molecule_offsets, const Tensor& row_positions) {
+    TORCH_CHECK(!cell.has_value(), "energy_batch(): batches of molecules are non-periodic: a cell is not supported");
+    TORCH_CHECK(positions.dim() == 3 && positions.size(2) == 3 && positions.size(0) >= 1, "energy_batch(): positions must be [molecules, atoms, 3]");
+    require_device_tensor(positions, "positions");
+    const int64_t B = positions.size(0), atoms = B * positions.size(1);
+    TORCH_CHECK(holder->moleculeCount() > 0, "energy_batch(): the holder has no molecule offsets (Holder.set_molecules): it evaluates one molecule");
+    TORCH_CHECK(holder->moleculeCount() == B && holder->atomCount() == atoms, "energy_batch(): positions hold ", B, " molecules of ", positions.size(1),
+                " atoms, the holder ", holder->moleculeCount(), " molecules and ", holder->atomCount(), " atoms");
+    for (const Tensor* t : {&molecule_offsets, &row_positions})
+        TORCH_CHECK(t->scalar_type() == torch::kInt32 && t->is_contiguous() && t->device() == positions.device() && t->dim() == 1,
+                    "energy_batch(): molecule_offsets and row_positions must be contiguous int32 vectors on the device of the positions");
+    TORCH_CHECK(molecule_offsets.numel() == B + 1, "energy_batch(): ", B, " molecules need ", B + 1, " molecule offsets (got ", molecule_offsets.numel(), ")");
+    TORCH_CHECK(row_positions.numel() == atoms && rows.numel() == atoms && rows.scalar_type() == torch::kInt32 && rows.device() == positions.device(),
+                "energy_batch(): rows and row_positions must hold one int32 entry for each of the ", atoms, " atoms");
+    holder->verifyBatchTables(molecule_offsets, row_positions, rows, stream_is_capturing(current_stream(positions.device())));
+    return BatchTables{molecule_offsets, row_positions, B};
+}
+
+class EnergyBatchFunction : public torch::autograd::Function<EnergyBatchFunction> {
+public:
+    static Tensor forward(AutogradContext* ctx, const HolderPtr& holder, const Tensor& positions, const Tensor& rows, std::vector<int64_t> kind_atoms,
+                          std::vector<int64_t> widths, int64_t members, const Tensor& planes, const Tensor& floats, const c10::optional<Tensor>& shift,
+                          const c10::optional<Tensor>& x_blocks, const c10::optional<Tensor>& dead_blocks, const Tensor& molecule_offsets,
+                          const Tensor& row_positions, bool need_gradient, int64_t act_scale_log2) {
+        const BatchTables batch = batch_tables(holder, positions, c10::nullopt, rows, molecule_offsets, row_positions);
+        Tensor energy, kept;
+        std::tie(energy, kept) = energy_step(holder, positions, c10::nullopt, rows, kind_atoms, widths, members, planes, floats, shift, x_blocks,
+                                             dead_blocks, need_gradient, 1.0f, act_scale_log2, nullptr, &batch);
+        if (need_gradient) {
+            ctx->save_for_backward({kept, molecule_offsets});
+            ctx->saved_data["shape"] = positions.sizes().vec();
+        }
+        return energy;
+    }
+    static tensor_list backward(AutogradContext* ctx, const tensor_list& grads) {
+        TORCH_CHECK(!torch::GradMode::is_enabled(),
+                    "NNPOpsANISymmetryFunctions::energy_batch: second derivatives are not implemented (backward was called with create_graph=True); "
+                    "use the four-module composition for that");
+        const auto saved = ctx->get_saved_variables();
+        TORCH_CHECK(!saved.empty(), "energy_batch() was evaluated without a gradient request");
+        const Tensor& kept = saved[0];                                       // dE_b/dpositions of every molecule, [B * N, 3] float32
+        const Tensor& offsets = saved[1];
+        const Tensor g = grads[0].contiguous();
+        TORCH_CHECK(g.numel() == offsets.numel() - 1 && g.device() == kept.device() &&
+                    (g.scalar_type() == torch::kFloat32 || g.scalar_type() == torch::kFloat64), "energy_batch(): unexpected gradient of the energies");
+        c10::hip::HIPGuard guard(kept.device().index());
+        Tensor out = torch::empty_like(kept);
+        if (nnpops_scale_by_segment(current_stream(kept.device()), kept.data_ptr<float>(), (int)kept.size(0), offsets.data_ptr<int32_t>(), (int)g.numel(),
+                                    g.data_ptr(), g.scalar_type() == torch::kFloat64 ? 1 : 0, out.data_ptr<float>()) != NNPOPS_OK)
+            raise_last("NNPOpsANISymmetryFunctions::energy_batch (backward)");
+        out = out.view(ctx->saved_data["shape"].toIntVector());
+        return {Tensor(), out, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(),
+                Tensor()};
+    }
+};
+
+Tensor energy_batch(const c10::optional<HolderPtr>& holder, const Tensor& positions, const c10::optional<Tensor>& cell, const Tensor& rows,
+                    std::vector<int64_t> kind_atoms, std::vector<int64_t> widths, int64_t members, const Tensor& planes, const Tensor& floats,
+                    const Tensor& molecule_offsets, const Tensor& row_positions, const c10::optional<Tensor>& shift,
+                    const c10::optional<Tensor>& x_blocks, const c10::optional<Tensor>& dead_blocks, int64_t act_scale_log2) {
+    TORCH_CHECK(!cell.has_value(), "energy_batch(): batches of molecules are non-periodic: a cell is not supported");
+    const bool need = torch::GradMode::is_enabled() && positions.requires_grad();
+    return EnergyBatchFunction::apply(*holder, positions, rows, kind_atoms, widths, members, planes, floats, shift, x_blocks, dead_blocks,
+                                      molecule_offsets, row_positions, need, act_scale_log2);
+}
+
+// energies [B] AND forces [B, N, 3] of the batch from one call, outside autograd (cf. energy_forces)
+std::tuple<Tensor, Tensor> energy_forces_batch(const c10::optional<HolderPtr>& holder, const Tensor& positions, const c10::optional<Tensor>& cell,
+                                               const Tensor& rows, std::vector<int64_t> kind_atoms, std::vector<int64_t> widths, int64_t members,
+                                               const Tensor& planes, const Tensor& floats, const Tensor& molecule_offsets, const Tensor& row_positions,
+                                               const c10::optional<Tensor>& shift, const c10::optional<Tensor>& x_blocks,
+                                               const c10::optional<Tensor>& dead_blocks, int64_t act_scale_log2) {
+    torch::NoGradGuard no_grad;
+    const BatchTables batch = batch_tables(*holder, positions, cell, rows, molecule_offsets, row_positions);
+    Tensor energy, forces;
+    std::tie(energy, forces) = energy_step(*holder, positions.detach(), c10::nullopt, rows, kind_atoms, widths, members, planes, floats, shift, x_blocks,
+                                           dead_blocks, true, -1.0f, act_scale_log2, nullptr, &batch);
+    return std::make_tuple(energy, forces.view(positions.sizes()));
+}
+
 TORCH_LIBRARY(NNPOpsANISymmetryFunctions, m) {
     m.class_<Holder>("Holder")
         .def(torch::init<int64_t, double, double, const std::vector<double>&, const std::vector<double>&,
@@ -710,6 +842,12 @@ TORCH_LIBRARY(NNPOpsANISymmetryFunctions, m) {
     m.def("energy_forces(__torch__.torch.classes.NNPOpsANISymmetryFunctions.Holder? holder, Tensor positions, Tensor? cell, Tensor rows, int[] kind_atoms, "
           "int[] widths, int members, Tensor planes, Tensor floats, Tensor? shift=None, Tensor? x_blocks=None, Tensor? dead_blocks=None, int act_scale_log2=4) -> (Tensor, Tensor)",
           energy_forces);
+    m.def("energy_batch(__torch__.torch.classes.NNPOpsANISymmetryFunctions.Holder? holder, Tensor positions, Tensor? cell, Tensor rows, int[] kind_atoms, "
+          "int[] widths, int members, Tensor planes, Tensor floats, Tensor molecule_offsets, Tensor row_positions, Tensor? shift=None, "
+          "Tensor? x_blocks=None, Tensor? dead_blocks=None, int act_scale_log2=4) -> Tensor", energy_batch);
+    m.def("energy_forces_batch(__torch__.torch.classes.NNPOpsANISymmetryFunctions.Holder? holder, Tensor positions, Tensor? cell, Tensor rows, "
+          "int[] kind_atoms, int[] widths, int members, Tensor planes, Tensor floats, Tensor molecule_offsets, Tensor row_positions, "
+          "Tensor? shift=None, Tensor? x_blocks=None, Tensor? dead_blocks=None, int act_scale_log2=4) -> (Tensor, Tensor)", energy_forces_batch);
 }
 
 }  // namespace ANISymmetryFunctions
