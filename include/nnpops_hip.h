@@ -377,7 +377,13 @@ int nnpops_neighbor_pairs_double_backward(int dtype, int num_atoms, int64_t num_
  * nnpops_pme_direct_workspace_bytes(...) bytes -- about num_atoms x min(4 x num_pairs / num_atoms + 32, 2048) x 16 bytes (a row of
  * incoming contributions per atom; num_pairs is the capacity of the list, so a heavily padded list costs workspace up to that
  * clamp: 32 KiB per atom).  The table of exclusions must be SYMMETRIC: every atom takes the terms of its excluded pairs from its own
- * row (the Python wrapper checks it once).  Graph-capturable. */
+ * row (the Python wrapper checks it once).  Graph-capturable.
+ * Reproducibility: the energy is bitwise reproducible for every list.  The derivatives of an atom are bitwise reproducible as long as
+ * the atom receives no more entries than its row holds: cap = min(4 x ceil(num_pairs / num_atoms) + 32, 2048), one entry per
+ * included pair the atom is second in and one per run of consecutive slots (within 64 aligned slots) it is first in.  Entries beyond
+ * cap -- a dense cluster among dilute atoms, a hub atom, any all-pairs list of more than 2 049 atoms -- are added with float atomics
+ * in the order they arrive: such an atom's derivatives are correct to float32 rounding but NOT bitwise reproducible from call to call.
+ * nnpops_pme_direct_indexed below has no such limit. */
 int64_t nnpops_pme_direct_workspace_bytes(int64_t num_pairs, int num_atoms, int max_exclusions);
 int nnpops_pme_direct(int num_atoms, int64_t num_pairs, int max_exclusions, const float* positions, const float* charges,
                       const int32_t* neighbors, const float* deltas, const float* distances, const int32_t* exclusions,

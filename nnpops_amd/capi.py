@@ -508,11 +508,13 @@ def neighbor_pairs_double_backward(num_atoms, neighbors, deltas, distances, grad
     return outs
 
 
-def pme_direct(positions, charges, neighbors, deltas, distances, exclusions, alpha, coulomb, index=None):
+def pme_direct(positions, charges, neighbors, deltas, distances, exclusions, alpha, coulomb, index=None, workspace_guard=False):
     """Direct-space PME on a pair list (reference src/pytorch/pme/pmeCUDA.cu:30-100) through the C ABI.
     -> (energy float32[1], dE/dpositions [N, 3], dE/dcharges [N]); `exclusions` int32 [N, max], rows sorted descending.
     index: the list's transposed index (neighbor_pairs_build_index) -- the list must then be a compacted one the forward op emitted
-    (used slots first, grouped by neighbors[0], -1 only behind them): no atomics."""
+    (used slots first, grouped by neighbors[0], -1 only behind them): no atomics.
+    workspace_guard: the workspace is exactly nnpops_pme_direct[_indexed]_workspace_bytes long, 256-byte aligned, filled with and
+    followed by a guard pattern (as pme_reciprocal_passes): a kernel that writes past it raises; the outputs start as NaN."""
     _dev_f32(positions, "positions")
     _dev_f32(charges, "charges")
     n, pairs = positions.size(0), neighbors.size(1)
@@ -523,20 +525,38 @@ def pme_direct(positions, charges, neighbors, deltas, distances, exclusions, alp
     pos_deriv = torch.empty((n, 3), dtype=torch.float32, device=dev)
     charge_deriv = torch.empty((n,), dtype=torch.float32, device=dev)
     L = lib()
+    nbytes = int(L.nnpops_pme_direct_indexed_workspace_bytes(pairs, n) if index is not None else
+                 L.nnpops_pme_direct_workspace_bytes(pairs, n, max_excl))
+    if workspace_guard:
+        # (0x7F bytes: a large finite float, a large double and an int far above any row -- what a call fails to clear shows)
+        pattern = 0x7F
+        buf = torch.full((nbytes + _PASSES_GUARD + 256,), pattern, dtype=torch.uint8, device=dev)
+        off = (-buf.data_ptr()) % 256
+        ws_ptr = C.c_void_p(buf.data_ptr() + off)
+        for out in (energy, pos_deriv, charge_deriv):          # every output is fully overwritten: an element left out stays NaN
+            out.fill_(float("nan"))
+    else:
+        buf = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        ws_ptr = _ptr(buf)
+
+    def guard_intact():
+        if workspace_guard and not (bool((buf[:off] == pattern).all()) and bool((buf[off + nbytes:] == pattern).all())):
+            raise RuntimeError(f"pme_direct wrote outside its workspace of {nbytes} bytes")
+
     if index is not None:
-        ws = torch.empty((int(L.nnpops_pme_direct_indexed_workspace_bytes(pairs, n)),), dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
             _check(L.nnpops_pme_direct_indexed(n, pairs, max_excl, _ptr(positions), _ptr(charges), _ptr(neighbors.contiguous()),
                                                _ptr(deltas.contiguous()), _ptr(distances.contiguous()), _ptr(exclusions) if max_excl else None,
                                                _ptr(index), float(alpha), float(coulomb), _ptr(energy), _ptr(pos_deriv), _ptr(charge_deriv),
-                                               _ptr(ws), _stream_ptr(dev)))
+                                               ws_ptr, _stream_ptr(dev)))
+        guard_intact()
         return energy, pos_deriv, charge_deriv
-    ws = torch.empty((int(L.nnpops_pme_direct_workspace_bytes(pairs, n, max_excl)),), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         _check(L.nnpops_pme_direct(n, pairs, max_excl, _ptr(positions), _ptr(charges), _ptr(neighbors.contiguous()),
                                    _ptr(deltas.contiguous()), _ptr(distances.contiguous()), _ptr(exclusions) if max_excl else None,
-                                   float(alpha), float(coulomb), _ptr(energy), _ptr(pos_deriv), _ptr(charge_deriv), _ptr(ws),
+                                   float(alpha), float(coulomb), _ptr(energy), _ptr(pos_deriv), _ptr(charge_deriv), ws_ptr,
                                    _stream_ptr(dev)))
+    guard_intact()
     return energy, pos_deriv, charge_deriv
 
 
