@@ -1,125 +1,14 @@
-"""Box-vector gradients of PME on the CPU key: pme::pme_direct_box and the box gradient of pme::pme_reciprocal against autograd of a
-float64 pure-torch restatement (SPME with the box as a leaf and a general inverse, the direct sum over the op's own pairs), against
-an independent float64 Ewald sum, virial symmetry, unchanged outputs, TorchScript and the refusal of second derivatives."""
-import math
-
-import numpy as np
+"""Box-vector gradients of PME on the CPU key: pme::pme_direct_box and the box gradient of pme::pme_reciprocal against autograd of the
+float64 pure-torch restatement of tests/pme_float64.py (SPME with the box as a leaf and a general inverse, the direct sum over the
+op's own pairs), against its independent float64 Ewald sum, virial symmetry, unchanged outputs, TorchScript and the refusal of
+second derivatives."""
 import pytest
 import torch
 
 import NNPOps  # noqa: F401  (loads the torch ops)
+import pme_float64 as f64
 from NNPOps.neighbors import getNeighborPairs
 from NNPOps.pme import PME
-
-
-# ---- a float64 restatement, differentiable in the box ----------------------------------------------------------------------
-def bspline_weights(dr, order):
-    """The kernels' recursion (pme_recip_spline) on float64 tensors: weight i belongs to grid point base + i."""
-    w = [None] * order
-    w[order - 1] = torch.zeros_like(dr)
-    w[1] = dr
-    w[0] = 1 - dr
-    for j in range(3, order):
-        div = 1.0 / (j - 1)
-        w[j - 1] = div * dr * w[j - 2]
-        for k in range(1, j - 1):
-            w[j - k - 1] = div * ((dr + k) * w[j - k - 2] + (j - k - dr) * w[j - k - 1])
-        w[0] = div * (1 - dr) * w[0]
-    scale = 1.0 / (order - 1)
-    w[order - 1] = scale * dr * w[order - 2]
-    for j in range(1, order - 1):
-        w[order - j - 1] = scale * ((dr + j) * w[order - j - 2] + (order - j - dr) * w[order - j - 1])
-    w[0] = scale * (1 - dr) * w[0]
-    return w
-
-
-def spme_energy(pos, q, box, grid, order, alpha, coulomb, moduli):
-    """0.5 sum_k w eterm |S(k)|^2 of the op (no self energy), float64; box enters through B^-1 (fractional coordinates, m = B^-1 k)
-    and det(B)."""
-    K = list(grid)
-    inv = torch.linalg.inv(box)
-    s = pos @ inv
-    u = (s - torch.floor(s)) * torch.tensor(K, dtype=torch.float64)
-    base = torch.floor(u)
-    dr = u - base
-    base = base.long()
-    th = [bspline_weights(dr[:, a], order) for a in range(3)]
-    Q = torch.zeros(K[0] * K[1] * K[2], dtype=torch.float64)
-    qs = q * math.sqrt(coulomb)
-    for i in range(order):
-        for j in range(order):
-            for l in range(order):
-                idx = (((base[:, 0] + i) % K[0]) * K[1] + (base[:, 1] + j) % K[1]) * K[2] + (base[:, 2] + l) % K[2]
-                Q = Q.index_add(0, idx, qs * th[0][i] * th[1][j] * th[2][l])
-    S = torch.fft.rfftn(Q.view(K[0], K[1], K[2]))
-    kz_n = K[2] // 2 + 1
-
-    def signed(k, n):
-        return torch.where(k < (n + 1) // 2, k, k - n).to(torch.float64)
-    mx, my, mz = signed(torch.arange(K[0]), K[0]), signed(torch.arange(K[1]), K[1]), signed(torch.arange(kz_n), K[2])
-    kvec = torch.stack(torch.meshgrid(mx, my, mz, indexing="ij"), -1)
-    m = kvec @ inv.T                                                    # m = B^-1 k
-    m2 = (m * m).sum(-1)
-    zero = m2 == 0
-    m2 = torch.where(zero, torch.ones_like(m2), m2)
-    V = torch.linalg.det(box)
-    mod = moduli[0].double()[:, None, None] * moduli[1].double()[None, :, None] * moduli[2].double()[None, None, :kz_n]
-    eterm = torch.where(zero, torch.zeros_like(m2), torch.exp(-(math.pi / alpha) ** 2 * m2) / (math.pi * V * m2 * mod))
-    kz = torch.arange(kz_n)
-    w = torch.where((kz > 0) & (kz <= (K[2] - 1) // 2), 2.0, 1.0).to(torch.float64)
-    return 0.5 * torch.sum(w * eterm * (S.real ** 2 + S.imag ** 2))
-
-
-def listed_pairs(neighbors, deltas, pos, box, exclusions):
-    """(i, j, n) of the slots the direct op includes, n the integer image shift recovered in float64."""
-    nb = neighbors.cpu().numpy()
-    used = nb[0] >= 0
-    ex = exclusions.cpu().numpy()
-    excluded = {(a, b) for a in range(ex.shape[0]) for b in ex[a] if b >= 0}
-    keep = np.array([u and (a, b) not in excluded for u, a, b in zip(used, nb[0], nb[1])], dtype=bool)
-    i, j = nb[0][keep], nb[1][keep]
-    p = pos.detach().double().cpu().numpy()
-    D = p[i] - p[j] - deltas.detach().double().cpu().numpy()[keep]
-    n = np.rint(D @ np.linalg.inv(box.detach().double().cpu().numpy()))
-    return torch.tensor(i), torch.tensor(j), torch.tensor(n)
-
-
-def direct_energy(pos, q, box, pairs, alpha, coulomb):
-    """sum over the included pairs of coulomb q_i q_j erfc(alpha r) / r, r = |x_i - x_j - n B| (the excluded pairs' correction is
-    box independent and left out)"""
-    i, j, n = pairs
-    d = pos[i] - pos[j] - n @ box
-    r = torch.linalg.norm(d, dim=1)
-    return coulomb * torch.sum(q[i] * q[j] * torch.erfc(alpha * r) / r)
-
-
-def system(triclinic, n=40, seed=2, outside=True):
-    rng = np.random.default_rng(seed)
-    L = 2.4
-    box = np.array([[L, 0, 0], [0.3 * L, 1.05 * L, 0], [-0.25 * L, 0.2 * L, 0.95 * L]]) if triclinic else np.diag([L, 1.1 * L, 0.9 * L])
-    frac = rng.random((n, 3))
-    if outside:                                                    # a third of the atoms one or two box lengths away
-        frac[: n // 3] += rng.integers(-2, 3, (n // 3, 3))
-    pos = frac @ box
-    q = rng.normal(0, 0.5, n)
-    q -= q.mean()
-    return pos.astype(np.float32), q.astype(np.float32), box.astype(np.float32)
-
-
-def exclusion_table(n, seed=4):
-    """symmetric, rows padded with -1: a few bonded-like pairs"""
-    rng = np.random.default_rng(seed)
-    rows = [set() for _ in range(n)]
-    for a in range(0, n - 1, 3):
-        b = int(rng.integers(a + 1, n))
-        rows[a].add(b)
-        rows[b].add(a)
-    width = max(len(r) for r in rows)
-    ex = -np.ones((n, width), np.int32)
-    for a, r in enumerate(rows):
-        ex[a, : len(r)] = sorted(r)
-    return torch.tensor(ex)
-
 
 ALPHA, COULOMB, CUTOFF = 3.0, 138.935, 1.0
 
@@ -136,16 +25,16 @@ def op_direct_box_grad(pos, q, box, ex, device="cpu"):
 
 @pytest.mark.parametrize("triclinic", [False, True])
 def test_direct_box_gradient_matches_the_float64_restatement(triclinic):
-    pos, q, box = system(triclinic)
-    ex = exclusion_table(len(q))
+    pos, q, box = f64.system(triclinic)
+    ex = f64.exclusion_table(len(q))
     _, _, _, gb = op_direct_box_grad(pos, q, box, ex)
     assert gb is not None and gb.dtype == torch.float32 and gb.shape == (3, 3)
     tb32 = torch.tensor(box)
     neighbors, deltas, _, _ = getNeighborPairs(torch.tensor(pos), CUTOFF, -1, tb32)
-    pairs = listed_pairs(neighbors, deltas, torch.tensor(pos), tb32, ex)
+    pairs = f64.listed_pairs_box(neighbors, deltas, torch.tensor(pos), tb32, ex)
     assert int((pairs[2] != 0).any(dim=1).sum()) > 10                   # wrapped pairs are present
     b64 = torch.tensor(box, dtype=torch.float64, requires_grad=True)
-    e = direct_energy(torch.tensor(pos, dtype=torch.float64), torch.tensor(q, dtype=torch.float64), b64, pairs, ALPHA, COULOMB)
+    e = f64.direct_energy_box(torch.tensor(pos, dtype=torch.float64), torch.tensor(q, dtype=torch.float64), b64, pairs, ALPHA, COULOMB)
     (ref,) = torch.autograd.grad(e, b64)
     scale = float(ref.abs().max())
     assert float(ref[0, 1].abs()) > 1e-3 * scale                        # entries above the diagonal are non-zero too
@@ -155,7 +44,7 @@ def test_direct_box_gradient_matches_the_float64_restatement(triclinic):
 @pytest.mark.parametrize("triclinic,order,grid", [(False, 4, (20, 22, 18)), (True, 5, (24, 25, 21)), (True, 4, (9, 10, 11))])
 def test_reciprocal_box_gradient_matches_the_float64_restatement(triclinic, order, grid):
     from nnpops_amd.pme.pme import bspline_moduli
-    pos, q, box = system(triclinic)
+    pos, q, box = f64.system(triclinic)
     mods = [bspline_moduli(k, order) for k in grid]
     tp = torch.tensor(pos, requires_grad=True)
     tq = torch.tensor(q, requires_grad=True)
@@ -164,7 +53,7 @@ def test_reciprocal_box_gradient_matches_the_float64_restatement(triclinic, orde
     e.backward()
     b64 = torch.tensor(box, dtype=torch.float64, requires_grad=True)
     p64 = torch.tensor(pos, dtype=torch.float64, requires_grad=True)
-    e64 = spme_energy(p64, torch.tensor(q, dtype=torch.float64), b64, grid, order, ALPHA, COULOMB, mods)
+    e64 = f64.spme_energy(p64, torch.tensor(q, dtype=torch.float64), b64, grid, order, ALPHA, COULOMB, mods)
     ref_b, ref_p = torch.autograd.grad(e64, (b64, p64))
     assert abs(float(e) - float(e64)) <= 1e-5 * abs(float(e64))
     torch.testing.assert_close(tp.grad.double(), ref_p, rtol=0, atol=1e-4 * float(ref_p.abs().max()))
@@ -173,30 +62,25 @@ def test_reciprocal_box_gradient_matches_the_float64_restatement(triclinic, orde
     torch.testing.assert_close(tb.grad.double(), ref_b, rtol=0, atol=2e-5 * scale)     # (measured: at most 1.1e-6 x scale)
 
 
-def virial(box, grad_box, pos, grad_pos):
-    """W = -(B^T dE/dB + sum_j x_j (x) dE/dx_j), float64"""
-    return -(box.double().T @ grad_box.double() + pos.double().T @ grad_pos.double())
-
-
 def test_virial_is_symmetric_for_each_term():
     from nnpops_amd.pme.pme import bspline_moduli
-    pos, q, box = system(True, n=60, seed=9)
-    ex = exclusion_table(len(q))
+    pos, q, box = f64.system(True, n=60, seed=9)
+    ex = f64.exclusion_table(len(q))
     _, gp, _, gb = op_direct_box_grad(pos, q, box, ex)
-    W = virial(torch.tensor(box), gb, torch.tensor(pos), gp)
+    W = f64.virial(torch.tensor(box), gb, torch.tensor(pos), gp)
     assert float((W - W.T).abs().max()) <= 2e-5 * float(W.abs().max()), W
     grid = (24, 24, 24)
     mods = [bspline_moduli(k, 5) for k in grid]
     tp = torch.tensor(pos, requires_grad=True)
     tb = torch.tensor(box, requires_grad=True)
     torch.ops.pme.pme_reciprocal(tp, torch.tensor(q), tb, *grid, 5, ALPHA, COULOMB, *mods).backward()
-    W = virial(torch.tensor(box), tb.grad, torch.tensor(pos), tp.grad)
+    W = f64.virial(torch.tensor(box), tb.grad, torch.tensor(pos), tp.grad)
     assert float((W - W.T).abs().max()) <= 2e-5 * float(W.abs().max()), W
 
 
 def test_outputs_unchanged_when_the_box_needs_a_gradient():
-    pos, q, box = system(True)
-    ex = exclusion_table(len(q))
+    pos, q, box = f64.system(True)
+    ex = f64.exclusion_table(len(q))
     pme = PME(20, 20, 20, 5, ALPHA, COULOMB, ex, reciprocal=True)
     out = []
     for box_grad in (False, True):
@@ -213,8 +97,8 @@ def test_outputs_unchanged_when_the_box_needs_a_gradient():
 
 
 def test_create_graph_is_refused_with_the_box():
-    pos, q, box = system(False)
-    pme = PME(16, 16, 16, 4, ALPHA, COULOMB, exclusion_table(len(q)), reciprocal=True)
+    pos, q, box = f64.system(False)
+    pme = PME(16, 16, 16, 4, ALPHA, COULOMB, f64.exclusion_table(len(q)), reciprocal=True)
     for term in ("direct", "reciprocal"):
         tp = torch.tensor(pos, requires_grad=True)
         tb = torch.tensor(box, requires_grad=True)
@@ -228,8 +112,8 @@ def test_pme_direct_box_scripts_and_matches_pme_direct():
     def energy(pos, q, nb, d, r, ex, box):
         return torch.ops.pme.pme_direct_box(pos, q, nb, d, r, ex, box, 3.0, 138.935)
 
-    pos, q, box = system(True)
-    ex = PME(8, 8, 8, 4, ALPHA, COULOMB, exclusion_table(len(q))).exclusions
+    pos, q, box = f64.system(True)
+    ex = PME(8, 8, 8, 4, ALPHA, COULOMB, f64.exclusion_table(len(q))).exclusions
     tp = torch.tensor(pos)
     tb = torch.tensor(box, requires_grad=True)
     nb, d, r, _ = getNeighborPairs(tp, CUTOFF, -1, tb.detach())
@@ -240,43 +124,12 @@ def test_pme_direct_box_scripts_and_matches_pme_direct():
     assert g.shape == (3, 3) and bool(torch.isfinite(g).all()) and float(g.abs().max()) > 0
 
 
-# ---- against the exact Ewald sum ------------------------------------------------------------------------------------------
-def ewald_energy(pos, q, box, alpha, coulomb, images=2):
-    """real-space images + full k-space + self, float64, differentiable in the box (positions fixed)"""
-    inv = torch.linalg.inv(box)
-    V = torch.linalg.det(box)
-    mmax = 8.0 * alpha / math.pi
-    bn = box.detach().numpy()
-    kmax = [int(np.ceil(mmax * np.linalg.norm(bn[i]))) + 1 for i in range(3)]
-    ks = np.stack(np.meshgrid(*[np.arange(-k, k + 1) for k in kmax], indexing="ij"), -1).reshape(-1, 3)
-    ks = torch.tensor(ks[np.any(ks != 0, axis=1)], dtype=torch.float64)
-    m = ks @ inv.T
-    m2 = (m * m).sum(1)
-    keep = m2.detach() <= mmax * mmax
-    m, m2 = m[keep], m2[keep]
-    phase = 2 * math.pi * (pos @ m.T)
-    S2 = (q @ torch.cos(phase)) ** 2 + (q @ torch.sin(phase)) ** 2
-    e_k = coulomb / (2 * math.pi * V) * torch.sum(torch.exp(-(math.pi / alpha) ** 2 * m2) / m2 * S2)
-    # images around each pair's nearest one (atoms may lie boxes away from each other); the shifts are integer constants
-    rng = torch.arange(-images, images + 1, dtype=torch.float64)
-    cells = torch.stack(torch.meshgrid(rng, rng, rng, indexing="ij"), -1).reshape(-1, 3)
-    x = pos[:, None, :] - pos[None, :, :]
-    n0 = torch.round(x.detach() @ inv.detach())
-    d = x[:, :, None, :] - (n0[:, :, None, :] + cells[None, None, :, :]) @ box
-    r = torch.linalg.norm(d, dim=-1)
-    same = r.detach() < 1e-12
-    r = torch.where(same, torch.ones_like(r), r)
-    t = torch.where(same, torch.zeros_like(r), torch.erfc(alpha * r) / r)
-    e_r = 0.5 * coulomb * torch.sum(q[:, None, None] * q[None, :, None] * t)
-    return e_r + e_k - coulomb * alpha / math.sqrt(math.pi) * torch.sum(q * q)
-
-
 def test_total_box_gradient_converges_to_the_ewald_sum():
-    pos, q, box = system(True, n=24, seed=3, outside=True)
+    pos, q, box = f64.system(True, n=24, seed=3, outside=True)
     alpha = 4.0
     b64 = torch.tensor(box, dtype=torch.float64, requires_grad=True)
-    (ref,) = torch.autograd.grad(ewald_energy(torch.tensor(pos, dtype=torch.float64), torch.tensor(q, dtype=torch.float64), b64,
-                                              alpha, COULOMB), b64)
+    (ref,) = torch.autograd.grad(f64.ewald_energy(torch.tensor(pos, dtype=torch.float64), torch.tensor(q, dtype=torch.float64), b64,
+                                                  alpha, COULOMB), b64)
     errs = []
     for grid in (12, 24, 48):
         pme = PME(grid, grid, grid, 5, alpha, COULOMB, torch.zeros(len(q), 0, dtype=torch.int32), reciprocal=True)

@@ -1,14 +1,13 @@
-"""Box-vector gradients of PME on the MI355X: pme::pme_direct_box and the box gradient of pme::pme_reciprocal against autograd of a
-float64 pure-torch restatement and of an independent Ewald sum, the CPU key, virial symmetry (up to config 5's 100 000 atoms), the
+"""Box-vector gradients of PME on the MI355X: pme::pme_direct_box and the box gradient of pme::pme_reciprocal against autograd of the
+float64 pure-torch restatement of tests/pme_float64.py and of its independent Ewald sum, the CPU key, virial symmetry (up to config 5's 100 000 atoms), the
 indexed direct path, bitwise repeatability and unchanged outputs, graph capture on a box written in place, and create_graph."""
-import math
-
 import numpy as np
 import pytest
 import torch
 from torch.profiler import ProfilerActivity, profile
 
 import NNPOps  # noqa: F401  (loads the torch ops)
+import pme_float64 as f64
 from NNPOps.neighbors import getNeighborPairs
 from NNPOps.pme import PME
 from nnpops_amd import workloads
@@ -16,150 +15,6 @@ from nnpops_amd.pme.pme import bspline_moduli
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-# ---- a float64 restatement, differentiable in the box ----------------------------------------------------------------------
-def bspline_weights(dr, order):
-    """The kernels' recursion (pme_recip_spline) on float64 tensors: weight i belongs to grid point base + i."""
-    w = [None] * order
-    w[order - 1] = torch.zeros_like(dr)
-    w[1] = dr
-    w[0] = 1 - dr
-    for j in range(3, order):
-        div = 1.0 / (j - 1)
-        w[j - 1] = div * dr * w[j - 2]
-        for k in range(1, j - 1):
-            w[j - k - 1] = div * ((dr + k) * w[j - k - 2] + (j - k - dr) * w[j - k - 1])
-        w[0] = div * (1 - dr) * w[0]
-    scale = 1.0 / (order - 1)
-    w[order - 1] = scale * dr * w[order - 2]
-    for j in range(1, order - 1):
-        w[order - j - 1] = scale * ((dr + j) * w[order - j - 2] + (order - j - dr) * w[order - j - 1])
-    w[0] = scale * (1 - dr) * w[0]
-    return w
-
-
-def spme_energy(pos, q, box, grid, order, alpha, coulomb, moduli):
-    """0.5 sum_k w eterm |S(k)|^2 of the op (no self energy), float64; box enters through B^-1 (fractional coordinates, m = B^-1 k)
-    and det(B)."""
-    K = list(grid)
-    inv = torch.linalg.inv(box)
-    s = pos @ inv
-    u = (s - torch.floor(s)) * torch.tensor(K, dtype=torch.float64)
-    base = torch.floor(u)
-    dr = u - base
-    base = base.long()
-    th = [bspline_weights(dr[:, a], order) for a in range(3)]
-    Q = torch.zeros(K[0] * K[1] * K[2], dtype=torch.float64)
-    qs = q * math.sqrt(coulomb)
-    for i in range(order):
-        for j in range(order):
-            for l in range(order):
-                idx = (((base[:, 0] + i) % K[0]) * K[1] + (base[:, 1] + j) % K[1]) * K[2] + (base[:, 2] + l) % K[2]
-                Q = Q.index_add(0, idx, qs * th[0][i] * th[1][j] * th[2][l])
-    S = torch.fft.rfftn(Q.view(K[0], K[1], K[2]))
-    kz_n = K[2] // 2 + 1
-
-    def signed(k, n):
-        return torch.where(k < (n + 1) // 2, k, k - n).to(torch.float64)
-    mx, my, mz = signed(torch.arange(K[0]), K[0]), signed(torch.arange(K[1]), K[1]), signed(torch.arange(kz_n), K[2])
-    kvec = torch.stack(torch.meshgrid(mx, my, mz, indexing="ij"), -1)
-    m = kvec @ inv.T                                                    # m = B^-1 k
-    m2 = (m * m).sum(-1)
-    zero = m2 == 0
-    m2 = torch.where(zero, torch.ones_like(m2), m2)
-    V = torch.linalg.det(box)
-    mod = moduli[0].double()[:, None, None] * moduli[1].double()[None, :, None] * moduli[2].double()[None, None, :kz_n]
-    eterm = torch.where(zero, torch.zeros_like(m2), torch.exp(-(math.pi / alpha) ** 2 * m2) / (math.pi * V * m2 * mod))
-    kz = torch.arange(kz_n)
-    w = torch.where((kz > 0) & (kz <= (K[2] - 1) // 2), 2.0, 1.0).to(torch.float64)
-    return 0.5 * torch.sum(w * eterm * (S.real ** 2 + S.imag ** 2))
-
-
-def listed_pairs(neighbors, deltas, pos, box, exclusions):
-    """(i, j, n) of the slots the direct op includes, n the integer image shift recovered in float64."""
-    nb = neighbors.cpu().numpy()
-    used = nb[0] >= 0
-    ex = exclusions.cpu().numpy()
-    excluded = {(a, b) for a in range(ex.shape[0]) for b in ex[a] if b >= 0}
-    keep = np.array([u and (a, b) not in excluded for u, a, b in zip(used, nb[0], nb[1])], dtype=bool)
-    i, j = nb[0][keep], nb[1][keep]
-    p = pos.detach().double().cpu().numpy()
-    D = p[i] - p[j] - deltas.detach().double().cpu().numpy()[keep]
-    n = np.rint(D @ np.linalg.inv(box.detach().double().cpu().numpy()))
-    return torch.tensor(i), torch.tensor(j), torch.tensor(n)
-
-
-def direct_energy(pos, q, box, pairs, alpha, coulomb):
-    """sum over the included pairs of coulomb q_i q_j erfc(alpha r) / r, r = |x_i - x_j - n B| (the excluded pairs' correction is
-    box independent and left out)"""
-    i, j, n = pairs
-    d = pos[i] - pos[j] - n @ box
-    r = torch.linalg.norm(d, dim=1)
-    return coulomb * torch.sum(q[i] * q[j] * torch.erfc(alpha * r) / r)
-
-
-def system(triclinic, n=40, seed=2, outside=True):
-    rng = np.random.default_rng(seed)
-    L = 2.4
-    box = np.array([[L, 0, 0], [0.3 * L, 1.05 * L, 0], [-0.25 * L, 0.2 * L, 0.95 * L]]) if triclinic else np.diag([L, 1.1 * L, 0.9 * L])
-    frac = rng.random((n, 3))
-    if outside:                                                    # a third of the atoms one or two box lengths away
-        frac[: n // 3] += rng.integers(-2, 3, (n // 3, 3))
-    pos = frac @ box
-    q = rng.normal(0, 0.5, n)
-    q -= q.mean()
-    return pos.astype(np.float32), q.astype(np.float32), box.astype(np.float32)
-
-
-def exclusion_table(n, seed=4):
-    """symmetric, rows padded with -1: a few bonded-like pairs"""
-    rng = np.random.default_rng(seed)
-    rows = [set() for _ in range(n)]
-    for a in range(0, n - 1, 3):
-        b = int(rng.integers(a + 1, n))
-        rows[a].add(b)
-        rows[b].add(a)
-    width = max(len(r) for r in rows)
-    ex = -np.ones((n, width), np.int32)
-    for a, r in enumerate(rows):
-        ex[a, : len(r)] = sorted(r)
-    return torch.tensor(ex)
-
-
-
-# ---- against the exact Ewald sum ------------------------------------------------------------------------------------------
-def ewald_energy(pos, q, box, alpha, coulomb, images=2):
-    """real-space images + full k-space + self, float64, differentiable in the box (positions fixed)"""
-    inv = torch.linalg.inv(box)
-    V = torch.linalg.det(box)
-    mmax = 8.0 * alpha / math.pi
-    bn = box.detach().numpy()
-    kmax = [int(np.ceil(mmax * np.linalg.norm(bn[i]))) + 1 for i in range(3)]
-    ks = np.stack(np.meshgrid(*[np.arange(-k, k + 1) for k in kmax], indexing="ij"), -1).reshape(-1, 3)
-    ks = torch.tensor(ks[np.any(ks != 0, axis=1)], dtype=torch.float64)
-    m = ks @ inv.T
-    m2 = (m * m).sum(1)
-    keep = m2.detach() <= mmax * mmax
-    m, m2 = m[keep], m2[keep]
-    phase = 2 * math.pi * (pos @ m.T)
-    S2 = (q @ torch.cos(phase)) ** 2 + (q @ torch.sin(phase)) ** 2
-    e_k = coulomb / (2 * math.pi * V) * torch.sum(torch.exp(-(math.pi / alpha) ** 2 * m2) / m2 * S2)
-    # images around each pair's nearest one (atoms may lie boxes away from each other); the shifts are integer constants
-    rng = torch.arange(-images, images + 1, dtype=torch.float64)
-    cells = torch.stack(torch.meshgrid(rng, rng, rng, indexing="ij"), -1).reshape(-1, 3)
-    x = pos[:, None, :] - pos[None, :, :]
-    n0 = torch.round(x.detach() @ inv.detach())
-    d = x[:, :, None, :] - (n0[:, :, None, :] + cells[None, None, :, :]) @ box
-    r = torch.linalg.norm(d, dim=-1)
-    same = r.detach() < 1e-12
-    r = torch.where(same, torch.ones_like(r), r)
-    t = torch.where(same, torch.zeros_like(r), torch.erfc(alpha * r) / r)
-    e_r = 0.5 * coulomb * torch.sum(q[:, None, None] * q[None, :, None] * t)
-    return e_r + e_k - coulomb * alpha / math.sqrt(math.pi) * torch.sum(q * q)
-
-
-
 ALPHA, COULOMB, CUTOFF = 3.0, 138.935, 1.0
 
 
@@ -182,24 +37,18 @@ def recip_step(pos, q, box, grid, order, device=DEV, alpha=ALPHA, box_grad=True)
     return (e.detach(),) + torch.autograd.grad(e, (tp, tq, tb) if box_grad else (tp, tq))
 
 
-def virial(box, grad_box, pos, grad_pos):
-    """W = -(B^T dE/dB + sum_j x_j (x) dE/dx_j), float64"""
-    box, grad_box, pos, grad_pos = (torch.as_tensor(t).double().cpu() for t in (box, grad_box, pos, grad_pos))
-    return -(box.T @ grad_box + pos.T @ grad_pos)
-
-
 @pytest.mark.parametrize("triclinic", [False, True])
 def test_direct_box_gradient_matches_the_float64_restatement(triclinic):
-    pos, q, box = system(triclinic)
-    ex = exclusion_table(len(q))
+    pos, q, box = f64.system(triclinic)
+    ex = f64.exclusion_table(len(q))
     gb = direct_step(pos, q, box, ex)[3]
     assert gb.dtype == torch.float32 and gb.device.type == "cuda"
     tb32 = torch.tensor(box)
     neighbors, deltas, _, _ = getNeighborPairs(torch.tensor(pos), CUTOFF, -1, tb32)
-    pairs = listed_pairs(neighbors, deltas, torch.tensor(pos), tb32, ex)
+    pairs = f64.listed_pairs_box(neighbors, deltas, torch.tensor(pos), tb32, ex)
     assert int((pairs[2] != 0).any(dim=1).sum()) > 10
     b64 = torch.tensor(box, dtype=torch.float64, requires_grad=True)
-    e = direct_energy(torch.tensor(pos, dtype=torch.float64), torch.tensor(q, dtype=torch.float64), b64, pairs, ALPHA, COULOMB)
+    e = f64.direct_energy_box(torch.tensor(pos, dtype=torch.float64), torch.tensor(q, dtype=torch.float64), b64, pairs, ALPHA, COULOMB)
     (ref,) = torch.autograd.grad(e, b64)
     # (measured on an MI355X: at most 8.9e-7 of the largest entry)
     torch.testing.assert_close(gb.double().cpu(), ref, rtol=0, atol=1e-5 * float(ref.abs().max()))
@@ -207,11 +56,11 @@ def test_direct_box_gradient_matches_the_float64_restatement(triclinic):
 
 @pytest.mark.parametrize("triclinic,order,grid", [(False, 4, (20, 22, 18)), (True, 5, (24, 25, 21)), (True, 4, (9, 10, 11))])
 def test_reciprocal_box_gradient_matches_the_float64_restatement(triclinic, order, grid):
-    pos, q, box = system(triclinic)
+    pos, q, box = f64.system(triclinic)
     e, gp, _, gb = recip_step(pos, q, box, grid, order)
     mods = [bspline_moduli(k, order) for k in grid]
     b64 = torch.tensor(box, dtype=torch.float64, requires_grad=True)
-    e64 = spme_energy(torch.tensor(pos, dtype=torch.float64), torch.tensor(q, dtype=torch.float64), b64, grid, order, ALPHA, COULOMB, mods)
+    e64 = f64.spme_energy(torch.tensor(pos, dtype=torch.float64), torch.tensor(q, dtype=torch.float64), b64, grid, order, ALPHA, COULOMB, mods)
     (ref,) = torch.autograd.grad(e64, b64)
     assert abs(float(e) - float(e64)) <= 1e-5 * abs(float(e64))
     # (measured on an MI355X: at most 2.3e-6 of the largest entry, the cubic order-4 case)
@@ -219,8 +68,8 @@ def test_reciprocal_box_gradient_matches_the_float64_restatement(triclinic, orde
 
 
 def test_device_matches_the_cpu_key():
-    pos, q, box = system(True, n=300, seed=12)
-    ex = exclusion_table(len(q))
+    pos, q, box = f64.system(True, n=300, seed=12)
+    ex = f64.exclusion_table(len(q))
     for fn in (lambda d: direct_step(pos, q, box, ex, device=d), lambda d: recip_step(pos, q, box, (24, 24, 24), 5, device=d)):
         host, dev = fn("cpu"), fn(DEV)
         for h, d in zip(host[1:], dev[1:]):              # (measured: at most 1.1e-6 of the largest entry)
@@ -228,11 +77,11 @@ def test_device_matches_the_cpu_key():
 
 
 def test_total_box_gradient_converges_to_the_ewald_sum():
-    pos, q, box = system(True, n=24, seed=3, outside=True)
+    pos, q, box = f64.system(True, n=24, seed=3, outside=True)
     alpha = 4.0
     b64 = torch.tensor(box, dtype=torch.float64, requires_grad=True)
-    (ref,) = torch.autograd.grad(ewald_energy(torch.tensor(pos, dtype=torch.float64), torch.tensor(q, dtype=torch.float64), b64,
-                                              alpha, COULOMB), b64)
+    (ref,) = torch.autograd.grad(f64.ewald_energy(torch.tensor(pos, dtype=torch.float64), torch.tensor(q, dtype=torch.float64), b64,
+                                                  alpha, COULOMB), b64)
     errs = []
     for grid in (12, 24, 48):
         pme = PME(grid, grid, grid, 5, alpha, COULOMB, torch.zeros(len(q), 0, dtype=torch.int32), reciprocal=True)
@@ -246,15 +95,15 @@ def test_total_box_gradient_converges_to_the_ewald_sum():
 
 
 def test_virial_is_symmetric_small_and_at_100k_atoms():
-    pos, q, box = system(True, n=200, seed=9)
-    ex = exclusion_table(len(q))
+    pos, q, box = f64.system(True, n=200, seed=9)
+    ex = f64.exclusion_table(len(q))
     # (asymmetry measured on an MI355X, relative to the largest entry: 9.0e-7 direct and 4.1e-7 reciprocal at 200 atoms, 2.1e-6
     #  and 1.6e-8 at 100 000)
     _, gp, _, gb = direct_step(pos, q, box, ex)
-    W = virial(box, gb, pos, gp)
+    W = f64.virial(box, gb, pos, gp)
     assert float((W - W.T).abs().max()) <= 1e-5 * float(W.abs().max()), W
     _, gp, _, gb = recip_step(pos, q, box, (32, 32, 32), 5)
-    W = virial(box, gb, pos, gp)
+    W = f64.virial(box, gb, pos, gp)
     assert float((W - W.T).abs().max()) <= 1e-5 * float(W.abs().max()), W
     # config 5: 100 000 atoms, cutoff 5.2, a 3.2 M-slot list (indexed path), reciprocal at 192^3, order 5
     pos, _, box = workloads.random_box(100000, density=0.1, seed=6)
@@ -262,17 +111,17 @@ def test_virial_is_symmetric_small_and_at_100k_atoms():
     q -= q.mean()
     ex = torch.zeros(len(pos), 0, dtype=torch.int32)
     _, gp, _, gb = direct_step(pos, q, box, ex, max_num_pairs=3_200_000, cutoff=5.2, alpha=0.6)
-    W = virial(box, gb, pos, gp)
+    W = f64.virial(box, gb, pos, gp)
     assert float((W - W.T).abs().max()) <= 2e-5 * float(W.abs().max()), W
     _, gp, _, gb = recip_step(pos, q, box, (192, 192, 192), 5, alpha=0.6)
-    W = virial(box, gb, pos, gp)
+    W = f64.virial(box, gb, pos, gp)
     assert float((W - W.T).abs().max()) <= 2e-5 * float(W.abs().max()), W
 
 
 def test_indexed_direct_path_matches_the_plain_path():
     pos, _, box = workloads.random_box(20000, density=0.1, seed=3)
     q = np.random.default_rng(3).normal(0, 0.4, len(pos)).astype(np.float32)
-    ex = exclusion_table(len(pos))
+    ex = f64.exclusion_table(len(pos))
     from nnpops_amd import capi
     exs = PME(16, 16, 16, 5, 0.6, COULOMB, ex).exclusions.to(DEV)
     out = []
@@ -306,8 +155,8 @@ def test_indexed_direct_path_matches_the_plain_path():
 
 
 def test_bitwise_repeatable_and_outputs_unchanged():
-    pos, q, box = system(True, n=300, seed=5)
-    ex = exclusion_table(len(q))
+    pos, q, box = f64.system(True, n=300, seed=5)
+    ex = f64.exclusion_table(len(q))
     pme = PME(24, 24, 24, 5, ALPHA, COULOMB, ex, reciprocal=True)
     runs = []
     for box_grad in (False, True, True):
@@ -327,8 +176,8 @@ def test_bitwise_repeatable_and_outputs_unchanged():
 
 
 def test_graph_capture_follows_a_box_written_in_place():
-    pos, q, box = system(True, n=120, seed=7, outside=False)
-    pme = PME(24, 24, 24, 5, ALPHA, COULOMB, exclusion_table(len(q)), reciprocal=True)
+    pos, q, box = f64.system(True, n=120, seed=7, outside=False)
+    pme = PME(24, 24, 24, 5, ALPHA, COULOMB, f64.exclusion_table(len(q)), reciprocal=True)
     tq = torch.tensor(q, device=DEV)
     static_pos = torch.tensor(pos, device=DEV, requires_grad=True)
     static_box = torch.tensor(box, device=DEV, requires_grad=True)
@@ -364,8 +213,8 @@ def test_graph_capture_follows_a_box_written_in_place():
 
 
 def test_create_graph_is_refused_with_the_box():
-    pos, q, box = system(False)
-    pme = PME(16, 16, 16, 4, ALPHA, COULOMB, exclusion_table(len(q)), reciprocal=True)
+    pos, q, box = f64.system(False)
+    pme = PME(16, 16, 16, 4, ALPHA, COULOMB, f64.exclusion_table(len(q)), reciprocal=True)
     for term in ("direct", "reciprocal"):
         tp = torch.tensor(pos, device=DEV, requires_grad=True)
         tb = torch.tensor(box, device=DEV, requires_grad=True)
@@ -377,8 +226,8 @@ def test_create_graph_is_refused_with_the_box():
 
 def test_c_abi_box_gradients():
     from nnpops_amd import capi
-    pos, q, box = system(True, n=300, seed=8)
-    ex = exclusion_table(len(q))
+    pos, q, box = f64.system(True, n=300, seed=8)
+    ex = f64.exclusion_table(len(q))
     exs = PME(8, 8, 8, 4, ALPHA, COULOMB, ex).exclusions.to(DEV)
     tp, tq, tb = (torch.tensor(a, device=DEV) for a in (pos, q, box))
     nb, d, r, _ = getNeighborPairs(tp, CUTOFF, -1, tb)

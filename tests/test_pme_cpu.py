@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+import pme_float64 as f64
 from oracle import pme_direct_oracle
 
 
@@ -13,14 +14,10 @@ def _cases(golden_dir):
         yield k, {name[len(f"c{k}_"):]: g[name] for name in g.files if name.startswith(f"c{k}_")}
 
 
-def _sorted_excl(excl):
-    return -np.sort(-excl.astype(np.int64), axis=1) if excl.shape[1] else excl.astype(np.int64)
-
-
 def test_oracle_is_pinned_to_the_reference_op(golden_dir):
     for k, c in _cases(golden_dir):
         e, pd, cd = pme_direct_oracle(c["positions"], c["charges"], c["neighbors"], c["deltas"], c["distances"],
-                                      _sorted_excl(c["exclusions"]), c["alpha"], c["coulomb"])
+                                      f64.sorted_excl(c["exclusions"]), c["alpha"], c["coulomb"])
         scale = np.abs(c["pos_grad"]).max()
         assert abs(e - float(c["energy"])) <= 2e-6 * max(abs(float(c["energy"])), 1.0), k
         np.testing.assert_allclose(pd, c["pos_grad"], rtol=2e-5, atol=2e-6 * scale)
@@ -63,7 +60,7 @@ def test_ops_run_below_autograd_and_validate_their_arguments(golden_dir):
     from NNPOps.neighbors import getNeighborPairs
     k, c = next(_cases(golden_dir))
     pos, q, box = torch.tensor(c["positions"]), torch.tensor(c["charges"]), torch.tensor(c["box"])
-    excl = torch.tensor(_sorted_excl(c["exclusions"]).astype(np.int32)).reshape(len(c["positions"]), -1)
+    excl = torch.tensor(f64.sorted_excl(c["exclusions"]).astype(np.int32)).reshape(len(c["positions"]), -1)
     with torch.inference_mode():
         nb, dl, ds, n = getNeighborPairs(pos, float(c["cutoff"]), -1, box)
         e = torch.ops.pme.pme_direct(pos, q, nb, dl, ds, excl, float(c["alpha"]), float(c["coulomb"]))

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import pme_direct_reference as ref
+import pme_float64 as f64
 from oracle import pme_direct_oracle
 
 _lists = {}
@@ -22,15 +23,11 @@ def _case(name):
     return _lists[name]
 
 
-def _sorted_excl(excl):
-    return -np.sort(-excl.astype(np.int64), axis=1) if excl.shape[1] else excl.astype(np.int64)
-
-
 def test_judge_reproduces_the_reference_vectors(golden_dir):
     g = np.load(f"{golden_dir}/pme_ref.npz")
     for k in range(int(g["num_cases"])):
         c = {name[len(f"c{k}_"):]: g[name] for name in g.files if name.startswith(f"c{k}_")}
-        excl = _sorted_excl(c["exclusions"]).reshape(len(c["positions"]), -1)
+        excl = f64.sorted_excl(c["exclusions"]).reshape(len(c["positions"]), -1)
         j = ref.judge(c["positions"], c["charges"], c["neighbors"], c["deltas"], c["distances"], excl, c["alpha"], c["coulomb"])
         assert abs(j["energy"] - float(c["energy"])) <= 1e-5 * max(abs(float(c["energy"])), 1.0), k
         assert np.abs(j["pos_deriv"] - c["pos_grad"]).max() <= 1e-4 * np.abs(c["pos_grad"]).max(), k
@@ -50,7 +47,7 @@ def test_judge_reproduces_the_oracle_on_a_salt_box():
         excl[a, 0], excl[b, 0] = b, a
     for a, b in zip(order[1:301:2], order[2:302:2]):
         excl[a, 1], excl[b, 1] = b, a
-    excl = _sorted_excl(excl)
+    excl = f64.sorted_excl(excl)
     nb, dl, ds, found = ref.host_pair_list(pos, 9.0, 100000, box)
     assert 50000 < found < 100000
     e, pd, cd = pme_direct_oracle(pos, q, nb, dl, ds, excl, 0.35, ref.COULOMB)

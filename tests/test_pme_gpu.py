@@ -3,15 +3,12 @@ import numpy as np
 import pytest
 import torch
 
+import pme_float64 as f64
 from nnpops_amd import workloads
 from oracle import pme_direct_oracle
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def _sorted_excl(excl):
-    return -np.sort(-excl.astype(np.int64), axis=1) if excl.shape[1] else excl.astype(np.int64)
 
 
 def test_c_abi_reproduces_the_reference_vectors(golden_dir):
@@ -21,7 +18,7 @@ def test_c_abi_reproduces_the_reference_vectors(golden_dir):
         c = {name[len(f"c{k}_"):]: g[name] for name in g.files if name.startswith(f"c{k}_")}
         t = lambda a, dt=torch.float32: torch.tensor(a, dtype=dt, device=DEV)
         e, pd, cd = capi.pme_direct(t(c["positions"]), t(c["charges"]), t(c["neighbors"], torch.int32), t(c["deltas"]), t(c["distances"]),
-                                    t(_sorted_excl(c["exclusions"]), torch.int32), float(c["alpha"]), float(c["coulomb"]))
+                                    t(f64.sorted_excl(c["exclusions"]), torch.int32), float(c["alpha"]), float(c["coulomb"]))
         assert abs(float(e) - float(c["energy"])) <= 1e-5 * max(abs(float(c["energy"])), 1.0), k
         assert np.abs(pd.cpu().numpy() - c["pos_grad"]).max() <= 1e-4 * np.abs(c["pos_grad"]).max()
         assert np.abs(cd.cpu().numpy() - c["charge_grad"]).max() <= 1e-4 * np.abs(c["charge_grad"]).max()
@@ -38,7 +35,7 @@ def _salt_box(n, seed, max_excl):
         for i, j in ((a, b), (b, a)):
             if fill[i] < max_excl:
                 excl[i, fill[i]] = j; fill[i] += 1
-    return pos, charges, box, _sorted_excl(excl)
+    return pos, charges, box, f64.sorted_excl(excl)
 
 
 @pytest.mark.parametrize("n,compact", [(1500, False), (4000, True)])

@@ -1,8 +1,9 @@
 """Every pass of reciprocal-space PME on the MI355X against float64, at the sizes where the passes' loops repeat: more than 1024
 bricks (the scan's carry), more than 64 atoms in a brick (the rank sort), more than 256 atoms staged for a brick (the gathers' LDS
 staging), more than 262 144 complex points (the convolution's and the box gradient's stride), more than 256 atoms (every per-atom
-kernel), and every regime of the cyclic window of bricks.  tests/test_pme_reciprocal_passes_reference_cpu.py holds the float64
-passes, the cases and the proof that each case reaches its loop; this file runs capi.pme_reciprocal_passes on them.
+kernel), and every regime of the cyclic window of bricks.  tests/pme_recip_passes_reference.py holds the float64 passes and the
+cases, tests/test_pme_reciprocal_passes_reference_cpu.py the proof that each case reaches its loop; this file runs
+capi.pme_reciprocal_passes on them.
 
 Each pass is judged with the DEVICE's own input to that pass, widened to float64, so an error belongs to one kernel: the spread from
 the positions, the convolution from the device's rfftn, the interpolation from the device's potential grid.  Every figure is
@@ -11,22 +12,15 @@ measured on the MI355X over all cases x 10, one digit (DESIGN.md s8b lists the m
 variation of float32 sums of up to about 2000 terms."""
 import ctypes as C
 import functools
-import importlib.util
 import math
-import os
 
 import pytest
 import torch
 
+import pme_recip_passes_reference as ref
 from nnpops_amd import capi
 
 pytestmark = pytest.mark.gpu
-
-_spec = importlib.util.spec_from_file_location("pme_reciprocal_passes_reference",
-                                               os.path.join(os.path.dirname(os.path.abspath(__file__)),
-                                                            "test_pme_reciprocal_passes_reference_cpu.py"))
-ref = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(ref)
 
 DEV = torch.device("cuda:0")
 ALPHA, COULOMB = ref.ALPHA, ref.COULOMB

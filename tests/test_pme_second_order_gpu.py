@@ -1,7 +1,7 @@
 """Second derivatives of PME with respect to positions and charges on the MI355X: pme::pme_direct_twice, pme::pme_reciprocal_twice,
-PME(..., twice_differentiable=True) and the C entries behind them against autograd of a float64 pure-torch restatement held in this
-file (as tests/test_pme_second_order_cpu.py holds one), against the CPU key, bit for bit between runs and against the existing ops'
-first-order outputs, on both kinds of pair list, at 100 000 atoms, and through a captured graph.
+PME(..., twice_differentiable=True) and the C entries behind them against autograd of the float64 pure-torch restatement of
+tests/pme_float64.py (the one tests/test_pme_second_order_cpu.py uses), against the CPU key, bit for bit between runs and against
+the existing ops' first-order outputs, on both kinds of pair list, at 100 000 atoms, and through a captured graph.
 
 Every comparison prints its figure before it asserts: max|op - ref| / max|ref| against the float64 restatement.  A bar is the worst
 figure measured on the MI355X over the test's cases x 10, rounded to one digit; device against CPU key: that bar plus the CPU key's
@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import NNPOps  # noqa: F401  (loads the torch ops)
+import pme_float64 as f64
 from NNPOps.neighbors import getNeighborPairs
 from NNPOps.pme import PME
 from nnpops_amd import capi, workloads
@@ -38,149 +39,6 @@ BAR_TRANSLATION = (0.0, 0.0)
 BAR_BILINEAR = {"direct": 3e-9, "reciprocal": 2e-8}      # |u.Hv - v.Hu| / sum |u_i (Hv)_i|: measured 3.2e-10, 1.5e-9
 
 
-# ---- the float64 restatement (see tests/test_pme_second_order_cpu.py) ----------------------------------------------------------------
-def bspline_weights(dr, order):
-    w = [None] * order
-    w[order - 1] = torch.zeros_like(dr)
-    w[1] = dr
-    w[0] = 1 - dr
-    for j in range(3, order):
-        div = 1.0 / (j - 1)
-        w[j - 1] = div * dr * w[j - 2]
-        for k in range(1, j - 1):
-            w[j - k - 1] = div * ((dr + k) * w[j - k - 2] + (j - k - dr) * w[j - k - 1])
-        w[0] = div * (1 - dr) * w[0]
-    scale = 1.0 / (order - 1)
-    w[order - 1] = scale * dr * w[order - 2]
-    for j in range(1, order - 1):
-        w[order - j - 1] = scale * ((dr + j) * w[order - j - 2] + (order - j - dr) * w[order - j - 1])
-    w[0] = scale * (1 - dr) * w[0]
-    return w
-
-
-def spme_energy(pos, q, box, grid, order, alpha, coulomb, moduli):
-    """0.5 sum_k w eterm |S(k)|^2 of the op (no self energy), float64 on the host, differentiable in pos and q"""
-    K = list(grid)
-    inv = torch.linalg.inv(box)
-    s = pos @ inv
-    u = (s - torch.floor(s.detach())) * torch.tensor(K, dtype=torch.float64)
-    base = torch.floor(u.detach())
-    dr = u - base
-    base = base.long()
-    th = [bspline_weights(dr[:, a], order) for a in range(3)]
-    Q = torch.zeros(K[0] * K[1] * K[2], dtype=torch.float64)
-    qs = q * math.sqrt(coulomb)
-    for i in range(order):
-        for j in range(order):
-            for l in range(order):
-                idx = (((base[:, 0] + i) % K[0]) * K[1] + (base[:, 1] + j) % K[1]) * K[2] + (base[:, 2] + l) % K[2]
-                Q = Q.index_add(0, idx, qs * th[0][i] * th[1][j] * th[2][l])
-    S = torch.fft.rfftn(Q.view(K[0], K[1], K[2]))
-    kz_n = K[2] // 2 + 1
-
-    def signed(k, n):
-        return torch.where(k < (n + 1) // 2, k, k - n).to(torch.float64)
-    mx, my, mz = signed(torch.arange(K[0]), K[0]), signed(torch.arange(K[1]), K[1]), signed(torch.arange(kz_n), K[2])
-    kvec = torch.stack(torch.meshgrid(mx, my, mz, indexing="ij"), -1)
-    m = kvec @ inv.T
-    m2 = (m * m).sum(-1)
-    zero = m2 == 0
-    m2 = torch.where(zero, torch.ones_like(m2), m2)
-    V = torch.linalg.det(box)
-    mod = moduli[0].double().cpu()[:, None, None] * moduli[1].double().cpu()[None, :, None] * moduli[2].double().cpu()[None, None, :kz_n]
-    eterm = torch.where(zero, torch.zeros_like(m2), torch.exp(-(math.pi / alpha) ** 2 * m2) / (math.pi * V * m2 * mod))
-    kz = torch.arange(kz_n)
-    w = torch.where((kz > 0) & (kz <= (K[2] - 1) // 2), 2.0, 1.0).to(torch.float64)
-    return 0.5 * torch.sum(w * eterm * (S.real ** 2 + S.imag ** 2))
-
-
-def listed_pairs(neighbors, deltas, pos, exclusions):
-    """(i, j, shift) of the slots the direct op includes -- shift = x_i - x_j - delta, frozen, float64 -- and the excluded pairs (a < b)"""
-    nb = neighbors.cpu().numpy()
-    ex = exclusions.cpu().numpy()
-    excluded = {(a, int(b)) for a in range(ex.shape[0]) for b in ex[a] if b >= 0}
-    keep = np.array([a >= 0 and b >= 0 and (a, b) not in excluded for a, b in zip(nb[0], nb[1])], dtype=bool)
-    i, j = torch.tensor(nb[0][keep]).long(), torch.tensor(nb[1][keep]).long()
-    p = pos.detach().double().cpu()
-    shift = p[i] - p[j] - deltas.detach().double().cpu()[torch.tensor(keep)]
-    once = sorted((a, b) for a, b in excluded if a < b)
-    return i, j, shift, torch.tensor([a for a, _ in once], dtype=torch.long), torch.tensor([b for _, b in once], dtype=torch.long)
-
-
-def direct_energy(pos, q, pairs, alpha, coulomb, magnitude=False):
-    i, j, shift, ea, eb = pairs
-    size = torch.abs if magnitude else (lambda t: t)
-    r = torch.linalg.norm(pos[i] - pos[j] - shift, dim=1)
-    e = torch.sum(size(coulomb * q[i] * q[j] * torch.erfc(alpha * r) / r))
-    if len(ea):
-        r = torch.linalg.norm(pos[ea] - pos[eb], dim=1)
-        e = e + torch.sum(size(-coulomb * q[ea] * q[eb] * torch.erf(alpha * r) / r))
-    return e
-
-
-def system(triclinic, n=40, seed=2, outside=True):
-    rng = np.random.default_rng(seed)
-    L = 2.4
-    box = np.array([[L, 0, 0], [0.3 * L, 1.05 * L, 0], [-0.25 * L, 0.2 * L, 0.95 * L]]) if triclinic else np.diag([L, 1.1 * L, 0.9 * L])
-    frac = rng.random((n, 3))
-    if outside:                                                    # a third of the atoms one or two box lengths away
-        frac[: n // 3] += rng.integers(-2, 3, (n // 3, 3))
-    pos = frac @ box
-    q = rng.normal(0, 0.5, n)
-    q -= q.mean()
-    return pos.astype(np.float32), q.astype(np.float32), box.astype(np.float32)
-
-
-def exclusion_table(n, seed=4):
-    rng = np.random.default_rng(seed)
-    rows = [set() for _ in range(n)]
-    for a in range(0, n - 1, 3):
-        b = int(rng.integers(a + 1, n))
-        rows[a].add(b)
-        rows[b].add(a)
-    width = max(len(r) for r in rows)
-    ex = -np.ones((n, width), np.int32)
-    for a, r in enumerate(rows):
-        ex[a, : len(r)] = sorted(r)
-    return torch.tensor(ex)
-
-
-def cotangents(n, seed):
-    gen = torch.Generator().manual_seed(seed)
-    return torch.randn(n, 3, generator=gen, dtype=torch.float64), torch.randn(n, generator=gen, dtype=torch.float64)
-
-
-def second_order(energy, x, q, g, v, w):
-    """energy, first gradients of g E, and the gradients of L = sum v . d(gE)/dx + sum w d(gE)/dq with respect to x, q, g"""
-    e = energy(x, q)
-    P, C = torch.autograd.grad(g * e, (x, q), create_graph=True)
-    L = (v * P).sum() + (w * C).sum()
-    gx, gq, gg = torch.autograd.grad(L, (x, q, g))
-    return e.detach(), P.detach(), C.detach(), gx, gq, gg
-
-
-def rel(a, ref):
-    ref = ref.detach().double().cpu()
-    return float((a.detach().double().cpu() - ref).abs().max()) / float(ref.abs().max())
-
-
-def compare(label, op, ref, terms=0.0):
-    """the restatement tied to the op by the project's existing bars (energy 1e-5 of max(sum of the terms' magnitudes, |energy|), first
-    gradients 1e-4 of the largest component); returns the second-order figures"""
-    assert abs(float(op[0]) - float(ref[0])) <= 1e-5 * max(terms, abs(float(ref[0]))), (label, float(op[0]), float(ref[0]))
-    assert rel(op[1], ref[1]) <= 1e-4 and rel(op[2], ref[2]) <= 1e-4, (label, rel(op[1], ref[1]), rel(op[2], ref[2]))
-    figures = tuple(rel(op[k], ref[k]) for k in (3, 4, 5))
-    print(f"{label}: dL/dx {figures[0]:.2e}  dL/dq {figures[1]:.2e}  dL/dg {figures[2]:.2e}")
-    return figures
-
-
-def leaves(pos, q, dtype, device):
-    x = torch.tensor(pos, dtype=dtype, device=device, requires_grad=True)
-    c = torch.tensor(q, dtype=dtype, device=device, requires_grad=True)
-    g = torch.tensor(0.7, dtype=dtype, device=device, requires_grad=True)
-    return x, c, g
-
-
 def device_list(pos, box, indexed):
     """the op's list on the device: from a differentiable call with a slot budget (the transposed index is built and cached) or from a
     plain call with one slot per candidate pair (-1 slots among the pairs, no index)"""
@@ -193,20 +51,20 @@ def device_list(pos, box, indexed):
 
 
 def direct_reference(pos, q, nb, dl, ex, v, w):
-    pairs = listed_pairs(nb, dl, torch.tensor(pos), ex)
+    pairs = f64.listed_pairs_frozen(nb, dl, torch.tensor(pos), ex)
     assert len(pairs[3]) > 5 and len(pairs[0]) > 100
-    x, c, g = leaves(pos, q, torch.float64, "cpu")
-    ref = second_order(lambda a, b: direct_energy(a, b, pairs, ALPHA, COULOMB), x, c, g, v, w)
-    return ref, float(direct_energy(x.detach(), c.detach(), pairs, ALPHA, COULOMB, magnitude=True))
+    x, c, g = f64.leaves(pos, q, torch.float64, "cpu")
+    ref = f64.second_order(lambda a, b: f64.direct_energy_frozen(a, b, pairs, ALPHA, COULOMB), x, c, g, v, w)
+    return ref, float(f64.direct_energy_frozen(x.detach(), c.detach(), pairs, ALPHA, COULOMB, magnitude=True))
 
 
 # ---- 7 + 9: against the restatement and the CPU key, both kinds of list ------------------------------------------------------------------
 @pytest.mark.parametrize("triclinic", [False, True])
 def test_direct_double_backward_on_both_kinds_of_list(triclinic):
-    pos, q, box = system(triclinic)
+    pos, q, box = f64.system(triclinic)
     n = len(q)
-    ex = PME(8, 8, 8, 4, ALPHA, COULOMB, exclusion_table(n)).exclusions
-    v, w = cotangents(n, 11)
+    ex = PME(8, 8, 8, 4, ALPHA, COULOMB, f64.exclusion_table(n)).exclusions
+    v, w = f64.cotangents(n, 11)
     vd, wd = v.float().to(DEV), w.float().to(DEV)
     results = {}
     for kind in ("indexed", "plain", "shuffled"):
@@ -215,24 +73,24 @@ def test_direct_double_backward_on_both_kinds_of_list(triclinic):
             perm = torch.randperm(nb.shape[1], generator=torch.Generator().manual_seed(5)).to(DEV)
             nb, dl, ds = nb[:, perm].contiguous(), dl[perm].contiguous(), ds[perm].contiguous()
         ref, terms = direct_reference(pos, q, nb, dl, ex, v, w)
-        x, c, g = leaves(pos, q, torch.float32, DEV)
+        x, c, g = f64.leaves(pos, q, torch.float32, DEV)
         exd = ex.to(DEV)
-        op = second_order(lambda a, b: torch.ops.pme.pme_direct_twice(a, b, nb, dl, ds, exd, ALPHA, COULOMB), x, c, g, vd, wd)
-        figures = compare(f"direct triclinic={triclinic} list={kind}", op, ref, terms)
+        op = f64.second_order(lambda a, b: torch.ops.pme.pme_direct_twice(a, b, nb, dl, ds, exd, ALPHA, COULOMB), x, c, g, vd, wd)
+        figures = f64.compare(f"direct triclinic={triclinic} list={kind}", op, ref, terms)
         assert all(f <= bar for f, bar in zip(figures, BAR_DIRECT)), figures
         results[kind] = op
         # the CPU key on the same list
-        xc, cc, gc = leaves(pos, q, torch.float32, "cpu")
-        host = second_order(lambda a, b: torch.ops.pme.pme_direct_twice(a, b, nb.cpu(), dl.cpu(), ds.cpu(), ex, ALPHA, COULOMB), xc, cc, gc,
+        xc, cc, gc = f64.leaves(pos, q, torch.float32, "cpu")
+        host = f64.second_order(lambda a, b: torch.ops.pme.pme_direct_twice(a, b, nb.cpu(), dl.cpu(), ds.cpu(), ex, ALPHA, COULOMB), xc, cc, gc,
                             v.float(), w.float())
         for k, name in ((3, "dL/dx"), (4, "dL/dq"), (5, "dL/dg")):
-            f = rel(op[k], host[k])
+            f = f64.rel(op[k], host[k])
             print(f"  device against the CPU key, {name}: {f:.2e}")
             assert f <= BAR_DIRECT[k - 3] + CPU_DIRECT[k - 3]
     # the kinds of list hold the same pairs: the same result to rounding (each within its bar of the restatement: twice the bar)
     for kind in ("plain", "shuffled"):
         for k in (3, 4, 5):
-            assert rel(results[kind][k], results["indexed"][k]) <= 2 * BAR_DIRECT[k - 3]
+            assert f64.rel(results[kind][k], results["indexed"][k]) <= 2 * BAR_DIRECT[k - 3]
 
 
 RECIPROCAL_CASES = [(False, 4, (20, 22, 18)), (True, 5, (24, 25, 21)), (True, 4, (9, 10, 11)), (False, 5, (12, 3, 14)),
@@ -241,24 +99,24 @@ RECIPROCAL_CASES = [(False, 4, (20, 22, 18)), (True, 5, (24, 25, 21)), (True, 4,
 
 @pytest.mark.parametrize("triclinic,order,grid", RECIPROCAL_CASES)
 def test_reciprocal_double_backward_matches_the_float64_restatement_and_the_cpu_key(triclinic, order, grid):
-    pos, q, box = system(triclinic)
+    pos, q, box = f64.system(triclinic)
     mods = [bspline_moduli(k, order) for k in grid]
-    v, w = cotangents(len(q), 12)
-    x, c, g = leaves(pos, q, torch.float64, "cpu")
+    v, w = f64.cotangents(len(q), 12)
+    x, c, g = f64.leaves(pos, q, torch.float64, "cpu")
     b64 = torch.tensor(box, dtype=torch.float64)
-    ref = second_order(lambda a, b: spme_energy(a, b, b64, grid, order, ALPHA, COULOMB, mods), x, c, g, v, w)
-    x, c, g = leaves(pos, q, torch.float32, DEV)
+    ref = f64.second_order(lambda a, b: f64.spme_energy(a, b, b64, grid, order, ALPHA, COULOMB, mods), x, c, g, v, w)
+    x, c, g = f64.leaves(pos, q, torch.float32, DEV)
     tb = torch.tensor(box, device=DEV)
     dm = [m.to(DEV) for m in mods]
-    op = second_order(lambda a, b: torch.ops.pme.pme_reciprocal_twice(a, b, tb, *grid, order, ALPHA, COULOMB, *dm), x, c, g,
+    op = f64.second_order(lambda a, b: torch.ops.pme.pme_reciprocal_twice(a, b, tb, *grid, order, ALPHA, COULOMB, *dm), x, c, g,
                       v.float().to(DEV), w.float().to(DEV))
-    figures = compare(f"reciprocal triclinic={triclinic} order={order} grid={grid}", op, ref)
+    figures = f64.compare(f"reciprocal triclinic={triclinic} order={order} grid={grid}", op, ref)
     assert all(f <= bar for f, bar in zip(figures, BAR_RECIPROCAL)), figures
-    xc, cc, gc = leaves(pos, q, torch.float32, "cpu")
-    host = second_order(lambda a, b: torch.ops.pme.pme_reciprocal_twice(a, b, torch.tensor(box), *grid, order, ALPHA, COULOMB, *mods), xc, cc, gc,
+    xc, cc, gc = f64.leaves(pos, q, torch.float32, "cpu")
+    host = f64.second_order(lambda a, b: torch.ops.pme.pme_reciprocal_twice(a, b, torch.tensor(box), *grid, order, ALPHA, COULOMB, *mods), xc, cc, gc,
                         v.float(), w.float())
     for k, name in ((3, "dL/dx"), (4, "dL/dq"), (5, "dL/dg")):
-        f = rel(op[k], host[k])
+        f = f64.rel(op[k], host[k])
         print(f"  device against the CPU key, {name}: {f:.2e}")
         assert f <= BAR_RECIPROCAL[k - 3] + CPU_RECIPROCAL[k - 3]
 
@@ -272,10 +130,10 @@ def force_matching_step(pme, x, c, tb, f_ref, max_num_pairs=-1):
 
 
 def force_matching_setup():
-    pos, q, box = system(True, n=48, seed=7)
+    pos, q, box = f64.system(True, n=48, seed=7)
     n = len(q)
     grid, order = (20, 21, 22), 5
-    pme = PME(*grid, order, ALPHA, COULOMB, exclusion_table(n), reciprocal=True, twice_differentiable=True)
+    pme = PME(*grid, order, ALPHA, COULOMB, f64.exclusion_table(n), reciprocal=True, twice_differentiable=True)
     f_ref = 50.0 * torch.randn(n, 3, generator=torch.Generator().manual_seed(3), dtype=torch.float64)
     return pos, q, box, pme, grid, order, f_ref
 
@@ -283,11 +141,11 @@ def force_matching_setup():
 def force_matching_reference(pos, q, box, pme, grid, order, f_ref):
     tb = torch.tensor(box, device=DEV)
     nb, dl, _, _ = getNeighborPairs(torch.tensor(pos, device=DEV), CUTOFF, -1, tb)
-    pairs = listed_pairs(nb, dl, torch.tensor(pos), pme.exclusions)
+    pairs = f64.listed_pairs_frozen(nb, dl, torch.tensor(pos), pme.exclusions)
     b64 = torch.tensor(box, dtype=torch.float64)
     x = torch.tensor(pos, dtype=torch.float64, requires_grad=True)
     c = torch.tensor(q, dtype=torch.float64, requires_grad=True)
-    e = (direct_energy(x, c, pairs, ALPHA, COULOMB) + spme_energy(x, c, b64, grid, order, ALPHA, COULOMB, pme.moduli)
+    e = (f64.direct_energy_frozen(x, c, pairs, ALPHA, COULOMB) + f64.spme_energy(x, c, b64, grid, order, ALPHA, COULOMB, pme.moduli)
          - torch.sum(c ** 2) * (COULOMB * ALPHA / math.sqrt(math.pi)))
     (dx,) = torch.autograd.grad(e, x, create_graph=True)
     loss = ((-dx - f_ref) ** 2).sum()
@@ -303,17 +161,17 @@ def test_force_matching_gradient_through_the_class():
         c = torch.tensor(q, device=DEV, requires_grad=True)
         loss = force_matching_step(pme, x, c, torch.tensor(box, device=DEV), f_ref.float().to(DEV), max_num_pairs)
         assert abs(float(loss) - ref_loss) <= 1e-4 * ref_loss
-        fq, fx = rel(c.grad, ref_q), rel(x.grad, ref_x)
+        fq, fx = f64.rel(c.grad, ref_q), f64.rel(x.grad, ref_x)
         print(f"force matching, max_num_pairs={max_num_pairs}: dloss/dq {fq:.2e}  dloss/dx {fx:.2e}")
         assert fq <= BAR_MATCH[0] and fx <= BAR_MATCH[1]
 
 
 # ---- 8: bit for bit ----------------------------------------------------------------------------------------------------------------
 def test_double_backward_is_repeatable_and_first_order_bits_are_the_existing_ops():
-    pos, q, box = system(True, n=200, seed=8)
+    pos, q, box = f64.system(True, n=200, seed=8)
     n = len(q)
-    ex = PME(8, 8, 8, 4, ALPHA, COULOMB, exclusion_table(n)).exclusions.to(DEV)
-    v, w = cotangents(n, 13)
+    ex = PME(8, 8, 8, 4, ALPHA, COULOMB, f64.exclusion_table(n)).exclusions.to(DEV)
+    v, w = f64.cotangents(n, 13)
     vd, wd = v.float().to(DEV), w.float().to(DEV)
     tb = torch.tensor(box, device=DEV)
     grid, order = (30, 32, 28), 5
@@ -322,14 +180,14 @@ def test_double_backward_is_repeatable_and_first_order_bits_are_the_existing_ops
         nb, dl, ds = device_list(pos, box, indexed)
         runs = []
         for _ in range(2):
-            x, c, g = leaves(pos, q, torch.float32, DEV)
-            runs.append(second_order(lambda a, b: torch.ops.pme.pme_direct_twice(a, b, nb, dl, ds, ex, ALPHA, COULOMB), x, c, g, vd, wd))
+            x, c, g = f64.leaves(pos, q, torch.float32, DEV)
+            runs.append(f64.second_order(lambda a, b: torch.ops.pme.pme_direct_twice(a, b, nb, dl, ds, ex, ALPHA, COULOMB), x, c, g, vd, wd))
         for a, b in zip(*runs):
             assert torch.equal(a, b)
         # forward and first order: the existing op's bits (with the index both take the indexed kernels, without it neither)
         out = []
         for op in (torch.ops.pme.pme_direct, torch.ops.pme.pme_direct_twice):
-            x, c, _ = leaves(pos, q, torch.float32, DEV)
+            x, c, _ = f64.leaves(pos, q, torch.float32, DEV)
             e = op(x, c, nb, dl, ds, ex, ALPHA, COULOMB)
             (1.3 * e).backward()
             out.append((e.detach(), x.grad, c.grad))
@@ -337,13 +195,13 @@ def test_double_backward_is_repeatable_and_first_order_bits_are_the_existing_ops
             assert torch.equal(a, b)
     runs = []
     for _ in range(2):
-        x, c, g = leaves(pos, q, torch.float32, DEV)
-        runs.append(second_order(lambda a, b: torch.ops.pme.pme_reciprocal_twice(a, b, tb, *grid, order, ALPHA, COULOMB, *dm), x, c, g, vd, wd))
+        x, c, g = f64.leaves(pos, q, torch.float32, DEV)
+        runs.append(f64.second_order(lambda a, b: torch.ops.pme.pme_reciprocal_twice(a, b, tb, *grid, order, ALPHA, COULOMB, *dm), x, c, g, vd, wd))
     for a, b in zip(*runs):
         assert torch.equal(a, b)
     out = []
     for op in (torch.ops.pme.pme_reciprocal, torch.ops.pme.pme_reciprocal_twice):
-        x, c, _ = leaves(pos, q, torch.float32, DEV)
+        x, c, _ = f64.leaves(pos, q, torch.float32, DEV)
         e = op(x, c, tb, *grid, order, ALPHA, COULOMB, *dm)
         (1.3 * e).backward()
         out.append((e.detach(), x.grad, c.grad))
@@ -354,18 +212,18 @@ def test_double_backward_is_repeatable_and_first_order_bits_are_the_existing_ops
 def test_saved_index_survives_a_later_pair_list():
     """the forward pass keeps the index it used: another differentiable getNeighborPairs call replaces the cache before the double
     backward runs"""
-    pos, q, box = system(True, n=200, seed=8)
+    pos, q, box = f64.system(True, n=200, seed=8)
     ex = torch.zeros(len(q), 0, dtype=torch.int32, device=DEV)
-    v, w = cotangents(len(q), 13)
+    v, w = f64.cotangents(len(q), 13)
     vd, wd = v.float().to(DEV), w.float().to(DEV)
     nb, dl, ds = device_list(pos, box, True)
     out = []
     for disturb in (False, True):
-        x, c, _ = leaves(pos, q, torch.float32, DEV)
+        x, c, _ = f64.leaves(pos, q, torch.float32, DEV)
         e = torch.ops.pme.pme_direct_twice(x, c, nb, dl, ds, ex, ALPHA, COULOMB)
         P, C = torch.autograd.grad(e, (x, c), create_graph=True)
         if disturb:
-            other, _, _ = system(False, n=77, seed=1)
+            other, _, _ = f64.system(False, n=77, seed=1)
             getNeighborPairs(torch.tensor(other, device=DEV, requires_grad=True), CUTOFF, 3000, torch.tensor(np.diag([2.4, 2.64, 2.16]).astype(np.float32), device=DEV))
         out.append(torch.autograd.grad((vd * P).sum() + (wd * C).sum(), (x, c)))
     for a, b in zip(*out):
@@ -374,10 +232,10 @@ def test_saved_index_survives_a_later_pair_list():
 
 # ---- 10: the C entries alone ---------------------------------------------------------------------------------------------------------
 def test_c_entries_against_float64():
-    pos, q, box = system(True)
+    pos, q, box = f64.system(True)
     n = len(q)
-    ex = PME(8, 8, 8, 4, ALPHA, COULOMB, exclusion_table(n)).exclusions
-    v, w = cotangents(n, 14)
+    ex = PME(8, 8, 8, 4, ALPHA, COULOMB, f64.exclusion_table(n)).exclusions
+    v, w = f64.cotangents(n, 14)
     tp, tq = torch.tensor(pos, device=DEV), torch.tensor(q, device=DEV)
     vd, wd = v.float().to(DEV), w.float().to(DEV)
     for indexed in (True, False):
@@ -385,16 +243,16 @@ def test_c_entries_against_float64():
         index = capi.neighbor_pairs_build_index(n, nb) if indexed else None
         gx, gq = capi.pme_direct_double_backward(tp, tq, nb, dl, ds, ex, vd, wd, ALPHA, COULOMB, index=index)
         ref, _ = direct_reference(pos, q, nb, dl, ex, v, w)        # (g = 0.7 multiplies the reference's outputs)
-        fx, fq = rel(gx * 0.7, ref[3]), rel(gq * 0.7, ref[4])
+        fx, fq = f64.rel(gx * 0.7, ref[3]), f64.rel(gq * 0.7, ref[4])
         print(f"C entry direct, index given={indexed}: dL/dx {fx:.2e}  dL/dq {fq:.2e}")
         assert fx <= BAR_C_DIRECT[0] and fq <= BAR_C_DIRECT[1]
     for order, grid in ((4, (20, 22, 18)), (5, (24, 25, 21))):
         mods = [bspline_moduli(k, order) for k in grid]
         gx, gq = capi.pme_reciprocal_double_backward(tp, tq, torch.tensor(box, device=DEV), *grid, order, ALPHA, COULOMB, *mods, vd, wd)
-        x, c, g = leaves(pos, q, torch.float64, "cpu")
+        x, c, g = f64.leaves(pos, q, torch.float64, "cpu")
         b64 = torch.tensor(box, dtype=torch.float64)
-        ref = second_order(lambda a, b: spme_energy(a, b, b64, grid, order, ALPHA, COULOMB, mods), x, c, g, v, w)
-        fx, fq = rel(gx * 0.7, ref[3]), rel(gq * 0.7, ref[4])
+        ref = f64.second_order(lambda a, b: f64.spme_energy(a, b, b64, grid, order, ALPHA, COULOMB, mods), x, c, g, v, w)
+        fx, fq = f64.rel(gx * 0.7, ref[3]), f64.rel(gq * 0.7, ref[4])
         print(f"C entry reciprocal order={order}: dL/dx {fx:.2e}  dL/dq {fq:.2e}")
         assert fx <= BAR_C_RECIPROCAL[0] and fq <= BAR_C_RECIPROCAL[1]
 
