@@ -1,8 +1,5 @@
-"""The batched energy step of OptimizedTorchANI: what exists without a GPU, and the float64 judge of the segmented mean (CPU only).
-
-`segment_means` restates nnpops_mlp_energy_mean_segments in numpy float64: the per-atom, per-member energies lie in the species-grouped
-order the networks write them in, `places[row]` is the place of a row in that order (the inverse of the frame's rows) and molecule b is
-the rows offsets[b] .. offsets[b + 1] - 1.  tests/test_ani_batch_energy_gpu.py loads it from this file.
+"""The batched energy step of OptimizedTorchANI: what exists without a GPU, and what pins the float64 judge of the segmented mean,
+`segment_means` of tests/ani_float64.py (CPU only).
 
 What pins it: a direct per-molecule sum over a random grouping with unequal molecule sizes (one empty, one larger than 64 atoms).  Both
 sides are float64 sums of the same numbers in different orders: bar 1e-13 of the sum of the absolute values.
@@ -12,26 +9,7 @@ import ctypes
 import numpy as np
 import torch
 
-
-def segment_means(energies, places, offsets, scale):
-    """energies [grouped atoms][members], places [rows], offsets [B + 1] -> float64 [B]: scale * sum over the molecule's atoms and members"""
-    e = np.asarray(energies, dtype=np.float64)
-    places, offsets = np.asarray(places, dtype=np.int64), np.asarray(offsets, dtype=np.int64)
-    return np.array([scale * e[places[offsets[b]:offsets[b + 1]]].sum() for b in range(len(offsets) - 1)], dtype=np.float64)
-
-
-def random_grouping(sizes, kinds, members, seed):
-    """A batch of molecules of the given sizes whose atoms carry random kinds: -> (energies in grouped order [n][members] float32,
-    rows [n] (grouped order -> row), places [n] (row -> grouped order), offsets [B + 1], kind of every row)"""
-    rng = np.random.default_rng(seed)
-    n = int(sum(sizes))
-    kind = rng.integers(0, kinds, n)
-    rows = np.argsort(kind, kind="stable").astype(np.int32)
-    places = np.empty(n, dtype=np.int32)
-    places[rows] = np.arange(n, dtype=np.int32)
-    offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
-    energies = (rng.standard_normal((n, members)) * 10.0 ** rng.uniform(-2, 1, (n, 1))).astype(np.float32)
-    return energies, rows, places, offsets, kind
+from ani_float64 import random_grouping, segment_means
 
 
 def test_judge_is_the_per_molecule_sum():

@@ -14,14 +14,13 @@ not.  The same 23 positions with 12 H, 7 C and 4 O ("HCO": 3 * 16 + 6 * 32 = 240
 the launch that adds the members up; every check that depends on the path runs on both molecules.
 """
 import functools
-import importlib.util
 import io
-import os
 
 import numpy as np
 import pytest
 import torch
 
+from ani_float64 import random_grouping, segment_means
 from nnpops_amd import workloads
 from oracle import AniOracle
 
@@ -30,12 +29,6 @@ DEV = torch.device("cuda:0")
 SAE = [-0.5, -38.0, -54.7, -75.2, -398.1, -99.8, -460.1]
 SLOTS = [60, 3, 17, 41, 66]
 ENERGY_RTOL, ENERGY_ATOL, FORCE_RTOL = 5e-6, 1e-4, 1e-4
-
-_spec = importlib.util.spec_from_file_location("ani_batch_energy_cpu", os.path.join(os.path.dirname(os.path.abspath(__file__)),
-                                                                                  "test_ani_batch_energy_cpu.py"))
-_cpu = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(_cpu)
-segment_means, random_grouping = _cpu.segment_means, _cpu.random_grouping
 
 
 def _numbers(species):

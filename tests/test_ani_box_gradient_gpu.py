@@ -1,86 +1,54 @@
 """Box-vector gradient (virial) of the ANI symmetry functions: nnpops_ani_backprop_box_strided and the torch surface above it.
 
-The judge is the float64 restatement of tests/test_ani_box_gradient_reference_cpu.py (pinned there to oracle.AniOracle64 and to
-finite differences of it): L = <w_r, radial> + <w_a, angular> with seeded float32 weights, dL/dB with the minimum-image shifts held
-fixed, all nine entries.  One float64 evaluation per (system, angle mode), kept for the module.
+The judge is the float64 restatement of tests/ani_float64.py (pinned by tests/test_ani_box_gradient_reference_cpu.py to
+oracle.AniOracle64 and to finite differences of it): L = <w_r, radial> + <w_a, angular> with seeded float32 weights, dL/dB with the
+minimum-image shifts held fixed, all nine entries.  One float64 evaluation per (system, angle mode), kept for the module.
 
 Bar (the project's force tolerance, FORCE_RTOL of test_ani_dispatch_gpu.py): max |gB - gB_ref| <= 1e-4 max |gB_ref|.
 Properties, same bar: the stress is symmetric -- the antisymmetric part of W = sum_i x_i (x) dL/dx_i + B^T dL/dB (rotation
 invariance of the AEV) stays below 1e-4 of the largest entry of W; two calls give equal bits; the position gradient is the plain
 backprop()'s, bit for bit.  Every evaluation prints its measured figures (pytest -s).
 """
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 import torch
 
+from ani_float64 import Restatement, system
+from box_gradient_judge import clean_env, judge
 from nnpops_amd import workloads
 
 pytestmark = pytest.mark.gpu
 
 FORCE_RTOL = 1e-4
 DEV = torch.device("cuda:0")
-CFG = (7, 5.1, 3.5)
 
-_spec = importlib.util.spec_from_file_location("ani_box_reference", os.path.join(os.path.dirname(os.path.abspath(__file__)),
-                                                                               "test_ani_box_gradient_reference_cpu.py"))
-_reference_module = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(_reference_module)
-Restatement = _reference_module.Restatement
-
-_SYSTEMS, _REFERENCES = {}, {}
-
-
-def _system(tag):
-    """-> (species, pos, box): the frames of test_ani_dispatch_gpu.py, and the 600-atom one moved"""
-    if tag not in _SYSTEMS:
-        if tag == "triclinic200":
-            pos, species, box = workloads.triclinic_box(200)
-        elif tag == "liquid600":                  # all-pairs build
-            pos, species, box = workloads.random_box(600, seed=81)
-        elif tag == "dense900":                   # 64-slot records, two waves per atom, leg forces in the receivers' rows
-            pos, species, box = workloads.random_box(900, density=0.2, seed=33)
-        elif tag == "liquid2100":                 # cell-grid build
-            pos, species, box = workloads.random_box(2100, seed=83)
-        elif tag == "liquid600_shifted":          # every atom 0.37 box lengths along x: a third of them outside the box
-            species, pos, box = _system("liquid600")
-            pos = (pos + np.array([0.37 * float(box[0, 0]), 0, 0], dtype=np.float32)).astype(np.float32)
-            assert 0.25 < float((pos[:, 0] > box[0, 0]).mean()) < 0.45
-        elif tag == "liquid600_wrapped":          # ... and those brought back by one box vector: other shifts, another dL/dB
-            species, pos, box = _system("liquid600_shifted")
-            pos = (pos - (pos[:, :1] > box[0, 0]) * box[0]).astype(np.float32)
-        else:
-            raise KeyError(tag)
-        _SYSTEMS[tag] = (species, pos, box)
-    return _SYSTEMS[tag]
+_REFERENCES = {}
 
 
 def _reference(tag, torchani):
     """float64: dict(g, gbox, wr, wa), once per (system, angle mode)"""
     key = (tag, torchani)
     if key not in _REFERENCES:
-        species, pos, box = _system(tag)
+        n_species, rcr, rca, species, pos, box = system(tag)
         rf, af = workloads.ani2x_functions()
         base = tag.split("_")[0]                  # (the moved frames take the weights of the frame they come from)
         rng = np.random.default_rng([len(species), int(torchani), sum(map(ord, base))])
         wr = rng.standard_normal((len(species), 7 * 16)).astype(np.float32)
         wa = rng.standard_normal((len(species), 28 * 32)).astype(np.float32)
-        out = Restatement(*CFG, species, rf, af, torchani).evaluate(pos, box, wr, wa)
+        out = Restatement(n_species, rcr, rca, species, rf, af, torchani).evaluate(pos, box, wr, wa)
         _REFERENCES[key] = dict(g=out["g"], gbox=out["gbox"], wr=wr, wa=wa)
     return _REFERENCES[key]
 
 
 def _handle(tag, torchani):
     from nnpops_amd.capi import AniSymmetryFunctions
-    species, pos, box = _system(tag)
-    return AniSymmetryFunctions(*CFG, species, *workloads.ani2x_functions(), periodic=True, torchani=torchani)
+    n_species, rcr, rca, species, _, _ = system(tag)
+    return AniSymmetryFunctions(n_species, rcr, rca, species, *workloads.ani2x_functions(), periodic=True, torchani=torchani)
 
 
 def _evaluate(sym, tag, ref):
     """compute(), the plain backprop(), two backprop_box() -> (position gradient, cell gradient) as float64 numpy arrays"""
-    species, pos, box = _system(tag)
+    _, _, _, _, pos, box = system(tag)
     tpos, tbox = torch.tensor(pos, device=DEV), torch.tensor(box, device=DEV)
     t_wr, t_wa = torch.tensor(ref["wr"], device=DEV), torch.tensor(ref["wa"], device=DEV)
     sym.compute(tpos, tbox)
@@ -95,24 +63,12 @@ def _evaluate(sym, tag, ref):
 
 
 def _judge(label, tag, ref, g, gbox):
-    species, pos, box = _system(tag)
-    top = float(np.abs(ref["gbox"]).max())
-    err = float(np.abs(gbox - ref["gbox"]).max())
-    x, B = pos.astype(np.float64), box.astype(np.float64)
-    W = x.T @ g + B.T @ gbox
-    W_ref = x.T @ ref["g"] + B.T @ ref["gbox"]
-    anti, anti_ref = float(np.abs(W - W.T).max()) / 2, float(np.abs(W_ref - W_ref.T).max()) / 2
-    wtop = float(np.abs(W_ref).max())
-    print(f"\n[ani-box] {label}: cell gradient {err / top:.2e} of max {top:.3e}; antisymmetric stress {anti / wtop:.2e} of max {wtop:.3e} "
-          f"(float64: {anti_ref / wtop:.1e}); force {np.abs(g - ref['g']).max() / np.abs(ref['g']).max():.2e}")
-    assert np.isfinite(gbox).all() and top > 0
-    assert err <= FORCE_RTOL * top, (label, err, top)
-    assert anti <= FORCE_RTOL * wtop, (label, anti, wtop)
+    _, _, _, _, pos, box = system(tag)
+    judge("ani-box", label, pos, box, ref, g, gbox, FORCE_RTOL, what="cell gradient")
 
 
 def _clean_env(monkeypatch):
-    for k in [k for k in os.environ if k.startswith("NNPOPS_ANI_")]:
-        monkeypatch.delenv(k)
+    clean_env(monkeypatch, "NNPOPS_ANI_")
 
 
 # ---------------------------------------------------------------------------------------------- the systems
@@ -206,7 +162,7 @@ def test_cell_gradient_with_the_coarse_cell_grid(monkeypatch):
 def test_refused_without_a_box_or_with_molecules():
     from nnpops_amd.capi import AniSymmetryFunctions, NNPOpsHipError
     pos, species = workloads.conformer(40, seed=3)
-    sym = AniSymmetryFunctions(*CFG, species, *workloads.ani2x_functions(), periodic=False)
+    sym = AniSymmetryFunctions(7, 5.1, 3.5, species, *workloads.ani2x_functions(), periodic=False)
     tpos = torch.tensor(pos, device=DEV)
     radial, angular = sym.compute(tpos, None)
     with pytest.raises(NNPOpsHipError, match="periodic"):
@@ -237,7 +193,7 @@ def test_torch_cell_gradient_is_the_c_abi_result(monkeypatch, surface):
     a cell that does not require a gradient still gets None."""
     _clean_env(monkeypatch)
     tag = "liquid600"
-    species, pos, box = _system(tag)
+    _, _, _, species, pos, box = system(tag)
     ref = _reference(tag, True)
     module = _aev_module(species)
     w = torch.tensor(np.concatenate([ref["wr"], ref["wa"]], axis=1), device=DEV)
@@ -270,7 +226,7 @@ def test_torch_cell_gradient_is_the_c_abi_result(monkeypatch, surface):
 
 def test_torch_cell_gradient_refuses_second_derivatives(monkeypatch):
     _clean_env(monkeypatch)
-    species, pos, box = _system("triclinic200")
+    _, _, _, species, pos, box = system("triclinic200")
     module = _aev_module(species)
     tpos = torch.tensor(pos, device=DEV).requires_grad_(True)
     cell = torch.tensor(box, device=DEV).requires_grad_(True)

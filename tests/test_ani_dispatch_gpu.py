@@ -30,6 +30,7 @@ import numpy as np
 import pytest
 import torch
 
+from ani_float64 import system as _system      # (tests here take a parameter named system)
 from nnpops_amd import workloads
 from oracle import AniOracle64
 
@@ -40,40 +41,12 @@ FORCE_RTOL = 1e-4      # of the largest force component of the system
 AEV_ATOL, AEV_RTOL = 2e-6, 2e-5
 
 _REFERENCES = {}       # key -> dict(r, a, g, wr, wa): one float64 evaluation per (system, function set, torchani)
-_SYSTEMS = {}          # tag -> (n_species, rcr, rca, species, pos, box)
 _DEFAULT_RUNS = {}     # section e: system tag -> (r, a, g) of the handle without any switch
 
 
 # ---------------------------------------------------------------------------------------------- inputs
-def _system(tag):
-    if tag not in _SYSTEMS:
-        box = None
-        if tag == "liquid600":                 # a: 7-species periodic liquid, ~18 angular neighbours
-            pos, species, box = workloads.random_box(600, seed=81)
-            cfg = (7, 5.1, 3.5)
-        elif tag == "conformer60":             # a: a compact molecule in vacuum
-            pos, species = workloads.conformer(60, seed=82)
-            cfg = (7, 5.1, 3.5)
-        elif tag == "slots128":                # b
-            pos, species, box = workloads.random_box(400, density=0.2, seed=7, min_dist=0.8, n_species=3)
-            cfg = (3, 5.2, 4.8)
-        elif tag in ("slots256", "slots256_loose"):      # c: the same lattice gas without its box; the loose frame is 1.15 x wider
-            pos, species, _ = workloads.random_box(260, density=0.5, seed=7, min_dist=0.5, n_species=2)
-            if tag == "slots256_loose":
-                pos = (pos * np.float32(1.15)).astype(np.float32)
-            cfg = (2, 5.2, 5.0)
-        elif tag == "dense900":                # d, e: the 64-slot dense liquid of test_ani_gpu.py
-            pos, species, box = workloads.random_box(900, density=0.2, seed=33)
-            cfg = (7, 5.1, 3.5)
-        elif tag == "liquid2100":              # e: large enough for NNPOPS_ANI_STREAMS to split (2 048 atoms or more)
-            pos, species, box = workloads.random_box(2100, seed=83)
-            cfg = (7, 5.1, 3.5)
-        else:
-            raise KeyError(tag)
-        _SYSTEMS[tag] = cfg + (species, pos, box)
-    return _SYSTEMS[tag]
-
-
+# The frames are ani_float64.system's: liquid600 and conformer60 (section a), slots128 (b), slots256 and slots256_loose (c), dense900
+# (d, e) and liquid2100 (e).
 def _neighbour_counts(pos, box, cutoff):
     """Neighbours of every atom inside `cutoff` (float64, minimum image in a cubic box)."""
     d = pos.astype(np.float64)[:, None, :] - pos.astype(np.float64)[None, :, :]

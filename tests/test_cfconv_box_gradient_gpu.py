@@ -1,8 +1,8 @@
 """Box-vector gradient (virial) of the periodic CFConv: nnpops_cfconv_backprop_box and the torch surface above it.
 
-The judge is the float64 restatement of tests/test_cfconv_box_gradient_reference_cpu.py (pinned there to the float32 oracle and to
-finite differences of itself): L = <gout, CFConv(x)> with seeded float32 weights and inputs, dL/dB with the minimum-image shifts
-held fixed, all nine entries.  One float64 evaluation per (system, layer), kept for the module.
+The judge is the float64 restatement of tests/cfconv_float64.py (pinned by tests/test_cfconv_box_gradient_reference_cpu.py to the
+float32 oracle and to finite differences of itself): L = <gout, CFConv(x)> with seeded float32 weights and inputs, dL/dB with the
+minimum-image shifts held fixed, all nine entries.  One float64 evaluation per (system, layer), kept for the module.
 
 Bar (the project's force tolerance, FORCE_RTOL of test_cfconv_gpu.py): max |gB - gB_ref| <= 1e-4 max |gB_ref|.
 Every evaluation also asserts: gB finite and non-trivial; the input and position gradients are the plain backprop()'s, bit for
@@ -26,13 +26,12 @@ Measured on an MI355X (worst box-gradient error per path, of the largest entry):
 planes 3.3e-6, fp32 matrix 1.5e-6, vector 1.4e-6, vector with streamed weights 2.9e-6, config-3 kernel 1.4e-5, NNPOPS_CFCONV_VALU=1
 1.6e-6, NNPOPS_CFCONV_SPLIT=0 1.9e-6; antisymmetric stress at most 2.2e-6 of its largest entry.
 """
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 import torch
 
+from box_gradient_judge import clean_env, judge
+from cfconv_float64 import Restatement, frame, handles, layer as _layer, sigma_of, weights      # (tests here call their module layer)
 from nnpops_amd import workloads
 
 pytestmark = pytest.mark.gpu
@@ -41,23 +40,7 @@ FORCE_RTOL = 1e-4
 DEV = torch.device("cuda:0")
 CUTOFF = 5.0
 
-_spec = importlib.util.spec_from_file_location("cfconv_box_reference", os.path.join(os.path.dirname(os.path.abspath(__file__)),
-                                                                                  "test_cfconv_box_gradient_reference_cpu.py"))
-_reference_module = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(_reference_module)
-Restatement, frame, weights = _reference_module.Restatement, _reference_module.frame, _reference_module.weights
-
 _REFERENCES = {}
-
-
-def _sigma(G):
-    return 0.1 if G >= 25 else 0.4
-
-
-def _layer(tag, W, G):
-    """-> (w1, b1, w2, b2, x, gout) of a layer on a frame: seeded by the shape (the moved frames take those of the frame they come from)"""
-    pos, _ = frame(tag)
-    return weights(W, G, len(pos), 1000 * W + G)
 
 
 def _reference(tag, W, G, act):
@@ -66,16 +49,8 @@ def _reference(tag, W, G, act):
     if key not in _REFERENCES:
         pos, box = frame(tag)
         w1, b1, w2, b2, x, gy = _layer(tag, W, G)
-        _REFERENCES[key] = Restatement(W, G, CUTOFF, _sigma(G), act, w1, b1, w2, b2).evaluate(pos, box, x, gy)
+        _REFERENCES[key] = Restatement(W, G, CUTOFF, sigma_of(G), act, w1, b1, w2, b2).evaluate(pos, box, x, gy)
     return _REFERENCES[key]
-
-
-def _handles(tag, W, G, act, periodic=True):
-    from nnpops_amd.capi import CFConv, CFConvNeighbors
-    pos, _ = frame(tag)
-    w1, b1, w2, b2, _, _ = _layer(tag, W, G)
-    return (CFConvNeighbors(len(pos), CUTOFF, periodic),
-            CFConv(len(pos), W, G, CUTOFF, _sigma(G), act, w1, b1, w2, b2, periodic=periodic))
 
 
 def _evaluate(nb, cf, tag, W, G, forward_first=True, pos=None):
@@ -101,26 +76,11 @@ def _evaluate(nb, cf, tag, W, G, forward_first=True, pos=None):
 
 
 def _judge(label, tag, ref, g, gbox, pos=None):
-    if pos is None:
-        pos = frame(tag)[0]
-    box = frame(tag)[1]
-    top = float(np.abs(ref["gbox"]).max())
-    err = float(np.abs(gbox - ref["gbox"]).max())
-    x, B = pos.astype(np.float64), box.astype(np.float64)
-    W = x.T @ g + B.T @ gbox
-    W_ref = x.T @ ref["g"] + B.T @ ref["gbox"]
-    anti, anti_ref = float(np.abs(W - W.T).max()) / 2, float(np.abs(W_ref - W_ref.T).max()) / 2
-    wtop = float(np.abs(W_ref).max())
-    print(f"\n[cfconv-box] {label}: box gradient {err / top:.2e} of max {top:.3e}; antisymmetric stress {anti / wtop:.2e} of max {wtop:.3e} "
-          f"(float64: {anti_ref / wtop:.1e}); force {np.abs(g - ref['g']).max() / np.abs(ref['g']).max():.2e}")
-    assert np.isfinite(gbox).all() and top > 0 and np.abs(gbox).max() > 0
-    assert err <= FORCE_RTOL * top, (label, err, top)
-    assert anti <= FORCE_RTOL * wtop, (label, anti, wtop)
+    judge("cfconv-box", label, frame(tag)[0] if pos is None else pos, frame(tag)[1], ref, g, gbox, FORCE_RTOL)
 
 
 def _clean_env(monkeypatch):
-    for k in [k for k in os.environ if k.startswith("NNPOPS_CFCONV_")]:
-        monkeypatch.delenv(k)
+    clean_env(monkeypatch, "NNPOPS_CFCONV_")
 
 
 # ---------------------------------------------------------------------------------------------- every kernel path
@@ -141,7 +101,7 @@ def test_box_gradient_against_float64(monkeypatch, path, tag):
     _clean_env(monkeypatch)
     W, G, act, _ = PATHS[path]
     ref = _reference(tag, W, G, act)
-    nb, cf = _handles(tag, W, G, act)
+    nb, cf = handles(tag, W, G, act, CUTOFF)
     g, gbox = _evaluate(nb, cf, tag, W, G)
     if tag in ("liquid1500", "dense1100"):
         assert nb.read_grid()["ok"], nb.read_grid()            # the cell grid built these rows
@@ -163,7 +123,7 @@ def test_box_gradient_on_the_forced_paths(monkeypatch, switch, value, tag):
     monkeypatch.setenv("NNPOPS_CFCONV_" + switch, value)
     W, G, act = 32, 16, "ssp"
     ref = _reference(tag, W, G, act)
-    nb, cf = _handles(tag, W, G, act)
+    nb, cf = handles(tag, W, G, act, CUTOFF)
     g, gbox = _evaluate(nb, cf, tag, W, G)
     _judge(f"{switch}={value} W={W} G={G} {act} {tag}", tag, ref, g, gbox)
 
@@ -212,7 +172,7 @@ def test_without_a_preceding_forward_call(monkeypatch, path):
     W, G, act, _ = PATHS[path]
     tag = "liquid1500"
     ref = _reference(tag, W, G, act)
-    nb, cf = _handles(tag, W, G, act)
+    nb, cf = handles(tag, W, G, act, CUTOFF)
     g, gbox = _evaluate(nb, cf, tag, W, G, forward_first=False)
     _judge(f"{path} {tag} no forward call", tag, ref, g, gbox)
 
@@ -225,14 +185,14 @@ def test_follows_a_rebuild(monkeypatch, path):
     tag = "liquid1500"
     pos, box = frame(tag)
     moved = (pos + np.random.default_rng(3).normal(0, 0.3, pos.shape)).astype(np.float32)
-    nb, cf = _handles(tag, W, G, act)
+    nb, cf = handles(tag, W, G, act, CUTOFF)
     g0, b0 = _evaluate(nb, cf, tag, W, G)
     g1, b1 = _evaluate(nb, cf, tag, W, G, pos=moved)
-    g2, b2 = _evaluate(*_handles(tag, W, G, act), tag, W, G, pos=moved)
+    g2, b2 = _evaluate(*handles(tag, W, G, act, CUTOFF), tag, W, G, pos=moved)
     assert np.array_equal(b1, b2) and np.array_equal(g1, g2)
     assert np.abs(b1 - b0).max() > 100 * FORCE_RTOL * np.abs(b0).max()
     w1, b1_, w2, b2_, x, gy = _layer(tag, W, G)
-    ref = Restatement(W, G, CUTOFF, _sigma(G), act, w1, b1_, w2, b2_).evaluate(moved, box, x, gy)
+    ref = Restatement(W, G, CUTOFF, sigma_of(G), act, w1, b1_, w2, b2_).evaluate(moved, box, x, gy)
     _judge(f"{path} {tag} rebuilt on moved positions", tag, ref, g1, b1, pos=moved)
 
 
@@ -243,11 +203,11 @@ def test_refused_without_a_periodic_list_or_a_box():
     pos, box = frame(tag)
     _, _, _, _, x, gy = _layer(tag, W, G)
     tpos, tbox, tx, tg = (torch.tensor(a, device=DEV) for a in (pos, box, x, gy))
-    nb, cf = _handles(tag, W, G, act, periodic=False)
+    nb, cf = handles(tag, W, G, act, CUTOFF, periodic=False)
     nb.build(tpos)
     with pytest.raises(NNPOpsHipError, match="periodic"):
         cf.backprop_box(nb, tpos, tx, tg, tbox)
-    nb, cf = _handles(tag, W, G, act)
+    nb, cf = handles(tag, W, G, act, CUTOFF)
     nb.build(tpos, tbox)
     with pytest.raises(NNPOpsHipError, match="NULL"):
         cf.backprop_box(nb, tpos, tx, tg, None)
@@ -268,7 +228,7 @@ def _torch_layer(tag, W, G, act):
             super().__init__()
             self.neighbors = CFConvNeighbors(CUTOFF)
             # the module takes weights1 as [G, W], a reinterpretation of the core's [W][G] buffer (CFConv.py, torch_binding.cpp)
-            self.conv = CFConv(_sigma(G), act, torch.tensor(w1).reshape(G, W), torch.tensor(b1), torch.tensor(w2), torch.tensor(b2))
+            self.conv = CFConv(sigma_of(G), act, torch.tensor(w1).reshape(G, W), torch.tensor(b1), torch.tensor(w2), torch.tensor(b2))
 
         def forward(self, positions: torch.Tensor, x: torch.Tensor, build_box: Optional[torch.Tensor], box: Optional[torch.Tensor]) -> torch.Tensor:
             self.neighbors.build(positions, build_box)
@@ -308,7 +268,7 @@ def test_torch_box_gradient_is_the_c_abi_result(monkeypatch, path):
         assert torch.equal(o, out0) and torch.equal(p, gp0) and torch.equal(xg, gx0)
     assert torch.equal(gb3, gb2)
     ref = _reference(tag, W, G, act)
-    g_abi, b_abi = _evaluate(*_handles(tag, W, G, act), tag, W, G)
+    g_abi, b_abi = _evaluate(*handles(tag, W, G, act, CUTOFF), tag, W, G)
     assert np.array_equal(gb2.cpu().numpy().astype(np.float64), b_abi)
     assert np.array_equal(gp2.cpu().numpy().astype(np.float64), g_abi)
     _judge(f"torch {path} {tag}", tag, ref, g_abi, b_abi)

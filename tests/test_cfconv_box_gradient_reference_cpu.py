@@ -1,12 +1,6 @@
-"""The float64 restatement of the periodic CFConv that the box-gradient tests compare against, and what pins it (CPU only).
+"""What pins the float64 restatement of the periodic CFConv that the box-gradient tests compare against (CPU only).
 
-`Restatement` writes the continuous-filter convolution in torch float64 on float32 inputs (widened exactly): the half list {i < j}
-with every displacement as d_ij = x_j - x_i + n_ij B (B: rows = box vectors), the integer minimum-image shifts n computed ONCE
-from the inputs by the reference's rule (z, then y, then x, each by the diagonal entry), the Gaussian expansion, the two dense
-layers, the cosine cutoff and the symmetric accumulation.  With L = <gout, CFConv(x)> it returns the output, dL/dx, and -- from
-dL/dd_ij of every pair, which autograd gives -- dL/dpos (+dL/dd on j, -dL/dd on i) and the formal derivative with the shifts
-held fixed, dL/dB = sum_pairs n_ij (x) dL/dd_ij, all nine entries: what nnpops_cfconv_backprop_box returns.  It is an independent
-statement of the mathematics, not a wrapper of the oracle; tests/test_cfconv_box_gradient_gpu.py loads it from this file.
+The restatement itself is `Restatement` of tests/cfconv_float64.py; its head says what it computes.
 
 What pins it:
     output, dL/dx, dL/dpos   against the float32 CFConvOracle at the tolerances of tests/test_cfconv_gpu.py (the oracle is the float32
@@ -25,141 +19,15 @@ What it also measures (printed, pytest -s): the kernel's formula on float32 reco
     the 1e-4 bar of the GPU tests leaves room for the float32 filter arithmetic behind the pair scalars.
 """
 import ctypes
-import math
 
 import numpy as np
 import pytest
 import torch
 
-from nnpops_amd import workloads
+from cfconv_float64 import FORCE_RTOL, OUT_ATOL_FRAC, OUT_RTOL, Restatement, frame, recovered_shifts, weights
 from oracle import CFConvNeighborsOracle, CFConvOracle
 
-OUT_RTOL, OUT_ATOL_FRAC = 2e-5, 2e-6       # tests/test_cfconv_gpu.py
-FORCE_RTOL = 1e-4
 FD_RTOL = 1e-6
-
-
-class Restatement:
-    """CFConv in torch float64; w1 is the core-level [W][G] array, w2 is [out][in] (as nnpops_cfconv_create takes them)."""
-
-    def __init__(self, width, n_gauss, cutoff, sigma, activation, w1, b1, w2, b2):
-        self.W, self.G = int(width), int(n_gauss)
-        self.cutoff, self.sigma = float(np.float32(cutoff)), float(np.float32(sigma))
-        self.act = {"ssp": 0, "tanh": 1, 0: 0, 1: 1}[activation]
-        wide = lambda a, shape: torch.tensor(np.asarray(a, dtype=np.float32).astype(np.float64).reshape(shape))
-        self.w1, self.b1 = wide(w1, (self.W, self.G)), wide(b1, (self.W,))
-        self.w2, self.b2 = wide(w2, (self.W, self.W)), wide(b2, (self.W,))
-        self.mu = torch.arange(self.G, dtype=torch.float64) * self.cutoff / (self.G - 1)
-
-    def pairs(self, pos, box):
-        """-> (i, j, n) of the half list {i < j, r < cutoff}: d_ij = x_j - x_i + n_ij B, the reference's single-round minimum image
-        (z, then y, then x); row by row, so that a few thousand atoms need no N x N x 3 array"""
-        N = len(pos)
-        out_i, out_j, out_n = [], [], []
-        for i in range(N - 1):
-            d = pos[i + 1:] - pos[i]
-            s3 = np.round(d[:, 2] / box[2, 2]); d = d - s3[:, None] * box[2]
-            s2 = np.round(d[:, 1] / box[1, 1]); d = d - s2[:, None] * box[1]
-            s1 = np.round(d[:, 0] / box[0, 0]); d = d - s1[:, None] * box[0]
-            keep = np.nonzero(np.einsum("ij,ij->i", d, d) < self.cutoff ** 2)[0]
-            out_i.append(np.full(len(keep), i)); out_j.append(keep + i + 1)
-            out_n.append(-np.stack([s1[keep], s2[keep], s3[keep]], axis=1))
-        return np.concatenate(out_i), np.concatenate(out_j), np.concatenate(out_n).reshape(-1, 3)
-
-    def filters(self, d):
-        """-> y2 [P][W], the filter row of every pair, from its displacement [P][3]"""
-        r = d.norm(dim=1)
-        gamma = torch.exp(-0.5 * ((r[:, None] - self.mu[None, :]) / self.sigma) ** 2)
-        s1 = gamma @ self.w1.T + self.b1
-        y1 = torch.log(0.5 * torch.exp(s1) + 0.5) if self.act == 0 else torch.tanh(s1)
-        fc = 0.5 * torch.cos(math.pi * r / self.cutoff) + 0.5
-        return fc[:, None] * (y1 @ self.w2.T + self.b2)
-
-    def energy(self, pos64, box64, x, gout):
-        """-> (L, pairs) at float64 positions and box (the finite differences displace the box in float64)"""
-        pi, pj, pn = self.pairs(pos64, box64)
-        y2 = self.filters(torch.tensor(pos64[pj] - pos64[pi] + pn @ box64))
-        xin, g = torch.tensor(np.asarray(x, dtype=np.float64)), torch.tensor(np.asarray(gout, dtype=np.float64))
-        return float((y2 * (xin[pj] * g[pi] + xin[pi] * g[pj])).sum()), (pi, pj, pn)
-
-    def evaluate(self, positions, box, x, gout, chunk=16384):
-        """-> dict(out, L, gx = dL/dx, g = dL/dpositions, gbox = dL/dB with the shifts held fixed, and per pair: i, j, n, d, s with
-        dL/dd = s d)"""
-        pos = np.asarray(positions, dtype=np.float32).astype(np.float64)
-        B = np.asarray(box, dtype=np.float32).astype(np.float64).reshape(3, 3)
-        pi, pj, pn = self.pairs(pos, B)
-        d_all = pos[pj] - pos[pi] + pn @ B
-        xin = torch.tensor(np.asarray(x, dtype=np.float32).astype(np.float64), requires_grad=True)
-        g = torch.tensor(np.asarray(gout, dtype=np.float32).astype(np.float64))
-        out = torch.zeros_like(g)
-        gx = torch.zeros_like(g)
-        dLdd = np.zeros_like(d_all)
-        L = 0.0
-        for lo in range(0, len(pi), chunk):
-            i, j = torch.tensor(pi[lo:lo + chunk]), torch.tensor(pj[lo:lo + chunk])
-            d = torch.tensor(d_all[lo:lo + chunk], requires_grad=True)
-            y2 = self.filters(d)
-            to_i, to_j = y2 * xin[j], y2 * xin[i]
-            out.index_add_(0, i, to_i.detach()); out.index_add_(0, j, to_j.detach())
-            part = (to_i * g[i]).sum() + (to_j * g[j]).sum()
-            dx, dd = torch.autograd.grad(part, [xin, d])
-            gx += dx
-            dLdd[lo:lo + chunk] = dd.numpy()
-            L += float(part.detach())
-        gpos = np.zeros_like(pos)
-        np.add.at(gpos, pj, dLdd)
-        np.add.at(gpos, pi, -dLdd)
-        r2 = np.einsum("ij,ij->i", d_all, d_all)
-        return dict(out=out.numpy(), L=L, gx=gx.numpy(), g=gpos, gbox=pn.T @ dLdd, i=pi, j=pj, n=pn, d=d_all,
-                    s=np.einsum("ij,ij->i", dLdd, d_all) / r2)
-
-
-def recovered_shifts(pos32, box32, i, j, rec32):
-    """n of every pair as image_shift (box_grad.h) recovers it in float32 from the positions, the stored displacement and the box"""
-    f = np.float32
-    D = ((pos32[i] - pos32[j]).astype(f) + rec32).astype(f)
-    nz = np.round((D[:, 2] / box32[2, 2]).astype(f))
-    ny = np.round(((D[:, 1] - (nz * box32[2, 1]).astype(f)).astype(f) / box32[1, 1]).astype(f))
-    nx = np.round((((D[:, 0] - (nz * box32[2, 0]).astype(f)).astype(f) - (ny * box32[1, 0]).astype(f)).astype(f) / box32[0, 0]).astype(f))
-    return np.stack([nx, ny, nz], axis=1).astype(np.float64)
-
-
-def weights(W, G, n, seed):
-    """-> (w1 [W][G], b1, w2, b2, x [n][W], gout [n][W]) float32, scaled as tests/test_cfconv_gpu.py scales them"""
-    rng = np.random.default_rng(seed)
-    w1 = (0.3 * rng.standard_normal((W, G))).astype(np.float32)
-    w2 = (0.2 * rng.standard_normal((W, W))).astype(np.float32)
-    b1 = (0.3 * rng.standard_normal(W)).astype(np.float32)
-    b2 = (0.3 * rng.standard_normal(W)).astype(np.float32)
-    x = rng.standard_normal((n, W)).astype(np.float32)
-    gout = rng.standard_normal((n, W)).astype(np.float32)
-    return w1, b1, w2, b2, x, gout
-
-
-def frame(tag):
-    """-> (pos, box): the frames of the GPU tests"""
-    if tag == "triclinic350":                     # all-pairs build
-        pos, _, box = workloads.triclinic_box(350, seed=52)
-    elif tag == "liquid1500":                     # cell-grid build, cell-ordered walk
-        pos, _, box = workloads.random_box(1500, seed=31)
-    elif tag == "dense1100":                      # rows longer than a wave
-        pos, _, box = workloads.random_box(1100, density=0.2, seed=71)
-    elif tag == "liquid600":
-        pos, _, box = workloads.random_box(600, seed=81)
-    elif tag == "liquid600_shifted":              # every atom 0.37 box lengths along x: a third of them outside the box
-        pos, box = frame("liquid600")
-        pos = (pos + np.array([0.37 * float(box[0, 0]), 0, 0], dtype=np.float32)).astype(np.float32)
-        assert 0.25 < float((pos[:, 0] > box[0, 0]).mean()) < 0.45
-    elif tag == "liquid600_wrapped":              # ... and those brought back by one box vector: other shifts, another dL/dB
-        pos, box = frame("liquid600_shifted")
-        pos = (pos - (pos[:, :1] > box[0, 0]) * box[0]).astype(np.float32)
-    elif tag == "triclinic80":                    # the pinning frames: L = 9.3 and 10.0, the cutoff below half the narrowest width
-        pos, _, box = workloads.triclinic_box(80, seed=5)
-    elif tag == "cubic100":
-        pos, _, box = workloads.random_box(100, seed=6)
-    else:
-        raise KeyError(tag)
-    return pos, box
 
 
 # ---------------------------------------------------------------------------------------------- the pinning tests

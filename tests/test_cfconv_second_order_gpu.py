@@ -1,7 +1,7 @@
 """Second derivatives of the CFConv: nnpops_cfconv_double_backward and the twice-differentiable torch surface above it.
 
-The judge is the float64 restatement of tests/test_cfconv_second_order_reference_cpu.py (pinned there to the float32 oracle, to the
-closed-form expressions and to finite differences): with seeded float32 weights, inputs and cotangents V, Q it gives the gradients
+The judge is `SecondOrder` of tests/cfconv_float64.py (pinned by tests/test_cfconv_second_order_reference_cpu.py to the float32 oracle,
+to the closed-form expressions and to finite differences): with seeded float32 weights, inputs and cotangents V, Q it gives the gradients
 of M = <V, gx> + <Q, gp> with respect to (output gradient, input, positions) over a fixed pair list.  Every comparison first takes
 the pair set from the device (nnpops_cfconv_neighbors_export) and asserts that it is the restatement's: both then sum the same
 pairs, and no pair sits inside the jump of F'' at the cutoff.  One float64 evaluation per (system, layer), kept for the module.
@@ -18,14 +18,11 @@ G 12 and G 256 (two channels per lane, weights in LDS and streamed), W 260 (eigh
 triclinic350 (all-pairs build), liquid1500 (cell-ordered walk), dense1100 (rows of 89-120 entries: more than a wave, no multiple of
 16), and a 60-atom molecule in vacuum with one atom far away (an empty row: exact zeros).
 """
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 import torch
 
-from nnpops_amd import workloads
+from cfconv_float64 import Restatement, SecondOrder, cotangents, frame, handles, layer, sigma_of, weights
 
 pytestmark = pytest.mark.gpu
 
@@ -35,13 +32,6 @@ BAR = {"matrix": 8e-5, "vector": 4e-5}
 SUM_BAR = {"matrix": 1e-5, "vector": 2e-5}         # |sum_i dM/dpos_i| of the largest entry
 STEP_BAR = {"matrix": 7e-6, "vector": 1e-5}        # the force-loss step through two layers
 HESSIAN_BAR = 3e-6                                 # |u.Hv - v.Hu| / |u.Hv|
-
-_spec = importlib.util.spec_from_file_location("cfconv_second_reference", os.path.join(os.path.dirname(os.path.abspath(__file__)),
-                                                                                     "test_cfconv_second_order_reference_cpu.py"))
-_reference_module = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(_reference_module)
-Restatement, SecondOrder = _reference_module.Restatement, _reference_module.SecondOrder
-frame, weights, cotangents = _reference_module.frame, _reference_module.weights, _reference_module.cotangents
 
 SHAPES = {                     # name: (family, W, G, activation, frames)
     "matrix-one-block": ("matrix", 16, 8, "ssp", ["triclinic350", "dense1100", "molecule"]),
@@ -61,35 +51,17 @@ SHAPES = {                     # name: (family, W, G, activation, frames)
 CASES = [(name, tag) for name, (_, _, _, _, tags) in SHAPES.items() for tag in tags]
 
 _REFERENCES = {}
-_FRAMES = {}
-
-
-def _sigma(G):
-    return 0.1 if G >= 25 else 0.4
-
-
-def _frame(tag):
-    """-> (pos, box or None)"""
-    if tag not in _FRAMES:
-        if tag == "molecule":          # 60 bonded atoms in vacuum and one atom 100 A away from them: an empty row
-            pos, _ = workloads.conformer(60, seed=4)
-            far = pos.mean(axis=0) + np.array([100.0, 0.0, 0.0])
-            _FRAMES[tag] = (np.concatenate([pos, far[None]]).astype(np.float32), None)
-        else:
-            _FRAMES[tag] = frame(tag)
-    return _FRAMES[tag]
 
 
 def _layer(tag, W, G):
     """-> (w1, b1, w2, b2, x, gout, V, Q) of a layer on a frame, seeded by the shape"""
-    n = len(_frame(tag)[0])
-    return weights(W, G, n, 1000 * W + G) + cotangents(n, W, 2000 * W + G)
+    return layer(tag, W, G) + cotangents(len(frame(tag)[0]), W, 2000 * W + G)
 
 
 def _second_order(tag, W, G, act):
-    pos, box = _frame(tag)
+    pos, box = frame(tag)
     w1, b1, w2, b2 = _layer(tag, W, G)[:4]
-    judge = Restatement(W, G, CUTOFF, _sigma(G), act, w1, b1, w2, b2)
+    judge = Restatement(W, G, CUTOFF, sigma_of(G), act, w1, b1, w2, b2)
     return SecondOrder.open(judge, pos) if box is None else SecondOrder.periodic(judge, pos, box)
 
 
@@ -99,16 +71,8 @@ def _reference(tag, W, G, act):
     if key not in _REFERENCES:
         so = _second_order(tag, W, G, act)
         _, _, _, _, x, gy, V, Q = _layer(tag, W, G)
-        _REFERENCES[key] = (so, so.second(_frame(tag)[0], x, gy, V, Q))
+        _REFERENCES[key] = (so, so.second(frame(tag)[0], x, gy, V, Q))
     return _REFERENCES[key]
-
-
-def _handles(tag, W, G, act):
-    from nnpops_amd.capi import CFConv, CFConvNeighbors
-    pos, box = _frame(tag)
-    w1, b1, w2, b2 = _layer(tag, W, G)[:4]
-    periodic = box is not None
-    return (CFConvNeighbors(len(pos), CUTOFF, periodic), CFConv(len(pos), W, G, CUTOFF, _sigma(G), act, w1, b1, w2, b2, periodic=periodic))
 
 
 def _dev(*arrays):
@@ -117,8 +81,8 @@ def _dev(*arrays):
 
 def _built(tag, W, G, act, so):
     """handles with the list built on the frame; asserts that the device's pair set is the restatement's"""
-    nb, cf = _handles(tag, W, G, act)
-    tpos, tbox = _dev(*_frame(tag))
+    nb, cf = handles(tag, W, G, act, CUTOFF)
+    tpos, tbox = _dev(*frame(tag))
     nb.build(tpos, tbox)
     atoms, _ = nb.export()
     assert np.array_equal(atoms[0], so.i.numpy()) and np.array_equal(atoms[1], so.j.numpy()), \
@@ -154,7 +118,7 @@ def test_double_backward_against_float64(shape, tag):
         assert torch.equal(a, b), "two calls give different bits"
     err = _errors(first, ref)
     print(f"\n[cfconv-second] {shape} W={W} G={G} {act} {tag} ({family}): dM/dg {err['dg']:.2e}  dM/dx {err['dx']:.2e}  dM/dpos {err['dp']:.2e} "
-          f"of max; rows {counts.min()}..{counts.max()}, margin to the cutoff {so.margin(_frame(tag)[0]):.1e}")
+          f"of max; rows {counts.min()}..{counts.max()}, margin to the cutoff {so.margin(frame(tag)[0]):.1e}")
     for t in first:
         assert bool(torch.isfinite(t).all())
     if tag == "molecule":
@@ -255,8 +219,8 @@ def test_refused_without_a_cotangent_or_a_list():
     from nnpops_amd.capi import NNPOpsHipError
     _, W, G, act, _ = SHAPES["matrix-ssp"]
     tag = "triclinic350"
-    nb, cf = _handles(tag, W, G, act)
-    tpos, tbox = _dev(*_frame(tag))
+    nb, cf = handles(tag, W, G, act, CUTOFF)
+    tpos, tbox = _dev(*frame(tag))
     x, gy, V, Q = _dev(*_layer(tag, W, G)[4:])
     with pytest.raises(NNPOpsHipError, match="not been built"):
         cf.double_backward(nb, tpos, x, gy, V, Q)
@@ -273,7 +237,7 @@ def _model(tag, W, G, act, twice, seed=0):
     from NNPOps.CFConv import CFConv
     from NNPOps.CFConvNeighbors import CFConvNeighbors
     la, lb = weights(W, G, 1, 31 + seed)[:4], weights(W, G, 1, 32 + seed)[:4]
-    as_module = lambda w1, b1, w2, b2: CFConv(_sigma(G), act, torch.tensor(w1).reshape(G, W), torch.tensor(b1), torch.tensor(w2),
+    as_module = lambda w1, b1, w2, b2: CFConv(sigma_of(G), act, torch.tensor(w1).reshape(G, W), torch.tensor(b1), torch.tensor(w2),
                                               torch.tensor(b2), twice_differentiable=twice)
 
     class Model(torch.nn.Module):
@@ -302,7 +266,7 @@ def _force_loss_step(model, pos, x, box, readout, f_ref):
 
 
 def _step_inputs(tag, W, G):
-    pos, box = _frame(tag)
+    pos, box = frame(tag)
     _, _, _, _, x, gy, _, Q = _layer(tag, W, G)
     return pos, box, x, (0.1 * gy).astype(np.float32), (0.1 * Q).astype(np.float32)
 
@@ -339,8 +303,8 @@ def test_force_loss_step_against_float64(shape):
     (sw, sp, sx), _, _ = _force_loss_step(scripted, tpos, tx, tbox, tr, tf)
     assert torch.equal(sw, gw) and torch.equal(sp, gp) and torch.equal(sx, gx), "the scripted module gives other numbers"
     # float64
-    so1 = SecondOrder.periodic(Restatement(W, G, CUTOFF, _sigma(G), act, *la), pos, box)
-    so2 = SecondOrder(Restatement(W, G, CUTOFF, _sigma(G), act, *lb), so1.i, so1.j, so1.shift)
+    so1 = SecondOrder.periodic(Restatement(W, G, CUTOFF, sigma_of(G), act, *la), pos, box)
+    so2 = SecondOrder(Restatement(W, G, CUTOFF, sigma_of(G), act, *lb), so1.i, so1.j, so1.shift)
     wide = lambda a: torch.tensor(np.asarray(a, dtype=np.float32).astype(np.float64))
     w = wide(model.linear.weight.detach().cpu().numpy()).requires_grad_(True)
     p, xin = wide(pos).requires_grad_(True), wide(x).requires_grad_(True)

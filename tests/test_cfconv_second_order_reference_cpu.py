@@ -1,14 +1,11 @@
-"""The float64 judge of the CFConv second derivatives, and what pins it (CPU only).
+"""What pins the float64 judge of the CFConv second derivatives (CPU only).
 
-`SecondOrder` restates the convolution in torch float64 over a FIXED pair list with frozen shifts -- d_ij = x_j - x_i + n_ij B, the
-pairs and n_ij B taken once from the restatement of tests/test_cfconv_box_gradient_reference_cpu.py (loaded from that file) -- as a
-differentiable function of positions, input and output gradient.  Autograd with create_graph gives the backward pass (gx, gp) and,
-for cotangents V of gx and Q of gp, the gradients of M = <V, gx> + <Q, gp> with respect to (g, x, positions): what
-nnpops_cfconv_double_backward returns.  tests/test_cfconv_second_order_gpu.py loads it from this file.
+The judge itself is `SecondOrder` of tests/cfconv_float64.py, over the pairs and shifts of that module's `Restatement`; its head says
+what both compute.
 
 What pins it:
-    out, gx, gp            against the float32 CFConvOracle at OUT_RTOL / OUT_ATOL_FRAC / FORCE_RTOL of the box-gradient reference.
-    dM/dg, dM/dx, dM/dpos  against the closed-form expressions the kernels implement (`closed_form` below writes them
+    out, gx, gp            against the float32 CFConvOracle at OUT_RTOL / OUT_ATOL_FRAC / FORCE_RTOL of tests/cfconv_float64.py.
+    dM/dg, dM/dx, dM/dpos  against the closed-form expressions the kernels implement (`closed_form` of that module writes them
         out pair by pair with explicit gamma'', act'', fc'' and F''), both activations.  Both sides are float64 and algebraically
         equal: bar 1e-12 of the largest entry (measured 2e-16 ... 7e-16).
     dM/dpos                against central differences of the first backward, M(p + h e) - M(p - h e) over 2h, Richardson-extrapolated
@@ -20,132 +17,18 @@ What pins it:
     the library exports nnpops_cfconv_double_backward, reports a null handle, and the two _twice ops and the module's flag exist.
 """
 import ctypes
-import importlib.util
-import math
-import os
 
 import numpy as np
 import pytest
 import torch
 
+from cfconv_float64 import (FORCE_RTOL, OUT_ATOL_FRAC, OUT_RTOL, Restatement, SecondOrder, _wide, closed_form, cotangents, frame,
+                            weights)
 from oracle import CFConvNeighborsOracle, CFConvOracle
-
-_spec = importlib.util.spec_from_file_location("cfconv_box_reference", os.path.join(os.path.dirname(os.path.abspath(__file__)),
-                                                                                  "test_cfconv_box_gradient_reference_cpu.py"))
-_box = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(_box)
-Restatement, frame, weights = _box.Restatement, _box.frame, _box.weights
-OUT_RTOL, OUT_ATOL_FRAC, FORCE_RTOL = _box.OUT_RTOL, _box.OUT_ATOL_FRAC, _box.FORCE_RTOL
 
 CLOSED_FORM_RTOL = 1e-12
 FD_RTOL = 2e-10
 FD_DIRECTION_RTOL = 6e-10
-
-
-def _wide(a):
-    return torch.tensor(np.asarray(a, dtype=np.float32).astype(np.float64))
-
-
-class SecondOrder:
-    """The convolution over a fixed half list (i, j) with frozen shifts [P][3] (d = x_j - x_i + shift), float64, differentiable.
-    `judge` is the Restatement that holds the layer."""
-
-    def __init__(self, judge, i, j, shift):
-        self.judge = judge
-        self.i, self.j = torch.as_tensor(np.asarray(i), dtype=torch.int64), torch.as_tensor(np.asarray(j), dtype=torch.int64)
-        self.shift = torch.as_tensor(np.asarray(shift, dtype=np.float64))
-
-    @classmethod
-    def periodic(cls, judge, pos, box):
-        """pairs and shifts of a periodic frame, by the restatement's own rule"""
-        p64, b64 = np.asarray(pos, np.float32).astype(np.float64), np.asarray(box, np.float32).astype(np.float64).reshape(3, 3)
-        i, j, n = judge.pairs(p64, b64)
-        return cls(judge, i, j, n @ b64)
-
-    @classmethod
-    def open(cls, judge, pos):
-        """pairs of a non-periodic frame: every i < j below the cutoff"""
-        p = np.asarray(pos, np.float32).astype(np.float64)
-        r2 = ((p[None] - p[:, None]) ** 2).sum(-1)
-        i, j = np.nonzero(np.triu(r2 < judge.cutoff ** 2, 1))
-        return cls(judge, i, j, np.zeros((len(i), 3)))
-
-    def margin(self, pos):
-        """smallest cutoff - r over the listed pairs"""
-        d = _wide(pos)[self.j] - _wide(pos)[self.i] + self.shift
-        return float((self.judge.cutoff - d.norm(dim=1)).min()) if len(self.i) else float("inf")
-
-    def forward(self, p, x):
-        d = p[self.j] - p[self.i] + self.shift
-        y2 = self.judge.filters(d)
-        out = torch.zeros_like(x)
-        return out.index_add(0, self.i, y2 * x[self.j]).index_add(0, self.j, y2 * x[self.i])
-
-    def first(self, pos, x, g, create_graph=False):
-        """-> (out, gx, gp, leaves): leaves = (p, x, g) float64 tensors that require a gradient"""
-        p, xin, gin = (_wide(a).requires_grad_(True) for a in (pos, x, g))
-        out = self.forward(p, xin)
-        gx, gp = torch.autograd.grad((out * gin).sum(), [xin, p], create_graph=create_graph)
-        return out, gx, gp, (p, xin, gin)
-
-    def second(self, pos, x, g, V=None, Q=None):
-        """-> dict(out, gx, gp, dg, dx, dp) as float64 numpy arrays; a cotangent that is None is zero"""
-        out, gx, gp, (p, xin, gin) = self.first(pos, x, g, create_graph=True)
-        M = 0.0
-        if V is not None:
-            M = M + (_wide(V) * gx).sum()
-        if Q is not None:
-            M = M + (_wide(Q) * gp).sum()
-        dg, dx, dp = torch.autograd.grad(M, [gin, xin, p], allow_unused=True)
-        z = lambda t, like: (torch.zeros_like(like) if t is None else t).numpy()
-        return dict(out=out.detach().numpy(), gx=gx.detach().numpy(), gp=gp.detach().numpy(), dg=z(dg, gin), dx=z(dx, xin), dp=z(dp, p),
-                    M=float(M.detach()))
-
-
-def closed_form(so, pos, x, g, V, Q):
-    """dM/dg, dM/dx, dM/dpos pair by pair from the written-out derivatives (no autograd)"""
-    J = so.judge
-    p, xin, gin, Vt, Qt = (_wide(a) for a in (pos, x, g, V, Q))
-    i, j = so.i, so.j
-    d = p[j] - p[i] + so.shift
-    r = d.norm(dim=1)
-    u = d / r[:, None]
-    t = r[:, None] - J.mu[None, :]
-    s2i = 1.0 / J.sigma ** 2
-    gam = torch.exp(-0.5 * t * t * s2i)
-    dgam = -t * s2i * gam
-    ddgam = (t * t * s2i - 1.0) * s2i * gam
-    s1, ds1, dds1 = gam @ J.w1.T + J.b1, dgam @ J.w1.T, ddgam @ J.w1.T
-    if J.act == 0:
-        sg = torch.sigmoid(s1)
-        y, a1, a2 = torch.log(0.5 * torch.exp(s1) + 0.5), sg, sg * (1.0 - sg)
-    else:
-        th = torch.tanh(s1)
-        y, a1, a2 = th, 1.0 - th * th, -2.0 * th * (1.0 - th * th)
-    dy, ddy = a1 * ds1, a2 * ds1 * ds1 + a1 * dds1
-    S, dS, ddS = y @ J.w2.T + J.b2, dy @ J.w2.T, ddy @ J.w2.T
-    k = math.pi / J.cutoff
-    fc, dfc, ddfc = 0.5 * torch.cos(k * r) + 0.5, -0.5 * k * torch.sin(k * r), -0.5 * k * k * torch.cos(k * r)
-    F = fc[:, None] * S
-    F1 = dfc[:, None] * S + fc[:, None] * dS
-    F2 = ddfc[:, None] * S + 2.0 * dfc[:, None] * dS + fc[:, None] * ddS
-    dQ = Qt[j] - Qt[i]
-    a = (u * dQ).sum(1)
-    A = Vt[j] * gin[i] + Vt[i] * gin[j]
-    B = xin[j] * gin[i] + xin[i] * gin[j]
-    F1A, F1B, F2B = (F1 * A).sum(1), (F1 * B).sum(1), (F2 * B).sum(1)
-    dg = torch.zeros_like(gin).index_add(0, i, F * Vt[j] + a[:, None] * F1 * xin[j]).index_add(0, j, F * Vt[i] + a[:, None] * F1 * xin[i])
-    dx = torch.zeros_like(xin).index_add(0, i, a[:, None] * F1 * gin[j]).index_add(0, j, a[:, None] * F1 * gin[i])
-    T = (F1A + a * F2B - a / r * F1B)[:, None] * u + (F1B / r)[:, None] * dQ
-    dp = torch.zeros_like(p).index_add(0, i, -T).index_add(0, j, T)
-    terms = dict(F1A=float(F1A.abs().max()), aF2B=float((a * F2B).abs().max()))
-    return dg.numpy(), dx.numpy(), dp.numpy(), terms
-
-
-def cotangents(n, W, seed):
-    rng = np.random.default_rng(seed)
-    return rng.standard_normal((n, W)).astype(np.float32), rng.standard_normal((n, 3)).astype(np.float32)
-
 
 PIN_CASES = [("triclinic80", 8, 6, 4.0, 0.5, "ssp"), ("triclinic80", 8, 6, 4.0, 0.5, "tanh"), ("cubic100", 12, 9, 4.5, 0.4, "tanh")]
 PIN_IDS = [c[0] + "-" + c[5] for c in PIN_CASES]

@@ -53,6 +53,24 @@ def test_product_never_imports_the_oracle():
     subprocess.check_call([sys.executable, "-c", code], cwd=ROOT)
 
 
+def test_no_test_file_is_loaded_as_a_module():
+    """What several test files share lives in plain modules under tests/ (pme_float64, cfconv_float64, ani_float64, ...): no test
+    file runs another test file as code.  (bench.py is loaded by path where its functions are under test.)"""
+    offenders = []
+    tests = os.path.join(ROOT, "tests")
+    for f in sorted(os.listdir(tests)):
+        if re.fullmatch(r"test_.*\.py", f):
+            text = open(os.path.join(tests, f)).read()
+            for call in re.finditer(r"spec_from_file_location\s*\(", text):
+                depth, end = 1, call.end()
+                while depth and end < len(text):                       # the call's arguments, to its closing parenthesis
+                    depth += {"(": 1, ")": -1}.get(text[end], 0)
+                    end += 1
+                if re.search(r"test_\w*\.py", text[call.end():end]):
+                    offenders.append(f)
+    assert not offenders, offenders
+
+
 def test_no_reference_sources_in_tree():
     """Fixtures are data; the reference's sources stay under /root/reference."""
     bad = []
