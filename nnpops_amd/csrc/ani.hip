@@ -17,7 +17,7 @@
 #include "ani_radial_bwd.h"
 #include "ani_build_forward.h"
 #include "ani_box_grad.h"
-#include "host_common.h"
+#include "celllist_host.h"
 
 using namespace nnpops;
 
@@ -74,7 +74,6 @@ struct nnpops_ani {
     int last_radial_lanes = -1;     // 1: a lane per neighbour (ani_radial_bwd.h), 0: the round-1 ani_radial_backward (rows)
     int last_tile = -1;             // pair-matrix tile and compact_bwd flag the round-1 angular backward was launched with
     int last_compact = -1;
-    bool fine_grid = true;          // cell grid of half-cutoff cells where it fits (celllist.h: decide_grid)
     bool fwd_row_via_lds = true;    // the angular row leaves as whole-wave stores from an LDS copy
     int fwd_occ = 7;                // A/B: register budget of the forward kernel (waves per SIMD)
     bool fwd_dynamic = false;       // quads dealt out per atom from its bucket sizes (ani_angular_mfma.h: DYN): set at create from the
@@ -96,21 +95,7 @@ struct nnpops_ani {
     int* h_status_dev = nullptr;    // the device's address of the same words
     int check_stamp = 0;
     bool check_pending = false;
-    // cell grid (celllist.h)
-    CellGrid* d_grid = nullptr;
-    int* d_cell_count = nullptr;    // [max_cells]
-    int* d_cell_start = nullptr;    // [max_cells+1]
-    int* d_atom_cell = nullptr;     // [N]
-    int* d_atom_rank = nullptr;     // [N]
-    int* d_sorted_cell = nullptr;   // [N] cell of the atom in every sorted slot
-    int* d_tile_total = nullptr;    // [max_cells / 8192 + 1] partial sums of the parallel cell scan
-    int* d_unsorted_atom = nullptr; // [N] cell segments in arrival order
-    int* d_sorted_atom = nullptr;   // [N]
-    float4* d_sorted_pos = nullptr; // [N]
-    int max_cells = 0;
-    int* d_hist = nullptr;          // two-kernel cell build (celllist.h): [kBinnedCells + 1]
-    int* d_bins = nullptr;          // [kBinnedCells][bin_cap]
-    int bin_cap = 64;
+    CellList cells;                 // cell grid (celllist_host.h); cells.fine: half-cutoff cells where they fit ($NNPOPS_ANI_FINE_GRID=0)
     bool cells_disabled = false;    // set when a box turned out too small for the 27-cell stencil
     int cap = 0;                    // row capacity (angular + radial-only neighbours)
     bool cap_fitted = false;        // the first clean check() shrinks `cap` to the system
@@ -120,7 +105,7 @@ struct nnpops_ani {
     bool computed = false;
     // optional per-kernel HIP-event timing (nnpops_ani_enable_timing)
     int ld_radial = 0, ld_angular = 0;   // row strides (floats) of the AEV / gradient arrays of the call in progress
-    bool last_used_cells = false;   // the last compute() built a cell grid (d_sorted_atom is a permutation in cell order)
+    bool last_used_cells = false;   // the last compute() built a cell grid (cells.sorted_atom is a permutation in cell order)
     int* d_work_order = nullptr;    // [N] atoms by DECREASING number of angular neighbours (check() builds it): the schedule of the
     bool work_order_valid = false;  //     angular kernels -- heaviest atoms first, the light ones fill the tail
     unsigned char* d_class_tile = nullptr;   // [N] pair-matrix edge of the backward launch every atom belongs to (255: no limit)
@@ -514,7 +499,7 @@ bool pair_backward_fits(const nnpops_ani* h) {
 // The spans of one evaluation: nstreams stretches of the (cell-ordered) atoms when the kernels in use take ranges, else one.
 int make_spans(nnpops_ani* h, Span (&spans)[4]) {
     const int N = h->hp.N;
-    const int* order = h->last_used_cells ? h->d_sorted_atom : nullptr;
+    const int* order = h->last_used_cells ? h->cells.sorted_atom : nullptr;
     int k = h->can_split && N >= 2048 ? std::max(1, std::min(4, h->nstreams)) : 1;
     if (k > 1 && (!h->ev_fork || !h->side[k - 2])) {           // first use: streams cannot be created while the caller captures a graph
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -674,7 +659,8 @@ int nnpops_ani_create(nnpops_ani_t* out, int num_atoms, int num_species, float r
         if (const char* e = std::getenv("NNPOPS_ANI_CELL_ATOMS")) h->cell_atoms = std::max(1, std::atoi(e));
         if (const char* e = std::getenv("NNPOPS_ANI_RBWD")) h->rbwd_lanes = std::atoi(e) != 0;
         if (const char* e = std::getenv("NNPOPS_ANI_SCATTER")) h->scatter_mode = std::atoi(e) != 0 ? 1 : 0;
-        if (const char* e = std::getenv("NNPOPS_ANI_FINE_GRID")) h->fine_grid = std::atoi(e) != 0;
+        h->cells.fine = 1;
+        if (const char* e = std::getenv("NNPOPS_ANI_FINE_GRID")) h->cells.fine = std::atoi(e) != 0;
         if (const char* e = std::getenv("NNPOPS_ANI_FWD_ROWLDS")) h->fwd_row_via_lds = std::atoi(e) != 0;
         if (const char* e = std::getenv("NNPOPS_ANI_FWD_OCC")) h->fwd_occ = std::atoi(e);
         {   // Does the per-atom quad table pay?  With one quad set per species pair the step loop of phase 2 runs max_b n_b / K times,
@@ -716,21 +702,7 @@ int nnpops_ani_create(nnpops_ani_t* out, int num_atoms, int num_species, float r
     if ((rc = dev_alloc(&h->d_status, (size_t)kStatAlloc))) return cleanup(rc);
     if (periodic && (rc = dev_alloc(&h->d_box_partials, (size_t)9 * ani_box_blocks(num_atoms)))) return cleanup(rc);
     if ((rc = alloc_rows(h))) return cleanup(rc);
-    h->max_cells = num_atoms + 4096;
-    if ((rc = dev_alloc(&h->d_grid, 1))) return cleanup(rc);
-    if ((rc = dev_alloc(&h->d_cell_count, (size_t)h->max_cells))) return cleanup(rc);
-    if ((rc = dev_alloc(&h->d_cell_start, (size_t)h->max_cells + 1))) return cleanup(rc);
-    if (const char* e = std::getenv("NNPOPS_CELL_BIN_CAP")) h->bin_cap = std::max(4, std::atoi(e) & ~3);   // tests: force growth
-    if (periodic && num_atoms <= kBinnedAtoms) {
-        if ((rc = dev_alloc(&h->d_hist, (size_t)kHistWords))) return cleanup(rc);
-        if ((rc = dev_alloc(&h->d_bins, (size_t)kBinnedCells * h->bin_cap))) return cleanup(rc);
-        if (hipMemset(h->d_hist, 0, sizeof(int) * kHistWords) != hipSuccess) return cleanup(fail(NNPOPS_ERR_HIP, "memset failed"));
-    }
-    if ((rc = dev_alloc(&h->d_atom_cell, (size_t)num_atoms))) return cleanup(rc);
-    if ((rc = dev_alloc(&h->d_atom_rank, (size_t)num_atoms))) return cleanup(rc);
-    if ((rc = dev_alloc(&h->d_sorted_cell, (size_t)num_atoms))) return cleanup(rc);
-    if ((rc = dev_alloc(&h->d_tile_total, (size_t)h->max_cells / kScanTile + 2))) return cleanup(rc);
-    if ((rc = dev_alloc(&h->d_sorted_atom, (size_t)num_atoms))) return cleanup(rc);
+    if ((rc = h->cells.allocate(num_atoms, periodic != 0, /*tiled_scan=*/true))) return cleanup(rc);
     if ((rc = dev_alloc(&h->d_work_order, (size_t)num_atoms))) return cleanup(rc);
     if ((rc = dev_alloc(&h->d_class_tile, (size_t)num_atoms))) return cleanup(rc);
     if (hipMemset(h->d_class_tile, 255, (size_t)num_atoms) != hipSuccess) return cleanup(fail(NNPOPS_ERR_HIP, "memset failed"));
@@ -738,8 +710,6 @@ int nnpops_ani_create(nnpops_ani_t* out, int num_atoms, int num_species, float r
     if (const char* e = std::getenv("NNPOPS_ANI_BWD_CLASSES")) h->bwd_by_class = std::atoi(e) != 0;
     if (const char* e = std::getenv("NNPOPS_ANI_BWD_CLASS_MIN")) h->bwd_class_min = std::max(0, std::atoi(e));
     if (const char* e = std::getenv("NNPOPS_ANI_BWD_CLASS_ATOMS")) h->bwd_class_atoms = std::max(0, std::atoi(e));
-    if ((rc = dev_alloc(&h->d_unsorted_atom, (size_t)num_atoms))) return cleanup(rc);
-    if ((rc = dev_alloc(&h->d_sorted_pos, (size_t)num_atoms))) return cleanup(rc);
     if ((rc = dev_alloc(&h->d_bucket_offsets, (size_t)num_atoms * (hp.NB + 1)))) return cleanup(rc);
     hp.bucket_offsets = h->d_bucket_offsets;
     if (hipMemset(h->d_bucket_offsets, 0, sizeof(int) * (size_t)num_atoms * (hp.NB + 1)) != hipSuccess)
@@ -797,9 +767,8 @@ int nnpops_ani_destroy(nnpops_ani_t h) {
     dev_free(h->d_params); dev_free(h->d_species); dev_free(h->d_segment);
     dev_free(h->d_nbr); dev_free(h->d_recA); dev_free(h->d_recB); dev_free(h->d_tri); dev_free(h->d_cnt_a); dev_free(h->d_cnt_ro); dev_free(h->d_cnt_pos); dev_free(h->d_status); dev_free(h->d_box_partials);
     dev_free(h->d_ids); dev_free(h->d_leg_force); dev_free(h->d_centre_force); dev_free(h->d_bucket_offsets);
-    dev_free(h->d_hist); dev_free(h->d_bins);
-    dev_free(h->d_grid); dev_free(h->d_cell_count); dev_free(h->d_cell_start); dev_free(h->d_atom_cell);
-    dev_free(h->d_atom_rank); dev_free(h->d_sorted_cell); dev_free(h->d_tile_total); dev_free(h->d_sorted_atom); dev_free(h->d_work_order); dev_free(h->d_class_tile); dev_free(h->d_unsorted_atom); dev_free(h->d_sorted_pos);
+    dev_free(h->d_work_order); dev_free(h->d_class_tile);
+    h->cells.release();
     for (int q = 0; q < 3; q++) {
         if (h->side[q]) (void)hipStreamDestroy(h->side[q]);
         if (h->ev_join[q]) (void)hipEventDestroy(h->ev_join[q]);
@@ -886,10 +855,7 @@ int nnpops_ani_compute_strided(nnpops_ani_t h, const float* positions, const flo
     h->last_used_cells = use_cells;
     if (use_cells) {
         KernelTimer timer(h, NNPOPS_ANI_K_CELL_GRID);
-        const CellBuffers cb{h->d_grid, h->d_cell_count, h->d_cell_start, h->d_atom_cell, h->d_atom_rank,
-                             h->d_unsorted_atom, h->d_sorted_atom, h->d_sorted_pos, h->max_cells,
-                             h->d_hist, h->d_bins, h->bin_cap, h->fine_grid ? 1 : 0, h->d_sorted_cell, h->d_tile_total};
-        launch_cell_build(h->stream, N, positions, box, per, h->hp.rcr, h->d_species, cb);
+        launch_cell_build(h->stream, N, positions, box, per, h->hp.rcr, h->d_species, h->cells);
     }
     // The per-atom kernels, span by span: every span's chain (neighbour build -> angular forward) runs on its own stream.
     h->can_split = !h->generic && h->forward_kernel == 2 && h->backward_kernel >= 1 &&
@@ -905,7 +871,7 @@ int nnpops_ani_compute_strided(nnpops_ani_t h, const float* positions, const flo
         if (h->last_fused_build) {                             // one launch: build + radial + angular forward (timed as the build)
             KernelTimer timer(h, NNPOPS_ANI_K_NEIGHBORS, sp.stream);
             KernelTimer merged_timer(h, NNPOPS_ANI_K_NEIGHBORS, sp.stream, /*merged=*/true);      // (merge mode brackets the same launch: ADVICE r04)
-            const BuildInputs in{box, h->d_grid, h->d_cell_start, h->d_sorted_cell, h->d_sorted_pos, h->d_hist, positions, h->d_species,
+            const BuildInputs in{box, h->cells.grid, h->cells.cell_start, h->cells.sorted_cell, h->cells.sorted_pos, h->cells.hist, positions, h->d_species,
                                  h->d_segment, use_cells ? 1 : 0, per ? 1 : 0};
             const BuildOutputs out{h->d_nbr, h->d_recA, h->d_recB, h->d_ids, h->d_tri, h->d_cnt_a, h->d_cnt_ro, h->d_cnt_pos, h->d_status, radial, h->ld_radial};
             rc = h->hp.torchani ? launch_build_forward<true>(h, in, out, angular, sp) : launch_build_forward<false>(h, in, out, angular, sp);
@@ -917,14 +883,14 @@ int nnpops_ani_compute_strided(nnpops_ani_t h, const float* positions, const flo
         KernelTimer timer(h, NNPOPS_ANI_K_NEIGHBORS, sp.stream);
         if (use_cells) {
             if (per)
-                hipLaunchKernelGGL(ani_neighbors_cells<true>, sgrid, ablock, lds_b, sp.stream, h->d_params, box, h->d_grid,
-                                   h->d_cell_start, h->d_sorted_cell, h->d_sorted_pos, h->d_nbr, h->cap, h->cap_angular, h->d_recA,
-                                   h->d_recB, h->d_ids, h->d_tri, h->d_cnt_a, h->d_cnt_ro, h->d_cnt_pos, h->d_status, radial, h->ld_radial, lds_bw, h->d_hist,
+                hipLaunchKernelGGL(ani_neighbors_cells<true>, sgrid, ablock, lds_b, sp.stream, h->d_params, box, h->cells.grid,
+                                   h->cells.cell_start, h->cells.sorted_cell, h->cells.sorted_pos, h->d_nbr, h->cap, h->cap_angular, h->d_recA,
+                                   h->d_recB, h->d_ids, h->d_tri, h->d_cnt_a, h->d_cnt_ro, h->d_cnt_pos, h->d_status, radial, h->ld_radial, lds_bw, h->cells.hist,
                                    sp.w0, sp.nw);
             else
-                hipLaunchKernelGGL(ani_neighbors_cells<false>, sgrid, ablock, lds_b, sp.stream, h->d_params, box, h->d_grid,
-                                   h->d_cell_start, h->d_sorted_cell, h->d_sorted_pos, h->d_nbr, h->cap, h->cap_angular, h->d_recA,
-                                   h->d_recB, h->d_ids, h->d_tri, h->d_cnt_a, h->d_cnt_ro, h->d_cnt_pos, h->d_status, radial, h->ld_radial, lds_bw, h->d_hist,
+                hipLaunchKernelGGL(ani_neighbors_cells<false>, sgrid, ablock, lds_b, sp.stream, h->d_params, box, h->cells.grid,
+                                   h->cells.cell_start, h->cells.sorted_cell, h->cells.sorted_pos, h->d_nbr, h->cap, h->cap_angular, h->d_recA,
+                                   h->d_recB, h->d_ids, h->d_tri, h->d_cnt_a, h->d_cnt_ro, h->d_cnt_pos, h->d_status, radial, h->ld_radial, lds_bw, h->cells.hist,
                                    sp.w0, sp.nw);
         } else if (per)
             hipLaunchKernelGGL(ani_neighbors_allpairs<true>, sgrid, ablock, lds_b, sp.stream, h->d_params, positions, box,
@@ -1052,7 +1018,7 @@ int nnpops_ani_backprop_box_strided(nnpops_ani_t h, const float* positions, cons
     const int nblocks = ani_box_blocks(h->hp.N);
     hipLaunchKernelGGL(ani_box_partials, dim3(nblocks), dim3(kBoxThreads), 0, h->stream, h->d_params, positions, box, h->d_nbr, h->cap,
                        h->cap_angular, h->d_cnt_pos, radial_deriv, h->ld_radial, h->d_recA, h->d_ids, h->d_leg_force,
-                       h->last_used_cells ? h->d_sorted_atom : nullptr, h->scatter_now ? 1 : 0, h->d_box_partials);
+                       h->last_used_cells ? h->cells.sorted_atom : nullptr, h->scatter_now ? 1 : 0, h->d_box_partials);
     hipLaunchKernelGGL(pairs_box_finish<float>, dim3(1), dim3(kBoxThreads), 0, h->stream, nblocks, (const double*)h->d_box_partials, box_deriv);
     NNPOPS_HIP_TRY(hipGetLastError());
     return NNPOPS_OK;
@@ -1237,17 +1203,14 @@ int nnpops_ani_check(nnpops_ani_t h, int* max_radial_neighbors, int* max_angular
         }
         return NNPOPS_OK;
     }
-    if (st[kStatOverflow] & 4) {          // a cell holds more atoms than a bin of the two-kernel grid build: grow the bins
-        const int old_bin = h->bin_cap;
-        h->bin_cap *= 2;
-        dev_free(h->d_bins);
-        h->d_bins = nullptr;
-        int rc = dev_alloc(&h->d_bins, (size_t)kBinnedCells * h->bin_cap);
+    if (st[kStatOverflow] & kGridBinOverflow) {     // a cell holds more atoms than a bin of the two-kernel grid build: grow the bins
+        int old_bin;
+        int rc = h->cells.grow_bins(&old_bin);
         if (rc != NNPOPS_OK) return rc;
         h->computed = false;
-        return fail(NNPOPS_ERR_CAPACITY, "cell bins overflowed (%d ids per cell); grown to %d, call compute() again", old_bin, h->bin_cap);
+        return fail(NNPOPS_ERR_CAPACITY, "cell bins overflowed (%d ids per cell); grown to %d, call compute() again", old_bin, h->cells.bin_cap);
     }
-    if (st[kStatOverflow] & 2) {
+    if (st[kStatOverflow] & kGridBoxTooSmall) {
         if (h->algorithm == 2)
             return fail(NNPOPS_ERR_UNSUPPORTED, "cell list forced but the periodic box is fewer than 3 cells wide on some axis");
         h->cells_disabled = true;
@@ -1313,11 +1276,7 @@ int nnpops_ani_read_grid(nnpops_ani_t h, int32_t* out) {
     NNPOPS_REQUIRE(h != nullptr && out != nullptr, "NULL argument");
     DeviceGuard guard(h->device);
     if (!guard.ok) return fail(NNPOPS_ERR_HIP, "cannot select device %d", h->device);
-    CellGrid g;
-    NNPOPS_HIP_TRY(hipMemcpyAsync(&g, h->d_grid, sizeof(CellGrid), hipMemcpyDeviceToHost, h->stream));
-    NNPOPS_HIP_TRY(hipStreamSynchronize(h->stream));
-    grid_words(g, out);
-    return NNPOPS_OK;
+    return h->cells.read_words(h->stream, out);
 }
 
 int nnpops_ani_describe(nnpops_ani_t h, char* text, int capacity) {

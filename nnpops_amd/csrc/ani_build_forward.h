@@ -91,7 +91,7 @@ __global__ __launch_bounds__(128, OCC) void ani_build_forward(const AniParams* _
         if (role == 0) {
             int na = 0, nro = 0;
             if (void_grid) {                                   // box too small for the stencil: tell the host
-                if (lane == 0 && slot_id == 0) atomicOr(&out.status[kStatOverflow], g.bin_overflow ? 6 : 2);   // 4: grow the cell bins
+                if (lane == 0 && slot_id == 0) atomicOr(&out.status[kStatOverflow], refused_grid_bits(g));
             } else if (in.use_cells) {
                 const int c = in.sorted_cell[slot_id];
                 int cx, cy, cz;

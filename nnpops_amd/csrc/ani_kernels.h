@@ -555,7 +555,7 @@ __global__ __launch_bounds__(64 * kWavesPerGroup) void ani_neighbors_cells(const
     const CellGrid g = *grid;
     if (!g.ok) {                                           // box too small for the stencil: tell the host
         if (lane == 0) {
-            if (slot_id == 0) atomicOr(&status[kStatOverflow], g.bin_overflow ? 6 : 2);   // 4: grow the cell bins
+            if (slot_id == 0) atomicOr(&status[kStatOverflow], refused_grid_bits(g));
             cnt_a[slot_id] = 0;                            // keep the consumers of this (void) build harmless
             cnt_ro[slot_id] = 0;
             cnt_pos[slot_id] = 0;

@@ -36,6 +36,14 @@ struct CellGrid {
     float bx, cx, cy;
 };
 
+// The grid's two bits of its consumer's overflow word (include/nnpops_hip.h), and what a consumer ORs into that word for a
+// grid g that refused to build (g.ok == 0).
+constexpr int kGridBoxTooSmall = 2;     // the stencil is invalid for this box: the owner switches to the all-pairs search
+constexpr int kGridBinOverflow = 4;     // ... because a bin of the two-kernel build overflowed: the owner grows the bins
+__device__ __forceinline__ int refused_grid_bits(const CellGrid& g) {
+    return g.bin_overflow ? (kGridBoxTooSmall | kGridBinOverflow) : kGridBoxTooSmall;
+}
+
 __device__ __forceinline__ void cell_of(const CellGrid& g, float x, float y, float z, int& cx, int& cy, int& cz) {
     // lattice coordinates of p = sx*a + sy*b + sz*c for the lower-triangular cell a=(ax,0,0), b=(bx,by,0),
     // c=(cx,cy,cz); for the non-periodic bounding box bx = cx = cy = 0 and the origin is its corner
@@ -52,7 +60,7 @@ __device__ __forceinline__ void cell_of(const CellGrid& g, float x, float y, flo
 
 // Linear cell index -> (cx, cy, cz) without an integer division: the quotient is estimated with v_rcp_f32 (1 ulp) in
 // float and corrected by one exact integer step.  The estimate alone is only a floor while c * 2e-7 < 1/2, i.e. below
-// ~2.7 M cells (max_cells = N + 4096 allows more, N up to 2^24 - 1); the correction makes it exact for every grid an
+// ~2.7 M cells (max_cells, CellList::cells_for(N), allows more: N up to 2^24 - 1); the correction makes it exact for every grid an
 // int can index: the estimate is off by at most one whenever the relative error times the QUOTIENT (<= nz, ny) is
 // below one.  Checked against c / n over whole grids of up to 16 M cells by tools/ubench/split_cell_check.hip.
 __device__ __forceinline__ void split_cell(const CellGrid& g, int c, int& cx, int& cy, int& cz) {
@@ -632,14 +640,14 @@ __device__ __forceinline__ void clear_cell_histogram(int* __restrict__ hist) {
     for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < kHistWords; c += stride) hist[c] = 0;
 }
 
-// Host side: the buffers of one grid and the launch sequence.
+// Host side: the buffers of one grid and the launch sequence (celllist_host.h: their sizes and their owner, CellList).
 struct CellBuffers {
-    CellGrid* grid;
-    int *cell_count, *cell_start;          // [max_cells], [max_cells + 1]
-    int *atom_cell, *atom_rank;            // [N]
-    int *unsorted_atom, *sorted_atom;      // [N]
-    float4* sorted_pos;                    // [N]
-    int max_cells;
+    CellGrid* grid = nullptr;
+    int *cell_count = nullptr, *cell_start = nullptr;          // [max_cells], [max_cells + 1]
+    int *atom_cell = nullptr, *atom_rank = nullptr;            // [N]
+    int *unsorted_atom = nullptr, *sorted_atom = nullptr;      // [N]
+    float4* sorted_pos = nullptr;                              // [N]
+    int max_cells = 0;
     // two-kernel path (optional): a zero-initialised histogram of kHistWords ints that the consumer kernel
     // clears again after every build, and bins of kBinnedCells * bin_cap ints
     int* hist = nullptr;
@@ -647,7 +655,7 @@ struct CellBuffers {
     int bin_cap = 0;
     int fine = 0;                          // 1: prefer half-cutoff cells (decide_grid); only for consumers that read CellGrid::m
     int* sorted_cell = nullptr;            // [N] optional: cell of the atom in every sorted slot
-    int* tile_total = nullptr;             // [max_cells / 8192 + 1] optional: lets grids of more than 8192 cells scan in parallel
+    int* tile_total = nullptr;             // [CellList::tile_total_len] optional: lets grids of more than 8192 cells scan in parallel
 };
 
 // What the read_grid entry points of the consumers report (include/nnpops_hip.h): a host copy of the grid, as eight ints.

@@ -40,11 +40,11 @@
 #include <vector>
 
 #include "cfconv_box_grad.h"
+#include "celllist_host.h"
 #include "cfconv_build.h"
 #include "cfconv_fallback_kernels.h"
 #include "cfconv_filters.h"
 #include "cfconv_second_order.h"
-#include "host_common.h"
 
 using namespace nnpops;
 
@@ -70,16 +70,7 @@ struct nnpops_cfconv_neighbors {
     float4* d_rows = nullptr;
     int* d_cnt = nullptr;
     int* d_status = nullptr;
-    // cell grid
-    CellGrid* d_grid = nullptr;
-    int *d_cell_count = nullptr, *d_cell_start = nullptr, *d_atom_cell = nullptr, *d_atom_rank = nullptr;
-    int* d_sorted_cell = nullptr;   // [N] cell of the atom in every sorted slot (rows_cells reads it with the slot's position)
-    int *d_unsorted = nullptr, *d_sorted = nullptr;
-    float4* d_sorted_pos = nullptr;
-    int max_cells = 0;
-    int* d_hist = nullptr;          // two-kernel cell build (celllist.h)
-    int* d_bins = nullptr;
-    int bin_cap = 64;
+    CellList cells;                 // cell grid (rows_cells reads sorted_cell with the slot's position)
     // half list behind the rows (scan_half / half_slots): built with the rows once a matrix-core convolution has
     // asked for it, on demand before that
     int *d_lo_cnt = nullptr, *d_half_off = nullptr, *d_pid = nullptr, *d_ids = nullptr;
@@ -87,7 +78,7 @@ struct nnpops_cfconv_neighbors {
     int2* d_half_ij = nullptr;
     bool want_half = false, half_built = false;
     unsigned long long epoch = 0;      // number of the last build (process-wide counter): what a convolution keeps per list (its filter rows) is valid for one build
-    bool cell_ordered = false;      // the last build went through the cell grid: d_sorted_pos lists the atoms in cell order
+    bool cell_ordered = false;      // the last build went through the cell grid: cells.sorted_pos lists the atoms in cell order
     int pair_cap() const { return (int)std::min<size_t>((size_t)N * cap / 2, (size_t)INT32_MAX - 1); }
 };
 
@@ -109,7 +100,7 @@ static int alloc_half(nnpops_cfconv_neighbors* h) {
 
 // the two launches behind the rows that give every pair its slot
 static int launch_half_build(nnpops_cfconv_neighbors* h, hipStream_t stream) {
-    const float4* order = h->cell_ordered ? h->d_sorted_pos : nullptr;
+    const float4* order = h->cell_ordered ? h->cells.sorted_pos : nullptr;
     hipLaunchKernelGGL(scan_half, dim3(1), dim3(1024), 0, stream, h->N, h->d_lo_cnt, h->d_half_off);
     hipLaunchKernelGGL(half_slots, dim3(h->N), dim3(64), 0, stream, h->d_rows, h->d_ids, h->d_cnt, h->d_half_off, h->cap, h->pair_cap(),
                        h->d_pid, h->d_half_r, h->d_half_ij, h->d_status, h->N, order);
@@ -172,33 +163,18 @@ int nnpops_cfconv_neighbors_create(nnpops_cfconv_neighbors_t* out, int num_atoms
     NNPOPS_REQUIRE(device >= 0 && device < ndev, "device %d out of range (have %d)", device, ndev);
     auto* h = new nnpops_cfconv_neighbors();
     h->N = num_atoms; h->cutoff = cutoff; h->periodic = periodic != 0; h->device = device;
-    h->max_cells = num_atoms + 4096;
     DeviceGuard guard(device);
     int rc;
     auto cleanup = [&](int code) { nnpops_cfconv_neighbors_destroy(h); return code; };
     if ((rc = dev_alloc(&h->d_rows, (size_t)num_atoms * h->cap))) return cleanup(rc);
     if ((rc = dev_alloc(&h->d_cnt, (size_t)num_atoms))) return cleanup(rc);
     if ((rc = dev_alloc(&h->d_status, (size_t)kStWordsN))) return cleanup(rc);
-    if ((rc = dev_alloc(&h->d_grid, 1))) return cleanup(rc);
-    if ((rc = dev_alloc(&h->d_cell_count, (size_t)h->max_cells))) return cleanup(rc);
-    if ((rc = dev_alloc(&h->d_cell_start, (size_t)h->max_cells + 1))) return cleanup(rc);
-    if (const char* e = std::getenv("NNPOPS_CELL_BIN_CAP")) h->bin_cap = std::max(4, std::atoi(e) & ~3);   // tests: force growth
-    if (periodic && num_atoms <= kBinnedAtoms) {
-        if ((rc = dev_alloc(&h->d_hist, (size_t)kHistWords))) return cleanup(rc);
-        if ((rc = dev_alloc(&h->d_bins, (size_t)kBinnedCells * h->bin_cap))) return cleanup(rc);
-        if (hipMemset(h->d_hist, 0, sizeof(int) * kHistWords) != hipSuccess) return cleanup(fail(NNPOPS_ERR_HIP, "memset failed"));
-    }
+    if ((rc = h->cells.allocate(num_atoms, h->periodic, /*tiled_scan=*/false))) return cleanup(rc);     // (one-block scan at every size)
     if ((rc = dev_alloc(&h->d_lo_cnt, (size_t)num_atoms))) return cleanup(rc);
     if ((rc = dev_alloc(&h->d_half_off, (size_t)num_atoms + 1))) return cleanup(rc);
     if (hipMemset(h->d_lo_cnt, 0, sizeof(int) * num_atoms) != hipSuccess || hipMemset(h->d_half_off, 0, sizeof(int) * ((size_t)num_atoms + 1)) != hipSuccess)
         return cleanup(fail(NNPOPS_ERR_HIP, "memset failed"));
     if ((rc = alloc_half(h))) return cleanup(rc);
-    if ((rc = dev_alloc(&h->d_atom_cell, (size_t)num_atoms))) return cleanup(rc);
-    if ((rc = dev_alloc(&h->d_atom_rank, (size_t)num_atoms))) return cleanup(rc);
-    if ((rc = dev_alloc(&h->d_sorted_cell, (size_t)num_atoms))) return cleanup(rc);
-    if ((rc = dev_alloc(&h->d_unsorted, (size_t)num_atoms))) return cleanup(rc);
-    if ((rc = dev_alloc(&h->d_sorted, (size_t)num_atoms))) return cleanup(rc);
-    if ((rc = dev_alloc(&h->d_sorted_pos, (size_t)num_atoms))) return cleanup(rc);
     if (hipMemset(h->d_cnt, 0, sizeof(int) * num_atoms) != hipSuccess || hipMemset(h->d_status, 0, sizeof(int) * kStWordsN) != hipSuccess)
         return cleanup(fail(NNPOPS_ERR_HIP, "memset failed"));
     *out = h;
@@ -209,10 +185,8 @@ int nnpops_cfconv_neighbors_destroy(nnpops_cfconv_neighbors_t h) {
     if (!h) return NNPOPS_OK;
     DeviceGuard guard(h->device);
     dev_free(h->d_rows); dev_free(h->d_cnt); dev_free(h->d_status);
-    dev_free(h->d_hist); dev_free(h->d_bins);
     dev_free(h->d_lo_cnt); dev_free(h->d_half_off); dev_free(h->d_pid); dev_free(h->d_half_r); dev_free(h->d_half_ij); dev_free(h->d_ids);
-    dev_free(h->d_grid); dev_free(h->d_cell_count); dev_free(h->d_cell_start); dev_free(h->d_atom_cell);
-    dev_free(h->d_atom_rank); dev_free(h->d_sorted_cell); dev_free(h->d_unsorted); dev_free(h->d_sorted); dev_free(h->d_sorted_pos);
+    h->cells.release();
     delete h;
     return NNPOPS_OK;
 }
@@ -234,16 +208,14 @@ int nnpops_cfconv_neighbors_build(nnpops_cfconv_neighbors_t h, const float* posi
     // status words are cleared by create() and by check() after it has read them, not per build
     const bool use_cells = N >= 1024 && !h->cells_disabled;
     if (use_cells) {
-        CellBuffers cb{h->d_grid, h->d_cell_count, h->d_cell_start, h->d_atom_cell, h->d_atom_rank, h->d_unsorted,
-                       h->d_sorted, h->d_sorted_pos, h->max_cells, h->d_hist, h->d_bins, h->bin_cap};
-        cb.sorted_cell = h->d_sorted_cell;
-        launch_cell_build(h->stream, N, positions, box, per, h->cutoff, nullptr, cb);
+        const CellList& g = h->cells;
+        launch_cell_build(h->stream, N, positions, box, per, h->cutoff, nullptr, g);
         if (per)
-            hipLaunchKernelGGL(rows_cells<true>, dim3(N), dim3(64), 0, h->stream, box, c2, h->d_grid, h->d_cell_start,
-                               h->d_sorted_cell, h->d_sorted_pos, h->d_rows, h->d_ids, h->cap, h->d_cnt, h->d_lo_cnt, h->d_status, h->d_hist);
+            hipLaunchKernelGGL(rows_cells<true>, dim3(N), dim3(64), 0, h->stream, box, c2, g.grid, g.cell_start,
+                               g.sorted_cell, g.sorted_pos, h->d_rows, h->d_ids, h->cap, h->d_cnt, h->d_lo_cnt, h->d_status, g.hist);
         else
-            hipLaunchKernelGGL(rows_cells<false>, dim3(N), dim3(64), 0, h->stream, box, c2, h->d_grid, h->d_cell_start,
-                               h->d_sorted_cell, h->d_sorted_pos, h->d_rows, h->d_ids, h->cap, h->d_cnt, h->d_lo_cnt, h->d_status, h->d_hist);
+            hipLaunchKernelGGL(rows_cells<false>, dim3(N), dim3(64), 0, h->stream, box, c2, g.grid, g.cell_start,
+                               g.sorted_cell, g.sorted_pos, h->d_rows, h->d_ids, h->cap, h->d_cnt, h->d_lo_cnt, h->d_status, g.hist);
     } else if (per) {
         hipLaunchKernelGGL(rows_allpairs<true>, dim3(N), dim3(64), 0, h->stream, N, positions, box, c2, h->d_rows, h->d_ids, h->cap, h->d_cnt, h->d_lo_cnt);
     } else {
@@ -278,17 +250,14 @@ int nnpops_cfconv_neighbors_check(nnpops_cfconv_neighbors_t h, int* num_pairs) {
     NNPOPS_HIP_TRY(hipMemsetAsync(h->d_status, 0, sizeof(int) * kStWordsN, h->stream));   // consumed: builds do not clear it
     NNPOPS_HIP_TRY(hipStreamSynchronize(h->stream));
     if (num_pairs) *num_pairs = st[kStPairs];
-    if (st[kStOverflow] & 4) {            // a cell holds more atoms than a bin of the two-kernel grid build: grow the bins
-        const int old_bin = h->bin_cap;
-        h->bin_cap *= 2;
-        dev_free(h->d_bins);
-        h->d_bins = nullptr;
-        int rc = dev_alloc(&h->d_bins, (size_t)kBinnedCells * h->bin_cap);
+    if (st[kStOverflow] & kGridBinOverflow) {      // a cell holds more atoms than a bin of the two-kernel grid build: grow the bins
+        int old_bin;
+        int rc = h->cells.grow_bins(&old_bin);
         if (rc != NNPOPS_OK) return rc;
         h->built = false;
-        return fail(NNPOPS_ERR_CAPACITY, "cell bins overflowed (%d ids per cell); grown to %d, call build() again", old_bin, h->bin_cap);
+        return fail(NNPOPS_ERR_CAPACITY, "cell bins overflowed (%d ids per cell); grown to %d, call build() again", old_bin, h->cells.bin_cap);
     }
-    if (st[kStOverflow] & 2) {
+    if (st[kStOverflow] & kGridBoxTooSmall) {
         h->cells_disabled = true;
         h->built = false;
         return fail(NNPOPS_ERR_CAPACITY, "periodic box is fewer than 3 cells wide on some axis: switched to the all-pairs "
@@ -312,11 +281,7 @@ int nnpops_cfconv_neighbors_check(nnpops_cfconv_neighbors_t h, int* num_pairs) {
 int nnpops_cfconv_neighbors_read_grid(nnpops_cfconv_neighbors_t h, int32_t* out) {
     NNPOPS_REQUIRE(h != nullptr && out != nullptr, "NULL argument");
     DeviceGuard guard(h->device);
-    CellGrid g;
-    NNPOPS_HIP_TRY(hipMemcpyAsync(&g, h->d_grid, sizeof(CellGrid), hipMemcpyDeviceToHost, h->stream));
-    NNPOPS_HIP_TRY(hipStreamSynchronize(h->stream));
-    grid_words(g, out);
-    return NNPOPS_OK;
+    return h->cells.read_words(h->stream, out);
 }
 
 int nnpops_cfconv_neighbors_export(nnpops_cfconv_neighbors_t h, int capacity, int32_t* pair_atoms, float* distances) {
@@ -667,7 +632,7 @@ int launch_half(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, const float* x, c
     else { h->filt_list = nb; h->filt_epoch = nb->epoch; }
     const int N = h->p.N;
     const float* v = BWD ? gout : x;
-    const float4* order = nb->cell_ordered ? nb->d_sorted_pos : nullptr;
+    const float4* order = nb->cell_ordered ? nb->cells.sorted_pos : nullptr;
     if (h->p.W == 128)
         hipLaunchKernelGGL((cfconv_gather<BWD, true>), dim3(div_up(N, 4)), dim3(256), 0, h->stream, N, h->p.W, nb->d_rows, nb->d_cnt,
                            nb->cap, nb->d_pid, pair_cap, h->d_filt, h->d_pair_s, v, out, pos_grad, order);
@@ -729,7 +694,7 @@ int launch_second_mfma(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, const floa
         NNPOPS_HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const int blocks = std::max(1, std::min(h->blocks, div_up(h->p.N, wpb)));
     hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * wpb), lds, h->stream, h->p, h->d_w1t, h->d_b1, h->d_w2t, h->d_b2, nb->d_rows, nb->d_cnt,
-                       nb->cap, nb->cell_ordered ? nb->d_sorted_pos : (const float4*)nullptr, x, g, V, Q, out_g, out_x, out_pos);
+                       nb->cap, nb->cell_ordered ? nb->cells.sorted_pos : (const float4*)nullptr, x, g, V, Q, out_g, out_x, out_pos);
     NNPOPS_HIP_TRY(hipGetLastError());
     return NNPOPS_OK;
 }
@@ -748,7 +713,7 @@ int launch_second_vector(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, const fl
         NNPOPS_HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const int blocks = std::max(1, std::min(h->blocks, div_up(h->p.N, wpb)));
     hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * wpb), lds, h->stream, h->p, h->d_w1t, h->d_b1, h->d_w2t, h->d_b2, nb->d_rows, nb->d_cnt,
-                       nb->cap, nb->cell_ordered ? nb->d_sorted_pos : (const float4*)nullptr, x, g, V, Q, out_g, out_x, out_pos);
+                       nb->cap, nb->cell_ordered ? nb->cells.sorted_pos : (const float4*)nullptr, x, g, V, Q, out_g, out_x, out_pos);
     NNPOPS_HIP_TRY(hipGetLastError());
     return NNPOPS_OK;
 }
@@ -830,7 +795,7 @@ int nnpops_cfconv_backprop_box(nnpops_cfconv_t h, nnpops_cfconv_neighbors_t neig
     if (row_s && (rc = launch_vector<true, true>(h, neighbors, input, output_deriv, nullptr, nullptr)) != NNPOPS_OK) return rc;
     // ... then one pass over the rows and the pair scalars it left behind, and the sum of its workgroups (cfconv_box_grad.h)
     const int N = h->p.N, nblocks = cfconv_box_blocks(N);
-    const float4* order = neighbors->cell_ordered ? neighbors->d_sorted_pos : nullptr;
+    const float4* order = neighbors->cell_ordered ? neighbors->cells.sorted_pos : nullptr;
     if (row_s)
         hipLaunchKernelGGL(cfconv_box_partials<true>, dim3(nblocks), dim3(kBoxThreads), 0, h->stream, N, positions, box, neighbors->d_rows,
                            neighbors->d_cnt, neighbors->cap, (const int*)nullptr, 0, (const float*)h->d_row_s, order, h->d_box_partials);

@@ -71,7 +71,7 @@ __global__ __launch_bounds__(64) void rows_cells(const float* __restrict__ box, 
     const CellGrid g = *grid;
     if (!g.ok) {
         if (lane == 0) {
-            if (blockIdx.x == 0) atomicOr(&status[kStOverflow], g.bin_overflow ? 6 : 2);   // 4: grow the cell bins
+            if (blockIdx.x == 0) atomicOr(&status[kStOverflow], refused_grid_bits(g));
             publish_row((int)blockIdx.x, 0, 0, cnt, lo_cnt);
         }
         return;

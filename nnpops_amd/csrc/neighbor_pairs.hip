@@ -22,8 +22,7 @@
 #include <cmath>
 #include <limits>
 
-#include "celllist.h"
-#include "host_common.h"
+#include "celllist_host.h"
 
 using namespace nnpops;
 
@@ -526,21 +525,13 @@ struct Workspace {
     int* row_count;
     int* row_offset;
     int* block_prefix;    // [ceil(N/1024) + 1] + the scan's ticket counter behind it
-    CellGrid* grid;
-    int* cell_count;
-    int* cell_start;
-    int* atom_cell;
-    int* atom_rank;
-    int* unsorted_atom;
-    int* sorted_atom;
-    float4* sorted_pos;
+    // The grid's arrays (no sorted_cell).  hist [kHistWords] and bins [kBinnedCells][kPairsBinCap] of the two-launch build are
+    // carved for periodic and non-periodic calls alike: forward_impl drops them from the copy it builds with where the call
+    // takes the five-launch build, and zeroes hist where it does not.
+    CellBuffers cells;
     float* fpos;
     int* st_col;          // [N][kStageCap]
     void* st_rec;         // [N][kStageCap] Staged<T> (sized for double)
-    int* hist;            // [kHistWords] two-launch grid build (periodic systems of up to kPairsBinnedAtoms atoms), zeroed by every call
-    int* bins;            // [kBinnedCells][kPairsBinCap]
-    int* tile_total;      // [max_cells / kScanTile + 2] partial sums of the tiled cell scan (grids of more than 8 192 cells)
-    int max_cells;
 };
 
 size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -548,28 +539,30 @@ size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 size_t carve(Workspace* w, char* base, int N) {
     size_t off = 0;
     auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes); return p; };
-    const int max_cells = N + 4096;
+    const int max_cells = CellList::cells_for(N);
     Workspace tmp;
-    tmp.max_cells = max_cells;
+    CellBuffers& g = tmp.cells;
+    g.max_cells = max_cells;
     tmp.row_count = (int*)take(sizeof(int) * ((size_t)N + 1));
     tmp.row_offset = (int*)take(sizeof(int) * ((size_t)N + 1));
     tmp.block_prefix = (int*)take(sizeof(int) * ((size_t)N / 1024 + 4));
-    tmp.grid = (CellGrid*)take(sizeof(CellGrid));
-    tmp.cell_count = (int*)take(sizeof(int) * (size_t)max_cells);
-    tmp.cell_start = (int*)take(sizeof(int) * ((size_t)max_cells + 1));
-    tmp.atom_cell = (int*)take(sizeof(int) * (size_t)N);
-    tmp.atom_rank = (int*)take(sizeof(int) * (size_t)N);
-    tmp.unsorted_atom = (int*)take(sizeof(int) * (size_t)N);
-    tmp.sorted_atom = (int*)take(sizeof(int) * (size_t)N);
-    tmp.sorted_pos = (float4*)take(sizeof(float4) * (size_t)N);
+    g.grid = (CellGrid*)take(sizeof(CellGrid));
+    g.cell_count = (int*)take(sizeof(int) * (size_t)max_cells);
+    g.cell_start = (int*)take(sizeof(int) * ((size_t)max_cells + 1));
+    g.atom_cell = (int*)take(sizeof(int) * (size_t)N);
+    g.atom_rank = (int*)take(sizeof(int) * (size_t)N);
+    g.unsorted_atom = (int*)take(sizeof(int) * (size_t)N);
+    g.sorted_atom = (int*)take(sizeof(int) * (size_t)N);
+    g.sorted_pos = (float4*)take(sizeof(float4) * (size_t)N);
     tmp.fpos = (float*)take(sizeof(float) * 3 * (size_t)N);
     const bool staged = N >= kCellThreshold;          // only the cell-grid path stages rows
     tmp.st_col = (int*)take(staged ? sizeof(int) * (size_t)N * kStageCap : 0);
     tmp.st_rec = (void*)take(staged ? sizeof(Staged<double>) * (size_t)N * kStageCap : 0);
     const bool binned = staged && N <= kPairsBinnedAtoms;
-    tmp.hist = (int*)take(binned ? sizeof(int) * kHistWords : 0);
-    tmp.bins = (int*)take(binned ? sizeof(int) * (size_t)kBinnedCells * kPairsBinCap : 0);
-    tmp.tile_total = (int*)take(sizeof(int) * ((size_t)max_cells / kScanTile + 2));
+    g.hist = (int*)take(binned ? sizeof(int) * kHistWords : 0);
+    g.bins = (int*)take(binned ? sizeof(int) * (size_t)kBinnedCells * kPairsBinCap : 0);
+    g.bin_cap = kPairsBinCap;
+    g.tile_total = (int*)take(sizeof(int) * CellList::tile_total_len(max_cells));
     if (w) *w = tmp;
     return off;
 }
@@ -612,7 +605,7 @@ int forward_impl(int N, const T* pos, const T* box, double cutoff, long long max
             fpos = w.fpos;
         }
         const float* fbox = nullptr;
-        float* fbox_dev = (float*)w.sorted_pos;      // reuse: sorted_pos is not needed by the pair kernels
+        float* fbox_dev = (float*)w.cells.sorted_pos;      // reuse: sorted_pos is not needed by the pair kernels
         if (periodic) {
             if (sizeof(T) == 8) {
                 hipLaunchKernelGGL(to_float_positions<T>, dim3(1), dim3(64), 0, stream, 9, box, fbox_dev);
@@ -622,9 +615,7 @@ int forward_impl(int N, const T* pos, const T* box, double cutoff, long long max
             }
         }
         // (the grid also emits cell-ordered positions; they land in scratch this op does not otherwise use)
-        CellBuffers cb{w.grid, w.cell_count, w.cell_start, w.atom_cell, w.atom_rank, w.unsorted_atom, w.sorted_atom,
-                       w.sorted_pos, w.max_cells};
-        cb.tile_total = w.tile_total;
+        CellBuffers cb = w.cells;
         // A periodic system of up to kPairsBinnedAtoms atoms takes the two-launch grid of the stateful handles (celllist.h:
         // bin_atoms + order_binned) behind ONE memset of its 32 KiB histogram -- three launches where grid_setup / assign_cells /
         // scan_cells / fill_cells / order_cells are five (round 4; the workspace is the caller's and arrives dirty, so the
@@ -635,21 +626,21 @@ int forward_impl(int N, const T* pos, const T* box, double cutoff, long long max
         // scan is tiled) -- the grid costs ~6 us more there and pairs_cells_stage ~35 us less (100 000 atoms).
         const bool fine = !(std::getenv("NNPOPS_PAIRS_FINE_GRID") && std::atoi(std::getenv("NNPOPS_PAIRS_FINE_GRID")) == 0);
         cb.fine = fine ? 1 : 0;
-        if (periodic && N <= (fine ? kPairsFineBinnedAtoms : kPairsBinnedAtoms)) {
-            hipLaunchKernelGGL(zero_words, dim3(div_up(kHistWords, 256)), dim3(256), 0, stream, (long long)kHistWords, w.hist);
-            cb.hist = w.hist; cb.bins = w.bins; cb.bin_cap = kPairsBinCap;
-        }
+        if (periodic && N <= (fine ? kPairsFineBinnedAtoms : kPairsBinnedAtoms))
+            hipLaunchKernelGGL(zero_words, dim3(div_up(kHistWords, 256)), dim3(256), 0, stream, (long long)kHistWords, cb.hist);
+        else
+            cb.hist = cb.bins = nullptr;               // (the five-launch build)
         launch_cell_build(stream, N, fpos, fbox, periodic != 0, (float)cutoff, nullptr, cb);
         const dim3 rgrid(div_up(N, 4)), rblock(256);       // one wave per row
         Staged<T>* st_rec = (Staged<T>*)w.st_rec;
         const int periodic_flags = periodic | ((periodic && std::getenv("NNPOPS_PAIRS_DIVIDE") && std::atoi(std::getenv("NNPOPS_PAIRS_DIVIDE"))) ? 2 : 0) |
                                    ((periodic && std::getenv("NNPOPS_PAIRS_TIE_TEST") && std::atoi(std::getenv("NNPOPS_PAIRS_TIE_TEST"))) ? 4 : 0);      // (4: keep the tie test, A/B)
-        hipLaunchKernelGGL(pairs_cells_stage<T>, rgrid, rblock, 0, stream, N, pos, box, periodic_flags, cutoff2, w.grid, w.cell_start,
-                           w.atom_cell, w.sorted_atom, w.sorted_pos, w.st_col, st_rec, w.row_count, ticket);
+        hipLaunchKernelGGL(pairs_cells_stage<T>, rgrid, rblock, 0, stream, N, pos, box, periodic_flags, cutoff2, cb.grid, cb.cell_start,
+                           cb.atom_cell, cb.sorted_atom, cb.sorted_pos, w.st_col, st_rec, w.row_count, ticket);
         hipLaunchKernelGGL(scan_rows, dim3(nscan), dim3(kScanBlock), 0, stream, N, w.row_count, w.row_offset, w.block_prefix, ticket,
                            num_pairs);
-        hipLaunchKernelGGL(pairs_cells_emit<T>, rgrid, rblock, 0, stream, N, pos, box, periodic_flags, cutoff2, num_slots, w.grid,
-                           w.cell_start, w.atom_cell, w.sorted_atom, w.sorted_pos, w.st_col, st_rec, w.row_count, w.row_offset,
+        hipLaunchKernelGGL(pairs_cells_emit<T>, rgrid, rblock, 0, stream, N, pos, box, periodic_flags, cutoff2, num_slots, cb.grid,
+                           cb.cell_start, cb.atom_cell, cb.sorted_atom, cb.sorted_pos, w.st_col, st_rec, w.row_count, w.row_offset,
                            w.block_prefix, neighbors, deltas, distances);
     } else {
         hipLaunchKernelGGL((pairs_allpairs<T, 0, false>), dim3(N), dim3(64), 0, stream, N, pos, box, periodic, cutoff2, num_slots,
@@ -717,11 +708,7 @@ int nnpops_neighbor_pairs_read_grid(const void* workspace, int num_atoms, void* 
     NNPOPS_REQUIRE(num_atoms > 0, "num_atoms must be positive");
     Workspace w;
     carve(&w, (char*)const_cast<void*>(workspace), num_atoms);      // (the layout the forward call used)
-    CellGrid g;
-    NNPOPS_HIP_TRY(hipMemcpyAsync(&g, w.grid, sizeof(CellGrid), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    NNPOPS_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    grid_words(g, out);
-    return NNPOPS_OK;
+    return read_grid_words(w.cells.grid, (hipStream_t)stream, out);
 }
 
 int64_t nnpops_neighbor_pairs_backward_workspace_bytes(int num_atoms) {
