@@ -588,6 +588,14 @@ typedef struct {
      * (nnpops_mlp_energy_mean_segments below) -- mean_out / mean_out_shifted then hold num_segments values.  segment_offsets
      * [num_segments + 1] and segment_positions [sum of num_atoms] are device arrays; NULL / 0: one mean over everything. */
     const int32_t* segment_offsets; const int32_t* segment_positions; int num_segments;
+    /* Optional, honoured by nnpops_mlp_input_grad on both of its paths: one upstream weight per (molecule, member), a device table
+     * [num_segments or 1][member_weights_ld] with member_weights_ld >= num_members.  dx is then the gradient of
+     * sum_b sum_m member_weights[b][m] * E_m(molecule b) -- member m's share W_0m^T dE_m/dy1 times the weight of the atom's molecule,
+     * members in their fixed order -- instead of the gradient of the plain sum over the members (upstream and dx_scale still multiply
+     * it).  The atom's molecule is found from segment_offsets / num_segments, which may then be given without the means and without
+     * segment_positions; without them every row belongs to molecule 0.  A member whose weight is zero is SKIPPED: its share is not
+     * added, whatever it holds.  At most 128 members.  NULL / 0: every weight is 1, as before. */
+    const float* member_weights; int member_weights_ld;
 } nnpops_mlp_frame;
 int64_t nnpops_mlp_packed_halves(int rows, int cols);
 int64_t nnpops_mlp_d1_halves(int num_atoms, int num_members, int h1);
@@ -619,6 +627,17 @@ int nnpops_mlp_energy_mean_segments(void* stream, const float* energies, int num
 int nnpops_mlp_energy_mean_segments_shifted(void* stream, const float* energies, int num_atoms, int num_members,
                                             const int32_t* molecule_offsets, int num_molecules, const int32_t* positions, float scale,
                                             const double* shift, double* out);
+/* The energy of every ensemble member, molecule by molecule: out[b][m] = sum over the atoms a of molecule b of
+ * energies[positions[a]][m], a device [num_molecules][num_members] array (tables as for nnpops_mlp_energy_mean_segments; with
+ * molecule_offsets and positions both NULL and num_molecules 1 everything is one molecule in the order it lies in).  One wave per
+ * molecule: lane l adds the atoms l, l + 64, ... of the molecule, every member into a float64 accumulator of its own, and the lane sums
+ * meet in the fixed butterfly of the means -- a value depends on the molecule's own atoms only, not on the batch or the molecule's
+ * place in it. */
+int nnpops_mlp_member_sums(void* stream, const float* energies, int num_atoms, int num_members, const int32_t* molecule_offsets,
+                           int num_molecules, const int32_t* positions, float* out);
+/* ... promoted and shifted: out[b][m] = (double)(float)sum + shift[0], device doubles. */
+int nnpops_mlp_member_sums_shifted(void* stream, const float* energies, int num_atoms, int num_members, const int32_t* molecule_offsets,
+                                   int num_molecules, const int32_t* positions, const double* shift, double* out);
 /* out[row][0..2] = in[row][0..2] * (float)factors[molecule of row] for the num_atoms rows of a batch of molecules (offsets as above);
  * `factors` is a DEVICE array of num_molecules doubles when factor_is_double != 0, floats otherwise.  The backward of the batched
  * one-node step: every molecule's kept forces times its own upstream gradient, in one launch. */

@@ -76,6 +76,18 @@ class _BatchedNN(nn.Module):
         energies = torch.sum(v, (1, 2, 3, 4)) / v.shape[2]
         return SpeciesEnergies(species, energies)
 
+    @torch.jit.unused
+    def members_energies(self, species_aev: Tuple[Tensor, Tensor]) -> SpeciesEnergies:
+        """The same reduction without the sum over the models: energies [models, molecules] (TorchANI's ``members_energies``)."""
+        species, aev = species_aev
+        linear = torch.ops.NNPOpsBatchedNN.BatchedLinear
+        v = aev.unsqueeze(-2).unsqueeze(-1)
+        v = F.celu(linear(v, self.layer0_weights, self.layer0_biases), alpha=0.1)
+        v = F.celu(linear(v, self.layer2_weights, self.layer2_biases), alpha=0.1)
+        v = F.celu(linear(v, self.layer4_weights, self.layer4_biases), alpha=0.1)
+        v = linear(v, self.layer6_weights, self.layer6_biases)
+        return SpeciesEnergies(species, torch.sum(v, (1, 3, 4)).t())
+
 
 class _SpeciesGroupedNN(nn.Module):
     """Same function, MI355X layout: atoms are grouped by species once (the species of a Holder never change),
@@ -120,6 +132,28 @@ class _SpeciesGroupedNN(nn.Module):
 
     def forward(self, species_aev: Tuple[Tensor, Tensor]) -> SpeciesEnergies:
         return self._grouped_forward(species_aev)
+
+    @torch.jit.unused
+    def members_energies(self, species_aev: Tuple[Tensor, Tensor]) -> SpeciesEnergies:
+        """Every model's energy, energies [models, molecules] (TorchANI's ``members_energies``): plain torch, twice differentiable."""
+        species, aev = species_aev
+        mols = aev.shape[0]
+        x = aev.index_select(1, self.atom_order)
+        num_models = self.layer0_weights.shape[1]
+        energies = torch.zeros((num_models, mols), dtype=aev.dtype, device=aev.device)
+        first = 0
+        for kind, n in enumerate(self.group_sizes):                         # (the layers of _grouped_forward; the models are kept apart)
+            xs = x[:, first:first + n].reshape(mols * n, -1).t()
+            first += n
+            cols = mols * n
+            w0, b0 = self.layer0_weights[kind], self.layer0_biases[kind]
+            v = torch.addmm(b0.reshape(-1, 1), w0.reshape(-1, w0.shape[2]), xs).reshape(num_models, w0.shape[1], cols)
+            v = F.celu(v, alpha=0.1)
+            v = F.celu(torch.baddbmm(self.layer2_biases[kind].expand(-1, -1, cols), self.layer2_weights[kind], v), alpha=0.1)
+            v = F.celu(torch.baddbmm(self.layer4_biases[kind].expand(-1, -1, cols), self.layer4_weights[kind], v), alpha=0.1)
+            v = torch.baddbmm(self.layer6_biases[kind].expand(-1, -1, cols), self.layer6_weights[kind], v)
+            energies = energies + v.reshape(num_models, -1, mols, n).sum((1, 3))
+        return SpeciesEnergies(species, energies)
 
     def _grouped_forward(self, species_aev: Tuple[Tensor, Tensor]) -> SpeciesEnergies:
         species, aev = species_aev
@@ -322,6 +356,31 @@ class _FusedSpeciesNN(_SpeciesGroupedNN):
                                                    self.mlp_planes, self.mlp_floats, self.act_scale_log2)
         return SpeciesEnergies(species, total / self.num_models)
 
+    @torch.jit.unused
+    def fused_members(self, aev: Tensor, shift: Optional[Tensor] = None, batch: Optional[Tuple[Tensor, List[int], Tensor, Tensor]] = None) -> Tensor:
+        """Every member's energy of the molecule(s) behind ``aev`` [atoms, features] (float32, on the device) as ONE autograd node
+        (``torch.ops.NNPOpsBatchedNN.FusedMLPMembers``): -> [molecules, members], float32, or float64 and shifted with ``shift``.  Its
+        backward is one launch of the networks' input gradient weighted by the upstream gradient of every (molecule, member); a
+        zero there skips the member.  ``batch``: (rows, group sizes, places, offsets) of a conformer batch (``_batch_plan``).  Inside
+        OptimizedTorchANI the networks run over the live column blocks, as in ``fused_energy``."""
+        if not self.fused_ok:        # (a state dict loaded since construction: the weights no longer bound the fp16 operands)
+            raise RuntimeError("the loaded weights exceed the activation bound of the fused network kernels (BatchedNN.py: fused_ok); "
+                               "build the model with OptimizedTorchANI(..., fused_step=False) or nn_layout='grouped'")
+        rows, sizes, places, offsets = batch if batch is not None else (self.atom_order32, self.group_sizes, None, None)
+        if self.x_blocks.numel() > 0:
+            return torch.ops.NNPOpsBatchedNN.FusedMLPMembers(aev, rows, sizes, self.widths, self.num_models, self.live_planes, self.mlp_floats,
+                                                             self.x_blocks, self.dead_blocks, self.act_scale_log2, offsets, places, shift)
+        return torch.ops.NNPOpsBatchedNN.FusedMLPMembers(aev, rows, sizes, self.widths, self.num_models, self.mlp_planes, self.mlp_floats,
+                                                         None, None, self.act_scale_log2, offsets, places, shift)
+
+    @torch.jit.unused
+    def members_energies(self, species_aev: Tuple[Tensor, Tensor]) -> SpeciesEnergies:
+        species, aev = species_aev
+        if (aev.shape[0] != 1 or not aev.is_cuda or aev.dtype != torch.float32 or self.mlp_planes.dtype != torch.float16
+                or self.atom_order32.dtype != torch.int32 or not self.fused_ok or self.x_blocks.numel() > 0):
+            return _SpeciesGroupedNN.members_energies(self, species_aev)    # (live blocks: only the positions of OptimizedTorchANI vouch for them)
+        return SpeciesEnergies(species, self.fused_members(aev[0].contiguous()).t())
+
     def set_check_interval(self, interval: int) -> None:
         """(inside OptimizedTorchANI) how often the AEV holder behind fused_energy() verifies its neighbour capacities."""
         self.holder.set_check_interval(interval)
@@ -491,6 +550,14 @@ class TorchANIBatchedNN(nn.ModuleList):
 
     def forward(self, species_aev: Tuple[Tensor, Tensor]) -> SpeciesEnergies:
         return self[0].forward(species_aev)
+
+    @torch.jit.unused
+    def members_energies(self, species_aev: Tuple[Tensor, Tensor]) -> SpeciesEnergies:
+        """Extension (TorchANI's ``Ensemble.members_energies``): (species, aev [molecules, atoms, features]) ->
+        SpeciesEnergies(species, energies [models, molecules]), every model's sum over the atoms, differentiable with respect to the
+        AEV.  ``layout='fused'`` runs one molecule on the fused kernels as one autograd node (first derivatives); every other layout,
+        CPU tensors, float64, several molecules and networks outside the kernels' shape take plain torch (twice differentiable)."""
+        return self[0].members_energies(species_aev)
 
     def fused_energy(self, positions: Tensor, cell: Optional[Tensor], shift: Optional[Tensor] = None) -> Tensor:
         return self[0].fused_energy(positions, cell, shift)

@@ -60,6 +60,51 @@ class OptimizedTorchANI(torch.nn.Module):
         species_energies = self.neural_networks(species_aevs)
         return self.energy_shifter(species_energies)
 
+    @torch.jit.unused
+    def members_energies(self, species_coordinates: Tuple[Tensor, Tensor], cell: Optional[Tensor] = None,
+                         pbc: Optional[Tensor] = None) -> SpeciesEnergies:
+        """Extension (TorchANI's ``members_energies``; the reference keeps only the mean): the energy of every ensemble member,
+        SpeciesEnergies(species, energies [models, 1]), float64, each member shifted by the molecule's self energy as ``forward``
+        shifts the mean -- differentiable with respect to the coordinates.  Arguments and checks of ``forward``."""
+        species_coordinates = self.species_converter(species_coordinates)
+        species_aevs = self.aev_computer(species_coordinates, cell, pbc)
+        members = self.neural_networks.members_energies(species_aevs).energies
+        return SpeciesEnergies(species_aevs[0], members + self.energy_shifter.self_energies)
+
+    @torch.jit.unused
+    def members_energies_batch(self, species_coordinates: Tuple[Tensor, Tensor], cell: Optional[Tensor] = None,
+                               pbc: Optional[Tensor] = None) -> SpeciesEnergies:
+        """``members_energies`` for B conformers of the module's molecule (arguments and checks of ``forward_batch``):
+        SpeciesEnergies(species, energies [models, B])."""
+        species, coordinates = self._batch_arguments(species_coordinates, cell, pbc)
+        species_aevs = self.aev_computer.forward_batch((species, coordinates))
+        members = self.neural_networks.members_energies(species_aevs).energies
+        return SpeciesEnergies(species, members + self.energy_shifter.self_energies)
+
+    @staticmethod
+    def _qbcs(species: Tensor, members: Tensor, unbiased: bool) -> Tuple[Tensor, Tensor, Tensor]:
+        """members [models, molecules] float64 -> (species, mean over the models, std over the models / sqrt(atoms)): TorchANI's
+        ``energies_qbcs``, both differentiable through the member energies"""
+        members = members.double()
+        qbcs = members.std(0, unbiased=unbiased) / (float(species.shape[1]) ** 0.5)
+        return species, members.mean(0), qbcs
+
+    @torch.jit.unused
+    def energies_qbcs(self, species_coordinates: Tuple[Tensor, Tensor], cell: Optional[Tensor] = None, pbc: Optional[Tensor] = None,
+                      unbiased: bool = True) -> Tuple[Tensor, Tensor, Tensor]:
+        """Extension (TorchANI's ``energies_qbcs``): (species, energies [1], qbcs [1]) -- the mean over the ensemble members and their
+        query-by-committee factor ``std(members, unbiased) / sqrt(atoms)``, both from ``members_energies`` in float64 and
+        differentiable through it (uncertainty-biased dynamics takes d qbcs / d coordinates from ONE backward)."""
+        out = self.members_energies(species_coordinates, cell, pbc)
+        return self._qbcs(out.species, out.energies, unbiased)
+
+    @torch.jit.unused
+    def energies_qbcs_batch(self, species_coordinates: Tuple[Tensor, Tensor], cell: Optional[Tensor] = None, pbc: Optional[Tensor] = None,
+                            unbiased: bool = True) -> Tuple[Tensor, Tensor, Tensor]:
+        """``energies_qbcs`` for B conformers: (species [B, N], energies [B], qbcs [B])."""
+        out = self.members_energies_batch(species_coordinates, cell, pbc)
+        return self._qbcs(out.species, out.energies, unbiased)
+
 
 class FusedOptimizedTorchANI(OptimizedTorchANI):
     """OptimizedTorchANI whose forward is ``torch.ops.NNPOpsANISymmetryFunctions.energy``: neighbour search + AEV + the four
@@ -123,6 +168,39 @@ class FusedOptimizedTorchANI(OptimizedTorchANI):
         if shift.dtype == torch.float64 and shift.numel() == 1 and shift.device == coordinates.device:
             return SpeciesEnergies(species, self.neural_networks.fused_energy_batch(holder, coordinates, shift))
         return self.energy_shifter((species, self.neural_networks.fused_energy_batch(holder, coordinates)))
+
+    @torch.jit.unused
+    def _shift_for(self, positions: Tensor) -> Optional[Tensor]:
+        shift = self.energy_shifter.self_energies
+        return shift if shift.dtype == torch.float64 and shift.numel() == 1 and shift.device == positions.device else None
+
+    @torch.jit.unused
+    def members_energies(self, species_coordinates: Tuple[Tensor, Tensor], cell: Optional[Tensor] = None,
+                         pbc: Optional[Tensor] = None) -> SpeciesEnergies:
+        """``OptimizedTorchANI.members_energies`` as TWO autograd nodes: the AEV op with its deferred backward and
+        ``torch.ops.NNPOpsBatchedNN.FusedMLPMembers``, whose backward is one weighted launch of the networks' input gradient -- any
+        function of the member energies costs one such launch and one AEV backward.  Second derivatives are refused."""
+        converted = self.species_converter(species_coordinates)
+        species, positions = converted.species, converted.coordinates
+        self.aev_computer.check_arguments(species, cell, pbc)
+        aev = torch.ops.NNPOpsANISymmetryFunctions.aev(self.aev_computer.holder, positions[0], cell)
+        shift = self._shift_for(positions)
+        members = self.neural_networks[0].fused_members(aev, shift).t()
+        return SpeciesEnergies(species, members if shift is not None else members + self.energy_shifter.self_energies)
+
+    @torch.jit.unused
+    def members_energies_batch(self, species_coordinates: Tuple[Tensor, Tensor], cell: Optional[Tensor] = None,
+                               pbc: Optional[Tensor] = None) -> SpeciesEnergies:
+        """``OptimizedTorchANI.members_energies_batch`` on the same two nodes, over all B x N atoms behind the batched holder of
+        ``aev_computer``: a conformer's member energies and its gradient are the same bits wherever it stands in whatever batch."""
+        species, coordinates = self._batch_arguments(species_coordinates, cell, pbc)
+        batch, atoms = int(coordinates.shape[0]), int(coordinates.shape[1])
+        nets = self.neural_networks[0]
+        holder, rows, sizes, places, offsets = nets._batch_plan(self.aev_computer.batch_holder(batch), batch, coordinates.device)
+        aev = torch.ops.NNPOpsANISymmetryFunctions.aev(holder, coordinates.reshape(batch * atoms, 3), None)
+        shift = self._shift_for(coordinates)
+        members = nets.fused_members(aev, shift, (rows, sizes, places, offsets)).t()
+        return SpeciesEnergies(species, members if shift is not None else members + self.energy_shifter.self_energies)
 
     @torch.jit.unused
     def energy_and_forces_batch(self, species_coordinates: Tuple[Tensor, Tensor], cell: Optional[Tensor] = None,

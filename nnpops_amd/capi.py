@@ -90,6 +90,9 @@ SIGNATURES = {
     "nnpops_mlp_energy_mean_segments_shifted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float,
                                                           C.c_void_p, C.c_void_p]),
     "nnpops_scale_by_segment": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "nnpops_mlp_member_sums": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "nnpops_mlp_member_sums_shifted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]),
     "nnpops_neighbor_pairs_workspace_bytes": (C.c_int64, [C.c_int]),
     "nnpops_neighbor_pairs_forward": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int64,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -942,7 +945,8 @@ class _MlpFrame(C.Structure):
                 ("x_groups", C.c_void_p), ("dead_groups", C.c_void_p), ("num_dead_groups", C.c_int), ("dx_partial", C.c_void_p),
                 ("mean_scale", C.c_float), ("mean_out", C.c_void_p), ("mean_shift", C.c_void_p), ("mean_out_shifted", C.c_void_p),
                 ("publish_word", C.c_void_p), ("publish_to", C.c_void_p), ("publish_stamp", C.c_int32), ("act_scale_log2", C.c_int),
-                ("segment_offsets", C.c_void_p), ("segment_positions", C.c_void_p), ("num_segments", C.c_int)]
+                ("segment_offsets", C.c_void_p), ("segment_positions", C.c_void_p), ("num_segments", C.c_int),
+                ("member_weights", C.c_void_p), ("member_weights_ld", C.c_int)]
 
 
 def mlp_pack(w, rows, cols, transpose=False, permute=False):
@@ -1056,15 +1060,32 @@ class FusedMLP:
                                                     _ptr(shift), _ptr(out)))
         return out
 
-    def input_grad(self, like, upstream=None, out=None, scale=1.0):
+    def input_grad(self, like, upstream=None, out=None, scale=1.0, member_weights=None, molecule_offsets=None):
         """dE/dx of the summed energies of the last forward(with_gradient=True): [atoms][F] float32 (rows of atoms that
-        belong to no kind are left as they are)."""
+        belong to no kind are left as they are).  With ``member_weights`` (float32 device tensor [molecules or 1][M]) the gradient of
+        sum_b sum_m member_weights[b][m] E_m(molecule b) instead (nnpops_hip.h: member_weights); ``molecule_offsets`` (int32 device
+        tensor [molecules + 1]) says which rows of x are which molecule, without it everything is molecule 0."""
         if out is None:
             out = torch.zeros((like.shape[0], self.x_width), dtype=torch.float32, device=like.device)
         self.frame.dx, self.frame.lddx = out.data_ptr(), out.shape[1]
         self.frame.upstream = upstream.data_ptr() if upstream is not None else None
         self.frame.dx_scale = float(scale)
-        _check(lib().nnpops_mlp_input_grad(_stream_ptr(out.device), C.byref(self.frame)))
+        saved = (self.frame.segment_offsets, self.frame.num_segments)
+        if member_weights is not None:
+            member_weights = _dev_f32(member_weights, "member_weights")
+            count = 1 if molecule_offsets is None else molecule_offsets.numel() - 1
+            if member_weights.dim() != 2 or tuple(member_weights.shape) != (count, self.M):
+                raise ValueError(f"member_weights must be [{count}][{self.M}]")
+            self.frame.member_weights, self.frame.member_weights_ld = member_weights.data_ptr(), self.M
+            if molecule_offsets is not None:
+                if not (molecule_offsets.is_cuda and molecule_offsets.dtype == torch.int32 and molecule_offsets.is_contiguous()):
+                    raise ValueError('"molecule_offsets" must be a contiguous int32 device tensor')
+                self.frame.segment_offsets, self.frame.num_segments = molecule_offsets.data_ptr(), count
+        try:
+            _check(lib().nnpops_mlp_input_grad(_stream_ptr(out.device), C.byref(self.frame)))
+        finally:
+            self.frame.member_weights, self.frame.member_weights_ld = None, 0
+            self.frame.segment_offsets, self.frame.num_segments = saved
         return out
 
 
@@ -1104,6 +1125,25 @@ def mlp_energy_mean_segments(energies, molecule_offsets, positions, scale=1.0, s
     out = torch.empty((count,), dtype=torch.float64, device=energies.device)
     _check(lib().nnpops_mlp_energy_mean_segments_shifted(_stream_ptr(out.device), _ptr(energies), n, members, _ptr(molecule_offsets), count,
                                                          _ptr(positions), float(scale), _ptr(shift), _ptr(out)))
+    return out
+
+
+def mlp_member_sums(energies, molecule_offsets=None, positions=None, shift=None):
+    """The energy of every member, molecule by molecule (nnpops_mlp_member_sums): ``energies`` [grouped atoms][members], tables as for
+    mlp_energy_mean_segments (both None: one molecule) -> float32 [B][members], or -- with ``shift`` -- float64 = (double)(float)sum + shift."""
+    energies = _dev_f32(energies, "energies")
+    n, members = energies.shape
+    count = 1
+    if molecule_offsets is not None or positions is not None:
+        count = _segment_tables(molecule_offsets, positions, n)
+    tables = (_ptr(molecule_offsets) if molecule_offsets is not None else None, count, _ptr(positions) if positions is not None else None)
+    if shift is None:
+        out = torch.empty((count, members), dtype=torch.float32, device=energies.device)
+        _check(lib().nnpops_mlp_member_sums(_stream_ptr(out.device), _ptr(energies), n, members, *tables, _ptr(out)))
+        return out
+    assert shift.dtype == torch.float64 and shift.is_cuda and shift.numel() >= 1
+    out = torch.empty((count, members), dtype=torch.float64, device=energies.device)
+    _check(lib().nnpops_mlp_member_sums_shifted(_stream_ptr(out.device), _ptr(energies), n, members, *tables, _ptr(shift), _ptr(out)))
     return out
 
 

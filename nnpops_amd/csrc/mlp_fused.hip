@@ -82,7 +82,21 @@ struct MlpArgs {
     float scale, unscale;                   // 2^-act_scale_log2 and its inverse: the operand scale of the fp16 planes (nnpops_hip.h; 1/16 by default)
     const int* seg_offsets; const int* seg_positions; int num_segments;                      // optional: the mean is taken molecule by molecule (energy_mean_segment)
     KindDesc kinds[NNPOPS_MLP_MAX_KINDS];
+    // (behind the kinds: what the unweighted kernels read keeps its place in the kernel arguments)
+    const float* member_weights; int ldw;   // optional [w_segments or 1][ldw]: the upstream weight of every (molecule, member) (WEIGHTED kernels)
+    const int* w_offsets; int w_segments;   // the molecules the rows belong to (rows w_offsets[b] .. w_offsets[b + 1] - 1); NULL: one molecule
 };
+
+// the molecule of a row: the last b with offsets[b] <= row, by bisection over offsets[1 .. count - 1] -- whatever the table holds, the
+// answer lies in 0 .. count - 1 (a bad table gives wrong numbers, not a fault)
+__device__ __forceinline__ int molecule_of_row(const int* __restrict__ offsets, int count, int row) {
+    int lo = 0, hi = count;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (offsets[mid] <= row) lo = mid; else hi = mid;
+    }
+    return lo;
+}
 
 // v (already scaled into range) -> hi + 2^-11 lo'.  The high plane is rounded toward zero two values at a time
 // (v_cvt_pkrtz_f16_f32: any fp16 near v will do, the low plane carries the exact remainder), the low plane to nearest.
@@ -407,9 +421,18 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_forward(const MlpArgs g) {
 // dE/dAEV^T [F x atoms] = W0^T [F x M*H1] . dE/dy1^T: workgroup = (tile of 64 atoms, 8 row blocks = 128 AEV columns)
 // =============================================================================================
 constexpr int kGradBlocks = kWaves;         // row blocks of F per workgroup: one per wave
+constexpr int kMaxWeightedMembers = 128;    // WEIGHTED: 256 B of LDS per member behind the 16 KiB of the stages (48 KiB at most)
 
+// WEIGHTED: dL/dAEV for upstream weights g_m of the member energies, sum_m g_m W0_m^T dE_m/dy1.  The K dimension is member after
+// member (s1 steps each), so the accumulators are FOLDED at every member boundary -- total += w (acc1 + acc2 / 2048), accumulators
+// cleared -- with w the weight of the column's atom: the row of `member_weights` of the atom's molecule (a tile of a batch holds atoms
+// of several molecules).  The fp16 planes are never scaled: hi + 2^-11 lo is an exact split of the value, of a multiple of it it is
+// not.  A member whose weight is zero is skipped (its share is not added, whatever it holds).  The weights of the tile wait in LDS
+// ([member][atom of the tile]; read with ds instructions, so the fold does not wait for the weight fragments in flight).
+// The unweighted instantiation is the kernel as it always was.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(kThreads, 2) void mlp_input_grad(const MlpArgs g) {
-    extern __shared__ __attribute__((aligned(16))) char lds[];     // 2 stages x 8 KiB of B fragments
+    extern __shared__ __attribute__((aligned(16))) char lds[];     // 2 stages x 8 KiB of B fragments (+ WEIGHTED: M x 64 weights)
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const KindDesc& kd = kind_of_block(g, blockIdx.x);
     const int local = blockIdx.x - kd.block0;
@@ -425,6 +448,19 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_input_grad(const MlpArgs g) {
     f32x4 acc1[kCB], acc2[kCB];
 #pragma unroll
     for (int cb = 0; cb < kCB; cb++) { acc1[cb] = f32x4{0.f, 0.f, 0.f, 0.f}; acc2[cb] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    f32x4 total[kCB];                                       // WEIGHTED: the folded members
+    const float* wtile = reinterpret_cast<const float*>(lds + 2 * kStageBytes);
+    int until_fold = s1, member = 0;                        // WEIGHTED: steps left in the current member
+    if constexpr (WEIGHTED) {
+#pragma unroll
+        for (int cb = 0; cb < kCB; cb++) total[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // thread -> (atom of the tile = tid % 64, members tid / 64, + 8, ...); atoms past the kind get weight zero
+        const int r = r0 + lane;
+        int mol = -1;
+        if (r < kd.n) mol = g.w_offsets ? molecule_of_row(g.w_offsets, g.w_segments, g.rows[kd.first + r]) : 0;
+        float* wdst = reinterpret_cast<float*>(lds + 2 * kStageBytes);
+        for (int m = w; m < g.M; m += kWaves) wdst[m * kTile + lane] = mol >= 0 ? g.member_weights[(size_t)mol * g.ldw + m] : 0.0f;
+    }
 
     struct A1 { f16x8 h, l; };
     auto load_a1 = [&](A1& a, int s) {
@@ -463,6 +499,21 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_input_grad(const MlpArgs g) {
         mma(cur, lds + (s & 1) * kStageBytes);
         stage_b((s + 1) & 1);
         fetch_b(min(s + 2, steps - 1));
+        if constexpr (WEIGHTED) {
+            if (--until_fold == 0) {                         // step s was the member's last one (uniform over the workgroup)
+#pragma unroll
+                for (int cb = 0; cb < kCB; cb++) {
+                    const float wm = wtile[member * kTile + cb * 16 + (lane & 15)];
+#pragma unroll
+                    for (int q = 0; q < 4; q++) {
+                        const float share = fmaf(kLoInv, acc2[cb][q], acc1[cb][q]);
+                        total[cb][q] = wm != 0.0f ? fmaf(wm, share, total[cb][q]) : total[cb][q];
+                    }
+                    acc1[cb] = f32x4{0.f, 0.f, 0.f, 0.f}; acc2[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+                until_fold = s1; member++;
+            }
+        }
         __syncthreads();
     };
     for (int s = 0; s < steps; s += 4) {
@@ -488,6 +539,12 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_input_grad(const MlpArgs g) {
         for (int cb = 0; cb < kCB; cb++) {
             const int r = r0 + cb * 16 + a16;
             if (r >= kd.n) continue;
+            if constexpr (WEIGHTED) {
+                *reinterpret_cast<float4*>(g.dx + (size_t)g.rows[kd.first + r] * g.lddx + col) =
+                    make_float4(total[cb][0] * g.unscale * up, total[cb][1] * g.unscale * up, total[cb][2] * g.unscale * up,
+                                total[cb][3] * g.unscale * up);
+                continue;
+            }
             float4 v;
             v.x = (acc1[cb][0] + kLoInv * acc2[cb][0]) * g.unscale * up;
             v.y = (acc1[cb][1] + kLoInv * acc2[cb][1]) * g.unscale * up;
@@ -567,6 +624,9 @@ __device__ __forceinline__ void energy_mean_segment(const float* __restrict__ v,
 
 // dx = scale * sum over the members of dx_partial (what mlp_forward left when the frame carries dx_partial), written to the
 // columns the feature blocks live in; dead column blocks are set to zero.  One thread per (grouped atom, four columns).
+// WEIGHTED: every member's share times member_weights[molecule of the atom][member], members in the same fixed order; a member whose
+// weight is zero is skipped, as in mlp_input_grad<true>.  The unweighted instantiation is the kernel as it always was.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void mlp_sum_members(const MlpArgs g) {
     __shared__ double red[1024 / 64];
     if (g.seg_offsets) {                                                        // (a batch of molecules: one wave per molecule)
@@ -584,8 +644,16 @@ __global__ __launch_bounds__(256) void mlp_sum_members(const MlpArgs g) {
         if (e < quads) {
             const int c = 4 * e;
             float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+            const float* wrow = nullptr;
+            if constexpr (WEIGHTED)
+                wrow = g.member_weights + (size_t)(g.w_offsets ? molecule_of_row(g.w_offsets, g.w_segments, g.rows[r]) : 0) * g.ldw;
             for (int m = 0; m < g.M; m++) {                  // fixed order: bitwise reproducible
                 const float4 v = *reinterpret_cast<const float4*>(g.dx_partial + ((size_t)m * g.n_grouped + r) * g.F + c);
+                if constexpr (WEIGHTED) {
+                    const float wm = wrow[m];
+                    if (wm != 0.0f) { acc.x = fmaf(wm, v.x, acc.x); acc.y = fmaf(wm, v.y, acc.y); acc.z = fmaf(wm, v.z, acc.z); acc.w = fmaf(wm, v.w, acc.w); }
+                    continue;
+                }
                 acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
             }
             const int grp = g.x_groups ? g.x_groups[c >> 4] : (c >> 4);
@@ -648,6 +716,42 @@ __global__ __launch_bounds__(256) void mlp_energy_mean_segments(const float* __r
         energy_mean_segment(v, n, M, offsets, position, b, scale, out, shift, out_shifted);
 }
 
+// The energy of every ensemble member, molecule by molecule: out[b][m] = sum over the atoms of molecule b of v[place][m].  One wave per
+// molecule as in energy_mean_segment -- lane l adds the atoms l, l + 64, ... counted inside the molecule, the lane sums meet in the same
+// fixed butterfly -- but every member keeps its own float64 accumulator (kMemberChunk members per pass over the molecule's atoms; a
+// member's additions do not depend on the pass it is in).  A value is a function of the molecule's own atoms only.  Without offsets
+// and positions everything is one molecule.  shift != NULL: out is a double and gets (double)(float)sum + shift[0], as the means do.
+constexpr int kMemberChunk = 8;
+__global__ __launch_bounds__(256) void mlp_member_sums(const float* __restrict__ v, int n, int M, const int* __restrict__ offsets,
+                                                       int num_segments, const int* __restrict__ position, float* __restrict__ out,
+                                                       const double* __restrict__ shift, double* __restrict__ out_shifted) {
+    const int lane = threadIdx.x & 63;
+    for (int b = blockIdx.x * 4 + (threadIdx.x >> 6); b < num_segments; b += gridDim.x * 4) {
+        const int begin = offsets ? min(max(offsets[b], 0), n) : 0, end = offsets ? min(max(offsets[b + 1], begin), n) : n;
+        for (int m0 = 0; m0 < M; m0 += kMemberChunk) {
+            double acc[kMemberChunk];
+#pragma unroll
+            for (int j = 0; j < kMemberChunk; j++) acc[j] = 0.0;
+            for (int a = begin + lane; a < end; a += 64) {
+                const float* e = v + (size_t)(position ? min(max(position[a], 0), n - 1) : a) * M + m0;
+#pragma unroll
+                for (int j = 0; j < kMemberChunk; j++)
+                    if (m0 + j < M) acc[j] += (double)e[j];
+            }
+#pragma unroll
+            for (int j = 0; j < kMemberChunk; j++) {
+#pragma unroll
+                for (int off = 32; off >= 1; off >>= 1) acc[j] += __shfl_xor(acc[j], off, 64);
+                if (lane == 0 && m0 + j < M) {
+                    const float sum = (float)acc[j];
+                    if (shift) out_shifted[(size_t)b * M + m0 + j] = (double)sum + shift[0];
+                    else out[(size_t)b * M + m0 + j] = sum;
+                }
+            }
+        }
+    }
+}
+
 // out[row][0..2] = in[row][0..2] * (float)factor[molecule of row]: one wave per molecule (the backward of the batched energy node)
 template <typename F>
 __global__ __launch_bounds__(256) void scale_by_segment(const float* __restrict__ in, int n, const int* __restrict__ offsets, int num_segments,
@@ -686,10 +790,19 @@ int check_and_fill(const nnpops_mlp_frame* fr, MlpArgs& g, bool grad, int blocks
     NNPOPS_REQUIRE(!fr->publish_word || fr->publish_to, "publish_word without publish_to");
     NNPOPS_REQUIRE(!(fr->mean_out && fr->mean_out_shifted) && (!fr->mean_out_shifted || fr->mean_shift), "one energy mean: float, or shifted double with its shift");
     g.seg_offsets = nullptr; g.seg_positions = nullptr; g.num_segments = 0;
-    if (fr->segment_offsets || fr->segment_positions || fr->num_segments != 0) {
+    g.member_weights = nullptr; g.ldw = 0; g.w_offsets = nullptr; g.w_segments = 0;
+    const bool want_mean = fr->mean_out || fr->mean_out_shifted;
+    if (fr->member_weights) {                                // (the molecules of the weights are the segments; the means need not be asked for)
+        NNPOPS_REQUIRE(fr->member_weights_ld >= fr->num_members, "member_weights_ld (%d) is below the number of members (%d)", fr->member_weights_ld,
+                       fr->num_members);
+        NNPOPS_REQUIRE((fr->segment_offsets != nullptr) == (fr->num_segments != 0) && fr->num_segments >= 0,
+                       "member_weights of a batch need segment_offsets and the number of molecules (got %d)", fr->num_segments);
+        g.member_weights = fr->member_weights; g.ldw = fr->member_weights_ld; g.w_offsets = fr->segment_offsets; g.w_segments = fr->num_segments;
+    }
+    if ((fr->segment_offsets || fr->segment_positions || fr->num_segments != 0) && (want_mean || !fr->member_weights)) {
         NNPOPS_REQUIRE(fr->segment_offsets && fr->segment_positions && fr->num_segments >= 1,
                        "a mean per molecule needs segment_offsets, segment_positions and at least one molecule (got %d)", fr->num_segments);
-        NNPOPS_REQUIRE(fr->mean_out || fr->mean_out_shifted, "segment_offsets without mean_out / mean_out_shifted");
+        NNPOPS_REQUIRE(want_mean, "segment_offsets without mean_out / mean_out_shifted");
         g.seg_offsets = fr->segment_offsets; g.seg_positions = fr->segment_positions; g.num_segments = fr->num_segments;
     }
     NNPOPS_REQUIRE(!fr->x_groups || fr->num_features % 16 == 0, "x_groups maps blocks of 16 features: the feature count must be a multiple of 16 (got %d)",
@@ -808,6 +921,31 @@ int nnpops_mlp_energy_mean_segments_shifted(void* stream, const float* energies,
     return NNPOPS_OK;
 }
 
+static int member_sums(void* stream, const float* energies, int num_atoms, int num_members, const int32_t* molecule_offsets, int num_molecules,
+                       const int32_t* positions, float* out, const double* shift, double* out_shifted) {
+    NNPOPS_REQUIRE(energies && (out || (shift && out_shifted)), "NULL device pointer");
+    NNPOPS_REQUIRE(num_molecules >= 1 && num_atoms >= 1 && num_members >= 1, "empty batch (%d molecules, %d atoms, %d members)", num_molecules,
+                   num_atoms, num_members);
+    NNPOPS_REQUIRE((molecule_offsets != nullptr) == (positions != nullptr), "molecule_offsets and positions come together (both NULL: one molecule)");
+    NNPOPS_REQUIRE(molecule_offsets || num_molecules == 1, "without molecule_offsets everything is one molecule (got %d)", num_molecules);
+    hipLaunchKernelGGL(mlp_member_sums, dim3(std::min((num_molecules + 3) / 4, 4096)), dim3(256), 0, (hipStream_t)stream, energies, num_atoms,
+                       num_members, molecule_offsets, num_molecules, positions, out, shift, out_shifted);
+    NNPOPS_HIP_TRY(hipGetLastError());
+    return NNPOPS_OK;
+}
+
+int nnpops_mlp_member_sums(void* stream, const float* energies, int num_atoms, int num_members, const int32_t* molecule_offsets,
+                           int num_molecules, const int32_t* positions, float* out) {
+    NNPOPS_REQUIRE(out, "NULL device pointer");
+    return member_sums(stream, energies, num_atoms, num_members, molecule_offsets, num_molecules, positions, out, nullptr, nullptr);
+}
+
+int nnpops_mlp_member_sums_shifted(void* stream, const float* energies, int num_atoms, int num_members, const int32_t* molecule_offsets,
+                                   int num_molecules, const int32_t* positions, const double* shift, double* out) {
+    NNPOPS_REQUIRE(shift && out, "NULL device pointer");
+    return member_sums(stream, energies, num_atoms, num_members, molecule_offsets, num_molecules, positions, nullptr, shift, out);
+}
+
 int nnpops_scale_by_segment(void* stream, const float* in, int num_atoms, const int32_t* molecule_offsets, int num_molecules,
                             const void* factors, int factor_is_double, float* out) {
     NNPOPS_REQUIRE(in && molecule_offsets && factors && out, "NULL device pointer");
@@ -846,11 +984,20 @@ int nnpops_mlp_input_grad(void* stream, const nnpops_mlp_frame* frame) {
     if (blocks == 0) return NNPOPS_OK;
     if (g.dx_partial) {                                      // the forward launch has formed every member's share: add them up
         const long total = (long)g.n_grouped * ((g.F >> 2) + g.num_dead * 4);
-        hipLaunchKernelGGL(mlp_sum_members, dim3((int)std::min<long>((total + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream, g);
+        const dim3 grid((int)std::min<long>((total + 255) / 256, 4096));
+        if (g.member_weights) hipLaunchKernelGGL(mlp_sum_members<true>, grid, dim3(256), 0, (hipStream_t)stream, g);
+        else hipLaunchKernelGGL(mlp_sum_members<false>, grid, dim3(256), 0, (hipStream_t)stream, g);
         NNPOPS_HIP_TRY(hipGetLastError());
         return NNPOPS_OK;
     }
-    hipLaunchKernelGGL(mlp_input_grad, dim3(blocks), dim3(kThreads), 2 * kStageBytes, (hipStream_t)stream, g);
+    if (g.member_weights) {                                  // (the weights of a tile wait in LDS behind the two stages: [member][64])
+        NNPOPS_REQUIRE(g.M <= kMaxWeightedMembers, "member_weights: at most %d members (got %d)", kMaxWeightedMembers, g.M);
+        hipLaunchKernelGGL(mlp_input_grad<true>, dim3(blocks), dim3(kThreads), 2 * kStageBytes + (size_t)g.M * kTile * sizeof(float),
+                           (hipStream_t)stream, g);
+        NNPOPS_HIP_TRY(hipGetLastError());
+        return NNPOPS_OK;
+    }
+    hipLaunchKernelGGL(mlp_input_grad<false>, dim3(blocks), dim3(kThreads), 2 * kStageBytes, (hipStream_t)stream, g);
     NNPOPS_HIP_TRY(hipGetLastError());
     return NNPOPS_OK;
 }

@@ -82,6 +82,7 @@ struct MlpCall {
 // workspaces of a frame that a caller with a home for them (the AEV holder of the one-node step) keeps between the steps
 struct MlpScratch {
     Tensor partial, energies;
+    std::vector<Tensor> d1;           // (FusedMLPMembers: the node's own dE/dy1 planes, one per kind, handed back to its backward)
 };
 
 int64_t mlp_halves(int64_t rows, int64_t cols) { return nnpops_mlp_packed_halves((int)rows, (int)cols); }
@@ -154,7 +155,9 @@ MlpCall mlp_prepare(const Tensor& x, const Tensor& rows, const std::vector<int64
         kd.w6 = pf + of; of += M * h3;
         kd.b6 = pf + of; of += M;
         if (with_gradient && !in_forward) {
-            Tensor d1 = torch::empty({std::max<int64_t>(nnpops_mlp_d1_halves((int)kind_atoms[k], (int)M, (int)h1), 1)}, planes.options());
+            const int64_t halves = std::max<int64_t>(nnpops_mlp_d1_halves((int)kind_atoms[k], (int)M, (int)h1), 1);
+            Tensor d1 = scratch && k < (int64_t)scratch->d1.size() && scratch->d1[k].numel() == halves && scratch->d1[k].device() == x.device()
+                ? scratch->d1[k] : torch::empty({halves}, planes.options());
             kd.d1 = d1.data_ptr();
             c.keep.push_back(d1);
         }
@@ -2928,8 +2931,104 @@ Tensor FusedMLP(const Tensor& x, const Tensor& rows, std::vector<int64_t> kind_a
     return FusedMLPFunction::apply(x, rows, kind_atoms, widths, members, planes, floats, need, act_scale_log2);
 }
 
+// =============================================================================================
+// FusedMLPMembers: the energy of every ensemble member as a differentiable output -- [B, M], B = 1 without the tables of a batch
+// (offsets [B + 1], places [atoms]: nnpops_mlp_member_sums), float32, or float64 and shifted with `shift` (a float64 device scalar).
+// forward: nnpops_mlp_forward (with its gradient half when x requires a gradient) + the member sums.  What the gradient half leaves
+// (dE/dy1, or every member's share of dE/dx) belongs to the NODE -- not to a holder whose next step would overwrite it -- and waits
+// for the upstream gradient: backward takes grad [B, M] and runs the WEIGHTED nnpops_mlp_input_grad (nnpops_hip.h: member_weights),
+// one launch whatever the function of the member energies was.  No host synchronisation anywhere: the op can be captured.
+// =============================================================================================
+class FusedMLPMembersFunction : public torch::autograd::Function<FusedMLPMembersFunction> {
+public:
+    static Tensor forward(AutogradContext* ctx, const Tensor& x, const Tensor& rows, std::vector<int64_t> kind_atoms, std::vector<int64_t> widths,
+                          int64_t members, const Tensor& planes, const Tensor& floats, const c10::optional<Tensor>& x_blocks,
+                          const c10::optional<Tensor>& dead_blocks, int64_t act_scale_log2, const c10::optional<Tensor>& offsets,
+                          const c10::optional<Tensor>& places, const c10::optional<Tensor>& shift, bool need_gradient) {
+        const char* op = "NNPOpsBatchedNN::FusedMLPMembers";
+        TORCH_CHECK(x.dim() == 2 && x.size(0) >= 1, "FusedMLPMembers: an empty batch (x must be [atoms, features] with at least one atom)");
+        TORCH_CHECK(offsets.has_value() == places.has_value(), "FusedMLPMembers: molecule offsets and row places come together");
+        int64_t B = 1;
+        if (offsets.has_value()) {
+            for (const Tensor* t : {&*offsets, &*places})
+                TORCH_CHECK(t->scalar_type() == torch::kInt32 && t->is_contiguous() && t->device() == x.device() && t->dim() == 1,
+                            "FusedMLPMembers: molecule offsets and row places must be contiguous int32 vectors on the device of x");
+            B = offsets->numel() - 1;
+            TORCH_CHECK(B >= 1, "FusedMLPMembers: an empty batch (", offsets->numel(), " molecule offsets)");
+            TORCH_CHECK(places->numel() == x.size(0), "FusedMLPMembers: ", x.size(0), " atoms need as many row places (got ", places->numel(), ")");
+        }
+        c10::hip::HIPGuard guard(x.device().index());
+        void* stream = current_stream(x.device());
+        MlpCall call = mlp_prepare(x, rows, kind_atoms, widths, members, planes, floats, need_gradient, x_blocks, dead_blocks, act_scale_log2);
+        if (nnpops_mlp_forward(stream, &call.frame, need_gradient ? 1 : 0) != NNPOPS_OK) raise_last(op);
+        const int32_t* off = offsets.has_value() ? offsets->data_ptr<int32_t>() : nullptr;
+        const int32_t* plc = places.has_value() ? places->data_ptr<int32_t>() : nullptr;
+        Tensor out;
+        if (shift.has_value()) {
+            TORCH_CHECK(shift->scalar_type() == torch::kFloat64 && shift->device() == x.device() && shift->numel() == 1 && shift->is_contiguous(),
+                        "FusedMLPMembers: the self-energy shift must be one float64 on the device of x");
+            out = torch::empty({B, members}, x.options().dtype(torch::kFloat64));
+            if (nnpops_mlp_member_sums_shifted(stream, call.energies.data_ptr<float>(), (int)x.size(0), (int)members, off, (int)B, plc,
+                                               shift->data_ptr<double>(), out.data_ptr<double>()) != NNPOPS_OK) raise_last(op);
+        } else {
+            out = torch::empty({B, members}, x.options());
+            if (nnpops_mlp_member_sums(stream, call.energies.data_ptr<float>(), (int)x.size(0), (int)members, off, (int)B, plc,
+                                       out.data_ptr<float>()) != NNPOPS_OK) raise_last(op);
+        }
+        if (need_gradient) {
+            tensor_list keep = {x, rows, planes, floats, call.energies};
+            keep.insert(keep.end(), call.keep.begin(), call.keep.end());      // dx_partial, or dE/dy1 of every kind
+            ctx->save_for_backward(keep);
+            ctx->saved_data["in_forward"] = call.frame.dx_partial != nullptr;
+            ctx->saved_data["kind_atoms"] = kind_atoms; ctx->saved_data["widths"] = widths;
+            ctx->saved_data["members"] = members; ctx->saved_data["act_scale_log2"] = act_scale_log2;
+            ctx->saved_data["x_blocks"] = x_blocks; ctx->saved_data["dead_blocks"] = dead_blocks; ctx->saved_data["offsets"] = offsets;
+        }
+        return out;
+    }
+    static tensor_list backward(AutogradContext* ctx, const tensor_list& grads) {
+        TORCH_CHECK(!torch::GradMode::is_enabled(), "NNPOpsBatchedNN::FusedMLPMembers: second derivatives are not implemented (create_graph=True); "
+                                                    "use layout='grouped' for that");
+        const auto saved = ctx->get_saved_variables();
+        TORCH_CHECK(!saved.empty(), "FusedMLPMembers was evaluated without a gradient request");
+        const Tensor &x = saved[0], &rows = saved[1], &planes = saved[2], &floats = saved[3];
+        const int64_t members = ctx->saved_data["members"].toInt();
+        const c10::optional<Tensor> x_blocks = ctx->saved_data["x_blocks"].toOptional<Tensor>(), dead_blocks = ctx->saved_data["dead_blocks"].toOptional<Tensor>(),
+                                    offsets = ctx->saved_data["offsets"].toOptional<Tensor>();
+        const int64_t B = offsets.has_value() ? offsets->numel() - 1 : 1;
+        TORCH_CHECK(grads[0].defined() && grads[0].dim() == 2 && grads[0].size(0) == B && grads[0].size(1) == members && grads[0].device() == x.device() &&
+                    (grads[0].scalar_type() == torch::kFloat32 || grads[0].scalar_type() == torch::kFloat64),
+                    "FusedMLPMembers: unexpected gradient of the member energies (shape [", B, ", ", members, "] in float32 or float64 expected)");
+        const Tensor g = grads[0].to(torch::kFloat32).contiguous();
+        MlpScratch own;                                       // the workspaces the forward left, handed back to the frame
+        own.energies = saved[4];
+        if (ctx->saved_data["in_forward"].toBool()) own.partial = saved[5];
+        else own.d1.assign(saved.begin() + 5, saved.end());
+        c10::hip::HIPGuard guard(x.device().index());
+        MlpCall call = mlp_prepare(x, rows, ctx->saved_data["kind_atoms"].toIntVector(), ctx->saved_data["widths"].toIntVector(), members, planes, floats,
+                                   true, x_blocks, dead_blocks, ctx->saved_data["act_scale_log2"].toInt(), &own);
+        Tensor dx = torch::empty_like(x);
+        call.frame.dx = dx.data_ptr<float>(); call.frame.lddx = (int)dx.size(1); call.frame.dx_scale = 1.0f;
+        call.frame.member_weights = g.data_ptr<float>(); call.frame.member_weights_ld = (int)members;
+        if (offsets.has_value()) { call.frame.segment_offsets = offsets->data_ptr<int32_t>(); call.frame.num_segments = (int)B; }
+        if (nnpops_mlp_input_grad(current_stream(x.device()), &call.frame) != NNPOPS_OK) raise_last("NNPOpsBatchedNN::FusedMLPMembers (backward)");
+        return {dx, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+    }
+};
+
+Tensor FusedMLPMembers(const Tensor& x, const Tensor& rows, std::vector<int64_t> kind_atoms, std::vector<int64_t> widths, int64_t members,
+                       const Tensor& planes, const Tensor& floats, const c10::optional<Tensor>& x_blocks, const c10::optional<Tensor>& dead_blocks,
+                       int64_t act_scale_log2, const c10::optional<Tensor>& offsets, const c10::optional<Tensor>& places,
+                       const c10::optional<Tensor>& shift) {
+    const bool need = torch::GradMode::is_enabled() && x.requires_grad();
+    return FusedMLPMembersFunction::apply(x, rows, kind_atoms, widths, members, planes, floats, x_blocks, dead_blocks, act_scale_log2, offsets, places,
+                                          shift, need);
+}
+
 TORCH_LIBRARY(NNPOpsBatchedNN, m) {
     m.def("BatchedLinear", BatchedLinear);
+    m.def("FusedMLPMembers(Tensor x, Tensor rows, int[] kind_atoms, int[] widths, int members, Tensor planes, Tensor floats, Tensor? x_blocks=None, "
+          "Tensor? dead_blocks=None, int act_scale_log2=4, Tensor? offsets=None, Tensor? places=None, Tensor? shift=None) -> Tensor", FusedMLPMembers);
     m.def("FusedMLP(Tensor x, Tensor rows, int[] kind_atoms, int[] widths, int members, Tensor planes, Tensor floats, int act_scale_log2=4) -> Tensor", FusedMLP);
     m.def("GroupedMLP(Tensor x, Tensor order, int[] group_sizes, int num_models, int h1, int h2, int h3, Tensor fwd_hi, Tensor fwd_lo, "
           "Tensor bwd_hi, Tensor bwd_lo, Tensor biases, Tensor last_w, float[] last_b) -> Tensor", GroupedMLP);

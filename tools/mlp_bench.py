@@ -1,6 +1,7 @@
 """Times the fused atomic networks alone on the shapes of BASELINE config 2 (and larger frames):
-    python tools/mlp_bench.py [n_waters ...]
-forward(+small-layer backward) and input-gradient launches, HIP events over 200 launches each."""
+    python tools/mlp_bench.py [--live] [--weighted] [n_waters ...]
+forward(+small-layer backward) and input-gradient launches, HIP events over 200 launches each.  --weighted also times the
+input gradient with one upstream weight per member (nnpops_hip.h: member_weights), next to the unweighted one at the same shape."""
 import sys
 import numpy as np
 import torch
@@ -31,6 +32,9 @@ def timeit(fn, reps=200):
 
 # --live: the networks over the AEV column blocks a water box can fill (species H = 0 and O = 3 of 7: 8 of the 63 blocks), with
 # the input gradient formed inside the forward launch -- what OptimizedTorchANI runs
+WEIGHTED = "--weighted" in sys.argv
+if WEIGHTED:
+    sys.argv.remove("--weighted")
 LIVE = None
 if "--live" in sys.argv:
     sys.argv.remove("--live")
@@ -57,6 +61,11 @@ for waters in [int(a) for a in sys.argv[1:]] or [667, 3334]:
     t_e = timeit(lambda: mlp.forward(x, with_gradient=False))
     t_f = timeit(lambda: mlp.forward(x, with_gradient=True))
     t_g = timeit(lambda: mlp.input_grad(x, out=dx))
+    if WEIGHTED:
+        weights = torch.rand((1, 8), device="cuda") * 2 - 1
+        t_w = timeit(lambda: mlp.input_grad(x, out=dx, member_weights=weights))
+        t_g2 = timeit(lambda: mlp.input_grad(x, out=dx))
+        print(f"{n} atoms: input gradient {t_g:.1f} / {t_g2:.1f} us unweighted, {t_w:.1f} us weighted ({100 * (t_w / min(t_g, t_g2) - 1):+.1f} %)")
     macs = 8 * (waters * (1008 * 192 + 192 * 160 + 160 * 128 + 128) + 2 * waters * (1008 * 256 + 256 * 192 + 192 * 160 + 160))
     print(f"{n} atoms: energy-only {t_e:.1f} us | forward + small-layer backward {t_f:.1f} us | input gradient {t_g:.1f} us | "
           f"fwd+bwd {t_f + t_g:.1f} us = {4 * macs / (t_f + t_g) / 1e6:.1f} TFLOP/s algorithmic")
