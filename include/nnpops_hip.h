@@ -273,6 +273,18 @@ int nnpops_cfconv_double_backward(nnpops_cfconv_t h, nnpops_cfconv_neighbors_t n
 /* The number of the list's last build (a process-wide counter, never 0 for a built list; 0 before the first build): what was
  * computed for one build of a list may be told apart from a later one. */
 int nnpops_cfconv_neighbors_build_count(nnpops_cfconv_neighbors_t h, unsigned long long* count);
+/* Batched evaluation of independent NON-PERIODIC molecules behind one list (the counterpart of nnpops_ani_set_molecules, same
+ * convention): atoms [molecule_offsets[m], molecule_offsets[m+1]) form molecule m (host array, num_molecules + 1 entries, first 0, last
+ * num_atoms, strictly increasing); atoms of different molecules never become neighbours, however their coordinates overlap.  The
+ * per-atom segment table is uploaded here, once; build() then fills the rows with a scan of every atom's own molecule (all pairs inside
+ * the segment at every total size -- a shared cell grid says nothing about overlapping molecules -- so a molecule of many hundreds of
+ * atoms costs its square), in ascending index order: a molecule's rows, pair slots and summation order are those of a list that holds
+ * the molecule alone.  check(), capacity growth, export(), build_count() and nnpops_cfconv_compute / _backprop / _double_backward work
+ * as they are: one launch sequence evaluates the whole batch.  Refused: a periodic list, offsets that do not start at 0 or end at
+ * num_atoms, an empty or decreasing segment; build() with a box on such a list is an error, and nnpops_cfconv_backprop_box refuses it as
+ * any non-periodic list.  The current build is invalidated (build_count() returns 0 until the next build()).  num_molecules <= 0 (or a
+ * NULL table) restores the single-system list.  Blocks on the list's stream; not capturable. */
+int nnpops_cfconv_neighbors_set_molecules(nnpops_cfconv_neighbors_t h, int num_molecules, const int32_t* molecule_offsets);
 
 /* ------------------------------------------------------------------------------------------
  * getNeighborPairs (replaces the neighbors::getNeighborPairs CUDA kernels)

@@ -71,6 +71,7 @@ SIGNATURES = {
     "nnpops_cfconv_double_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_cfconv_neighbors_build_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
+    "nnpops_cfconv_neighbors_set_molecules": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "nnpops_split_planes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p, C.c_long]),
     "nnpops_rows_dot": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "nnpops_gemm_split": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_long, C.c_void_p,
@@ -753,6 +754,7 @@ class CFConvNeighbors:
         self._lib = lib()
         self._h = C.c_void_p()
         self.num_atoms, self.cutoff, self.periodic = int(num_atoms), float(cutoff), bool(periodic)
+        self.batched = False
         self.device = torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
         _check(self._lib.nnpops_cfconv_neighbors_create(C.byref(self._h), self.num_atoms, self.cutoff, int(self.periodic),
                                                         self.device.index))
@@ -763,6 +765,17 @@ class CFConvNeighbors:
             self._lib.nnpops_cfconv_neighbors_destroy(h)
             self._h = None
 
+    def set_molecules(self, molecule_offsets):
+        """Treat the list's atoms as a batch of independent non-periodic molecules: atoms [offsets[m], offsets[m+1]) belong to
+        molecule m and never pair with another molecule's (None or an empty list restores one system).  Invalidates the current build."""
+        if molecule_offsets is None or len(molecule_offsets) == 0:
+            _check(self._lib.nnpops_cfconv_neighbors_set_molecules(self._h, 0, None))
+            self.batched = False
+            return
+        off = np.ascontiguousarray(molecule_offsets, dtype=np.int32)
+        _check(self._lib.nnpops_cfconv_neighbors_set_molecules(self._h, int(off.shape[0]) - 1, off.ctypes.data_as(C.c_void_p)))
+        self.batched = True
+
     def build(self, positions, box=None, check=True):
         _dev_f32(positions, "positions", (self.num_atoms, 3))
         if self.periodic:
@@ -771,7 +784,8 @@ class CFConvNeighbors:
             _dev_f32(box, "box", (3, 3))
         _check(self._lib.nnpops_cfconv_neighbors_set_stream(self._h, _stream_ptr(positions.device)))
         for _ in range(8):
-            _check(self._lib.nnpops_cfconv_neighbors_build(self._h, _ptr(positions), _ptr(box if self.periodic else None)))
+            # (a non-periodic single-system list ignores a box; a batch of molecules hands it on and is refused)
+            _check(self._lib.nnpops_cfconv_neighbors_build(self._h, _ptr(positions), _ptr(box if self.periodic or self.batched else None)))
             if not check:
                 return
             code = self._lib.nnpops_cfconv_neighbors_check(self._h, None)

@@ -79,6 +79,7 @@ struct nnpops_cfconv_neighbors {
     bool want_half = false, half_built = false;
     unsigned long long epoch = 0;      // number of the last build (process-wide counter): what a convolution keeps per list (its filter rows) is valid for one build
     bool cell_ordered = false;      // the last build went through the cell grid: cells.sorted_pos lists the atoms in cell order
+    int2* d_segment = nullptr;      // [N] per-atom [lo, hi) of its molecule (batched lists only: nnpops_cfconv_neighbors_set_molecules)
     int pair_cap() const { return (int)std::min<size_t>((size_t)N * cap / 2, (size_t)INT32_MAX - 1); }
 };
 
@@ -184,7 +185,7 @@ int nnpops_cfconv_neighbors_create(nnpops_cfconv_neighbors_t* out, int num_atoms
 int nnpops_cfconv_neighbors_destroy(nnpops_cfconv_neighbors_t h) {
     if (!h) return NNPOPS_OK;
     DeviceGuard guard(h->device);
-    dev_free(h->d_rows); dev_free(h->d_cnt); dev_free(h->d_status);
+    dev_free(h->d_rows); dev_free(h->d_cnt); dev_free(h->d_status); dev_free(h->d_segment);
     dev_free(h->d_lo_cnt); dev_free(h->d_half_off); dev_free(h->d_pid); dev_free(h->d_half_r); dev_free(h->d_half_ij); dev_free(h->d_ids);
     h->cells.release();
     delete h;
@@ -197,17 +198,50 @@ int nnpops_cfconv_neighbors_set_stream(nnpops_cfconv_neighbors_t h, void* stream
     return NNPOPS_OK;
 }
 
+// Batched molecules: the per-atom [lo, hi) table of rows_segments, uploaded once (the convention of nnpops_ani_set_molecules).
+int nnpops_cfconv_neighbors_set_molecules(nnpops_cfconv_neighbors_t h, int num_molecules, const int32_t* molecule_offsets) {
+    NNPOPS_REQUIRE(h != nullptr, "NULL handle");
+    DeviceGuard guard(h->device);
+    if (num_molecules <= 0 || molecule_offsets == nullptr) {     // back to one system
+        NNPOPS_HIP_TRY(hipStreamSynchronize(h->stream));         // (a build in flight may still read the table)
+        dev_free(h->d_segment);
+        h->d_segment = nullptr;
+        h->built = false;
+        return NNPOPS_OK;
+    }
+    NNPOPS_REQUIRE(!h->periodic, "batched molecules are non-periodic systems (this list was created periodic)");
+    NNPOPS_REQUIRE(molecule_offsets[0] == 0 && molecule_offsets[num_molecules] == h->N,
+                   "molecule_offsets must start at 0 and end at num_atoms (%d)", h->N);
+    for (int m = 0; m < num_molecules; m++)
+        NNPOPS_REQUIRE(molecule_offsets[m] < molecule_offsets[m + 1] && molecule_offsets[m + 1] <= h->N,
+                       "molecule %d is empty or offsets are not increasing", m);
+    std::vector<int2> seg(h->N);
+    for (int m = 0; m < num_molecules; m++)
+        for (int i = molecule_offsets[m]; i < molecule_offsets[m + 1]; i++) seg[i] = int2{molecule_offsets[m], molecule_offsets[m + 1]};
+    int rc;
+    if (!h->d_segment && (rc = dev_alloc(&h->d_segment, (size_t)h->N))) return rc;
+    NNPOPS_HIP_TRY(hipStreamSynchronize(h->stream));
+    NNPOPS_HIP_TRY(hipMemcpy(h->d_segment, seg.data(), sizeof(int2) * seg.size(), hipMemcpyHostToDevice));
+    h->built = false;
+    return NNPOPS_OK;
+}
+
 int nnpops_cfconv_neighbors_build(nnpops_cfconv_neighbors_t h, const float* positions, const float* box) {
     NNPOPS_REQUIRE(h != nullptr && positions != nullptr, "NULL argument");
     NNPOPS_REQUIRE(!h->periodic || box, "periodic neighbour list needs box vectors");
+    NNPOPS_REQUIRE(!h->d_segment || !box, "a list of batched molecules takes no box vectors (nnpops_cfconv_neighbors_set_molecules)");
     DeviceGuard guard(h->device);
     const int N = h->N;
     const bool per = h->periodic;
     const float c2 = h->cutoff * h->cutoff;
     // positions and box are read in place (the rows keep displacements, nothing refers back to them later); the
     // status words are cleared by create() and by check() after it has read them, not per build
-    const bool use_cells = N >= 1024 && !h->cells_disabled;
-    if (use_cells) {
+    // batched molecules overlap in space: the shared cell grid tells them nothing, so their rows come from the segmented scan at every size
+    const bool use_cells = N >= 1024 && !h->cells_disabled && !h->d_segment;
+    if (h->d_segment) {
+        hipLaunchKernelGGL(rows_segments, dim3(N), dim3(64), 0, h->stream, N, positions, (const int2*)h->d_segment, c2, h->d_rows, h->d_ids,
+                           h->cap, h->d_cnt, h->d_lo_cnt);
+    } else if (use_cells) {
         const CellList& g = h->cells;
         launch_cell_build(h->stream, N, positions, box, per, h->cutoff, nullptr, g);
         if (per)

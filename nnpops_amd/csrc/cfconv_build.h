@@ -59,6 +59,34 @@ __global__ __launch_bounds__(64) void rows_allpairs(int N, const float* __restri
     if (lane == 0) publish_row(i, n, n_lo, cnt, lo_cnt);
 }
 
+// Batched molecules (nnpops_cfconv_neighbors_set_molecules): rows_allpairs<false> with the scan confined to the atom's own molecule,
+// segment[i] = {lo, hi} as in ani_kernels.h.  The same displacement arithmetic and strict test, candidates in ascending index order,
+// so a molecule's rows are those of rows_allpairs on the molecule alone with every index moved by lo -- whatever the other molecules
+// hold, NaN included: no lane ever reads a position outside [lo, hi).  One wave per atom; a molecule of up to 64 atoms is one pass.
+__global__ __launch_bounds__(64) void rows_segments(int N, const float* __restrict__ pos, const int2* __restrict__ segment,
+                                                    float cutoff2, float4* __restrict__ rows, int* __restrict__ ids, int cap,
+                                                    int* __restrict__ cnt, int* __restrict__ lo_cnt) {
+    const int i = blockIdx.x, lane = lane_id();
+    if (i >= N) return;
+    const int2 seg = segment[i];
+    const int lo = max(seg.x, 0), hi = min(seg.y, N);       // (the host validated the table: the clamps keep a damaged one in bounds)
+    const float xi = pos[3 * i], yi = pos[3 * i + 1], zi = pos[3 * i + 2];
+    float4* row = rows + (size_t)i * cap;
+    int n = 0, n_lo = 0;
+    for (int base = lo; base < hi; base += 64) {
+        const int j = base + lane;
+        bool keep = false;
+        float dx = 0.f, dy = 0.f, dz = 0.f;
+        if (j < hi && j != i) {
+            dx = pos[3 * j] - xi; dy = pos[3 * j + 1] - yi; dz = pos[3 * j + 2] - zi;
+            keep = dx * dx + dy * dy + dz * dz < cutoff2;          // strict, on r^2, as rows_allpairs
+        }
+        append(row, ids + (size_t)i * cap, cap, keep, dx, dy, dz, j, n);
+        n_lo += __popcll(__ballot(keep && j > i));
+    }
+    if (lane == 0) publish_row(i, n, n_lo, cnt, lo_cnt);
+}
+
 template <bool PERIODIC>
 __global__ __launch_bounds__(64) void rows_cells(const float* __restrict__ box, float cutoff2,
                                                  const CellGrid* __restrict__ grid, const int* __restrict__ cell_start,

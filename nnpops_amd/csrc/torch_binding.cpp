@@ -872,6 +872,8 @@ public:
     // Additive to the reference (whose binding is non-periodic, CFConvNeighbors.cpp:52,57,74, although its core
     // supports a box, CFConv.h:57): the same list under periodic boundary conditions.  box: (3, 3), rows = vectors.
     void buildPeriodic(const Tensor& positions, const Tensor& box) {
+        if (!molecules.empty())
+            throw std::runtime_error("CFConvNeighbors::build: a list of batched molecules (set_molecules) is non-periodic and takes no \"box\"");
         if (box.scalar_type() != torch::kFloat32) throw std::runtime_error("The type of \"box\" has to be float32");
         if (box.dim() != 2 || box.size(0) != 3 || box.size(1) != 3) throw std::runtime_error("The shape of \"box\" has to be (3, 3)");
         require_device_tensor(box, "box");
@@ -890,6 +892,15 @@ public:
             periodic = box != nullptr;
             if (nnpops_cfconv_neighbors_create(&impl, (int)numAtoms, (float)cutoff, periodic ? 1 : 0, device.index()) != NNPOPS_OK)
                 raise_last("NNPOpsCFConvNeighbors");
+            if (!molecules.empty()) {
+                try {
+                    applyMolecules();
+                } catch (...) {                                   // (offsets that do not fit these positions: no half-made handle stays behind)
+                    nnpops_cfconv_neighbors_destroy(impl);
+                    impl = nullptr;
+                    throw;
+                }
+            }
         }
         if (positions.size(0) != numAtoms) throw std::runtime_error("The size of the 2nd dimension of \"positions\" has changed");
         if (positions.device() != device) throw std::runtime_error("The device of \"positions\" has changed");
@@ -908,6 +919,26 @@ public:
             if (rc != NNPOPS_ERR_CAPACITY || attempt > 8) raise_last("CFConvNeighbors::build");
         }
     }
+    // Additive: the atoms are a batch of independent non-periodic molecules, atoms [offsets[m], offsets[m+1]) molecule m
+    // (nnpops_cfconv_neighbors_set_molecules).  Kept here and applied when the handle is created (the first build) and on later calls;
+    // an empty list restores the single-system behaviour.  The current build is invalidated.
+    void setMolecules(std::vector<int64_t> offsets) {
+        for (int64_t v : offsets)
+            if (v < 0 || v > INT32_MAX) throw std::runtime_error("set_molecules: molecule offsets must lie in [0, num_atoms]");
+        if (!offsets.empty() && offsets.size() < 2) throw std::runtime_error("set_molecules: molecule offsets hold B + 1 entries (or none: one system)");
+        if (!offsets.empty() && impl && periodic) throw std::runtime_error("set_molecules: batched molecules are non-periodic systems (this list was built with a box)");
+        const std::vector<int64_t> before = molecules;
+        molecules = std::move(offsets);
+        if (!impl) return;
+        try {
+            applyMolecules();
+        } catch (...) {
+            molecules = before;                                   // (the handle kept its table: a refused call changes nothing)
+            throw;
+        }
+    }
+    std::vector<int64_t> getMolecules() const { return molecules; }
+    int64_t moleculeCount() const { return molecules.empty() ? 0 : (int64_t)molecules.size() - 1; }
     double getCutoff() const { return cutoff; }
     bool isPeriodic() const { return periodic; }
     nnpops_cfconv_neighbors_t getImpl() const { return impl; }
@@ -919,11 +950,19 @@ public:
     }
 
 private:
+    void applyMolecules() {
+        const std::vector<int32_t> off(molecules.begin(), molecules.end());
+        nnpops_cfconv_neighbors_set_stream(impl, current_stream(device));
+        if (nnpops_cfconv_neighbors_set_molecules(impl, off.empty() ? 0 : (int)off.size() - 1, off.empty() ? nullptr : off.data()) != NNPOPS_OK)
+            raise_last("NNPOpsCFConvNeighbors::set_molecules");
+    }
+
     double cutoff;
     int64_t numAtoms = 0;
     bool periodic = false;
     torch::Device device = torch::kCPU;
     nnpops_cfconv_neighbors_t impl = nullptr;
+    std::vector<int64_t> molecules;      // B + 1 offsets; empty: one system
 };
 using HolderPtr = torch::intrusive_ptr<Holder>;
 
@@ -933,6 +972,8 @@ TORCH_LIBRARY(NNPOpsCFConvNeighbors, m) {
         .def("build", &Holder::build)
         .def("build_periodic", &Holder::buildPeriodic)
         .def("build_count", &Holder::getBuildCount)
+        .def("set_molecules", &Holder::setMolecules)
+        .def("molecules", &Holder::getMolecules)
         .def_pickle([](const HolderPtr& self) -> double { return self->getCutoff(); },
                     [](double cutoff) -> HolderPtr { return HolderPtr::make(cutoff); });
 }
@@ -1031,6 +1072,8 @@ public:
         require_device_tensor(box_, "box");
         if (box_.device() != positions_.device()) throw std::runtime_error("The device of \"box\" and \"positions\" has to be the same");
         const NeighborsPtr nb = neighbors_.toCustomClass<Neighbors>();
+        if (nb->moleculeCount() > 0)
+            throw std::runtime_error("\"neighbors\" holds batched molecules (set_molecules), which are non-periodic: the convolution takes no \"box\" with them");
         if (!nb->getImpl()) throw std::runtime_error("\"neighbors\" has not been built");
         if (!nb->isPeriodic()) throw std::runtime_error("\"neighbors\" has been built without a box: a \"box\" needs a periodic neighbour list");
         Tensor output = forward(neighbors_, positions_, input_);
