@@ -285,6 +285,23 @@ int nnpops_cfconv_neighbors_build_count(nnpops_cfconv_neighbors_t h, unsigned lo
  * any non-periodic list.  The current build is invalidated (build_count() returns 0 until the next build()).  num_molecules <= 0 (or a
  * NULL table) restores the single-system list.  Blocks on the list's stream; not capturable. */
 int nnpops_cfconv_neighbors_set_molecules(nnpops_cfconv_neighbors_t h, int num_molecules, const int32_t* molecule_offsets);
+/* The plan of a convolution: which kernels a layer of this shape and these weights runs, and how they are launched.  Pure host
+ * arithmetic (no device is needed or touched); it reads the NNPOPS_CFCONV_* switches as nnpops_cfconv_create does and refuses what
+ * create refuses about the layer (NULL weights, activation, gaussian_width, num_gaussians, width).  w1, b1, w2 as for create.
+ *     out[0]  path: 0 vector kernel, 1 filters on the fp32 matrix instruction, 2 split-fp16 filters through LDS planes,
+ *             3 split-fp16 filters fed from registers (1-3: followed by the owner-computes gather, which takes no dynamic LDS)
+ *     out[1]  waves per workgroup of the forward launch (vector kernel or filters kernel)
+ *     out[2]  its dynamic LDS in bytes
+ *     out[3]  waves per workgroup of the backward launch
+ *     out[4]  its dynamic LDS in bytes
+ *     out[5]  vector path: channels per lane (1, 2, 4 or 8; the same in both directions); else 0
+ *     out[6]  vector path: bit 0 = the forward launch keeps its weights in LDS, bit 1 = the backward launch does (a clear bit:
+ *             streamed through the caches); else 0
+ *     out[7]  log2 of the power of two the split-fp16 backward kernels scale dY1 by (0 where the width has no split kernels) */
+int nnpops_cfconv_plan(int width, int num_gaussians, float gaussian_width, int activation, const float* w1, const float* b1,
+                       const float* w2, int32_t out[8]);
+/* The same eight words for a handle: what its compute() and backprop() launches use (they go through the same arithmetic). */
+int nnpops_cfconv_describe(nnpops_cfconv_t h, int32_t out[8]);
 
 /* ------------------------------------------------------------------------------------------
  * getNeighborPairs (replaces the neighbors::getNeighborPairs CUDA kernels)

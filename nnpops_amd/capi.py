@@ -72,6 +72,8 @@ SIGNATURES = {
                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_cfconv_neighbors_build_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "nnpops_cfconv_neighbors_set_molecules": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "nnpops_cfconv_plan": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "nnpops_cfconv_describe": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "nnpops_split_planes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p, C.c_long]),
     "nnpops_rows_dot": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "nnpops_gemm_split": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_long, C.c_void_p,
@@ -823,6 +825,34 @@ class CFConvNeighbors:
         return atoms[:, :P], dist[:P]
 
 
+CFCONV_PATHS = ("vector", "matrix", "split_planes", "split_registers")
+
+
+def _plan_dict(words):
+    """The eight words of nnpops_cfconv_plan / nnpops_cfconv_describe (nnpops_hip.h) by name."""
+    w = [int(v) for v in words]
+    return dict(path=CFCONV_PATHS[w[0]], waves_fwd=w[1], lds_fwd=w[2], waves_bwd=w[3], lds_bwd=w[4], channels_per_lane=w[5],
+                weights_in_lds_fwd=bool(w[6] & 1), weights_in_lds_bwd=bool(w[6] & 2), dy_scale_log2=w[7])
+
+
+def cfconv_plan(width, num_gaussians, gaussian_width, activation, w1, b1, w2):
+    """-> dict(path, waves_fwd, lds_fwd, waves_bwd, lds_bwd, channels_per_lane, weights_in_lds_fwd, weights_in_lds_bwd,
+    dy_scale_log2): the kernels a CFConv of this shape and these weights runs and how they are launched.  Host arithmetic: needs
+    no device.  Reads the NNPOPS_CFCONV_* switches as the constructor of CFConv does."""
+    act = {"ssp": 0, "tanh": 1, 0: 0, 1: 1}.get(activation)
+    if act is None:
+        raise ValueError('Invalid value of "activation"')
+    w1 = np.ascontiguousarray(w1, np.float32).reshape(-1)
+    w2 = np.ascontiguousarray(w2, np.float32).reshape(-1)
+    b1 = np.ascontiguousarray(b1, np.float32).reshape(-1)
+    if 1 <= width <= 512 and 2 <= num_gaussians <= 256:      # (other shapes are the library's to refuse; it reads nothing then)
+        assert w1.size == width * num_gaussians and w2.size == width * width and b1.size == width
+    words = (C.c_int32 * 8)()
+    _check(lib().nnpops_cfconv_plan(int(width), int(num_gaussians), gaussian_width, act, w1.ctypes.data_as(C.c_void_p),
+                                    b1.ctypes.data_as(C.c_void_p), w2.ctypes.data_as(C.c_void_p), words))
+    return _plan_dict(words)
+
+
 class CFConv:
     """Continuous-filter convolution (reference CFConv, CFConv.h:109-217).  ``w1`` is the core-level
     [width][num_gaussians] array, ``w2`` is [out][in]."""
@@ -851,6 +881,12 @@ class CFConv:
         if h:
             self._lib.nnpops_cfconv_destroy(h)
             self._h = None
+
+    def describe(self):
+        """-> the dict of cfconv_plan for this handle: what its compute() and backprop() launches use."""
+        words = (C.c_int32 * 8)()
+        _check(self._lib.nnpops_cfconv_describe(self._h, words))
+        return _plan_dict(words)
 
     def compute(self, neighbors, positions, x, box=None, out=None):
         _dev_f32(positions, "positions", (self.num_atoms, 3))

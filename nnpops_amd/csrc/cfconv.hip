@@ -18,8 +18,9 @@
 //     filter row; an OWNER-COMPUTES gather (cfconv_gather: one wave per atom, lanes = channels) then accumulates
 //     out[i] (backward: dE/dx[i], dE/dpos[i]) over the atom's full row.  No atomics, no scatter, deterministic.
 //     The filters kernel is chosen once, when the convolution is created (ConvPath):
-//       cfconv_filters_h2x2 / _h2b   W 32, 64, 96, 128 with G + 1 <= 64: both layers as split-fp16 products
-//                                    (three v_mfma_f32_16x16x32_f16 in place of eight fp32 ones), operands in registers
+//       cfconv_filters_h2x2 / _h2b   W 32, 64, 96 with G + 1 <= 64, W 128 with G <= 55 (the W1 planes beside eight waves' tiles in
+//                                    160 KiB): both layers as split-fp16 products (three v_mfma_f32_16x16x32_f16 in place of eight
+//                                    fp32 ones), operands in registers
 //       cfconv_filters_h2            the same widths with more Gaussians: layer 2 split, layer 1 on the fp32 instruction
 //       cfconv_filters_mfma          W 16, 48, 80, 112, or weights outside the fp16 range: v_mfma_f32_16x16x4_f32 (exact fp32)
 //   * other widths use the vector kernel: one wave per atom, lane = filter channel(s), pairs processed 8 at a
@@ -116,9 +117,168 @@ namespace {
 enum class ConvPath {
     kVector,            // cfconv_kernel: W not a multiple of 16, W > 128, the matrix-core weights do not fit in LDS, or $NNPOPS_CFCONV_VALU=1
     kMatrix,            // cfconv_filters_mfma (fp32 matrix instruction): W in {16, 48, 80, 112}, or weights outside the fp16 range
-    kSplitPlanes,       // cfconv_filters_h2 (layer 2 split-fp16, through LDS planes): W in {32, 64, 96, 128}, G + 1 > 64
-    kSplitRegisters,    // cfconv_filters_h2x2 / _h2b (both layers split-fp16, register-fed): W in {32, 64, 96, 128}, G + 1 <= 64
+    kSplitPlanes,       // cfconv_filters_h2 (layer 2 split-fp16, through LDS planes): W in {32, 64, 96, 128}, too many Gaussians for registers
+    kSplitRegisters,    // cfconv_filters_h2x2 / _h2b (both layers split-fp16, register-fed): W in {32, 64, 96} with G <= 63, W = 128 with G <= 55
 };
+
+// ---------------------------------------------------------------------------------------------
+// The plan of a convolution: which path, and the workgroup shape and dynamic LDS of its forward and backward launch.  Host arithmetic
+// only -- nnpops_cfconv_create, the launches below, nnpops_cfconv_plan and nnpops_cfconv_describe all go through these helpers, so what
+// the query reports is what is launched.
+// ---------------------------------------------------------------------------------------------
+// The environment switches, read by nnpops_cfconv_create and nnpops_cfconv_plan only.  Each forces a path that some shape or weights reach
+// without it.
+struct ConvSwitches {
+    bool force_valu = false;        // $NNPOPS_CFCONV_VALU=1: keep the matrix cores out (A/B timing, debugging)
+    int split_level = 2;            // $NNPOPS_CFCONV_SPLIT: 0 fp32 only, 1 second layer split, 2 both layers where possible
+    bool reuse_filters = true;      // $NNPOPS_CFCONV_REUSE_FILTERS=0: a backward call always stores its filter rows
+};
+
+ConvSwitches read_switches() {
+    ConvSwitches sw;
+    if (const char* e = std::getenv("NNPOPS_CFCONV_VALU")) sw.force_valu = std::atoi(e) != 0;
+    if (const char* e = std::getenv("NNPOPS_CFCONV_SPLIT")) sw.split_level = std::atoi(e);
+    if (const char* e = std::getenv("NNPOPS_CFCONV_REUSE_FILTERS")) sw.reuse_filters = std::atoi(e) != 0;
+    return sw;
+}
+
+// what create() and plan() refuse alike (create() has more to say about atoms, cutoff and device)
+int check_layer(int width, int num_gaussians, float gaussian_width, int activation, const float* w1, const float* b1, const float* w2) {
+    NNPOPS_REQUIRE(w1 && b1 && w2, "NULL weight pointer");
+    NNPOPS_REQUIRE(activation == 0 || activation == 1, "Invalid value of \"activation\"");
+    NNPOPS_REQUIRE(gaussian_width > 0, "gaussian_width must be positive");
+    NNPOPS_REQUIRE(num_gaussians >= 2, "num_gaussians must be at least 2 (centres are spaced cutoff/(G-1))");
+    if (width < 1 || width > kMaxWidth || num_gaussians > kMaxGauss)
+        return fail(NNPOPS_ERR_UNSUPPORTED, "this build supports width in [1, %d] and up to %d Gaussians (got %d, %d)",
+                    kMaxWidth, kMaxGauss, width, num_gaussians);
+    return NNPOPS_OK;
+}
+
+// one launch: waves per workgroup (0: its tiles do not fit in LDS) and dynamic LDS bytes; the vector kernel's instantiation
+struct LaunchShape {
+    int waves = 0;
+    size_t lds = 0;
+    int cpl = 0;                    // vector kernel: channels per lane (1, 2, 4, 8)
+    bool wlds = false;              // vector kernel: the weights sit in LDS (else they are streamed through the caches)
+};
+
+// The vector kernel of one direction: weights in LDS when they fit beside one wave's tiles (W <= 128 only), else streamed; as many waves
+// per workgroup as fit next to the shared weights in 156 KiB.
+LaunchShape vector_shape(int W, int G, bool bwd) {
+    LaunchShape s;
+    const size_t budget = 156 * 1024 / sizeof(float);
+    const size_t per_wave = conv_wave_floats(W, G, bwd);
+    s.wlds = conv_weight_floats(W, G) + per_wave <= budget && W <= 128;
+    const int cpl = div_up(W, 64);
+    s.cpl = s.wlds ? (W > 64 ? 2 : 1) : cpl <= 2 ? 2 : cpl <= 4 ? 4 : 8;
+    const size_t wfl = s.wlds ? conv_weight_floats(W, G) : 0;
+    if (wfl + per_wave > budget) return s;
+    s.waves = (int)std::min<size_t>(kMaxWavesPerBlock, (budget - wfl) / per_wave);
+    s.lds = (wfl + (size_t)s.waves * per_wave) * sizeof(float);
+    return s;
+}
+
+// waves per workgroup of cfconv_filters_h2b: one per SIMD at widths 96 / 128, two below (launch_filters says why)
+constexpr int h2b_waves(int ncb) { return ncb >= 6 ? 4 : 8; }
+
+// The filters kernel of a matrix-core path, one direction (the gather behind it takes no dynamic LDS).
+LaunchShape filters_shape(ConvPath path, int W, int G, bool bwd) {
+    LaunchShape s;
+    switch (path) {
+        case ConvPath::kSplitRegisters:
+            if (!bwd) {
+                s.waves = kMaxWavesPerBlock;
+                s.lds = h2_weight_bytes_l1h(W, G) + (size_t)s.waves * 128 * sizeof(float);
+            } else {
+                s.waves = h2b_waves(W / 16);
+                s.lds = h2_weight_bytes_l1h(W, G) + ((size_t)W + s.waves * 96) * sizeof(float);
+            }
+            break;
+        case ConvPath::kSplitPlanes: {
+            const size_t budget = 160 * 1024;
+            const size_t wb = h2_weight_bytes(W, G), per_wave = h2_wave_bytes(W);
+            s.waves = (int)std::min<size_t>(kMaxWavesPerBlock, (budget - wb) / per_wave);
+            s.lds = wb + (size_t)s.waves * per_wave;
+            break;
+        }
+        case ConvPath::kMatrix: {
+            const size_t budget = 160 * 1024 / sizeof(float);
+            const size_t wfl = mfma_weight_floats(W, G), per_wave = mfma_wave_floats_bwd(W);
+            s.waves = (int)std::min<size_t>(kMaxWavesPerBlock, (budget - wfl) / per_wave);
+            s.lds = (wfl + (size_t)s.waves * per_wave) * sizeof(float);
+            break;
+        }
+        case ConvPath::kVector:
+            return vector_shape(W, G, bwd);
+    }
+    return s;
+}
+
+// Bounds on what the split-fp16 kernels put into fp16 planes, in the scaled domain they work in (see activate_fast): the largest |W2| entry,
+// |Y1| and |dY1|
+struct SplitBounds { double max_w2 = 0, max_y = 0, max_dy = 0; };
+
+SplitBounds split_bounds(int W, int G, int activation, float gaussian_width, const float* w1, const float* b1, const float* w2) {
+    const float s1 = activation == 0 ? kLog2e : 1.0f, s2 = activation == 0 ? 1.0f / kLog2e : 1.0f;
+    SplitBounds b;
+    for (int f = 0; f < W; f++) {
+        double row = 0;
+        for (int g = 0; g < G; g++) row += std::fabs((double)s1 * w1[(size_t)f * G + g]);
+        b.max_y = std::max(b.max_y, row + std::fabs((double)s1 * b1[f]) + 1.0);     // |act(s)| <= |s| + 1 in either domain
+        b.max_dy = std::max(b.max_dy, row * 0.61 / gaussian_width);                  // |d gamma / dr| <= 0.607 / sigma, act' <= 1
+    }
+    for (size_t q = 0; q < (size_t)W * W; q++) b.max_w2 = std::max(b.max_w2, (double)std::fabs(s2 * w2[q]));
+    return b;
+}
+
+struct ConvPlan {
+    ConvPath path = ConvPath::kVector;
+    bool split_ok = false;          // the weights suit fp16 planes and $NNPOPS_CFCONV_SPLIT allows them (W in {32, 64, 96, 128})
+    bool split_l1 = false;          // layer 1 as split products too (G + 1 <= 64 and the planes fit in LDS beside eight waves' tiles)
+    int dy_log2 = 0;                // log2 of ConvParams::dy_scale
+};
+
+ConvPlan plan_conv(int W, int G, int activation, float gaussian_width, const float* w1, const float* b1, const float* w2,
+                   const ConvSwitches& sw) {
+    ConvPlan pl;
+    if (W % 32 == 0 && W <= 128) {
+        const SplitBounds b = split_bounds(W, G, activation, gaussian_width, w1, b1, w2);
+        const double limit = 3.0e4;                         // fp16 holds 65504; the low planes stay below 32 in any case
+        pl.split_ok = b.max_w2 < limit && b.max_y < limit && b.max_dy < limit && sw.split_level != 0;
+        // dY1 goes into its fp16 planes scaled to the top of the range (ConvParams::dy_scale): the largest power of two, up to 2^12,
+        // that keeps the bound on |dY1| below `limit`
+        while (pl.dy_log2 < 12 && b.max_dy * std::ldexp(1.0, pl.dy_log2 + 1) < limit) pl.dy_log2++;
+        pl.split_l1 = pl.split_ok && sw.split_level >= 2 && G + 1 <= 64 &&
+                      h2_weight_bytes_l1h(W, G) + kMaxWavesPerBlock * h2_wave_bytes(W) <= (size_t)160 * 1024;
+    }
+    // the matrix-core kernels keep both weight matrices in LDS beside at least one wave's tile; layers with very many Gaussians
+    // (W = 128: G > 172) do not fit and take the vector kernel, which streams its weights
+    const bool mfma_fits = mfma_weight_floats(W, G) + mfma_wave_floats_bwd(W) <= (size_t)160 * 1024 / sizeof(float);
+    if (sw.force_valu || W % 16 != 0 || W > 128 || !mfma_fits)
+        pl.path = ConvPath::kVector;
+    else if (pl.split_l1)
+        pl.path = ConvPath::kSplitRegisters;
+    else if (pl.split_ok && h2_weight_bytes(W, G) + h2_wave_bytes(W) <= (size_t)160 * 1024)
+        pl.path = ConvPath::kSplitPlanes;
+    else
+        pl.path = ConvPath::kMatrix;
+    return pl;
+}
+
+// the eight words of nnpops_cfconv_plan / nnpops_cfconv_describe (nnpops_hip.h)
+int plan_words(ConvPath path, int W, int G, int dy_log2, int32_t out[8]) {
+    const LaunchShape f = filters_shape(path, W, G, false), b = filters_shape(path, W, G, true);
+    if (f.waves < 1 || b.waves < 1)
+        return fail(NNPOPS_ERR_UNSUPPORTED, "CFConv tiles of width %d with %d Gaussians do not fit in LDS", W, G);
+    const bool vec = path == ConvPath::kVector;
+    out[0] = (int32_t)path;
+    out[1] = f.waves; out[2] = (int32_t)f.lds;
+    out[3] = b.waves; out[4] = (int32_t)b.lds;
+    out[5] = vec ? f.cpl : 0;
+    out[6] = vec ? (f.wlds ? 1 : 0) | (b.wlds ? 2 : 0) : 0;
+    out[7] = dy_log2;
+    return NNPOPS_OK;
+}
 }  // namespace
 
 struct nnpops_cfconv {
@@ -145,6 +305,7 @@ struct nnpops_cfconv {
     unsigned long long filt_epoch = 0;
     bool graph_seen = false;      // a filters launch of this convolution has been captured into a graph: replays write d_filt unseen
     bool reuse_filters = true;                     // $NNPOPS_CFCONV_REUSE_FILTERS=0: always store
+    int dy_log2 = 0;                               // log2 of p.dy_scale (nnpops_cfconv_describe)
     // box-gradient calls only (nnpops_cfconv_backprop_box), sized on first use like d_filt: the partial sums of the pass
     // [cfconv_box_blocks(N)][9] and, on the vector path, the pair scalar of every row entry [N][cap]
     double* d_box_partials = nullptr;
@@ -355,13 +516,9 @@ int nnpops_cfconv_create(nnpops_cfconv_t* out, int num_atoms, int width, int num
     NNPOPS_REQUIRE(out != nullptr, "out handle pointer is NULL");
     *out = nullptr;
     NNPOPS_REQUIRE(num_atoms > 0, "num_atoms must be positive");
-    NNPOPS_REQUIRE(w1 && b1 && w2 && b2, "NULL weight pointer");
-    NNPOPS_REQUIRE(activation == 0 || activation == 1, "Invalid value of \"activation\"");
-    NNPOPS_REQUIRE(cutoff > 0 && gaussian_width > 0, "cutoff and gaussian_width must be positive");
-    NNPOPS_REQUIRE(num_gaussians >= 2, "num_gaussians must be at least 2 (centres are spaced cutoff/(G-1))");
-    if (width < 1 || width > kMaxWidth || num_gaussians > kMaxGauss)
-        return fail(NNPOPS_ERR_UNSUPPORTED, "this build supports width in [1, %d] and up to %d Gaussians (got %d, %d)",
-                    kMaxWidth, kMaxGauss, width, num_gaussians);
+    NNPOPS_REQUIRE(b2 != nullptr, "NULL weight pointer");
+    NNPOPS_REQUIRE(cutoff > 0, "cutoff must be positive");
+    if (int rc = check_layer(width, num_gaussians, gaussian_width, activation, w1, b1, w2)) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(NNPOPS_ERR_NO_DEVICE, "no HIP device available");
     NNPOPS_REQUIRE(device >= 0 && device < ndev, "device %d out of range (have %d)", device, ndev);
@@ -371,12 +528,13 @@ int nnpops_cfconv_create(nnpops_cfconv_t* out, int num_atoms, int width, int num
     h->p.skip_filter_store = 0; h->p.dy_scale = 1.0f; h->p.dy_unscale = 1.0f;
     h->periodic = periodic != 0; h->device = device;
     const int W = width, G = num_gaussians;
-    // The environment switches, read here only.  Each forces a path that some shape or weights reach without it.
-    bool force_valu = false;                            // $NNPOPS_CFCONV_VALU=1: keep the matrix cores out (A/B timing, debugging)
-    int split_level = 2;                                // $NNPOPS_CFCONV_SPLIT: 0 fp32 only, 1 second layer split, 2 both layers where possible
-    if (const char* e = std::getenv("NNPOPS_CFCONV_VALU")) force_valu = std::atoi(e) != 0;
-    if (const char* e = std::getenv("NNPOPS_CFCONV_SPLIT")) split_level = std::atoi(e);
-    if (const char* e = std::getenv("NNPOPS_CFCONV_REUSE_FILTERS")) h->reuse_filters = std::atoi(e) != 0;
+    const ConvSwitches sw = read_switches();
+    h->reuse_filters = sw.reuse_filters;
+    const ConvPlan plan = plan_conv(W, G, activation, gaussian_width, w1, b1, w2, sw);
+    h->path = plan.path;
+    h->dy_log2 = plan.dy_log2;
+    h->p.dy_scale = (float)std::ldexp(1.0, plan.dy_log2);
+    h->p.dy_unscale = (float)std::ldexp(1.0, -plan.dy_log2);
     std::vector<float> w1t((size_t)G * W), w2t((size_t)W * W);
     for (int a = 0; a < W; a++)
         for (int g = 0; g < G; g++) w1t[(size_t)g * W + a] = w1[(size_t)a * G + g];        // core layout [W][G], CpuCFConv.cpp:163
@@ -407,23 +565,15 @@ int nnpops_cfconv_create(nnpops_cfconv_t* out, int num_atoms, int width, int num
             hipMemcpy(h->d_b1_s, b1s.data(), (size_t)W * 4, hipMemcpyHostToDevice) != hipSuccess)
             return cleanup(fail(NNPOPS_ERR_HIP, "weight upload failed"));
     }
-    bool split_ok = false, split_l1 = false;            // split_l1: layer 1 as split products too (G + 1 <= 64 and the planes fit in LDS)
-    if (W % 32 == 0 && W <= 128) {
-        // operands of the split-fp16 second layer, in the scaled domain the kernels work in (see activate_fast)
+    if (plan.split_ok) {
+        // operands of the split-fp16 kernels, in the scaled domain they work in (see activate_fast)
         const float s1 = activation == 0 ? kLog2e : 1.0f, s2 = activation == 0 ? 1.0f / kLog2e : 1.0f;
         const int Gq = h2_l1_rows(G);
         std::vector<float> w1b((size_t)Gq * W, 0.f);
         std::vector<_Float16> w2h((size_t)W * W), w2l((size_t)W * W);
-        double max_w2 = 0, max_y = 0, max_dy = 0;
         for (int f = 0; f < W; f++) {
-            double row = 0;
-            for (int g = 0; g < G; g++) {
-                w1b[(size_t)g * W + f] = s1 * w1[(size_t)f * G + g];
-                row += std::fabs((double)s1 * w1[(size_t)f * G + g]);
-            }
+            for (int g = 0; g < G; g++) w1b[(size_t)g * W + f] = s1 * w1[(size_t)f * G + g];
             w1b[(size_t)G * W + f] = s1 * b1[f];
-            max_y = std::max(max_y, row + std::fabs((double)s1 * b1[f]) + 1.0);     // |act(s)| <= |s| + 1 in either domain
-            max_dy = std::max(max_dy, row * 0.61 / gaussian_width);                  // |d gamma / dr| <= 0.607 / sigma, act' <= 1
         }
         for (int f2 = 0; f2 < W; f2++)
             for (int k = 0; k < W; k++) {
@@ -431,20 +581,8 @@ int nnpops_cfconv_create(nnpops_cfconv_t* out, int num_atoms, int width, int num
                 const _Float16 hi = (_Float16)v;
                 w2h[(size_t)f2 * W + k] = hi;
                 w2l[(size_t)f2 * W + k] = (_Float16)((v - (float)hi) * kLoScale);
-                max_w2 = std::max(max_w2, (double)std::fabs(v));
             }
-        const double limit = 3.0e4;                         // fp16 holds 65504; the low planes stay below 32 in any case
-        split_ok = max_w2 < limit && max_y < limit && max_dy < limit && split_level != 0;
-        {   // dY1 goes into its fp16 planes scaled to the top of the range (ConvParams::dy_scale): the largest power of two, up to 2^12,
-            // that keeps the bound on |dY1| below `limit`
-            int k = 0;
-            while (k < 12 && max_dy * std::ldexp(1.0, k + 1) < limit) k++;
-            h->p.dy_scale = (float)std::ldexp(1.0, k);
-            h->p.dy_unscale = (float)std::ldexp(1.0, -k);
-        }
-        split_l1 = split_ok && split_level >= 2 && G + 1 <= 64 &&
-                   h2_weight_bytes_l1h(W, G) + kMaxWavesPerBlock * h2_wave_bytes(W) <= (size_t)160 * 1024;
-        if (split_l1) {
+        if (plan.split_l1) {
             const int rowh = h2_l1_row_bytes(G) / 2;        // halves per plane row
             std::vector<_Float16> w1h((size_t)W * rowh, (_Float16)0.f), w1l((size_t)W * rowh, (_Float16)0.f);
             for (int f = 0; f < W; f++)
@@ -460,31 +598,31 @@ int nnpops_cfconv_create(nnpops_cfconv_t* out, int num_atoms, int width, int num
                 hipMemcpy(h->d_w1l, w1l.data(), w1l.size() * 2, hipMemcpyHostToDevice) != hipSuccess)
                 return cleanup(fail(NNPOPS_ERR_HIP, "weight upload failed"));
         }
-        if (split_ok) {
-            if ((rc = dev_alloc(&h->d_w1b, w1b.size()))) return cleanup(rc);
-            if ((rc = dev_alloc(&h->d_w2h, w2h.size()))) return cleanup(rc);
-            if ((rc = dev_alloc(&h->d_w2l, w2l.size()))) return cleanup(rc);
-            if (hipMemcpy(h->d_w1b, w1b.data(), w1b.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(h->d_w2h, w2h.data(), w2h.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(h->d_w2l, w2l.data(), w2l.size() * 2, hipMemcpyHostToDevice) != hipSuccess)
-                return cleanup(fail(NNPOPS_ERR_HIP, "weight upload failed"));
-        }
+        if ((rc = dev_alloc(&h->d_w1b, w1b.size()))) return cleanup(rc);
+        if ((rc = dev_alloc(&h->d_w2h, w2h.size()))) return cleanup(rc);
+        if ((rc = dev_alloc(&h->d_w2l, w2l.size()))) return cleanup(rc);
+        if (hipMemcpy(h->d_w1b, w1b.data(), w1b.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(h->d_w2h, w2h.data(), w2h.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(h->d_w2l, w2l.data(), w2l.size() * 2, hipMemcpyHostToDevice) != hipSuccess)
+            return cleanup(fail(NNPOPS_ERR_HIP, "weight upload failed"));
     }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) h->blocks = prop.multiProcessorCount;
-    // the matrix-core kernels keep both weight matrices in LDS beside at least one wave's tile; layers with very many Gaussians
-    // (W = 128: G > ~180) do not fit and take the vector kernel, which streams its weights
-    const bool mfma_fits = mfma_weight_floats(W, G) + mfma_wave_floats_bwd(W) <= (size_t)160 * 1024 / sizeof(float);
-    if (force_valu || W % 16 != 0 || W > 128 || !mfma_fits)
-        h->path = ConvPath::kVector;
-    else if (split_l1)
-        h->path = ConvPath::kSplitRegisters;
-    else if (split_ok && h2_weight_bytes(W, G) + h2_wave_bytes(W) <= (size_t)160 * 1024)
-        h->path = ConvPath::kSplitPlanes;
-    else
-        h->path = ConvPath::kMatrix;
     *out = h;
     return NNPOPS_OK;
+}
+
+int nnpops_cfconv_plan(int width, int num_gaussians, float gaussian_width, int activation, const float* w1, const float* b1,
+                       const float* w2, int32_t out[8]) {
+    NNPOPS_REQUIRE(out != nullptr, "out pointer is NULL");
+    if (int rc = check_layer(width, num_gaussians, gaussian_width, activation, w1, b1, w2)) return rc;
+    const ConvPlan plan = plan_conv(width, num_gaussians, activation, gaussian_width, w1, b1, w2, read_switches());
+    return plan_words(plan.path, width, num_gaussians, plan.dy_log2, out);
+}
+
+int nnpops_cfconv_describe(nnpops_cfconv_t h, int32_t out[8]) {
+    NNPOPS_REQUIRE(h != nullptr && out != nullptr, "NULL argument");
+    return plan_words(h->path, h->p.W, h->p.G, h->dy_log2, out);
 }
 
 int nnpops_cfconv_destroy(nnpops_cfconv_t h) {
@@ -511,13 +649,12 @@ namespace {
 // (ROW_S: the pair scalar of every row entry to h->d_row_s and nothing else, for a box-gradient call)
 template <int ACT, int CPL, bool BWD, bool WLDS = true, bool ROW_S = false>
 int launch_conv(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, const float* x, const float* gout, float* out, float* pos_grad) {
-    // as many waves per workgroup as fit next to the shared weights in 160 KiB of LDS
-    const size_t budget = 156 * 1024 / sizeof(float);
-    const size_t wfl = WLDS ? conv_weight_floats(h->p.W, h->p.G) : 0, per_wave = conv_wave_floats(h->p.W, h->p.G, BWD);
-    if (wfl + per_wave > budget)
-        return fail(NNPOPS_ERR_UNSUPPORTED, "CFConv tiles (%zu floats) do not fit in LDS", wfl + per_wave);
-    const int wpb = (int)std::min<size_t>(kMaxWavesPerBlock, (budget - wfl) / per_wave);
-    const size_t lds = (wfl + (size_t)wpb * per_wave) * sizeof(float);
+    // as many waves per workgroup as fit next to the shared weights (vector_shape, which also chose this instantiation)
+    const LaunchShape shape = vector_shape(h->p.W, h->p.G, BWD);
+    if (shape.waves < 1 || shape.wlds != WLDS || shape.cpl != CPL)
+        return fail(NNPOPS_ERR_UNSUPPORTED, "CFConv tiles of width %d with %d Gaussians do not fit in LDS", h->p.W, h->p.G);
+    const int wpb = shape.waves;
+    const size_t lds = shape.lds;
     auto k = cfconv_kernel<ACT, CPL, BWD, WLDS, ROW_S>;
     if (lds > 64 * 1024)
         NNPOPS_HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -531,15 +668,14 @@ int launch_conv(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, const float* x, c
 // the vector kernels: weights in LDS when they fit beside one wave's tiles, else streamed through the caches
 template <bool BWD, bool ROW_S = false>
 int launch_vector(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, const float* x, const float* gout, float* out, float* pos_grad) {
-    const size_t budget = 156 * 1024 / sizeof(float);
-    const bool fits = conv_weight_floats(h->p.W, h->p.G) + conv_wave_floats(h->p.W, h->p.G, BWD) <= budget && h->p.W <= 128;
-    if (fits) {
-        const bool two = h->p.W > 64;
+    const LaunchShape shape = vector_shape(h->p.W, h->p.G, BWD);
+    if (shape.wlds) {
+        const bool two = shape.cpl == 2;
         if (h->p.activation == 0)
             return two ? launch_conv<0, 2, BWD, true, ROW_S>(h, nb, x, gout, out, pos_grad) : launch_conv<0, 1, BWD, true, ROW_S>(h, nb, x, gout, out, pos_grad);
         return two ? launch_conv<1, 2, BWD, true, ROW_S>(h, nb, x, gout, out, pos_grad) : launch_conv<1, 1, BWD, true, ROW_S>(h, nb, x, gout, out, pos_grad);
     }
-    const int cpl = div_up(h->p.W, 64);
+    const int cpl = shape.cpl;
     if (h->p.activation == 0) {
         if (cpl <= 2) return launch_conv<0, 2, BWD, false, ROW_S>(h, nb, x, gout, out, pos_grad);
         if (cpl <= 4) return launch_conv<0, 4, BWD, false, ROW_S>(h, nb, x, gout, out, pos_grad);
@@ -575,6 +711,7 @@ int ensure_half_path(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb) {
 template <int ACT, int NCB, bool BWD>
 int launch_filters(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, const ConvParams& cp, const float* x, const float* gout) {
     const int pair_cap = nb->pair_cap();
+    const LaunchShape shape = filters_shape(h->path, h->p.W, h->p.G, BWD);     // waves per workgroup and LDS: what describe() reports
     switch (h->path) {
         case ConvPath::kSplitRegisters:
             if constexpr (NCB % 2 == 0 && !BWD) {
@@ -583,8 +720,8 @@ int launch_filters(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, const ConvPara
                 //  154 registers -- 50.5 us; on 16 waves, spilling, 68.6 us: the weight reads a second tile shares are worth more than a third wave)
                 // (... and on FOUR waves -- one per SIMD, 512 registers -- two tiles per pass 57.0 us, four tiles per pass 84.8 us)
                 auto k2 = cfconv_filters_h2x2<ACT, NCB, 2, kMaxWavesPerBlock>;
-                const int wv = kMaxWavesPerBlock;
-                const size_t lds2 = h2_weight_bytes_l1h(h->p.W, h->p.G) + (size_t)wv * 128 * sizeof(float);
+                const int wv = shape.waves;                  // (kMaxWavesPerBlock, the kernel's launch bound)
+                const size_t lds2 = shape.lds;
                 if (lds2 > 64 * 1024)
                     NNPOPS_HIP_TRY(hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
                 hipLaunchKernelGGL(k2, dim3(h->blocks), dim3(64 * wv), lds2, h->stream, cp, h->d_w1h, h->d_w1l, h->d_w2h, h->d_w2l,
@@ -596,9 +733,9 @@ int launch_filters(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, const ConvPara
                 // fragments and the x / gout rows of its pair: ~410 registers.  With two waves per SIMD (256 each) it spills 444 bytes
                 // per lane and takes 206 us; with one, nothing is spilled: 99 us (the round-5 four-pass kernel, two waves per SIMD:
                 // 125.5 us).  Widths below 96 fit two waves per SIMD.
-                constexpr int wv = NCB >= 6 ? 4 : 8;
+                constexpr int wv = h2b_waves(NCB);
                 auto k2 = cfconv_filters_h2b<ACT, NCB, wv>;
-                const size_t lds2 = h2_weight_bytes_l1h(h->p.W, h->p.G) + ((size_t)h->p.W + wv * 96) * sizeof(float);
+                const size_t lds2 = shape.lds;
                 if (lds2 > 64 * 1024)
                     NNPOPS_HIP_TRY(hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
                 hipLaunchKernelGGL(k2, dim3(h->blocks), dim3(64 * wv), lds2, h->stream, cp, h->d_w1h, h->d_w1l, h->d_w2h, h->d_w2l,
@@ -608,10 +745,8 @@ int launch_filters(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, const ConvPara
             break;
         case ConvPath::kSplitPlanes:
             if constexpr (NCB % 2 == 0) {
-                const size_t budget = 160 * 1024;
-                const size_t wb = h2_weight_bytes(h->p.W, h->p.G), per_wave = h2_wave_bytes(h->p.W);
-                const int wpb = (int)std::min<size_t>(kMaxWavesPerBlock, (budget - wb) / per_wave);
-                const size_t lds = wb + (size_t)wpb * per_wave;
+                const int wpb = shape.waves;
+                const size_t lds = shape.lds;
                 auto k = cfconv_filters_h2<ACT, NCB, BWD>;
                 if (lds > 64 * 1024)
                     NNPOPS_HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -622,10 +757,8 @@ int launch_filters(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, const ConvPara
             }
             break;
         case ConvPath::kMatrix: {
-            const size_t budget = 160 * 1024 / sizeof(float);
-            const size_t wfl = mfma_weight_floats(h->p.W, h->p.G), per_wave = mfma_wave_floats_bwd(h->p.W);
-            const int wpb = (int)std::min<size_t>(kMaxWavesPerBlock, (budget - wfl) / per_wave);
-            const size_t lds = (wfl + (size_t)wpb * per_wave) * sizeof(float);
+            const int wpb = shape.waves;
+            const size_t lds = shape.lds;
             auto k = cfconv_filters_mfma<ACT, NCB, BWD>;
             if (lds > 64 * 1024)
                 NNPOPS_HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

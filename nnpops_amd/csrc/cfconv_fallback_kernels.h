@@ -5,8 +5,8 @@
 //                         (its ROW_S instantiations, launched by box-gradient calls only, store the pair scalar of every row entry)
 //   cfconv_filters_mfma   filters on the fp32 matrix instruction: widths 16, 48, 80, 112, weights outside the fp16 range, or
 //                         $NNPOPS_CFCONV_SPLIT=0
-//   cfconv_filters_h2     filters with layer 2 as split-fp16 products through LDS planes: widths 32, 64, 96, 128 with more than
-//                         63 Gaussians, or $NNPOPS_CFCONV_SPLIT=1
+//   cfconv_filters_h2     filters with layer 2 as split-fp16 products through LDS planes: widths 32, 64, 96 with more than 63 Gaussians,
+//                         width 128 with more than 55 (and up to 171), or $NNPOPS_CFCONV_SPLIT=1
 // Both filters kernels feed cfconv_gather.  Included by cfconv.hip only.
 #pragma once
 
@@ -443,8 +443,8 @@ __global__ __launch_bounds__(64 * kMaxWavesPerBlock) void cfconv_filters_mfma(
 // split, and a SMALLER error against a double-precision product (1.6e-6 against 3.8e-6 at |y| ~ 9: exact fp16
 // products summed in fp32 versus a chain of 128 rounded fp32 FMAs).  The host only takes this kernel when the weights
 // bound every operand below the fp16 range (nnpops_cfconv_create); $NNPOPS_CFCONV_SPLIT=0 keeps the all-fp32 one.
-// This kernel splits layer 2 only; where layer 1 can be split too (G + 1 <= 64) the register-fed kernels below take over
-// (cfconv_filters_h2x2 / cfconv_filters_h2b), so it serves G >= 64 and $NNPOPS_CFCONV_SPLIT=1.
+// This kernel splits layer 2 only; where layer 1 can be split too (G + 1 <= 64 and, at W = 128, G <= 55: plan_conv in cfconv.hip) the
+// register-fed kernels take over (cfconv_filters_h2x2 / cfconv_filters_h2b), so it serves the Gaussians beyond and $NNPOPS_CFCONV_SPLIT=1.
 //   layer 1   is computed TRANSPOSED (rows = filters, columns = pairs), so a lane ends up with four consecutive filters
 //             of one pair -- after the activation exactly the 8-byte groups the A planes of layer 2 are written in.  b1
 //             rides along as one more K index against a constant 1.  v_mfma_f32_16x16x4_f32 with the operands swapped.
