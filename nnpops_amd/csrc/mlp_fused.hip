@@ -239,7 +239,8 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_forward(const MlpArgs g) {
         // staging role: thread -> (atom a = tid / 8, piece = tid % 8): four consecutive columns, one 8-byte half of a fragment slot
         const int sa = tid >> 3, piece = tid & 7;
         const int srow = g.rows[kd.first + min(r0 + sa, kd.n - 1)];
-        const float* xsrc = g.x + (size_t)srow * g.ldx + (piece & 3) * 4;
+        // (a piece past F re-reads block 0 of the row, times 0: its columns are clamped into F for F = 8, where block 0 is half a block)
+        const float* xsrc = g.x + (size_t)srow * g.ldx + min((piece & 3) * 4, g.F - 4);
         char* xdst = xstage + ((sa >> 4) * 2) * 1024 + ((sa & 15) + 16 * (piece >> 1)) * 16 + 8 * (piece & 1);
         // (the loaded columns are NOT touched before they are staged one step later: an instruction that consumes them right
         //  after the load makes the compiler wait for EVERY outstanding load there -- s_waitcnt vmcnt(0) after each barrier,

@@ -4,41 +4,13 @@ The function is the reference's TorchANIBatchedNN (src/pytorch/BatchedNN.py:100-
 between, summed) and its gradient with respect to the AEV (BatchedNN.cpp:41-47 applied four times by autograd).  Bars:
 north_star's 1e-5 on energies; gradients 1e-4 of the largest component (they become forces through the AEV backward).
 """
-import numpy as np
 import pytest
 import torch
 
+from mlp_float64 import host_reference as _host_reference, networks as _networks
+
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
-
-
-def _networks(widths, members, features, seed, scale=1.0):
-    gen = torch.Generator().manual_seed(seed)
-    h1, h2, h3 = widths
-    def rnd(*shape, fan):
-        return (scale * torch.randn(shape, generator=gen) / np.sqrt(fan)).float()
-    return dict(w0=rnd(members, h1, features, fan=features), b0=0.1 * torch.randn((members, h1), generator=gen),
-                w2=rnd(members, h2, h1, fan=h1), b2=0.1 * torch.randn((members, h2), generator=gen),
-                w4=rnd(members, h3, h2, fan=h2), b4=0.1 * torch.randn((members, h3), generator=gen),
-                w6=rnd(members, h3, fan=h3), b6=0.1 * torch.randn((members,), generator=gen))
-
-
-def _host_reference(kinds, x):
-    """-> per (grouped atom, member) energies [n, M] and dE_total/dx [atoms, F], float64."""
-    xd = x.double().requires_grad_(True)
-    outs = []
-    for kd in kinds:
-        xs = xd[kd["atoms"].long()]
-        per_member = []
-        for m in range(kd["w0"].shape[0]):
-            y = torch.nn.functional.celu(xs @ kd["w0"][m].double().t() + kd["b0"][m].double(), alpha=0.1)
-            y = torch.nn.functional.celu(y @ kd["w2"][m].double().t() + kd["b2"][m].double(), alpha=0.1)
-            y = torch.nn.functional.celu(y @ kd["w4"][m].double().t() + kd["b4"][m].double(), alpha=0.1)
-            per_member.append(y @ kd["w6"][m].double() + kd["b6"][m].double())
-        outs.append(torch.stack(per_member, dim=1))
-    e = torch.cat(outs, dim=0)
-    e.sum().backward()
-    return e.detach(), xd.grad
 
 
 def _run(kinds_host, x_host, features, act_scale_log2=4):
