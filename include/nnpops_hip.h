@@ -15,6 +15,8 @@
  *   nnpops_cfconv_create / compute / backprop   CFConv ctor / compute / backprop   src/schnet/CFConv.h:109-217
  *   nnpops_cfconv_backprop_box       (additive) backprop and the box-vector gradient of a periodic list
  *   nnpops_cfconv_double_backward    (additive) the backward of backprop: second derivatives w.r.t. positions and input
+ *   nnpops_cfconv_backprop_weights / _set_weights   (additive) gradients of the filter network's four weight arrays; new weights for a
+ *                                               live handle (trainable filters)
  *   nnpops_neighbor_pairs_forward / _backward   neighbors::getNeighborPairs forward/backward kernels
  *                                               src/pytorch/neighbors/getNeighborPairsCUDA.cu:31-101
  *   nnpops_neighbor_pairs_box_backward / _double_backward   box gradient and second derivatives of that op
@@ -302,6 +304,26 @@ int nnpops_cfconv_plan(int width, int num_gaussians, float gaussian_width, int a
                        const float* w2, int32_t out[8]);
 /* The same eight words for a handle: what its compute() and backprop() launches use (they go through the same arithmetic). */
 int nnpops_cfconv_describe(nnpops_cfconv_t h, int32_t out[8]);
+/* The gradients of a scalar L with respect to the filter network's four weight arrays, given output_deriv = dL/doutput [N][W] of
+ * nnpops_cfconv_compute on the list's last build():
+ *     w1_deriv [W][G],   b1_deriv [W],   w2_deriv [W][W] ([out][in]),   b2_deriv [W]       (the layouts create() takes)
+ * All pointers are device pointers and none may be NULL; the four outputs are fully overwritten.  Only the list's stored distances,
+ * input and output_deriv are read, so periodic and batched lists work as they are.  First derivatives only: nothing here is
+ * differentiated further.  One kernel over the pair slots (the fp32 matrix instruction where the width is a multiple of 16 up to 128
+ * and the weights fit in LDS, a vector kernel otherwise, whatever path the forward runs) writes one partial row per workgroup, a
+ * second adds the rows in a fixed order in float64: no atomics, two calls agree bit for bit, a list without pairs gives exact
+ * zeros.  Runs on the convolution's stream with no host synchronisation; its scratch (the partial rows, at most 32 MiB) is allocated by
+ * the first call and sized once, so run one step before capturing a HIP graph.  What compute / backprop keep between calls (the
+ * filter rows) is left untouched. */
+int nnpops_cfconv_backprop_weights(nnpops_cfconv_t h, nnpops_cfconv_neighbors_t neighbors, const float* input, const float* output_deriv,
+                                   float* w1_deriv, float* b1_deriv, float* w2_deriv, float* b2_deriv);
+/* New weights for a live convolution (after an optimizer step): four HOST arrays exactly as nnpops_cfconv_create takes them.  The plan
+ * is made again from the new values (the split-fp16 decision and word 7 depend on them; nnpops_cfconv_describe reports the new plan),
+ * every packed form create() uploads is uploaded again and the kept filter rows are forgotten: the handle then computes, bit for
+ * bit, what a fresh handle created with these weights computes.  It waits for the handle's stream and copies synchronously: it blocks
+ * and cannot be captured into a HIP graph (a captured graph of this handle keeps launching the kernels of the plan it was captured
+ * with: capture again after a change of plan). */
+int nnpops_cfconv_set_weights(nnpops_cfconv_t h, const float* w1, const float* b1, const float* w2, const float* b2);
 
 /* ------------------------------------------------------------------------------------------
  * getNeighborPairs (replaces the neighbors::getNeighborPairs CUDA kernels)

@@ -77,10 +77,33 @@ public:
         posDeriv.finish();
     }
 
+    // Additive (no counterpart in the reference's CFConv): the gradients of the filter network's four weight arrays for outputDeriv =
+    // dL/doutput on the list's last build, host arrays in the layouts the constructor takes (nnpops_cfconv_backprop_weights) ...
+    void backpropWeights(const CFConvNeighbors& neighbors, const float* input, const float* outputDeriv, float* w1Deriv, float* b1Deriv,
+                         float* w2Deriv, float* b2Deriv) {
+        using namespace nnpops_integration;
+        const size_t n = (size_t)getNumAtoms(), w = (size_t)getWidth(), g = (size_t)getNumGaussians();
+        const float* dIn = in.in(input, n * w);
+        const float* dOutDeriv = outDeriv.in(outputDeriv, n * w);
+        float* dW1 = w1Grad.out(w1Deriv, w * g);
+        float* dB1 = b1Grad.out(b1Deriv, w);
+        float* dW2 = w2Grad.out(w2Deriv, w * w);
+        float* dB2 = b2Grad.out(b2Deriv, w);
+        abiTry(nnpops_cfconv_backprop_weights(handle, hip(neighbors), dIn, dOutDeriv, dW1, dB1, dW2, dB2));
+        hipTry(hipDeviceSynchronize(), "backpropWeights");
+        w1Grad.finish(); b1Grad.finish(); w2Grad.finish(); b2Grad.finish();
+    }
+
+    // ... and new weights for this convolution after an optimizer step (nnpops_cfconv_set_weights: host arrays as for the constructor;
+    // blocks, plans again)
+    void setWeights(const float* w1, const float* b1, const float* w2, const float* b2) {
+        nnpops_integration::abiTry(nnpops_cfconv_set_weights(handle, w1, b1, w2, b2));
+    }
+
 private:
     static nnpops_cfconv_neighbors_t hip(const CFConvNeighbors& neighbors) {
         return dynamic_cast<const HipCFConvNeighbors&>(neighbors).getHandle();      // CudaCFConv does the same cast
     }
     nnpops_cfconv_t handle = nullptr;
-    nnpops_integration::DeviceMirror pos, box, in, out, outDeriv, inDeriv, posDeriv;
+    nnpops_integration::DeviceMirror pos, box, in, out, outDeriv, inDeriv, posDeriv, w1Grad, b1Grad, w2Grad, b2Grad;
 };

@@ -17,6 +17,13 @@ differentiated once more with respect to positions and input -- ``torch.autograd
 ``loss.backward()``, or a Hessian-vector product.  Forward and first backward are those of the default layer, bit for bit; the box
 gets no gradient from it, and the list must not be rebuilt between the forward pass and the last derivative.  The default layer's
 backward is not differentiable: under ``create_graph=True`` its share of the second derivative is missing.
+
+Trainable filters (an extension): ``CFConv(..., trainable=True)`` turns the four arrays into ``torch.nn.Parameter``s (``weights1``,
+``biases1``, ``weights2``, ``biases2``, with the shapes the constructor takes) that receive gradients from ``backward()``; the
+convolution's own handle is given the new values on the first forward pass after an optimizer step, ``load_state_dict`` or
+``.to(device)``, and nothing is copied while they stand.  Forward and the gradients in positions, input and box are those of the
+default layer, bit for bit.  First derivatives only: ``create_graph=True`` raises, and so does ``trainable=True`` together with
+``twice_differentiable=True`` (mixed second derivatives with respect to the weights are not implemented).
 """
 from typing import Optional
 
@@ -32,12 +39,30 @@ torch_binding.load()
 class CFConv(torch.nn.Module):
 
     def __init__(self, gaussianWidth: float, activation: str, weights1: Tensor, biases1: Tensor, weights2: Tensor,
-                 biases2: Tensor, twice_differentiable: bool = False) -> None:
+                 biases2: Tensor, twice_differentiable: bool = False, trainable: bool = False) -> None:
         super().__init__()
+        if trainable and twice_differentiable:
+            raise ValueError("CFConv: trainable=True cannot be combined with twice_differentiable=True: mixed second derivatives with "
+                             "respect to the filter network's weights (a force loss differentiated with respect to them) are not "
+                             "implemented")
         self.twice_differentiable = twice_differentiable
+        self.trainable = trainable
+        if trainable:
+            new = lambda t: torch.nn.Parameter(t.detach().to(torch.float32).clone().contiguous())
+            self.weights1, self.biases1 = new(weights1), new(biases1)
+            self.weights2, self.biases2 = new(weights2), new(biases2)
+        else:       # (attributes of the same names and types, for scripting; not parameters, not in the state_dict, never read)
+            self.weights1, self.biases1 = torch.empty(0), torch.empty(0)
+            self.weights2, self.biases2 = torch.empty(0), torch.empty(0)
         self.holder = torch.classes.NNPOpsCFConv.Holder(gaussianWidth, activation, weights1, biases1, weights2, biases2)
 
     def forward(self, neighbors: CFConvNeighbors, positions: Tensor, input: Tensor, box: Optional[Tensor] = None) -> Tensor:
+        if self.trainable:
+            if box is None:
+                return torch.ops.NNPOpsCFConv.operation_weights(self.holder, neighbors.holder, positions, input, self.weights1,
+                                                                self.biases1, self.weights2, self.biases2)
+            return torch.ops.NNPOpsCFConv.operation_periodic_weights(self.holder, neighbors.holder, positions, box, input, self.weights1,
+                                                                     self.biases1, self.weights2, self.biases2)
         if self.twice_differentiable:
             if box is None:
                 return torch.ops.NNPOpsCFConv.operation_twice(self.holder, neighbors.holder, positions, input)

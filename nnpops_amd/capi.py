@@ -74,6 +74,9 @@ SIGNATURES = {
     "nnpops_cfconv_neighbors_set_molecules": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "nnpops_cfconv_plan": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "nnpops_cfconv_describe": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "nnpops_cfconv_backprop_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]),
+    "nnpops_cfconv_set_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_split_planes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p, C.c_long]),
     "nnpops_rows_dot": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "nnpops_gemm_split": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_long, C.c_void_p,
@@ -941,6 +944,31 @@ class CFConv:
         _check(self._lib.nnpops_cfconv_double_backward(self._h, neighbors._h, _ptr(positions), _ptr(x), _ptr(out_grad), _ptr(gg_x),
                                                        _ptr(gg_pos), _ptr(d_out_grad), _ptr(d_x), _ptr(d_pos)))
         return d_out_grad, d_x, d_pos
+
+    def backprop_weights(self, neighbors, x, out_grad):
+        """The gradients of the filter network's weights for ``out_grad`` = dL/d(output of compute) on the list's last build()
+        -> (w1_grad [width][num_gaussians], b1_grad, w2_grad [out][in], b2_grad), float32 on the device."""
+        _dev_f32(x, "input", (self.num_atoms, self.width))
+        _dev_f32(out_grad, "output_grad", (self.num_atoms, self.width))
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x.device)
+        w1_grad, b1_grad = new(self.width, self.num_gaussians), new(self.width)
+        w2_grad, b2_grad = new(self.width, self.width), new(self.width)
+        _check(self._lib.nnpops_cfconv_set_stream(self._h, _stream_ptr(x.device)))
+        _check(self._lib.nnpops_cfconv_backprop_weights(self._h, neighbors._h, _ptr(x), _ptr(out_grad), _ptr(w1_grad), _ptr(b1_grad),
+                                                        _ptr(w2_grad), _ptr(b2_grad)))
+        return w1_grad, b1_grad, w2_grad, b2_grad
+
+    def set_weights(self, w1, b1, w2, b2):
+        """New weights for this handle (host arrays as the constructor takes them): the plan is made again and every packed form
+        uploaded again, as for a fresh handle.  Blocks on the handle's stream."""
+        w1 = np.ascontiguousarray(w1, np.float32).reshape(-1)
+        w2 = np.ascontiguousarray(w2, np.float32).reshape(-1)
+        b1 = np.ascontiguousarray(b1, np.float32).reshape(-1)
+        b2 = np.ascontiguousarray(b2, np.float32).reshape(-1)
+        assert w1.size == self.width * self.num_gaussians and w2.size == self.width * self.width
+        assert b1.size == self.width and b2.size == self.width
+        _check(self._lib.nnpops_cfconv_set_weights(self._h, w1.ctypes.data_as(C.c_void_p), b1.ctypes.data_as(C.c_void_p),
+                                                   w2.ctypes.data_as(C.c_void_p), b2.ctypes.data_as(C.c_void_p)))
 
 
 # ---- dense layers (batched_nn.hip) ----

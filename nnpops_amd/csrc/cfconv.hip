@@ -33,6 +33,9 @@
 // that pass leaves on the device (cfconv_box_grad.h).
 // nnpops_cfconv_double_backward is the backward of the backward pass with respect to output_deriv, input and positions: one
 // owner-computes pass over the full rows that keeps nothing between calls (cfconv_second_order.h).
+// nnpops_cfconv_backprop_weights returns the gradients of the filter network's four weight arrays: one pass over the pair slots that
+// writes a partial row per workgroup, and the float64 sum of the rows (cfconv_weight_grad.h); nnpops_cfconv_set_weights
+// gives a live handle new weights through plan_and_upload, the planning and upload block it shares with nnpops_cfconv_create.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -46,6 +49,7 @@
 #include "cfconv_fallback_kernels.h"
 #include "cfconv_filters.h"
 #include "cfconv_second_order.h"
+#include "cfconv_weight_grad.h"
 
 using namespace nnpops;
 
@@ -288,6 +292,8 @@ struct nnpops_cfconv {
     int device = 0;
     hipStream_t stream = nullptr;
     float *d_w1t = nullptr, *d_b1 = nullptr, *d_w2t = nullptr, *d_b2 = nullptr;
+    float* d_w2 = nullptr;          // W2 as given, [out][in]: the weight-gradient kernels (cfconv_weight_grad.h)
+    float gaussian_width = 0;       // as given to create(): plan_conv's bounds are recomputed from it by set_weights()
     // shifted softplus on the matrix-core path: log2(e) folded into layer 1 and ln(2) into W2, so that the
     // activation is exp2 / fma / log2 with no scaling multiplies (see activate_fast)
     float *d_w1t_s = nullptr, *d_b1_s = nullptr, *d_w2t_s = nullptr;
@@ -311,6 +317,10 @@ struct nnpops_cfconv {
     double* d_box_partials = nullptr;
     float* d_row_s = nullptr;
     size_t row_s_len = 0;
+    // weight-gradient calls only (nnpops_cfconv_backprop_weights), sized once on first use: the workgroups' partial sums
+    // [wgrad_blocks][W (W + G + 2)]
+    float* d_wgrad_partials = nullptr;
+    int wgrad_blocks = 0;
 };
 
 extern "C" {
@@ -510,27 +520,16 @@ int nnpops_cfconv_neighbors_export(nnpops_cfconv_neighbors_t h, int capacity, in
     return NNPOPS_OK;
 }
 
-int nnpops_cfconv_create(nnpops_cfconv_t* out, int num_atoms, int width, int num_gaussians, float cutoff, int periodic,
-                         float gaussian_width, int activation, const float* w1, const float* b1, const float* w2,
-                         const float* b2, int device) {
-    NNPOPS_REQUIRE(out != nullptr, "out handle pointer is NULL");
-    *out = nullptr;
-    NNPOPS_REQUIRE(num_atoms > 0, "num_atoms must be positive");
-    NNPOPS_REQUIRE(b2 != nullptr, "NULL weight pointer");
-    NNPOPS_REQUIRE(cutoff > 0, "cutoff must be positive");
-    if (int rc = check_layer(width, num_gaussians, gaussian_width, activation, w1, b1, w2)) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(NNPOPS_ERR_NO_DEVICE, "no HIP device available");
-    NNPOPS_REQUIRE(device >= 0 && device < ndev, "device %d out of range (have %d)", device, ndev);
-    auto* h = new nnpops_cfconv();
-    h->p.N = num_atoms; h->p.W = width; h->p.G = num_gaussians; h->p.cutoff = cutoff;
-    h->p.sigma_inv = 1.0f / gaussian_width; h->p.activation = activation;
-    h->p.skip_filter_store = 0; h->p.dy_scale = 1.0f; h->p.dy_unscale = 1.0f;
-    h->periodic = periodic != 0; h->device = device;
-    const int W = width, G = num_gaussians;
+}  // extern "C"
+
+// What a convolution derives from its four weight arrays: the plan (path, dy_log2) and every packed form on the device.  Shared by
+// nnpops_cfconv_create and nnpops_cfconv_set_weights, so that a handle given new weights holds what a fresh one would.  Buffers are
+// allocated on first need and kept (their sizes depend on W and G alone); the caller holds the device and has drained the stream.
+static int plan_and_upload(nnpops_cfconv* h, const float* w1, const float* b1, const float* w2, const float* b2) {
+    const int W = h->p.W, G = h->p.G, activation = h->p.activation;
     const ConvSwitches sw = read_switches();
     h->reuse_filters = sw.reuse_filters;
-    const ConvPlan plan = plan_conv(W, G, activation, gaussian_width, w1, b1, w2, sw);
+    const ConvPlan plan = plan_conv(W, G, activation, h->gaussian_width, w1, b1, w2, sw);
     h->path = plan.path;
     h->dy_log2 = plan.dy_log2;
     h->p.dy_scale = (float)std::ldexp(1.0, plan.dy_log2);
@@ -540,30 +539,30 @@ int nnpops_cfconv_create(nnpops_cfconv_t* out, int num_atoms, int width, int num
         for (int g = 0; g < G; g++) w1t[(size_t)g * W + a] = w1[(size_t)a * G + g];        // core layout [W][G], CpuCFConv.cpp:163
     for (int a = 0; a < W; a++)
         for (int b = 0; b < W; b++) w2t[(size_t)b * W + a] = w2[(size_t)a * W + b];        // [out][in], CpuCFConv.cpp:174
-    DeviceGuard guard(device);
     int rc;
-    auto cleanup = [&](int code) { nnpops_cfconv_destroy(h); return code; };
-    if ((rc = dev_alloc(&h->d_w1t, w1t.size()))) return cleanup(rc);
-    if ((rc = dev_alloc(&h->d_w2t, w2t.size()))) return cleanup(rc);
-    if ((rc = dev_alloc(&h->d_b1, (size_t)W))) return cleanup(rc);
-    if ((rc = dev_alloc(&h->d_b2, (size_t)W))) return cleanup(rc);
+    if (!h->d_w1t && (rc = dev_alloc(&h->d_w1t, w1t.size()))) return rc;
+    if (!h->d_w2t && (rc = dev_alloc(&h->d_w2t, w2t.size()))) return rc;
+    if (!h->d_b1 && (rc = dev_alloc(&h->d_b1, (size_t)W))) return rc;
+    if (!h->d_b2 && (rc = dev_alloc(&h->d_b2, (size_t)W))) return rc;
+    if (!h->d_w2 && (rc = dev_alloc(&h->d_w2, (size_t)W * W))) return rc;
     if (hipMemcpy(h->d_w1t, w1t.data(), w1t.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(h->d_w2t, w2t.data(), w2t.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(h->d_b1, b1, (size_t)W * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(h->d_b2, b2, (size_t)W * 4, hipMemcpyHostToDevice) != hipSuccess)
-        return cleanup(fail(NNPOPS_ERR_HIP, "weight upload failed"));
+        hipMemcpy(h->d_b2, b2, (size_t)W * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(h->d_w2, w2, (size_t)W * W * 4, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(NNPOPS_ERR_HIP, "weight upload failed");
     if (activation == 0) {
         std::vector<float> w1s(w1t), w2s(w2t), b1s(b1, b1 + W);
         for (float& v : w1s) v *= kLog2e;
         for (float& v : b1s) v *= kLog2e;
         for (float& v : w2s) v *= 1.0f / kLog2e;
-        if ((rc = dev_alloc(&h->d_w1t_s, w1s.size()))) return cleanup(rc);
-        if ((rc = dev_alloc(&h->d_w2t_s, w2s.size()))) return cleanup(rc);
-        if ((rc = dev_alloc(&h->d_b1_s, (size_t)W))) return cleanup(rc);
+        if (!h->d_w1t_s && (rc = dev_alloc(&h->d_w1t_s, w1s.size()))) return rc;
+        if (!h->d_w2t_s && (rc = dev_alloc(&h->d_w2t_s, w2s.size()))) return rc;
+        if (!h->d_b1_s && (rc = dev_alloc(&h->d_b1_s, (size_t)W))) return rc;
         if (hipMemcpy(h->d_w1t_s, w1s.data(), w1s.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(h->d_w2t_s, w2s.data(), w2s.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(h->d_b1_s, b1s.data(), (size_t)W * 4, hipMemcpyHostToDevice) != hipSuccess)
-            return cleanup(fail(NNPOPS_ERR_HIP, "weight upload failed"));
+            return fail(NNPOPS_ERR_HIP, "weight upload failed");
     }
     if (plan.split_ok) {
         // operands of the split-fp16 kernels, in the scaled domain they work in (see activate_fast)
@@ -592,20 +591,46 @@ int nnpops_cfconv_create(nnpops_cfconv_t* out, int num_atoms, int width, int num
                     w1h[(size_t)f * rowh + k] = hi;
                     w1l[(size_t)f * rowh + k] = (_Float16)((v - (float)hi) * kLoScale);
                 }
-            if ((rc = dev_alloc(&h->d_w1h, w1h.size()))) return cleanup(rc);
-            if ((rc = dev_alloc(&h->d_w1l, w1l.size()))) return cleanup(rc);
+            if (!h->d_w1h && (rc = dev_alloc(&h->d_w1h, w1h.size()))) return rc;
+            if (!h->d_w1l && (rc = dev_alloc(&h->d_w1l, w1l.size()))) return rc;
             if (hipMemcpy(h->d_w1h, w1h.data(), w1h.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
                 hipMemcpy(h->d_w1l, w1l.data(), w1l.size() * 2, hipMemcpyHostToDevice) != hipSuccess)
-                return cleanup(fail(NNPOPS_ERR_HIP, "weight upload failed"));
+                return fail(NNPOPS_ERR_HIP, "weight upload failed");
         }
-        if ((rc = dev_alloc(&h->d_w1b, w1b.size()))) return cleanup(rc);
-        if ((rc = dev_alloc(&h->d_w2h, w2h.size()))) return cleanup(rc);
-        if ((rc = dev_alloc(&h->d_w2l, w2l.size()))) return cleanup(rc);
+        if (!h->d_w1b && (rc = dev_alloc(&h->d_w1b, w1b.size()))) return rc;
+        if (!h->d_w2h && (rc = dev_alloc(&h->d_w2h, w2h.size()))) return rc;
+        if (!h->d_w2l && (rc = dev_alloc(&h->d_w2l, w2l.size()))) return rc;
         if (hipMemcpy(h->d_w1b, w1b.data(), w1b.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(h->d_w2h, w2h.data(), w2h.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(h->d_w2l, w2l.data(), w2l.size() * 2, hipMemcpyHostToDevice) != hipSuccess)
-            return cleanup(fail(NNPOPS_ERR_HIP, "weight upload failed"));
+            return fail(NNPOPS_ERR_HIP, "weight upload failed");
     }
+    h->filt_list = nullptr;                                 // the kept filter rows belong to the old weights
+    return NNPOPS_OK;
+}
+
+extern "C" {
+
+int nnpops_cfconv_create(nnpops_cfconv_t* out, int num_atoms, int width, int num_gaussians, float cutoff, int periodic,
+                         float gaussian_width, int activation, const float* w1, const float* b1, const float* w2,
+                         const float* b2, int device) {
+    NNPOPS_REQUIRE(out != nullptr, "out handle pointer is NULL");
+    *out = nullptr;
+    NNPOPS_REQUIRE(num_atoms > 0, "num_atoms must be positive");
+    NNPOPS_REQUIRE(b2 != nullptr, "NULL weight pointer");
+    NNPOPS_REQUIRE(cutoff > 0, "cutoff must be positive");
+    if (int rc = check_layer(width, num_gaussians, gaussian_width, activation, w1, b1, w2)) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(NNPOPS_ERR_NO_DEVICE, "no HIP device available");
+    NNPOPS_REQUIRE(device >= 0 && device < ndev, "device %d out of range (have %d)", device, ndev);
+    auto* h = new nnpops_cfconv();
+    h->p.N = num_atoms; h->p.W = width; h->p.G = num_gaussians; h->p.cutoff = cutoff;
+    h->p.sigma_inv = 1.0f / gaussian_width; h->p.activation = activation;
+    h->p.skip_filter_store = 0; h->p.dy_scale = 1.0f; h->p.dy_unscale = 1.0f;
+    h->periodic = periodic != 0; h->device = device;
+    h->gaussian_width = gaussian_width;
+    DeviceGuard guard(device);
+    if (int rc = plan_and_upload(h, w1, b1, w2, b2)) { nnpops_cfconv_destroy(h); return rc; }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) h->blocks = prop.multiProcessorCount;
     *out = h;
@@ -628,7 +653,7 @@ int nnpops_cfconv_describe(nnpops_cfconv_t h, int32_t out[8]) {
 int nnpops_cfconv_destroy(nnpops_cfconv_t h) {
     if (!h) return NNPOPS_OK;
     DeviceGuard guard(h->device);
-    dev_free(h->d_w1t); dev_free(h->d_w2t); dev_free(h->d_b1); dev_free(h->d_b2);
+    dev_free(h->d_w1t); dev_free(h->d_w2t); dev_free(h->d_b1); dev_free(h->d_b2); dev_free(h->d_w2); dev_free(h->d_wgrad_partials);
     dev_free(h->d_w1t_s); dev_free(h->d_w2t_s); dev_free(h->d_b1_s);
     dev_free(h->d_filt); dev_free(h->d_pair_s); dev_free(h->d_box_partials); dev_free(h->d_row_s);
     dev_free(h->d_w1b); dev_free(h->d_w2h); dev_free(h->d_w2l); dev_free(h->d_w1h); dev_free(h->d_w1l);
@@ -920,6 +945,67 @@ int check_pair(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb) {
     return NNPOPS_OK;
 }
 
+// The weight gradients (cfconv_weight_grad.h).  As for the double backward, the family is a matter of the width and of LDS alone, whatever
+// path the forward runs: the fp32 matrix instruction where W is a multiple of 16 up to 128 and the kernel's LDS image fits, else the
+// vector kernel.  One workgroup per compute unit, fewer where the partial rows would pass kWgradPartialBytes: every matrix-core layer of
+// SchNet's sizes keeps the full launch (W = 128, G = 50: 256 rows of 92 KB, 23 MB), and the widest layer the library accepts
+// (W = 512, G = 256: 1.5 MB a row) runs on 21 workgroups instead of holding 400 MB.
+constexpr size_t kWgradPartialBytes = (size_t)32 << 20;
+
+bool wgrad_takes_mfma(int W, int G) {
+    return W % 16 == 0 && W <= 128 && wgrad_mfma_floats(W, G) * sizeof(float) <= (size_t)160 * 1024;
+}
+
+template <int NCB>
+int launch_wgrad_mfma(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, const float* x, const float* g) {
+    const size_t lds = wgrad_mfma_floats(h->p.W, h->p.G) * sizeof(float);
+    auto launch = [&](auto k) {
+        if (lds > 64 * 1024)
+            NNPOPS_HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(k, dim3(h->wgrad_blocks), dim3(64 * NCB), lds, h->stream, h->p, h->d_w1t, h->d_b1, h->d_w2, nb->d_half_off,
+                           nb->d_half_r, nb->d_half_ij, nb->pair_cap(), x, g, h->d_wgrad_partials);
+        return (int)NNPOPS_OK;
+    };
+    return wgrad_gamma_blocks(h->p.G) == 4 ? launch(cfconv_wgrad_mfma<NCB, 4>) : launch(cfconv_wgrad_mfma<NCB, 16>);
+}
+
+int launch_wgrad(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, const float* x, const float* g, float* dw1, float* db1, float* dw2,
+                 float* db2) {
+    const int W = h->p.W, G = h->p.G;
+    nb->want_half = true;                                   // later builds carry the pair slots along (as launch_filters asks)
+    int rc;
+    if (!nb->half_built && (rc = launch_half_build(nb, h->stream)) != NNPOPS_OK) return rc;
+    if (!h->d_wgrad_partials) {                             // first call: not capturable
+        const size_t row_bytes = wgrad_row_floats(W, G) * sizeof(float);
+        const int blocks = (int)std::max<size_t>(1, std::min<size_t>((size_t)h->blocks, kWgradPartialBytes / row_bytes));
+        if ((rc = dev_alloc(&h->d_wgrad_partials, (size_t)blocks * wgrad_row_floats(W, G)))) return rc;
+        h->wgrad_blocks = blocks;
+    }
+    if (wgrad_takes_mfma(W, G)) {
+        switch (W) {
+            case 16:  rc = launch_wgrad_mfma<1>(h, nb, x, g); break;
+            case 32:  rc = launch_wgrad_mfma<2>(h, nb, x, g); break;
+            case 48:  rc = launch_wgrad_mfma<3>(h, nb, x, g); break;
+            case 64:  rc = launch_wgrad_mfma<4>(h, nb, x, g); break;
+            case 80:  rc = launch_wgrad_mfma<5>(h, nb, x, g); break;
+            case 96:  rc = launch_wgrad_mfma<6>(h, nb, x, g); break;
+            case 112: rc = launch_wgrad_mfma<7>(h, nb, x, g); break;
+            default:  rc = launch_wgrad_mfma<8>(h, nb, x, g); break;
+        }
+        if (rc != NNPOPS_OK) return rc;
+    } else {
+        const size_t lds = wgrad_vector_floats(W, G) * sizeof(float);
+        if (lds > 64 * 1024)
+            NNPOPS_HIP_TRY(hipFuncSetAttribute((const void*)cfconv_wgrad_vector, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(cfconv_wgrad_vector, dim3(h->wgrad_blocks), dim3(kWgradVectorThreads), lds, h->stream, h->p, h->d_w1t, h->d_b1,
+                           h->d_w2, nb->d_half_off, nb->d_half_r, nb->d_half_ij, nb->pair_cap(), x, g, h->d_wgrad_partials);
+    }
+    hipLaunchKernelGGL(cfconv_wgrad_finish, dim3(div_up((long long)wgrad_row_floats(W, G), 256)), dim3(256), 0, h->stream, W, G,
+                       h->wgrad_blocks, (const float*)h->d_wgrad_partials, dw1, db1, dw2, db2);
+    NNPOPS_HIP_TRY(hipGetLastError());
+    return NNPOPS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -987,6 +1073,23 @@ int nnpops_cfconv_double_backward(nnpops_cfconv_t h, nnpops_cfconv_neighbors_t n
     return h->p.activation == 0
                ? dispatch_second<0>(h, neighbors, input, output_deriv, gg_input_deriv, gg_position_deriv, out_output_deriv, out_input, out_positions)
                : dispatch_second<1>(h, neighbors, input, output_deriv, gg_input_deriv, gg_position_deriv, out_output_deriv, out_input, out_positions);
+}
+
+int nnpops_cfconv_backprop_weights(nnpops_cfconv_t h, nnpops_cfconv_neighbors_t neighbors, const float* input, const float* output_deriv,
+                                   float* w1_deriv, float* b1_deriv, float* w2_deriv, float* b2_deriv) {
+    int rc = check_pair(h, neighbors);
+    if (rc != NNPOPS_OK) return rc;
+    NNPOPS_REQUIRE(input && output_deriv && w1_deriv && b1_deriv && w2_deriv && b2_deriv, "NULL device pointer");
+    DeviceGuard guard(h->device);
+    return launch_wgrad(h, neighbors, input, output_deriv, w1_deriv, b1_deriv, w2_deriv, b2_deriv);
+}
+
+int nnpops_cfconv_set_weights(nnpops_cfconv_t h, const float* w1, const float* b1, const float* w2, const float* b2) {
+    NNPOPS_REQUIRE(h != nullptr, "NULL handle");
+    NNPOPS_REQUIRE(w1 && b1 && w2 && b2, "NULL weight pointer");
+    DeviceGuard guard(h->device);
+    NNPOPS_HIP_TRY(hipStreamSynchronize(h->stream));        // launches in flight still read the old forms
+    return plan_and_upload(h, w1, b1, w2, b2);
 }
 
 }  // extern "C"

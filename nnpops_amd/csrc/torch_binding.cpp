@@ -9,6 +9,7 @@
 //   torch.classes.NNPOpsCFConvNeighbors.Holder            (reference src/pytorch/CFConvNeighbors.cpp:77-85)
 //   torch.classes.NNPOpsCFConv.Holder / torch.ops.NNPOpsCFConv.operation / operation_periodic (additive: dL/dbox)
 //   torch.ops.NNPOpsCFConv.operation_twice / operation_periodic_twice (additive: the same ops, twice differentiable)
+//   torch.ops.NNPOpsCFConv.operation_weights / operation_periodic_weights (additive: the same ops with trainable weights)
 //                                                         (reference src/pytorch/CFConv.cpp:276-291)
 //   torch.ops.neighbors.getNeighborPairs                  (reference src/pytorch/neighbors/neighbors.cpp:4)
 //   torch.ops.NNPOpsBatchedNN.BatchedLinear               (reference src/pytorch/BatchedNN.cpp:48-50)
@@ -1146,6 +1147,53 @@ public:
         return {dOutputGrad, dInput, dPositions};
     }
 
+    // Trainable filters (operation_weights / operation_periodic_weights): bring the handle up to date with four weight tensors the
+    // caller owns.  What was last uploaded is remembered by storage and version counter, so a forward pass with unchanged parameters
+    // copies nothing; after an optimizer step (an in-place update: a new version) the host copies are replaced and a live handle is
+    // given them through nnpops_cfconv_set_weights, which plans again.  Shapes are those the holder was constructed with.
+    void syncWeights(const Tensor& w1, const Tensor& b1, const Tensor& w2, const Tensor& b2) {
+        const Tensor* given[4] = {&w1, &b1, &w2, &b2};
+        const Tensor* kept[4] = {&weights1, &biases1, &weights2, &biases2};
+        static const char* const names[4] = {"weights1", "biases1", "weights2", "biases2"};
+        bool same = uploads > 0;
+        for (int k = 0; k < 4; k++) {
+            const Tensor& t = *given[k];
+            if (t.scalar_type() != torch::kFloat32) throw std::runtime_error(std::string("The type of \"") + names[k] + "\" has to be float32");
+            if (t.sizes() != kept[k]->sizes())
+                throw std::runtime_error(std::string("The shape of \"") + names[k] + "\" has changed since the convolution was constructed");
+            same = same && t.is_contiguous() && t.data_ptr() == uploadedData[k] && (int64_t)t._version() == uploadedVersion[k];
+        }
+        if (same) return;
+        weights1 = w1.detach().cpu().contiguous().clone(); biases1 = b1.detach().cpu().contiguous().clone();
+        weights2 = w2.detach().cpu().contiguous().clone(); biases2 = b2.detach().cpu().contiguous().clone();
+        if (impl) {
+            nnpops_cfconv_set_stream(impl, current_stream(device));
+            if (nnpops_cfconv_set_weights(impl, weights1.data_ptr<float>(), biases1.data_ptr<float>(), weights2.data_ptr<float>(),
+                                          biases2.data_ptr<float>()) != NNPOPS_OK)
+                raise_last("NNPOpsCFConv::operation_weights (set_weights)");
+        }                                                    // (no handle yet: the first forward pass creates it from these copies)
+        for (int k = 0; k < 4; k++) { uploadedData[k] = given[k]->data_ptr(); uploadedVersion[k] = (int64_t)given[k]->_version(); }
+        uploads++;
+    }
+
+    // how many times syncWeights() has replaced the weights (a forward pass with unchanged parameters does not count)
+    int64_t getUploads() const { return uploads; }
+
+    // dL/d(weights1, biases1, weights2, biases2) for the tensors of the last forward pass (nnpops_cfconv_backprop_weights).  weights1 keeps
+    // the module's convention: the core's [W][G] result is the [G, W] tensor's buffer, reinterpreted and not transposed.
+    tensor_list backwardWeights(const Tensor& outputGrad_) {
+        if (!impl) throw std::runtime_error("backward() called before forward()");
+        const Tensor outputGrad = outputGrad_.detach().contiguous();
+        const auto opts = torch::TensorOptions().device(device).dtype(torch::kFloat32);
+        Tensor g1 = torch::empty(weights1.sizes(), opts), gb1 = torch::empty({numFilters}, opts);
+        Tensor g2 = torch::empty({numFilters, numFilters}, opts), gb2 = torch::empty({numFilters}, opts);
+        nnpops_cfconv_set_stream(impl, current_stream(device));
+        if (nnpops_cfconv_backprop_weights(impl, neighbors->getImpl(), input.data_ptr<float>(), outputGrad.data_ptr<float>(),
+                                           g1.data_ptr<float>(), gb1.data_ptr<float>(), g2.data_ptr<float>(), gb2.data_ptr<float>()) != NNPOPS_OK)
+            raise_last("NNPOpsCFConv::operation_weights (backward)");
+        return {g1, gb1, g2, gb2};
+    }
+
     static std::string serialize(const HolderPtr& self) {
         torch::serialize::OutputArchive archive;
         archive.write("gaussianWidth", self->gaussianWidth);
@@ -1184,6 +1232,10 @@ private:
     NeighborsPtr neighbors;
     Tensor positions, input, box;
     nnpops_cfconv_t impl = nullptr;
+    // syncWeights(): what the handle (or, before the first forward pass, the host copies) last received
+    const void* uploadedData[4] = {nullptr, nullptr, nullptr, nullptr};
+    int64_t uploadedVersion[4] = {0, 0, 0, 0};
+    int64_t uploads = 0;
 };
 
 class AutogradFunctions : public torch::autograd::Function<AutogradFunctions> {
@@ -1322,17 +1374,98 @@ Tensor operation_periodic_twice(const c10::optional<HolderPtr>& holder, const c1
     return CFConvTwiceFunction::apply(*holder, neighbors, positions, c10::optional<Tensor>(box), input);
 }
 
+// ---------------------------------------------------------------------------------------------
+// operation_weights / operation_periodic_weights: operation / operation_periodic with the four weight arrays as inputs that take a
+// gradient (trainable filters).  The forward pass first brings the handle up to date (Holder::syncWeights) and is then
+// that of the default op, bit for bit; the backward pass returns the default op's gradients (Holder::backward / backwardBox) and, from the
+// same call, the weight gradients of nnpops_cfconv_backprop_weights when a weight asks for one.  First derivatives only: the backward
+// pass refuses to be recorded (create_graph=True), and a list rebuilt since the forward pass.
+// ---------------------------------------------------------------------------------------------
+class CFConvWeightsFunction : public torch::autograd::Function<CFConvWeightsFunction> {
+public:
+    // box: empty for the non-periodic op.  wants: bit k = weight k requires a gradient; bit 4 = the box does (decided by the caller,
+    // where grad mode is what the user set)
+    static Tensor forward(AutogradContext* ctx, const HolderPtr& holder, const c10::IValue& neighbors, const Tensor& positions,
+                          const c10::optional<Tensor>& box, const Tensor& input, const Tensor& weights1, const Tensor& biases1,
+                          const Tensor& weights2, const Tensor& biases2, int64_t wants) {
+        holder->syncWeights(weights1, biases1, weights2, biases2);
+        const Tensor output = box ? holder->forwardPeriodic(neighbors, positions, *box, input) : holder->forward(neighbors, positions, input);
+        const Tensor* w[4] = {&weights1, &biases1, &weights2, &biases2};
+        c10::List<int64_t> on_cpu;
+        for (int k = 0; k < 4; k++) on_cpu.push_back(w[k]->is_cpu() ? 1 : 0);
+        ctx->saved_data["holder"] = holder;
+        ctx->saved_data["neighbors"] = neighbors;
+        ctx->saved_data["build"] = neighbors.toCustomClass<Neighbors>()->getBuildCount();
+        ctx->saved_data["periodic"] = box.has_value();
+        ctx->saved_data["wants"] = wants;
+        ctx->saved_data["on_cpu"] = on_cpu;
+        return output;
+    }
+    static tensor_list backward(AutogradContext* ctx, const tensor_list& grads) {
+        TORCH_CHECK(!torch::GradMode::is_enabled(),
+                    "NNPOpsCFConv::operation_weights: second derivatives are not implemented for the trainable convolution (create_graph=True): "
+                    "mixed second derivatives with respect to the filter network's weights are missing; training on forces takes "
+                    "CFConv(..., twice_differentiable=True) with fixed weights");
+        const HolderPtr holder = ctx->saved_data["holder"].toCustomClass<Holder>();
+        const NeighborsPtr nb = ctx->saved_data["neighbors"].toCustomClass<Neighbors>();
+        TORCH_CHECK(nb->getBuildCount() == ctx->saved_data["build"].toInt(),
+                    "NNPOpsCFConv::operation_weights: \"neighbors\" has been rebuilt since the forward pass; its rows no longer belong to the "
+                    "positions this gradient is taken at (build the list, run the forward pass and differentiate before building it again)");
+        const int64_t wants = ctx->saved_data["wants"].toInt();
+        const bool periodic = ctx->saved_data["periodic"].toBool();
+        tensor_list out;                                     // {holder, neighbours, positions, box, input, four weights, wants}
+        if (periodic && (wants & 16)) {
+            out = holder->backwardBox(grads);
+        } else {
+            out = holder->backward(grads);                   // {holder, neighbours, positions, input}
+            out.insert(out.begin() + 3, Tensor());
+        }
+        if (wants & 15) {
+            const tensor_list w = holder->backwardWeights(grads[0]);
+            const c10::List<int64_t> on_cpu = ctx->saved_data["on_cpu"].toIntList();
+            for (int k = 0; k < 4; k++) out.push_back(!(wants >> k & 1) ? Tensor() : on_cpu.get(k) ? w[k].cpu() : w[k]);
+        } else {
+            for (int k = 0; k < 4; k++) out.push_back(Tensor());
+        }
+        out.push_back(Tensor());
+        return out;
+    }
+};
+
+inline int64_t weight_wants(const Tensor& w1, const Tensor& b1, const Tensor& w2, const Tensor& b2) {
+    if (!torch::GradMode::is_enabled()) return 0;
+    return (w1.requires_grad() ? 1 : 0) | (b1.requires_grad() ? 2 : 0) | (w2.requires_grad() ? 4 : 0) | (b2.requires_grad() ? 8 : 0);
+}
+
+Tensor operation_weights(const c10::optional<HolderPtr>& holder, const c10::IValue& neighbors, const Tensor& positions, const Tensor& input,
+                         const Tensor& weights1, const Tensor& biases1, const Tensor& weights2, const Tensor& biases2) {
+    return CFConvWeightsFunction::apply(*holder, neighbors, positions, c10::optional<Tensor>(), input, weights1, biases1, weights2, biases2,
+                                        weight_wants(weights1, biases1, weights2, biases2));
+}
+
+Tensor operation_periodic_weights(const c10::optional<HolderPtr>& holder, const c10::IValue& neighbors, const Tensor& positions,
+                                  const Tensor& box, const Tensor& input, const Tensor& weights1, const Tensor& biases1,
+                                  const Tensor& weights2, const Tensor& biases2) {
+    TORCH_CHECK(box.defined(), "NNPOpsCFConv::operation_periodic_weights: \"box\" is undefined");
+    const int64_t box_wants = torch::GradMode::is_enabled() && box.requires_grad() ? 16 : 0;
+    return CFConvWeightsFunction::apply(*holder, neighbors, positions, c10::optional<Tensor>(box), input, weights1, biases1, weights2, biases2,
+                                        weight_wants(weights1, biases1, weights2, biases2) | box_wants);
+}
+
 TORCH_LIBRARY(NNPOpsCFConv, m) {
     m.class_<Holder>("Holder")
         .def(torch::init<double, const std::string&, const Tensor&, const Tensor&, const Tensor&, const Tensor&>())
         .def("forward", &Holder::forward)
         .def("backward", &Holder::backward)
+        .def("uploads", &Holder::getUploads)
         .def_pickle([](const HolderPtr& self) -> std::string { return Holder::serialize(self); },
                     [](const std::string& state) -> HolderPtr { return Holder::deserialize(state); });
     m.def("operation", operation);
     m.def("operation_periodic", operation_periodic);
     m.def("operation_twice", operation_twice);
     m.def("operation_periodic_twice", operation_periodic_twice);
+    m.def("operation_weights", operation_weights);
+    m.def("operation_periodic_weights", operation_periodic_weights);
 }
 
 }  // namespace CFConv
