@@ -653,6 +653,29 @@ int64_t nnpops_mlp_d1_halves(int num_atoms, int num_members, int h1);
 int nnpops_mlp_pack(void* stream, int rows, int cols, const float* w, long ldw, int transpose, int permute, void* out);
 int nnpops_mlp_forward(void* stream, const nnpops_mlp_frame* frame, int with_gradient);
 int nnpops_mlp_input_grad(void* stream, const nnpops_mlp_frame* frame);
+/* The gradient of  sum_b sum_m member_weights[b][m] * E_m(molecule b)  (every weight 1 without the table) with respect to the eight
+ * parameter arrays of every kind: fp32 device arrays in torch's Linear layout at the kind's PACKED widths (h1, h2, h3 of
+ * nnpops_mlp_kind; rows and columns of the zero padding come out as exact zeros),
+ *   dw0 [M][h1][F]  db0 [M][h1]  dw2 [M][h2][h1]  db2 [M][h2]  dw4 [M][h3][h2]  db4 [M][h3]  dw6 [M][h3]  db6 [M]
+ * with F = num_features: with x_groups the live width, column f of dw0 belonging to column 16 x_groups[f / 16] + f % 16 of x (the
+ * gradient of the dead columns is zero, x being zero there).  The call is SELF-CONTAINED: it runs the networks over the frame's x
+ * again (it needs a frame that could take nnpops_mlp_forward(frame, 1): transposed planes, d1 or dx_partial) and reads or writes
+ * none of energies, d1, dx_partial and dx, so it may come before, between or after nnpops_mlp_forward and nnpops_mlp_input_grad.
+ * It honours member_weights, member_weights_ld, segment_offsets, num_segments, x_groups and act_scale_log2 of the frame.
+ * Deterministic: no atomics; every value is one wave's sum over the atoms of the kind in their order in rows[] -- fp32 inside the
+ * matrix instructions for the four matrices, float64 for the bias sums -- so two calls give the same bits.  A member whose weight is
+ * zero for every molecule is skipped and its gradients are zeros; kinds without atoms and frames without atoms give zeros.
+ * workspace: nnpops_mlp_weight_grad_workspace_bytes(frame) bytes of device memory, 16-byte aligned -- per-atom data only, (2 (h1 +
+ * h2 + h3) + 1) floats per atom (rounded up to 64 per kind) and member; no partial sums. */
+typedef struct {
+    float *dw0, *db0, *dw2, *db2, *dw4, *db4, *dw6, *db6;
+} nnpops_mlp_weight_grad_kind;
+typedef struct {
+    void* workspace; int64_t workspace_bytes;
+    nnpops_mlp_weight_grad_kind kinds[NNPOPS_MLP_MAX_KINDS];
+} nnpops_mlp_weight_grad_out;
+int64_t nnpops_mlp_weight_grad_workspace_bytes(const nnpops_mlp_frame* frame);
+int nnpops_mlp_weight_grad(void* stream, const nnpops_mlp_frame* frame, const nnpops_mlp_weight_grad_out* out);
 /* out[0] = scale * sum(energies[0 .. count)) in double precision and a fixed order: the sum over atoms and the mean over
  * members of BatchedNN.py:109 (scale = 1 / num_members) in one small launch.  Device pointers. */
 int nnpops_mlp_energy_mean(void* stream, const float* energies, int64_t count, float scale, float* out);

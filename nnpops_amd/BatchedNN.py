@@ -461,6 +461,146 @@ class _FusedSpeciesNN(_SpeciesGroupedNN):
         return self._batch_call(torch.ops.NNPOpsANISymmetryFunctions.energy_forces_batch, holder, positions, shift)
 
 
+PARAMETER_NAMES = tuple(f'layer{ilayer}_{what}' for ilayer in (0, 2, 4, 6) for what in ('weights', 'biases'))
+
+
+def _buffers_to_parameters(module: nn.Module) -> None:
+    """the eight ``layer{0,2,4,6}_{weights,biases}`` buffers of a species-grouped module become ``nn.Parameter``s of the same names (and
+    the same places in its state dict)"""
+    for name in PARAMETER_NAMES:
+        value = module._buffers.pop(name)
+        module.register_parameter(name, nn.Parameter(value.detach().clone()))
+
+
+class _TrainableGroupedNN(_SpeciesGroupedNN):
+    """:class:`_SpeciesGroupedNN` with its eight arrays as parameters: plain torch, differentiable in the AEV and in the parameters
+    to any order.  ``TorchANIBatchedNN(..., layout='grouped', trainable=True)``; what the fused trainable layout is compared with.
+    The zero padding to the widest species is structural: its gradient is exactly zero (a padded unit has no input weights, no bias
+    and no output weights), so it stays zero under any optimizer that leaves a zero-gradient entry alone.  Not scriptable."""
+
+    def __init__(self, converter, ensemble, atomicNumbers: Tensor):
+        super().__init__(converter, ensemble, atomicNumbers)
+        _buffers_to_parameters(self)
+
+
+class _TrainableFusedNN(_FusedSpeciesNN):
+    """:class:`_FusedSpeciesNN` with its eight arrays as parameters (``TorchANIBatchedNN(..., trainable=True)``).  One molecule on the
+    device in float32 runs ``torch.ops.NNPOpsBatchedNN.FusedMLPMembersTrainable``: the forward pass of ``FusedMLPMembers`` on the
+    packed planes, bit for bit, and a backward pass that returns the gradient of the AEV as before and, from one call of
+    ``nnpops_mlp_weight_grad`` (csrc/mlp_weight_grad.h), the gradients of all eight arrays for whatever function of the member
+    energies was differentiated.  CPU tensors, float64, several molecules and networks outside the kernels' shape take the parent's
+    plain-torch path, which is differentiable in the parameters as it stands.
+
+    The packed planes are derived from the parameters: they are rebuilt on the first forward pass after a parameter's version has
+    changed (an optimizer step, an in-place edit) and after ``load_state_dict``; while the parameters stand, nothing is rebuilt
+    (``plane_rebuilds`` counts).  The widths every species is packed at are fixed at construction from the source networks; a rebuild
+    that finds others raises.  First derivatives only (no force-loss training: use ``layout='grouped'``), not scriptable."""
+
+    __jit_ignored_attributes__ = ["_batch_plans", "_plane_versions", "_fixed_widths", "plane_rebuilds"]
+
+    _fixed_widths = None           # (class defaults: _refresh_planes runs inside the parent's constructor)
+    _plane_versions = None
+    plane_rebuilds = 0
+
+    def __init__(self, converter, ensemble, atomicNumbers: Tensor):
+        super().__init__(converter, ensemble, atomicNumbers)
+        self._fixed_widths = list(self.widths)
+        _buffers_to_parameters(self)
+        self._plane_versions = self._versions()
+
+    def _versions(self):
+        return tuple((id(p), p._version, p.device) for p in (getattr(self, name) for name in PARAMETER_NAMES))
+
+    @torch.jit.unused
+    def _packed_widths(self) -> List[int]:
+        """the widths _refresh_planes would pack every kind at, from the current values"""
+        out = []
+        for k in range(int(self.layer0_weights.shape[0])):
+            for w, b in ((self.layer0_weights, self.layer0_biases), (self.layer2_weights, self.layer2_biases), (self.layer4_weights, self.layer4_biases)):
+                out.append(min(self._true_width(w[k].float(), b[k].float()), _up32(int(w.shape[2]))))
+        return out
+
+    @torch.jit.unused
+    def _refresh_planes(self) -> None:
+        with torch.no_grad():
+            if self._fixed_widths is not None:             # (checked BEFORE anything is replaced: a refused structure leaves the module as it was)
+                widths = self._packed_widths()
+                if widths != self._fixed_widths:
+                    raise RuntimeError(f"the networks' widths changed from {self._fixed_widths} to {widths}: the structure of a trainable "
+                                       "module is fixed at construction (the zero padding must stay zero)")
+            super()._refresh_planes()
+        self.plane_rebuilds += 1
+        self._plane_versions = self._versions()
+
+    @torch.jit.unused
+    def _current_planes(self) -> None:
+        if self._plane_versions != self._versions():
+            self._refresh_planes()
+
+    def forward(self, species_aev: Tuple[Tensor, Tensor]) -> SpeciesEnergies:
+        species, aev = species_aev
+        self._current_planes()
+        if (aev.shape[0] != 1 or not aev.is_cuda or aev.dtype != torch.float32 or self.mlp_planes.dtype != torch.float16
+                or self.atom_order32.dtype != torch.int32 or not self.fused_ok):
+            return self._grouped_forward(species_aev)
+        # (the default module's arithmetic, over all columns as there: the sum over atoms and members from the kernel, divided here)
+        return SpeciesEnergies(species, self._trainable_op(aev[0].contiguous(), None, None, True, True, True) / self.num_models)
+
+    @torch.jit.unused
+    def fused_members(self, aev: Tensor, shift: Optional[Tensor] = None, batch: Optional[Tuple[Tensor, List[int], Tensor, Tensor]] = None) -> Tensor:
+        """``_FusedSpeciesNN.fused_members`` as a node that is differentiable in the parameters as well"""
+        self._current_planes()
+        return self._trainable_op(aev, shift, batch, False)
+
+    @torch.jit.unused
+    def fused_mean(self, aev: Tensor, shift: Optional[Tensor] = None, batch: Optional[Tuple[Tensor, List[int], Tensor, Tensor]] = None) -> Tensor:
+        """The ensemble mean of the molecule(s) behind ``aev`` -> [molecules] (``torch.ops.NNPOpsBatchedNN.FusedMLPMeanTrainable``): the
+        energy of ``fused_energy`` / ``fused_energy_batch``, bit for bit, as a node that is differentiable in the AEV and the parameters"""
+        self._current_planes()
+        return self._trainable_op(aev, shift, batch, True)
+
+    @torch.jit.unused
+    def _trainable_op(self, aev: Tensor, shift: Optional[Tensor], batch: Optional[Tuple[Tensor, List[int], Tensor, Tensor]], mean: bool,
+                      total: bool = False, all_columns: bool = False) -> Tensor:
+        if not self.fused_ok:
+            raise RuntimeError("the weights exceed the activation bound of the fused network kernels (BatchedNN.py: fused_ok); "
+                               "train with nn_layout='grouped'")
+        rows, sizes, places, offsets = batch if batch is not None else (self.atom_order32, self.group_sizes, None, None)
+        parameters = [getattr(self, name) for name in PARAMETER_NAMES]
+        if self.x_blocks.numel() > 0 and not all_columns:
+            args = (aev, rows, sizes, self.widths, self.num_models, self.live_planes, self.mlp_floats, self.x_blocks, self.dead_blocks,
+                    self.act_scale_log2, offsets, places, shift, parameters)
+        else:
+            args = (aev, rows, sizes, self.widths, self.num_models, self.mlp_planes, self.mlp_floats, None, None, self.act_scale_log2, offsets, places,
+                    shift, parameters)
+        if mean:
+            return torch.ops.NNPOpsBatchedNN.FusedMLPMeanTrainable(*args, total)
+        return torch.ops.NNPOpsBatchedNN.FusedMLPMembersTrainable(*args)
+
+    @torch.jit.unused
+    def members_energies(self, species_aev: Tuple[Tensor, Tensor]) -> SpeciesEnergies:
+        self._current_planes()
+        species, aev = species_aev
+        if (aev.shape[0] != 1 or not aev.is_cuda or aev.dtype != torch.float32 or self.mlp_planes.dtype != torch.float16
+                or self.atom_order32.dtype != torch.int32 or not self.fused_ok or self.x_blocks.numel() > 0):
+            return _SpeciesGroupedNN.members_energies(self, species_aev)
+        return SpeciesEnergies(species, self._trainable_op(aev[0].contiguous(), None, None, False).t())
+
+    # (the one-node steps take no parameter gradient: they run outside the parameters' autograd, on the current weights)
+    def fused_energy(self, positions: Tensor, cell: Optional[Tensor], shift: Optional[Tensor] = None) -> Tensor:
+        self._current_planes()
+        return super().fused_energy(positions, cell, shift)
+
+    def fused_energy_forces(self, positions: Tensor, cell: Optional[Tensor], shift: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+        self._current_planes()
+        return super().fused_energy_forces(positions, cell, shift)
+
+    @torch.jit.unused
+    def _batch_call(self, op, holder, positions: Tensor, shift: Optional[Tensor]):
+        self._current_planes()
+        return super()._batch_call(op, holder, positions, shift)
+
+
 class _SplitGemmSpeciesNN(_SpeciesGroupedNN):
     """(Round-1/2 default, kept as ``layout='gemm'`` for comparison and for widths the fused kernels do not take.)  The
     species-grouped networks on the library's own GEMM (``torch.ops.NNPOpsBatchedNN.GroupedMLP``, csrc/batched_nn.hip): fp32 in and out, products as split-fp16 matrix instructions with fp32 accumulation, bias + CELU
@@ -540,12 +680,23 @@ class TorchANIBatchedNN(nn.ModuleList):
     """``layout='fused'`` (default): species-grouped networks as two launches of the fused kernels (csrc/mlp_fused.hip);
     ``'gemm'``: one split-fp16 GEMM per layer and species with fused activations (csrc/batched_nn.hip); ``'grouped'``: the same
     grouping on torch's library GEMMs; ``'reference'``: the reference's per-atom replicated weights through ``BatchedLinear``
-    (interchange with reference state dicts / archives)."""
+    (interchange with reference state dicts / archives).
 
-    def __init__(self, converter, ensemble, atomicNumbers: Tensor, layout: str = 'fused'):
+    ``trainable=True`` (extension; ``'fused'`` and ``'grouped'`` only): the eight ``layer{0,2,4,6}_{weights,biases}`` arrays are
+    ``nn.Parameter``s under the same names -- state dicts interchange with the default module in both directions, the reference's
+    per-atom state dict still loads -- and every output is differentiable in them: ``'fused'`` through
+    ``torch.ops.NNPOpsBatchedNN.FusedMLPMembersTrainable`` for one molecule on the device in float32 (first derivatives), plain torch
+    otherwise and for ``'grouped'``.  Out of scope: scripting a trainable module, second derivatives through the fused op (training
+    on forces), periodic batches."""
+
+    def __init__(self, converter, ensemble, atomicNumbers: Tensor, layout: str = 'fused', trainable: bool = False):
         if layout not in ('fused', 'gemm', 'grouped', 'reference'):
             raise ValueError("layout must be 'fused', 'gemm', 'grouped' or 'reference'")
+        if trainable and layout not in ('fused', 'grouped'):
+            raise ValueError(f"trainable=True needs layout='fused' or layout='grouped' (got {layout!r}: its packed operands have no weight gradient)")
         impl = {'fused': _FusedSpeciesNN, 'gemm': _SplitGemmSpeciesNN, 'grouped': _SpeciesGroupedNN, 'reference': _BatchedNN}[layout]
+        if trainable:
+            impl = {'fused': _TrainableFusedNN, 'grouped': _TrainableGroupedNN}[layout]
         super().__init__([impl(converter, ensemble, atomicNumbers)])
 
     def forward(self, species_aev: Tuple[Tensor, Tensor]) -> SpeciesEnergies:

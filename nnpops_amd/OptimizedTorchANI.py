@@ -15,20 +15,25 @@ class OptimizedTorchANI(torch.nn.Module):
     """The reference's four-module composition.  ``nn_layout`` (additive) picks the layout of the networks
     (:class:`TorchANIBatchedNN`); with the default ``'fused'`` and networks the fused kernels take, the instance becomes a
     :class:`FusedOptimizedTorchANI`: same modules, same state dict, same results, but AEV and networks run as ONE autograd
-    node (``fused_step=False`` keeps the plain composition)."""
+    node (``fused_step=False`` keeps the plain composition).
 
-    def __init__(self, model, atomicNumbers: Tensor, nn_layout: str = 'fused', fused_step: bool = True, live_columns: bool = True) -> None:
+    ``trainable=True`` (extension): the networks' arrays are parameters (``TorchANIBatchedNN(..., trainable=True)``) and, with the
+    fused layout, the instance becomes a :class:`TrainableOptimizedTorchANI`.  Out of scope: scripting a trainable module, second
+    derivatives (training on forces), periodic batches."""
+
+    def __init__(self, model, atomicNumbers: Tensor, nn_layout: str = 'fused', fused_step: bool = True, live_columns: bool = True,
+                 trainable: bool = False) -> None:
         super().__init__()
         self.species_converter = TorchANISpeciesConverter(model.species_converter, atomicNumbers)
         self.aev_computer = TorchANISymmetryFunctions(model.species_converter, model.aev_computer, atomicNumbers)
-        self.neural_networks = TorchANIBatchedNN(model.species_converter, model.neural_networks, atomicNumbers, layout=nn_layout)
+        self.neural_networks = TorchANIBatchedNN(model.species_converter, model.neural_networks, atomicNumbers, layout=nn_layout, trainable=trainable)
         self.energy_shifter = TorchANIEnergyShifter(model.species_converter, model.energy_shifter, atomicNumbers)
         nets = self.neural_networks[0]
         if fused_step and isinstance(nets, _FusedSpeciesNN) and nets.fused_ok:
             nets.holder = self.aev_computer.holder        # the networks' fused_energy() drives the AEV kernels itself
             if live_columns:                               # ... and multiplies only the AEV blocks this molecule's species can fill
                 nets.set_live_blocks(self.aev_computer.live_column_blocks())
-            self.__class__ = FusedOptimizedTorchANI
+            self.__class__ = TrainableOptimizedTorchANI if trainable else FusedOptimizedTorchANI
 
     def forward(self, species_coordinates: Tuple[Tensor, Tensor], cell: Optional[Tensor] = None,
                 pbc: Optional[Tensor] = None) -> SpeciesEnergies:
@@ -214,3 +219,36 @@ class FusedOptimizedTorchANI(OptimizedTorchANI):
             return self.neural_networks.fused_energy_forces_batch(holder, coordinates, shift)
         energies, forces = self.neural_networks.fused_energy_forces_batch(holder, coordinates)
         return energies + self.energy_shifter.self_energies, forces
+
+
+class TrainableOptimizedTorchANI(FusedOptimizedTorchANI):
+    """``OptimizedTorchANI(..., trainable=True)`` on the fused layout.  ``forward``, ``forward_batch``, ``members_energies``,
+    ``members_energies_batch``, ``energies_qbcs`` and ``energies_qbcs_batch`` run as TWO autograd nodes -- the AEV op and
+    ``torch.ops.NNPOpsBatchedNN.FusedMLPMembersTrainable`` (``FusedMLPMeanTrainable`` for the mean) -- and are differentiable in the
+    coordinates and in the networks' parameters (``neural_networks.parameters()``): one backward pass costs the networks' input
+    gradient, one call of their weight gradient and the AEV backward, whatever function of the energies was differentiated.
+    Energies and coordinate gradients are the bits of the default module at equal weights.  ``energy_and_forces`` /
+    ``energy_and_forces_batch`` stay outside autograd and use the current weights.  Out of scope: scripting, second derivatives (a
+    loss on forces), periodic batches, a gradient of the cell."""
+
+    def forward(self, species_coordinates: Tuple[Tensor, Tensor], cell: Optional[Tensor] = None,
+                pbc: Optional[Tensor] = None) -> SpeciesEnergies:
+        converted = self.species_converter(species_coordinates)
+        species, positions = converted.species, converted.coordinates
+        self.aev_computer.check_arguments(species, cell, pbc)
+        aev = torch.ops.NNPOpsANISymmetryFunctions.aev(self.aev_computer.holder, positions[0], cell)
+        shift = self._shift_for(positions)
+        energy = self.neural_networks[0].fused_mean(aev, shift)
+        return SpeciesEnergies(species, energy) if shift is not None else self.energy_shifter((species, energy))
+
+    @torch.jit.unused
+    def forward_batch(self, species_coordinates: Tuple[Tensor, Tensor], cell: Optional[Tensor] = None,
+                      pbc: Optional[Tensor] = None) -> SpeciesEnergies:
+        species, coordinates = self._batch_arguments(species_coordinates, cell, pbc)
+        batch, atoms = int(coordinates.shape[0]), int(coordinates.shape[1])
+        nets = self.neural_networks[0]
+        holder, rows, sizes, places, offsets = nets._batch_plan(self.aev_computer.batch_holder(batch), batch, coordinates.device)
+        aev = torch.ops.NNPOpsANISymmetryFunctions.aev(holder, coordinates.reshape(batch * atoms, 3), None)
+        shift = self._shift_for(coordinates)
+        energies = nets.fused_mean(aev, shift, (rows, sizes, places, offsets))
+        return SpeciesEnergies(species, energies) if shift is not None else self.energy_shifter((species, energies))

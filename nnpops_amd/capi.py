@@ -88,6 +88,8 @@ SIGNATURES = {
     "nnpops_mlp_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p]),
     "nnpops_mlp_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "nnpops_mlp_input_grad": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "nnpops_mlp_weight_grad_workspace_bytes": (C.c_int64, [C.c_void_p]),
+    "nnpops_mlp_weight_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_mlp_energy_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
     "nnpops_mlp_energy_mean_shifted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
     "nnpops_scale_by_scalar": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]),
@@ -1027,6 +1029,17 @@ class _MlpFrame(C.Structure):
                 ("member_weights", C.c_void_p), ("member_weights_ld", C.c_int)]
 
 
+MLP_GRADIENTS = ("dw0", "db0", "dw2", "db2", "dw4", "db4", "dw6", "db6")
+
+
+class _MlpWeightGradKind(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in MLP_GRADIENTS]
+
+
+class _MlpWeightGradOut(C.Structure):
+    _fields_ = [("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("kinds", _MlpWeightGradKind * MLP_MAX_KINDS)]
+
+
 def mlp_pack(w, rows, cols, transpose=False, permute=False):
     """fp32 device matrix -> the fragment planes nnpops_mlp_forward / _input_grad take as the LEFT operand of a product with
     `rows` outputs and `cols` inputs (`w` is [rows][cols], or [cols][rows] with transpose)."""
@@ -1065,6 +1078,7 @@ class FusedMLP:
         self.F, self.alpha = int(num_features), float(alpha)
         self.M = int(kinds[0]["w0"].shape[0])
         self._keep = []
+        self._shapes, self._packed = [], []                   # per kind, the eight parameter arrays as given and at the packed widths
         self.frame = _MlpFrame()
         self.frame.num_kinds, self.frame.num_features, self.frame.num_members, self.frame.alpha = len(kinds), self.F, self.M, self.alpha
         self.frame.act_scale_log2 = int(act_scale_log2)       # activations are scaled by 2^-k before the fp16 split (nnpops_hip.h)
@@ -1097,6 +1111,8 @@ class FusedMLP:
             n = int(kd["atoms"].numel())
             d1 = torch.empty((max(int(lib().nnpops_mlp_d1_halves(n, M, h1)), 1),), dtype=torch.float16, device=dev)
             self._keep += [planes, b0, b2, b4, w6, b6, d1]
+            self._shapes.append(((M, H1, F), (M, H1), (M, H2, H1), (M, H2), (M, H3, H2), (M, H3), (M, H3), (M,)))
+            self._packed.append(((M, h1, F), (M, h1), (M, h2, h1), (M, h2), (M, h3, h2), (M, h3), (M, h3), (M,)))
             fk = self.frame.kinds[k]
             fk.num_atoms, fk.h1, fk.h2, fk.h3 = n, h1, h2, h3
             for name, t in planes.items():
@@ -1148,9 +1164,20 @@ class FusedMLP:
         self.frame.dx, self.frame.lddx = out.data_ptr(), out.shape[1]
         self.frame.upstream = upstream.data_ptr() if upstream is not None else None
         self.frame.dx_scale = float(scale)
-        saved = (self.frame.segment_offsets, self.frame.num_segments)
         if member_weights is not None:
             member_weights = _dev_f32(member_weights, "member_weights")
+        saved = self._with_weights(member_weights, molecule_offsets)
+        try:
+            _check(lib().nnpops_mlp_input_grad(_stream_ptr(out.device), C.byref(self.frame)))
+        finally:
+            self.frame.member_weights, self.frame.member_weights_ld = None, 0
+            self.frame.segment_offsets, self.frame.num_segments = saved
+        return out
+
+    def _with_weights(self, member_weights, molecule_offsets):
+        """sets member_weights / segment_offsets of the frame; -> what to put back"""
+        saved = (self.frame.segment_offsets, self.frame.num_segments)
+        if member_weights is not None:
             count = 1 if molecule_offsets is None else molecule_offsets.numel() - 1
             if member_weights.dim() != 2 or tuple(member_weights.shape) != (count, self.M):
                 raise ValueError(f"member_weights must be [{count}][{self.M}]")
@@ -1159,12 +1186,37 @@ class FusedMLP:
                 if not (molecule_offsets.is_cuda and molecule_offsets.dtype == torch.int32 and molecule_offsets.is_contiguous()):
                     raise ValueError('"molecule_offsets" must be a contiguous int32 device tensor')
                 self.frame.segment_offsets, self.frame.num_segments = molecule_offsets.data_ptr(), count
+        return saved
+
+    def weight_grad(self, member_weights=None, molecule_offsets=None):
+        """The gradient of sum_b sum_m member_weights[b][m] E_m(molecule b) (all ones without the table; tables as for input_grad) with
+        respect to the networks' parameters, over the x of the last forward(): one dict per kind with the eight float32 tensors
+        dw0 [M,H1,F], db0 [M,H1], dw2 [M,H2,H1], db2, dw4 [M,H3,H2], db4, dw6 [M,H3], db6 [M] in the shapes the constructor was given
+        (with live_groups, F counts the live columns in their order).  nnpops_mlp_weight_grad: self-contained, it leaves ``energies``
+        and what input_grad() reads as they are."""
+        if not self.frame.x:
+            raise RuntimeError("weight_grad() reads the x of the last forward(): call forward() first")
+        dev = self.device
+        if member_weights is not None:
+            member_weights = _dev_f32(member_weights, "member_weights")
+        full = [[torch.empty(shape, dtype=torch.float32, device=dev) for shape in shapes] for shapes in self._packed]
+        out = _MlpWeightGradOut()
+        need = int(lib().nnpops_mlp_weight_grad_workspace_bytes(C.byref(self.frame)))
+        ws = getattr(self, "_weight_ws", None)
+        if ws is None or ws.numel() * 4 < need:
+            ws = self._weight_ws = torch.empty((max(need // 4, 64),), dtype=torch.float32, device=dev)
+        out.workspace, out.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+        for k, arrays in enumerate(full):
+            for name, t in zip(MLP_GRADIENTS, arrays):
+                setattr(out.kinds[k], name, t.data_ptr())
+        saved = self._with_weights(member_weights, molecule_offsets)
         try:
-            _check(lib().nnpops_mlp_input_grad(_stream_ptr(out.device), C.byref(self.frame)))
+            _check(lib().nnpops_mlp_weight_grad(_stream_ptr(dev), C.byref(self.frame), C.byref(out)))
         finally:
             self.frame.member_weights, self.frame.member_weights_ld = None, 0
             self.frame.segment_offsets, self.frame.num_segments = saved
-        return out
+        return [{name: t[tuple(slice(0, n) for n in shape)].contiguous() for name, t, shape in zip(MLP_GRADIENTS, arrays, shapes)}
+                for arrays, shapes in zip(full, self._shapes)]
 
 
 def scale_by_scalar(values, factor):

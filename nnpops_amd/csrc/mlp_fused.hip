@@ -33,6 +33,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
+#include <type_traits>
 
 #include "host_common.h"
 
@@ -201,11 +202,16 @@ __device__ __forceinline__ const KindDesc& kind_of_block(const MlpArgs& g, int b
     return g.kinds[k];
 }
 
+#include "mlp_weight_grad.h"                 // (the layout of the weight gradient's workspace and its contraction kernels)
+
 // =============================================================================================
 // forward through all four layers (+ backward through layers 6, 4, 2 when GRAD)
 // =============================================================================================
-template <bool GRAD>
-__global__ __launch_bounds__(kThreads, 2) void mlp_forward(const MlpArgs g) {
+// (WG: the tile pass of the weight gradient, mlp_weight_grad.h -- the gradient pass, except that what it holds of the tile goes to the
+//  workspace in fp32 instead of being thrown away, and that it writes neither energies nor dE/dy1)
+struct MlpWgArgs : MlpArgs { WgTile wt; };  // (the kernel arguments of the WG instantiation: MlpArgs keeps its size)
+template <bool GRAD, bool WG = false>
+__global__ __launch_bounds__(kThreads, 2) void mlp_forward(const std::conditional_t<WG, MlpWgArgs, MlpArgs> g) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     char* xstage = lds;                                     // 2 x 8 KiB: the AEV columns of a K step, split, fragment layout
     char* actA = lds + 2 * kStageBytes;                     // 64 KiB
@@ -215,6 +221,20 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_forward(const MlpArgs g) {
     const KindDesc& kd = kind_of_block(g, blockIdx.x);
     const int local = blockIdx.x - kd.block0;
     const int m = local % g.M, tile = local / g.M;
+    float* ctile = reinterpret_cast<float*>(xgroup + 64);   // WG: the upstream weight of (the molecule of every atom of the tile, m); 0 past the kind
+    if constexpr (WG) {
+        if (!g.wt.live[m]) return;                          // (a member nobody weighs: uniform over the workgroup)
+        if (tid >= 128 && tid < 192) {
+            const int r = tile * kTile + tid - 128;
+            float c = 0.0f;
+            if (r < kd.n) {
+                c = 1.0f;
+                if (g.member_weights)
+                    c = g.member_weights[(size_t)(g.w_offsets ? molecule_of_row(g.w_offsets, g.w_segments, g.rows[kd.first + r]) : 0) * g.ldw + m];
+            }
+            ctile[tid - 128] = c;
+        }
+    }
     if (tid < 64) xgroup[tid] = 16 * tid < g.F ? (g.x_groups ? g.x_groups[tid] : tid) : 0;
     if (g.publish_to && blockIdx.x == 0 && tid == 64) {     // (nnpops_hip.h: publish_*; what ani_publish_status would need a launch for)
         const int word = __hip_atomic_load(g.publish_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -232,6 +252,23 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_forward(const MlpArgs g) {
 
     f32x4 acc1[kRB][kCB], acc2[kRB][kCB];
     f32x4 c1[kRB][kCB], c2[kRB][kCB];                      // CELU' of hidden layers 1 and 2 (GRAD; layer 3's is used on the spot)
+    // WG: the tile's columns of this (kind, member)'s rows in the workspace; a block in D layout goes to rows row0 + 16 rb + 4 g + q
+    [[maybe_unused]] float* wtile = nullptr;
+    [[maybe_unused]] size_t npad = 0;
+    if constexpr (WG) {
+        int kidx = 0;
+#pragma unroll
+        for (int i = 1; i < NNPOPS_MLP_MAX_KINDS; i++)
+            if (i < g.num_kinds && (int)blockIdx.x >= g.kinds[i].block0) kidx = i;
+        npad = (size_t)kd.tiles * kTile;
+        wtile = g.wt.ws + g.wt.base[kidx] + (size_t)m * wg_rows(kd.h1, kd.h2, kd.h3) * npad + r0;
+    }
+    [[maybe_unused]] auto emit = [&](int row0, int rb, int cb, const f32x4& v, bool weighted) {
+        const float f = g.unscale * (weighted ? ctile[cb * 16 + a16] : 1.0f);
+        float* p = wtile + (size_t)(row0 + rb * 16 + kgD * 4) * npad + cb * 16 + a16;
+#pragma unroll
+        for (int q = 0; q < 4; q++) p[q * npad] = v[q] * f;
+    };
 
     // ---------------- layer 0: the AEV rows of the tile stream through LDS, 32 columns per step ----------------
     {
@@ -287,7 +324,7 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_forward(const MlpArgs g) {
     // accumulators (acc1 + acc2 / 2048 + b / 16), CELU(v) / 16 = vs > 0 ? vs : (alpha / 16) (exp(16 vs / alpha) - 1).
     const float kScale = g.scale, kUnscale = g.unscale;     // (run-time powers of two since round 5; the names of the constants they replace)
     const float exp_scale = kUnscale * inv_alpha * 1.44269504089f, alpha_s = g.alpha * kScale;
-    auto activate = [&](const float* __restrict__ bias, int nmine, f32x4 (&c)[kRB][kCB], char* act) {
+    auto activate = [&](const float* __restrict__ bias, int nmine, f32x4 (&c)[kRB][kCB], char* act, [[maybe_unused]] int wg_row) {
         for_blocks(nmine, w, [&](int j, int rb) {
             const float4 b = *reinterpret_cast<const float4*>(bias + rb * 16 + kgD * 4);
             const float bq[4] = {b.x * kScale, b.y * kScale, b.z * kScale, b.w * kScale};
@@ -302,14 +339,15 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_forward(const MlpArgs g) {
                     if (GRAD) c[j][cb][q] = vs > 0.f ? 1.0f : e;
                 }
                 put_fragment(act, rb, cb, lane, y);
+                if constexpr (WG) emit(wg_row, rb, cb, y, false);
             }
         });
     };
-    activate(kd.b0 + (size_t)m * kd.h1, n1, c1, actA);
+    activate(kd.b0 + (size_t)m * kd.h1, n1, c1, actA, wg_row_y1(kd.h1, kd.h2, kd.h3));
     __syncthreads();
     // ---------------- layer 2 ----------------
     layer_resident(kd.w2 + (size_t)m * nb2 * s1 * 2 * kFrag, s1, nb2, n2, w, lane, actA, acc1, acc2);
-    activate(kd.b2 + (size_t)m * kd.h2, n2, c2, actB);
+    activate(kd.b2 + (size_t)m * kd.h2, n2, c2, actB, wg_row_y2(kd.h1, kd.h2, kd.h3));
     __syncthreads();
     // ---------------- layer 4 ----------------
     layer_resident(kd.w4 + (size_t)m * nb3 * s2 * 2 * kFrag, s2, nb3, n3, w, lane, actB, acc1, acc2);
@@ -327,6 +365,7 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_forward(const MlpArgs g) {
 #pragma unroll
             for (int cb = 0; cb < kCB; cb++) {
                 f32x4 d;
+                [[maybe_unused]] f32x4 y3;
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
                     const float vs = fmaf(kLoInv, acc2[j][cb][q], acc1[j][cb][q]) + bq[q];
@@ -334,8 +373,13 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_forward(const MlpArgs g) {
                     const float ys = vs > 0.f ? vs : fmaf(alpha_s, e, -alpha_s);
                     part[cb] = fmaf(wq[q], ys, part[cb]);
                     d[q] = vs > 0.f ? ws[q] : ws[q] * e;                    // dE/d(pre-activation 3) / 16 = w6 CELU' / 16
+                    if constexpr (WG) y3[q] = ys;
                 }
                 if (GRAD) put_fragment(actA, rb, cb, lane, d);              // (region A: layer 2 is done with it)
+                if constexpr (WG) {
+                    emit(wg_row_d3(kd.h1, kd.h2), rb, cb, d, true);
+                    emit(wg_row_cy3(kd.h1, kd.h2, kd.h3), rb, cb, y3, true);
+                }
             }
         });
     }
@@ -349,7 +393,9 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_forward(const MlpArgs g) {
         if (kgD == 0) red[w * kTile + cb * 16 + a16] = p;
     }
     __syncthreads();
-    if (tid < kTile && r0 + tid < kd.n)
+    if constexpr (WG) {
+        if (tid < kTile) wtile[(size_t)wg_row_c(kd.h1, kd.h2, kd.h3) * npad + tid] = ctile[tid];
+    } else if (tid < kTile && r0 + tid < kd.n)
     {
         float e = kd.b6[m];
 #pragma unroll
@@ -366,10 +412,23 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_forward(const MlpArgs g) {
 #pragma unroll
             for (int q = 0; q < 4; q++) d[q] = fmaf(kLoInv, acc2[j][cb][q], acc1[j][cb][q]) * c2[j][cb][q];      // d2 / 16
             put_fragment(actB, rb, cb, lane, d);
+            if constexpr (WG) emit(wg_row_d2(kd.h1), rb, cb, d, true);
         }
     });
     __syncthreads();
     layer_resident(kd.w2t + (size_t)m * nb1 * s2 * 2 * kFrag, s2, nb1, n1, w, lane, actB, acc1, acc2);
+    if constexpr (WG) {
+        for_blocks(n1, w, [&](int j, int rb) {
+#pragma unroll
+            for (int cb = 0; cb < kCB; cb++) {
+                f32x4 d;
+#pragma unroll
+                for (int q = 0; q < 4; q++) d[q] = fmaf(kLoInv, acc2[j][cb][q], acc1[j][cb][q]) * c1[j][cb][q];      // d1 / 16
+                emit(wg_row_d1(), rb, cb, d, true);
+            }
+        });
+        return;
+    }
     if (g.dx_partial) {
         // Few input columns (the AEV blocks of the species the molecule has: x_groups): this member's share of dE/dx,
         // W0_m^T d1, is one more small product on the spot -- d1 goes to region A like d2 went to region B -- instead of a
@@ -999,6 +1058,71 @@ int nnpops_mlp_input_grad(void* stream, const nnpops_mlp_frame* frame) {
         return NNPOPS_OK;
     }
     hipLaunchKernelGGL(mlp_input_grad<false>, dim3(blocks), dim3(kThreads), 2 * kStageBytes, (hipStream_t)stream, g);
+    NNPOPS_HIP_TRY(hipGetLastError());
+    return NNPOPS_OK;
+}
+
+int64_t nnpops_mlp_weight_grad_workspace_bytes(const nnpops_mlp_frame* frame) {
+    if (!frame || frame->num_kinds < 1 || frame->num_kinds > NNPOPS_MLP_MAX_KINDS || frame->num_members < 1) return 0;
+    return wg_workspace_floats(frame) * (int64_t)sizeof(float);
+}
+
+int nnpops_mlp_weight_grad(void* stream, const nnpops_mlp_frame* frame, const nnpops_mlp_weight_grad_out* out) {
+    MlpWgArgs g{};
+    int blocks = 0;
+    int rc = check_and_fill(frame, g, true, frame ? frame->num_members : 1, &blocks);
+    if (rc != NNPOPS_OK) return rc;
+    NNPOPS_REQUIRE(out != nullptr && out->workspace != nullptr && ((uintptr_t)out->workspace % 16) == 0, "the workspace must be a 16-byte aligned device pointer");
+    NNPOPS_REQUIRE(out->workspace_bytes >= nnpops_mlp_weight_grad_workspace_bytes(frame), "the workspace holds %lld bytes, %lld are needed",
+                   (long long)out->workspace_bytes, (long long)nnpops_mlp_weight_grad_workspace_bytes(frame));
+    NNPOPS_REQUIRE(frame->num_members <= 65535, "at most 65535 members (got %d)", frame->num_members);
+    g.dx_partial = nullptr; g.publish_to = nullptr;          // (the tile pass forms no input gradient and publishes nothing)
+    WgArgs a{};
+    a.num_kinds = g.num_kinds; a.F = g.F; a.M = g.M; a.ldx = g.ldx; a.x = g.x; a.rows = g.rows; a.x_groups = g.x_groups;
+    float* ws = (float*)out->workspace;
+    int* live = (int*)out->workspace;
+    a.ws = ws; a.live = live;
+    WgTile& wt = g.wt;
+    wt.ws = ws; wt.live = live;
+    long base = (long)((g.M + kWgLiveFloats - 1) / kWgLiveFloats) * kWgLiveFloats;
+    int max_sum_rows = 1, max_blocks[3] = {1, 1, 1};
+    for (int k = 0; k < g.num_kinds; k++) {
+        const KindDesc& d = g.kinds[k];
+        const nnpops_mlp_weight_grad_kind& o = out->kinds[k];
+        NNPOPS_REQUIRE(o.dw0 && o.db0 && o.dw2 && o.db2 && o.dw4 && o.db4 && o.dw6 && o.db6, "NULL gradient pointer (kind %d)", k);
+        WgKind& wk = a.kinds[k];
+        wk.n = d.n; wk.first = d.first; wk.npad = d.tiles * kTile; wk.h1 = d.h1; wk.h2 = d.h2; wk.h3 = d.h3; wk.base = base;
+        wk.dw0 = o.dw0; wk.db0 = o.db0; wk.dw2 = o.dw2; wk.db2 = o.db2; wk.dw4 = o.dw4; wk.db4 = o.db4; wk.dw6 = o.dw6; wk.db6 = o.db6;
+        wt.base[k] = base;
+        base += (long)g.M * wg_rows(d.h1, d.h2, d.h3) * wk.npad;
+        max_sum_rows = std::max(max_sum_rows, wg_row_c(d.h1, d.h2, d.h3) + 1);
+        max_blocks[0] = std::max(max_blocks[0], ((d.h1 + 63) / 64) * ((g.F + 63) / 64));
+        max_blocks[1] = std::max(max_blocks[1], ((d.h2 + 63) / 64) * ((d.h1 + 63) / 64));
+        max_blocks[2] = std::max(max_blocks[2], ((d.h3 + 63) / 64) * ((d.h2 + 63) / 64));
+    }
+    for (int k = g.num_kinds; k < NNPOPS_MLP_MAX_KINDS; k++) { a.kinds[k] = a.kinds[0]; wt.base[k] = wt.base[0]; }
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(mlp_weight_live, dim3(1), dim3(256), 0, s, g.member_weights, g.ldw, std::max(g.w_segments, 1), g.M, live);
+    NNPOPS_HIP_TRY(hipGetLastError());
+    if (blocks > 0) {
+        const size_t lds = 2 * kStageBytes + 2 * kActBytes + 256 + kTile * sizeof(float);     // mlp_forward's, and the weights of the tile's atoms
+        static bool raised[64] = {};
+        int dev = 0;
+        NNPOPS_HIP_TRY(hipGetDevice(&dev));
+        if (dev >= 64 || !raised[dev & 63]) {
+            NNPOPS_HIP_TRY(hipFuncSetAttribute((const void*)mlp_forward<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            raised[dev & 63] = true;
+        }
+        hipLaunchKernelGGL((mlp_forward<true, true>), dim3(blocks), dim3(kThreads), lds, s, g);
+        NNPOPS_HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(mlp_weight_rowsums, dim3((max_sum_rows + 3) / 4, g.M, g.num_kinds), dim3(256), 0, s, a);
+    NNPOPS_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(mlp_weight_contract<0>, dim3(max_blocks[0], g.M, g.num_kinds), dim3(256), 0, s, a);
+    NNPOPS_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(mlp_weight_contract<1>, dim3(max_blocks[1], g.M, g.num_kinds), dim3(256), 0, s, a);
+    NNPOPS_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(mlp_weight_contract<2>, dim3(max_blocks[2], g.M, g.num_kinds), dim3(256), 0, s, a);
     NNPOPS_HIP_TRY(hipGetLastError());
     return NNPOPS_OK;
 }

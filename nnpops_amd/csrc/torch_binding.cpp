@@ -29,6 +29,7 @@
 #include <torch/script.h>
 #include <torch/serialize/archive.h>
 
+#include <array>
 #include <cmath>
 #include <cstdlib>
 #include <limits>
@@ -3121,6 +3122,17 @@ public:
                           int64_t members, const Tensor& planes, const Tensor& floats, const c10::optional<Tensor>& x_blocks,
                           const c10::optional<Tensor>& dead_blocks, int64_t act_scale_log2, const c10::optional<Tensor>& offsets,
                           const c10::optional<Tensor>& places, const c10::optional<Tensor>& shift, bool need_gradient) {
+        return run(ctx, x, rows, kind_atoms, widths, members, planes, floats, x_blocks, dead_blocks, act_scale_log2, offsets, places, shift, need_gradient,
+                   0);
+    }
+    // mean (FusedMLPMeanTrainable only) 1: the ensemble mean [B] of the one-node step (energy_step: the same launches on the same
+    // energies, hence its bits) instead of the member energies [B, M]; 2: the sum over atoms and members as FusedMLP returns it.
+    // What is kept for the backward pass is the same
+    static Tensor run(AutogradContext* ctx, const Tensor& x, const Tensor& rows, const std::vector<int64_t>& kind_atoms,
+                      const std::vector<int64_t>& widths, int64_t members, const Tensor& planes, const Tensor& floats,
+                      const c10::optional<Tensor>& x_blocks, const c10::optional<Tensor>& dead_blocks, int64_t act_scale_log2,
+                      const c10::optional<Tensor>& offsets, const c10::optional<Tensor>& places, const c10::optional<Tensor>& shift,
+                      bool need_gradient, int64_t mean) {
         const char* op = "NNPOpsBatchedNN::FusedMLPMembers";
         TORCH_CHECK(x.dim() == 2 && x.size(0) >= 1, "FusedMLPMembers: an empty batch (x must be [atoms, features] with at least one atom)");
         TORCH_CHECK(offsets.has_value() == places.has_value(), "FusedMLPMembers: molecule offsets and row places come together");
@@ -3140,9 +3152,22 @@ public:
         const int32_t* off = offsets.has_value() ? offsets->data_ptr<int32_t>() : nullptr;
         const int32_t* plc = places.has_value() ? places->data_ptr<int32_t>() : nullptr;
         Tensor out;
-        if (shift.has_value()) {
+        if (shift.has_value())
             TORCH_CHECK(shift->scalar_type() == torch::kFloat64 && shift->device() == x.device() && shift->numel() == 1 && shift->is_contiguous(),
                         "FusedMLPMembers: the self-energy shift must be one float64 on the device of x");
+        if (mean) {
+            const float scale = mean == 2 ? 1.0f : 1.0f / (float)members;
+            const float* e = call.energies.data_ptr<float>();
+            out = torch::empty({B}, shift.has_value() ? x.options().dtype(torch::kFloat64) : x.options());
+            int rc;
+            if (off) rc = shift.has_value()
+                ? nnpops_mlp_energy_mean_segments_shifted(stream, e, (int)x.size(0), (int)members, off, (int)B, plc, scale, shift->data_ptr<double>(), out.data_ptr<double>())
+                : nnpops_mlp_energy_mean_segments(stream, e, (int)x.size(0), (int)members, off, (int)B, plc, scale, out.data_ptr<float>());
+            else rc = shift.has_value()
+                ? nnpops_mlp_energy_mean_shifted(stream, e, call.energies.numel(), scale, shift->data_ptr<double>(), out.data_ptr<double>())
+                : nnpops_mlp_energy_mean(stream, e, call.energies.numel(), scale, out.data_ptr<float>());
+            if (rc != NNPOPS_OK) raise_last(op);
+        } else if (shift.has_value()) {
             out = torch::empty({B, members}, x.options().dtype(torch::kFloat64));
             if (nnpops_mlp_member_sums_shifted(stream, call.energies.data_ptr<float>(), (int)x.size(0), (int)members, off, (int)B, plc,
                                                shift->data_ptr<double>(), out.data_ptr<double>()) != NNPOPS_OK) raise_last(op);
@@ -3201,8 +3226,155 @@ Tensor FusedMLPMembers(const Tensor& x, const Tensor& rows, std::vector<int64_t>
                                           shift, need);
 }
 
+// =============================================================================================
+// FusedMLPMembersTrainable: FusedMLPMembers with the networks' parameters as differentiable inputs -- `parameters`, the eight
+// layer{0,2,4,6}_{weights,biases} tensors in the module's shapes [kinds, M, out, in] ([kinds, M, out, 1] for the biases), kind k of the
+// module being kind k of the op.  The forward pass does not read them: it is FusedMLPMembers' forward on the packed planes, bit for
+// bit, and the caller vouches that the planes were packed from these parameters (BatchedNN.py: _TrainableFusedNN).  The backward
+// pass returns the gradient of x as FusedMLPMembers does and, from one call of nnpops_mlp_weight_grad with the upstream gradient of
+// every (molecule, member) as its weights, the eight parameter gradients scattered into the module's shapes: entries outside a
+// kind's packed widths and the columns of dead AEV blocks are exact zeros.  First derivatives only.
+// =============================================================================================
+class FusedMLPMembersTrainableFunction : public torch::autograd::Function<FusedMLPMembersTrainableFunction> {
+public:
+    static Tensor forward(AutogradContext* ctx, const Tensor& x, const Tensor& rows, std::vector<int64_t> kind_atoms, std::vector<int64_t> widths,
+                          int64_t members, const Tensor& planes, const Tensor& floats, const c10::optional<Tensor>& x_blocks,
+                          const c10::optional<Tensor>& dead_blocks, int64_t act_scale_log2, const c10::optional<Tensor>& offsets,
+                          const c10::optional<Tensor>& places, const c10::optional<Tensor>& shift, bool need_gradient, int64_t mean,
+                          at::TensorList parameters) {
+        const int64_t kinds = (int64_t)kind_atoms.size();
+        TORCH_CHECK(parameters.size() == 8, "FusedMLPMembersTrainable: eight parameter tensors (layer{0,2,4,6}_{weights,biases}), got ", parameters.size());
+        std::vector<int64_t> shapes;
+        for (const Tensor& p : parameters) {
+            TORCH_CHECK(p.dim() == 4 && p.size(0) == kinds && p.size(1) == members && p.device() == x.device() && p.scalar_type() == torch::kFloat32,
+                        "FusedMLPMembersTrainable: parameters are float32 [kinds, members, out, in] tensors on the device of x");
+            shapes.push_back(p.size(2)); shapes.push_back(p.size(3));
+        }
+        Tensor out = FusedMLPMembersFunction::run(ctx, x, rows, kind_atoms, widths, members, planes, floats, x_blocks, dead_blocks, act_scale_log2,
+                                                  offsets, places, shift, need_gradient, mean);
+        if (need_gradient) { ctx->saved_data["parameter_shapes"] = shapes; ctx->saved_data["mean"] = mean; }
+        return out;
+    }
+    static tensor_list backward(AutogradContext* ctx, const tensor_list& grads) {
+        const char* op = "NNPOpsBatchedNN::FusedMLPMembersTrainable (backward)";
+        TORCH_CHECK(!torch::GradMode::is_enabled(), "NNPOpsBatchedNN::FusedMLPMembersTrainable: second derivatives are not implemented (create_graph=True): "
+                                                    "training on forces needs layout='grouped'");
+        const int64_t mean = ctx->saved_data["mean"].toInt();
+        const float mean_scale = mean == 2 ? 1.0f : 1.0f / (float)ctx->saved_data["members"].toInt();
+        tensor_list result;
+        if (!mean) result = FusedMLPMembersFunction::backward(ctx, grads);        // (dx in front; the weighted input gradient, as ever)
+        const auto saved = ctx->get_saved_variables();
+        TORCH_CHECK(!saved.empty(), "FusedMLPMembersTrainable was evaluated without a gradient request");
+        const Tensor &x = saved[0], &rows = saved[1], &planes = saved[2], &floats = saved[3];
+        const int64_t members = ctx->saved_data["members"].toInt();
+        const std::vector<int64_t> kind_atoms = ctx->saved_data["kind_atoms"].toIntVector(), widths = ctx->saved_data["widths"].toIntVector(),
+                                   shapes = ctx->saved_data["parameter_shapes"].toIntVector();
+        const c10::optional<Tensor> x_blocks = ctx->saved_data["x_blocks"].toOptional<Tensor>(), dead_blocks = ctx->saved_data["dead_blocks"].toOptional<Tensor>(),
+                                    offsets = ctx->saved_data["offsets"].toOptional<Tensor>();
+        const int64_t B = offsets.has_value() ? offsets->numel() - 1 : 1, kinds = (int64_t)kind_atoms.size();
+        Tensor g = grads[0].to(torch::kFloat32).contiguous();
+        if (mean) {                                           // every member of molecule b carries the mean's upstream gradient over M
+            TORCH_CHECK(g.numel() == B && g.device() == x.device(), "FusedMLPMeanTrainable: unexpected gradient of the energies (", B, " expected)");
+            g = (g.reshape({B, 1}) * mean_scale).expand({B, members}).contiguous();
+        }
+        MlpScratch own;                                       // (the frame needs workspaces of the gradient pass; the weight gradient touches none)
+        own.energies = saved[4];
+        if (ctx->saved_data["in_forward"].toBool()) own.partial = saved[5];
+        else own.d1.assign(saved.begin() + 5, saved.end());
+        c10::hip::HIPGuard guard(x.device().index());
+        MlpCall call = mlp_prepare(x, rows, kind_atoms, widths, members, planes, floats, true, x_blocks, dead_blocks,
+                                   ctx->saved_data["act_scale_log2"].toInt(), &own);
+        if (mean) {
+            // the gradient of x as the one-node step forms it -- the unweighted pass with 1 / M as its scale -- then times the upstream
+            // gradient of the row's molecule: with an upstream gradient of one, the bits energy_step hands to the AEV backward
+            Tensor dx = torch::empty_like(x);
+            call.frame.dx = dx.data_ptr<float>(); call.frame.lddx = (int)dx.size(1); call.frame.dx_scale = mean_scale;
+            if (nnpops_mlp_input_grad(current_stream(x.device()), &call.frame) != NNPOPS_OK) raise_last(op);
+            const Tensor up = grads[0].to(torch::kFloat32).reshape({B});
+            if (offsets.has_value()) {
+                const Tensor counts = (offsets->slice(0, 1, B + 1) - offsets->slice(0, 0, B)).to(torch::kLong);
+                dx.mul_(torch::repeat_interleave(up, counts, 0, x.size(0)).unsqueeze(1));
+            } else {
+                dx.mul_(up);
+            }
+            result = {dx, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+        }
+        call.frame.member_weights = g.data_ptr<float>(); call.frame.member_weights_ld = (int)members;
+        if (offsets.has_value()) { call.frame.segment_offsets = offsets->data_ptr<int32_t>(); call.frame.num_segments = (int)B; }
+        const int64_t F = call.frame.num_features, M = members;
+        nnpops_mlp_weight_grad_out wg{};
+        const int64_t bytes = nnpops_mlp_weight_grad_workspace_bytes(&call.frame);
+        Tensor workspace = torch::empty({std::max<int64_t>(bytes / 4, 64)}, x.options());
+        wg.workspace = workspace.data_ptr<float>(); wg.workspace_bytes = workspace.numel() * 4;
+        std::vector<std::array<Tensor, 8>> packed((size_t)kinds);
+        for (int64_t k = 0; k < kinds; k++) {
+            const int64_t h1 = widths[3 * k], h2 = widths[3 * k + 1], h3 = widths[3 * k + 2];
+            packed[k] = {torch::empty({M, h1, F}, x.options()), torch::empty({M, h1, 1}, x.options()), torch::empty({M, h2, h1}, x.options()),
+                         torch::empty({M, h2, 1}, x.options()), torch::empty({M, h3, h2}, x.options()), torch::empty({M, h3, 1}, x.options()),
+                         torch::empty({M, 1, h3}, x.options()), torch::empty({M, 1, 1}, x.options())};
+            nnpops_mlp_weight_grad_kind& o = wg.kinds[k];
+            float** slots[8] = {&o.dw0, &o.db0, &o.dw2, &o.db2, &o.dw4, &o.db4, &o.dw6, &o.db6};
+            for (int i = 0; i < 8; i++) *slots[i] = packed[k][i].data_ptr<float>();
+        }
+        if (nnpops_mlp_weight_grad(current_stream(x.device()), &call.frame, &wg) != NNPOPS_OK) raise_last(op);
+        // into the module's shapes: rows and columns up to the smaller of the packed width and the module's, the first layer's columns where
+        // the live blocks lie
+        Tensor live_columns;
+        if (call.frame.x_groups)
+            live_columns = ((x_blocks->to(torch::kLong) * 16).unsqueeze(1) + torch::arange(16, x_blocks->options().dtype(torch::kLong)).unsqueeze(0)).reshape(-1);
+        for (int i = 0; i < 8; i++) {
+            Tensor full = torch::zeros({kinds, M, shapes[2 * i], shapes[2 * i + 1]}, x.options());
+            for (int64_t k = 0; k < kinds; k++) {
+                const Tensor& src = packed[k][i];
+                const int64_t r = std::min<int64_t>(src.size(1), shapes[2 * i]);
+                if (i == 0 && live_columns.defined()) {
+                    full[k].narrow(1, 0, r).index_copy_(2, live_columns, src.narrow(1, 0, r));
+                    continue;
+                }
+                const int64_t c = std::min<int64_t>(src.size(2), shapes[2 * i + 1]);
+                full[k].narrow(1, 0, r).narrow(2, 0, c).copy_(src.narrow(1, 0, r).narrow(2, 0, c));
+            }
+            result.push_back(full);
+        }
+        result.insert(result.begin() + 14, Tensor());        // (the `mean` flag)
+        return result;
+    }
+};
+
+Tensor FusedMLPMembersTrainable(const Tensor& x, const Tensor& rows, std::vector<int64_t> kind_atoms, std::vector<int64_t> widths, int64_t members,
+                                const Tensor& planes, const Tensor& floats, const c10::optional<Tensor>& x_blocks,
+                                const c10::optional<Tensor>& dead_blocks, int64_t act_scale_log2, const c10::optional<Tensor>& offsets,
+                                const c10::optional<Tensor>& places, const c10::optional<Tensor>& shift, at::TensorList parameters) {
+    bool need = x.requires_grad();
+    for (const Tensor& p : parameters) need = need || p.requires_grad();
+    need = need && torch::GradMode::is_enabled();
+    return FusedMLPMembersTrainableFunction::apply(x, rows, kind_atoms, widths, members, planes, floats, x_blocks, dead_blocks, act_scale_log2, offsets,
+                                                   places, shift, need, (int64_t)0, parameters);
+}
+
+// FusedMLPMeanTrainable: the same node with the ensemble mean [B] as its output -- the energy of the one-node step
+// (NNPOpsANISymmetryFunctions::energy / energy_batch), bit for bit, and with an upstream gradient of one its gradient of x as well --
+// differentiable in the parameters: the weight gradient runs with upstream / M for every member of the molecule.  total: the sum over
+// atoms and members instead (scale 1, as FusedMLP returns it and differentiates it).
+Tensor FusedMLPMeanTrainable(const Tensor& x, const Tensor& rows, std::vector<int64_t> kind_atoms, std::vector<int64_t> widths, int64_t members,
+                             const Tensor& planes, const Tensor& floats, const c10::optional<Tensor>& x_blocks,
+                             const c10::optional<Tensor>& dead_blocks, int64_t act_scale_log2, const c10::optional<Tensor>& offsets,
+                             const c10::optional<Tensor>& places, const c10::optional<Tensor>& shift, at::TensorList parameters, bool total) {
+    bool need = x.requires_grad();
+    for (const Tensor& p : parameters) need = need || p.requires_grad();
+    need = need && torch::GradMode::is_enabled();
+    return FusedMLPMembersTrainableFunction::apply(x, rows, kind_atoms, widths, members, planes, floats, x_blocks, dead_blocks, act_scale_log2, offsets,
+                                                   places, shift, need, (int64_t)(total ? 2 : 1), parameters);
+}
+
 TORCH_LIBRARY(NNPOpsBatchedNN, m) {
     m.def("BatchedLinear", BatchedLinear);
+    m.def("FusedMLPMembersTrainable(Tensor x, Tensor rows, int[] kind_atoms, int[] widths, int members, Tensor planes, Tensor floats, Tensor? x_blocks, "
+          "Tensor? dead_blocks, int act_scale_log2, Tensor? offsets, Tensor? places, Tensor? shift, Tensor[] parameters) -> Tensor",
+          FusedMLPMembersTrainable);
+    m.def("FusedMLPMeanTrainable(Tensor x, Tensor rows, int[] kind_atoms, int[] widths, int members, Tensor planes, Tensor floats, Tensor? x_blocks, "
+          "Tensor? dead_blocks, int act_scale_log2, Tensor? offsets, Tensor? places, Tensor? shift, Tensor[] parameters, bool total=False) -> Tensor",
+          FusedMLPMeanTrainable);
     m.def("FusedMLPMembers(Tensor x, Tensor rows, int[] kind_atoms, int[] widths, int members, Tensor planes, Tensor floats, Tensor? x_blocks=None, "
           "Tensor? dead_blocks=None, int act_scale_log2=4, Tensor? offsets=None, Tensor? places=None, Tensor? shift=None) -> Tensor", FusedMLPMembers);
     m.def("FusedMLP(Tensor x, Tensor rows, int[] kind_atoms, int[] widths, int members, Tensor planes, Tensor floats, int act_scale_log2=4) -> Tensor", FusedMLP);
