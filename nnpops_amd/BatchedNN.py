@@ -5,6 +5,7 @@ common shape, four BatchedLinear calls with CELU(0.1) in between, and one fused 
 Buffer names (``layer{0,2,4,6}_{weights,biases}``) and the ModuleList-of-one structure are kept so
 that state dicts and TorchScript files stay interchangeable.
 """
+import math
 from typing import List, NamedTuple, Optional, Tuple
 
 import torch
@@ -493,14 +494,20 @@ class _TrainableFusedNN(_FusedSpeciesNN):
 
     The packed planes are derived from the parameters: they are rebuilt on the first forward pass after a parameter's version has
     changed (an optimizer step, an in-place edit) and after ``load_state_dict``; while the parameters stand, nothing is rebuilt
-    (``plane_rebuilds`` counts).  The widths every species is packed at are fixed at construction from the source networks; a rebuild
-    that finds others raises.  First derivatives only (no force-loss training: use ``layout='grouped'``), not scriptable."""
+    (``plane_rebuilds`` counts).  With float32 parameters on a GPU the rebuild is ``torch.ops.NNPOpsBatchedNN.PackNetworks``
+    (csrc/mlp_pack_networks.h: two launches, fresh tensors, the planes the host route writes bit for bit) and one small copy to the host
+    that carries every decision (``device_packs`` counts those); the constructor, CPU parameters, other dtypes and a new list of live
+    blocks pack on the host as the default module does.  The widths every species is packed at are fixed at construction from the
+    source networks; a rebuild that finds others raises and leaves the module as it was.  First derivatives only (no force-loss
+    training: use ``layout='grouped'``), not scriptable."""
 
-    __jit_ignored_attributes__ = ["_batch_plans", "_plane_versions", "_fixed_widths", "plane_rebuilds"]
+    __jit_ignored_attributes__ = ["_batch_plans", "_plane_versions", "_fixed_widths", "plane_rebuilds", "device_packs", "_blocks_packed"]
 
     _fixed_widths = None           # (class defaults: _refresh_planes runs inside the parent's constructor)
     _plane_versions = None
     plane_rebuilds = 0
+    device_packs = 0               # the rebuilds among them that packed on the device (torch.ops.NNPOpsBatchedNN.PackNetworks)
+    _blocks_packed = None          # the live blocks x_blocks / dead_blocks were last built for (on the host)
 
     def __init__(self, converter, ensemble, atomicNumbers: Tensor):
         super().__init__(converter, ensemble, atomicNumbers)
@@ -521,14 +528,66 @@ class _TrainableFusedNN(_FusedSpeciesNN):
         return out
 
     @torch.jit.unused
+    def _packs_on_device(self) -> bool:
+        """whether a rebuild can take ``torch.ops.NNPOpsBatchedNN.PackNetworks``: a constructed module whose eight parameters are float32
+        on one GPU, in the shape of the fused kernels, with the live blocks its ``x_blocks`` already holds"""
+        if self._fixed_widths is None or self._blocks_packed != self.live_blocks:
+            return False
+        parameters = [getattr(self, name) for name in PARAMETER_NAMES]
+        w0, w6 = parameters[0], parameters[6]
+        if any(not p.is_cuda or p.dtype != torch.float32 or p.device != w0.device or not p.is_contiguous() for p in parameters):
+            return False
+        if self.x_blocks.device != w0.device or self.x_blocks.dtype != torch.int32:
+            return False
+        return (int(w0.shape[3]) % 8 == 0 and int(w0.shape[3]) <= 1024 and max(self._fixed_widths) <= 256 and int(w0.shape[0]) <= 8
+                and int(w0.shape[1]) <= 128 and int(w6.shape[2]) == 1)
+
+    @torch.jit.unused
+    def _refresh_planes_on_device(self) -> None:
+        """``_FusedSpeciesNN._refresh_planes`` with the planes packed by one op (csrc/mlp_pack_networks.h) and every decision taken from
+        its status block: one small copy to the host, nothing else waits for the device"""
+        parameters = [getattr(self, name).detach() for name in PARAMETER_NAMES]
+        planes, floats, live, status = torch.ops.NNPOpsBatchedNN.PackNetworks(parameters, self._fixed_widths, self.x_blocks if self.live_blocks else None)
+        words = status.cpu()
+        last, not_finite, scalars = words[:24].tolist(), int(words[24]), words[26:44].view(torch.float64).tolist()
+        shapes = [int(parameters[i].shape[2]) for i in (0, 2, 4)]
+        kinds = int(parameters[0].shape[0])
+        widths = [min(_up32(max(last[3 * k + layer], 1)), _up32(shapes[layer])) for k in range(kinds) for layer in range(3)]
+        if widths != self._fixed_widths:                   # (BEFORE anything is replaced, as on the host)
+            raise RuntimeError(f"the networks' widths changed from {self._fixed_widths} to {widths}: the structure of a trainable "
+                               "module is fixed at construction (the zero padding must stay zero)")
+        rows, columns, biases, last_weight = scalars[0:3], scalars[3:5], scalars[5:8], scalars[8]
+        bound = 64.0                                       # (the bounds of _FusedSpeciesNN._refresh_planes, from the block's nine scalars)
+        for row, bias in zip(rows, biases):
+            bound = row * bound + bias
+        back = last_weight * columns[0] * columns[1]
+        worst = max(bound, back) if not not_finite and math.isfinite(bound) and math.isfinite(back) else float("inf")
+        k = 4
+        while k < 12 and worst >= 62500.0 * 2.0 ** k:
+            k += 1
+        self.mlp_planes, self.mlp_floats, self.live_planes = planes, floats, live
+        self.act_scale_log2 = k
+        self.fused_ok = worst < 62500.0 * 2.0 ** k         # (the shape was checked before this route was taken)
+        holder = getattr(self, 'holder', None)
+        if holder is not None:
+            holder.reset_gradient_cache()
+        for plan in self._batch_plans.values():
+            plan[0].reset_gradient_cache()
+        self.device_packs += 1
+
+    @torch.jit.unused
     def _refresh_planes(self) -> None:
         with torch.no_grad():
-            if self._fixed_widths is not None:             # (checked BEFORE anything is replaced: a refused structure leaves the module as it was)
-                widths = self._packed_widths()
-                if widths != self._fixed_widths:
-                    raise RuntimeError(f"the networks' widths changed from {self._fixed_widths} to {widths}: the structure of a trainable "
-                                       "module is fixed at construction (the zero padding must stay zero)")
-            super()._refresh_planes()
+            if self._packs_on_device():
+                self._refresh_planes_on_device()
+            else:
+                if self._fixed_widths is not None:         # (checked BEFORE anything is replaced: a refused structure leaves the module as it was)
+                    widths = self._packed_widths()
+                    if widths != self._fixed_widths:
+                        raise RuntimeError(f"the networks' widths changed from {self._fixed_widths} to {widths}: the structure of a trainable "
+                                           "module is fixed at construction (the zero padding must stay zero)")
+                super()._refresh_planes()
+                self._blocks_packed = list(self.live_blocks)
         self.plane_rebuilds += 1
         self._plane_versions = self._versions()
 

@@ -86,6 +86,9 @@ SIGNATURES = {
     "nnpops_mlp_packed_halves": (C.c_int64, [C.c_int, C.c_int]),
     "nnpops_mlp_d1_halves": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "nnpops_mlp_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p]),
+    "nnpops_mlp_networks_plane_halves": (C.c_int64, [C.c_void_p, C.c_int]),
+    "nnpops_mlp_networks_floats": (C.c_int64, [C.c_void_p]),
+    "nnpops_mlp_pack_networks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_mlp_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "nnpops_mlp_input_grad": (C.c_int, [C.c_void_p, C.c_void_p]),
     "nnpops_mlp_weight_grad_workspace_bytes": (C.c_int64, [C.c_void_p]),
@@ -1040,6 +1043,30 @@ class _MlpWeightGradOut(C.Structure):
     _fields_ = [("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("kinds", _MlpWeightGradKind * MLP_MAX_KINDS)]
 
 
+MLP_PACK_STATUS_BYTES = 176
+MLP_PARAMETERS = tuple(f"layer{layer}_{what}" for layer in (0, 2, 4, 6) for what in ("weights", "biases"))
+
+
+class _MlpNetworks(C.Structure):
+    _fields_ = [("num_kinds", C.c_int), ("num_members", C.c_int), ("num_features", C.c_int),
+                ("out0", C.c_int), ("out2", C.c_int), ("in2", C.c_int), ("out4", C.c_int), ("in4", C.c_int), ("out6", C.c_int), ("in6", C.c_int),
+                *[(name, C.c_void_p) for name in MLP_PARAMETERS],
+                ("widths", C.c_int * (3 * MLP_MAX_KINDS)), ("live_blocks", C.c_void_p), ("num_live_blocks", C.c_int)]
+
+
+def mlp_networks(shapes, widths, num_live_blocks=0):
+    """The descriptor of nnpops_mlp_pack_networks for parameter arrays of these shapes (layer{0,2,4,6}_weights [kinds, M, out, in], in that
+    order) and packed widths (h1, h2, h3 per kind); pointers unset.  Shapes the descriptor cannot hold are the library's to refuse."""
+    w0, w2, w4, w6 = (tuple(int(v) for v in s) for s in shapes)
+    nets = _MlpNetworks()
+    nets.num_kinds, nets.num_members, nets.num_features = w0[0], w0[1], w0[3]
+    nets.out0, nets.out2, nets.in2, nets.out4, nets.in4, nets.out6, nets.in6 = w0[2], w2[2], w2[3], w4[2], w4[3], w6[2], w6[3]
+    for i, h in enumerate(list(widths)[:3 * MLP_MAX_KINDS]):
+        nets.widths[i] = int(h)
+    nets.num_live_blocks = int(num_live_blocks)
+    return nets
+
+
 def mlp_pack(w, rows, cols, transpose=False, permute=False):
     """fp32 device matrix -> the fragment planes nnpops_mlp_forward / _input_grad take as the LEFT operand of a product with
     `rows` outputs and `cols` inputs (`w` is [rows][cols], or [cols][rows] with transpose)."""
@@ -1217,6 +1244,43 @@ class FusedMLP:
             self.frame.segment_offsets, self.frame.num_segments = saved
         return [{name: t[tuple(slice(0, n) for n in shape)].contiguous() for name, t, shape in zip(MLP_GRADIENTS, arrays, shapes)}
                 for arrays, shapes in zip(full, self._shapes)]
+
+    @staticmethod
+    def pack_networks(parameters, widths, x_blocks=None):
+        """All planes of an ensemble from its eight parameter arrays in a module's layout (nnpops_mlp_pack_networks): ``parameters`` the
+        float32 device tensors layer{0,2,4,6}_{weights,biases} [kinds, M, out, in], ``widths`` (h1, h2, h3) per kind, ``x_blocks`` an int32
+        device tensor of live 16-column blocks or None -> (planes fp16, floats fp32, live_planes fp16 -- empty without blocks --, status
+        int32 [44]; nnpops_hip.h).  Fresh tensors, two launches on the current stream, no synchronisation."""
+        parameters = list(parameters)
+        if len(parameters) != 8 or any(p.dim() != 4 for p in parameters):
+            raise ValueError("eight [kinds, M, out, in] arrays")
+        parameters = [_dev_f32(p, name) for p, name in zip(parameters, MLP_PARAMETERS)]
+        dev = parameters[0].device
+        blocks = 0
+        if x_blocks is not None and x_blocks.numel() > 0:
+            if not (x_blocks.is_cuda and x_blocks.dtype == torch.int32 and x_blocks.is_contiguous()):
+                raise ValueError('"x_blocks" must be a contiguous int32 device tensor')
+            blocks = int(x_blocks.numel())
+        nets = mlp_networks([p.shape for p in parameters[0::2]], widths, blocks)
+        if len(widths) != 3 * nets.num_kinds:
+            raise ValueError("three widths per kind")
+        for name, w, b in zip(MLP_PARAMETERS[0::2], parameters[0::2], parameters[1::2]):
+            if tuple(b.shape) != (*w.shape[:3], 1) or tuple(w.shape[:2]) != tuple(parameters[0].shape[:2]):
+                raise ValueError(f"{name}: weights [kinds, M, out, in] come with biases [kinds, M, out, 1]")
+        for name, p in zip(MLP_PARAMETERS, parameters):
+            setattr(nets, name, p.data_ptr())
+        nets.live_blocks = x_blocks.data_ptr() if blocks else None
+        sizes = [int(lib().nnpops_mlp_networks_plane_halves(C.byref(nets), 0)), int(lib().nnpops_mlp_networks_floats(C.byref(nets))),
+                 int(lib().nnpops_mlp_networks_plane_halves(C.byref(nets), 1))]
+        if min(sizes) < 0:
+            _check(min(sizes))
+        planes = torch.empty((sizes[0],), dtype=torch.float16, device=dev)
+        floats = torch.empty((sizes[1],), dtype=torch.float32, device=dev)
+        live = torch.empty((sizes[2],), dtype=torch.float16, device=dev)
+        status = torch.empty((MLP_PACK_STATUS_BYTES // 4,), dtype=torch.int32, device=dev)
+        _check(lib().nnpops_mlp_pack_networks(_stream_ptr(dev), C.byref(nets), _ptr(planes), _ptr(floats), _ptr(live) if blocks else None,
+                                              _ptr(status)))
+        return planes, floats, live, status
 
 
 def scale_by_scalar(values, factor):

@@ -1,5 +1,5 @@
 // mlp_fused.hip -- the ANI atomic networks of a frame as ONE forward launch and ONE input-gradient launch
-// (C ABI: nnpops_mlp_pack, nnpops_mlp_forward, nnpops_mlp_input_grad).
+// (C ABI: nnpops_mlp_pack, nnpops_mlp_pack_networks, nnpops_mlp_forward, nnpops_mlp_input_grad).
 //
 // What it serves: TorchANIBatchedNN inside OptimizedTorchANI (reference src/pytorch/BatchedNN.py:37-122,
 // OptimizedTorchANI.py:49-52): per atom and ensemble member  Linear(F,H1) CELU Linear(H1,H2) CELU Linear(H2,H3) CELU
@@ -750,6 +750,8 @@ __global__ __launch_bounds__(256) void mlp_pack(int rows, int cols, const float*
     }
 }
 
+#include "mlp_pack_networks.h"               // (all planes of an ensemble from its parameter arrays, and what the host decides from)
+
 // out[0] = scale * sum of v[0 .. n): one workgroup, double accumulation, fixed order (bitwise reproducible)
 // (shift != NULL: out is a double and gets (double)(float)mean + shift[0] -- the float energy promoted and shifted exactly as
 //  `energies + self_energies` does it in the reference's EnergyShifter.py:52)
@@ -916,6 +918,24 @@ int nnpops_mlp_pack(void* stream, int rows, int cols, const float* w, long ldw, 
     hipLaunchKernelGGL(mlp_pack, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rows, cols, w, ldw, transpose, permute, (_Float16*)out);
     NNPOPS_HIP_TRY(hipGetLastError());
     return NNPOPS_OK;
+}
+
+int64_t nnpops_mlp_networks_plane_halves(const nnpops_mlp_networks* nets, int live) {
+    PkArgs g{};
+    int64_t halves[2];
+    const int rc = pk_plan(nets, g, halves);
+    return rc != NNPOPS_OK ? rc : halves[live ? 1 : 0];
+}
+
+int64_t nnpops_mlp_networks_floats(const nnpops_mlp_networks* nets) {
+    PkArgs g{};
+    int64_t halves[2];
+    const int rc = pk_plan(nets, g, halves);
+    return rc != NNPOPS_OK ? rc : g.float0[g.kinds];
+}
+
+int nnpops_mlp_pack_networks(void* stream, const nnpops_mlp_networks* nets, void* planes, float* floats, void* live_planes, void* status) {
+    return pk_launch((hipStream_t)stream, nets, planes, floats, live_planes, status);
 }
 
 int nnpops_mlp_forward(void* stream, const nnpops_mlp_frame* frame, int with_gradient) {

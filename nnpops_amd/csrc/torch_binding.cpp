@@ -3367,7 +3367,58 @@ Tensor FusedMLPMeanTrainable(const Tensor& x, const Tensor& rows, std::vector<in
                                                    places, shift, need, (int64_t)(total ? 2 : 1), parameters);
 }
 
+// =============================================================================================
+// PackNetworks: the packed planes of FusedMLP* from the eight parameter arrays of a module ([kinds, M, out, in] / [kinds, M, out, 1],
+// float32, contiguous, on one device) at the given packed widths, by nnpops_mlp_pack_networks: two launches on the current stream and
+// no synchronisation.  -> (planes, floats, live_planes -- over the column blocks of x_blocks; an empty float32 tensor without them, as
+// the module keeps it --, status: int32 [NNPOPS_MLP_PACK_STATUS_BYTES / 4], nnpops_hip.h).  FRESH tensors every call: a graph recorded
+// on earlier planes keeps them.  Device tensors only, no autograd (the planes are not differentiable: FusedMLP*Trainable are).
+// =============================================================================================
+std::tuple<Tensor, Tensor, Tensor, Tensor> PackNetworks(at::TensorList parameters, std::vector<int64_t> widths, const c10::optional<Tensor>& x_blocks) {
+    const char* op = "NNPOpsBatchedNN::PackNetworks";
+    TORCH_CHECK(parameters.size() == 8, "PackNetworks: eight parameter tensors (layer{0,2,4,6}_{weights,biases}), got ", parameters.size());
+    const Tensor& w0 = parameters[0];
+    for (size_t i = 0; i < 8; i++) {
+        const Tensor& p = parameters[i];
+        TORCH_CHECK(p.is_cuda() && p.dim() == 4 && p.scalar_type() == torch::kFloat32 && p.is_contiguous() && p.device() == w0.device() &&
+                    p.size(0) == w0.size(0) && p.size(1) == w0.size(1),
+                    "PackNetworks: parameters are contiguous float32 [kinds, members, out, in] tensors on one device");
+        if (i % 2)
+            TORCH_CHECK(p.size(2) == parameters[i - 1].size(2) && p.size(3) == 1, "PackNetworks: biases are [kinds, members, out, 1]");
+    }
+    nnpops_mlp_networks nets{};
+    TORCH_CHECK(w0.size(0) <= NNPOPS_MLP_MAX_KINDS && (int64_t)widths.size() == 3 * w0.size(0), "PackNetworks: at most ", NNPOPS_MLP_MAX_KINDS,
+                " kinds, three widths each");
+    auto dim = [&](int i, int d) { return (int)std::min<int64_t>(parameters[i].size(d), 1 << 30); };
+    nets.num_kinds = dim(0, 0); nets.num_members = dim(0, 1); nets.num_features = dim(0, 3);
+    nets.out0 = dim(0, 2); nets.out2 = dim(2, 2); nets.in2 = dim(2, 3); nets.out4 = dim(4, 2); nets.in4 = dim(4, 3); nets.out6 = dim(6, 2); nets.in6 = dim(6, 3);
+    const float** slots[8] = {&nets.layer0_weights, &nets.layer0_biases, &nets.layer2_weights, &nets.layer2_biases,
+                              &nets.layer4_weights, &nets.layer4_biases, &nets.layer6_weights, &nets.layer6_biases};
+    for (int i = 0; i < 8; i++) *slots[i] = parameters[i].data_ptr<float>();
+    for (size_t i = 0; i < widths.size(); i++) nets.widths[i] = (int)std::min<int64_t>(std::max<int64_t>(widths[i], -1), 1 << 30);
+    const bool narrow = x_blocks.has_value() && x_blocks->numel() > 0;
+    if (narrow) {
+        TORCH_CHECK(x_blocks->scalar_type() == torch::kInt32 && x_blocks->is_contiguous() && x_blocks->device() == w0.device() && x_blocks->dim() == 1,
+                    "PackNetworks: x_blocks must be a contiguous int32 vector on the device of the parameters");
+        nets.live_blocks = x_blocks->data_ptr<int32_t>();
+        nets.num_live_blocks = (int)std::min<int64_t>(x_blocks->numel(), 1 << 30);
+    }
+    const int64_t halves = nnpops_mlp_networks_plane_halves(&nets, 0);
+    if (halves < 0) raise_last(op);
+    const int64_t floats_n = nnpops_mlp_networks_floats(&nets), live_n = nnpops_mlp_networks_plane_halves(&nets, 1);
+    if (floats_n < 0 || live_n < 0) raise_last(op);
+    c10::hip::HIPGuard guard(w0.device().index());
+    const auto f32 = w0.options().requires_grad(false);
+    Tensor planes = torch::empty({halves}, f32.dtype(torch::kFloat16)), floats = torch::empty({floats_n}, f32);
+    Tensor live = narrow ? torch::empty({live_n}, f32.dtype(torch::kFloat16)) : torch::empty({0}, f32);
+    Tensor status = torch::empty({NNPOPS_MLP_PACK_STATUS_BYTES / 4}, f32.dtype(torch::kInt32));
+    if (nnpops_mlp_pack_networks(current_stream(w0.device()), &nets, planes.data_ptr(), floats.data_ptr<float>(), narrow ? live.data_ptr() : nullptr,
+                                 status.data_ptr()) != NNPOPS_OK) raise_last(op);
+    return {planes, floats, live, status};
+}
+
 TORCH_LIBRARY(NNPOpsBatchedNN, m) {
+    m.def("PackNetworks(Tensor[] parameters, int[] widths, Tensor? x_blocks) -> (Tensor planes, Tensor floats, Tensor live_planes, Tensor status)");
     m.def("BatchedLinear", BatchedLinear);
     m.def("FusedMLPMembersTrainable(Tensor x, Tensor rows, int[] kind_atoms, int[] widths, int members, Tensor planes, Tensor floats, Tensor? x_blocks, "
           "Tensor? dead_blocks, int act_scale_log2, Tensor? offsets, Tensor? places, Tensor? shift, Tensor[] parameters) -> Tensor",
@@ -3381,5 +3432,7 @@ TORCH_LIBRARY(NNPOpsBatchedNN, m) {
     m.def("GroupedMLP(Tensor x, Tensor order, int[] group_sizes, int num_models, int h1, int h2, int h3, Tensor fwd_hi, Tensor fwd_lo, "
           "Tensor bwd_hi, Tensor bwd_lo, Tensor biases, Tensor last_w, float[] last_b) -> Tensor", GroupedMLP);
 }
+
+TORCH_LIBRARY_IMPL(NNPOpsBatchedNN, CUDA, m) { m.impl("PackNetworks", PackNetworks); }
 
 }  // namespace

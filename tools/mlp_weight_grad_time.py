@@ -7,8 +7,12 @@ call, cases interleaved, medians of several rounds.
 
     (a) default module: energy + coordinate gradient         what a step with fixed networks costs
     (b) trainable module: the same + the eight weight gradients
-    (c) one rebuild of the packed planes (wall clock: it runs on the host as well)   what an optimizer step adds before the next forward
+    (c) one rebuild of the packed planes: what an optimizer step adds before the next forward.  On the host route
+        (_FusedSpeciesNN._refresh_planes: a few hundred small torch calls, wall clock) and on the device route
+        (torch.ops.NNPOpsBatchedNN.PackNetworks + one small copy to the host: stream time and wall clock)
     (g) nn_layout='grouped', trainable=True: the step of (b) in plain torch, on the same device in the same run
+    (l) a full loop step -- zero_grad, forward, backward, opt.step() (SGD), the next forward finding new weights -- of the fused and of
+        the grouped trainable module: wall clock per step with the device drained at the end, and stream time
 Prints the largest difference between the fused and the grouped parameter gradients as a fraction of each array's largest entry, as a
 sanity figure (both float32).
 
@@ -87,13 +91,43 @@ def measure(name, rounds, profile):
 
     step_fused, step_grouped = step_of(fused), step_of(grouped)
     nets = fused.neural_networks[0]
+    call(fused, p)                                                     # (the planes of the module on the device)
+    assert nets._packs_on_device(), "the fused trainable module does not pack on the device here"
+    from NNPOps.BatchedNN import _FusedSpeciesNN
+
+    def loop_of(module):
+        opt = torch.optim.SGD(module.neural_networks.parameters(), lr=1e-9)
+
+        def step():
+            opt.zero_grad(set_to_none=True)
+            p.grad = None
+            call(module, p).sum().backward()
+            opt.step()
+        return step
+
+    loop_fused, loop_grouped = loop_of(fused), loop_of(grouped)
+    parameters = [q.detach() for q in nets.parameters()]
+
+    def pack_alone():                                                  # (the op without the copy of its status block: nothing waits)
+        return torch.ops.NNPOpsBatchedNN.PackNetworks(parameters, nets.widths, nets.x_blocks if nets.live_blocks else None)
+
+    def host_route():
+        with torch.no_grad():
+            _FusedSpeciesNN._refresh_planes(nets)
     stream = [("(a) default: energy + coordinate gradient", step_default),
               ("(b) trainable, fused: + the eight weight gradients", step_fused),
-              ("(g) trainable, grouped (plain torch): the same step", step_grouped)]
-    wall = [("(c) one rebuild of the packed planes (wall clock)", nets._refresh_planes)]
+              ("(g) trainable, grouped (plain torch): the same step", step_grouped),
+              ("(c) PackNetworks alone: the two launches (stream)", pack_alone),
+              ("(c) rebuild of the planes, device route (stream)", nets._refresh_planes),
+              ("(l) loop step, fused (stream)", loop_fused),
+              ("(l) loop step, grouped (stream)", loop_grouped)]
+    wall = [("(c) rebuild of the planes, host route (wall clock)", host_route),
+            ("(c) rebuild of the planes, device route (wall clock)", nets._refresh_planes),
+            ("(l) loop step, fused (wall clock)", loop_fused),
+            ("(l) loop step, grouped (wall clock)", loop_grouped)]
     if profile:
         for _ in range(3):
-            for _, fn in stream + wall:
+            for _, fn in stream[:5]:
                 fn()
         torch.cuda.synchronize()
         return
@@ -104,7 +138,12 @@ def measure(name, rounds, profile):
     print(f"{name}: {coords.shape[0]} x {coords.shape[1]} atoms, 8 members, medians of {rounds} interleaved rounds (spread = max - min):")
     for n, m, s in zip(names, med, spread):
         print(f"  {n:58s} {m:10.1f} us  (spread {s:.1f})")
-    print(f"  (b) / (a) {med[1] / med[0]:.2f}    (g) / (b) {med[2] / med[1]:.2f}    (c) / (b) {med[3] / med[1]:.2f}")
+    print(f"  (b) / (a) {med[1] / med[0]:.2f}    (g) / (b) {med[2] / med[1]:.2f}    (c) host / device, wall clock {med[7] / med[8]:.1f}"
+          f"    (l) grouped / fused, wall clock {med[10] / med[9]:.2f}")
+    read = sum(q.numel() * 4 for q in parameters)
+    written = 2 * (nets.mlp_planes.numel() + nets.live_planes.numel()) + 4 * nets.mlp_floats.numel()
+    print(f"  the device rebuild reads {read / 1e6:.1f} MB of parameters once (the first layer three to five times: its planes, their transposes,"
+          f" the live sets) and writes {written / 1e6:.1f} MB: {(read + written) / med[3] / 1e6:.2f} TB/s of stream time counting every array once")
     worst = 0.0
     for a, b in zip(step_fused()[1:], step_grouped()[1:]):
         for k in range(a.shape[0]):
