@@ -15,6 +15,7 @@
  *   nnpops_cfconv_create / compute / backprop   CFConv ctor / compute / backprop   src/schnet/CFConv.h:109-217
  *   nnpops_cfconv_backprop_box       (additive) backprop and the box-vector gradient of a periodic list
  *   nnpops_cfconv_double_backward    (additive) the backward of backprop: second derivatives w.r.t. positions and input
+ *   nnpops_cfconv_double_backward_weights   (additive) the weight gradients of what double_backward differentiates (a force loss)
  *   nnpops_cfconv_backprop_weights / _set_weights   (additive) gradients of the filter network's four weight arrays; new weights for a
  *                                               live handle (trainable filters)
  *   nnpops_neighbor_pairs_forward / _backward   neighbors::getNeighborPairs forward/backward kernels
@@ -317,6 +318,25 @@ int nnpops_cfconv_describe(nnpops_cfconv_t h, int32_t out[8]);
  * filter rows) is left untouched. */
 int nnpops_cfconv_backprop_weights(nnpops_cfconv_t h, nnpops_cfconv_neighbors_t neighbors, const float* input, const float* output_deriv,
                                    float* w1_deriv, float* b1_deriv, float* w2_deriv, float* b2_deriv);
+/* The weight gradients of a force loss: the gradients, with respect to the filter network's four weight arrays, of the scalar that
+ * nnpops_cfconv_double_backward differentiates.  With output_deriv g, input x and the cotangents gg_input_deriv V [N][W] of backprop's
+ * input_deriv and gg_position_deriv Q [N][3] of its position_deriv, M = <V, gx> + <Q, gp>, and this returns
+ *     w1_deriv [W][G] = dM/dw1,   b1_deriv [W],   w2_deriv [W][W] ([out][in]),   b2_deriv [W]       (the layouts create() takes)
+ * for the list's last build(), the pair set and the minimum-image shifts held fixed.  Either cotangent may be NULL, meaning zero, but
+ * not both; with Q NULL the result is that of nnpops_cfconv_backprop_weights with V in the place of input.  All pointers are device
+ * pointers; the four outputs are fully overwritten.  Only the list's rows, stored distances and pair slots and the per-atom arrays are
+ * read, so periodic and batched lists work as they are.  Nothing here is differentiated further (no weight-weight second
+ * derivatives).  With Q given, a short pass over the neighbour rows first writes the pair scalar u.(Q_j - Q_i) per pair slot; one kernel
+ * over the pair slots (the fp32 matrix instruction where the width is a multiple of 16 up to 128 and its LDS image -- both weight
+ * matrices, six pair tiles and two Gaussian tiles -- fits in 160 KiB, a vector kernel otherwise) then writes one partial row per
+ * workgroup, and nnpops_cfconv_backprop_weights' finish adds the rows in a fixed order in float64: no atomics, two calls agree bit
+ * for bit, a list without pairs gives exact zeros.  Runs on the convolution's stream with no host synchronisation; its scratch (one
+ * float per pair slot, and the partial rows it shares with nnpops_cfconv_backprop_weights, at most 32 MiB) is allocated by the first call
+ * and again only when the list's capacity has grown, so run one step before capturing a HIP graph.  What compute / backprop keep
+ * between calls (the filter rows) is left untouched. */
+int nnpops_cfconv_double_backward_weights(nnpops_cfconv_t h, nnpops_cfconv_neighbors_t neighbors, const float* input,
+                                          const float* output_deriv, const float* gg_input_deriv, const float* gg_position_deriv,
+                                          float* w1_deriv, float* b1_deriv, float* w2_deriv, float* b2_deriv);
 /* New weights for a live convolution (after an optimizer step): four HOST arrays exactly as nnpops_cfconv_create takes them.  The plan
  * is made again from the new values (the split-fp16 decision and word 7 depend on them; nnpops_cfconv_describe reports the new plan),
  * every packed form create() uploads is uploaded again and the kept filter rows are forgotten: the handle then computes, bit for

@@ -23,7 +23,16 @@ Trainable filters (an extension): ``CFConv(..., trainable=True)`` turns the four
 convolution's own handle is given the new values on the first forward pass after an optimizer step, ``load_state_dict`` or
 ``.to(device)``, and nothing is copied while they stand.  Forward and the gradients in positions, input and box are those of the
 default layer, bit for bit.  First derivatives only: ``create_graph=True`` raises, and so does ``trainable=True`` together with
-``twice_differentiable=True`` (mixed second derivatives with respect to the weights are not implemented).
+``twice_differentiable=True`` (mixed second derivatives with respect to the weights are not implemented by those two ops).
+
+Trainable filters under a force loss (an extension): ``CFConv(..., force_trainable=True)`` has the four parameters of
+``trainable=True`` (same names and shapes: state dicts interchange, ``.to(device)``, optimizers and the lazy upload work as there) and
+records its backward pass as ``twice_differentiable=True`` does, so that ``F = -torch.autograd.grad(E, positions, create_graph=True)``
+followed by ``loss(E, F).backward()`` reaches the weights: the mixed second derivatives come from one more kernel over the pair list.
+Forward, first gradients and first-order weight gradients are those of ``trainable=True``, the second derivatives in positions and
+input those of ``twice_differentiable=True``, bit for bit.  The flag stands alone (with either of the other two it raises).  Refused:
+third derivatives, second derivatives of the weight gradients themselves, a box that requires a gradient, a list rebuilt or weights
+changed between the forward pass and the last derivative.
 """
 from typing import Optional
 
@@ -39,15 +48,19 @@ torch_binding.load()
 class CFConv(torch.nn.Module):
 
     def __init__(self, gaussianWidth: float, activation: str, weights1: Tensor, biases1: Tensor, weights2: Tensor,
-                 biases2: Tensor, twice_differentiable: bool = False, trainable: bool = False) -> None:
+                 biases2: Tensor, twice_differentiable: bool = False, trainable: bool = False, force_trainable: bool = False) -> None:
         super().__init__()
+        if force_trainable and (trainable or twice_differentiable):
+            raise ValueError("CFConv: force_trainable=True stands alone: it already has the parameters of trainable=True and the second "
+                             "derivatives of twice_differentiable=True, and cannot be combined with either flag")
         if trainable and twice_differentiable:
             raise ValueError("CFConv: trainable=True cannot be combined with twice_differentiable=True: mixed second derivatives with "
                              "respect to the filter network's weights (a force loss differentiated with respect to them) are not "
-                             "implemented")
+                             "implemented by these two flags; CFConv(..., force_trainable=True) has them")
         self.twice_differentiable = twice_differentiable
         self.trainable = trainable
-        if trainable:
+        self.force_trainable = force_trainable
+        if trainable or force_trainable:
             new = lambda t: torch.nn.Parameter(t.detach().to(torch.float32).clone().contiguous())
             self.weights1, self.biases1 = new(weights1), new(biases1)
             self.weights2, self.biases2 = new(weights2), new(biases2)
@@ -57,6 +70,12 @@ class CFConv(torch.nn.Module):
         self.holder = torch.classes.NNPOpsCFConv.Holder(gaussianWidth, activation, weights1, biases1, weights2, biases2)
 
     def forward(self, neighbors: CFConvNeighbors, positions: Tensor, input: Tensor, box: Optional[Tensor] = None) -> Tensor:
+        if self.force_trainable:
+            if box is None:
+                return torch.ops.NNPOpsCFConv.operation_weights_twice(self.holder, neighbors.holder, positions, input, self.weights1,
+                                                                      self.biases1, self.weights2, self.biases2)
+            return torch.ops.NNPOpsCFConv.operation_periodic_weights_twice(self.holder, neighbors.holder, positions, box, input,
+                                                                           self.weights1, self.biases1, self.weights2, self.biases2)
         if self.trainable:
             if box is None:
                 return torch.ops.NNPOpsCFConv.operation_weights(self.holder, neighbors.holder, positions, input, self.weights1,

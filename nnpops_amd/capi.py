@@ -76,6 +76,8 @@ SIGNATURES = {
     "nnpops_cfconv_describe": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "nnpops_cfconv_backprop_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p]),
+    "nnpops_cfconv_double_backward_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_cfconv_set_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_split_planes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p, C.c_long]),
     "nnpops_rows_dot": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
@@ -961,6 +963,25 @@ class CFConv:
         _check(self._lib.nnpops_cfconv_set_stream(self._h, _stream_ptr(x.device)))
         _check(self._lib.nnpops_cfconv_backprop_weights(self._h, neighbors._h, _ptr(x), _ptr(out_grad), _ptr(w1_grad), _ptr(b1_grad),
                                                         _ptr(w2_grad), _ptr(b2_grad)))
+        return w1_grad, b1_grad, w2_grad, b2_grad
+
+    def double_backward_weights(self, neighbors, x, out_grad, gg_x=None, gg_pos=None):
+        """The weight gradients of what double_backward() differentiates: with cotangents ``gg_x`` (N, W) and ``gg_pos`` (N, 3) of
+        backprop()'s two gradients (either may be None = zero, not both) -> the gradients of <gg_x, x_grad> + <gg_pos, pos_grad> with
+        respect to the four weight arrays, (w1_grad [width][num_gaussians], b1_grad, w2_grad [out][in], b2_grad), float32 on the
+        device, for the list's last build()."""
+        _dev_f32(x, "input", (self.num_atoms, self.width))
+        _dev_f32(out_grad, "output_grad", (self.num_atoms, self.width))
+        if gg_x is not None:
+            _dev_f32(gg_x, "gg_input_grad", (self.num_atoms, self.width))
+        if gg_pos is not None:
+            _dev_f32(gg_pos, "gg_position_grad", (self.num_atoms, 3))
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x.device)
+        w1_grad, b1_grad = new(self.width, self.num_gaussians), new(self.width)
+        w2_grad, b2_grad = new(self.width, self.width), new(self.width)
+        _check(self._lib.nnpops_cfconv_set_stream(self._h, _stream_ptr(x.device)))
+        _check(self._lib.nnpops_cfconv_double_backward_weights(self._h, neighbors._h, _ptr(x), _ptr(out_grad), _ptr(gg_x), _ptr(gg_pos),
+                                                               _ptr(w1_grad), _ptr(b1_grad), _ptr(w2_grad), _ptr(b2_grad)))
         return w1_grad, b1_grad, w2_grad, b2_grad
 
     def set_weights(self, w1, b1, w2, b2):

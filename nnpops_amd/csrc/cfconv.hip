@@ -36,6 +36,9 @@
 // nnpops_cfconv_backprop_weights returns the gradients of the filter network's four weight arrays: one pass over the pair slots that
 // writes a partial row per workgroup, and the float64 sum of the rows (cfconv_weight_grad.h); nnpops_cfconv_set_weights
 // gives a live handle new weights through plan_and_upload, the planning and upload block it shares with nnpops_cfconv_create.
+// nnpops_cfconv_double_backward_weights returns the gradients, in the same four arrays, of the scalar the double backward differentiates
+// (the weight gradients of a force loss): a short pass over the rows for the pair scalar a, then the same partial rows and float64 sum
+// (cfconv_weight_grad_second.h).
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -50,6 +53,7 @@
 #include "cfconv_filters.h"
 #include "cfconv_second_order.h"
 #include "cfconv_weight_grad.h"
+#include "cfconv_weight_grad_second.h"
 
 using namespace nnpops;
 
@@ -321,6 +325,9 @@ struct nnpops_cfconv {
     // [wgrad_blocks][W (W + G + 2)]
     float* d_wgrad_partials = nullptr;
     int wgrad_blocks = 0;
+    // nnpops_cfconv_double_backward_weights: a = u.(Q_j - Q_i) per pair slot (it shares the partial rows above)
+    float* d_pair_a = nullptr;
+    size_t pair_a_len = 0;
 };
 
 extern "C" {
@@ -653,7 +660,7 @@ int nnpops_cfconv_describe(nnpops_cfconv_t h, int32_t out[8]) {
 int nnpops_cfconv_destroy(nnpops_cfconv_t h) {
     if (!h) return NNPOPS_OK;
     DeviceGuard guard(h->device);
-    dev_free(h->d_w1t); dev_free(h->d_w2t); dev_free(h->d_b1); dev_free(h->d_b2); dev_free(h->d_w2); dev_free(h->d_wgrad_partials);
+    dev_free(h->d_w1t); dev_free(h->d_w2t); dev_free(h->d_b1); dev_free(h->d_b2); dev_free(h->d_w2); dev_free(h->d_wgrad_partials); dev_free(h->d_pair_a);
     dev_free(h->d_w1t_s); dev_free(h->d_w2t_s); dev_free(h->d_b1_s);
     dev_free(h->d_filt); dev_free(h->d_pair_s); dev_free(h->d_box_partials); dev_free(h->d_row_s);
     dev_free(h->d_w1b); dev_free(h->d_w2h); dev_free(h->d_w2l); dev_free(h->d_w1h); dev_free(h->d_w1l);
@@ -956,6 +963,17 @@ bool wgrad_takes_mfma(int W, int G) {
     return W % 16 == 0 && W <= 128 && wgrad_mfma_floats(W, G) * sizeof(float) <= (size_t)160 * 1024;
 }
 
+// the partial rows, shared by both weight-gradient entry points (first call of either: not capturable)
+int ensure_wgrad_partials(nnpops_cfconv* h) {
+    if (h->d_wgrad_partials) return NNPOPS_OK;
+    const size_t row_bytes = wgrad_row_floats(h->p.W, h->p.G) * sizeof(float);
+    const int blocks = (int)std::max<size_t>(1, std::min<size_t>((size_t)h->blocks, kWgradPartialBytes / row_bytes));
+    int rc;
+    if ((rc = dev_alloc(&h->d_wgrad_partials, (size_t)blocks * wgrad_row_floats(h->p.W, h->p.G)))) return rc;
+    h->wgrad_blocks = blocks;
+    return NNPOPS_OK;
+}
+
 template <int NCB>
 int launch_wgrad_mfma(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, const float* x, const float* g) {
     const size_t lds = wgrad_mfma_floats(h->p.W, h->p.G) * sizeof(float);
@@ -975,12 +993,7 @@ int launch_wgrad(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, const float* x, 
     nb->want_half = true;                                   // later builds carry the pair slots along (as launch_filters asks)
     int rc;
     if (!nb->half_built && (rc = launch_half_build(nb, h->stream)) != NNPOPS_OK) return rc;
-    if (!h->d_wgrad_partials) {                             // first call: not capturable
-        const size_t row_bytes = wgrad_row_floats(W, G) * sizeof(float);
-        const int blocks = (int)std::max<size_t>(1, std::min<size_t>((size_t)h->blocks, kWgradPartialBytes / row_bytes));
-        if ((rc = dev_alloc(&h->d_wgrad_partials, (size_t)blocks * wgrad_row_floats(W, G)))) return rc;
-        h->wgrad_blocks = blocks;
-    }
+    if ((rc = ensure_wgrad_partials(h)) != NNPOPS_OK) return rc;
     if (wgrad_takes_mfma(W, G)) {
         switch (W) {
             case 16:  rc = launch_wgrad_mfma<1>(h, nb, x, g); break;
@@ -999,6 +1012,70 @@ int launch_wgrad(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, const float* x, 
             NNPOPS_HIP_TRY(hipFuncSetAttribute((const void*)cfconv_wgrad_vector, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(cfconv_wgrad_vector, dim3(h->wgrad_blocks), dim3(kWgradVectorThreads), lds, h->stream, h->p, h->d_w1t, h->d_b1,
                            h->d_w2, nb->d_half_off, nb->d_half_r, nb->d_half_ij, nb->pair_cap(), x, g, h->d_wgrad_partials);
+    }
+    hipLaunchKernelGGL(cfconv_wgrad_finish, dim3(div_up((long long)wgrad_row_floats(W, G), 256)), dim3(256), 0, h->stream, W, G,
+                       h->wgrad_blocks, (const float*)h->d_wgrad_partials, dw1, db1, dw2, db2);
+    NNPOPS_HIP_TRY(hipGetLastError());
+    return NNPOPS_OK;
+}
+
+// The weight gradients of the double backward's scalar (cfconv_weight_grad_second.h): launch_wgrad's choice of family with the taller
+// LDS image, its partial rows and its finish.  Q given: cfconv_pair_a first fills a per pair slot from the full rows.
+bool wgrad2_takes_mfma(int W, int G) {
+    return W % 16 == 0 && W <= 128 && wgrad2_mfma_floats(W, G) * sizeof(float) <= (size_t)160 * 1024;
+}
+
+template <int NCB>
+int launch_wgrad2_mfma(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, const float* pair_a, const float* x, const float* g, const float* V) {
+    const size_t lds = wgrad2_mfma_floats(h->p.W, h->p.G) * sizeof(float);
+    auto launch = [&](auto k) {
+        if (lds > 64 * 1024)
+            NNPOPS_HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(k, dim3(h->wgrad_blocks), dim3(64 * NCB), lds, h->stream, h->p, h->d_w1t, h->d_b1, h->d_w2, nb->d_half_off,
+                           nb->d_half_r, nb->d_half_ij, nb->pair_cap(), pair_a, x, g, V, h->d_wgrad_partials);
+        return (int)NNPOPS_OK;
+    };
+    return wgrad_gamma_blocks(h->p.G) == 4 ? launch(cfconv_wgrad2_mfma<NCB, 4>) : launch(cfconv_wgrad2_mfma<NCB, 16>);
+}
+
+int launch_wgrad2(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, const float* x, const float* g, const float* V, const float* Q, float* dw1,
+                  float* db1, float* dw2, float* db2) {
+    const int W = h->p.W, G = h->p.G;
+    nb->want_half = true;                                   // later builds carry the pair slots along (as launch_filters asks)
+    int rc;
+    if (!nb->half_built && (rc = launch_half_build(nb, h->stream)) != NNPOPS_OK) return rc;
+    if ((rc = ensure_wgrad_partials(h)) != NNPOPS_OK) return rc;
+    const float* pair_a = nullptr;
+    if (Q) {
+        const size_t need = (size_t)nb->pair_cap() + 1;
+        if (h->pair_a_len < need) {                         // first call with Q, or the neighbour rows have grown: not capturable
+            dev_free(h->d_pair_a);
+            h->d_pair_a = nullptr; h->pair_a_len = 0;
+            if ((rc = dev_alloc(&h->d_pair_a, need))) return rc;
+            h->pair_a_len = need;
+        }
+        hipLaunchKernelGGL(cfconv_pair_a, dim3(div_up(nb->N, 4)), dim3(256), 0, h->stream, nb->N, (const float4*)nb->d_rows,
+                           (const int*)nb->d_cnt, nb->cap, (const int*)nb->d_pid, nb->pair_cap(), Q, h->d_pair_a);
+        pair_a = h->d_pair_a;
+    }
+    if (wgrad2_takes_mfma(W, G)) {
+        switch (W) {
+            case 16:  rc = launch_wgrad2_mfma<1>(h, nb, pair_a, x, g, V); break;
+            case 32:  rc = launch_wgrad2_mfma<2>(h, nb, pair_a, x, g, V); break;
+            case 48:  rc = launch_wgrad2_mfma<3>(h, nb, pair_a, x, g, V); break;
+            case 64:  rc = launch_wgrad2_mfma<4>(h, nb, pair_a, x, g, V); break;
+            case 80:  rc = launch_wgrad2_mfma<5>(h, nb, pair_a, x, g, V); break;
+            case 96:  rc = launch_wgrad2_mfma<6>(h, nb, pair_a, x, g, V); break;
+            case 112: rc = launch_wgrad2_mfma<7>(h, nb, pair_a, x, g, V); break;
+            default:  rc = launch_wgrad2_mfma<8>(h, nb, pair_a, x, g, V); break;
+        }
+        if (rc != NNPOPS_OK) return rc;
+    } else {
+        const size_t lds = wgrad2_vector_floats(W, G) * sizeof(float);
+        if (lds > 64 * 1024)
+            NNPOPS_HIP_TRY(hipFuncSetAttribute((const void*)cfconv_wgrad2_vector, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(cfconv_wgrad2_vector, dim3(h->wgrad_blocks), dim3(kWgradVectorThreads), lds, h->stream, h->p, h->d_w1t, h->d_b1,
+                           h->d_w2, nb->d_half_off, nb->d_half_r, nb->d_half_ij, nb->pair_cap(), pair_a, x, g, V, h->d_wgrad_partials);
     }
     hipLaunchKernelGGL(cfconv_wgrad_finish, dim3(div_up((long long)wgrad_row_floats(W, G), 256)), dim3(256), 0, h->stream, W, G,
                        h->wgrad_blocks, (const float*)h->d_wgrad_partials, dw1, db1, dw2, db2);
@@ -1082,6 +1159,17 @@ int nnpops_cfconv_backprop_weights(nnpops_cfconv_t h, nnpops_cfconv_neighbors_t 
     NNPOPS_REQUIRE(input && output_deriv && w1_deriv && b1_deriv && w2_deriv && b2_deriv, "NULL device pointer");
     DeviceGuard guard(h->device);
     return launch_wgrad(h, neighbors, input, output_deriv, w1_deriv, b1_deriv, w2_deriv, b2_deriv);
+}
+
+int nnpops_cfconv_double_backward_weights(nnpops_cfconv_t h, nnpops_cfconv_neighbors_t neighbors, const float* input,
+                                          const float* output_deriv, const float* gg_input_deriv, const float* gg_position_deriv,
+                                          float* w1_deriv, float* b1_deriv, float* w2_deriv, float* b2_deriv) {
+    int rc = check_pair(h, neighbors);
+    if (rc != NNPOPS_OK) return rc;
+    NNPOPS_REQUIRE(input && output_deriv && w1_deriv && b1_deriv && w2_deriv && b2_deriv, "NULL device pointer");
+    NNPOPS_REQUIRE(gg_input_deriv || gg_position_deriv, "gg_input_deriv and gg_position_deriv are both NULL: nothing to differentiate");
+    DeviceGuard guard(h->device);
+    return launch_wgrad2(h, neighbors, input, output_deriv, gg_input_deriv, gg_position_deriv, w1_deriv, b1_deriv, w2_deriv, b2_deriv);
 }
 
 int nnpops_cfconv_set_weights(nnpops_cfconv_t h, const float* w1, const float* b1, const float* w2, const float* b2) {

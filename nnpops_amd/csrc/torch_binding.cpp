@@ -10,6 +10,7 @@
 //   torch.classes.NNPOpsCFConv.Holder / torch.ops.NNPOpsCFConv.operation / operation_periodic (additive: dL/dbox)
 //   torch.ops.NNPOpsCFConv.operation_twice / operation_periodic_twice (additive: the same ops, twice differentiable)
 //   torch.ops.NNPOpsCFConv.operation_weights / operation_periodic_weights (additive: the same ops with trainable weights)
+//   torch.ops.NNPOpsCFConv.operation_weights_twice / operation_periodic_weights_twice (additive: trainable weights under a force loss)
 //                                                         (reference src/pytorch/CFConv.cpp:276-291)
 //   torch.ops.neighbors.getNeighborPairs                  (reference src/pytorch/neighbors/neighbors.cpp:4)
 //   torch.ops.NNPOpsBatchedNN.BatchedLinear               (reference src/pytorch/BatchedNN.cpp:48-50)
@@ -1195,6 +1196,42 @@ public:
         return {g1, gb1, g2, gb2};
     }
 
+    // The force-trainable ops (operation_weights_twice / operation_periodic_weights_twice) keep their tensors in their own autograd
+    // contexts: the weight gradients on what the caller hands over (the routine and the bits of backwardWeights()) ...
+    tensor_list backwardWeightsOf(const NeighborsPtr& nb, const Tensor& input_, const Tensor& outputGrad_) {
+        if (!impl) throw std::runtime_error("backward() called before forward()");
+        const Tensor in = input_.detach().contiguous(), outputGrad = outputGrad_.detach().contiguous();
+        const auto opts = torch::TensorOptions().device(device).dtype(torch::kFloat32);
+        Tensor g1 = torch::empty(weights1.sizes(), opts), gb1 = torch::empty({numFilters}, opts);
+        Tensor g2 = torch::empty({numFilters, numFilters}, opts), gb2 = torch::empty({numFilters}, opts);
+        nnpops_cfconv_set_stream(impl, current_stream(device));
+        if (nnpops_cfconv_backprop_weights(impl, nb->getImpl(), in.data_ptr<float>(), outputGrad.data_ptr<float>(), g1.data_ptr<float>(),
+                                           gb1.data_ptr<float>(), g2.data_ptr<float>(), gb2.data_ptr<float>()) != NNPOPS_OK)
+            raise_last("NNPOpsCFConv::operation_weights_twice (backward)");
+        return {g1, gb1, g2, gb2};
+    }
+
+    // ... and the weight gradients of what doubleBackward() differentiates (nnpops_cfconv_double_backward_weights), weights1 in the
+    // module's convention as above
+    tensor_list doubleBackwardWeights(const NeighborsPtr& nb, const Tensor& input_, const Tensor& outputGrad_, const Tensor& ggInput_,
+                                      const Tensor& ggPositions_) {
+        if (!impl) throw std::runtime_error("backward() called before forward()");
+        const Tensor in = input_.detach().contiguous(), outputGrad = outputGrad_.detach().contiguous();
+        Tensor ggInput, ggPositions;
+        if (ggInput_.defined()) ggInput = ggInput_.detach().to(torch::kFloat32).contiguous();
+        if (ggPositions_.defined()) ggPositions = ggPositions_.detach().to(torch::kFloat32).contiguous();
+        const auto opts = torch::TensorOptions().device(device).dtype(torch::kFloat32);
+        Tensor g1 = torch::empty(weights1.sizes(), opts), gb1 = torch::empty({numFilters}, opts);
+        Tensor g2 = torch::empty({numFilters, numFilters}, opts), gb2 = torch::empty({numFilters}, opts);
+        nnpops_cfconv_set_stream(impl, current_stream(device));
+        if (nnpops_cfconv_double_backward_weights(impl, nb->getImpl(), in.data_ptr<float>(), outputGrad.data_ptr<float>(),
+                                                  ggInput.defined() ? ggInput.data_ptr<float>() : nullptr,
+                                                  ggPositions.defined() ? ggPositions.data_ptr<float>() : nullptr, g1.data_ptr<float>(),
+                                                  gb1.data_ptr<float>(), g2.data_ptr<float>(), gb2.data_ptr<float>()) != NNPOPS_OK)
+            raise_last("NNPOpsCFConv::operation_weights_twice (double backward)");
+        return {g1, gb1, g2, gb2};
+    }
+
     static std::string serialize(const HolderPtr& self) {
         torch::serialize::OutputArchive archive;
         archive.write("gaussianWidth", self->gaussianWidth);
@@ -1453,6 +1490,145 @@ Tensor operation_periodic_weights(const c10::optional<HolderPtr>& holder, const 
                                         weight_wants(weights1, biases1, weights2, biases2) | box_wants);
 }
 
+// ---------------------------------------------------------------------------------------------
+// operation_weights_twice / operation_periodic_weights_twice: trainable filters under a force loss.  The forward pass is
+// that of operation_weights (Holder::syncWeights, then the default forward); the first backward is a recorded node, so that
+// torch.autograd.grad(E, positions, create_graph=True) can be differentiated once more, with respect to the weights as well:
+//     CFConvForceBackwardFunction         (g, positions, input, four weights) -> (gx, gp, the wanted weight gradients): nnpops_cfconv_backprop
+//                                         and, only where the engine asks for a weight gradient, nnpops_cfconv_backprop_weights
+//     CFConvForceDoubleBackwardFunction   (V, Q, g, positions, input) -> (dM/dg, dM/dx, dM/dpositions, the wanted weight gradients):
+//                                         nnpops_cfconv_double_backward and nnpops_cfconv_double_backward_weights
+// Every node records the list's build count and the holder's upload count of the forward pass and raises on another.  Refused: third
+// derivatives, a cotangent for the first-order weight gradients (weight-weight second derivatives), a box that requires a gradient.
+// ---------------------------------------------------------------------------------------------
+inline void check_same_state(const HolderPtr& holder, const NeighborsPtr& nb, int64_t build, int64_t uploads) {
+    TORCH_CHECK(nb->getBuildCount() == build, "NNPOpsCFConv::operation_weights_twice: \"neighbors\" has been rebuilt since the forward pass; "
+                "its rows no longer belong to the positions this gradient is taken at (build the list, run the forward pass and "
+                "differentiate before building it again)");
+    TORCH_CHECK(holder->getUploads() == uploads, "NNPOpsCFConv::operation_weights_twice: the weights have been uploaded again since the "
+                "forward pass (an optimizer step or another forward pass with new values); this gradient would be taken at other "
+                "weights than the output it belongs to (differentiate before the weights change)");
+}
+
+// a weight gradient where its weight lives (a parameter kept on the CPU receives a CPU gradient, as in operation_weights)
+inline Tensor weight_grad_for(const Tensor& grad, const Tensor& weight) { return weight.is_cpu() ? grad.cpu() : grad; }
+
+class CFConvForceDoubleBackwardFunction : public torch::autograd::Function<CFConvForceDoubleBackwardFunction> {
+public:
+    // wants: bit k = weight k takes a gradient
+    static tensor_list forward(AutogradContext*, const c10::optional<Tensor>& ggInput, const c10::optional<Tensor>& ggPositions, const Tensor& g,
+                               const Tensor& positions, const Tensor& input, const HolderPtr& holder, const c10::IValue& neighbors,
+                               int64_t build, int64_t uploads, int64_t wants) {
+        const NeighborsPtr nb = neighbors.toCustomClass<Neighbors>();
+        check_same_state(holder, nb, build, uploads);
+        const Tensor V = ggInput ? *ggInput : Tensor(), Q = ggPositions ? *ggPositions : Tensor();
+        tensor_list out = holder->doubleBackward(nb, positions, input, g, V, Q);
+        if (wants & 15) {                                    // (a recorded node has no undefined outputs: the wanted ones only, in order)
+            const tensor_list w = holder->doubleBackwardWeights(nb, input, g, V, Q);
+            for (int k = 0; k < 4; k++)
+                if (wants >> k & 1) out.push_back(w[k]);
+        }
+        return out;
+    }
+    static tensor_list backward(AutogradContext*, tensor_list) {
+        TORCH_CHECK(false, "NNPOpsCFConv::operation_weights_twice: third derivatives are not implemented");
+        return {};
+    }
+};
+
+class CFConvForceBackwardFunction : public torch::autograd::Function<CFConvForceBackwardFunction> {
+public:
+    static tensor_list forward(AutogradContext* ctx, const Tensor& g, const Tensor& positions, const Tensor& input, const Tensor& weights1,
+                               const Tensor& biases1, const Tensor& weights2, const Tensor& biases2, const HolderPtr& holder,
+                               const c10::IValue& neighbors, int64_t build, int64_t uploads, int64_t wants) {
+        const NeighborsPtr nb = neighbors.toCustomClass<Neighbors>();
+        check_same_state(holder, nb, build, uploads);
+        ctx->set_materialize_grads(false);
+        ctx->save_for_backward({g, positions, input, weights1, biases1, weights2, biases2});
+        ctx->saved_data["holder"] = holder;
+        ctx->saved_data["neighbors"] = neighbors;
+        ctx->saved_data["build"] = build;
+        ctx->saved_data["uploads"] = uploads;
+        tensor_list out = holder->backwardOf(nb, positions, input, g);
+        if (wants & 15) {                                    // (a recorded node has no undefined outputs: the wanted ones only, in order)
+            const tensor_list w = holder->backwardWeightsOf(nb, input, g);
+            for (int k = 0; k < 4; k++)
+                if (wants >> k & 1) out.push_back(w[k]);
+        }
+        return out;
+    }
+    static tensor_list backward(AutogradContext* ctx, tensor_list grads) {
+        for (size_t k = 2; k < grads.size(); k++)
+            TORCH_CHECK(!grads[k].defined(), "NNPOpsCFConv::operation_weights_twice: second derivatives of the weight gradients themselves "
+                        "(weight-weight second derivatives: a cotangent arrived for the gradient of a weight) are not implemented; the "
+                        "second derivatives of this op are those of the gradients with respect to positions and input");
+        tensor_list none(12);
+        if (!grads[0].defined() && !grads[1].defined()) return none;
+        const auto s = ctx->get_saved_variables();
+        int64_t wants = 0;
+        for (int k = 0; k < 4; k++) wants |= ctx->needs_input_grad(3 + k) ? (int64_t)1 << k : 0;
+        const auto given = [](const Tensor& t) { return t.defined() ? c10::optional<Tensor>(t) : c10::optional<Tensor>(); };
+        const tensor_list d = CFConvForceDoubleBackwardFunction::apply(given(grads[0]), given(grads[1]), s[0], s[1], s[2],
+                                                                       ctx->saved_data["holder"].toCustomClass<Holder>(),
+                                                                       ctx->saved_data["neighbors"], ctx->saved_data["build"].toInt(),
+                                                                       ctx->saved_data["uploads"].toInt(), wants);
+        tensor_list out = {d[0], d[2], d[1]};
+        size_t next = 3;
+        for (int k = 0; k < 4; k++) out.push_back(wants >> k & 1 ? weight_grad_for(d[next++], s[3 + k]) : Tensor());
+        out.resize(12);
+        return out;
+    }
+};
+
+// (periodic: the box is an input only so that the op has operation_periodic_weights' schema; its slot stays empty)
+class CFConvForceFunction : public torch::autograd::Function<CFConvForceFunction> {
+public:
+    static Tensor forward(AutogradContext* ctx, const HolderPtr& holder, const c10::IValue& neighbors, const Tensor& positions,
+                          const c10::optional<Tensor>& box, const Tensor& input, const Tensor& weights1, const Tensor& biases1,
+                          const Tensor& weights2, const Tensor& biases2) {
+        holder->syncWeights(weights1, biases1, weights2, biases2);
+        const Tensor output = box ? holder->forwardPeriodic(neighbors, positions, *box, input) : holder->forward(neighbors, positions, input);
+        ctx->save_for_backward({positions, input, weights1, biases1, weights2, biases2});
+        ctx->saved_data["holder"] = holder;
+        ctx->saved_data["neighbors"] = neighbors;
+        ctx->saved_data["build"] = neighbors.toCustomClass<Neighbors>()->getBuildCount();
+        ctx->saved_data["uploads"] = holder->getUploads();
+        ctx->saved_data["periodic"] = box.has_value();
+        return output;
+    }
+    static tensor_list backward(AutogradContext* ctx, tensor_list grads) {
+        const auto s = ctx->get_saved_variables();
+        // (the node's edges count its tensor inputs only: positions, the box where there is one, input, four weights)
+        const size_t first_weight = ctx->saved_data["periodic"].toBool() ? 3 : 2;
+        int64_t wants = 0;
+        for (int k = 0; k < 4; k++) wants |= ctx->needs_input_grad(first_weight + k) ? (int64_t)1 << k : 0;
+        const tensor_list d = CFConvForceBackwardFunction::apply(grads[0], s[0], s[1], s[2], s[3], s[4], s[5],
+                                                                 ctx->saved_data["holder"].toCustomClass<Holder>(),
+                                                                 ctx->saved_data["neighbors"], ctx->saved_data["build"].toInt(),
+                                                                 ctx->saved_data["uploads"].toInt(), wants);
+        tensor_list out = {Tensor(), Tensor(), d[1], Tensor(), d[0]};
+        size_t next = 2;
+        for (int k = 0; k < 4; k++) out.push_back(wants >> k & 1 ? weight_grad_for(d[next++], s[2 + k]) : Tensor());
+        return out;
+    }
+};
+
+Tensor operation_weights_twice(const c10::optional<HolderPtr>& holder, const c10::IValue& neighbors, const Tensor& positions,
+                               const Tensor& input, const Tensor& weights1, const Tensor& biases1, const Tensor& weights2,
+                               const Tensor& biases2) {
+    return CFConvForceFunction::apply(*holder, neighbors, positions, c10::optional<Tensor>(), input, weights1, biases1, weights2, biases2);
+}
+
+Tensor operation_periodic_weights_twice(const c10::optional<HolderPtr>& holder, const c10::IValue& neighbors, const Tensor& positions,
+                                        const Tensor& box, const Tensor& input, const Tensor& weights1, const Tensor& biases1,
+                                        const Tensor& weights2, const Tensor& biases2) {
+    TORCH_CHECK(box.defined(), "NNPOpsCFConv::operation_periodic_weights_twice: \"box\" is undefined");
+    TORCH_CHECK(!(torch::GradMode::is_enabled() && box.requires_grad()),
+                "NNPOpsCFConv::operation_periodic_weights_twice: box gradients need the default op or operation_periodic_weights (CFConv "
+                "without force_trainable=True): the twice-differentiable ops return no box gradient");
+    return CFConvForceFunction::apply(*holder, neighbors, positions, c10::optional<Tensor>(box), input, weights1, biases1, weights2, biases2);
+}
+
 TORCH_LIBRARY(NNPOpsCFConv, m) {
     m.class_<Holder>("Holder")
         .def(torch::init<double, const std::string&, const Tensor&, const Tensor&, const Tensor&, const Tensor&>())
@@ -1467,6 +1643,8 @@ TORCH_LIBRARY(NNPOpsCFConv, m) {
     m.def("operation_periodic_twice", operation_periodic_twice);
     m.def("operation_weights", operation_weights);
     m.def("operation_periodic_weights", operation_periodic_weights);
+    m.def("operation_weights_twice", operation_weights_twice);
+    m.def("operation_periodic_weights_twice", operation_periodic_weights_twice);
 }
 
 }  // namespace CFConv

@@ -1,0 +1,429 @@
+"""The weight gradients of a CFConv force loss (nnpops_cfconv_double_backward_weights, the two `_weights_twice` ops and
+CFConv(..., force_trainable=True)) on the GPU, against float64.
+
+The judge, its closed form, the float32 witness and the table of cases are in tests/cfconv_force_weights_float64.py;
+tests/test_cfconv_force_weights_reference_cpu.py pins them without a GPU and shows that the witness sits inside half of the bar on every
+case.
+
+BAR: each of the four gradients within FORCE_RTOL = 1e-4 (cfconv_float64.py) of the judge, as a fraction of that gradient's largest
+entry -- the project's bar for CFConv gradients, widened for no case.  Every judged case prints its four errors and the witness's on
+the same case (pytest -s).  Measured on an MI355X (docs/LAB_NOTEBOOK_cfconv_force_weights.md has the table): the worst error over the
+table is 4.3e-6 of the largest entry (liquid1500_w32_g16-ssp, b2), 0.043 of the bar; away from the periodic frame it stays below
+2.6e-6, the witness's own size.  66 tests, 6 s.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import cfconv_force_weights_float64 as ff
+from box_gradient_judge import clean_env
+from cfconv_float64 import sigma_of
+from nnpops_amd import capi, workloads
+
+wf = ff.wf
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+def _env(monkeypatch):
+    clean_env(monkeypatch, "NNPOPS_CFCONV_")
+
+
+def _dev(a):
+    return None if a is None else torch.tensor(a, device=DEV)
+
+
+def _handles(case):
+    pos, box, cutoff, weights, x, g, V, Q = ff.inputs(case)
+    periodic = box is not None
+    nb = capi.CFConvNeighbors(len(pos), cutoff, periodic)
+    cf = capi.CFConv(len(pos), case.W, case.G, cutoff, sigma_of(case.G), case.act, *weights, periodic=periodic)
+    tpos, tbox = _dev(pos), _dev(box)
+    nb.build(tpos, tbox)
+    return nb, cf, tpos, tbox, _dev(x), _dev(g), _dev(V), _dev(Q)
+
+
+def _numpy(grads):
+    return {n: t.cpu().numpy() for n, t in zip(ff.NAMES, grads)}
+
+
+def _case(name):
+    return next(c for c in ff.CASES if c.name == name)
+
+
+# ---------------------------------------------------------------------------------------------- every case of the table
+@pytest.mark.parametrize("case", ff.CASES, ids=[c.name for c in ff.CASES])
+def test_weight_gradients_against_float64(monkeypatch, case):
+    _env(monkeypatch)
+    ref = ff.reference(case)
+    nb, cf, tpos, tbox, tx, tg, tV, tQ = _handles(case)
+    assert ff.expected_kernel(case.W, case.G) == case.kernel
+    assert nb.num_pairs() == len(ref["i"])
+    first = cf.double_backward_weights(nb, tx, tg, tV, tQ)
+    second = cf.double_backward_weights(nb, tx, tg, tV, tQ)
+    torch.cuda.synchronize()
+    got = _numpy(first)
+    for n, a, b in zip(ff.NAMES, first, second):
+        assert torch.equal(a, b), n                                     # two calls agree bit for bit
+        assert np.all(np.isfinite(got[n])), n
+    err, wit = ff.errors(got, ref["judge"]), ff.errors(ref["witness"], ref["judge"])
+    print(f"\n{case.name} [{case.kernel}, {case.cot}] pairs {len(ref['i'])}: {ff.figures(err)} | witness {ff.figures(wit)}")
+    if len(ref["i"]) == 0:
+        for n in ff.NAMES:
+            assert not np.any(got[n]), n                                # no pair: exact zeros
+    for n in ff.NAMES:
+        assert err[n] <= ff.BAR, (n, err[n])
+
+
+def test_batched_molecules_sum_the_molecules_own_gradients(monkeypatch):
+    """three molecules whose coordinates overlap behind one list: the gradients are the sum of the molecules' own"""
+    _env(monkeypatch)
+    sizes = (30, 17, 25)
+    pos = np.concatenate([workloads.conformer(n, seed=20 + k)[0] for k, n in enumerate(sizes)]).astype(np.float32)
+    offsets = [0, 30, 47, 72]
+    for W, G, act in ((16, 8, "ssp"), (24, 10, "tanh")):
+        w1, b1, w2, b2, x, g = wf.cfconv_float64.weights(W, G, len(pos), 7000 + W)
+        V, Q = wf.cfconv_float64.cotangents(len(pos), W, 7100 + W)
+        J = ff.judge_of(W, G, 5.0, act, w1, b1, w2, b2)
+        i, j, d = ff.pair_displacements(J, pos, offsets=offsets)
+        assert len(ff.pair_displacements(J, pos)[0]) > len(i)           # (the molecules do overlap: one list of all atoms has more pairs)
+        ref = ff.judge(J, i, j, d, x, g, V, Q)
+        nb = capi.CFConvNeighbors(len(pos), 5.0, False)
+        nb.set_molecules(offsets)
+        cf = capi.CFConv(len(pos), W, G, 5.0, sigma_of(G), act, w1, b1, w2, b2)
+        nb.build(_dev(pos))
+        assert nb.num_pairs() == len(i)
+        got = _numpy(cf.double_backward_weights(nb, _dev(x), _dev(g), _dev(V), _dev(Q)))
+        err = ff.errors(got, ref)
+        print(f"\nbatched W={W} G={G}: {ff.figures(err)}")
+        assert max(err.values()) <= ff.BAR, err
+
+
+# ---------------------------------------------------------------------------------------------- exact cases
+@pytest.mark.parametrize("name", ["w64_g50-ssp", "w24_g10-tanh", "liquid1500_w32_g16-ssp"])
+def test_a_rigid_translation_in_Q_gives_the_bits_of_no_Q_and_alone_exact_zeros(monkeypatch, name):
+    _env(monkeypatch)
+    nb, cf, tpos, tbox, tx, tg, tV, tQ = _handles(_case(name))
+    rigid = torch.tensor([0.75, -1.25, 3.5], device=DEV).repeat(len(tpos), 1)      # Q_j - Q_i = 0 for every pair: a = 0 exactly
+    without = cf.double_backward_weights(nb, tx, tg, tV, None)
+    with_rigid = cf.double_backward_weights(nb, tx, tg, tV, rigid)
+    alone = cf.double_backward_weights(nb, tx, tg, None, rigid)
+    for n, a, b, z in zip(ff.NAMES, without, with_rigid, alone):
+        assert torch.equal(a, b), n
+        assert bool(a.any()), n
+        assert not bool(z.any()), n
+
+
+@pytest.mark.parametrize("name", ["w64_g50-ssp", "w24_g10-tanh"])
+def test_without_Q_the_result_is_the_first_order_weight_gradient_with_V_for_the_input(monkeypatch, name):
+    """... to the bar (another kernel evaluates the same sums)"""
+    _env(monkeypatch)
+    nb, cf, tpos, tbox, tx, tg, tV, tQ = _handles(_case(name))
+    got = _numpy(cf.double_backward_weights(nb, tx, tg, tV, None))
+    first = _numpy(cf.backprop_weights(nb, tV, tg))
+    err = ff.errors(got, {n: v.astype(np.float64) for n, v in first.items()})
+    assert max(err.values()) <= ff.BAR, err
+
+
+@pytest.mark.parametrize("name", ["w64_g50-ssp", "w16_g8-tanh", "w136_g10-tanh", "liquid1500_w24_g10-tanh"])
+def test_the_other_entry_points_keep_their_bits_around_the_call(monkeypatch, name):
+    _env(monkeypatch)
+    nb, cf, tpos, tbox, tx, tg, tV, tQ = _handles(_case(name))
+
+    def everything():
+        out = cf.compute(nb, tpos, tx, tbox)
+        gx, gp = cf.backprop(nb, tpos, tx, tg, tbox)
+        return [out, gx, gp, *cf.backprop_weights(nb, tx, tg), *cf.double_backward(nb, tpos, tx, tg, tV, tQ)]
+
+    before = everything()
+    mine = cf.double_backward_weights(nb, tx, tg, tV, tQ)
+    after = everything()
+    again = cf.double_backward_weights(nb, tx, tg, tV, tQ)
+    for k, (a, b) in enumerate(zip(before, after)):
+        assert torch.equal(a, b), k
+    for a, b in zip(mine, again):
+        assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("name", ["w48_g7-ssp", "w8_g10-tanh"])
+def test_sentinels_behind_the_four_outputs_survive(monkeypatch, name):
+    _env(monkeypatch)
+    case = _case(name)
+    nb, cf, tpos, tbox, tx, tg, tV, tQ = _handles(case)
+    W, G, pad = case.W, case.G, 64
+    sizes = [W * G, W, W * W, W]
+    buf = torch.full((sum(sizes) + pad * 5,), 12345.0, device=DEV)
+    starts = np.cumsum([pad] + [s + pad for s in sizes[:-1]])
+    ptrs = [C.c_void_p(buf.data_ptr() + 4 * int(s)) for s in starts]
+    p = lambda t: C.c_void_p(t.data_ptr())
+    assert capi.lib().nnpops_cfconv_double_backward_weights(cf._h, nb._h, p(tx), p(tg), p(tV), p(tQ), *ptrs) == 0
+    host = buf.cpu().numpy()
+    want = _numpy(cf.double_backward_weights(nb, tx, tg, tV, tQ))
+    inside = np.zeros(len(host), bool)
+    for n, s, size in zip(ff.NAMES, starts, sizes):
+        inside[s:s + size] = True
+        assert np.array_equal(host[s:s + size], want[n].reshape(-1)), n       # fully overwritten, the same bits
+    assert np.all(host[~inside] == 12345.0)
+
+
+def test_errors_are_reported_with_a_message(monkeypatch):
+    _env(monkeypatch)
+    nb, cf, tpos, tbox, tx, tg, tV, tQ = _handles(_case("w16_g8-ssp"))
+    L = capi.lib()
+    out = [torch.empty(n, device=DEV) for n in (16 * 8, 16, 256, 16)]
+    p = lambda t: C.c_void_p(t.data_ptr())
+    f = L.nnpops_cfconv_double_backward_weights
+    assert f(cf._h, nb._h, p(tx), p(tg), None, None, *map(p, out)) < 0
+    assert b"both NULL" in L.nnpops_last_error()
+    assert f(cf._h, nb._h, p(tx), p(tg), p(tV), p(tQ), p(out[0]), None, p(out[2]), p(out[3])) < 0
+    assert b"NULL" in L.nnpops_last_error()
+    assert f(cf._h, nb._h, None, p(tg), p(tV), p(tQ), *map(p, out)) < 0
+    assert b"NULL" in L.nnpops_last_error()
+    unbuilt = capi.CFConvNeighbors(len(tpos), 5.0, False)
+    assert f(cf._h, unbuilt._h, p(tx), p(tg), p(tV), p(tQ), *map(p, out)) < 0
+    assert b"not been built" in L.nnpops_last_error()
+    with pytest.raises(Exception):
+        cf.double_backward_weights(nb, tx, tg, None, None)
+
+
+# ---------------------------------------------------------------------------------------------- the torch surface
+def _module(W, G, act, weights, **kw):
+    from NNPOps.CFConv import CFConv
+    w1, b1, w2, b2 = (torch.tensor(w) for w in weights)
+    return CFConv(sigma_of(G), act, w1.reshape(G, W), b1, w2, b2, **kw)      # weights1: the core's [W][G] buffer seen as [G, W]
+
+
+def _neighbors(pos, box, cutoff):
+    from NNPOps.CFConvNeighbors import CFConvNeighbors
+    nb = CFConvNeighbors(cutoff)
+    nb.build(pos, box)
+    return nb
+
+
+def _leaf(a):
+    return torch.tensor(a, device=DEV, requires_grad=True)
+
+
+def _param_grads(conv, W, G):
+    return dict(w1=conv.weights1.grad.cpu().numpy().reshape(W, G), b1=conv.biases1.grad.cpu().numpy(),
+                w2=conv.weights2.grad.cpu().numpy(), b2=conv.biases2.grad.cpu().numpy())
+
+
+@pytest.mark.parametrize("periodic", [False, True], ids=["open", "periodic"])
+def test_first_order_results_are_the_trainable_modules_bits(monkeypatch, periodic):
+    _env(monkeypatch)
+    W, G, act = 32, 16, "ssp"
+    if periodic:
+        pos, box = wf.cfconv_float64.frame("cubic100")
+        cutoff = 4.5
+    else:
+        pos, box, cutoff = wf.frame("conformer90")
+    w1, b1, w2, b2, x, g = wf.cfconv_float64.weights(W, G, len(pos), 555)
+    results = []
+    for kw in (dict(force_trainable=True), dict(trainable=True)):
+        conv = _module(W, G, act, (w1, b1, w2, b2), **kw).to(DEV)
+        tpos, tx = _leaf(pos), _leaf(x)
+        tbox = _dev(box)                                                 # (passed, and not requiring a gradient)
+        nb = _neighbors(tpos.detach(), tbox, cutoff)
+        out = conv(nb, tpos, tx, tbox)
+        (out * _dev(g)).sum().backward()
+        results.append([out.detach(), tpos.grad, tx.grad, *(p.grad for p in conv.parameters())])
+        assert conv.weights1.grad.shape == (G, W) and conv.holder.uploads() == 1
+    for k, (a, b) in enumerate(zip(*results)):
+        assert torch.equal(a, b), k
+
+
+def test_second_derivatives_in_positions_and_input_are_the_twice_differentiable_modules_bits(monkeypatch):
+    _env(monkeypatch)
+    W, G, act = 32, 16, "tanh"
+    pos, box, cutoff = wf.frame("conformer90")
+    w1, b1, w2, b2, x, g = wf.cfconv_float64.weights(W, G, len(pos), 556)
+    V, Q = wf.cfconv_float64.cotangents(len(pos), W, 557)
+    results = []
+    for kw in (dict(force_trainable=True), dict(twice_differentiable=True)):
+        conv = _module(W, G, act, (w1, b1, w2, b2), **kw).to(DEV)
+        tpos, tx, tg = _leaf(pos), _leaf(x), _leaf(g)
+        nb = _neighbors(tpos.detach(), None, cutoff)
+        out = conv(nb, tpos, tx)
+        gx, gp = torch.autograd.grad((out * tg).sum(), [tx, tpos], create_graph=True)
+        M = (gx * _dev(V)).sum() + (gp * _dev(Q)).sum()
+        results.append([out.detach(), gx.detach(), gp.detach(), *torch.autograd.grad(M, [tg, tx, tpos])])
+    for k, (a, b) in enumerate(zip(*results)):
+        assert torch.equal(a, b), k
+
+
+def _stack_inputs(W, G, n):
+    la = wf.cfconv_float64.weights(W, G, n, 811)
+    lb = wf.cfconv_float64.weights(W, G, n, 812)
+    return la, lb, la[4], 0.1 * lb[5]
+
+
+def _targets(J, start, i, j, pos, x, readout, shift=None):
+    """E0, F0: half of the energy and of the forces at the start (float32 values)"""
+    _, E, F = ff.force_loss(J, start, i, j, pos, x, readout, 0.0, np.zeros((len(pos), 3), np.float32), shift)
+    return float(np.float32(0.5 * float(E.detach()))), (0.5 * F.detach().numpy()).astype(np.float32)
+
+
+def _gpu_loss(convs, nb, tpos, tx, treadout, E0, tF0, tbox=None):
+    h = tx
+    for conv in convs:
+        h = conv(nb, tpos, h, tbox)
+    E = (h * treadout).sum()
+    F = -torch.autograd.grad(E, tpos, create_graph=True)[0]
+    return (E - E0) ** 2 + ((F - tF0) ** 2).sum()
+
+
+@pytest.mark.parametrize("periodic", [False, True], ids=["open_two_layers", "periodic_one_layer"])
+def test_parameter_gradients_of_a_force_loss(monkeypatch, periodic):
+    """(E - E0)^2 + |F - F0|^2 with F = -autograd.grad(E, pos, create_graph=True): every parameter gradient against float64 autograd"""
+    _env(monkeypatch)
+    W, G, act = 16, 8, "tanh"
+    if periodic:
+        pos, box = wf.cfconv_float64.frame("cubic100")
+        cutoff, layers = 4.5, 1
+    else:
+        (pos, box, cutoff), layers = wf.frame("conformer90"), 2
+    la, lb, x, readout = _stack_inputs(W, G, len(pos))
+    J = ff.judge_of(W, G, cutoff, act, *la[:4])
+    i, j, d = ff.pair_displacements(J, pos, box)
+    p64 = np.asarray(pos, np.float32).astype(np.float64)
+    shift = d - (p64[j] - p64[i]) if periodic else None
+    start = [wf._wide(w) for w in (*la[:4], *lb[:4])][:4 * layers]
+    E0, F0 = _targets(J, start, i, j, pos, x, readout, shift)
+    params = [p.clone().requires_grad_(True) for p in start]
+    ref = torch.autograd.grad(ff.force_loss(J, params, i, j, pos, x, readout, E0, F0, shift)[0], params)
+
+    convs = [_module(W, G, act, w[:4], force_trainable=True).to(DEV) for w in (la, lb)[:layers]]
+    tpos = _leaf(pos)
+    tbox = _dev(box)
+    nb = _neighbors(tpos.detach(), tbox, cutoff)
+    loss = _gpu_loss(convs, nb, tpos, _dev(x), _dev(readout), E0, _dev(F0), tbox)
+    loss.backward()
+    for k, conv in enumerate(convs):
+        want = {n: v.numpy() for n, v in zip(ff.NAMES, ref[4 * k:4 * k + 4])}
+        err = ff.errors(_param_grads(conv, W, G), want)
+        print(f"\nforce loss, periodic={periodic}, layer {k}: {ff.figures(err)}")
+        assert max(err.values()) <= ff.BAR, (k, err)
+    assert tpos.grad is not None and bool(torch.isfinite(tpos.grad).all())
+
+
+def test_three_sgd_steps_on_a_force_loss(monkeypatch):
+    """... lower the float64-judged loss and match the same three steps taken in the judge; the upload counter moves once per step"""
+    _env(monkeypatch)
+    W, G, act, lr = 16, 8, "tanh", 1e-5          # (the judge descends 174.0 -> 71.7 -> 57.6 -> 53.4 at this rate; updates ~1e-2)
+    pos, box, cutoff = wf.frame("conformer90")
+    la, lb, x, readout = _stack_inputs(W, G, len(pos))
+    J = ff.judge_of(W, G, cutoff, act, *la[:4])
+    i, j, d = ff.pair_displacements(J, pos)
+    start = [wf._wide(w) for w in (*la[:4], *lb[:4])]
+    E0, F0 = _targets(J, start, i, j, pos, x, readout)
+    judged = lambda ps: ff.force_loss(J, ps, i, j, pos, x, readout, E0, F0)[0]
+    params = [p.clone().requires_grad_(True) for p in start]
+    losses = []
+    for _ in range(3):
+        L = judged(params)
+        losses.append(float(L.detach()))
+        grads = torch.autograd.grad(L, params)
+        params = [(p - lr * gr).detach().requires_grad_(True) for p, gr in zip(params, grads)]
+    losses.append(float(judged(params).detach()))
+    assert losses[3] < losses[2] < losses[1] < losses[0], losses
+
+    convs = [_module(W, G, act, w[:4], force_trainable=True).to(DEV) for w in (la, lb)]
+    tx, treadout, tF0 = _dev(x), _dev(readout), _dev(F0)
+    nb = _neighbors(_dev(pos), None, cutoff)
+    opt = torch.optim.SGD([p for c in convs for p in c.parameters()], lr=lr)
+    assert len(opt.param_groups[0]["params"]) == 8
+    for step in range(3):
+        opt.zero_grad()
+        loss = _gpu_loss(convs, nb, _leaf(pos), tx, treadout, E0, tF0)
+        assert all(c.holder.uploads() == step + 1 for c in convs)
+        loss.backward()
+        assert all(c.holder.uploads() == step + 1 for c in convs)          # (the derivatives upload nothing)
+        opt.step()
+    mine = [p.detach().cpu().numpy().astype(np.float64) for c in convs for p in c.parameters()]
+    at_mine = [torch.tensor(m.reshape(s.shape)) for m, s in zip(mine, start)]
+    assert float(judged(at_mine).detach()) < losses[0]
+    assert abs(float(judged(at_mine).detach()) - losses[3]) <= ff.BAR * losses[0]
+    for k, (m, p, s) in enumerate(zip(mine, params, start)):
+        step_ref = (p.detach() - s).numpy()
+        step_got = m.reshape(step_ref.shape) - s.numpy()
+        # (bar on the update, plus the rounding of three float32 parameter updates: 3 x 2^-24 of the largest weight)
+        bound = ff.BAR * np.abs(step_ref).max() + 3 * 2.0 ** -24 * np.abs(s.numpy()).max()
+        assert np.abs(step_got - step_ref).max() <= bound, (k, np.abs(step_got - step_ref).max(), bound)
+
+
+def test_a_force_evaluation_alone_leaves_the_parameters_alone_and_its_loss_reaches_all_four(monkeypatch):
+    """torch.autograd.grad(E, positions, create_graph=True) records the first backward and gives no parameter a gradient"""
+    _env(monkeypatch)
+    W, G, act = 16, 8, "ssp"
+    pos, box, cutoff = wf.frame("conformer90")
+    w1, b1, w2, b2, x, g = wf.cfconv_float64.weights(W, G, len(pos), 904)
+    conv = _module(W, G, act, (w1, b1, w2, b2), force_trainable=True).to(DEV)
+    tpos = _leaf(pos)
+    nb = _neighbors(tpos.detach(), None, cutoff)
+    F, = torch.autograd.grad(conv(nb, tpos, _dev(x)).sum(), tpos, create_graph=True)
+    node = F.grad_fn
+    assert "CFConvForceBackwardFunction" in type(node).__name__ or "CFConvForceBackwardFunction" in node.name()
+    assert F.requires_grad and all(p.grad is None for p in conv.parameters())
+    (F ** 2).sum().backward()
+    assert all(p.grad is not None and bool(p.grad.any()) for p in conv.parameters())
+
+
+def test_refusals(monkeypatch):
+    _env(monkeypatch)
+    W, G, act = 16, 8, "ssp"
+    pos, box, cutoff = wf.frame("conformer90")
+    w1, b1, w2, b2, x, g = wf.cfconv_float64.weights(W, G, len(pos), 903)
+    tpos, tx = _leaf(pos), _leaf(x)
+    nb = _neighbors(tpos.detach(), None, cutoff)
+    conv = _module(W, G, act, (w1, b1, w2, b2), force_trainable=True).to(DEV)
+    # a third derivative
+    F, = torch.autograd.grad(conv(nb, tpos, tx).sum(), tpos, create_graph=True)
+    H, = torch.autograd.grad((F ** 2).sum(), tpos, create_graph=True)
+    with pytest.raises(RuntimeError, match="third derivatives are not implemented"):
+        torch.autograd.grad(H.sum(), tpos)
+    # a cotangent for a first-order weight gradient
+    gw, = torch.autograd.grad(conv(nb, tpos, tx).sum(), conv.weights2, create_graph=True)
+    with pytest.raises(RuntimeError, match="weight-weight second derivatives"):
+        torch.autograd.grad((gw ** 2).sum(), tpos)
+    # a list rebuilt since the forward pass, in the first and in the second derivative
+    out = conv(nb, tpos, tx)
+    nb.build(tpos.detach())
+    with pytest.raises(RuntimeError, match="rebuilt since the forward pass"):
+        out.sum().backward()
+    F, = torch.autograd.grad(conv(nb, tpos, tx).sum(), tpos, create_graph=True)
+    nb.build(tpos.detach())
+    with pytest.raises(RuntimeError, match="rebuilt since the forward pass"):
+        (F ** 2).sum().backward()
+    # weights uploaded again between the forward pass and a derivative
+    op = torch.ops.NNPOpsCFConv.operation_weights_twice
+    good = [conv.weights1, conv.biases1, conv.weights2, conv.biases2]
+    other = [torch.nn.Parameter(0.5 * p.detach().clone()) for p in good]
+    out = op(conv.holder, nb.holder, tpos, tx, *good)
+    op(conv.holder, nb.holder, tpos, tx, *other)
+    with pytest.raises(RuntimeError, match="uploaded again since the forward pass"):
+        out.sum().backward()
+    F, = torch.autograd.grad(op(conv.holder, nb.holder, tpos, tx, *other).sum(), tpos, create_graph=True)
+    op(conv.holder, nb.holder, tpos, tx, *good)
+    with pytest.raises(RuntimeError, match="uploaded again since the forward pass"):
+        (F ** 2).sum().backward()
+    # shapes and types, as operation_weights
+    for k, bad, what in [(0, conv.weights1.detach().reshape(W, G)[:, :G - 1], "shape of \"weights1\""),
+                         (2, conv.weights2.detach().double(), "type of \"weights2\"")]:
+        args = list(good)
+        args[k] = bad
+        with pytest.raises(RuntimeError, match=what):
+            op(conv.holder, nb.holder, tpos, tx, *args)
+    # a box that requires a gradient
+    ppos, pbox = wf.cfconv_float64.frame("cubic100")
+    tp, tb = _leaf(ppos), _leaf(pbox)
+    pnb = _neighbors(tp.detach(), tb.detach(), 4.5)
+    px = _dev(wf.cfconv_float64.weights(W, G, len(ppos), 905)[4])
+    with pytest.raises(RuntimeError, match="box gradients"):
+        conv(pnb, tp, px, tb)
+    # trainable=True alone keeps refusing create_graph=True
+    plain = _module(W, G, act, (w1, b1, w2, b2), trainable=True).to(DEV)
+    with pytest.raises(RuntimeError, match="second derivatives are not implemented"):
+        torch.autograd.grad(plain(nb, tpos, tx).sum(), tpos, create_graph=True)
