@@ -1007,7 +1007,7 @@ public:
     }
 
     Tensor forward(const c10::IValue& neighbors_, const Tensor& positions_, const Tensor& input_) {
-        neighbors = neighbors_.toCustomClass<Neighbors>();      // kept for the backward pass
+        neighbors = neighbors_.toCustomClass<Neighbors>();      // kept, with positions and input, for the scripted backward() alone
         if (positions_.scalar_type() != torch::kFloat32) throw std::runtime_error("The type of \"positions\" has to be float32");
         if (positions_.dim() != 2) throw std::runtime_error("The shape of \"positions\" has to have 2 dimensions");
         if (positions_.size(1) != 3) throw std::runtime_error("The size of the 2nd dimension of \"positions\" has to be 3");
@@ -1067,8 +1067,8 @@ public:
         return output;
     }
 
-    // Additive (operation_periodic): the same forward, to the bit, on a list built with box vectors; the box is kept next to the positions
-    // for a backward pass that returns dL/dbox (the box vectors must be those of the list's last build).
+    // Additive (operation_periodic): the same forward, to the bit, on a list built with box vectors.  The box is checked here and kept by
+    // the node that asked, for a backward pass that returns dL/dbox (the box vectors must be those of the list's last build).
     Tensor forwardPeriodic(const c10::IValue& neighbors_, const Tensor& positions_, const Tensor& box_, const Tensor& input_) {
         if (box_.scalar_type() != torch::kFloat32) throw std::runtime_error("The type of \"box\" has to be float32");
         if (box_.dim() != 2 || box_.size(0) != 3 || box_.size(1) != 3) throw std::runtime_error("The shape of \"box\" has to be (3, 3)");
@@ -1079,74 +1079,85 @@ public:
             throw std::runtime_error("\"neighbors\" holds batched molecules (set_molecules), which are non-periodic: the convolution takes no \"box\" with them");
         if (!nb->getImpl()) throw std::runtime_error("\"neighbors\" has not been built");
         if (!nb->isPeriodic()) throw std::runtime_error("\"neighbors\" has been built without a box: a \"box\" needs a periodic neighbour list");
-        Tensor output = forward(neighbors_, positions_, input_);
-        box = box_.detach().contiguous();
-        return output;
+        return forward(neighbors_, positions_, input_);
     }
 
-    // backward() and dL/dbox behind it (nnpops_cfconv_backprop_box): {holder, neighbours, positions, box, input}
-    tensor_list backwardBox(const tensor_list& grads) {
-        if (!impl || !box.defined()) throw std::runtime_error("backwardBox() called before forwardPeriodic()");
-        const Tensor outputGrad = grads[0].contiguous();
-        const auto opts = torch::TensorOptions().device(device).dtype(torch::kFloat32);
-        Tensor inputGrad = torch::empty({numAtoms, numFilters}, opts);
-        Tensor positionsGrad = torch::empty({numAtoms, 3}, opts);
-        Tensor boxGrad = torch::empty({3, 3}, opts);
-        nnpops_cfconv_set_stream(impl, current_stream(device));
-        if (nnpops_cfconv_backprop_box(impl, neighbors->getImpl(), positions.data_ptr<float>(), box.data_ptr<float>(), input.data_ptr<float>(),
-                                       outputGrad.data_ptr<float>(), inputGrad.data_ptr<float>(), positionsGrad.data_ptr<float>(),
-                                       boxGrad.data_ptr<float>()) != NNPOPS_OK)
-            raise_last("NNPOpsCFConv::backward");
-        return {Tensor(), Tensor(), positionsGrad, boxGrad, inputGrad};
-    }
-
+    // The scripted backward() of the reference's surface: the gradients of the last direct forward() call, {holder, neighbours, positions,
+    // input} (nothing for the first two, :189).  It is the only reader of the slot; the autograd nodes below keep the tensors of their own
+    // forward pass in their own contexts and hand them to the four routines that follow.
     tensor_list backward(const tensor_list& grads) {
         if (!impl) throw std::runtime_error("backward() called before forward()");
-        const Tensor outputGrad = grads[0].contiguous();
-        const auto opts = torch::TensorOptions().device(device).dtype(torch::kFloat32);
-        Tensor inputGrad = torch::empty({numAtoms, numFilters}, opts);
-        Tensor positionsGrad = torch::empty({numAtoms, 3}, opts);
-        nnpops_cfconv_set_stream(impl, current_stream(device));
-        if (nnpops_cfconv_backprop(impl, neighbors->getImpl(), positions.data_ptr<float>(), nullptr, input.data_ptr<float>(),
-                                   outputGrad.data_ptr<float>(), inputGrad.data_ptr<float>(), positionsGrad.data_ptr<float>()) != NNPOPS_OK)
-            raise_last("NNPOpsCFConv::backward");
-        return {Tensor(), Tensor(), positionsGrad, inputGrad};    // nothing for the holder and the neighbours (:189)
+        const tensor_list d = backwardOf(neighbors, positions, Tensor(), input, grads[0], false);
+        return {Tensor(), Tensor(), d[1], d[0]};
     }
 
-    // The twice-differentiable ops (operation_twice / operation_periodic_twice) keep their tensors in their own autograd contexts, not in
-    // the slot above: the backward pass on what the caller hands over (the routine and the bits of backward()) ...
-    tensor_list backwardOf(const NeighborsPtr& nb, const Tensor& positions_, const Tensor& input_, const Tensor& outputGrad_) {
-        if (!impl) throw std::runtime_error("backward() called before forward()");
-        const Tensor pos = positions_.detach().contiguous(), in = input_.detach().contiguous(), outputGrad = outputGrad_.detach().contiguous();
-        const auto opts = torch::TensorOptions().device(device).dtype(torch::kFloat32);
-        Tensor inputGrad = torch::empty({numAtoms, numFilters}, opts);
-        Tensor positionsGrad = torch::empty({numAtoms, 3}, opts);
-        nnpops_cfconv_set_stream(impl, current_stream(device));
-        if (nnpops_cfconv_backprop(impl, nb->getImpl(), pos.data_ptr<float>(), nullptr, in.data_ptr<float>(), outputGrad.data_ptr<float>(),
-                                   inputGrad.data_ptr<float>(), positionsGrad.data_ptr<float>()) != NNPOPS_OK)
-            raise_last("NNPOpsCFConv::backward");
-        return {inputGrad, positionsGrad};
+    // {inputGrad, positionsGrad, boxGrad} of one forward pass on the tensors the caller hands over: nnpops_cfconv_backprop, or, when the
+    // box wants its gradient, nnpops_cfconv_backprop_box (the same launches and dL/dbox behind them); boxGrad is undefined otherwise
+    tensor_list backwardOf(const NeighborsPtr& nb, const Tensor& positions_, const Tensor& box_ /* undefined: none */, const Tensor& input_,
+                           const Tensor& outputGrad_, bool wantBox) {
+        const auto opts = gradOptions();
+        const Tensor pos = dense(positions_), in = dense(input_), outputGrad = dense(outputGrad_);
+        Tensor inputGrad = torch::empty({numAtoms, numFilters}, opts), positionsGrad = torch::empty({numAtoms, 3}, opts), boxGrad;
+        if (wantBox) {
+            if (!box_.defined()) throw std::runtime_error("a box gradient needs the box vectors of the forward pass");
+            const Tensor box = dense(box_);
+            boxGrad = torch::empty({3, 3}, opts);
+            launch("NNPOpsCFConv::backward", [&] {
+                return nnpops_cfconv_backprop_box(impl, nb->getImpl(), pos.data_ptr<float>(), box.data_ptr<float>(), in.data_ptr<float>(),
+                                                  outputGrad.data_ptr<float>(), inputGrad.data_ptr<float>(), positionsGrad.data_ptr<float>(),
+                                                  boxGrad.data_ptr<float>());
+            });
+        } else {
+            launch("NNPOpsCFConv::backward", [&] {
+                return nnpops_cfconv_backprop(impl, nb->getImpl(), pos.data_ptr<float>(), nullptr, in.data_ptr<float>(),
+                                              outputGrad.data_ptr<float>(), inputGrad.data_ptr<float>(), positionsGrad.data_ptr<float>());
+            });
+        }
+        return {inputGrad, positionsGrad, boxGrad};
     }
 
-    // ... and its backward (nnpops_cfconv_double_backward): cotangents of the two gradients (either may be undefined = zero) to the
-    // gradients with respect to {outputGrad, input, positions}
+    // dL/d(weights1, biases1, weights2, biases2) of the same pass (nnpops_cfconv_backprop_weights).  weights1 keeps the module's
+    // convention: the core's [W][G] result is the [G, W] tensor's buffer, reinterpreted and not transposed.
+    tensor_list backwardWeightsOf(const NeighborsPtr& nb, const Tensor& input_, const Tensor& outputGrad_) {
+        const tensor_list w = weightGrads(gradOptions());
+        const Tensor in = dense(input_), outputGrad = dense(outputGrad_);
+        launch("NNPOpsCFConv::backward (weights)", [&] {
+            return nnpops_cfconv_backprop_weights(impl, nb->getImpl(), in.data_ptr<float>(), outputGrad.data_ptr<float>(), w[0].data_ptr<float>(),
+                                                  w[1].data_ptr<float>(), w[2].data_ptr<float>(), w[3].data_ptr<float>());
+        });
+        return w;
+    }
+
+    // The backward of backwardOf() (nnpops_cfconv_double_backward): cotangents of its two gradients (either may be undefined = zero) to
+    // the gradients with respect to {outputGrad, input, positions} ...
     tensor_list doubleBackward(const NeighborsPtr& nb, const Tensor& positions_, const Tensor& input_, const Tensor& outputGrad_,
                                const Tensor& ggInput_, const Tensor& ggPositions_) {
-        if (!impl) throw std::runtime_error("backward() called before forward()");
-        const Tensor pos = positions_.detach().contiguous(), in = input_.detach().contiguous(), outputGrad = outputGrad_.detach().contiguous();
-        Tensor ggInput, ggPositions;
-        if (ggInput_.defined()) ggInput = ggInput_.detach().to(torch::kFloat32).contiguous();
-        if (ggPositions_.defined()) ggPositions = ggPositions_.detach().to(torch::kFloat32).contiguous();
-        const auto opts = torch::TensorOptions().device(device).dtype(torch::kFloat32);
+        const auto opts = gradOptions();
+        const Tensor pos = dense(positions_), in = dense(input_), outputGrad = dense(outputGrad_);
+        const Tensor ggInput = cotangent(ggInput_), ggPositions = cotangent(ggPositions_);
         Tensor dOutputGrad = torch::empty({numAtoms, numFilters}, opts), dInput = torch::empty({numAtoms, numFilters}, opts);
         Tensor dPositions = torch::empty({numAtoms, 3}, opts);
-        nnpops_cfconv_set_stream(impl, current_stream(device));
-        if (nnpops_cfconv_double_backward(impl, nb->getImpl(), pos.data_ptr<float>(), in.data_ptr<float>(), outputGrad.data_ptr<float>(),
-                                          ggInput.defined() ? ggInput.data_ptr<float>() : nullptr,
-                                          ggPositions.defined() ? ggPositions.data_ptr<float>() : nullptr, dOutputGrad.data_ptr<float>(),
-                                          dInput.data_ptr<float>(), dPositions.data_ptr<float>()) != NNPOPS_OK)
-            raise_last("NNPOpsCFConv::operation_twice (double backward)");
+        launch("NNPOpsCFConv::double backward", [&] {
+            return nnpops_cfconv_double_backward(impl, nb->getImpl(), pos.data_ptr<float>(), in.data_ptr<float>(), outputGrad.data_ptr<float>(),
+                                                 data_or_null(ggInput), data_or_null(ggPositions), dOutputGrad.data_ptr<float>(),
+                                                 dInput.data_ptr<float>(), dPositions.data_ptr<float>());
+        });
         return {dOutputGrad, dInput, dPositions};
+    }
+
+    // ... and the weight gradients of what doubleBackward() differentiates (nnpops_cfconv_double_backward_weights), weights1 in the
+    // module's convention as above
+    tensor_list doubleBackwardWeights(const NeighborsPtr& nb, const Tensor& input_, const Tensor& outputGrad_, const Tensor& ggInput_,
+                                      const Tensor& ggPositions_) {
+        const tensor_list w = weightGrads(gradOptions());
+        const Tensor in = dense(input_), outputGrad = dense(outputGrad_);
+        const Tensor ggInput = cotangent(ggInput_), ggPositions = cotangent(ggPositions_);
+        launch("NNPOpsCFConv::double backward (weights)", [&] {
+            return nnpops_cfconv_double_backward_weights(impl, nb->getImpl(), in.data_ptr<float>(), outputGrad.data_ptr<float>(),
+                                                         data_or_null(ggInput), data_or_null(ggPositions), w[0].data_ptr<float>(),
+                                                         w[1].data_ptr<float>(), w[2].data_ptr<float>(), w[3].data_ptr<float>());
+        });
+        return w;
     }
 
     // Trainable filters (operation_weights / operation_periodic_weights): bring the handle up to date with four weight tensors the
@@ -1181,57 +1192,6 @@ public:
     // how many times syncWeights() has replaced the weights (a forward pass with unchanged parameters does not count)
     int64_t getUploads() const { return uploads; }
 
-    // dL/d(weights1, biases1, weights2, biases2) for the tensors of the last forward pass (nnpops_cfconv_backprop_weights).  weights1 keeps
-    // the module's convention: the core's [W][G] result is the [G, W] tensor's buffer, reinterpreted and not transposed.
-    tensor_list backwardWeights(const Tensor& outputGrad_) {
-        if (!impl) throw std::runtime_error("backward() called before forward()");
-        const Tensor outputGrad = outputGrad_.detach().contiguous();
-        const auto opts = torch::TensorOptions().device(device).dtype(torch::kFloat32);
-        Tensor g1 = torch::empty(weights1.sizes(), opts), gb1 = torch::empty({numFilters}, opts);
-        Tensor g2 = torch::empty({numFilters, numFilters}, opts), gb2 = torch::empty({numFilters}, opts);
-        nnpops_cfconv_set_stream(impl, current_stream(device));
-        if (nnpops_cfconv_backprop_weights(impl, neighbors->getImpl(), input.data_ptr<float>(), outputGrad.data_ptr<float>(),
-                                           g1.data_ptr<float>(), gb1.data_ptr<float>(), g2.data_ptr<float>(), gb2.data_ptr<float>()) != NNPOPS_OK)
-            raise_last("NNPOpsCFConv::operation_weights (backward)");
-        return {g1, gb1, g2, gb2};
-    }
-
-    // The force-trainable ops (operation_weights_twice / operation_periodic_weights_twice) keep their tensors in their own autograd
-    // contexts: the weight gradients on what the caller hands over (the routine and the bits of backwardWeights()) ...
-    tensor_list backwardWeightsOf(const NeighborsPtr& nb, const Tensor& input_, const Tensor& outputGrad_) {
-        if (!impl) throw std::runtime_error("backward() called before forward()");
-        const Tensor in = input_.detach().contiguous(), outputGrad = outputGrad_.detach().contiguous();
-        const auto opts = torch::TensorOptions().device(device).dtype(torch::kFloat32);
-        Tensor g1 = torch::empty(weights1.sizes(), opts), gb1 = torch::empty({numFilters}, opts);
-        Tensor g2 = torch::empty({numFilters, numFilters}, opts), gb2 = torch::empty({numFilters}, opts);
-        nnpops_cfconv_set_stream(impl, current_stream(device));
-        if (nnpops_cfconv_backprop_weights(impl, nb->getImpl(), in.data_ptr<float>(), outputGrad.data_ptr<float>(), g1.data_ptr<float>(),
-                                           gb1.data_ptr<float>(), g2.data_ptr<float>(), gb2.data_ptr<float>()) != NNPOPS_OK)
-            raise_last("NNPOpsCFConv::operation_weights_twice (backward)");
-        return {g1, gb1, g2, gb2};
-    }
-
-    // ... and the weight gradients of what doubleBackward() differentiates (nnpops_cfconv_double_backward_weights), weights1 in the
-    // module's convention as above
-    tensor_list doubleBackwardWeights(const NeighborsPtr& nb, const Tensor& input_, const Tensor& outputGrad_, const Tensor& ggInput_,
-                                      const Tensor& ggPositions_) {
-        if (!impl) throw std::runtime_error("backward() called before forward()");
-        const Tensor in = input_.detach().contiguous(), outputGrad = outputGrad_.detach().contiguous();
-        Tensor ggInput, ggPositions;
-        if (ggInput_.defined()) ggInput = ggInput_.detach().to(torch::kFloat32).contiguous();
-        if (ggPositions_.defined()) ggPositions = ggPositions_.detach().to(torch::kFloat32).contiguous();
-        const auto opts = torch::TensorOptions().device(device).dtype(torch::kFloat32);
-        Tensor g1 = torch::empty(weights1.sizes(), opts), gb1 = torch::empty({numFilters}, opts);
-        Tensor g2 = torch::empty({numFilters, numFilters}, opts), gb2 = torch::empty({numFilters}, opts);
-        nnpops_cfconv_set_stream(impl, current_stream(device));
-        if (nnpops_cfconv_double_backward_weights(impl, nb->getImpl(), in.data_ptr<float>(), outputGrad.data_ptr<float>(),
-                                                  ggInput.defined() ? ggInput.data_ptr<float>() : nullptr,
-                                                  ggPositions.defined() ? ggPositions.data_ptr<float>() : nullptr, g1.data_ptr<float>(),
-                                                  gb1.data_ptr<float>(), g2.data_ptr<float>(), gb2.data_ptr<float>()) != NNPOPS_OK)
-            raise_last("NNPOpsCFConv::operation_weights_twice (double backward)");
-        return {g1, gb1, g2, gb2};
-    }
-
     static std::string serialize(const HolderPtr& self) {
         torch::serialize::OutputArchive archive;
         archive.write("gaussianWidth", self->gaussianWidth);
@@ -1261,14 +1221,35 @@ public:
     }
 
 private:
+    // what the four gradient routines share: float32 outputs on the handle's device (a handle there must be) ...
+    torch::TensorOptions gradOptions() const {
+        if (!impl) throw std::runtime_error("backward() called before forward()");
+        return torch::TensorOptions().device(device).dtype(torch::kFloat32);
+    }
+    tensor_list weightGrads(const torch::TensorOptions& opts) const {
+        return {torch::empty(weights1.sizes(), opts), torch::empty({numFilters}, opts), torch::empty({numFilters, numFilters}, opts),
+                torch::empty({numFilters}, opts)};
+    }
+    // ... what the core reads: a tensor as it is, an optional cotangent as float32 or as nullptr ...
+    static Tensor dense(const Tensor& t) { return t.is_contiguous() ? t : t.detach().contiguous(); }
+    static Tensor cotangent(const Tensor& t) { return t.defined() ? t.detach().to(torch::kFloat32).contiguous() : Tensor(); }
+    static const float* data_or_null(const Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; }
+    // ... and one call of the core on the current stream
+    template <typename Call>
+    void launch(const char* what, Call&& call) {
+        nnpops_cfconv_set_stream(impl, current_stream(device));
+        if (call() != NNPOPS_OK) raise_last(what);
+    }
+
     double gaussianWidth;
     std::string activation;
     Tensor weights1, biases1, weights2, biases2;
     torch::Device device = torch::kCPU;
     int64_t numAtoms = 0, numFilters = 0;
     double cutoff = 0;
+    // the slot: the tensors of the last forward() call, read by the scripted backward() and by nothing else
     NeighborsPtr neighbors;
-    Tensor positions, input, box;
+    Tensor positions, input;
     nnpops_cfconv_t impl = nullptr;
     // syncWeights(): what the handle (or, before the first forward pass, the host copies) last received
     const void* uploadedData[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -1276,251 +1257,112 @@ private:
     int64_t uploads = 0;
 };
 
-class AutogradFunctions : public torch::autograd::Function<AutogradFunctions> {
-public:
-    static Tensor forward(AutogradContext* ctx, const HolderPtr& holder, const c10::IValue& neighbors, const Tensor& positions,
-                          const Tensor& input) {
-        ctx->saved_data["holder"] = holder;
-        return holder->forward(neighbors, positions, input);
-    }
-    static tensor_list backward(AutogradContext* ctx, const tensor_list& grads) {
-        const HolderPtr holder = ctx->saved_data["holder"].toCustomClass<Holder>();
-        ctx->saved_data.erase("holder");
-        return holder->backward(grads);
-    }
-};
-
-// `boxGrad` (decided by the caller, where grad mode is what the user set) = the box vectors require a gradient: the node's backward then
-// runs the box-gradient pass behind the usual launches and fills the box's slot; otherwise it is the plain backward and the slot stays empty.
-class PeriodicAutogradFunctions : public torch::autograd::Function<PeriodicAutogradFunctions> {
-public:
-    static Tensor forward(AutogradContext* ctx, const HolderPtr& holder, const c10::IValue& neighbors, const Tensor& positions,
-                          const Tensor& box, const Tensor& input, bool boxGrad) {
-        ctx->saved_data["holder"] = holder;
-        ctx->saved_data["box_grad"] = boxGrad;
-        return holder->forwardPeriodic(neighbors, positions, box, input);
-    }
-    static tensor_list backward(AutogradContext* ctx, const tensor_list& grads) {
-        const HolderPtr holder = ctx->saved_data["holder"].toCustomClass<Holder>();
-        ctx->saved_data.erase("holder");
-        tensor_list out;
-        if (ctx->saved_data["box_grad"].toBool()) {
-            out = holder->backwardBox(grads);
-        } else {
-            out = holder->backward(grads);                   // {holder, neighbours, positions, input}
-            out.insert(out.begin() + 3, Tensor());           // (no gradient for the box)
-        }
-        out.push_back(Tensor());
-        return out;
-    }
-};
-
-Tensor operation(const c10::optional<HolderPtr>& holder, const c10::IValue& neighbors, const Tensor& positions,
-                 const Tensor& input) {
-    return AutogradFunctions::apply(*holder, neighbors, positions, input);
-}
-
-Tensor operation_periodic(const c10::optional<HolderPtr>& holder, const c10::IValue& neighbors, const Tensor& positions,
-                          const Tensor& box, const Tensor& input) {
-    return PeriodicAutogradFunctions::apply(*holder, neighbors, positions, box, input, torch::GradMode::is_enabled() && box.requires_grad());
-}
-
 // ---------------------------------------------------------------------------------------------
-// operation_twice / operation_periodic_twice: the forward and the first backward of operation / operation_periodic (Holder::forward,
-// nnpops_cfconv_backprop: the same kernels and bits), recorded so that the backward pass is itself differentiable with respect to
-// the output gradient, the positions and the input.
-//     CFConvBackwardFunction         (g, positions, input) -> (gx, gp); keeps its tensors in its own context
-//     CFConvDoubleBackwardFunction   (V, Q, g, positions, input) -> (dM/dg, dM/dx, dM/dpositions), nnpops_cfconv_double_backward
-// Every node records the number of the list's build in the forward pass and raises on another: the rows it would walk belong to
-// other positions.  No box gradient (operation_periodic has it) and no third derivative: both raise.
+// The eight ops are adaptors onto two families of autograd nodes.  Every node keeps the tensors of its own forward pass in its own
+// context, so two calls of one CFConv before the first is differentiated do not disturb each other.
+//   first order (CFConvFunction): operation, operation_periodic and, with the four weight arrays as inputs that take a gradient (trainable
+//     filters), operation_weights, operation_periodic_weights.  Its backward is Holder::backwardOf -- with dL/dbox where
+//     the box asked for it -- and, where a weight asks, Holder::backwardWeightsOf; it is not recorded.
+//   recorded (CFConvTwiceFunction -> CFConvBackwardFunction -> CFConvDoubleBackwardFunction): operation_twice, operation_periodic_twice
+//      and, with the weights, operation_weights_twice, operation_periodic_weights_twice (3.7f): the same forward and
+//     first backward, to the bit, recorded so that the backward pass is itself differentiable:
+//       CFConvBackwardFunction         (g, positions, input, weights) -> (gx, gp, the wanted weight gradients)
+//       CFConvDoubleBackwardFunction   (V, Q, g, positions, input) -> (dM/dg, dM/dx, dM/dpositions, the wanted weight gradients)
+//     Refused: third derivatives, a cotangent for the first-order weight gradients (weight-weight second derivatives), a box that
+//     requires a gradient (the first-order ops have it).
+// With weights the forward pass first brings the handle up to date (Holder::syncWeights).  Every node but that of the two default ops
+// records the number of the list's build in the forward pass, the recorded ones with weights the holder's upload count too, and raises
+// on another: the rows it would walk belong to other positions, the gradient to other weights.
 // ---------------------------------------------------------------------------------------------
-inline void check_same_build(const NeighborsPtr& nb, int64_t build) {
-    TORCH_CHECK(nb->getBuildCount() == build, "NNPOpsCFConv::operation_twice: \"neighbors\" has been rebuilt since the forward pass; its rows "
-                "no longer belong to the positions this gradient is taken at (build the list, run the forward pass and differentiate "
+using MaybeTensor = c10::optional<Tensor>;
+
+inline void check_same_state(const HolderPtr& holder, const NeighborsPtr& nb, int64_t build, int64_t uploads /* -1: not tracked */,
+                             const char* op) {
+    TORCH_CHECK(nb->getBuildCount() == build, "NNPOpsCFConv::", op, ": \"neighbors\" has been rebuilt since the forward pass; its rows no "
+                "longer belong to the positions this gradient is taken at (build the list, run the forward pass and differentiate "
                 "before building it again)");
+    TORCH_CHECK(uploads < 0 || holder->getUploads() == uploads, "NNPOpsCFConv::", op, ": the weights have been uploaded again since the "
+                "forward pass (an optimizer step or another forward pass with new values); this gradient would be taken at other "
+                "weights than the output it belongs to (differentiate before the weights change)");
 }
 
-class CFConvDoubleBackwardFunction : public torch::autograd::Function<CFConvDoubleBackwardFunction> {
-public:
-    // (a cotangent nobody asked for arrives undefined -- CFConvBackwardFunction does not materialise zeros -- and travels as nullopt)
-    static tensor_list forward(AutogradContext*, const c10::optional<Tensor>& ggInput, const c10::optional<Tensor>& ggPositions, const Tensor& g,
-                               const Tensor& positions, const Tensor& input, const HolderPtr& holder, const c10::IValue& neighbors,
-                               int64_t build) {
-        const NeighborsPtr nb = neighbors.toCustomClass<Neighbors>();
-        check_same_build(nb, build);
-        return holder->doubleBackward(nb, positions, input, g, ggInput ? *ggInput : Tensor(), ggPositions ? *ggPositions : Tensor());
-    }
-    static tensor_list backward(AutogradContext*, tensor_list) {
-        TORCH_CHECK(false, "NNPOpsCFConv::operation_twice: third derivatives are not implemented");
-        return {};
-    }
-};
+// the forward pass of every op: the weights, where they are inputs, reach the handle first
+inline Tensor run_forward(const HolderPtr& holder, const c10::IValue& neighbors, const Tensor& positions, const MaybeTensor& box,
+                          const Tensor& input, const MaybeTensor& weights1, const MaybeTensor& biases1, const MaybeTensor& weights2,
+                          const MaybeTensor& biases2) {
+    if (weights1) holder->syncWeights(*weights1, *biases1, *weights2, *biases2);
+    return box ? holder->forwardPeriodic(neighbors, positions, *box, input) : holder->forward(neighbors, positions, input);
+}
 
-class CFConvBackwardFunction : public torch::autograd::Function<CFConvBackwardFunction> {
-public:
-    static tensor_list forward(AutogradContext* ctx, const Tensor& g, const Tensor& positions, const Tensor& input, const HolderPtr& holder,
-                               const c10::IValue& neighbors, int64_t build) {
-        const NeighborsPtr nb = neighbors.toCustomClass<Neighbors>();
-        check_same_build(nb, build);
-        ctx->set_materialize_grads(false);
-        ctx->save_for_backward({g, positions, input});
-        ctx->saved_data["holder"] = holder;
-        ctx->saved_data["neighbors"] = neighbors;
-        ctx->saved_data["build"] = build;
-        return holder->backwardOf(nb, positions, input, g);
-    }
-    static tensor_list backward(AutogradContext* ctx, tensor_list grads) {
-        if (!grads[0].defined() && !grads[1].defined()) return {Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
-        const auto s = ctx->get_saved_variables();
-        const auto given = [](const Tensor& t) { return t.defined() ? c10::optional<Tensor>(t) : c10::optional<Tensor>(); };
-        const tensor_list d = CFConvDoubleBackwardFunction::apply(given(grads[0]), given(grads[1]), s[0], s[1], s[2],
-                                                                  ctx->saved_data["holder"].toCustomClass<Holder>(),
-                                                                  ctx->saved_data["neighbors"], ctx->saved_data["build"].toInt());
-        return {d[0], d[2], d[1], Tensor(), Tensor(), Tensor()};
-    }
-};
+// bit k = weight k takes a gradient: what the engine asks of a node whose weights are its tensor inputs first, first + 1, ...
+inline int64_t wanted_weights(AutogradContext* ctx, size_t first) {
+    int64_t wants = 0;
+    for (int k = 0; k < 4; k++) wants |= ctx->needs_input_grad(first + k) ? (int64_t)1 << k : 0;
+    return wants;
+}
 
-// (periodic: the box is an input only so that the op has operation_periodic's schema; its slot stays empty)
-class CFConvTwiceFunction : public torch::autograd::Function<CFConvTwiceFunction> {
+// a weight gradient where its weight lives (a parameter kept on the CPU receives a CPU gradient)
+inline Tensor weight_grad_for(const Tensor& grad, const Tensor& weight) { return weight.is_cpu() ? grad.cpu() : grad; }
+
+// box: empty for the non-periodic ops; weights: empty for the default ops.  wants (decided by the caller, where grad mode is what the
+// user set): bit k = weight k requires a gradient, bit 4 = the box does.
+class CFConvFunction : public torch::autograd::Function<CFConvFunction> {
 public:
     static Tensor forward(AutogradContext* ctx, const HolderPtr& holder, const c10::IValue& neighbors, const Tensor& positions,
-                          const c10::optional<Tensor>& box, const Tensor& input) {
-        const Tensor output = box ? holder->forwardPeriodic(neighbors, positions, *box, input) : holder->forward(neighbors, positions, input);
-        ctx->save_for_backward({positions, input});
+                          const MaybeTensor& box, const Tensor& input, const MaybeTensor& weights1, const MaybeTensor& biases1,
+                          const MaybeTensor& weights2, const MaybeTensor& biases2, int64_t wants) {
+        // (what the core reads is what the backward pass is handed: it copies nothing again)
+        const Tensor pos = positions.detach().contiguous(), in = input.detach().contiguous();
+        const Tensor output = run_forward(holder, neighbors, pos, box, in, weights1, biases1, weights2, biases2);
+        int64_t on_cpu = 0;
+        if (weights1) on_cpu = (weights1->is_cpu() ? 1 : 0) | (biases1->is_cpu() ? 2 : 0) | (weights2->is_cpu() ? 4 : 0) | (biases2->is_cpu() ? 8 : 0);
         ctx->saved_data["holder"] = holder;
         ctx->saved_data["neighbors"] = neighbors;
-        ctx->saved_data["build"] = neighbors.toCustomClass<Neighbors>()->getBuildCount();
-        return output;
-    }
-    static tensor_list backward(AutogradContext* ctx, tensor_list grads) {
-        const auto s = ctx->get_saved_variables();
-        const tensor_list d = CFConvBackwardFunction::apply(grads[0], s[0], s[1], ctx->saved_data["holder"].toCustomClass<Holder>(),
-                                                            ctx->saved_data["neighbors"], ctx->saved_data["build"].toInt());
-        return {Tensor(), Tensor(), d[1], Tensor(), d[0]};
-    }
-};
-
-Tensor operation_twice(const c10::optional<HolderPtr>& holder, const c10::IValue& neighbors, const Tensor& positions, const Tensor& input) {
-    return CFConvTwiceFunction::apply(*holder, neighbors, positions, c10::optional<Tensor>(), input);
-}
-
-Tensor operation_periodic_twice(const c10::optional<HolderPtr>& holder, const c10::IValue& neighbors, const Tensor& positions,
-                                const Tensor& box, const Tensor& input) {
-    TORCH_CHECK(!(torch::GradMode::is_enabled() && box.requires_grad()),
-                "NNPOpsCFConv::operation_periodic_twice: box gradients need the default op (operation_periodic; CFConv without "
-                "twice_differentiable=True): the twice-differentiable ops return no box gradient");
-    return CFConvTwiceFunction::apply(*holder, neighbors, positions, c10::optional<Tensor>(box), input);
-}
-
-// ---------------------------------------------------------------------------------------------
-// operation_weights / operation_periodic_weights: operation / operation_periodic with the four weight arrays as inputs that take a
-// gradient (trainable filters).  The forward pass first brings the handle up to date (Holder::syncWeights) and is then
-// that of the default op, bit for bit; the backward pass returns the default op's gradients (Holder::backward / backwardBox) and, from the
-// same call, the weight gradients of nnpops_cfconv_backprop_weights when a weight asks for one.  First derivatives only: the backward
-// pass refuses to be recorded (create_graph=True), and a list rebuilt since the forward pass.
-// ---------------------------------------------------------------------------------------------
-class CFConvWeightsFunction : public torch::autograd::Function<CFConvWeightsFunction> {
-public:
-    // box: empty for the non-periodic op.  wants: bit k = weight k requires a gradient; bit 4 = the box does (decided by the caller,
-    // where grad mode is what the user set)
-    static Tensor forward(AutogradContext* ctx, const HolderPtr& holder, const c10::IValue& neighbors, const Tensor& positions,
-                          const c10::optional<Tensor>& box, const Tensor& input, const Tensor& weights1, const Tensor& biases1,
-                          const Tensor& weights2, const Tensor& biases2, int64_t wants) {
-        holder->syncWeights(weights1, biases1, weights2, biases2);
-        const Tensor output = box ? holder->forwardPeriodic(neighbors, positions, *box, input) : holder->forward(neighbors, positions, input);
-        const Tensor* w[4] = {&weights1, &biases1, &weights2, &biases2};
-        c10::List<int64_t> on_cpu;
-        for (int k = 0; k < 4; k++) on_cpu.push_back(w[k]->is_cpu() ? 1 : 0);
-        ctx->saved_data["holder"] = holder;
-        ctx->saved_data["neighbors"] = neighbors;
-        ctx->saved_data["build"] = neighbors.toCustomClass<Neighbors>()->getBuildCount();
-        ctx->saved_data["periodic"] = box.has_value();
+        ctx->saved_data["positions"] = pos;
+        ctx->saved_data["input"] = in;
+        if (wants & 16) ctx->saved_data["box"] = box->detach().contiguous();
+        ctx->saved_data["build"] = weights1 ? neighbors.toCustomClass<Neighbors>()->getBuildCount() : (int64_t)-1;      // -1: a default op
         ctx->saved_data["wants"] = wants;
         ctx->saved_data["on_cpu"] = on_cpu;
         return output;
     }
     static tensor_list backward(AutogradContext* ctx, const tensor_list& grads) {
-        TORCH_CHECK(!torch::GradMode::is_enabled(),
+        const int64_t build = ctx->saved_data["build"].toInt();
+        TORCH_CHECK(build < 0 || !torch::GradMode::is_enabled(),
                     "NNPOpsCFConv::operation_weights: second derivatives are not implemented for the trainable convolution (create_graph=True): "
                     "mixed second derivatives with respect to the filter network's weights are missing; training on forces takes "
                     "CFConv(..., twice_differentiable=True) with fixed weights");
         const HolderPtr holder = ctx->saved_data["holder"].toCustomClass<Holder>();
         const NeighborsPtr nb = ctx->saved_data["neighbors"].toCustomClass<Neighbors>();
-        TORCH_CHECK(nb->getBuildCount() == ctx->saved_data["build"].toInt(),
-                    "NNPOpsCFConv::operation_weights: \"neighbors\" has been rebuilt since the forward pass; its rows no longer belong to the "
-                    "positions this gradient is taken at (build the list, run the forward pass and differentiate before building it again)");
+        if (build >= 0) check_same_state(holder, nb, build, -1, "operation_weights");
         const int64_t wants = ctx->saved_data["wants"].toInt();
-        const bool periodic = ctx->saved_data["periodic"].toBool();
-        tensor_list out;                                     // {holder, neighbours, positions, box, input, four weights, wants}
-        if (periodic && (wants & 16)) {
-            out = holder->backwardBox(grads);
-        } else {
-            out = holder->backward(grads);                   // {holder, neighbours, positions, input}
-            out.insert(out.begin() + 3, Tensor());
-        }
+        const Tensor input = ctx->saved_data["input"].toTensor();
+        const Tensor box = wants & 16 ? ctx->saved_data["box"].toTensor() : Tensor();
+        const tensor_list d = holder->backwardOf(nb, ctx->saved_data["positions"].toTensor(), box, input, grads[0], (wants & 16) != 0);
+        tensor_list out = {Tensor(), Tensor(), d[1], d[2], d[0]};      // {holder, neighbours, positions, box, input, four weights, wants}
+        out.resize(10);
         if (wants & 15) {
-            const tensor_list w = holder->backwardWeights(grads[0]);
-            const c10::List<int64_t> on_cpu = ctx->saved_data["on_cpu"].toIntList();
-            for (int k = 0; k < 4; k++) out.push_back(!(wants >> k & 1) ? Tensor() : on_cpu.get(k) ? w[k].cpu() : w[k]);
-        } else {
-            for (int k = 0; k < 4; k++) out.push_back(Tensor());
+            const tensor_list w = holder->backwardWeightsOf(nb, input, grads[0]);
+            const int64_t on_cpu = ctx->saved_data["on_cpu"].toInt();
+            for (int k = 0; k < 4; k++)
+                if (wants >> k & 1) out[5 + k] = on_cpu >> k & 1 ? w[k].cpu() : w[k];
         }
-        out.push_back(Tensor());
         return out;
     }
 };
 
-inline int64_t weight_wants(const Tensor& w1, const Tensor& b1, const Tensor& w2, const Tensor& b2) {
-    if (!torch::GradMode::is_enabled()) return 0;
-    return (w1.requires_grad() ? 1 : 0) | (b1.requires_grad() ? 2 : 0) | (w2.requires_grad() ? 4 : 0) | (b2.requires_grad() ? 8 : 0);
-}
+inline const char* twice_op(int64_t uploads) { return uploads < 0 ? "operation_twice" : "operation_weights_twice"; }
 
-Tensor operation_weights(const c10::optional<HolderPtr>& holder, const c10::IValue& neighbors, const Tensor& positions, const Tensor& input,
-                         const Tensor& weights1, const Tensor& biases1, const Tensor& weights2, const Tensor& biases2) {
-    return CFConvWeightsFunction::apply(*holder, neighbors, positions, c10::optional<Tensor>(), input, weights1, biases1, weights2, biases2,
-                                        weight_wants(weights1, biases1, weights2, biases2));
-}
-
-Tensor operation_periodic_weights(const c10::optional<HolderPtr>& holder, const c10::IValue& neighbors, const Tensor& positions,
-                                  const Tensor& box, const Tensor& input, const Tensor& weights1, const Tensor& biases1,
-                                  const Tensor& weights2, const Tensor& biases2) {
-    TORCH_CHECK(box.defined(), "NNPOpsCFConv::operation_periodic_weights: \"box\" is undefined");
-    const int64_t box_wants = torch::GradMode::is_enabled() && box.requires_grad() ? 16 : 0;
-    return CFConvWeightsFunction::apply(*holder, neighbors, positions, c10::optional<Tensor>(box), input, weights1, biases1, weights2, biases2,
-                                        weight_wants(weights1, biases1, weights2, biases2) | box_wants);
-}
-
-// ---------------------------------------------------------------------------------------------
-// operation_weights_twice / operation_periodic_weights_twice: trainable filters under a force loss.  The forward pass is
-// that of operation_weights (Holder::syncWeights, then the default forward); the first backward is a recorded node, so that
-// torch.autograd.grad(E, positions, create_graph=True) can be differentiated once more, with respect to the weights as well:
-//     CFConvForceBackwardFunction         (g, positions, input, four weights) -> (gx, gp, the wanted weight gradients): nnpops_cfconv_backprop
-//                                         and, only where the engine asks for a weight gradient, nnpops_cfconv_backprop_weights
-//     CFConvForceDoubleBackwardFunction   (V, Q, g, positions, input) -> (dM/dg, dM/dx, dM/dpositions, the wanted weight gradients):
-//                                         nnpops_cfconv_double_backward and nnpops_cfconv_double_backward_weights
-// Every node records the list's build count and the holder's upload count of the forward pass and raises on another.  Refused: third
-// derivatives, a cotangent for the first-order weight gradients (weight-weight second derivatives), a box that requires a gradient.
-// ---------------------------------------------------------------------------------------------
-inline void check_same_state(const HolderPtr& holder, const NeighborsPtr& nb, int64_t build, int64_t uploads) {
-    TORCH_CHECK(nb->getBuildCount() == build, "NNPOpsCFConv::operation_weights_twice: \"neighbors\" has been rebuilt since the forward pass; "
-                "its rows no longer belong to the positions this gradient is taken at (build the list, run the forward pass and "
-                "differentiate before building it again)");
-    TORCH_CHECK(holder->getUploads() == uploads, "NNPOpsCFConv::operation_weights_twice: the weights have been uploaded again since the "
-                "forward pass (an optimizer step or another forward pass with new values); this gradient would be taken at other "
-                "weights than the output it belongs to (differentiate before the weights change)");
-}
-
-// a weight gradient where its weight lives (a parameter kept on the CPU receives a CPU gradient, as in operation_weights)
-inline Tensor weight_grad_for(const Tensor& grad, const Tensor& weight) { return weight.is_cpu() ? grad.cpu() : grad; }
-
-class CFConvForceDoubleBackwardFunction : public torch::autograd::Function<CFConvForceDoubleBackwardFunction> {
+// uploads: the holder's count in the forward pass, -1 for the ops without weights.  wants: bit k = weight k takes a gradient (0 without).
+class CFConvDoubleBackwardFunction : public torch::autograd::Function<CFConvDoubleBackwardFunction> {
 public:
-    // wants: bit k = weight k takes a gradient
-    static tensor_list forward(AutogradContext*, const c10::optional<Tensor>& ggInput, const c10::optional<Tensor>& ggPositions, const Tensor& g,
+    // (a cotangent nobody asked for arrives undefined -- CFConvBackwardFunction does not materialise zeros -- and travels as nullopt)
+    static tensor_list forward(AutogradContext* ctx, const MaybeTensor& ggInput, const MaybeTensor& ggPositions, const Tensor& g,
                                const Tensor& positions, const Tensor& input, const HolderPtr& holder, const c10::IValue& neighbors,
                                int64_t build, int64_t uploads, int64_t wants) {
         const NeighborsPtr nb = neighbors.toCustomClass<Neighbors>();
-        check_same_state(holder, nb, build, uploads);
+        check_same_state(holder, nb, build, uploads, twice_op(uploads));
+        ctx->saved_data["uploads"] = uploads;
         const Tensor V = ggInput ? *ggInput : Tensor(), Q = ggPositions ? *ggPositions : Tensor();
         tensor_list out = holder->doubleBackward(nb, positions, input, g, V, Q);
         if (wants & 15) {                                    // (a recorded node has no undefined outputs: the wanted ones only, in order)
@@ -1530,27 +1372,30 @@ public:
         }
         return out;
     }
-    static tensor_list backward(AutogradContext*, tensor_list) {
-        TORCH_CHECK(false, "NNPOpsCFConv::operation_weights_twice: third derivatives are not implemented");
+    static tensor_list backward(AutogradContext* ctx, tensor_list) {
+        TORCH_CHECK(false, "NNPOpsCFConv::", twice_op(ctx->saved_data["uploads"].toInt()), ": third derivatives are not implemented");
         return {};
     }
 };
 
-class CFConvForceBackwardFunction : public torch::autograd::Function<CFConvForceBackwardFunction> {
+class CFConvBackwardFunction : public torch::autograd::Function<CFConvBackwardFunction> {
 public:
-    static tensor_list forward(AutogradContext* ctx, const Tensor& g, const Tensor& positions, const Tensor& input, const Tensor& weights1,
-                               const Tensor& biases1, const Tensor& weights2, const Tensor& biases2, const HolderPtr& holder,
+    static tensor_list forward(AutogradContext* ctx, const Tensor& g, const Tensor& positions, const Tensor& input, const MaybeTensor& weights1,
+                               const MaybeTensor& biases1, const MaybeTensor& weights2, const MaybeTensor& biases2, const HolderPtr& holder,
                                const c10::IValue& neighbors, int64_t build, int64_t uploads, int64_t wants) {
         const NeighborsPtr nb = neighbors.toCustomClass<Neighbors>();
-        check_same_state(holder, nb, build, uploads);
+        check_same_state(holder, nb, build, uploads, twice_op(uploads));
         ctx->set_materialize_grads(false);
-        ctx->save_for_backward({g, positions, input, weights1, biases1, weights2, biases2});
+        tensor_list kept = {g, positions, input};
+        if (weights1) kept.insert(kept.end(), {*weights1, *biases1, *weights2, *biases2});
+        ctx->save_for_backward(kept);
         ctx->saved_data["holder"] = holder;
         ctx->saved_data["neighbors"] = neighbors;
         ctx->saved_data["build"] = build;
         ctx->saved_data["uploads"] = uploads;
-        tensor_list out = holder->backwardOf(nb, positions, input, g);
-        if (wants & 15) {                                    // (a recorded node has no undefined outputs: the wanted ones only, in order)
+        tensor_list out = holder->backwardOf(nb, positions, Tensor(), input, g, false);
+        out.resize(2);                                       // (a recorded node has no undefined outputs: the wanted ones only, in order)
+        if (wants & 15) {
             const tensor_list w = holder->backwardWeightsOf(nb, input, g);
             for (int k = 0; k < 4; k++)
                 if (wants >> k & 1) out.push_back(w[k]);
@@ -1562,71 +1407,116 @@ public:
             TORCH_CHECK(!grads[k].defined(), "NNPOpsCFConv::operation_weights_twice: second derivatives of the weight gradients themselves "
                         "(weight-weight second derivatives: a cotangent arrived for the gradient of a weight) are not implemented; the "
                         "second derivatives of this op are those of the gradients with respect to positions and input");
-        tensor_list none(12);
-        if (!grads[0].defined() && !grads[1].defined()) return none;
-        const auto s = ctx->get_saved_variables();
-        int64_t wants = 0;
-        for (int k = 0; k < 4; k++) wants |= ctx->needs_input_grad(3 + k) ? (int64_t)1 << k : 0;
-        const auto given = [](const Tensor& t) { return t.defined() ? c10::optional<Tensor>(t) : c10::optional<Tensor>(); };
-        const tensor_list d = CFConvForceDoubleBackwardFunction::apply(given(grads[0]), given(grads[1]), s[0], s[1], s[2],
-                                                                       ctx->saved_data["holder"].toCustomClass<Holder>(),
-                                                                       ctx->saved_data["neighbors"], ctx->saved_data["build"].toInt(),
-                                                                       ctx->saved_data["uploads"].toInt(), wants);
-        tensor_list out = {d[0], d[2], d[1]};
+        tensor_list out(12);
+        if (!grads[0].defined() && !grads[1].defined()) return out;
+        const auto s = ctx->get_saved_variables();           // {g, positions, input} and, with them, the four weights
+        const int64_t wants = s.size() > 3 ? wanted_weights(ctx, 3) : 0;
+        const auto given = [](const Tensor& t) { return t.defined() ? MaybeTensor(t) : MaybeTensor(); };
+        const tensor_list d = CFConvDoubleBackwardFunction::apply(given(grads[0]), given(grads[1]), s[0], s[1], s[2],
+                                                                  ctx->saved_data["holder"].toCustomClass<Holder>(),
+                                                                  ctx->saved_data["neighbors"], ctx->saved_data["build"].toInt(),
+                                                                  ctx->saved_data["uploads"].toInt(), wants);
+        out[0] = d[0]; out[1] = d[2]; out[2] = d[1];
         size_t next = 3;
-        for (int k = 0; k < 4; k++) out.push_back(wants >> k & 1 ? weight_grad_for(d[next++], s[3 + k]) : Tensor());
-        out.resize(12);
+        for (int k = 0; k < 4; k++)
+            if (wants >> k & 1) out[3 + k] = weight_grad_for(d[next++], s[3 + k]);
         return out;
     }
 };
 
-// (periodic: the box is an input only so that the op has operation_periodic_weights' schema; its slot stays empty)
-class CFConvForceFunction : public torch::autograd::Function<CFConvForceFunction> {
+// (periodic: the box is an input only so that the ops have the schemas of the first-order ones; its slot stays empty)
+class CFConvTwiceFunction : public torch::autograd::Function<CFConvTwiceFunction> {
 public:
     static Tensor forward(AutogradContext* ctx, const HolderPtr& holder, const c10::IValue& neighbors, const Tensor& positions,
-                          const c10::optional<Tensor>& box, const Tensor& input, const Tensor& weights1, const Tensor& biases1,
-                          const Tensor& weights2, const Tensor& biases2) {
-        holder->syncWeights(weights1, biases1, weights2, biases2);
-        const Tensor output = box ? holder->forwardPeriodic(neighbors, positions, *box, input) : holder->forward(neighbors, positions, input);
-        ctx->save_for_backward({positions, input, weights1, biases1, weights2, biases2});
+                          const MaybeTensor& box, const Tensor& input, const MaybeTensor& weights1, const MaybeTensor& biases1,
+                          const MaybeTensor& weights2, const MaybeTensor& biases2) {
+        const Tensor output = run_forward(holder, neighbors, positions, box, input, weights1, biases1, weights2, biases2);
+        tensor_list kept = {positions, input};
+        if (weights1) kept.insert(kept.end(), {*weights1, *biases1, *weights2, *biases2});
+        ctx->save_for_backward(kept);
         ctx->saved_data["holder"] = holder;
         ctx->saved_data["neighbors"] = neighbors;
         ctx->saved_data["build"] = neighbors.toCustomClass<Neighbors>()->getBuildCount();
-        ctx->saved_data["uploads"] = holder->getUploads();
+        ctx->saved_data["uploads"] = weights1 ? holder->getUploads() : (int64_t)-1;
         ctx->saved_data["periodic"] = box.has_value();
         return output;
     }
     static tensor_list backward(AutogradContext* ctx, tensor_list grads) {
-        const auto s = ctx->get_saved_variables();
+        const auto s = ctx->get_saved_variables();           // {positions, input} and, with them, the four weights
+        const bool weights = s.size() > 2;
         // (the node's edges count its tensor inputs only: positions, the box where there is one, input, four weights)
-        const size_t first_weight = ctx->saved_data["periodic"].toBool() ? 3 : 2;
-        int64_t wants = 0;
-        for (int k = 0; k < 4; k++) wants |= ctx->needs_input_grad(first_weight + k) ? (int64_t)1 << k : 0;
-        const tensor_list d = CFConvForceBackwardFunction::apply(grads[0], s[0], s[1], s[2], s[3], s[4], s[5],
-                                                                 ctx->saved_data["holder"].toCustomClass<Holder>(),
-                                                                 ctx->saved_data["neighbors"], ctx->saved_data["build"].toInt(),
-                                                                 ctx->saved_data["uploads"].toInt(), wants);
+        const int64_t wants = weights ? wanted_weights(ctx, ctx->saved_data["periodic"].toBool() ? 3 : 2) : 0;
+        const auto weight = [&](int k) { return weights ? MaybeTensor(s[2 + k]) : MaybeTensor(); };
+        const tensor_list d = CFConvBackwardFunction::apply(grads[0], s[0], s[1], weight(0), weight(1), weight(2), weight(3),
+                                                            ctx->saved_data["holder"].toCustomClass<Holder>(), ctx->saved_data["neighbors"],
+                                                            ctx->saved_data["build"].toInt(), ctx->saved_data["uploads"].toInt(), wants);
         tensor_list out = {Tensor(), Tensor(), d[1], Tensor(), d[0]};
+        out.resize(9);
         size_t next = 2;
-        for (int k = 0; k < 4; k++) out.push_back(wants >> k & 1 ? weight_grad_for(d[next++], s[2 + k]) : Tensor());
+        for (int k = 0; k < 4; k++)
+            if (wants >> k & 1) out[5 + k] = weight_grad_for(d[next++], s[2 + k]);
         return out;
     }
 };
 
+inline int64_t weight_wants(const Tensor& w1, const Tensor& b1, const Tensor& w2, const Tensor& b2) {
+    if (!torch::GradMode::is_enabled()) return 0;
+    return (w1.requires_grad() ? 1 : 0) | (b1.requires_grad() ? 2 : 0) | (w2.requires_grad() ? 4 : 0) | (b2.requires_grad() ? 8 : 0);
+}
+inline int64_t box_wants(const Tensor& box) { return torch::GradMode::is_enabled() && box.requires_grad() ? 16 : 0; }
+const MaybeTensor none;
+
+Tensor operation(const c10::optional<HolderPtr>& holder, const c10::IValue& neighbors, const Tensor& positions, const Tensor& input) {
+    return CFConvFunction::apply(*holder, neighbors, positions, none, input, none, none, none, none, (int64_t)0);
+}
+
+Tensor operation_periodic(const c10::optional<HolderPtr>& holder, const c10::IValue& neighbors, const Tensor& positions, const Tensor& box,
+                          const Tensor& input) {
+    return CFConvFunction::apply(*holder, neighbors, positions, MaybeTensor(box), input, none, none, none, none, box_wants(box));
+}
+
+Tensor operation_twice(const c10::optional<HolderPtr>& holder, const c10::IValue& neighbors, const Tensor& positions, const Tensor& input) {
+    return CFConvTwiceFunction::apply(*holder, neighbors, positions, none, input, none, none, none, none);
+}
+
+Tensor operation_periodic_twice(const c10::optional<HolderPtr>& holder, const c10::IValue& neighbors, const Tensor& positions,
+                                const Tensor& box, const Tensor& input) {
+    TORCH_CHECK(!box_wants(box),
+                "NNPOpsCFConv::operation_periodic_twice: box gradients need the default op (operation_periodic; CFConv without "
+                "twice_differentiable=True): the twice-differentiable ops return no box gradient");
+    return CFConvTwiceFunction::apply(*holder, neighbors, positions, MaybeTensor(box), input, none, none, none, none);
+}
+
+Tensor operation_weights(const c10::optional<HolderPtr>& holder, const c10::IValue& neighbors, const Tensor& positions, const Tensor& input,
+                         const Tensor& weights1, const Tensor& biases1, const Tensor& weights2, const Tensor& biases2) {
+    return CFConvFunction::apply(*holder, neighbors, positions, none, input, MaybeTensor(weights1), MaybeTensor(biases1), MaybeTensor(weights2),
+                                 MaybeTensor(biases2), weight_wants(weights1, biases1, weights2, biases2));
+}
+
+Tensor operation_periodic_weights(const c10::optional<HolderPtr>& holder, const c10::IValue& neighbors, const Tensor& positions,
+                                  const Tensor& box, const Tensor& input, const Tensor& weights1, const Tensor& biases1,
+                                  const Tensor& weights2, const Tensor& biases2) {
+    TORCH_CHECK(box.defined(), "NNPOpsCFConv::operation_periodic_weights: \"box\" is undefined");
+    return CFConvFunction::apply(*holder, neighbors, positions, MaybeTensor(box), input, MaybeTensor(weights1), MaybeTensor(biases1),
+                                 MaybeTensor(weights2), MaybeTensor(biases2), weight_wants(weights1, biases1, weights2, biases2) | box_wants(box));
+}
+
 Tensor operation_weights_twice(const c10::optional<HolderPtr>& holder, const c10::IValue& neighbors, const Tensor& positions,
                                const Tensor& input, const Tensor& weights1, const Tensor& biases1, const Tensor& weights2,
                                const Tensor& biases2) {
-    return CFConvForceFunction::apply(*holder, neighbors, positions, c10::optional<Tensor>(), input, weights1, biases1, weights2, biases2);
+    return CFConvTwiceFunction::apply(*holder, neighbors, positions, none, input, MaybeTensor(weights1), MaybeTensor(biases1),
+                                      MaybeTensor(weights2), MaybeTensor(biases2));
 }
 
 Tensor operation_periodic_weights_twice(const c10::optional<HolderPtr>& holder, const c10::IValue& neighbors, const Tensor& positions,
                                         const Tensor& box, const Tensor& input, const Tensor& weights1, const Tensor& biases1,
                                         const Tensor& weights2, const Tensor& biases2) {
     TORCH_CHECK(box.defined(), "NNPOpsCFConv::operation_periodic_weights_twice: \"box\" is undefined");
-    TORCH_CHECK(!(torch::GradMode::is_enabled() && box.requires_grad()),
+    TORCH_CHECK(!box_wants(box),
                 "NNPOpsCFConv::operation_periodic_weights_twice: box gradients need the default op or operation_periodic_weights (CFConv "
                 "without force_trainable=True): the twice-differentiable ops return no box gradient");
-    return CFConvForceFunction::apply(*holder, neighbors, positions, c10::optional<Tensor>(box), input, weights1, biases1, weights2, biases2);
+    return CFConvTwiceFunction::apply(*holder, neighbors, positions, MaybeTensor(box), input, MaybeTensor(weights1), MaybeTensor(biases1),
+                                      MaybeTensor(weights2), MaybeTensor(biases2));
 }
 
 TORCH_LIBRARY(NNPOpsCFConv, m) {

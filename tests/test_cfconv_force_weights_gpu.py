@@ -365,7 +365,7 @@ def test_a_force_evaluation_alone_leaves_the_parameters_alone_and_its_loss_reach
     nb = _neighbors(tpos.detach(), None, cutoff)
     F, = torch.autograd.grad(conv(nb, tpos, _dev(x)).sum(), tpos, create_graph=True)
     node = F.grad_fn
-    assert "CFConvForceBackwardFunction" in type(node).__name__ or "CFConvForceBackwardFunction" in node.name()
+    assert "CFConvBackwardFunction" in type(node).__name__ or "CFConvBackwardFunction" in node.name()
     assert F.requires_grad and all(p.grad is None for p in conv.parameters())
     (F ** 2).sum().backward()
     assert all(p.grad is not None and bool(p.grad.any()) for p in conv.parameters())

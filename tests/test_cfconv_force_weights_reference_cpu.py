@@ -114,6 +114,30 @@ def test_both_ops_are_registered():
         assert schema.replace(name, old) == theirs                        # the schema of the first-order op
 
 
+HOLDER = "__torch__.torch.classes.NNPOpsCFConv.Holder? _0, Any _1"
+SCHEMAS = [        # the eight ops as scripted modules saved before the nodes behind them were merged know them
+    f"NNPOpsCFConv::operation({HOLDER}, Tensor _2, Tensor _3) -> Tensor _0",
+    f"NNPOpsCFConv::operation_periodic({HOLDER}, Tensor _2, Tensor _3, Tensor _4) -> Tensor _0",
+    f"NNPOpsCFConv::operation_twice({HOLDER}, Tensor _2, Tensor _3) -> Tensor _0",
+    f"NNPOpsCFConv::operation_periodic_twice({HOLDER}, Tensor _2, Tensor _3, Tensor _4) -> Tensor _0",
+    f"NNPOpsCFConv::operation_weights({HOLDER}, Tensor _2, Tensor _3, Tensor _4, Tensor _5, Tensor _6, Tensor _7) -> Tensor _0",
+    f"NNPOpsCFConv::operation_periodic_weights({HOLDER}, Tensor _2, Tensor _3, Tensor _4, Tensor _5, Tensor _6, Tensor _7, Tensor _8) -> Tensor _0",
+    f"NNPOpsCFConv::operation_weights_twice({HOLDER}, Tensor _2, Tensor _3, Tensor _4, Tensor _5, Tensor _6, Tensor _7) -> Tensor _0",
+    f"NNPOpsCFConv::operation_periodic_weights_twice({HOLDER}, Tensor _2, Tensor _3, Tensor _4, Tensor _5, Tensor _6, Tensor _7, Tensor _8) "
+    "-> Tensor _0",
+]
+
+
+def test_all_eight_schemas_are_the_recorded_ones():
+    from nnpops_amd import torch_binding
+    torch_binding.load()
+    for want in SCHEMAS:
+        name = want[len("NNPOpsCFConv::"):want.index("(")]
+        assert str(getattr(torch.ops.NNPOpsCFConv, name).default._schema) == want
+    registered = [str(s) for s in torch._C._jit_get_all_schemas() if s.name.startswith("NNPOpsCFConv::")]
+    assert sorted(registered) == sorted(SCHEMAS)                          # and no ninth
+
+
 def _module(**kw):
     from NNPOps.CFConv import CFConv
     G, W = 7, 5
