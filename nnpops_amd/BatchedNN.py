@@ -64,15 +64,19 @@ class _BatchedNN(nn.Module):
                 biases[0, iatom, imodel, :n_out, 0] = layer.bias.detach()
         return weights, biases
 
-    def forward(self, species_aev: Tuple[Tensor, Tensor]) -> SpeciesEnergies:
-        species, aev = species_aev
+    def _layers(self, aev: Tensor) -> Tensor:
+        """the four BatchedLinear layers: aev [mols, atoms, features] -> v [mols, atoms, models, out, 1]"""
         linear = torch.ops.NNPOpsBatchedNN.BatchedLinear
         # [mols, atoms, features] -> [mols, atoms, 1, features, 1]
         v = aev.unsqueeze(-2).unsqueeze(-1)
         v = F.celu(linear(v, self.layer0_weights, self.layer0_biases), alpha=0.1)
         v = F.celu(linear(v, self.layer2_weights, self.layer2_biases), alpha=0.1)
         v = F.celu(linear(v, self.layer4_weights, self.layer4_biases), alpha=0.1)
-        v = linear(v, self.layer6_weights, self.layer6_biases)
+        return linear(v, self.layer6_weights, self.layer6_biases)
+
+    def forward(self, species_aev: Tuple[Tensor, Tensor]) -> SpeciesEnergies:
+        species, aev = species_aev
+        v = self._layers(aev)
         # sum over atoms (and the padded dims) and mean over models in ONE reduction, as the reference does
         energies = torch.sum(v, (1, 2, 3, 4)) / v.shape[2]
         return SpeciesEnergies(species, energies)
@@ -81,13 +85,7 @@ class _BatchedNN(nn.Module):
     def members_energies(self, species_aev: Tuple[Tensor, Tensor]) -> SpeciesEnergies:
         """The same reduction without the sum over the models: energies [models, molecules] (TorchANI's ``members_energies``)."""
         species, aev = species_aev
-        linear = torch.ops.NNPOpsBatchedNN.BatchedLinear
-        v = aev.unsqueeze(-2).unsqueeze(-1)
-        v = F.celu(linear(v, self.layer0_weights, self.layer0_biases), alpha=0.1)
-        v = F.celu(linear(v, self.layer2_weights, self.layer2_biases), alpha=0.1)
-        v = F.celu(linear(v, self.layer4_weights, self.layer4_biases), alpha=0.1)
-        v = linear(v, self.layer6_weights, self.layer6_biases)
-        return SpeciesEnergies(species, torch.sum(v, (1, 3, 4)).t())
+        return SpeciesEnergies(species, torch.sum(self._layers(aev), (1, 3, 4)).t())
 
 
 class _SpeciesGroupedNN(nn.Module):
@@ -134,6 +132,17 @@ class _SpeciesGroupedNN(nn.Module):
     def forward(self, species_aev: Tuple[Tensor, Tensor]) -> SpeciesEnergies:
         return self._grouped_forward(species_aev)
 
+    def _kind_outputs(self, kind: int, xs: Tensor) -> Tensor:
+        """The four layers of one species: xs [features, cols] -> v [models, out, cols] (padded outputs are exactly zero)."""
+        cols = xs.shape[1]
+        # layer 0: every model reads the same AEVs -> ONE GEMM [models*out, features] x [features, cols]
+        w0, b0 = self.layer0_weights[kind], self.layer0_biases[kind]
+        v = torch.addmm(b0.reshape(-1, 1), w0.reshape(-1, w0.shape[2]), xs).reshape(w0.shape[0], w0.shape[1], cols)
+        v = F.celu(v, alpha=0.1)                                         # [models, out, cols]
+        v = F.celu(torch.baddbmm(self.layer2_biases[kind].expand(-1, -1, cols), self.layer2_weights[kind], v), alpha=0.1)
+        v = F.celu(torch.baddbmm(self.layer4_biases[kind].expand(-1, -1, cols), self.layer4_weights[kind], v), alpha=0.1)
+        return torch.baddbmm(self.layer6_biases[kind].expand(-1, -1, cols), self.layer6_weights[kind], v)
+
     @torch.jit.unused
     def members_energies(self, species_aev: Tuple[Tensor, Tensor]) -> SpeciesEnergies:
         """Every model's energy, energies [models, molecules] (TorchANI's ``members_energies``): plain torch, twice differentiable."""
@@ -143,16 +152,9 @@ class _SpeciesGroupedNN(nn.Module):
         num_models = self.layer0_weights.shape[1]
         energies = torch.zeros((num_models, mols), dtype=aev.dtype, device=aev.device)
         first = 0
-        for kind, n in enumerate(self.group_sizes):                         # (the layers of _grouped_forward; the models are kept apart)
-            xs = x[:, first:first + n].reshape(mols * n, -1).t()
+        for kind, n in enumerate(self.group_sizes):                         # (the models are kept apart)
+            v = self._kind_outputs(kind, x[:, first:first + n].reshape(mols * n, -1).t())
             first += n
-            cols = mols * n
-            w0, b0 = self.layer0_weights[kind], self.layer0_biases[kind]
-            v = torch.addmm(b0.reshape(-1, 1), w0.reshape(-1, w0.shape[2]), xs).reshape(num_models, w0.shape[1], cols)
-            v = F.celu(v, alpha=0.1)
-            v = F.celu(torch.baddbmm(self.layer2_biases[kind].expand(-1, -1, cols), self.layer2_weights[kind], v), alpha=0.1)
-            v = F.celu(torch.baddbmm(self.layer4_biases[kind].expand(-1, -1, cols), self.layer4_weights[kind], v), alpha=0.1)
-            v = torch.baddbmm(self.layer6_biases[kind].expand(-1, -1, cols), self.layer6_weights[kind], v)
             energies = energies + v.reshape(num_models, -1, mols, n).sum((1, 3))
         return SpeciesEnergies(species, energies)
 
@@ -164,16 +166,8 @@ class _SpeciesGroupedNN(nn.Module):
         energies = torch.zeros(mols, dtype=aev.dtype, device=aev.device)
         first = 0
         for kind, n in enumerate(self.group_sizes):
-            xs = x[:, first:first + n].reshape(mols * n, -1).t()            # [features, mols * n]
+            v = self._kind_outputs(kind, x[:, first:first + n].reshape(mols * n, -1).t())     # xs [features, mols * n]
             first += n
-            cols = mols * n
-            # layer 0: every model reads the same AEVs -> ONE GEMM [models*out, features] x [features, cols]
-            w0, b0 = self.layer0_weights[kind], self.layer0_biases[kind]
-            v = torch.addmm(b0.reshape(-1, 1), w0.reshape(-1, w0.shape[2]), xs).reshape(num_models, w0.shape[1], cols)
-            v = F.celu(v, alpha=0.1)                                         # [models, out, cols]
-            v = F.celu(torch.baddbmm(self.layer2_biases[kind].expand(-1, -1, cols), self.layer2_weights[kind], v), alpha=0.1)
-            v = F.celu(torch.baddbmm(self.layer4_biases[kind].expand(-1, -1, cols), self.layer4_weights[kind], v), alpha=0.1)
-            v = torch.baddbmm(self.layer6_biases[kind].expand(-1, -1, cols), self.layer6_weights[kind], v)
             energies = energies + v.reshape(-1, mols, n).sum((0, 2))        # padded outputs are exactly zero
         return SpeciesEnergies(species, energies / num_models)
 
@@ -208,6 +202,66 @@ def _pack_fragments(w: Tensor, permute: bool) -> Tensor:
 
 def _up32(v: int) -> int:
     return (v + 31) // 32 * 32
+
+
+def _takes_packed_path(aev: Tensor, planes: Tensor, order32: Tensor, fused_ok: bool, live_blocks: int = 0) -> bool:
+    """Whether a module call goes to the kernels on its packed operands: one molecule on the device in float32, the planes and the
+    atom order in the kernels' types (a ``.double()`` or ``.half()`` of the module has not touched them), the weights inside the
+    activation bound.  ``live_blocks``: how many live column blocks stand in the way (members_energies: only the positions of
+    OptimizedTorchANI vouch for them)."""
+    return (aev.shape[0] == 1 and aev.is_cuda and aev.dtype == torch.float32 and planes.dtype == torch.float16
+            and order32.dtype == torch.int32 and fused_ok and live_blocks == 0)
+
+
+def _operand_bounds(weights: Tuple[Tensor, Tensor, Tensor, Tensor], biases: Tuple[Tensor, Tensor, Tensor]) -> Tuple[Tensor, Tensor]:
+    """Crude bounds of what the kernels split into fp16, from the weights alone (AEV entries are sums of at most a few dozen terms
+    <= 1): ``bound`` for the activations of the forward pass, ``back`` for the operands of the backward pass, which take the same
+    planes: |d3| <= |w6|, |d2| <= |d3| ||W4||_1, |d1| <= |d2| ||W2||_1 (CELU' <= 1).  One-element tensors on the arrays' device."""
+    w0, w2, w4, w6 = weights
+    bound = torch.full((1,), 64.0, device=w0.device)
+    for w, b in zip((w0, w2, w4), biases):
+        bound = (w.abs().sum(-1).amax() * bound + b.abs().amax()).reshape(1)
+    back = w6.abs().amax().reshape(1)
+    for w in (w4, w2):
+        back = (w.abs().sum(-2).amax() * back).reshape(1)
+    return bound, back
+
+
+def _activation_scale(worst: float) -> Tuple[int, bool]:
+    """The kernels scale every activation by 2^-k before the fp16 split, k = ``act_scale_log2`` of the ops: the smallest k >= 4 whose
+    bound 62 500 * 2^k (fp16's largest number, with margin) holds ``worst``; 4 for networks of ordinary size, up to 12 (bounds below
+    2.56e8).  -> (k, whether it holds: beyond, the weights are left to the library-GEMM path)."""
+    k = 4
+    while k < 12 and worst >= 62500.0 * 2.0 ** k:
+        k += 1
+    return k, worst < 62500.0 * 2.0 ** k
+
+
+def _cut(t: Tensor, rows: int, cols: int) -> Tensor:
+    """[M, out, in] -> [M, rows, cols], zero padded / trimmed"""
+    out = torch.zeros((t.shape[0], rows, cols), dtype=torch.float32, device=t.device)
+    r, c = min(rows, t.shape[1]), min(cols, t.shape[2])
+    out[:, :r, :c] = t[:, :r, :c]
+    return out
+
+
+def _kind_fragments(w0: Tensor, w2: Tensor, w4: Tensor, h1: int, h2: int, h3: int, columns: Optional[Tensor], with_w0tm: bool) -> List[Tensor]:
+    """The planes of one kind at the packed widths h1, h2, h3, from its arrays [M, out, in], over all columns of the first layer
+    or over ``columns`` of it: w0 (M members) | w2 (M) | w4 (M) | w4t (M) | w2t (M) | w0t [| w0tm (M)]."""
+    M = w0.shape[0]
+    if columns is not None:
+        w0 = w0[:, :, columns]
+    F = int(w0.shape[2])
+    k0, k2, k4 = _cut(w0, h1, F), _cut(w2, h2, h1), _cut(w4, h3, h2)
+    planes = [_pack_fragments(k0[m], False) for m in range(M)]
+    planes += [_pack_fragments(k2[m], True) for m in range(M)]
+    planes += [_pack_fragments(k4[m], True) for m in range(M)]
+    planes += [_pack_fragments(k4[m].t(), True) for m in range(M)]
+    planes += [_pack_fragments(k2[m].t(), True) for m in range(M)]
+    planes.append(_pack_fragments(k0.reshape(M * h1, F).t(), True))
+    if with_w0tm:
+        planes += [_pack_fragments(k0[m].t(), True) for m in range(M)]
+    return planes
 
 
 class _FusedSpeciesNN(_SpeciesGroupedNN):
@@ -270,47 +324,19 @@ class _FusedSpeciesNN(_SpeciesGroupedNN):
             h1, h2, h3 = self._true_width(w0[k], b0[k]), self._true_width(w2[k], b2[k]), self._true_width(w4[k], b4[k])
             h1, h2, h3 = min(h1, _up32(w0.shape[2])), min(h2, _up32(w2.shape[2])), min(h3, _up32(w4.shape[2]))
             widths += [h1, h2, h3]
-
-            def cut(t: Tensor, rows: int, cols: int) -> Tensor:          # [M, out, in] -> [M, rows, cols], zero padded / trimmed
-                out = torch.zeros((M, rows, cols), dtype=torch.float32, device=t.device)
-                r, c = min(rows, t.shape[1]), min(cols, t.shape[2])
-                out[:, :r, :c] = t[:, :r, :c]
-                return out
-            k0, k2, k4 = cut(w0[k], h1, F), cut(w2[k], h2, h1), cut(w4[k], h3, h2)
-            planes += [_pack_fragments(k0[m], False) for m in range(M)]
-            planes += [_pack_fragments(k2[m], True) for m in range(M)]
-            planes += [_pack_fragments(k4[m], True) for m in range(M)]
-            planes += [_pack_fragments(k4[m].t(), True) for m in range(M)]
-            planes += [_pack_fragments(k2[m].t(), True) for m in range(M)]
-            planes.append(_pack_fragments(k0.reshape(M * h1, F).t(), True))
-            floats += [cut(b0[k], h1, 1).reshape(-1), cut(b2[k], h2, 1).reshape(-1), cut(b4[k], h3, 1).reshape(-1),
-                       cut(w6[k][:, 0:1, :].transpose(1, 2), h3, 1).reshape(-1), b6[k].reshape(M, -1)[:, 0].reshape(-1)]
+            planes += _kind_fragments(w0[k], w2[k], w4[k], h1, h2, h3, None, False)
+            floats += [_cut(b0[k], h1, 1).reshape(-1), _cut(b2[k], h2, 1).reshape(-1), _cut(b4[k], h3, 1).reshape(-1),
+                       _cut(w6[k][:, 0:1, :].transpose(1, 2), h3, 1).reshape(-1), b6[k].reshape(M, -1)[:, 0].reshape(-1)]
         self.mlp_planes = torch.cat(planes).contiguous()
         self.mlp_floats = torch.cat(floats).contiguous()
         self.widths = widths
-        # the same networks over the live column blocks of the AEV only (set_live_blocks): w0 | w2 | w4 | w4t | w2t | w0t [| w0tm]
+        # the same networks over the live column blocks of the AEV only (set_live_blocks); at most 256 columns carry w0tm as well
         dev = w0.device
         if self.live_blocks:
             cols = torch.tensor([16 * g + c for g in self.live_blocks for c in range(16)], dtype=torch.long, device=dev)
-            Fl = int(cols.numel())
             live = []
             for k in range(kinds):
-                h1, h2, h3 = widths[3 * k], widths[3 * k + 1], widths[3 * k + 2]
-
-                def cut(t: Tensor, rows: int, ncols: int) -> Tensor:
-                    out = torch.zeros((M, rows, ncols), dtype=torch.float32, device=t.device)
-                    r, c = min(rows, t.shape[1]), min(ncols, t.shape[2])
-                    out[:, :r, :c] = t[:, :r, :c]
-                    return out
-                k0, k2, k4 = cut(w0[k][:, :, cols], h1, Fl), cut(w2[k], h2, h1), cut(w4[k], h3, h2)
-                live += [_pack_fragments(k0[m], False) for m in range(M)]
-                live += [_pack_fragments(k2[m], True) for m in range(M)]
-                live += [_pack_fragments(k4[m], True) for m in range(M)]
-                live += [_pack_fragments(k4[m].t(), True) for m in range(M)]
-                live += [_pack_fragments(k2[m].t(), True) for m in range(M)]
-                live.append(_pack_fragments(k0.reshape(M * h1, Fl).t(), True))
-                if Fl <= 256:
-                    live += [_pack_fragments(k0[m].t(), True) for m in range(M)]
+                live += _kind_fragments(w0[k], w2[k], w4[k], widths[3 * k], widths[3 * k + 1], widths[3 * k + 2], cols, int(cols.numel()) <= 256)
             self.live_planes = torch.cat(live).contiguous()
             self.x_blocks = torch.tensor(self.live_blocks, dtype=torch.int32, device=dev)
             self.dead_blocks = torch.tensor([g for g in range(F // 16) if g not in set(self.live_blocks)], dtype=torch.int32, device=dev)
@@ -318,40 +344,48 @@ class _FusedSpeciesNN(_SpeciesGroupedNN):
             self.live_planes = torch.empty(0, device=dev)
             self.x_blocks = torch.empty(0, dtype=torch.int32, device=dev)
             self.dead_blocks = torch.empty(0, dtype=torch.int32, device=dev)
-        # the kernels scale every activation by a power of two before the fp16 split (1/16: activations below ~1e6).  A crude
-        # bound from the weights (AEV entries are sums of at most a few dozen terms <= 1) decides; networks that could
-        # exceed it keep the library-GEMM path.  The backward operands take the same planes: |d3| <= |w6|,
-        # |d2| <= |d3| ||W4||_1, |d1| <= |d2| ||W2||_1 (CELU' <= 1).
-        bound = torch.full((1,), 64.0, device=w0.device)
-        for w, b in ((w0, b0), (w2, b2), (w4, b4)):
-            bound = (w.abs().sum(-1).amax() * bound + b.abs().amax()).reshape(1)
-        back = w6.abs().amax().reshape(1)
-        for w in (w4, w2):
-            back = (w.abs().sum(-2).amax() * back).reshape(1)
-        # The scale is 2^-k, k = act_scale_log2 of the ops: the smallest k >= 4 whose bound 62 500 * 2^k (fp16's largest
-        # number, with margin) holds the crude bounds; 4 for networks of ordinary size, up to 12 (bounds below 2.56e8)
-        # before the weights are left to the library-GEMM path.
+        # the activation scale from the crude bounds of the weights; networks beyond every scale keep the library-GEMM path
+        bound, back = _operand_bounds((w0, w2, w4, w6), (b0, b2, b4))
         worst = max(float(bound), float(back)) if bool(torch.isfinite(bound).all()) and bool(torch.isfinite(back).all()) else float("inf")
-        k = 4
-        while k < 12 and worst >= 62500.0 * 2.0 ** k:
-            k += 1
-        self.act_scale_log2 = k
-        self.fused_ok = (worst < 62500.0 * 2.0 ** k
-                         and F % 8 == 0 and F <= 1024 and max(widths) <= 256 and kinds <= 8 and int(w6.shape[2]) == 1)
-        holder = getattr(self, 'holder', None)         # (the one-node step keeps dE/dAEV between the steps, cleared once for ONE list of
-        if holder is not None:                         #  live blocks: torch_binding.cpp, Holder::gradCache)
+        self.act_scale_log2, holds = _activation_scale(worst)
+        self.fused_ok = holds and F % 8 == 0 and F <= 1024 and max(widths) <= 256 and kinds <= 8 and int(w6.shape[2]) == 1
+        self._reset_gradient_caches()
+
+    @torch.jit.unused
+    def _reset_gradient_caches(self) -> None:
+        """new planes: the one-node step keeps dE/dAEV between the steps, cleared once for ONE list of live blocks
+        (torch_binding.cpp, Holder::gradCache), and so does every batched holder"""
+        holder = getattr(self, 'holder', None)
+        if holder is not None:
             holder.reset_gradient_cache()
-        for plan in self._batch_plans.values():        # (... and so does every batched holder)
+        for plan in self._batch_plans.values():
             plan[0].reset_gradient_cache()
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
         super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
         self._refresh_planes()
 
+    def _require_fused(self, training: bool = False) -> None:
+        """the steps that have no other path refuse weights beyond the activation bound (a state dict loaded since construction, an
+        optimizer step: the weights no longer bound the fp16 operands)"""
+        if self.fused_ok:
+            return
+        if training:
+            raise RuntimeError("the weights exceed the activation bound of the fused network kernels (BatchedNN.py: fused_ok); "
+                               "train with nn_layout='grouped'")
+        raise RuntimeError("the loaded weights exceed the activation bound of the fused network kernels (BatchedNN.py: fused_ok); "
+                           "build the model with OptimizedTorchANI(..., fused_step=False) or nn_layout='grouped'")
+
+    def _operands(self, all_columns: bool = False) -> Tuple[Tensor, Optional[Tensor], Optional[Tensor]]:
+        """(planes, x_blocks, dead_blocks) of an op call: the networks packed over the live column blocks and the two block lists when
+        there are live blocks (set_live_blocks), else -- or with ``all_columns`` -- the planes over all columns and no lists"""
+        if self.x_blocks.numel() > 0 and not all_columns:
+            return self.live_planes, self.x_blocks, self.dead_blocks
+        return self.mlp_planes, None, None
+
     def forward(self, species_aev: Tuple[Tensor, Tensor]) -> SpeciesEnergies:
         species, aev = species_aev
-        if (aev.shape[0] != 1 or not aev.is_cuda or aev.dtype != torch.float32 or self.mlp_planes.dtype != torch.float16
-                or self.atom_order32.dtype != torch.int32 or not self.fused_ok):
+        if not _takes_packed_path(aev, self.mlp_planes, self.atom_order32, self.fused_ok):
             return self._grouped_forward(species_aev)
         total = torch.ops.NNPOpsBatchedNN.FusedMLP(aev[0].contiguous(), self.atom_order32, self.group_sizes, self.widths, self.num_models,
                                                    self.mlp_planes, self.mlp_floats, self.act_scale_log2)
@@ -364,22 +398,17 @@ class _FusedSpeciesNN(_SpeciesGroupedNN):
         backward is one launch of the networks' input gradient weighted by the upstream gradient of every (molecule, member); a
         zero there skips the member.  ``batch``: (rows, group sizes, places, offsets) of a conformer batch (``_batch_plan``).  Inside
         OptimizedTorchANI the networks run over the live column blocks, as in ``fused_energy``."""
-        if not self.fused_ok:        # (a state dict loaded since construction: the weights no longer bound the fp16 operands)
-            raise RuntimeError("the loaded weights exceed the activation bound of the fused network kernels (BatchedNN.py: fused_ok); "
-                               "build the model with OptimizedTorchANI(..., fused_step=False) or nn_layout='grouped'")
+        self._require_fused()
         rows, sizes, places, offsets = batch if batch is not None else (self.atom_order32, self.group_sizes, None, None)
-        if self.x_blocks.numel() > 0:
-            return torch.ops.NNPOpsBatchedNN.FusedMLPMembers(aev, rows, sizes, self.widths, self.num_models, self.live_planes, self.mlp_floats,
-                                                             self.x_blocks, self.dead_blocks, self.act_scale_log2, offsets, places, shift)
-        return torch.ops.NNPOpsBatchedNN.FusedMLPMembers(aev, rows, sizes, self.widths, self.num_models, self.mlp_planes, self.mlp_floats,
-                                                         None, None, self.act_scale_log2, offsets, places, shift)
+        planes, x_blocks, dead_blocks = self._operands()
+        return torch.ops.NNPOpsBatchedNN.FusedMLPMembers(aev, rows, sizes, self.widths, self.num_models, planes, self.mlp_floats,
+                                                         x_blocks, dead_blocks, self.act_scale_log2, offsets, places, shift)
 
     @torch.jit.unused
     def members_energies(self, species_aev: Tuple[Tensor, Tensor]) -> SpeciesEnergies:
         species, aev = species_aev
-        if (aev.shape[0] != 1 or not aev.is_cuda or aev.dtype != torch.float32 or self.mlp_planes.dtype != torch.float16
-                or self.atom_order32.dtype != torch.int32 or not self.fused_ok or self.x_blocks.numel() > 0):
-            return _SpeciesGroupedNN.members_energies(self, species_aev)    # (live blocks: only the positions of OptimizedTorchANI vouch for them)
+        if not _takes_packed_path(aev, self.mlp_planes, self.atom_order32, self.fused_ok, int(self.x_blocks.numel())):
+            return _SpeciesGroupedNN.members_energies(self, species_aev)
         return SpeciesEnergies(species, self.fused_members(aev[0].contiguous()).t())
 
     def set_check_interval(self, interval: int) -> None:
@@ -390,27 +419,18 @@ class _FusedSpeciesNN(_SpeciesGroupedNN):
         """AEV + networks of the whole frame as one autograd node (only inside OptimizedTorchANI, which hands over the AEV
         holder): positions [N, 3] or [1, N, 3] -> ensemble-mean energy [1]; with ``shift`` (the molecule's self energy, one
         float64 on the device) the energy comes back in float64, shifted as the reference's EnergyShifter does it."""
-        if not self.fused_ok:        # (a state dict loaded since construction: the weights no longer bound the fp16 operands)
-            raise RuntimeError("the loaded weights exceed the activation bound of the fused network kernels (BatchedNN.py: fused_ok); "
-                               "build the model with OptimizedTorchANI(..., fused_step=False) or nn_layout='grouped'")
-        if self.x_blocks.numel() > 0:
-            return torch.ops.NNPOpsANISymmetryFunctions.energy(self.holder, positions, cell, self.atom_order32, self.group_sizes, self.widths,
-                                                               self.num_models, self.live_planes, self.mlp_floats, shift, self.x_blocks,
-                                                               self.dead_blocks, self.act_scale_log2)
+        self._require_fused()
+        planes, x_blocks, dead_blocks = self._operands()
         return torch.ops.NNPOpsANISymmetryFunctions.energy(self.holder, positions, cell, self.atom_order32, self.group_sizes, self.widths,
-                                                           self.num_models, self.mlp_planes, self.mlp_floats, shift, None, None, self.act_scale_log2)
+                                                           self.num_models, planes, self.mlp_floats, shift, x_blocks, dead_blocks, self.act_scale_log2)
 
     def fused_energy_forces(self, positions: Tensor, cell: Optional[Tensor], shift: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
         """The same step outside autograd: (energy [1], forces = -dE/dpositions in the shape of ``positions``) from one call."""
-        if not self.fused_ok:        # (a state dict loaded since construction: the weights no longer bound the fp16 operands)
-            raise RuntimeError("the loaded weights exceed the activation bound of the fused network kernels (BatchedNN.py: fused_ok); "
-                               "build the model with OptimizedTorchANI(..., fused_step=False) or nn_layout='grouped'")
-        if self.x_blocks.numel() > 0:
-            return torch.ops.NNPOpsANISymmetryFunctions.energy_forces(self.holder, positions, cell, self.atom_order32, self.group_sizes,
-                                                                      self.widths, self.num_models, self.live_planes, self.mlp_floats, shift,
-                                                                      self.x_blocks, self.dead_blocks, self.act_scale_log2)
+        self._require_fused()
+        planes, x_blocks, dead_blocks = self._operands()
         return torch.ops.NNPOpsANISymmetryFunctions.energy_forces(self.holder, positions, cell, self.atom_order32, self.group_sizes, self.widths,
-                                                                  self.num_models, self.mlp_planes, self.mlp_floats, shift, None, None, self.act_scale_log2)
+                                                                  self.num_models, planes, self.mlp_floats, shift, x_blocks, dead_blocks,
+                                                                  self.act_scale_log2)
 
     @torch.jit.unused
     def _batch_plan(self, holder, batch: int, device: torch.device):
@@ -439,15 +459,11 @@ class _FusedSpeciesNN(_SpeciesGroupedNN):
 
     @torch.jit.unused
     def _batch_call(self, op, holder, positions: Tensor, shift: Optional[Tensor]):
-        if not self.fused_ok:        # (a state dict loaded since construction: the weights no longer bound the fp16 operands)
-            raise RuntimeError("the loaded weights exceed the activation bound of the fused network kernels (BatchedNN.py: fused_ok); "
-                               "build the model with OptimizedTorchANI(..., fused_step=False) or nn_layout='grouped'")
+        self._require_fused()
         holder, rows, sizes, places, offsets = self._batch_plan(holder, int(positions.shape[0]), positions.device)
-        if self.x_blocks.numel() > 0:
-            return op(holder, positions, None, rows, sizes, self.widths, self.num_models, self.live_planes, self.mlp_floats, offsets, places, shift,
-                      self.x_blocks, self.dead_blocks, self.act_scale_log2)
-        return op(holder, positions, None, rows, sizes, self.widths, self.num_models, self.mlp_planes, self.mlp_floats, offsets, places, shift,
-                  None, None, self.act_scale_log2)
+        planes, x_blocks, dead_blocks = self._operands()
+        return op(holder, positions, None, rows, sizes, self.widths, self.num_models, planes, self.mlp_floats, offsets, places, shift,
+                  x_blocks, dead_blocks, self.act_scale_log2)
 
     @torch.jit.unused
     def fused_energy_batch(self, holder, positions: Tensor, shift: Optional[Tensor] = None) -> Tensor:
@@ -553,27 +569,24 @@ class _TrainableFusedNN(_FusedSpeciesNN):
         shapes = [int(parameters[i].shape[2]) for i in (0, 2, 4)]
         kinds = int(parameters[0].shape[0])
         widths = [min(_up32(max(last[3 * k + layer], 1)), _up32(shapes[layer])) for k in range(kinds) for layer in range(3)]
-        if widths != self._fixed_widths:                   # (BEFORE anything is replaced, as on the host)
-            raise RuntimeError(f"the networks' widths changed from {self._fixed_widths} to {widths}: the structure of a trainable "
-                               "module is fixed at construction (the zero padding must stay zero)")
+        self._require_fixed_widths(widths)                 # (BEFORE anything is replaced, as on the host)
         rows, columns, biases, last_weight = scalars[0:3], scalars[3:5], scalars[5:8], scalars[8]
-        bound = 64.0                                       # (the bounds of _FusedSpeciesNN._refresh_planes, from the block's nine scalars)
+        bound = 64.0                                       # (the bounds of _operand_bounds, from the block's nine scalars)
         for row, bias in zip(rows, biases):
             bound = row * bound + bias
         back = last_weight * columns[0] * columns[1]
         worst = max(bound, back) if not not_finite and math.isfinite(bound) and math.isfinite(back) else float("inf")
-        k = 4
-        while k < 12 and worst >= 62500.0 * 2.0 ** k:
-            k += 1
         self.mlp_planes, self.mlp_floats, self.live_planes = planes, floats, live
-        self.act_scale_log2 = k
-        self.fused_ok = worst < 62500.0 * 2.0 ** k         # (the shape was checked before this route was taken)
-        holder = getattr(self, 'holder', None)
-        if holder is not None:
-            holder.reset_gradient_cache()
-        for plan in self._batch_plans.values():
-            plan[0].reset_gradient_cache()
+        self.act_scale_log2, self.fused_ok = _activation_scale(worst)     # (the shape was checked before this route was taken)
+        self._reset_gradient_caches()
         self.device_packs += 1
+
+    @torch.jit.unused
+    def _require_fixed_widths(self, widths: List[int]) -> None:
+        """a rebuild that would pack other widths than the constructor did is refused, and leaves the module as it was"""
+        if widths != self._fixed_widths:
+            raise RuntimeError(f"the networks' widths changed from {self._fixed_widths} to {widths}: the structure of a trainable "
+                               "module is fixed at construction (the zero padding must stay zero)")
 
     @torch.jit.unused
     def _refresh_planes(self) -> None:
@@ -581,11 +594,8 @@ class _TrainableFusedNN(_FusedSpeciesNN):
             if self._packs_on_device():
                 self._refresh_planes_on_device()
             else:
-                if self._fixed_widths is not None:         # (checked BEFORE anything is replaced: a refused structure leaves the module as it was)
-                    widths = self._packed_widths()
-                    if widths != self._fixed_widths:
-                        raise RuntimeError(f"the networks' widths changed from {self._fixed_widths} to {widths}: the structure of a trainable "
-                                           "module is fixed at construction (the zero padding must stay zero)")
+                if self._fixed_widths is not None:         # (checked BEFORE anything is replaced; none yet inside the base class's constructor)
+                    self._require_fixed_widths(self._packed_widths())
                 super()._refresh_planes()
                 self._blocks_packed = list(self.live_blocks)
         self.plane_rebuilds += 1
@@ -599,8 +609,7 @@ class _TrainableFusedNN(_FusedSpeciesNN):
     def forward(self, species_aev: Tuple[Tensor, Tensor]) -> SpeciesEnergies:
         species, aev = species_aev
         self._current_planes()
-        if (aev.shape[0] != 1 or not aev.is_cuda or aev.dtype != torch.float32 or self.mlp_planes.dtype != torch.float16
-                or self.atom_order32.dtype != torch.int32 or not self.fused_ok):
+        if not _takes_packed_path(aev, self.mlp_planes, self.atom_order32, self.fused_ok):
             return self._grouped_forward(species_aev)
         # (the default module's arithmetic, over all columns as there: the sum over atoms and members from the kernel, divided here)
         return SpeciesEnergies(species, self._trainable_op(aev[0].contiguous(), None, None, True, True, True) / self.num_models)
@@ -621,17 +630,11 @@ class _TrainableFusedNN(_FusedSpeciesNN):
     @torch.jit.unused
     def _trainable_op(self, aev: Tensor, shift: Optional[Tensor], batch: Optional[Tuple[Tensor, List[int], Tensor, Tensor]], mean: bool,
                       total: bool = False, all_columns: bool = False) -> Tensor:
-        if not self.fused_ok:
-            raise RuntimeError("the weights exceed the activation bound of the fused network kernels (BatchedNN.py: fused_ok); "
-                               "train with nn_layout='grouped'")
+        self._require_fused(training=True)
         rows, sizes, places, offsets = batch if batch is not None else (self.atom_order32, self.group_sizes, None, None)
-        parameters = [getattr(self, name) for name in PARAMETER_NAMES]
-        if self.x_blocks.numel() > 0 and not all_columns:
-            args = (aev, rows, sizes, self.widths, self.num_models, self.live_planes, self.mlp_floats, self.x_blocks, self.dead_blocks,
-                    self.act_scale_log2, offsets, places, shift, parameters)
-        else:
-            args = (aev, rows, sizes, self.widths, self.num_models, self.mlp_planes, self.mlp_floats, None, None, self.act_scale_log2, offsets, places,
-                    shift, parameters)
+        planes, x_blocks, dead_blocks = self._operands(all_columns)
+        args = (aev, rows, sizes, self.widths, self.num_models, planes, self.mlp_floats, x_blocks, dead_blocks, self.act_scale_log2, offsets, places,
+                shift, [getattr(self, name) for name in PARAMETER_NAMES])
         if mean:
             return torch.ops.NNPOpsBatchedNN.FusedMLPMeanTrainable(*args, total)
         return torch.ops.NNPOpsBatchedNN.FusedMLPMembersTrainable(*args)
@@ -640,8 +643,7 @@ class _TrainableFusedNN(_FusedSpeciesNN):
     def members_energies(self, species_aev: Tuple[Tensor, Tensor]) -> SpeciesEnergies:
         self._current_planes()
         species, aev = species_aev
-        if (aev.shape[0] != 1 or not aev.is_cuda or aev.dtype != torch.float32 or self.mlp_planes.dtype != torch.float16
-                or self.atom_order32.dtype != torch.int32 or not self.fused_ok or self.x_blocks.numel() > 0):
+        if not _takes_packed_path(aev, self.mlp_planes, self.atom_order32, self.fused_ok, int(self.x_blocks.numel())):
             return _SpeciesGroupedNN.members_energies(self, species_aev)
         return SpeciesEnergies(species, self._trainable_op(aev[0].contiguous(), None, None, False).t())
 
@@ -701,16 +703,9 @@ class _SplitGemmSpeciesNN(_SpeciesGroupedNN):
             last_b.append(float(self.layer6_biases[k].sum()))
         self.fwd_hi, self.fwd_lo = torch.cat(fwd_hi), torch.cat(fwd_lo)
         self.bwd_hi, self.bwd_lo = torch.cat(bwd_hi), torch.cat(bwd_lo)
-        # the split GEMM scales its A operand by 1/16 before the fp16 split: activations must stay below ~1e6.  A crude
-        # bound from the weights (AEV entries are sums of at most a few dozen terms <= 1) decides; networks that could
-        # exceed it keep the library-GEMM path.
-        bound = torch.full((1,), 64.0, device=w0.device)
-        for w, b in ((w0, self.layer0_biases), (w2, self.layer2_biases), (w4, self.layer4_biases)):
-            bound = (w.abs().sum(-1).amax() * bound + b.abs().amax()).reshape(1)
-        # the backward operands take the same planes: |d3| <= |w6|, |d2| <= |d3| ||W4||_1, |d1| <= |d2| ||W2||_1 (CELU' <= 1)
-        back = w6.abs().amax().reshape(1)
-        for w in (w4, w2):
-            back = (w.abs().sum(-2).amax() * back).reshape(1)
+        # the split GEMM scales its A operand by 1/16 before the fp16 split: activations must stay below ~1e6, in the forward pass
+        # and in the backward pass; networks that could exceed it keep the library-GEMM path.
+        bound, back = _operand_bounds((w0, w2, w4, w6), (self.layer0_biases, self.layer2_biases, self.layer4_biases))
         self.fused_ok = (bool(torch.isfinite(bound).all()) and float(bound) < 1.0e6
                          and bool(torch.isfinite(back).all()) and float(back) < 1.0e6)
         self.packed_biases = torch.cat(biases).float().contiguous()
@@ -723,8 +718,7 @@ class _SplitGemmSpeciesNN(_SpeciesGroupedNN):
 
     def forward(self, species_aev: Tuple[Tensor, Tensor]) -> SpeciesEnergies:
         species, aev = species_aev
-        if (aev.shape[0] != 1 or not aev.is_cuda or aev.dtype != torch.float32 or self.fwd_hi.dtype != torch.float16
-                or self.atom_order32.dtype != torch.int32 or not self.fused_ok):
+        if not _takes_packed_path(aev, self.fwd_hi, self.atom_order32, self.fused_ok):
             return self._grouped_forward(species_aev)
         # (the op reads the atoms of a species through atom_order32 and writes their gradients back through it: no gather
         #  into species order, no scatter back)

@@ -171,6 +171,49 @@ MlpCall mlp_prepare(const Tensor& x, const Tensor& rows, const std::vector<int64
     return c;
 }
 
+// where the next nnpops_mlp_input_grad of the frame writes, and the factor on it
+void mlp_point_gradient(nnpops_mlp_frame& fr, const Tensor& dx, float scale) {
+    fr.dx = dx.data_ptr<float>(); fr.lddx = (int)dx.size(1); fr.dx_scale = scale;
+}
+// the upstream gradient of every (molecule, member) -- weights [B, M], float32, contiguous -- as the weights of the frame's gradient
+// passes (nnpops_hip.h: member_weights), with the molecule offsets of a batch
+void mlp_point_upstream(nnpops_mlp_frame& fr, const Tensor& weights, const c10::optional<Tensor>& offsets) {
+    fr.member_weights = weights.data_ptr<float>(); fr.member_weights_ld = (int)weights.size(1);
+    if (offsets.has_value()) { fr.segment_offsets = offsets->data_ptr<int32_t>(); fr.num_segments = (int)weights.size(0); }
+}
+
+// `shift`, the self energy added in double precision: who ("energy():") asks, and on whose device ("the positions")
+void check_shift(const c10::optional<Tensor>& shift, const torch::Device& device, const char* who, const char* whose) {
+    if (shift.has_value())
+        TORCH_CHECK(shift->scalar_type() == torch::kFloat64 && shift->device() == device && shift->numel() == 1 && shift->is_contiguous(),
+                    who, " the self-energy shift must be one float64 on the device of ", whose);
+}
+
+// The reduction of a frame's per-atom energies [atoms][members] into `out`, one small launch: every member's sum over the atoms of a
+// molecule, out [B, M] (members); the ensemble mean of every molecule, out [B] (mean: the factor 1 / M); or the plain sum over atoms
+// and members (total: the factor 1).  offsets / places: the tables of a batch, or NULL for one molecule.  With `shift`, out is float64.
+enum class MlpReduce : int64_t { members = 0, mean = 1, total = 2 };
+
+void mlp_reduce(void* stream, const MlpCall& call, int64_t members, const Tensor* offsets, const Tensor* places, MlpReduce mode,
+                const c10::optional<Tensor>& shift, Tensor& out, const char* op) {
+    const float* e = call.energies.data_ptr<float>();
+    const int atoms = (int)call.energies.size(0), M = (int)members, count = (int)out.size(0);
+    const int32_t* off = offsets ? offsets->data_ptr<int32_t>() : nullptr;
+    const int32_t* plc = places ? places->data_ptr<int32_t>() : nullptr;
+    const float scale = mode == MlpReduce::total ? 1.0f : 1.0f / (float)members;
+    int rc;
+    if (mode == MlpReduce::members)
+        rc = shift.has_value() ? nnpops_mlp_member_sums_shifted(stream, e, atoms, M, off, count, plc, shift->data_ptr<double>(), out.data_ptr<double>())
+                               : nnpops_mlp_member_sums(stream, e, atoms, M, off, count, plc, out.data_ptr<float>());
+    else if (off)
+        rc = shift.has_value() ? nnpops_mlp_energy_mean_segments_shifted(stream, e, atoms, M, off, count, plc, scale, shift->data_ptr<double>(), out.data_ptr<double>())
+                               : nnpops_mlp_energy_mean_segments(stream, e, atoms, M, off, count, plc, scale, out.data_ptr<float>());
+    else
+        rc = shift.has_value() ? nnpops_mlp_energy_mean_shifted(stream, e, call.energies.numel(), scale, shift->data_ptr<double>(), out.data_ptr<double>())
+                               : nnpops_mlp_energy_mean(stream, e, call.energies.numel(), scale, out.data_ptr<float>());
+    if (rc != NNPOPS_OK) raise_last(op);
+}
+
 void require_device_tensor(const Tensor& t, const char* name) {
     if (!t.is_cuda())
         throw std::runtime_error(std::string("Unsupported device for \"") + name + "\": " + t.device().str() +
@@ -604,37 +647,19 @@ std::pair<Tensor, Tensor> energy_step(const HolderPtr& holder, const Tensor& fra
         // the ensemble mean (BatchedNN.py:109), shifted by the self energy when the caller hands it over: its own small launch,
         // or -- when the input gradient is only a sum over the members (dx_partial) -- a passenger of that launch
         const bool mean_rides = need_gradient && call.frame.dx_partial != nullptr;
-        if (shift.has_value()) {
-            TORCH_CHECK(shift->scalar_type() == torch::kFloat64 && shift->device() == aev.device() && shift->numel() == 1 && shift->is_contiguous(),
-                        "energy(): the self-energy shift must be one float64 on the device of the positions");
-            energy = torch::empty({count}, aev.options().dtype(torch::kFloat64));
-        } else {
-            energy = torch::empty({count}, aev.options());
-        }
-        const float mean_scale = 1.0f / (float)members;
+        check_shift(shift, aev.device(), "energy():", "the positions");
+        energy = torch::empty({count}, shift.has_value() ? aev.options().dtype(torch::kFloat64) : aev.options());
         if (mean_rides) {
-            call.frame.mean_scale = mean_scale;
+            call.frame.mean_scale = 1.0f / (float)members;
             if (shift.has_value()) { call.frame.mean_shift = shift->data_ptr<double>(); call.frame.mean_out_shifted = energy.data_ptr<double>(); }
             else call.frame.mean_out = energy.data_ptr<float>();
             if (batch) {
                 call.frame.segment_offsets = batch->offsets.data_ptr<int32_t>(); call.frame.segment_positions = batch->places.data_ptr<int32_t>();
                 call.frame.num_segments = (int)count;
             }
-        } else if (batch) {
-            const int rc = shift.has_value()
-                ? nnpops_mlp_energy_mean_segments_shifted(stream, call.energies.data_ptr<float>(), (int)call.energies.size(0), (int)members,
-                                                          batch->offsets.data_ptr<int32_t>(), (int)count, batch->places.data_ptr<int32_t>(),
-                                                          mean_scale, shift->data_ptr<double>(), energy.data_ptr<double>())
-                : nnpops_mlp_energy_mean_segments(stream, call.energies.data_ptr<float>(), (int)call.energies.size(0), (int)members,
-                                                  batch->offsets.data_ptr<int32_t>(), (int)count, batch->places.data_ptr<int32_t>(), mean_scale,
-                                                  energy.data_ptr<float>());
-            if (rc != NNPOPS_OK) raise_last("NNPOpsANISymmetryFunctions::energy_batch");
         } else {
-            const int rc = shift.has_value()
-                ? nnpops_mlp_energy_mean_shifted(stream, call.energies.data_ptr<float>(), call.energies.numel(), mean_scale,
-                                                 shift->data_ptr<double>(), energy.data_ptr<double>())
-                : nnpops_mlp_energy_mean(stream, call.energies.data_ptr<float>(), call.energies.numel(), mean_scale, energy.data_ptr<float>());
-            if (rc != NNPOPS_OK) raise_last("NNPOpsANISymmetryFunctions::energy");
+            mlp_reduce(stream, call, members, batch ? &batch->offsets : nullptr, batch ? &batch->places : nullptr, MlpReduce::mean, shift, energy,
+                       batch ? "NNPOpsANISymmetryFunctions::energy_batch" : "NNPOpsANISymmetryFunctions::energy");
         }
         if (need_gradient) {
             Tensor daev;
@@ -651,7 +676,7 @@ std::pair<Tensor, Tensor> energy_step(const HolderPtr& holder, const Tensor& fra
             } else {
                 daev = torch::empty_like(aev);
             }
-            call.frame.dx = daev.data_ptr<float>(); call.frame.lddx = (int)daev.size(1); call.frame.dx_scale = gradient_sign / (float)members;
+            mlp_point_gradient(call.frame, daev, gradient_sign / (float)members);
             if (nnpops_mlp_input_grad(stream, &call.frame) != NNPOPS_OK) raise_last("NNPOpsANISymmetryFunctions::energy");
             if (kept_cell != nullptr) {
                 TORCH_CHECK(cell.has_value(), "energy(): a gradient of the cell was requested without a cell");
@@ -3142,23 +3167,34 @@ Tensor GroupedMLP(const Tensor& x, const Tensor& order, std::vector<int64_t> gro
 // (BatchedNN.py:100-111 up to the division by the number of members).  When x requires a gradient the input-gradient pass
 // runs inside forward and backward is one multiplication (see EnergyFunction above).
 // =============================================================================================
+// how many gradient slots a node's backward returns: one for every argument of its forward behind the context
+template <class R, class... Args>
+constexpr size_t forward_arguments(R (*)(AutogradContext*, Args...)) { return sizeof...(Args); }
+
+// The input gradient of a prepared frame, one launch of nnpops_mlp_input_grad into a fresh tensor: dx_scale times the plain sum
+// over the members (the mean and total modes, FusedMLP's pass inside its forward), or -- with `upstream` [B, M], float32, contiguous --
+// every (molecule, member) weighted by its upstream gradient (the member energies).
+Tensor mlp_input_gradient(void* stream, MlpCall& call, const Tensor& x, float dx_scale, const Tensor* upstream, const c10::optional<Tensor>& offsets,
+                          const char* op) {
+    Tensor dx = torch::empty_like(x);
+    mlp_point_gradient(call.frame, dx, dx_scale);
+    if (upstream) mlp_point_upstream(call.frame, *upstream, offsets);
+    if (nnpops_mlp_input_grad(stream, &call.frame) != NNPOPS_OK) raise_last(op);
+    return dx;
+}
+
 class FusedMLPFunction : public torch::autograd::Function<FusedMLPFunction> {
 public:
     static Tensor forward(AutogradContext* ctx, const Tensor& x, const Tensor& rows, std::vector<int64_t> kind_atoms, std::vector<int64_t> widths,
                           int64_t members, const Tensor& planes, const Tensor& floats, bool need_gradient, int64_t act_scale_log2) {
+        const char* op = "NNPOpsBatchedNN::FusedMLP";
         c10::hip::HIPGuard guard(x.device().index());
         void* stream = current_stream(x.device());
         MlpCall call = mlp_prepare(x, rows, kind_atoms, widths, members, planes, floats, need_gradient, c10::nullopt, c10::nullopt, act_scale_log2);
-        if (nnpops_mlp_forward(stream, &call.frame, need_gradient ? 1 : 0) != NNPOPS_OK) raise_last("NNPOpsBatchedNN::FusedMLP");
+        if (nnpops_mlp_forward(stream, &call.frame, need_gradient ? 1 : 0) != NNPOPS_OK) raise_last(op);
         Tensor total = torch::empty({1}, x.options());
-        if (nnpops_mlp_energy_mean(stream, call.energies.data_ptr<float>(), call.energies.numel(), 1.0f, total.data_ptr<float>()) != NNPOPS_OK)
-            raise_last("NNPOpsBatchedNN::FusedMLP");
-        if (need_gradient) {
-            Tensor dx = torch::empty_like(x);
-            call.frame.dx = dx.data_ptr<float>(); call.frame.lddx = (int)dx.size(1); call.frame.dx_scale = 1.0f;
-            if (nnpops_mlp_input_grad(stream, &call.frame) != NNPOPS_OK) raise_last("NNPOpsBatchedNN::FusedMLP");
-            ctx->save_for_backward({dx});
-        }
+        mlp_reduce(stream, call, members, nullptr, nullptr, MlpReduce::total, c10::nullopt, total, op);
+        if (need_gradient) ctx->save_for_backward({mlp_input_gradient(stream, call, x, 1.0f, nullptr, c10::nullopt, op)});
         return total;
     }
     static tensor_list backward(AutogradContext* ctx, const tensor_list& grads) {
@@ -3166,7 +3202,9 @@ public:
                                                     "use layout='grouped' for that");
         const auto saved = ctx->get_saved_variables();
         TORCH_CHECK(!saved.empty(), "FusedMLP was evaluated without a gradient request");
-        return {saved[0] * grads[0], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+        tensor_list result(forward_arguments(&forward));
+        result[0] = saved[0] * grads[0];                      // x
+        return result;
     }
 };
 
@@ -3184,104 +3222,117 @@ Tensor FusedMLP(const Tensor& x, const Tensor& rows, std::vector<int64_t> kind_a
 // for the upstream gradient: backward takes grad [B, M] and runs the WEIGHTED nnpops_mlp_input_grad (nnpops_hip.h: member_weights),
 // one launch whatever the function of the member energies was.  No host synchronisation anywhere: the op can be captured.
 // =============================================================================================
+// What a members node keeps between its forward and its backward pass.  save() and load() are the only code that knows where a
+// piece lies in the context.
+struct MlpNodeState {
+    Tensor x, rows, planes, floats, energies;
+    std::vector<Tensor> workspace;    // what the forward's gradient half left: dx_partial alone, or dE/dy1 of every kind
+    bool in_forward;                  // ... which of the two
+    std::vector<int64_t> kind_atoms, widths;
+    int64_t members, act_scale_log2;
+    c10::optional<Tensor> x_blocks, dead_blocks, offsets;
+    MlpReduce mode;                   // (the trainable node: what its output was, and the eight parameters' [out, in])
+    std::vector<int64_t> parameter_shapes;
+
+    int64_t molecules() const { return offsets.has_value() ? offsets->numel() - 1 : 1; }
+
+    void save(AutogradContext* ctx) const {
+        tensor_list keep = {x, rows, planes, floats, energies};
+        keep.insert(keep.end(), workspace.begin(), workspace.end());
+        ctx->save_for_backward(keep);
+        auto& d = ctx->saved_data;
+        d["in_forward"] = in_forward; d["kind_atoms"] = kind_atoms; d["widths"] = widths; d["members"] = members;
+        d["act_scale_log2"] = act_scale_log2; d["x_blocks"] = x_blocks; d["dead_blocks"] = dead_blocks; d["offsets"] = offsets;
+        d["mean"] = (int64_t)mode; d["parameter_shapes"] = parameter_shapes;
+    }
+    static MlpNodeState load(AutogradContext* ctx, const char* name) {
+        const auto saved = ctx->get_saved_variables();
+        TORCH_CHECK(!saved.empty(), name, " was evaluated without a gradient request");
+        auto& d = ctx->saved_data;
+        return {saved[0], saved[1], saved[2], saved[3], saved[4], {saved.begin() + 5, saved.end()}, d["in_forward"].toBool(),
+                d["kind_atoms"].toIntVector(), d["widths"].toIntVector(), d["members"].toInt(), d["act_scale_log2"].toInt(),
+                d["x_blocks"].toOptional<Tensor>(), d["dead_blocks"].toOptional<Tensor>(), d["offsets"].toOptional<Tensor>(),
+                (MlpReduce)d["mean"].toInt(), d["parameter_shapes"].toIntVector()};
+    }
+};
+
+// the frame of a node's backward pass: the forward's frame again, its workspaces handed back (nothing is allocated, nothing launched)
+MlpCall prepare_backward(const MlpNodeState& s) {
+    MlpScratch own;
+    own.energies = s.energies;
+    if (s.in_forward) own.partial = s.workspace[0];
+    else own.d1 = s.workspace;
+    return mlp_prepare(s.x, s.rows, s.kind_atoms, s.widths, s.members, s.planes, s.floats, true, s.x_blocks, s.dead_blocks, s.act_scale_log2, &own);
+}
+
+// the slots of a members node's gradients, in the order of the arguments of FusedMLPMembersFunction::forward; the trainable node's
+// forward goes on with `mean` and the parameters (one slot each)
+namespace mlp_slot { enum : size_t { x, rows, kind_atoms, widths, members, planes, floats, x_blocks, dead_blocks, act_scale_log2, offsets, places, shift,
+                                     need_gradient, mean, parameters }; }
+
+// The forward pass of the members nodes.  mode (mean and total: FusedMLPMeanTrainable only): the member energies [B, M]; the ensemble
+// mean [B] of the one-node step (energy_step: the same launches on the same energies, hence its bits); the sum over atoms and members
+// as FusedMLP returns it.  What is kept for the backward pass is the same.
+Tensor mlp_members_forward(AutogradContext* ctx, const Tensor& x, const Tensor& rows, const std::vector<int64_t>& kind_atoms,
+                           const std::vector<int64_t>& widths, int64_t members, const Tensor& planes, const Tensor& floats,
+                           const c10::optional<Tensor>& x_blocks, const c10::optional<Tensor>& dead_blocks, int64_t act_scale_log2,
+                           const c10::optional<Tensor>& offsets, const c10::optional<Tensor>& places, const c10::optional<Tensor>& shift,
+                           bool need_gradient, MlpReduce mode, const std::vector<int64_t>& parameter_shapes) {
+    const char* op = "NNPOpsBatchedNN::FusedMLPMembers";
+    TORCH_CHECK(x.dim() == 2 && x.size(0) >= 1, "FusedMLPMembers: an empty batch (x must be [atoms, features] with at least one atom)");
+    TORCH_CHECK(offsets.has_value() == places.has_value(), "FusedMLPMembers: molecule offsets and row places come together");
+    int64_t B = 1;
+    if (offsets.has_value()) {
+        for (const Tensor* t : {&*offsets, &*places})
+            TORCH_CHECK(t->scalar_type() == torch::kInt32 && t->is_contiguous() && t->device() == x.device() && t->dim() == 1,
+                        "FusedMLPMembers: molecule offsets and row places must be contiguous int32 vectors on the device of x");
+        B = offsets->numel() - 1;
+        TORCH_CHECK(B >= 1, "FusedMLPMembers: an empty batch (", offsets->numel(), " molecule offsets)");
+        TORCH_CHECK(places->numel() == x.size(0), "FusedMLPMembers: ", x.size(0), " atoms need as many row places (got ", places->numel(), ")");
+    }
+    c10::hip::HIPGuard guard(x.device().index());
+    void* stream = current_stream(x.device());
+    MlpCall call = mlp_prepare(x, rows, kind_atoms, widths, members, planes, floats, need_gradient, x_blocks, dead_blocks, act_scale_log2);
+    if (nnpops_mlp_forward(stream, &call.frame, need_gradient ? 1 : 0) != NNPOPS_OK) raise_last(op);
+    check_shift(shift, x.device(), "FusedMLPMembers:", "x");
+    const auto options = shift.has_value() ? x.options().dtype(torch::kFloat64) : x.options();
+    Tensor out = mode == MlpReduce::members ? torch::empty({B, members}, options) : torch::empty({B}, options);
+    mlp_reduce(stream, call, members, offsets.has_value() ? &*offsets : nullptr, places.has_value() ? &*places : nullptr, mode, shift, out, op);
+    if (need_gradient)
+        MlpNodeState{x, rows, planes, floats, call.energies, call.keep, call.frame.dx_partial != nullptr, kind_atoms, widths, members, act_scale_log2,
+                     x_blocks, dead_blocks, offsets, mode, parameter_shapes}.save(ctx);
+    return out;
+}
+
+// the upstream gradient of the member energies as the weights of a gradient pass: [B, M], float32 or float64 -> float32, contiguous
+Tensor mlp_member_upstream(const Tensor& grad, const MlpNodeState& s) {
+    const int64_t B = s.molecules();
+    TORCH_CHECK(grad.defined() && grad.dim() == 2 && grad.size(0) == B && grad.size(1) == s.members && grad.device() == s.x.device() &&
+                (grad.scalar_type() == torch::kFloat32 || grad.scalar_type() == torch::kFloat64),
+                "FusedMLPMembers: unexpected gradient of the member energies (shape [", B, ", ", s.members, "] in float32 or float64 expected)");
+    return grad.to(torch::kFloat32).contiguous();
+}
+
 class FusedMLPMembersFunction : public torch::autograd::Function<FusedMLPMembersFunction> {
 public:
     static Tensor forward(AutogradContext* ctx, const Tensor& x, const Tensor& rows, std::vector<int64_t> kind_atoms, std::vector<int64_t> widths,
                           int64_t members, const Tensor& planes, const Tensor& floats, const c10::optional<Tensor>& x_blocks,
                           const c10::optional<Tensor>& dead_blocks, int64_t act_scale_log2, const c10::optional<Tensor>& offsets,
                           const c10::optional<Tensor>& places, const c10::optional<Tensor>& shift, bool need_gradient) {
-        return run(ctx, x, rows, kind_atoms, widths, members, planes, floats, x_blocks, dead_blocks, act_scale_log2, offsets, places, shift, need_gradient,
-                   0);
-    }
-    // mean (FusedMLPMeanTrainable only) 1: the ensemble mean [B] of the one-node step (energy_step: the same launches on the same
-    // energies, hence its bits) instead of the member energies [B, M]; 2: the sum over atoms and members as FusedMLP returns it.
-    // What is kept for the backward pass is the same
-    static Tensor run(AutogradContext* ctx, const Tensor& x, const Tensor& rows, const std::vector<int64_t>& kind_atoms,
-                      const std::vector<int64_t>& widths, int64_t members, const Tensor& planes, const Tensor& floats,
-                      const c10::optional<Tensor>& x_blocks, const c10::optional<Tensor>& dead_blocks, int64_t act_scale_log2,
-                      const c10::optional<Tensor>& offsets, const c10::optional<Tensor>& places, const c10::optional<Tensor>& shift,
-                      bool need_gradient, int64_t mean) {
-        const char* op = "NNPOpsBatchedNN::FusedMLPMembers";
-        TORCH_CHECK(x.dim() == 2 && x.size(0) >= 1, "FusedMLPMembers: an empty batch (x must be [atoms, features] with at least one atom)");
-        TORCH_CHECK(offsets.has_value() == places.has_value(), "FusedMLPMembers: molecule offsets and row places come together");
-        int64_t B = 1;
-        if (offsets.has_value()) {
-            for (const Tensor* t : {&*offsets, &*places})
-                TORCH_CHECK(t->scalar_type() == torch::kInt32 && t->is_contiguous() && t->device() == x.device() && t->dim() == 1,
-                            "FusedMLPMembers: molecule offsets and row places must be contiguous int32 vectors on the device of x");
-            B = offsets->numel() - 1;
-            TORCH_CHECK(B >= 1, "FusedMLPMembers: an empty batch (", offsets->numel(), " molecule offsets)");
-            TORCH_CHECK(places->numel() == x.size(0), "FusedMLPMembers: ", x.size(0), " atoms need as many row places (got ", places->numel(), ")");
-        }
-        c10::hip::HIPGuard guard(x.device().index());
-        void* stream = current_stream(x.device());
-        MlpCall call = mlp_prepare(x, rows, kind_atoms, widths, members, planes, floats, need_gradient, x_blocks, dead_blocks, act_scale_log2);
-        if (nnpops_mlp_forward(stream, &call.frame, need_gradient ? 1 : 0) != NNPOPS_OK) raise_last(op);
-        const int32_t* off = offsets.has_value() ? offsets->data_ptr<int32_t>() : nullptr;
-        const int32_t* plc = places.has_value() ? places->data_ptr<int32_t>() : nullptr;
-        Tensor out;
-        if (shift.has_value())
-            TORCH_CHECK(shift->scalar_type() == torch::kFloat64 && shift->device() == x.device() && shift->numel() == 1 && shift->is_contiguous(),
-                        "FusedMLPMembers: the self-energy shift must be one float64 on the device of x");
-        if (mean) {
-            const float scale = mean == 2 ? 1.0f : 1.0f / (float)members;
-            const float* e = call.energies.data_ptr<float>();
-            out = torch::empty({B}, shift.has_value() ? x.options().dtype(torch::kFloat64) : x.options());
-            int rc;
-            if (off) rc = shift.has_value()
-                ? nnpops_mlp_energy_mean_segments_shifted(stream, e, (int)x.size(0), (int)members, off, (int)B, plc, scale, shift->data_ptr<double>(), out.data_ptr<double>())
-                : nnpops_mlp_energy_mean_segments(stream, e, (int)x.size(0), (int)members, off, (int)B, plc, scale, out.data_ptr<float>());
-            else rc = shift.has_value()
-                ? nnpops_mlp_energy_mean_shifted(stream, e, call.energies.numel(), scale, shift->data_ptr<double>(), out.data_ptr<double>())
-                : nnpops_mlp_energy_mean(stream, e, call.energies.numel(), scale, out.data_ptr<float>());
-            if (rc != NNPOPS_OK) raise_last(op);
-        } else if (shift.has_value()) {
-            out = torch::empty({B, members}, x.options().dtype(torch::kFloat64));
-            if (nnpops_mlp_member_sums_shifted(stream, call.energies.data_ptr<float>(), (int)x.size(0), (int)members, off, (int)B, plc,
-                                               shift->data_ptr<double>(), out.data_ptr<double>()) != NNPOPS_OK) raise_last(op);
-        } else {
-            out = torch::empty({B, members}, x.options());
-            if (nnpops_mlp_member_sums(stream, call.energies.data_ptr<float>(), (int)x.size(0), (int)members, off, (int)B, plc,
-                                       out.data_ptr<float>()) != NNPOPS_OK) raise_last(op);
-        }
-        if (need_gradient) {
-            tensor_list keep = {x, rows, planes, floats, call.energies};
-            keep.insert(keep.end(), call.keep.begin(), call.keep.end());      // dx_partial, or dE/dy1 of every kind
-            ctx->save_for_backward(keep);
-            ctx->saved_data["in_forward"] = call.frame.dx_partial != nullptr;
-            ctx->saved_data["kind_atoms"] = kind_atoms; ctx->saved_data["widths"] = widths;
-            ctx->saved_data["members"] = members; ctx->saved_data["act_scale_log2"] = act_scale_log2;
-            ctx->saved_data["x_blocks"] = x_blocks; ctx->saved_data["dead_blocks"] = dead_blocks; ctx->saved_data["offsets"] = offsets;
-        }
-        return out;
+        return mlp_members_forward(ctx, x, rows, kind_atoms, widths, members, planes, floats, x_blocks, dead_blocks, act_scale_log2, offsets, places,
+                                   shift, need_gradient, MlpReduce::members, {});
     }
     static tensor_list backward(AutogradContext* ctx, const tensor_list& grads) {
         TORCH_CHECK(!torch::GradMode::is_enabled(), "NNPOpsBatchedNN::FusedMLPMembers: second derivatives are not implemented (create_graph=True); "
                                                     "use layout='grouped' for that");
-        const auto saved = ctx->get_saved_variables();
-        TORCH_CHECK(!saved.empty(), "FusedMLPMembers was evaluated without a gradient request");
-        const Tensor &x = saved[0], &rows = saved[1], &planes = saved[2], &floats = saved[3];
-        const int64_t members = ctx->saved_data["members"].toInt();
-        const c10::optional<Tensor> x_blocks = ctx->saved_data["x_blocks"].toOptional<Tensor>(), dead_blocks = ctx->saved_data["dead_blocks"].toOptional<Tensor>(),
-                                    offsets = ctx->saved_data["offsets"].toOptional<Tensor>();
-        const int64_t B = offsets.has_value() ? offsets->numel() - 1 : 1;
-        TORCH_CHECK(grads[0].defined() && grads[0].dim() == 2 && grads[0].size(0) == B && grads[0].size(1) == members && grads[0].device() == x.device() &&
-                    (grads[0].scalar_type() == torch::kFloat32 || grads[0].scalar_type() == torch::kFloat64),
-                    "FusedMLPMembers: unexpected gradient of the member energies (shape [", B, ", ", members, "] in float32 or float64 expected)");
-        const Tensor g = grads[0].to(torch::kFloat32).contiguous();
-        MlpScratch own;                                       // the workspaces the forward left, handed back to the frame
-        own.energies = saved[4];
-        if (ctx->saved_data["in_forward"].toBool()) own.partial = saved[5];
-        else own.d1.assign(saved.begin() + 5, saved.end());
-        c10::hip::HIPGuard guard(x.device().index());
-        MlpCall call = mlp_prepare(x, rows, ctx->saved_data["kind_atoms"].toIntVector(), ctx->saved_data["widths"].toIntVector(), members, planes, floats,
-                                   true, x_blocks, dead_blocks, ctx->saved_data["act_scale_log2"].toInt(), &own);
-        Tensor dx = torch::empty_like(x);
-        call.frame.dx = dx.data_ptr<float>(); call.frame.lddx = (int)dx.size(1); call.frame.dx_scale = 1.0f;
-        call.frame.member_weights = g.data_ptr<float>(); call.frame.member_weights_ld = (int)members;
-        if (offsets.has_value()) { call.frame.segment_offsets = offsets->data_ptr<int32_t>(); call.frame.num_segments = (int)B; }
-        if (nnpops_mlp_input_grad(current_stream(x.device()), &call.frame) != NNPOPS_OK) raise_last("NNPOpsBatchedNN::FusedMLPMembers (backward)");
-        return {dx, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+        const MlpNodeState s = MlpNodeState::load(ctx, "FusedMLPMembers");
+        const Tensor g = mlp_member_upstream(grads[0], s);
+        c10::hip::HIPGuard guard(s.x.device().index());
+        MlpCall call = prepare_backward(s);
+        static_assert(forward_arguments(&forward) == mlp_slot::need_gradient + 1, "one gradient slot for every argument of forward");
+        tensor_list result(forward_arguments(&forward));
+        result[mlp_slot::x] = mlp_input_gradient(current_stream(s.x.device()), call, s.x, 1.0f, &g, s.offsets, "NNPOpsBatchedNN::FusedMLPMembers (backward)");
+        return result;
     }
 };
 
@@ -3303,6 +3354,50 @@ Tensor FusedMLPMembers(const Tensor& x, const Tensor& rows, std::vector<int64_t>
 // every (molecule, member) as its weights, the eight parameter gradients scattered into the module's shapes: entries outside a
 // kind's packed widths and the columns of dead AEV blocks are exact zeros.  First derivatives only.
 // =============================================================================================
+// The gradients of the eight parameter arrays for `upstream` [B, M] (float32, contiguous), the weight of every (molecule, member):
+// per-kind outputs at the packed widths, ONE call of nnpops_mlp_weight_grad, and the scatter into the module's shapes -- rows and
+// columns up to the smaller of the packed width and the module's, the first layer's columns where the live blocks lie; the rest zeros.
+tensor_list mlp_weight_gradients(void* stream, MlpCall& call, const MlpNodeState& s, const Tensor& upstream, const char* op) {
+    mlp_point_upstream(call.frame, upstream, s.offsets);
+    const auto options = s.x.options();
+    const std::vector<int64_t>& shapes = s.parameter_shapes;
+    const int64_t F = call.frame.num_features, M = s.members, kinds = (int64_t)s.kind_atoms.size();
+    nnpops_mlp_weight_grad_out wg{};
+    const int64_t bytes = nnpops_mlp_weight_grad_workspace_bytes(&call.frame);
+    Tensor workspace = torch::empty({std::max<int64_t>(bytes / 4, 64)}, options);
+    wg.workspace = workspace.data_ptr<float>(); wg.workspace_bytes = workspace.numel() * 4;
+    std::vector<std::array<Tensor, 8>> packed((size_t)kinds);
+    for (int64_t k = 0; k < kinds; k++) {
+        const int64_t h1 = s.widths[3 * k], h2 = s.widths[3 * k + 1], h3 = s.widths[3 * k + 2];
+        packed[k] = {torch::empty({M, h1, F}, options), torch::empty({M, h1, 1}, options), torch::empty({M, h2, h1}, options),
+                     torch::empty({M, h2, 1}, options), torch::empty({M, h3, h2}, options), torch::empty({M, h3, 1}, options),
+                     torch::empty({M, 1, h3}, options), torch::empty({M, 1, 1}, options)};
+        nnpops_mlp_weight_grad_kind& o = wg.kinds[k];
+        float** slots[8] = {&o.dw0, &o.db0, &o.dw2, &o.db2, &o.dw4, &o.db4, &o.dw6, &o.db6};
+        for (int i = 0; i < 8; i++) *slots[i] = packed[k][i].data_ptr<float>();
+    }
+    if (nnpops_mlp_weight_grad(stream, &call.frame, &wg) != NNPOPS_OK) raise_last(op);
+    Tensor live_columns;
+    if (call.frame.x_groups)
+        live_columns = ((s.x_blocks->to(torch::kLong) * 16).unsqueeze(1) + torch::arange(16, s.x_blocks->options().dtype(torch::kLong)).unsqueeze(0)).reshape(-1);
+    tensor_list gradients;
+    for (int i = 0; i < 8; i++) {
+        Tensor full = torch::zeros({kinds, M, shapes[2 * i], shapes[2 * i + 1]}, options);
+        for (int64_t k = 0; k < kinds; k++) {
+            const Tensor& src = packed[k][i];
+            const int64_t r = std::min<int64_t>(src.size(1), shapes[2 * i]);
+            if (i == 0 && live_columns.defined()) {
+                full[k].narrow(1, 0, r).index_copy_(2, live_columns, src.narrow(1, 0, r));
+                continue;
+            }
+            const int64_t c = std::min<int64_t>(src.size(2), shapes[2 * i + 1]);
+            full[k].narrow(1, 0, r).narrow(2, 0, c).copy_(src.narrow(1, 0, r).narrow(2, 0, c));
+        }
+        gradients.push_back(full);
+    }
+    return gradients;
+}
+
 class FusedMLPMembersTrainableFunction : public torch::autograd::Function<FusedMLPMembersTrainableFunction> {
 public:
     static Tensor forward(AutogradContext* ctx, const Tensor& x, const Tensor& rows, std::vector<int64_t> kind_atoms, std::vector<int64_t> widths,
@@ -3318,106 +3413,58 @@ public:
                         "FusedMLPMembersTrainable: parameters are float32 [kinds, members, out, in] tensors on the device of x");
             shapes.push_back(p.size(2)); shapes.push_back(p.size(3));
         }
-        Tensor out = FusedMLPMembersFunction::run(ctx, x, rows, kind_atoms, widths, members, planes, floats, x_blocks, dead_blocks, act_scale_log2,
-                                                  offsets, places, shift, need_gradient, mean);
-        if (need_gradient) { ctx->saved_data["parameter_shapes"] = shapes; ctx->saved_data["mean"] = mean; }
-        return out;
+        return mlp_members_forward(ctx, x, rows, kind_atoms, widths, members, planes, floats, x_blocks, dead_blocks, act_scale_log2, offsets, places,
+                                   shift, need_gradient, (MlpReduce)mean, shapes);
     }
     static tensor_list backward(AutogradContext* ctx, const tensor_list& grads) {
         const char* op = "NNPOpsBatchedNN::FusedMLPMembersTrainable (backward)";
         TORCH_CHECK(!torch::GradMode::is_enabled(), "NNPOpsBatchedNN::FusedMLPMembersTrainable: second derivatives are not implemented (create_graph=True): "
                                                     "training on forces needs layout='grouped'");
-        const int64_t mean = ctx->saved_data["mean"].toInt();
-        const float mean_scale = mean == 2 ? 1.0f : 1.0f / (float)ctx->saved_data["members"].toInt();
-        tensor_list result;
-        if (!mean) result = FusedMLPMembersFunction::backward(ctx, grads);        // (dx in front; the weighted input gradient, as ever)
-        const auto saved = ctx->get_saved_variables();
-        TORCH_CHECK(!saved.empty(), "FusedMLPMembersTrainable was evaluated without a gradient request");
-        const Tensor &x = saved[0], &rows = saved[1], &planes = saved[2], &floats = saved[3];
-        const int64_t members = ctx->saved_data["members"].toInt();
-        const std::vector<int64_t> kind_atoms = ctx->saved_data["kind_atoms"].toIntVector(), widths = ctx->saved_data["widths"].toIntVector(),
-                                   shapes = ctx->saved_data["parameter_shapes"].toIntVector();
-        const c10::optional<Tensor> x_blocks = ctx->saved_data["x_blocks"].toOptional<Tensor>(), dead_blocks = ctx->saved_data["dead_blocks"].toOptional<Tensor>(),
-                                    offsets = ctx->saved_data["offsets"].toOptional<Tensor>();
-        const int64_t B = offsets.has_value() ? offsets->numel() - 1 : 1, kinds = (int64_t)kind_atoms.size();
-        Tensor g = grads[0].to(torch::kFloat32).contiguous();
-        if (mean) {                                           // every member of molecule b carries the mean's upstream gradient over M
-            TORCH_CHECK(g.numel() == B && g.device() == x.device(), "FusedMLPMeanTrainable: unexpected gradient of the energies (", B, " expected)");
-            g = (g.reshape({B, 1}) * mean_scale).expand({B, members}).contiguous();
-        }
-        MlpScratch own;                                       // (the frame needs workspaces of the gradient pass; the weight gradient touches none)
-        own.energies = saved[4];
-        if (ctx->saved_data["in_forward"].toBool()) own.partial = saved[5];
-        else own.d1.assign(saved.begin() + 5, saved.end());
-        c10::hip::HIPGuard guard(x.device().index());
-        MlpCall call = mlp_prepare(x, rows, kind_atoms, widths, members, planes, floats, true, x_blocks, dead_blocks,
-                                   ctx->saved_data["act_scale_log2"].toInt(), &own);
-        if (mean) {
+        const MlpNodeState s = MlpNodeState::load(ctx, "FusedMLPMembersTrainable");
+        const int64_t B = s.molecules();
+        c10::hip::HIPGuard guard(s.x.device().index());
+        void* stream = current_stream(s.x.device());
+        MlpCall call = prepare_backward(s);
+        static_assert(forward_arguments(&forward) == mlp_slot::parameters + 1, "one gradient slot for every argument of forward");
+        tensor_list result(mlp_slot::parameters);             // (... and one for every parameter of the list behind them)
+        Tensor g;                                             // the weight of every (molecule, member) in the weight gradient
+        if (s.mode == MlpReduce::members) {
+            g = mlp_member_upstream(grads[0], s);
+            result[mlp_slot::x] = mlp_input_gradient(stream, call, s.x, 1.0f, &g, s.offsets, op);
+        } else {
             // the gradient of x as the one-node step forms it -- the unweighted pass with 1 / M as its scale -- then times the upstream
             // gradient of the row's molecule: with an upstream gradient of one, the bits energy_step hands to the AEV backward
-            Tensor dx = torch::empty_like(x);
-            call.frame.dx = dx.data_ptr<float>(); call.frame.lddx = (int)dx.size(1); call.frame.dx_scale = mean_scale;
-            if (nnpops_mlp_input_grad(current_stream(x.device()), &call.frame) != NNPOPS_OK) raise_last(op);
-            const Tensor up = grads[0].to(torch::kFloat32).reshape({B});
-            if (offsets.has_value()) {
-                const Tensor counts = (offsets->slice(0, 1, B + 1) - offsets->slice(0, 0, B)).to(torch::kLong);
-                dx.mul_(torch::repeat_interleave(up, counts, 0, x.size(0)).unsqueeze(1));
+            const float mean_scale = s.mode == MlpReduce::total ? 1.0f : 1.0f / (float)s.members;
+            const Tensor up = grads[0].to(torch::kFloat32).contiguous();
+            TORCH_CHECK(up.numel() == B && up.device() == s.x.device(), "FusedMLPMeanTrainable: unexpected gradient of the energies (", B, " expected)");
+            g = (up.reshape({B, 1}) * mean_scale).expand({B, s.members}).contiguous();     // every member carries the upstream gradient over M
+            Tensor dx = mlp_input_gradient(stream, call, s.x, mean_scale, nullptr, c10::nullopt, op);
+            if (s.offsets.has_value()) {
+                const Tensor counts = (s.offsets->slice(0, 1, B + 1) - s.offsets->slice(0, 0, B)).to(torch::kLong);
+                dx.mul_(torch::repeat_interleave(up.reshape({B}), counts, 0, s.x.size(0)).unsqueeze(1));
             } else {
-                dx.mul_(up);
+                dx.mul_(up.reshape({B}));
             }
-            result = {dx, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+            result[mlp_slot::x] = dx;
         }
-        call.frame.member_weights = g.data_ptr<float>(); call.frame.member_weights_ld = (int)members;
-        if (offsets.has_value()) { call.frame.segment_offsets = offsets->data_ptr<int32_t>(); call.frame.num_segments = (int)B; }
-        const int64_t F = call.frame.num_features, M = members;
-        nnpops_mlp_weight_grad_out wg{};
-        const int64_t bytes = nnpops_mlp_weight_grad_workspace_bytes(&call.frame);
-        Tensor workspace = torch::empty({std::max<int64_t>(bytes / 4, 64)}, x.options());
-        wg.workspace = workspace.data_ptr<float>(); wg.workspace_bytes = workspace.numel() * 4;
-        std::vector<std::array<Tensor, 8>> packed((size_t)kinds);
-        for (int64_t k = 0; k < kinds; k++) {
-            const int64_t h1 = widths[3 * k], h2 = widths[3 * k + 1], h3 = widths[3 * k + 2];
-            packed[k] = {torch::empty({M, h1, F}, x.options()), torch::empty({M, h1, 1}, x.options()), torch::empty({M, h2, h1}, x.options()),
-                         torch::empty({M, h2, 1}, x.options()), torch::empty({M, h3, h2}, x.options()), torch::empty({M, h3, 1}, x.options()),
-                         torch::empty({M, 1, h3}, x.options()), torch::empty({M, 1, 1}, x.options())};
-            nnpops_mlp_weight_grad_kind& o = wg.kinds[k];
-            float** slots[8] = {&o.dw0, &o.db0, &o.dw2, &o.db2, &o.dw4, &o.db4, &o.dw6, &o.db6};
-            for (int i = 0; i < 8; i++) *slots[i] = packed[k][i].data_ptr<float>();
-        }
-        if (nnpops_mlp_weight_grad(current_stream(x.device()), &call.frame, &wg) != NNPOPS_OK) raise_last(op);
-        // into the module's shapes: rows and columns up to the smaller of the packed width and the module's, the first layer's columns where
-        // the live blocks lie
-        Tensor live_columns;
-        if (call.frame.x_groups)
-            live_columns = ((x_blocks->to(torch::kLong) * 16).unsqueeze(1) + torch::arange(16, x_blocks->options().dtype(torch::kLong)).unsqueeze(0)).reshape(-1);
-        for (int i = 0; i < 8; i++) {
-            Tensor full = torch::zeros({kinds, M, shapes[2 * i], shapes[2 * i + 1]}, x.options());
-            for (int64_t k = 0; k < kinds; k++) {
-                const Tensor& src = packed[k][i];
-                const int64_t r = std::min<int64_t>(src.size(1), shapes[2 * i]);
-                if (i == 0 && live_columns.defined()) {
-                    full[k].narrow(1, 0, r).index_copy_(2, live_columns, src.narrow(1, 0, r));
-                    continue;
-                }
-                const int64_t c = std::min<int64_t>(src.size(2), shapes[2 * i + 1]);
-                full[k].narrow(1, 0, r).narrow(2, 0, c).copy_(src.narrow(1, 0, r).narrow(2, 0, c));
-            }
-            result.push_back(full);
-        }
-        result.insert(result.begin() + 14, Tensor());        // (the `mean` flag)
+        for (Tensor& gradient : mlp_weight_gradients(stream, call, s, g, op)) result.push_back(std::move(gradient));
         return result;
     }
 };
+
+// whether a trainable node has anything to keep: gradients are recorded and x or one of the parameters asks for one
+bool needs_gradient(const Tensor& x, at::TensorList parameters) {
+    bool need = x.requires_grad();
+    for (const Tensor& p : parameters) need = need || p.requires_grad();
+    return need && torch::GradMode::is_enabled();
+}
 
 Tensor FusedMLPMembersTrainable(const Tensor& x, const Tensor& rows, std::vector<int64_t> kind_atoms, std::vector<int64_t> widths, int64_t members,
                                 const Tensor& planes, const Tensor& floats, const c10::optional<Tensor>& x_blocks,
                                 const c10::optional<Tensor>& dead_blocks, int64_t act_scale_log2, const c10::optional<Tensor>& offsets,
                                 const c10::optional<Tensor>& places, const c10::optional<Tensor>& shift, at::TensorList parameters) {
-    bool need = x.requires_grad();
-    for (const Tensor& p : parameters) need = need || p.requires_grad();
-    need = need && torch::GradMode::is_enabled();
     return FusedMLPMembersTrainableFunction::apply(x, rows, kind_atoms, widths, members, planes, floats, x_blocks, dead_blocks, act_scale_log2, offsets,
-                                                   places, shift, need, (int64_t)0, parameters);
+                                                   places, shift, needs_gradient(x, parameters), (int64_t)MlpReduce::members, parameters);
 }
 
 // FusedMLPMeanTrainable: the same node with the ensemble mean [B] as its output -- the energy of the one-node step
@@ -3428,11 +3475,8 @@ Tensor FusedMLPMeanTrainable(const Tensor& x, const Tensor& rows, std::vector<in
                              const Tensor& planes, const Tensor& floats, const c10::optional<Tensor>& x_blocks,
                              const c10::optional<Tensor>& dead_blocks, int64_t act_scale_log2, const c10::optional<Tensor>& offsets,
                              const c10::optional<Tensor>& places, const c10::optional<Tensor>& shift, at::TensorList parameters, bool total) {
-    bool need = x.requires_grad();
-    for (const Tensor& p : parameters) need = need || p.requires_grad();
-    need = need && torch::GradMode::is_enabled();
     return FusedMLPMembersTrainableFunction::apply(x, rows, kind_atoms, widths, members, planes, floats, x_blocks, dead_blocks, act_scale_log2, offsets,
-                                                   places, shift, need, (int64_t)(total ? 2 : 1), parameters);
+                                                   places, shift, needs_gradient(x, parameters), (int64_t)(total ? MlpReduce::total : MlpReduce::mean), parameters);
 }
 
 // =============================================================================================
