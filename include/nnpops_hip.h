@@ -110,6 +110,17 @@ int nnpops_ani_backprop_strided(nnpops_ani_t h, const float* radial_deriv, int r
  * Allocates nothing: graph-capturable like backprop.  Additive. */
 int nnpops_ani_backprop_box_strided(nnpops_ani_t h, const float* positions, const float* box, const float* radial_deriv, int radial_ld,
                                     const float* angular_deriv, int angular_ld, float* position_deriv, float* box_deriv);
+/* The tangent J.v of the AEV: the directional derivative d/dt aev(x + t v) at t = 0 along position_tangent (device [num_atoms][3]), on
+ * the lists the preceding compute() left (shifts and box held fixed: the tangent of every displacement is v_j - v_i, so periodic
+ * handles, non-periodic ones and nnpops_ani_set_molecules batches are alike).  What the parameter gradient of a force loss needs of the
+ * AEV: with F = -J^T g(theta, aev) it is (dg/dtheta)^T (J.v), v = dL/dF.  It is the adjoint of backprop:
+ * <w, tangent(v)> = <backprop(w), v>.  radial_tangent / angular_tangent: shapes and strides as compute_strided (0 = dense), fully
+ * overwritten, zeros for atoms without neighbours.  One owner per element, no atomics: two calls agree bit for bit.  Any function
+ * list (factorable or generic), both angle conventions.  Reads what compute() left and writes only its outputs: compute, backprop and
+ * backprop_box around it keep their bits.  Allocates nothing, honours the handle's stream: graph-capturable like backprop.  Additive.
+ * Second derivatives of the AEV in the positions or the box (Hessians, a force loss differentiated in the coordinates) are NOT here. */
+int nnpops_ani_tangent_strided(nnpops_ani_t h, const float* position_tangent, float* radial_tangent, int radial_ld,
+                               float* angular_tangent, int angular_ld);
 /* Blocks on the handle's stream and reports whether the last compute() overflowed a neighbour
  * buffer (NNPOPS_ERR_CAPACITY; the handle has then already grown its buffers, so simply call
  * compute() again).  max_radial_neighbors / max_angular_neighbors (host, may be NULL) receive the

@@ -18,8 +18,22 @@ class OptimizedTorchANI(torch.nn.Module):
     node (``fused_step=False`` keeps the plain composition).
 
     ``trainable=True`` (extension): the networks' arrays are parameters (``TorchANIBatchedNN(..., trainable=True)``) and, with the
-    fused layout, the instance becomes a :class:`TrainableOptimizedTorchANI`.  Out of scope: scripting a trainable module, second
-    derivatives (training on forces), periodic batches."""
+    fused layout, the instance becomes a :class:`TrainableOptimizedTorchANI`.
+
+    A loss on FORCES trains ``nn_layout='grouped', trainable=True`` (this composition; ``forward`` and ``forward_batch``), no flag::
+
+        E = model((Z, x)).energies                                      # x.requires_grad_()
+        F = -torch.autograd.grad(E.sum(), x, create_graph=True)[0]
+        loss = (E - E0) ** 2 + ((F - F0) ** 2).sum()
+        loss.backward(inputs=list(model.neural_networks.parameters()))   # or torch.autograd.grad(loss, parameters)
+
+    Under ``create_graph=True`` the AEV op records its backward; the derivative of that node in the AEV cotangent is the AEV's tangent
+    ``J.v`` (``Holder.tangent``), which autograd carries through the networks.  Refused with a message, never dropped: the gradient of
+    a force in the POSITIONS (``loss.backward()`` without ``inputs=``, Hessians -- second derivatives of the AEV are not implemented),
+    third derivatives, a forward pass on the same module between the forward and the derivatives that belong to it, and
+    ``create_graph=True`` with a cell that requires a gradient.  The fused layout still trains on energies only.
+
+    Out of scope: scripting a trainable module, second derivatives through the fused networks, periodic batches."""
 
     def __init__(self, model, atomicNumbers: Tensor, nn_layout: str = 'fused', fused_step: bool = True, live_columns: bool = True,
                  trainable: bool = False) -> None:
@@ -229,7 +243,8 @@ class TrainableOptimizedTorchANI(FusedOptimizedTorchANI):
     gradient, one call of their weight gradient and the AEV backward, whatever function of the energies was differentiated.
     Energies and coordinate gradients are the bits of the default module at equal weights.  ``energy_and_forces`` /
     ``energy_and_forces_batch`` stay outside autograd and use the current weights.  Out of scope: scripting, second derivatives (a
-    loss on forces), periodic batches, a gradient of the cell."""
+    loss on forces trains ``nn_layout='grouped'``, see :class:`OptimizedTorchANI`; here ``create_graph=True`` is refused), periodic
+    batches, a gradient of the cell."""
 
     def forward(self, species_coordinates: Tuple[Tensor, Tensor], cell: Optional[Tensor] = None,
                 pbc: Optional[Tensor] = None) -> SpeciesEnergies:

@@ -134,7 +134,14 @@ class TorchANISymmetryFunctions(torch.nn.Module):
         backward also returns dL/dcell [3, 3] -- the derivative with the minimum-image shifts of the forward held fixed, all nine
         entries, the convention of ``getNeighborPairs`` and ``PME`` -- from which a stress follows as
         ``(positions.T @ positions.grad + cell.T @ cell.grad) / volume``.  A cell that does not require a gradient costs nothing
-        and gets none; ``create_graph=True`` with a cell gradient is refused."""
+        and gets none; ``create_graph=True`` with a cell gradient is refused.
+
+        Extension: a loss on forces.  Under ``create_graph=True``, when the gradient arriving at the AEV itself carries a graph (it
+        came through networks whose parameters require a gradient), the backward is recorded: the force keeps its bits and gains a
+        graph whose derivative in the AEV cotangent is the tangent ``J.v`` of the AEV (``holder.tangent(v)``) -- all that
+        ``loss.backward(inputs=parameters)`` / ``torch.autograd.grad(loss, parameters)`` of a force loss needs.  Refused with a
+        message: the gradient of a force in the positions (second derivatives of the AEV; ``loss.backward()`` without ``inputs=``
+        asks for it), third derivatives, and a derivative taken after another forward pass of this module rebuilt its lists."""
         species, positions = species_positions
         self.check_arguments(species, cell, pbc)
         # the reference concatenates the two outputs of `operation` (SymmetryFunctions.py:120-122); `aev` has the kernels

@@ -37,6 +37,7 @@ SIGNATURES = {
     "nnpops_ani_backprop_strided": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "nnpops_ani_backprop_box_strided": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                                   C.c_void_p]),
+    "nnpops_ani_tangent_strided": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "nnpops_ani_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "nnpops_ani_check_begin": (C.c_int, [C.c_void_p]),
     "nnpops_ani_check_end": (C.c_int, [C.c_void_p]),
@@ -325,6 +326,28 @@ class AniSymmetryFunctions:
         _check(self._lib.nnpops_ani_backprop_box_strided(self._h, _ptr(positions), _ptr(box), _ptr(radial_grad), 0, _ptr(angular_grad), 0,
                                                          _ptr(position_grad), _ptr(box_grad)))
         return position_grad, box_grad
+
+    def tangent(self, position_tangent, radial_tangent=None, angular_tangent=None):
+        """The tangent ``J.v`` of the AEV of the preceding ``compute`` along ``position_tangent`` [N,3] -> (radial [N,S*nR], angular
+        [N,NB*nA]): ``d/dt aev(x + t v)`` at ``t = 0`` on the lists the handle holds, shifts and box fixed.  The adjoint of ``backprop``
+        (``<w, tangent(v)> == <backprop(w), v>``) and what the parameter gradient of a force loss needs of the AEV.  Outputs may be
+        row-strided views (one [N, W_r + W_a] array, as ``compute_strided`` writes); they are fully overwritten, bit-reproducibly."""
+        _dev_f32(position_tangent, "position_tangent", (self.num_atoms, 3))
+        dev = position_tangent.device
+        if radial_tangent is None:
+            radial_tangent = torch.empty((self.num_atoms, self.radial_width), dtype=torch.float32, device=dev)
+        if angular_tangent is None:
+            angular_tangent = torch.empty((self.num_atoms, self.angular_width), dtype=torch.float32, device=dev)
+        lds = []
+        for t, width, name in ((radial_tangent, self.radial_width, "radial_tangent"), (angular_tangent, self.angular_width, "angular_tangent")):
+            if (t.dtype != torch.float32 or t.device != dev or tuple(t.shape) != (self.num_atoms, width) or t.stride(1) != 1
+                    or t.stride(0) < width):
+                raise ValueError(f"{name} must be a float32 [{self.num_atoms}, {width}] device array with unit inner stride")
+            lds.append(int(t.stride(0)))
+        _check(self._lib.nnpops_ani_set_stream(self._h, _stream_ptr(dev)))
+        _check(self._lib.nnpops_ani_tangent_strided(self._h, _ptr(position_tangent), C.c_void_p(radial_tangent.data_ptr()), lds[0],
+                                                    C.c_void_p(angular_tangent.data_ptr()), lds[1]))
+        return radial_tangent, angular_tangent
 
     KERNELS = ("neighbors", "radial_forward", "angular_forward", "radial_backward", "angular_backward", "cell_grid")
 

@@ -17,6 +17,7 @@
 #include "ani_radial_bwd.h"
 #include "ani_build_forward.h"
 #include "ani_box_grad.h"
+#include "ani_tangent.h"
 #include "celllist_host.h"
 
 using namespace nnpops;
@@ -1020,6 +1021,27 @@ int nnpops_ani_backprop_box_strided(nnpops_ani_t h, const float* positions, cons
                        h->cap_angular, h->d_cnt_pos, radial_deriv, h->ld_radial, h->d_recA, h->d_ids, h->d_leg_force,
                        h->last_used_cells ? h->cells.sorted_atom : nullptr, h->scatter_now ? 1 : 0, h->d_box_partials);
     hipLaunchKernelGGL(pairs_box_finish<float>, dim3(1), dim3(kBoxThreads), 0, h->stream, nblocks, (const double*)h->d_box_partials, box_deriv);
+    NNPOPS_HIP_TRY(hipGetLastError());
+    return NNPOPS_OK;
+}
+
+int nnpops_ani_tangent_strided(nnpops_ani_t h, const float* position_tangent, float* radial_tangent, int radial_ld,
+                               float* angular_tangent, int angular_ld) {
+    NNPOPS_REQUIRE(h != nullptr, "NULL handle");
+    const int wr = h->hp.S * h->hp.nR, wa = h->hp.NB * h->hp.nA;
+    NNPOPS_REQUIRE((radial_ld == 0 || radial_ld >= wr) && (angular_ld == 0 || angular_ld >= wa),
+                   "row strides must be 0 (dense) or at least the row widths (%d, %d)", wr, wa);
+    NNPOPS_REQUIRE(position_tangent && radial_tangent && angular_tangent, "NULL device pointer");
+    NNPOPS_REQUIRE(h->computed, "tangent() must follow compute() on the same handle");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(NNPOPS_ERR_HIP, "cannot select device %d", h->device);
+    // (the strides are this call's own: the handle's ld_radial / ld_angular belong to compute() and backprop())
+    const size_t lds = (ani_tangent_lds_bytes(h->cap, h->cap_angular, h->hp.NB) + 15) & ~(size_t)15;
+    if (lds > 64 * 1024) return fail(NNPOPS_ERR_UNSUPPORTED, "tangent kernel needs %zu bytes of LDS (row capacity %d)", lds, h->cap);
+    auto k = h->hp.torchani ? ani_tangent<true> : ani_tangent<false>;
+    hipLaunchKernelGGL(k, dim3(h->hp.N), dim3(64), lds, h->stream, h->d_params, h->d_nbr, h->cap, h->cap_angular, h->d_cnt_pos, h->d_recA,
+                       h->d_recB, h->d_ids, h->d_tri, h->last_used_cells ? h->cells.sorted_atom : nullptr, position_tangent, radial_tangent,
+                       radial_ld ? radial_ld : wr, angular_tangent, angular_ld ? angular_ld : wa);
     NNPOPS_HIP_TRY(hipGetLastError());
     return NNPOPS_OK;
 }

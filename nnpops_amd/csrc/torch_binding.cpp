@@ -344,6 +344,7 @@ public:
         void* stream = current_stream(device);
         nnpops_ani_set_stream(impl, stream);
         const bool capturing = stream_is_capturing(stream);
+        buildCount++;                                 // the lists are rebuilt: a recorded backward of an earlier forward is stale (AevBackwardFunction)
         for (int attempt = 0;; attempt++) {
             if (nnpops_ani_compute_strided(impl, pos.data_ptr<float>(), periodic ? cell.data_ptr<float>() : nullptr, pr, ld, pa, ld) !=
                 NNPOPS_OK)
@@ -394,6 +395,24 @@ public:
             raise_last("NNPOpsANISymmetryFunctions::backward");
         return {Tensor(), positionsGrad, Tensor()};          // no gradient for the holder and the box (:174)
     }
+
+    // Additive: the tangent J.v of the AEV of the last forward along v [N, 3] (nnpops_ani_tangent_strided) -- the adjoint of backward(),
+    // what the parameter gradient of a force loss needs of the AEV.  tangent(): the fused layout [N, W_r + W_a] of aev();
+    // tangentSplit(): {radial [N, W_r], angular [N, W_a]} as operation() returns them.
+    Tensor tangent(const Tensor& v) {
+        const int64_t wr = numSpecies * numRadial, wa = numSpecies * (numSpecies + 1) / 2 * numAngular;
+        Tensor out = torch::empty({(int64_t)atomSpecies.size(), wr + wa}, torch::TensorOptions().device(device).dtype(torch::kFloat32));
+        tangentInto(v, out.data_ptr<float>(), (int)(wr + wa), out.data_ptr<float>() + wr, (int)(wr + wa));
+        return out;
+    }
+    tensor_list tangentSplit(const Tensor& v) {
+        const int64_t wr = numSpecies * numRadial, wa = numSpecies * (numSpecies + 1) / 2 * numAngular;
+        const auto opts = torch::TensorOptions().device(device).dtype(torch::kFloat32);
+        Tensor radial = torch::empty({(int64_t)atomSpecies.size(), wr}, opts), angular = torch::empty({(int64_t)atomSpecies.size(), wa}, opts);
+        tangentInto(v, radial.data_ptr<float>(), 0, angular.data_ptr<float>(), 0);
+        return {radial, angular};
+    }
+    int64_t getBuildCount() const { return buildCount; }
 
     // The two backward forms WITH the gradient of the box vectors (nnpops_ani_backprop_box_strided): `positions` and `cell` are the
     // tensors of the forward this backward belongs to -- the minimum-image shifts are recovered from them.  -> {none, dL/dpositions,
@@ -470,6 +489,17 @@ private:
         return {Tensor(), positionsGrad, cellGrad};
     }
 
+    void tangentInto(const Tensor& v, float* radial, int ldRadial, float* angular, int ldAngular) {
+        if (!impl) throw std::runtime_error("tangent() called before forward()");
+        TORCH_CHECK(v.defined() && v.scalar_type() == torch::kFloat32 && v.dim() == 2 && v.size(0) == (int64_t)atomSpecies.size() && v.size(1) == 3,
+                    "NNPOpsANISymmetryFunctions::tangent: the tangent has to be a float32 tensor of the shape of \"positions\"");
+        TORCH_CHECK(v.device() == device, "NNPOpsANISymmetryFunctions::tangent: the tangent has to be on the device of \"positions\"");
+        const Tensor t = v.contiguous();
+        nnpops_ani_set_stream(impl, current_stream(device));
+        if (nnpops_ani_tangent_strided(impl, t.data_ptr<float>(), radial, ldRadial, angular, ldAngular) != NNPOPS_OK)
+            raise_last("NNPOpsANISymmetryFunctions::tangent");
+    }
+
     void applyMolecules() {
         std::vector<int32_t> off(moleculeOffsets.begin(), moleculeOffsets.end());
         if (nnpops_ani_set_molecules(impl, off.empty() ? 0 : (int)off.size() - 1, off.empty() ? nullptr : off.data()) != NNPOPS_OK)
@@ -488,6 +518,7 @@ private:
     int64_t checkInterval = 1;      // capacity check every k-th forward (0: only the first); see setCheckInterval
     bool forceCheck = false;        // the next forwardImpl() re-issues a step after a reported overflow: always checked
     int64_t calls = 0;
+    int64_t buildCount = 0;         // forwardImpl() calls so far: which build of the lists a recorded backward belongs to
     bool checkPending = false;
 public:
     // energy_step: the capacity check's word is published by nnpops_mlp_forward (frame.publish_*) instead of a launch of its own
@@ -538,6 +569,66 @@ void refuse_second_derivatives(const char* op) {
                 ": second derivatives are not implemented (backward was called with create_graph=True and the cell requires a gradient)");
 }
 
+// The backward of the two nodes below, RECORDED: dL/dpositions = J^T g as a function of the AEV cotangent(s) g -- it is linear in them,
+// so its own backward, given the cotangent v of the position gradient, is the tangent J.v (Holder::tangent) in the slot(s) of g.  That is
+// all the parameter gradient of a force loss needs: with F = -J^T g(theta, aev) it is (dg/dtheta)^T (J.v), and autograd carries J.v on
+// through the networks that made g.  What it does NOT provide is refused, never dropped: the gradient of this node in the POSITIONS
+// (second derivatives of the AEV: Hessians, a force loss differentiated in the coordinates), a third derivative, and a tangent on lists
+// that a later forward of the same holder has rebuilt.  Tensor inputs: the cotangent(s) first, the positions last.
+void check_same_build(const HolderPtr& holder, int64_t build, const char* op) {
+    TORCH_CHECK(holder->getBuildCount() == build, "NNPOpsANISymmetryFunctions::", op, ": the holder has run another forward pass since the one "
+                "this derivative belongs to; its neighbour lists were rebuilt and no longer belong to these positions (run the forward "
+                "pass and take every derivative of it before the next forward pass on the same holder)");
+}
+
+class AevBackwardFunction : public torch::autograd::Function<AevBackwardFunction> {
+public:
+    // angularGrad: empty for the fused layout (aev), where `grad` is the whole [N, W_r + W_a] cotangent
+    static Tensor forward(AutogradContext* ctx, const Tensor& grad, const c10::optional<Tensor>& angularGrad, const Tensor& positions,
+                          const HolderPtr& holder, int64_t build) {
+        const bool fused = !angularGrad.has_value();
+        check_same_build(holder, build, fused ? "aev" : "operation");
+        ctx->saved_data["holder"] = holder;
+        ctx->saved_data["build"] = build;
+        ctx->saved_data["fused"] = fused;
+        // (exactly the call the unrecorded backward makes: the same bits)
+        return fused ? holder->backwardFused(grad)[1] : holder->backward({grad, *angularGrad})[1];
+    }
+    static tensor_list backward(AutogradContext* ctx, const tensor_list& grads) {
+        const bool fused = ctx->saved_data["fused"].toBool();
+        const char* op = fused ? "aev" : "operation";
+        const size_t ncot = fused ? 1 : 2;                 // (the node's edges count its tensor inputs only: the positions follow the cotangents)
+        TORCH_CHECK(!ctx->needs_input_grad(ncot),"NNPOpsANISymmetryFunctions::", op, ": second derivatives with respect to the positions are not "
+                    "implemented (the gradient of a force with respect to the positions was asked for: a Hessian, or loss.backward() on a "
+                    "loss of forces, which also differentiates in the positions).  The parameter gradient of a force loss is obtained "
+                    "with torch.autograd.grad(loss, parameters) or loss.backward(inputs=parameters)");
+        const Tensor& v = grads[0];
+        TORCH_CHECK(!(torch::GradMode::is_enabled() && v.defined() && v.requires_grad()), "NNPOpsANISymmetryFunctions::", op,
+                    ": third derivatives are not implemented (the derivative of a force was taken with create_graph=True)");
+        const auto holder = ctx->saved_data["holder"].toCustomClass<Holder>();
+        check_same_build(holder, ctx->saved_data["build"].toInt(), op);
+        tensor_list out(5);                                // {cotangent, angular cotangent, positions, holder, build}
+        if (!v.defined()) return out;
+        if (fused) {
+            if (ctx->needs_input_grad(0)) out[0] = holder->tangent(v);
+        } else if (ctx->needs_input_grad(0) || ctx->needs_input_grad(1)) {
+            const tensor_list t = holder->tangentSplit(v);
+            if (ctx->needs_input_grad(0)) out[0] = t[0];
+            if (ctx->needs_input_grad(1)) out[1] = t[1];
+        }
+        return out;
+    }
+};
+
+// Is the backward in progress one to record?  Grad mode on (create_graph=True) and a cotangent that carries a graph of its own --
+// the energy came from networks whose parameters require a gradient.  Everything else takes the plain path: nothing more launched.
+bool record_backward(const tensor_list& grads) {
+    if (!torch::GradMode::is_enabled()) return false;
+    for (const Tensor& g : grads)
+        if (g.defined() && g.requires_grad()) return true;
+    return false;
+}
+
 class AutogradFunctions : public torch::autograd::Function<AutogradFunctions> {
 public:
     static tensor_list forward(AutogradContext* ctx, const HolderPtr& holder, const Tensor& positions,
@@ -545,17 +636,25 @@ public:
         ctx->saved_data["holder"] = holder;
         ctx->saved_data["cell_grad"] = cellGrad;
         if (cellGrad) ctx->save_for_backward({positions, *periodicBoxVectors});
-        return holder->forward(positions, periodicBoxVectors);
+        else ctx->save_for_backward({positions});          // (a reference to an input: what a recorded backward hangs its refusal on)
+        tensor_list out = holder->forward(positions, periodicBoxVectors);
+        ctx->saved_data["build"] = holder->getBuildCount();
+        return out;
     }
     static tensor_list backward(AutogradContext* ctx, const tensor_list& grads) {
         const auto holder = ctx->saved_data["holder"].toCustomClass<Holder>();
-        ctx->saved_data.erase("holder");
         tensor_list out;
         if (ctx->saved_data["cell_grad"].toBool()) {
+            ctx->saved_data.erase("holder");
             refuse_second_derivatives("operation");
             const auto saved = ctx->get_saved_variables();
             out = holder->backwardCell(grads, saved[0], saved[1]);
+        } else if (record_backward(grads)) {
+            const Tensor positions = ctx->get_saved_variables()[0];
+            out = {Tensor(), AevBackwardFunction::apply(grads[0], c10::optional<Tensor>(grads[1]), positions, holder,
+                                                        ctx->saved_data["build"].toInt()), Tensor()};
         } else {
+            ctx->saved_data.erase("holder");
             out = holder->backward(grads);
         }
         out.push_back(Tensor());
@@ -575,17 +674,25 @@ public:
         ctx->saved_data["holder"] = holder;
         ctx->saved_data["cell_grad"] = cellGrad;
         if (cellGrad) ctx->save_for_backward({positions, *periodicBoxVectors});
-        return holder->forwardImpl(positions, periodicBoxVectors, true)[0];
+        else ctx->save_for_backward({positions});          // (a reference to an input: what a recorded backward hangs its refusal on)
+        Tensor out = holder->forwardImpl(positions, periodicBoxVectors, true)[0];
+        ctx->saved_data["build"] = holder->getBuildCount();
+        return out;
     }
     static tensor_list backward(AutogradContext* ctx, const tensor_list& grads) {
         const auto holder = ctx->saved_data["holder"].toCustomClass<Holder>();
-        ctx->saved_data.erase("holder");
         tensor_list out;
         if (ctx->saved_data["cell_grad"].toBool()) {
+            ctx->saved_data.erase("holder");
             refuse_second_derivatives("aev");
             const auto saved = ctx->get_saved_variables();
             out = holder->backwardFusedCell(grads[0], saved[0], saved[1]);
+        } else if (record_backward(grads)) {
+            const Tensor positions = ctx->get_saved_variables()[0];
+            out = {Tensor(), AevBackwardFunction::apply(grads[0], c10::optional<Tensor>(), positions, holder, ctx->saved_data["build"].toInt()),
+                   Tensor()};
         } else {
+            ctx->saved_data.erase("holder");
             out = holder->backwardFused(grads[0]);
         }
         out.push_back(Tensor());
@@ -860,6 +967,9 @@ TORCH_LIBRARY(NNPOpsANISymmetryFunctions, m) {
                          const std::vector<double>&, const std::vector<int64_t>&>())
         .def("forward", &Holder::forward)
         .def("backward", &Holder::backward)
+        .def("tangent", &Holder::tangent)
+        .def("tangent_split", &Holder::tangentSplit)
+        .def("build_count", &Holder::getBuildCount)
         .def("set_check_interval", &Holder::setCheckInterval)
         .def("overflow_flag", &Holder::overflowFlag)
         .def("set_molecules", &Holder::setMolecules)
