@@ -600,6 +600,11 @@ int nnpops_gemm_split(void* stream, int M, int N, int K, int batch, const float*
                       const void* Bl, long ldb, long strideB, float* C, long ldc, long strideC, int epilogue, const float* bias,
                       long strideBias, const float* Y, long ldy, long strideY, int prologue, const float* PY, long ldpy,
                       long stridePY, const float* pv, long stridePv, float alpha, float a_scale, const int* a_rows, const int* c_rows);
+/* Which kernel the calling thread's last nnpops_gemm_split launched (host only, no device work): bn = 128 or 64 (columns of a
+ * workgroup's tile), k_split = 1 or 2 (2: eight waves, the two halves of every K step added through LDS), fast = 1 when the
+ * staging loads took the straight-line 16-byte path (K a multiple of 8, leading dimension and strides multiples of 4 floats,
+ * 16-byte aligned bases, NNPOPS_GEMM_FAST not 0).  An error before the thread's first launch; a refused call leaves it unchanged. */
+int nnpops_gemm_split_last(int* bn, int* k_split, int* fast);
 
 /* ---- the atomic networks of a whole frame in two launches (replaces the four BatchedLinear + CELU calls and the
  * sum of BatchedNN.py:100-111 inside OptimizedTorchANI.py:49-52, and their autograd backward to the AEV) ----

@@ -86,6 +86,7 @@ SIGNATURES = {
                                     C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_void_p, C.c_long,
                                     C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_long,
                                     C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "nnpops_gemm_split_last": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "nnpops_mlp_packed_halves": (C.c_int64, [C.c_int, C.c_int]),
     "nnpops_mlp_d1_halves": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "nnpops_mlp_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p]),
@@ -1021,23 +1022,73 @@ class CFConv:
 
 
 # ---- dense layers (batched_nn.hip) ----
-def split_planes(w, transpose=False):
+def split_planes(w, transpose=False, src_cols=None, ldp=None):
     """fp32 matrix [rows][cols] on the device -> (hi, lo) fp16 planes [R][ldp] of it (or of its transpose), ldp = the row
-    length rounded up to 32, zero padded; what nnpops_gemm_split takes as its B operand."""
+    length rounded up to 32, zero padded; what nnpops_gemm_split takes as its B operand.  ``src_cols``: the matrix is the first
+    src_cols columns of ``w`` (its leading dimension stays w's row length); ``ldp``: a longer plane row (a multiple of 32)."""
     w = _dev_f32(w, "w")
-    src_rows, src_cols = w.shape
+    src_rows, ldw = w.shape
+    src_cols = ldw if src_cols is None else int(src_cols)
+    if not 0 < src_cols <= ldw:
+        raise ValueError('"src_cols" must lie within the rows of "w"')
     rows, cols = (src_cols, src_rows) if transpose else (src_rows, src_cols)
-    ldp = (cols + 31) // 32 * 32
+    ldp = (cols + 31) // 32 * 32 if ldp is None else int(ldp)
     hi = torch.empty((rows, ldp), dtype=torch.float16, device=w.device)
     lo = torch.empty_like(hi)
-    _check(lib().nnpops_split_planes(_stream_ptr(w.device), rows, cols, _ptr(w), src_cols, int(transpose), _ptr(hi), _ptr(lo), ldp))
+    _check(lib().nnpops_split_planes(_stream_ptr(w.device), rows, cols, _ptr(w), ldw, int(transpose), _ptr(hi), _ptr(lo), ldp))
     return hi, lo
+
+
+def _operand(t, name, dtype):
+    """the device pointer of an operand given as a tensor or a view into a larger buffer (its own data pointer: a view may start
+    anywhere), or NULL for None"""
+    if t is None:
+        return None
+    if not t.is_cuda:
+        raise ValueError(f'"{name}" must live on the HIP device (nnpops_amd has no CPU path)')
+    if t.dtype != dtype:
+        raise ValueError(f'"{name}" must be {dtype}')
+    return _ptr(t)
+
+
+def gemm_split_strided(M, N, K, batch, A, lda, strideA, Bh, Bl, ldb, strideB, C_out, ldc, strideC, epilogue=0, bias=None, strideBias=0,
+                       Y=None, ldy=0, strideY=0, prologue=0, PY=None, ldpy=0, stridePY=0, pv=None, stridePv=0, alpha=0.1, a_scale=1.0,
+                       a_rows=None, c_rows=None):
+    """nnpops_gemm_split with its whole argument list (nnpops_hip.h), on buffers the caller owns: every tensor stands for the address
+    of its first element (a view into a larger buffer is taken where it starts), leading dimensions and strides count elements, and
+    nothing is allocated, copied or checked for extent here -- the caller vouches for ``batch`` problems ``stride*`` apart with rows
+    ``ld*`` apart.  A, bias, Y, PY, pv: float32; Bh, Bl: float16 planes; a_rows, c_rows: int32.  Writes C_out and returns it."""
+    dev = C_out.device
+    _check(lib().nnpops_gemm_split(_stream_ptr(dev), int(M), int(N), int(K), int(batch), _operand(A, "A", torch.float32), int(lda), int(strideA),
+                                   _operand(Bh, "Bh", torch.float16), _operand(Bl, "Bl", torch.float16), int(ldb), int(strideB),
+                                   _operand(C_out, "C_out", torch.float32), int(ldc), int(strideC), int(epilogue),
+                                   _operand(bias, "bias", torch.float32), int(strideBias), _operand(Y, "Y", torch.float32), int(ldy), int(strideY),
+                                   int(prologue), _operand(PY, "PY", torch.float32), int(ldpy), int(stridePY), _operand(pv, "pv", torch.float32),
+                                   int(stridePv), float(alpha), float(a_scale), _operand(a_rows, "a_rows", torch.int32),
+                                   _operand(c_rows, "c_rows", torch.int32)))
+    return C_out
+
+
+def gemm_split_last():
+    """-> (bn, k_split, fast) of the calling thread's last nnpops_gemm_split launch: the tile's columns (128 or 64), 2 where eight
+    waves split every K step, and whether the staging loads took the straight-line path.  Raises before the thread's first launch."""
+    bn, ks, fast = C.c_int(), C.c_int(), C.c_int()
+    _check(lib().nnpops_gemm_split_last(C.byref(bn), C.byref(ks), C.byref(fast)))
+    return bn.value, ks.value, fast.value
+
+
+def rows_dot(M, K, A, lda, w, bias, out, out_rows=None):
+    """nnpops_rows_dot on buffers the caller owns (as gemm_split_strided): out[out_rows ? out_rows[m] : m] = A[m][0..K) . w + bias
+    for m < M, rows of A ``lda`` floats apart.  A, w, out: float32; out_rows: int32; bias: a number.  Returns out."""
+    _check(lib().nnpops_rows_dot(_stream_ptr(out.device), int(M), int(K), _operand(A, "A", torch.float32), int(lda), _operand(w, "w", torch.float32),
+                                 float(bias), _operand(out, "out", torch.float32), _operand(out_rows, "out_rows", torch.int32)))
+    return out
 
 
 def gemm_split(a, planes, bias=None, celu_of=None, alpha=0.1, a_scale=1.0, out=None, a_rows=None, c_rows=None, rows=None):
     """out[M][N] = a[M][K] @ B, B = the planes of an [N][K] matrix (see split_planes).  ``bias``: add it and apply CELU;
-    ``celu_of``: multiply by CELU'(.) of that saved activation instead.  Single problem (the batched / strided form is
-    what the torch op uses)."""
+    ``celu_of``: multiply by CELU'(.) of that saved activation instead.  Single problem with dense rows (gemm_split_strided takes
+    the batched / strided form the torch op uses)."""
     a = _dev_f32(a, "a")
     hi, lo = planes
     m, k = a.shape
@@ -1047,11 +1098,8 @@ def gemm_split(a, planes, bias=None, celu_of=None, alpha=0.1, a_scale=1.0, out=N
     if out is None:
         out = torch.empty((m, n), dtype=torch.float32, device=a.device)
     epi = 1 if bias is not None else 2 if celu_of is not None else 0
-    _check(lib().nnpops_gemm_split(_stream_ptr(a.device), m, n, k, 1, _ptr(a), k, 0, _ptr(hi), _ptr(lo), hi.shape[1], 0, _ptr(out), n, 0,
-                                   epi, _ptr(bias) if bias is not None else None, 0, _ptr(celu_of) if celu_of is not None else None, n, 0,
-                                   0, None, 0, 0, None, 0, float(alpha), float(a_scale),
-                                   _ptr(a_rows) if a_rows is not None else None, _ptr(c_rows) if c_rows is not None else None))
-    return out
+    return gemm_split_strided(m, n, k, 1, a, k, 0, hi, lo, hi.shape[1], 0, out, n, 0, epilogue=epi, bias=bias, Y=celu_of, ldy=n,
+                              alpha=alpha, a_scale=a_scale, a_rows=a_rows, c_rows=c_rows)
 
 
 # ---- the atomic networks of a frame in two launches (mlp_fused.hip) ----

@@ -299,9 +299,44 @@ __global__ __launch_bounds__(256) void rows_dot(int M, int K, const float* __res
     if (lane == 0) out[out_rows ? out_rows[row] : row] = acc + bias;
 }
 
+// Which of the instantiations a call runs.  shape 0: 64 x 128 tiles, four waves, when they still give every CU a few workgroups;
+// 1: 64 x 64 tiles, four waves; 2: 64 x 64 tiles with eight waves splitting every K step (the layers of one species of a 2 000-atom
+// frame are 10-300 tiles: one wave per SIMD hides nothing).  fast: see gemm_h2 -- `a` is the matrix the staging loads read (PY under
+// the prologue), NNPOPS_GEMM_FAST=0 (read at every call) turns it off.
+struct GemmLaunch {
+    int shape = -1; bool fast = false;
+    int bn() const { return shape == 0 ? 128 : 64; }
+    int k_split() const { return shape == 2 ? 2 : 1; }
+};
+
+GemmLaunch choose_launch(int M, int N, int K, int batch, const float* a, long lda, long strideA, bool prologue, const float* pv,
+                         long stridePv) {
+    GemmLaunch L;
+    const long tiles128 = (long)((N + 127) / 128) * ((M + BM - 1) / BM) * batch;
+    const long tiles64 = (long)((N + 63) / 64) * ((M + BM - 1) / BM) * batch;
+    L.shape = tiles128 >= 512 ? 0 : tiles64 >= 600 ? 1 : 2;
+    const char* env = std::getenv("NNPOPS_GEMM_FAST");
+    L.fast = (K % 8) == 0 && (lda % 4) == 0 && ((uintptr_t)a % 16) == 0 && (batch == 1 || (strideA % 4) == 0) &&
+             (!prologue || (((uintptr_t)pv % 16) == 0 && (stridePv % 4) == 0)) && !(env && std::atoi(env) == 0);
+    return L;
+}
+
+GemmLaunch& last_launch() {                                 // host only, per thread: the last launch nnpops_gemm_split chose
+    static thread_local GemmLaunch slot;
+    return slot;
+}
+
 }  // namespace
 
 extern "C" {
+
+int nnpops_gemm_split_last(int* bn, int* k_split, int* fast) {
+    const GemmLaunch& L = last_launch();
+    NNPOPS_REQUIRE(L.shape >= 0, "no nnpops_gemm_split launch on this thread yet");
+    NNPOPS_REQUIRE(bn && k_split && fast, "NULL output pointer");
+    *bn = L.bn(); *k_split = L.k_split(); *fast = L.fast ? 1 : 0;
+    return NNPOPS_OK;
+}
 
 int nnpops_rows_dot(void* stream, int M, int K, const float* A, long lda, const float* w, float bias, float* out, const int* out_rows) {
     NNPOPS_REQUIRE(M > 0 && K > 0 && A && w && out, "empty problem or NULL device pointer");
@@ -337,22 +372,14 @@ int nnpops_gemm_split(void* stream, int M, int N, int K, int batch, const float*
     NNPOPS_REQUIRE((!a_rows && !c_rows) || batch == 1, "row maps are for single problems");
     GemmArgs g{M, N, K, A, lda, strideA, (const _Float16*)Bh, (const _Float16*)Bl, ldb, strideB, C, ldc, strideC, bias, strideBias,
                Y, ldy, strideY, PY, ldpy, stridePY, pv, stridePv, alpha, a_scale, a_rows, c_rows};
-    // 64 x 128 tiles, four waves, when they still give every CU a few workgroups; otherwise 64 x 64 tiles with eight waves
-    // splitting every K step (the layers of one species of a 2 000-atom frame are 10-300 tiles: one wave per SIMD hides
-    // nothing)
-    const long tiles128 = (long)((N + 127) / 128) * ((M + BM - 1) / BM) * batch;
-    const long tiles64 = (long)((N + 63) / 64) * ((M + BM - 1) / BM) * batch;
-    const int shape = tiles128 >= 512 ? 0 : tiles64 >= 600 ? 1 : 2;       // 0: 64x128 | 1: 64x64 | 2: 64x64, eight waves splitting K
-    const int bn = shape == 0 ? 128 : 64;
+    const GemmLaunch L = choose_launch(M, N, K, batch, prologue == 1 ? PY : A, prologue == 1 ? ldpy : lda,
+                                       prologue == 1 ? stridePY : strideA, prologue == 1, pv, stridePv);
+    const int shape = L.shape, bn = L.bn();
+    const bool fast = L.fast;
     const dim3 grid((N + bn - 1) / bn, (M + BM - 1) / BM, batch);
-    const size_t lds = (shape == 2 ? 2 : 1) * 2 * stage_bytes(bn);
+    const size_t lds = L.k_split() * 2 * stage_bytes(bn);
     hipStream_t st = (hipStream_t)stream;
-    const long lda_eff = prologue == 1 ? ldpy : lda;
-    const float* a_eff = prologue == 1 ? PY : A;
-    const bool fast = (K % 8) == 0 && (lda_eff % 4) == 0 && ((uintptr_t)a_eff % 16) == 0 &&
-                      (batch == 1 || ((prologue == 1 ? stridePY : strideA) % 4) == 0) &&
-                      (prologue == 0 || (((uintptr_t)pv % 16) == 0 && (stridePv % 4) == 0)) &&
-                      !(std::getenv("NNPOPS_GEMM_FAST") && std::atoi(std::getenv("NNPOPS_GEMM_FAST")) == 0);
+    last_launch() = L;                                      // (what nnpops_gemm_split_last reports: the very value the launch reads)
 #define NNPOPS_LAUNCH_GEMM_F(E, P, F) \
     do { if (shape == 0) hipLaunchKernelGGL((gemm_h2<E, P, 128, 1, F>), grid, dim3(256), lds, st, g); \
          else if (shape == 1) hipLaunchKernelGGL((gemm_h2<E, P, 64, 1, F>), grid, dim3(256), lds, st, g); \
