@@ -749,6 +749,27 @@ typedef struct {
 } nnpops_mlp_weight_grad_out;
 int64_t nnpops_mlp_weight_grad_workspace_bytes(const nnpops_mlp_frame* frame);
 int nnpops_mlp_weight_grad(void* stream, const nnpops_mlp_frame* frame, const nnpops_mlp_weight_grad_out* out);
+/* The gradient, in the same eight parameter arrays (shapes and padding as above), of a DIRECTIONAL DERIVATIVE of the networks:
+ *   M = sum_b sum_m member_weights[b][m] sum_{atoms a of molecule b} < t_a, dE_m(a)/dx_a >
+ * -- what a loss on forces asks for: t is the cotangent of the input gradient (through the AEV: its tangent J.v).  db6 is exactly zero.
+ * t: device [atoms][ldt] floats, rows and columns as x of the frame (with x_groups the columns outside the live blocks are not read
+ * and get a zero gradient); 16-byte aligned rows, ldt >= num_features, any magnitude (each row is normalised by a power of two inside).
+ * tangent_energies (optional): device [sum of num_atoms][num_members] in the grouped order of `energies`: E' = <t_a, dE_m(a)/dx_a>,
+ * UNWEIGHTED -- its sum over a molecule's atoms is dM/dmember_weights[b][m].
+ * The contract is nnpops_mlp_weight_grad's: SELF-CONTAINED (it runs the networks over the frame's x again and reads or writes none of
+ * energies, d1, dx_partial, dx); it honours member_weights(_ld), segment_offsets, num_segments, x_groups and act_scale_log2;
+ * deterministic (no atomics, no partial sums: the same bits every call); a member whose weight is zero for every molecule is
+ * skipped and gives zeros; kinds or frames without atoms give zeros; a bad descriptor returns NNPOPS_ERR_INVALID_ARGUMENT and launches
+ * nothing.  workspace: nnpops_mlp_weight_grad_tangent_workspace_bytes(frame) bytes, 16-byte aligned: (4 h1 + 4 h2 + 3 h3) floats per
+ * atom (rounded up to 32 per kind) and member. */
+typedef struct {
+    const float* t; int ldt;
+    void* workspace; int64_t workspace_bytes;
+    float* tangent_energies;
+    nnpops_mlp_weight_grad_kind kinds[NNPOPS_MLP_MAX_KINDS];
+} nnpops_mlp_weight_grad_tangent_out;
+int64_t nnpops_mlp_weight_grad_tangent_workspace_bytes(const nnpops_mlp_frame* frame);
+int nnpops_mlp_weight_grad_tangent(void* stream, const nnpops_mlp_frame* frame, const nnpops_mlp_weight_grad_tangent_out* out);
 /* out[0] = scale * sum(energies[0 .. count)) in double precision and a fixed order: the sum over atoms and the mean over
  * members of BatchedNN.py:109 (scale = 1 / num_members) in one small launch.  Device pointers. */
 int nnpops_mlp_energy_mean(void* stream, const float* energies, int64_t count, float scale, float* out);

@@ -514,8 +514,8 @@ class _TrainableFusedNN(_FusedSpeciesNN):
     (csrc/mlp_pack_networks.h: two launches, fresh tensors, the planes the host route writes bit for bit) and one small copy to the host
     that carries every decision (``device_packs`` counts those); the constructor, CPU parameters, other dtypes and a new list of live
     blocks pack on the host as the default module does.  The widths every species is packed at are fixed at construction from the
-    source networks; a rebuild that finds others raises and leaves the module as it was.  First derivatives only (no force-loss
-    training: use ``layout='grouped'``), not scriptable."""
+    source networks; a rebuild that finds others raises and leaves the module as it was.  First derivatives only (a loss on forces
+    trains ``force_trainable=True``), not scriptable."""
 
     __jit_ignored_attributes__ = ["_batch_plans", "_plane_versions", "_fixed_widths", "plane_rebuilds", "device_packs", "_blocks_packed"]
 
@@ -662,6 +662,29 @@ class _TrainableFusedNN(_FusedSpeciesNN):
         return super()._batch_call(op, holder, positions, shift)
 
 
+class _ForceTrainableFusedNN(_TrainableFusedNN):
+    """:class:`_TrainableFusedNN` for a loss on forces (``TorchANIBatchedNN(..., force_trainable=True)``): the same parameters, names,
+    state dicts, lazy plane rebuild and counters, behind ``torch.ops.NNPOpsBatchedNN.FusedMLPMembersForceTrainable`` /
+    ``FusedMLPMeanForceTrainable``.  Forward passes and -- without ``create_graph`` -- backward passes are those of ``trainable=True``,
+    bit for bit.  Under ``create_graph=True`` the backward pass is recorded: the gradient of the AEV comes with a graph whose own
+    backward, given the AEV's tangent ``J.v``, is ONE call of ``nnpops_mlp_weight_grad_tangent`` (csrc/mlp_weight_grad_tangent.h) for the
+    eight parameter gradients, and the gradient of the upstream tensor where a function of the member energies asks for it.  Refused
+    with a message: the gradient of a force in the AEV (Hessians, ``loss.backward()`` without ``inputs=``), second derivatives in the
+    parameters alone, third derivatives.  Not scriptable."""
+
+    @torch.jit.unused
+    def _trainable_op(self, aev: Tensor, shift: Optional[Tensor], batch: Optional[Tuple[Tensor, List[int], Tensor, Tensor]], mean: bool,
+                      total: bool = False, all_columns: bool = False) -> Tensor:
+        self._require_fused(training=True)
+        rows, sizes, places, offsets = batch if batch is not None else (self.atom_order32, self.group_sizes, None, None)
+        planes, x_blocks, dead_blocks = self._operands(all_columns)
+        args = (aev, rows, sizes, self.widths, self.num_models, planes, self.mlp_floats, x_blocks, dead_blocks, self.act_scale_log2, offsets, places,
+                shift, [getattr(self, name) for name in PARAMETER_NAMES])
+        if mean:
+            return torch.ops.NNPOpsBatchedNN.FusedMLPMeanForceTrainable(*args, total)
+        return torch.ops.NNPOpsBatchedNN.FusedMLPMembersForceTrainable(*args)
+
+
 class _SplitGemmSpeciesNN(_SpeciesGroupedNN):
     """(Round-1/2 default, kept as ``layout='gemm'`` for comparison and for widths the fused kernels do not take.)  The
     species-grouped networks on the library's own GEMM (``torch.ops.NNPOpsBatchedNN.GroupedMLP``, csrc/batched_nn.hip): fp32 in and out, products as split-fp16 matrix instructions with fp32 accumulation, bias + CELU
@@ -740,16 +763,27 @@ class TorchANIBatchedNN(nn.ModuleList):
     per-atom state dict still loads -- and every output is differentiable in them: ``'fused'`` through
     ``torch.ops.NNPOpsBatchedNN.FusedMLPMembersTrainable`` for one molecule on the device in float32 (first derivatives), plain torch
     otherwise and for ``'grouped'``.  Out of scope: scripting a trainable module, second derivatives through the fused op (training
-    on forces), periodic batches."""
+    on forces: ``force_trainable``), periodic batches.
 
-    def __init__(self, converter, ensemble, atomicNumbers: Tensor, layout: str = 'fused', trainable: bool = False):
+    ``force_trainable=True`` (extension; stands alone, ``'fused'`` and ``'grouped'`` only): the parameters of ``trainable=True`` -- same
+    names, state dicts interchange -- behind ``torch.ops.NNPOpsBatchedNN.FusedMLPMembersForceTrainable``, whose backward pass is recorded
+    under ``create_graph=True``, so that a loss on forces reaches the parameters (:class:`_ForceTrainableFusedNN`).  For ``'grouped'``,
+    which is plain torch and differentiable to any order, it is a synonym of ``trainable=True``."""
+
+    def __init__(self, converter, ensemble, atomicNumbers: Tensor, layout: str = 'fused', trainable: bool = False, force_trainable: bool = False):
         if layout not in ('fused', 'gemm', 'grouped', 'reference'):
             raise ValueError("layout must be 'fused', 'gemm', 'grouped' or 'reference'")
+        if force_trainable and trainable:
+            raise ValueError("force_trainable=True stands alone: it already has the parameters and the first derivatives of trainable=True")
         if trainable and layout not in ('fused', 'grouped'):
             raise ValueError(f"trainable=True needs layout='fused' or layout='grouped' (got {layout!r}: its packed operands have no weight gradient)")
+        if force_trainable and layout not in ('fused', 'grouped'):
+            raise ValueError(f"force_trainable=True needs layout='fused' or layout='grouped' (got {layout!r}: its packed operands have no weight gradient)")
         impl = {'fused': _FusedSpeciesNN, 'gemm': _SplitGemmSpeciesNN, 'grouped': _SpeciesGroupedNN, 'reference': _BatchedNN}[layout]
         if trainable:
             impl = {'fused': _TrainableFusedNN, 'grouped': _TrainableGroupedNN}[layout]
+        if force_trainable:
+            impl = {'fused': _ForceTrainableFusedNN, 'grouped': _TrainableGroupedNN}[layout]
         super().__init__([impl(converter, ensemble, atomicNumbers)])
 
     def forward(self, species_aev: Tuple[Tensor, Tensor]) -> SpeciesEnergies:

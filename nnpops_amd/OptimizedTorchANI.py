@@ -20,7 +20,12 @@ class OptimizedTorchANI(torch.nn.Module):
     ``trainable=True`` (extension): the networks' arrays are parameters (``TorchANIBatchedNN(..., trainable=True)``) and, with the
     fused layout, the instance becomes a :class:`TrainableOptimizedTorchANI`.
 
-    A loss on FORCES trains ``nn_layout='grouped', trainable=True`` (this composition; ``forward`` and ``forward_batch``), no flag::
+    ``force_trainable=True`` (extension; stands alone): the parameters of ``trainable=True`` behind nodes whose backward pass is recorded
+    under ``create_graph=True`` (``TorchANIBatchedNN(..., force_trainable=True)``); with the fused layout the instance becomes a
+    :class:`ForceTrainableOptimizedTorchANI`.
+
+    A loss on FORCES trains ``force_trainable=True`` on the fused layout (``forward``, ``forward_batch``, ``members_energies(_batch)``,
+    ``energies_qbcs(_batch)``) and ``nn_layout='grouped', trainable=True`` (this composition; ``forward`` and ``forward_batch``)::
 
         E = model((Z, x)).energies                                      # x.requires_grad_()
         F = -torch.autograd.grad(E.sum(), x, create_graph=True)[0]
@@ -31,23 +36,27 @@ class OptimizedTorchANI(torch.nn.Module):
     ``J.v`` (``Holder.tangent``), which autograd carries through the networks.  Refused with a message, never dropped: the gradient of
     a force in the POSITIONS (``loss.backward()`` without ``inputs=``, Hessians -- second derivatives of the AEV are not implemented),
     third derivatives, a forward pass on the same module between the forward and the derivatives that belong to it, and
-    ``create_graph=True`` with a cell that requires a gradient.  The fused layout still trains on energies only.
+    ``create_graph=True`` with a cell that requires a gradient.  The fused layout with ``trainable=True`` trains on energies only
+    (there ``create_graph=True`` is refused); ``force_trainable=True`` is the fused layout for a loss with forces in it.
 
-    Out of scope: scripting a trainable module, second derivatives through the fused networks, periodic batches."""
+    Out of scope: scripting a trainable module, second derivatives in positions or box, weight-weight second derivatives, periodic
+    batches."""
 
     def __init__(self, model, atomicNumbers: Tensor, nn_layout: str = 'fused', fused_step: bool = True, live_columns: bool = True,
-                 trainable: bool = False) -> None:
+                 trainable: bool = False, force_trainable: bool = False) -> None:
         super().__init__()
         self.species_converter = TorchANISpeciesConverter(model.species_converter, atomicNumbers)
         self.aev_computer = TorchANISymmetryFunctions(model.species_converter, model.aev_computer, atomicNumbers)
-        self.neural_networks = TorchANIBatchedNN(model.species_converter, model.neural_networks, atomicNumbers, layout=nn_layout, trainable=trainable)
+        self.neural_networks = TorchANIBatchedNN(model.species_converter, model.neural_networks, atomicNumbers, layout=nn_layout, trainable=trainable,
+                                                 force_trainable=force_trainable)
         self.energy_shifter = TorchANIEnergyShifter(model.species_converter, model.energy_shifter, atomicNumbers)
         nets = self.neural_networks[0]
         if fused_step and isinstance(nets, _FusedSpeciesNN) and nets.fused_ok:
             nets.holder = self.aev_computer.holder        # the networks' fused_energy() drives the AEV kernels itself
             if live_columns:                               # ... and multiplies only the AEV blocks this molecule's species can fill
                 nets.set_live_blocks(self.aev_computer.live_column_blocks())
-            self.__class__ = TrainableOptimizedTorchANI if trainable else FusedOptimizedTorchANI
+            self.__class__ = (ForceTrainableOptimizedTorchANI if force_trainable else TrainableOptimizedTorchANI if trainable
+                              else FusedOptimizedTorchANI)
 
     def forward(self, species_coordinates: Tuple[Tensor, Tensor], cell: Optional[Tensor] = None,
                 pbc: Optional[Tensor] = None) -> SpeciesEnergies:
@@ -267,3 +276,15 @@ class TrainableOptimizedTorchANI(FusedOptimizedTorchANI):
         shift = self._shift_for(coordinates)
         energies = nets.fused_mean(aev, shift, (rows, sizes, places, offsets))
         return SpeciesEnergies(species, energies) if shift is not None else self.energy_shifter((species, energies))
+
+
+class ForceTrainableOptimizedTorchANI(TrainableOptimizedTorchANI):
+    """``OptimizedTorchANI(..., force_trainable=True)`` on the fused layout: :class:`TrainableOptimizedTorchANI` -- the same methods, two
+    autograd nodes each, the same bits without ``create_graph`` -- on ``torch.ops.NNPOpsBatchedNN.FusedMLPMembersForceTrainable`` /
+    ``FusedMLPMeanForceTrainable``.  Under ``create_graph=True`` both nodes record their backward pass: the force comes with a graph,
+    and the parameter gradient of a loss with forces in it costs, next to the energy's own backward pass, the AEV tangent ``J.v`` and
+    ONE call of ``nnpops_mlp_weight_grad_tangent``.  A force evaluation alone launches no weight gradient.  Take the gradient with
+    ``loss.backward(inputs=parameters)`` or ``torch.autograd.grad(loss, parameters)``; refused with a message: the gradient of a force in
+    the positions (``loss.backward()`` without ``inputs=``, Hessians), second derivatives in the parameters alone, third derivatives, a
+    forward pass between a forward pass and its derivatives, and a cell that requires a gradient.  Out of scope: scripting, periodic
+    batches."""

@@ -97,6 +97,8 @@ SIGNATURES = {
     "nnpops_mlp_input_grad": (C.c_int, [C.c_void_p, C.c_void_p]),
     "nnpops_mlp_weight_grad_workspace_bytes": (C.c_int64, [C.c_void_p]),
     "nnpops_mlp_weight_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nnpops_mlp_weight_grad_tangent_workspace_bytes": (C.c_int64, [C.c_void_p]),
+    "nnpops_mlp_weight_grad_tangent": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_mlp_energy_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
     "nnpops_mlp_energy_mean_shifted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
     "nnpops_scale_by_scalar": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]),
@@ -1135,6 +1137,11 @@ class _MlpWeightGradOut(C.Structure):
     _fields_ = [("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("kinds", _MlpWeightGradKind * MLP_MAX_KINDS)]
 
 
+class _MlpWeightGradTangentOut(C.Structure):
+    _fields_ = [("t", C.c_void_p), ("ldt", C.c_int), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+                ("tangent_energies", C.c_void_p), ("kinds", _MlpWeightGradKind * MLP_MAX_KINDS)]
+
+
 MLP_PACK_STATUS_BYTES = 176
 MLP_PARAMETERS = tuple(f"layer{layer}_{what}" for layer in (0, 2, 4, 6) for what in ("weights", "biases"))
 
@@ -1336,6 +1343,42 @@ class FusedMLP:
             self.frame.segment_offsets, self.frame.num_segments = saved
         return [{name: t[tuple(slice(0, n) for n in shape)].contiguous() for name, t, shape in zip(MLP_GRADIENTS, arrays, shapes)}
                 for arrays, shapes in zip(full, self._shapes)]
+
+    def weight_grad_tangent(self, t, member_weights=None, molecule_offsets=None, tangent_energies=False):
+        """The gradient, in the networks' parameters, of  sum_b sum_m member_weights[b][m] sum_{a in b} <t_a, dE_m(a)/dx_a>  over the x of
+        the last forward(): ``t`` [atoms][>= x width] float32, rows and columns as x (the cotangent of input_grad()'s result under a loss
+        on forces).  Dicts as weight_grad() gives them; with ``tangent_energies`` also the float32 tensor [grouped atoms][M] of the
+        unweighted <t_a, dE_m(a)/dx_a>.  nnpops_mlp_weight_grad_tangent: self-contained like weight_grad()."""
+        if not self.frame.x:
+            raise RuntimeError("weight_grad_tangent() reads the x of the last forward(): call forward() first")
+        dev = self.device
+        t = _dev_f32(t, "t")
+        if t.dim() != 2 or t.shape[1] < self.x_width:
+            raise ValueError(f'"t" must be [atoms][>= {self.x_width}]')
+        if member_weights is not None:
+            member_weights = _dev_f32(member_weights, "member_weights")
+        full = [[torch.empty(shape, dtype=torch.float32, device=dev) for shape in shapes] for shapes in self._packed]
+        out = _MlpWeightGradTangentOut()
+        out.t, out.ldt = t.data_ptr(), t.shape[1]
+        need = int(lib().nnpops_mlp_weight_grad_tangent_workspace_bytes(C.byref(self.frame)))
+        ws = getattr(self, "_tangent_ws", None)
+        if ws is None or ws.numel() * 4 < need:
+            ws = self._tangent_ws = torch.empty((max(need // 4, 64),), dtype=torch.float32, device=dev)
+        out.workspace, out.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+        edot = torch.zeros((self.rows.numel(), self.M), dtype=torch.float32, device=dev) if tangent_energies else None
+        out.tangent_energies = edot.data_ptr() if edot is not None and edot.numel() else None
+        for k, arrays in enumerate(full):
+            for name, a in zip(MLP_GRADIENTS, arrays):
+                setattr(out.kinds[k], name, a.data_ptr())
+        saved = self._with_weights(member_weights, molecule_offsets)
+        try:
+            _check(lib().nnpops_mlp_weight_grad_tangent(_stream_ptr(dev), C.byref(self.frame), C.byref(out)))
+        finally:
+            self.frame.member_weights, self.frame.member_weights_ld = None, 0
+            self.frame.segment_offsets, self.frame.num_segments = saved
+        grads = [{name: a[tuple(slice(0, n) for n in shape)].contiguous() for name, a, shape in zip(MLP_GRADIENTS, arrays, shapes)}
+                 for arrays, shapes in zip(full, self._shapes)]
+        return (grads, edot) if tangent_energies else grads
 
     @staticmethod
     def pack_networks(parameters, widths, x_blocks=None):

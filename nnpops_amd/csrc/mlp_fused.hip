@@ -898,6 +898,8 @@ int check_and_fill(const nnpops_mlp_frame* fr, MlpArgs& g, bool grad, int blocks
     return NNPOPS_OK;
 }
 
+#include "mlp_weight_grad_tangent.h"         // (weight gradients of a directional derivative: its tile pass, contractions and launch)
+
 }  // namespace
 
 extern "C" {
@@ -1145,6 +1147,15 @@ int nnpops_mlp_weight_grad(void* stream, const nnpops_mlp_frame* frame, const nn
     hipLaunchKernelGGL(mlp_weight_contract<2>, dim3(max_blocks[2], g.M, g.num_kinds), dim3(256), 0, s, a);
     NNPOPS_HIP_TRY(hipGetLastError());
     return NNPOPS_OK;
+}
+
+int64_t nnpops_mlp_weight_grad_tangent_workspace_bytes(const nnpops_mlp_frame* frame) {
+    if (!frame || frame->num_kinds < 1 || frame->num_kinds > NNPOPS_MLP_MAX_KINDS || frame->num_members < 1) return 0;
+    return tg_workspace_floats(frame) * (int64_t)sizeof(float);
+}
+
+int nnpops_mlp_weight_grad_tangent(void* stream, const nnpops_mlp_frame* frame, const nnpops_mlp_weight_grad_tangent_out* out) {
+    return tg_launch(stream, frame, out);
 }
 
 }  // extern "C"

@@ -23,6 +23,7 @@
 //   * outputs are fresh tensors on every call (the reference re-returns the same storage,
 //     SymmetryFunctions.cpp:136-138,157) -- no caller can observe the difference except by aliasing bugs;
 //   * CFConv honours the current stream (the reference leaves that commented out, CFConv.cpp:167-170).
+#include <atomic>
 #include <c10/hip/HIPGuard.h>
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime_api.h>
@@ -3343,26 +3344,33 @@ struct MlpNodeState {
     c10::optional<Tensor> x_blocks, dead_blocks, offsets;
     MlpReduce mode;                   // (the trainable node: what its output was, and the eight parameters' [out, in])
     std::vector<int64_t> parameter_shapes;
+    c10::optional<Tensor> places;     // (the force-trainable node: the row places of a batch, and the parameters themselves -- the
+    std::vector<Tensor> parameters;   //  inputs of its recorded backward)
 
     int64_t molecules() const { return offsets.has_value() ? offsets->numel() - 1 : 1; }
 
     void save(AutogradContext* ctx) const {
         tensor_list keep = {x, rows, planes, floats, energies};
         keep.insert(keep.end(), workspace.begin(), workspace.end());
+        keep.insert(keep.end(), parameters.begin(), parameters.end());
         ctx->save_for_backward(keep);
         auto& d = ctx->saved_data;
         d["in_forward"] = in_forward; d["kind_atoms"] = kind_atoms; d["widths"] = widths; d["members"] = members;
         d["act_scale_log2"] = act_scale_log2; d["x_blocks"] = x_blocks; d["dead_blocks"] = dead_blocks; d["offsets"] = offsets;
         d["mean"] = (int64_t)mode; d["parameter_shapes"] = parameter_shapes;
+        if (!parameters.empty()) { d["places"] = places; d["parameters"] = (int64_t)parameters.size(); }
     }
     static MlpNodeState load(AutogradContext* ctx, const char* name) {
         const auto saved = ctx->get_saved_variables();
         TORCH_CHECK(!saved.empty(), name, " was evaluated without a gradient request");
         auto& d = ctx->saved_data;
-        return {saved[0], saved[1], saved[2], saved[3], saved[4], {saved.begin() + 5, saved.end()}, d["in_forward"].toBool(),
+        const bool force = d.count("parameters") != 0;
+        const auto behind = saved.end() - (force ? d["parameters"].toInt() : 0);
+        return {saved[0], saved[1], saved[2], saved[3], saved[4], {saved.begin() + 5, behind}, d["in_forward"].toBool(),
                 d["kind_atoms"].toIntVector(), d["widths"].toIntVector(), d["members"].toInt(), d["act_scale_log2"].toInt(),
                 d["x_blocks"].toOptional<Tensor>(), d["dead_blocks"].toOptional<Tensor>(), d["offsets"].toOptional<Tensor>(),
-                (MlpReduce)d["mean"].toInt(), d["parameter_shapes"].toIntVector()};
+                (MlpReduce)d["mean"].toInt(), d["parameter_shapes"].toIntVector(),
+                force ? d["places"].toOptional<Tensor>() : c10::optional<Tensor>(), {behind, saved.end()}};
     }
 };
 
@@ -3387,7 +3395,7 @@ Tensor mlp_members_forward(AutogradContext* ctx, const Tensor& x, const Tensor& 
                            const std::vector<int64_t>& widths, int64_t members, const Tensor& planes, const Tensor& floats,
                            const c10::optional<Tensor>& x_blocks, const c10::optional<Tensor>& dead_blocks, int64_t act_scale_log2,
                            const c10::optional<Tensor>& offsets, const c10::optional<Tensor>& places, const c10::optional<Tensor>& shift,
-                           bool need_gradient, MlpReduce mode, const std::vector<int64_t>& parameter_shapes) {
+                           bool need_gradient, MlpReduce mode, const std::vector<int64_t>& parameter_shapes, at::TensorList keep_parameters = {}) {
     const char* op = "NNPOpsBatchedNN::FusedMLPMembers";
     TORCH_CHECK(x.dim() == 2 && x.size(0) >= 1, "FusedMLPMembers: an empty batch (x must be [atoms, features] with at least one atom)");
     TORCH_CHECK(offsets.has_value() == places.has_value(), "FusedMLPMembers: molecule offsets and row places come together");
@@ -3410,7 +3418,8 @@ Tensor mlp_members_forward(AutogradContext* ctx, const Tensor& x, const Tensor& 
     mlp_reduce(stream, call, members, offsets.has_value() ? &*offsets : nullptr, places.has_value() ? &*places : nullptr, mode, shift, out, op);
     if (need_gradient)
         MlpNodeState{x, rows, planes, floats, call.energies, call.keep, call.frame.dx_partial != nullptr, kind_atoms, widths, members, act_scale_log2,
-                     x_blocks, dead_blocks, offsets, mode, parameter_shapes}.save(ctx);
+                     x_blocks, dead_blocks, offsets, mode, parameter_shapes, keep_parameters.empty() ? c10::optional<Tensor>() : places,
+                     keep_parameters.vec()}.save(ctx);
     return out;
 }
 
@@ -3464,16 +3473,23 @@ Tensor FusedMLPMembers(const Tensor& x, const Tensor& rows, std::vector<int64_t>
 // every (molecule, member) as its weights, the eight parameter gradients scattered into the module's shapes: entries outside a
 // kind's packed widths and the columns of dead AEV blocks are exact zeros.  First derivatives only.
 // =============================================================================================
+// (how many times this process has asked for the first-order gradients, and for those of a directional derivative: WeightGradientCalls)
+static std::atomic<int64_t> mlp_weight_gradient_calls[2];
 // The gradients of the eight parameter arrays for `upstream` [B, M] (float32, contiguous), the weight of every (molecule, member):
 // per-kind outputs at the packed widths, ONE call of nnpops_mlp_weight_grad, and the scatter into the module's shapes -- rows and
 // columns up to the smaller of the packed width and the module's, the first layer's columns where the live blocks lie; the rest zeros.
-tensor_list mlp_weight_gradients(void* stream, MlpCall& call, const MlpNodeState& s, const Tensor& upstream, const char* op) {
+// With `tangent` [atoms, width of x] (float32, contiguous) the gradients of the DIRECTIONAL DERIVATIVE of the networks along it instead
+// (nnpops_mlp_weight_grad_tangent: what a loss on forces asks for), and into `tangent_energies`, when given, the unweighted
+// <t_a, dE_m(a)/dx_a> [grouped atoms, M].
+tensor_list mlp_weight_gradients(void* stream, MlpCall& call, const MlpNodeState& s, const Tensor& upstream, const char* op,
+                                 const Tensor* tangent = nullptr, Tensor* tangent_energies = nullptr) {
+    mlp_weight_gradient_calls[tangent ? 1 : 0]++;
     mlp_point_upstream(call.frame, upstream, s.offsets);
     const auto options = s.x.options();
     const std::vector<int64_t>& shapes = s.parameter_shapes;
     const int64_t F = call.frame.num_features, M = s.members, kinds = (int64_t)s.kind_atoms.size();
     nnpops_mlp_weight_grad_out wg{};
-    const int64_t bytes = nnpops_mlp_weight_grad_workspace_bytes(&call.frame);
+    const int64_t bytes = tangent ? nnpops_mlp_weight_grad_tangent_workspace_bytes(&call.frame) : nnpops_mlp_weight_grad_workspace_bytes(&call.frame);
     Tensor workspace = torch::empty({std::max<int64_t>(bytes / 4, 64)}, options);
     wg.workspace = workspace.data_ptr<float>(); wg.workspace_bytes = workspace.numel() * 4;
     std::vector<std::array<Tensor, 8>> packed((size_t)kinds);
@@ -3486,7 +3502,14 @@ tensor_list mlp_weight_gradients(void* stream, MlpCall& call, const MlpNodeState
         float** slots[8] = {&o.dw0, &o.db0, &o.dw2, &o.db2, &o.dw4, &o.db4, &o.dw6, &o.db6};
         for (int i = 0; i < 8; i++) *slots[i] = packed[k][i].data_ptr<float>();
     }
-    if (nnpops_mlp_weight_grad(stream, &call.frame, &wg) != NNPOPS_OK) raise_last(op);
+    if (tangent) {
+        nnpops_mlp_weight_grad_tangent_out tg{};
+        tg.t = tangent->data_ptr<float>(); tg.ldt = (int)tangent->size(1);
+        tg.workspace = wg.workspace; tg.workspace_bytes = wg.workspace_bytes;
+        tg.tangent_energies = tangent_energies ? tangent_energies->data_ptr<float>() : nullptr;
+        for (int64_t k = 0; k < kinds; k++) tg.kinds[k] = wg.kinds[k];
+        if (nnpops_mlp_weight_grad_tangent(stream, &call.frame, &tg) != NNPOPS_OK) raise_last(op);
+    } else if (nnpops_mlp_weight_grad(stream, &call.frame, &wg) != NNPOPS_OK) raise_last(op);
     Tensor live_columns;
     if (call.frame.x_groups)
         live_columns = ((s.x_blocks->to(torch::kLong) * 16).unsqueeze(1) + torch::arange(16, s.x_blocks->options().dtype(torch::kLong)).unsqueeze(0)).reshape(-1);
@@ -3506,6 +3529,41 @@ tensor_list mlp_weight_gradients(void* stream, MlpCall& call, const MlpNodeState
         gradients.push_back(full);
     }
     return gradients;
+}
+
+// The backward pass of the trainable nodes for the upstream gradient `grad` of their output: the slots of forward's arguments with the
+// gradient of x in its place and -- with_weights -- the eight parameter gradients behind them.  weights_out: the weight of every
+// (molecule, member) that `grad` amounts to, [B, M] (what a weight gradient of this node takes as member_weights).
+tensor_list mlp_trainable_backward(const MlpNodeState& s, const Tensor& grad, bool with_weights, Tensor* weights_out, const char* op) {
+    const int64_t B = s.molecules();
+    c10::hip::HIPGuard guard(s.x.device().index());
+    void* stream = current_stream(s.x.device());
+    MlpCall call = prepare_backward(s);
+    tensor_list result(mlp_slot::parameters);             // (... and one for every parameter of the list behind them)
+    Tensor g;                                             // the weight of every (molecule, member) in the weight gradient
+    if (s.mode == MlpReduce::members) {
+        g = mlp_member_upstream(grad, s);
+        result[mlp_slot::x] = mlp_input_gradient(stream, call, s.x, 1.0f, &g, s.offsets, op);
+    } else {
+        // the gradient of x as the one-node step forms it -- the unweighted pass with 1 / M as its scale -- then times the upstream
+        // gradient of the row's molecule: with an upstream gradient of one, the bits energy_step hands to the AEV backward
+        const float mean_scale = s.mode == MlpReduce::total ? 1.0f : 1.0f / (float)s.members;
+        const Tensor up = grad.to(torch::kFloat32).contiguous();
+        TORCH_CHECK(up.numel() == B && up.device() == s.x.device(), "FusedMLPMeanTrainable: unexpected gradient of the energies (", B, " expected)");
+        g = (up.reshape({B, 1}) * mean_scale).expand({B, s.members}).contiguous();     // every member carries the upstream gradient over M
+        Tensor dx = mlp_input_gradient(stream, call, s.x, mean_scale, nullptr, c10::nullopt, op);
+        if (s.offsets.has_value()) {
+            const Tensor counts = (s.offsets->slice(0, 1, B + 1) - s.offsets->slice(0, 0, B)).to(torch::kLong);
+            dx.mul_(torch::repeat_interleave(up.reshape({B}), counts, 0, s.x.size(0)).unsqueeze(1));
+        } else {
+            dx.mul_(up.reshape({B}));
+        }
+        result[mlp_slot::x] = dx;
+    }
+    if (weights_out) *weights_out = g;
+    if (with_weights)
+        for (Tensor& gradient : mlp_weight_gradients(stream, call, s, g, op)) result.push_back(std::move(gradient));
+    return result;
 }
 
 class FusedMLPMembersTrainableFunction : public torch::autograd::Function<FusedMLPMembersTrainableFunction> {
@@ -3531,34 +3589,8 @@ public:
         TORCH_CHECK(!torch::GradMode::is_enabled(), "NNPOpsBatchedNN::FusedMLPMembersTrainable: second derivatives are not implemented (create_graph=True): "
                                                     "training on forces needs layout='grouped'");
         const MlpNodeState s = MlpNodeState::load(ctx, "FusedMLPMembersTrainable");
-        const int64_t B = s.molecules();
-        c10::hip::HIPGuard guard(s.x.device().index());
-        void* stream = current_stream(s.x.device());
-        MlpCall call = prepare_backward(s);
         static_assert(forward_arguments(&forward) == mlp_slot::parameters + 1, "one gradient slot for every argument of forward");
-        tensor_list result(mlp_slot::parameters);             // (... and one for every parameter of the list behind them)
-        Tensor g;                                             // the weight of every (molecule, member) in the weight gradient
-        if (s.mode == MlpReduce::members) {
-            g = mlp_member_upstream(grads[0], s);
-            result[mlp_slot::x] = mlp_input_gradient(stream, call, s.x, 1.0f, &g, s.offsets, op);
-        } else {
-            // the gradient of x as the one-node step forms it -- the unweighted pass with 1 / M as its scale -- then times the upstream
-            // gradient of the row's molecule: with an upstream gradient of one, the bits energy_step hands to the AEV backward
-            const float mean_scale = s.mode == MlpReduce::total ? 1.0f : 1.0f / (float)s.members;
-            const Tensor up = grads[0].to(torch::kFloat32).contiguous();
-            TORCH_CHECK(up.numel() == B && up.device() == s.x.device(), "FusedMLPMeanTrainable: unexpected gradient of the energies (", B, " expected)");
-            g = (up.reshape({B, 1}) * mean_scale).expand({B, s.members}).contiguous();     // every member carries the upstream gradient over M
-            Tensor dx = mlp_input_gradient(stream, call, s.x, mean_scale, nullptr, c10::nullopt, op);
-            if (s.offsets.has_value()) {
-                const Tensor counts = (s.offsets->slice(0, 1, B + 1) - s.offsets->slice(0, 0, B)).to(torch::kLong);
-                dx.mul_(torch::repeat_interleave(up.reshape({B}), counts, 0, s.x.size(0)).unsqueeze(1));
-            } else {
-                dx.mul_(up.reshape({B}));
-            }
-            result[mlp_slot::x] = dx;
-        }
-        for (Tensor& gradient : mlp_weight_gradients(stream, call, s, g, op)) result.push_back(std::move(gradient));
-        return result;
+        return mlp_trainable_backward(s, grads[0], true, nullptr, op);
     }
 };
 
@@ -3588,6 +3620,138 @@ Tensor FusedMLPMeanTrainable(const Tensor& x, const Tensor& rows, std::vector<in
     return FusedMLPMembersTrainableFunction::apply(x, rows, kind_atoms, widths, members, planes, floats, x_blocks, dead_blocks, act_scale_log2, offsets,
                                                    places, shift, needs_gradient(x, parameters), (int64_t)(total ? MlpReduce::total : MlpReduce::mean), parameters);
 }
+
+// =============================================================================================
+// FusedMLPMembersForceTrainable / FusedMLPMeanForceTrainable: the trainable nodes for a loss on FORCES.  Forward and -- with grad mode
+// off -- backward are the trainable nodes', bit for bit.  With grad mode on (create_graph=True) the backward pass is RECORDED, on the
+// model of AevBackwardFunction: MlpBackwardFunction's forward makes the calls the plain backward makes (the same bits of dx; the eight
+// first-order weight gradients only when the engine asks for them, so a force evaluation pays for none), and its own backward, given
+// the cotangent t of dx (through the AEV node: the tangent J.v), returns
+//   * the eight parameter gradients from ONE nnpops_mlp_weight_grad_tangent, the upstream gradient of every (molecule, member) as its
+//     weights, scattered as mlp_weight_gradients scatters them;
+//   * the gradient of the upstream tensor when that is asked for (a force of a function of the member energies whose weights depend
+//     on the parameters, as the QBC factors do): <t_a, dE_m(a)/dx_a> summed per (molecule, member), times the mode's scale.
+// Refused with a message, never dropped: the gradient of this node in x (the networks' Hessian in the AEV), a cotangent on one of the
+// first-order weight gradients (weight-weight second derivatives) and a third derivative.
+// =============================================================================================
+namespace mlp_back { enum : size_t { upstream = 0, parameters = 1, x = 9, state = 10, with_weights = 11, count = 12 }; }
+
+class MlpBackwardFunction : public torch::autograd::Function<MlpBackwardFunction> {
+public:
+    static tensor_list forward(AutogradContext* ctx, const Tensor& grad, at::TensorList parameters, const Tensor& x, const MlpNodeState& s,
+                               bool with_weights) {
+        const char* op = "NNPOpsBatchedNN::FusedMLPMembersForceTrainable (backward)";
+        Tensor weights;
+        tensor_list all = mlp_trainable_backward(s, grad, with_weights, &weights, op);      // (exactly the calls of the plain backward)
+        tensor_list out = {all[mlp_slot::x]};
+        out.insert(out.end(), all.begin() + mlp_slot::parameters, all.end());
+        s.save(ctx);
+        ctx->saved_data["upstream_weights"] = weights;
+        ctx->saved_data["upstream_sizes"] = grad.sizes().vec();
+        ctx->saved_data["upstream_double"] = grad.scalar_type() == torch::kFloat64;
+        ctx->set_materialize_grads(false);                 // (an output nobody differentiates hands back an undefined cotangent, not zeros)
+        return out;
+    }
+    static tensor_list backward(AutogradContext* ctx, const tensor_list& grads) {
+        const char* op = "NNPOpsBatchedNN::FusedMLPMembersForceTrainable";
+        TORCH_CHECK(!ctx->needs_input_grad(mlp_back::x), op, ": second derivatives with respect to the AEV are not implemented (the gradient "
+                    "of a force with respect to the positions was asked for: a Hessian, or loss.backward() on a loss of forces, which also "
+                    "differentiates in the positions).  The parameter gradient of a force loss is obtained with "
+                    "torch.autograd.grad(loss, parameters) or loss.backward(inputs=parameters)");
+        for (size_t i = 1; i < grads.size(); i++)
+            TORCH_CHECK(!grads[i].defined(), op, ": second derivatives with respect to the parameters are not implemented (a gradient of the "
+                        "networks' first-order weight gradients was asked for)");
+        const Tensor& v = grads[0];
+        TORCH_CHECK(!(torch::GradMode::is_enabled() && v.defined() && v.requires_grad()), op,
+                    ": third derivatives are not implemented (the derivative of a force was taken with create_graph=True)");
+        tensor_list out(mlp_back::count);                  // (one slot per argument, the parameter list taking eight)
+        if (!v.defined()) return out;
+        const MlpNodeState s = MlpNodeState::load(ctx, op);
+        TORCH_CHECK(v.dim() == 2 && v.size(0) == s.x.size(0) && v.size(1) == s.x.size(1) && v.device() == s.x.device(), op,
+                    ": unexpected cotangent of the AEV gradient");
+        const Tensor t = v.to(torch::kFloat32).contiguous();
+        const Tensor weights = ctx->saved_data["upstream_weights"].toTensor();
+        c10::hip::HIPGuard guard(s.x.device().index());
+        void* stream = current_stream(s.x.device());
+        MlpCall call = prepare_backward(s);
+        const bool want_upstream = ctx->needs_input_grad(mlp_back::upstream);
+        Tensor edot;
+        if (want_upstream) edot = torch::zeros({call.energies.size(0), s.members}, s.x.options());
+        tensor_list gradients = mlp_weight_gradients(stream, call, s, weights, op, &t, want_upstream ? &edot : nullptr);
+        for (size_t i = 0; i < 8; i++)
+            if (ctx->needs_input_grad(mlp_back::parameters + i)) out[mlp_back::parameters + i] = gradients[i];
+        if (want_upstream) {
+            const int64_t B = s.molecules();
+            Tensor sums = torch::empty({B, s.members}, s.x.options());
+            if (nnpops_mlp_member_sums(stream, edot.data_ptr<float>(), (int)edot.size(0), (int)s.members,
+                                       s.offsets.has_value() ? s.offsets->data_ptr<int32_t>() : nullptr, (int)B,
+                                       s.places.has_value() ? s.places->data_ptr<int32_t>() : nullptr, sums.data_ptr<float>()) != NNPOPS_OK) raise_last(op);
+            if (s.mode != MlpReduce::members) sums = sums.sum(1) * (s.mode == MlpReduce::total ? 1.0f : 1.0f / (float)s.members);
+            if (ctx->saved_data["upstream_double"].toBool()) sums = sums.to(torch::kFloat64);
+            out[mlp_back::upstream] = sums.reshape(ctx->saved_data["upstream_sizes"].toIntVector());
+        }
+        return out;
+    }
+};
+
+class FusedMLPForceTrainableFunction : public torch::autograd::Function<FusedMLPForceTrainableFunction> {
+public:
+    static Tensor forward(AutogradContext* ctx, const Tensor& x, const Tensor& rows, std::vector<int64_t> kind_atoms, std::vector<int64_t> widths,
+                          int64_t members, const Tensor& planes, const Tensor& floats, const c10::optional<Tensor>& x_blocks,
+                          const c10::optional<Tensor>& dead_blocks, int64_t act_scale_log2, const c10::optional<Tensor>& offsets,
+                          const c10::optional<Tensor>& places, const c10::optional<Tensor>& shift, bool need_gradient, int64_t mean,
+                          at::TensorList parameters) {
+        const int64_t kinds = (int64_t)kind_atoms.size();
+        TORCH_CHECK(parameters.size() == 8, "FusedMLPMembersForceTrainable: eight parameter tensors (layer{0,2,4,6}_{weights,biases}), got ", parameters.size());
+        std::vector<int64_t> shapes;
+        for (const Tensor& p : parameters) {
+            TORCH_CHECK(p.dim() == 4 && p.size(0) == kinds && p.size(1) == members && p.device() == x.device() && p.scalar_type() == torch::kFloat32,
+                        "FusedMLPMembersForceTrainable: parameters are float32 [kinds, members, out, in] tensors on the device of x");
+            shapes.push_back(p.size(2)); shapes.push_back(p.size(3));
+        }
+        // (the node's edges count its tensor inputs only: x, rows, planes, floats, the optional tensors that are there, then the parameters)
+        int64_t edge = 4;
+        for (const c10::optional<Tensor>* t : {&x_blocks, &dead_blocks, &offsets, &places, &shift})
+            if (t->has_value() && (*t)->defined()) edge++;
+        ctx->saved_data["parameter_edge"] = edge;
+        return mlp_members_forward(ctx, x, rows, kind_atoms, widths, members, planes, floats, x_blocks, dead_blocks, act_scale_log2, offsets, places,
+                                   shift, need_gradient, (MlpReduce)mean, shapes, parameters);
+    }
+    static tensor_list backward(AutogradContext* ctx, const tensor_list& grads) {
+        const char* op = "NNPOpsBatchedNN::FusedMLPMembersForceTrainable (backward)";
+        const MlpNodeState s = MlpNodeState::load(ctx, "FusedMLPMembersForceTrainable");
+        static_assert(forward_arguments(&forward) == mlp_slot::parameters + 1, "one gradient slot for every argument of forward");
+        if (!torch::GradMode::is_enabled()) return mlp_trainable_backward(s, grads[0], true, nullptr, op);
+        const size_t edge = (size_t)ctx->saved_data["parameter_edge"].toInt();
+        bool with_weights = false;
+        for (size_t i = 0; i < 8; i++) with_weights = with_weights || ctx->needs_input_grad(edge + i);
+        // (the list goes in as a TensorList: a std::vector would be taken for a non-tensor argument and the node would have no edge to a parameter)
+        const tensor_list recorded = MlpBackwardFunction::apply(grads[0], at::TensorList(s.parameters), s.x, s, with_weights);
+        tensor_list result(mlp_slot::parameters);
+        result[mlp_slot::x] = recorded[0];
+        for (size_t i = 0; i < 8; i++) result.push_back(with_weights ? recorded[1 + i] : Tensor());
+        return result;
+    }
+};
+
+Tensor FusedMLPMembersForceTrainable(const Tensor& x, const Tensor& rows, std::vector<int64_t> kind_atoms, std::vector<int64_t> widths, int64_t members,
+                                     const Tensor& planes, const Tensor& floats, const c10::optional<Tensor>& x_blocks,
+                                     const c10::optional<Tensor>& dead_blocks, int64_t act_scale_log2, const c10::optional<Tensor>& offsets,
+                                     const c10::optional<Tensor>& places, const c10::optional<Tensor>& shift, at::TensorList parameters) {
+    return FusedMLPForceTrainableFunction::apply(x, rows, kind_atoms, widths, members, planes, floats, x_blocks, dead_blocks, act_scale_log2, offsets,
+                                                 places, shift, needs_gradient(x, parameters), (int64_t)MlpReduce::members, parameters);
+}
+
+Tensor FusedMLPMeanForceTrainable(const Tensor& x, const Tensor& rows, std::vector<int64_t> kind_atoms, std::vector<int64_t> widths, int64_t members,
+                                  const Tensor& planes, const Tensor& floats, const c10::optional<Tensor>& x_blocks,
+                                  const c10::optional<Tensor>& dead_blocks, int64_t act_scale_log2, const c10::optional<Tensor>& offsets,
+                                  const c10::optional<Tensor>& places, const c10::optional<Tensor>& shift, at::TensorList parameters, bool total) {
+    return FusedMLPForceTrainableFunction::apply(x, rows, kind_atoms, widths, members, planes, floats, x_blocks, dead_blocks, act_scale_log2, offsets,
+                                                 places, shift, needs_gradient(x, parameters), (int64_t)(total ? MlpReduce::total : MlpReduce::mean), parameters);
+}
+
+// [first-order weight gradients, weight gradients of a directional derivative] this process has launched through the nodes above
+std::vector<int64_t> WeightGradientCalls() { return {mlp_weight_gradient_calls[0].load(), mlp_weight_gradient_calls[1].load()}; }
 
 // =============================================================================================
 // PackNetworks: the packed planes of FusedMLP* from the eight parameter arrays of a module ([kinds, M, out, in] / [kinds, M, out, 1],
@@ -3648,6 +3812,13 @@ TORCH_LIBRARY(NNPOpsBatchedNN, m) {
     m.def("FusedMLPMeanTrainable(Tensor x, Tensor rows, int[] kind_atoms, int[] widths, int members, Tensor planes, Tensor floats, Tensor? x_blocks, "
           "Tensor? dead_blocks, int act_scale_log2, Tensor? offsets, Tensor? places, Tensor? shift, Tensor[] parameters, bool total=False) -> Tensor",
           FusedMLPMeanTrainable);
+    m.def("FusedMLPMembersForceTrainable(Tensor x, Tensor rows, int[] kind_atoms, int[] widths, int members, Tensor planes, Tensor floats, Tensor? x_blocks, "
+          "Tensor? dead_blocks, int act_scale_log2, Tensor? offsets, Tensor? places, Tensor? shift, Tensor[] parameters) -> Tensor",
+          FusedMLPMembersForceTrainable);
+    m.def("FusedMLPMeanForceTrainable(Tensor x, Tensor rows, int[] kind_atoms, int[] widths, int members, Tensor planes, Tensor floats, Tensor? x_blocks, "
+          "Tensor? dead_blocks, int act_scale_log2, Tensor? offsets, Tensor? places, Tensor? shift, Tensor[] parameters, bool total=False) -> Tensor",
+          FusedMLPMeanForceTrainable);
+    m.def("WeightGradientCalls() -> int[]", WeightGradientCalls);
     m.def("FusedMLPMembers(Tensor x, Tensor rows, int[] kind_atoms, int[] widths, int members, Tensor planes, Tensor floats, Tensor? x_blocks=None, "
           "Tensor? dead_blocks=None, int act_scale_log2=4, Tensor? offsets=None, Tensor? places=None, Tensor? shift=None) -> Tensor", FusedMLPMembers);
     m.def("FusedMLP(Tensor x, Tensor rows, int[] kind_atoms, int[] widths, int members, Tensor planes, Tensor floats, int act_scale_log2=4) -> Tensor", FusedMLP);
