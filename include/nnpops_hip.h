@@ -87,7 +87,9 @@ int nnpops_ani_set_stream(nnpops_ani_t h, void* stream);
 /* positions: device [num_atoms][3]; box: device [3][3] rows = box vectors (ignored, may be NULL,
  * when the handle is not periodic); radial: device [num_atoms][num_species][num_radial];
  * angular: device [num_atoms][num_species*(num_species+1)/2][num_angular].  Outputs are fully
- * overwritten.  Positions / box / neighbour lists are retained for backprop. */
+ * overwritten.  Positions / box / neighbour lists are retained for backprop.
+ * A periodic handle with molecules (nnpops_ani_set_molecules): box is device [num_molecules][3][3], molecule m uses rows
+ * 9m .. 9m+8 and wraps the displacements among its own atoms in it. */
 int nnpops_ani_compute(nnpops_ani_t h, const float* positions, const float* box, float* radial, float* angular);
 /* radial_deriv / angular_deriv: device, shapes as the outputs above; position_deriv: device
  * [num_atoms][3], fully overwritten.  Must follow a compute() on the same handle. */
@@ -106,7 +108,13 @@ int nnpops_ani_backprop_strided(nnpops_ani_t h, const float* radial_deriv, int r
  * formal derivative as nnpops_neighbor_pairs_box_backward.  box_deriv: device [3][3], fully overwritten (float32, accumulated in
  * float64 in a fixed order: two calls agree bit for bit); position_deriv is exactly what backprop_strided writes.
  * CONTRACT: positions and box are the arrays of the preceding compute(), unchanged -- the shifts are recovered from them and from
- * the displacements the handle kept, not stored.  Periodic handles only, and not with nnpops_ani_set_molecules (NNPOPS_ERR_INVALID_ARGUMENT).
+ * the displacements the handle kept, not stored.  Periodic handles only (NNPOPS_ERR_INVALID_ARGUMENT otherwise, with or without
+ * molecules).
+ * A periodic handle with molecules (a periodic batch, nnpops_ani_set_molecules): box and box_deriv are device [num_molecules][3][3];
+ * molecule m's nine entries are the same sum over the displacements of ITS atoms only, shifts recovered against box m.  A number of
+ * workgroups per molecule that depends on its atom count alone, then one sum per molecule: float64, a fixed order, no atomics, the
+ * partial sums in a workspace nnpops_ani_set_molecules sized: two calls agree bit for bit and
+ * a molecule's entries do not depend on its companions.  position_deriv is again exactly what backprop_strided writes.
  * Allocates nothing: graph-capturable like backprop.  Additive. */
 int nnpops_ani_backprop_box_strided(nnpops_ani_t h, const float* positions, const float* box, const float* radial_deriv, int radial_ld,
                                     const float* angular_deriv, int angular_ld, float* position_deriv, float* box_deriv);
@@ -153,7 +161,8 @@ int nnpops_ani_read_grid(nnpops_ani_t h, int32_t* out);
  * chunked | mfma; backward= kernel number; generic= the function list does not factor; uniform= one eta and one zeta; grid= eight
  * radial factors on equally spaced shifts (taken by recurrence); literal= the constants are the published ANI-2x set and the
  * forward kernels carry them as literals; dynamic_quads, fused_build, cap, cap_angular, chunk, classes, cells: state after the last
- * compute() / check().  What the last backprop() launched (host-side records, no device work): bwd_mode= 0 the first-generation
+ * compute() / check().  A periodic handle with molecules appends batch_boxes=1 (the builder with one box per molecule runs); on every
+ * other handle the word is absent.  What the last backprop() launched (host-side records, no device work): bwd_mode= 0 the first-generation
  * angular backward (what runs when the pair matrix of the records does not fit the LDS, or on request), 1-4 the pair-matrix
  * kernels (1 / 3 one / two waves per atom with 16-byte gradient loads, 2 / 4 the same with the gradient row staged in LDS; where
  * the launch ran by class, the top class's mode); radial_bwd= lanes | rows (a lane per neighbour, or the first-generation row
@@ -177,12 +186,18 @@ int nnpops_ani_check_end(nnpops_ani_t h);
  * algorithm, O(N^2)), 2 = cell list (O(N); periodic boxes must be at least 3 cells wide per axis). */
 int nnpops_ani_set_neighbor_algorithm(nnpops_ani_t h, int algorithm);
 
-/* Batched evaluation of independent NON-PERIODIC molecules in one handle (the reference has no batch
+/* Batched evaluation of independent molecules (or periodic frames) in one handle (the reference has no batch
  * dimension: src/pytorch/SymmetryFunctions.py:110; this is the additive API SURVEY.md s8f ranks second).
  * Atoms [molecule_offsets[m], molecule_offsets[m+1]) form molecule m (host array, num_molecules+1 entries,
  * first 0, last num_atoms); atoms of different molecules never see each other.  compute()/backprop() are
  * unchanged -- every kernel is per atom -- so one launch sequence evaluates the whole batch.
- * num_molecules <= 0 restores the single-system behaviour. */
+ * On a PERIODIC handle every molecule is a frame in a box of its own: the box of compute() / backprop_box is then a device
+ * array [num_molecules][3][3] (molecule m: rows 9m .. 9m+8), and the atoms of molecule m see each other through the minimum
+ * image of box m -- the single-round rule of a single frame (z, then y, then x, each by the diagonal entry).  As for a single
+ * frame every box must be at least two radial cutoffs wide; that is the caller's contract and is not checked on the device.
+ * The neighbour search of a batch is the all-pairs scan inside the molecule (never the cell grid): meant for frames of tens to
+ * a few hundred atoms -- a 64-water box -- not for frames of thousands.
+ * num_molecules <= 0 restores the single-system behaviour (a periodic handle: one [3][3] box again). */
 int nnpops_ani_set_molecules(nnpops_ani_t h, int num_molecules, const int32_t* molecule_offsets);
 
 /* Per-kernel timing with HIP events recorded on the handle's stream around kernel launches

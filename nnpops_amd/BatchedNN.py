@@ -438,7 +438,7 @@ class _FusedSpeciesNN(_SpeciesGroupedNN):
         one of TorchANISymmetryFunctions.batch_holder: no second holder for the same size), the rows of the batch * N atoms grouped by
         species -- conformer after conformer inside a species --, the group sizes, the place of every row in that order and the
         molecule offsets.  The packed planes, live blocks and activation scale are the ones of the single-molecule step."""
-        key = (batch, str(device))
+        key = (batch, str(device), id(holder))      # (the periodic and the non-periodic holder of one batch size each keep their plan)
         plan = self._batch_plans.get(key)
         if plan is None or plan[0] is not holder:
             n = self.num_atoms
@@ -458,24 +458,26 @@ class _FusedSpeciesNN(_SpeciesGroupedNN):
         return plan
 
     @torch.jit.unused
-    def _batch_call(self, op, holder, positions: Tensor, shift: Optional[Tensor]):
+    def _batch_call(self, op, holder, positions: Tensor, shift: Optional[Tensor], cell: Optional[Tensor] = None):
         self._require_fused()
         holder, rows, sizes, places, offsets = self._batch_plan(holder, int(positions.shape[0]), positions.device)
         planes, x_blocks, dead_blocks = self._operands()
-        return op(holder, positions, None, rows, sizes, self.widths, self.num_models, planes, self.mlp_floats, offsets, places, shift,
+        return op(holder, positions, cell, rows, sizes, self.widths, self.num_models, planes, self.mlp_floats, offsets, places, shift,
                   x_blocks, dead_blocks, self.act_scale_log2)
 
     @torch.jit.unused
-    def fused_energy_batch(self, holder, positions: Tensor, shift: Optional[Tensor] = None) -> Tensor:
+    def fused_energy_batch(self, holder, positions: Tensor, shift: Optional[Tensor] = None, cell: Optional[Tensor] = None) -> Tensor:
         """fused_energy() for B conformers (only inside OptimizedTorchANI, which hands over the batched AEV holder): positions [B, N, 3]
         -> ensemble-mean energies [B] as one autograd node (``torch.ops.NNPOpsANISymmetryFunctions.energy_batch``); float64 and shifted
-        with ``shift``."""
-        return self._batch_call(torch.ops.NNPOpsANISymmetryFunctions.energy_batch, holder, positions, shift)
+        with ``shift``.  ``cell`` [B, 3, 3]: a periodic batch, every frame in its own box (``holder`` is then the periodic batch holder);
+        a cell that requires a gradient gets dE_b/dcell_b."""
+        return self._batch_call(torch.ops.NNPOpsANISymmetryFunctions.energy_batch, holder, positions, shift, cell)
 
     @torch.jit.unused
-    def fused_energy_forces_batch(self, holder, positions: Tensor, shift: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
-        """The same step outside autograd: (energies [B], forces [B, N, 3] = -dE_b/dpositions)."""
-        return self._batch_call(torch.ops.NNPOpsANISymmetryFunctions.energy_forces_batch, holder, positions, shift)
+    def fused_energy_forces_batch(self, holder, positions: Tensor, shift: Optional[Tensor] = None,
+                                  cell: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+        """The same step outside autograd: (energies [B], forces [B, N, 3] = -dE_b/dpositions); no virial."""
+        return self._batch_call(torch.ops.NNPOpsANISymmetryFunctions.energy_forces_batch, holder, positions, shift, cell)
 
 
 PARAMETER_NAMES = tuple(f'layer{ilayer}_{what}' for ilayer in (0, 2, 4, 6) for what in ('weights', 'biases'))
@@ -763,7 +765,7 @@ class TorchANIBatchedNN(nn.ModuleList):
     per-atom state dict still loads -- and every output is differentiable in them: ``'fused'`` through
     ``torch.ops.NNPOpsBatchedNN.FusedMLPMembersTrainable`` for one molecule on the device in float32 (first derivatives), plain torch
     otherwise and for ``'grouped'``.  Out of scope: scripting a trainable module, second derivatives through the fused op (training
-    on forces: ``force_trainable``), periodic batches.
+    on forces: ``force_trainable``).
 
     ``force_trainable=True`` (extension; stands alone, ``'fused'`` and ``'grouped'`` only): the parameters of ``trainable=True`` -- same
     names, state dicts interchange -- behind ``torch.ops.NNPOpsBatchedNN.FusedMLPMembersForceTrainable``, whose backward pass is recorded
@@ -807,9 +809,10 @@ class TorchANIBatchedNN(nn.ModuleList):
         self[0].set_check_interval(interval)
 
     @torch.jit.unused
-    def fused_energy_batch(self, holder, positions: Tensor, shift: Optional[Tensor] = None) -> Tensor:
-        return self[0].fused_energy_batch(holder, positions, shift)
+    def fused_energy_batch(self, holder, positions: Tensor, shift: Optional[Tensor] = None, cell: Optional[Tensor] = None) -> Tensor:
+        return self[0].fused_energy_batch(holder, positions, shift, cell)
 
     @torch.jit.unused
-    def fused_energy_forces_batch(self, holder, positions: Tensor, shift: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
-        return self[0].fused_energy_forces_batch(holder, positions, shift)
+    def fused_energy_forces_batch(self, holder, positions: Tensor, shift: Optional[Tensor] = None,
+                                  cell: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+        return self[0].fused_energy_forces_batch(holder, positions, shift, cell)

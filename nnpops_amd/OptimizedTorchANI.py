@@ -39,8 +39,11 @@ class OptimizedTorchANI(torch.nn.Module):
     ``create_graph=True`` with a cell that requires a gradient.  The fused layout with ``trainable=True`` trains on energies only
     (there ``create_graph=True`` is refused); ``force_trainable=True`` is the fused layout for a loss with forces in it.
 
-    Out of scope: scripting a trainable module, second derivatives in positions or box, weight-weight second derivatives, periodic
-    batches."""
+    Periodic batches (extension): every ``*_batch`` method takes ``cell`` [B, 3, 3] with ``pbc`` all True -- B periodic frames, each in
+    its own box (see ``forward_batch``) -- on every layout, ``trainable`` and ``force_trainable`` included.
+
+    Out of scope: scripting a trainable module, second derivatives in positions or box, weight-weight second derivatives, frames of
+    thousands of atoms in a periodic batch (its neighbour search is the all-pairs scan inside each frame)."""
 
     def __init__(self, model, atomicNumbers: Tensor, nn_layout: str = 'fused', fused_step: bool = True, live_columns: bool = True,
                  trainable: bool = False, force_trainable: bool = False) -> None:
@@ -67,11 +70,10 @@ class OptimizedTorchANI(torch.nn.Module):
 
     @torch.jit.unused
     def _batch_arguments(self, species_coordinates: Tuple[Tensor, Tensor], cell: Optional[Tensor], pbc: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
-        """The argument errors of the batched methods; -> (species [B, N] of the module's molecule, coordinates [B, N, 3])."""
-        if cell is not None or pbc is not None:
-            raise ValueError('Batches of conformers are non-periodic: "cell" and "pbc" are not supported')
+        """The argument errors of the batched methods; -> (species [B, N] of the module's molecule, coordinates [B, N, 3]).  A batch is
+        non-periodic, or periodic with ``cell`` [B, 3, 3] -- one box per frame -- and ``pbc`` all True."""
         coordinates = species_coordinates[1]
-        batch = self.aev_computer.check_batch_arguments(coordinates)
+        batch = self.aev_computer.check_batch_arguments(coordinates, cell, pbc)
         if batch < 1:
             raise ValueError('"positions" has to hold at least one conformer')
         return self.species_converter.species.expand(batch, -1), coordinates
@@ -79,12 +81,16 @@ class OptimizedTorchANI(torch.nn.Module):
     @torch.jit.unused
     def forward_batch(self, species_coordinates: Tuple[Tensor, Tensor], cell: Optional[Tensor] = None,
                       pbc: Optional[Tensor] = None) -> SpeciesEnergies:
-        """Extension (the reference scores one molecule per call): B conformers of THE molecule this module was built for, non-periodic.
+        """Extension (the reference scores one molecule per call): B conformers of THE molecule this module was built for.
         (species[B, N], coordinates[B, N, 3]) -> SpeciesEnergies(species, energies[B]), one float64 energy per conformer, shifted by the
         molecule's self energy as ``forward`` returns it, differentiable with respect to the coordinates.  Here: the composition of
-        ``aev_computer.forward_batch``, the networks and the shifter."""
+        ``aev_computer.forward_batch``, the networks and the shifter.
+
+        Periodic batches: ``cell`` [B, 3, 3] with ``pbc`` all True scores B periodic frames, each in its own box (a minibatch of an
+        NPT trajectory); a cell that requires a gradient gets ``cell.grad`` [B, 3, 3], from which each frame's stress follows as in
+        ``forward``.  Every batched method takes the same two arguments."""
         species, coordinates = self._batch_arguments(species_coordinates, cell, pbc)
-        species_aevs = self.aev_computer.forward_batch((species, coordinates))
+        species_aevs = self.aev_computer.forward_batch((species, coordinates), cell, pbc)
         species_energies = self.neural_networks(species_aevs)
         return self.energy_shifter(species_energies)
 
@@ -105,7 +111,7 @@ class OptimizedTorchANI(torch.nn.Module):
         """``members_energies`` for B conformers of the module's molecule (arguments and checks of ``forward_batch``):
         SpeciesEnergies(species, energies [models, B])."""
         species, coordinates = self._batch_arguments(species_coordinates, cell, pbc)
-        species_aevs = self.aev_computer.forward_batch((species, coordinates))
+        species_aevs = self.aev_computer.forward_batch((species, coordinates), cell, pbc)
         members = self.neural_networks.members_energies(species_aevs).energies
         return SpeciesEnergies(species, members + self.energy_shifter.self_energies)
 
@@ -191,11 +197,11 @@ class FusedOptimizedTorchANI(OptimizedTorchANI):
         by its own upstream gradient.  An energy is the same bits wherever its conformer stands in whatever batch.  Second
         derivatives are refused, as in ``forward``."""
         species, coordinates = self._batch_arguments(species_coordinates, cell, pbc)
-        holder = self.aev_computer.batch_holder(int(coordinates.shape[0]))
+        holder = self.aev_computer.batch_holder(int(coordinates.shape[0]), cell is not None)
         shift = self.energy_shifter.self_energies
         if shift.dtype == torch.float64 and shift.numel() == 1 and shift.device == coordinates.device:
-            return SpeciesEnergies(species, self.neural_networks.fused_energy_batch(holder, coordinates, shift))
-        return self.energy_shifter((species, self.neural_networks.fused_energy_batch(holder, coordinates)))
+            return SpeciesEnergies(species, self.neural_networks.fused_energy_batch(holder, coordinates, shift, cell))
+        return self.energy_shifter((species, self.neural_networks.fused_energy_batch(holder, coordinates, None, cell)))
 
     @torch.jit.unused
     def _shift_for(self, positions: Tensor) -> Optional[Tensor]:
@@ -224,8 +230,8 @@ class FusedOptimizedTorchANI(OptimizedTorchANI):
         species, coordinates = self._batch_arguments(species_coordinates, cell, pbc)
         batch, atoms = int(coordinates.shape[0]), int(coordinates.shape[1])
         nets = self.neural_networks[0]
-        holder, rows, sizes, places, offsets = nets._batch_plan(self.aev_computer.batch_holder(batch), batch, coordinates.device)
-        aev = torch.ops.NNPOpsANISymmetryFunctions.aev(holder, coordinates.reshape(batch * atoms, 3), None)
+        holder, rows, sizes, places, offsets = nets._batch_plan(self.aev_computer.batch_holder(batch, cell is not None), batch, coordinates.device)
+        aev = torch.ops.NNPOpsANISymmetryFunctions.aev(holder, coordinates.reshape(batch * atoms, 3), cell)
         shift = self._shift_for(coordinates)
         members = nets.fused_members(aev, shift, (rows, sizes, places, offsets)).t()
         return SpeciesEnergies(species, members if shift is not None else members + self.energy_shifter.self_energies)
@@ -236,11 +242,11 @@ class FusedOptimizedTorchANI(OptimizedTorchANI):
         """Extension: (energies [B], forces [B, N, 3] = -dE_b/dcoordinates) of B conformers from ONE call, outside autograd -- the
         counterpart of ``energy_and_forces``; the energies of ``forward_batch`` and the negated gradients, bit for bit."""
         _, coordinates = self._batch_arguments(species_coordinates, cell, pbc)
-        holder = self.aev_computer.batch_holder(int(coordinates.shape[0]))
+        holder = self.aev_computer.batch_holder(int(coordinates.shape[0]), cell is not None)
         shift = self.energy_shifter.self_energies
         if shift.dtype == torch.float64 and shift.numel() == 1 and shift.device == coordinates.device:
-            return self.neural_networks.fused_energy_forces_batch(holder, coordinates, shift)
-        energies, forces = self.neural_networks.fused_energy_forces_batch(holder, coordinates)
+            return self.neural_networks.fused_energy_forces_batch(holder, coordinates, shift, cell)
+        energies, forces = self.neural_networks.fused_energy_forces_batch(holder, coordinates, None, cell)
         return energies + self.energy_shifter.self_energies, forces
 
 
@@ -252,8 +258,7 @@ class TrainableOptimizedTorchANI(FusedOptimizedTorchANI):
     gradient, one call of their weight gradient and the AEV backward, whatever function of the energies was differentiated.
     Energies and coordinate gradients are the bits of the default module at equal weights.  ``energy_and_forces`` /
     ``energy_and_forces_batch`` stay outside autograd and use the current weights.  Out of scope: scripting, second derivatives (a
-    loss on forces trains ``nn_layout='grouped'``, see :class:`OptimizedTorchANI`; here ``create_graph=True`` is refused), periodic
-    batches, a gradient of the cell."""
+    loss on forces trains ``nn_layout='grouped'``, see :class:`OptimizedTorchANI`; here ``create_graph=True`` is refused)."""
 
     def forward(self, species_coordinates: Tuple[Tensor, Tensor], cell: Optional[Tensor] = None,
                 pbc: Optional[Tensor] = None) -> SpeciesEnergies:
@@ -271,8 +276,8 @@ class TrainableOptimizedTorchANI(FusedOptimizedTorchANI):
         species, coordinates = self._batch_arguments(species_coordinates, cell, pbc)
         batch, atoms = int(coordinates.shape[0]), int(coordinates.shape[1])
         nets = self.neural_networks[0]
-        holder, rows, sizes, places, offsets = nets._batch_plan(self.aev_computer.batch_holder(batch), batch, coordinates.device)
-        aev = torch.ops.NNPOpsANISymmetryFunctions.aev(holder, coordinates.reshape(batch * atoms, 3), None)
+        holder, rows, sizes, places, offsets = nets._batch_plan(self.aev_computer.batch_holder(batch, cell is not None), batch, coordinates.device)
+        aev = torch.ops.NNPOpsANISymmetryFunctions.aev(holder, coordinates.reshape(batch * atoms, 3), cell)
         shift = self._shift_for(coordinates)
         energies = nets.fused_mean(aev, shift, (rows, sizes, places, offsets))
         return SpeciesEnergies(species, energies) if shift is not None else self.energy_shifter((species, energies))
@@ -286,5 +291,4 @@ class ForceTrainableOptimizedTorchANI(TrainableOptimizedTorchANI):
     ONE call of ``nnpops_mlp_weight_grad_tangent``.  A force evaluation alone launches no weight gradient.  Take the gradient with
     ``loss.backward(inputs=parameters)`` or ``torch.autograd.grad(loss, parameters)``; refused with a message: the gradient of a force in
     the positions (``loss.backward()`` without ``inputs=``, Hessians), second derivatives in the parameters alone, third derivatives, a
-    forward pass between a forward pass and its derivatives, and a cell that requires a gradient.  Out of scope: scripting, periodic
-    batches."""
+    forward pass between a forward pass and its derivatives, and a cell that requires a gradient.  Out of scope: scripting."""

@@ -84,34 +84,59 @@ class TorchANISymmetryFunctions(torch.nn.Module):
         return self.holder.overflow_flag()
 
     @torch.jit.unused
-    def batch_holder(self, batch: int):
+    def batch_holder(self, batch: int, periodic: bool = False):
         """The holder that evaluates ``batch`` conformers of this module's molecule at once (molecule offsets 0, N, 2N, ...), made
-        on first use and kept: forward_batch and the batched step of :class:`OptimizedTorchANI` share it."""
-        holder = self._batch_holders.get(batch)
+        on first use and kept: forward_batch and the batched step of :class:`OptimizedTorchANI` share it.  ``periodic``: the holder
+        of ``batch`` periodic frames (cell [batch, 3, 3]) -- an entry of its own, since a holder's periodicity is frozen at its
+        first call."""
+        key = (batch, True) if periodic else batch
+        holder = self._batch_holders.get(key)
         if holder is None:
             holder = torch.classes.NNPOpsANISymmetryFunctions.Holder(*self._ctor, self._species * batch)
             holder.set_molecules([k * len(self._species) for k in range(batch + 1)])
-            self._batch_holders[batch] = holder
+            self._batch_holders[key] = holder
         return holder
 
     @torch.jit.unused
-    def check_batch_arguments(self, positions: Tensor) -> int:
-        """The argument error of forward_batch; -> the number of conformers."""
+    def check_batch_arguments(self, positions: Tensor, cell: Optional[Tensor] = None, pbc: Optional[Tensor] = None) -> int:
+        """The argument errors of forward_batch; -> the number of conformers.  A batch is non-periodic (no ``cell``, no ``pbc``) or
+        fully periodic with one box per frame: ``cell`` [batch, 3, 3] and ``pbc`` all True."""
         if positions.dim() != 3 or positions.shape[1] != len(self._species) or positions.shape[2] != 3:
             raise ValueError(f'"positions" has to have the shape [batch, {len(self._species)}, 3]')
-        return int(positions.shape[0])
+        batch = int(positions.shape[0])
+        if cell is None:
+            if pbc is not None:
+                raise ValueError('Batches of conformers are non-periodic: "cell" and "pbc" are not supported '
+                                 '(a periodic batch takes "cell" of the shape [batch, 3, 3] and "pbc" all True)')
+            return batch
+        if cell.dim() != 3:
+            raise ValueError('Batches of conformers are non-periodic: "cell" and "pbc" are not supported '
+                             '(a periodic batch takes "cell" of the shape [batch, 3, 3], one box per frame)')
+        if tuple(cell.shape) != (batch, 3, 3):
+            raise ValueError(f'"cell" has to have the shape [{batch}, 3, 3], one box per frame')
+        if pbc is None:
+            raise ValueError('"pbc" has to be defined')
+        if pbc.tolist() != [True, True, True]:
+            raise ValueError('Only fully periodic systems are supported, i.e. pbc = [True, True, True]')
+        return batch
 
     @torch.jit.unused
-    def forward_batch(self, species_positions: Tuple[Tensor, Tensor]) -> Tuple[Tensor, Tensor]:
+    def forward_batch(self, species_positions: Tuple[Tensor, Tensor], cell: Optional[Tensor] = None,
+                      pbc: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
         """Extension (the reference rejects batches, SymmetryFunctions.py:110): B conformers of THE molecule this module was
-        built for, non-periodic.  (species[B, N], positions[B, N, 3]) -> (species, aev[B, N, W]), differentiable w.r.t.
+        built for.  (species[B, N], positions[B, N, 3]) -> (species, aev[B, N, W]), differentiable w.r.t.
         positions.  All B x N atoms are evaluated by ONE batched holder (molecule offsets 0, N, 2N, ...; atoms of different
-        conformers never interact) in one launch sequence -- not B launches of a one-molecule holder."""
+        conformers never interact) in one launch sequence -- not B launches of a one-molecule holder.
+
+        ``cell`` [B, 3, 3] with ``pbc`` all True: B periodic frames, each in its own box (an NPT minibatch) -- frame b sees its atoms
+        through the minimum image of ``cell[b]``, every box at least two radial cutoffs wide, as for ``forward``.  Differentiable in
+        the cell as well (``cell.grad`` [B, 3, 3], shifts held fixed).  The neighbour search of a batch is the all-pairs scan inside
+        each frame: frames of tens to a few hundred atoms."""
         species, positions = species_positions
-        batch = self.check_batch_arguments(positions)
-        holder = self.batch_holder(batch)
+        batch = self.check_batch_arguments(positions, cell, pbc)
+        holder = self.batch_holder(batch, cell is not None)
         flat = positions.reshape(batch * len(self._species), 3)
-        features = torch.ops.NNPOpsANISymmetryFunctions.aev(holder, flat, None)
+        features = torch.ops.NNPOpsANISymmetryFunctions.aev(holder, flat, cell)
         return species, features.reshape(batch, len(self._species), -1)
 
     def check_arguments(self, species: Tensor, cell: Optional[Tensor], pbc: Optional[Tensor]) -> None:

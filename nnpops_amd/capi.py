@@ -247,6 +247,7 @@ class AniSymmetryFunctions:
         self.num_atoms, self.num_species = int(species.shape[0]), int(num_species)
         self.num_radial, self.num_angular = int(rf.shape[0]), int(af.shape[0])
         self.periodic = bool(periodic)
+        self.num_molecules = 0          # > 0: set_molecules is in force; a periodic evaluator then takes one box per molecule
         self.device = torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
         _check(self._lib.nnpops_ani_create(C.byref(self._h), self.num_atoms, self.num_species, radial_cutoff,
                                            angular_cutoff, int(self.periodic), species.ctypes.data_as(C.c_void_p),
@@ -262,19 +263,26 @@ class AniSymmetryFunctions:
             self._h = None
 
     def set_molecules(self, molecule_offsets):
-        """Treat the handle's atoms as a batch of independent non-periodic molecules:
-        atoms [offsets[m], offsets[m+1]) belong to molecule m (None restores one system)."""
+        """Treat the handle's atoms as a batch of independent molecules: atoms [offsets[m], offsets[m+1]) belong to molecule m
+        (None restores one system).  On a periodic evaluator every molecule is a frame in a box of its own: ``compute`` and
+        ``backprop_box`` then take ``box [M,3,3]`` (all-pairs search inside the frame: frames of tens to a few hundred atoms)."""
         if molecule_offsets is None:
             _check(self._lib.nnpops_ani_set_molecules(self._h, 0, None))
+            self.num_molecules = 0
             return
         off = np.ascontiguousarray(molecule_offsets, dtype=np.int32)
         _check(self._lib.nnpops_ani_set_molecules(self._h, int(off.shape[0]) - 1, off.ctypes.data_as(C.c_void_p)))
+        self.num_molecules = int(off.shape[0]) - 1
+
+    def _box_shape(self):
+        return (self.num_molecules, 3, 3) if self.num_molecules > 0 else (3, 3)
 
     def set_neighbor_algorithm(self, algorithm):
         _check(self._lib.nnpops_ani_set_neighbor_algorithm(self._h, int(algorithm)))
 
     def compute(self, positions, box=None, radial=None, angular=None, check=True):
-        """positions [N,3] (device fp32), box [3,3] or None -> (radial [N,S*nR], angular [N,NB*nA]).
+        """positions [N,3] (device fp32), box [3,3] ([M,3,3] when molecules are set on a periodic evaluator) or None
+        -> (radial [N,S*nR], angular [N,NB*nA]).
 
         ``check=True`` blocks once on the stream to see whether a neighbour row overflowed and, if
         so, repeats the computation with the grown buffers (the C ABI reports, never truncates)."""
@@ -282,7 +290,7 @@ class AniSymmetryFunctions:
         if self.periodic:
             if box is None:
                 raise ValueError("periodic evaluator needs box vectors")
-            _dev_f32(box, "box", (3, 3))
+            _dev_f32(box, "box", self._box_shape())
         if radial is None:
             radial = torch.empty((self.num_atoms, self.radial_width), dtype=torch.float32, device=positions.device)
         if angular is None:
@@ -312,19 +320,23 @@ class AniSymmetryFunctions:
         return position_grad
 
     def backprop_box(self, positions, box, radial_grad, angular_grad, position_grad=None, box_grad=None):
-        """``backprop`` plus the box-vector gradient (virial) of the same scalar -> (position_grad [N,3], box_grad [3,3]).
+        """``backprop`` plus the box-vector gradient (virial) of the same scalar -> (position_grad [N,3], box_grad [3,3]);
+        with molecules set on a periodic evaluator ``box`` and ``box_grad`` are [M,3,3], molecule m's entries summed over its own atoms.
 
         ``box_grad[k][c] = sum n_k (dL/dd)_c`` over every displacement ``d = x_j - x_i + n @ box`` the AEV used, the integer
         minimum-image shifts ``n`` held fixed; all nine entries.  ``positions`` and ``box`` must be the tensors of the preceding
         ``compute`` (the shifts are recovered from them).  Periodic evaluators only."""
         _dev_f32(positions, "positions", (self.num_atoms, 3))
-        _dev_f32(box, "box", (3, 3))
+        shape = self._box_shape() if self.periodic else (3, 3)
+        _dev_f32(box, "box", shape)
         _dev_f32(radial_grad, "radial_grad", (self.num_atoms, self.radial_width))
         _dev_f32(angular_grad, "angular_grad", (self.num_atoms, self.angular_width))
         if position_grad is None:
             position_grad = torch.empty((self.num_atoms, 3), dtype=torch.float32, device=radial_grad.device)
         if box_grad is None:
-            box_grad = torch.empty((3, 3), dtype=torch.float32, device=radial_grad.device)
+            box_grad = torch.empty(shape, dtype=torch.float32, device=radial_grad.device)
+        else:
+            _dev_f32(box_grad, "box_grad", shape)
         _check(self._lib.nnpops_ani_set_stream(self._h, _stream_ptr(radial_grad.device)))
         _check(self._lib.nnpops_ani_backprop_box_strided(self._h, _ptr(positions), _ptr(box), _ptr(radial_grad), 0, _ptr(angular_grad), 0,
                                                          _ptr(position_grad), _ptr(box_grad)))
@@ -365,7 +377,8 @@ class AniSymmetryFunctions:
         _check(self._lib.nnpops_ani_enable_timing(self._h, mask))
 
     def describe(self):
-        """-> {key: value} of nnpops_ani_describe: which kernels this handle runs (forward, backward, uniform, grid, literal, ...)."""
+        """-> {key: value} of nnpops_ani_describe: which kernels this handle runs (forward, backward, uniform, grid, literal, ...);
+        ``batch_boxes`` is there ('1') only while molecules are set on a periodic evaluator."""
         buf = C.create_string_buffer(512)
         _check(self._lib.nnpops_ani_describe(self._h, buf, 512))
         return dict(word.split("=", 1) for word in buf.value.decode().split())

@@ -35,6 +35,13 @@ struct nnpops_ani {
     // device state
     int32_t* d_species = nullptr;
     int2* d_segment = nullptr;      // [N] per-atom [lo, hi) of its molecule (batched handles only)
+    int* d_molecule = nullptr;      // [N] per-atom molecule index: which box of a periodic batch the builder wraps its displacements in
+    int* d_mol_offsets = nullptr;   // [num_molecules + 1] the offsets as given: the walk of the per-molecule box gradient (ani_box_grad.h)
+    int2* d_mol_blocks = nullptr;   // [num_mol_blocks] {molecule, k}: the workgroups of that pass, ani_box_molecule_blocks(atoms) per molecule
+    int* d_mol_first_block = nullptr;   // [num_molecules + 1] first workgroup of every molecule
+    double* d_mol_partials = nullptr;   // [num_mol_blocks][9] their partial sums
+    int num_mol_blocks = 0;
+    int num_molecules = 0;          // > 0: molecules are set; with hp.periodic the box arguments are [num_molecules][3][3]
     float4* d_nbr = nullptr;        // [N][cap] records {dx, dy, dz, (species<<24)|atom}, rows by POSITION of the radial backward's walk (slot in cell order / atom index)
     int* d_cnt_pos = nullptr;       // [N] na | nro << 16, by the same position
     float4* d_recA = nullptr;       // [N][cap_angular] sorted angular records {dx,dy,dz,r}
@@ -468,7 +475,8 @@ int fused_chunk(const nnpops_ani* h) {
 
 bool build_forward_fused(const nnpops_ani* h, const float* angular) {
     const bool want = h->fuse_forward < 0 ? h->hp.N <= kFuseAtoms : h->fuse_forward != 0;
-    return want && !h->generic && h->forward_kernel == 2 && h->fwd_waves_per_atom == 2 && h->nfrp == 8 && h->nfzp == 4 &&
+    // (a periodic batch takes the two launches: the fused kernel sits at its scalar-register limit and has no per-molecule box)
+    return want && !(h->hp.periodic && h->d_segment) && !h->generic && h->forward_kernel == 2 && h->fwd_waves_per_atom == 2 && h->nfrp == 8 && h->nfzp == 4 &&
            h->nstreams == 1 && h->fwd_identity && h->ld_angular % 4 == 0 && ((uintptr_t)angular & 15) == 0 &&
            build_forward_lds_bytes<8, 4>(h->cap, h->cap_angular, h->hp.S, h->hp.NB, fused_chunk(h)) <= 160 * 1024;
 }
@@ -765,7 +773,8 @@ int nnpops_ani_create(nnpops_ani_t* out, int num_atoms, int num_species, float r
 int nnpops_ani_destroy(nnpops_ani_t h) {
     if (!h) return NNPOPS_OK;
     DeviceGuard guard(h->device);
-    dev_free(h->d_params); dev_free(h->d_species); dev_free(h->d_segment);
+    dev_free(h->d_params); dev_free(h->d_species); dev_free(h->d_segment); dev_free(h->d_molecule); dev_free(h->d_mol_offsets);
+    dev_free(h->d_mol_blocks); dev_free(h->d_mol_first_block); dev_free(h->d_mol_partials);
     dev_free(h->d_nbr); dev_free(h->d_recA); dev_free(h->d_recB); dev_free(h->d_tri); dev_free(h->d_cnt_a); dev_free(h->d_cnt_ro); dev_free(h->d_cnt_pos); dev_free(h->d_status); dev_free(h->d_box_partials);
     dev_free(h->d_ids); dev_free(h->d_leg_force); dev_free(h->d_centre_force); dev_free(h->d_bucket_offsets);
     dev_free(h->d_work_order); dev_free(h->d_class_tile);
@@ -794,21 +803,48 @@ int nnpops_ani_set_molecules(nnpops_ani_t h, int num_molecules, const int32_t* m
     NNPOPS_REQUIRE(h != nullptr, "NULL handle");
     DeviceGuard guard(h->device);
     if (num_molecules <= 0 || molecule_offsets == nullptr) {     // back to one system
-        dev_free(h->d_segment);
+        dev_free(h->d_segment); dev_free(h->d_molecule); dev_free(h->d_mol_offsets);
+        dev_free(h->d_mol_blocks); dev_free(h->d_mol_first_block); dev_free(h->d_mol_partials);
+        h->num_molecules = h->num_mol_blocks = 0;
         h->computed = false;
         return NNPOPS_OK;
     }
-    NNPOPS_REQUIRE(!h->hp.periodic, "batched molecules are non-periodic systems");
     NNPOPS_REQUIRE(molecule_offsets[0] == 0 && molecule_offsets[num_molecules] == h->hp.N,
                    "molecule_offsets must start at 0 and end at num_atoms (%d)", h->hp.N);
+    for (int m = 0; m < num_molecules; m++)       // (before anything is written: every offset inside [0, N], every molecule non-empty)
+        NNPOPS_REQUIRE(molecule_offsets[m] >= 0 && molecule_offsets[m] < molecule_offsets[m + 1] && molecule_offsets[m + 1] <= h->hp.N,
+                       "molecule %d is empty or offsets are not increasing", m);
     std::vector<int2> seg(h->hp.N);
-    for (int m = 0; m < num_molecules; m++) {
-        NNPOPS_REQUIRE(molecule_offsets[m] < molecule_offsets[m + 1], "molecule %d is empty or offsets are not increasing", m);
-        for (int i = molecule_offsets[m]; i < molecule_offsets[m + 1]; i++) seg[i] = int2{molecule_offsets[m], molecule_offsets[m + 1]};
-    }
+    std::vector<int> mol(h->hp.N);
+    for (int m = 0; m < num_molecules; m++)
+        for (int i = molecule_offsets[m]; i < molecule_offsets[m + 1]; i++) { seg[i] = int2{molecule_offsets[m], molecule_offsets[m + 1]}; mol[i] = m; }
     int rc;
     if (!h->d_segment && (rc = dev_alloc(&h->d_segment, (size_t)h->hp.N))) return rc;
     NNPOPS_HIP_TRY(hipMemcpy(h->d_segment, seg.data(), sizeof(int2) * seg.size(), hipMemcpyHostToDevice));
+    if (h->hp.periodic) {                                          // a periodic batch: one box per molecule
+        if (!h->d_molecule && (rc = dev_alloc(&h->d_molecule, (size_t)h->hp.N))) return rc;
+        NNPOPS_HIP_TRY(hipMemcpy(h->d_molecule, mol.data(), sizeof(int) * mol.size(), hipMemcpyHostToDevice));
+        dev_free(h->d_mol_offsets);                                // (its length follows the molecule count)
+        if ((rc = dev_alloc(&h->d_mol_offsets, (size_t)num_molecules + 1))) return rc;
+        NNPOPS_HIP_TRY(hipMemcpy(h->d_mol_offsets, molecule_offsets, sizeof(int) * ((size_t)num_molecules + 1), hipMemcpyHostToDevice));
+        // the workgroups of the box-gradient pass and their partial sums: here, not at call time (backprop_box stays graph-capturable)
+        std::vector<int2> blocks;
+        std::vector<int> first(num_molecules + 1, 0);
+        for (int m = 0; m < num_molecules; m++) {
+            const int k_m = ani_box_molecule_blocks(molecule_offsets[m + 1] - molecule_offsets[m]);
+            for (int k = 0; k < k_m; k++) blocks.push_back(int2{m, k});
+            first[m + 1] = (int)blocks.size();
+        }
+        dev_free(h->d_mol_blocks); dev_free(h->d_mol_first_block); dev_free(h->d_mol_partials);
+        h->num_mol_blocks = 0;
+        if ((rc = dev_alloc(&h->d_mol_blocks, blocks.size()))) return rc;
+        if ((rc = dev_alloc(&h->d_mol_first_block, first.size()))) return rc;
+        if ((rc = dev_alloc(&h->d_mol_partials, 9 * blocks.size()))) return rc;
+        NNPOPS_HIP_TRY(hipMemcpy(h->d_mol_blocks, blocks.data(), sizeof(int2) * blocks.size(), hipMemcpyHostToDevice));
+        NNPOPS_HIP_TRY(hipMemcpy(h->d_mol_first_block, first.data(), sizeof(int) * first.size(), hipMemcpyHostToDevice));
+        h->num_mol_blocks = (int)blocks.size();
+    }
+    h->num_molecules = num_molecules;
     h->computed = false;
     return NNPOPS_OK;
 }
@@ -893,14 +929,18 @@ int nnpops_ani_compute_strided(nnpops_ani_t h, const float* positions, const flo
                                    h->cells.cell_start, h->cells.sorted_cell, h->cells.sorted_pos, h->d_nbr, h->cap, h->cap_angular, h->d_recA,
                                    h->d_recB, h->d_ids, h->d_tri, h->d_cnt_a, h->d_cnt_ro, h->d_cnt_pos, h->d_status, radial, h->ld_radial, lds_bw, h->cells.hist,
                                    sp.w0, sp.nw);
-        } else if (per)
+        } else if (per && h->d_segment)                        // a periodic batch: every atom against the box of its molecule
+            hipLaunchKernelGGL((ani_neighbors_allpairs<true, true>), sgrid, ablock, lds_b, sp.stream, h->d_params, positions, box,
+                               h->d_species, h->d_segment, h->d_nbr, h->cap, h->cap_angular, h->d_recA, h->d_recB, h->d_ids, h->d_tri,
+                               h->d_cnt_a, h->d_cnt_ro, h->d_cnt_pos, h->d_status, radial, h->ld_radial, lds_bw, sp.w0, sp.nw, h->d_molecule);
+        else if (per)
             hipLaunchKernelGGL(ani_neighbors_allpairs<true>, sgrid, ablock, lds_b, sp.stream, h->d_params, positions, box,
                                h->d_species, h->d_segment, h->d_nbr, h->cap, h->cap_angular, h->d_recA, h->d_recB, h->d_ids, h->d_tri,
-                               h->d_cnt_a, h->d_cnt_ro, h->d_cnt_pos, h->d_status, radial, h->ld_radial, lds_bw, sp.w0, sp.nw);
+                               h->d_cnt_a, h->d_cnt_ro, h->d_cnt_pos, h->d_status, radial, h->ld_radial, lds_bw, sp.w0, sp.nw, nullptr);
         else
             hipLaunchKernelGGL(ani_neighbors_allpairs<false>, sgrid, ablock, lds_b, sp.stream, h->d_params, positions, box,
                                h->d_species, h->d_segment, h->d_nbr, h->cap, h->cap_angular, h->d_recA, h->d_recB, h->d_ids, h->d_tri,
-                               h->d_cnt_a, h->d_cnt_ro, h->d_cnt_pos, h->d_status, radial, h->ld_radial, lds_bw, sp.w0, sp.nw);
+                               h->d_cnt_a, h->d_cnt_ro, h->d_cnt_pos, h->d_status, radial, h->ld_radial, lds_bw, sp.w0, sp.nw, nullptr);
         }
         NNPOPS_HIP_TRY(hipGetLastError());
         // (the radial AEV is written by the builder wave itself: radial_forward_from_lds)
@@ -1007,8 +1047,8 @@ int nnpops_ani_backprop_strided(nnpops_ani_t h, const float* radial_deriv, int r
 int nnpops_ani_backprop_box_strided(nnpops_ani_t h, const float* positions, const float* box, const float* radial_deriv, int radial_ld,
                                     const float* angular_deriv, int angular_ld, float* position_deriv, float* box_deriv) {
     NNPOPS_REQUIRE(h != nullptr, "NULL handle");
-    NNPOPS_REQUIRE(h->hp.periodic, "the box gradient needs a periodic handle (this one was created without box vectors)");
-    NNPOPS_REQUIRE(!h->d_segment, "the box gradient is not defined for a handle of batched molecules (nnpops_ani_set_molecules)");
+    NNPOPS_REQUIRE(h->hp.periodic, "the box gradient needs a periodic handle (this one was created without box vectors%s)",
+                   h->d_segment ? ": batched molecules of a non-periodic handle have no box" : "");
     NNPOPS_REQUIRE(positions && box && box_deriv, "NULL device pointer");
     int rc = nnpops_ani_backprop_strided(h, radial_deriv, radial_ld, angular_deriv, angular_ld, position_deriv);
     if (rc != NNPOPS_OK) return rc;
@@ -1016,6 +1056,15 @@ int nnpops_ani_backprop_box_strided(nnpops_ani_t h, const float* positions, cons
     // rows, the records and the leg forces, then the sum of its workgroups (ani_box_grad.h)
     DeviceGuard guard(h->device);
     if (!guard.ok) return fail(NNPOPS_ERR_HIP, "cannot select device %d", h->device);
+    if (h->d_segment) {                                        // a periodic batch: the workgroups of every molecule, then nine sums per molecule
+        hipLaunchKernelGGL(ani_box_partials_molecules, dim3(h->num_mol_blocks), dim3(kBoxThreads), 0, h->stream, h->d_params, positions, box,
+                           h->d_mol_offsets, h->d_mol_blocks, h->d_nbr, h->cap, h->cap_angular, h->d_cnt_pos, radial_deriv, h->ld_radial,
+                           h->d_recA, h->d_ids, h->d_leg_force, h->scatter_now ? 1 : 0, h->d_mol_partials);
+        hipLaunchKernelGGL(ani_box_finish_molecules, dim3(h->num_molecules), dim3(kBoxThreads), 0, h->stream, h->d_mol_first_block,
+                           (const double*)h->d_mol_partials, box_deriv);
+        NNPOPS_HIP_TRY(hipGetLastError());
+        return NNPOPS_OK;
+    }
     const int nblocks = ani_box_blocks(h->hp.N);
     hipLaunchKernelGGL(ani_box_partials, dim3(nblocks), dim3(kBoxThreads), 0, h->stream, h->d_params, positions, box, h->d_nbr, h->cap,
                        h->cap_angular, h->d_cnt_pos, radial_deriv, h->ld_radial, h->d_recA, h->d_ids, h->d_leg_force,
@@ -1307,7 +1356,7 @@ int nnpops_ani_describe(nnpops_ani_t h, char* text, int capacity) {
     const bool shape2x = h->nfrp == 8 && h->nfzp == 4;
     std::snprintf(text, (size_t)capacity,
                   "forward=%s backward=%d generic=%d uniform=%d grid=%d literal=%d dynamic_quads=%d fused_build=%d cap=%d cap_angular=%d "
-                  "chunk=%d classes=%d cells=%d scatter=%d row_major_walk=%d bwd_mode=%d radial_bwd=%s tile=%d compact=%d",
+                  "chunk=%d classes=%d cells=%d scatter=%d row_major_walk=%d bwd_mode=%d radial_bwd=%s tile=%d compact=%d%s",
                   h->forward_kernel == 2 ? "mfma" : h->forward_kernel == 1 ? "chunked" : "merge", h->backward_kernel, (int)h->generic,
                   (int)uni, (int)(uni && h->fwd_grid), (int)(uni && h->fwd_grid && shape2x && h->fwd_literal), (int)h->fwd_dynamic,
                   (int)(h->computed ? h->last_fused_build : (h->fuse_forward < 0 ? h->hp.N <= kFuseAtoms : h->fuse_forward != 0)), h->cap, h->cap_angular,
@@ -1316,7 +1365,9 @@ int nnpops_ani_describe(nnpops_ani_t h, char* text, int capacity) {
                   (int)h->bwd_classes.size(), (int)h->last_used_cells,
                   (int)h->scatter_now, h->hp.tri_row_major,       // (scatter: the last backprop() stored the leg forces in the receivers' rows)
                   // what the last backprop() launched: mode 0 = the round-1 angular backward (with its tile and layout), 1-4 = the pair kernels
-                  h->last_bwd_mode, h->last_radial_lanes < 0 ? "none" : h->last_radial_lanes ? "lanes" : "rows", h->last_tile, h->last_compact);
+                  h->last_bwd_mode, h->last_radial_lanes < 0 ? "none" : h->last_radial_lanes ? "lanes" : "rows", h->last_tile, h->last_compact,
+                  // (a periodic batch says so -- the builder wraps every molecule in a box of its own; other handles keep the words they had)
+                  h->hp.periodic && h->d_segment ? " batch_boxes=1" : "");
     return NNPOPS_OK;
 }
 

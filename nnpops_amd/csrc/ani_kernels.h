@@ -469,7 +469,10 @@ __device__ __forceinline__ void radial_forward_from_lds(const AniParams* __restr
 
 // All-pairs scan (the reference's O(N^2) search, one wave per atom; used for small systems and for
 // boxes too small for the cell stencil).  Row order = ascending atom id.
-template <bool PERIODIC>
+// BATCH_BOX (periodic batches, nnpops_ani_set_molecules on a periodic handle): `box` holds one [3][3] box per molecule and
+// `molecule[i]` names the one of atom i.  A wave owns one atom, so the index is wave-uniform -- readfirstlane says so to the
+// compiler, and the box stays nine scalar loads and one Box in scalar registers as in the single-box instantiations.
+template <bool PERIODIC, bool BATCH_BOX = false>
 __global__ __launch_bounds__(64 * kWavesPerGroup) void ani_neighbors_allpairs(const AniParams* __restrict__ P,
                                                              const float* __restrict__ pos,
                                                              const float* __restrict__ box,
@@ -480,7 +483,8 @@ __global__ __launch_bounds__(64 * kWavesPerGroup) void ani_neighbors_allpairs(co
                                                              float4* __restrict__ recB, int* __restrict__ ids,
                                                              int* __restrict__ tri,
                                                              int* __restrict__ cnt_a, int* __restrict__ cnt_ro, int* __restrict__ cnt_pos, int* __restrict__ status,
-                                                             float* __restrict__ radial, int ld_radial, int lds_per_wave, int w0, int nw) {
+                                                             float* __restrict__ radial, int ld_radial, int lds_per_wave, int w0, int nw,
+                                                             const int* __restrict__ molecule = nullptr) {   // per-atom molecule index (BATCH_BOX only)
     extern __shared__ __attribute__((aligned(16))) char lds_raw[];
     float4* stage = (float4*)(lds_raw + (size_t)wave_in_group() * lds_per_wave);
     float* rscratch = (float*)(stage + cap);
@@ -491,7 +495,10 @@ __global__ __launch_bounds__(64 * kWavesPerGroup) void ani_neighbors_allpairs(co
     const int N = P->N;
     const float rcr2 = P->rcr2, rca2 = P->rca2;
     Box b{};
-    if (PERIODIC) b = load_box(box);
+    if (PERIODIC) {
+        if (BATCH_BOX) b = load_box(box + 9 * (size_t)__builtin_amdgcn_readfirstlane(molecule[i]));
+        else b = load_box(box);
+    }
     const float xi = pos[3 * i], yi = pos[3 * i + 1], zi = pos[3 * i + 2];
     float4* row = nbr + (size_t)i * cap;                  // (rows and cnt_pos go by POSITION in the walk of the radial backward: here the atom index)
     // batched molecules: an atom only sees the atoms of its own molecule (independent systems in one handle)

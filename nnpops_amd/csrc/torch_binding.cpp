@@ -266,9 +266,10 @@ public:
     }
 
     // Additive (the reference has no batch dimension, SymmetryFunctions.py:110): the atoms of this Holder
-    // are `offsets.size() - 1` independent NON-PERIODIC molecules, molecule m = atoms [offsets[m], offsets[m+1]); atoms of
+    // are `offsets.size() - 1` independent molecules, molecule m = atoms [offsets[m], offsets[m+1]); atoms of
     // different molecules never see each other, forward/backward evaluate the whole batch in one launch sequence
-    // (nnpops_ani_set_molecules).  An empty list restores the single-system behaviour.
+    // (nnpops_ani_set_molecules).  A Holder first used with a cell evaluates a PERIODIC batch: the cell is then [molecules, 3, 3],
+    // a box for every molecule, and so is its gradient.  An empty list restores the single-system behaviour.
     void setMolecules(const std::vector<int64_t>& offsets) {
         if (!offsets.empty() && (offsets.front() != 0 || offsets.back() != (int64_t)atomSpecies.size()))
             throw std::runtime_error("molecule offsets have to start at 0 and end at the number of atoms");
@@ -296,9 +297,16 @@ public:
         if (cellOpt) {
             cell = *cellOpt;
             if (cell.scalar_type() != torch::kFloat32) throw std::runtime_error("The type of \"cell\" has to be float32");
+            if (!moleculeOffsets.empty()) {
+                // a periodic batch (setMolecules): one box per molecule, [molecules, 3, 3] (nnpops_ani_set_molecules on a periodic handle)
+                if (cell.dim() != 3 || cell.size(0) != moleculeCount() || cell.size(1) != 3 || cell.size(2) != 3)
+                    throw std::runtime_error("The shape of \"cell\" has to be [" + std::to_string(moleculeCount()) +
+                                             ", 3, 3]: this Holder evaluates a batch of molecules, one box for each");
+            } else {
             if (cell.dim() != 2) throw std::runtime_error("The shape of \"cell\" has to have 2 dimensions");
             if (cell.size(0) != 3) throw std::runtime_error("The size of the 1nd dimension of \"cell\" has to be 3");
             if (cell.size(1) != 3) throw std::runtime_error("The size of the 2nd dimension of \"cell\" has to be 3");
+            }
             if (cell.device() != positions.device()) throw std::runtime_error("\"cell\" has to be on the same device as \"positions\"");
             cell = cell.contiguous();
         }
@@ -417,7 +425,7 @@ public:
 
     // The two backward forms WITH the gradient of the box vectors (nnpops_ani_backprop_box_strided): `positions` and `cell` are the
     // tensors of the forward this backward belongs to -- the minimum-image shifts are recovered from them.  -> {none, dL/dpositions,
-    // dL/dcell [3, 3]}; the position gradient is the one backward() / backwardFused() return, bit for bit.
+    // dL/dcell [3, 3] -- [molecules, 3, 3] for a periodic batch}; the position gradient is the one backward() / backwardFused() return, bit for bit.
     tensor_list backwardFusedCell(const Tensor& aevGrad, const Tensor& positions, const Tensor& cell) {
         const Tensor g = aevGrad.contiguous();
         const int64_t wr = numSpecies * numRadial, w = g.size(1);
@@ -482,7 +490,7 @@ private:
         if (!impl) throw std::runtime_error("backward() called before forward()");
         const Tensor pos = positions.contiguous(), box = cell.contiguous();
         const auto opts = torch::TensorOptions().device(device).dtype(torch::kFloat32);
-        Tensor positionsGrad = torch::empty({(int64_t)atomSpecies.size(), 3}, opts), cellGrad = torch::empty({3, 3}, opts);
+        Tensor positionsGrad = torch::empty({(int64_t)atomSpecies.size(), 3}, opts), cellGrad = torch::empty(box.sizes(), opts);
         nnpops_ani_set_stream(impl, current_stream(device));
         if (nnpops_ani_backprop_box_strided(impl, pos.data_ptr<float>(), box.data_ptr<float>(), radialGrad, ldRadial, angularGrad, ldAngular,
                                             positionsGrad.data_ptr<float>(), cellGrad.data_ptr<float>()) != NNPOPS_OK)
@@ -733,7 +741,7 @@ std::pair<Tensor, Tensor> energy_step(const HolderPtr& holder, const Tensor& fra
                                       const c10::optional<Tensor>& x_blocks, const c10::optional<Tensor>& dead_blocks, bool need_gradient,
                                       float gradient_sign, int64_t act_scale_log2, Tensor* kept_cell = nullptr,
                                       const BatchTables* batch = nullptr) {
-    // (kept_cell != NULL, with need_gradient: the AEV backward also runs its box-gradient pass and dE/dcell * gradient_sign [3, 3] is kept there)
+    // (kept_cell != NULL, with need_gradient: the AEV backward also runs its box-gradient pass and dE/dcell * gradient_sign [3, 3] -- of a periodic batch [B, 3, 3] -- is kept there)
     TORCH_CHECK(batch != nullptr || frame.dim() == 2 || (frame.dim() == 3 && frame.size(0) == 1),
                 "energy(): positions must be [atoms, 3] or [1, atoms, 3]");
     const Tensor positions = batch ? frame.reshape({-1, 3}) : frame.dim() == 3 ? frame[0] : frame;
@@ -879,11 +887,18 @@ std::tuple<Tensor, Tensor> energy_forces(const c10::optional<HolderPtr>& holder,
 // positions [B, N, 3] -> energies [B]: one AEV launch sequence and one launch of the networks over all B * N atoms, one mean per
 // molecule (nnpops_mlp_energy_mean_segments), dE_b/dpositions of every molecule kept from the forward [B * N, 3]; the backward scales
 // each molecule's rows by its own upstream gradient (nnpops_scale_by_segment) and hands them back as [B, N, 3].
+// A PERIODIC batch -- B frames, each in a box of its own -- passes cell [B, 3, 3] (the holder then was first used with such a cell:
+// Holder::forwardImpl).  When the cell requires a gradient the step keeps dE_b/dcell_b [B, 3, 3] next to the position gradient, and
+// the backward scales frame b's nine entries by frame b's upstream gradient: the same nnpops_scale_by_segment over the [3 B, 3] view
+// with offsets 0, 3, 6, ...  A 2-D cell is what a single frame takes and stays refused.
 // ---------------------------------------------------------------------------------------------
 BatchTables batch_tables(const HolderPtr& holder, const Tensor& positions, const c10::optional<Tensor>& cell, const Tensor& rows,
                          const Tensor& molecule_offsets, const Tensor& row_positions) {
-    TORCH_CHECK(!cell.has_value(), "energy_batch(): batches of molecules are non-periodic: a cell is not supported");
+    TORCH_CHECK(!cell.has_value() || cell->dim() == 3, "energy_batch(): batches of molecules are non-periodic: a cell is not supported "
+                "(a periodic batch takes one box per molecule, cell [molecules, 3, 3])");
     TORCH_CHECK(positions.dim() == 3 && positions.size(2) == 3 && positions.size(0) >= 1, "energy_batch(): positions must be [molecules, atoms, 3]");
+    TORCH_CHECK(!cell.has_value() || (cell->size(0) == positions.size(0) && cell->size(1) == 3 && cell->size(2) == 3),
+                "energy_batch(): the cell of a periodic batch must be [", positions.size(0), ", 3, 3], one box per molecule");
     require_device_tensor(positions, "positions");
     const int64_t B = positions.size(0), atoms = B * positions.size(1);
     TORCH_CHECK(holder->moleculeCount() > 0, "energy_batch(): the holder has no molecule offsets (Holder.set_molecules): it evaluates one molecule");
@@ -901,16 +916,21 @@ BatchTables batch_tables(const HolderPtr& holder, const Tensor& positions, const
 
 class EnergyBatchFunction : public torch::autograd::Function<EnergyBatchFunction> {
 public:
-    static Tensor forward(AutogradContext* ctx, const HolderPtr& holder, const Tensor& positions, const Tensor& rows, std::vector<int64_t> kind_atoms,
-                          std::vector<int64_t> widths, int64_t members, const Tensor& planes, const Tensor& floats, const c10::optional<Tensor>& shift,
-                          const c10::optional<Tensor>& x_blocks, const c10::optional<Tensor>& dead_blocks, const Tensor& molecule_offsets,
-                          const Tensor& row_positions, bool need_gradient, int64_t act_scale_log2) {
-        const BatchTables batch = batch_tables(holder, positions, c10::nullopt, rows, molecule_offsets, row_positions);
-        Tensor energy, kept;
-        std::tie(energy, kept) = energy_step(holder, positions, c10::nullopt, rows, kind_atoms, widths, members, planes, floats, shift, x_blocks,
-                                             dead_blocks, need_gradient, 1.0f, act_scale_log2, nullptr, &batch);
+    static Tensor forward(AutogradContext* ctx, const HolderPtr& holder, const Tensor& positions, const c10::optional<Tensor>& cell, const Tensor& rows,
+                          std::vector<int64_t> kind_atoms, std::vector<int64_t> widths, int64_t members, const Tensor& planes, const Tensor& floats,
+                          const c10::optional<Tensor>& shift, const c10::optional<Tensor>& x_blocks, const c10::optional<Tensor>& dead_blocks,
+                          const Tensor& molecule_offsets, const Tensor& row_positions, bool need_gradient, int64_t act_scale_log2, bool need_cell) {
+        const BatchTables batch = batch_tables(holder, positions, cell, rows, molecule_offsets, row_positions);
+        Tensor energy, kept, kept_cell;
+        std::tie(energy, kept) = energy_step(holder, positions, cell, rows, kind_atoms, widths, members, planes, floats, shift, x_blocks,
+                                             dead_blocks, need_gradient, 1.0f, act_scale_log2, need_cell ? &kept_cell : nullptr, &batch);
         if (need_gradient) {
-            ctx->save_for_backward({kept, molecule_offsets});
+            if (need_cell) {      // dE_b/dcell_b [B, 3, 3] next to the position gradient, and the offsets 0, 3, 6, ... of its [3 B, 3] view
+                const Tensor cell_offsets = torch::arange(0, 3 * batch.molecules + 1, 3, molecule_offsets.options());
+                ctx->save_for_backward({kept, molecule_offsets, kept_cell, cell_offsets});
+            } else {
+                ctx->save_for_backward({kept, molecule_offsets});
+            }
             ctx->saved_data["shape"] = positions.sizes().vec();
         }
         return energy;
@@ -932,8 +952,15 @@ public:
                                     g.data_ptr(), g.scalar_type() == torch::kFloat64 ? 1 : 0, out.data_ptr<float>()) != NNPOPS_OK)
             raise_last("NNPOpsANISymmetryFunctions::energy_batch (backward)");
         out = out.view(ctx->saved_data["shape"].toIntVector());
-        return {Tensor(), out, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(),
-                Tensor()};
+        Tensor cell_out;
+        if (saved.size() > 2) {                                              // frame b's nine entries by frame b's upstream gradient
+            cell_out = torch::empty_like(saved[2]);
+            if (nnpops_scale_by_segment(current_stream(kept.device()), saved[2].data_ptr<float>(), (int)(3 * g.numel()), saved[3].data_ptr<int32_t>(),
+                                        (int)g.numel(), g.data_ptr(), g.scalar_type() == torch::kFloat64 ? 1 : 0, cell_out.data_ptr<float>()) != NNPOPS_OK)
+                raise_last("NNPOpsANISymmetryFunctions::energy_batch (backward)");
+        }
+        return {Tensor(), out, cell_out, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(),
+                Tensor(), Tensor(), Tensor()};
     }
 };
 
@@ -941,10 +968,10 @@ Tensor energy_batch(const c10::optional<HolderPtr>& holder, const Tensor& positi
                     std::vector<int64_t> kind_atoms, std::vector<int64_t> widths, int64_t members, const Tensor& planes, const Tensor& floats,
                     const Tensor& molecule_offsets, const Tensor& row_positions, const c10::optional<Tensor>& shift,
                     const c10::optional<Tensor>& x_blocks, const c10::optional<Tensor>& dead_blocks, int64_t act_scale_log2) {
-    TORCH_CHECK(!cell.has_value(), "energy_batch(): batches of molecules are non-periodic: a cell is not supported");
-    const bool need = torch::GradMode::is_enabled() && positions.requires_grad();
-    return EnergyBatchFunction::apply(*holder, positions, rows, kind_atoms, widths, members, planes, floats, shift, x_blocks, dead_blocks,
-                                      molecule_offsets, row_positions, need, act_scale_log2);
+    const bool need_cell = torch::GradMode::is_enabled() && cell.has_value() && cell->requires_grad();
+    const bool need = (torch::GradMode::is_enabled() && positions.requires_grad()) || need_cell;
+    return EnergyBatchFunction::apply(*holder, positions, cell, rows, kind_atoms, widths, members, planes, floats, shift, x_blocks, dead_blocks,
+                                      molecule_offsets, row_positions, need, act_scale_log2, need_cell);
 }
 
 // energies [B] AND forces [B, N, 3] of the batch from one call, outside autograd (cf. energy_forces)
@@ -956,7 +983,7 @@ std::tuple<Tensor, Tensor> energy_forces_batch(const c10::optional<HolderPtr>& h
     torch::NoGradGuard no_grad;
     const BatchTables batch = batch_tables(*holder, positions, cell, rows, molecule_offsets, row_positions);
     Tensor energy, forces;
-    std::tie(energy, forces) = energy_step(*holder, positions.detach(), c10::nullopt, rows, kind_atoms, widths, members, planes, floats, shift, x_blocks,
+    std::tie(energy, forces) = energy_step(*holder, positions.detach(), cell, rows, kind_atoms, widths, members, planes, floats, shift, x_blocks,
                                            dead_blocks, true, -1.0f, act_scale_log2, nullptr, &batch);
     return std::make_tuple(energy, forces.view(positions.sizes()));
 }
