@@ -185,6 +185,11 @@ int nnpops_ani_check_end(nnpops_ani_t h);
 /* Neighbour search used by compute(): 0 = automatic, 1 = all-pairs scan (the reference's
  * algorithm, O(N^2)), 2 = cell list (O(N); periodic boxes must be at least 3 cells wide per axis). */
 int nnpops_ani_set_neighbor_algorithm(nnpops_ani_t h, int algorithm);
+/* Which launches build the cell grid of a periodic system of up to 20 000 atoms: 1 (default; $NNPOPS_ANI_GRID_OWNED=0 at
+ * create: 0) one launch in which every block orders the cells it owns, 0 the two launches bin_atoms + order_binned.  Results
+ * are bit-identical; a handle may change from call to call (tests, A/B measurements).  describe() of a handle whose search
+ * goes through the cell grid: grid_build=owned|binned (scan: the five-launch build of non-periodic and larger systems). */
+int nnpops_ani_set_grid_build(nnpops_ani_t h, int one_launch);
 
 /* Batched evaluation of independent molecules (or periodic frames) in one handle (the reference has no batch
  * dimension: src/pytorch/SymmetryFunctions.py:110; this is the additive API SURVEY.md s8f ranks second).

@@ -42,6 +42,7 @@ SIGNATURES = {
     "nnpops_ani_check_begin": (C.c_int, [C.c_void_p]),
     "nnpops_ani_check_end": (C.c_int, [C.c_void_p]),
     "nnpops_ani_set_neighbor_algorithm": (C.c_int, [C.c_void_p, C.c_int]),
+    "nnpops_ani_set_grid_build": (C.c_int, [C.c_void_p, C.c_int]),
     "nnpops_ani_set_molecules": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "nnpops_ani_enable_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "nnpops_ani_set_timing_stride": (C.c_int, [C.c_void_p, C.c_int]),
@@ -279,6 +280,11 @@ class AniSymmetryFunctions:
 
     def set_neighbor_algorithm(self, algorithm):
         _check(self._lib.nnpops_ani_set_neighbor_algorithm(self._h, int(algorithm)))
+
+    def set_grid_build(self, one_launch):
+        """True: the one-launch build of the periodic cell grid (where the system is small enough for it), False: the two-launch
+        build; describe()["grid_build"] says which the handle runs.  Bit-identical results (tests, A/B)."""
+        _check(self._lib.nnpops_ani_set_grid_build(self._h, int(bool(one_launch))))
 
     def compute(self, positions, box=None, radial=None, angular=None, check=True):
         """positions [N,3] (device fp32), box [3,3] ([M,3,3] when molecules are set on a periodic evaluator) or None

@@ -105,6 +105,7 @@ struct nnpops_ani {
     bool check_pending = false;
     CellList cells;                 // cell grid (celllist_host.h); cells.fine: half-cutoff cells where they fit ($NNPOPS_ANI_FINE_GRID=0)
     bool cells_disabled = false;    // set when a box turned out too small for the 27-cell stencil
+    int last_grid_build = -1;       // what the last compute() built the grid with: 0 five launches, 1 bin_atoms + order_binned, 2 bin_atoms_owned (-1: no grid)
     int cap = 0;                    // row capacity (angular + radial-only neighbours)
     bool cap_fitted = false;        // the first clean check() shrinks `cap` to the system
     int cap_angular = 0;            // LDS capacity of the angular kernels
@@ -670,6 +671,10 @@ int nnpops_ani_create(nnpops_ani_t* out, int num_atoms, int num_species, float r
         if (const char* e = std::getenv("NNPOPS_ANI_SCATTER")) h->scatter_mode = std::atoi(e) != 0 ? 1 : 0;
         h->cells.fine = 1;
         if (const char* e = std::getenv("NNPOPS_ANI_FINE_GRID")) h->cells.fine = std::atoi(e) != 0;
+        // the one-launch grid build (celllist.h: bin_atoms_owned) for periodic systems of up to kOwnedAtoms atoms; 0: always the two-launch build (A/B, tests)
+        h->cells.owned = 1;
+        if (const char* e = std::getenv("NNPOPS_ANI_GRID_OWNED")) h->cells.owned = std::atoi(e) != 0;
+        if (const char* e = std::getenv("NNPOPS_ANI_GRID_BLOCKS")) h->cells.owned_launch = std::max(kOwnedMinBlocks, std::min(256, std::atoi(e)));
         if (const char* e = std::getenv("NNPOPS_ANI_FWD_ROWLDS")) h->fwd_row_via_lds = std::atoi(e) != 0;
         if (const char* e = std::getenv("NNPOPS_ANI_FWD_OCC")) h->fwd_occ = std::atoi(e);
         {   // Does the per-atom quad table pay?  With one quad set per species pair the step loop of phase 2 runs max_b n_b / K times,
@@ -856,6 +861,16 @@ int nnpops_ani_set_neighbor_algorithm(nnpops_ani_t h, int algorithm) {
     return NNPOPS_OK;
 }
 
+int nnpops_ani_set_grid_build(nnpops_ani_t h, int one_launch) {
+    NNPOPS_REQUIRE(h != nullptr, "NULL handle");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(NNPOPS_ERR_HIP, "cannot select device %d", h->device);
+    h->cells.owned = one_launch != 0;
+    // (the one-launch build never clears the overflow word of the grid: start it from a clean one)
+    if (h->cells.owned) NNPOPS_HIP_TRY(hipMemsetAsync(&h->cells.grid->bin_overflow, 0, sizeof(int), h->stream));
+    return NNPOPS_OK;
+}
+
 int nnpops_ani_compute(nnpops_ani_t h, const float* positions, const float* box, float* radial, float* angular) {
     return nnpops_ani_compute_strided(h, positions, box, radial, 0, angular, 0);
 }
@@ -892,6 +907,7 @@ int nnpops_ani_compute_strided(nnpops_ani_t h, const float* positions, const flo
     h->last_used_cells = use_cells;
     if (use_cells) {
         KernelTimer timer(h, NNPOPS_ANI_K_CELL_GRID);
+        h->last_grid_build = cell_build_is_owned(N, per, h->cells) ? 2 : cell_build_is_binned(N, per, h->cells) ? 1 : 0;
         launch_cell_build(h->stream, N, positions, box, per, h->hp.rcr, h->d_species, h->cells);
     }
     // The per-atom kernels, span by span: every span's chain (neighbour build -> angular forward) runs on its own stream.
@@ -1274,6 +1290,12 @@ int nnpops_ani_check(nnpops_ani_t h, int* max_radial_neighbors, int* max_angular
         }
         return NNPOPS_OK;
     }
+    if ((st[kStatOverflow] & kGridBinOverflow) && h->last_grid_build == 2) {      // the cells of one block of the one-launch build hold more atoms than its list
+        h->cells.owned = 0;                         // (for good: a frame this crowded is not what that build is for, and larger bins do not help it)
+        h->computed = false;
+        return fail(NNPOPS_ERR_CAPACITY, "a cell range of the one-launch grid build holds more than %d atoms: switched to the two-launch build, "
+                                         "call compute() again", kOwnedCap);
+    }
     if (st[kStatOverflow] & kGridBinOverflow) {     // a cell holds more atoms than a bin of the two-kernel grid build: grow the bins
         int old_bin;
         int rc = h->cells.grow_bins(&old_bin);
@@ -1354,9 +1376,10 @@ int nnpops_ani_describe(nnpops_ani_t h, char* text, int capacity) {
     NNPOPS_REQUIRE(h != nullptr && text != nullptr && capacity > 0, "NULL argument");
     const bool uni = h->fwd_uniform && h->hp.nFR == h->nfrp && h->hp.nFZ == h->nfzp;
     const bool shape2x = h->nfrp == 8 && h->nfzp == 4;
+    const bool grid_next = !h->d_segment && (h->algorithm == 2 || (h->algorithm == 0 && h->hp.N >= h->cell_atoms && !h->cells_disabled));
     std::snprintf(text, (size_t)capacity,
                   "forward=%s backward=%d generic=%d uniform=%d grid=%d literal=%d dynamic_quads=%d fused_build=%d cap=%d cap_angular=%d "
-                  "chunk=%d classes=%d cells=%d scatter=%d row_major_walk=%d bwd_mode=%d radial_bwd=%s tile=%d compact=%d%s",
+                  "chunk=%d classes=%d cells=%d scatter=%d row_major_walk=%d bwd_mode=%d radial_bwd=%s tile=%d compact=%d%s%s%s",
                   h->forward_kernel == 2 ? "mfma" : h->forward_kernel == 1 ? "chunked" : "merge", h->backward_kernel, (int)h->generic,
                   (int)uni, (int)(uni && h->fwd_grid), (int)(uni && h->fwd_grid && shape2x && h->fwd_literal), (int)h->fwd_dynamic,
                   (int)(h->computed ? h->last_fused_build : (h->fuse_forward < 0 ? h->hp.N <= kFuseAtoms : h->fuse_forward != 0)), h->cap, h->cap_angular,
@@ -1366,6 +1389,11 @@ int nnpops_ani_describe(nnpops_ani_t h, char* text, int capacity) {
                   (int)h->scatter_now, h->hp.tri_row_major,       // (scatter: the last backprop() stored the leg forces in the receivers' rows)
                   // what the last backprop() launched: mode 0 = the round-1 angular backward (with its tile and layout), 1-4 = the pair kernels
                   h->last_bwd_mode, h->last_radial_lanes < 0 ? "none" : h->last_radial_lanes ? "lanes" : "rows", h->last_tile, h->last_compact,
+                  // (a handle whose neighbour search goes through the cell grid says which launches build it -- what it is set to, for the
+                  //  size it has: owned = bin_atoms_owned, binned = bin_atoms + order_binned, scan = the five launches; other handles keep
+                  //  the words they had)
+                  grid_next ? " grid_build=" : "",
+                  !grid_next ? "" : !h->hp.periodic || !h->cells.hist ? "scan" : cell_build_is_owned(h->hp.N, true, h->cells) ? "owned" : "binned",
                   // (a periodic batch says so -- the builder wraps every molecule in a box of its own; other handles keep the words they had)
                   h->hp.periodic && h->d_segment ? " batch_boxes=1" : "");
     return NNPOPS_OK;

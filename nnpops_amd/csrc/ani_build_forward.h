@@ -74,7 +74,7 @@ __global__ __launch_bounds__(128, OCC) void ani_build_forward(const AniParams* _
     Box b{};
     if (in.periodic) b = load_box(in.box);
     CellGrid g{};
-    if (in.use_cells) g = *in.grid;
+    if (in.use_cells) g = load_built_grid(in.grid);
 
     {   // one atom per workgroup (no grid-stride loop: every kernel argument would stay live across the iterations)
         const int w = blockIdx.x;

@@ -559,7 +559,7 @@ __global__ __launch_bounds__(64 * kWavesPerGroup) void ani_neighbors_cells(const
     const int slot_id = slot0 + wave_global_id();          // position in cell order; this launch covers [slot0, slot0 + nslots)
     clear_cell_histogram(cell_hist);
     if (wave_global_id() >= nslots) return;
-    const CellGrid g = *grid;
+    const CellGrid g = load_built_grid(grid);
     if (!g.ok) {                                           // box too small for the stencil: tell the host
         if (lane == 0) {
             if (slot_id == 0) atomicOr(&status[kStatOverflow], refused_grid_bits(g));

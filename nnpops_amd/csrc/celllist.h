@@ -10,6 +10,7 @@
 //   order_cells     1 thread/atom   rank inside the segment by atom id (deterministic order), emit
 //                                   cell-ordered float4 {x, y, z, id}
 //   bin_atoms + order_binned   the same in two launches for stateful periodic callers (see below)
+//   bin_atoms_owned            the same in one launch, every block ordering the cells it owns (periodic ANI handles of up to kOwnedAtoms atoms)
 // Consumers walk the 3x3x3 block of cells around an atom.  The stencil only prunes candidates: the
 // displacement of every candidate is still computed with the reference's minimum-image rule
 // (device_common.h: min_image), so results are identical to the all-pairs scan.  The stencil is
@@ -29,7 +30,8 @@ struct CellGrid {
     int periodic;
     int m;                  // stencil half-width in cells: cells are at least cutoff / m wide (1, or 2 for the fine grid)
     int ok;                 // 0: the stencil would be invalid for this box (too few cells), or a bin overflowed
-    int bin_overflow;       // 1: ok was cleared because a cell holds more atoms than the bins of the two-kernel build
+    int bin_overflow;       // 1: ok was cleared because a cell holds more atoms than the bins of the two-kernel build; set WITHOUT
+                            //    ok = 0 by the one-launch build whose list overflowed (bin_atoms_owned; read with load_built_grid)
     // lattice coordinates: sz = (z-oz)*izz; sy = ((y-oy) - sz*cy)*iyy; sx = ((x-ox) - sy*bx - sz*cx)*ixx
     float ox, oy, oz;
     float ixx, iyy, izz;
@@ -410,6 +412,226 @@ static __global__ __launch_bounds__(T) void order_binned(int N, const float* __r
     order_block<T>(N, grid, pos, tag, hist, bins, bin_cap, atom_cell, cell_start, sorted_atom, sorted_pos, sorted_cell, s_start, wave_tot);
 }
 
+// ---------------------------------------------------------------------------------------------
+// One-launch build, partitioned by OUTPUT: block b owns the contiguous cells [b * per, (b + 1) * per) and emits exactly
+// their slice of the sorted arrays.  What it needs for that -- how many atoms lie in the cells in front of its range, and
+// which atoms lie inside it -- it takes from one pass of its own over all N positions (every load independent, the
+// positions L2-resident after the first block has touched them): no block waits for another, so there is no histogram in
+// global memory, no global atomic, no bins and no second launch.
+//   pass A   all atoms, blockDim apart: first only the slab (cell_slab); a slab below the range bumps a per-thread counter,
+//            a slab of the range lists {x, y, z, id} in LDS.  Then the listed atoms, dense: the cell by cell_of (the same
+//            arithmetic as bin_one_atom, bit for bit); a cell below the range bumps the counter, a cell inside it puts the
+//            entry on the block's list and takes an arrival number in its cell (LDS atomics)
+//   offsets  block sum of the counters; exclusive scan over the block's own <= kOwnedMaxPer cells
+//   pass B   the list: ids regrouped by cell through the arrival numbers, rank = ids of the cell below mine (the
+//            deterministic order order_binned produces), slot = before + start + rank
+// The pass over all atoms is the price: it grows with N in every block, so the build is for small grids
+// (launch_cell_build: kOwnedAtoms).  A range that holds more than kOwnedCap atoms (or whose slabs hold more than kOwnedMaybe)
+// sets grid->bin_overflow; the owner then
+// goes back to the two-launch build (growing the bins would not help here).  Block 0 stores every word of the grid BUT
+// bin_overflow, which only an overflowing block writes (one value, any number of writers): two blocks never store
+// different values to one word, so no order between them is needed.  The flag stays set until a build that writes the
+// whole grid (bin_atoms, grid_setup) runs; consumers of an owned build read the grid with load_built_grid().
+// ---------------------------------------------------------------------------------------------
+constexpr int kOwnedThreads = 1024;
+constexpr int kOwnedMinBlocks = 32, kOwnedMaxBlocks = 128;
+constexpr int kOwnedMaxPer = kBinnedCells / kOwnedMinBlocks;      // cells of one block, at most
+constexpr int kOwnedCap = 2 * kOwnedThreads;                      // atoms of one block's cells, at most (two entries per thread in pass B)
+constexpr int kOwnedMaybe = 2304;                                 // atoms in the slabs of one block's cells, at most ({x, y, z, id} in LDS: 36 KiB of the 64)
+constexpr int kOwnedUnroll = 10;                                  // positions a thread requests per round trip (10 240 atoms: one trip)
+// Largest system that takes the one-launch build when its owner opts in (CellBuffers::owned).  Measured on MI355X
+// (docs/LAB_NOTEBOOK_cell_owned.md): the largest size of the table there at which the build is still ahead of bin_atoms + order_binned.
+constexpr int kOwnedAtoms = 20000;
+
+// blocks of the one-launch build: from N alone (the host does not know the cell count)
+static inline int owned_blocks(int N) {
+    const int b = (N + 127) / 128;
+    return b < kOwnedMinBlocks ? kOwnedMinBlocks : b > kOwnedMaxBlocks ? kOwnedMaxBlocks : b;
+}
+
+// The grid as a consumer must see it: refused when an owned build overflowed (bin_overflow without ok = 0, see above).
+__device__ __forceinline__ CellGrid load_built_grid(const CellGrid* __restrict__ grid) {
+    CellGrid g = *grid;
+    if (g.bin_overflow) g.ok = 0;
+    return g;
+}
+
+// The slab of an atom: cz of cell_of, by the same operations on the same numbers (cell_of's sz takes nothing from x and y).
+__device__ __forceinline__ int cell_slab(const CellGrid& g, float z) {
+    float sz = (z - g.oz) * g.izz;
+    if (g.periodic) sz -= floorf(sz);
+    return min(max((int)(sz * g.nz), 0), g.nz - 1);
+}
+
+struct PackedPos { float x, y, z; };      // (12 bytes, 4-byte aligned: one three-dword load)
+
+static __global__ __launch_bounds__(kOwnedThreads) void bin_atoms_owned(int N, const float* __restrict__ pos,
+                                                                         const int* __restrict__ tag,
+                                                                         const float* __restrict__ box, float cutoff, int max_cells,
+                                                                         CellGrid* __restrict__ grid, int* __restrict__ atom_cell,
+                                                                         int* __restrict__ cell_start, int* __restrict__ sorted_atom,
+                                                                         float4* __restrict__ sorted_pos, int* __restrict__ sorted_cell,
+                                                                         int fine) {
+    constexpr int T = kOwnedThreads, U = kOwnedUnroll, WAVES = T / 64;
+    __shared__ CellGrid g;
+    __shared__ float4 s_maybe[kOwnedMaybe];        // the atoms in the slabs of the range, in arrival order: {x, y, z, id}
+    __shared__ int s_own[kOwnedCap];               // owned atoms in arrival order: their entry of s_maybe
+    __shared__ int s_key[kOwnedCap];               //   (cell - c0) << 16 | arrival number inside the cell
+    __shared__ int s_bucket[kOwnedCap];            // owned ids, grouped by cell
+    __shared__ int s_cnt[kOwnedMaxPer];            // atoms per owned cell
+    __shared__ int s_start[kOwnedMaxPer];          // first entry of the cell, relative to the block's first slot
+    __shared__ int s_n, s_nm, s_zlo, s_zhi;
+    __shared__ int wave_tot[WAVES], wave_before[WAVES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const PackedPos* __restrict__ p3 = reinterpret_cast<const PackedPos*>(pos);
+    // (the first positions are requested BEFORE the grid is decided, as in bin_atoms)
+    PackedPos p[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) p[u] = p3[min(tid + u * T, N - 1)];
+    if (tid < kOwnedMaxPer) s_cnt[tid] = 0;
+    if (tid == 0) {
+        s_n = 0;
+        s_nm = 0;
+        g = decide_grid(1, box, nullptr, nullptr, cutoff, min(max_cells, kBinnedCells), fine);
+        if (blockIdx.x == 0) {                                 // every word but bin_overflow
+            grid->nx = g.nx; grid->ny = g.ny; grid->nz = g.nz; grid->ncells = g.ncells;
+            grid->periodic = g.periodic; grid->m = g.m; grid->ok = g.ok;
+            grid->ox = g.ox; grid->oy = g.oy; grid->oz = g.oz;
+            grid->ixx = g.ixx; grid->iyy = g.iyy; grid->izz = g.izz;
+            grid->bx = g.bx; grid->cx = g.cx; grid->cy = g.cy;
+        }
+        // the slabs (layers of nx * ny cells) the range touches: cells of slab z are [z * nxy, (z + 1) * nxy)
+        const int nxy = g.nx * g.ny, per0 = (g.ncells + (int)gridDim.x - 1) / (int)gridDim.x;
+        const int lo = min((int)blockIdx.x * per0, g.ncells), hi = min(lo + per0, g.ncells);
+        s_zlo = lo / nxy;
+        s_zhi = (max(hi, 1) - 1) / nxy;
+    }
+    __syncthreads();
+    if (!g.ok) return;
+    const int ncells = g.ncells;
+    const int per = (ncells + (int)gridDim.x - 1) / (int)gridDim.x;        // <= kOwnedMaxPer: ncells <= kBinnedCells, gridDim >= kOwnedMinBlocks
+    const int c0 = min((int)blockIdx.x * per, ncells), c1 = min(c0 + per, ncells);
+    if (c0 >= c1) return;                                      // more blocks than cells: nothing to emit (block 0 always owns cell 0)
+    const int zlo = s_zlo, zhi = s_zhi;
+
+    // pass A, first half: every atom, its slab only.  A slab below the range counts as "before", one above it is none of
+    // this block's business, and an atom in a slab of the range goes into s_maybe: seven instructions for most atoms
+    // instead of the thirty of cell_of, and the atoms that need those come out dense (one in ten lanes would otherwise
+    // drag its whole wave through them).
+    int before = 0;
+    for (int base = tid;;) {
+        unsigned mask = 0;
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const int z = (base + u * T < N) ? cell_slab(g, p[u].z) : g.nz;
+            before += z < zlo ? 1 : 0;
+            mask |= (z >= zlo && z <= zhi) ? 1u << u : 0u;
+        }
+        {   // one LDS atomic per wave and round (a thousand threads adding to one word serialise)
+            const int cnt = __popc(mask), incl = wave_prefix_sum(cnt);
+            int room = 0;
+            if (lane == 63 && incl > 0) room = atomicAdd(&s_nm, incl);
+            int at = __builtin_amdgcn_readlane(room, 63) + incl - cnt;
+#pragma unroll
+            for (int u = 0; u < U; u++)
+                if (mask >> u & 1) {
+                    if (at < kOwnedMaybe) s_maybe[at] = make_float4(p[u].x, p[u].y, p[u].z, __int_as_float(base + u * T));
+                    at++;
+                }
+        }
+        base += U * T;
+        if (base - tid >= N) break;                            // (the same for the whole block: the wave operations above need every lane)
+#pragma unroll
+        for (int u = 0; u < U; u++) p[u] = p3[min(base + u * T, N - 1)];
+    }
+    __syncthreads();
+    const int nm = s_nm;
+    if (nm > kOwnedMaybe) {                                    // the slabs of the range hold more atoms than the list: a very flat or very crowded box
+        if (tid == 0) grid->bin_overflow = 1;
+        return;
+    }
+    // pass A, second half: the listed atoms, dense: the cell by cell_of (the same arithmetic as bin_one_atom, bit for bit),
+    // owned atoms into the block's list
+    {
+        constexpr int R = (kOwnedMaybe + T - 1) / T;
+#pragma unroll
+        for (int r = 0; r < R; r++)
+            if (tid + r * T < nm) {
+                const float4 m = s_maybe[tid + r * T];
+                int cx, cy, cz;
+                cell_of(g, m.x, m.y, m.z, cx, cy, cz);
+                const int c = (cz * g.ny + cy) * g.nx + cx;
+                before += c < c0 ? 1 : 0;
+                if (c >= c0 && c < c1) {
+                    const int k = atomicAdd(&s_cnt[c - c0], 1);
+                    const int e = atomicAdd(&s_n, 1);
+                    if (e < kOwnedCap) {
+                        s_own[e] = tid + r * T;
+                        s_key[e] = ((c - c0) << 16) | k;            // (k < kOwnedCap < 65 536 wherever the entry is used)
+                    }
+                }
+            }
+    }
+    {
+        const int incl = wave_prefix_sum(before);
+        if (lane == 63) wave_before[wave] = incl;
+    }
+    __syncthreads();
+    const int n = s_n;
+    if (n > kOwnedCap) {                                       // a very crowded range: this build cannot order it
+        if (tid == 0) grid->bin_overflow = 1;
+        return;
+    }
+    // pass B: my (at most two) entries, and the one load that hangs on them (it is back when the offsets are done)
+    float mx[2], my[2], mz[2];
+    int id[2], key[2], tg[2];
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        const int e = min(tid + q * T, max(n - 1, 0));
+        const float4 m = s_maybe[n > 0 ? s_own[e] : 0];
+        mx[q] = m.x; my[q] = m.y; mz[q] = m.z;
+        id[q] = __float_as_int(m.w);
+        key[q] = s_key[e];
+        tg[q] = (tag && tid + q * T < n) ? tag[id[q]] : 0;
+    }
+    // offsets: atoms in front of the range, and the exclusive scan of the range's own cells
+    int count = 0, incl = 0;
+    if (tid < kOwnedMaxPer) {                                  // (whole waves: kOwnedMaxPer is a multiple of 64)
+        count = s_cnt[tid];
+        incl = wave_prefix_sum(count);
+        if (lane == 63) wave_tot[wave] = incl;
+    }
+    int first = 0;                                             // atoms in the cells below c0: the block's first slot
+#pragma unroll
+    for (int w = 0; w < WAVES; w++) first += wave_before[w];
+    __syncthreads();
+    if (tid < kOwnedMaxPer) {
+        int start = incl - count;
+        for (int w = 0; w < wave; w++) start += wave_tot[w];
+        s_start[tid] = start;
+        if (c0 + tid < c1) cell_start[c0 + tid] = first + start;
+    }
+    if (tid == 0 && c1 == ncells && c0 < c1) cell_start[ncells] = N;          // (the block that owns the last cell)
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 2; q++)
+        if (tid + q * T < n) s_bucket[s_start[key[q] >> 16] + (key[q] & 0xffff)] = id[q];
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        if (tid + q * T >= n) continue;
+        const int lc = key[q] >> 16, i = id[q];
+        const int lo = s_start[lc], cnt = s_cnt[lc];
+        int rank = 0;                                          // deterministic order inside the cell
+        for (int a = 0; a < cnt; a++) rank += s_bucket[lo + a] < i ? 1 : 0;
+        const int slot = first + lo + rank;
+        sorted_atom[slot] = i;
+        if (sorted_cell) sorted_cell[slot] = c0 + lc;
+        sorted_pos[slot] = make_float4(mx[q], my[q], mz[q], __int_as_float(i | (tg[q] << kTagShift)));      // (as order_block packs it)
+        atom_cell[i] = c0 + lc;
+    }
+}
+
 // The same stencil as ONE flat candidate index space: lane r < 18 looks up range r, a wave scan gives
 // the offsets, and candidate k of the atom is sorted slot k + off[range of k].  A consumer then runs
 // ceil(candidates / 64) full iterations with independent loads instead of one (mostly half-empty,
@@ -656,12 +878,15 @@ struct CellBuffers {
     int fine = 0;                          // 1: prefer half-cutoff cells (decide_grid); only for consumers that read CellGrid::m
     int* sorted_cell = nullptr;            // [N] optional: cell of the atom in every sorted slot
     int* tile_total = nullptr;             // [CellList::tile_total_len] optional: lets grids of more than 8192 cells scan in parallel
+    int owned = 0;                         // 1: periodic systems of up to kOwnedAtoms atoms take the one-launch build (bin_atoms_owned); only for
+                                           //    consumers that read the grid with load_built_grid() and go back to owned = 0 on kGridBinOverflow
+    int owned_launch = 0;                  // > 0: that many blocks instead of owned_blocks(N) (measurements; at least kOwnedMinBlocks)
 };
 
 // What the read_grid entry points of the consumers report (include/nnpops_hip.h): a host copy of the grid, as eight ints.
 static inline void grid_words(const CellGrid& g, int32_t* out) {
     out[0] = g.nx; out[1] = g.ny; out[2] = g.nz; out[3] = g.ncells;
-    out[4] = g.m; out[5] = g.ok; out[6] = g.bin_overflow; out[7] = g.periodic;
+    out[4] = g.m; out[5] = g.bin_overflow ? 0 : g.ok; out[6] = g.bin_overflow; out[7] = g.periodic;      // (ok: as load_built_grid)
 }
 
 static inline bool cell_build_is_binned(int N, bool periodic, const CellBuffers& b) {
@@ -670,9 +895,20 @@ static inline bool cell_build_is_binned(int N, bool periodic, const CellBuffers&
     return periodic && b.hist != nullptr && b.bins != nullptr;
 }
 
+// (the histogram and the bins stay as the consumer left them, cleared: a handle may change between this build and the two-launch
+//  one from call to call)
+static inline bool cell_build_is_owned(int N, bool periodic, const CellBuffers& b) {
+    return b.owned != 0 && N <= kOwnedAtoms && cell_build_is_binned(N, periodic, b);
+}
+
 static inline void launch_cell_build(hipStream_t stream, int N, const float* pos, const float* box, bool periodic, float cutoff,
                                      const int* tag, const CellBuffers& b) {
     const int tb = 256, nb = (N + tb - 1) / tb;
+    if (cell_build_is_owned(N, periodic, b)) {
+        hipLaunchKernelGGL(bin_atoms_owned, dim3(b.owned_launch > 0 ? b.owned_launch : owned_blocks(N)), dim3(kOwnedThreads), 0, stream, N, pos, tag, box,
+                           cutoff, b.max_cells, b.grid, b.atom_cell, b.cell_start, b.sorted_atom, b.sorted_pos, b.sorted_cell, b.fine);
+        return;
+    }
     if (cell_build_is_binned(N, periodic, b)) {
         hipLaunchKernelGGL(bin_atoms, dim3(nb), dim3(kBinnedThreads), 0, stream, N, pos, box, cutoff, b.max_cells, b.grid, b.hist, b.bins,
                            b.bin_cap, b.atom_cell, b.fine);

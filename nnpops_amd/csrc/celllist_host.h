@@ -52,6 +52,7 @@ struct CellList : CellBuffers {
         const bool binned = periodic && N <= kBinnedAtoms;
         int rc = each_array((size_t)N, binned, tiled_scan, [](auto*& p, size_t len) { return dev_alloc(&p, len); });
         if (rc != NNPOPS_OK) return rc;
+        if (hipMemset(grid, 0, sizeof(CellGrid)) != hipSuccess) return fail(NNPOPS_ERR_HIP, "memset failed");      // (bin_overflow: the one-launch build never clears it)
         if (binned && hipMemset(hist, 0, sizeof(int) * kHistWords) != hipSuccess) return fail(NNPOPS_ERR_HIP, "memset failed");
         return NNPOPS_OK;
     }
