@@ -78,7 +78,7 @@ struct nnpops_ani {
     bool scatter_now = false;       // ... decided by backprop() for the call in progress
     bool last_fused_build = false;  // the last compute() ran the one-launch build + forward (what describe() reports)
     // what the last backprop() launched (host-side records for describe(); -1: no backprop() yet / that kernel did not run)
-    int last_bwd_mode = -1;         // 0: the round-1 ani_angular_backward, 1-4: the pair kernels (with classes: the top class's mode)
+    int last_bwd_mode = -1;         // 0: the round-1 ani_angular_backward, 1-4: the pair kernels (with classes: the mode of the first class that has atoms)
     int last_radial_lanes = -1;     // 1: a lane per neighbour (ani_radial_bwd.h), 0: the round-1 ani_radial_backward (rows)
     int last_tile = -1;             // pair-matrix tile and compact_bwd flag the round-1 angular backward was launched with
     int last_compact = -1;
@@ -361,7 +361,7 @@ int launch_angular(nnpops_ani* h, bool forward, const float* grad_or_null, float
         //  with two waves everywhere; the 153-triple atoms of a liquid stay with one wave, 15.8 against 25 us)
         if (mode == 1 && !h->backward_forced && (cl.two_waves || h->scatter_now || ang_bwd_pair_lds_bytes<NFRP, NFZP>(tile, h->hp.NB, false) > 16 * 1024)) mode = 3;
         if (!vec_ok && (mode == 1 || mode == 3)) mode++;
-        if (c == 0) h->last_bwd_mode = mode;                   // (describe(): the whole launch, or the top class)
+        if (h->last_bwd_mode < 0) h->last_bwd_mode = mode;     // (describe(): the whole launch, or the first class that has atoms -- the top one may be empty)
         const bool glds = mode == 2 || mode == 4;
         const size_t lb = (ang_bwd_pair_lds_bytes<NFRP, NFZP>(tile, h->hp.NB, glds) + 15) & ~(size_t)15;
         void (*k)(const AniParams*, const AngularConsts, int, int, int, const float4*, const float4*, const int*, const int*, const int*, const float*, int,
