@@ -19,6 +19,16 @@ ARCH = "gfx950"
 # translation units of the C-ABI library (the torch binding is built separately, see torch_binding.py)
 UNITS = ["capi_common.hip", "ani.hip", "cfconv.hip", "neighbor_pairs.hip", "pairs_index.hip", "pairs_second_order.hip", "batched_nn.hip", "mlp_fused.hip", "pme.hip", "pme_recip.hip", "pme_second_order.hip"]
 
+# Flags of single units, part of the recipe.  ani.hip: the first 14 words of every kernel's argument block are in scalar registers when
+# a wave starts, so the per-atom kernels (which put what their first requests need in those words) begin without a round trip for
+# their arguments; on a machine that does not preload, the prologue the compiler adds loads the same registers.
+UNIT_FLAGS = {"ani.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=14"]}
+
+
+def _flags_stamp(src, flags):
+    """What is recorded next to an object: the development flags and the unit's own."""
+    return " ".join(list(flags) + UNIT_FLAGS.get(os.path.basename(src), []))
+
 
 def _sources():
     return [os.path.join(CSRC, u) for u in UNITS if os.path.exists(os.path.join(CSRC, u))]
@@ -52,10 +62,10 @@ def built_hash():
 def _stale():
     if not os.path.exists(LIB) or built_hash() != source_hash():
         return True
-    flags = " ".join(os.environ.get("NNPOPS_HIPCC_FLAGS", "").split())
+    flags = os.environ.get("NNPOPS_HIPCC_FLAGS", "").split()
     for src in _sources():                                    # (a development build with other flags is not the product binary)
         stamp = os.path.join(CSRC, "_obj", os.path.basename(src) + ".o.flags")
-        if not os.path.exists(stamp) or open(stamp).read() != flags:
+        if not os.path.exists(stamp) or open(stamp).read() != _flags_stamp(src, flags):
             return True
     t = os.path.getmtime(LIB)
     deps = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hip")) + \
@@ -91,12 +101,12 @@ def build(force=False, verbose=False):
         # An object is reused when it is newer than its source and every header that source includes AND was compiled with the
         # same flags (recorded next to it).  capi_common.hip carries the source hash of the whole library: always recompiled.
         stamp = obj + ".flags"
-        fresh = (not force and os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read() == " ".join(flags)
+        fresh = (not force and os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read() == _flags_stamp(src, flags)
                  and os.path.basename(src) != "capi_common.hip"
                  and all(os.path.getmtime(d) < os.path.getmtime(obj) for d in _deps(src)))
         if fresh:
             continue
-        cmd = [hipcc, *flags, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", f'-DNNPOPS_SOURCE_HASH="{source_hash()}"', "-c", src, "-o", obj]
+        cmd = [hipcc, *flags, *UNIT_FLAGS.get(os.path.basename(src), []), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", f'-DNNPOPS_SOURCE_HASH="{source_hash()}"', "-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd))
         procs.append((src, stamp, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
@@ -104,7 +114,7 @@ def build(force=False, verbose=False):
         out, _ = p.communicate()
         if p.returncode != 0:
             raise RuntimeError(f"hipcc failed on {src}:\n{out.decode()}")
-        open(stamp, "w").write(" ".join(flags))
+        open(stamp, "w").write(_flags_stamp(src, flags))
     cmd = [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB] + objs
     if verbose:
         print(" ".join(cmd))

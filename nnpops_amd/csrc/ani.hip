@@ -318,8 +318,8 @@ int launch_angular(nnpops_ani* h, bool forward, const float* grad_or_null, float
                     k = dyn ? ani_angular_forward_mfma<TA, 8, 4, 2, 7, 2, true> : ani_angular_forward_mfma<TA, 8, 4, 2, 7, 2>;
             }
             if (lw > 64 * 1024) NNPOPS_HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lw));
-            hipLaunchKernelGGL(k, dim3(groups), dim3(128), (size_t)lw, sp.stream, h->d_params, h->cap, h->cap_angular, CH, h->d_recA,
-                               h->d_recB, h->d_tri, h->d_cnt_a, h->d_cnt_ro, out, h->ld_angular, vec_ok, lw, sp.ang_order, sp.w0, sp.nw);
+            hipLaunchKernelGGL(k, dim3(groups), dim3(128), (size_t)lw, sp.stream, sp.ang_order, sp.w0, sp.nw, 2, groups, h->d_params, h->cap,
+                               h->cap_angular, CH, h->d_recA, h->d_recB, h->d_tri, h->d_cnt_a, h->d_cnt_ro, out, h->ld_angular, vec_ok, lw);
         } else {
             const int wpg2 = waves_per_group(lw);
             const size_t lg = (size_t)lw * wpg2;
@@ -327,8 +327,8 @@ int launch_angular(nnpops_ani* h, bool forward, const float* grad_or_null, float
             if (h->fwd_atoms_per_group > 1) groups = div_up(groups, h->fwd_atoms_per_group);
             auto k = ani_angular_forward_mfma<TA, NFRP, NFZP, 1, 5>;
             if (lg > 64 * 1024) NNPOPS_HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lg));
-            hipLaunchKernelGGL(k, dim3(groups), dim3(64 * wpg2), lg, sp.stream, h->d_params, h->cap, h->cap_angular, CH, h->d_recA,
-                               h->d_recB, h->d_tri, h->d_cnt_a, h->d_cnt_ro, out, h->ld_angular, vec_ok, lw, sp.ang_order, sp.w0, sp.nw);
+            hipLaunchKernelGGL(k, dim3(groups), dim3(64 * wpg2), lg, sp.stream, sp.ang_order, sp.w0, sp.nw, wpg2, groups, h->d_params, h->cap,
+                               h->cap_angular, CH, h->d_recA, h->d_recB, h->d_tri, h->d_cnt_a, h->d_cnt_ro, out, h->ld_angular, vec_ok, lw);
         }
     } else if (forward) {
         auto k = h->chunked_forward ? ani_angular_forward_chunked<TA, NFRP, NFZP> : ani_angular_forward<TA, NFRP, NFZP>;
@@ -364,8 +364,8 @@ int launch_angular(nnpops_ani* h, bool forward, const float* grad_or_null, float
         if (h->last_bwd_mode < 0) h->last_bwd_mode = mode;     // (describe(): the whole launch, or the first class that has atoms -- the top one may be empty)
         const bool glds = mode == 2 || mode == 4;
         const size_t lb = (ang_bwd_pair_lds_bytes<NFRP, NFZP>(tile, h->hp.NB, glds) + 15) & ~(size_t)15;
-        void (*k)(const AniParams*, const AngularConsts, int, int, int, const float4*, const float4*, const int*, const int*, const int*, const float*, int,
-                  float4*, float4*, const int*, float4*, int, int, int, const int*, int, int, int) =
+        void (*k)(const int*, int, int, int, int, const AniParams*, const AngularConsts, int, int, int, const float4*, const float4*, const int*, const int*,
+                  const int*, const float*, int, float4*, float4*, const int*, float4*, int, int, int, int) =
             mode == 1 ? (h->occ6 ? ani_angular_backward_pair<TA, NFRP, NFZP, 6, 1, false>
                          : (h->fwd_uniform && h->hp.nFR == NFRP && h->hp.nFZ == NFZP) ? ani_angular_backward_pair<TA, NFRP, NFZP, 5, 1, false, false, 1>
                                                                                        : ani_angular_backward_pair<TA, NFRP, NFZP, 5, 1, false>)
@@ -405,10 +405,9 @@ int launch_angular(nnpops_ani* h, bool forward, const float* grad_or_null, float
         //  it returns at once unless a class launch left an atom out: ani_angular_bwd.h)
         const int class_mode = !by_class ? 0 : c < nclasses ? 1 : 2;
         const int groups = class_mode == 2 ? std::min(div_up(cnw, apg), 256) : div_up(cnw, apg);
-        hipLaunchKernelGGL(k, dim3(groups), dim3(threads), lb * apg, sp.stream, h->d_params, h->ac, h->cap, h->cap_angular, tile, h->d_recA, h->d_recB, h->d_tri,
-                           h->d_cnt_a, h->d_cnt_ro, grad_or_null, h->ld_angular, h->d_leg_force, h->d_centre_force, h->d_ids,
-                           scat ? h->d_leg_force : nullptr, vec_ok, h->hp.NB, (int)lb,
-                           sp.ang_order, cw0, cnw, h->backprop_stamp);
+        hipLaunchKernelGGL(k, dim3(groups), dim3(threads), lb * apg, sp.stream, sp.ang_order, cw0, cnw, apg, groups, h->d_params, h->ac, h->cap,
+                           h->cap_angular, tile, h->d_recA, h->d_recB, h->d_tri, h->d_cnt_a, h->d_cnt_ro, grad_or_null, h->ld_angular, h->d_leg_force,
+                           h->d_centre_force, h->d_ids, scat ? h->d_leg_force : nullptr, vec_ok, h->hp.NB, (int)lb, h->backprop_stamp);
         }
     } else {
         auto k = ani_angular_backward<TA, NFRP, NFZP>;
@@ -455,8 +454,9 @@ int launch_generic(nnpops_ani* h, bool forward, const float* g, float* out, cons
         auto k = ani_angular_backward_pair<TA, 4, 4, 4, 1, false, true>;
         h->last_bwd_mode = 1;                                  // (the pair kernel, one wave per atom, gradients through the L1)
         if (lb > 64 * 1024) NNPOPS_HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
-        hipLaunchKernelGGL(k, dim3(N), dim3(64), lb, sp.stream, h->d_params, h->ac, h->cap, h->cap_angular, h->cap_angular, h->d_recA, h->d_recB, h->d_tri,
-                           h->d_cnt_a, h->d_cnt_ro, g, h->ld_angular, h->d_leg_force, h->d_centre_force, h->d_ids, nullptr, 0, h->hp.NB, (int)lb, nullptr, 0, N, 0);
+        hipLaunchKernelGGL(k, dim3(N), dim3(64), lb, sp.stream, nullptr, 0, N, 1, N, h->d_params, h->ac, h->cap, h->cap_angular, h->cap_angular, h->d_recA,
+                           h->d_recB, h->d_tri, h->d_cnt_a, h->d_cnt_ro, g, h->ld_angular, h->d_leg_force, h->d_centre_force, h->d_ids, nullptr, 0, h->hp.NB,
+                           (int)lb, 0);
     }
     NNPOPS_HIP_TRY(hipGetLastError());
     return NNPOPS_OK;
@@ -910,6 +910,9 @@ int nnpops_ani_compute_strided(nnpops_ani_t h, const float* positions, const flo
         h->last_grid_build = cell_build_is_owned(N, per, h->cells) ? 2 : cell_build_is_binned(N, per, h->cells) ? 1 : 0;
         launch_cell_build(h->stream, N, positions, box, per, h->hp.rcr, h->d_species, h->cells);
     }
+    // Only the two-launch build writes the histogram, so only the consumer of such a build clears it (celllist.h: clear_cell_histogram):
+    // it is zero between evaluations whichever builds alternate on this handle, eager or replayed from a graph.
+    int* const hist_to_clear = use_cells && h->last_grid_build == 1 ? h->cells.hist : nullptr;
     // The per-atom kernels, span by span: every span's chain (neighbour build -> angular forward) runs on its own stream.
     h->can_split = !h->generic && h->forward_kernel == 2 && h->backward_kernel >= 1 &&
                    pair_backward_fits(h);
@@ -924,7 +927,7 @@ int nnpops_ani_compute_strided(nnpops_ani_t h, const float* positions, const flo
         if (h->last_fused_build) {                             // one launch: build + radial + angular forward (timed as the build)
             KernelTimer timer(h, NNPOPS_ANI_K_NEIGHBORS, sp.stream);
             KernelTimer merged_timer(h, NNPOPS_ANI_K_NEIGHBORS, sp.stream, /*merged=*/true);      // (merge mode brackets the same launch: ADVICE r04)
-            const BuildInputs in{box, h->cells.grid, h->cells.cell_start, h->cells.sorted_cell, h->cells.sorted_pos, h->cells.hist, positions, h->d_species,
+            const BuildInputs in{box, h->cells.grid, h->cells.cell_start, h->cells.sorted_cell, h->cells.sorted_pos, hist_to_clear, positions, h->d_species,
                                  h->d_segment, use_cells ? 1 : 0, per ? 1 : 0};
             const BuildOutputs out{h->d_nbr, h->d_recA, h->d_recB, h->d_ids, h->d_tri, h->d_cnt_a, h->d_cnt_ro, h->d_cnt_pos, h->d_status, radial, h->ld_radial};
             rc = h->hp.torchani ? launch_build_forward<true>(h, in, out, angular, sp) : launch_build_forward<false>(h, in, out, angular, sp);
@@ -936,27 +939,27 @@ int nnpops_ani_compute_strided(nnpops_ani_t h, const float* positions, const flo
         KernelTimer timer(h, NNPOPS_ANI_K_NEIGHBORS, sp.stream);
         if (use_cells) {
             if (per)
-                hipLaunchKernelGGL(ani_neighbors_cells<true>, sgrid, ablock, lds_b, sp.stream, h->d_params, box, h->cells.grid,
-                                   h->cells.cell_start, h->cells.sorted_cell, h->cells.sorted_pos, h->d_nbr, h->cap, h->cap_angular, h->d_recA,
-                                   h->d_recB, h->d_ids, h->d_tri, h->d_cnt_a, h->d_cnt_ro, h->d_cnt_pos, h->d_status, radial, h->ld_radial, lds_bw, h->cells.hist,
-                                   sp.w0, sp.nw);
+                hipLaunchKernelGGL(ani_neighbors_cells<true>, sgrid, ablock, lds_b, sp.stream, hist_to_clear, h->cells.grid, h->cells.sorted_pos,
+                                   h->cells.sorted_cell, sp.w0, sp.nw, wpg_b, lds_bw, h->d_params, box, h->cells.cell_start, h->d_nbr, h->cap,
+                                   h->cap_angular, h->d_recA, h->d_recB, h->d_ids, h->d_tri, h->d_cnt_a, h->d_cnt_ro, h->d_cnt_pos, h->d_status, radial,
+                                   h->ld_radial);
             else
-                hipLaunchKernelGGL(ani_neighbors_cells<false>, sgrid, ablock, lds_b, sp.stream, h->d_params, box, h->cells.grid,
-                                   h->cells.cell_start, h->cells.sorted_cell, h->cells.sorted_pos, h->d_nbr, h->cap, h->cap_angular, h->d_recA,
-                                   h->d_recB, h->d_ids, h->d_tri, h->d_cnt_a, h->d_cnt_ro, h->d_cnt_pos, h->d_status, radial, h->ld_radial, lds_bw, h->cells.hist,
-                                   sp.w0, sp.nw);
+                hipLaunchKernelGGL(ani_neighbors_cells<false>, sgrid, ablock, lds_b, sp.stream, hist_to_clear, h->cells.grid, h->cells.sorted_pos,
+                                   h->cells.sorted_cell, sp.w0, sp.nw, wpg_b, lds_bw, h->d_params, box, h->cells.cell_start, h->d_nbr, h->cap,
+                                   h->cap_angular, h->d_recA, h->d_recB, h->d_ids, h->d_tri, h->d_cnt_a, h->d_cnt_ro, h->d_cnt_pos, h->d_status, radial,
+                                   h->ld_radial);
         } else if (per && h->d_segment)                        // a periodic batch: every atom against the box of its molecule
             hipLaunchKernelGGL((ani_neighbors_allpairs<true, true>), sgrid, ablock, lds_b, sp.stream, h->d_params, positions, box,
                                h->d_species, h->d_segment, h->d_nbr, h->cap, h->cap_angular, h->d_recA, h->d_recB, h->d_ids, h->d_tri,
-                               h->d_cnt_a, h->d_cnt_ro, h->d_cnt_pos, h->d_status, radial, h->ld_radial, lds_bw, sp.w0, sp.nw, h->d_molecule);
+                               h->d_cnt_a, h->d_cnt_ro, h->d_cnt_pos, h->d_status, radial, h->ld_radial, lds_bw, sp.w0, sp.nw, wpg_b, h->d_molecule);
         else if (per)
             hipLaunchKernelGGL(ani_neighbors_allpairs<true>, sgrid, ablock, lds_b, sp.stream, h->d_params, positions, box,
                                h->d_species, h->d_segment, h->d_nbr, h->cap, h->cap_angular, h->d_recA, h->d_recB, h->d_ids, h->d_tri,
-                               h->d_cnt_a, h->d_cnt_ro, h->d_cnt_pos, h->d_status, radial, h->ld_radial, lds_bw, sp.w0, sp.nw, nullptr);
+                               h->d_cnt_a, h->d_cnt_ro, h->d_cnt_pos, h->d_status, radial, h->ld_radial, lds_bw, sp.w0, sp.nw, wpg_b, nullptr);
         else
             hipLaunchKernelGGL(ani_neighbors_allpairs<false>, sgrid, ablock, lds_b, sp.stream, h->d_params, positions, box,
                                h->d_species, h->d_segment, h->d_nbr, h->cap, h->cap_angular, h->d_recA, h->d_recB, h->d_ids, h->d_tri,
-                               h->d_cnt_a, h->d_cnt_ro, h->d_cnt_pos, h->d_status, radial, h->ld_radial, lds_bw, sp.w0, sp.nw, nullptr);
+                               h->d_cnt_a, h->d_cnt_ro, h->d_cnt_pos, h->d_status, radial, h->ld_radial, lds_bw, sp.w0, sp.nw, wpg_b, nullptr);
         }
         NNPOPS_HIP_TRY(hipGetLastError());
         // (the radial AEV is written by the builder wave itself: radial_forward_from_lds)
@@ -1046,9 +1049,10 @@ int nnpops_ani_backprop_strided(nnpops_ani_t h, const float* radial_deriv, int r
                 case 7: k = wide ? ani_radial_backward_lanes<7, 64> : ani_radial_backward_lanes<7, 32>; break;
                 default: k = wide ? ani_radial_backward_lanes<8, 64> : ani_radial_backward_lanes<8, 32>; break;
             }
-            hipLaunchKernelGGL(k, dim3(div_up(sp.nw, wpg)), dim3(64 * wpg), (size_t)lw * wpg, sp.stream, h->d_params, h->d_species, h->d_nbr,
-                               h->cap, h->d_cnt_pos, radial_deriv, h->ld_radial, h->d_ids, h->d_leg_force, h->d_centre_force,
-                               sp.order, position_deriv, lw, sp.w0, sp.nw);
+            // (the kernel derives this launch shape from nw: kWavesPerGroup waves per workgroup, one wave per position)
+            hipLaunchKernelGGL(k, dim3(div_up(sp.nw, wpg)), dim3(64 * wpg), (size_t)lw * wpg, sp.stream, h->d_nbr, h->d_cnt_pos, sp.order, radial_deriv,
+                               sp.w0, sp.nw, h->cap, h->ld_radial, h->hp.N, h->hp.S, h->d_params, h->d_species, h->d_ids, h->d_leg_force,
+                               h->d_centre_force, position_deriv, lw);
         } else
         hipLaunchKernelGGL(ani_radial_backward, dim3(div_up(sp.nw, wpg_r)), ablock, lds_r, sp.stream, h->d_params, h->d_species, h->d_nbr, h->cap,
                            h->cap_angular, h->d_cnt_pos, radial_deriv, h->ld_radial, h->d_ids, h->d_leg_force, h->d_centre_force,

@@ -124,12 +124,16 @@ __host__ __device__ inline size_t ang_bwd_pair_lds_bytes(int capA, int NB, bool 
 // kernel a third of its speed (18-22 spilled scalar registers: 32.6 -> 44 us on a 7 600-atom block of conformers).
 template <bool TORCHANI, int NFRP, int NFZP, int OCC, int WPA, bool GLDS, bool GENERIC = false, int UNI = 0, int CLASSES = 0, bool SCAT = false>
 __global__ __launch_bounds__(WPA == 2 ? 128 : 64 * kWavesPerGroup, OCC) void ani_angular_backward_pair(
+    const int* __restrict__ order, int w0, int nw,     // positions [w0, w0 + nw) of `order`
+    int apg, int nwg,                                  // the launch shape: atoms per workgroup (WPA == 1: its waves), workgroups
     const AniParams* __restrict__ P, const AngularConsts C, int cap, int capA, int tile, const float4* __restrict__ recA_g,
     const float4* __restrict__ recB_g, const int* __restrict__ tri_g, const int* __restrict__ cnt_a, const int* __restrict__ cnt_ro,
     const float* __restrict__ angular_grad, int ld_angular, float4* __restrict__ leg_force, float4* __restrict__ centre_force,
     const int* __restrict__ ids_g, float4* __restrict__ recv,      // recv != NULL (two waves per atom only): see "where the leg forces go"
-    int vec_ok, int NB, int lds_per_atom, const int* __restrict__ order, int w0, int nw,     // positions [w0, w0 + nw) of `order`
+    int vec_ok, int NB, int lds_per_atom,
     int class_word) {      // this backprop()'s stamp (CLASSES != 0)
+    // (order, the range and the shape first: the leading argument words are in scalar registers when the wave starts -- the atom's id is
+    //  requested without a wait; the launch shape as arguments, not from the hidden argument block: device_common.h)
     // CLASSES (launches by class of atoms, nnpops_ani_check): 0 -- one launch for everybody, `tile` covers every record slot;
     // 1 -- the launch of one class: an atom that has outgrown the class since check() (more angular neighbours than `tile`) is LEFT
     // OUT here -- the launch says so by writing this backprop()'s stamp to class_flag -- and evaluated by the launch of mode 2, which
@@ -148,10 +152,18 @@ __global__ __launch_bounds__(WPA == 2 ? 128 : 64 * kWavesPerGroup, OCC) void ani
     const int lane = lane_id();
     const int wig = __builtin_amdgcn_readfirstlane(wave_in_group());
     const int role = WPA == 2 ? wig : 0;
-    // one wave per atom: a workgroup holds blockDim / 64 independent atoms (fewer, larger dispatches), each with its own LDS slice
-    const int atoms_per_group = WPA == 2 ? 1 : (int)(blockDim.x >> 6);
+    // one wave per atom: a workgroup holds `apg` independent atoms (fewer, larger dispatches), each with its own LDS slice
+    const int atoms_per_group = WPA == 2 ? 1 : apg;
     const int slot_in_group = WPA == 2 ? 0 : wig;
     const int nA = C.nA;
+    // (the first atom's id is requested here, from argument words that are in registers at the wave's start: the loads of the other
+    //  arguments and their wait run under that round trip, not in front of it)
+    // (AHEAD: not the GENERIC instantiations -- one more value alive across their set-up took them from 72 to 73 vector registers and
+    //  from seven waves per SIMD to six; they ask in the loop as before)
+    constexpr bool AHEAD = !GENERIC;
+    const int w_first = blockIdx.x * atoms_per_group + slot_in_group;
+    int i_ahead = 0;
+    if constexpr (AHEAD) i_ahead = (order && w_first < nw) ? order[w0 + w_first] : w0 + w_first;
     // tile: edge of the LDS pair matrix and number of record slots of THIS launch (<= capA, the stride of the global arrays): check()
     // groups the atoms by their number of angular neighbours and the groups are launched one after the other, each with the
     // LDS its atoms need -- 7 KB for up to 32 neighbours, 15 KB for 48, 27 KB for 64: in a batch of compact molecules (BASELINE
@@ -241,9 +253,12 @@ __global__ __launch_bounds__(WPA == 2 ? 128 : 64 * kWavesPerGroup, OCC) void ani
         }
     }
 
-    const int stride_atoms = gridDim.x * atoms_per_group;
-    for (int w = blockIdx.x * atoms_per_group + slot_in_group; w < nw; w += stride_atoms) {
-        int i = order ? order[w0 + w] : w0 + w;
+    const int stride_atoms = nwg * atoms_per_group;
+    for (int w = w_first; w < nw; w += stride_atoms) {
+        int i = AHEAD ? i_ahead : order ? order[w0 + w] : w0 + w;
+        if constexpr (AHEAD) {                                 // (the next one: under this atom's work)
+            if (w + stride_atoms < nw) i_ahead = order ? order[w0 + w + stride_atoms] : w0 + w + stride_atoms;
+        }
         if ((unsigned)i >= (unsigned)C.N) i = w0 + w;          // (a void grid build leaves no valid order: stay in bounds)
         // (the first batch of triple words and the first 64 records are requested before the counts are known: what lies behind
         //  the atom's last triple / record is allocated and ignored -- one dependent round trip less per atom, ani_angular_mfma.h)

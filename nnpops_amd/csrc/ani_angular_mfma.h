@@ -444,22 +444,33 @@ struct MfmaForward {
 
 template <bool TORCHANI, int NFRP, int NFZP, int WPA, int OCC, int UNI = 0, bool DYN = false>
 __global__ __launch_bounds__(WPA == 2 ? 128 : 64 * kWavesPerGroup, OCC) void ani_angular_forward_mfma(
+    const int* __restrict__ order, int w0, int nw,       // this launch covers positions [w0, w0 + nw) of `order` (NULL: atom = position)
+    int wpg, int nwg,                                    // its shape: waves per workgroup (one atom each unless WPA == 2), workgroups
     const AniParams* __restrict__ P, int cap, int capA, int CH, const float4* __restrict__ recA_g,
     const float4* __restrict__ recB_g, const int* __restrict__ tri_g, const int* __restrict__ cnt_a,
-    const int* __restrict__ cnt_ro, float* __restrict__ angular, int ld_angular, int vec_ok, int lds_per_atom,
-    const int* __restrict__ order, int w0, int nw) {      // this launch covers positions [w0, w0 + nw) of `order` (NULL: atom = position)
+    const int* __restrict__ cnt_ro, float* __restrict__ angular, int ld_angular, int vec_ok, int lds_per_atom) {
+    // (order, the range and the shape first: the leading argument words are in scalar registers when the wave starts, so the atom's id
+    //  is requested without a wait; the launch shape as arguments, not from the hidden argument block -- device_common.h)
     extern __shared__ __attribute__((aligned(16))) char lds_raw[];
     const int wig = __builtin_amdgcn_readfirstlane(wave_in_group());        // wave-uniform: keeps per-atom addressing scalar
     const int slot_in_group = WPA == 2 ? 0 : wig;               // which atom of the workgroup
+    const int natoms_group = WPA == 2 ? 1 : wpg;
+    const int stride_atoms = nwg * natoms_group;
+    // The id of the first atom is requested HERE, from argument words that are in registers at the start: the set-up of the constants
+    // below (three groups of loads through P, each with its wait) runs under that round trip, not in front of it.
+    // (AHEAD: not where TORCHANI = false -- those instantiations have no scalar register to spare, the early request cost each of them
+    //  four more bytes of scratch; they ask in the loop as before)
+    constexpr bool AHEAD = TORCHANI;
+    const int w_first = blockIdx.x * natoms_group + slot_in_group;
+    int i_ahead = 0;
+    if constexpr (AHEAD) i_ahead = (order && w_first < nw) ? order[w0 + w_first] : w0 + w_first;
     MfmaForward<TORCHANI, NFRP, NFZP, WPA, UNI, DYN> F;
     F.init(P, capA, CH, vec_ok, angular, ld_angular, lds_raw + (size_t)slot_in_group * lds_per_atom, WPA == 2 ? wig : 0);
     F.write_zero_record();
     const int lane = F.lane, NB = F.NB;
 
-    const int natoms_group = WPA == 2 ? 1 : (blockDim.x >> 6);
-    const int stride_atoms = gridDim.x * natoms_group;
-    for (int w = blockIdx.x * natoms_group + slot_in_group; w < nw; w += stride_atoms) {
-        int i = order ? order[w0 + w] : w0 + w;
+    for (int w = w_first; w < nw; w += stride_atoms) {
+        int i = AHEAD ? i_ahead : order ? order[w0 + w] : w0 + w;
         if ((unsigned)i >= (unsigned)P->N) i = w0 + w;         // (a void grid build leaves no valid order: stay in bounds)
         int n, nro;
         clamp_counts(cnt_a[i], cnt_ro[i], cap, capA, n, nro);
@@ -478,7 +489,10 @@ __global__ __launch_bounds__(WPA == 2 ? 128 : 64 * kWavesPerGroup, OCC) void ani
                        load_angular_records(recA_g + (size_t)i * capA, recB_g + (size_t)i * capA, n, F.recA, F.recB);
                    }
                });
-        if (w + stride_atoms < nw) F.sync();                   // (another atom follows: records and staging area must be free)
+        if (w + stride_atoms < nw) {                           // (another atom follows: records and staging area must be free)
+            F.sync();
+            if constexpr (AHEAD) i_ahead = order ? order[w0 + w + stride_atoms] : w0 + w + stride_atoms;
+        }
     }
 }
 

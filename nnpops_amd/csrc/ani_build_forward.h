@@ -68,7 +68,7 @@ __global__ __launch_bounds__(128, OCC) void ani_build_forward(const AniParams* _
     const AtomGroups G = carve_groups(groups, P->S, P->NB);
     int* shared = groups + ((group_ints(P->S, P->NB, cap) + 3) & ~(size_t)3);       // [0] angular count, [1] radial-only count
     int* tri_l = (int*)(lds_raw + tri_offset);
-    clear_cell_histogram(in.use_cells ? in.cell_hist : nullptr);
+    clear_cell_histogram(in.cell_hist, (int)blockIdx.x * 128 + (int)threadIdx.x, nw * 128);      // (nw workgroups of 128; NULL unless a two-kernel build came before)
 
     const float rcr2 = P->rcr2, rca2 = P->rca2;
     Box b{};

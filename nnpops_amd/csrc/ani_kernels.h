@@ -484,13 +484,14 @@ __global__ __launch_bounds__(64 * kWavesPerGroup) void ani_neighbors_allpairs(co
                                                              int* __restrict__ tri,
                                                              int* __restrict__ cnt_a, int* __restrict__ cnt_ro, int* __restrict__ cnt_pos, int* __restrict__ status,
                                                              float* __restrict__ radial, int ld_radial, int lds_per_wave, int w0, int nw,
+                                                             int wpg,                                        // waves per workgroup of this launch
                                                              const int* __restrict__ molecule = nullptr) {   // per-atom molecule index (BATCH_BOX only)
     extern __shared__ __attribute__((aligned(16))) char lds_raw[];
     float4* stage = (float4*)(lds_raw + (size_t)wave_in_group() * lds_per_wave);
     float* rscratch = (float*)(stage + cap);
     const AtomGroups G = carve_groups((int*)(rscratch + 3 * cap + 64 * P->S), P->S, P->NB);
-    if (wave_global_id() >= nw) return;
-    const int i = w0 + wave_global_id();                   // this launch covers atoms [w0, w0 + nw)
+    if (wave_global_id(wpg) >= nw) return;
+    const int i = w0 + wave_global_id(wpg);                // this launch covers atoms [w0, w0 + nw)
     const int lane = lane_id();
     const int N = P->N;
     const float rcr2 = P->rcr2, rca2 = P->rca2;
@@ -539,27 +540,42 @@ __global__ __launch_bounds__(64 * kWavesPerGroup) void ani_neighbors_allpairs(co
 // Cell-grid search (celllist.h): one wave per atom walks the 3x3x3 stencil of its cell; candidates
 // are read as coalesced float4 {x,y,z,(species<<24)|id} runs.  Row order = stencil order.
 template <bool PERIODIC>
-__global__ __launch_bounds__(64 * kWavesPerGroup) void ani_neighbors_cells(const AniParams* __restrict__ P,
-                                                          const float* __restrict__ box,
+// (the arguments a wave needs for its first requests -- the grid, its slot's position and cell -- and its first branches come first:
+//  the leading argument words are in scalar registers when the wave starts, see ani_radial_bwd.h)
+__global__ __launch_bounds__(64 * kWavesPerGroup) void ani_neighbors_cells(int* __restrict__ cell_hist,      // the histogram to clear: only behind a two-kernel build (celllist.h)
                                                           const CellGrid* __restrict__ grid,
-                                                          const int* __restrict__ cell_start,
+                                                          const float4* __restrict__ sorted_pos,
                                                           const int* __restrict__ sorted_cell,
-                                                          const float4* __restrict__ sorted_pos, float4* __restrict__ nbr,
+                                                          int slot0, int nslots,
+                                                          int wpg,                                           // waves per workgroup of this launch
+                                                          int lds_per_wave,
+                                                          const AniParams* __restrict__ P,
+                                                          const float* __restrict__ box,
+                                                          const int* __restrict__ cell_start,
+                                                          float4* __restrict__ nbr,
                                                           int cap, int capA, float4* __restrict__ recA,
                                                           float4* __restrict__ recB, int* __restrict__ ids,
                                                           int* __restrict__ tri,
                                                           int* __restrict__ cnt_a, int* __restrict__ cnt_ro, int* __restrict__ cnt_pos,
                                                           int* __restrict__ status, float* __restrict__ radial,
-                                                          int ld_radial, int lds_per_wave, int* __restrict__ cell_hist, int slot0, int nslots) {
+                                                          int ld_radial) {
     extern __shared__ __attribute__((aligned(16))) char lds_raw[];
     float4* stage = (float4*)(lds_raw + (size_t)wave_in_group() * lds_per_wave);
     float* rscratch = (float*)(stage + cap);
     const AtomGroups G = carve_groups((int*)(rscratch + 3 * cap + 64 * P->S), P->S, P->NB);
     const int lane = lane_id();
-    const int slot_id = slot0 + wave_global_id();          // position in cell order; this launch covers [slot0, slot0 + nslots)
-    clear_cell_histogram(cell_hist);
-    if (wave_global_id() >= nslots) return;
+    const int wave_id = wave_global_id(wpg);
+    const int slot_id = slot0 + wave_id;                   // position in cell order; this launch covers [slot0, slot0 + nslots)
+    if (wave_id >= nslots) return;
+    // Everything that depends on nothing but the slot is requested at once, from argument words that are in registers at the wave's
+    // start: the grid, the slot's position and cell (slots below nslots exist whatever the build made of them), the box.  One round
+    // trip, where "arguments, then grid, then position and cell" were three.
     const CellGrid g = load_built_grid(grid);
+    const float4 me = sorted_pos[slot_id];
+    const int c = sorted_cell[slot_id];                    // (written in sorted order by the grid build: no load that waits for the id)
+    Box b{};
+    if (PERIODIC) b = load_box(box);
+    clear_cell_histogram(cell_hist, wave_id * 64 + lane, nslots * 64);      // (the nslots waves that stay)
     if (!g.ok) {                                           // box too small for the stencil: tell the host
         if (lane == 0) {
             if (slot_id == 0) atomicOr(&status[kStatOverflow], refused_grid_bits(g));
@@ -570,10 +586,6 @@ __global__ __launch_bounds__(64 * kWavesPerGroup) void ani_neighbors_cells(const
         return;
     }
     const float rcr2 = P->rcr2, rca2 = P->rca2;
-    Box b{};
-    if (PERIODIC) b = load_box(box);
-    const float4 me = sorted_pos[slot_id];
-    const int c = sorted_cell[slot_id];                    // (written in sorted order by the grid build: no load that waits for the id)
     const int i = __float_as_int(me.w) & kIdMask;
     int cx, cy, cz;
     split_cell(g, c, cx, cy, cz);                          // (no integer division; exact: celllist.h)

@@ -27,17 +27,23 @@ namespace nnpops {
 // lane, requested with the atom's gradient row; no id rows, no search.
 template <int NR4, int CAPA, bool LAT = false, bool RECV = false>
 __global__ __launch_bounds__(64 * kWavesPerGroup, LAT ? 4 : 8) void ani_radial_backward_lanes(
-    const AniParams* __restrict__ P, const int* __restrict__ species, const float4* __restrict__ nbr, int cap,
-    const int* __restrict__ cnt_pos, const float* __restrict__ radial_grad, int ld_radial,
-    const int* __restrict__ ids, const float4* __restrict__ leg_force, const float4* __restrict__ centre_force,
+    // (what the wave's first requests and first branch need comes first: the leading argument words are in scalar registers when
+    //  the wave starts -- kernel-argument preloading, nnpops_amd/build.py -- and N, S by value gate no request on a load through P)
+    const float4* __restrict__ nbr, const int* __restrict__ cnt_pos,
     const int* __restrict__ order,     // atoms in cell order, or NULL
-    float* __restrict__ pos_grad, int lds_per_wave, int w0, int nw) {
+    const float* __restrict__ radial_grad, int w0, int nw, int cap, int ld_radial, int N, int S,
+    const AniParams* __restrict__ P, const int* __restrict__ species,
+    const int* __restrict__ ids, const float4* __restrict__ leg_force, const float4* __restrict__ centre_force,
+    float* __restrict__ pos_grad, int lds_per_wave) {
     constexpr int NR = 4 * NR4;
     constexpr int QL = CAPA / 4, RPP = 64 / QL, NT = CAPA / RPP;      // id row = QL 16-byte pieces; RPP rows per pass of the wave; NT passes cover a row's worth of neighbours
     extern __shared__ __attribute__((aligned(16))) char lds_raw[];
     float* g_own = (float*)(lds_raw + (size_t)wave_in_group() * lds_per_wave);      // [S * NR] this atom's gradient row
     const int lane = lane_id();
-    const int wl = order ? xcd_contiguous_wave_id() : wave_global_id();      // this launch covers positions [w0, w0 + nw)
+    // (launched with kWavesPerGroup waves per workgroup, one wave per position: the launch shape follows from nw)
+    constexpr int WPG = kWavesPerGroup;
+    const int nwg = (int)((unsigned)(nw + WPG - 1) / WPG);
+    const int wl = order ? xcd_contiguous_wave_id(WPG, nwg) : wave_global_id(WPG);      // this launch covers positions [w0, w0 + nw)
     if (wl >= nw) return;
     const int w = __builtin_amdgcn_readfirstlane(w0 + wl);         // (wave-uniform: counts and atom id through the scalar cache)
     // Rows and counts are stored by POSITION in this walk (the builders' slot in cell order, or the atom index): the row, its counts
@@ -46,8 +52,8 @@ __global__ __launch_bounds__(64 * kWavesPerGroup, LAT ? 4 : 8) void ani_radial_b
     const float4 first = row[min(lane, cap - 1)];          // rows are contiguous (flush_row): requested before the counts are known
     const int counts = cnt_pos[w];
     int i = order ? order[w] : w;
-    if ((unsigned)i >= (unsigned)P->N) i = w;              // (a void grid build leaves no valid order: stay in bounds)
-    const int width = P->S * NR;
+    if ((unsigned)i >= (unsigned)N) i = w;              // (a void grid build leaves no valid order: stay in bounds)
+    const int width = S * NR;
     int na, nro;
     int raw_a, raw_ro, my_species;                         // (the species rides in the same word: the neighbours' gradient rows are
     unpack_cnt_pos(counts, raw_a, raw_ro, my_species);     //  addressed with it, and species[i] would be one more dependent round trip)

@@ -285,7 +285,8 @@ static __global__ void order_cells(int N, const float* __restrict__ pos, const C
 //                                  the same cell-ordered arrays as order_cells
 //   (consumer)                     the kernel that walks the grid next clears the histogram for the
 //                                  following build (clear_cell_histogram): no memset node, and a captured
-//                                  graph replays correctly
+//                                  graph replays correctly.  Only behind THIS build: nothing else writes the
+//                                  histogram, so it is zero between evaluations whatever builds alternate
 // A bin that overflows clears grid.ok; the owner grows the bins in its check() and rebuilds.
 // ---------------------------------------------------------------------------------------------
 constexpr int kBinnedAtoms = 65536;
@@ -854,12 +855,15 @@ __device__ __forceinline__ int stencil_slot(const PrefixStencil& S, int k) {
     return k + __builtin_amdgcn_ds_bpermute(r << 2, S.delta);
 }
 
-// Called by the kernel that consumes the grid (all of its threads, before any early exit): leaves the
-// histogram of the two-kernel build zeroed for the next build.  `hist` may be NULL (five-kernel path).
-__device__ __forceinline__ void clear_cell_histogram(int* __restrict__ hist) {
+// Called by the kernel that consumes the grid of a two-kernel build: leaves the histogram zeroed for the next build.
+// `nthreads` threads call, each with its own `tid` in [0, nthreads) -- the caller says which, from values it has anyway (no read
+// of blockDim / gridDim, device_common.h).  `hist` is NULL behind every other build: the one-launch build and the five-kernel
+// path never touch the histogram, so the host (which knows what it launched) passes NULL and the wave goes straight on.
+// (neither unrolled nor interleaved: either needs the trip count, an integer division per wave.)
+__device__ __forceinline__ void clear_cell_histogram(int* __restrict__ hist, int tid, int nthreads) {
     if (hist == nullptr) return;
-    const int stride = gridDim.x * blockDim.x;
-    for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < kHistWords; c += stride) hist[c] = 0;
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+    for (int c = tid; c < kHistWords; c += nthreads) hist[c] = 0;
 }
 
 // Host side: the buffers of one grid and the launch sequence (celllist_host.h: their sizes and their owner, CellList).
@@ -871,7 +875,7 @@ struct CellBuffers {
     float4* sorted_pos = nullptr;                              // [N]
     int max_cells = 0;
     // two-kernel path (optional): a zero-initialised histogram of kHistWords ints that the consumer kernel
-    // clears again after every build, and bins of kBinnedCells * bin_cap ints
+    // clears again after every two-kernel build (nothing else writes it), and bins of kBinnedCells * bin_cap ints
     int* hist = nullptr;
     int* bins = nullptr;
     int bin_cap = 0;

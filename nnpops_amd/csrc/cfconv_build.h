@@ -95,7 +95,7 @@ __global__ __launch_bounds__(64) void rows_cells(const float* __restrict__ box, 
                                                  int* __restrict__ lo_cnt, int* __restrict__ status,
                                                  int* __restrict__ cell_hist) {
     const int lane = lane_id();
-    clear_cell_histogram(cell_hist);
+    clear_cell_histogram(cell_hist, (int)blockIdx.x * 64 + lane, (int)gridDim.x * 64);      // (one wave per workgroup)
     const CellGrid g = *grid;
     if (!g.ok) {
         if (lane == 0) {

@@ -73,19 +73,26 @@ __device__ __forceinline__ void wave_fence() {
     __builtin_amdgcn_wave_barrier();
 }
 __device__ __forceinline__ int wave_in_group() { return threadIdx.x >> 6; }
-__device__ __forceinline__ int wave_global_id() { return blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); }
+// The per-atom ANI kernels are told their launch shape -- `wpg` waves per workgroup, `nwg` workgroups -- as compile-time values or
+// kernel arguments: blockDim and gridDim live in the hidden argument block, and reading them there is two dependent round trips (one
+// of them a vector load) in front of every wave's first useful request.  The forms without arguments read them and are for kernels
+// where that does not matter.
+__device__ __forceinline__ int wave_global_id(int wpg) { return blockIdx.x * wpg + (threadIdx.x >> 6); }
+__device__ __forceinline__ int wave_global_id() { return wave_global_id(blockDim.x >> 6); }
 
 // XCD-aware work order.  MI355X deals workgroups round-robin to its 8 XCDs (workgroup g runs on XCD g % 8), each
 // with a private L2.  When neighbouring work items share data (atoms adjacent in cell order gather the same rows),
 // give every XCD a CONTIGUOUS eighth of the ordered work instead of every eighth item: otherwise all eight L2s end
 // up fetching everything.  Returns the position of this wave in the ordered sequence (a bijection on
-// [0, gridDim.x * waves_per_group)).
-__device__ __forceinline__ int xcd_contiguous_wave_id() {
-    const int g = blockIdx.x, nwg = gridDim.x, xcd = g & 7;
-    int start = 0;
-    for (int c = 0; c < xcd; c++) start += (nwg - c + 7) >> 3;          // workgroups that land on the XCDs before mine
-    return (start + (g >> 3)) * (blockDim.x >> 6) + (threadIdx.x >> 6);
+// [0, nwg * wpg)).
+// XCD c is dealt ceil((nwg - c) / 8) = (nwg >> 3) + (c < (nwg & 7)) workgroups, so the ones that land on the XCDs before mine are
+// xcd * (nwg >> 3) + min(xcd, nwg & 7): no loop.
+__device__ __forceinline__ int xcd_contiguous_wave_id(int wpg, int nwg) {
+    const int g = blockIdx.x, xcd = g & 7;
+    const int start = xcd * (nwg >> 3) + min(xcd, nwg & 7);
+    return (start + (g >> 3)) * wpg + (threadIdx.x >> 6);
 }
+__device__ __forceinline__ int xcd_contiguous_wave_id() { return xcd_contiguous_wave_id(blockDim.x >> 6, gridDim.x); }
 
 // number of set bits of `mask` strictly below this lane
 __device__ __forceinline__ int prefix_popc(unsigned long long mask) {
