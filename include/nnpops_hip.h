@@ -319,6 +319,24 @@ int nnpops_cfconv_neighbors_build_count(nnpops_cfconv_neighbors_t h, unsigned lo
  * any non-periodic list.  The current build is invalidated (build_count() returns 0 until the next build()).  num_molecules <= 0 (or a
  * NULL table) restores the single-system list.  Blocks on the list's stream; not capturable. */
 int nnpops_cfconv_neighbors_set_molecules(nnpops_cfconv_neighbors_t h, int num_molecules, const int32_t* molecule_offsets);
+/* Batched evaluation of PERIODIC frames behind one list, every frame in its own box (a minibatch of an NPT trajectory): atoms
+ * [frame_offsets[m], frame_offsets[m+1]) form frame m (host array, num_frames + 1 entries, first 0, last num_atoms, strictly
+ * increasing).  Valid on a list created periodic = 1 only.  With frames set
+ *   - nnpops_cfconv_neighbors_build reads box as device [num_frames][3][3]: atom i of frame m is paired only with atoms of its own
+ *     frame, through the minimum image of box[m] (the single-round rule of a single system; every box at least two cutoffs wide, the
+ *     caller's contract).  Frames are scanned all-pairs at every total size, candidates in ascending index order: a frame's rows, pair
+ *     slots and summation order are those of a periodic list that holds the frame alone;
+ *   - nnpops_cfconv_backprop_box reads box as [num_frames][3][3] and writes box_deriv [num_frames][3][3]: frame m's nine entries are
+ *     summed over its own pairs, shifts recovered against box[m], in float64 in a fixed order that depends on the frame's atom count
+ *     alone (no atomics: two calls agree bit for bit, and a frame's entries do not depend on its companions or its place);
+ *   - every other entry point is unchanged: check(), capacity growth, export(), nnpops_cfconv_compute / _backprop / _double_backward /
+ *     _backprop_weights / _double_backward_weights work from the stored rows.
+ * Every table is sized and uploaded by this call, those of the box pass included, so build, compute, backprop and backprop_box stay
+ * capturable once the row capacity has settled (the partial sums of the box pass belong to the convolution and are sized by its
+ * first nnpops_cfconv_backprop_box on a list of frames, as its other scratch).  Refused: a non-periodic list, offsets that do not start
+ * at 0 or end at num_atoms, an empty or decreasing frame; build() without a box on such a list is an error.  The current build is
+ * invalidated.  num_frames <= 0 (or a NULL table) restores the single-system list.  Blocks on the list's stream; not capturable. */
+int nnpops_cfconv_neighbors_set_frames(nnpops_cfconv_neighbors_t h, int num_frames, const int32_t* frame_offsets);
 /* The plan of a convolution: which kernels a layer of this shape and these weights runs, and how they are launched.  Pure host
  * arithmetic (no device is needed or touched); it reads the NNPOPS_CFCONV_* switches as nnpops_cfconv_create does and refuses what
  * create refuses about the layer (NULL weights, activation, gaussian_width, num_gaussians, width).  w1, b1, w2 as for create.

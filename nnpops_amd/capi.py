@@ -74,6 +74,7 @@ SIGNATURES = {
                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_cfconv_neighbors_build_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "nnpops_cfconv_neighbors_set_molecules": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "nnpops_cfconv_neighbors_set_frames": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "nnpops_cfconv_plan": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "nnpops_cfconv_describe": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "nnpops_cfconv_backprop_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -812,6 +813,7 @@ class CFConvNeighbors:
         self._h = C.c_void_p()
         self.num_atoms, self.cutoff, self.periodic = int(num_atoms), float(cutoff), bool(periodic)
         self.batched = False
+        self.num_frames = 0             # > 0: set_frames is in force; build() and CFConv.backprop_box() then take one box per frame
         self.device = torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
         _check(self._lib.nnpops_cfconv_neighbors_create(C.byref(self._h), self.num_atoms, self.cutoff, int(self.periodic),
                                                         self.device.index))
@@ -833,12 +835,27 @@ class CFConvNeighbors:
         _check(self._lib.nnpops_cfconv_neighbors_set_molecules(self._h, int(off.shape[0]) - 1, off.ctypes.data_as(C.c_void_p)))
         self.batched = True
 
+    def set_frames(self, frame_offsets):
+        """Treat a periodic list's atoms as a batch of periodic frames, each in its own box: atoms [offsets[m], offsets[m+1]) belong
+        to frame m and pair only with each other, through the minimum image of box[m]; build() then takes box [B, 3, 3] (None or an
+        empty list restores one system).  Invalidates the current build."""
+        if frame_offsets is None or len(frame_offsets) == 0:
+            _check(self._lib.nnpops_cfconv_neighbors_set_frames(self._h, 0, None))
+            self.num_frames = 0
+            return
+        off = np.ascontiguousarray(frame_offsets, dtype=np.int32)
+        _check(self._lib.nnpops_cfconv_neighbors_set_frames(self._h, int(off.shape[0]) - 1, off.ctypes.data_as(C.c_void_p)))
+        self.num_frames = int(off.shape[0]) - 1
+
+    def box_shape(self):
+        return (self.num_frames, 3, 3) if self.num_frames else (3, 3)
+
     def build(self, positions, box=None, check=True):
         _dev_f32(positions, "positions", (self.num_atoms, 3))
-        if self.periodic:
-            if box is None:
-                raise ValueError("periodic neighbour list needs box vectors")
-            _dev_f32(box, "box", (3, 3))
+        if self.periodic and box is not None:
+            _dev_f32(box, "box", self.box_shape())
+        elif self.periodic and not self.num_frames:
+            raise ValueError("periodic neighbour list needs box vectors")
         _check(self._lib.nnpops_cfconv_neighbors_set_stream(self._h, _stream_ptr(positions.device)))
         for _ in range(8):
             # (a non-periodic single-system list ignores a box; a batch of molecules hands it on and is refused)
@@ -964,16 +981,16 @@ class CFConv:
         return x_grad, pos_grad
 
     def backprop_box(self, neighbors, positions, x, out_grad, box):
-        """backprop() and the box-vector gradient of a periodic list -> (input_grad, position_grad, box_grad float32 (3, 3)).
-        ``positions`` and ``box`` must be those of the list's last build()."""
+        """backprop() and the box-vector gradient of a periodic list -> (input_grad, position_grad, box_grad float32 (3, 3), or
+        [B, 3, 3] on a list of B frames).  ``positions`` and ``box`` must be those of the list's last build()."""
         _dev_f32(positions, "positions", (self.num_atoms, 3))
         _dev_f32(x, "input", (self.num_atoms, self.width))
         _dev_f32(out_grad, "output_grad", (self.num_atoms, self.width))
         if box is not None:
-            _dev_f32(box, "box", (3, 3))
+            _dev_f32(box, "box", neighbors.box_shape())
         x_grad = torch.empty_like(x)
         pos_grad = torch.empty((self.num_atoms, 3), dtype=torch.float32, device=x.device)
-        box_grad = torch.empty((3, 3), dtype=torch.float32, device=x.device)
+        box_grad = torch.empty(neighbors.box_shape(), dtype=torch.float32, device=x.device)
         _check(self._lib.nnpops_cfconv_set_stream(self._h, _stream_ptr(x.device)))
         _check(self._lib.nnpops_cfconv_backprop_box(self._h, neighbors._h, _ptr(positions), _ptr(box), _ptr(x), _ptr(out_grad),
                                                     _ptr(x_grad), _ptr(pos_grad), _ptr(box_grad)))

@@ -89,6 +89,13 @@ struct nnpops_cfconv_neighbors {
     unsigned long long epoch = 0;      // number of the last build (process-wide counter): what a convolution keeps per list (its filter rows) is valid for one build
     bool cell_ordered = false;      // the last build went through the cell grid: cells.sorted_pos lists the atoms in cell order
     int2* d_segment = nullptr;      // [N] per-atom [lo, hi) of its molecule (batched lists only: nnpops_cfconv_neighbors_set_molecules)
+    // periodic frames (nnpops_cfconv_neighbors_set_frames), all sized and uploaded there: the per-atom {lo, hi, frame, 0} of rows_frames
+    // and the tables of the per-frame box pass (cfconv_box_grad.h): offsets [B + 1], one {frame, k} per workgroup, first_block [B + 1]
+    int4* d_frame = nullptr;
+    int* d_frame_offsets = nullptr;
+    int2* d_frame_blocks = nullptr;
+    int* d_frame_first = nullptr;
+    int num_frames = 0, frame_blocks = 0;
     int pair_cap() const { return (int)std::min<size_t>((size_t)N * cap / 2, (size_t)INT32_MAX - 1); }
 };
 
@@ -317,8 +324,9 @@ struct nnpops_cfconv {
     bool reuse_filters = true;                     // $NNPOPS_CFCONV_REUSE_FILTERS=0: always store
     int dy_log2 = 0;                               // log2 of p.dy_scale (nnpops_cfconv_describe)
     // box-gradient calls only (nnpops_cfconv_backprop_box), sized on first use like d_filt: the partial sums of the pass
-    // [cfconv_box_blocks(N)][9] and, on the vector path, the pair scalar of every row entry [N][cap]
+    // [cfconv_box_blocks(N)][9] ([N][9] once a list of frames has asked: ensure_box_buffers) and, on the vector path, the pair scalar of every row entry [N][cap]
     double* d_box_partials = nullptr;
+    size_t box_partials_len = 0;       // in partial sums (9 doubles each)
     float* d_row_s = nullptr;
     size_t row_s_len = 0;
     // weight-gradient calls only (nnpops_cfconv_backprop_weights), sized once on first use: the workgroups' partial sums
@@ -364,6 +372,7 @@ int nnpops_cfconv_neighbors_destroy(nnpops_cfconv_neighbors_t h) {
     if (!h) return NNPOPS_OK;
     DeviceGuard guard(h->device);
     dev_free(h->d_rows); dev_free(h->d_cnt); dev_free(h->d_status); dev_free(h->d_segment);
+    dev_free(h->d_frame); dev_free(h->d_frame_offsets); dev_free(h->d_frame_blocks); dev_free(h->d_frame_first);
     dev_free(h->d_lo_cnt); dev_free(h->d_half_off); dev_free(h->d_pid); dev_free(h->d_half_r); dev_free(h->d_half_ij); dev_free(h->d_ids);
     h->cells.release();
     delete h;
@@ -404,8 +413,62 @@ int nnpops_cfconv_neighbors_set_molecules(nnpops_cfconv_neighbors_t h, int num_m
     return NNPOPS_OK;
 }
 
+// Periodic frames: a batch of periodic systems behind one list, every frame in its own box.  Every table is sized and uploaded here --
+// that of rows_frames and those of the per-frame box pass -- so that build(), compute(), backprop() and backprop_box() allocate nothing.
+static void drop_frames(nnpops_cfconv_neighbors* h) {
+    dev_free(h->d_frame); dev_free(h->d_frame_offsets); dev_free(h->d_frame_blocks); dev_free(h->d_frame_first);
+    h->d_frame = nullptr; h->d_frame_offsets = nullptr; h->d_frame_blocks = nullptr; h->d_frame_first = nullptr;
+    h->num_frames = 0; h->frame_blocks = 0;
+}
+
+int nnpops_cfconv_neighbors_set_frames(nnpops_cfconv_neighbors_t h, int num_frames, const int32_t* frame_offsets) {
+    NNPOPS_REQUIRE(h != nullptr, "NULL handle");
+    DeviceGuard guard(h->device);
+    if (num_frames <= 0 || frame_offsets == nullptr) {           // back to one system
+        NNPOPS_HIP_TRY(hipStreamSynchronize(h->stream));         // (a build in flight may still read the tables)
+        drop_frames(h);
+        h->built = false;
+        return NNPOPS_OK;
+    }
+    NNPOPS_REQUIRE(h->periodic, "frames are periodic systems, each in its own box (this list was created non-periodic: batches of "
+                                "non-periodic molecules take nnpops_cfconv_neighbors_set_molecules)");
+    NNPOPS_REQUIRE(frame_offsets[0] == 0 && frame_offsets[num_frames] == h->N, "frame_offsets must start at 0 and end at num_atoms (%d)", h->N);
+    for (int m = 0; m < num_frames; m++)
+        NNPOPS_REQUIRE(frame_offsets[m] < frame_offsets[m + 1] && frame_offsets[m + 1] <= h->N,
+                       "frame %d is empty or offsets are not increasing", m);
+    std::vector<int4> fr(h->N);
+    std::vector<int2> blocks;
+    std::vector<int> first(num_frames + 1);
+    for (int m = 0; m < num_frames; m++) {
+        for (int i = frame_offsets[m]; i < frame_offsets[m + 1]; i++) fr[i] = int4{frame_offsets[m], frame_offsets[m + 1], m, 0};
+        first[m] = (int)blocks.size();
+        const int nb = cfconv_box_frame_blocks(frame_offsets[m + 1] - frame_offsets[m]);
+        for (int k = 0; k < nb; k++) blocks.push_back(int2{m, k});
+    }
+    first[num_frames] = (int)blocks.size();
+    NNPOPS_HIP_TRY(hipStreamSynchronize(h->stream));
+    drop_frames(h);
+    h->built = false;
+    int rc;
+    auto cleanup = [&](int code) { drop_frames(h); return code; };
+    if ((rc = dev_alloc(&h->d_frame, (size_t)h->N))) return cleanup(rc);
+    if ((rc = dev_alloc(&h->d_frame_offsets, (size_t)num_frames + 1))) return cleanup(rc);
+    if ((rc = dev_alloc(&h->d_frame_blocks, blocks.size()))) return cleanup(rc);
+    if ((rc = dev_alloc(&h->d_frame_first, first.size()))) return cleanup(rc);
+    if (hipMemcpy(h->d_frame, fr.data(), sizeof(int4) * fr.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(h->d_frame_offsets, frame_offsets, sizeof(int) * ((size_t)num_frames + 1), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(h->d_frame_blocks, blocks.data(), sizeof(int2) * blocks.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(h->d_frame_first, first.data(), sizeof(int) * first.size(), hipMemcpyHostToDevice) != hipSuccess)
+        return cleanup(fail(NNPOPS_ERR_HIP, "frame table upload failed"));
+    h->num_frames = num_frames;
+    h->frame_blocks = (int)blocks.size();
+    return NNPOPS_OK;
+}
+
 int nnpops_cfconv_neighbors_build(nnpops_cfconv_neighbors_t h, const float* positions, const float* box) {
     NNPOPS_REQUIRE(h != nullptr && positions != nullptr, "NULL argument");
+    NNPOPS_REQUIRE(!h->d_frame || box, "a list of periodic frames needs the box vectors of every frame, [num_frames][3][3] "
+                                       "(nnpops_cfconv_neighbors_set_frames)");
     NNPOPS_REQUIRE(!h->periodic || box, "periodic neighbour list needs box vectors");
     NNPOPS_REQUIRE(!h->d_segment || !box, "a list of batched molecules takes no box vectors (nnpops_cfconv_neighbors_set_molecules)");
     DeviceGuard guard(h->device);
@@ -415,8 +478,12 @@ int nnpops_cfconv_neighbors_build(nnpops_cfconv_neighbors_t h, const float* posi
     // positions and box are read in place (the rows keep displacements, nothing refers back to them later); the
     // status words are cleared by create() and by check() after it has read them, not per build
     // batched molecules overlap in space: the shared cell grid tells them nothing, so their rows come from the segmented scan at every size
-    const bool use_cells = N >= 1024 && !h->cells_disabled && !h->d_segment;
-    if (h->d_segment) {
+    // (so do periodic frames, each in its own box: rows_frames)
+    const bool use_cells = N >= 1024 && !h->cells_disabled && !h->d_segment && !h->d_frame;
+    if (h->d_frame) {
+        hipLaunchKernelGGL(rows_frames, dim3(N), dim3(64), 0, h->stream, N, h->num_frames, positions, box, (const int4*)h->d_frame, c2,
+                           h->d_rows, h->d_ids, h->cap, h->d_cnt, h->d_lo_cnt);
+    } else if (h->d_segment) {
         hipLaunchKernelGGL(rows_segments, dim3(N), dim3(64), 0, h->stream, N, positions, (const int2*)h->d_segment, c2, h->d_rows, h->d_ids,
                            h->cap, h->d_cnt, h->d_lo_cnt);
     } else if (use_cells) {
@@ -867,7 +934,14 @@ int dispatch_conv(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, const float* x,
 // what a box-gradient call keeps beside the backward pass's own buffers (first use, or the neighbour rows have grown: not capturable)
 int ensure_box_buffers(nnpops_cfconv* h, nnpops_cfconv_neighbors* nb, bool row_s) {
     int rc;
-    if (!h->d_box_partials && (rc = dev_alloc(&h->d_box_partials, (size_t)9 * cfconv_box_blocks(h->p.N)))) return rc;
+    // (a list of frames leaves one partial sum per workgroup of its pass, at most one per atom whatever the partition)
+    const size_t partials = nb->d_frame ? (size_t)h->p.N : (size_t)cfconv_box_blocks(h->p.N);
+    if (h->box_partials_len < partials) {
+        dev_free(h->d_box_partials);
+        h->d_box_partials = nullptr; h->box_partials_len = 0;
+        if ((rc = dev_alloc(&h->d_box_partials, 9 * partials))) return rc;
+        h->box_partials_len = partials;
+    }
     const size_t need = (size_t)nb->N * nb->cap;
     if (row_s && h->row_s_len < need) {
         dev_free(h->d_row_s);
@@ -1125,6 +1199,23 @@ int nnpops_cfconv_backprop_box(nnpops_cfconv_t h, nnpops_cfconv_neighbors_t neig
     if (row_s && (rc = launch_vector<true, true>(h, neighbors, input, output_deriv, nullptr, nullptr)) != NNPOPS_OK) return rc;
     // ... then one pass over the rows and the pair scalars it left behind, and the sum of its workgroups (cfconv_box_grad.h)
     const int N = h->p.N, nblocks = cfconv_box_blocks(N);
+    if (neighbors->d_frame) {
+        // periodic frames: box and box_deriv are [num_frames][3][3]; every frame's workgroups, then one workgroup per frame
+        const int total = neighbors->frame_blocks, B = neighbors->num_frames;
+        if (row_s)
+            hipLaunchKernelGGL(cfconv_box_partials_frames<true>, dim3(total), dim3(kBoxThreads), 0, h->stream, N, positions, box,
+                               (const int*)neighbors->d_frame_offsets, (const int2*)neighbors->d_frame_blocks, neighbors->d_rows,
+                               neighbors->d_cnt, neighbors->cap, (const int*)nullptr, 0, (const float*)h->d_row_s, h->d_box_partials);
+        else
+            hipLaunchKernelGGL(cfconv_box_partials_frames<false>, dim3(total), dim3(kBoxThreads), 0, h->stream, N, positions, box,
+                               (const int*)neighbors->d_frame_offsets, (const int2*)neighbors->d_frame_blocks, neighbors->d_rows,
+                               neighbors->d_cnt, neighbors->cap, (const int*)neighbors->d_pid, neighbors->pair_cap(),
+                               (const float*)h->d_pair_s, h->d_box_partials);
+        hipLaunchKernelGGL(cfconv_box_finish_frames, dim3(B), dim3(kBoxThreads), 0, h->stream, (const int*)neighbors->d_frame_first,
+                           (const double*)h->d_box_partials, box_deriv);
+        NNPOPS_HIP_TRY(hipGetLastError());
+        return NNPOPS_OK;
+    }
     const float4* order = neighbors->cell_ordered ? neighbors->cells.sorted_pos : nullptr;
     if (row_s)
         hipLaunchKernelGGL(cfconv_box_partials<true>, dim3(nblocks), dim3(kBoxThreads), 0, h->stream, N, positions, box, neighbors->d_rows,

@@ -87,6 +87,39 @@ __global__ __launch_bounds__(64) void rows_segments(int N, const float* __restri
     if (lane == 0) publish_row(i, n, n_lo, cnt, lo_cnt);
 }
 
+// Periodic frames (nnpops_cfconv_neighbors_set_frames): rows_segments with every frame in its own box.  frame[i] = {lo, hi, m, 0}, the
+// atom's frame [lo, hi) and its number: one 16-byte entry at a wave-uniform address (blockIdx.x = i), so the frame, and behind it the
+// nine floats of boxes[m] (load_box), arrive through scalar loads and no vector load stands before the scan.  The displacement
+// arithmetic is that of rows_allpairs<true> -- pos[j] - pos[i], min_image<true> against the frame's box, the strict test on r^2,
+// candidates in ascending index -- so a frame's rows are those of rows_allpairs<true> on the frame alone with every index moved by
+// lo, whatever the other frames and their boxes hold: no lane reads a position outside [lo, hi) or a box other than m's.
+__global__ __launch_bounds__(64) void rows_frames(int N, int num_frames, const float* __restrict__ pos, const float* __restrict__ boxes,
+                                                  const int4* __restrict__ frame, float cutoff2, float4* __restrict__ rows,
+                                                  int* __restrict__ ids, int cap, int* __restrict__ cnt, int* __restrict__ lo_cnt) {
+    const int i = blockIdx.x, lane = lane_id();
+    if (i >= N) return;
+    const int4 fr = frame[i];
+    const int lo = max(fr.x, 0), hi = min(fr.y, N);         // (the host validated the table: the clamps keep a damaged one in bounds)
+    const int m = min(max(fr.z, 0), num_frames - 1);
+    const Box b = load_box(boxes + 9 * (size_t)m);
+    const float xi = pos[3 * i], yi = pos[3 * i + 1], zi = pos[3 * i + 2];
+    float4* row = rows + (size_t)i * cap;
+    int n = 0, n_lo = 0;
+    for (int base = lo; base < hi; base += 64) {
+        const int j = base + lane;
+        bool keep = false;
+        float dx = 0.f, dy = 0.f, dz = 0.f;
+        if (j < hi && j != i) {
+            dx = pos[3 * j] - xi; dy = pos[3 * j + 1] - yi; dz = pos[3 * j + 2] - zi;
+            min_image<true>(dx, dy, dz, b);
+            keep = dx * dx + dy * dy + dz * dz < cutoff2;          // strict, on r^2, as rows_allpairs
+        }
+        append(row, ids + (size_t)i * cap, cap, keep, dx, dy, dz, j, n);
+        n_lo += __popcll(__ballot(keep && j > i));
+    }
+    if (lane == 0) publish_row(i, n, n_lo, cnt, lo_cnt);
+}
+
 template <bool PERIODIC>
 __global__ __launch_bounds__(64) void rows_cells(const float* __restrict__ box, float cutoff2,
                                                  const CellGrid* __restrict__ grid, const int* __restrict__ cell_start,

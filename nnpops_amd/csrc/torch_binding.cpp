@@ -1036,12 +1036,13 @@ public:
     void build(const Tensor& positions) { buildImpl(positions, nullptr); }
 
     // Additive to the reference (whose binding is non-periodic, CFConvNeighbors.cpp:52,57,74, although its core
-    // supports a box, CFConv.h:57): the same list under periodic boundary conditions.  box: (3, 3), rows = vectors.
+    // supports a box, CFConv.h:57): the same list under periodic boundary conditions.  box: (3, 3), rows = vectors; on a holder
+    // with frames (set_frames) [B, 3, 3], a box for every frame.
     void buildPeriodic(const Tensor& positions, const Tensor& box) {
         if (!molecules.empty())
             throw std::runtime_error("CFConvNeighbors::build: a list of batched molecules (set_molecules) is non-periodic and takes no \"box\"");
         if (box.scalar_type() != torch::kFloat32) throw std::runtime_error("The type of \"box\" has to be float32");
-        if (box.dim() != 2 || box.size(0) != 3 || box.size(1) != 3) throw std::runtime_error("The shape of \"box\" has to be (3, 3)");
+        checkBoxShape(box);
         require_device_tensor(box, "box");
         const Tensor b = box.detach().contiguous();
         buildImpl(positions, &b);
@@ -1058,9 +1059,10 @@ public:
             periodic = box != nullptr;
             if (nnpops_cfconv_neighbors_create(&impl, (int)numAtoms, (float)cutoff, periodic ? 1 : 0, device.index()) != NNPOPS_OK)
                 raise_last("NNPOpsCFConvNeighbors");
-            if (!molecules.empty()) {
+            if (!molecules.empty() || !frames.empty()) {
                 try {
-                    applyMolecules();
+                    if (!molecules.empty()) applyMolecules();
+                    if (!frames.empty()) applyFrames();
                 } catch (...) {                                   // (offsets that do not fit these positions: no half-made handle stays behind)
                     nnpops_cfconv_neighbors_destroy(impl);
                     impl = nullptr;
@@ -1092,6 +1094,8 @@ public:
         for (int64_t v : offsets)
             if (v < 0 || v > INT32_MAX) throw std::runtime_error("set_molecules: molecule offsets must lie in [0, num_atoms]");
         if (!offsets.empty() && offsets.size() < 2) throw std::runtime_error("set_molecules: molecule offsets hold B + 1 entries (or none: one system)");
+        if (!offsets.empty() && !frames.empty())
+            throw std::runtime_error("set_molecules: this list holds periodic frames (set_frames); batched molecules are non-periodic systems");
         if (!offsets.empty() && impl && periodic) throw std::runtime_error("set_molecules: batched molecules are non-periodic systems (this list was built with a box)");
         const std::vector<int64_t> before = molecules;
         molecules = std::move(offsets);
@@ -1105,6 +1109,38 @@ public:
     }
     std::vector<int64_t> getMolecules() const { return molecules; }
     int64_t moleculeCount() const { return molecules.empty() ? 0 : (int64_t)molecules.size() - 1; }
+    // Additive: the atoms are a batch of PERIODIC frames, atoms [offsets[m], offsets[m+1]) frame m, every frame in its own box
+    // (nnpops_cfconv_neighbors_set_frames): build_periodic and the periodic ops then take box [B, 3, 3].  Kept and applied like the
+    // molecules; an empty list restores the single-system behaviour.  The current build is invalidated.
+    void setFrames(std::vector<int64_t> offsets) {
+        for (int64_t v : offsets)
+            if (v < 0 || v > INT32_MAX) throw std::runtime_error("set_frames: frame offsets must lie in [0, num_atoms]");
+        if (!offsets.empty() && offsets.size() < 2) throw std::runtime_error("set_frames: frame offsets hold B + 1 entries (or none: one system)");
+        if (!offsets.empty() && !molecules.empty())
+            throw std::runtime_error("set_frames: this list holds batched molecules (set_molecules), which are non-periodic; frames are periodic systems");
+        if (!offsets.empty() && impl && !periodic)
+            throw std::runtime_error("set_frames: frames are periodic systems, each in its own box (this list was built without a box)");
+        const std::vector<int64_t> before = frames;
+        frames = std::move(offsets);
+        if (!impl) return;
+        try {
+            applyFrames();
+        } catch (...) {
+            frames = before;                                      // (the handle kept its tables: a refused call changes nothing)
+            throw;
+        }
+    }
+    std::vector<int64_t> getFrames() const { return frames; }
+    int64_t frameCount() const { return frames.empty() ? 0 : (int64_t)frames.size() - 1; }
+    // the box of a build or of a periodic op: (3, 3), or [B, 3, 3] on a holder with B frames
+    void checkBoxShape(const Tensor& box) const {
+        if (frames.empty()) {
+            if (box.dim() != 2 || box.size(0) != 3 || box.size(1) != 3) throw std::runtime_error("The shape of \"box\" has to be (3, 3)");
+        } else if (box.dim() != 3 || box.size(0) != frameCount() || box.size(1) != 3 || box.size(2) != 3) {
+            throw std::runtime_error("The shape of \"box\" has to be [" + std::to_string(frameCount()) +
+                                     ", 3, 3]: this list holds periodic frames (set_frames), one box for each");
+        }
+    }
     double getCutoff() const { return cutoff; }
     bool isPeriodic() const { return periodic; }
     nnpops_cfconv_neighbors_t getImpl() const { return impl; }
@@ -1123,12 +1159,20 @@ private:
             raise_last("NNPOpsCFConvNeighbors::set_molecules");
     }
 
+    void applyFrames() {
+        const std::vector<int32_t> off(frames.begin(), frames.end());
+        nnpops_cfconv_neighbors_set_stream(impl, current_stream(device));
+        if (nnpops_cfconv_neighbors_set_frames(impl, off.empty() ? 0 : (int)off.size() - 1, off.empty() ? nullptr : off.data()) != NNPOPS_OK)
+            raise_last("NNPOpsCFConvNeighbors::set_frames");
+    }
+
     double cutoff;
     int64_t numAtoms = 0;
     bool periodic = false;
     torch::Device device = torch::kCPU;
     nnpops_cfconv_neighbors_t impl = nullptr;
     std::vector<int64_t> molecules;      // B + 1 offsets; empty: one system
+    std::vector<int64_t> frames;         // B + 1 offsets of periodic frames; empty: one system
 };
 using HolderPtr = torch::intrusive_ptr<Holder>;
 
@@ -1140,6 +1184,8 @@ TORCH_LIBRARY(NNPOpsCFConvNeighbors, m) {
         .def("build_count", &Holder::getBuildCount)
         .def("set_molecules", &Holder::setMolecules)
         .def("molecules", &Holder::getMolecules)
+        .def("set_frames", &Holder::setFrames)
+        .def("frames", &Holder::getFrames)
         .def_pickle([](const HolderPtr& self) -> double { return self->getCutoff(); },
                     [](double cutoff) -> HolderPtr { return HolderPtr::make(cutoff); });
 }
@@ -1234,10 +1280,10 @@ public:
     // the node that asked, for a backward pass that returns dL/dbox (the box vectors must be those of the list's last build).
     Tensor forwardPeriodic(const c10::IValue& neighbors_, const Tensor& positions_, const Tensor& box_, const Tensor& input_) {
         if (box_.scalar_type() != torch::kFloat32) throw std::runtime_error("The type of \"box\" has to be float32");
-        if (box_.dim() != 2 || box_.size(0) != 3 || box_.size(1) != 3) throw std::runtime_error("The shape of \"box\" has to be (3, 3)");
+        const NeighborsPtr nb = neighbors_.toCustomClass<Neighbors>();
+        nb->checkBoxShape(box_);                             // (3, 3), or [B, 3, 3] on a list of B frames
         require_device_tensor(box_, "box");
         if (box_.device() != positions_.device()) throw std::runtime_error("The device of \"box\" and \"positions\" has to be the same");
-        const NeighborsPtr nb = neighbors_.toCustomClass<Neighbors>();
         if (nb->moleculeCount() > 0)
             throw std::runtime_error("\"neighbors\" holds batched molecules (set_molecules), which are non-periodic: the convolution takes no \"box\" with them");
         if (!nb->getImpl()) throw std::runtime_error("\"neighbors\" has not been built");
@@ -1264,7 +1310,8 @@ public:
         if (wantBox) {
             if (!box_.defined()) throw std::runtime_error("a box gradient needs the box vectors of the forward pass");
             const Tensor box = dense(box_);
-            boxGrad = torch::empty({3, 3}, opts);
+            nb->checkBoxShape(box);
+            boxGrad = torch::empty(box.sizes(), opts);        // (3, 3), or [B, 3, 3] on a list of B frames
             launch("NNPOpsCFConv::backward", [&] {
                 return nnpops_cfconv_backprop_box(impl, nb->getImpl(), pos.data_ptr<float>(), box.data_ptr<float>(), in.data_ptr<float>(),
                                                   outputGrad.data_ptr<float>(), inputGrad.data_ptr<float>(), positionsGrad.data_ptr<float>(),
