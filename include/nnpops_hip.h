@@ -22,6 +22,7 @@
  *                                               src/pytorch/neighbors/getNeighborPairsCUDA.cu:31-101
  *   nnpops_neighbor_pairs_box_backward / _double_backward   box gradient and second derivatives of that op
  *                                               (the reference's CPU op differentiates both: getNeighborPairsCPU.cpp:56-98)
+ *   nnpops_neighbor_pairs_frames_*              (additive) the pair lists of a batch of frames, every frame in its own box
  *   nnpops_pme_direct                           pme::pme_direct (computeDirect)   src/pytorch/pme/pmeCUDA.cu:30-100
  *   nnpops_pme_direct_double_backward, nnpops_pme_reciprocal_spread_directional / _interpolate_second   second derivatives of both PME
  *                                               terms w.r.t. positions and charges (the reference refuses them)
@@ -482,6 +483,40 @@ int nnpops_neighbor_pairs_double_backward(int dtype, int num_atoms, int64_t num_
                                           const void* box, const void* deltas, const void* distances, const void* grad_distances,
                                           const void* gg_positions, const void* gg_box, void* d_grad_deltas, void* d_grad_distances,
                                           void* d_deltas, void* d_distances, void* stream);
+
+/* getNeighborPairsFrames: the pair lists of a batch of frames in one launch sequence, every frame in its own box (additive; the
+ * reference's op is single-system).  Frame m holds the atoms [offsets[m], offsets[m+1]) of positions; an atom is paired only with atoms
+ * of its own frame, through the minimum image of boxes[m], and a frame's slots hold the bits nnpops_neighbor_pairs_forward gives for
+ * that frame alone (atom indices are global).
+ *   nnpops_neighbor_pairs_frames_table (host only, no GPU): validates offsets [num_frames + 1] (first 0, ascending; empty frames are
+ *     fine) and cuts every frame's lower triangle, n(n-1)/2 pairs in row-major order, into consecutive segments of at most
+ *     NNPOPS_PAIRS_FRAMES_PART_PAIRS pairs.  rows: host int32 [S][5] = {frame, first atom, atom count, first flat pair, pair count},
+ *     ordered by frame, then by first pair, or NULL to count only.  Returns S (one workgroup per segment), or a negative error code.
+ *   table: the rows on the device.  The kernels clamp what they read from it: no table makes them touch memory outside positions
+ *     [num_atoms][3] and boxes [num_frames][3][3].
+ *   max_num_pairs == -1: one slot per pair of each frame's triangle, frames concatenated; num_slots = sum n(n-1)/2.
+ *   max_num_pairs > 0: num_slots = max_num_pairs; the compacted list, deterministic: grouped by neighbors[0] ascending, ascending
+ *     neighbors[1] inside a row -- a list nnpops_neighbor_pairs_build_index accepts.  Surplus pairs are dropped, num_pairs is the truth.
+ *   segment_slots: device int32 [S + 1], the first slot of every segment and the end of the last (the box gradient's input).
+ *   workspace: device, 256-byte aligned, nnpops_neighbor_pairs_frames_workspace_bytes(S) bytes.  No host synchronisation, capturable.
+ * nnpops_neighbor_pairs_frames_box_backward: grad_boxes[m][a][:] = - sum_k n_ka G_k over the slots of frame m, n_k and G_k as for
+ *   nnpops_neighbor_pairs_box_backward (n_k recovered from positions, boxes[m] and the delta).  One workgroup per segment adds its
+ *   own slots up in float64 in a fixed order, one wave per frame adds the frame's segments in segment order: no atomics, bitwise
+ *   reproducible.  workspace: device, 8-byte aligned, nnpops_neighbor_pairs_frames_box_backward_workspace_bytes(S) bytes.
+ * The position gradient of such a list is nnpops_neighbor_pairs_backward_indexed / _backward_ws, unchanged. */
+#define NNPOPS_PAIRS_FRAMES_PART_PAIRS 2079      /* = 65 * 64 / 2 - 1: a wave's quarter is eight rounds of 64 lanes */
+int64_t nnpops_neighbor_pairs_frames_table(int num_frames, const int64_t* offsets, int32_t* rows);
+int64_t nnpops_neighbor_pairs_frames_workspace_bytes(int num_segments);
+int nnpops_neighbor_pairs_frames_forward(int dtype, int num_atoms, int num_frames, int num_segments, const int32_t* table,
+                                         const void* positions, const void* boxes, double cutoff, int64_t max_num_pairs, int64_t num_slots,
+                                         int32_t* neighbors, void* deltas, void* distances, int32_t* num_pairs, int32_t* segment_slots,
+                                         void* workspace, void* stream);
+int64_t nnpops_neighbor_pairs_frames_box_backward_workspace_bytes(int num_segments);
+int nnpops_neighbor_pairs_frames_box_backward(int dtype, int num_atoms, int num_frames, int num_segments, const int32_t* table,
+                                              const int32_t* segment_slots, int64_t num_slots, const int32_t* neighbors,
+                                              const void* positions, const void* boxes, const void* deltas, const void* distances,
+                                              const void* grad_deltas, const void* grad_distances, void* grad_boxes, void* workspace,
+                                              void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * PME, direct-space part (replaces computeDirect: src/pytorch/pme/pmeCUDA.cu:30-100, pmeCPU.cpp:75-163) -- the immediate

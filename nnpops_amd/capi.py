@@ -164,6 +164,15 @@ SIGNATURES = {
                                                         C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_neighbor_pairs_backward_ws": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nnpops_neighbor_pairs_frames_table": (C.c_int64, [C.c_int, C.POINTER(C.c_int64), C.c_void_p]),
+    "nnpops_neighbor_pairs_frames_workspace_bytes": (C.c_int64, [C.c_int]),
+    "nnpops_neighbor_pairs_frames_forward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                                       C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p]),
+    "nnpops_neighbor_pairs_frames_box_backward_workspace_bytes": (C.c_int64, [C.c_int]),
+    "nnpops_neighbor_pairs_frames_box_backward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
+                                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None
@@ -568,6 +577,77 @@ def neighbor_pairs_double_backward(num_atoms, neighbors, deltas, distances, grad
         _check(lib().nnpops_neighbor_pairs_double_backward(_DTYPE_CODE[dt], num_atoms, slots, _ptr(neighbors), *(_ptr(t) for t in ins),
                                                            *(_ptr(t) for t in outs), _stream_ptr(dev)))
     return outs
+
+
+def neighbor_pairs_frames_table(offsets):
+    """The segment table of a batch of frames (host only, no GPU): int32 [S, 5] host tensor of {frame, first atom, atom count, first flat
+    pair, pair count}, ordered by frame, then by first pair.  offsets: B + 1 ascending ints, the first 0."""
+    offsets = [int(v) for v in offsets]
+    if not offsets:
+        raise ValueError('Expected "offsets" to hold at least one entry')
+    arr = (C.c_int64 * len(offsets))(*offsets)
+    L = lib()
+    segments = int(L.nnpops_neighbor_pairs_frames_table(len(offsets) - 1, arr, None))
+    if segments < 0:
+        _check(segments)
+    rows = torch.empty((segments, 5), dtype=torch.int32)
+    _check(min(0, int(L.nnpops_neighbor_pairs_frames_table(len(offsets) - 1, arr, C.c_void_p(rows.data_ptr())))))
+    return rows
+
+
+def neighbor_pairs_frames_forward(positions, cutoff, offsets, table, max_num_pairs=-1, boxes=None):
+    """-> (neighbors int32[2,P], deltas[P,3], distances[P], num_pairs int32[1], segment_slots int32[S+1]) on positions' device.
+
+    offsets as given to neighbor_pairs_frames_table, table its result on the device.  P = sum n(n-1)/2 over the frames when
+    max_num_pairs == -1, else max_num_pairs.  boxes [B,3,3] or None.  No host synchronisation."""
+    if not positions.is_cuda or positions.dtype not in _DTYPE_CODE:
+        raise ValueError('"positions" must be a float32 or float64 tensor on the HIP device (nnpops_amd has no CPU path)')
+    if positions.dim() != 2 or positions.size(1) != 3 or not positions.is_contiguous():
+        raise ValueError('Expected "positions" to be a contiguous (num_atoms, 3) tensor')
+    offsets = [int(v) for v in offsets]
+    n, frames, segments = positions.size(0), len(offsets) - 1, table.size(0)
+    if offsets[-1] != n:
+        raise ValueError(f'Expected the last offset ({offsets[-1]}) to be the 1st dimension size of "positions" ({n})')
+    if table.dtype != torch.int32 or table.dim() != 2 or table.size(1) != 5 or table.device != positions.device or not table.is_contiguous():
+        raise ValueError('Expected "table" to be a contiguous int32 (num_segments, 5) tensor on the device of "positions"')
+    max_num_pairs = int(max_num_pairs)
+    slots = sum((b - a) * (b - a - 1) // 2 for a, b in zip(offsets, offsets[1:])) if max_num_pairs == -1 else max_num_pairs
+    dev, dt = positions.device, positions.dtype
+    if boxes is not None and boxes.numel():
+        if tuple(boxes.shape) != (frames, 3, 3):
+            raise ValueError(f'Expected "box_vectors" to have shape ({frames}, 3, 3)')
+        boxes = boxes.to(device=dev, dtype=dt).contiguous()
+    else:
+        boxes = None
+    neighbors = torch.empty((2, max(slots, 0)), dtype=torch.int32, device=dev)
+    deltas = torch.empty((max(slots, 0), 3), dtype=dt, device=dev)
+    distances = torch.empty((max(slots, 0),), dtype=dt, device=dev)
+    num_pairs = torch.empty((1,), dtype=torch.int32, device=dev)
+    segment_slots = torch.empty((segments + 1,), dtype=torch.int32, device=dev)
+    L = lib()
+    ws = torch.empty((int(L.nnpops_neighbor_pairs_frames_workspace_bytes(segments)),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(L.nnpops_neighbor_pairs_frames_forward(_DTYPE_CODE[dt], n, frames, segments, _ptr(table), _ptr(positions), _ptr(boxes),
+                                                      float(cutoff), max_num_pairs, slots, _ptr(neighbors), _ptr(deltas), _ptr(distances),
+                                                      _ptr(num_pairs), _ptr(segment_slots), _ptr(ws), _stream_ptr(dev)))
+    return neighbors, deltas, distances, num_pairs, segment_slots
+
+
+def neighbor_pairs_frames_box_backward(table, segment_slots, neighbors, positions, boxes, deltas, distances, grad_deltas, grad_distances):
+    """grad_boxes [B,3,3] = - sum_k n_k (x) G_k over every frame's own slots (float64 sums in a fixed order, bitwise reproducible);
+    table / segment_slots as neighbor_pairs_frames_forward took and returned them, boxes in deltas' dtype."""
+    dev, dt = deltas.device, deltas.dtype
+    frames, segments, slots = boxes.size(0), table.size(0), distances.numel()
+    grad_boxes = torch.empty((frames, 3, 3), dtype=dt, device=dev)
+    L = lib()
+    with torch.cuda.device(dev):
+        ws = torch.empty((int(L.nnpops_neighbor_pairs_frames_box_backward_workspace_bytes(segments)) // 8,), dtype=torch.float64, device=dev)
+        _check(L.nnpops_neighbor_pairs_frames_box_backward(_DTYPE_CODE[dt], positions.size(0), frames, segments, _ptr(table),
+                                                           _ptr(segment_slots), slots, _ptr(neighbors), _ptr(positions.contiguous()),
+                                                           _ptr(boxes.contiguous()), _ptr(deltas.contiguous()), _ptr(distances.contiguous()),
+                                                           _ptr(grad_deltas.contiguous()), _ptr(grad_distances.contiguous()),
+                                                           _ptr(grad_boxes), _ptr(ws), _stream_ptr(dev)))
+    return grad_boxes
 
 
 def pme_direct(positions, charges, neighbors, deltas, distances, exclusions, alpha, coulomb, index=None, workspace_guard=False):

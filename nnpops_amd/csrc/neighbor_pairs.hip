@@ -745,3 +745,5 @@ int nnpops_neighbor_pairs_backward(int dtype, int num_atoms, int64_t num_slots, 
 }
 
 }  // extern "C"
+
+#include "neighbor_pairs_frames.h"      // getNeighborPairsFrames: batches of frames (shares wrapped_delta, scan_rows, fill_unused)

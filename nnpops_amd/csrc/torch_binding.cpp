@@ -13,6 +13,7 @@
 //   torch.ops.NNPOpsCFConv.operation_weights_twice / operation_periodic_weights_twice (additive: trainable weights under a force loss)
 //                                                         (reference src/pytorch/CFConv.cpp:276-291)
 //   torch.ops.neighbors.getNeighborPairs                  (reference src/pytorch/neighbors/neighbors.cpp:4)
+//   torch.ops.neighbors.getNeighborPairsFrames / frameTable   (additive: a batch of frames, every frame in its own box)
 //   torch.ops.NNPOpsBatchedNN.BatchedLinear               (reference src/pytorch/BatchedNN.cpp:48-50)
 //
 // Differences that are deliberate:
@@ -2098,6 +2099,184 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> neighbor_pairs_device_entry(const Ten
 TORCH_LIBRARY_IMPL(neighbors, AutogradCUDA, m) { m.impl("getNeighborPairs", neighbor_pairs_device_entry); }
 // (the backend key itself: what runs below autograd -- torch.inference_mode(), AutoDispatchBelowAutograd)
 TORCH_LIBRARY_IMPL(neighbors, CUDA, m) { m.impl("getNeighborPairs", neighbor_pairs_device_entry); }
+
+// ---------------------------------------------------------------------------------------------
+// getNeighborPairsFrames: a batch of frames, every frame in its own box (neighbor_pairs_frames.h).  Device keys only.
+//
+// neighbors::frameTable cuts the frames into segments on the host, once per batch shape, and REMEMBERS what only the offsets tell --
+// frame count, atom count, slots of the max_num_pairs == -1 list -- next to the device tensor it returns (same storage, same version
+// counter, held alive so that the address cannot be handed to another tensor; the 64 most recent tables).  The op finds them there:
+// with a prepared table a call reads nothing back from the device and copies nothing to it, and can be captured in a graph.  A table
+// of any other origin (built by hand, edited, moved to another device) is refused -- the kernels clamp whatever a table holds, but
+// the sizes of the outputs have to come from somewhere.
+//
+// Gradients.  A compacted list of this op is grouped by neighbors[0] with global atom indices: the position gradient is the recorded
+// NeighborPairsBackwardFunction of the single-system op, over the same transposed index, twice differentiable in the same way (no
+// box enters it).  The box gradient [B, 3, 3] comes from the per-frame reduction and carries no graph.
+// ---------------------------------------------------------------------------------------------
+struct FrameTableInfo {
+    Tensor table;
+    uint32_t version = 0;
+    int64_t frames = 0, atoms = 0, pairs = 0;
+};
+std::mutex frame_table_guard;
+std::vector<FrameTableInfo>& frame_tables() {
+    static std::vector<FrameTableInfo>* tables = new std::vector<FrameTableInfo>();      // (never destroyed, as pair_index_cache)
+    return *tables;
+}
+
+Tensor frame_table_entry(const Tensor& offsets, c10::Device device) {
+    TORCH_CHECK(!offsets.is_cuda() && offsets.dim() == 1 && offsets.scalar_type() == torch::kInt64 && offsets.size(0) >= 1,
+                "Expected \"offsets\" to be a one-dimensional int64 host tensor of at least one entry");
+    TORCH_CHECK(device.is_cuda(), "Expected \"device\" to be a GPU (getNeighborPairsFrames has no CPU key)");
+    const Tensor off = offsets.contiguous();
+    const int64_t frames = off.size(0) - 1;
+    TORCH_CHECK(frames <= std::numeric_limits<int32_t>::max(), "Too many frames for getNeighborPairsFrames");
+    const int64_t* o = off.data_ptr<int64_t>();
+    const int64_t segments = nnpops_neighbor_pairs_frames_table((int)frames, o, nullptr);
+    if (segments < 0) raise_last("neighbors::frameTable");
+    Tensor rows = torch::empty({segments, 5}, torch::dtype(torch::kInt32));
+    if (nnpops_neighbor_pairs_frames_table((int)frames, o, rows.data_ptr<int32_t>()) < 0) raise_last("neighbors::frameTable");
+    FrameTableInfo info;
+    info.frames = frames;
+    info.atoms = o[frames];
+    for (int64_t m = 0; m < frames; m++) info.pairs += (o[m + 1] - o[m]) * (o[m + 1] - o[m] - 1) / 2;
+    info.table = rows.to(device);
+    info.version = info.table._version();
+    std::lock_guard<std::mutex> lock(frame_table_guard);
+    auto& tables = frame_tables();
+    if (tables.size() >= 64) tables.erase(tables.begin());
+    tables.push_back(info);
+    return info.table;
+}
+
+FrameTableInfo find_frame_table(const Tensor& table) {
+    std::lock_guard<std::mutex> lock(frame_table_guard);
+    for (const FrameTableInfo& t : frame_tables())
+        if (t.table.data_ptr() == table.data_ptr() && t.table.size(0) == table.size(0) && t.version == table._version() &&
+            t.table.device() == table.device())
+            return t;
+    TORCH_CHECK(false, "Expected \"table\" to be a tensor that frame_table returned, unchanged and on the device it was made for");
+}
+
+class NeighborPairsFramesFunction : public torch::autograd::Function<NeighborPairsFramesFunction> {
+public:
+    static tensor_list forward(AutogradContext* ctx, const Tensor& positions, const torch::Scalar& cutoff, const torch::Scalar& max_num_pairs,
+                               const Tensor& table, const Tensor& box_vectors, bool checkErrors) {
+        TORCH_CHECK(positions.dim() == 2, "Expected \"positions\" to have two dimensions");
+        TORCH_CHECK(positions.size(0) > 0, "Expected the 1nd dimension size of \"positions\" to be more than 0");
+        TORCH_CHECK(positions.size(1) == 3, "Expected the 2nd dimension size of \"positions\" to be 3");
+        TORCH_CHECK(positions.is_contiguous(), "Expected \"positions\" to be contiguous");
+        TORCH_CHECK(positions.scalar_type() == torch::kFloat32 || positions.scalar_type() == torch::kFloat64,
+                    "Expected \"positions\" to be float32 or float64");
+        const int64_t max_pairs = max_num_pairs.toLong();
+        TORCH_CHECK(max_pairs > 0 || max_pairs == -1, "Expected \"max_num_pairs\" to be positive or equal to -1");
+        TORCH_CHECK(cutoff.toDouble() > 0, "Expected \"cutoff\" to be positive");
+        TORCH_CHECK(table.dim() == 2 && table.size(1) == 5, "Expected \"table\" to have shape (num_segments, 5)");
+        TORCH_CHECK(table.scalar_type() == torch::kInt32, "Expected \"table\" to be int32");
+        TORCH_CHECK(table.device() == positions.device() && table.is_contiguous(), "Expected \"table\" to be contiguous and on the device of \"positions\"");
+        const int64_t num_atoms = positions.size(0);
+        TORCH_CHECK(num_atoms <= std::numeric_limits<int32_t>::max(), "Too many atoms for getNeighborPairsFrames");
+        const FrameTableInfo info = find_frame_table(table);
+        TORCH_CHECK(info.atoms == num_atoms, "Expected the last offset of \"table\" (" + std::to_string(info.atoms) +
+                    ") to be the 1st dimension size of \"positions\" (" + std::to_string(num_atoms) + ")");
+        const bool use_periodic = box_vectors.numel() != 0;
+        Tensor boxes;
+        if (use_periodic) {
+            TORCH_CHECK(box_vectors.dim() == 3 && box_vectors.size(1) == 3 && box_vectors.size(2) == 3,
+                        "Expected \"box_vectors\" to have shape (num_frames, 3, 3)");
+            TORCH_CHECK(box_vectors.size(0) == info.frames, "Expected the 1st dimension size of \"box_vectors\" (" +
+                        std::to_string(box_vectors.size(0)) + ") to be the number of frames of \"table\" (" + std::to_string(info.frames) + ")");
+            boxes = box_vectors.to(positions.options()).contiguous();
+        }
+        const int64_t slots = max_pairs == -1 ? info.pairs : max_pairs;
+        TORCH_CHECK(slots <= std::numeric_limits<int32_t>::max(), "Too many pair slots for getNeighborPairsFrames (" + std::to_string(slots) +
+                    "): use a compacted list");
+        const int64_t segments = table.size(0);
+        const auto options = positions.options();
+        Tensor neighbors = torch::empty({2, slots}, options.dtype(torch::kInt32));
+        Tensor deltas = torch::empty({slots, 3}, options);
+        Tensor distances = torch::empty({slots}, options);
+        Tensor num_pairs = torch::empty({1}, options.dtype(torch::kInt32));
+        Tensor segment_slots = torch::empty({segments + 1}, options.dtype(torch::kInt32));
+        Tensor workspace = torch::empty({nnpops_neighbor_pairs_frames_workspace_bytes((int)segments)}, options.dtype(torch::kUInt8));
+        const int dtype = positions.scalar_type() == torch::kFloat64 ? 1 : 0;
+        c10::hip::HIPGuard guard(positions.device().index());
+        void* stream = current_stream(positions.device());
+        if (nnpops_neighbor_pairs_frames_forward(dtype, (int)num_atoms, (int)info.frames, (int)segments, table.data_ptr<int32_t>(),
+                                                 positions.data_ptr(), use_periodic ? boxes.data_ptr() : nullptr, cutoff.toDouble(), max_pairs,
+                                                 slots, neighbors.data_ptr<int32_t>(), deltas.data_ptr(), distances.data_ptr(),
+                                                 num_pairs.data_ptr<int32_t>(), segment_slots.data_ptr<int32_t>(), workspace.data_ptr(),
+                                                 stream) != NNPOPS_OK)
+            raise_last("neighbors::getNeighborPairsFrames");
+        if (checkErrors) {      // synchronises: incompatible with graph capture, as for the single-system op
+            const int found = num_pairs.item<int32_t>();
+            TORCH_CHECK(found <= slots, "Too many neighbor pairs found. Maximum is " + std::to_string(slots),
+                        " but found " + std::to_string(found));
+        }
+        // (the transposed index of a compacted list, as NeighborPairsFunction builds it; PME's cache of the last list is not touched)
+        Tensor index;
+        if (positions.requires_grad() && max_pairs > 0 && num_atoms <= NNPOPS_PAIRS_INDEX_MAX_ATOMS) {
+            index = torch::empty({nnpops_neighbor_pairs_index_ints((int)num_atoms, slots)}, options.dtype(torch::kInt32));
+            Tensor iws = torch::empty({nnpops_neighbor_pairs_index_workspace_bytes((int)num_atoms, slots) / 8 + 1}, options.dtype(torch::kInt64));
+            if (nnpops_neighbor_pairs_build_index((int)num_atoms, slots, neighbors.data_ptr<int32_t>(), index.data_ptr<int32_t>(), iws.data_ptr(),
+                                                  stream) != NNPOPS_OK)
+                raise_last("neighbors::getNeighborPairsFrames (transposed index)");
+        }
+        const bool box_grad = use_periodic && box_vectors.requires_grad();
+        ctx->save_for_backward({neighbors, deltas, distances, index, box_grad ? positions.detach() : Tensor(), box_grad ? boxes.detach() : Tensor(),
+                                box_grad ? table : Tensor(), box_grad ? segment_slots : Tensor()});
+        ctx->saved_data["num_atoms"] = num_atoms;
+        ctx->saved_data["box_dtype"] = (int64_t)box_vectors.scalar_type();
+        return {neighbors, deltas, distances, num_pairs};
+    }
+
+    static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) {
+        const auto saved = ctx->get_saved_variables();
+        const Tensor neighbors = saved[0], deltas = saved[1], distances = saved[2], index = saved[3], positions = saved[4], boxes = saved[5],
+                     table = saved[6], segment_slots = saved[7];
+        const int64_t num_atoms = ctx->saved_data["num_atoms"].toInt();
+        const bool want_positions = ctx->needs_input_grad(0), want_box = ctx->needs_input_grad(2) && boxes.defined();      // (indices count the tensor inputs)
+        TORCH_CHECK(!(want_box && torch::GradMode::is_enabled()),
+                    "neighbors::getNeighborPairsFrames: second derivatives that involve the box are not available for frames "
+                    "(run the backward pass without create_graph, or with box_vectors that do not require a gradient)");
+        const Tensor grad_deltas = grad_outputs[1].defined() ? grad_outputs[1].contiguous() : torch::zeros_like(deltas);
+        const Tensor grad_distances = grad_outputs[2].defined() ? grad_outputs[2].contiguous() : torch::zeros_like(distances);
+        Tensor grad_positions, grad_boxes;
+        if (want_positions)
+            grad_positions = NeighborPairsBackwardFunction::apply(grad_deltas, grad_distances, deltas, distances, neighbors, opt(index), opt(Tensor()),
+                                                                  opt(Tensor()), num_atoms, true, false)[0];
+        if (want_box) {
+            const int64_t frames = boxes.size(0), segments = table.size(0), slots = distances.size(0);
+            const Tensor d = deltas.detach(), r = distances.detach();
+            grad_boxes = torch::empty({frames, 3, 3}, d.options());
+            Tensor workspace = torch::empty({nnpops_neighbor_pairs_frames_box_backward_workspace_bytes((int)segments) / 8}, d.options().dtype(torch::kFloat64));
+            c10::hip::HIPGuard guard(d.device().index());
+            if (nnpops_neighbor_pairs_frames_box_backward(d.scalar_type() == torch::kFloat64 ? 1 : 0, (int)num_atoms, (int)frames, (int)segments,
+                                                          table.data_ptr<int32_t>(), segment_slots.data_ptr<int32_t>(), slots,
+                                                          neighbors.data_ptr<int32_t>(), positions.data_ptr(), boxes.data_ptr(), d.data_ptr(),
+                                                          r.data_ptr(), grad_deltas.data_ptr(), grad_distances.data_ptr(), grad_boxes.data_ptr(),
+                                                          workspace.data_ptr(), current_stream(d.device())) != NNPOPS_OK)
+                raise_last("neighbors::getNeighborPairsFrames backward (box)");
+            grad_boxes = grad_boxes.to((torch::ScalarType)ctx->saved_data["box_dtype"].toInt());
+        }
+        return {grad_positions, Tensor(), Tensor(), Tensor(), grad_boxes, Tensor()};
+    }
+};
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> neighbor_pairs_frames_entry(const Tensor& positions, const torch::Scalar& cutoff,
+                                                                       const torch::Scalar& max_num_pairs, const Tensor& table,
+                                                                       const Tensor& box_vectors, bool checkErrors) {
+    const tensor_list r = NeighborPairsFramesFunction::apply(positions, cutoff, max_num_pairs, table, box_vectors, checkErrors);
+    return std::make_tuple(r[0], r[1], r[2], r[3]);
+}
+TORCH_LIBRARY_FRAGMENT(neighbors, m) {
+    m.def("getNeighborPairsFrames(Tensor positions, Scalar cutoff, Scalar max_num_neighbors, Tensor table, Tensor box_vectors, "
+          "bool checkErrors) -> (Tensor neighbors, Tensor deltas, Tensor distances, Tensor num_pairs)");
+    m.def("frameTable(Tensor offsets, Device device) -> Tensor", frame_table_entry);
+}
+TORCH_LIBRARY_IMPL(neighbors, AutogradCUDA, m) { m.impl("getNeighborPairsFrames", neighbor_pairs_frames_entry); }
+TORCH_LIBRARY_IMPL(neighbors, CUDA, m) { m.impl("getNeighborPairsFrames", neighbor_pairs_frames_entry); }
 
 // ---------------------------------------------------------------------------------------------
 // Host tensors.  The reference registers a CPU kernel of this op next to the device one (reference
