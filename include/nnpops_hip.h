@@ -653,6 +653,51 @@ int nnpops_pme_reciprocal_interpolate_second(int num_atoms, int gridx, int gridy
                                              const float* directional_grid, float* grad_positions, float* grad_charges, void* workspace,
                                              void* second_workspace, void* stream);
 
+/* PME over a batch of frames, every frame in its own box (additive; the reference's ops are single-system): per-frame energies and
+ * dE/dpositions, dE/dcharges of both terms in a handful of launches for the whole minibatch (pme_frames.hip).  Frame m
+ * holds the atoms [offsets[m], offsets[m+1]); it sees them through the minimum image of box_vectors[m] (the single-round rule of the
+ * pair list: every box at least two cutoffs wide) and never sees an atom of another frame.  float32, orders 4 and 5.
+ *   nnpops_pme_frames_table (host only, no GPU): offsets [num_frames + 1] (first 0, ascending, empty frames are fine) -> int32 table of
+ *     nnpops_pme_frames_table_ints(...) entries:
+ *       {B, N, T, 0} | offsets [B + 1] | tile_start [B + 1] | tiles [T][4] = {frame, first atom of the frame, atoms of the frame, first
+ *       owner} | atom_frame [N]
+ *     A tile is NNPOPS_PME_FRAMES_TILE consecutive owner atoms of one frame (the last tile of a frame may hold fewer); a frame's tiles
+ *     are consecutive, [tile_start[m], tile_start[m+1]).  T = num_tiles below.  `table` everywhere else: these entries on the device.
+ *     The kernels clamp what they read from it: no table makes them touch memory outside the arrays' num_atoms / num_frames entries.
+ *   nnpops_pme_direct_frames: the direct term without a pair list, one workgroup per tile, 16 lanes per owner atom walking the frame's
+ *     atoms (staged in LDS up to 1 024 of them).  A pair is kept when !(d^2 > cutoff^2) with the displacement and roundings of
+ *     nnpops_neighbor_pairs_frames_forward, so the included pairs are exactly the ones that list holds; exclusions [num_atoms][max]
+ *     (global indices, rows sorted descending, symmetric, every partner inside the atom's frame) as for nnpops_pme_direct.  Every pair is
+ *     evaluated by both its atoms from the same float values: position_deriv [N][3], charge_deriv [N] and energies [B] are fully
+ *     written, no atomics, bitwise reproducible, and a frame's results do not depend on the batch around it.  The cost is that of an
+ *     all-pairs scan of every frame: meant for frames of at most a few hundred atoms.
+ *     workspace: nnpops_pme_direct_frames_workspace_bytes(T) bytes.
+ *   nnpops_pme_reciprocal_frames_spread -> the caller's rfftn over the last three dimensions of real_grids [B][gx][gy][gz] ->
+ *   nnpops_pme_reciprocal_frames_convolve (recip_grids [B][gx][gy][gz/2+1] complex, scaled in place; energies [B], without the self
+ *   energy) -> the caller's irfftn(norm = "forward") -> nnpops_pme_reciprocal_frames_interpolate: the steps of the single-system entries
+ *   with their float expressions, every atom in its own frame's box and grid.  The spread is a gather with no sort in front of it (one
+ *   workgroup per frame and brick of 4 x 4 x 16 points walks the frame's atoms in ascending order); every point of every grid is
+ *   written exactly once (no clearing), a frame without atoms gets zeros.  The same workspace,
+ *   nnpops_pme_reciprocal_frames_workspace_bytes(...) bytes, for the three steps of one evaluation.
+ * No entry allocates or synchronises: graph-capturable. */
+#define NNPOPS_PME_FRAMES_TILE 16
+int64_t nnpops_pme_frames_table_ints(int num_frames, const int64_t* offsets);
+int nnpops_pme_frames_table(int num_frames, const int64_t* offsets, int32_t* table);
+int64_t nnpops_pme_direct_frames_workspace_bytes(int num_tiles);
+int nnpops_pme_direct_frames(int num_atoms, int num_frames, int num_tiles, int max_exclusions, const int32_t* table, const float* positions,
+                             const float* charges, const int32_t* exclusions, const float* box_vectors, float cutoff, float alpha,
+                             float coulomb, float* energies, float* position_deriv, float* charge_deriv, void* workspace, void* stream);
+int64_t nnpops_pme_reciprocal_frames_workspace_bytes(int num_atoms, int num_frames, int gridx, int gridy, int gridz, int order);
+int nnpops_pme_reciprocal_frames_spread(int num_atoms, int num_frames, int num_tiles, int gridx, int gridy, int gridz, int order,
+                                        const int32_t* table, const float* positions, const float* charges, const float* box_vectors,
+                                        float coulomb, float* real_grids, void* workspace, void* stream);
+int nnpops_pme_reciprocal_frames_convolve(int num_atoms, int num_frames, int gridx, int gridy, int gridz, int order, const float* box_vectors,
+                                          float alpha, const float* xmoduli, const float* ymoduli, const float* zmoduli, void* recip_grids,
+                                          float* energies, void* workspace, void* stream);
+int nnpops_pme_reciprocal_frames_interpolate(int num_atoms, int num_frames, int gridx, int gridy, int gridz, int order, const float* charges,
+                                             const float* box_vectors, float coulomb, const float* real_grids, float* position_deriv,
+                                             float* charge_deriv, void* workspace, void* stream);
+
 /* ---- dense layers of the ANI atomic networks (reference src/pytorch/BatchedNN.cpp:30-50, BatchedNN.py:37-122) ----
  * C[M x N] = A[M x K] B with fp32 in and out; the products run on the half-precision matrix instruction with every
  * operand carried as two fp16 planes (22 significant bits) and fp32 accumulation.  B arrives pre-split:

@@ -147,6 +147,18 @@ SIGNATURES = {
     "nnpops_pme_reciprocal_interpolate_second": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
                                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                            C.c_void_p]),
+    "nnpops_pme_frames_table_ints": (C.c_int64, [C.c_int, C.POINTER(C.c_int64)]),
+    "nnpops_pme_frames_table": (C.c_int, [C.c_int, C.POINTER(C.c_int64), C.c_void_p]),
+    "nnpops_pme_direct_frames_workspace_bytes": (C.c_int64, [C.c_int]),
+    "nnpops_pme_direct_frames": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nnpops_pme_reciprocal_frames_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nnpops_pme_reciprocal_frames_spread": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nnpops_pme_reciprocal_frames_convolve": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nnpops_pme_reciprocal_frames_interpolate": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                           C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_neighbor_pairs_backward": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_neighbor_pairs_backward_workspace_bytes": (C.c_int64, [C.c_int]),
@@ -747,6 +759,70 @@ def pme_reciprocal(positions, charges, box_vectors, gridx, gridy, gridz, order, 
     [N, 3], dE/dcharges [N]).  Orders 4 and 5."""
     return pme_reciprocal_passes(positions, charges, box_vectors, gridx, gridy, gridz, order, alpha, coulomb, xmoduli, ymoduli,
                                  zmoduli)[4:]
+
+
+def pme_frames_table(offsets):
+    """The batch-shape table of the PME frames entries (host only, no GPU): int32 host tensor {B, N, T, 0} | offsets [B + 1] |
+    tile_start [B + 1] | tiles [T][4] = {frame, first atom of the frame, atoms of the frame, first owner} | atom_frame [N]
+    (nnpops_hip.h).  offsets: B + 1 ascending ints, the first 0."""
+    offsets = [int(v) for v in offsets]
+    if not offsets:
+        raise ValueError('Expected "offsets" to hold at least one entry')
+    arr = (C.c_int64 * len(offsets))(*offsets)
+    L = lib()
+    ints = int(L.nnpops_pme_frames_table_ints(len(offsets) - 1, arr))
+    if ints < 0:
+        _check(ints)
+    table = torch.empty((ints,), dtype=torch.int32)
+    _check(L.nnpops_pme_frames_table(len(offsets) - 1, arr, C.c_void_p(table.data_ptr())))
+    return table
+
+
+def pme_direct_frames(positions, charges, exclusions, box_vectors, table, cutoff, alpha, coulomb):
+    """Direct-space PME of a batch of frames through the C ABI -> (energies [B], dE/dpositions [N, 3], dE/dcharges [N]), float32.
+    table: pme_frames_table(offsets) on the device; exclusions int32 [N, max_excl], rows sorted descending."""
+    n, frames, max_excl = positions.size(0), box_vectors.size(0), exclusions.size(1)
+    tiles = (table.numel() - 4 - 2 * (frames + 1) - n) // 4
+    dev = positions.device
+    energies = torch.empty((frames,), dtype=torch.float32, device=dev)
+    pos_deriv = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    charge_deriv = torch.empty((n,), dtype=torch.float32, device=dev)
+    L = lib()
+    ws = torch.empty((int(L.nnpops_pme_direct_frames_workspace_bytes(tiles)),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(L.nnpops_pme_direct_frames(n, frames, tiles, max_excl, _ptr(table), _ptr(positions.contiguous()), _ptr(charges.contiguous()),
+                                          _ptr(exclusions.contiguous()) if max_excl else None, _ptr(box_vectors.contiguous()), float(cutoff),
+                                          float(alpha), float(coulomb), _ptr(energies), _ptr(pos_deriv), _ptr(charge_deriv), _ptr(ws),
+                                          _stream_ptr(dev)))
+    return energies, pos_deriv, charge_deriv
+
+
+def pme_reciprocal_frames(positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha, coulomb, xmoduli, ymoduli, zmoduli):
+    """Reciprocal-space PME of a batch of frames through the C ABI: spread -> torch.fft.rfftn over the last three dimensions -> convolve
+    -> torch.fft.irfftn(norm="forward") -> interpolate.  -> (energies [B] without the self energy, dE/dpositions [N, 3], dE/dcharges
+    [N]).  Orders 4 and 5."""
+    n, frames = positions.size(0), box_vectors.size(0)
+    tiles = (table.numel() - 4 - 2 * (frames + 1) - n) // 4
+    dev = positions.device
+    positions, charges, box_vectors = positions.contiguous(), charges.contiguous(), box_vectors.contiguous()
+    mods = [m.contiguous() for m in (xmoduli, ymoduli, zmoduli)]
+    L = lib()
+    dims = (gridx, gridy, gridz, order)
+    ws = torch.empty((int(L.nnpops_pme_reciprocal_frames_workspace_bytes(n, frames, *dims)),), dtype=torch.uint8, device=dev)
+    real = torch.empty((frames, gridx, gridy, gridz), dtype=torch.float32, device=dev)
+    energies = torch.empty((frames,), dtype=torch.float32, device=dev)
+    pos_deriv = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    charge_deriv = torch.empty((n,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _check(L.nnpops_pme_reciprocal_frames_spread(n, frames, tiles, *dims, _ptr(table), _ptr(positions), _ptr(charges), _ptr(box_vectors),
+                                                     float(coulomb), _ptr(real), _ptr(ws), _stream_ptr(dev)))
+        recip = torch.fft.rfftn(real, dim=(1, 2, 3)).contiguous()
+        _check(L.nnpops_pme_reciprocal_frames_convolve(n, frames, *dims, _ptr(box_vectors), float(alpha), _ptr(mods[0]), _ptr(mods[1]),
+                                                       _ptr(mods[2]), _ptr(recip), _ptr(energies), _ptr(ws), _stream_ptr(dev)))
+        grid = torch.fft.irfftn(recip, s=(gridx, gridy, gridz), dim=(1, 2, 3), norm="forward").contiguous()
+        _check(L.nnpops_pme_reciprocal_frames_interpolate(n, frames, *dims, _ptr(charges), _ptr(box_vectors), float(coulomb), _ptr(grid),
+                                                          _ptr(pos_deriv), _ptr(charge_deriv), _ptr(ws), _stream_ptr(dev)))
+    return energies, pos_deriv, charge_deriv
 
 
 def pme_direct_box(positions, charges, neighbors, deltas, distances, exclusions, box_vectors, alpha, coulomb):

@@ -23,32 +23,16 @@
 #include <limits>
 
 #include "celllist_host.h"
+#include "pair_delta.h"
 
 using namespace nnpops;
 
 namespace {
 
-template <typename T> struct Vec3 { T x, y, z; };
-
 // rows are scanned in blocks of kScanBlock (scan_rows below): offset of a row = offset inside its block + block prefix
 constexpr int kScanBlock = 1024;
 __device__ __forceinline__ long long first_slot(const int* __restrict__ row_offset, const int* __restrict__ block_prefix, int row) {
     return (long long)row_offset[row] + block_prefix[row >> 10];
-}
-
-template <typename T>
-__device__ __forceinline__ Vec3<T> wrapped_delta(const T* __restrict__ pos, int row, int col, const T* __restrict__ box,
-                                                 bool periodic) {
-    Vec3<T> d{pos[3 * row] - pos[3 * col], pos[3 * row + 1] - pos[3 * col + 1], pos[3 * row + 2] - pos[3 * col + 2]};
-    if (periodic) {
-        const T s3 = round(d.z / box[8]);
-        d.x -= s3 * box[6]; d.y -= s3 * box[7]; d.z -= s3 * box[8];
-        const T s2 = round(d.y / box[4]);
-        d.x -= s2 * box[3]; d.y -= s2 * box[4];
-        const T s1 = round(d.x / box[0]);
-        d.x -= s1 * box[0];
-    }
-    return d;
 }
 
 template <typename T>

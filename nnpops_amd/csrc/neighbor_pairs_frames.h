@@ -55,19 +55,6 @@ __device__ __forceinline__ int tri_row(int p) {
     return r;
 }
 
-// |d|^2 with the roundings of pairs_allpairs.  Its float32 sum is compiled as two rounded products and one fused step,
-// (fma(y, y, x * x)) + z * z; without packed arithmetic the same source line would fuse twice, so the steps are spelled out here.
-// float64 has one compiled form, the source line's.
-template <typename T>
-__device__ __forceinline__ T allpairs_norm2(const Vec3<T>& d) { return d.x * d.x + d.y * d.y + d.z * d.z; }
-template <>
-__device__ __forceinline__ float allpairs_norm2<float>(const Vec3<float>& d) {
-#pragma clang fp contract(off)
-    const float xx = d.x * d.x, zz = d.z * d.z;
-    const float xy = __builtin_fmaf(d.y, d.y, xx);
-    return xy + zz;
-}
-
 template <typename T, int PASS, bool ALL_SLOTS>
 NNPOPS_FRAMES_KERNEL __launch_bounds__(256) void pairs_frames(int N, int B, int S, const int32_t* __restrict__ table, const T* __restrict__ pos,
                                                     const T* __restrict__ boxes, T cutoff2, long long num_slots,

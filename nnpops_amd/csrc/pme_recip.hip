@@ -33,6 +33,7 @@
 
 #include "device_common.h"
 #include "host_common.h"
+#include "pme_recip_common.h"
 
 using namespace nnpops;
 
@@ -43,22 +44,6 @@ constexpr int kBX = 4, kBY = 4, kBZ = 16;              // brick of grid points =
 constexpr int kMaxBinsPerAxis = 4;                     // bricks a cyclic window of (brick + order - 1) cells can touch
 constexpr int kConvBlocksMax = 1024;
 static_assert(kBX * kBY * kBZ == kBlock, "one lane per grid point of a brick");
-
-struct RecipBox { float r00, r10, r11, r20, r21, r22; };
-
-// the reciprocal box of a reduced triclinic box (lower triangular), the same float expressions as the reference's invertBoxVectors
-__device__ __forceinline__ RecipBox recip_box(const float* __restrict__ b) {
-    const float det = b[0] * b[4] * b[8];
-    const float s = 1.0f / det;
-    RecipBox r;
-    r.r00 = b[4] * b[8] * s;
-    r.r10 = -b[3] * b[8] * s;
-    r.r11 = b[0] * b[8] * s;
-    r.r20 = (b[3] * b[7] - b[4] * b[6]) * s;
-    r.r21 = -b[0] * b[7] * s;
-    r.r22 = b[0] * b[4] * s;
-    return r;
-}
 
 struct Dims {
     int kx, ky, kz;          // grid
@@ -261,17 +246,6 @@ __device__ int window_bins(int b, int B, int K, int nb, int order, int* out) {
         if (!seen && n < kMaxBinsPerAxis) out[n++] = bin;       // (never more than kMaxBinsPerAxis: see kMaxBinsPerAxis)
     }
     return n;
-}
-
-// weight of the atom with base `g0` at point `g` along one axis: every stencil slot i with (g0 + i) mod K == g (a grid smaller
-// than the order folds the stencil onto itself)
-template <int ORDER>
-__device__ __forceinline__ float axis_weight(int g, int g0, int K, const float* th) {
-    int dd = g - g0;
-    dd += dd < 0 ? K : 0;
-    float w = 0.f;
-    for (int i = dd; i < ORDER; i += K) w += th[i];
-    return w;
 }
 
 // ---- pass 5: the spread as a gather, one workgroup per brick of grid points ----

@@ -3375,6 +3375,186 @@ TORCH_LIBRARY_IMPL(pme, CPU, m) {
     m.impl("pme_reciprocal_twice", pme_reciprocal_twice_entry);
 }
 
+// ---------------------------------------------------------------------------------------------
+// PME over a batch of frames, every frame in its own box (pme_frames.hip; additive, device keys only): per-frame energies [B].
+// pme::pmeFramesTable lays the batch shape out on the host, once per `offsets`; the ops take B from box_vectors, N from positions and
+// the tile count from the table's length, so a call reads nothing back from the device and can be captured in a graph (the kernels
+// clamp whatever a table holds).  The derivatives are computed with the forward pass; the backward scales every frame's rows by that
+// frame's upstream gradient.  First order in positions and charges only: no box gradient, no create_graph.
+// ---------------------------------------------------------------------------------------------
+Tensor pme_frames_table_entry(const Tensor& offsets, c10::Device device) {
+    TORCH_CHECK(!offsets.is_cuda() && offsets.dim() == 1 && offsets.scalar_type() == torch::kInt64 && offsets.size(0) >= 1,
+                "Expected \"offsets\" to be a one-dimensional int64 host tensor of at least one entry");
+    const Tensor off = offsets.contiguous();
+    const int64_t frames = off.size(0) - 1;
+    TORCH_CHECK(frames <= std::numeric_limits<int32_t>::max() / 8, "Too many frames for pme::pmeFramesTable");
+    const int64_t ints = nnpops_pme_frames_table_ints((int)frames, off.data_ptr<int64_t>());
+    if (ints < 0) raise_last("pme::pmeFramesTable");
+    Tensor table = torch::empty({ints}, torch::dtype(torch::kInt32));
+    if (nnpops_pme_frames_table((int)frames, off.data_ptr<int64_t>(), table.data_ptr<int32_t>()) != NNPOPS_OK) raise_last("pme::pmeFramesTable");
+    return table.to(device);
+}
+
+struct PmeFramesShape { int64_t frames, atoms, tiles; };
+
+// what both ops check of their common arguments; the tile count follows from the table's length
+PmeFramesShape pme_frames_check(const char* op, const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table) {
+    TORCH_CHECK(positions.is_cuda(), op, ": device tensors only (the frames ops have no CPU key)");
+    TORCH_CHECK(positions.dim() == 2 && positions.size(1) == 3, op, ": positions must have shape (atoms, 3)");
+    TORCH_CHECK(charges.dim() == 1 && charges.size(0) == positions.size(0), op, ": charges must be 1D, one per atom");
+    TORCH_CHECK(box_vectors.dim() == 3 && box_vectors.size(0) >= 1 && box_vectors.size(1) == 3 && box_vectors.size(2) == 3, op,
+                ": box_vectors must have shape (frames, 3, 3) with at least one frame");
+    TORCH_CHECK(positions.scalar_type() == torch::kFloat32 && charges.scalar_type() == torch::kFloat32 &&
+                box_vectors.scalar_type() == torch::kFloat32, op, " computes in float32");
+    TORCH_CHECK(!(box_vectors.requires_grad() && torch::GradMode::is_enabled()), op,
+                ": box gradients over frames are not available (pass box_vectors that do not require a gradient)");
+    TORCH_CHECK(table.dim() == 1 && table.scalar_type() == torch::kInt32 && table.is_contiguous(), op,
+                ": table must be the int32 tensor pmeFramesTable returned");
+    for (const Tensor* t : {&charges, &box_vectors, &table})
+        TORCH_CHECK(t->device() == positions.device(), op, ": every tensor must be on the device of positions (", positions.device(), "), got ",
+                    t->device());
+    PmeFramesShape s{box_vectors.size(0), positions.size(0), 0};
+    TORCH_CHECK(s.atoms <= std::numeric_limits<int32_t>::max() / 8 && s.frames <= std::numeric_limits<int32_t>::max() / 8, op, ": batch too large");
+    const int64_t rest = table.numel() - 4 - 2 * (s.frames + 1) - s.atoms;
+    TORCH_CHECK(rest >= 0 && rest % 4 == 0 && rest / 4 >= (s.atoms + NNPOPS_PME_FRAMES_TILE - 1) / NNPOPS_PME_FRAMES_TILE &&
+                rest / 4 <= s.atoms, op, ": table does not describe ", s.frames, " frames of ", s.atoms,
+                " atoms in all (offsets must end at the number of atoms, box_vectors must hold one box per frame)");
+    s.tiles = rest / 4;
+    return s;
+}
+
+// every frame's rows of the kept derivatives times that frame's upstream gradient
+tensor_list pme_frames_scale(const char* op, const Tensor& pos_deriv, const Tensor& charge_deriv, const Tensor& table, const Tensor& grad) {
+    TORCH_CHECK(!torch::GradMode::is_enabled(), op, ": second derivatives are not implemented (backward was called with create_graph=True)");
+    const int64_t n = charge_deriv.size(0), frames = grad.numel();
+    const int64_t tiles = (table.numel() - 4 - 2 * (frames + 1) - n) / 4;
+    const Tensor g = grad.contiguous();
+    TORCH_CHECK(g.device() == pos_deriv.device() && (g.scalar_type() == torch::kFloat32 || g.scalar_type() == torch::kFloat64), op,
+                ": unexpected gradient of the energies");
+    Tensor out = torch::empty_like(pos_deriv);
+    if (n == 0) return {out, torch::empty_like(charge_deriv)};
+    c10::hip::HIPGuard guard(pos_deriv.device().index());
+    if (nnpops_scale_by_segment(current_stream(pos_deriv.device()), pos_deriv.data_ptr<float>(), (int)n, table.data_ptr<int32_t>() + 4, (int)frames,
+                                g.data_ptr(), g.scalar_type() == torch::kFloat64 ? 1 : 0, out.data_ptr<float>()) != NNPOPS_OK)
+        raise_last(op);
+    const Tensor atom_frame = table.narrow(0, 4 + 2 * (frames + 1) + 4 * tiles, n);
+    return {out, charge_deriv * g.to(torch::kFloat32).index_select(0, atom_frame)};
+}
+
+class PmeDirectFramesFunction : public torch::autograd::Function<PmeDirectFramesFunction> {
+public:
+    static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& exclusions,
+                          const Tensor& box_vectors, const Tensor& table, const torch::Scalar& cutoff, const torch::Scalar& alpha,
+                          const torch::Scalar& coulomb) {
+        const PmeFramesShape s = pme_frames_check("pme_direct_frames", positions, charges, box_vectors, table);
+        TORCH_CHECK(exclusions.dim() == 2 && exclusions.size(0) == s.atoms && exclusions.device() == positions.device() &&
+                    at::isIntegralType(exclusions.scalar_type(), false), "pme_direct_frames: exclusions must be integers of shape (atoms, max_exclusions) on the device of positions");
+        const Tensor pos = positions.contiguous(), q = charges.contiguous(), ex = exclusions.to(torch::kInt32).contiguous(),
+                     boxes = box_vectors.contiguous();
+        const auto opts = positions.options();
+        Tensor energies = torch::empty({s.frames}, opts), pos_deriv = torch::empty({s.atoms, 3}, opts), charge_deriv = torch::empty({s.atoms}, opts);
+        Tensor workspace = torch::empty({nnpops_pme_direct_frames_workspace_bytes((int)s.tiles)}, opts.dtype(torch::kUInt8));
+        const int64_t max_excl = ex.size(1);
+        c10::hip::HIPGuard guard(positions.device().index());
+        if (nnpops_pme_direct_frames((int)s.atoms, (int)s.frames, (int)s.tiles, (int)max_excl, table.data_ptr<int32_t>(), pos.data_ptr<float>(),
+                                     q.data_ptr<float>(), max_excl ? ex.data_ptr<int32_t>() : nullptr, boxes.data_ptr<float>(),
+                                     (float)cutoff.toDouble(), (float)alpha.toDouble(), (float)coulomb.toDouble(), energies.data_ptr<float>(),
+                                     pos_deriv.data_ptr<float>(), charge_deriv.data_ptr<float>(), workspace.data_ptr(),
+                                     current_stream(positions.device())) != NNPOPS_OK)
+            raise_last("pme::pme_direct_frames");
+        ctx->save_for_backward({pos_deriv, charge_deriv, table});
+        return energies;
+    }
+    static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) {
+        const auto saved = ctx->get_saved_variables();
+        const tensor_list g = pme_frames_scale("pme_direct_frames", saved[0], saved[1], saved[2], grad_outputs[0]);
+        return {g[0], g[1], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+    }
+};
+
+class PmeReciprocalFramesFunction : public torch::autograd::Function<PmeReciprocalFramesFunction> {
+public:
+    static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table,
+                          const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz, const torch::Scalar& order,
+                          const torch::Scalar& alpha, const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli,
+                          const Tensor& zmoduli) {
+        const PmeFramesShape s = pme_frames_check("pme_reciprocal_frames", positions, charges, box_vectors, table);
+        const std::vector<int64_t> K{gridx.toLong(), gridy.toLong(), gridz.toLong()};
+        const int64_t o = order.toLong();
+        TORCH_CHECK(K[0] >= 1 && K[1] >= 1 && K[2] >= 1, "pme_reciprocal_frames: the grid dimensions must be positive");
+        TORCH_CHECK(o == 4 || o == 5, "pme_reciprocal_frames: Only pmeOrder 4 or 5 is supported (got ", o, ")");
+        const double a = alpha.toDouble(), k = coulomb.toDouble();
+        TORCH_CHECK(a > 0 && k > 0, "pme_reciprocal_frames: alpha and coulomb must be positive");
+        const Tensor* moduli[3] = {&xmoduli, &ymoduli, &zmoduli};
+        for (int i = 0; i < 3; i++)
+            TORCH_CHECK(moduli[i]->dim() == 1 && moduli[i]->size(0) == K[i] && moduli[i]->scalar_type() == torch::kFloat32 &&
+                        moduli[i]->device() == positions.device(), "pme_reciprocal_frames: the moduli must be float32 tensors of the grid's sizes on the device of positions");
+        const Tensor pos = positions.contiguous(), q = charges.contiguous(), boxes = box_vectors.contiguous(), xm = xmoduli.contiguous(),
+                     ym = ymoduli.contiguous(), zm = zmoduli.contiguous();
+        const auto opts = positions.options();
+        const int n = (int)s.atoms, B = (int)s.frames, gx = (int)K[0], gy = (int)K[1], gz = (int)K[2];
+        c10::hip::HIPGuard guard(positions.device().index());
+        void* stream = current_stream(positions.device());
+        const int64_t bytes = nnpops_pme_reciprocal_frames_workspace_bytes(n, B, gx, gy, gz, (int)o);
+        if (bytes <= 0) raise_last("pme::pme_reciprocal_frames");
+        Tensor workspace = torch::empty({bytes}, opts.dtype(torch::kUInt8));
+        Tensor real = torch::empty({s.frames, K[0], K[1], K[2]}, opts);
+        if (nnpops_pme_reciprocal_frames_spread(n, B, (int)s.tiles, gx, gy, gz, (int)o, table.data_ptr<int32_t>(), pos.data_ptr<float>(),
+                                                q.data_ptr<float>(), boxes.data_ptr<float>(), (float)k, real.data_ptr<float>(),
+                                                workspace.data_ptr(), stream) != NNPOPS_OK)
+            raise_last("pme::pme_reciprocal_frames");
+        const std::vector<int64_t> dims{1, 2, 3};
+        Tensor recip = torch::fft::rfftn(real, c10::nullopt, torch::IntArrayRef(dims)).contiguous();
+        Tensor energies = torch::empty({s.frames}, opts);
+        if (nnpops_pme_reciprocal_frames_convolve(n, B, gx, gy, gz, (int)o, boxes.data_ptr<float>(), (float)a, xm.data_ptr<float>(),
+                                                  ym.data_ptr<float>(), zm.data_ptr<float>(), recip.data_ptr(), energies.data_ptr<float>(),
+                                                  workspace.data_ptr(), stream) != NNPOPS_OK)
+            raise_last("pme::pme_reciprocal_frames");
+        if (positions.requires_grad() || charges.requires_grad()) {
+            const Tensor grid = torch::fft::irfftn(recip, torch::IntArrayRef(K), torch::IntArrayRef(dims), "forward").contiguous();
+            Tensor pos_deriv = torch::empty({s.atoms, 3}, opts), charge_deriv = torch::empty({s.atoms}, opts);
+            if (nnpops_pme_reciprocal_frames_interpolate(n, B, gx, gy, gz, (int)o, q.data_ptr<float>(), boxes.data_ptr<float>(), (float)k,
+                                                         grid.data_ptr<float>(), pos_deriv.data_ptr<float>(), charge_deriv.data_ptr<float>(),
+                                                         workspace.data_ptr(), stream) != NNPOPS_OK)
+                raise_last("pme::pme_reciprocal_frames");
+            ctx->save_for_backward({pos_deriv, charge_deriv, table});
+        }
+        return energies;
+    }
+    static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) {
+        const auto saved = ctx->get_saved_variables();
+        const tensor_list g = pme_frames_scale("pme_reciprocal_frames", saved[0], saved[1], saved[2], grad_outputs[0]);
+        return {g[0], g[1], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+    }
+};
+
+Tensor pme_direct_frames_entry(const Tensor& positions, const Tensor& charges, const Tensor& exclusions, const Tensor& box_vectors,
+                               const Tensor& table, const torch::Scalar& cutoff, const torch::Scalar& alpha, const torch::Scalar& coulomb) {
+    return PmeDirectFramesFunction::apply(positions, charges, exclusions, box_vectors, table, cutoff, alpha, coulomb);
+}
+Tensor pme_reciprocal_frames_entry(const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table,
+                                   const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz, const torch::Scalar& order,
+                                   const torch::Scalar& alpha, const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli,
+                                   const Tensor& zmoduli) {
+    return PmeReciprocalFramesFunction::apply(positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha, coulomb, xmoduli,
+                                              ymoduli, zmoduli);
+}
+TORCH_LIBRARY_FRAGMENT(pme, m) {
+    m.def("pmeFramesTable(Tensor offsets, Device device) -> Tensor", pme_frames_table_entry);
+    m.def("pme_direct_frames(Tensor positions, Tensor charges, Tensor exclusions, Tensor box_vectors, Tensor table, Scalar cutoff, "
+          "Scalar alpha, Scalar coulomb) -> Tensor");
+    m.def("pme_reciprocal_frames(Tensor positions, Tensor charges, Tensor box_vectors, Tensor table, Scalar gridx, Scalar gridy, "
+          "Scalar gridz, Scalar order, Scalar alpha, Scalar coulomb, Tensor xmoduli, Tensor ymoduli, Tensor zmoduli) -> Tensor");
+}
+TORCH_LIBRARY_IMPL(pme, AutogradCUDA, m) {
+    m.impl("pme_direct_frames", pme_direct_frames_entry);
+    m.impl("pme_reciprocal_frames", pme_reciprocal_frames_entry);
+}
+TORCH_LIBRARY_IMPL(pme, CUDA, m) {
+    m.impl("pme_direct_frames", pme_direct_frames_entry);
+    m.impl("pme_reciprocal_frames", pme_reciprocal_frames_entry);
+}
+
 // =============================================================================================
 // BatchedLinear (reference src/pytorch/BatchedNN.cpp:30-50): y = W v + b broadcast over
 // [molecules, atoms, models]; the backward skips the parameter gradients.

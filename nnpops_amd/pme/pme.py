@@ -15,6 +15,10 @@ The class reaches it through a keyword-only opt-in, ``PME(..., reciprocal=True)`
 moduli and ``compute_reciprocal`` returns the self energy plus the op, as the reference does.  With the default
 ``reciprocal=False`` the class behaves exactly as before and ``compute_reciprocal`` raises; making ``True`` the default is left
 to a later change.
+
+Batches of frames, every frame in its own box: ``compute_direct_frames`` / ``compute_reciprocal_frames`` return per-frame energies [B]
+from ``torch.ops.pme.pme_direct_frames`` / ``pme_reciprocal_frames`` (nnpops_amd/csrc/pme_frames.hip): device tensors
+only, first derivatives with respect to positions and charges, no box gradient.
 """
 import math
 
@@ -105,6 +109,8 @@ class PME:
         self.twice_differentiable = bool(twice_differentiable)
         if self.reciprocal:
             self.moduli = [bspline_moduli(k, order) for k in (gridx, gridy, gridz)]
+        self._frames_checked = None               # the offsets whose frames the exclusions were last checked against
+        self._frames = None                       # (offsets, device, table, device offsets) of the last compute_*_frames call
 
     def compute_direct(self, positions: torch.Tensor, charges: torch.Tensor, cutoff: float, box_vectors: torch.Tensor,
                        max_num_pairs: int = -1):
@@ -159,3 +165,65 @@ class PME:
         return self_energy + torch.ops.pme.pme_reciprocal(positions, charges, box_vectors, self.gridx, self.gridy, self.gridz,
                                                           self.order, self.alpha, self.coulomb, self.moduli[0], self.moduli[1],
                                                           self.moduli[2])
+
+    def _frames_table(self, what, positions, charges, box_vectors, offsets):
+        """The checks both frames methods share, and the device table of ``offsets`` (made once per distinct offsets and device)."""
+        if self.twice_differentiable:
+            raise RuntimeError(f"{what}: second derivatives over frames are not available; use a PME object without "
+                               "twice_differentiable=True")
+        if positions.dim() != 2 or positions.shape[1] != 3:
+            raise ValueError('positions must have shape (atoms, 3)')
+        if charges.dim() != 1:
+            raise ValueError('charges must be 1D')
+        n = positions.shape[0]
+        if n != self.exclusions.shape[0] or charges.shape[0] != n:
+            raise ValueError('positions, charges, and exclusions must all have the same length')
+        offsets = tuple(int(v) for v in offsets)
+        if len(offsets) < 2 or offsets[0] != 0 or offsets[-1] != n or any(b < a for a, b in zip(offsets, offsets[1:])):
+            raise ValueError(f'offsets must be ascending, start at 0, end at the number of atoms ({n}) and describe at least one frame')
+        if box_vectors.dim() != 3 or tuple(box_vectors.shape) != (len(offsets) - 1, 3, 3):
+            raise ValueError(f'box_vectors must have shape ({len(offsets) - 1}, 3, 3), one box per frame')
+        if self._frames_checked != offsets:
+            # every exclusion partner must lie in its atom's frame: the kernels never look outside it.  Checked once per offsets.
+            ex = self.exclusions.to(torch.int64).cpu()
+            bounds = torch.tensor(offsets, dtype=torch.int64)
+            frame_of = torch.bucketize(torch.arange(n), bounds[1:], right=True)
+            lo, hi = bounds[frame_of].unsqueeze(1), bounds[frame_of + 1].unsqueeze(1)
+            if ex.numel() and bool(((ex >= 0) & ((ex < lo) | (ex >= hi))).any()):
+                raise ValueError('exclusions must stay inside a frame: an atom and its exclusion partner lie in different frames of offsets')
+            self._frames_checked = offsets
+        if not (positions.is_cuda and charges.is_cuda and box_vectors.is_cuda):
+            raise ValueError(f'{what}: positions, charges and box_vectors must be on the GPU (the frames methods have no CPU path)')
+        if box_vectors.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError(f'{what}: box gradients over frames are not available; pass box_vectors that do not require a gradient')
+        if self._frames is None or self._frames[0] != offsets or self._frames[1] != positions.device:
+            table = torch.ops.pme.pmeFramesTable(torch.tensor(offsets, dtype=torch.int64), positions.device)
+            self._frames = (offsets, positions.device, table, table[4:4 + len(offsets)].to(torch.int64))
+        return self._frames[2]
+
+    def compute_direct_frames(self, positions: torch.Tensor, charges: torch.Tensor, cutoff: float, box_vectors: torch.Tensor, offsets):
+        """Direct-space energies [B] of a batch of frames: atoms [offsets[m], offsets[m+1]) are frame m, seen through the minimum image
+        of box_vectors[m] (every box at least two cutoffs wide) and never paired with another frame's atoms.  Differentiable with
+        respect to positions and charges (first order).  Every frame is scanned all-pairs: for frames of up to a few hundred atoms."""
+        table = self._frames_table('compute_direct_frames', positions, charges, box_vectors, offsets)
+        if cutoff <= 0:
+            raise ValueError('cutoff must be positive')
+        self.exclusions = self.exclusions.to(positions.device)
+        return torch.ops.pme.pme_direct_frames(positions, charges, self.exclusions, box_vectors, table, cutoff, self.alpha, self.coulomb)
+
+    def compute_reciprocal_frames(self, positions: torch.Tensor, charges: torch.Tensor, box_vectors: torch.Tensor, offsets):
+        """Reciprocal-space energies [B] of a batch of frames, each frame's self energy included; needs ``PME(..., reciprocal=True)``
+        and order 4 or 5.  The grid, order, alpha and coulomb are the object's, the same for all frames.  Differentiable with respect
+        to positions and charges (first order)."""
+        if not self.reciprocal:
+            raise RuntimeError("the reciprocal-space term of PME is not enabled on this object: construct it with PME(..., reciprocal=True)")
+        if self.order not in (4, 5):
+            raise ValueError(f'compute_reciprocal_frames: only order 4 or 5 is supported (got {self.order})')
+        table = self._frames_table('compute_reciprocal_frames', positions, charges, box_vectors, offsets)
+        for i in range(3):
+            self.moduli[i] = self.moduli[i].to(positions.device)
+        # (one lane per frame adds its atoms in order: deterministic, and a frame's sum does not depend on the batch around it)
+        self_energy = torch.segment_reduce(charges ** 2, 'sum', offsets=self._frames[3], unsafe=True) * (-self.coulomb * self.alpha / math.sqrt(math.pi))
+        return self_energy + torch.ops.pme.pme_reciprocal_frames(positions, charges, box_vectors, table, self.gridx, self.gridy, self.gridz,
+                                                                 self.order, self.alpha, self.coulomb, self.moduli[0], self.moduli[1],
+                                                                 self.moduli[2])

@@ -1,0 +1,94 @@
+"""PME over frames against the loop of single-frame calls it replaces: direct and reciprocal term, forward + backward (positions and
+charges), of B frames of a 192-atom water box, every frame in its own box (an NPT trajectory).  Both sides run in this process,
+interleaved round by round; stream time, medians.  The repository's benchmarks hold no PME configuration for such a box: cutoff 5 A,
+alpha 0.6 / A, a 24^3 grid, order 5.
+
+    python tools/pme_frames_time.py [--frames 8 64 256] [--rounds 7] [--batched-only]      (--batched-only: for a kernel profile)"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import NNPOps  # noqa: E402,F401
+from NNPOps.pme import PME  # noqa: E402
+from nnpops_amd import workloads  # noqa: E402
+
+dev = torch.device("cuda:0")
+CUTOFF, ALPHA, COULOMB, GRID, ORDER, N = 5.0, 0.6, 332.0637, 24, 5, 192
+
+
+def timed(fn, reps, warm=3):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return 1e3 * e0.elapsed_time(e1) / reps
+
+
+def water_frames(B, seed=0):
+    """B frames of a 64-water box as an NPT run leaves them -> positions [B * 192, 3], charges, boxes [B, 3, 3], exclusions (a water's
+    atoms exclude each other)"""
+    pos, species, box = workloads.water_box(64, seed=seed + 11)
+    rng = np.random.default_rng(seed + 1)
+    scale = rng.uniform(0.97, 1.04, B)
+    ps = [((pos + rng.normal(0, 0.05, pos.shape)) * s).astype(np.float32) for s in scale]
+    q1 = np.where(np.asarray(species) == np.max(species), -0.834, 0.417).astype(np.float32)
+    atoms = np.arange(B * N)
+    mol = atoms - atoms % 3
+    excl = np.stack([mol + (atoms % 3 + 1) % 3, mol + (atoms % 3 + 2) % 3], 1).astype(np.int32)
+    return np.concatenate(ps), np.tile(q1, B), np.stack([(box * np.float32(s)).astype(np.float32) for s in scale]), excl
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, nargs="+", default=[8, 64, 256])
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--batched-only", action="store_true")
+    args = ap.parse_args()
+    print(f"PME over frames: {N}-atom water boxes, cutoff {CUTOFF}, alpha {ALPHA}, grid {GRID}^3, order {ORDER}; forward + backward, stream time, "
+          f"medians of {args.rounds} interleaved rounds (spread = max - min)")
+    print(f"  {'B':>4s} {'term':>11s} {'batched us':>11s} {'(spread)':>9s} {'loop us':>10s} {'(spread)':>9s} {'loop / batched':>15s}")
+    for B in args.frames:
+        host_pos, host_q, host_boxes, excl = water_frames(B)
+        offsets = [m * N for m in range(B + 1)]
+        pos, q = torch.tensor(host_pos, device=dev).requires_grad_(), torch.tensor(host_q, device=dev).requires_grad_()
+        boxes = torch.tensor(host_boxes, device=dev)
+        pme = PME(GRID, GRID, GRID, ORDER, ALPHA, COULOMB, torch.tensor(excl), reciprocal=True)
+        one = PME(GRID, GRID, GRID, ORDER, ALPHA, COULOMB, torch.tensor(excl[:N]), reciprocal=True)
+        parts = [(pos.detach()[m * N:(m + 1) * N].clone().requires_grad_(), q.detach()[m * N:(m + 1) * N].clone().requires_grad_(), boxes[m].clone())
+                 for m in range(B)]
+        terms = {
+            "direct": (lambda: pme.compute_direct_frames(pos, q, CUTOFF, boxes, offsets), lambda p, c, b: one.compute_direct(p, c, CUTOFF, b)),
+            "reciprocal": (lambda: pme.compute_reciprocal_frames(pos, q, boxes, offsets), lambda p, c, b: one.compute_reciprocal(p, c, b)),
+        }
+        for name, (frames_energy, single_energy) in terms.items():
+            def batched():
+                return torch.autograd.grad(frames_energy().sum(), (pos, q))
+
+            def loop():
+                return [torch.autograd.grad(single_energy(p, c, b), (p, c)) for p, c, b in parts]
+
+            gb, gl = batched(), loop()                      # the two sides must agree before they are timed
+            for k in range(2):
+                joined = torch.cat([g[k] for g in gl])
+                assert float((joined - gb[k]).abs().max()) <= 1e-4 * float(gb[k].abs().max()), name
+            reps_b, reps_l = max(20, min(200, 4096 // B)), max(3, min(30, 512 // B))
+            if args.batched_only:
+                timed(batched, reps_b)
+                continue
+            rounds = [(timed(batched, reps_b), timed(loop, reps_l)) for _ in range(args.rounds)]
+            tb, tl = np.array(rounds).T
+            mb, ml = float(np.median(tb)), float(np.median(tl))
+            print(f"  {B:4d} {name:>11s} {mb:11.1f} {tb.max() - tb.min():9.1f} {ml:10.1f} {tl.max() - tl.min():9.1f} {ml / mb:15.1f}", flush=True)
+
+
+if __name__ == "__main__":
+    main()
