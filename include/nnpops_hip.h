@@ -697,6 +697,28 @@ int nnpops_pme_reciprocal_frames_convolve(int num_atoms, int num_frames, int gri
 int nnpops_pme_reciprocal_frames_interpolate(int num_atoms, int num_frames, int gridx, int gridy, int gridz, int order, const float* charges,
                                              const float* box_vectors, float coulomb, const float* real_grids, float* position_deriv,
                                              float* charge_deriv, void* workspace, void* stream);
+/* Box gradients over frames: box_deriv [num_frames][3][3] = dE_m/dB_m, float32, fully written (rows a, b, c; positions and image shifts
+ * held fixed, as nnpops_pme_direct_box / nnpops_pme_reciprocal_box_gradient define it).  Passes of their own: the entries above and
+ * their results are untouched.  Float64 sums in a fixed order, no atomics; a frame's gradient does not depend on the batch around it.
+ *   nnpops_pme_direct_frames_box: the arguments of nnpops_pme_direct_frames.  One workgroup per tile walks every pair once, from its
+ *     higher index; - sum_k n_k (x) G_k over the included pairs whose image shift n_k is not zero (the others add nothing and are left
+ *     after the shift is known).  A frame with fewer than two atoms or without a shifted pair gets exact zeros.
+ *     workspace: nnpops_pme_direct_frames_box_workspace_bytes(T) bytes.
+ *   nnpops_pme_reciprocal_frames_box_pi: between nnpops_pme_reciprocal_frames_convolve and the caller's irfftn, on the scaled
+ *     recip_grids (read only); then nnpops_pme_reciprocal_frames_box_gradient after nnpops_pme_reciprocal_frames_interpolate, with that
+ *     entry's position_deriv (unscaled) and the positions as passed to the spread: - B_m^-T (Pi_m + X_m), one workgroup per frame.  A frame
+ *     without atoms gets zeros.  box_workspace: nnpops_pme_reciprocal_frames_box_workspace_bytes(...) bytes, the same buffer for both. */
+int64_t nnpops_pme_direct_frames_box_workspace_bytes(int num_tiles);
+int nnpops_pme_direct_frames_box(int num_atoms, int num_frames, int num_tiles, int max_exclusions, const int32_t* table, const float* positions,
+                                 const float* charges, const int32_t* exclusions, const float* box_vectors, float cutoff, float alpha,
+                                 float coulomb, float* box_deriv, void* workspace, void* stream);
+int64_t nnpops_pme_reciprocal_frames_box_workspace_bytes(int num_frames, int gridx, int gridy, int gridz);
+int nnpops_pme_reciprocal_frames_box_pi(int num_atoms, int num_frames, int gridx, int gridy, int gridz, int order, const float* box_vectors,
+                                        float alpha, const float* xmoduli, const float* ymoduli, const float* zmoduli, const void* recip_grids,
+                                        void* box_workspace, void* stream);
+int nnpops_pme_reciprocal_frames_box_gradient(int num_atoms, int num_frames, int gridx, int gridy, int gridz, int order,
+                                              const int32_t* table, const float* positions, const float* position_deriv,
+                                              const float* box_vectors, float* box_deriv, void* box_workspace, void* stream);
 
 /* ---- dense layers of the ANI atomic networks (reference src/pytorch/BatchedNN.cpp:30-50, BatchedNN.py:37-122) ----
  * C[M x N] = A[M x K] B with fp32 in and out; the products run on the half-precision matrix instruction with every

@@ -159,6 +159,14 @@ SIGNATURES = {
                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_pme_reciprocal_frames_interpolate": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                            C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nnpops_pme_direct_frames_box_workspace_bytes": (C.c_int64, [C.c_int]),
+    "nnpops_pme_direct_frames_box": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nnpops_pme_reciprocal_frames_box_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nnpops_pme_reciprocal_frames_box_pi": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nnpops_pme_reciprocal_frames_box_gradient": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_neighbor_pairs_backward": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_neighbor_pairs_backward_workspace_bytes": (C.c_int64, [C.c_int]),
@@ -823,6 +831,55 @@ def pme_reciprocal_frames(positions, charges, box_vectors, table, gridx, gridy, 
         _check(L.nnpops_pme_reciprocal_frames_interpolate(n, frames, *dims, _ptr(charges), _ptr(box_vectors), float(coulomb), _ptr(grid),
                                                           _ptr(pos_deriv), _ptr(charge_deriv), _ptr(ws), _stream_ptr(dev)))
     return energies, pos_deriv, charge_deriv
+
+
+def pme_direct_frames_box(positions, charges, exclusions, box_vectors, table, cutoff, alpha, coulomb):
+    """dE_m/dB_m [B, 3, 3] float32 of the direct-space PME energies of a batch of frames through the C ABI (the arguments of
+    pme_direct_frames): - sum_k n_k (x) G_k over every frame's included pairs, float64 sums in a fixed order."""
+    n, frames, max_excl = positions.size(0), box_vectors.size(0), exclusions.size(1)
+    tiles = (table.numel() - 4 - 2 * (frames + 1) - n) // 4
+    dev = positions.device
+    box_deriv = torch.empty((frames, 3, 3), dtype=torch.float32, device=dev)
+    L = lib()
+    ws = torch.empty((int(L.nnpops_pme_direct_frames_box_workspace_bytes(tiles)),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(L.nnpops_pme_direct_frames_box(n, frames, tiles, max_excl, _ptr(table), _ptr(positions.contiguous()), _ptr(charges.contiguous()),
+                                              _ptr(exclusions.contiguous()) if max_excl else None, _ptr(box_vectors.contiguous()),
+                                              float(cutoff), float(alpha), float(coulomb), _ptr(box_deriv), _ptr(ws), _stream_ptr(dev)))
+    return box_deriv
+
+
+def pme_reciprocal_frames_box(positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha, coulomb, xmoduli, ymoduli, zmoduli):
+    """pme_reciprocal_frames and dE_m/dB_m through the C ABI: ... -> convolve -> box_pi -> irfftn -> interpolate -> box_gradient.
+    -> (energies [B] without the self energy, dE/dpositions [N, 3], dE/dcharges [N], dE/dbox [B, 3, 3])."""
+    n, frames = positions.size(0), box_vectors.size(0)
+    tiles = (table.numel() - 4 - 2 * (frames + 1) - n) // 4
+    dev = positions.device
+    positions, charges, box_vectors = positions.contiguous(), charges.contiguous(), box_vectors.contiguous()
+    mods = [m.contiguous() for m in (xmoduli, ymoduli, zmoduli)]
+    L = lib()
+    dims = (gridx, gridy, gridz, order)
+    ws = torch.empty((int(L.nnpops_pme_reciprocal_frames_workspace_bytes(n, frames, *dims)),), dtype=torch.uint8, device=dev)
+    box_ws = torch.empty((int(L.nnpops_pme_reciprocal_frames_box_workspace_bytes(frames, gridx, gridy, gridz)),), dtype=torch.uint8, device=dev)
+    real = torch.empty((frames, gridx, gridy, gridz), dtype=torch.float32, device=dev)
+    energies = torch.empty((frames,), dtype=torch.float32, device=dev)
+    pos_deriv = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    charge_deriv = torch.empty((n,), dtype=torch.float32, device=dev)
+    box_deriv = torch.empty((frames, 3, 3), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _check(L.nnpops_pme_reciprocal_frames_spread(n, frames, tiles, *dims, _ptr(table), _ptr(positions), _ptr(charges), _ptr(box_vectors),
+                                                     float(coulomb), _ptr(real), _ptr(ws), _stream_ptr(dev)))
+        recip = torch.fft.rfftn(real, dim=(1, 2, 3)).contiguous()
+        _check(L.nnpops_pme_reciprocal_frames_convolve(n, frames, *dims, _ptr(box_vectors), float(alpha), _ptr(mods[0]), _ptr(mods[1]),
+                                                       _ptr(mods[2]), _ptr(recip), _ptr(energies), _ptr(ws), _stream_ptr(dev)))
+        _check(L.nnpops_pme_reciprocal_frames_box_pi(n, frames, *dims, _ptr(box_vectors), float(alpha), _ptr(mods[0]), _ptr(mods[1]),
+                                                     _ptr(mods[2]), _ptr(recip), _ptr(box_ws), _stream_ptr(dev)))
+        grid = torch.fft.irfftn(recip, s=(gridx, gridy, gridz), dim=(1, 2, 3), norm="forward").contiguous()
+        _check(L.nnpops_pme_reciprocal_frames_interpolate(n, frames, *dims, _ptr(charges), _ptr(box_vectors), float(coulomb), _ptr(grid),
+                                                          _ptr(pos_deriv), _ptr(charge_deriv), _ptr(ws), _stream_ptr(dev)))
+        _check(L.nnpops_pme_reciprocal_frames_box_gradient(n, frames, *dims, _ptr(table), _ptr(positions), _ptr(pos_deriv), _ptr(box_vectors),
+                                                           _ptr(box_deriv), _ptr(box_ws), _stream_ptr(dev)))
+    return energies, pos_deriv, charge_deriv, box_deriv
 
 
 def pme_direct_box(positions, charges, neighbors, deltas, distances, exclusions, box_vectors, alpha, coulomb):

@@ -26,6 +26,11 @@
 //   pme_recip_convolve_frames  one lane per complex point of a frame's grid, the frame's box in scalar registers; energy in double per
 //                              (frame, workgroup).
 //   pme_recip_interp_frames    one lane per atom: the order^3 gather from its own frame's slab of the potential grid.
+// The box gradient dE_m/dB_m of both terms (DESIGN.md s8c for the formulae), in passes of their own so that the kernels above keep their bits:
+//   pme_direct_frames_box      the tiles of pme_direct_frames, every pair once from its higher index: the shift n_k first (box_grad.h),
+//                              pairs with n_k = 0 stop there; nine float64 sums per tile.  pme_frames_box_sum: one wave per frame.
+//   pme_recip_box_pi_frames    after the convolution: Pi in float64 per (frame, workgroup) from the scaled grids.
+//   pme_recip_box_finish_frames one workgroup per frame: the Pi partials, X = sum_j x_j (x) g_j over the frame's atoms, - B^-T (Pi / 2 + X).
 //
 // The table (nnpops_pme_frames_table, int32): {B, N, T, 0} | offsets [B + 1] | tile_start [B + 1] | tiles [T][4] = {frame, first atom of
 // the frame, atoms of the frame, first owner} | atom_frame [N].  A frame's tiles are consecutive.  The kernels clamp whatever a table
@@ -35,6 +40,7 @@
 #include <cmath>
 #include <limits>
 
+#include "box_grad.h"
 #include "device_common.h"
 #include "host_common.h"
 #include "pair_delta.h"
@@ -51,6 +57,7 @@ constexpr int kBX = 4, kBY = 4, kBZ = 16;              // brick of grid points =
 constexpr int kConvBlocksMax = 1024;
 constexpr float kTwoOverSqrtPi = 1.12837916709551257390f;
 static_assert(kTileOwners * 16 == kBlock && kBX * kBY * kBZ == kBlock, "one lane per (owner, sub) and per grid point of a brick");
+static_assert(kBoxThreads == kBlock, "box_block_sum9 adds up a workgroup of kBlock lanes");
 
 struct TableView {
     const int32_t *offsets, *tile_start, *tiles, *atom_frame;
@@ -189,6 +196,90 @@ __global__ __launch_bounds__(64) void pme_frames_energy(const int32_t* __restric
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) e += __shfl_xor(e, off, 64);
     if (threadIdx.x == 0) energy[m] = (float)(scale * e);
+}
+
+// ---- box gradient of the direct term: dE_m/dB_m = - sum_k n_k (x) G_k = sum_k n_k (x) (dedr_k delta_k) over frame m's included pairs ----
+// A pass of its own (pme_direct_frames keeps its bits): the same tiles, staging, displacement, keep rule, exclusion test and float
+// expressions for dedr, but owner i's lanes walk j = sub, sub + 16, ... < i only -- every pair ONCE, from its higher index, the side the
+// forward counts the energy from.  The shift n_k is recovered (box_grad.h: image_shift) before anything else: a pair with n_k = 0 adds
+// exactly nothing and skips the exclusion scan, the charges and the transcendentals.  Nine float64 sums per lane, box_block_sum9 per
+// tile.  The excluded pairs' erf correction is un-wrapped: it does not depend on the box.
+__global__ __launch_bounds__(kBlock) void pme_direct_frames_box(int N, int B, int max_excl, const int32_t* __restrict__ tiles,
+                                                                 const float* __restrict__ pos, const float* __restrict__ charge,
+                                                                 const int* __restrict__ excl, const float* __restrict__ boxes, float cutoff2,
+                                                                 float alpha, float coulomb, double* __restrict__ tile_box) {
+    __shared__ float spos[3 * kFrameLdsAtoms];
+    __shared__ float sq[kFrameLdsAtoms];
+    const Tile t = load_tile(tiles, blockIdx.x, N, B);
+    const float* box = boxes + 9 * (size_t)t.frame;                         // (uniform address: scalar loads)
+    const float* fpos = pos + 3 * (size_t)t.first;
+    const float* fq = charge + t.first;
+    const bool staged = t.n <= kFrameLdsAtoms;
+    if (staged) {
+        for (int k = threadIdx.x; k < 3 * t.n; k += kBlock) spos[k] = fpos[k];
+        for (int k = threadIdx.x; k < t.n; k += kBlock) sq[k] = fq[k];
+    }
+    __syncthreads();
+    const int sub = threadIdx.x & 15;
+    const int i = t.owner0 - t.first + (threadIdx.x >> 4);                  // the owner, counted inside its frame
+    double acc[9];
+#pragma unroll
+    for (int q = 0; q < 9; q++) acc[q] = 0.0;
+    auto walk = [&](const float* __restrict__ P, const float* __restrict__ Q) {
+        const int* row = excl + (size_t)(t.first + i) * max_excl;
+        for (int j = sub; j < i; j += 16) {
+            const Vec3<float> d = wrapped_delta<float>(P, i, j, box, true);
+            const float d2 = allpairs_norm2<float>(d);
+            if (d2 > cutoff2) continue;
+            float n[3];
+            image_shift(P, i, j, d.x, d.y, d.z, box, n);
+            if (n[0] == 0.f && n[1] == 0.f && n[2] == 0.f) continue;
+            const int gj = t.first + j;
+            bool include = true;
+            for (int e = 0; e < max_excl; e++) {                             // rows are sorted in descending order (pme.py)
+                const int x = row[e];
+                if (x < gj) break;
+                if (x == gj) { include = false; break; }
+            }
+            if (!include) continue;
+            const float r = sqrtf(d2);
+            const float inv_r = 1.0f / r, ar = alpha * r;
+            const float ex = expf(-ar * ar), erfc_ar = erfcf(ar);
+            const float pre = coulomb * inv_r;
+            const float c1 = Q[i], c2 = Q[j];
+            const float dedr = pre * c1 * c2 * (erfc_ar + ar * ex * kTwoOverSqrtPi) * inv_r * inv_r;
+            const float f[3] = {dedr * d.x, dedr * d.y, dedr * d.z};         // -G_k
+#pragma unroll
+            for (int a = 0; a < 3; a++)
+#pragma unroll
+                for (int q = 0; q < 3; q++) acc[3 * a + q] += (double)n[a] * (double)f[q];
+        }
+    };
+    if (i < t.n) {
+        if (staged) walk(spos, sq); else walk(fpos, fq);
+    }
+    box_block_sum9(acc, tile_box + 9 * (size_t)blockIdx.x);
+}
+
+// box_deriv[m] = the nine sums of frame m's tiles [tile_start[m], tile_start[m + 1]): one wave per frame, lane l adds tiles l, l + 64, ...
+// then the xor order.  A frame without tiles or without a shifted pair gets exact zeros; the order does not depend on the batch.
+__global__ __launch_bounds__(64) void pme_frames_box_sum(const int32_t* __restrict__ tile_start, int T, const double* __restrict__ tile_box,
+                                                         float* __restrict__ box_deriv) {
+    const int m = blockIdx.x;
+    const int begin = min(max(tile_start[m], 0), T), end = min(max(tile_start[m + 1], begin), T);
+    double acc[9];
+#pragma unroll
+    for (int q = 0; q < 9; q++) acc[q] = 0.0;
+    for (int k = begin + (int)threadIdx.x; k < end; k += 64) {
+#pragma unroll
+        for (int q = 0; q < 9; q++) acc[q] += tile_box[9 * (size_t)k + q];
+    }
+#pragma unroll
+    for (int q = 0; q < 9; q++) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) acc[q] += __shfl_xor(acc[q], off, 64);
+        if (threadIdx.x == q) box_deriv[9 * (size_t)m + q] = (float)acc[q];
+    }
 }
 
 // ---- reciprocal space ----
@@ -418,6 +509,120 @@ __global__ __launch_bounds__(kBlock) void pme_recip_interp_frames(int N, int B, 
     charge_deriv[atom] = dq * sqrt_coulomb;
 }
 
+// ---- box gradient of the reciprocal term: dE_m/dB_m = - B_m^-T (Pi_m + X_m) ----
+// Pi: a pass of its own over the grids pme_recip_convolve_frames has scaled (that kernel keeps its bits), frame and workgroup from
+// blockIdx.x as there, the convolution's float expressions for eterm, the six float64 sums of pme_recip_box_pi (without the 1/2) per
+// (frame, workgroup) into pi_partial [B][cb][6].  Points whose eterm underflows add nothing.
+__global__ __launch_bounds__(kBlock) void pme_recip_box_pi_frames(int gx, int gy, int gz, int cb, const float* __restrict__ boxes,
+                                                                 float recip_exp_factor, const float* __restrict__ xmod,
+                                                                 const float* __restrict__ ymod, const float* __restrict__ zmod,
+                                                                 const float2* __restrict__ cgrids, double* __restrict__ pi_partial) {
+    __shared__ double red[kBlock / 64][6];
+    const int frame = blockIdx.x / cb, blk = blockIdx.x % cb;               // (the host launches exactly B * cb workgroups)
+    float b[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) b[i] = boxes[9 * (size_t)frame + i];        // (uniform: scalar loads)
+    const RecipBox r = recip_box(b);
+    const float scale_factor = (float)M_PI * b[0] * b[4] * b[8];
+    const int zsize = gz / 2 + 1;
+    const long long points = (long long)gx * gy * zsize;
+    const float2* cgrid = cgrids + (size_t)frame * points;
+    double pi[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (long long idx = (long long)blk * kBlock + threadIdx.x; idx < points; idx += (long long)cb * kBlock) {
+        if (idx == 0) continue;
+        const int kx = (int)(idx / ((long long)gy * zsize));
+        const int rem = (int)(idx - (long long)kx * gy * zsize);
+        const int ky = rem / zsize, kz = rem - ky * zsize;
+        const int mx = kx < (gx + 1) / 2 ? kx : kx - gx;
+        const int my = ky < (gy + 1) / 2 ? ky : ky - gy;
+        const int mz = kz < (gz + 1) / 2 ? kz : kz - gz;
+        const float mhx = mx * r.r00;
+        const float mhy = mx * r.r10 + my * r.r11;
+        const float mhz = mx * r.r20 + my * r.r21 + mz * r.r22;
+        const float m2 = mhx * mhx + mhy * mhy + mhz * mhz;
+        const float denom = m2 * (scale_factor * xmod[kx]) * ymod[ky] * zmod[kz];
+        const float eterm = expf(-recip_exp_factor * m2) / denom;
+        if (!(eterm > 0.f)) continue;
+        const float w = (kz > 0 && kz <= (gz - 1) / 2) ? 2.f : 1.f;
+        const float2 g = cgrid[idx];
+        const double t = (double)w * ((double)g.x * g.x + (double)g.y * g.y) / (double)eterm;
+        const double c = 2.0 * ((double)recip_exp_factor + 1.0 / (double)m2);
+        const double hx = mhx, hy = mhy, hz = mhz;
+        pi[0] += t * (1.0 - c * hx * hx); pi[1] += t * (1.0 - c * hy * hy); pi[2] += t * (1.0 - c * hz * hz);
+        pi[3] -= t * c * hx * hy;         pi[4] -= t * c * hx * hz;         pi[5] -= t * c * hy * hz;
+    }
+#pragma unroll
+    for (int q = 0; q < 6; q++)
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) pi[q] += __shfl_xor(pi[q], off, 64);
+    if (lane_id() == 0) {
+#pragma unroll
+        for (int q = 0; q < 6; q++) red[threadIdx.x >> 6][q] = pi[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        double s = red[0][threadIdx.x];
+        for (int w = 1; w < kBlock / 64; w++) s += red[w][threadIdx.x];
+        pi_partial[(size_t)blockIdx.x * 6 + threadIdx.x] = s;
+    }
+}
+
+// One workgroup per frame: lane t adds the frame's Pi partials t, t + 256, ... and, for X = sum_j x_j (x) g_j, its atoms
+// offsets[m] + t, + 256, ... from the positions as passed and the unscaled interpolated dE/dpositions (float64 products); the fifteen
+// sums go through the xor tree, then the four waves in order; one lane forms the general 3 x 3 inverse of B_m in float64 and stores
+// - B_m^-T (Pi / 2 + X).  A frame's atoms are few enough for one workgroup: no separate atoms launch, and nothing here depends on the
+// batch around the frame.  An empty frame has zero grids and no atoms: zeros.
+__global__ __launch_bounds__(kBlock) void pme_recip_box_finish_frames(int N, int cb, const int32_t* __restrict__ offsets,
+                                                                     const double* __restrict__ pi_partial, const float* __restrict__ pos,
+                                                                     const float* __restrict__ pos_deriv, const float* __restrict__ boxes,
+                                                                     float* __restrict__ box_deriv) {
+    __shared__ double red[kBlock / 64][15];
+    const int frame = blockIdx.x;
+    const int a0 = min(max(offsets[frame], 0), N), a1 = min(max(offsets[frame + 1], a0), N);
+    double acc[15];
+#pragma unroll
+    for (int q = 0; q < 15; q++) acc[q] = 0.0;
+    for (int k = threadIdx.x; k < cb; k += kBlock) {
+#pragma unroll
+        for (int q = 0; q < 6; q++) acc[q] += pi_partial[((size_t)frame * cb + k) * 6 + q];
+    }
+    for (int atom = a0 + (int)threadIdx.x; atom < a1; atom += kBlock) {
+#pragma unroll
+        for (int a = 0; a < 3; a++)
+#pragma unroll
+            for (int c = 0; c < 3; c++) acc[6 + 3 * a + c] += (double)pos[3 * (size_t)atom + a] * (double)pos_deriv[3 * (size_t)atom + c];
+    }
+#pragma unroll
+    for (int q = 0; q < 15; q++)
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) acc[q] += __shfl_xor(acc[q], off, 64);
+    if (lane_id() == 0) {
+#pragma unroll
+        for (int q = 0; q < 15; q++) red[threadIdx.x >> 6][q] = acc[q];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s[15];
+        for (int q = 0; q < 15; q++) {
+            s[q] = red[0][q];
+            for (int w = 1; w < kBlock / 64; w++) s[q] += red[w][q];
+        }
+        const double pxx = 0.5 * s[0], pyy = 0.5 * s[1], pzz = 0.5 * s[2], pxy = 0.5 * s[3], pxz = 0.5 * s[4], pyz = 0.5 * s[5];
+        const double M[9] = {pxx + s[6], pxy + s[7], pxz + s[8], pxy + s[9], pyy + s[10], pyz + s[11], pxz + s[12], pyz + s[13], pzz + s[14]};
+        double Bm[9];
+        for (int q = 0; q < 9; q++) Bm[q] = (double)boxes[9 * (size_t)frame + q];
+        // B^-1 = adj(B) / det(B)
+        const double c00 = Bm[4] * Bm[8] - Bm[5] * Bm[7], c01 = Bm[5] * Bm[6] - Bm[3] * Bm[8], c02 = Bm[3] * Bm[7] - Bm[4] * Bm[6];
+        const double det = Bm[0] * c00 + Bm[1] * c01 + Bm[2] * c02;
+        const double inv[9] = {c00 / det, (Bm[2] * Bm[7] - Bm[1] * Bm[8]) / det, (Bm[1] * Bm[5] - Bm[2] * Bm[4]) / det,
+                               c01 / det, (Bm[0] * Bm[8] - Bm[2] * Bm[6]) / det, (Bm[2] * Bm[3] - Bm[0] * Bm[5]) / det,
+                               c02 / det, (Bm[1] * Bm[6] - Bm[0] * Bm[7]) / det, (Bm[0] * Bm[4] - Bm[1] * Bm[3]) / det};
+        for (int a = 0; a < 3; a++)
+            for (int c = 0; c < 3; c++)       // (B^-T M)[a][c] = sum_k B^-1[k][a] M[k][c]
+                box_deriv[9 * (size_t)frame + 3 * a + c] = (float)(0.0 - (inv[a] * M[c] + inv[3 + a] * M[3 + c] + inv[6 + a] * M[6 + c]));
+    }
+}
+
 int check_recip(int num_atoms, int num_frames, int gx, int gy, int gz, int order) {
     NNPOPS_REQUIRE(num_atoms >= 0 && num_frames >= 1, "bad sizes (atoms %d, frames %d)", num_atoms, num_frames);
     NNPOPS_REQUIRE(gx >= 1 && gy >= 1 && gz >= 1, "the grid dimensions must be positive (%d, %d, %d)", gx, gy, gz);
@@ -569,6 +774,67 @@ int nnpops_pme_reciprocal_frames_interpolate(int num_atoms, int num_frames, int 
     else
         hipLaunchKernelGGL(pme_recip_interp_frames<5>, dim3(ab), dim3(kBlock), 0, s, num_atoms, num_frames, d, box_vectors, charges, sqrt_coulomb,
                            (const int4*)w.base, (const float*)w.theta, (const float*)w.dtheta, real_grids, position_deriv, charge_deriv);
+    NNPOPS_HIP_TRY(hipGetLastError());
+    return NNPOPS_OK;
+}
+
+// ---- box gradients: box_deriv [num_frames][3][3] = dE_m/dB_m, fully written ----
+int64_t nnpops_pme_direct_frames_box_workspace_bytes(int num_tiles) {
+    return num_tiles < 0 ? 0 : (int64_t)sizeof(double) * 9 * std::max(num_tiles, 1) + 256;
+}
+
+int nnpops_pme_direct_frames_box(int num_atoms, int num_frames, int num_tiles, int max_exclusions, const int32_t* table, const float* positions,
+                                 const float* charges, const int32_t* exclusions, const float* box_vectors, float cutoff, float alpha,
+                                 float coulomb, float* box_deriv, void* workspace, void* stream) {
+    NNPOPS_REQUIRE(num_atoms >= 0 && num_frames >= 1 && num_tiles >= 0 && max_exclusions >= 0, "bad sizes (atoms %d, frames %d, tiles %d, exclusions %d)",
+                   num_atoms, num_frames, num_tiles, max_exclusions);
+    NNPOPS_REQUIRE(cutoff > 0 && alpha > 0 && coulomb > 0, "cutoff, alpha and coulomb must be positive");
+    NNPOPS_REQUIRE(table && box_vectors && box_deriv && workspace, "NULL device pointer");
+    NNPOPS_REQUIRE(num_atoms == 0 || (positions && charges), "NULL device pointer");
+    NNPOPS_REQUIRE(max_exclusions == 0 || num_atoms == 0 || exclusions, "NULL exclusions pointer");
+    hipStream_t s = (hipStream_t)stream;
+    const TableView v = view(table, num_frames, num_tiles);
+    double* tile_box = (double*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    if (num_tiles > 0)
+        hipLaunchKernelGGL(pme_direct_frames_box, dim3(num_tiles), dim3(kBlock), 0, s, num_atoms, num_frames, max_exclusions, v.tiles, positions,
+                           charges, exclusions, box_vectors, cutoff * cutoff, alpha, coulomb, tile_box);
+    hipLaunchKernelGGL(pme_frames_box_sum, dim3(num_frames), dim3(64), 0, s, v.tile_start, num_tiles, (const double*)tile_box, box_deriv);
+    NNPOPS_HIP_TRY(hipGetLastError());
+    return NNPOPS_OK;
+}
+
+int64_t nnpops_pme_reciprocal_frames_box_workspace_bytes(int num_frames, int gridx, int gridy, int gridz) {
+    if (check_recip(0, num_frames, gridx, gridy, gridz, 4) != NNPOPS_OK) return 0;
+    return (int64_t)sizeof(double) * 6 * (int64_t)num_frames * conv_blocks(gridx, gridy, gridz) + 256;
+}
+
+int nnpops_pme_reciprocal_frames_box_pi(int num_atoms, int num_frames, int gridx, int gridy, int gridz, int order, const float* box_vectors,
+                                        float alpha, const float* xmoduli, const float* ymoduli, const float* zmoduli, const void* recip_grids,
+                                        void* box_workspace, void* stream) {
+    if (int rc = check_recip(num_atoms, num_frames, gridx, gridy, gridz, order)) return rc;
+    NNPOPS_REQUIRE(alpha > 0, "alpha must be positive");
+    NNPOPS_REQUIRE(box_vectors && xmoduli && ymoduli && zmoduli && recip_grids && box_workspace, "NULL device pointer");
+    hipStream_t s = (hipStream_t)stream;
+    const int cb = conv_blocks(gridx, gridy, gridz);
+    const float recip_exp_factor = (float)(M_PI * M_PI / ((double)alpha * (double)alpha));
+    double* pi_partial = (double*)(((uintptr_t)box_workspace + 255) & ~(uintptr_t)255);
+    hipLaunchKernelGGL(pme_recip_box_pi_frames, dim3((unsigned)num_frames * (unsigned)cb), dim3(kBlock), 0, s, gridx, gridy, gridz, cb, box_vectors,
+                       recip_exp_factor, xmoduli, ymoduli, zmoduli, (const float2*)recip_grids, pi_partial);
+    NNPOPS_HIP_TRY(hipGetLastError());
+    return NNPOPS_OK;
+}
+
+int nnpops_pme_reciprocal_frames_box_gradient(int num_atoms, int num_frames, int gridx, int gridy, int gridz, int order,
+                                              const int32_t* table, const float* positions, const float* position_deriv,
+                                              const float* box_vectors, float* box_deriv, void* box_workspace, void* stream) {
+    if (int rc = check_recip(num_atoms, num_frames, gridx, gridy, gridz, order)) return rc;
+    NNPOPS_REQUIRE(table && box_vectors && box_deriv && box_workspace, "NULL device pointer");
+    NNPOPS_REQUIRE(num_atoms == 0 || (positions && position_deriv), "NULL positions / derivative pointer");
+    hipStream_t s = (hipStream_t)stream;
+    const TableView v = view(table, num_frames, 0);                         // (the offsets come before the tiles)
+    const double* pi_partial = (const double*)(((uintptr_t)box_workspace + 255) & ~(uintptr_t)255);
+    hipLaunchKernelGGL(pme_recip_box_finish_frames, dim3(num_frames), dim3(kBlock), 0, s, num_atoms, conv_blocks(gridx, gridy, gridz), v.offsets,
+                       pi_partial, positions, position_deriv, box_vectors, box_deriv);
     NNPOPS_HIP_TRY(hipGetLastError());
     return NNPOPS_OK;
 }

@@ -3381,6 +3381,8 @@ TORCH_LIBRARY_IMPL(pme, CPU, m) {
 // the tile count from the table's length, so a call reads nothing back from the device and can be captured in a graph (the kernels
 // clamp whatever a table holds).  The derivatives are computed with the forward pass; the backward scales every frame's rows by that
 // frame's upstream gradient.  First order in positions and charges only: no box gradient, no create_graph.
+// pme_direct_frames_box / pme_reciprocal_frames_box: the same forward calls, and dE_m/dB_m [B, 3, 3] from the box passes of
+// pme_frames.hip when box_vectors requires a gradient; the backward adds box_deriv[m] times frame m's upstream gradient.
 // ---------------------------------------------------------------------------------------------
 Tensor pme_frames_table_entry(const Tensor& offsets, c10::Device device) {
     TORCH_CHECK(!offsets.is_cuda() && offsets.dim() == 1 && offsets.scalar_type() == torch::kInt64 && offsets.size(0) >= 1,
@@ -3397,8 +3399,10 @@ Tensor pme_frames_table_entry(const Tensor& offsets, c10::Device device) {
 
 struct PmeFramesShape { int64_t frames, atoms, tiles; };
 
-// what both ops check of their common arguments; the tile count follows from the table's length
-PmeFramesShape pme_frames_check(const char* op, const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table) {
+// what the ops check of their common arguments; the tile count follows from the table's length.  box_op: the two _box ops, which
+// take a box that requires a gradient.
+PmeFramesShape pme_frames_check(const char* op, const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table,
+                                bool box_op = false) {
     TORCH_CHECK(positions.is_cuda(), op, ": device tensors only (the frames ops have no CPU key)");
     TORCH_CHECK(positions.dim() == 2 && positions.size(1) == 3, op, ": positions must have shape (atoms, 3)");
     TORCH_CHECK(charges.dim() == 1 && charges.size(0) == positions.size(0), op, ": charges must be 1D, one per atom");
@@ -3406,7 +3410,7 @@ PmeFramesShape pme_frames_check(const char* op, const Tensor& positions, const T
                 ": box_vectors must have shape (frames, 3, 3) with at least one frame");
     TORCH_CHECK(positions.scalar_type() == torch::kFloat32 && charges.scalar_type() == torch::kFloat32 &&
                 box_vectors.scalar_type() == torch::kFloat32, op, " computes in float32");
-    TORCH_CHECK(!(box_vectors.requires_grad() && torch::GradMode::is_enabled()), op,
+    TORCH_CHECK(box_op || !(box_vectors.requires_grad() && torch::GradMode::is_enabled()), op,
                 ": box gradients over frames are not available (pass box_vectors that do not require a gradient)");
     TORCH_CHECK(table.dim() == 1 && table.scalar_type() == torch::kInt32 && table.is_contiguous(), op,
                 ": table must be the int32 tensor pmeFramesTable returned");
@@ -3441,14 +3445,22 @@ tensor_list pme_frames_scale(const char* op, const Tensor& pos_deriv, const Tens
     return {out, charge_deriv * g.to(torch::kFloat32).index_select(0, atom_frame)};
 }
 
+// the box gradient the _box ops saved (fourth, when there is one) times every frame's upstream gradient
+Tensor pme_frames_box_scale(const torch::autograd::variable_list& saved, const Tensor& grad) {
+    return saved.size() > 3 ? saved[3] * grad.to(torch::kFloat32).reshape({-1, 1, 1}) : Tensor();
+}
+
 class PmeDirectFramesFunction : public torch::autograd::Function<PmeDirectFramesFunction> {
 public:
     static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& exclusions,
                           const Tensor& box_vectors, const Tensor& table, const torch::Scalar& cutoff, const torch::Scalar& alpha,
-                          const torch::Scalar& coulomb) {
-        const PmeFramesShape s = pme_frames_check("pme_direct_frames", positions, charges, box_vectors, table);
+                          const torch::Scalar& coulomb, bool box_op, bool box_grad) {
+        const char* op = box_op ? "pme_direct_frames_box" : "pme_direct_frames";
+        const std::string qualified = std::string("pme::") + op;
+        ctx->saved_data["box_op"] = box_op;
+        const PmeFramesShape s = pme_frames_check(op, positions, charges, box_vectors, table, box_op);
         TORCH_CHECK(exclusions.dim() == 2 && exclusions.size(0) == s.atoms && exclusions.device() == positions.device() &&
-                    at::isIntegralType(exclusions.scalar_type(), false), "pme_direct_frames: exclusions must be integers of shape (atoms, max_exclusions) on the device of positions");
+                    at::isIntegralType(exclusions.scalar_type(), false), op, ": exclusions must be integers of shape (atoms, max_exclusions) on the device of positions");
         const Tensor pos = positions.contiguous(), q = charges.contiguous(), ex = exclusions.to(torch::kInt32).contiguous(),
                      boxes = box_vectors.contiguous();
         const auto opts = positions.options();
@@ -3461,14 +3473,25 @@ public:
                                      (float)cutoff.toDouble(), (float)alpha.toDouble(), (float)coulomb.toDouble(), energies.data_ptr<float>(),
                                      pos_deriv.data_ptr<float>(), charge_deriv.data_ptr<float>(), workspace.data_ptr(),
                                      current_stream(positions.device())) != NNPOPS_OK)
-            raise_last("pme::pme_direct_frames");
-        ctx->save_for_backward({pos_deriv, charge_deriv, table});
+            raise_last(qualified.c_str());
+        if (box_grad) {
+            Tensor box_deriv = torch::empty({s.frames, 3, 3}, opts);
+            Tensor box_workspace = torch::empty({nnpops_pme_direct_frames_box_workspace_bytes((int)s.tiles)}, opts.dtype(torch::kUInt8));
+            if (nnpops_pme_direct_frames_box((int)s.atoms, (int)s.frames, (int)s.tiles, (int)max_excl, table.data_ptr<int32_t>(), pos.data_ptr<float>(),
+                                             q.data_ptr<float>(), max_excl ? ex.data_ptr<int32_t>() : nullptr, boxes.data_ptr<float>(),
+                                             (float)cutoff.toDouble(), (float)alpha.toDouble(), (float)coulomb.toDouble(),
+                                             box_deriv.data_ptr<float>(), box_workspace.data_ptr(), current_stream(positions.device())) != NNPOPS_OK)
+                raise_last(qualified.c_str());
+            ctx->save_for_backward({pos_deriv, charge_deriv, table, box_deriv});
+        } else {
+            ctx->save_for_backward({pos_deriv, charge_deriv, table});
+        }
         return energies;
     }
     static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) {
         const auto saved = ctx->get_saved_variables();
-        const tensor_list g = pme_frames_scale("pme_direct_frames", saved[0], saved[1], saved[2], grad_outputs[0]);
-        return {g[0], g[1], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+        const tensor_list g = pme_frames_scale(ctx->saved_data["box_op"].toBool() ? "pme_direct_frames_box" : "pme_direct_frames", saved[0], saved[1], saved[2], grad_outputs[0]);
+        return {g[0], g[1], Tensor(), pme_frames_box_scale(saved, grad_outputs[0]), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
     }
 };
 
@@ -3477,18 +3500,21 @@ public:
     static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table,
                           const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz, const torch::Scalar& order,
                           const torch::Scalar& alpha, const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli,
-                          const Tensor& zmoduli) {
-        const PmeFramesShape s = pme_frames_check("pme_reciprocal_frames", positions, charges, box_vectors, table);
+                          const Tensor& zmoduli, bool box_op, bool box_grad) {
+        const char* op = box_op ? "pme_reciprocal_frames_box" : "pme_reciprocal_frames";
+        const std::string qualified = std::string("pme::") + op;
+        ctx->saved_data["box_op"] = box_op;
+        const PmeFramesShape s = pme_frames_check(op, positions, charges, box_vectors, table, box_op);
         const std::vector<int64_t> K{gridx.toLong(), gridy.toLong(), gridz.toLong()};
         const int64_t o = order.toLong();
-        TORCH_CHECK(K[0] >= 1 && K[1] >= 1 && K[2] >= 1, "pme_reciprocal_frames: the grid dimensions must be positive");
-        TORCH_CHECK(o == 4 || o == 5, "pme_reciprocal_frames: Only pmeOrder 4 or 5 is supported (got ", o, ")");
+        TORCH_CHECK(K[0] >= 1 && K[1] >= 1 && K[2] >= 1, op, ": the grid dimensions must be positive");
+        TORCH_CHECK(o == 4 || o == 5, op, ": Only pmeOrder 4 or 5 is supported (got ", o, ")");
         const double a = alpha.toDouble(), k = coulomb.toDouble();
-        TORCH_CHECK(a > 0 && k > 0, "pme_reciprocal_frames: alpha and coulomb must be positive");
+        TORCH_CHECK(a > 0 && k > 0, op, ": alpha and coulomb must be positive");
         const Tensor* moduli[3] = {&xmoduli, &ymoduli, &zmoduli};
         for (int i = 0; i < 3; i++)
             TORCH_CHECK(moduli[i]->dim() == 1 && moduli[i]->size(0) == K[i] && moduli[i]->scalar_type() == torch::kFloat32 &&
-                        moduli[i]->device() == positions.device(), "pme_reciprocal_frames: the moduli must be float32 tensors of the grid's sizes on the device of positions");
+                        moduli[i]->device() == positions.device(), op, ": the moduli must be float32 tensors of the grid's sizes on the device of positions");
         const Tensor pos = positions.contiguous(), q = charges.contiguous(), boxes = box_vectors.contiguous(), xm = xmoduli.contiguous(),
                      ym = ymoduli.contiguous(), zm = zmoduli.contiguous();
         const auto opts = positions.options();
@@ -3496,48 +3522,80 @@ public:
         c10::hip::HIPGuard guard(positions.device().index());
         void* stream = current_stream(positions.device());
         const int64_t bytes = nnpops_pme_reciprocal_frames_workspace_bytes(n, B, gx, gy, gz, (int)o);
-        if (bytes <= 0) raise_last("pme::pme_reciprocal_frames");
+        if (bytes <= 0) raise_last(qualified.c_str());
         Tensor workspace = torch::empty({bytes}, opts.dtype(torch::kUInt8));
         Tensor real = torch::empty({s.frames, K[0], K[1], K[2]}, opts);
         if (nnpops_pme_reciprocal_frames_spread(n, B, (int)s.tiles, gx, gy, gz, (int)o, table.data_ptr<int32_t>(), pos.data_ptr<float>(),
                                                 q.data_ptr<float>(), boxes.data_ptr<float>(), (float)k, real.data_ptr<float>(),
                                                 workspace.data_ptr(), stream) != NNPOPS_OK)
-            raise_last("pme::pme_reciprocal_frames");
+            raise_last(qualified.c_str());
         const std::vector<int64_t> dims{1, 2, 3};
         Tensor recip = torch::fft::rfftn(real, c10::nullopt, torch::IntArrayRef(dims)).contiguous();
         Tensor energies = torch::empty({s.frames}, opts);
         if (nnpops_pme_reciprocal_frames_convolve(n, B, gx, gy, gz, (int)o, boxes.data_ptr<float>(), (float)a, xm.data_ptr<float>(),
                                                   ym.data_ptr<float>(), zm.data_ptr<float>(), recip.data_ptr(), energies.data_ptr<float>(),
                                                   workspace.data_ptr(), stream) != NNPOPS_OK)
-            raise_last("pme::pme_reciprocal_frames");
-        if (positions.requires_grad() || charges.requires_grad()) {
+            raise_last(qualified.c_str());
+        Tensor box_workspace;
+        if (box_grad) {                                            // Pi from the scaled grids, before the inverse transform
+            const int64_t box_bytes = nnpops_pme_reciprocal_frames_box_workspace_bytes(B, gx, gy, gz);
+            if (box_bytes <= 0) raise_last(qualified.c_str());
+            box_workspace = torch::empty({box_bytes}, opts.dtype(torch::kUInt8));
+            if (nnpops_pme_reciprocal_frames_box_pi(n, B, gx, gy, gz, (int)o, boxes.data_ptr<float>(), (float)a, xm.data_ptr<float>(),
+                                                    ym.data_ptr<float>(), zm.data_ptr<float>(), recip.data_ptr(), box_workspace.data_ptr(),
+                                                    stream) != NNPOPS_OK)
+                raise_last(qualified.c_str());
+        }
+        if (positions.requires_grad() || charges.requires_grad() || box_grad) {     // (X needs the interpolated dE/dpositions)
             const Tensor grid = torch::fft::irfftn(recip, torch::IntArrayRef(K), torch::IntArrayRef(dims), "forward").contiguous();
             Tensor pos_deriv = torch::empty({s.atoms, 3}, opts), charge_deriv = torch::empty({s.atoms}, opts);
             if (nnpops_pme_reciprocal_frames_interpolate(n, B, gx, gy, gz, (int)o, q.data_ptr<float>(), boxes.data_ptr<float>(), (float)k,
                                                          grid.data_ptr<float>(), pos_deriv.data_ptr<float>(), charge_deriv.data_ptr<float>(),
                                                          workspace.data_ptr(), stream) != NNPOPS_OK)
-                raise_last("pme::pme_reciprocal_frames");
-            ctx->save_for_backward({pos_deriv, charge_deriv, table});
+                raise_last(qualified.c_str());
+            if (box_grad) {
+                Tensor box_deriv = torch::empty({s.frames, 3, 3}, opts);
+                if (nnpops_pme_reciprocal_frames_box_gradient(n, B, gx, gy, gz, (int)o, table.data_ptr<int32_t>(), pos.data_ptr<float>(),
+                                                              pos_deriv.data_ptr<float>(), boxes.data_ptr<float>(), box_deriv.data_ptr<float>(),
+                                                              box_workspace.data_ptr(), stream) != NNPOPS_OK)
+                    raise_last(qualified.c_str());
+                ctx->save_for_backward({pos_deriv, charge_deriv, table, box_deriv});
+            } else {
+                ctx->save_for_backward({pos_deriv, charge_deriv, table});
+            }
         }
         return energies;
     }
     static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) {
         const auto saved = ctx->get_saved_variables();
-        const tensor_list g = pme_frames_scale("pme_reciprocal_frames", saved[0], saved[1], saved[2], grad_outputs[0]);
-        return {g[0], g[1], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+        const tensor_list g = pme_frames_scale(ctx->saved_data["box_op"].toBool() ? "pme_reciprocal_frames_box" : "pme_reciprocal_frames", saved[0], saved[1], saved[2], grad_outputs[0]);
+        return {g[0], g[1], pme_frames_box_scale(saved, grad_outputs[0]), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(),
+                Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
     }
 };
 
 Tensor pme_direct_frames_entry(const Tensor& positions, const Tensor& charges, const Tensor& exclusions, const Tensor& box_vectors,
                                const Tensor& table, const torch::Scalar& cutoff, const torch::Scalar& alpha, const torch::Scalar& coulomb) {
-    return PmeDirectFramesFunction::apply(positions, charges, exclusions, box_vectors, table, cutoff, alpha, coulomb);
+    return PmeDirectFramesFunction::apply(positions, charges, exclusions, box_vectors, table, cutoff, alpha, coulomb, false, false);
+}
+Tensor pme_direct_frames_box_entry(const Tensor& positions, const Tensor& charges, const Tensor& exclusions, const Tensor& box_vectors,
+                                   const Tensor& table, const torch::Scalar& cutoff, const torch::Scalar& alpha, const torch::Scalar& coulomb) {
+    return PmeDirectFramesFunction::apply(positions, charges, exclusions, box_vectors, table, cutoff, alpha, coulomb, true,
+                                          box_vectors.requires_grad() && torch::GradMode::is_enabled());
 }
 Tensor pme_reciprocal_frames_entry(const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table,
                                    const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz, const torch::Scalar& order,
                                    const torch::Scalar& alpha, const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli,
                                    const Tensor& zmoduli) {
     return PmeReciprocalFramesFunction::apply(positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha, coulomb, xmoduli,
-                                              ymoduli, zmoduli);
+                                              ymoduli, zmoduli, false, false);
+}
+Tensor pme_reciprocal_frames_box_entry(const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table,
+                                       const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz,
+                                       const torch::Scalar& order, const torch::Scalar& alpha, const torch::Scalar& coulomb,
+                                       const Tensor& xmoduli, const Tensor& ymoduli, const Tensor& zmoduli) {
+    return PmeReciprocalFramesFunction::apply(positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha, coulomb, xmoduli,
+                                              ymoduli, zmoduli, true, box_vectors.requires_grad() && torch::GradMode::is_enabled());
 }
 TORCH_LIBRARY_FRAGMENT(pme, m) {
     m.def("pmeFramesTable(Tensor offsets, Device device) -> Tensor", pme_frames_table_entry);
@@ -3545,14 +3603,22 @@ TORCH_LIBRARY_FRAGMENT(pme, m) {
           "Scalar alpha, Scalar coulomb) -> Tensor");
     m.def("pme_reciprocal_frames(Tensor positions, Tensor charges, Tensor box_vectors, Tensor table, Scalar gridx, Scalar gridy, "
           "Scalar gridz, Scalar order, Scalar alpha, Scalar coulomb, Tensor xmoduli, Tensor ymoduli, Tensor zmoduli) -> Tensor");
+    m.def("pme_direct_frames_box(Tensor positions, Tensor charges, Tensor exclusions, Tensor box_vectors, Tensor table, Scalar cutoff, "
+          "Scalar alpha, Scalar coulomb) -> Tensor");
+    m.def("pme_reciprocal_frames_box(Tensor positions, Tensor charges, Tensor box_vectors, Tensor table, Scalar gridx, Scalar gridy, "
+          "Scalar gridz, Scalar order, Scalar alpha, Scalar coulomb, Tensor xmoduli, Tensor ymoduli, Tensor zmoduli) -> Tensor");
 }
 TORCH_LIBRARY_IMPL(pme, AutogradCUDA, m) {
     m.impl("pme_direct_frames", pme_direct_frames_entry);
     m.impl("pme_reciprocal_frames", pme_reciprocal_frames_entry);
+    m.impl("pme_direct_frames_box", pme_direct_frames_box_entry);
+    m.impl("pme_reciprocal_frames_box", pme_reciprocal_frames_box_entry);
 }
 TORCH_LIBRARY_IMPL(pme, CUDA, m) {
     m.impl("pme_direct_frames", pme_direct_frames_entry);
     m.impl("pme_reciprocal_frames", pme_reciprocal_frames_entry);
+    m.impl("pme_direct_frames_box", pme_direct_frames_box_entry);
+    m.impl("pme_reciprocal_frames_box", pme_reciprocal_frames_box_entry);
 }
 
 // =============================================================================================

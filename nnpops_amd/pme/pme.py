@@ -18,7 +18,9 @@ to a later change.
 
 Batches of frames, every frame in its own box: ``compute_direct_frames`` / ``compute_reciprocal_frames`` return per-frame energies [B]
 from ``torch.ops.pme.pme_direct_frames`` / ``pme_reciprocal_frames`` (nnpops_amd/csrc/pme_frames.hip): device tensors
-only, first derivatives with respect to positions and charges, no box gradient.
+only, first derivatives with respect to positions and charges.  The box gradient over frames is an opt-in: with
+``box_gradient=True`` the two methods call ``pme_direct_frames_box`` / ``pme_reciprocal_frames_box`` -- the same forward passes, bit for
+bit -- and ``backward()`` fills ``box_vectors.grad[B, 3, 3]``; the default call still refuses a box that requires a gradient.
 """
 import math
 
@@ -166,7 +168,7 @@ class PME:
                                                           self.order, self.alpha, self.coulomb, self.moduli[0], self.moduli[1],
                                                           self.moduli[2])
 
-    def _frames_table(self, what, positions, charges, box_vectors, offsets):
+    def _frames_table(self, what, positions, charges, box_vectors, offsets, box_gradient=False):
         """The checks both frames methods share, and the device table of ``offsets`` (made once per distinct offsets and device)."""
         if self.twice_differentiable:
             raise RuntimeError(f"{what}: second derivatives over frames are not available; use a PME object without "
@@ -194,36 +196,43 @@ class PME:
             self._frames_checked = offsets
         if not (positions.is_cuda and charges.is_cuda and box_vectors.is_cuda):
             raise ValueError(f'{what}: positions, charges and box_vectors must be on the GPU (the frames methods have no CPU path)')
-        if box_vectors.requires_grad and torch.is_grad_enabled():
-            raise RuntimeError(f'{what}: box gradients over frames are not available; pass box_vectors that do not require a gradient')
+        if box_vectors.requires_grad and torch.is_grad_enabled() and not box_gradient:
+            raise RuntimeError(f'{what}: box gradients over frames are an opt-in; pass box_gradient=True, or box_vectors that do not '
+                               'require a gradient')
         if self._frames is None or self._frames[0] != offsets or self._frames[1] != positions.device:
             table = torch.ops.pme.pmeFramesTable(torch.tensor(offsets, dtype=torch.int64), positions.device)
             self._frames = (offsets, positions.device, table, table[4:4 + len(offsets)].to(torch.int64))
         return self._frames[2]
 
-    def compute_direct_frames(self, positions: torch.Tensor, charges: torch.Tensor, cutoff: float, box_vectors: torch.Tensor, offsets):
+    def compute_direct_frames(self, positions: torch.Tensor, charges: torch.Tensor, cutoff: float, box_vectors: torch.Tensor, offsets,
+                              box_gradient: bool = False):
         """Direct-space energies [B] of a batch of frames: atoms [offsets[m], offsets[m+1]) are frame m, seen through the minimum image
         of box_vectors[m] (every box at least two cutoffs wide) and never paired with another frame's atoms.  Differentiable with
-        respect to positions and charges (first order).  Every frame is scanned all-pairs: for frames of up to a few hundred atoms."""
-        table = self._frames_table('compute_direct_frames', positions, charges, box_vectors, offsets)
+        respect to positions and charges (first order) and, with ``box_gradient=True``, box_vectors: ``box_vectors.grad[m]`` is
+        dE_m/dB_m times frame m's upstream gradient, positions held fixed as passed.  Every frame is scanned all-pairs:
+        for frames of up to a few hundred atoms."""
+        table = self._frames_table('compute_direct_frames', positions, charges, box_vectors, offsets, box_gradient)
         if cutoff <= 0:
             raise ValueError('cutoff must be positive')
         self.exclusions = self.exclusions.to(positions.device)
-        return torch.ops.pme.pme_direct_frames(positions, charges, self.exclusions, box_vectors, table, cutoff, self.alpha, self.coulomb)
+        op = torch.ops.pme.pme_direct_frames_box if box_gradient else torch.ops.pme.pme_direct_frames
+        return op(positions, charges, self.exclusions, box_vectors, table, cutoff, self.alpha, self.coulomb)
 
-    def compute_reciprocal_frames(self, positions: torch.Tensor, charges: torch.Tensor, box_vectors: torch.Tensor, offsets):
+    def compute_reciprocal_frames(self, positions: torch.Tensor, charges: torch.Tensor, box_vectors: torch.Tensor, offsets,
+                                  box_gradient: bool = False):
         """Reciprocal-space energies [B] of a batch of frames, each frame's self energy included; needs ``PME(..., reciprocal=True)``
         and order 4 or 5.  The grid, order, alpha and coulomb are the object's, the same for all frames.  Differentiable with respect
-        to positions and charges (first order)."""
+        to positions and charges (first order) and, with ``box_gradient=True``, box_vectors (the self energy does not depend on the
+        box)."""
         if not self.reciprocal:
             raise RuntimeError("the reciprocal-space term of PME is not enabled on this object: construct it with PME(..., reciprocal=True)")
         if self.order not in (4, 5):
             raise ValueError(f'compute_reciprocal_frames: only order 4 or 5 is supported (got {self.order})')
-        table = self._frames_table('compute_reciprocal_frames', positions, charges, box_vectors, offsets)
+        table = self._frames_table('compute_reciprocal_frames', positions, charges, box_vectors, offsets, box_gradient)
         for i in range(3):
             self.moduli[i] = self.moduli[i].to(positions.device)
         # (one lane per frame adds its atoms in order: deterministic, and a frame's sum does not depend on the batch around it)
         self_energy = torch.segment_reduce(charges ** 2, 'sum', offsets=self._frames[3], unsafe=True) * (-self.coulomb * self.alpha / math.sqrt(math.pi))
-        return self_energy + torch.ops.pme.pme_reciprocal_frames(positions, charges, box_vectors, table, self.gridx, self.gridy, self.gridz,
-                                                                 self.order, self.alpha, self.coulomb, self.moduli[0], self.moduli[1],
-                                                                 self.moduli[2])
+        op = torch.ops.pme.pme_reciprocal_frames_box if box_gradient else torch.ops.pme.pme_reciprocal_frames
+        return self_energy + op(positions, charges, box_vectors, table, self.gridx, self.gridy, self.gridz, self.order, self.alpha,
+                                self.coulomb, self.moduli[0], self.moduli[1], self.moduli[2])

@@ -3,7 +3,9 @@ charges), of B frames of a 192-atom water box, every frame in its own box (an NP
 interleaved round by round; stream time, medians.  The repository's benchmarks hold no PME configuration for such a box: cutoff 5 A,
 alpha 0.6 / A, a 24^3 grid, order 5.
 
-    python tools/pme_frames_time.py [--frames 8 64 256] [--rounds 7] [--batched-only]      (--batched-only: for a kernel profile)"""
+    python tools/pme_frames_time.py [--frames 8 64 256] [--rounds 7] [--batched-only]      (--batched-only: for a kernel profile)
+    python tools/pme_frames_time.py --box ...       the box gradient as well (box_gradient=True) against the loop of single-frame calls
+                                                    with a box that requires a gradient, and against the batch without box gradient"""
 import argparse
 import os
 import sys
@@ -52,42 +54,54 @@ def main():
     ap.add_argument("--frames", type=int, nargs="+", default=[8, 64, 256])
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--batched-only", action="store_true")
+    ap.add_argument("--box", action="store_true")
     args = ap.parse_args()
     print(f"PME over frames: {N}-atom water boxes, cutoff {CUTOFF}, alpha {ALPHA}, grid {GRID}^3, order {ORDER}; forward + backward, stream time, "
           f"medians of {args.rounds} interleaved rounds (spread = max - min)")
-    print(f"  {'B':>4s} {'term':>11s} {'batched us':>11s} {'(spread)':>9s} {'loop us':>10s} {'(spread)':>9s} {'loop / batched':>15s}")
+    print(f"  {'B':>4s} {'term':>11s} {'batched us':>11s} {'(spread)':>9s} {'loop us':>10s} {'(spread)':>9s} {'loop / batched':>15s}" +
+          (f" {'no box us':>10s} {'(spread)':>9s} {'batched / no box':>17s}" if args.box else ""))
     for B in args.frames:
         host_pos, host_q, host_boxes, excl = water_frames(B)
         offsets = [m * N for m in range(B + 1)]
         pos, q = torch.tensor(host_pos, device=dev).requires_grad_(), torch.tensor(host_q, device=dev).requires_grad_()
         boxes = torch.tensor(host_boxes, device=dev)
+        gboxes = boxes.clone().requires_grad_()                  # --box: the batch's boxes as a leaf
         pme = PME(GRID, GRID, GRID, ORDER, ALPHA, COULOMB, torch.tensor(excl), reciprocal=True)
         one = PME(GRID, GRID, GRID, ORDER, ALPHA, COULOMB, torch.tensor(excl[:N]), reciprocal=True)
-        parts = [(pos.detach()[m * N:(m + 1) * N].clone().requires_grad_(), q.detach()[m * N:(m + 1) * N].clone().requires_grad_(), boxes[m].clone())
-                 for m in range(B)]
+        parts = [(pos.detach()[m * N:(m + 1) * N].clone().requires_grad_(), q.detach()[m * N:(m + 1) * N].clone().requires_grad_(),
+                  boxes[m].clone().requires_grad_(args.box)) for m in range(B)]
         terms = {
             "direct": (lambda: pme.compute_direct_frames(pos, q, CUTOFF, boxes, offsets), lambda p, c, b: one.compute_direct(p, c, CUTOFF, b)),
             "reciprocal": (lambda: pme.compute_reciprocal_frames(pos, q, boxes, offsets), lambda p, c, b: one.compute_reciprocal(p, c, b)),
         }
+        box_terms = {
+            "direct": lambda: pme.compute_direct_frames(pos, q, CUTOFF, gboxes, offsets, box_gradient=True),
+            "reciprocal": lambda: pme.compute_reciprocal_frames(pos, q, gboxes, offsets, box_gradient=True),
+        }
         for name, (frames_energy, single_energy) in terms.items():
-            def batched():
+            def no_box():
                 return torch.autograd.grad(frames_energy().sum(), (pos, q))
 
-            def loop():
-                return [torch.autograd.grad(single_energy(p, c, b), (p, c)) for p, c, b in parts]
+            def with_box():
+                return torch.autograd.grad(box_terms[name]().sum(), (pos, q, gboxes))
 
+            def loop():
+                return [torch.autograd.grad(single_energy(p, c, b), (p, c, b) if args.box else (p, c)) for p, c, b in parts]
+
+            batched = with_box if args.box else no_box
             gb, gl = batched(), loop()                      # the two sides must agree before they are timed
-            for k in range(2):
-                joined = torch.cat([g[k] for g in gl])
-                assert float((joined - gb[k]).abs().max()) <= 1e-4 * float(gb[k].abs().max()), name
+            for k in range(len(gb)):
+                joined = (torch.stack if k == 2 else torch.cat)([g[k] for g in gl])
+                assert float((joined - gb[k]).abs().max()) <= 1e-4 * float(gb[k].abs().max()), (name, k)
             reps_b, reps_l = max(20, min(200, 4096 // B)), max(3, min(30, 512 // B))
             if args.batched_only:
                 timed(batched, reps_b)
                 continue
-            rounds = [(timed(batched, reps_b), timed(loop, reps_l)) for _ in range(args.rounds)]
-            tb, tl = np.array(rounds).T
-            mb, ml = float(np.median(tb)), float(np.median(tl))
-            print(f"  {B:4d} {name:>11s} {mb:11.1f} {tb.max() - tb.min():9.1f} {ml:10.1f} {tl.max() - tl.min():9.1f} {ml / mb:15.1f}", flush=True)
+            rounds = [(timed(batched, reps_b), timed(loop, reps_l), timed(no_box, reps_b) if args.box else 0.0) for _ in range(args.rounds)]
+            tb, tl, tn = np.array(rounds).T
+            mb, ml, mn = float(np.median(tb)), float(np.median(tl)), float(np.median(tn))
+            print(f"  {B:4d} {name:>11s} {mb:11.1f} {tb.max() - tb.min():9.1f} {ml:10.1f} {tl.max() - tl.min():9.1f} {ml / mb:15.1f}" +
+                  (f" {mn:10.1f} {tn.max() - tn.min():9.1f} {mb / mn:17.2f}" if args.box else ""), flush=True)
 
 
 if __name__ == "__main__":
