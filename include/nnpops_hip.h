@@ -719,6 +719,43 @@ int nnpops_pme_reciprocal_frames_box_pi(int num_atoms, int num_frames, int gridx
 int nnpops_pme_reciprocal_frames_box_gradient(int num_atoms, int num_frames, int gridx, int gridy, int gridz, int order,
                                               const int32_t* table, const float* positions, const float* position_deriv,
                                               const float* box_vectors, float* box_deriv, void* box_workspace, void* stream);
+/* Second derivatives over frames with respect to positions and charges (pme_frames_second_order.hip; the formulae are
+ * those of nnpops_pme_direct_double_backward / nnpops_pme_reciprocal_spread_directional with every frame in its own box).  v [N][3] and
+ * w [N] are the cotangents of the first backward's two outputs, upstream [B] (float32) the energies' upstream gradient g:
+ *     L = sum_m g_m sum_{i in m} (v_i . P_i + w_i C_i),   P = dE/dpositions, C = dE/dcharges (unscaled).
+ * grad_positions [N][3] = dL/dx and grad_charges [N] = dL/dq are fully written, already multiplied by g_m; a frame with g_m = 0 gets
+ * exact zeros.  Float64 sums in a fixed order, no atomics; a frame's rows do not depend on the batch around it.  Box second
+ * derivatives are not computed.
+ *   nnpops_pme_direct_frames_double_backward: the arguments and the work split of nnpops_pme_direct_frames (one workgroup per tile, the
+ *     frame's positions, charges, v and w staged in LDS up to 1 024 atoms); every pair is evaluated by both its atoms from the same float
+ *     values.  The pass needs no scratch memory: workspace is any valid pointer, nnpops_pme_direct_frames_double_backward_workspace_bytes
+ *     (T) bytes (the alignment slack only).
+ *   nnpops_pme_reciprocal_frames_spread_directional: after one evaluation's nnpops_pme_reciprocal_frames_spread, whose `workspace` it
+ *     reads (base indices and weights; positions and boxes must be the same); fills real_grids [B][gx][gy][gz] with Q' = sum_i [w_i W_i +
+ *     q_i (v_i . grad) W_i] and second_workspace (nnpops_pme_reciprocal_frames_second_workspace_bytes bytes) with the double weights.
+ *     Then the caller's rfftn, nnpops_pme_reciprocal_frames_convolve on Q' (its energies are of no use), and the inverse transforms of
+ *     both scaled grids (in double, rounded to float once: the interpolation differences them twice).
+ *   nnpops_pme_reciprocal_frames_interpolate_second: potential_grids = phi (of the forward's scaled grids), directional_grids = phi'.
+ *   nnpops_pme_frames_upstream_grad: grad_upstream [B] = dL/dg_m = sum_{i in m} (v_i . P_i + w_i C_i) from the saved first-order outputs
+ *     position_deriv, charge_deriv (unscaled), one wave per frame.
+ * No entry allocates or synchronises: graph-capturable. */
+int64_t nnpops_pme_direct_frames_double_backward_workspace_bytes(int num_tiles);
+int nnpops_pme_direct_frames_double_backward(int num_atoms, int num_frames, int num_tiles, int max_exclusions, const int32_t* table,
+                                             const float* positions, const float* charges, const int32_t* exclusions, const float* box_vectors,
+                                             const float* v, const float* w, const float* upstream, float cutoff, float alpha, float coulomb,
+                                             float* grad_positions, float* grad_charges, void* workspace, void* stream);
+int nnpops_pme_frames_upstream_grad(int num_atoms, int num_frames, const int32_t* table, const float* v, const float* w,
+                                    const float* position_deriv, const float* charge_deriv, float* grad_upstream, void* stream);
+int64_t nnpops_pme_reciprocal_frames_second_workspace_bytes(int num_atoms, int num_frames, int gridx, int gridy, int gridz, int order);
+int nnpops_pme_reciprocal_frames_spread_directional(int num_atoms, int num_frames, int num_tiles, int gridx, int gridy, int gridz, int order,
+                                                    const int32_t* table, const float* positions, const float* charges,
+                                                    const float* box_vectors, float coulomb, const float* v, const float* w,
+                                                    float* real_grids, const void* workspace, void* second_workspace, void* stream);
+int nnpops_pme_reciprocal_frames_interpolate_second(int num_atoms, int num_frames, int gridx, int gridy, int gridz, int order,
+                                                    const float* charges, const float* box_vectors, float coulomb, const float* w,
+                                                    const float* upstream, const float* potential_grids, const float* directional_grids,
+                                                    float* grad_positions, float* grad_charges, const void* workspace,
+                                                    void* second_workspace, void* stream);
 
 /* ---- dense layers of the ANI atomic networks (reference src/pytorch/BatchedNN.cpp:30-50, BatchedNN.py:37-122) ----
  * C[M x N] = A[M x K] B with fp32 in and out; the products run on the half-precision matrix instruction with every

@@ -167,6 +167,13 @@ SIGNATURES = {
                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_pme_reciprocal_frames_box_gradient": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nnpops_pme_direct_frames_double_backward_workspace_bytes": (C.c_int64, [C.c_int]),
+    "nnpops_pme_direct_frames_double_backward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8 +
+                                                 [C.c_float, C.c_float, C.c_float] + [C.c_void_p] * 4),
+    "nnpops_pme_frames_upstream_grad": (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 7),
+    "nnpops_pme_reciprocal_frames_second_workspace_bytes": (C.c_int64, [C.c_int] * 6),
+    "nnpops_pme_reciprocal_frames_spread_directional": (C.c_int, [C.c_int] * 7 + [C.c_void_p] * 4 + [C.c_float] + [C.c_void_p] * 6),
+    "nnpops_pme_reciprocal_frames_interpolate_second": (C.c_int, [C.c_int] * 6 + [C.c_void_p] * 2 + [C.c_float] + [C.c_void_p] * 9),
     "nnpops_neighbor_pairs_backward": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_neighbor_pairs_backward_workspace_bytes": (C.c_int64, [C.c_int]),

@@ -3454,8 +3454,9 @@ class PmeDirectFramesFunction : public torch::autograd::Function<PmeDirectFrames
 public:
     static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& exclusions,
                           const Tensor& box_vectors, const Tensor& table, const torch::Scalar& cutoff, const torch::Scalar& alpha,
-                          const torch::Scalar& coulomb, bool box_op, bool box_grad) {
-        const char* op = box_op ? "pme_direct_frames_box" : "pme_direct_frames";
+                          const torch::Scalar& coulomb, bool box_op, bool box_grad, tensor_list* kept = nullptr) {
+        // kept: the _twice op runs this forward and saves for itself (exclusions, boxes, dE/dpositions, dE/dcharges)
+        const char* op = kept ? "pme_direct_frames_twice" : box_op ? "pme_direct_frames_box" : "pme_direct_frames";
         const std::string qualified = std::string("pme::") + op;
         ctx->saved_data["box_op"] = box_op;
         const PmeFramesShape s = pme_frames_check(op, positions, charges, box_vectors, table, box_op);
@@ -3483,6 +3484,8 @@ public:
                                              box_deriv.data_ptr<float>(), box_workspace.data_ptr(), current_stream(positions.device())) != NNPOPS_OK)
                 raise_last(qualified.c_str());
             ctx->save_for_backward({pos_deriv, charge_deriv, table, box_deriv});
+        } else if (kept) {
+            *kept = {ex, boxes, pos_deriv, charge_deriv};
         } else {
             ctx->save_for_backward({pos_deriv, charge_deriv, table});
         }
@@ -3500,8 +3503,10 @@ public:
     static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table,
                           const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz, const torch::Scalar& order,
                           const torch::Scalar& alpha, const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli,
-                          const Tensor& zmoduli, bool box_op, bool box_grad) {
-        const char* op = box_op ? "pme_reciprocal_frames_box" : "pme_reciprocal_frames";
+                          const Tensor& zmoduli, bool box_op, bool box_grad, tensor_list* kept = nullptr) {
+        // kept: the _twice op runs this forward and saves for itself (boxes, the workspace with the base indices and weights, the scaled
+        // complex grids, the moduli, dE/dpositions, dE/dcharges)
+        const char* op = kept ? "pme_reciprocal_frames_twice" : box_op ? "pme_reciprocal_frames_box" : "pme_reciprocal_frames";
         const std::string qualified = std::string("pme::") + op;
         ctx->saved_data["box_op"] = box_op;
         const PmeFramesShape s = pme_frames_check(op, positions, charges, box_vectors, table, box_op);
@@ -3560,6 +3565,8 @@ public:
                                                               box_workspace.data_ptr(), stream) != NNPOPS_OK)
                     raise_last(qualified.c_str());
                 ctx->save_for_backward({pos_deriv, charge_deriv, table, box_deriv});
+            } else if (kept) {
+                *kept = {boxes, workspace, recip, xm, ym, zm, pos_deriv, charge_deriv};
             } else {
                 ctx->save_for_backward({pos_deriv, charge_deriv, table});
             }
@@ -3597,8 +3604,226 @@ Tensor pme_reciprocal_frames_box_entry(const Tensor& positions, const Tensor& ch
     return PmeReciprocalFramesFunction::apply(positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha, coulomb, xmoduli,
                                               ymoduli, zmoduli, true, box_vectors.requires_grad() && torch::GradMode::is_enabled());
 }
+// ---------------------------------------------------------------------------------------------
+// pme_direct_frames_twice / pme_reciprocal_frames_twice: the forwards above, unchanged (energies, dE/dpositions and dE/dcharges are the
+// bits of pme_direct_frames / pme_reciprocal_frames), with a RECORDED backward that can be differentiated once more with respect to
+// positions and charges (pme_frames_second_order.hip):
+//     Pme*FramesBackwardFunction        g [B] -> g_m P, g_m C through pme_frames_scale, as the default ops' backward
+//     Pme*FramesDoubleBackwardFunction  (v, w) -> dL/dx [N, 3], dL/dq [N] (already times g_m), dL/dg [B]
+// No box gradient and no third derivative: both raise.
+// ---------------------------------------------------------------------------------------------
+int64_t pme_frames_tiles(const Tensor& table, int64_t frames, int64_t atoms) { return (table.numel() - 4 - 2 * (frames + 1) - atoms) / 4; }
+
+// a cotangent as the kernels read it: float32, contiguous, zeros when autograd passed none
+Tensor pme_frames_cotangent(const Tensor& t, const Tensor& like) {
+    return t.defined() ? t.to(torch::kFloat32).contiguous() : torch::zeros_like(like);
+}
+
+Tensor pme_frames_upstream_grad(const char* op, const Tensor& v, const Tensor& w, const Tensor& pos_deriv, const Tensor& charge_deriv,
+                                const Tensor& table, const Tensor& g) {
+    Tensor gg = torch::empty({g.numel()}, pos_deriv.options());
+    if (nnpops_pme_frames_upstream_grad((int)charge_deriv.size(0), (int)g.numel(), table.data_ptr<int32_t>(), v.data_ptr<float>(),
+                                        w.data_ptr<float>(), pos_deriv.data_ptr<float>(), charge_deriv.data_ptr<float>(), gg.data_ptr<float>(),
+                                        current_stream(pos_deriv.device())) != NNPOPS_OK)
+        raise_last(op);
+    return gg.reshape(g.sizes()).to(g.scalar_type());
+}
+
+class PmeDirectFramesDoubleBackwardFunction : public torch::autograd::Function<PmeDirectFramesDoubleBackwardFunction> {
+public:
+    static tensor_list forward(AutogradContext*, const Tensor& v_in, const Tensor& w_in, const Tensor& g_in, const Tensor& positions,
+                               const Tensor& charges, const Tensor& ex, const Tensor& boxes, const Tensor& table, const Tensor& pos_deriv,
+                               const Tensor& charge_deriv, double cutoff, double alpha, double k) {
+        const char* op = "pme::pme_direct_frames_twice (double backward)";
+        const Tensor v = pme_frames_cotangent(v_in, pos_deriv), w = pme_frames_cotangent(w_in, charge_deriv);
+        const Tensor g = g_in.to(torch::kFloat32).contiguous(), pos = positions.contiguous(), q = charges.contiguous();
+        const int64_t n = q.size(0), frames = boxes.size(0), tiles = pme_frames_tiles(table, frames, n), max_excl = ex.size(1);
+        Tensor gx = torch::empty({n, 3}, q.options()), gq = torch::empty({n}, q.options());
+        Tensor workspace = torch::empty({nnpops_pme_direct_frames_double_backward_workspace_bytes((int)tiles)}, q.options().dtype(torch::kUInt8));
+        c10::hip::HIPGuard guard(q.device().index());
+        if (nnpops_pme_direct_frames_double_backward((int)n, (int)frames, (int)tiles, (int)max_excl, table.data_ptr<int32_t>(), pos.data_ptr<float>(),
+                                                     q.data_ptr<float>(), max_excl ? ex.data_ptr<int32_t>() : nullptr, boxes.data_ptr<float>(),
+                                                     v.data_ptr<float>(), w.data_ptr<float>(), g.data_ptr<float>(), (float)cutoff, (float)alpha,
+                                                     (float)k, gx.data_ptr<float>(), gq.data_ptr<float>(), workspace.data_ptr(),
+                                                     current_stream(q.device())) != NNPOPS_OK)
+            raise_last(op);
+        return {gx, gq, pme_frames_upstream_grad(op, v, w, pos_deriv, charge_deriv, table, g_in)};
+    }
+    static tensor_list backward(AutogradContext*, tensor_list) {
+        TORCH_CHECK(false, "pme_direct_frames_twice: third derivatives are not implemented");
+        return {};
+    }
+};
+
+class PmeDirectFramesBackwardFunction : public torch::autograd::Function<PmeDirectFramesBackwardFunction> {
+public:
+    static tensor_list forward(AutogradContext* ctx, const Tensor& g, const Tensor& positions, const Tensor& charges, const Tensor& ex,
+                               const Tensor& boxes, const Tensor& table, const Tensor& pos_deriv, const Tensor& charge_deriv, double cutoff,
+                               double alpha, double k) {
+        ctx->save_for_backward({g, positions, charges, ex, boxes, table, pos_deriv, charge_deriv});
+        ctx->saved_data["cutoff"] = cutoff;
+        ctx->saved_data["alpha"] = alpha;
+        ctx->saved_data["coulomb"] = k;
+        return pme_frames_scale("pme_direct_frames_twice", pos_deriv, charge_deriv, table, g);
+    }
+    static tensor_list backward(AutogradContext* ctx, tensor_list grads) {
+        const auto s = ctx->get_saved_variables();
+        const tensor_list d = PmeDirectFramesDoubleBackwardFunction::apply(grads[0], grads[1], s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7],
+                                                                           ctx->saved_data["cutoff"].toDouble(), ctx->saved_data["alpha"].toDouble(),
+                                                                           ctx->saved_data["coulomb"].toDouble());
+        return {d[2], d[0], d[1], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+    }
+};
+
+class PmeDirectFramesTwiceFunction : public torch::autograd::Function<PmeDirectFramesTwiceFunction> {
+public:
+    static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& exclusions,
+                          const Tensor& box_vectors, const Tensor& table, const torch::Scalar& cutoff, const torch::Scalar& alpha,
+                          const torch::Scalar& coulomb) {
+        tensor_list kept;
+        const Tensor energies = PmeDirectFramesFunction::forward(ctx, positions, charges, exclusions, box_vectors, table, cutoff, alpha, coulomb,
+                                                                 false, false, &kept);
+        ctx->save_for_backward({positions, charges, kept[0], kept[1], table, kept[2], kept[3]});
+        ctx->saved_data["cutoff"] = cutoff.toDouble();
+        ctx->saved_data["alpha"] = alpha.toDouble();
+        ctx->saved_data["coulomb"] = coulomb.toDouble();
+        return energies;
+    }
+    static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) {
+        const auto s = ctx->get_saved_variables();
+        const tensor_list d = PmeDirectFramesBackwardFunction::apply(grad_outputs[0], s[0], s[1], s[2], s[3], s[4], s[5], s[6],
+                                                                     ctx->saved_data["cutoff"].toDouble(), ctx->saved_data["alpha"].toDouble(),
+                                                                     ctx->saved_data["coulomb"].toDouble());
+        return {d[0], d[1], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+    }
+};
+
+class PmeRecipFramesDoubleBackwardFunction : public torch::autograd::Function<PmeRecipFramesDoubleBackwardFunction> {
+public:
+    static tensor_list forward(AutogradContext*, const Tensor& v_in, const Tensor& w_in, const Tensor& g_in, const Tensor& positions,
+                               const Tensor& charges, const Tensor& boxes, const Tensor& table, const Tensor& workspace, const Tensor& recip,
+                               const Tensor& xm, const Tensor& ym, const Tensor& zm, const Tensor& pos_deriv, const Tensor& charge_deriv,
+                               std::vector<int64_t> K, int64_t pme_order, double alpha, double k) {
+        const char* op = "pme::pme_reciprocal_frames_twice (double backward)";
+        const Tensor v = pme_frames_cotangent(v_in, pos_deriv), w = pme_frames_cotangent(w_in, charge_deriv);
+        const Tensor g = g_in.to(torch::kFloat32).contiguous(), pos = positions.contiguous(), q = charges.contiguous();
+        const int n = (int)q.size(0), B = (int)boxes.size(0), tiles = (int)pme_frames_tiles(table, B, n);
+        const int gx = (int)K[0], gy = (int)K[1], gz = (int)K[2], o = (int)pme_order;
+        const auto opts = q.options();
+        Tensor grad_x = torch::empty({n, 3}, opts), grad_q = torch::empty({n}, opts);
+        c10::hip::HIPGuard guard(q.device().index());
+        void* stream = current_stream(q.device());
+        const int64_t bytes = nnpops_pme_reciprocal_frames_second_workspace_bytes(n, B, gx, gy, gz, o);
+        if (bytes <= 0) raise_last(op);
+        Tensor second = torch::empty({bytes}, opts.dtype(torch::kUInt8));
+        Tensor real = torch::empty({(int64_t)B, K[0], K[1], K[2]}, opts);
+        if (nnpops_pme_reciprocal_frames_spread_directional(n, B, tiles, gx, gy, gz, o, table.data_ptr<int32_t>(), pos.data_ptr<float>(),
+                                                            q.data_ptr<float>(), boxes.data_ptr<float>(), (float)k, v.data_ptr<float>(),
+                                                            w.data_ptr<float>(), real.data_ptr<float>(), workspace.data_ptr(), second.data_ptr(),
+                                                            stream) != NNPOPS_OK)
+            raise_last(op);
+        const std::vector<int64_t> dims{1, 2, 3};
+        Tensor recip2 = torch::fft::rfftn(real, c10::nullopt, torch::IntArrayRef(dims)).contiguous();
+        Tensor unused = torch::empty({(int64_t)B}, opts);
+        // (the convolution's partial sums share the forward's workspace; the base indices and weights behind them stay)
+        if (nnpops_pme_reciprocal_frames_convolve(n, B, gx, gy, gz, o, boxes.data_ptr<float>(), (float)alpha, xm.data_ptr<float>(),
+                                                  ym.data_ptr<float>(), zm.data_ptr<float>(), recip2.data_ptr(), unused.data_ptr<float>(),
+                                                  workspace.data_ptr(), stream) != NNPOPS_OK)
+            raise_last(op);
+        // Both potential grids are transformed back in double and rounded to float once: the interpolation differences them twice, and
+        // the float transform's error grew there with the square of the grid size.
+        auto back = [&](const Tensor& c) {
+            return torch::fft::irfftn(c.to(torch::kComplexDouble), torch::IntArrayRef(K), torch::IntArrayRef(dims), "forward").to(torch::kFloat).contiguous();
+        };
+        const Tensor phi = back(recip), phi2 = back(recip2);
+        if (nnpops_pme_reciprocal_frames_interpolate_second(n, B, gx, gy, gz, o, q.data_ptr<float>(), boxes.data_ptr<float>(), (float)k,
+                                                            w.data_ptr<float>(), g.data_ptr<float>(), phi.data_ptr<float>(), phi2.data_ptr<float>(),
+                                                            grad_x.data_ptr<float>(), grad_q.data_ptr<float>(), workspace.data_ptr(),
+                                                            second.data_ptr(), stream) != NNPOPS_OK)
+            raise_last(op);
+        return {grad_x, grad_q, pme_frames_upstream_grad(op, v, w, pos_deriv, charge_deriv, table, g_in)};
+    }
+    static tensor_list backward(AutogradContext*, tensor_list) {
+        TORCH_CHECK(false, "pme_reciprocal_frames_twice: third derivatives are not implemented");
+        return {};
+    }
+};
+
+class PmeRecipFramesBackwardFunction : public torch::autograd::Function<PmeRecipFramesBackwardFunction> {
+public:
+    static tensor_list forward(AutogradContext* ctx, const Tensor& g, const Tensor& positions, const Tensor& charges, const Tensor& boxes,
+                               const Tensor& table, const Tensor& workspace, const Tensor& recip, const Tensor& xm, const Tensor& ym,
+                               const Tensor& zm, const Tensor& pos_deriv, const Tensor& charge_deriv, std::vector<int64_t> K, int64_t pme_order,
+                               double alpha, double k) {
+        ctx->save_for_backward({g, positions, charges, boxes, table, workspace, recip, xm, ym, zm, pos_deriv, charge_deriv});
+        ctx->saved_data["grid"] = K;
+        ctx->saved_data["order"] = pme_order;
+        ctx->saved_data["alpha"] = alpha;
+        ctx->saved_data["coulomb"] = k;
+        return pme_frames_scale("pme_reciprocal_frames_twice", pos_deriv, charge_deriv, table, g);
+    }
+    static tensor_list backward(AutogradContext* ctx, tensor_list grads) {
+        const auto s = ctx->get_saved_variables();
+        const tensor_list d = PmeRecipFramesDoubleBackwardFunction::apply(grads[0], grads[1], s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], s[8],
+                                                                          s[9], s[10], s[11], ctx->saved_data["grid"].toIntVector(),
+                                                                          ctx->saved_data["order"].toInt(), ctx->saved_data["alpha"].toDouble(),
+                                                                          ctx->saved_data["coulomb"].toDouble());
+        return {d[2], d[0], d[1], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(),
+                Tensor(), Tensor()};
+    }
+};
+
+class PmeReciprocalFramesTwiceFunction : public torch::autograd::Function<PmeReciprocalFramesTwiceFunction> {
+public:
+    static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table,
+                          const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz, const torch::Scalar& order,
+                          const torch::Scalar& alpha, const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli,
+                          const Tensor& zmoduli) {
+        tensor_list kept;
+        const Tensor energies = PmeReciprocalFramesFunction::forward(ctx, positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha,
+                                                                     coulomb, xmoduli, ymoduli, zmoduli, false, false, &kept);
+        if (!kept.empty())                                          // (positions or charges require a gradient)
+            ctx->save_for_backward({positions, charges, kept[0], table, kept[1], kept[2], kept[3], kept[4], kept[5], kept[6], kept[7]});
+        ctx->saved_data["grid"] = std::vector<int64_t>{gridx.toLong(), gridy.toLong(), gridz.toLong()};
+        ctx->saved_data["order"] = order.toLong();
+        ctx->saved_data["alpha"] = alpha.toDouble();
+        ctx->saved_data["coulomb"] = coulomb.toDouble();
+        return energies;
+    }
+    static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) {
+        const auto s = ctx->get_saved_variables();
+        const tensor_list d = PmeRecipFramesBackwardFunction::apply(grad_outputs[0], s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], s[8], s[9], s[10],
+                                                                    ctx->saved_data["grid"].toIntVector(), ctx->saved_data["order"].toInt(),
+                                                                    ctx->saved_data["alpha"].toDouble(), ctx->saved_data["coulomb"].toDouble());
+        return {d[0], d[1], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+    }
+};
+
+// (a Function's forward runs with grad mode off: what depends on it is checked here)
+void pme_frames_twice_check_box(const char* op, const Tensor& box_vectors) {
+    TORCH_CHECK(!(box_vectors.requires_grad() && torch::GradMode::is_enabled()), op,
+                ": second derivatives that involve the box are not implemented (pass box_vectors that do not require a gradient)");
+}
+Tensor pme_direct_frames_twice_entry(const Tensor& positions, const Tensor& charges, const Tensor& exclusions, const Tensor& box_vectors,
+                                     const Tensor& table, const torch::Scalar& cutoff, const torch::Scalar& alpha, const torch::Scalar& coulomb) {
+    pme_frames_twice_check_box("pme_direct_frames_twice", box_vectors);
+    return PmeDirectFramesTwiceFunction::apply(positions, charges, exclusions, box_vectors, table, cutoff, alpha, coulomb);
+}
+Tensor pme_reciprocal_frames_twice_entry(const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table,
+                                         const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz,
+                                         const torch::Scalar& order, const torch::Scalar& alpha, const torch::Scalar& coulomb,
+                                         const Tensor& xmoduli, const Tensor& ymoduli, const Tensor& zmoduli) {
+    pme_frames_twice_check_box("pme_reciprocal_frames_twice", box_vectors);
+    return PmeReciprocalFramesTwiceFunction::apply(positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha, coulomb, xmoduli,
+                                                   ymoduli, zmoduli);
+}
 TORCH_LIBRARY_FRAGMENT(pme, m) {
     m.def("pmeFramesTable(Tensor offsets, Device device) -> Tensor", pme_frames_table_entry);
+    // the twice-differentiable variants over frames (force loss): the schemas of pme_direct_frames and pme_reciprocal_frames
+    m.def("pme_direct_frames_twice(Tensor positions, Tensor charges, Tensor exclusions, Tensor box_vectors, Tensor table, Scalar cutoff, "
+          "Scalar alpha, Scalar coulomb) -> Tensor");
+    m.def("pme_reciprocal_frames_twice(Tensor positions, Tensor charges, Tensor box_vectors, Tensor table, Scalar gridx, Scalar gridy, "
+          "Scalar gridz, Scalar order, Scalar alpha, Scalar coulomb, Tensor xmoduli, Tensor ymoduli, Tensor zmoduli) -> Tensor");
     m.def("pme_direct_frames(Tensor positions, Tensor charges, Tensor exclusions, Tensor box_vectors, Tensor table, Scalar cutoff, "
           "Scalar alpha, Scalar coulomb) -> Tensor");
     m.def("pme_reciprocal_frames(Tensor positions, Tensor charges, Tensor box_vectors, Tensor table, Scalar gridx, Scalar gridy, "
@@ -3613,12 +3838,16 @@ TORCH_LIBRARY_IMPL(pme, AutogradCUDA, m) {
     m.impl("pme_reciprocal_frames", pme_reciprocal_frames_entry);
     m.impl("pme_direct_frames_box", pme_direct_frames_box_entry);
     m.impl("pme_reciprocal_frames_box", pme_reciprocal_frames_box_entry);
+    m.impl("pme_direct_frames_twice", pme_direct_frames_twice_entry);
+    m.impl("pme_reciprocal_frames_twice", pme_reciprocal_frames_twice_entry);
 }
 TORCH_LIBRARY_IMPL(pme, CUDA, m) {
     m.impl("pme_direct_frames", pme_direct_frames_entry);
     m.impl("pme_reciprocal_frames", pme_reciprocal_frames_entry);
     m.impl("pme_direct_frames_box", pme_direct_frames_box_entry);
     m.impl("pme_reciprocal_frames_box", pme_reciprocal_frames_box_entry);
+    m.impl("pme_direct_frames_twice", pme_direct_frames_twice_entry);
+    m.impl("pme_reciprocal_frames_twice", pme_reciprocal_frames_twice_entry);
 }
 
 // =============================================================================================

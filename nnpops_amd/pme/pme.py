@@ -21,6 +21,8 @@ from ``torch.ops.pme.pme_direct_frames`` / ``pme_reciprocal_frames`` (nnpops_amd
 only, first derivatives with respect to positions and charges.  The box gradient over frames is an opt-in: with
 ``box_gradient=True`` the two methods call ``pme_direct_frames_box`` / ``pme_reciprocal_frames_box`` -- the same forward passes, bit for
 bit -- and ``backward()`` fills ``box_vectors.grad[B, 3, 3]``; the default call still refuses a box that requires a gradient.
+Second derivatives with respect to positions and charges are an opt-in per call as well: ``twice_differentiable=True`` calls
+``pme_direct_frames_twice`` / ``pme_reciprocal_frames_twice`` (nnpops_amd/csrc/pme_frames_second_order.hip).
 """
 import math
 
@@ -51,6 +53,34 @@ def bspline_moduli(size: int, order: int) -> torch.Tensor:
         if mod[k] < 1e-7:
             mod[k] = (mod[(k - 1 + size) % size] + mod[(k + 1) % size]) * 0.5
     return torch.tensor(mod, dtype=torch.float32)
+
+
+class _SumFrames(torch.autograd.Function):
+    """Per-frame sums [B] of per-atom values [N]: ``segment_reduce``'s forward (its bits), with a backward that autograd can
+    differentiate again (``aten::_segment_reduce_backward`` has no derivative).  ``_ExpandFrames`` is its adjoint; the two are linear and
+    each other's backward, so any order of derivative is deterministic: no index_add."""
+
+    @staticmethod
+    def forward(ctx, values, offsets, atom_frame):
+        ctx.frames = (offsets, atom_frame)
+        return torch.segment_reduce(values, 'sum', offsets=offsets, unsafe=True)
+
+    @staticmethod
+    def backward(ctx, grad):
+        return _ExpandFrames.apply(grad, *ctx.frames), None, None
+
+
+class _ExpandFrames(torch.autograd.Function):
+    """Every atom's copy [N] of its frame's value [B]."""
+
+    @staticmethod
+    def forward(ctx, values, offsets, atom_frame):
+        ctx.frames = (offsets, atom_frame)
+        return values.index_select(0, atom_frame)
+
+    @staticmethod
+    def backward(ctx, grad):
+        return _SumFrames.apply(grad.contiguous(), *ctx.frames), None, None
 
 
 _TWICE_BOX_MESSAGE = ("PME(..., twice_differentiable=True): box gradients need the default ops (PME without twice_differentiable); the "
@@ -168,11 +198,14 @@ class PME:
                                                           self.order, self.alpha, self.coulomb, self.moduli[0], self.moduli[1],
                                                           self.moduli[2])
 
-    def _frames_table(self, what, positions, charges, box_vectors, offsets, box_gradient=False):
+    def _frames_table(self, what, positions, charges, box_vectors, offsets, box_gradient=False, twice=False):
         """The checks both frames methods share, and the device table of ``offsets`` (made once per distinct offsets and device)."""
         if self.twice_differentiable:
-            raise RuntimeError(f"{what}: second derivatives over frames are not available; use a PME object without "
+            raise RuntimeError(f"{what}: the frames methods take twice_differentiable=True per call; use a PME object without "
                                "twice_differentiable=True")
+        if twice and box_gradient:
+            raise RuntimeError(f'{what}: twice_differentiable=True cannot be combined with box_gradient=True (second derivatives that '
+                               'involve the box are not implemented)')
         if positions.dim() != 2 or positions.shape[1] != 3:
             raise ValueError('positions must have shape (atoms, 3)')
         if charges.dim() != 1:
@@ -196,6 +229,9 @@ class PME:
             self._frames_checked = offsets
         if not (positions.is_cuda and charges.is_cuda and box_vectors.is_cuda):
             raise ValueError(f'{what}: positions, charges and box_vectors must be on the GPU (the frames methods have no CPU path)')
+        if box_vectors.requires_grad and torch.is_grad_enabled() and twice:
+            raise RuntimeError(f'{what}: twice_differentiable=True returns no box gradient (second derivatives that involve the box are '
+                               'not implemented); pass box_vectors that do not require a gradient')
         if box_vectors.requires_grad and torch.is_grad_enabled() and not box_gradient:
             raise RuntimeError(f'{what}: box gradients over frames are an opt-in; pass box_gradient=True, or box_vectors that do not '
                                'require a gradient')
@@ -205,34 +241,44 @@ class PME:
         return self._frames[2]
 
     def compute_direct_frames(self, positions: torch.Tensor, charges: torch.Tensor, cutoff: float, box_vectors: torch.Tensor, offsets,
-                              box_gradient: bool = False):
+                              box_gradient: bool = False, twice_differentiable: bool = False):
         """Direct-space energies [B] of a batch of frames: atoms [offsets[m], offsets[m+1]) are frame m, seen through the minimum image
         of box_vectors[m] (every box at least two cutoffs wide) and never paired with another frame's atoms.  Differentiable with
         respect to positions and charges (first order) and, with ``box_gradient=True``, box_vectors: ``box_vectors.grad[m]`` is
         dE_m/dB_m times frame m's upstream gradient, positions held fixed as passed.  Every frame is scanned all-pairs:
-        for frames of up to a few hundred atoms."""
-        table = self._frames_table('compute_direct_frames', positions, charges, box_vectors, offsets, box_gradient)
+        for frames of up to a few hundred atoms.
+
+        ``twice_differentiable=True`` (per call, not with ``box_gradient``) calls ``pme_direct_frames_twice``: the same energies and
+        first derivatives, bit for bit, and a backward that can be differentiated again with respect to positions and charges
+        (``create_graph=True``: forces in the loss)."""
+        table = self._frames_table('compute_direct_frames', positions, charges, box_vectors, offsets, box_gradient, twice_differentiable)
         if cutoff <= 0:
             raise ValueError('cutoff must be positive')
         self.exclusions = self.exclusions.to(positions.device)
-        op = torch.ops.pme.pme_direct_frames_box if box_gradient else torch.ops.pme.pme_direct_frames
+        op = torch.ops.pme.pme_direct_frames_twice if twice_differentiable else \
+            torch.ops.pme.pme_direct_frames_box if box_gradient else torch.ops.pme.pme_direct_frames
         return op(positions, charges, self.exclusions, box_vectors, table, cutoff, self.alpha, self.coulomb)
 
     def compute_reciprocal_frames(self, positions: torch.Tensor, charges: torch.Tensor, box_vectors: torch.Tensor, offsets,
-                                  box_gradient: bool = False):
+                                  box_gradient: bool = False, twice_differentiable: bool = False):
         """Reciprocal-space energies [B] of a batch of frames, each frame's self energy included; needs ``PME(..., reciprocal=True)``
         and order 4 or 5.  The grid, order, alpha and coulomb are the object's, the same for all frames.  Differentiable with respect
         to positions and charges (first order) and, with ``box_gradient=True``, box_vectors (the self energy does not depend on the
-        box)."""
+        box).  ``twice_differentiable=True``: as for ``compute_direct_frames``, through ``pme_reciprocal_frames_twice``."""
         if not self.reciprocal:
             raise RuntimeError("the reciprocal-space term of PME is not enabled on this object: construct it with PME(..., reciprocal=True)")
         if self.order not in (4, 5):
             raise ValueError(f'compute_reciprocal_frames: only order 4 or 5 is supported (got {self.order})')
-        table = self._frames_table('compute_reciprocal_frames', positions, charges, box_vectors, offsets, box_gradient)
+        table = self._frames_table('compute_reciprocal_frames', positions, charges, box_vectors, offsets, box_gradient, twice_differentiable)
         for i in range(3):
             self.moduli[i] = self.moduli[i].to(positions.device)
         # (one lane per frame adds its atoms in order: deterministic, and a frame's sum does not depend on the batch around it)
-        self_energy = torch.segment_reduce(charges ** 2, 'sum', offsets=self._frames[3], unsafe=True) * (-self.coulomb * self.alpha / math.sqrt(math.pi))
-        op = torch.ops.pme.pme_reciprocal_frames_box if box_gradient else torch.ops.pme.pme_reciprocal_frames
+        if twice_differentiable:                  # the same sums, with a backward that differentiates again
+            frame_sums = _SumFrames.apply(charges ** 2, self._frames[3], table[table.numel() - charges.shape[0]:].to(torch.int64))
+        else:
+            frame_sums = torch.segment_reduce(charges ** 2, 'sum', offsets=self._frames[3], unsafe=True)
+        self_energy = frame_sums * (-self.coulomb * self.alpha / math.sqrt(math.pi))
+        op = torch.ops.pme.pme_reciprocal_frames_twice if twice_differentiable else \
+            torch.ops.pme.pme_reciprocal_frames_box if box_gradient else torch.ops.pme.pme_reciprocal_frames
         return self_energy + op(positions, charges, box_vectors, table, self.gridx, self.gridy, self.gridz, self.order, self.alpha,
                                 self.coulomb, self.moduli[0], self.moduli[1], self.moduli[2])

@@ -5,7 +5,10 @@ alpha 0.6 / A, a 24^3 grid, order 5.
 
     python tools/pme_frames_time.py [--frames 8 64 256] [--rounds 7] [--batched-only]      (--batched-only: for a kernel profile)
     python tools/pme_frames_time.py --box ...       the box gradient as well (box_gradient=True) against the loop of single-frame calls
-                                                    with a box that requires a gradient, and against the batch without box gradient"""
+                                                    with a box that requires a gradient, and against the batch without box gradient
+    python tools/pme_frames_time.py --twice ...     the force-loss step E -> grad(E, (x, q), create_graph=True) -> |F - F_ref|^2.backward()
+                                                    (twice_differentiable=True per call) against the loop of single-frame steps on a
+                                                    PME(..., twice_differentiable=True) object"""
 import argparse
 import os
 import sys
@@ -49,14 +52,23 @@ def water_frames(B, seed=0):
     return np.concatenate(ps), np.tile(q1, B), np.stack([(box * np.float32(s)).astype(np.float32) for s in scale]), excl
 
 
+def force_loss(energy, x, c, f_ref):
+    """the gradients of |F - F_ref|^2 with respect to positions and charges, F = -dE/dx recorded"""
+    dx = torch.autograd.grad(energy, (x, c), create_graph=True)[0]
+    return torch.autograd.grad(((-dx - f_ref) ** 2).sum(), (x, c))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, nargs="+", default=[8, 64, 256])
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--batched-only", action="store_true")
     ap.add_argument("--box", action="store_true")
+    ap.add_argument("--twice", action="store_true")
     args = ap.parse_args()
-    print(f"PME over frames: {N}-atom water boxes, cutoff {CUTOFF}, alpha {ALPHA}, grid {GRID}^3, order {ORDER}; forward + backward, stream time, "
+    assert not (args.box and args.twice), "--box and --twice are separate measurements"
+    what = "force-loss step" if args.twice else "forward + backward"
+    print(f"PME over frames: {N}-atom water boxes, cutoff {CUTOFF}, alpha {ALPHA}, grid {GRID}^3, order {ORDER}; {what}, stream time, "
           f"medians of {args.rounds} interleaved rounds (spread = max - min)")
     print(f"  {'B':>4s} {'term':>11s} {'batched us':>11s} {'(spread)':>9s} {'loop us':>10s} {'(spread)':>9s} {'loop / batched':>15s}" +
           (f" {'no box us':>10s} {'(spread)':>9s} {'batched / no box':>17s}" if args.box else ""))
@@ -67,12 +79,15 @@ def main():
         boxes = torch.tensor(host_boxes, device=dev)
         gboxes = boxes.clone().requires_grad_()                  # --box: the batch's boxes as a leaf
         pme = PME(GRID, GRID, GRID, ORDER, ALPHA, COULOMB, torch.tensor(excl), reciprocal=True)
-        one = PME(GRID, GRID, GRID, ORDER, ALPHA, COULOMB, torch.tensor(excl[:N]), reciprocal=True)
+        one = PME(GRID, GRID, GRID, ORDER, ALPHA, COULOMB, torch.tensor(excl[:N]), reciprocal=True, twice_differentiable=args.twice)
+        f_ref = torch.randn(B * N, 3, device=dev, generator=torch.Generator(dev).manual_seed(B))
         parts = [(pos.detach()[m * N:(m + 1) * N].clone().requires_grad_(), q.detach()[m * N:(m + 1) * N].clone().requires_grad_(),
                   boxes[m].clone().requires_grad_(args.box)) for m in range(B)]
         terms = {
-            "direct": (lambda: pme.compute_direct_frames(pos, q, CUTOFF, boxes, offsets), lambda p, c, b: one.compute_direct(p, c, CUTOFF, b)),
-            "reciprocal": (lambda: pme.compute_reciprocal_frames(pos, q, boxes, offsets), lambda p, c, b: one.compute_reciprocal(p, c, b)),
+            "direct": (lambda: pme.compute_direct_frames(pos, q, CUTOFF, boxes, offsets, twice_differentiable=args.twice),
+                       lambda p, c, b: one.compute_direct(p, c, CUTOFF, b)),
+            "reciprocal": (lambda: pme.compute_reciprocal_frames(pos, q, boxes, offsets, twice_differentiable=args.twice),
+                           lambda p, c, b: one.compute_reciprocal(p, c, b)),
         }
         box_terms = {
             "direct": lambda: pme.compute_direct_frames(pos, q, CUTOFF, gboxes, offsets, box_gradient=True),
@@ -86,9 +101,14 @@ def main():
                 return torch.autograd.grad(box_terms[name]().sum(), (pos, q, gboxes))
 
             def loop():
+                if args.twice:
+                    return [force_loss(single_energy(p, c, b), p, c, f_ref[m * N:(m + 1) * N]) for m, (p, c, b) in enumerate(parts)]
                 return [torch.autograd.grad(single_energy(p, c, b), (p, c, b) if args.box else (p, c)) for p, c, b in parts]
 
-            batched = with_box if args.box else no_box
+            def twice():
+                return force_loss(frames_energy().sum(), pos, q, f_ref)
+
+            batched = twice if args.twice else with_box if args.box else no_box
             gb, gl = batched(), loop()                      # the two sides must agree before they are timed
             for k in range(len(gb)):
                 joined = (torch.stack if k == 2 else torch.cat)([g[k] for g in gl])
