@@ -812,10 +812,24 @@ def pme_direct_frames(positions, charges, exclusions, box_vectors, table, cutoff
     return energies, pos_deriv, charge_deriv
 
 
-def pme_reciprocal_frames(positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha, coulomb, xmoduli, ymoduli, zmoduli):
-    """Reciprocal-space PME of a batch of frames through the C ABI: spread -> torch.fft.rfftn over the last three dimensions -> convolve
-    -> torch.fft.irfftn(norm="forward") -> interpolate.  -> (energies [B] without the self energy, dE/dpositions [N, 3], dE/dcharges
-    [N]).  Orders 4 and 5."""
+def _frames_rfftn(real):
+    """rfftn of a batch of grids [B, Kx, Ky, Kz] in two steps, real along z and complex over (x, y), as the torch ops take it
+    (torch_binding.cpp: pme_frames_rfftn; the single batched 3-D real transform went wrong after transforms of other shapes)"""
+    return torch.fft.fftn(torch.fft.rfft(real, dim=3), dim=(1, 2)).contiguous()
+
+
+def _frames_irfftn(recip, gridz):
+    return torch.fft.irfft(torch.fft.ifftn(recip, dim=(1, 2), norm="forward"), n=gridz, dim=3, norm="forward")
+
+
+def pme_reciprocal_frames_passes(positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha, coulomb, xmoduli, ymoduli,
+                                 zmoduli, box=False):
+    """pme_reciprocal_frames with every pass's output kept (the frames twin of pme_reciprocal_passes): -> (real grids [B, Kx, Ky, Kz] of
+    the spread, complex grids [B, Kx, Ky, Kz/2 + 1] before scaling, scaled complex grids, potential grids (irfftn, norm="forward"),
+    energies [B], dE/dpositions [N, 3], dE/dcharges [N]) and, with `box`, dE/dbox [B, 3, 3] (box_pi after the convolution, box_gradient
+    after the interpolation).  The real grids start as NaN (the spread writes every point of every frame exactly once and needs no
+    clearing); both workspaces are exactly nnpops_pme_reciprocal_frames[_box]_workspace_bytes long, 256-byte aligned and followed by a
+    guard pattern: a pass that writes past one raises."""
     n, frames = positions.size(0), box_vectors.size(0)
     tiles = (table.numel() - 4 - 2 * (frames + 1) - n) // 4
     dev = positions.device
@@ -823,21 +837,51 @@ def pme_reciprocal_frames(positions, charges, box_vectors, table, gridx, gridy, 
     mods = [m.contiguous() for m in (xmoduli, ymoduli, zmoduli)]
     L = lib()
     dims = (gridx, gridy, gridz, order)
-    ws = torch.empty((int(L.nnpops_pme_reciprocal_frames_workspace_bytes(n, frames, *dims)),), dtype=torch.uint8, device=dev)
-    real = torch.empty((frames, gridx, gridy, gridz), dtype=torch.float32, device=dev)
+
+    def guarded(nbytes):
+        buf = torch.full((nbytes + _PASSES_GUARD + 256,), _PASSES_PATTERN, dtype=torch.uint8, device=dev)
+        off = (-buf.data_ptr()) % 256
+        return buf, off, nbytes, C.c_void_p(buf.data_ptr() + off)
+    sizes = [int(L.nnpops_pme_reciprocal_frames_workspace_bytes(n, frames, *dims))]
+    if box:
+        sizes.append(int(L.nnpops_pme_reciprocal_frames_box_workspace_bytes(frames, gridx, gridy, gridz)))
+    spaces = [guarded(nbytes) for nbytes in sizes]
+    ws = spaces[0][3]
+    real = torch.full((frames, gridx, gridy, gridz), float("nan"), dtype=torch.float32, device=dev)
     energies = torch.empty((frames,), dtype=torch.float32, device=dev)
     pos_deriv = torch.empty((n, 3), dtype=torch.float32, device=dev)
     charge_deriv = torch.empty((n,), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         _check(L.nnpops_pme_reciprocal_frames_spread(n, frames, tiles, *dims, _ptr(table), _ptr(positions), _ptr(charges), _ptr(box_vectors),
-                                                     float(coulomb), _ptr(real), _ptr(ws), _stream_ptr(dev)))
-        recip = torch.fft.rfftn(real, dim=(1, 2, 3)).contiguous()
+                                                     float(coulomb), _ptr(real), ws, _stream_ptr(dev)))
+        before = _frames_rfftn(real)
+        recip = before.clone()
         _check(L.nnpops_pme_reciprocal_frames_convolve(n, frames, *dims, _ptr(box_vectors), float(alpha), _ptr(mods[0]), _ptr(mods[1]),
-                                                       _ptr(mods[2]), _ptr(recip), _ptr(energies), _ptr(ws), _stream_ptr(dev)))
-        grid = torch.fft.irfftn(recip, s=(gridx, gridy, gridz), dim=(1, 2, 3), norm="forward").contiguous()
+                                                       _ptr(mods[2]), _ptr(recip), _ptr(energies), ws, _stream_ptr(dev)))
+        if box:
+            box_ws = spaces[1][3]
+            box_deriv = torch.empty((frames, 3, 3), dtype=torch.float32, device=dev)
+            _check(L.nnpops_pme_reciprocal_frames_box_pi(n, frames, *dims, _ptr(box_vectors), float(alpha), _ptr(mods[0]), _ptr(mods[1]),
+                                                         _ptr(mods[2]), _ptr(recip), box_ws, _stream_ptr(dev)))
+        grid = _frames_irfftn(recip, gridz).contiguous()
         _check(L.nnpops_pme_reciprocal_frames_interpolate(n, frames, *dims, _ptr(charges), _ptr(box_vectors), float(coulomb), _ptr(grid),
-                                                          _ptr(pos_deriv), _ptr(charge_deriv), _ptr(ws), _stream_ptr(dev)))
-    return energies, pos_deriv, charge_deriv
+                                                          _ptr(pos_deriv), _ptr(charge_deriv), ws, _stream_ptr(dev)))
+        if box:
+            _check(L.nnpops_pme_reciprocal_frames_box_gradient(n, frames, *dims, _ptr(table), _ptr(positions), _ptr(pos_deriv), _ptr(box_vectors),
+                                                               _ptr(box_deriv), box_ws, _stream_ptr(dev)))
+    for what, (buf, off, nbytes, _) in zip(("", "box "), spaces):
+        if not bool((buf[:off] == _PASSES_PATTERN).all()) or not bool((buf[off + nbytes:] == _PASSES_PATTERN).all()):
+            raise RuntimeError(f"pme_reciprocal_frames wrote outside its {what}workspace of {nbytes} bytes")
+    out = (real, before, recip, grid, energies, pos_deriv, charge_deriv)
+    return out + (box_deriv,) if box else out
+
+
+def pme_reciprocal_frames(positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha, coulomb, xmoduli, ymoduli, zmoduli):
+    """Reciprocal-space PME of a batch of frames through the C ABI: spread -> rfftn over the last three dimensions (in two steps, _frames_rfftn) ->
+    convolve -> irfftn(norm="forward") -> interpolate.  -> (energies [B] without the self energy, dE/dpositions [N, 3], dE/dcharges
+    [N]).  Orders 4 and 5."""
+    return pme_reciprocal_frames_passes(positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha, coulomb, xmoduli,
+                                        ymoduli, zmoduli)[4:]
 
 
 def pme_direct_frames_box(positions, charges, exclusions, box_vectors, table, cutoff, alpha, coulomb):
@@ -859,34 +903,8 @@ def pme_direct_frames_box(positions, charges, exclusions, box_vectors, table, cu
 def pme_reciprocal_frames_box(positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha, coulomb, xmoduli, ymoduli, zmoduli):
     """pme_reciprocal_frames and dE_m/dB_m through the C ABI: ... -> convolve -> box_pi -> irfftn -> interpolate -> box_gradient.
     -> (energies [B] without the self energy, dE/dpositions [N, 3], dE/dcharges [N], dE/dbox [B, 3, 3])."""
-    n, frames = positions.size(0), box_vectors.size(0)
-    tiles = (table.numel() - 4 - 2 * (frames + 1) - n) // 4
-    dev = positions.device
-    positions, charges, box_vectors = positions.contiguous(), charges.contiguous(), box_vectors.contiguous()
-    mods = [m.contiguous() for m in (xmoduli, ymoduli, zmoduli)]
-    L = lib()
-    dims = (gridx, gridy, gridz, order)
-    ws = torch.empty((int(L.nnpops_pme_reciprocal_frames_workspace_bytes(n, frames, *dims)),), dtype=torch.uint8, device=dev)
-    box_ws = torch.empty((int(L.nnpops_pme_reciprocal_frames_box_workspace_bytes(frames, gridx, gridy, gridz)),), dtype=torch.uint8, device=dev)
-    real = torch.empty((frames, gridx, gridy, gridz), dtype=torch.float32, device=dev)
-    energies = torch.empty((frames,), dtype=torch.float32, device=dev)
-    pos_deriv = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    charge_deriv = torch.empty((n,), dtype=torch.float32, device=dev)
-    box_deriv = torch.empty((frames, 3, 3), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _check(L.nnpops_pme_reciprocal_frames_spread(n, frames, tiles, *dims, _ptr(table), _ptr(positions), _ptr(charges), _ptr(box_vectors),
-                                                     float(coulomb), _ptr(real), _ptr(ws), _stream_ptr(dev)))
-        recip = torch.fft.rfftn(real, dim=(1, 2, 3)).contiguous()
-        _check(L.nnpops_pme_reciprocal_frames_convolve(n, frames, *dims, _ptr(box_vectors), float(alpha), _ptr(mods[0]), _ptr(mods[1]),
-                                                       _ptr(mods[2]), _ptr(recip), _ptr(energies), _ptr(ws), _stream_ptr(dev)))
-        _check(L.nnpops_pme_reciprocal_frames_box_pi(n, frames, *dims, _ptr(box_vectors), float(alpha), _ptr(mods[0]), _ptr(mods[1]),
-                                                     _ptr(mods[2]), _ptr(recip), _ptr(box_ws), _stream_ptr(dev)))
-        grid = torch.fft.irfftn(recip, s=(gridx, gridy, gridz), dim=(1, 2, 3), norm="forward").contiguous()
-        _check(L.nnpops_pme_reciprocal_frames_interpolate(n, frames, *dims, _ptr(charges), _ptr(box_vectors), float(coulomb), _ptr(grid),
-                                                          _ptr(pos_deriv), _ptr(charge_deriv), _ptr(ws), _stream_ptr(dev)))
-        _check(L.nnpops_pme_reciprocal_frames_box_gradient(n, frames, *dims, _ptr(table), _ptr(positions), _ptr(pos_deriv), _ptr(box_vectors),
-                                                           _ptr(box_deriv), _ptr(box_ws), _stream_ptr(dev)))
-    return energies, pos_deriv, charge_deriv, box_deriv
+    return pme_reciprocal_frames_passes(positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha, coulomb, xmoduli,
+                                        ymoduli, zmoduli, box=True)[4:]
 
 
 def pme_direct_box(positions, charges, neighbors, deltas, distances, exclusions, box_vectors, alpha, coulomb):

@@ -3399,6 +3399,19 @@ Tensor pme_frames_table_entry(const Tensor& offsets, c10::Device device) {
 
 struct PmeFramesShape { int64_t frames, atoms, tiles; };
 
+// The transforms of a batch of grids [B, Kx, Ky, Kz] in two steps: real along z, complex over (x, y).  The library's single batched
+// three-dimensional real transform returned wrong values for some shapes after transforms of other shapes in the same process
+// ([3, 8, 8, 16] after [3, 8, 8, 15]: off by half the largest entry, forward and inverse); the two-step form was right wherever that
+// was seen (docs/LAB_NOTEBOOK_pme_frames_passes.md).  capi.pme_reciprocal_frames_passes makes the same calls.
+Tensor pme_frames_rfftn(const Tensor& real) {
+    const std::vector<int64_t> xy{1, 2};
+    return torch::fft::fftn(torch::fft::rfft(real, c10::nullopt, 3), c10::nullopt, torch::IntArrayRef(xy)).contiguous();
+}
+Tensor pme_frames_irfftn(const Tensor& recip, int64_t kz) {      // norm "forward": no factor on the way back
+    const std::vector<int64_t> xy{1, 2};
+    return torch::fft::irfft(torch::fft::ifftn(recip, c10::nullopt, torch::IntArrayRef(xy), "forward"), kz, 3, "forward");
+}
+
 // what the ops check of their common arguments; the tile count follows from the table's length.  box_op: the two _box ops, which
 // take a box that requires a gradient.
 PmeFramesShape pme_frames_check(const char* op, const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table,
@@ -3534,8 +3547,7 @@ public:
                                                 q.data_ptr<float>(), boxes.data_ptr<float>(), (float)k, real.data_ptr<float>(),
                                                 workspace.data_ptr(), stream) != NNPOPS_OK)
             raise_last(qualified.c_str());
-        const std::vector<int64_t> dims{1, 2, 3};
-        Tensor recip = torch::fft::rfftn(real, c10::nullopt, torch::IntArrayRef(dims)).contiguous();
+        Tensor recip = pme_frames_rfftn(real);
         Tensor energies = torch::empty({s.frames}, opts);
         if (nnpops_pme_reciprocal_frames_convolve(n, B, gx, gy, gz, (int)o, boxes.data_ptr<float>(), (float)a, xm.data_ptr<float>(),
                                                   ym.data_ptr<float>(), zm.data_ptr<float>(), recip.data_ptr(), energies.data_ptr<float>(),
@@ -3552,7 +3564,7 @@ public:
                 raise_last(qualified.c_str());
         }
         if (positions.requires_grad() || charges.requires_grad() || box_grad) {     // (X needs the interpolated dE/dpositions)
-            const Tensor grid = torch::fft::irfftn(recip, torch::IntArrayRef(K), torch::IntArrayRef(dims), "forward").contiguous();
+            const Tensor grid = pme_frames_irfftn(recip, K[2]).contiguous();
             Tensor pos_deriv = torch::empty({s.atoms, 3}, opts), charge_deriv = torch::empty({s.atoms}, opts);
             if (nnpops_pme_reciprocal_frames_interpolate(n, B, gx, gy, gz, (int)o, q.data_ptr<float>(), boxes.data_ptr<float>(), (float)k,
                                                          grid.data_ptr<float>(), pos_deriv.data_ptr<float>(), charge_deriv.data_ptr<float>(),
@@ -3722,8 +3734,7 @@ public:
                                                             w.data_ptr<float>(), real.data_ptr<float>(), workspace.data_ptr(), second.data_ptr(),
                                                             stream) != NNPOPS_OK)
             raise_last(op);
-        const std::vector<int64_t> dims{1, 2, 3};
-        Tensor recip2 = torch::fft::rfftn(real, c10::nullopt, torch::IntArrayRef(dims)).contiguous();
+        Tensor recip2 = pme_frames_rfftn(real);
         Tensor unused = torch::empty({(int64_t)B}, opts);
         // (the convolution's partial sums share the forward's workspace; the base indices and weights behind them stay)
         if (nnpops_pme_reciprocal_frames_convolve(n, B, gx, gy, gz, o, boxes.data_ptr<float>(), (float)alpha, xm.data_ptr<float>(),
@@ -3733,7 +3744,7 @@ public:
         // Both potential grids are transformed back in double and rounded to float once: the interpolation differences them twice, and
         // the float transform's error grew there with the square of the grid size.
         auto back = [&](const Tensor& c) {
-            return torch::fft::irfftn(c.to(torch::kComplexDouble), torch::IntArrayRef(K), torch::IntArrayRef(dims), "forward").to(torch::kFloat).contiguous();
+            return pme_frames_irfftn(c.to(torch::kComplexDouble), K[2]).to(torch::kFloat).contiguous();
         };
         const Tensor phi = back(recip), phi2 = back(recip2);
         if (nnpops_pme_reciprocal_frames_interpolate_second(n, B, gx, gy, gz, o, q.data_ptr<float>(), boxes.data_ptr<float>(), (float)k,

@@ -93,12 +93,13 @@ def batch(sizes, seed, scales=(1.0,), triclinic=True, excl="few"):
 
 
 # name -> batch(...) arguments.  Tile edges (15, 16, 17, 33), lanes without a partner and an atom without a neighbour (0, 1, 2); many
-# small frames; one frame one atom over the LDS limit next to a small one; neighbouring boxes a factor of two apart; a wide exclusion
+# small frames; one frame one atom over the LDS limit, and one exactly at it, next to a small one; neighbouring boxes a factor of two apart; a wide exclusion
 # row; a frame in which every pair is excluded.
 DIRECT_CASES = {
     "tile_edges": dict(sizes=(0, 1, 2, 15, 16, 17, 33), seed=11, scales=(1.0, 2.0)),
     "seventy_small": dict(sizes=tuple(1 + m % 9 for m in range(70)), seed=200, scales=(1.0, 2.0, 1.5)),
     "over_lds": dict(sizes=(LDS_ATOMS + 1, 5), seed=31, scales=(8.0, 1.0)),
+    "at_lds": dict(sizes=(LDS_ATOMS, 3), seed=33, scales=(8.0, 1.0)),       # the last staged size (a box of 2.4 holds no 1 024 atoms clear of the cutoff)
     "orthorhombic": dict(sizes=(20, 33), seed=41, triclinic=False, excl="none"),
     "wide_row": dict(sizes=(33, 40), seed=51, excl="wide"),
     "all_excluded": dict(sizes=(6, 17, 9), seed=61, excl="all"),

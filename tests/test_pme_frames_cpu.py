@@ -75,6 +75,21 @@ def test_python_refusals():
         PME(8, 8, 8, 6, 3.0, 138.935, none, reciprocal=True).compute_reciprocal_frames(pos, q, boxes, [0, 3, 6])
 
 
+def test_reciprocal_workspace_refuses_more_workgroups_than_one_launch_takes():
+    """check_recip: frames x max(bricks, convolution workgroups) must fit blockIdx.x, 2^31 - 1; a refused shape reports 0 bytes"""
+    size = capi.lib().nnpops_pme_reciprocal_frames_workspace_bytes
+    box_size = capi.lib().nnpops_pme_reciprocal_frames_box_workspace_bytes
+    limit = 2 ** 31 - 1
+    for grid, per_frame in (((64, 64, 64), 1024),          # 16 x 16 x 4 bricks = the convolution's cap of 1 024 workgroups
+                            ((8, 8, 16), 4),               # 2 x 2 x 1 bricks, 3 convolution workgroups
+                            ((256, 256, 64), 16384)):      # 64 x 64 x 4 bricks, above the convolution's cap
+        most = limit // per_frame
+        for order in (4, 5):
+            assert size(0, most, *grid, order) > 0 and size(0, most + 1, *grid, order) == 0, (grid, order)
+        assert box_size(most, *grid) > 0 and box_size(most + 1, *grid) == 0, grid
+    assert size(0, 1, 8, 8, 8, 6) == 0 and size(0, 0, 8, 8, 8, 5) == 0 and size(-1, 1, 8, 8, 8, 5) == 0
+
+
 @pytest.mark.parametrize("triclinic", [False, True])
 def test_judge_equals_the_single_system_restatement(triclinic):
     pos, q, box = f64.system(triclinic, n=30, seed=5, outside=True)
