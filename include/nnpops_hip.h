@@ -719,6 +719,22 @@ int nnpops_pme_reciprocal_frames_box_pi(int num_atoms, int num_frames, int gridx
 int nnpops_pme_reciprocal_frames_box_gradient(int num_atoms, int num_frames, int gridx, int gridy, int gridz, int order,
                                               const int32_t* table, const float* positions, const float* position_deriv,
                                               const float* box_vectors, float* box_deriv, void* box_workspace, void* stream);
+/* The transforms and the convolution of a batch of frames in one launch (pme_frames_fft.hip): what stands between
+ * nnpops_pme_reciprocal_frames_spread and nnpops_pme_reciprocal_frames_interpolate -- the caller's rfftn, nnpops_pme_reciprocal_frames_convolve
+ * and the caller's irfftn(norm = "forward") -- done by one workgroup per frame that keeps the frame's half-spectrum in LDS.
+ *   Served: 2 <= gridx, gridy, gridz <= 64, every prime factor at most 7, gridz even, and gridx * gridy * (gridz / 2 + 1) * 8 bytes plus
+ *     padding and tables within the 160 KiB of LDS of a workgroup (24^3 and 32^3 are).  Any other grid is refused before a launch.
+ *   nnpops_pme_reciprocal_frames_transform_lds_bytes: the LDS a frame takes, or 0 when the grid is not served (nnpops_last_error names
+ *     the rule and the dimension).  Host only.
+ *   nnpops_pme_reciprocal_frames_transform: real_grids [B][gx][gy][gz] as the spread left them -> potential_grids of the same shape (the
+ *     two may be one buffer), energies [B] as nnpops_pme_reciprocal_frames_convolve defines them, and, when scaled_grids is not NULL, the
+ *     scaled half-spectra [B][gx][gy][gz/2+1] complex float32 in natural order as nnpops_pme_reciprocal_frames_box_pi reads them.  The
+ *     grids are 8-byte aligned.  Deterministic: a frame's results do not depend on the batch around it.  Allocates nothing, does not
+ *     synchronise, capturable.  The results are those of the three-step route within float32 rounding, not bit for bit. */
+int64_t nnpops_pme_reciprocal_frames_transform_lds_bytes(int gridx, int gridy, int gridz);
+int nnpops_pme_reciprocal_frames_transform(int num_atoms, int num_frames, int gridx, int gridy, int gridz, int order, const float* box_vectors,
+                                           float alpha, const float* xmoduli, const float* ymoduli, const float* zmoduli,
+                                           const float* real_grids, float* potential_grids, void* scaled_grids, float* energies, void* stream);
 /* Second derivatives over frames with respect to positions and charges (pme_frames_second_order.hip; the formulae are
  * those of nnpops_pme_direct_double_backward / nnpops_pme_reciprocal_spread_directional with every frame in its own box).  v [N][3] and
  * w [N] are the cotangents of the first backward's two outputs, upstream [B] (float32) the energies' upstream gradient g:

@@ -17,16 +17,18 @@ LIB = os.path.join(HERE, "libnnpops_hip.so")
 ARCH = "gfx950"
 
 # translation units of the C-ABI library (the torch binding is built separately, see torch_binding.py)
-UNITS = ["capi_common.hip", "ani.hip", "cfconv.hip", "neighbor_pairs.hip", "pairs_index.hip", "pairs_second_order.hip", "batched_nn.hip", "mlp_fused.hip", "pme.hip", "pme_recip.hip", "pme_second_order.hip", "pme_frames.hip", "pme_frames_second_order.hip"]
+UNITS = ["capi_common.hip", "ani.hip", "cfconv.hip", "neighbor_pairs.hip", "pairs_index.hip", "pairs_second_order.hip", "batched_nn.hip", "mlp_fused.hip", "pme.hip", "pme_recip.hip", "pme_second_order.hip", "pme_frames.hip", "pme_frames_second_order.hip", "pme_frames_fft.hip"]
 
 # Flags of single units, part of the recipe.  ani.hip: the first 14 words of every kernel's argument block are in scalar registers when
 # a wave starts, so the per-atom kernels (which put what their first requests need in those words) begin without a round trip for
 # their arguments; on a machine that does not preload, the prologue the compiler adds loads the same registers.
 # pme_frames.hip: compiled without packed float32 arithmetic; plain VALU instructions give the same IEEE results element by element.
 # pme_frames_second_order.hip: the same, so that its pair displacements round as the forward's do.
+# pme_frames_fft.hip: the same, so that its convolution rounds as pme_frames.hip's does.
 UNIT_FLAGS = {"ani.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=14"],
               "pme_frames.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
-              "pme_frames_second_order.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+              "pme_frames_second_order.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              "pme_frames_fft.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _flags_stamp(src, flags):

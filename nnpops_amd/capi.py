@@ -167,6 +167,8 @@ SIGNATURES = {
                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nnpops_pme_reciprocal_frames_box_gradient": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nnpops_pme_reciprocal_frames_transform_lds_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "nnpops_pme_reciprocal_frames_transform": (C.c_int, [C.c_int] * 6 + [C.c_void_p, C.c_float] + [C.c_void_p] * 8),
     "nnpops_pme_direct_frames_double_backward_workspace_bytes": (C.c_int64, [C.c_int]),
     "nnpops_pme_direct_frames_double_backward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8 +
                                                  [C.c_float, C.c_float, C.c_float] + [C.c_void_p] * 4),
@@ -882,6 +884,32 @@ def pme_reciprocal_frames(positions, charges, box_vectors, table, gridx, gridy, 
     [N]).  Orders 4 and 5."""
     return pme_reciprocal_frames_passes(positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha, coulomb, xmoduli,
                                         ymoduli, zmoduli)[4:]
+
+
+def pme_reciprocal_frames_transform_lds_bytes(gridx, gridy, gridz):
+    """The LDS one frame of a grid takes in pme_reciprocal_frames_transform -> (bytes, ""), or (0, the rule the grid breaks).  Host only."""
+    L = lib()
+    nbytes = int(L.nnpops_pme_reciprocal_frames_transform_lds_bytes(int(gridx), int(gridy), int(gridz)))
+    return nbytes, "" if nbytes else L.nnpops_last_error().decode()
+
+
+def pme_reciprocal_frames_transform(real_grids, box_vectors, order, alpha, xmoduli, ymoduli, zmoduli, scaled=False, energies=None):
+    """rfftn -> convolve -> irfftn(norm="forward") of a batch of spread grids [B, Kx, Ky, Kz] in one launch, a frame's half-spectrum in the
+    LDS of its workgroup (pme_frames_fft.hip) -> (potential grids [B, Kx, Ky, Kz], the scaled half-spectra [B, Kx, Ky, Kz/2 + 1] complex64
+    in natural order when `scaled`, else None, energies [B]).  A grid the kernel does not serve raises NNPOpsHipError before any launch."""
+    frames, gridx, gridy, gridz = real_grids.shape
+    dev = real_grids.device
+    real_grids, box_vectors = real_grids.contiguous(), box_vectors.contiguous()
+    mods = [m.contiguous() for m in (xmoduli, ymoduli, zmoduli)]
+    potential = torch.empty_like(real_grids)
+    recip = torch.empty((frames, gridx, gridy, gridz // 2 + 1), dtype=torch.complex64, device=dev) if scaled else None
+    if energies is None:
+        energies = torch.empty((frames,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib().nnpops_pme_reciprocal_frames_transform(0, frames, gridx, gridy, gridz, order, _ptr(box_vectors), float(alpha), _ptr(mods[0]),
+                                                            _ptr(mods[1]), _ptr(mods[2]), _ptr(real_grids), _ptr(potential), _ptr(recip),
+                                                            _ptr(energies), _stream_ptr(dev)))
+    return potential, recip, energies
 
 
 def pme_direct_frames_box(positions, charges, exclusions, box_vectors, table, cutoff, alpha, coulomb):

@@ -3516,10 +3516,13 @@ public:
     static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table,
                           const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz, const torch::Scalar& order,
                           const torch::Scalar& alpha, const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli,
-                          const Tensor& zmoduli, bool box_op, bool box_grad, tensor_list* kept = nullptr) {
+                          const Tensor& zmoduli, bool box_op, bool box_grad, bool lds, tensor_list* kept = nullptr) {
         // kept: the _twice op runs this forward and saves for itself (boxes, the workspace with the base indices and weights, the scaled
         // complex grids, the moduli, dE/dpositions, dE/dcharges)
-        const char* op = kept ? "pme_reciprocal_frames_twice" : box_op ? "pme_reciprocal_frames_box" : "pme_reciprocal_frames";
+        // lds: the transforms and the convolution in one launch of pme_frames_fft.hip (the _lds ops) instead of the library transforms
+        // around nnpops_pme_reciprocal_frames_convolve; everything before and after is the same.
+        const char* op = kept ? "pme_reciprocal_frames_twice" : lds ? (box_op ? "pme_reciprocal_frames_lds_box" : "pme_reciprocal_frames_lds") :
+                         box_op ? "pme_reciprocal_frames_box" : "pme_reciprocal_frames";
         const std::string qualified = std::string("pme::") + op;
         ctx->saved_data["box_op"] = box_op;
         const PmeFramesShape s = pme_frames_check(op, positions, charges, box_vectors, table, box_op);
@@ -3539,6 +3542,7 @@ public:
         const int n = (int)s.atoms, B = (int)s.frames, gx = (int)K[0], gy = (int)K[1], gz = (int)K[2];
         c10::hip::HIPGuard guard(positions.device().index());
         void* stream = current_stream(positions.device());
+        if (lds && nnpops_pme_reciprocal_frames_transform_lds_bytes(gx, gy, gz) == 0) raise_last(qualified.c_str());     // (before any launch)
         const int64_t bytes = nnpops_pme_reciprocal_frames_workspace_bytes(n, B, gx, gy, gz, (int)o);
         if (bytes <= 0) raise_last(qualified.c_str());
         Tensor workspace = torch::empty({bytes}, opts.dtype(torch::kUInt8));
@@ -3547,12 +3551,21 @@ public:
                                                 q.data_ptr<float>(), boxes.data_ptr<float>(), (float)k, real.data_ptr<float>(),
                                                 workspace.data_ptr(), stream) != NNPOPS_OK)
             raise_last(qualified.c_str());
-        Tensor recip = pme_frames_rfftn(real);
+        Tensor recip;
         Tensor energies = torch::empty({s.frames}, opts);
-        if (nnpops_pme_reciprocal_frames_convolve(n, B, gx, gy, gz, (int)o, boxes.data_ptr<float>(), (float)a, xm.data_ptr<float>(),
-                                                  ym.data_ptr<float>(), zm.data_ptr<float>(), recip.data_ptr(), energies.data_ptr<float>(),
-                                                  workspace.data_ptr(), stream) != NNPOPS_OK)
-            raise_last(qualified.c_str());
+        if (lds) {                                                 // the potential grids take the real grids' place
+            if (box_grad) recip = torch::empty({s.frames, K[0], K[1], K[2] / 2 + 1}, opts.dtype(torch::kComplexFloat));
+            if (nnpops_pme_reciprocal_frames_transform(n, B, gx, gy, gz, (int)o, boxes.data_ptr<float>(), (float)a, xm.data_ptr<float>(),
+                                                       ym.data_ptr<float>(), zm.data_ptr<float>(), real.data_ptr<float>(), real.data_ptr<float>(),
+                                                       box_grad ? recip.data_ptr() : nullptr, energies.data_ptr<float>(), stream) != NNPOPS_OK)
+                raise_last(qualified.c_str());
+        } else {
+            recip = pme_frames_rfftn(real);
+            if (nnpops_pme_reciprocal_frames_convolve(n, B, gx, gy, gz, (int)o, boxes.data_ptr<float>(), (float)a, xm.data_ptr<float>(),
+                                                      ym.data_ptr<float>(), zm.data_ptr<float>(), recip.data_ptr(), energies.data_ptr<float>(),
+                                                      workspace.data_ptr(), stream) != NNPOPS_OK)
+                raise_last(qualified.c_str());
+        }
         Tensor box_workspace;
         if (box_grad) {                                            // Pi from the scaled grids, before the inverse transform
             const int64_t box_bytes = nnpops_pme_reciprocal_frames_box_workspace_bytes(B, gx, gy, gz);
@@ -3564,7 +3577,7 @@ public:
                 raise_last(qualified.c_str());
         }
         if (positions.requires_grad() || charges.requires_grad() || box_grad) {     // (X needs the interpolated dE/dpositions)
-            const Tensor grid = pme_frames_irfftn(recip, K[2]).contiguous();
+            const Tensor grid = lds ? real : pme_frames_irfftn(recip, K[2]).contiguous();
             Tensor pos_deriv = torch::empty({s.atoms, 3}, opts), charge_deriv = torch::empty({s.atoms}, opts);
             if (nnpops_pme_reciprocal_frames_interpolate(n, B, gx, gy, gz, (int)o, q.data_ptr<float>(), boxes.data_ptr<float>(), (float)k,
                                                          grid.data_ptr<float>(), pos_deriv.data_ptr<float>(), charge_deriv.data_ptr<float>(),
@@ -3589,7 +3602,7 @@ public:
         const auto saved = ctx->get_saved_variables();
         const tensor_list g = pme_frames_scale(ctx->saved_data["box_op"].toBool() ? "pme_reciprocal_frames_box" : "pme_reciprocal_frames", saved[0], saved[1], saved[2], grad_outputs[0]);
         return {g[0], g[1], pme_frames_box_scale(saved, grad_outputs[0]), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(),
-                Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+                Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
     }
 };
 
@@ -3607,14 +3620,29 @@ Tensor pme_reciprocal_frames_entry(const Tensor& positions, const Tensor& charge
                                    const torch::Scalar& alpha, const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli,
                                    const Tensor& zmoduli) {
     return PmeReciprocalFramesFunction::apply(positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha, coulomb, xmoduli,
-                                              ymoduli, zmoduli, false, false);
+                                              ymoduli, zmoduli, false, false, false);
 }
 Tensor pme_reciprocal_frames_box_entry(const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table,
                                        const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz,
                                        const torch::Scalar& order, const torch::Scalar& alpha, const torch::Scalar& coulomb,
                                        const Tensor& xmoduli, const Tensor& ymoduli, const Tensor& zmoduli) {
     return PmeReciprocalFramesFunction::apply(positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha, coulomb, xmoduli,
-                                              ymoduli, zmoduli, true, box_vectors.requires_grad() && torch::GradMode::is_enabled());
+                                              ymoduli, zmoduli, true, box_vectors.requires_grad() && torch::GradMode::is_enabled(), false);
+}
+// the same two ops with the transforms and the convolution in the LDS of one workgroup per frame (pme_frames_fft.hip)
+Tensor pme_reciprocal_frames_lds_entry(const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table,
+                                       const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz,
+                                       const torch::Scalar& order, const torch::Scalar& alpha, const torch::Scalar& coulomb,
+                                       const Tensor& xmoduli, const Tensor& ymoduli, const Tensor& zmoduli) {
+    return PmeReciprocalFramesFunction::apply(positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha, coulomb, xmoduli,
+                                              ymoduli, zmoduli, false, false, true);
+}
+Tensor pme_reciprocal_frames_lds_box_entry(const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table,
+                                           const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz,
+                                           const torch::Scalar& order, const torch::Scalar& alpha, const torch::Scalar& coulomb,
+                                           const Tensor& xmoduli, const Tensor& ymoduli, const Tensor& zmoduli) {
+    return PmeReciprocalFramesFunction::apply(positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha, coulomb, xmoduli,
+                                              ymoduli, zmoduli, true, box_vectors.requires_grad() && torch::GradMode::is_enabled(), true);
 }
 // ---------------------------------------------------------------------------------------------
 // pme_direct_frames_twice / pme_reciprocal_frames_twice: the forwards above, unchanged (energies, dE/dpositions and dE/dcharges are the
@@ -3792,7 +3820,7 @@ public:
                           const Tensor& zmoduli) {
         tensor_list kept;
         const Tensor energies = PmeReciprocalFramesFunction::forward(ctx, positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha,
-                                                                     coulomb, xmoduli, ymoduli, zmoduli, false, false, &kept);
+                                                                     coulomb, xmoduli, ymoduli, zmoduli, false, false, false, &kept);
         if (!kept.empty())                                          // (positions or charges require a gradient)
             ctx->save_for_backward({positions, charges, kept[0], table, kept[1], kept[2], kept[3], kept[4], kept[5], kept[6], kept[7]});
         ctx->saved_data["grid"] = std::vector<int64_t>{gridx.toLong(), gridy.toLong(), gridz.toLong()};
@@ -3843,12 +3871,18 @@ TORCH_LIBRARY_FRAGMENT(pme, m) {
           "Scalar alpha, Scalar coulomb) -> Tensor");
     m.def("pme_reciprocal_frames_box(Tensor positions, Tensor charges, Tensor box_vectors, Tensor table, Scalar gridx, Scalar gridy, "
           "Scalar gridz, Scalar order, Scalar alpha, Scalar coulomb, Tensor xmoduli, Tensor ymoduli, Tensor zmoduli) -> Tensor");
+    m.def("pme_reciprocal_frames_lds(Tensor positions, Tensor charges, Tensor box_vectors, Tensor table, Scalar gridx, Scalar gridy, "
+          "Scalar gridz, Scalar order, Scalar alpha, Scalar coulomb, Tensor xmoduli, Tensor ymoduli, Tensor zmoduli) -> Tensor");
+    m.def("pme_reciprocal_frames_lds_box(Tensor positions, Tensor charges, Tensor box_vectors, Tensor table, Scalar gridx, Scalar gridy, "
+          "Scalar gridz, Scalar order, Scalar alpha, Scalar coulomb, Tensor xmoduli, Tensor ymoduli, Tensor zmoduli) -> Tensor");
 }
 TORCH_LIBRARY_IMPL(pme, AutogradCUDA, m) {
     m.impl("pme_direct_frames", pme_direct_frames_entry);
     m.impl("pme_reciprocal_frames", pme_reciprocal_frames_entry);
     m.impl("pme_direct_frames_box", pme_direct_frames_box_entry);
     m.impl("pme_reciprocal_frames_box", pme_reciprocal_frames_box_entry);
+    m.impl("pme_reciprocal_frames_lds", pme_reciprocal_frames_lds_entry);
+    m.impl("pme_reciprocal_frames_lds_box", pme_reciprocal_frames_lds_box_entry);
     m.impl("pme_direct_frames_twice", pme_direct_frames_twice_entry);
     m.impl("pme_reciprocal_frames_twice", pme_reciprocal_frames_twice_entry);
 }
@@ -3857,6 +3891,8 @@ TORCH_LIBRARY_IMPL(pme, CUDA, m) {
     m.impl("pme_reciprocal_frames", pme_reciprocal_frames_entry);
     m.impl("pme_direct_frames_box", pme_direct_frames_box_entry);
     m.impl("pme_reciprocal_frames_box", pme_reciprocal_frames_box_entry);
+    m.impl("pme_reciprocal_frames_lds", pme_reciprocal_frames_lds_entry);
+    m.impl("pme_reciprocal_frames_lds_box", pme_reciprocal_frames_lds_box_entry);
     m.impl("pme_direct_frames_twice", pme_direct_frames_twice_entry);
     m.impl("pme_reciprocal_frames_twice", pme_reciprocal_frames_twice_entry);
 }

@@ -260,15 +260,29 @@ class PME:
         return op(positions, charges, self.exclusions, box_vectors, table, cutoff, self.alpha, self.coulomb)
 
     def compute_reciprocal_frames(self, positions: torch.Tensor, charges: torch.Tensor, box_vectors: torch.Tensor, offsets,
-                                  box_gradient: bool = False, twice_differentiable: bool = False):
+                                  box_gradient: bool = False, twice_differentiable: bool = False, transform: str = "torch"):
         """Reciprocal-space energies [B] of a batch of frames, each frame's self energy included; needs ``PME(..., reciprocal=True)``
         and order 4 or 5.  The grid, order, alpha and coulomb are the object's, the same for all frames.  Differentiable with respect
         to positions and charges (first order) and, with ``box_gradient=True``, box_vectors (the self energy does not depend on the
-        box).  ``twice_differentiable=True``: as for ``compute_direct_frames``, through ``pme_reciprocal_frames_twice``."""
+        box).  ``twice_differentiable=True``: as for ``compute_direct_frames``, through ``pme_reciprocal_frames_twice``.
+        ``transform="lds"``: the transforms and the convolution between spread and interpolation in one launch, a frame's half-spectrum
+        in the LDS of its workgroup (``pme_reciprocal_frames_lds[_box]``), for grids of 2 .. 64 points per axis with
+        prime factors up to 7, an even gridz and gridx * gridy * (gridz / 2 + 1) * 8 bytes within 160 KiB; the results agree with the
+        default ``"torch"`` within float32 rounding, not bit for bit."""
         if not self.reciprocal:
             raise RuntimeError("the reciprocal-space term of PME is not enabled on this object: construct it with PME(..., reciprocal=True)")
         if self.order not in (4, 5):
             raise ValueError(f'compute_reciprocal_frames: only order 4 or 5 is supported (got {self.order})')
+        if transform not in ("torch", "lds"):
+            raise ValueError(f'compute_reciprocal_frames: transform must be "torch" or "lds" (got {transform!r})')
+        if transform == "lds":
+            if twice_differentiable:
+                raise RuntimeError('compute_reciprocal_frames: transform="lds" cannot be combined with twice_differentiable=True (the '
+                                   'second-order pass transforms in double precision and stays on transform="torch")')
+            from .. import capi
+            nbytes, rule = capi.pme_reciprocal_frames_transform_lds_bytes(self.gridx, self.gridy, self.gridz)
+            if not nbytes:
+                raise ValueError(f'compute_reciprocal_frames: transform="lds" does not serve this grid: {rule}')
         table = self._frames_table('compute_reciprocal_frames', positions, charges, box_vectors, offsets, box_gradient, twice_differentiable)
         for i in range(3):
             self.moduli[i] = self.moduli[i].to(positions.device)
@@ -280,5 +294,7 @@ class PME:
         self_energy = frame_sums * (-self.coulomb * self.alpha / math.sqrt(math.pi))
         op = torch.ops.pme.pme_reciprocal_frames_twice if twice_differentiable else \
             torch.ops.pme.pme_reciprocal_frames_box if box_gradient else torch.ops.pme.pme_reciprocal_frames
+        if transform == "lds":
+            op = torch.ops.pme.pme_reciprocal_frames_lds_box if box_gradient else torch.ops.pme.pme_reciprocal_frames_lds
         return self_energy + op(positions, charges, box_vectors, table, self.gridx, self.gridy, self.gridz, self.order, self.alpha,
                                 self.coulomb, self.moduli[0], self.moduli[1], self.moduli[2])

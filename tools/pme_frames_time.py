@@ -8,7 +8,11 @@ alpha 0.6 / A, a 24^3 grid, order 5.
                                                     with a box that requires a gradient, and against the batch without box gradient
     python tools/pme_frames_time.py --twice ...     the force-loss step E -> grad(E, (x, q), create_graph=True) -> |F - F_ref|^2.backward()
                                                     (twice_differentiable=True per call) against the loop of single-frame steps on a
-                                                    PME(..., twice_differentiable=True) object"""
+                                                    PME(..., twice_differentiable=True) object
+    python tools/pme_frames_time.py --transform lds [--box] [--grid 24] [--batched-only]
+                                                    the reciprocal term with transform="lds" (pme_frames_fft.hip) against the default
+                                                    transform="torch", forward + backward; --batched-only runs "lds" alone, and with
+                                                    --transform torch the default alone (for kernel profiles)"""
 import argparse
 import os
 import sys
@@ -58,6 +62,33 @@ def force_loss(energy, x, c, f_ref):
     return torch.autograd.grad(((-dx - f_ref) ** 2).sum(), (x, c))
 
 
+def transforms(args):
+    """transform="lds" against transform="torch": the reciprocal term's forward + backward, with the box gradient under --box"""
+    G = args.grid
+    print(f"PME reciprocal over frames, transform lds against torch: {N}-atom water boxes, alpha {ALPHA}, grid {G}^3, order {ORDER}; forward + "
+          f"backward{' with the box gradient' if args.box else ''}, stream time, medians of {args.rounds} interleaved rounds (spread = max - min)")
+    print(f"  {'B':>4s} {'lds us':>9s} {'(spread)':>9s} {'torch us':>9s} {'(spread)':>9s} {'torch / lds':>12s}")
+    for B in args.frames:
+        host_pos, host_q, host_boxes, excl = water_frames(B)
+        offsets = [m * N for m in range(B + 1)]
+        pos, q = torch.tensor(host_pos, device=dev).requires_grad_(), torch.tensor(host_q, device=dev).requires_grad_()
+        boxes = torch.tensor(host_boxes, device=dev).requires_grad_(args.box)
+        pme = PME(G, G, G, ORDER, ALPHA, COULOMB, torch.tensor(excl), reciprocal=True)
+
+        def step(transform):
+            e = pme.compute_reciprocal_frames(pos, q, boxes, offsets, box_gradient=args.box, transform=transform)
+            return torch.autograd.grad(e.sum(), (pos, q, boxes) if args.box else (pos, q))
+        reps = max(20, min(200, 4096 // B))
+        if args.batched_only:
+            timed(lambda: step(args.transform), reps)
+            continue
+        for a, b in zip(step("lds"), step("torch")):                     # the two routes must agree before they are timed
+            assert float((a - b).abs().max()) <= 1e-4 * float(b.abs().max())
+        tl, tt = np.array([(timed(lambda: step("lds"), reps), timed(lambda: step("torch"), reps)) for _ in range(args.rounds)]).T
+        ml, mt = float(np.median(tl)), float(np.median(tt))
+        print(f"  {B:4d} {ml:9.1f} {tl.max() - tl.min():9.1f} {mt:9.1f} {tt.max() - tt.min():9.1f} {mt / ml:12.2f}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, nargs="+", default=[8, 64, 256])
@@ -65,7 +96,11 @@ def main():
     ap.add_argument("--batched-only", action="store_true")
     ap.add_argument("--box", action="store_true")
     ap.add_argument("--twice", action="store_true")
+    ap.add_argument("--transform", choices=["torch", "lds"], default=None)
+    ap.add_argument("--grid", type=int, default=GRID)
     args = ap.parse_args()
+    if args.transform:
+        return transforms(args)
     assert not (args.box and args.twice), "--box and --twice are separate measurements"
     what = "force-loss step" if args.twice else "forward + backward"
     print(f"PME over frames: {N}-atom water boxes, cutoff {CUTOFF}, alpha {ALPHA}, grid {GRID}^3, order {ORDER}; {what}, stream time, "
