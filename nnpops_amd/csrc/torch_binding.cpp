@@ -2448,18 +2448,135 @@ TORCH_LIBRARY_IMPL(neighbors, CPU, m) { m.impl("getNeighborPairs", neighbor_pair
 // name and schema; the energy's autograd backward scales the derivatives computed in the forward pass, exactly as the
 // reference does.  The reciprocal-space op (pme_reciprocal) follows it below.
 // =============================================================================================
-// the energy and its derivatives, and the inputs as the kernels read them
-struct PmeDirectForward {
-    Tensor energy, pos_deriv, charge_deriv;
-    Tensor pos, q, nb, dl, ds, ex;
-    Tensor index;      // the list's cached transposed index when the indexed kernels ran (pme_direct_twice keeps it)
+// What a PME forward pass computed and what a PME node keeps for a later pass, for all four terms (direct and reciprocal, single system
+// and frames); a term leaves the members of the others undefined.  The `run` routines return one, every node saves from the one it got
+// back, and save() and load() are the only code that knows where a piece lies in the context.
+struct PmeState {
+    Tensor energy;                                  // what the op returns (not kept)
+    Tensor g;                                       // the recorded backward node: its upstream gradient
+    Tensor positions, charges;                      // the recorded nodes: the inputs as the caller passed them (the nodes' edges)
+    Tensor pos, q;                                  // the inputs as the kernels read them
+    Tensor pos_deriv, charge_deriv, box_deriv;      // dE/dpositions, dE/dcharges, dE/dbox computed with the forward pass
+    Tensor nb, dl, ds, ex;                          // direct: the pair list and the exclusions as the kernels read them
+    Tensor index;                                   // ... and the list's cached transposed index when the indexed kernels ran
+    Tensor box, table;                              // the box (frames: the boxes [B, 3, 3] and the frames table)
+    Tensor recip, workspace, pi, xm, ym, zm;        // reciprocal: the scaled complex grid(s), the splines, the Pi sums, the moduli
+    Tensor phi;                                     // ... and the potential grid of the single system's first-order backward
+    std::vector<int64_t> grid;
+    int64_t order = 0;
+    double cutoff = 0, alpha = 0, coulomb = 0;
+    bool box_op = false;                            // one of the _box ops (they name themselves in their backward's refusal)
+
+    // what the default ops keep when the derivatives come with the forward pass (and the table that scales them frame by frame)
+    PmeState derivatives() const {
+        PmeState k;
+        k.pos_deriv = pos_deriv; k.charge_deriv = charge_deriv; k.box_deriv = box_deriv; k.table = table; k.box_op = box_op;
+        return k;
+    }
+    // The tensors a node keeps, by name, in the order save() and load() both walk.  Only the defined ones are saved (a default node
+    // keeps three or four): one key of saved_data holds which (a bit each), then box_op, order, cutoff, alpha, coulomb and the grid.
+    static constexpr size_t kKept = 22;
+    static const std::array<Tensor PmeState::*, kKept>& kept() {
+        static const std::array<Tensor PmeState::*, kKept> members = {
+            &PmeState::g, &PmeState::positions, &PmeState::charges, &PmeState::pos, &PmeState::q, &PmeState::pos_deriv, &PmeState::charge_deriv,
+            &PmeState::box_deriv, &PmeState::nb, &PmeState::dl, &PmeState::ds, &PmeState::ex, &PmeState::index, &PmeState::box, &PmeState::table,
+            &PmeState::recip, &PmeState::workspace, &PmeState::pi, &PmeState::xm, &PmeState::ym, &PmeState::zm, &PmeState::phi};
+        return members;
+    }
+    void save(AutogradContext* ctx) const {
+        tensor_list keep;
+        int64_t which = 0;
+        for (size_t i = 0; i < kKept; i++)
+            if ((this->*kept()[i]).defined()) { keep.push_back(this->*kept()[i]); which |= int64_t(1) << i; }
+        ctx->save_for_backward(keep);
+        std::vector<double> scalars = {(double)which, box_op ? 1.0 : 0.0, (double)order, cutoff, alpha, coulomb};
+        scalars.insert(scalars.end(), grid.begin(), grid.end());
+        ctx->saved_data["state"] = scalars;
+    }
+    static PmeState load(AutogradContext* ctx) {
+        const auto saved = ctx->get_saved_variables();
+        const std::vector<double> scalars = ctx->saved_data["state"].toDoubleVector();
+        PmeState s;
+        const int64_t which = (int64_t)scalars[0];
+        for (size_t i = 0, next = 0; i < kKept; i++)
+            if (which >> i & 1) s.*kept()[i] = saved[next++];
+        s.box_op = scalars[1] != 0; s.order = (int64_t)scalars[2]; s.cutoff = scalars[3]; s.alpha = scalars[4]; s.coulomb = scalars[5];
+        s.grid.assign(scalars.begin() + 6, scalars.end());
+        return s;
+    }
 };
 
+// ---------------------------------------------------------------------------------------------
+// The recorded chain of the five _twice ops (force matching): a term's forward and first-order backward, the same
+// kernels and bits as its default op, recorded so that the backward pass is itself differentiable with respect to positions and charges.
+// As with the pair list, the backward is a Function whose own backward is the double backward; a third derivative raises.
+//     PmeTwiceFunction<Term>           Term::run, keeps what it returned
+//     PmeBackwardFunction<Term>        Term::first_order(state, g) -> {g P, g C}; may add to the state what the next pass reads
+//     PmeDoubleBackwardFunction<Term>  Term::second_order(state, v, w, g), v and w the cotangents of g P and g C
+//                                      -> d/dpositions, d/dcharges, d/dg of g (sum v . P + sum w C)
+// A Term names its op (`op`), counts its arguments (`arguments`: one gradient slot each) and has these three routines:
+// PmeDirectTerm, PmeReciprocalTerm, PmeDirectFramesTerm, PmeReciprocalFramesTerm below, each behind its default op.  The default ops keep
+// their refusal of create_graph=True: the _twice ops are the opt-in.  No box gradient there (the default ops have it).
+// ---------------------------------------------------------------------------------------------
+template <class Term>
+class PmeDoubleBackwardFunction : public torch::autograd::Function<PmeDoubleBackwardFunction<Term>> {
+public:
+    // (g, positions and charges are arguments for their edges: a third derivative reaches backward below and raises)
+    static tensor_list forward(AutogradContext*, const Tensor& v, const Tensor& w, const Tensor& g, const Tensor& positions, const Tensor& charges,
+                               const PmeState& s) {
+        return Term::second_order(s, v, w, g);
+    }
+    static tensor_list backward(AutogradContext*, tensor_list) {
+        TORCH_CHECK(false, Term::op, ": third derivatives are not implemented");
+        return {};
+    }
+};
+
+template <class Term>
+class PmeBackwardFunction : public torch::autograd::Function<PmeBackwardFunction<Term>> {
+public:
+    static tensor_list forward(AutogradContext* ctx, const Tensor& g, const Tensor& positions, const Tensor& charges, PmeState s) {
+        s.g = g;
+        const tensor_list scaled = Term::first_order(s, g);
+        s.save(ctx);
+        return scaled;
+    }
+    static tensor_list backward(AutogradContext* ctx, tensor_list grads) {
+        const PmeState s = PmeState::load(ctx);
+        const tensor_list d = PmeDoubleBackwardFunction<Term>::apply(grads[0], grads[1], s.g, s.positions, s.charges, s);
+        return {d[2], d[0], d[1], Tensor()};
+    }
+};
+
+template <class Term>
+class PmeTwiceFunction : public torch::autograd::Function<PmeTwiceFunction<Term>> {
+public:
+    template <class... Rest>
+    static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Rest&... rest) {
+        static_assert(2 + sizeof...(Rest) == Term::arguments, "one gradient slot for every argument of forward");
+        PmeState s = Term::run(positions, charges, rest...);
+        s.positions = positions;
+        s.charges = charges;
+        s.save(ctx);
+        return s.energy;
+    }
+    static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) {
+        const PmeState s = PmeState::load(ctx);
+        const tensor_list d = PmeBackwardFunction<Term>::apply(grad_outputs[0], s.positions, s.charges, s);
+        tensor_list out(Term::arguments);
+        out[0] = d[0];
+        out[1] = d[1];
+        return out;
+    }
+};
+
+// pme_direct and pme_direct_box in one node: box_vectors is undefined under pme_direct.
 class PmeDirectFunction : public torch::autograd::Function<PmeDirectFunction> {
 public:
-    // the forward pass on either key, shared with pme_direct_box
-    static PmeDirectForward run(const Tensor& positions, const Tensor& charges, const Tensor& neighbors, const Tensor& deltas,
-                                const Tensor& distances, const Tensor& exclusions, const torch::Scalar& alpha, const torch::Scalar& coulomb) {
+    // the forward pass on either key, shared by pme_direct, pme_direct_box and pme_direct_twice: the energy and its derivatives, and the
+    // inputs as the kernels read them
+    static PmeState run(const Tensor& positions, const Tensor& charges, const Tensor& neighbors, const Tensor& deltas,
+                        const Tensor& distances, const Tensor& exclusions, const torch::Scalar& alpha, const torch::Scalar& coulomb) {
         TORCH_CHECK(positions.dim() == 2 && positions.size(1) == 3, "positions must have shape (atoms, 3)");
         TORCH_CHECK(charges.dim() == 1 && charges.size(0) == positions.size(0), "charges must be 1D, one per atom");
         TORCH_CHECK(neighbors.dim() == 2 && neighbors.size(0) == 2, "neighbors must have shape (2, pairs)");
@@ -2541,41 +2658,29 @@ public:
                 }
             energy.fill_((float)e);
         }
-        return {energy, pos_deriv, charge_deriv, pos, q, nb, dl, ds, ex, used_index};
+        PmeState f;
+        f.energy = energy; f.pos_deriv = pos_deriv; f.charge_deriv = charge_deriv;
+        f.pos = pos; f.q = q; f.nb = nb; f.dl = dl; f.ds = ds; f.ex = ex; f.index = used_index;
+        f.alpha = alpha.toDouble(); f.coulomb = coulomb.toDouble();
+        return f;
     }
 
+    // pme_direct_box: pme_direct's forward (same kernels, same bits, the indexed path included) and, when box_vectors needs a gradient,
+    // dE/dB = - sum_k n_k (x) G_k over the included pairs (nnpops_pme_direct_box / the host loop below), computed in the forward pass
+    // like the other derivatives.  No gradient flows into deltas or distances, as with pme_direct: a list whose deltas depend on the box
+    // is not counted twice.
     static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& neighbors,
-                          const Tensor& deltas, const Tensor& distances, const Tensor& exclusions, const torch::Scalar& alpha,
-                          const torch::Scalar& coulomb) {
-        const PmeDirectForward f = run(positions, charges, neighbors, deltas, distances, exclusions, alpha, coulomb);
-        ctx->save_for_backward({f.pos_deriv, f.charge_deriv});
-        return f.energy;
-    }
-
-    static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) {
-        // The derivatives were computed (and detached) in the forward pass: a backward pass that is itself being recorded
-        // (create_graph=True: force matching, Hessians) would silently see d(force)/d(positions, charges) = 0 from here.
-        TORCH_CHECK(!torch::GradMode::is_enabled(),
-                    "pme_direct: second derivatives are not implemented (backward was called with create_graph=True)");
-        const auto saved = ctx->get_saved_variables();
-        return {saved[0] * grad_outputs[0], saved[1] * grad_outputs[0], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
-    }
-};
-
-// pme_direct_box: pme_direct's forward (same kernels, same bits, the indexed path included) and, when box_vectors needs a gradient,
-// dE/dB = - sum_k n_k (x) G_k over the included pairs (nnpops_pme_direct_box / the host loop below), computed in the forward pass
-// like the other derivatives.  No gradient flows into deltas or distances, as with pme_direct: a list whose deltas depend on the box
-// is not counted twice.
-class PmeDirectBoxFunction : public torch::autograd::Function<PmeDirectBoxFunction> {
-public:
-    static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& neighbors,
-                          const Tensor& deltas, const Tensor& distances, const Tensor& exclusions, const Tensor& box_vectors,
+                          const Tensor& deltas, const Tensor& distances, const Tensor& exclusions, const std::optional<Tensor>& box_opt,
                           const torch::Scalar& alpha, const torch::Scalar& coulomb, bool box_grad) {
-        TORCH_CHECK(box_vectors.dim() == 2 && box_vectors.size(0) == 3 && box_vectors.size(1) == 3, "box_vectors must have shape (3, 3)");
-        TORCH_CHECK(box_vectors.scalar_type() == torch::kFloat32, "pme_direct_box computes in float32");
-        TORCH_CHECK(box_vectors.device() == positions.device(), "pme_direct_box: every tensor must be on the device of positions (",
-                    positions.device(), "), got ", box_vectors.device());
-        const PmeDirectForward f = PmeDirectFunction::run(positions, charges, neighbors, deltas, distances, exclusions, alpha, coulomb);
+        const Tensor box_vectors = box_opt.value_or(Tensor());
+        if (box_vectors.defined()) {
+            TORCH_CHECK(box_vectors.dim() == 2 && box_vectors.size(0) == 3 && box_vectors.size(1) == 3, "box_vectors must have shape (3, 3)");
+            TORCH_CHECK(box_vectors.scalar_type() == torch::kFloat32, "pme_direct_box computes in float32");
+            TORCH_CHECK(box_vectors.device() == positions.device(), "pme_direct_box: every tensor must be on the device of positions (",
+                        positions.device(), "), got ", box_vectors.device());
+        }
+        PmeState f = run(positions, charges, neighbors, deltas, distances, exclusions, alpha, coulomb);
+        f.box_op = box_vectors.defined();
         Tensor grad_box;
         if (box_grad) {
             const Tensor box = box_vectors.contiguous();
@@ -2619,25 +2724,28 @@ public:
                 for (int c = 0; c < 9; c++) GB[c] = (float)acc[c];
             }
         }
-        ctx->save_for_backward({f.pos_deriv, f.charge_deriv, grad_box});
+        f.box_deriv = grad_box;
+        f.derivatives().save(ctx);
         return f.energy;
     }
 
     static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) {
-        TORCH_CHECK(!torch::GradMode::is_enabled(),
-                    "pme_direct_box: second derivatives are not implemented (backward was called with create_graph=True)");
-        const auto saved = ctx->get_saved_variables();
-        return {saved[0] * grad_outputs[0], saved[1] * grad_outputs[0], Tensor(), Tensor(), Tensor(), Tensor(),
-                saved[2].defined() ? saved[2] * grad_outputs[0] : Tensor(), Tensor(), Tensor(), Tensor()};
+        const PmeState s = PmeState::load(ctx);
+        // The derivatives were computed (and detached) in the forward pass: a backward pass that is itself being recorded
+        // (create_graph=True: force matching, Hessians) would silently see d(force)/d(positions, charges) = 0 from here.
+        TORCH_CHECK(!torch::GradMode::is_enabled(), s.box_op ? "pme_direct_box" : "pme_direct",
+                    ": second derivatives are not implemented (backward was called with create_graph=True)");
+        tensor_list out(10);                               // (one slot for every argument of forward; box_vectors is the seventh)
+        out[0] = s.pos_deriv * grad_outputs[0];
+        out[1] = s.charge_deriv * grad_outputs[0];
+        if (s.box_deriv.defined()) out[6] = s.box_deriv * grad_outputs[0];
+        return out;
     }
 };
 
 // ---------------------------------------------------------------------------------------------
-// pme_direct_twice: pme_direct's forward and first-order backward (PmeDirectFunction::run, the same kernels and bits), recorded so that
-// the backward pass is itself differentiable with respect to positions and charges (force matching).  As with the
-// pair list: the backward is a Function (PmeDirectBackwardFunction: g -> g P, g C) whose own backward is the double backward
-// (PmeDirectDoubleBackwardFunction: pme_second_order.hip on the device, plain loops on the host); a third derivative raises.
-// pme_direct and pme_direct_box keep their refusal of create_graph=True: this op is the opt-in.
+// pme_direct_twice: PmeDirectFunction::run behind the recorded chain (PmeDirectTerm); the double backward is pme_second_order.hip on the
+// device, plain loops on the host.
 // ---------------------------------------------------------------------------------------------
 // transposed index (pairs_index.hip) of a [2, pairs] int32 list whose unused entries have been replaced by num_atoms
 Tensor pme_build_pair_index(const Tensor& nb, int64_t n) {
@@ -2650,20 +2758,30 @@ Tensor pme_build_pair_index(const Tensor& nb, int64_t n) {
     return index;
 }
 
-class PmeDirectDoubleBackwardFunction : public torch::autograd::Function<PmeDirectDoubleBackwardFunction> {
-public:
-    // (v, w: cotangents of g P and g C) -> d/dpositions, d/dcharges, d/dg of g (sum v . P + sum w C)
-    static tensor_list forward(AutogradContext*, const Tensor& v_in, const Tensor& w_in, const Tensor& g, const Tensor& positions,
-                               const Tensor& charges, const Tensor& pos_deriv, const Tensor& charge_deriv, const Tensor& nb, const Tensor& dl,
-                               const Tensor& ds, const Tensor& ex, const std::optional<Tensor>& index_opt, double alpha, double coulomb) {
-        const Tensor v = v_in.contiguous(), w = w_in.contiguous(), pos = positions.contiguous(), q = charges.contiguous();
+struct PmeDirectTerm {
+    static constexpr const char* op = "pme_direct_twice";
+    static constexpr size_t arguments = 8;
+
+    // (the index the forward pass found in the cache travels with the saved tensors: a later getNeighborPairs call replaces the cache)
+    static PmeState run(const Tensor& positions, const Tensor& charges, const Tensor& neighbors, const Tensor& deltas, const Tensor& distances,
+                        const Tensor& exclusions, const torch::Scalar& alpha, const torch::Scalar& coulomb) {
+        PmeState f = PmeDirectFunction::run(positions, charges, neighbors, deltas, distances, exclusions, alpha, coulomb);
+        f.pos = f.q = Tensor();                            // (a later pass reads the inputs as the caller passed them)
+        return f;
+    }
+
+    static tensor_list first_order(PmeState& s, const Tensor& g) { return {s.pos_deriv * g, s.charge_deriv * g}; }
+
+    static tensor_list second_order(const PmeState& s, const Tensor& v_in, const Tensor& w_in, const Tensor& g) {
+        const Tensor v = v_in.contiguous(), w = w_in.contiguous(), pos = s.positions.contiguous(), q = s.charges.contiguous();
+        const Tensor &nb = s.nb, &dl = s.dl, &ds = s.ds, &ex = s.ex;
         const int64_t n = pos.size(0), pairs = nb.size(1), max_excl = ex.size(1);
         const auto opts = pos.options();
         Tensor gx = torch::empty({n, 3}, opts), gq = torch::empty({n}, opts);
-        const float a = (float)alpha, k = (float)coulomb;
+        const float a = (float)s.alpha, k = (float)s.coulomb;
         if (pos.is_cuda()) {
             c10::hip::HIPGuard guard(pos.device().index());
-            Tensor index = index_opt.value_or(Tensor()), first_index;
+            Tensor index = s.index, first_index;
             if (!index.defined()) {
                 // a list of unknown origin: any order, -1 slots anywhere -- both sides through column segments (nnpops_hip.h)
                 const Tensor clean = torch::where(nb < 0, torch::full({}, n, nb.options()), nb).contiguous();
@@ -2721,52 +2839,7 @@ public:
             for (int64_t i = 0; i < 3 * n; i++) GX[i] = (float)ax[i];
             for (int64_t i = 0; i < n; i++) GQ[i] = (float)aq[i];
         }
-        return {gx * g, gq * g, ((v * pos_deriv).sum() + (w * charge_deriv).sum()).reshape(g.sizes())};
-    }
-
-    static tensor_list backward(AutogradContext*, tensor_list) {
-        TORCH_CHECK(false, "pme_direct_twice: third derivatives are not implemented");
-        return {};
-    }
-};
-
-class PmeDirectBackwardFunction : public torch::autograd::Function<PmeDirectBackwardFunction> {
-public:
-    static tensor_list forward(AutogradContext* ctx, const Tensor& g, const Tensor& positions, const Tensor& charges, const Tensor& pos_deriv,
-                               const Tensor& charge_deriv, const Tensor& nb, const Tensor& dl, const Tensor& ds, const Tensor& ex,
-                               const std::optional<Tensor>& index_opt, double alpha, double coulomb) {
-        ctx->save_for_backward({g, positions, charges, pos_deriv, charge_deriv, nb, dl, ds, ex, index_opt.value_or(Tensor())});
-        ctx->saved_data["alpha"] = alpha;
-        ctx->saved_data["coulomb"] = coulomb;
-        return {pos_deriv * g, charge_deriv * g};
-    }
-
-    static tensor_list backward(AutogradContext* ctx, tensor_list grads) {
-        const auto s = ctx->get_saved_variables();
-        const tensor_list d = PmeDirectDoubleBackwardFunction::apply(grads[0], grads[1], s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], s[8], opt(s[9]),
-                                                                     ctx->saved_data["alpha"].toDouble(), ctx->saved_data["coulomb"].toDouble());
-        return {d[2], d[0], d[1], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
-    }
-};
-
-class PmeDirectTwiceFunction : public torch::autograd::Function<PmeDirectTwiceFunction> {
-public:
-    static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& neighbors,
-                          const Tensor& deltas, const Tensor& distances, const Tensor& exclusions, const torch::Scalar& alpha,
-                          const torch::Scalar& coulomb) {
-        const PmeDirectForward f = PmeDirectFunction::run(positions, charges, neighbors, deltas, distances, exclusions, alpha, coulomb);
-        // (the index the forward pass found in the cache travels with the saved tensors: a later getNeighborPairs call replaces the cache)
-        ctx->save_for_backward({positions, charges, f.pos_deriv, f.charge_deriv, f.nb, f.dl, f.ds, f.ex, f.index});
-        ctx->saved_data["alpha"] = alpha.toDouble();
-        ctx->saved_data["coulomb"] = coulomb.toDouble();
-        return f.energy;
-    }
-
-    static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) {
-        const auto s = ctx->get_saved_variables();
-        const tensor_list d = PmeDirectBackwardFunction::apply(grad_outputs[0], s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], opt(s[8]),
-                                                               ctx->saved_data["alpha"].toDouble(), ctx->saved_data["coulomb"].toDouble());
-        return {d[0], d[1], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+        return {gx * g, gq * g, ((v * s.pos_deriv).sum() + (w * s.charge_deriv).sum()).reshape(g.sizes())};
     }
 };
 
@@ -2883,21 +2956,41 @@ void box_gradient(int64_t n, const float* pos, const float* pos_deriv, const dou
 
 }  // namespace pme_recip_host
 
-// the energy, what the backward passes need, and the inputs as the kernels read them
-struct PmeRecipForward {
-    Tensor energy, q, box, recip, workspace, pos, pi, xm, ym, zm;
-    std::vector<int64_t> grid;
-    int64_t order;
-    double alpha, coulomb;
-};
+// The middle of the single system's device passes, the forward's and the double backward's: a real grid -> rfftn -> the convolution in
+// place, with the Pi sums when `pi` is defined -> the scaled complex grid.  s: the box, alpha and the moduli; what: who raises.
+Tensor pme_recip_convolve(const char* what, const PmeState& s, int n, const Tensor& real, const Tensor& energy, const Tensor& workspace,
+                          const Tensor& pi, void* stream) {
+    const int gx = (int)real.size(0), gy = (int)real.size(1), gz = (int)real.size(2), o = (int)s.order;
+    Tensor recip = torch::fft::rfftn(real).contiguous();
+    if (pi.defined()) {
+        if (nnpops_pme_reciprocal_convolve_box(n, gx, gy, gz, o, s.box.data_ptr<float>(), (float)s.alpha, s.xm.data_ptr<float>(),
+                                               s.ym.data_ptr<float>(), s.zm.data_ptr<float>(), recip.data_ptr(), energy.data_ptr<float>(),
+                                               workspace.data_ptr(), pi.data_ptr(), stream) != NNPOPS_OK)
+            raise_last(what);
+    } else if (nnpops_pme_reciprocal_convolve(n, gx, gy, gz, o, s.box.data_ptr<float>(), (float)s.alpha, s.xm.data_ptr<float>(),
+                                              s.ym.data_ptr<float>(), s.zm.data_ptr<float>(), recip.data_ptr(), energy.data_ptr<float>(),
+                                              workspace.data_ptr(), stream) != NNPOPS_OK)
+        raise_last(what);
+    return recip;
+}
+
+// ... and from the scaled complex grid back to the potential grid (norm "forward": no factor on the way back).  in_double: transformed
+// in double and rounded to float once, for the second-order interpolation on the device: it differences the grid twice, and the float
+// transform's error, white across the grid, grew there with the square of the grid size.  The first-order outputs keep
+// the float transform and their bits.
+Tensor pme_recip_potential(const Tensor& recip, const std::vector<int64_t>& K, bool in_double) {
+    if (!in_double) return torch::fft::irfftn(recip, torch::IntArrayRef(K), c10::nullopt, "forward").contiguous();
+    return torch::fft::irfftn(recip.to(torch::kComplexDouble), torch::IntArrayRef(K), c10::nullopt, "forward").to(torch::kFloat).contiguous();
+}
 
 class PmeReciprocalFunction : public torch::autograd::Function<PmeReciprocalFunction> {
 public:
-    // the forward pass on either key, shared with pme_reciprocal_twice
-    static PmeRecipForward run(const Tensor& positions, const Tensor& charges, const Tensor& box_vectors,
-                          const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz, const torch::Scalar& order,
-                          const torch::Scalar& alpha, const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli,
-                          const Tensor& zmoduli, bool box_grad) {
+    // the forward pass on either key, shared with pme_reciprocal_twice: the energy, what the backward passes need, and the inputs as the
+    // kernels read them
+    static PmeState run(const Tensor& positions, const Tensor& charges, const Tensor& box_vectors,
+                        const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz, const torch::Scalar& order,
+                        const torch::Scalar& alpha, const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli,
+                        const Tensor& zmoduli, bool box_grad) {
         TORCH_CHECK(positions.dim() == 2 && positions.size(1) == 3, "positions must have shape (atoms, 3)");
         TORCH_CHECK(charges.dim() == 1 && charges.size(0) == positions.size(0), "charges must be 1D, one per atom");
         TORCH_CHECK(box_vectors.dim() == 2 && box_vectors.size(0) == 3 && box_vectors.size(1) == 3, "box_vectors must have shape (3, 3)");
@@ -2922,29 +3015,25 @@ public:
         const int64_t n = positions.size(0);
         const auto opts = positions.options();
         // box_grad: the box gradient -B^-T (Pi + X) (pme_recip.hip): Pi is summed here, X in the backward from the position derivatives
+        PmeState f;
+        f.pos = pos; f.q = q; f.box = box; f.xm = xm; f.ym = ym; f.zm = zm;
+        f.grid = {K[0], K[1], K[2]}; f.order = pme_order; f.alpha = a; f.coulomb = k;
         Tensor energy, recip, workspace, pi;
         if (positions.is_cuda()) {
             TORCH_CHECK(pme_order == 4 || pme_order == 5, "pme_reciprocal: Only pmeOrder 4 or 5 is supported on the device (got ", pme_order, ")");
             c10::hip::HIPGuard guard(positions.device().index());
             void* stream = current_stream(positions.device());
-            const int gx = (int)K[0], gy = (int)K[1], gz = (int)K[2], o = (int)pme_order;
-            workspace = torch::empty({nnpops_pme_reciprocal_workspace_bytes((int)n, gx, gy, gz, o)}, opts.dtype(torch::kUInt8));
+            workspace = torch::empty({nnpops_pme_reciprocal_workspace_bytes((int)n, (int)K[0], (int)K[1], (int)K[2], (int)pme_order)},
+                                     opts.dtype(torch::kUInt8));
             Tensor real = torch::empty({K[0], K[1], K[2]}, opts);
-            if (nnpops_pme_reciprocal_spread((int)n, gx, gy, gz, o, pos.data_ptr<float>(), q.data_ptr<float>(), box.data_ptr<float>(), (float)k,
-                                             real.data_ptr<float>(), workspace.data_ptr(), stream) != NNPOPS_OK)
+            if (nnpops_pme_reciprocal_spread((int)n, (int)K[0], (int)K[1], (int)K[2], (int)pme_order, pos.data_ptr<float>(), q.data_ptr<float>(),
+                                             box.data_ptr<float>(), (float)k, real.data_ptr<float>(), workspace.data_ptr(), stream) != NNPOPS_OK)
                 raise_last("pme::pme_reciprocal");
-            recip = torch::fft::rfftn(real).contiguous();
             energy = torch::empty({}, opts);
-            if (box_grad) {
-                pi = torch::empty({nnpops_pme_reciprocal_box_workspace_bytes((int)n, gx, gy, gz, o)}, opts.dtype(torch::kUInt8));
-                if (nnpops_pme_reciprocal_convolve_box((int)n, gx, gy, gz, o, box.data_ptr<float>(), (float)a, xm.data_ptr<float>(),
-                                                       ym.data_ptr<float>(), zm.data_ptr<float>(), recip.data_ptr(), energy.data_ptr<float>(),
-                                                       workspace.data_ptr(), pi.data_ptr(), stream) != NNPOPS_OK)
-                    raise_last("pme::pme_reciprocal");
-            } else if (nnpops_pme_reciprocal_convolve((int)n, gx, gy, gz, o, box.data_ptr<float>(), (float)a, xm.data_ptr<float>(), ym.data_ptr<float>(),
-                                               zm.data_ptr<float>(), recip.data_ptr(), energy.data_ptr<float>(), workspace.data_ptr(),
-                                               stream) != NNPOPS_OK)
-                raise_last("pme::pme_reciprocal");
+            if (box_grad)
+                pi = torch::empty({nnpops_pme_reciprocal_box_workspace_bytes((int)n, (int)K[0], (int)K[1], (int)K[2], (int)pme_order)},
+                                  opts.dtype(torch::kUInt8));
+            recip = pme_recip_convolve("pme::pme_reciprocal", f, (int)n, real, energy, workspace, pi, stream);
         } else {
             // host tensors: the reference registers a CPU kernel (pmeCPU.cpp:174-364); plain loops, double energy
             using namespace pme_recip_host;
@@ -3004,23 +3093,20 @@ public:
             energy = torch::full({}, (float)(0.5 * e), opts);
             if (box_grad) pi = torch::tensor(std::vector<double>(PS, PS + 6), opts.dtype(torch::kFloat64));
         }
-        return {energy, q, box, recip, workspace, pos, pi, xm, ym, zm, std::vector<int64_t>{K[0], K[1], K[2]}, pme_order, a, k};
+        f.energy = energy; f.recip = recip; f.workspace = workspace; f.pi = pi;
+        return f;
     }
 
     static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& box_vectors,
                           const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz, const torch::Scalar& order,
                           const torch::Scalar& alpha, const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli,
                           const Tensor& zmoduli, bool box_grad) {
-        const PmeRecipForward f = run(positions, charges, box_vectors, gridx, gridy, gridz, order, alpha, coulomb, xmoduli, ymoduli, zmoduli, box_grad);
-        // (the device path keeps the splines in the workspace and does not need the positions again, unless for the box gradient)
-        const Tensor none = torch::empty({0}, positions.options());
-        if (box_grad)
-            ctx->save_for_backward({f.q, f.box, f.recip, f.workspace.defined() ? f.workspace : none, f.pos, f.pi});
-        else
-            ctx->save_for_backward({f.q, f.box, f.recip, f.workspace.defined() ? f.workspace : none, positions.is_cuda() ? none : f.pos});
-        ctx->saved_data["grid"] = f.grid;
-        ctx->saved_data["order"] = f.order;
-        ctx->saved_data["coulomb"] = f.coulomb;
+        PmeState f = run(positions, charges, box_vectors, gridx, gridy, gridz, order, alpha, coulomb, xmoduli, ymoduli, zmoduli, box_grad);
+        // (the device path keeps the splines in the workspace and does not need the positions again, unless for the box gradient; no pass
+        // of this node reads the moduli again)
+        if (positions.is_cuda() && !box_grad) f.pos = Tensor();
+        f.xm = f.ym = f.zm = Tensor();
+        f.save(ctx);
         return f.energy;
     }
 
@@ -3071,81 +3157,96 @@ public:
         }
     }
 
+    // the first-order backward on either key, shared with pme_reciprocal_twice: the float inverse transform (kept in s.phi), then
+    // s.pos_deriv and s.charge_deriv (unscaled) through interpolate
+    static void derivatives(PmeState& s, const Tensor& q, const Tensor& pos) {
+        const int64_t n = q.size(0);
+        s.phi = pme_recip_potential(s.recip, s.grid, false);
+        s.pos_deriv = torch::empty({n, 3}, q.options());
+        s.charge_deriv = torch::empty({n}, q.options());
+        interpolate(s.phi, q, s.box, s.workspace, pos, s.grid, s.order, s.coulomb, s.pos_deriv, s.charge_deriv);
+    }
+
     static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) {
         TORCH_CHECK(!torch::GradMode::is_enabled(),
                     "pme_reciprocal: second derivatives are not implemented (backward was called with create_graph=True)");
-        const auto saved = ctx->get_saved_variables();
-        const Tensor q = saved[0], box = saved[1], recip = saved[2], workspace = saved[3], pos = saved[4];
-        const std::vector<int64_t> K = ctx->saved_data["grid"].toIntVector();
-        const int64_t pme_order = ctx->saved_data["order"].toInt();
-        const double k = ctx->saved_data["coulomb"].toDouble();
-        const int64_t n = q.size(0);
-        const Tensor grid = torch::fft::irfftn(recip, torch::IntArrayRef(K), c10::nullopt, "forward").contiguous();
-        const auto opts = q.options();
-        Tensor pos_deriv = torch::empty({n, 3}, opts), charge_deriv = torch::empty({n}, opts);
-        interpolate(grid, q, box, workspace, pos, K, pme_order, k, pos_deriv, charge_deriv);
-        Tensor grad_box;
-        if (saved.size() > 5) {
-            const Tensor pi = saved[5];
-            grad_box = torch::empty({3, 3}, opts);
-            if (q.is_cuda()) {
-                c10::hip::HIPGuard guard(q.device().index());
-                if (nnpops_pme_reciprocal_box_gradient((int)n, (int)K[0], (int)K[1], (int)K[2], (int)pme_order, pos.data_ptr<float>(),
-                                                       box.data_ptr<float>(), pos_deriv.data_ptr<float>(), grad_box.data_ptr<float>(),
-                                                       pi.data_ptr(), current_stream(q.device())) != NNPOPS_OK)
+        PmeState s = PmeState::load(ctx);
+        const int64_t n = s.q.size(0);
+        derivatives(s, s.q, s.pos);
+        tensor_list out(13);                               // (one slot for every argument of forward; box_vectors is the third)
+        out[0] = s.pos_deriv * grad_outputs[0];
+        out[1] = s.charge_deriv * grad_outputs[0];
+        if (s.pi.defined()) {
+            Tensor grad_box = torch::empty({3, 3}, s.q.options());
+            if (s.q.is_cuda()) {
+                c10::hip::HIPGuard guard(s.q.device().index());
+                if (nnpops_pme_reciprocal_box_gradient((int)n, (int)s.grid[0], (int)s.grid[1], (int)s.grid[2], (int)s.order, s.pos.data_ptr<float>(),
+                                                       s.box.data_ptr<float>(), s.pos_deriv.data_ptr<float>(), grad_box.data_ptr<float>(),
+                                                       s.pi.data_ptr(), current_stream(s.q.device())) != NNPOPS_OK)
                     raise_last("pme::pme_reciprocal");
             } else {
-                pme_recip_host::box_gradient(n, pos.data_ptr<float>(), pos_deriv.data_ptr<float>(), pi.data_ptr<double>(),
-                                             box.data_ptr<float>(), grad_box.data_ptr<float>());
+                pme_recip_host::box_gradient(n, s.pos.data_ptr<float>(), s.pos_deriv.data_ptr<float>(), s.pi.data_ptr<double>(),
+                                             s.box.data_ptr<float>(), grad_box.data_ptr<float>());
             }
-            grad_box = grad_box * grad_outputs[0];
+            out[2] = grad_box * grad_outputs[0];
         }
-        return {pos_deriv * grad_outputs[0], charge_deriv * grad_outputs[0], grad_box, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(),
-                Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+        return out;
     }
 };
 
 // ---------------------------------------------------------------------------------------------
-// pme_reciprocal_twice: pme_reciprocal's forward and first-order backward (PmeReciprocalFunction::run / ::interpolate, the same kernels
-// and bits), recorded so that the backward pass is itself differentiable with respect to positions and charges.
-//     PmeRecipBackwardFunction        g -> g P, g C; keeps the potential grid phi (the irfftn it needed anyway) for the next pass
-//     PmeRecipDoubleBackwardFunction  (v, w) -> spread of Q' -> rfftn -> the existing convolution -> irfftn = phi' -> two-grid
-//                                     interpolation (pme_recip.hip); plain loops on the host
-// No box gradient (the default ops have it) and no third derivative: both raise.
+// pme_reciprocal_twice: PmeReciprocalFunction::run / ::derivatives behind the recorded chain (PmeReciprocalTerm):
+//     first_order   g -> g P, g C; keeps the potential grid phi (the irfftn it needed anyway) for the next pass
+//     second_order  (v, w) -> spread of Q' -> rfftn -> the existing convolution -> irfftn = phi' -> two-grid interpolation
+//                   (pme_recip.hip); plain loops on the host
 // ---------------------------------------------------------------------------------------------
-class PmeRecipDoubleBackwardFunction : public torch::autograd::Function<PmeRecipDoubleBackwardFunction> {
-public:
-    static tensor_list forward(AutogradContext*, const Tensor& v_in, const Tensor& w_in, const Tensor& g, const Tensor& positions,
-                               const Tensor& charges, const Tensor& box, const Tensor& workspace, const Tensor& xm, const Tensor& ym,
-                               const Tensor& zm, const Tensor& phi, const Tensor& pos_deriv, const Tensor& charge_deriv,
-                               std::vector<int64_t> K, int64_t pme_order, double alpha, double k) {
-        const Tensor v = v_in.contiguous(), w = w_in.contiguous(), pos = positions.contiguous(), q = charges.contiguous();
-        const int64_t n = q.size(0);
+struct PmeReciprocalTerm {
+    static constexpr const char* op = "pme_reciprocal_twice";
+    static constexpr size_t arguments = 12;
+
+    static PmeState run(const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const torch::Scalar& gridx,
+                        const torch::Scalar& gridy, const torch::Scalar& gridz, const torch::Scalar& order, const torch::Scalar& alpha,
+                        const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli, const Tensor& zmoduli) {
+        TORCH_CHECK(order.toLong() >= 4, "pme_reciprocal_twice: order must be at least 4 (below that the second derivatives of the B-spline "
+                    "weights are not continuous), got ", order.toLong());
+        PmeState f = PmeReciprocalFunction::run(positions, charges, box_vectors, gridx, gridy, gridz, order, alpha, coulomb, xmoduli, ymoduli,
+                                                zmoduli, false);
+        f.pos = f.q = Tensor();                            // (a later pass reads the inputs as the caller passed them)
+        return f;
+    }
+
+    static tensor_list first_order(PmeState& s, const Tensor& g) {
+        PmeReciprocalFunction::derivatives(s, s.charges.contiguous(), s.positions.contiguous());
+        return {s.pos_deriv * g, s.charge_deriv * g};
+    }
+
+    static tensor_list second_order(const PmeState& s, const Tensor& v_in, const Tensor& w_in, const Tensor& g) {
+        const Tensor v = v_in.contiguous(), w = w_in.contiguous(), pos = s.positions.contiguous(), q = s.charges.contiguous();
+        const Tensor &box = s.box, &xm = s.xm, &ym = s.ym, &zm = s.zm;
+        const std::vector<int64_t>& K = s.grid;
+        const int64_t n = q.size(0), pme_order = s.order;
+        const double alpha = s.alpha, k = s.coulomb;
         const auto opts = q.options();
+        // (on the device not the first-order pass's float phi: pme_recip_potential)
+        const Tensor phi = q.is_cuda() ? pme_recip_potential(s.recip, K, true) : s.phi;
         Tensor gx = torch::empty({n, 3}, opts), gq = torch::empty({n}, opts);
         if (q.is_cuda()) {
             c10::hip::HIPGuard guard(q.device().index());
             void* stream = current_stream(q.device());
+            const char* what = "pme::pme_reciprocal_twice (double backward)";
             const int kx = (int)K[0], ky = (int)K[1], kz = (int)K[2], o = (int)pme_order;
             Tensor second = torch::empty({nnpops_pme_reciprocal_second_workspace_bytes((int)n, kx, ky, kz, o)}, opts.dtype(torch::kUInt8));
             Tensor real = torch::empty({K[0], K[1], K[2]}, opts);
             if (nnpops_pme_reciprocal_spread_directional((int)n, kx, ky, kz, o, pos.data_ptr<float>(), q.data_ptr<float>(), box.data_ptr<float>(),
                                                          (float)k, v.data_ptr<float>(), w.data_ptr<float>(), real.data_ptr<float>(),
-                                                         workspace.data_ptr(), second.data_ptr(), stream) != NNPOPS_OK)
-                raise_last("pme::pme_reciprocal_twice (double backward)");
-            Tensor recip = torch::fft::rfftn(real).contiguous();
-            Tensor unused = torch::empty({}, opts);
-            if (nnpops_pme_reciprocal_convolve((int)n, kx, ky, kz, o, box.data_ptr<float>(), (float)alpha, xm.data_ptr<float>(), ym.data_ptr<float>(),
-                                               zm.data_ptr<float>(), recip.data_ptr(), unused.data_ptr<float>(), workspace.data_ptr(),
-                                               stream) != NNPOPS_OK)
-                raise_last("pme::pme_reciprocal_twice (double backward)");
-            // (the inverse transform in double, as for phi: PmeRecipBackwardFunction::backward)
-            const Tensor phi2 = torch::fft::irfftn(recip.to(torch::kComplexDouble), torch::IntArrayRef(K), c10::nullopt, "forward")
-                                    .to(torch::kFloat).contiguous();
+                                                         s.workspace.data_ptr(), second.data_ptr(), stream) != NNPOPS_OK)
+                raise_last(what);
+            const Tensor recip = pme_recip_convolve(what, s, (int)n, real, torch::empty({}, opts), s.workspace, Tensor(), stream);
+            const Tensor phi2 = pme_recip_potential(recip, K, true);
             if (nnpops_pme_reciprocal_interpolate_second((int)n, kx, ky, kz, o, q.data_ptr<float>(), box.data_ptr<float>(), (float)k,
                                                          w.data_ptr<float>(), phi.data_ptr<float>(), phi2.data_ptr<float>(), gx.data_ptr<float>(),
-                                                         gq.data_ptr<float>(), workspace.data_ptr(), second.data_ptr(), stream) != NNPOPS_OK)
-                raise_last("pme::pme_reciprocal_twice (double backward)");
+                                                         gq.data_ptr<float>(), s.workspace.data_ptr(), second.data_ptr(), stream) != NNPOPS_OK)
+                raise_last(what);
         } else {
             using namespace pme_recip_host;
             const float* B = box.data_ptr<float>();
@@ -3222,74 +3323,7 @@ public:
                 GX[3 * atom + 2] = (float)(fx * r.m[2][0] + fy * r.m[2][1] + fz * r.m[2][2]);
             }
         }
-        return {gx * g, gq * g, ((v * pos_deriv).sum() + (w * charge_deriv).sum()).reshape(g.sizes())};
-    }
-
-    static tensor_list backward(AutogradContext*, tensor_list) {
-        TORCH_CHECK(false, "pme_reciprocal_twice: third derivatives are not implemented");
-        return {};
-    }
-};
-
-class PmeRecipBackwardFunction : public torch::autograd::Function<PmeRecipBackwardFunction> {
-public:
-    static tensor_list forward(AutogradContext* ctx, const Tensor& g, const Tensor& positions, const Tensor& charges, const Tensor& box,
-                               const Tensor& recip, const Tensor& workspace, const Tensor& xm, const Tensor& ym, const Tensor& zm,
-                               std::vector<int64_t> K, int64_t pme_order, double alpha, double k) {
-        const Tensor pos = positions.contiguous(), q = charges.contiguous();
-        const int64_t n = q.size(0);
-        const Tensor phi = torch::fft::irfftn(recip, torch::IntArrayRef(K), c10::nullopt, "forward").contiguous();
-        Tensor pos_deriv = torch::empty({n, 3}, q.options()), charge_deriv = torch::empty({n}, q.options());
-        PmeReciprocalFunction::interpolate(phi, q, box, workspace, pos, K, pme_order, k, pos_deriv, charge_deriv);
-        ctx->save_for_backward({g, positions, charges, box, workspace, xm, ym, zm, phi, pos_deriv, charge_deriv, recip});
-        ctx->saved_data["grid"] = K;
-        ctx->saved_data["order"] = pme_order;
-        ctx->saved_data["alpha"] = alpha;
-        ctx->saved_data["coulomb"] = k;
-        return {pos_deriv * g, charge_deriv * g};
-    }
-
-    static tensor_list backward(AutogradContext* ctx, tensor_list grads) {
-        const auto s = ctx->get_saved_variables();
-        // On the device the second-order interpolation reads a potential grid transformed back in double and rounded once: it
-        // differences phi twice, and the float transform's error, white across the grid, grew there with the square of the grid size
-        // (DESIGN.md s8b).  The first-order outputs keep the float transform and their bits.
-        const std::vector<int64_t> K = ctx->saved_data["grid"].toIntVector();
-        const Tensor phi = s[1].is_cuda() ? torch::fft::irfftn(s[11].to(torch::kComplexDouble), torch::IntArrayRef(K), c10::nullopt, "forward")
-                                                .to(torch::kFloat).contiguous()
-                                          : s[8];
-        const tensor_list d = PmeRecipDoubleBackwardFunction::apply(grads[0], grads[1], s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], phi, s[9], s[10],
-                                                                    K, ctx->saved_data["order"].toInt(),
-                                                                    ctx->saved_data["alpha"].toDouble(), ctx->saved_data["coulomb"].toDouble());
-        return {d[2], d[0], d[1], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
-    }
-};
-
-class PmeReciprocalTwiceFunction : public torch::autograd::Function<PmeReciprocalTwiceFunction> {
-public:
-    static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& box_vectors,
-                          const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz, const torch::Scalar& order,
-                          const torch::Scalar& alpha, const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli,
-                          const Tensor& zmoduli) {
-        TORCH_CHECK(order.toLong() >= 4, "pme_reciprocal_twice: order must be at least 4 (below that the second derivatives of the B-spline "
-                    "weights are not continuous), got ", order.toLong());
-        const PmeRecipForward f = PmeReciprocalFunction::run(positions, charges, box_vectors, gridx, gridy, gridz, order, alpha, coulomb, xmoduli,
-                                                             ymoduli, zmoduli, false);
-        const Tensor none = torch::empty({0}, positions.options());
-        ctx->save_for_backward({positions, charges, f.box, f.recip, f.workspace.defined() ? f.workspace : none, f.xm, f.ym, f.zm});
-        ctx->saved_data["grid"] = f.grid;
-        ctx->saved_data["order"] = f.order;
-        ctx->saved_data["alpha"] = f.alpha;
-        ctx->saved_data["coulomb"] = f.coulomb;
-        return f.energy;
-    }
-
-    static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) {
-        const auto s = ctx->get_saved_variables();
-        const tensor_list d = PmeRecipBackwardFunction::apply(grad_outputs[0], s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7],
-                                                              ctx->saved_data["grid"].toIntVector(), ctx->saved_data["order"].toInt(),
-                                                              ctx->saved_data["alpha"].toDouble(), ctx->saved_data["coulomb"].toDouble());
-        return {d[0], d[1], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+        return {gx * g, gq * g, ((v * s.pos_deriv).sum() + (w * s.charge_deriv).sum()).reshape(g.sizes())};
     }
 };
 
@@ -3311,7 +3345,8 @@ Tensor pme_direct_box_entry(const Tensor& positions, const Tensor& charges, cons
                             const Tensor& distances, const Tensor& exclusions, const Tensor& box_vectors, const torch::Scalar& alpha,
                             const torch::Scalar& coulomb) {
     const bool box_grad = torch::GradMode::is_enabled() && box_vectors.requires_grad();
-    return PmeDirectBoxFunction::apply(positions, charges, neighbors, deltas, distances, exclusions, box_vectors, alpha, coulomb, box_grad);
+    return PmeDirectFunction::apply(positions, charges, neighbors, deltas, distances, exclusions, std::optional<Tensor>(box_vectors), alpha,
+                                    coulomb, box_grad);
 }
 
 Tensor pme_reciprocal_entry(const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const torch::Scalar& gridx,
@@ -3325,7 +3360,7 @@ Tensor pme_reciprocal_entry(const Tensor& positions, const Tensor& charges, cons
 
 Tensor pme_direct_twice_entry(const Tensor& positions, const Tensor& charges, const Tensor& neighbors, const Tensor& deltas,
                               const Tensor& distances, const Tensor& exclusions, const torch::Scalar& alpha, const torch::Scalar& coulomb) {
-    return PmeDirectTwiceFunction::apply(positions, charges, neighbors, deltas, distances, exclusions, alpha, coulomb);
+    return PmeTwiceFunction<PmeDirectTerm>::apply(positions, charges, neighbors, deltas, distances, exclusions, alpha, coulomb);
 }
 
 Tensor pme_reciprocal_twice_entry(const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const torch::Scalar& gridx,
@@ -3335,13 +3370,14 @@ Tensor pme_reciprocal_twice_entry(const Tensor& positions, const Tensor& charges
     TORCH_CHECK(!(torch::GradMode::is_enabled() && box_vectors.requires_grad()),
                 "pme_reciprocal_twice: box gradients need the default ops (pme_reciprocal; PME without twice_differentiable=True): the "
                 "twice-differentiable ops return no box gradient");
-    return PmeReciprocalTwiceFunction::apply(positions, charges, box_vectors, gridx, gridy, gridz, order, alpha, coulomb, xmoduli, ymoduli,
-                                             zmoduli);
+    return PmeTwiceFunction<PmeReciprocalTerm>::apply(positions, charges, box_vectors, gridx, gridy, gridz, order, alpha, coulomb, xmoduli,
+                                                      ymoduli, zmoduli);
 }
 
 Tensor pme_direct_entry(const Tensor& positions, const Tensor& charges, const Tensor& neighbors, const Tensor& deltas,
                         const Tensor& distances, const Tensor& exclusions, const torch::Scalar& alpha, const torch::Scalar& coulomb) {
-    return PmeDirectFunction::apply(positions, charges, neighbors, deltas, distances, exclusions, alpha, coulomb);
+    return PmeDirectFunction::apply(positions, charges, neighbors, deltas, distances, exclusions, std::optional<Tensor>(), alpha, coulomb,
+                                    false);
 }
 
 TORCH_LIBRARY_IMPL(pme, AutogradCUDA, m) {
@@ -3397,7 +3433,22 @@ Tensor pme_frames_table_entry(const Tensor& offsets, c10::Device device) {
     return table.to(device);
 }
 
-struct PmeFramesShape { int64_t frames, atoms, tiles; };
+// The table pme::pmeFramesTable returned, seen as its parts (nnpops_hip.h: {B, N, T, 0} | offsets [B + 1] | tile_start [B + 1] |
+// tiles [T][4] | atom_frame [N]) for a batch of `frames` frames and `atoms` atoms: the tile count T follows from the length.  The only
+// code here that knows the layout.
+struct PmeFramesTable {
+    Tensor table;
+    int64_t frames, atoms, rest, tiles;
+    PmeFramesTable(const Tensor& table, int64_t frames, int64_t atoms)
+        : table(table), frames(frames), atoms(atoms), rest(table.numel() - 4 - 2 * (frames + 1) - atoms), tiles(rest / 4) {}
+    // whether a table of this length can describe such a batch
+    bool fits() const {
+        return rest >= 0 && rest % 4 == 0 && tiles >= (atoms + NNPOPS_PME_FRAMES_TILE - 1) / NNPOPS_PME_FRAMES_TILE && tiles <= atoms;
+    }
+    const int32_t* data() const { return table.data_ptr<int32_t>(); }
+    const int32_t* offsets() const { return data() + 4; }
+    Tensor atom_frame() const { return table.narrow(0, 4 + 2 * (frames + 1) + 4 * tiles, atoms); }
+};
 
 // The transforms of a batch of grids [B, Kx, Ky, Kz] in two steps: real along z, complex over (x, y).  The library's single batched
 // three-dimensional real transform returned wrong values for some shapes after transforms of other shapes in the same process
@@ -3414,7 +3465,7 @@ Tensor pme_frames_irfftn(const Tensor& recip, int64_t kz) {      // norm "forwar
 
 // what the ops check of their common arguments; the tile count follows from the table's length.  box_op: the two _box ops, which
 // take a box that requires a gradient.
-PmeFramesShape pme_frames_check(const char* op, const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table,
+PmeFramesTable pme_frames_check(const char* op, const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table,
                                 bool box_op = false) {
     TORCH_CHECK(positions.is_cuda(), op, ": device tensors only (the frames ops have no CPU key)");
     TORCH_CHECK(positions.dim() == 2 && positions.size(1) == 3, op, ": positions must have shape (atoms, 3)");
@@ -3430,102 +3481,139 @@ PmeFramesShape pme_frames_check(const char* op, const Tensor& positions, const T
     for (const Tensor* t : {&charges, &box_vectors, &table})
         TORCH_CHECK(t->device() == positions.device(), op, ": every tensor must be on the device of positions (", positions.device(), "), got ",
                     t->device());
-    PmeFramesShape s{box_vectors.size(0), positions.size(0), 0};
-    TORCH_CHECK(s.atoms <= std::numeric_limits<int32_t>::max() / 8 && s.frames <= std::numeric_limits<int32_t>::max() / 8, op, ": batch too large");
-    const int64_t rest = table.numel() - 4 - 2 * (s.frames + 1) - s.atoms;
-    TORCH_CHECK(rest >= 0 && rest % 4 == 0 && rest / 4 >= (s.atoms + NNPOPS_PME_FRAMES_TILE - 1) / NNPOPS_PME_FRAMES_TILE &&
-                rest / 4 <= s.atoms, op, ": table does not describe ", s.frames, " frames of ", s.atoms,
+    const PmeFramesTable t(table, box_vectors.size(0), positions.size(0));
+    TORCH_CHECK(t.atoms <= std::numeric_limits<int32_t>::max() / 8 && t.frames <= std::numeric_limits<int32_t>::max() / 8, op, ": batch too large");
+    TORCH_CHECK(t.fits(), op, ": table does not describe ", t.frames, " frames of ", t.atoms,
                 " atoms in all (offsets must end at the number of atoms, box_vectors must hold one box per frame)");
-    s.tiles = rest / 4;
-    return s;
+    return t;
 }
 
 // every frame's rows of the kept derivatives times that frame's upstream gradient
 tensor_list pme_frames_scale(const char* op, const Tensor& pos_deriv, const Tensor& charge_deriv, const Tensor& table, const Tensor& grad) {
     TORCH_CHECK(!torch::GradMode::is_enabled(), op, ": second derivatives are not implemented (backward was called with create_graph=True)");
-    const int64_t n = charge_deriv.size(0), frames = grad.numel();
-    const int64_t tiles = (table.numel() - 4 - 2 * (frames + 1) - n) / 4;
+    const PmeFramesTable t(table, grad.numel(), charge_deriv.size(0));
     const Tensor g = grad.contiguous();
     TORCH_CHECK(g.device() == pos_deriv.device() && (g.scalar_type() == torch::kFloat32 || g.scalar_type() == torch::kFloat64), op,
                 ": unexpected gradient of the energies");
     Tensor out = torch::empty_like(pos_deriv);
-    if (n == 0) return {out, torch::empty_like(charge_deriv)};
+    if (t.atoms == 0) return {out, torch::empty_like(charge_deriv)};
     c10::hip::HIPGuard guard(pos_deriv.device().index());
-    if (nnpops_scale_by_segment(current_stream(pos_deriv.device()), pos_deriv.data_ptr<float>(), (int)n, table.data_ptr<int32_t>() + 4, (int)frames,
+    if (nnpops_scale_by_segment(current_stream(pos_deriv.device()), pos_deriv.data_ptr<float>(), (int)t.atoms, t.offsets(), (int)t.frames,
                                 g.data_ptr(), g.scalar_type() == torch::kFloat64 ? 1 : 0, out.data_ptr<float>()) != NNPOPS_OK)
         raise_last(op);
-    const Tensor atom_frame = table.narrow(0, 4 + 2 * (frames + 1) + 4 * tiles, n);
-    return {out, charge_deriv * g.to(torch::kFloat32).index_select(0, atom_frame)};
+    return {out, charge_deriv * g.to(torch::kFloat32).index_select(0, t.atom_frame())};
 }
 
-// the box gradient the _box ops saved (fourth, when there is one) times every frame's upstream gradient
-Tensor pme_frames_box_scale(const torch::autograd::variable_list& saved, const Tensor& grad) {
-    return saved.size() > 3 ? saved[3] * grad.to(torch::kFloat32).reshape({-1, 1, 1}) : Tensor();
+// the first-order backward of the default frames ops: the kept derivatives (s.derivatives()) times every frame's upstream gradient,
+// the box gradient of the _box ops into `box_slot` of the `slots` arguments of their forward
+tensor_list pme_frames_backward(const char* op, const PmeState& s, const Tensor& grad, size_t slots, size_t box_slot) {
+    const tensor_list g = pme_frames_scale(op, s.pos_deriv, s.charge_deriv, s.table, grad);
+    tensor_list out(slots);
+    out[0] = g[0];
+    out[1] = g[1];
+    if (s.box_deriv.defined()) out[box_slot] = s.box_deriv * grad.to(torch::kFloat32).reshape({-1, 1, 1});
+    return out;
 }
 
 class PmeDirectFramesFunction : public torch::autograd::Function<PmeDirectFramesFunction> {
 public:
-    static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& exclusions,
-                          const Tensor& box_vectors, const Tensor& table, const torch::Scalar& cutoff, const torch::Scalar& alpha,
-                          const torch::Scalar& coulomb, bool box_op, bool box_grad, tensor_list* kept = nullptr) {
-        // kept: the _twice op runs this forward and saves for itself (exclusions, boxes, dE/dpositions, dE/dcharges)
-        const char* op = kept ? "pme_direct_frames_twice" : box_op ? "pme_direct_frames_box" : "pme_direct_frames";
+    // the forward pass of pme_direct_frames, pme_direct_frames_box and pme_direct_frames_twice (op: which; it names itself when it
+    // raises): the energies, dE/dpositions and dE/dcharges, dE/dboxes with box_grad, and the exclusions and boxes as the kernels read them
+    static PmeState run(const char* op, const Tensor& positions, const Tensor& charges, const Tensor& exclusions, const Tensor& box_vectors,
+                        const Tensor& table, const torch::Scalar& cutoff, const torch::Scalar& alpha, const torch::Scalar& coulomb, bool box_op,
+                        bool box_grad) {
         const std::string qualified = std::string("pme::") + op;
-        ctx->saved_data["box_op"] = box_op;
-        const PmeFramesShape s = pme_frames_check(op, positions, charges, box_vectors, table, box_op);
-        TORCH_CHECK(exclusions.dim() == 2 && exclusions.size(0) == s.atoms && exclusions.device() == positions.device() &&
+        const PmeFramesTable t = pme_frames_check(op, positions, charges, box_vectors, table, box_op);
+        TORCH_CHECK(exclusions.dim() == 2 && exclusions.size(0) == t.atoms && exclusions.device() == positions.device() &&
                     at::isIntegralType(exclusions.scalar_type(), false), op, ": exclusions must be integers of shape (atoms, max_exclusions) on the device of positions");
-        const Tensor pos = positions.contiguous(), q = charges.contiguous(), ex = exclusions.to(torch::kInt32).contiguous(),
-                     boxes = box_vectors.contiguous();
+        const Tensor pos = positions.contiguous(), q = charges.contiguous();
         const auto opts = positions.options();
-        Tensor energies = torch::empty({s.frames}, opts), pos_deriv = torch::empty({s.atoms, 3}, opts), charge_deriv = torch::empty({s.atoms}, opts);
-        Tensor workspace = torch::empty({nnpops_pme_direct_frames_workspace_bytes((int)s.tiles)}, opts.dtype(torch::kUInt8));
-        const int64_t max_excl = ex.size(1);
+        PmeState f;
+        f.ex = exclusions.to(torch::kInt32).contiguous(); f.box = box_vectors.contiguous(); f.table = table;
+        f.cutoff = cutoff.toDouble(); f.alpha = alpha.toDouble(); f.coulomb = coulomb.toDouble(); f.box_op = box_op;
+        f.energy = torch::empty({t.frames}, opts); f.pos_deriv = torch::empty({t.atoms, 3}, opts); f.charge_deriv = torch::empty({t.atoms}, opts);
+        Tensor workspace = torch::empty({nnpops_pme_direct_frames_workspace_bytes((int)t.tiles)}, opts.dtype(torch::kUInt8));
+        const int64_t max_excl = f.ex.size(1);
         c10::hip::HIPGuard guard(positions.device().index());
-        if (nnpops_pme_direct_frames((int)s.atoms, (int)s.frames, (int)s.tiles, (int)max_excl, table.data_ptr<int32_t>(), pos.data_ptr<float>(),
-                                     q.data_ptr<float>(), max_excl ? ex.data_ptr<int32_t>() : nullptr, boxes.data_ptr<float>(),
-                                     (float)cutoff.toDouble(), (float)alpha.toDouble(), (float)coulomb.toDouble(), energies.data_ptr<float>(),
-                                     pos_deriv.data_ptr<float>(), charge_deriv.data_ptr<float>(), workspace.data_ptr(),
+        if (nnpops_pme_direct_frames((int)t.atoms, (int)t.frames, (int)t.tiles, (int)max_excl, t.data(), pos.data_ptr<float>(),
+                                     q.data_ptr<float>(), max_excl ? f.ex.data_ptr<int32_t>() : nullptr, f.box.data_ptr<float>(),
+                                     (float)f.cutoff, (float)f.alpha, (float)f.coulomb, f.energy.data_ptr<float>(),
+                                     f.pos_deriv.data_ptr<float>(), f.charge_deriv.data_ptr<float>(), workspace.data_ptr(),
                                      current_stream(positions.device())) != NNPOPS_OK)
             raise_last(qualified.c_str());
         if (box_grad) {
-            Tensor box_deriv = torch::empty({s.frames, 3, 3}, opts);
-            Tensor box_workspace = torch::empty({nnpops_pme_direct_frames_box_workspace_bytes((int)s.tiles)}, opts.dtype(torch::kUInt8));
-            if (nnpops_pme_direct_frames_box((int)s.atoms, (int)s.frames, (int)s.tiles, (int)max_excl, table.data_ptr<int32_t>(), pos.data_ptr<float>(),
-                                             q.data_ptr<float>(), max_excl ? ex.data_ptr<int32_t>() : nullptr, boxes.data_ptr<float>(),
-                                             (float)cutoff.toDouble(), (float)alpha.toDouble(), (float)coulomb.toDouble(),
-                                             box_deriv.data_ptr<float>(), box_workspace.data_ptr(), current_stream(positions.device())) != NNPOPS_OK)
+            f.box_deriv = torch::empty({t.frames, 3, 3}, opts);
+            Tensor box_workspace = torch::empty({nnpops_pme_direct_frames_box_workspace_bytes((int)t.tiles)}, opts.dtype(torch::kUInt8));
+            if (nnpops_pme_direct_frames_box((int)t.atoms, (int)t.frames, (int)t.tiles, (int)max_excl, t.data(), pos.data_ptr<float>(),
+                                             q.data_ptr<float>(), max_excl ? f.ex.data_ptr<int32_t>() : nullptr, f.box.data_ptr<float>(),
+                                             (float)f.cutoff, (float)f.alpha, (float)f.coulomb, f.box_deriv.data_ptr<float>(),
+                                             box_workspace.data_ptr(), current_stream(positions.device())) != NNPOPS_OK)
                 raise_last(qualified.c_str());
-            ctx->save_for_backward({pos_deriv, charge_deriv, table, box_deriv});
-        } else if (kept) {
-            *kept = {ex, boxes, pos_deriv, charge_deriv};
-        } else {
-            ctx->save_for_backward({pos_deriv, charge_deriv, table});
         }
-        return energies;
+        return f;
+    }
+
+    static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& exclusions,
+                          const Tensor& box_vectors, const Tensor& table, const torch::Scalar& cutoff, const torch::Scalar& alpha,
+                          const torch::Scalar& coulomb, bool box_op, bool box_grad) {
+        const PmeState f = run(box_op ? "pme_direct_frames_box" : "pme_direct_frames", positions, charges, exclusions, box_vectors, table, cutoff,
+                               alpha, coulomb, box_op, box_grad);
+        f.derivatives().save(ctx);
+        return f.energy;
     }
     static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) {
-        const auto saved = ctx->get_saved_variables();
-        const tensor_list g = pme_frames_scale(ctx->saved_data["box_op"].toBool() ? "pme_direct_frames_box" : "pme_direct_frames", saved[0], saved[1], saved[2], grad_outputs[0]);
-        return {g[0], g[1], Tensor(), pme_frames_box_scale(saved, grad_outputs[0]), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+        const PmeState s = PmeState::load(ctx);            // (box_vectors is the fourth of forward's ten arguments)
+        return pme_frames_backward(s.box_op ? "pme_direct_frames_box" : "pme_direct_frames", s, grad_outputs[0], 10, 3);
     }
 };
 
+// The middle of the frames' reciprocal passes, the forward's and the double backward's: real grids [B, Kx, Ky, Kz] -> transforms ->
+// the convolution in place -> the scaled complex grids; s: the boxes, alpha, the moduli and the workspace; what: who raises.
+// lds: the transforms and the convolution in one launch of pme_frames_fft.hip (the _lds ops) instead of the library transforms around
+// nnpops_pme_reciprocal_frames_convolve; that launch transforms back as well -- the potential grids take the real grids' place -- and
+// writes the scaled grids only when they are wanted.  box_workspace: wanted with the box gradient, which sums Pi from the scaled grids
+// into it before any inverse transform.
+Tensor pme_frames_convolve(const char* what, const PmeState& s, int n, const Tensor& real, const Tensor& energies, bool lds,
+                           Tensor* box_workspace, void* stream) {
+    const int B = (int)real.size(0), gx = (int)real.size(1), gy = (int)real.size(2), gz = (int)real.size(3), o = (int)s.order;
+    const float a = (float)s.alpha;
+    Tensor recip;
+    if (lds) {
+        if (box_workspace) recip = torch::empty({real.size(0), real.size(1), real.size(2), real.size(3) / 2 + 1}, real.options().dtype(torch::kComplexFloat));
+        if (nnpops_pme_reciprocal_frames_transform(n, B, gx, gy, gz, o, s.box.data_ptr<float>(), a, s.xm.data_ptr<float>(), s.ym.data_ptr<float>(),
+                                                   s.zm.data_ptr<float>(), real.data_ptr<float>(), real.data_ptr<float>(),
+                                                   box_workspace ? recip.data_ptr() : nullptr, energies.data_ptr<float>(), stream) != NNPOPS_OK)
+            raise_last(what);
+    } else {
+        recip = pme_frames_rfftn(real);
+        // (in the double backward the convolution's partial sums share the forward's workspace; the base indices and weights behind them stay)
+        if (nnpops_pme_reciprocal_frames_convolve(n, B, gx, gy, gz, o, s.box.data_ptr<float>(), a, s.xm.data_ptr<float>(), s.ym.data_ptr<float>(),
+                                                  s.zm.data_ptr<float>(), recip.data_ptr(), energies.data_ptr<float>(), s.workspace.data_ptr(),
+                                                  stream) != NNPOPS_OK)
+            raise_last(what);
+    }
+    if (box_workspace) {
+        const int64_t box_bytes = nnpops_pme_reciprocal_frames_box_workspace_bytes(B, gx, gy, gz);
+        if (box_bytes <= 0) raise_last(what);
+        *box_workspace = torch::empty({box_bytes}, real.options().dtype(torch::kUInt8));
+        if (nnpops_pme_reciprocal_frames_box_pi(n, B, gx, gy, gz, o, s.box.data_ptr<float>(), a, s.xm.data_ptr<float>(), s.ym.data_ptr<float>(),
+                                                s.zm.data_ptr<float>(), recip.data_ptr(), box_workspace->data_ptr(), stream) != NNPOPS_OK)
+            raise_last(what);
+    }
+    return recip;
+}
+
 class PmeReciprocalFramesFunction : public torch::autograd::Function<PmeReciprocalFramesFunction> {
 public:
-    static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table,
-                          const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz, const torch::Scalar& order,
-                          const torch::Scalar& alpha, const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli,
-                          const Tensor& zmoduli, bool box_op, bool box_grad, bool lds, tensor_list* kept = nullptr) {
-        // kept: the _twice op runs this forward and saves for itself (boxes, the workspace with the base indices and weights, the scaled
-        // complex grids, the moduli, dE/dpositions, dE/dcharges)
-        // lds: the transforms and the convolution in one launch of pme_frames_fft.hip (the _lds ops) instead of the library transforms
-        // around nnpops_pme_reciprocal_frames_convolve; everything before and after is the same.
-        const char* op = kept ? "pme_reciprocal_frames_twice" : lds ? (box_op ? "pme_reciprocal_frames_lds_box" : "pme_reciprocal_frames_lds") :
-                         box_op ? "pme_reciprocal_frames_box" : "pme_reciprocal_frames";
+    // the forward pass of the four pme_reciprocal_frames[_lds][_box] ops and of pme_reciprocal_frames_twice (op: which; it names itself
+    // when it raises): the energies; when a gradient is wanted dE/dpositions and dE/dcharges, and dE/dboxes with box_grad; the boxes and
+    // moduli as the kernels read them, the workspace with the base indices and weights, and the scaled complex grids
+    static PmeState run(const char* op, const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table,
+                        const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz, const torch::Scalar& order,
+                        const torch::Scalar& alpha, const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli,
+                        const Tensor& zmoduli, bool box_op, bool box_grad, bool lds) {
         const std::string qualified = std::string("pme::") + op;
-        ctx->saved_data["box_op"] = box_op;
-        const PmeFramesShape s = pme_frames_check(op, positions, charges, box_vectors, table, box_op);
+        const PmeFramesTable t = pme_frames_check(op, positions, charges, box_vectors, table, box_op);
         const std::vector<int64_t> K{gridx.toLong(), gridy.toLong(), gridz.toLong()};
         const int64_t o = order.toLong();
         TORCH_CHECK(K[0] >= 1 && K[1] >= 1 && K[2] >= 1, op, ": the grid dimensions must be positive");
@@ -3536,305 +3624,176 @@ public:
         for (int i = 0; i < 3; i++)
             TORCH_CHECK(moduli[i]->dim() == 1 && moduli[i]->size(0) == K[i] && moduli[i]->scalar_type() == torch::kFloat32 &&
                         moduli[i]->device() == positions.device(), op, ": the moduli must be float32 tensors of the grid's sizes on the device of positions");
-        const Tensor pos = positions.contiguous(), q = charges.contiguous(), boxes = box_vectors.contiguous(), xm = xmoduli.contiguous(),
-                     ym = ymoduli.contiguous(), zm = zmoduli.contiguous();
+        const Tensor pos = positions.contiguous(), q = charges.contiguous();
+        PmeState f;
+        f.box = box_vectors.contiguous(); f.table = table; f.xm = xmoduli.contiguous(); f.ym = ymoduli.contiguous(); f.zm = zmoduli.contiguous();
+        f.grid = K; f.order = o; f.alpha = a; f.coulomb = k; f.box_op = box_op;
         const auto opts = positions.options();
-        const int n = (int)s.atoms, B = (int)s.frames, gx = (int)K[0], gy = (int)K[1], gz = (int)K[2];
+        const int n = (int)t.atoms, B = (int)t.frames, gx = (int)K[0], gy = (int)K[1], gz = (int)K[2];
         c10::hip::HIPGuard guard(positions.device().index());
         void* stream = current_stream(positions.device());
         if (lds && nnpops_pme_reciprocal_frames_transform_lds_bytes(gx, gy, gz) == 0) raise_last(qualified.c_str());     // (before any launch)
         const int64_t bytes = nnpops_pme_reciprocal_frames_workspace_bytes(n, B, gx, gy, gz, (int)o);
         if (bytes <= 0) raise_last(qualified.c_str());
-        Tensor workspace = torch::empty({bytes}, opts.dtype(torch::kUInt8));
-        Tensor real = torch::empty({s.frames, K[0], K[1], K[2]}, opts);
-        if (nnpops_pme_reciprocal_frames_spread(n, B, (int)s.tiles, gx, gy, gz, (int)o, table.data_ptr<int32_t>(), pos.data_ptr<float>(),
-                                                q.data_ptr<float>(), boxes.data_ptr<float>(), (float)k, real.data_ptr<float>(),
-                                                workspace.data_ptr(), stream) != NNPOPS_OK)
+        f.workspace = torch::empty({bytes}, opts.dtype(torch::kUInt8));
+        Tensor real = torch::empty({t.frames, K[0], K[1], K[2]}, opts);
+        if (nnpops_pme_reciprocal_frames_spread(n, B, (int)t.tiles, gx, gy, gz, (int)o, t.data(), pos.data_ptr<float>(),
+                                                q.data_ptr<float>(), f.box.data_ptr<float>(), (float)k, real.data_ptr<float>(),
+                                                f.workspace.data_ptr(), stream) != NNPOPS_OK)
             raise_last(qualified.c_str());
-        Tensor recip;
-        Tensor energies = torch::empty({s.frames}, opts);
-        if (lds) {                                                 // the potential grids take the real grids' place
-            if (box_grad) recip = torch::empty({s.frames, K[0], K[1], K[2] / 2 + 1}, opts.dtype(torch::kComplexFloat));
-            if (nnpops_pme_reciprocal_frames_transform(n, B, gx, gy, gz, (int)o, boxes.data_ptr<float>(), (float)a, xm.data_ptr<float>(),
-                                                       ym.data_ptr<float>(), zm.data_ptr<float>(), real.data_ptr<float>(), real.data_ptr<float>(),
-                                                       box_grad ? recip.data_ptr() : nullptr, energies.data_ptr<float>(), stream) != NNPOPS_OK)
-                raise_last(qualified.c_str());
-        } else {
-            recip = pme_frames_rfftn(real);
-            if (nnpops_pme_reciprocal_frames_convolve(n, B, gx, gy, gz, (int)o, boxes.data_ptr<float>(), (float)a, xm.data_ptr<float>(),
-                                                      ym.data_ptr<float>(), zm.data_ptr<float>(), recip.data_ptr(), energies.data_ptr<float>(),
-                                                      workspace.data_ptr(), stream) != NNPOPS_OK)
-                raise_last(qualified.c_str());
-        }
+        f.energy = torch::empty({t.frames}, opts);
         Tensor box_workspace;
-        if (box_grad) {                                            // Pi from the scaled grids, before the inverse transform
-            const int64_t box_bytes = nnpops_pme_reciprocal_frames_box_workspace_bytes(B, gx, gy, gz);
-            if (box_bytes <= 0) raise_last(qualified.c_str());
-            box_workspace = torch::empty({box_bytes}, opts.dtype(torch::kUInt8));
-            if (nnpops_pme_reciprocal_frames_box_pi(n, B, gx, gy, gz, (int)o, boxes.data_ptr<float>(), (float)a, xm.data_ptr<float>(),
-                                                    ym.data_ptr<float>(), zm.data_ptr<float>(), recip.data_ptr(), box_workspace.data_ptr(),
-                                                    stream) != NNPOPS_OK)
-                raise_last(qualified.c_str());
-        }
+        f.recip = pme_frames_convolve(qualified.c_str(), f, n, real, f.energy, lds, box_grad ? &box_workspace : nullptr, stream);
         if (positions.requires_grad() || charges.requires_grad() || box_grad) {     // (X needs the interpolated dE/dpositions)
-            const Tensor grid = lds ? real : pme_frames_irfftn(recip, K[2]).contiguous();
-            Tensor pos_deriv = torch::empty({s.atoms, 3}, opts), charge_deriv = torch::empty({s.atoms}, opts);
-            if (nnpops_pme_reciprocal_frames_interpolate(n, B, gx, gy, gz, (int)o, q.data_ptr<float>(), boxes.data_ptr<float>(), (float)k,
-                                                         grid.data_ptr<float>(), pos_deriv.data_ptr<float>(), charge_deriv.data_ptr<float>(),
-                                                         workspace.data_ptr(), stream) != NNPOPS_OK)
+            const Tensor grid = lds ? real : pme_frames_irfftn(f.recip, K[2]).contiguous();
+            f.pos_deriv = torch::empty({t.atoms, 3}, opts);
+            f.charge_deriv = torch::empty({t.atoms}, opts);
+            if (nnpops_pme_reciprocal_frames_interpolate(n, B, gx, gy, gz, (int)o, q.data_ptr<float>(), f.box.data_ptr<float>(), (float)k,
+                                                         grid.data_ptr<float>(), f.pos_deriv.data_ptr<float>(), f.charge_deriv.data_ptr<float>(),
+                                                         f.workspace.data_ptr(), stream) != NNPOPS_OK)
                 raise_last(qualified.c_str());
             if (box_grad) {
-                Tensor box_deriv = torch::empty({s.frames, 3, 3}, opts);
-                if (nnpops_pme_reciprocal_frames_box_gradient(n, B, gx, gy, gz, (int)o, table.data_ptr<int32_t>(), pos.data_ptr<float>(),
-                                                              pos_deriv.data_ptr<float>(), boxes.data_ptr<float>(), box_deriv.data_ptr<float>(),
+                f.box_deriv = torch::empty({t.frames, 3, 3}, opts);
+                if (nnpops_pme_reciprocal_frames_box_gradient(n, B, gx, gy, gz, (int)o, t.data(), pos.data_ptr<float>(),
+                                                              f.pos_deriv.data_ptr<float>(), f.box.data_ptr<float>(), f.box_deriv.data_ptr<float>(),
                                                               box_workspace.data_ptr(), stream) != NNPOPS_OK)
                     raise_last(qualified.c_str());
-                ctx->save_for_backward({pos_deriv, charge_deriv, table, box_deriv});
-            } else if (kept) {
-                *kept = {boxes, workspace, recip, xm, ym, zm, pos_deriv, charge_deriv};
-            } else {
-                ctx->save_for_backward({pos_deriv, charge_deriv, table});
             }
         }
-        return energies;
+        return f;
+    }
+
+    static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table,
+                          const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz, const torch::Scalar& order,
+                          const torch::Scalar& alpha, const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli,
+                          const Tensor& zmoduli, bool box_op, bool box_grad, bool lds) {
+        const char* op = lds ? (box_op ? "pme_reciprocal_frames_lds_box" : "pme_reciprocal_frames_lds") :
+                         box_op ? "pme_reciprocal_frames_box" : "pme_reciprocal_frames";
+        const PmeState f = run(op, positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha, coulomb, xmoduli, ymoduli, zmoduli,
+                               box_op, box_grad, lds);
+        f.derivatives().save(ctx);
+        return f.energy;
     }
     static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) {
-        const auto saved = ctx->get_saved_variables();
-        const tensor_list g = pme_frames_scale(ctx->saved_data["box_op"].toBool() ? "pme_reciprocal_frames_box" : "pme_reciprocal_frames", saved[0], saved[1], saved[2], grad_outputs[0]);
-        return {g[0], g[1], pme_frames_box_scale(saved, grad_outputs[0]), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(),
-                Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+        const PmeState s = PmeState::load(ctx);            // (box_vectors is the third of forward's sixteen arguments)
+        return pme_frames_backward(s.box_op ? "pme_reciprocal_frames_box" : "pme_reciprocal_frames", s, grad_outputs[0], 16, 2);
     }
 };
 
+// The entries of the frames ops, one instance for every op.  (A Function's forward runs with grad mode off: what depends on it is decided here.)
+template <bool box_op>
 Tensor pme_direct_frames_entry(const Tensor& positions, const Tensor& charges, const Tensor& exclusions, const Tensor& box_vectors,
                                const Tensor& table, const torch::Scalar& cutoff, const torch::Scalar& alpha, const torch::Scalar& coulomb) {
-    return PmeDirectFramesFunction::apply(positions, charges, exclusions, box_vectors, table, cutoff, alpha, coulomb, false, false);
+    return PmeDirectFramesFunction::apply(positions, charges, exclusions, box_vectors, table, cutoff, alpha, coulomb, box_op,
+                                          box_op && box_vectors.requires_grad() && torch::GradMode::is_enabled());
 }
-Tensor pme_direct_frames_box_entry(const Tensor& positions, const Tensor& charges, const Tensor& exclusions, const Tensor& box_vectors,
-                                   const Tensor& table, const torch::Scalar& cutoff, const torch::Scalar& alpha, const torch::Scalar& coulomb) {
-    return PmeDirectFramesFunction::apply(positions, charges, exclusions, box_vectors, table, cutoff, alpha, coulomb, true,
-                                          box_vectors.requires_grad() && torch::GradMode::is_enabled());
-}
+// lds: the same ops with the transforms and the convolution in the LDS of one workgroup per frame (pme_frames_fft.hip)
+template <bool box_op, bool lds>
 Tensor pme_reciprocal_frames_entry(const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table,
                                    const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz, const torch::Scalar& order,
                                    const torch::Scalar& alpha, const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli,
                                    const Tensor& zmoduli) {
     return PmeReciprocalFramesFunction::apply(positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha, coulomb, xmoduli,
-                                              ymoduli, zmoduli, false, false, false);
+                                              ymoduli, zmoduli, box_op, box_op && box_vectors.requires_grad() && torch::GradMode::is_enabled(), lds);
 }
-Tensor pme_reciprocal_frames_box_entry(const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table,
-                                       const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz,
-                                       const torch::Scalar& order, const torch::Scalar& alpha, const torch::Scalar& coulomb,
-                                       const Tensor& xmoduli, const Tensor& ymoduli, const Tensor& zmoduli) {
-    return PmeReciprocalFramesFunction::apply(positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha, coulomb, xmoduli,
-                                              ymoduli, zmoduli, true, box_vectors.requires_grad() && torch::GradMode::is_enabled(), false);
-}
-// the same two ops with the transforms and the convolution in the LDS of one workgroup per frame (pme_frames_fft.hip)
-Tensor pme_reciprocal_frames_lds_entry(const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table,
-                                       const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz,
-                                       const torch::Scalar& order, const torch::Scalar& alpha, const torch::Scalar& coulomb,
-                                       const Tensor& xmoduli, const Tensor& ymoduli, const Tensor& zmoduli) {
-    return PmeReciprocalFramesFunction::apply(positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha, coulomb, xmoduli,
-                                              ymoduli, zmoduli, false, false, true);
-}
-Tensor pme_reciprocal_frames_lds_box_entry(const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table,
-                                           const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz,
-                                           const torch::Scalar& order, const torch::Scalar& alpha, const torch::Scalar& coulomb,
-                                           const Tensor& xmoduli, const Tensor& ymoduli, const Tensor& zmoduli) {
-    return PmeReciprocalFramesFunction::apply(positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha, coulomb, xmoduli,
-                                              ymoduli, zmoduli, true, box_vectors.requires_grad() && torch::GradMode::is_enabled(), true);
-}
+
 // ---------------------------------------------------------------------------------------------
 // pme_direct_frames_twice / pme_reciprocal_frames_twice: the forwards above, unchanged (energies, dE/dpositions and dE/dcharges are the
-// bits of pme_direct_frames / pme_reciprocal_frames), with a RECORDED backward that can be differentiated once more with respect to
-// positions and charges (pme_frames_second_order.hip):
-//     Pme*FramesBackwardFunction        g [B] -> g_m P, g_m C through pme_frames_scale, as the default ops' backward
-//     Pme*FramesDoubleBackwardFunction  (v, w) -> dL/dx [N, 3], dL/dq [N] (already times g_m), dL/dg [B]
-// No box gradient and no third derivative: both raise.
+// bits of pme_direct_frames / pme_reciprocal_frames), behind the recorded chain (PmeDirectFramesTerm, PmeReciprocalFramesTerm;
+// pme_frames_second_order.hip):
+//     first_order   g [B] -> g_m P, g_m C through pme_frames_scale, as the default ops' backward
+//     second_order  (v, w) -> dL/dx [N, 3], dL/dq [N] (already times g_m), dL/dg [B]
 // ---------------------------------------------------------------------------------------------
-int64_t pme_frames_tiles(const Tensor& table, int64_t frames, int64_t atoms) { return (table.numel() - 4 - 2 * (frames + 1) - atoms) / 4; }
-
 // a cotangent as the kernels read it: float32, contiguous, zeros when autograd passed none
 Tensor pme_frames_cotangent(const Tensor& t, const Tensor& like) {
     return t.defined() ? t.to(torch::kFloat32).contiguous() : torch::zeros_like(like);
 }
 
-Tensor pme_frames_upstream_grad(const char* op, const Tensor& v, const Tensor& w, const Tensor& pos_deriv, const Tensor& charge_deriv,
-                                const Tensor& table, const Tensor& g) {
-    Tensor gg = torch::empty({g.numel()}, pos_deriv.options());
-    if (nnpops_pme_frames_upstream_grad((int)charge_deriv.size(0), (int)g.numel(), table.data_ptr<int32_t>(), v.data_ptr<float>(),
-                                        w.data_ptr<float>(), pos_deriv.data_ptr<float>(), charge_deriv.data_ptr<float>(), gg.data_ptr<float>(),
-                                        current_stream(pos_deriv.device())) != NNPOPS_OK)
+Tensor pme_frames_upstream_grad(const char* op, const Tensor& v, const Tensor& w, const PmeState& s, const Tensor& g) {
+    Tensor gg = torch::empty({g.numel()}, s.pos_deriv.options());
+    if (nnpops_pme_frames_upstream_grad((int)s.charge_deriv.size(0), (int)g.numel(), s.table.data_ptr<int32_t>(), v.data_ptr<float>(),
+                                        w.data_ptr<float>(), s.pos_deriv.data_ptr<float>(), s.charge_deriv.data_ptr<float>(), gg.data_ptr<float>(),
+                                        current_stream(s.pos_deriv.device())) != NNPOPS_OK)
         raise_last(op);
     return gg.reshape(g.sizes()).to(g.scalar_type());
 }
 
-class PmeDirectFramesDoubleBackwardFunction : public torch::autograd::Function<PmeDirectFramesDoubleBackwardFunction> {
-public:
-    static tensor_list forward(AutogradContext*, const Tensor& v_in, const Tensor& w_in, const Tensor& g_in, const Tensor& positions,
-                               const Tensor& charges, const Tensor& ex, const Tensor& boxes, const Tensor& table, const Tensor& pos_deriv,
-                               const Tensor& charge_deriv, double cutoff, double alpha, double k) {
-        const char* op = "pme::pme_direct_frames_twice (double backward)";
-        const Tensor v = pme_frames_cotangent(v_in, pos_deriv), w = pme_frames_cotangent(w_in, charge_deriv);
-        const Tensor g = g_in.to(torch::kFloat32).contiguous(), pos = positions.contiguous(), q = charges.contiguous();
-        const int64_t n = q.size(0), frames = boxes.size(0), tiles = pme_frames_tiles(table, frames, n), max_excl = ex.size(1);
-        Tensor gx = torch::empty({n, 3}, q.options()), gq = torch::empty({n}, q.options());
-        Tensor workspace = torch::empty({nnpops_pme_direct_frames_double_backward_workspace_bytes((int)tiles)}, q.options().dtype(torch::kUInt8));
+struct PmeDirectFramesTerm {
+    static constexpr const char* op = "pme_direct_frames_twice";
+    static constexpr size_t arguments = 8;
+
+    static PmeState run(const Tensor& positions, const Tensor& charges, const Tensor& exclusions, const Tensor& box_vectors, const Tensor& table,
+                        const torch::Scalar& cutoff, const torch::Scalar& alpha, const torch::Scalar& coulomb) {
+        return PmeDirectFramesFunction::run(op, positions, charges, exclusions, box_vectors, table, cutoff, alpha, coulomb, false, false);
+    }
+
+    static tensor_list first_order(PmeState& s, const Tensor& g) { return pme_frames_scale(op, s.pos_deriv, s.charge_deriv, s.table, g); }
+
+    static tensor_list second_order(const PmeState& s, const Tensor& v_in, const Tensor& w_in, const Tensor& g_in) {
+        const char* what = "pme::pme_direct_frames_twice (double backward)";
+        const Tensor v = pme_frames_cotangent(v_in, s.pos_deriv), w = pme_frames_cotangent(w_in, s.charge_deriv);
+        const Tensor g = g_in.to(torch::kFloat32).contiguous(), pos = s.positions.contiguous(), q = s.charges.contiguous();
+        const PmeFramesTable t(s.table, s.box.size(0), q.size(0));
+        const int64_t max_excl = s.ex.size(1);
+        Tensor gx = torch::empty({t.atoms, 3}, q.options()), gq = torch::empty({t.atoms}, q.options());
+        Tensor workspace = torch::empty({nnpops_pme_direct_frames_double_backward_workspace_bytes((int)t.tiles)}, q.options().dtype(torch::kUInt8));
         c10::hip::HIPGuard guard(q.device().index());
-        if (nnpops_pme_direct_frames_double_backward((int)n, (int)frames, (int)tiles, (int)max_excl, table.data_ptr<int32_t>(), pos.data_ptr<float>(),
-                                                     q.data_ptr<float>(), max_excl ? ex.data_ptr<int32_t>() : nullptr, boxes.data_ptr<float>(),
-                                                     v.data_ptr<float>(), w.data_ptr<float>(), g.data_ptr<float>(), (float)cutoff, (float)alpha,
-                                                     (float)k, gx.data_ptr<float>(), gq.data_ptr<float>(), workspace.data_ptr(),
+        if (nnpops_pme_direct_frames_double_backward((int)t.atoms, (int)t.frames, (int)t.tiles, (int)max_excl, t.data(), pos.data_ptr<float>(),
+                                                     q.data_ptr<float>(), max_excl ? s.ex.data_ptr<int32_t>() : nullptr, s.box.data_ptr<float>(),
+                                                     v.data_ptr<float>(), w.data_ptr<float>(), g.data_ptr<float>(), (float)s.cutoff, (float)s.alpha,
+                                                     (float)s.coulomb, gx.data_ptr<float>(), gq.data_ptr<float>(), workspace.data_ptr(),
                                                      current_stream(q.device())) != NNPOPS_OK)
-            raise_last(op);
-        return {gx, gq, pme_frames_upstream_grad(op, v, w, pos_deriv, charge_deriv, table, g_in)};
-    }
-    static tensor_list backward(AutogradContext*, tensor_list) {
-        TORCH_CHECK(false, "pme_direct_frames_twice: third derivatives are not implemented");
-        return {};
+            raise_last(what);
+        return {gx, gq, pme_frames_upstream_grad(what, v, w, s, g_in)};
     }
 };
 
-class PmeDirectFramesBackwardFunction : public torch::autograd::Function<PmeDirectFramesBackwardFunction> {
-public:
-    static tensor_list forward(AutogradContext* ctx, const Tensor& g, const Tensor& positions, const Tensor& charges, const Tensor& ex,
-                               const Tensor& boxes, const Tensor& table, const Tensor& pos_deriv, const Tensor& charge_deriv, double cutoff,
-                               double alpha, double k) {
-        ctx->save_for_backward({g, positions, charges, ex, boxes, table, pos_deriv, charge_deriv});
-        ctx->saved_data["cutoff"] = cutoff;
-        ctx->saved_data["alpha"] = alpha;
-        ctx->saved_data["coulomb"] = k;
-        return pme_frames_scale("pme_direct_frames_twice", pos_deriv, charge_deriv, table, g);
-    }
-    static tensor_list backward(AutogradContext* ctx, tensor_list grads) {
-        const auto s = ctx->get_saved_variables();
-        const tensor_list d = PmeDirectFramesDoubleBackwardFunction::apply(grads[0], grads[1], s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7],
-                                                                           ctx->saved_data["cutoff"].toDouble(), ctx->saved_data["alpha"].toDouble(),
-                                                                           ctx->saved_data["coulomb"].toDouble());
-        return {d[2], d[0], d[1], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
-    }
-};
+struct PmeReciprocalFramesTerm {
+    static constexpr const char* op = "pme_reciprocal_frames_twice";
+    static constexpr size_t arguments = 13;
 
-class PmeDirectFramesTwiceFunction : public torch::autograd::Function<PmeDirectFramesTwiceFunction> {
-public:
-    static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& exclusions,
-                          const Tensor& box_vectors, const Tensor& table, const torch::Scalar& cutoff, const torch::Scalar& alpha,
-                          const torch::Scalar& coulomb) {
-        tensor_list kept;
-        const Tensor energies = PmeDirectFramesFunction::forward(ctx, positions, charges, exclusions, box_vectors, table, cutoff, alpha, coulomb,
-                                                                 false, false, &kept);
-        ctx->save_for_backward({positions, charges, kept[0], kept[1], table, kept[2], kept[3]});
-        ctx->saved_data["cutoff"] = cutoff.toDouble();
-        ctx->saved_data["alpha"] = alpha.toDouble();
-        ctx->saved_data["coulomb"] = coulomb.toDouble();
-        return energies;
+    static PmeState run(const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table, const torch::Scalar& gridx,
+                        const torch::Scalar& gridy, const torch::Scalar& gridz, const torch::Scalar& order, const torch::Scalar& alpha,
+                        const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli, const Tensor& zmoduli) {
+        return PmeReciprocalFramesFunction::run(op, positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha, coulomb, xmoduli,
+                                                ymoduli, zmoduli, false, false, false);
     }
-    static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) {
-        const auto s = ctx->get_saved_variables();
-        const tensor_list d = PmeDirectFramesBackwardFunction::apply(grad_outputs[0], s[0], s[1], s[2], s[3], s[4], s[5], s[6],
-                                                                     ctx->saved_data["cutoff"].toDouble(), ctx->saved_data["alpha"].toDouble(),
-                                                                     ctx->saved_data["coulomb"].toDouble());
-        return {d[0], d[1], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
-    }
-};
 
-class PmeRecipFramesDoubleBackwardFunction : public torch::autograd::Function<PmeRecipFramesDoubleBackwardFunction> {
-public:
-    static tensor_list forward(AutogradContext*, const Tensor& v_in, const Tensor& w_in, const Tensor& g_in, const Tensor& positions,
-                               const Tensor& charges, const Tensor& boxes, const Tensor& table, const Tensor& workspace, const Tensor& recip,
-                               const Tensor& xm, const Tensor& ym, const Tensor& zm, const Tensor& pos_deriv, const Tensor& charge_deriv,
-                               std::vector<int64_t> K, int64_t pme_order, double alpha, double k) {
-        const char* op = "pme::pme_reciprocal_frames_twice (double backward)";
-        const Tensor v = pme_frames_cotangent(v_in, pos_deriv), w = pme_frames_cotangent(w_in, charge_deriv);
-        const Tensor g = g_in.to(torch::kFloat32).contiguous(), pos = positions.contiguous(), q = charges.contiguous();
-        const int n = (int)q.size(0), B = (int)boxes.size(0), tiles = (int)pme_frames_tiles(table, B, n);
-        const int gx = (int)K[0], gy = (int)K[1], gz = (int)K[2], o = (int)pme_order;
+    static tensor_list first_order(PmeState& s, const Tensor& g) { return pme_frames_scale(op, s.pos_deriv, s.charge_deriv, s.table, g); }
+
+    static tensor_list second_order(const PmeState& s, const Tensor& v_in, const Tensor& w_in, const Tensor& g_in) {
+        const char* what = "pme::pme_reciprocal_frames_twice (double backward)";
+        const Tensor v = pme_frames_cotangent(v_in, s.pos_deriv), w = pme_frames_cotangent(w_in, s.charge_deriv);
+        const Tensor g = g_in.to(torch::kFloat32).contiguous(), pos = s.positions.contiguous(), q = s.charges.contiguous();
+        const PmeFramesTable t(s.table, s.box.size(0), q.size(0));
+        const std::vector<int64_t>& K = s.grid;
+        const int n = (int)t.atoms, B = (int)t.frames, gx = (int)K[0], gy = (int)K[1], gz = (int)K[2], o = (int)s.order;
         const auto opts = q.options();
         Tensor grad_x = torch::empty({n, 3}, opts), grad_q = torch::empty({n}, opts);
         c10::hip::HIPGuard guard(q.device().index());
         void* stream = current_stream(q.device());
         const int64_t bytes = nnpops_pme_reciprocal_frames_second_workspace_bytes(n, B, gx, gy, gz, o);
-        if (bytes <= 0) raise_last(op);
+        if (bytes <= 0) raise_last(what);
         Tensor second = torch::empty({bytes}, opts.dtype(torch::kUInt8));
         Tensor real = torch::empty({(int64_t)B, K[0], K[1], K[2]}, opts);
-        if (nnpops_pme_reciprocal_frames_spread_directional(n, B, tiles, gx, gy, gz, o, table.data_ptr<int32_t>(), pos.data_ptr<float>(),
-                                                            q.data_ptr<float>(), boxes.data_ptr<float>(), (float)k, v.data_ptr<float>(),
-                                                            w.data_ptr<float>(), real.data_ptr<float>(), workspace.data_ptr(), second.data_ptr(),
+        if (nnpops_pme_reciprocal_frames_spread_directional(n, B, (int)t.tiles, gx, gy, gz, o, t.data(), pos.data_ptr<float>(),
+                                                            q.data_ptr<float>(), s.box.data_ptr<float>(), (float)s.coulomb, v.data_ptr<float>(),
+                                                            w.data_ptr<float>(), real.data_ptr<float>(), s.workspace.data_ptr(), second.data_ptr(),
                                                             stream) != NNPOPS_OK)
-            raise_last(op);
-        Tensor recip2 = pme_frames_rfftn(real);
-        Tensor unused = torch::empty({(int64_t)B}, opts);
-        // (the convolution's partial sums share the forward's workspace; the base indices and weights behind them stay)
-        if (nnpops_pme_reciprocal_frames_convolve(n, B, gx, gy, gz, o, boxes.data_ptr<float>(), (float)alpha, xm.data_ptr<float>(),
-                                                  ym.data_ptr<float>(), zm.data_ptr<float>(), recip2.data_ptr(), unused.data_ptr<float>(),
-                                                  workspace.data_ptr(), stream) != NNPOPS_OK)
-            raise_last(op);
+            raise_last(what);
+        const Tensor recip2 = pme_frames_convolve(what, s, n, real, torch::empty({(int64_t)B}, opts), false, nullptr, stream);
         // Both potential grids are transformed back in double and rounded to float once: the interpolation differences them twice, and
         // the float transform's error grew there with the square of the grid size.
         auto back = [&](const Tensor& c) {
             return pme_frames_irfftn(c.to(torch::kComplexDouble), K[2]).to(torch::kFloat).contiguous();
         };
-        const Tensor phi = back(recip), phi2 = back(recip2);
-        if (nnpops_pme_reciprocal_frames_interpolate_second(n, B, gx, gy, gz, o, q.data_ptr<float>(), boxes.data_ptr<float>(), (float)k,
+        const Tensor phi = back(s.recip), phi2 = back(recip2);
+        if (nnpops_pme_reciprocal_frames_interpolate_second(n, B, gx, gy, gz, o, q.data_ptr<float>(), s.box.data_ptr<float>(), (float)s.coulomb,
                                                             w.data_ptr<float>(), g.data_ptr<float>(), phi.data_ptr<float>(), phi2.data_ptr<float>(),
-                                                            grad_x.data_ptr<float>(), grad_q.data_ptr<float>(), workspace.data_ptr(),
+                                                            grad_x.data_ptr<float>(), grad_q.data_ptr<float>(), s.workspace.data_ptr(),
                                                             second.data_ptr(), stream) != NNPOPS_OK)
-            raise_last(op);
-        return {grad_x, grad_q, pme_frames_upstream_grad(op, v, w, pos_deriv, charge_deriv, table, g_in)};
-    }
-    static tensor_list backward(AutogradContext*, tensor_list) {
-        TORCH_CHECK(false, "pme_reciprocal_frames_twice: third derivatives are not implemented");
-        return {};
-    }
-};
-
-class PmeRecipFramesBackwardFunction : public torch::autograd::Function<PmeRecipFramesBackwardFunction> {
-public:
-    static tensor_list forward(AutogradContext* ctx, const Tensor& g, const Tensor& positions, const Tensor& charges, const Tensor& boxes,
-                               const Tensor& table, const Tensor& workspace, const Tensor& recip, const Tensor& xm, const Tensor& ym,
-                               const Tensor& zm, const Tensor& pos_deriv, const Tensor& charge_deriv, std::vector<int64_t> K, int64_t pme_order,
-                               double alpha, double k) {
-        ctx->save_for_backward({g, positions, charges, boxes, table, workspace, recip, xm, ym, zm, pos_deriv, charge_deriv});
-        ctx->saved_data["grid"] = K;
-        ctx->saved_data["order"] = pme_order;
-        ctx->saved_data["alpha"] = alpha;
-        ctx->saved_data["coulomb"] = k;
-        return pme_frames_scale("pme_reciprocal_frames_twice", pos_deriv, charge_deriv, table, g);
-    }
-    static tensor_list backward(AutogradContext* ctx, tensor_list grads) {
-        const auto s = ctx->get_saved_variables();
-        const tensor_list d = PmeRecipFramesDoubleBackwardFunction::apply(grads[0], grads[1], s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], s[8],
-                                                                          s[9], s[10], s[11], ctx->saved_data["grid"].toIntVector(),
-                                                                          ctx->saved_data["order"].toInt(), ctx->saved_data["alpha"].toDouble(),
-                                                                          ctx->saved_data["coulomb"].toDouble());
-        return {d[2], d[0], d[1], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(),
-                Tensor(), Tensor()};
-    }
-};
-
-class PmeReciprocalFramesTwiceFunction : public torch::autograd::Function<PmeReciprocalFramesTwiceFunction> {
-public:
-    static Tensor forward(AutogradContext* ctx, const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table,
-                          const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz, const torch::Scalar& order,
-                          const torch::Scalar& alpha, const torch::Scalar& coulomb, const Tensor& xmoduli, const Tensor& ymoduli,
-                          const Tensor& zmoduli) {
-        tensor_list kept;
-        const Tensor energies = PmeReciprocalFramesFunction::forward(ctx, positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha,
-                                                                     coulomb, xmoduli, ymoduli, zmoduli, false, false, false, &kept);
-        if (!kept.empty())                                          // (positions or charges require a gradient)
-            ctx->save_for_backward({positions, charges, kept[0], table, kept[1], kept[2], kept[3], kept[4], kept[5], kept[6], kept[7]});
-        ctx->saved_data["grid"] = std::vector<int64_t>{gridx.toLong(), gridy.toLong(), gridz.toLong()};
-        ctx->saved_data["order"] = order.toLong();
-        ctx->saved_data["alpha"] = alpha.toDouble();
-        ctx->saved_data["coulomb"] = coulomb.toDouble();
-        return energies;
-    }
-    static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs) {
-        const auto s = ctx->get_saved_variables();
-        const tensor_list d = PmeRecipFramesBackwardFunction::apply(grad_outputs[0], s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], s[8], s[9], s[10],
-                                                                    ctx->saved_data["grid"].toIntVector(), ctx->saved_data["order"].toInt(),
-                                                                    ctx->saved_data["alpha"].toDouble(), ctx->saved_data["coulomb"].toDouble());
-        return {d[0], d[1], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+            raise_last(what);
+        return {grad_x, grad_q, pme_frames_upstream_grad(what, v, w, s, g_in)};
     }
 };
 
@@ -3846,15 +3805,15 @@ void pme_frames_twice_check_box(const char* op, const Tensor& box_vectors) {
 Tensor pme_direct_frames_twice_entry(const Tensor& positions, const Tensor& charges, const Tensor& exclusions, const Tensor& box_vectors,
                                      const Tensor& table, const torch::Scalar& cutoff, const torch::Scalar& alpha, const torch::Scalar& coulomb) {
     pme_frames_twice_check_box("pme_direct_frames_twice", box_vectors);
-    return PmeDirectFramesTwiceFunction::apply(positions, charges, exclusions, box_vectors, table, cutoff, alpha, coulomb);
+    return PmeTwiceFunction<PmeDirectFramesTerm>::apply(positions, charges, exclusions, box_vectors, table, cutoff, alpha, coulomb);
 }
 Tensor pme_reciprocal_frames_twice_entry(const Tensor& positions, const Tensor& charges, const Tensor& box_vectors, const Tensor& table,
                                          const torch::Scalar& gridx, const torch::Scalar& gridy, const torch::Scalar& gridz,
                                          const torch::Scalar& order, const torch::Scalar& alpha, const torch::Scalar& coulomb,
                                          const Tensor& xmoduli, const Tensor& ymoduli, const Tensor& zmoduli) {
     pme_frames_twice_check_box("pme_reciprocal_frames_twice", box_vectors);
-    return PmeReciprocalFramesTwiceFunction::apply(positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha, coulomb, xmoduli,
-                                                   ymoduli, zmoduli);
+    return PmeTwiceFunction<PmeReciprocalFramesTerm>::apply(positions, charges, box_vectors, table, gridx, gridy, gridz, order, alpha, coulomb,
+                                                            xmoduli, ymoduli, zmoduli);
 }
 TORCH_LIBRARY_FRAGMENT(pme, m) {
     m.def("pmeFramesTable(Tensor offsets, Device device) -> Tensor", pme_frames_table_entry);
@@ -3877,22 +3836,22 @@ TORCH_LIBRARY_FRAGMENT(pme, m) {
           "Scalar gridz, Scalar order, Scalar alpha, Scalar coulomb, Tensor xmoduli, Tensor ymoduli, Tensor zmoduli) -> Tensor");
 }
 TORCH_LIBRARY_IMPL(pme, AutogradCUDA, m) {
-    m.impl("pme_direct_frames", pme_direct_frames_entry);
-    m.impl("pme_reciprocal_frames", pme_reciprocal_frames_entry);
-    m.impl("pme_direct_frames_box", pme_direct_frames_box_entry);
-    m.impl("pme_reciprocal_frames_box", pme_reciprocal_frames_box_entry);
-    m.impl("pme_reciprocal_frames_lds", pme_reciprocal_frames_lds_entry);
-    m.impl("pme_reciprocal_frames_lds_box", pme_reciprocal_frames_lds_box_entry);
+    m.impl("pme_direct_frames", pme_direct_frames_entry<false>);
+    m.impl("pme_reciprocal_frames", pme_reciprocal_frames_entry<false, false>);
+    m.impl("pme_direct_frames_box", pme_direct_frames_entry<true>);
+    m.impl("pme_reciprocal_frames_box", pme_reciprocal_frames_entry<true, false>);
+    m.impl("pme_reciprocal_frames_lds", pme_reciprocal_frames_entry<false, true>);
+    m.impl("pme_reciprocal_frames_lds_box", pme_reciprocal_frames_entry<true, true>);
     m.impl("pme_direct_frames_twice", pme_direct_frames_twice_entry);
     m.impl("pme_reciprocal_frames_twice", pme_reciprocal_frames_twice_entry);
 }
 TORCH_LIBRARY_IMPL(pme, CUDA, m) {
-    m.impl("pme_direct_frames", pme_direct_frames_entry);
-    m.impl("pme_reciprocal_frames", pme_reciprocal_frames_entry);
-    m.impl("pme_direct_frames_box", pme_direct_frames_box_entry);
-    m.impl("pme_reciprocal_frames_box", pme_reciprocal_frames_box_entry);
-    m.impl("pme_reciprocal_frames_lds", pme_reciprocal_frames_lds_entry);
-    m.impl("pme_reciprocal_frames_lds_box", pme_reciprocal_frames_lds_box_entry);
+    m.impl("pme_direct_frames", pme_direct_frames_entry<false>);
+    m.impl("pme_reciprocal_frames", pme_reciprocal_frames_entry<false, false>);
+    m.impl("pme_direct_frames_box", pme_direct_frames_entry<true>);
+    m.impl("pme_reciprocal_frames_box", pme_reciprocal_frames_entry<true, false>);
+    m.impl("pme_reciprocal_frames_lds", pme_reciprocal_frames_entry<false, true>);
+    m.impl("pme_reciprocal_frames_lds_box", pme_reciprocal_frames_entry<true, true>);
     m.impl("pme_direct_frames_twice", pme_direct_frames_twice_entry);
     m.impl("pme_reciprocal_frames_twice", pme_reciprocal_frames_twice_entry);
 }
